@@ -87,7 +87,38 @@ def parse():
     ap.add_argument("--n1-reference", default="auto", choices=["auto", "on", "off"],
                     help="--gpus N > 1 started without a launcher: also run the per-GPU workload on one GPU first and report "
                          "parallel_efficiency_vs_n1 (auto: weak scaling only - a strong-scaling N = 1 run of 512^3 is its own job)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="single-GPU path: after the timed steps write what the last timed solve returned as DIR/<name>.npy "
+                         "(float64): resvec, and x - or, when x holds more than 2^21 values, x at a fixed seeded sample of its "
+                         "rows (x_rows.npy holds their indices)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded_path or args.ghost_dry):
+        ap.error("--dump-outputs is defined for the single-GPU path (--gpus 1)")
+    return args
+
+
+DUMP_MAX_VALUES = 1 << 21      # x values written by --dump-outputs: 16 MiB, and as much again for the sampled row indices
+
+
+def dump_outputs(out_dir, x, resvec, torch):
+    """Write the arrays a caller of the timed path receives (h.solve_dev: x updated in place, resvec returned) as float64
+    .npy files.  x of more than DUMP_MAX_VALUES values is sampled at rows drawn once from default_rng(0) (sorted), so
+    that the same arguments give the same rows on every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = x.shape[0]
+    nrhs = 1 if x.dim() == 1 else x.shape[1]
+    files = {"resvec": np.asarray(resvec, dtype=np.float64)}
+    if n * nrhs <= DUMP_MAX_VALUES:
+        files["x"] = x.double().cpu().numpy()
+    else:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_VALUES // nrhs, replace=False))
+        files["x"] = x[torch.from_numpy(rows).to(x.device)].double().cpu().numpy()
+        files["x_rows"] = rows.astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    log("[bench] outputs of the last timed step: " + ", ".join(f"{k}{list(v.shape)}" for k, v in files.items()) + f" -> {out_dir}")
 
 
 def visible_gpus():
@@ -444,6 +475,8 @@ def main():
         barrier()
         region.append(time.perf_counter() - t0)
         assert iters == K
+    if args.dump_outputs:      # (before the instrumented pass below solves into x again)
+        dump_outputs(args.dump_outputs, x, resvec, torch)
     dt = float(np.median(region))
     relres = float(resvec[-1] / resvec[0])
     dof_per_s = world * n * nrhs * K / dt

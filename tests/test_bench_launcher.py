@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,3 +45,23 @@ def test_bench_gpus2_from_a_bare_python_call(form):
     if form == "ghost":
         assert out["ghost"]["exchanges_per_step"] > 0 and out["transport"].startswith("plug-in")
     assert 0 < out["relres_after_steps"] < 1e-2
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_solve(mg, built, tmp_path):
+    """--dump-outputs DIR: the residual history of exactly --steps steps and the iterate they produced (33^3 rows: x whole),
+    which must leave the residual the history ends with on the seeded right-hand side bench.py solves."""
+    K = 4
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cells", "32", "--steps", str(K),
+                        "--warmup", "1", "--no-cpu-baseline", "--no-generic-pass", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, env=_clean_env(), timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
+    assert out["steps"] == K and out["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["resvec.npy", "x.npy"]
+    resvec, x = np.load(tmp_path / "resvec.npy"), np.load(tmp_path / "x.npy")
+    assert resvec.dtype == x.dtype == np.float64 and resvec.shape == (K + 1,) and x.shape == (33 ** 3,)
+    assert resvec[-1] / resvec[0] == pytest.approx(out["relres_after_steps"], rel=1e-12)
+    A, _ = mg.poisson_shifted([32, 32, 32])
+    b = mg.seeded_rhs(A)
+    assert abs(np.linalg.norm(b - A @ x) - resvec[-1]) <= 1e-10 * resvec[0]

@@ -4,7 +4,9 @@ oracle/_ref/parLU.so is the reference's deps/src/parLU.cpp built in place by ora
 into the repo).  Its applyLUsolve_FP64_INT64 (parLU.cpp:52-63,120-190) is the "Julia factors, native applies"
 path of src/ParallelJuliaSolver: x[q] = U \\ (L \\ b[p]) on CSR factors with 1-based Int64 indices, L's diagonal
 last and U's diagonal first in every row.  The same factors (here from SuperLU instead of UMFPACK) fed to the
-reference binary must reproduce the oracle's solveCoarsest and the dense inverse the device applies.
+reference binary must reproduce the oracle's solveCoarsest and the dense inverse the device applies.  Where the binary
+is not built (no reference tree), the tests use its outputs on the same inputs from
+tests/golden/reference_binaries/outputs.npz.
 """
 import ctypes as C
 import os
@@ -14,9 +16,9 @@ import pytest
 import scipy.sparse as sp
 
 from oracle import mg_oracle as orc
+from tests_helpers import reference_output
 
 REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "parLU.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/parLU.so not built (reference tree absent)")
 
 _i64p = C.POINTER(C.c_longlong)
 _f64p = C.POINTER(C.c_double)
@@ -76,8 +78,8 @@ def test_transposed_solve_of_the_reference_binary(mg, built, nrhs):
     lu = spla.splu(A, permc_spec="MMD_AT_PLUS_A")
     rng = np.random.default_rng(11)
     B = rng.standard_normal((A.shape[0], nrhs)) if nrhs > 1 else rng.standard_normal(A.shape[0])
-    X0 = _ref_lu_solve(lu, B, 0)
-    X1 = _ref_lu_solve(lu, B, 1)
+    X0 = reference_output(f"parlu_nonsymmetric_nrhs{nrhs}_plain", "parLU.so", lambda: _ref_lu_solve(lu, B, 0))
+    X1 = reference_output(f"parlu_nonsymmetric_nrhs{nrhs}_transposed", "parLU.so", lambda: _ref_lu_solve(lu, B, 1))
     assert np.abs(A @ X0 - B).max() <= 1e-10 * np.abs(B).max()
     assert np.abs(A.T @ X1 - B).max() <= 1e-10 * np.abs(B).max()
     assert np.abs(X1 - lu.solve(B, trans="T")).max() <= 1e-12 * np.abs(X1).max()
@@ -91,7 +93,8 @@ def test_coarse_solve_matches_reference_binary(mg, built, cells, levels, nrhs):
     Ac = p.As[-1]
     rng = np.random.default_rng(3)
     B = rng.standard_normal((Ac.shape[0], nrhs)) if nrhs > 1 else rng.standard_normal(Ac.shape[0])
-    Xref = _ref_lu_solve(p.LU, B)                               # the reference's compiled triangular solves
+    Xref = reference_output(f"parlu_coarse_{'x'.join(map(str, cells))}_l{levels}_nrhs{nrhs}", "parLU.so",
+                            lambda: _ref_lu_solve(p.LU, B))     # the reference's compiled triangular solves
     Xo = orc.solveCoarsest(p, B, np.zeros_like(B))              # oracle (MGcycle.jl:177)
     assert np.abs(Xref - Xo).max() <= 1e-12 * np.abs(Xo).max()
     Ainv = p.LU.solve(np.eye(Ac.shape[0]))                      # what device.py uploads (mg_set_coarse_dense_inverse)
