@@ -567,6 +567,54 @@ int mg_ghost_comm_count(mg_hierarchy* h, long long* count);
 /* all-reduces this rank entered since mg_ghost_attach (the scalars of norms / dots, the rows of the first replicated level) */
 int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count);
 
+/* ---- ComplexF64 values, Int64 indices (CF64): single GPU, generic CSR ------------------------------------------------
+ * The reference's solver is generic in VAL (MGparam{VAL,IND}, recursiveCycle, relax, solveMG: MGdef.jl:91-116); these entry
+ * points serve VAL = ComplexF64 (frequency-domain users: shifted-Laplacian preconditioners for Helmholtz).
+ *
+ * Layout.  Complex arrays are interleaved (re, im) doubles - Julia ComplexF64, numpy complex128, hipDoubleComplex.  The
+ *   prototypes take double*; every element count (n, n_rows, nnz, ...) counts complex numbers.
+ * Applied operator.  mg_set_operator_CF64_INT64 takes the CSC arrays of the reference's AT, as the FP64 entry does, and applies
+ *   AT^H - what Ac_mul_B! / mul!(target, adjoint(AT), x, alpha, beta) computes (SpMatMul.jl:9): y_i = sum_k conj(nzval_k) *
+ *   x[rowval_k] over CSC column i.  The values are conjugated once, at upload.
+ * Transfer operators.  P and R stay real (MGsetup.jl:80-81, SA-AMG.jl:9-10): upload them with mg_set_operator_FP64_INT64 on
+ *   the CF64 handle; they are applied to complex vectors.
+ * Relaxation.  relaxPrecs are complex (getRelaxPrec conjugates, MGsetup.jl:145-149); the update is x += d .* r, a pointwise
+ *   complex product.
+ * Norms.  ||r|| = sqrt(sum |r_i|^2), Julia's norm of a complex vector: solveMG's stopping test and resvec (which stays double).
+ * Coarsest solve.  The dense inverse (column-major complex n x n) or sparse factors in the layout of
+ *   mg_set_coarse_lu_FP64_INT64 / the reference's applyLUsolve_CFP64_INT64 (deps/src/parLU.cpp:69-72) with complex values,
+ *   applied by the same level-scheduled triangular sweeps.
+ * The handle.  The value type is fixed by the constructor.  Shared by both types: mg_set_cycle_type ('V', 'W', 'F'),
+ *   mg_set_relax_type (0), mg_set_option, mg_set_nrhs (1), mg_finalize, mg_destroy, mg_graph_launches, mg_set_grid_hint (a
+ *   no-op hint here), mg_profile_enable / _reset / _get (nothing is recorded), mg_last_error.  Every other FP64 entry point
+ *   called with a CF64 handle fails with MG_ERR_STATE, and every CF64 entry point called with an FP64 handle fails with
+ *   MG_ERR_STATE too; nothing is changed.
+ * Refused with MG_ERR_UNSUPPORTED (and a mg_last_error message): cycle 'K', relaxType 1 (Jac-GMRES), the GMRES coarse solve
+ *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries), the Krylov drivers
+ *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*), mg_rap_FP64, mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
+ *   mg_ghost_* call and mg_dist_set_tail_INT64 with a CF64 tail (the mg_dist_* handles are FP64 by construction).
+ * Formats.  Generic CSR only, one streaming kernel (int32 row pointers; 64-bit beyond 2^31 - 4096 non-zeros or with the option
+ *   "force_rowptr64"); the row-class, band, tile, march and small-level formats are real-valued and not used.  No HIP graphs. */
+int mg_create_CF64(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out);
+/* MG_OP_A only (complex nzval of AT, 2*nnz doubles); P and R go through mg_set_operator_FP64_INT64. */
+int mg_set_operator_CF64_INT64(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols,
+                               const long long* colptr, const long long* rowval, const double* nzval);
+/* relaxPrecs[level]: n complex values. */
+int mg_set_relax_CF64(mg_hierarchy* h, long long level, const double* d, long long n, long long relaxPre,
+                      long long relaxPost);
+int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double* Ainv_colmajor);
+int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* Lptr, const long long* Lcol,
+                                const double* Lval, const long long* Uptr, const long long* Ucol,
+                                const double* Uval, const long long* p, const long long* q);
+/* x <- recursiveCycle(param,b,x,1); b, x: n complex values; nrhs must be 1; x_is_zero as for mg_cycle_FP64. */
+int mg_cycle_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long x_is_zero);
+/* solveMG; resvec (double, length maxIter+1, may be NULL) receives ||r0|| and ||r|| after every cycle. */
+int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
+                  long long maxIter, long long* iters, double* resvec);
+/* target = beta*target + alpha*Op*x on one level; alpha and beta are complex, each a (re, im) pair. */
+int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* x,
+                 const double* beta, double* y, long long nrhs);
+
 const char* mg_last_error(void);
 const char* mg_version(void);
 

@@ -46,6 +46,7 @@ int mg_create(long long nlevels, long long nrhs, long long device_id, mg_hierarc
 // inverse back with mg_set_coarse_dense_inverse_FP64 and call mg_finalize.
 int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind,
                 const double* omega, long long* levels_done) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
@@ -99,6 +100,7 @@ int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
 }
 
 int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   Csr* M = pick(h, level, which);
   if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
@@ -110,6 +112,7 @@ int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double
 }
 
 int mg_get_relax_FP64(mg_hierarchy* h, long long level, double* out, long long n) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
   Level& L = h->lev[(size_t)level - 1];
@@ -126,6 +129,7 @@ int mg_destroy(mg_hierarchy* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)spin_sync(h->stream);
   if (h->ghost) { gh_release(h->ghost); h->ghost = nullptr; }
+  if (h->cx) { cx_destroy(h->cx); h->cx = nullptr; }
   prof_collect(h);
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   for (auto& L : h->lev) {
@@ -192,6 +196,7 @@ int mg_set_operator_FP64_INT64(mg_hierarchy* h, long long level, long long which
                                const double* nzval) {
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (h->cx) return cx_set_transfer(h, level, which, n_rows, n_cols, colptr, rowval, nzval);   // P, R of a CF64 handle (real)
   graphs_clear(h);
   Csr* M = pick(h, level, which);
   if (!M) return fail(MG_ERR_INVALID, "bad (level=%lld, which=%lld)", level, which);
@@ -205,6 +210,7 @@ int mg_set_operator_FP64_INT64(mg_hierarchy* h, long long level, long long which
 
 int mg_set_relax_FP64(mg_hierarchy* h, long long level, const double* d, long long n,
                       long long relaxPre, long long relaxPost) {
+  MG_REAL_ONLY(h);
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
@@ -264,6 +270,7 @@ int mg_set_relax_type(mg_hierarchy* h, long long relaxType) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
   if (relaxType != 0 && relaxType != 1) return fail(MG_ERR_INVALID, "relaxType must be 0 (Jac/SPAI) or 1 (Jac-GMRES)");
+  if (h->cx && relaxType == 1) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF64 handles");
   h->relax_type = (int)relaxType;
   h->finalized = false;
   return MG_OK;
@@ -273,6 +280,7 @@ int mg_set_cycle_type(mg_hierarchy* h, long long cycleType) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (cycleType != 'V' && cycleType != 'W' && cycleType != 'F' && cycleType != 'K')
     return fail(MG_ERR_INVALID, "cycleType must be 'V', 'W', 'F' or 'K'");
+  if (h->cx && cycleType == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF64 handles");
   if (h->cycle == (char)cycleType) return MG_OK;   // (the cycle type is part of the graph key: nothing to drop)
   graphs_clear(h);
   if ((cycleType == 'K') != (h->cycle == 'K')) h->finalized = false;  // memKcycle must be (de)allocated
@@ -281,6 +289,7 @@ int mg_set_cycle_type(mg_hierarchy* h, long long cycleType) {
 }
 
 int mg_set_coarse_dense_inverse_FP64(mg_hierarchy* h, long long n, const double* Ainv) {
+  MG_REAL_ONLY(h);
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
@@ -307,6 +316,7 @@ int mg_set_coarse_dense_inverse_FP64(mg_hierarchy* h, long long n, const double*
 int mg_set_coarse_lu_FP64_INT64(mg_hierarchy* h, long long n, const long long* Lptr, const long long* Lcol,
                                 const double* Lval, const long long* Uptr, const long long* Ucol,
                                 const double* Uval, const long long* p, const long long* q) {
+  MG_REAL_ONLY(h);
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
@@ -315,63 +325,10 @@ int mg_set_coarse_lu_FP64_INT64(mg_hierarchy* h, long long n, const long long* L
     return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
   (void)hipSetDevice(h->device);
   const size_t N = (size_t)n;
-  // dependency levels of the rows [0, n-M) of a triangular factor; the trailing M rows are handled apart (for U they
-  // are solved BEFORE every level, for L after all of them), so they impose no ordering here
   auto levels = [&](const std::vector<int>& P, const std::vector<int>& Cc, bool lower, int M, std::vector<int>& order,
-                    std::vector<int>& lvlptr) {
-    const int na = (int)n - M;
-    std::vector<int> lvl((size_t)na, 0);
-    int nl = 0;
-    if (lower) {
-      for (int i = 0; i < na; ++i) {
-        int m = 0;
-        for (int k = P[(size_t)i]; k < P[(size_t)i + 1] - 1; ++k) m = std::max(m, lvl[(size_t)Cc[(size_t)k]] + 1);
-        lvl[(size_t)i] = m;
-        nl = std::max(nl, m + 1);
-      }
-    } else {
-      for (int i = na - 1; i >= 0; --i) {
-        int m = 0;
-        for (int k = P[(size_t)i] + 1; k < P[(size_t)i + 1]; ++k)
-          if (Cc[(size_t)k] < na) m = std::max(m, lvl[(size_t)Cc[(size_t)k]] + 1);
-        lvl[(size_t)i] = m;
-        nl = std::max(nl, m + 1);
-      }
-    }
-    lvlptr.assign((size_t)nl + 1, 0);
-    for (int i = 0; i < na; ++i) lvlptr[(size_t)lvl[(size_t)i] + 1]++;
-    for (int l = 0; l < nl; ++l) lvlptr[(size_t)l + 1] += lvlptr[(size_t)l];
-    order.resize((size_t)na);
-    std::vector<int> pos(lvlptr.begin(), lvlptr.end() - 1);
-    for (int i = 0; i < na; ++i) order[(size_t)pos[(size_t)lvl[(size_t)i]]++] = i;
-  };
+                    std::vector<int>& lvlptr) { lu_levels(n, P, Cc, lower, M, order, lvlptr); };
   auto conv = [&](const long long* ptr, const long long* col, bool lower, std::vector<int>& P, std::vector<int>& Cc,
-                  std::vector<int>& order, std::vector<int>& lvlptr) -> int {
-    const long long nnz = ptr[n] - 1;
-    P.resize(N + 1);
-    Cc.resize((size_t)nnz);
-    for (size_t i = 0; i <= N; ++i) P[i] = (int)(ptr[i] - 1);
-    for (long long k = 0; k < nnz; ++k) {
-      const long long c = col[k] - 1;
-      if (c < 0 || c >= n) return fail(MG_ERR_INVALID, "factor column index out of range");
-      Cc[(size_t)k] = (int)c;
-    }
-    if (lower) {
-      for (size_t i = 0; i < N; ++i) {
-        if (P[i + 1] - P[i] < 1 || Cc[(size_t)P[i + 1] - 1] != (int)i) return fail(MG_ERR_INVALID, "L: the diagonal must be the last entry of row %zu", i + 1);
-        for (int k = P[i]; k < P[i + 1] - 1; ++k)
-          if (Cc[(size_t)k] >= (int)i) return fail(MG_ERR_INVALID, "L is not lower triangular");
-      }
-    } else {
-      for (size_t ii = 0; ii < N; ++ii) {
-        if (P[ii + 1] - P[ii] < 1 || Cc[(size_t)P[ii]] != (int)ii) return fail(MG_ERR_INVALID, "U: the diagonal must be the first entry of row %zu", ii + 1);
-        for (int k = P[ii] + 1; k < P[ii + 1]; ++k)
-          if (Cc[(size_t)k] <= (int)ii) return fail(MG_ERR_INVALID, "U is not upper triangular");
-      }
-    }
-    levels(P, Cc, lower, 0, order, lvlptr);
-    return MG_OK;
-  };
+                  std::vector<int>& order, std::vector<int>& lvlptr) -> int { return lu_convert(n, ptr, col, lower, P, Cc, order, lvlptr); };
   std::vector<int> LP, LC, LO, LL, UP, UC, UO, UL, pp(N), qq(N);
   MG_TRY(conv(Lptr, Lcol, true, LP, LC, LO, LL));
   MG_TRY(conv(Uptr, Ucol, false, UP, UC, UO, UL));
@@ -465,6 +422,7 @@ int mg_set_coarse_lu_FP64_INT64(mg_hierarchy* h, long long n, const long long* L
 // Coarsest solve by Jacobi-preconditioned FGMRES (coarseSolveType "GMRES", MGcycle.jl:152-168): d = relaxParam ./ diag(A_c)
 // as defineCoarsestAinv stores it in param.LU (MGsetup.jl:334).
 int mg_set_coarse_gmres_FP64(mg_hierarchy* h, long long n, const double* d) {
+  MG_CF64_UNSUPPORTED(h);
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
@@ -484,6 +442,7 @@ int mg_set_coarse_gmres_FP64(mg_hierarchy* h, long long n, const double* d) {
 int mg_finalize(mg_hierarchy* h) {
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (h->cx) return cx_finalize(h);
   graphs_clear(h);
   (void)hipSetDevice(h->device);
   const int nl = (int)h->nlevels;
@@ -525,6 +484,7 @@ int mg_set_nrhs(mg_hierarchy* h, long long nrhs) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
   if (nrhs < 1) return fail(MG_ERR_INVALID, "nrhs must be >= 1");
+  if (h->cx && nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
   if (nrhs == h->nrhs) return MG_OK;
   if (h->ghost && nrhs > 24) return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: blocks of up to 24 columns (column-wise solve)");
   (void)hipSetDevice(h->device);
@@ -538,6 +498,7 @@ int mg_set_nrhs(mg_hierarchy* h, long long nrhs) {
 
 int mg_replace_values_FP64(mg_hierarchy* h, long long level, long long which, const double* nzval,
                            long long nnz) {
+  MG_REAL_ONLY(h);
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
@@ -565,6 +526,7 @@ int mg_replace_values_FP64(mg_hierarchy* h, long long level, long long which, co
 // ---- device-resident hot path ---------------------------------------------------------------------
 int mg_cycle_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
                       long long x_is_zero) {
+  MG_REAL_ONLY(h);
   MG_TRY(check_ready(h, n, nrhs, true));
   if (h->ghost && x_is_zero < 0) return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: pass x_is_zero = 0 or 1 (the norm of x is a sum over all ranks: mg_solve_dev_FP64 takes it)");
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
@@ -584,6 +546,7 @@ int mg_cycle_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, 
 
 int mg_solve_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
                       double tol, long long maxIter, long long* iters, double* resvec) {
+  MG_REAL_ONLY(h);
   MG_TRY(check_ready(h, n, nrhs, true));
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
@@ -599,6 +562,7 @@ int mg_solve_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, 
 
 int mg_spmv_dev_FP64(mg_hierarchy* h, long long level, long long which, double alpha,
                      const double* x, double beta, double* y, long long nrhs) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   Csr* M = pick(h, level, which);
@@ -615,6 +579,7 @@ int mg_spmv_dev_FP64(mg_hierarchy* h, long long level, long long which, double a
 
 int mg_fused_dev_FP64(mg_hierarchy* h, long long level, long long kernel, const double* b,
                       const double* x, double* out, long long nrhs) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
@@ -639,6 +604,7 @@ int mg_fused_dev_FP64(mg_hierarchy* h, long long level, long long kernel, const 
 // form of relax's last sweep + the residual that follows it (MGcycle.jl:129-131 + 58-60; SolveFuncs.jl:26-30).
 int mg_sweep_residual_dev_FP64(mg_hierarchy* h, long long level, const double* b, const double* x, double* t, double* r,
                                double* xn, double* norm_r) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   if (level < 1 || level >= h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
@@ -656,6 +622,7 @@ int mg_sweep_residual_dev_FP64(mg_hierarchy* h, long long level, const double* b
 
 int mg_four_stage_dev_FP64(mg_hierarchy* h, long long level, const double* b, const double* x, double* tp, double* rp,
                            double* norm_r) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   if (level < 1 || level >= h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
@@ -734,6 +701,7 @@ int transpose_longest_column_ok(const Csr& M) {
 }
 }  // namespace
 int mg_transpose_hierarchy(mg_hierarchy* h) {
+  MG_CF64_UNSUPPORTED(h);
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
@@ -776,6 +744,7 @@ int mg_transpose_hierarchy(mg_hierarchy* h) {
 }
 
 int mg_operator_shape(mg_hierarchy* h, long long level, long long which, long long* shape) {
+  MG_REAL_ONLY(h);
   if (!h || !shape) return fail(MG_ERR_INVALID, "null argument");
   Csr* M = pick(h, level, which);
   if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
@@ -785,6 +754,7 @@ int mg_operator_shape(mg_hierarchy* h, long long level, long long which, long lo
   return MG_OK;
 }
 int mg_four_stage_form(mg_hierarchy* h, long long level, long long* yes, long long* geometry) {
+  MG_REAL_ONLY(h);
   if (!h || !yes || !geometry) return fail(MG_ERR_INVALID, "null argument");
   if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
   const Csr& A = h->lev[(size_t)level - 1].A;
@@ -832,6 +802,7 @@ static int upload_x_or_zero(mg_hierarchy* h, const double* x, long long n, long 
 
 int mg_cycle_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
                   long long x_is_zero) {
+  MG_REAL_ONLY(h);
   MG_TRY(check_ready(h, n, nrhs));
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   (void)hipSetDevice(h->device);
@@ -847,6 +818,7 @@ int mg_cycle_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long
 
 int mg_solve_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
                   double tol, long long maxIter, long long* iters, double* resvec) {
+  MG_REAL_ONLY(h);
   MG_TRY(check_ready(h, n, nrhs));
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
@@ -862,6 +834,7 @@ int mg_solve_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long
 
 int mg_pcg_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol,
                     long long maxIter, long long* iters, long long* flag, double* resvec) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, 1, /*sharded_ok=*/true));   // (ghost-layer form: the sharded drivers of mg_krylov.inc)
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -872,6 +845,7 @@ int mg_pcg_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, do
 
 int mg_pcg_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter,
                 long long* iters, long long* flag, double* resvec) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, 1));
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -885,6 +859,7 @@ int mg_pcg_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double
 
 int mg_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol,
                    long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, 1));
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -898,6 +873,7 @@ int mg_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long n, lon
 
 int mg_fgmres_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol,
                        long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, 1, /*sharded_ok=*/true));   // (ghost-layer form: the sharded drivers of mg_krylov.inc)
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -908,6 +884,7 @@ int mg_fgmres_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n,
 
 int mg_bicgstab_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol,
                          long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, 1, /*sharded_ok=*/true));   // (ghost-layer form: the sharded drivers of mg_krylov.inc)
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -918,6 +895,7 @@ int mg_bicgstab_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long 
 
 int mg_bicgstab_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter,
                      long long* iters, long long* flag, double* resvec, long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, 1));
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -932,6 +910,7 @@ int mg_bicgstab_FP64(mg_hierarchy* h, const double* b, double* x, long long n, d
 // ---- block Krylov drivers: host (column-major n x nrhs) and device-resident (row-major [n][nrhs]) forms ---------------
 int mg_block_pcg_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                           long long maxIter, long long* iters, long long* flag, double* resmat) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, nrhs, /*sharded_ok=*/true));   // (ghost-layer form: the sharded block drivers of mg_krylov.inc)
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -941,6 +920,7 @@ int mg_block_pcg_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long
 }
 int mg_block_pcg_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                       long long maxIter, long long* iters, long long* flag, double* resmat) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, nrhs));
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -953,6 +933,7 @@ int mg_block_pcg_FP64(mg_hierarchy* h, const double* b, double* x, long long n, 
 }
 int mg_block_bicgstab_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                                long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, nrhs, /*sharded_ok=*/true));   // (ghost-layer form: the sharded block drivers of mg_krylov.inc)
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -962,6 +943,7 @@ int mg_block_bicgstab_dev_FP64(mg_hierarchy* h, const double* b, double* x, long
 }
 int mg_block_bicgstab_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                            long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, nrhs));
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -975,6 +957,7 @@ int mg_block_bicgstab_FP64(mg_hierarchy* h, const double* b, double* x, long lon
 int mg_block_fgmres_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long inner,
                              double tol, long long maxIter, long long* iters, long long* flag, double* resvec,
                              long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, nrhs, /*sharded_ok=*/true));   // (ghost-layer form: the sharded block drivers of mg_krylov.inc)
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -985,6 +968,7 @@ int mg_block_fgmres_dev_FP64(mg_hierarchy* h, const double* b, double* x, long l
 int mg_block_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long inner,
                          double tol, long long maxIter, long long* iters, long long* flag, double* resvec,
                          long long* nres) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, nrhs));
   if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
   (void)hipSetDevice(h->device);
@@ -999,6 +983,7 @@ int mg_block_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long 
 // Mixed-precision preconditioner hook (getMultigridPreconditioner, SolveFuncs.jl:52-58): the caller's block is Float32,
 // the hierarchy Float64: bl .= b ; z .= 0 ; recursiveCycle(param, bl, z, 1) ; z2 .= z.  b32 / z32: n x nrhs column-major.
 int mg_cycle_mixed_FP32(mg_hierarchy* h, const float* b32, float* z32, long long n, long long nrhs) {
+  MG_REAL_ONLY(h);
   MG_TRY(check_ready(h, n, nrhs));
   if (!b32 || !z32) return fail(MG_ERR_INVALID, "null vector");
   (void)hipSetDevice(h->device);
@@ -1168,6 +1153,7 @@ int mg_host_unregister(void* ptr) {
 
 int mg_spmv_FP64(mg_hierarchy* h, long long level, long long which, double alpha, const double* x,
                  double beta, double* y, long long nrhs) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   Csr* M = pick(h, level, which);
@@ -1186,6 +1172,7 @@ int mg_spmv_FP64(mg_hierarchy* h, long long level, long long which, double alpha
 // ---- measurement --------------------------------------------------------------------------------------
 int mg_time_op_dev_FP64(mg_hierarchy* h, long long level, long long kernel, long long nrhs,
                         long long reps, double* ms_avg, double* bytes) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
@@ -1298,6 +1285,7 @@ int mg_profile_get(mg_hierarchy* h, long long level, long long kernel, double* t
 }
 
 int mg_profile_get_moved(mg_hierarchy* h, long long level, long long kernel, double* moved_bytes_per_launch) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (level < 1 || level > h->nlevels || kernel < 0 || kernel >= MG_K_COUNT || !moved_bytes_per_launch)
     return fail(MG_ERR_INVALID, "bad (level=%lld, kernel=%lld)", level, kernel);
@@ -1308,6 +1296,7 @@ int mg_profile_get_moved(mg_hierarchy* h, long long level, long long kernel, dou
 
 int mg_operator_format(mg_hierarchy* h, long long level, long long which, long long* npatterns,
                        long long* dict_entries, double* index_bytes_per_launch) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   Csr* M = pick(h, level, which);
   if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
@@ -1324,6 +1313,7 @@ int mg_operator_format(mg_hierarchy* h, long long level, long long which, long l
 
 int mg_operator_rowclasses(mg_hierarchy* h, long long level, long long which, long long* nclasses,
                            long long* dict_entries, double* matrix_bytes_per_launch) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   Csr* M = pick(h, level, which);
   if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
@@ -1344,6 +1334,7 @@ int mg_operator_rowclasses(mg_hierarchy* h, long long level, long long which, lo
 
 int mg_operator_rowclass_flags(mg_hierarchy* h, long long level, long long which, long long* implicit_first,
                                long long* class_relax, long long* kernel_variant, long long* exception_rows) {
+  MG_REAL_ONLY(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   Csr* M = pick(h, level, which);
   if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
@@ -1373,6 +1364,7 @@ int mg_operator_rowclass_flags(mg_hierarchy* h, long long level, long long which
 // workgroups, dynamic LDS bytes, estimated bytes filled + stored per row x 100, threads per workgroup, segments of the
 // lockstep schedule (0: balanced ranges), planes per segment, entries of the class table.
 int mg_sweep_residual_form(mg_hierarchy* h, long long level, long long* form, long long* geometry) {
+  MG_REAL_ONLY(h);
   if (!h || !form) return fail(MG_ERR_INVALID, "null argument");
   if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
   const Csr& A = h->lev[(size_t)level - 1].A;
@@ -1401,6 +1393,7 @@ int mg_sweep_residual_form(mg_hierarchy* h, long long level, long long* form, lo
 }
 
 int mg_band_form(mg_hierarchy* h, long long level, long long* info) {
+  MG_REAL_ONLY(h);
   if (!h || !info) return fail(MG_ERR_INVALID, "null argument");
   if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
   const Csr& A = h->lev[(size_t)level - 1].A;
@@ -1419,6 +1412,7 @@ int mg_band_form(mg_hierarchy* h, long long level, long long* info) {
 }
 
 int mg_cycle_bytes(mg_hierarchy* h, double* bytes) {
+  MG_REAL_ONLY(h);
   if (!h || !bytes) return fail(MG_ERR_INVALID, "null argument");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   // one V-cycle from x = 0 (SURVEY.md 8d "minimal-traffic fused model"); W/F revisit coarse levels
@@ -1442,6 +1436,7 @@ int mg_cycle_bytes(mg_hierarchy* h, double* bytes) {
 }
 
 int mg_device_bytes(mg_hierarchy* h, double* bytes) {
+  MG_REAL_ONLY(h);
   if (!h || !bytes) return fail(MG_ERR_INVALID, "null argument");
   double t = 0.0;
   for (auto& L : h->lev)

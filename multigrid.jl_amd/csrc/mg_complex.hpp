@@ -1,0 +1,188 @@
+// mg_complex.hpp - gfx950 kernels of the ComplexF64 (CF64) cycle: generic CSR only.
+//
+// Complex values are interleaved (re, im) doubles - Julia ComplexF64, numpy complex128, hipDoubleComplex - and are
+// loaded as one 16-byte d2_t.  The operator A of a CF64 handle is stored conjugated at upload (nzval of the
+// reference's AT, conj'd once), so every kernel here computes a plain sum of products: y_i = sum_k val_k * x[col_k]
+// is the reference's mul!(y, adjoint(AT), x) (SpMatMul.jl:9).  P and R stay real (MGsetup.jl:80-81) and are applied
+// to complex vectors by the same kernel with a real value stream.
+//
+// Streaming layout (the complex form of csr_stream_spmv, mg_kernels.hpp): the host cuts the rows into row blocks
+// whose non-zeros fit one LDS chunk of CX_CHUNK products; a workgroup issues every load of its block up front (16 B
+// per lane per complex value, coalesced), stages the products in LDS, and ONE lane per row sums its row's products
+// in stored order, then applies the fused epilogue.  Workgroups are banded per XCD (xcd_band).  A row longer than a
+// chunk has a block of its own and the whole workgroup strides over it.
+#pragma once
+#include "mg_kernels.hpp"
+
+namespace mgk {
+
+constexpr int CX_ITEMS = 4;                 // complex products per thread per chunk
+constexpr int CX_CHUNK = BLK * CX_ITEMS;    // 1024 products = 16 KiB of LDS per workgroup
+
+__device__ __forceinline__ d2_t cmul(d2_t a, d2_t b) { return d2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ d2_t cmul(double a, d2_t b) { return d2_t{a * b.x, a * b.y}; }
+__device__ __forceinline__ d2_t cdiv(d2_t a, d2_t b) {
+  const double s = b.x * b.x + b.y * b.y;
+  return d2_t{(a.x * b.x + a.y * b.y) / s, (a.y * b.x - a.x * b.y) / s};
+}
+__device__ __forceinline__ double cabs2(d2_t a) { return a.x * a.x + a.y * a.y; }
+__device__ __forceinline__ d2_t shfl_xor_v(d2_t a, int o) { return d2_t{__shfl_xor(a.x, o), __shfl_xor(a.y, o)}; }
+
+// the value stream of an operator: complex (A, conj'd at upload) or real (P, R)
+template <typename PTR, typename VT>
+struct CxCsrDev {
+  const PTR* rowptr;   // n_rows+1, 0-based
+  const int* colidx;   // nnz
+  const VT* val;       // nnz
+  const int* blk_row;  // nblocks+1
+  int nblocks;
+  int n_rows;
+};
+
+struct CxVecArgs {
+  const d2_t* x;   // gathered vector  [n_cols]
+  d2_t* y;         // output           [n_rows]
+  const d2_t* b;   // RESID / SMOOTH   [n_rows]
+  const d2_t* d;   // SMOOTH: relaxPrec [n_rows]
+  double* sumsq;   // optional: per-row-block sum of |out|^2 (summed by sum_final)
+  d2_t alpha;      // AXPBY
+  d2_t beta;       // AXPBY (beta == 0: y is not read)
+  int beta_zero;
+};
+
+// pb: beta*y (AXPBY) or b (RESID, SMOOTH); px, pd: the row's x and d (SMOOTH; x is the gathered vector itself)
+template <int MODE>
+__device__ __forceinline__ d2_t cx_epilogue(const CxVecArgs& v, d2_t acc, d2_t pb, d2_t pd, d2_t px) {
+  if (MODE == AXPBY) return cmul(v.alpha, acc) + pb;
+  if (MODE == RESID) return pb - acc;
+  return px + cmul(pd, pb - acc);   // SMOOTH: x + d.*(b - A x)   (MGcycle.jl:129-131)
+}
+
+template <int MODE>
+__device__ __forceinline__ void cx_operands(const CxVecArgs& v, int row, d2_t& pb, d2_t& pd, d2_t& px) {
+  if (MODE == AXPBY) {
+    if (!v.beta_zero) pb = cmul(v.beta, v.y[row]);
+  } else {
+    pb = v.b[row];
+  }
+  if (MODE == SMOOTH) {
+    pd = v.d[row];
+    px = v.x[row];
+  }
+}
+
+template <int MODE, typename PTR, typename VT>
+__global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, CxVecArgs v) {
+  __shared__ d2_t prod[CX_CHUNK];
+  __shared__ int srow[MAXROWS + 1];
+  __shared__ double red[2 * (BLK / 64)];
+
+  const int tid = threadIdx.x;
+  const int bid = xcd_band(blockIdx.x, A.nblocks);
+  const int r0 = A.blk_row[bid];
+  const int r1 = A.blk_row[bid + 1];
+  const int nrows = r1 - r0;
+  const PTR k0 = A.rowptr[r0];
+  const PTR k1 = A.rowptr[r1];
+
+  if (nrows == 1 && (k1 - k0) > CX_CHUNK) {
+    // one row longer than a chunk: the whole workgroup strides over it
+    d2_t acc = d2_t{0.0, 0.0};
+    for (PTR k = k0 + tid; k < k1; k += BLK) acc += cmul(A.val[k], v.x[A.colidx[k]]);
+    for (int o = 32; o > 0; o >>= 1) acc += shfl_xor_v(acc, o);
+    if ((tid & 63) == 0) {
+      red[2 * (tid >> 6)] = acc.x;
+      red[2 * (tid >> 6) + 1] = acc.y;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      d2_t s = d2_t{0.0, 0.0};
+      for (int w = 0; w < BLK / 64; ++w) s += d2_t{red[2 * w], red[2 * w + 1]};
+      d2_t pb = d2_t{0.0, 0.0}, pd = pb, px = pb;
+      cx_operands<MODE>(v, r0, pb, pd, px);
+      const d2_t o = cx_epilogue<MODE>(v, s, pb, pd, px);
+      v.y[r0] = o;
+      if (v.sumsq) v.sumsq[bid] = cabs2(o);
+    }
+    return;
+  }
+
+  // ---- every global load up front: matrix stream, row pointers, epilogue operands ----------------
+  VT va[CX_ITEMS];
+  int ca[CX_ITEMS];
+#pragma unroll
+  for (int it = 0; it < CX_ITEMS; ++it) {
+    const PTR idx = k0 + it * BLK + tid;
+    if (idx < k1) {
+      va[it] = A.val[idx];
+      ca[it] = A.colidx[idx];
+    } else {
+      va[it] = VT{};
+      ca[it] = 0;
+    }
+  }
+  if (tid <= nrows) srow[tid] = (int)(A.rowptr[r0 + tid] - k0);
+  if (tid == 0 && nrows == MAXROWS) srow[MAXROWS] = (int)(k1 - k0);
+  const bool owner = tid < nrows;
+  d2_t pb = d2_t{0.0, 0.0}, pd = pb, px = pb;
+  if (owner) cx_operands<MODE>(v, r0 + tid, pb, pd, px);
+  // ---- gather x and stage the products -----------------------------------------------------------
+#pragma unroll
+  for (int it = 0; it < CX_ITEMS; ++it) {
+    const PTR idx = k0 + it * BLK + tid;
+    if (idx < k1) prod[it * BLK + tid] = cmul(va[it], v.x[ca[it]]);
+  }
+  __syncthreads();
+  // ---- one lane per row: the row's products in stored order, fused epilogue ------------------------
+  d2_t outv = d2_t{0.0, 0.0};
+  if (owner) {
+    d2_t acc = d2_t{0.0, 0.0};
+    const int s = srow[tid], e = srow[tid + 1];
+    for (int k = s; k < e; ++k) acc += prod[k];
+    outv = cx_epilogue<MODE>(v, acc, pb, pd, px);
+    v.y[r0 + tid] = outv;
+  }
+  if (v.sumsq) {   // ||r||^2 = sum |r_i|^2 (SolveFuncs.jl:30): a deterministic per-block partial, summed by sum_final
+    double sq = cabs2(outv);
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+    if ((tid & 63) == 0) red[tid >> 6] = sq;
+    __syncthreads();
+    if (tid == 0) {
+      double t = 0.0;
+      for (int w = 0; w < BLK / 64; ++w) t += red[w];
+      v.sumsq[bid] = t;
+    }
+  }
+}
+
+// x = d.*b: relax's only update when the sweep starts from x = 0 (MGcycle.jl:134 with r = b)
+__global__ __launch_bounds__(BLK) void cx_dscale(const d2_t* __restrict__ d, const d2_t* __restrict__ b, d2_t* __restrict__ x,
+                                                 long long n) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i < n) x[i] = cmul(d[i], b[i]);
+}
+
+// first pass of the deterministic sum of |z_i|^2: one partial per workgroup (second pass: sum_final)
+__global__ __launch_bounds__(BLK) void cx_sumsq_partial(const d2_t* __restrict__ z, long long n, double* __restrict__ partial) {
+  __shared__ double red[BLK / 64];
+  const long long stride = (long long)gridDim.x * BLK;
+  double acc = 0.0;
+  for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) acc += cabs2(z[i]);
+  const double s = block_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// coarsest solve from the explicit inverse: x = Ainv * b, Ainv row-major n x n complex; one wavefront per row
+__global__ __launch_bounds__(BLK) void cx_dense_matvec(const d2_t* __restrict__ Ainv, const d2_t* __restrict__ b,
+                                                       d2_t* __restrict__ x, int n) {
+  const long long wave = ((long long)blockIdx.x * BLK + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wave >= n) return;
+  const d2_t* a = Ainv + wave * (long long)n;
+  d2_t acc = d2_t{0.0, 0.0};
+  for (int j = lane; j < n; j += 64) acc += cmul(a[j], b[j]);
+  for (int o = 32; o > 0; o >>= 1) acc += shfl_xor_v(acc, o);
+  if (lane == 0) x[wave] = acc;
+}
+
+}  // namespace mgk

@@ -1,0 +1,522 @@
+// mg_complex.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
+// ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F cycles,
+// pointwise relaxation, dense-inverse or sparse-LU coarsest solve.  The state lives apart from the real levels (CxState);
+// the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
+//
+// Reference behaviour reproduced for VAL = ComplexF64:
+//   recursiveCycle  src/Multigrid/MGcycle.jl:1-118, relax l.122-136, solveCoarsest l.177
+//   solveMG         src/Multigrid/SolveFuncs.jl:3-39 (norm: sqrt(sum |r_i|^2))
+//   SpMatMul        src/Multigrid/SpMatMul.jl:4-13: mul!(target, adjoint(AT), x, alpha, beta) - A = AT^H, conj'd at upload
+typedef mgk::d2_t cx_t;
+
+// (the state types live beside mg_hierarchy, outside the anonymous namespace: the handle holds a CxState*)
+// one operator of a CF64 hierarchy, generic CSR: complex values (A = AT^H) or real values (P, R)
+struct CxMat {
+  bool set = false, cplx = false, wide = false;
+  long long n_rows = 0, n_cols = 0, nnz = 0;
+  int nblocks = 0;
+  DevBuf<int> rowptr, colidx, blk_row;
+  DevBuf<long long> rowptr64;   // wide: >= 2^31 - 4096 non-zeros (or the option force_rowptr64)
+  DevBuf<double> val;           // nnz real values, or 2*nnz interleaved (re, im)
+  void release() {
+    rowptr.release(); colidx.release(); blk_row.release(); rowptr64.release(); val.release();
+    set = false;
+  }
+};
+
+struct CxLevel {
+  CxMat A, P, R;
+  DevBuf<double> d;            // relaxPrecs[l], complex
+  bool relax_set = false;
+  long long npre = 0, npost = 0, n = 0;
+  DevBuf<double> b, r, x[2];   // complex scratch (CYCLEmem, MGdef.jl:56-60); x ping-pongs between the sweeps
+};
+
+struct CxState {
+  std::vector<CxLevel> lev;
+  bool finalized = false;
+  bool coarse_set = false, coarse_lu = false;
+  long long n_coarse = 0;
+  DevBuf<double> Ainv;         // row-major n_c x n_c complex
+  DevBuf<int> luLptr, luLcol, luUptr, luUcol, luP, luQ, luLorder, luLlvl, luUorder, luUlvl;
+  DevBuf<double> luLval, luUval, luWork;
+  int nLlvl = 0, nUlvl = 0;
+  DevBuf<double> stage_b, partial;   // the fine right-hand side; per-row-block partials of ||r||^2
+  ~CxState() {
+    for (auto& L : lev) {
+      L.A.release(); L.P.release(); L.R.release();
+      L.d.release(); L.b.release(); L.r.release(); L.x[0].release(); L.x[1].release();
+    }
+    Ainv.release();
+    for (DevBuf<int>* d : {&luLptr, &luLcol, &luUptr, &luUcol, &luP, &luQ, &luLorder, &luLlvl, &luUorder, &luUlvl}) d->release();
+    luLval.release(); luUval.release(); luWork.release();
+    stage_b.release(); partial.release();
+  }
+};
+
+namespace {
+
+void cx_destroy(CxState* s) { delete s; }
+
+inline cx_t* cxp(DevBuf<double>& b) { return reinterpret_cast<cx_t*>(b.p); }
+inline unsigned cx_grid(long long n) { return (unsigned)((n + mgk::BLK - 1) / mgk::BLK); }
+
+int cx_level_ok(mg_hierarchy* h, long long level) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
+  return MG_OK;
+}
+
+// Upload one operator from the reference's CSC-of-AT arrays (1-based Int64).  Complex values are conjugated here, once:
+// the kernels then compute y_i = sum_k val_k x[col_k] = (AT^H x)_i.
+int cx_upload(CxMat* M, const Options& opt, long long n_rows, long long n_cols, const long long* colptr, const long long* rowval,
+              const double* nzval, bool cplx) {
+  if (n_rows < 1 || n_cols < 1 || !colptr || !rowval || !nzval) return fail(MG_ERR_INVALID, "empty operator or null array");
+  if (n_rows >= (1LL << 31) - 1 || n_cols >= (1LL << 31) - 1) return fail(MG_ERR_UNSUPPORTED, "dimension exceeds int32 device indices");
+  if (colptr[0] != 1) return fail(MG_ERR_INVALID, "colptr[1] must be 1 (1-based Julia arrays expected)");
+  const long long nnz = colptr[n_rows] - 1;
+  if (nnz < 0) return fail(MG_ERR_INVALID, "colptr is not a 1-based pointer array");
+  std::vector<long long> rp((size_t)n_rows + 1);
+  for (long long i = 0; i <= n_rows; ++i) {
+    const long long v = colptr[i] - 1;
+    if (v < 0 || v > nnz || (i > 0 && v < rp[(size_t)i - 1]))
+      return fail(MG_ERR_INVALID, "colptr is not a monotone 1-based pointer array at %lld", i);
+    rp[(size_t)i] = v;
+  }
+  std::vector<int> ci((size_t)std::max<long long>(nnz, 1), 0);
+  for (long long k = 0; k < nnz; ++k) {
+    const long long c = rowval[k] - 1;
+    if (c < 0 || c >= n_cols) return fail(MG_ERR_INVALID, "rowval[%lld]=%lld outside 1..%lld", k + 1, rowval[k], n_cols);
+    ci[(size_t)k] = (int)c;
+  }
+  // row blocks: consecutive rows, <= MAXROWS rows and <= CX_CHUNK non-zeros (a longer row has a block of its own)
+  std::vector<int> blk(1, 0);
+  for (long long r = 0; r < n_rows;) {
+    long long e = r + 1;
+    while (e < n_rows && (e - r) < mgk::MAXROWS && rp[(size_t)e + 1] - rp[(size_t)r] <= mgk::CX_CHUNK) ++e;
+    blk.push_back((int)e);
+    r = e;
+  }
+  const size_t vw = cplx ? 2 : 1;
+  std::vector<double> v((size_t)std::max<long long>(nnz, 1) * vw, 0.0);
+  for (long long k = 0; k < (long long)nnz * (long long)vw; ++k) v[(size_t)k] = (cplx && (k & 1)) ? -nzval[k] : nzval[k];
+  M->release();
+  M->cplx = cplx;
+  M->wide = nnz >= (1LL << 31) - 4096 || opt.force_rowptr64;
+  M->n_rows = n_rows;
+  M->n_cols = n_cols;
+  M->nnz = nnz;
+  M->nblocks = (int)blk.size() - 1;
+  if (M->wide) {
+    MG_TRY(M->rowptr64.alloc(rp.size()));
+    HIP_TRY(hipMemcpy(M->rowptr64.p, rp.data(), rp.size() * sizeof(long long), hipMemcpyHostToDevice));
+  } else {
+    std::vector<int> rp32(rp.begin(), rp.end());
+    MG_TRY(M->rowptr.alloc(rp32.size()));
+    HIP_TRY(hipMemcpy(M->rowptr.p, rp32.data(), rp32.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  MG_TRY(M->colidx.alloc(ci.size()));
+  MG_TRY(M->val.alloc(v.size()));
+  MG_TRY(M->blk_row.alloc(blk.size()));
+  HIP_TRY(hipMemcpy(M->colidx.p, ci.data(), ci.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(M->val.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(M->blk_row.p, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
+  M->set = true;
+  return MG_OK;
+}
+
+// P or R of a CF64 handle (mg_set_operator_FP64_INT64 routes them here): real values, applied to complex vectors
+int cx_set_transfer(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols, const long long* colptr,
+                    const long long* rowval, const double* nzval) {
+  MG_TRY(cx_level_ok(h, level));
+  if (which == MG_OP_A)
+    return fail(MG_ERR_STATE, "mg_set_operator_FP64_INT64(MG_OP_A) on a CF64 handle: As are complex (mg_set_operator_CF64_INT64)");
+  if (which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
+  if (level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
+  (void)hipSetDevice(h->device);
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  MG_TRY(cx_upload(which == MG_OP_P ? &L.P : &L.R, h->opt, n_rows, n_cols, colptr, rowval, nzval, false));
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
+// y = epilogue(M * x) on h's stream; the launch of one (MODE, row-pointer width, value type)
+template <int MODE, typename PTR, typename VT>
+void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::CxVecArgs& v) {
+  mgk::CxCsrDev<PTR, VT> D;
+  D.rowptr = rowptr;
+  D.colidx = M.colidx.p;
+  D.val = reinterpret_cast<const VT*>(M.val.p);
+  D.blk_row = M.blk_row.p;
+  D.nblocks = M.nblocks;
+  D.n_rows = (int)M.n_rows;
+  hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<MODE, PTR, VT>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->stream, D, v);
+}
+
+template <int MODE>
+int cx_spmv(mg_hierarchy* h, const CxMat& M, const cx_t* x, cx_t* y, const cx_t* b, const cx_t* d, double* sumsq,
+            cx_t alpha = cx_t{1.0, 0.0}, cx_t beta = cx_t{0.0, 0.0}) {
+  mgk::CxVecArgs v;
+  v.x = x; v.y = y; v.b = b; v.d = d; v.sumsq = sumsq;
+  v.alpha = alpha; v.beta = beta;
+  v.beta_zero = (beta.x == 0.0 && beta.y == 0.0) ? 1 : 0;
+  if (M.cplx) {
+    if (M.wide) cx_launch<MODE, long long, cx_t>(h, M, M.rowptr64.p, v);
+    else cx_launch<MODE, int, cx_t>(h, M, M.rowptr.p, v);
+  } else {
+    if (MODE != mgk::AXPBY) return fail(MG_ERR_INVALID, "internal: a real transfer operator serves the AXPBY form only");
+    if (M.wide) cx_launch<mgk::AXPBY, long long, double>(h, M, M.rowptr64.p, v);
+    else cx_launch<mgk::AXPBY, int, double>(h, M, M.rowptr.p, v);
+  }
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// ||z||^2 = sum |z_i|^2 into the pinned host scalar: the two-pass deterministic sum
+int cx_norm2(mg_hierarchy* h, const cx_t* z, long long n, double* out) {
+  const int np = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n + mgk::BLK - 1) / mgk::BLK));
+  hipLaunchKernelGGL(mgk::cx_sumsq_partial, dim3((unsigned)np), dim3(mgk::BLK), 0, h->stream, z, n, h->partial.p);
+  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, np, h->scalar.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(spin_sync(h->stream));
+  *out = h->h_scalar[0];
+  return MG_OK;
+}
+
+// r = b - A x with the per-block partials of ||r||^2, then the sum into the pinned host scalar
+int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const cx_t* b, const cx_t* x, cx_t* r, double* out) {
+  CxState& S = *h->cx;
+  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, x, r, b, nullptr, S.partial.p));
+  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, S.partial.p, L.A.nblocks, h->scalar.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(spin_sync(h->stream));
+  *out = h->h_scalar[0];
+  return MG_OK;
+}
+
+// z = param.LU \ b (MGcycle.jl:177): explicit inverse, or x[q] = U \ (L \ b[p]) by the level-scheduled sptrsv_lu
+int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x) {
+  CxState& S = *h->cx;
+  const long long n = S.n_coarse;
+  if (S.coarse_lu) {
+    mgk::LuDevT<cx_t> F;
+    F.n = (int)n;
+    F.Lptr = S.luLptr.p; F.Lcol = S.luLcol.p; F.Lval = reinterpret_cast<const cx_t*>(S.luLval.p);
+    F.Uptr = S.luUptr.p; F.Ucol = S.luUcol.p; F.Uval = reinterpret_cast<const cx_t*>(S.luUval.p);
+    F.p = S.luP.p; F.q = S.luQ.p;
+    F.Lorder = S.luLorder.p; F.Llvl = S.luLlvl.p; F.nLlvl = S.nLlvl;
+    F.Uorder = S.luUorder.p; F.Ulvl = S.luUlvl.p; F.nUlvl = S.nUlvl;
+    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, h->stream, F, b, x, cxp(S.luWork), 1);
+  } else {
+    hipLaunchKernelGGL(mgk::cx_dense_matvec, dim3(cx_grid(n * 64)), dim3(mgk::BLK), 0, h->stream,
+                       reinterpret_cast<const cx_t*>(S.Ainv.p), b, x, (int)n);
+  }
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// relax (MGcycle.jl:122-136) entered with r = b - A x: numit-1 times {x += d.*r; r = b - A x}, then x += d.*r - i.e.
+// max(numit, 1) sweeps x' = x + d.*(b - A x); from x = 0 the first one is x = d.*b.  x ping-pongs between L.x[0] / L.x[1].
+int cx_relax(mg_hierarchy* h, CxLevel& L, const cx_t* b, int& xi, bool xzero, long long numit) {
+  long long sweeps = std::max<long long>(numit, 1);
+  if (xzero) {
+    hipLaunchKernelGGL(mgk::cx_dscale, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->stream, reinterpret_cast<const cx_t*>(L.d.p), b,
+                       cxp(L.x[xi]), L.n);
+    HIP_TRY(hipGetLastError());
+    --sweeps;
+  }
+  for (long long s = 0; s < sweeps; ++s) {
+    MG_TRY(cx_spmv<mgk::SMOOTH>(h, L.A, cxp(L.x[xi]), cxp(L.x[1 - xi]), b, reinterpret_cast<const cx_t*>(L.d.p), nullptr));
+    xi = 1 - xi;
+  }
+  return MG_OK;
+}
+
+// recursiveCycle (MGcycle.jl:1-118) from level l (0-based) on b; the iterate is lev[l].x[xi] (zero on entry when xzero)
+int cx_cycle(mg_hierarchy* h, int l, const cx_t* b, int& xi, bool xzero, char ctype) {
+  CxState& S = *h->cx;
+  const int nl = (int)h->nlevels;
+  CxLevel& L = S.lev[(size_t)l];
+  if (l == nl - 1) return cx_coarse(h, b, cxp(L.x[xi]));                               // l.13-18
+  MG_TRY(cx_relax(h, L, b, xi, xzero, L.npre));                                         // l.26-31, 54
+  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxp(L.x[xi]), cxp(L.r), b, nullptr, nullptr));     // l.58-60
+  CxLevel& C = S.lev[(size_t)l + 1];
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.R, cxp(L.r), cxp(C.b), nullptr, nullptr, nullptr));   // bc = R r   (l.66)
+  int ci = 0;
+  if (l + 1 == nl - 1) {
+    MG_TRY(cx_coarse(h, cxp(C.b), cxp(C.x[ci])));                                       // l.67-69
+  } else {
+    MG_TRY(cx_cycle(h, l + 1, cxp(C.b), ci, true, ctype));                              // xc = 0 (l.63-64), l.78
+    if (ctype == 'W') MG_TRY(cx_cycle(h, l + 1, cxp(C.b), ci, false, 'W'));            // l.79-80
+    else if (ctype == 'F') MG_TRY(cx_cycle(h, l + 1, cxp(C.b), ci, false, 'V'));       // l.81-84
+  }
+  // x += P xc (l.90): in place, the gather reads xc only
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxp(C.x[ci]), cxp(L.x[xi]), nullptr, nullptr, nullptr, cx_t{1.0, 0.0}, cx_t{1.0, 0.0}));
+  return cx_relax(h, L, b, xi, false, L.npost);                                        // r = b - A x, relax (l.92-102)
+}
+
+int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+  if (!h->cx->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
+  if (n != h->cx->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->cx->lev[0].n);
+  return MG_OK;
+}
+
+bool cx_host_zero(const double* x, long long n) {
+  for (long long i = 0; i < 2 * n; ++i)
+    if (x[i] != 0.0) return false;
+  return true;
+}
+
+// mg_finalize of a CF64 handle: shapes chain, every level complete, scratch allocated
+int cx_finalize(mg_hierarchy* h) {
+  CxState& S = *h->cx;
+  S.finalized = false;
+  const int nl = (int)h->nlevels;
+  if (h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF64 handles");
+  if (h->relax_type != 0) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF64 handles");
+  size_t maxblocks = 1;
+  for (int l = 0; l < nl; ++l) {
+    CxLevel& L = S.lev[(size_t)l];
+    if (!L.A.set) return fail(MG_ERR_STATE, "As[%d] was not set", l + 1);
+    if (L.A.n_rows != L.A.n_cols) return fail(MG_ERR_INVALID, "As[%d] is not square", l + 1);
+    L.n = L.A.n_rows;
+    maxblocks = std::max(maxblocks, (size_t)L.A.nblocks);
+    if (l < nl - 1) {
+      if (!L.P.set || !L.R.set) return fail(MG_ERR_STATE, "Ps[%d]/Rs[%d] were not set", l + 1, l + 1);
+      if (!L.relax_set) return fail(MG_ERR_STATE, "relaxPrecs[%d] was not set", l + 1);
+      if ((long long)L.d.n != 2 * L.n) return fail(MG_ERR_INVALID, "relaxPrecs[%d] has length %zu, expected %lld", l + 1, L.d.n / 2, L.n);
+    }
+  }
+  for (int l = 0; l < nl - 1; ++l) {
+    CxLevel& L = S.lev[(size_t)l];
+    const long long nc = S.lev[(size_t)l + 1].A.n_rows;
+    if (L.P.n_rows != L.n || L.P.n_cols != nc)
+      return fail(MG_ERR_INVALID, "Ps[%d] is %lldx%lld, expected %lldx%lld", l + 1, L.P.n_rows, L.P.n_cols, L.n, nc);
+    if (L.R.n_rows != nc || L.R.n_cols != L.n)
+      return fail(MG_ERR_INVALID, "Rs[%d] is %lldx%lld, expected %lldx%lld", l + 1, L.R.n_rows, L.R.n_cols, nc, L.n);
+  }
+  if (!S.coarse_set) return fail(MG_ERR_STATE, "the coarsest solve was not set");
+  if (S.n_coarse != S.lev[(size_t)nl - 1].n)
+    return fail(MG_ERR_INVALID, "coarse solve order %lld != coarsest level size %lld", S.n_coarse, S.lev[(size_t)nl - 1].n);
+  (void)hipSetDevice(h->device);
+  for (auto& L : S.lev) {
+    const size_t len = 2 * (size_t)L.n;
+    if (L.b.n != len) MG_TRY(L.b.alloc(len));
+    if (L.r.n != len) MG_TRY(L.r.alloc(len));
+    if (L.x[0].n != len) MG_TRY(L.x[0].alloc(len));
+    if (L.x[1].n != len) MG_TRY(L.x[1].alloc(len));
+  }
+  const size_t n0 = 2 * (size_t)S.lev[0].n;
+  if (S.stage_b.n != n0) MG_TRY(S.stage_b.alloc(n0));
+  if (S.partial.n < maxblocks) MG_TRY(S.partial.alloc(maxblocks));
+  if (S.coarse_lu && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
+  S.finalized = true;
+  return MG_OK;
+}
+
+}  // namespace
+
+// =================================================================================================
+// C ABI: the CF64 entry points
+// =================================================================================================
+extern "C" {
+
+int mg_create_CF64(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out) {
+  if (!out) return fail(MG_ERR_INVALID, "out is null");
+  *out = nullptr;
+  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
+  mg_hierarchy* h = nullptr;
+  MG_TRY(mg_create(nlevels, 1, device_id, &h));
+  h->cx = new CxState();
+  h->cx->lev.resize((size_t)nlevels);
+  *out = h;
+  return MG_OK;
+}
+
+int mg_set_operator_CF64_INT64(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols,
+                               const long long* colptr, const long long* rowval, const double* nzval) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, level));
+  if (which != MG_OP_A)
+    return fail(MG_ERR_INVALID, "mg_set_operator_CF64_INT64 takes MG_OP_A only: P and R stay real (mg_set_operator_FP64_INT64)");
+  (void)hipSetDevice(h->device);
+  MG_TRY(cx_upload(&h->cx->lev[(size_t)level - 1].A, h->opt, n_rows, n_cols, colptr, rowval, nzval, true));
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
+int mg_set_relax_CF64(mg_hierarchy* h, long long level, const double* d, long long n, long long relaxPre, long long relaxPost) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, level));
+  if (!d || n < 1) return fail(MG_ERR_INVALID, "empty relaxPrec");
+  if (relaxPre < 0 || relaxPost < 0) return fail(MG_ERR_INVALID, "negative sweep count");
+  (void)hipSetDevice(h->device);
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  MG_TRY(L.d.alloc(2 * (size_t)n));
+  HIP_TRY(hipMemcpy(L.d.p, d, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  L.relax_set = true;
+  L.npre = relaxPre;
+  L.npost = relaxPost;
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
+int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double* Ainv) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, 1));
+  if (n < 1 || !Ainv) return fail(MG_ERR_INVALID, "empty coarse inverse");
+  if (n > 32000) return fail(MG_ERR_UNSUPPORTED, "dense coarse inverse of order %lld is too large", n);
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  std::vector<double> rm(2 * (size_t)n * (size_t)n);   // column-major -> row-major, (re, im) pairs
+  for (long long j = 0; j < n; ++j)
+    for (long long i = 0; i < n; ++i) {
+      rm[2 * ((size_t)i * n + j)] = Ainv[2 * ((size_t)j * n + i)];
+      rm[2 * ((size_t)i * n + j) + 1] = Ainv[2 * ((size_t)j * n + i) + 1];
+    }
+  MG_TRY(S.Ainv.alloc(rm.size()));
+  HIP_TRY(hipMemcpy(S.Ainv.p, rm.data(), rm.size() * sizeof(double), hipMemcpyHostToDevice));
+  S.n_coarse = n;
+  S.coarse_set = true;
+  S.coarse_lu = false;
+  S.finalized = false;
+  return MG_OK;
+}
+
+int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* Lptr, const long long* Lcol, const double* Lval,
+                                const long long* Uptr, const long long* Ucol, const double* Uval, const long long* p,
+                                const long long* q) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, 1));
+  if (n < 1 || !Lptr || !Lcol || !Lval || !Uptr || !Ucol || !Uval || !p || !q) return fail(MG_ERR_INVALID, "null or empty factor");
+  if (n >= (1LL << 31) - 1 || Lptr[n] - 1 >= (1LL << 31) || Uptr[n] - 1 >= (1LL << 31))
+    return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
+  if (Lptr[0] != 1 || Uptr[0] != 1) return fail(MG_ERR_INVALID, "row pointers must be 1-based");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  const size_t N = (size_t)n;
+  std::vector<int> LP, LC, LO, LL, UP, UC, UO, UL, pp(N), qq(N);
+  MG_TRY(lu_convert(n, Lptr, Lcol, true, LP, LC, LO, LL));
+  MG_TRY(lu_convert(n, Uptr, Ucol, false, UP, UC, UO, UL));
+  for (size_t i = 0; i < N; ++i) {
+    if (p[i] < 1 || p[i] > n || q[i] < 1 || q[i] > n) return fail(MG_ERR_INVALID, "permutation entry out of range");
+    pp[i] = (int)(p[i] - 1);
+    qq[i] = (int)(q[i] - 1);
+  }
+  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) -> int {
+    MG_TRY(d.alloc(v.size()));
+    HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+    return MG_OK;
+  };
+  MG_TRY(up_i(S.luLptr, LP)); MG_TRY(up_i(S.luLcol, LC)); MG_TRY(up_i(S.luLorder, LO)); MG_TRY(up_i(S.luLlvl, LL));
+  MG_TRY(up_i(S.luUptr, UP)); MG_TRY(up_i(S.luUcol, UC)); MG_TRY(up_i(S.luUorder, UO)); MG_TRY(up_i(S.luUlvl, UL));
+  MG_TRY(up_i(S.luP, pp)); MG_TRY(up_i(S.luQ, qq));
+  MG_TRY(S.luLval.alloc(2 * LC.size()));
+  MG_TRY(S.luUval.alloc(2 * UC.size()));
+  HIP_TRY(hipMemcpy(S.luLval.p, Lval, 2 * LC.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(S.luUval.p, Uval, 2 * UC.size() * sizeof(double), hipMemcpyHostToDevice));
+  S.nLlvl = (int)LL.size() - 1;
+  S.nUlvl = (int)UL.size() - 1;
+  S.n_coarse = n;
+  S.coarse_set = true;
+  S.coarse_lu = true;
+  S.Ainv.release();
+  S.finalized = false;
+  return MG_OK;
+}
+
+int mg_cycle_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long x_is_zero) {
+  MG_TRY(cx_check_ready(h, n, nrhs));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  CxLevel& L0 = S.lev[0];
+  bool xz = (x_is_zero == 1);
+  if (x_is_zero < 0) xz = cx_host_zero(x, n);   // norm(x) > 0.0 decides (MGcycle.jl:29)
+  const size_t bytes = 2 * sizeof(double) * (size_t)n;
+  int xi = 0;
+  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->stream));
+  if (!xz) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->stream));
+  MG_TRY(cx_cycle(h, 0, cxp(S.stage_b), xi, xz, h->cycle));
+  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(spin_sync(h->stream));
+  return MG_OK;
+}
+
+int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
+                  long long* iters, double* resvec) {
+  MG_TRY(cx_check_ready(h, n, nrhs));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  CxLevel& L0 = S.lev[0];
+  const size_t bytes = 2 * sizeof(double) * (size_t)n;
+  const cx_t* bd = cxp(S.stage_b);
+  int xi = 0;
+  bool xz = cx_host_zero(x, n);
+  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->stream));
+  double res2 = 0.0;
+  if (xz) {   // SolveFuncs.jl:14-21
+    MG_TRY(cx_norm2(h, bd, n, &res2));
+  } else {
+    HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->stream));
+    MG_TRY(cx_residual_norm2(h, L0, bd, cxp(L0.x[xi]), cxp(L0.r), &res2));
+  }
+  const double res0 = std::sqrt(res2);
+  if (resvec) resvec[0] = res0;
+  long long it = 0;
+  for (long long count = 1; count <= maxIter; ++count) {   // l.23-37
+    MG_TRY(cx_cycle(h, 0, bd, xi, xz, h->cycle));
+    xz = false;
+    MG_TRY(cx_residual_norm2(h, L0, bd, cxp(L0.x[xi]), cxp(L0.r), &res2));
+    ++it;
+    const double res = std::sqrt(res2);
+    if (resvec) resvec[count] = res;
+    if (res / res0 < tol) break;
+  }
+  if (xz) HIP_TRY(hipMemsetAsync(L0.x[xi].p, 0, bytes, h->stream));   // maxIter = 0 from x = 0
+  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(spin_sync(h->stream));
+  if (iters) *iters = it;
+  return MG_OK;
+}
+
+int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* x, const double* beta,
+                 double* y, long long nrhs) {
+  MG_TRY(cx_level_ok(h, level));
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
+  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
+  if (!alpha || !beta || !x || !y) return fail(MG_ERR_INVALID, "null argument");
+  if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
+  CxLevel& L = S.lev[(size_t)level - 1];
+  if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
+  const CxMat& M = which == MG_OP_A ? L.A : which == MG_OP_P ? L.P : L.R;
+  (void)hipSetDevice(h->device);
+  const long long nr = M.n_rows, nc = M.n_cols;
+  const cx_t a = cx_t{alpha[0], alpha[1]}, bt = cx_t{beta[0], beta[1]};
+  const bool bz = bt.x == 0.0 && bt.y == 0.0;
+  DevBuf<double> dx, dy;   // (released below on every path)
+  int rc = dx.alloc(2 * (size_t)nc);
+  if (rc == MG_OK) rc = dy.alloc(2 * (size_t)nr);
+  if (rc == MG_OK && hipMemcpyAsync(dx.p, x, 2 * sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "upload of x failed");
+  if (rc == MG_OK && !bz && hipMemcpyAsync(dy.p, y, 2 * sizeof(double) * (size_t)nr, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "upload of y failed");
+  if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxp(dx), cxp(dy), nullptr, nullptr, nullptr, a, bt);
+  if (rc == MG_OK && hipMemcpyAsync(y, dy.p, 2 * sizeof(double) * (size_t)nr, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "download of the product failed");
+  if (spin_sync(h->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_spmv_CF64: stream failed");
+  dx.release();
+  dy.release();
+  return rc;
+}
+
+}  // extern "C"

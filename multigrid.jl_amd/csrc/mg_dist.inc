@@ -640,6 +640,7 @@ int mg_dist_set_tail_INT64(mg_dist* h, mg_hierarchy* tail, long long n_tail, lon
                            const long long* gather_index) {
   UploadFence upload_fence;
   if (!h || !tail || !gather_index || n_tail < 1 || max_tail < 1 || own_tail < 0 || own_tail > max_tail) return fail(MG_ERR_INVALID, "bad tail description");
+  MG_CF64_UNSUPPORTED(tail);
   (void)hipSetDevice(h->device);
   h->tail = tail;
   h->n_tail = n_tail;
@@ -864,6 +865,7 @@ int mg_set_stream(mg_hierarchy* h, void* stream) {
 // Enqueue one cycle and return without waiting (x_is_zero must be 0 or 1).
 int mg_cycle_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
                             long long x_is_zero) {
+  MG_REAL_ONLY(h);
   MG_TRY(check_ready(h, n, nrhs));
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for the asynchronous cycle");
@@ -876,6 +878,7 @@ int mg_cycle_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, long lo
 // level above it is sharded and its K-branch lands here.  A one-level hierarchy just solves.  Asynchronous like
 // mg_cycle_async_dev_FP64 as far as the stream goes (the FGMRES dots are host-visible, as everywhere in a K-cycle).
 int mg_kcycle_step_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n) {
+  MG_CF64_UNSUPPORTED(h);
   MG_TRY(check_ready(h, n, 1));
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   (void)hipSetDevice(h->device);
@@ -902,6 +905,7 @@ int mg_kcycle_step_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, l
 // fine box), b's owned rows must be valid, x's owned rows are valid on return; norms are over all ranks' owned rows.
 // =================================================================================================================
 int mg_ghost_attach(mg_hierarchy* h, long long rank, long long world, long long nlevels_sharded, const char* unique_id128) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (world < 1 || rank < 0 || rank >= world || nlevels_sharded < 1 || nlevels_sharded >= h->nlevels)
     return fail(MG_ERR_INVALID, "bad rank/world/levels (%lld/%lld, %lld sharded of %lld)", rank, world, nlevels_sharded, h->nlevels);
@@ -933,6 +937,7 @@ int mg_ghost_attach(mg_hierarchy* h, long long rank, long long world, long long 
 // side stream: RCCL serialises the operations of ONE communicator in issue order, whatever their streams; with its own
 // communicator the fine level's exchange runs beside the coarse cycle and its all-reduces instead of in front of them.
 int mg_ghost_set_side_comm(mg_hierarchy* h, const char* unique_id128) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h || !h->ghost || !unique_id128) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
   mg_ghost* g = h->ghost;
   if (!g->comm) return fail(MG_ERR_STATE, "this handle was attached without an RCCL communicator");
@@ -945,6 +950,7 @@ int mg_ghost_set_side_comm(mg_hierarchy* h, const char* unique_id128) {
 }
 
 int mg_ghost_set_exchange_plugin(mg_hierarchy* h, mg_exchange_fn fn, void* user) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h || !h->ghost || !fn) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
   if (h->ghost->comm) return fail(MG_ERR_STATE, "this handle was attached with an RCCL communicator");
   h->ghost->plug = fn;
@@ -960,6 +966,7 @@ int mg_ghost_set_exchange_plugin(mg_hierarchy* h, mg_exchange_fn fn, void* user)
 int mg_ghost_set_level_INT64(mg_hierarchy* h, long long level, const long long* ext, const long long* own_lo, const long long* own_hi,
                              long long gmin, long long n_send, const long long* send_idx, const long long* send_splits,
                              long long n_recv, const long long* recv_idx, const long long* recv_splits) {
+  MG_CF64_UNSUPPORTED(h);
   UploadFence upload_fence;
   if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
   mg_ghost* g = h->ghost;
@@ -1019,6 +1026,7 @@ int mg_ghost_set_level_INT64(mg_hierarchy* h, long long level, const long long* 
 }
 
 int mg_ghost_finalize(mg_hierarchy* h) {
+  MG_CF64_UNSUPPORTED(h);
   UploadFence upload_fence;
   if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
   if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
@@ -1090,6 +1098,7 @@ int mg_ghost_finalize(mg_hierarchy* h) {
 // unpack kernels, nothing travels, sums stay local.  The numbers such a handle computes mean nothing; its step time is what one
 // GPU of the N spends on compute, redundant ghost rows included (the ceiling of the strong scaling with free communication).
 int mg_ghost_set_dry(mg_hierarchy* h, long long on) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
   if (h->ghost->comm) return fail(MG_ERR_STATE, "this handle was attached with an RCCL communicator");
   h->ghost->dry = on != 0;
@@ -1097,18 +1106,21 @@ int mg_ghost_set_dry(mg_hierarchy* h, long long on) {
 }
 // exchanges started and doubles sent by this rank since mg_ghost_attach (what the schedule really communicates)
 int mg_ghost_stats(mg_hierarchy* h, long long* exchanges, long long* doubles_sent) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
   if (exchanges) *exchanges = h->ghost->n_exchanges;
   if (doubles_sent) *doubles_sent = h->ghost->n_sent;
   return MG_OK;
 }
 int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h || !h->ghost || !count) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
   *count = h->ghost->n_allreduce;
   return MG_OK;
 }
 // Ranks of this handle's communicator AS RCCL REPORTS THEM (ncclCommCount); 0 with the plug-in transport / a world of one without RCCL.
 int mg_ghost_comm_count(mg_hierarchy* h, long long* count) {
+  MG_CF64_UNSUPPORTED(h);
   if (!h || !h->ghost || !count) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
   *count = 0;
   if (!h->ghost->comm) return MG_OK;

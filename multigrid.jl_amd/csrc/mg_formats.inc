@@ -2120,4 +2120,67 @@ Csr* pick(mg_hierarchy* h, long long level, long long which) {
   return nullptr;
 }
 
+
+// ---- sparse triangular factors in parLU's layout (mg_set_coarse_lu_FP64_INT64 / _CF64_INT64) -------------------------
+// Dependency levels of the rows [0, n-M) of a triangular factor; the trailing M rows are handled apart (for U they
+// are solved BEFORE every level, for L after all of them), so they impose no ordering here.
+void lu_levels(long long n, const std::vector<int>& P, const std::vector<int>& Cc, bool lower, int M, std::vector<int>& order,
+               std::vector<int>& lvlptr) {
+  const int na = (int)n - M;
+  std::vector<int> lvl((size_t)na, 0);
+  int nl = 0;
+  if (lower) {
+    for (int i = 0; i < na; ++i) {
+      int m = 0;
+      for (int k = P[(size_t)i]; k < P[(size_t)i + 1] - 1; ++k) m = std::max(m, lvl[(size_t)Cc[(size_t)k]] + 1);
+      lvl[(size_t)i] = m;
+      nl = std::max(nl, m + 1);
+    }
+  } else {
+    for (int i = na - 1; i >= 0; --i) {
+      int m = 0;
+      for (int k = P[(size_t)i] + 1; k < P[(size_t)i + 1]; ++k)
+        if (Cc[(size_t)k] < na) m = std::max(m, lvl[(size_t)Cc[(size_t)k]] + 1);
+      lvl[(size_t)i] = m;
+      nl = std::max(nl, m + 1);
+    }
+  }
+  lvlptr.assign((size_t)nl + 1, 0);
+  for (int i = 0; i < na; ++i) lvlptr[(size_t)lvl[(size_t)i] + 1]++;
+  for (int l = 0; l < nl; ++l) lvlptr[(size_t)l + 1] += lvlptr[(size_t)l];
+  order.resize((size_t)na);
+  std::vector<int> pos(lvlptr.begin(), lvlptr.end() - 1);
+  for (int i = 0; i < na; ++i) order[(size_t)pos[(size_t)lvl[(size_t)i]]++] = i;
+}
+
+// 1-based Int64 CSR factor -> 0-based int32 arrays, checked (L: diagonal last, U: diagonal first), and its levels.
+int lu_convert(long long n, const long long* ptr, const long long* col, bool lower, std::vector<int>& P, std::vector<int>& Cc,
+               std::vector<int>& order, std::vector<int>& lvlptr) {
+  const size_t N = (size_t)n;
+  const long long nnz = ptr[n] - 1;
+  P.resize(N + 1);
+  Cc.resize((size_t)nnz);
+  for (size_t i = 0; i <= N; ++i) P[i] = (int)(ptr[i] - 1);
+  for (long long k = 0; k < nnz; ++k) {
+    const long long c = col[k] - 1;
+    if (c < 0 || c >= n) return fail(MG_ERR_INVALID, "factor column index out of range");
+    Cc[(size_t)k] = (int)c;
+  }
+  if (lower) {
+    for (size_t i = 0; i < N; ++i) {
+      if (P[i + 1] - P[i] < 1 || Cc[(size_t)P[i + 1] - 1] != (int)i) return fail(MG_ERR_INVALID, "L: the diagonal must be the last entry of row %zu", i + 1);
+      for (int k = P[i]; k < P[i + 1] - 1; ++k)
+        if (Cc[(size_t)k] >= (int)i) return fail(MG_ERR_INVALID, "L is not lower triangular");
+    }
+  } else {
+    for (size_t ii = 0; ii < N; ++ii) {
+      if (P[ii + 1] - P[ii] < 1 || Cc[(size_t)P[ii]] != (int)ii) return fail(MG_ERR_INVALID, "U: the diagonal must be the first entry of row %zu", ii + 1);
+      for (int k = P[ii] + 1; k < P[ii + 1]; ++k)
+        if (Cc[(size_t)k] <= (int)ii) return fail(MG_ERR_INVALID, "U is not upper triangular");
+    }
+  }
+  lu_levels(n, P, Cc, lower, 0, order, lvlptr);
+  return MG_OK;
+}
+
 }  // namespace

@@ -3741,25 +3741,38 @@ __global__ __launch_bounds__(BLK) void dense_apply(const double* __restrict__ Ai
 // level sets are computed on the host at setup), one wavefront per row, a workgroup barrier between levels:
 // no inter-workgroup waiting, so nothing can hang.  Latency-bound by design (a coarse level).
 // ------------------------------------------------------------------------------------------------
-struct LuDev {
+template <typename T>
+struct LuDevT {
   int n;
-  const int* Lptr; const int* Lcol; const double* Lval;   // CSR, diagonal last
-  const int* Uptr; const int* Ucol; const double* Uval;   // CSR, diagonal first
+  const int* Lptr; const int* Lcol; const T* Lval;        // CSR, diagonal last
+  const int* Uptr; const int* Ucol; const T* Uval;        // CSR, diagonal first
   const int* p; const int* q;                             // 0-based permutations
   const int* Lorder; const int* Llvl; int nLlvl;          // rows sorted by level, level pointers
   const int* Uorder; const int* Ulvl; int nUlvl;
 };
+typedef LuDevT<double> LuDev;
+
+// value-type arithmetic of the sweep: T = double (the FP64 handles) or the interleaved complex d2_t (CF64 handles)
+__device__ __forceinline__ double lu_mul(double a, double b) { return a * b; }
+__device__ __forceinline__ double lu_div(double a, double b) { return a / b; }
+__device__ __forceinline__ double lu_shfl_xor(double a, int o) { return __shfl_xor(a, o); }
+__device__ __forceinline__ d2_t lu_mul(d2_t a, d2_t b) { return d2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ d2_t lu_div(d2_t a, d2_t b) {
+  const double s = b.x * b.x + b.y * b.y;
+  return d2_t{(a.x * b.x + a.y * b.y) / s, (a.y * b.x - a.x * b.y) / s};
+}
+__device__ __forceinline__ d2_t lu_shfl_xor(d2_t a, int o) { return d2_t{__shfl_xor(a.x, o), __shfl_xor(a.y, o)}; }
 
 // One triangular sweep over the dependency levels.  A level with >= 16 rows gives every wavefront its own rows; a
 // level with fewer rows (the dense trailing supernodes of a factor are chains of single-row levels) splits each row
 // over g = 16/rows wavefronts and combines their partial sums through LDS.  Up to 4 right-hand-side columns travel
 // together (y is row-interleaved like every other device vector).
-template <bool LOWER>
+template <bool LOWER, typename T>
 __device__ __forceinline__ void sptrsv_sweep(const int* __restrict__ ptr, const int* __restrict__ col,
-                                             const double* __restrict__ val, const int* __restrict__ order,
+                                             const T* __restrict__ val, const int* __restrict__ order,
                                              const int* __restrict__ lvl, int nlvl, const int* __restrict__ perm,
-                                             const double* __restrict__ b, double* y, int nrhs, int c0, int nc,
-                                             double (*sred)[4]) {
+                                             const T* __restrict__ b, T* y, int nrhs, int c0, int nc,
+                                             T (*sred)[4]) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   for (int l = 0; l < nlvl; ++l) {
     const int t0 = lvl[l], t1 = lvl[l + 1], cnt = t1 - t0;
@@ -3770,23 +3783,23 @@ __device__ __forceinline__ void sptrsv_sweep(const int* __restrict__ ptr, const 
       const int row = order[t];
       const int s = LOWER ? ptr[row] : ptr[row] + 1;
       const int e = LOWER ? ptr[row + 1] - 1 : ptr[row + 1];
-      double acc[4] = {0.0, 0.0, 0.0, 0.0};
+      T acc[4] = {T{}, T{}, T{}, T{}};
       for (int k = s + part * 64 + lane; k < e; k += 64 * g) {
-        const double v = val[k];
-        const double* yy = y + (size_t)col[k] * nrhs + c0;
+        const T v = val[k];
+        const T* yy = y + (size_t)col[k] * nrhs + c0;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          if (u < nc) acc[u] += v * yy[u];
+          if (u < nc) acc[u] += lu_mul(v, yy[u]);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        for (int o = 32; o > 0; o >>= 1) acc[u] += __shfl_xor(acc[u], o);
+        for (int o = 32; o > 0; o >>= 1) acc[u] += lu_shfl_xor(acc[u], o);
       if (g == 1) {
         if (lane < nc) {
-          const double dg = val[LOWER ? e : s - 1];
-          const double rhs = LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
-          const double a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-          y[(size_t)row * nrhs + c0 + lane] = (rhs - a) / dg;
+          const T dg = val[LOWER ? e : s - 1];
+          const T rhs = LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
+          const T a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+          y[(size_t)row * nrhs + c0 + lane] = lu_div(rhs - a, dg);
         }
       } else if (lane < 4) {
         sred[wave][lane] = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
@@ -3797,20 +3810,21 @@ __device__ __forceinline__ void sptrsv_sweep(const int* __restrict__ ptr, const 
       const int t = t0 + wave / g;
       if (part == 0 && t < t1 && lane < nc) {
         const int row = order[t];
-        double a = 0.0;
+        T a = T{};
         for (int w = 0; w < g; ++w) a += sred[wave + w][lane];
-        const double dg = val[LOWER ? ptr[row + 1] - 1 : ptr[row]];
-        const double rhs = LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
-        y[(size_t)row * nrhs + c0 + lane] = (rhs - a) / dg;
+        const T dg = val[LOWER ? ptr[row + 1] - 1 : ptr[row]];
+        const T rhs = LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
+        y[(size_t)row * nrhs + c0 + lane] = lu_div(rhs - a, dg);
       }
     }
     __syncthreads();
   }
 }
 
-__global__ __launch_bounds__(1024) void sptrsv_lu(LuDev F, const double* __restrict__ b, double* __restrict__ x,
-                                                  double* work, int nrhs) {
-  __shared__ double sred[16][4];
+template <typename T>
+__global__ __launch_bounds__(1024) void sptrsv_lu(LuDevT<T> F, const T* __restrict__ b, T* __restrict__ x,
+                                                  T* work, int nrhs) {
+  __shared__ T sred[16][4];
   for (int c0 = 0; c0 < nrhs; c0 += 4) {
     const int nc = min(4, nrhs - c0);
     sptrsv_sweep<true>(F.Lptr, F.Lcol, F.Lval, F.Lorder, F.Llvl, F.nLlvl, F.p, b, work, nrhs, c0, nc, sred);   // y = L \\ b[p]

@@ -972,7 +972,7 @@ int k_coarse(mg_hierarchy* h, int level, const double* b, double* x) {
     F.Lorder = h->luLorder.p; F.Llvl = h->luLlvl.p; F.nLlvl = h->nLlvl;
     F.Uorder = h->luUorder.p; F.Ulvl = h->luUlvl.p; F.nUlvl = h->nUlvl;
     if (!h->lu_multi) {
-      hipLaunchKernelGGL(mgk::sptrsv_lu, dim3(1), dim3(1024), 0, h->stream, F, b, x, h->luWork.p, (int)h->nrhs);
+      hipLaunchKernelGGL(mgk::sptrsv_lu<double>, dim3(1), dim3(1024), 0, h->stream, F, b, x, h->luWork.p, (int)h->nrhs);
       HIP_TRY(hipGetLastError());
       return MG_OK;
     }

@@ -178,6 +178,17 @@ Options Options::from_env() {
     if (rc_ != MG_OK) return rc_; \
   } while (0)
 
+// The value type of a handle is fixed at creation (mg_create / mg_create_CF64): an FP64 entry point refuses a CF64 handle
+// (MG_ERR_STATE), and the capabilities the CF64 path does not serve say so (MG_ERR_UNSUPPORTED).
+#define MG_REAL_ONLY(h)                                                                                     \
+  do {                                                                                                      \
+    if ((h) && (h)->cx) return fail(MG_ERR_STATE, "%s: FP64 entry point called on a CF64 handle", __func__); \
+  } while (0)
+#define MG_CF64_UNSUPPORTED(h)                                                                              \
+  do {                                                                                                      \
+    if ((h) && (h)->cx) return fail(MG_ERR_UNSUPPORTED, "%s is not served for CF64 handles", __func__);    \
+  } while (0)
+
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
@@ -589,8 +600,11 @@ struct ProfSlot {
 }  // namespace
 
 struct mg_ghost;   // (mg_ghost.inc) geometry, plans and transport of the ghost-layer form of the sharded cycle
+struct CxState;   // mg_complex.inc: the levels of a ComplexF64 handle
+
 struct mg_hierarchy {
   Options opt;
+  CxState* cx = nullptr;       // set by mg_create_CF64: the value type is ComplexF64 and the real levels stay empty
   mg_ghost* ghost = nullptr;   // set by mg_ghost_attach: this hierarchy is one rank's part (extended boxes) of a sharded one
   int device = 0;
   long long nlevels = 0;

@@ -146,6 +146,14 @@ SIGNATURES = {
     "mg_ghost_stats": (C.c_int, [_vp, _lp, _lp]),
     "mg_ghost_comm_count": (C.c_int, [_vp, _lp]),
     "mg_ghost_allreduce_count": (C.c_int, [_vp, _lp]),
+    "mg_create_CF64": (C.c_int, [_ll, _ll, _ll, C.POINTER(_vp)]),
+    "mg_set_operator_CF64_INT64": (C.c_int, [_vp, _ll, _ll, _ll, _ll, _lp, _lp, _dp]),
+    "mg_set_relax_CF64": (C.c_int, [_vp, _ll, _dp, _ll, _ll, _ll]),
+    "mg_set_coarse_dense_inverse_CF64": (C.c_int, [_vp, _ll, _dp]),
+    "mg_set_coarse_lu_CF64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
+    "mg_cycle_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_solve_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
+    "mg_spmv_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _dp, _dp, _dp, _ll]),
     "mg_last_error": (C.c_char_p, []),
     "mg_version": (C.c_char_p, []),
 }
@@ -226,7 +234,14 @@ DENSE_COARSE_MAX = 16384
 
 
 class DeviceHierarchy:
-    """Owns one ``mg_hierarchy`` handle (HBM copy of As/Ps/Rs/relaxPrecs + coarse inverse)."""
+    """Owns one ``mg_hierarchy`` handle (HBM copy of As/Ps/Rs/relaxPrecs + coarse inverse).
+
+    Dtype-aware: a param with VAL = ComplexF64 gets a ComplexDeviceHierarchy (the _CF64 entry points)."""
+
+    def __new__(cls, param=None, *args, **kwargs):
+        if cls is DeviceHierarchy and param is not None and np.dtype(getattr(param, "VAL", np.float64)) == np.complex128:
+            cls = ComplexDeviceHierarchy
+        return super().__new__(cls)
 
     def __init__(self, param, device_id: int = 0, nrhs: Optional[int] = None, options: Optional[dict] = None):
         """options: per-handle format switches (mg_set_option), e.g. {"no_rowclass": 1} forces the streaming formats."""
@@ -719,6 +734,165 @@ class DeviceHierarchy:
         v = C.c_double(0)
         _check(self.lib, self.lib.mg_device_bytes(self.handle, C.byref(v)), "mg_device_bytes")
         return v.value
+
+
+def _c128(a):
+    return a.ctypes.data_as(_dp)
+
+
+class ComplexDeviceHierarchy(DeviceHierarchy):
+    """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F cycles, Jac / SPAI relaxation, dense-inverse or
+    sparse-LU coarsest solve, one right-hand side.  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
+    uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
+    conjugates back.  P and R are real."""
+
+    def __init__(self, param, device_id: int = 0, nrhs: Optional[int] = None, options: Optional[dict] = None):
+        self.lib = load_library()
+        self.handle = _vp()
+        self.nlevels = len(param.As)
+        self.n = int(param.As[0].shape[0])
+        self.nrhs = int(nrhs if nrhs is not None else max(1, param.nrhs))
+        if self.nrhs != 1:
+            raise NotImplementedError("ComplexF64 hierarchies serve one right-hand side on the device")
+        lib = self.lib
+        _check(lib, lib.mg_create_CF64(self.nlevels, 1, int(device_id), C.byref(self.handle)), "mg_create_CF64")
+        try:
+            for key, val in (options or {}).items():
+                _check(lib, lib.mg_set_option(self.handle, key.encode(), float(val)), f"mg_set_option({key})")
+            self._upload(param)
+        except Exception:
+            self.close()
+            raise
+
+    def _set_op(self, level, which, M):
+        if which != MG_OP_A:
+            if np.iscomplexobj(M.data):
+                raise TypeError("P and R of a ComplexF64 hierarchy are real")
+            return super()._set_op(level, which, M)
+        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64) + 1
+        rowval = np.ascontiguousarray(M.indices, dtype=np.int64) + 1
+        nzval = np.ascontiguousarray(np.conj(M.data), dtype=np.complex128)     # the reference's AT values
+        rc = self.lib.mg_set_operator_CF64_INT64(self.handle, level, which, M.shape[0], M.shape[1], _i64(colptr), _i64(rowval),
+                                                 _c128(nzval))
+        _check(self.lib, rc, f"mg_set_operator_CF64(level={level})")
+
+    def _set_relax(self, level, d, pre, post):
+        d = np.ascontiguousarray(d, dtype=np.complex128)
+        _check(self.lib, self.lib.mg_set_relax_CF64(self.handle, level, _c128(d), d.size, int(pre), int(post)),
+               f"mg_set_relax_CF64(level={level})")
+
+    def _upload(self, param):
+        lib = self.lib
+        nl = self.nlevels
+        if param.cycleType == "K" or param.relaxType == "Jac-GMRES":
+            raise NotImplementedError("ComplexF64 hierarchies: cycles V, W, F with the Jac / SPAI smoothers")
+        for l in range(1, nl + 1):
+            self._set_op(l, MG_OP_A, param.As[l - 1])
+            if l < nl:
+                self._set_op(l, MG_OP_P, param.Ps[l - 1])
+                self._set_op(l, MG_OP_R, param.Rs[l - 1])
+                self._set_relax(l, param.relaxPrecs[l - 1], param.relaxPre(l), param.relaxPost(l))
+        _check(lib, lib.mg_set_relax_type(self.handle, 0), "mg_set_relax_type")
+        _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
+        if param.LU is None:
+            raise MGDeviceError("param.LU is empty: run MGsetup first")
+        self._set_coarse(param)
+        _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        self._schedule = self._schedule_of(param)
+
+    def sync_schedule(self, param):
+        sig = self._schedule_of(param)
+        if sig == getattr(self, "_schedule", sig):
+            self._schedule = sig
+            return
+        if param.cycleType == "K" or param.relaxType == "Jac-GMRES":
+            raise NotImplementedError("ComplexF64 hierarchies: cycles V, W, F with the Jac / SPAI smoothers")
+        lib = self.lib
+        for l in range(1, self.nlevels):
+            self._set_relax(l, param.relaxPrecs[l - 1], sig[2][l - 1], sig[3][l - 1])
+        _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
+        _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        self._schedule = sig
+
+    def _set_coarse(self, param, force_sparse: bool = False):
+        """`z = param.LU\\b` (MGcycle.jl:177) from the complex splu: the explicit inverse up to DENSE_COARSE_MAX rows, else the
+        sparse factors in the parLU layout (mg_set_coarse_lu_CF64_INT64)."""
+        import scipy.sparse as sp
+        lib = self.lib
+        nc = int(param.As[-1].shape[0])
+        if param.coarseSolveType == "GMRES":
+            raise NotImplementedError("coarseSolveType='GMRES' is not served for ComplexF64 hierarchies")
+        if nc <= DENSE_COARSE_MAX and not force_sparse:
+            Ainv = np.asfortranarray(param.LU.solve(np.eye(nc, dtype=np.complex128)), dtype=np.complex128)
+            _check(lib, lib.mg_set_coarse_dense_inverse_CF64(self.handle, nc, _c128(Ainv)), "mg_set_coarse_dense_inverse_CF64")
+            return
+        Lp, Lc, Lv, Up, Uc, Uv, p, q = complex_lu_arrays(param.LU)
+        _check(lib, lib.mg_set_coarse_lu_CF64_INT64(self.handle, nc, _i64(Lp), _i64(Lc), _c128(Lv), _i64(Up), _i64(Uc), _c128(Uv),
+                                                    _i64(p), _i64(q)), "mg_set_coarse_lu_CF64")
+
+    def set_nrhs(self, nrhs: int):
+        if int(nrhs) != 1:
+            raise NotImplementedError("ComplexF64 hierarchies serve one right-hand side on the device")
+        _check(self.lib, self.lib.mg_set_nrhs(self.handle, 1), "mg_set_nrhs")
+
+    @staticmethod
+    def _host_block(a, writable=False):
+        if not isinstance(a, np.ndarray) or a.dtype != np.complex128:
+            raise TypeError("expected a complex128 numpy array for a ComplexF64 hierarchy")
+        if a.ndim == 2 and a.shape[1] != 1:
+            raise NotImplementedError("ComplexF64 hierarchies serve one right-hand side on the device")
+        if not a.flags.c_contiguous and not a.flags.f_contiguous:
+            raise ValueError("vectors must be contiguous")
+        if writable and not a.flags.writeable:
+            raise ValueError("x must be writable (it is updated in place)")
+        return a
+
+    def cycle(self, b, x, x_is_zero: int = -1):
+        b = self._host_block(b)
+        x = self._host_block(x, True)
+        _check(self.lib, self.lib.mg_cycle_CF64(self.handle, _c128(b), _c128(x), b.shape[0], 1, int(x_is_zero)), "mg_cycle_CF64")
+        return x
+
+    def solve(self, b, x, tol: float, maxIter: int):
+        b = self._host_block(b)
+        x = self._host_block(x, True)
+        iters = C.c_longlong(0)
+        resvec = np.zeros(int(maxIter) + 1)
+        _check(self.lib, self.lib.mg_solve_CF64(self.handle, _c128(b), _c128(x), b.shape[0], 1, float(tol), int(maxIter),
+                                                C.byref(iters), _f64(resvec)), "mg_solve_CF64")
+        return x, int(iters.value), resvec[: iters.value + 1]
+
+    def spmv(self, level: int, which: int, alpha, x, beta, y):
+        x = self._host_block(x)
+        y = self._host_block(y, True)
+        a = np.array([complex(alpha).real, complex(alpha).imag])
+        bt = np.array([complex(beta).real, complex(beta).imag])
+        _check(self.lib, self.lib.mg_spmv_CF64(self.handle, int(level), int(which), _f64(a), _c128(x), _f64(bt), _c128(y), 1),
+               "mg_spmv_CF64")
+        return y
+
+    def _refuse(self, *args, **kwargs):
+        raise NotImplementedError("the device Krylov drivers, the replace / transpose updates and the device-pointer entry points "
+                                  "serve FP64 hierarchies only; precondition a Krylov method with getMultigridPreconditioner")
+
+    pcg = bicgstab = fgmres = cycle_mixed_f32 = pcg_dev = block_pcg_dev = block_bicgstab_dev = block_fgmres_dev = _refuse
+    bicgstab_dev = fgmres_dev = cycle_dev = solve_dev = spmv_dev = fused_dev = sweep_residual_dev = four_stage_dev = _refuse
+    replace_values = replace_matrix = transpose_hierarchy = get_values = cycle_async_dev = _refuse
+
+
+def complex_lu_arrays(lu):
+    """A complex scipy splu in the parLU layout (deps/src/parLU.cpp:120-190): CSR L with the diagonal last, CSR U with the
+    diagonal first, 1-based Int64 pointers / indices, complex values, p and q with A[p, q] = L U."""
+    import scipy.sparse as sp
+    L = sp.csr_matrix(lu.L)
+    U = sp.csr_matrix(lu.U)
+    L.sort_indices()
+    U.sort_indices()
+    a64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+    c128 = lambda a: np.ascontiguousarray(a, dtype=np.complex128)
+    p = a64(np.argsort(lu.perm_r)) + 1
+    q = a64(np.argsort(lu.perm_c)) + 1
+    return (a64(L.indptr) + 1, a64(L.indices) + 1, c128(L.data), a64(U.indptr) + 1, a64(U.indices) + 1, c128(U.data), p, q)
 
 
 class DeviceOperator:

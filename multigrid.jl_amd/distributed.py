@@ -506,6 +506,8 @@ class DistributedHierarchy:
         """The Python-sequenced schedule implements the pointwise smoothers and V/W/F cycles; the native sequencer
         (mg_dist_*) also the Jac-GMRES smoother and the K-cycle (all-reduced dots).  Anything else must fail loudly rather
         than silently run a different method."""
+        if np.dtype(getattr(param, "VAL", np.float64)) == np.complex128:
+            raise NotImplementedError("ComplexF64 hierarchies run on one GPU: the multi-GPU cycle serves VAL=Float64")
         relax_ok = ("Jac", "SPAI", "Jac-GMRES") if native else ("Jac", "SPAI")
         cycle_ok = ("V", "W", "F", "K") if native else ("V", "W", "F")
         if param.relaxType not in relax_ok:

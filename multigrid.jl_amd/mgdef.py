@@ -61,10 +61,11 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
-    Only ``Float64``/``Int64`` are on the device path (fp32/complex deliberately off).
+    ``VAL`` is ``Float64`` or ``ComplexF64`` (np.complex128: the _CF64 entry points, single GPU, V/W/F cycles, Jac/SPAI);
+    every other value type is refused.
     """
-    if np.dtype(VAL) != np.float64:
-        raise TypeError("only VAL=Float64 is supported on the device path")
+    if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
+        raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path")
     if np.dtype(IND) != np.int64:
         raise TypeError("only IND=Int64 is supported")
     pre = relaxPre if callable(relaxPre) else (lambda level, _k=int(relaxPre): _k)
@@ -75,7 +76,12 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    relativeTol=float(relativeTol), relaxType=str(relaxType), relaxParam=relaxParam,
                    relaxPre=pre, relaxPost=post, cycleType=cycleType, coarseSolveType=str(coarseSolveType),
                    strongConnParam=float(strongConnParam), FilteringParam=float(FilteringParam),
-                   transferOperatorType=str(transferOperatorType), VAL=np.float64, IND=np.int64)
+                   transferOperatorType=str(transferOperatorType), VAL=np.dtype(VAL).type, IND=np.int64)
+
+
+def is_complex(param: MGparam) -> bool:
+    """VAL = ComplexF64: the hierarchy is served by the _CF64 entry points."""
+    return np.dtype(param.VAL) == np.complex128
 
 
 def hierarchyExists(param: MGparam) -> bool:

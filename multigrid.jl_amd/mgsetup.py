@@ -15,7 +15,7 @@ import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-from .mgdef import MGparam, destroyCoarsestLU, _release_device
+from .mgdef import MGparam, destroyCoarsestLU, _release_device, is_complex
 from .transfer_operators import getFWInterp
 
 
@@ -36,7 +36,7 @@ def getMultilevelOperatorConstructor(param, getOperator, restrictParams):
 
 
 def _as_csr(A):
-    A = sp.csr_matrix(A, dtype=np.float64)
+    A = sp.csr_matrix(A, dtype=np.complex128 if np.iscomplexobj(A.data if sp.issparse(A) else A) else np.float64)
     A.sort_indices()
     return A
 
@@ -48,6 +48,12 @@ def getSPAIprec(A):
     (equal to the row norm only for symmetric A).
     """
     A = _as_csr(A)
+    if np.iscomplexobj(A.data):
+        # complex VAL: Q = conj(AT[i,i]) / sum_j |AT[i,j]|^2 of the reference's AT = A^H (MGsetup.jl:359-362, real^2 + imag^2):
+        # the diagonal of AT is conj(diag(A)), its row i is column i of A conjugated.  (Applied as x += d.*r through A's
+        # own diagonal, d = omega * conj(diag(A)) / colsumsq|A| - the conj of getRelaxPrec's conj(relaxParam*Q), l.148-149.)
+        s = np.bincount(A.indices, weights=A.data.real ** 2 + A.data.imag ** 2, minlength=A.shape[1])
+        return np.conj(A.diagonal()) / s
     from .hostlib import col_sumsq
     s = col_sumsq(A)                                # (thread-parallel on the host; the scipy / numpy line below otherwise)
     if s is None:
@@ -56,7 +62,18 @@ def getSPAIprec(A):
 
 
 def getRelaxPrec(A, relaxType: str, relaxParam=1.0):
-    """Jac: d = omega/diag (MGsetup.jl:145-147).  SPAI: d = omega*diag/colnorm^2 (l.148-149)."""
+    """Jac: d = omega/diag (MGsetup.jl:145-147).  SPAI: d = omega*diag/colnorm^2 (l.148-149).
+
+    Complex A (the applied operator, = the reference's AT^H): the reference's d = conj(relaxParam ./ diag(AT)) and
+    conj(relaxParam*getSPAIprec(AT)) become d = omega/diag(A) and d = omega*conj(diag(A))/colsumsq|A| - for a real A both
+    are the formulas above."""
+    if np.iscomplexobj(A.data if sp.issparse(A) else A):
+        A = _as_csr(A)
+        if relaxType in ("Jac", "Jac-GMRES"):
+            return np.ascontiguousarray(float(relaxParam) / A.diagonal(), dtype=np.complex128)
+        if relaxType == "SPAI":
+            return np.ascontiguousarray(float(relaxParam) * getSPAIprec(A), dtype=np.complex128)
+        raise ValueError("Unknown relaxation type !!!!")
     if relaxType in ("Jac", "Jac-GMRES"):
         return np.ascontiguousarray(float(relaxParam) / _as_csr(A).diagonal(), dtype=np.float64)
     if relaxType == "SPAI":
@@ -74,6 +91,10 @@ def galerkin(R, A, P):
     """A_c = R*(A*P): the CSR view of ``Act = Ps[l]*AT*Rs[l]`` evaluated left to right (MGsetup.jl:102).
     The reference's serial Julia SpGEMM is the bulk of its setup time; here it is row-parallel on the host
     (csrc/mg_host.cpp) - still CPU, still before the device ever sees the hierarchy."""
+    if np.iscomplexobj(A.data):    # complex VAL: scipy's SpGEMM (real P, R; host setup speed is not a goal here)
+        Ac = (R @ (A @ P)).tocsr()
+        Ac.sort_indices()
+        return Ac
     from .hostlib import galerkin_dense_gpu, galerkin_dense_gpu_ok, galerkin_sparse_gpu, galerkin_sparse_gpu_ok, spgemm
     # (opt-in, MG_SETUP_GPU=1: the largest products of an SA-AMG setup on the GPU - same pattern, values to rounding; hostlib.py)
     if galerkin_dense_gpu_ok(A, P):        # nearly dense levels: dense GEMMs
@@ -96,7 +117,8 @@ def defineCoarsestAinv(param: MGparam, Ac) -> None:
         # which only broadcasts for a scalar relaxParam
         if isinstance(param.relaxParam, (list, tuple, np.ndarray)):
             raise ValueError("coarseSolveType='GMRES' needs a scalar relaxParam (MGsetup.jl:334 broadcasts it over diag(AT))")
-        param.LU = np.ascontiguousarray(float(param.relaxParam) / _as_csr(Ac).diagonal(), dtype=np.float64)
+        Acs = _as_csr(Ac)
+        param.LU = np.ascontiguousarray(float(param.relaxParam) / Acs.diagonal(), dtype=Acs.dtype)
         return
     param.LU = coarse_lu(Ac)
 
@@ -106,6 +128,17 @@ def coarse_lu(Ac):
     A+A'; SuperLU's closest ordering is MMD on A'+A (half the fill of its COLAMD default on these operators: 18M vs
     40M nonzeros per factor on a 33^3 27-point level)."""
     return spla.splu(sp.csc_matrix(Ac), permc_spec="MMD_AT_PLUS_A")
+
+
+def _of_val(param: MGparam, A):
+    """The operator in param.VAL: a complex hierarchy holds every A as complex128 (a real fine operator included); a complex
+    operator needs VAL = ComplexF64."""
+    A = _as_csr(A)
+    if is_complex(param):
+        return A.astype(np.complex128) if not np.iscomplexobj(A.data) else A
+    if np.iscomplexobj(A.data):
+        raise TypeError("complex operator with VAL=Float64: use getMGparam(VAL=np.complex128)")
+    return A
 
 
 def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> MGparam:
@@ -122,10 +155,10 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
     geometric = isinstance(ATf, multilevelOperatorConstructor)
     PDEparam = None
     if geometric:
-        As = [_as_csr(ATf.getOperator(Mesh, ATf.param))]
+        As = [_of_val(param, ATf.getOperator(Mesh, ATf.param))]
         PDEparam = ATf.param
     else:
-        As = [_as_csr(ATf)]
+        As = [_of_val(param, ATf)]
     from .operators import getRegularMesh
     Meshes = [Mesh]
     Ps, Rs, relaxPrecs = [], [], []
@@ -149,7 +182,7 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
         Meshes.append(getRegularMesh(Meshes[l - 1].domain, nc))
         if geometric:
             PDEparam = ATf.restrictParams(Meshes[l - 1], Meshes[l], PDEparam, l)
-            Ac = _as_csr(ATf.getOperator(Meshes[l], PDEparam))
+            Ac = _of_val(param, ATf.getOperator(Meshes[l], PDEparam))
         else:
             Ac = galerkin(R, A, P)
         As.append(Ac)
@@ -191,8 +224,8 @@ def adjustMemoryForNumRHS(param: MGparam, nrhs: int = 1, verbose: bool = False) 
 def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
     """New fine matrix, same P/R: recompute relaxPrecs, Galerkin products and the coarse LU (MGsetup.jl:226-270)."""
     relaxParamArr = _relax_param_arr(param)
-    A = _as_csr(A)
-    if param.device is not None and param.relaxType in ("Jac", "Jac-GMRES", "SPAI"):
+    A = _of_val(param, A)
+    if param.device is not None and not is_complex(param) and param.relaxType in ("Jac", "Jac-GMRES", "SPAI"):
         old = param.As[0]
         same = (A.shape == old.shape and A.nnz == old.nnz and np.array_equal(A.indptr, old.indptr)
                 and np.array_equal(A.indices, old.indices))
@@ -216,6 +249,8 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
 
 def transposeHierarchy(param: MGparam, verbose: bool = False) -> None:
     """Transpose every operator, swap P<->R roles (MGsetup.jl:274-318).  Real VAL: conj is a no-op."""
+    if is_complex(param):
+        raise NotImplementedError("transposeHierarchy of a ComplexF64 hierarchy (the device transpose serves FP64 handles)")
     if param.relaxType not in ("Jac", "Jac-GMRES", "SPAI"):
         raise RuntimeError("Not supported")
     param.As[0] = _as_csr(param.As[0].T)

@@ -9,8 +9,14 @@ from __future__ import annotations
 import numpy as np
 
 from .device import DeviceHierarchy, MG_OP_A, MG_OP_P, MG_OP_R
-from .mgdef import MGparam, hierarchyExists
+from .mgdef import MGparam, hierarchyExists, is_complex
 from .mgsetup import adjustMemoryForNumRHS
+
+
+def _real_only(param: MGparam, what: str):
+    if is_complex(param):
+        raise NotImplementedError(f"{what}: the device Krylov drivers serve VAL=Float64; for a ComplexF64 hierarchy precondition "
+                                  "a Krylov method with getMultigridPreconditioner")
 
 
 def _ncols(b):
@@ -80,6 +86,7 @@ def solveCG_MG(A, param: MGparam, b: np.ndarray, x0: np.ndarray, verbose: bool =
     the multigrid cycle as preconditioner, vectors resident on the device across iterations.  ``A`` is accepted
     for signature parity; the operator applied is ``param.As[1]`` on the device (the reference passes the same
     matrix twice).  x0 is updated in place.  ``size(b,2) > 1`` takes the blockCG branch (l.113), also on the device."""
+    _real_only(param, "solveCG_MG")
     adjustMemoryForNumRHS(param, _ncols(b))
     dev = to_device(param)
     x, flag, it, resvec = dev.pcg(b, x0, param.relativeTol, param.maxOuterIter)
@@ -94,6 +101,7 @@ def solveCG_MG(A, param: MGparam, b: np.ndarray, x0: np.ndarray, verbose: bool =
 def solveBiCGSTAB_MG(A, param: MGparam, b: np.ndarray, x0: np.ndarray, verbose: bool = False):
     """``(x, param, iter, nprec) = solveBiCGSTAB_MG(AT,param,b,x0,verbose)`` (SolveFuncs.jl:87-101): KrylovMethods.bicgstb
     with M1 = the multigrid cycle, M2 = identity, on the device; blocks take the blockBiCGSTB branch (l.95)."""
+    _real_only(param, "solveBiCGSTAB_MG")
     adjustMemoryForNumRHS(param, _ncols(b))
     dev = to_device(param)
     x, flag, it, resvec = dev.bicgstab(b, x0, param.relativeTol, param.maxOuterIter)
@@ -108,6 +116,7 @@ def solveGMRES_MG(A, param: MGparam, b: np.ndarray, x0: np.ndarray, flexible: bo
     KrylovMethods.fgmres with the multigrid cycle as preconditioner on the device (always the flexible variant: the
     cycle is a fixed linear operator, so flexible and standard GMRES generate the same iterates); blocks take the
     blockFGMRES branch (l.130)."""
+    _real_only(param, "solveGMRES_MG")
     adjustMemoryForNumRHS(param, _ncols(b))
     dev = to_device(param)
     x, flag, it, resvec = dev.fgmres(b, x0, inner, param.relativeTol, param.maxOuterIter)
