@@ -443,6 +443,21 @@ int mg_kaczmarz_apply_FP64(mg_kaczmarz* k, double* x, const double* b, long long
                            long long sequential);
 int mg_kaczmarz_apply_dev_FP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
                                long long sequential);
+/* ComplexF64 values (applyHybridKaczmarz_CFP64_INT64; ccall at parRelax.jl:71-74), the same arguments: valA = AT.nzval, the
+ * CSC of AT = A^H (the conj of A's CSR values), invD = omega ./ sum(conj(AT).*AT) stored complex, and valA, invD, x and b
+ * interleaved (re, im) doubles, x and b n x nrhs column-major.  Per listed row: inner = (b_i - sum_k conj(valA_k) x_k) *
+ * invD_i; x_k += inner * valA_k, every product and sum rounded separately (C99's plain complex product), so sequential = 1
+ * is bit-identical to the reference binary with numCores = 1.  With sequential = 0, sub-domains racing on a shared node may
+ * read its real and imaginary parts from different updates, as the reference's OpenMP threads may.  The handle records
+ * its value type: an FP64 apply on a CFP64 handle, or a CFP64 apply on an FP64 handle, fails with MG_ERR_STATE and
+ * leaves the handle usable.  Validation, limits and the no-GPU error are those of mg_kaczmarz_create_FP64_INT64. */
+int mg_kaczmarz_create_CFP64_INT64(long long device_id, long long n, const long long* rowptr, const double* valA,
+                                   const long long* colA, long long numDomains, long long domainLength,
+                                   const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out);
+int mg_kaczmarz_apply_CFP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit,
+                            long long sequential);
+int mg_kaczmarz_apply_dev_CFP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
+                                long long sequential);
 int mg_kaczmarz_destroy(mg_kaczmarz* k);
 
 /* ---- stand-alone sparse-factor applier -----------------------------------------------------------------------------

@@ -1774,6 +1774,7 @@ int mg_vec_sumsq_dev_FP64(const double* x, long long len, double* workspace, dou
 // ---- hybrid Kaczmarz relaxation (deps/src/parRelax.h:7-43) -------------------------------------------------------------
 struct mg_kaczmarz {
   int device = 0;
+  bool cx = false;   // value type: false = FP64, true = CFP64 (val, invD, x, b hold interleaved complex doubles)
   long long n = 0, nnz = 0, num_domains = 0, domain_length = 0;
   DevBuf<int> rowptr, col;
   DevBuf<double> val, invD, x, b;
@@ -1781,9 +1782,11 @@ struct mg_kaczmarz {
   hipStream_t stream = nullptr;
 };
 
-int mg_kaczmarz_create_FP64_INT64(long long device_id, long long n, const long long* rowptr, const double* valA,
-                                  const long long* colA, long long numDomains, long long domainLength,
-                                  const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out) {
+// Both value types: vw = doubles per value (1 FP64, 2 CFP64); valA and invD hold nnz and n values of vw doubles.
+static int kaczmarz_create(bool cx, long long device_id, long long n, const long long* rowptr, const double* valA,
+                           const long long* colA, long long numDomains, long long domainLength,
+                           const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out) {
+  const size_t vw = cx ? 2 : 1;
   UploadFence upload_fence;
   if (!out) return fail(MG_ERR_INVALID, "out is null");
   *out = nullptr;
@@ -1813,6 +1816,7 @@ int mg_kaczmarz_create_FP64_INT64(long long device_id, long long n, const long l
   HIP_TRY(hipSetDevice((int)device_id));
   mg_kaczmarz* k = new mg_kaczmarz();
   k->device = (int)device_id;
+  k->cx = cx;
   k->n = n;
   k->nnz = nnz;
   k->num_domains = numDomains;
@@ -1821,13 +1825,13 @@ int mg_kaczmarz_create_FP64_INT64(long long device_id, long long n, const long l
   auto up = [&]() -> int {
     MG_TRY(k->rowptr.alloc(rp.size()));
     MG_TRY(k->col.alloc(ci.size()));
-    MG_TRY(k->val.alloc((size_t)std::max<long long>(nnz, 1)));
-    MG_TRY(k->invD.alloc((size_t)n));
+    MG_TRY(k->val.alloc(vw * (size_t)std::max<long long>(nnz, 1)));
+    MG_TRY(k->invD.alloc(vw * (size_t)n));
     MG_TRY(k->arr.alloc((size_t)(numDomains * domainLength)));
     HIP_TRY(hipMemcpy(k->rowptr.p, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k->col.p, ci.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(k->val.p, valA, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(k->invD.p, invD, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k->val.p, valA, vw * (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k->invD.p, invD, vw * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k->arr.p, ArrIdxs, (size_t)(numDomains * domainLength) * sizeof(unsigned int), hipMemcpyHostToDevice));
     HIP_TRY(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking));
     return MG_OK;
@@ -1839,6 +1843,19 @@ int mg_kaczmarz_create_FP64_INT64(long long device_id, long long n, const long l
   }
   *out = k;
   return MG_OK;
+}
+
+int mg_kaczmarz_create_FP64_INT64(long long device_id, long long n, const long long* rowptr, const double* valA,
+                                  const long long* colA, long long numDomains, long long domainLength,
+                                  const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out) {
+  return kaczmarz_create(false, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
+}
+
+// valA = nzval of the CSC of the reference's AT = A^H (conj of A's CSR values), invD complex: interleaved (re, im) doubles
+int mg_kaczmarz_create_CFP64_INT64(long long device_id, long long n, const long long* rowptr, const double* valA,
+                                   const long long* colA, long long numDomains, long long domainLength,
+                                   const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out) {
+  return kaczmarz_create(true, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
 }
 
 int mg_kaczmarz_destroy(mg_kaczmarz* k) {
@@ -1865,6 +1882,7 @@ int mg_kaczmarz_destroy(mg_kaczmarz* k) {
 int mg_kaczmarz_apply_dev_FP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
                                long long sequential) {
   if (!k || !x_dev || !b_dev || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
+  if (k->cx) return fail(MG_ERR_STATE, "FP64 Kaczmarz entry point called on a CFP64 handle (mg_kaczmarz_apply*_CFP64)");
   (void)hipSetDevice(k->device);
   for (long long it = 0; it < numit; ++it)
     hipLaunchKernelGGL(mgk::hybrid_kaczmarz, dim3(sequential ? 1u : (unsigned)k->num_domains), dim3(64), 0, k->stream,
@@ -1878,6 +1896,7 @@ int mg_kaczmarz_apply_dev_FP64(mg_kaczmarz* k, double* x_dev, const double* b_de
 // Host buffers, exactly the reference's call (parRelax.jl:61-64): x (in/out) and b are n x nrhs column-major.
 int mg_kaczmarz_apply_FP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit, long long sequential) {
   if (!k || !x || !b || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
+  if (k->cx) return fail(MG_ERR_STATE, "FP64 Kaczmarz entry point called on a CFP64 handle (mg_kaczmarz_apply*_CFP64)");
   (void)hipSetDevice(k->device);
   const size_t len = (size_t)k->n * (size_t)nrhs;
   if (k->x.n != len) {
@@ -1887,6 +1906,40 @@ int mg_kaczmarz_apply_FP64(mg_kaczmarz* k, double* x, const double* b, long long
   HIP_TRY(hipMemcpyAsync(k->x.p, x, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
   HIP_TRY(hipMemcpyAsync(k->b.p, b, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
   MG_TRY(mg_kaczmarz_apply_dev_FP64(k, k->x.p, k->b.p, nrhs, numit, sequential));
+  HIP_TRY(hipMemcpyAsync(x, k->x.p, len * sizeof(double), hipMemcpyDeviceToHost, k->stream));
+  HIP_TRY(spin_sync(k->stream));
+  return MG_OK;
+}
+
+// The complex sweeps (applyHybridKaczmarz_CFP64_INT64): x_dev and b_dev are n x nrhs column-major complex, interleaved.
+int mg_kaczmarz_apply_dev_CFP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
+                                long long sequential) {
+  if (!k || !x_dev || !b_dev || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
+  if (!k->cx) return fail(MG_ERR_STATE, "CFP64 Kaczmarz entry point called on an FP64 handle (mg_kaczmarz_create_CFP64_INT64)");
+  (void)hipSetDevice(k->device);
+  for (long long it = 0; it < numit; ++it)
+    hipLaunchKernelGGL(mgk::hybrid_kaczmarz_c, dim3(sequential ? 1u : (unsigned)k->num_domains), dim3(64), 0, k->stream,
+                       k->rowptr.p, k->col.p, reinterpret_cast<const mgk::d2_t*>(k->val.p), k->arr.p, (int)k->num_domains,
+                       (int)k->domain_length, x_dev, b_dev, (int)nrhs, k->n,
+                       reinterpret_cast<const mgk::d2_t*>(k->invD.p), sequential ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(spin_sync(k->stream));
+  return MG_OK;
+}
+
+// Host buffers, exactly the reference's call (parRelax.jl:71-74): x (in/out) and b are n x nrhs column-major complex.
+int mg_kaczmarz_apply_CFP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit, long long sequential) {
+  if (!k || !x || !b || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
+  if (!k->cx) return fail(MG_ERR_STATE, "CFP64 Kaczmarz entry point called on an FP64 handle (mg_kaczmarz_create_CFP64_INT64)");
+  (void)hipSetDevice(k->device);
+  const size_t len = 2 * (size_t)k->n * (size_t)nrhs;   // doubles
+  if (k->x.n != len) {
+    MG_TRY(k->x.alloc(len));
+    MG_TRY(k->b.alloc(len));
+  }
+  HIP_TRY(hipMemcpyAsync(k->x.p, x, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
+  HIP_TRY(hipMemcpyAsync(k->b.p, b, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
+  MG_TRY(mg_kaczmarz_apply_dev_CFP64(k, k->x.p, k->b.p, nrhs, numit, sequential));
   HIP_TRY(hipMemcpyAsync(x, k->x.p, len * sizeof(double), hipMemcpyDeviceToHost, k->stream));
   HIP_TRY(spin_sync(k->stream));
   return MG_OK;

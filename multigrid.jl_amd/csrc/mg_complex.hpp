@@ -185,4 +185,75 @@ __global__ __launch_bounds__(BLK) void cx_dense_matvec(const d2_t* __restrict__ 
   if (lane == 0) x[wave] = acc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Complex hybrid Kaczmarz relaxation (reference native: deps/src/parRelax.h:7-43 built with spValType = double complex,
+// applyHybridKaczmarz_CFP64_INT64).  The schedule of the real hybrid_kaczmarz (mg_kernels.hpp): one wavefront per
+// sub-domain, or one wavefront for all sub-domains in order when `sequential` is set; rows in list order, zero padding
+// skipped, an nrhs loop over column-major blocks.  val is the reference's valA (nzval of the CSC of A^H = conj of A's CSR
+// values) and invD is complex; for row i
+//   inner = b_i - sum_k conj(val_k) x_k   (products in stored order, real and imaginary parts subtracted separately)
+//   inner = inner * invD_i ;  x_k += inner * val_k  for every k of the row.
+// Every product and sum is rounded separately with C99's plain formula (a+bi)(c+di) = (ac-bd) + (ad+bc)i, so the
+// sequential schedule equals the reference binary run with one thread bit for bit.  The helpers below carry their own
+// contract(off): the shared cmul above may be fused into FMAs.  x is read and written through L2 as two relaxed
+// agent-scope 8-byte atomics per value (L1 bypassed): a row sees the rows before it, and other sub-domains see what they
+// happen to see.  Racing sub-domains may read a value whose real and imaginary parts come from different updates (a torn
+// pair); the reference's OpenMP threads race on the same nodes the same way, unsynchronised.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ d2_t kz_cmul(double ar, double ai, double br, double bi) {
+#pragma clang fp contract(off)
+  return d2_t{ar * br - ai * bi, ar * bi + ai * br};
+}
+__device__ __forceinline__ double kz_load(double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void kz_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ __launch_bounds__(64) void hybrid_kaczmarz_c(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                        const d2_t* __restrict__ val, const unsigned int* __restrict__ arr,
+                                                        int num_domains, int domain_length, double* x,
+                                                        const double* __restrict__ b, int nrhs, long long n,
+                                                        const d2_t* __restrict__ invD, int sequential) {
+#pragma clang fp contract(off)   // every product and sum rounded separately, as in the reference's plain C (no FMA)
+  const int lane = threadIdx.x;
+  const int d0 = sequential ? 0 : blockIdx.x, d1 = sequential ? num_domains : blockIdx.x + 1;
+  for (int dom = d0; dom < d1; ++dom) {
+    for (int i = 0; i < domain_length; ++i) {
+      const unsigned int row1 = arr[(size_t)dom * domain_length + i];
+      if (row1 == 0) continue;   // zero padding (wave-uniform)
+      const int row = (int)row1 - 1;
+      const int s = rowptr[row], e = rowptr[row + 1];
+      const d2_t di = invD[row];
+      for (int c = 0; c < nrhs; ++c) {
+        double* xc = x + (size_t)c * 2 * n;            // interleaved (re, im)
+        const double* bc = b + (size_t)c * 2 * n;
+        double ir = bc[2 * (size_t)row], ii = bc[2 * (size_t)row + 1];
+        for (int k0 = s; k0 < e; k0 += 64) {
+          const int k = k0 + lane;
+          d2_t prod = d2_t{0.0, 0.0};
+          if (k < e) {
+            const d2_t v = val[k];
+            double* xp = xc + 2 * (size_t)col[k];
+            prod = kz_cmul(v.x, -v.y, kz_load(xp), kz_load(xp + 1));   // conj(val_k) * x_k
+          }
+          const int cnt = min(64, e - k0);
+          for (int t = 0; t < cnt; ++t) {   // stored order
+            ir = ir - __shfl(prod.x, t);
+            ii = ii - __shfl(prod.y, t);
+          }
+        }
+        const d2_t inner = kz_cmul(ir, ii, di.x, di.y);
+        for (int k = s + lane; k < e; k += 64) {
+          const d2_t v = val[k];
+          double* xp = xc + 2 * (size_t)col[k];
+          const double oldr = kz_load(xp), oldi = kz_load(xp + 1);
+          const d2_t upd = kz_cmul(inner.x, inner.y, v.x, v.y);
+          kz_store(xp, oldr + upd.x);
+          kz_store(xp + 1, oldi + upd.y);
+        }
+        // the next row of this wavefront must see these stores: wait until L2 has acknowledged them
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+    }
+  }
+}
+
 }  // namespace mgk

@@ -123,6 +123,9 @@ SIGNATURES = {
     "mg_kaczmarz_create_FP64_INT64": (C.c_int, [_ll, _ll, _lp, _dp, _lp, _ll, _ll, C.POINTER(C.c_uint), _dp, C.POINTER(_vp)]),
     "mg_kaczmarz_apply_FP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_kaczmarz_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_kaczmarz_create_CFP64_INT64": (C.c_int, [_ll, _ll, _lp, _dp, _lp, _ll, _ll, C.POINTER(C.c_uint), _dp, C.POINTER(_vp)]),
+    "mg_kaczmarz_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_kaczmarz_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
     "mg_kaczmarz_destroy": (C.c_int, [_vp]),
     "mg_dist_unique_id": (C.c_int, [C.c_char_p]),
     "mg_dist_create": (C.c_int, [_ll, _ll, _ll, C.c_char_p, _ll, _ll, _ll, C.POINTER(_vp)]),

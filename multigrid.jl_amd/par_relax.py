@@ -1,6 +1,7 @@
 """Hybrid Kaczmarz relaxation behind the reference's interface (src/Multigrid/parRelax.jl): ``getHybridKaczmarz``,
 ``setupHybridKaczmarz``, ``getHybridKaczmarzPrecond``, ``applyHybridKaczmarz``.  The sweeps run on the device
-(csrc: hybrid_kaczmarz <- deps/src/parRelax.h:7-43) through ``mg_kaczmarz_*``; there is no CPU fallback."""
+(csrc: hybrid_kaczmarz / hybrid_kaczmarz_c <- deps/src/parRelax.h:7-43) through ``mg_kaczmarz_*_FP64`` or, for
+VAL = ComplexF64, ``mg_kaczmarz_*_CFP64``; there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
@@ -30,6 +31,17 @@ class hybridKaczmarz:
     sequential: bool = False            # device schedule: False = one wavefront per sub-domain (the OpenMP analogue)
     _handle: object = field(default=None, repr=False)
     _key: object = field(default=None, repr=False)
+    VAL: object = None                  # value type (hybridKaczmarz{VAL}); None: complex128 if invDiag is complex, else float64
+
+    def __post_init__(self):
+        if self.VAL is None:
+            self.VAL = np.complex128 if self.invDiag is not None and np.iscomplexobj(self.invDiag) else np.float64
+        if np.dtype(self.VAL).kind == "c" and np.dtype(self.VAL) != np.complex128:
+            raise TypeError(f"hybridKaczmarz: VAL = {np.dtype(self.VAL)} is not supported (Float64 or ComplexF64)")
+
+    @property
+    def is_complex(self) -> bool:
+        return np.dtype(self.VAL) == np.complex128
 
     def close(self):
         if self._handle:
@@ -51,16 +63,33 @@ def getHybridKaczmarz(VAL, IND, *args):
         if int(np.prod(numDomains)) < numCores:
             print("*** WARNING: getHybridKaczmarz: numDomains < numCores. ***")
         return hybridKaczmarz(list(numDomains), None, int(numCores), float(omega), np.zeros((1, 1), ArrIdxsType), None,
-                              int(numit), getIdx)
+                              int(numit), getIdx, VAL=np.dtype(VAL).type if np.dtype(VAL).kind == "c" else np.float64)
     AT, mesh, numDomains, getIdx, omega, numCores, numit = args
     p = getHybridKaczmarz(VAL, IND, numDomains, getIdx, omega, numCores, numit)
     return setupHybridKaczmarz(p, AT, mesh)
 
 
+def _row_sums_in_order(A, vals):
+    """sum_k vals_k over each row of the CSR A, added in stored order (one pass per position in the row)."""
+    lens = np.diff(A.indptr)
+    out = np.zeros(A.shape[0])
+    for j in range(int(lens.max(initial=0))):
+        rows = np.nonzero(lens > j)[0]
+        out[rows] += vals[A.indptr[rows] + j]
+    return out
+
+
 def setupHybridKaczmarz(param: hybridKaczmarz, AT, mesh):
-    """invDiag = omega ./ sum(conj(AT).*AT, dims=1) and the index array of the sub-domains (parRelax.jl:31-36)."""
+    """invDiag = convert(Array{VAL,1}, omega ./ sum(conj(AT).*AT, dims=1)) and the index array of the sub-domains
+    (parRelax.jl:31-36).  For a complex AT, conj(a) a = re^2 + im^2 exactly, each row's terms are summed in stored order and
+    invDiag = omega / sum; a ComplexF64 param stores it as complex128 (zero imaginary part), a Float64 param as float64."""
     A = sp.csr_matrix(AT)                     # this package holds the CSR of A where Julia holds the CSC of A' (MGdef.jl:75-77)
-    param.invDiag = param.omega_damp / np.asarray(A.multiply(A).sum(axis=1)).ravel()
+    if np.iscomplexobj(A.data):
+        invd = param.omega_damp / _row_sums_in_order(A, A.data.real * A.data.real + A.data.imag * A.data.imag)
+        param.invDiag = invd.astype(np.complex128) if param.is_complex else invd
+    else:
+        invd = param.omega_damp / np.asarray(A.multiply(A).sum(axis=1)).ravel()
+        param.invDiag = invd.astype(np.complex128) if param.is_complex else invd
     param.ArrIdxs = getIndicesOfCellsArray(mesh, np.zeros(len(param.numDomains), dtype=np.int64), param.numDomains,
                                            param.getIndicesOfCell)
     param.close()
@@ -84,9 +113,21 @@ def _matrix_key(A):
             zlib.crc32(np.ascontiguousarray(A.indices).view(np.uint8)), zlib.crc32(np.ascontiguousarray(A.indptr).view(np.uint8)))
 
 
+def _check_types(param: hybridKaczmarz, **arrays):
+    """The reference dispatches applyHybridKaczmarz on hybridKaczmarz{VAL} with AT, r and x of that VAL (parRelax.jl:59-75):
+    a Float64 param takes no complex array (its imaginary part would be dropped) and a ComplexF64 param only complex128."""
+    for name, a in arrays.items():
+        dt = np.dtype(a.dtype)
+        if param.is_complex and dt != np.complex128:
+            raise TypeError(f"hybridKaczmarz{{ComplexF64}}: {name} is {dt}, expected complex128")
+        if not param.is_complex and dt.kind == "c":
+            raise TypeError(f"hybridKaczmarz{{Float64}}: {name} is {dt}; build the param with VAL = np.complex128")
+
+
 def _device_handle(param: hybridKaczmarz, A, values_changed: bool = True):
     """The uploaded copy of A, re-used while A is the same matrix.  values_changed = False: the caller vouches that a CSR
-    matrix with the same buffers as last time still holds the same values (skips the O(nnz) hash of every call)."""
+    matrix with the same buffers as last time still holds the same values (skips the O(nnz) hash of every call).
+    A ComplexF64 param uploads conj(A.data), the reference's AT.nzval (AT = A'), and a complex invDiag."""
     cheap = _cheap_key(A)
     if param._handle is not None and cheap is not None and cheap == getattr(param, "_cheap", None) and not values_changed:
         return param._handle
@@ -101,13 +142,18 @@ def _device_handle(param: hybridKaczmarz, A, values_changed: bool = True):
     A.sort_indices()
     cp = np.ascontiguousarray(A.indptr, dtype=np.int64) + 1
     rv = np.ascontiguousarray(A.indices, dtype=np.int64) + 1
-    nz = np.ascontiguousarray(A.data, dtype=np.float64)
     arr = np.asfortranarray(param.ArrIdxs, dtype=np.uint32)
-    invd = np.ascontiguousarray(param.invDiag, dtype=np.float64)
     h = C.c_void_p()
-    D._check(lib, lib.mg_kaczmarz_create_FP64_INT64(0, A.shape[0], D._i64(cp), D._f64(nz), D._i64(rv), arr.shape[1], arr.shape[0],
-                                                    arr.ctypes.data_as(C.POINTER(C.c_uint)), D._f64(invd), C.byref(h)),
-             "mg_kaczmarz_create")
+    if param.is_complex:
+        nz = np.ascontiguousarray(np.conj(A.data), dtype=np.complex128)
+        invd = np.ascontiguousarray(param.invDiag, dtype=np.complex128)
+        create, what = lib.mg_kaczmarz_create_CFP64_INT64, "mg_kaczmarz_create_CFP64"
+    else:
+        nz = np.ascontiguousarray(A.data, dtype=np.float64)
+        invd = np.ascontiguousarray(param.invDiag, dtype=np.float64)
+        create, what = lib.mg_kaczmarz_create_FP64_INT64, "mg_kaczmarz_create"
+    D._check(lib, create(0, A.shape[0], D._i64(cp), D._f64(nz), D._i64(rv), arr.shape[1], arr.shape[0],
+                         arr.ctypes.data_as(C.POINTER(C.c_uint)), D._f64(invd), C.byref(h)), what)
     param._handle, param._key, param._cheap = h, key, cheap
     return h
 
@@ -115,22 +161,34 @@ def _device_handle(param: hybridKaczmarz, A, values_changed: bool = True):
 def applyHybridKaczmarz(param: hybridKaczmarz, AT, r: np.ndarray, x: np.ndarray, numDomains: Optional[int] = None,
                         values_changed: bool = True):
     """``numit`` sweeps of x towards AT' x = r, in place (parRelax.jl:59-65).  values_changed = False (not in the reference's
-    signature): the CSR matrix handed over is unchanged since the last call - the uploaded copy is reused without hashing it."""
+    signature): the CSR matrix handed over is unchanged since the last call - the uploaded copy is reused without hashing it.
+    A ComplexF64 param (parRelax.jl:71-74) takes complex128 AT, r and x, and raises TypeError on any other before the device."""
+    _check_types(param, AT=AT, r=np.asarray(r), x=x)
     h = _device_handle(param, AT, values_changed)
     lib = D.load_library()
     if x.ndim == 2 and not x.flags.f_contiguous:
         raise ValueError("x must be column-major (Julia layout)")
+    seq = 1 if param.sequential else 0
+    if param.is_complex:
+        rr = np.asfortranarray(r, dtype=np.complex128)
+        if x.shape != rr.shape or rr.shape[0] != AT.shape[0] or not (x.flags.f_contiguous and x.flags.writeable):
+            raise ValueError("x and r must be n or n x nrhs column-major complex128 arrays of one shape (x writable)")
+        nrhs = 1 if rr.ndim == 1 else rr.shape[1]
+        D._check(lib, lib.mg_kaczmarz_apply_CFP64(h, D._f64(x), D._f64(rr), nrhs, int(param.numit), seq), "mg_kaczmarz_apply_CFP64")
+        return x
     rr = np.asfortranarray(r, dtype=np.float64)
     nrhs = 1 if rr.ndim == 1 else rr.shape[1]
-    D._check(lib, lib.mg_kaczmarz_apply_FP64(h, D._f64(x), D._f64(rr), nrhs, int(param.numit), 1 if param.sequential else 0),
+    D._check(lib, lib.mg_kaczmarz_apply_FP64(h, D._f64(x), D._f64(rr), nrhs, int(param.numit), seq),
              "mg_kaczmarz_apply")
     return x
 
 
 def getHybridKaczmarzPrecond(param: hybridKaczmarz, AT, nrhs: int):
     """r -> x with x = 0 on entry (parRelax.jl:49-57); the returned closure reuses one buffer, as the reference does."""
+    _check_types(param, AT=AT)
     n = AT.shape[1]
-    x = np.zeros(n) if nrhs == 1 else np.zeros((n, nrhs), order="F")
+    vt = np.complex128 if param.is_complex else np.float64
+    x = np.zeros(n, dtype=vt) if nrhs == 1 else np.zeros((n, nrhs), dtype=vt, order="F")
 
     Ac = AT if sp.isspmatrix_csr(AT) else sp.csr_matrix(AT)   # (converted once for every application of the closure)
     _device_handle(param, Ac, True)
