@@ -13,6 +13,11 @@ Workloads (BASELINE.json configs):
   c3            SA-AMG on anisotropic diffusion (edge weights 16:4:1 x log-normal sigma), general CSR, V(1,1) SPAI
   c1            32^3 cells (CPU-plumbing size; parity case, not a bench line)
 Use --cells N to shrink the grid for quick checks (the JSON then names the reduced workload).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the result line; `roofline` and
+`cpu_baseline` are null in it.  --full adds what takes runs of its own: the instrumented per-kernel pass (`roofline`), the
+legs of the default line (C5, generic-CSR pass, div sigma grad, C3 at 128^3), the CPU baseline, and for the sharded paths the
+N = 1 / global-grid reference runs, the per-kernel table and the single-GPU path in the same job.
 """
 import argparse
 import json
@@ -58,6 +63,9 @@ def parse():
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c5"])
     ap.add_argument("--cells", type=int, default=0, help="override cells per dimension")
     ap.add_argument("--levels", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: per-kernel / roofline pass, the legs of the default line, CPU baseline, "
+                         "reference runs and same-job comparisons (the --no-* options below thin this out)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N>1: weak = 256^3 cells PER GPU (N=8 is BASELINE configs[3], 512^3), sharded host setup; "
                          "strong = the same 256^3 grid cut into N boxes (every rank builds the global hierarchy)")
@@ -83,10 +91,12 @@ def parse():
     ap.add_argument("--global-cells", default="", help="single-GPU path: a,b,c cells of a non-cubic grid with h = 1/--cells in every "
                                                        "direction (the GLOBAL grid of an N-GPU weak-scaling run, on one GPU)")
     ap.add_argument("--strong-reference", default="auto", choices=["auto", "on", "off"],
-                    help="N > 1: also run the GLOBAL grid on ONE GPU in the same job (when it fits) and print strong_speedup_vs_n1")
+                    help="N > 1: also run the GLOBAL grid on ONE GPU in the same job (when it fits) and print strong_speedup_vs_n1 "
+                         "(auto: with --full only)")
     ap.add_argument("--n1-reference", default="auto", choices=["auto", "on", "off"],
                     help="--gpus N > 1 started without a launcher: also run the per-GPU workload on one GPU first and report "
-                         "parallel_efficiency_vs_n1 (auto: weak scaling only - a strong-scaling N = 1 run of 512^3 is its own job)")
+                         "parallel_efficiency_vs_n1 (auto: with --full and weak scaling only - a strong-scaling N = 1 run of 512^3 "
+                         "is its own job)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="single-GPU path: after the timed steps write what the last timed solve returned as DIR/<name>.npy "
                          "(float64): resvec, and x - or, when x holds more than 2^21 values, x at a fixed seeded sample of its "
@@ -232,7 +242,9 @@ def strong_reference_run(args, n):
     has the global grid cells x boxes; when that fits one GPU (512^3 = 135 M rows: 40 GB of HBM, ~170 GB of host memory during
     setup) it is also run through the single-GPU path in this job, in a fresh process of its own, BEFORE the N-GPU run.
     Returns its JSON line or None."""
-    if n <= 1 or args.workload != "c2" or args.strong_reference == "off" or os.environ.get("MG_BENCH_SHARE_GPU") == "1":
+    if n <= 1 or args.workload != "c2" or os.environ.get("MG_BENCH_SHARE_GPU") == "1":
+        return None
+    if args.strong_reference == "off" or (args.strong_reference == "auto" and not args.full):
         return None
     from multigrid_jl_amd.distributed import default_domains
     cells = args.cells or 256
@@ -248,7 +260,7 @@ def strong_reference_run(args, n):
     if args.strong_reference != "on" and host_mem_available_gb() < need_gb:
         log(f"[launcher] strong reference skipped: {host_mem_available_gb():.0f} GB of host memory available, ~{need_gb:.0f} GB needed")
         return None
-    a1 = ["--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-generic-pass",
+    a1 = ["--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),      # (a plain run: the headline alone)
           "--workload", "c2", "--cells", str(cells), "--global-cells", ",".join(str(c) for c in gcells)]
     # (under torchrun the other ranks wait in the rendezvous meanwhile: the child gets less than the process group's timeout)
     rc1, sref = run_ranks(a1, 1, {"MG_BENCH_N1_REFERENCE": "1"}, " n1-global", deadline_s=PG_TIMEOUT.total_seconds() - 300.0)
@@ -290,11 +302,10 @@ def launch(args):
             raise SystemExit(f"bench.py --gpus {n}: only {have} GPU(s) visible (set MG_BENCH_ALLOW_SHARE=1 for a functional "
                              f"run with all ranks on one GPU)")
     ref = None
-    if args.n1_reference == "on" or (args.n1_reference == "auto" and args.scaling == "weak"):
-        # the same per-GPU workload on ONE GPU through the single-GPU path (== the default `--gpus 1` line, minus the
-        # CPU baseline and the generic-CSR pass): the denominator of parallel_efficiency_vs_n1
-        a1 = ["--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu-baseline",
-              "--no-generic-pass", "--workload", args.workload]
+    if args.n1_reference == "on" or (args.n1_reference == "auto" and args.full and args.scaling == "weak"):
+        # the same per-GPU workload on ONE GPU through the single-GPU path (a plain `--gpus 1` run): the denominator of
+        # parallel_efficiency_vs_n1
+        a1 = ["--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--workload", args.workload]
         if args.cells:
             a1 += ["--cells", str(args.cells)]
         if args.levels:
@@ -480,6 +491,31 @@ def main():
     dt = float(np.median(region))
     relres = float(resvec[-1] / resvec[0])
     dof_per_s = world * n * nrhs * K / dt
+
+    def result_line(roofline, cpu):
+        return {
+            "metric": "V-cycle DoF-updates/s", "value": round(dof_per_s, 1), "unit": "DoF-updates/s",
+            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(dt / K * 1e3, 4),
+            "higher_is_better": True, "scaling": None, "vs_baseline": None, "dtype": "f64",   # (one GPU: neither weak nor strong)
+            "data": "synthetic",
+            "config": {"workload": f"{desc}, {p.levels} levels, nrhs={nrhs}, fp64"[:118],      # (kept under 120 characters: records of the line cut longer ones)
+                       "step": "one step = one cycle + the residual and norm of solveMG's stopping test (SolveFuncs.jl:24-37)",
+                       "cells": cells, "levels": p.levels, "nrhs": nrhs, "N": n, "nnz": int(A.nnz),
+                       "level_rows": [int(a.shape[0]) for a in p.As], "level_nnz": [int(a.nnz) for a in p.As],
+                       "parallelism": "1 process per GPU"},
+            "timed_regions_ms_per_step": [round(r / K * 1e3, 4) for r in region],
+            "timing": f"median of {len(region)} regions of exactly {K} steps each (barrier + synchronize on both sides)",
+            "relres_after_steps": relres,
+            "setup_s": {"operator": round(t_op, 2), "MGsetup": round(t_setup, 2), "upload": round(t_upload, 2)},
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+        }
+
+    if not args.full:      # a plain run ends with its headline figure; everything below takes runs of its own
+        if rank == 0:
+            emit(result_line(None, None))
+        mg.clear_(p)
+        return
 
     # ---- per-kernel HIP-event accounting over the same K steps (separate, instrumented pass) -----
     prof, moved, tot_ms = profiled_pass(h, b, x, K, torch)
@@ -872,24 +908,7 @@ def main():
         cpu = cpu_baseline(args, p, b_host, n, nrhs, cells, resvec)
 
     if rank == 0:
-        out = {
-            "metric": "V-cycle DoF-updates/s", "value": round(dof_per_s, 1), "unit": "DoF-updates/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(dt / K * 1e3, 4),
-            "higher_is_better": True, "scaling": None, "vs_baseline": None, "dtype": "f64",   # (one GPU: neither weak nor strong)
-            "data": "synthetic",
-            "config": {"workload": f"{desc}, {p.levels} levels, nrhs={nrhs}, fp64"[:118],      # (kept under 120 characters: the driver's record cuts longer ones)
-                       "step": "one step = one cycle + the residual and norm of solveMG's stopping test (SolveFuncs.jl:24-37)",
-                       "cells": cells, "levels": p.levels, "nrhs": nrhs, "N": n, "nnz": int(A.nnz),
-                       "level_rows": [int(a.shape[0]) for a in p.As], "level_nnz": [int(a.nnz) for a in p.As],
-                       "parallelism": "1 process per GPU"},
-            "timed_regions_ms_per_step": [round(r / K * 1e3, 4) for r in region],
-            "timing": f"median of {len(region)} regions of exactly {K} steps each (barrier + synchronize on both sides)",
-            "relres_after_steps": relres,
-            "setup_s": {"operator": round(t_op, 2), "MGsetup": round(t_setup, 2), "upload": round(t_upload, 2)},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
-        emit(out)
+        emit(result_line(roofline, cpu))
     mg.clear_(p)
     if world > 1:
         dist.destroy_process_group()
@@ -1215,7 +1234,7 @@ def bench_ghost(args, mg, torch, dist, cells, K, W, rank, world, local_rank):
     per_step_sent = (e1[1] - e0[1]) * 8.0 / (nreg * K)
     rccl_ranks = H.comm_count()
     kern_table = None
-    if world == 1:      # (one process: a world of one, or a dry rank) where the step goes, launch by launch (instrumented pass: graphs off, events on)
+    if world == 1 and args.full:      # (one process: a world of one, or a dry rank) where the step goes, launch by launch (instrumented pass: graphs off, events on)
         prof, moved, tot_ms = profiled_pass(H.dev, b, x, K, torch)
         kern_table = {f"L{l}:{k}": {"avg_us": round(v[0] / v[1] * 1e3, 2), "launches_per_step": round(v[1] / K, 2), "us_per_step": round(v[0] / K * 1e3, 1)}
                       for (l, k), v in sorted(prof.items())}
@@ -1225,7 +1244,7 @@ def bench_ghost(args, mg, torch, dist, cells, K, W, rank, world, local_rank):
         dist.all_reduce(rows_ext, op=dist.ReduceOp.MAX)
     # the same box through the plain single-GPU path, same process, same GPU (a world of one only: the extended box IS the grid)
     same_job = None
-    if world == 1 and not dry and not os.environ.get("MG_BENCH_NO_SAME_JOB"):
+    if world == 1 and not dry and args.full and not os.environ.get("MG_BENCH_NO_SAME_JOB"):
         try:
             H.close()
             A1, mesh1 = mg.poisson_shifted(gcells, [v for g in gcells for v in (0.0, g / float(cells))])

@@ -1,4 +1,4 @@
-"""Print the per-kernel table of a bench.py JSON line.  usage: python scripts/kern_table.py file.json [prefix]"""
+"""Print the per-kernel table of a `bench.py --full` JSON line.  usage: python scripts/kern_table.py file.json [prefix]"""
 import json, sys
 d = json.load(open(sys.argv[1]))
 pre = sys.argv[2] if len(sys.argv) > 2 else ""

@@ -7,19 +7,19 @@ part=${2:-1}
 mkdir -p $out
 export TMPDIR=/tmp
 if [ "$part" = "1" ]; then
-python bench.py --steps 20 --warmup 5 > $out/c2_bench.json 2> $out/c2_bench.err
+python bench.py --full --steps 20 --warmup 5 > $out/c2_bench.json 2> $out/c2_bench.err
 echo "c2 done" > $out/progress.txt
-MG_NO_PIPELINE=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass > $out/c2_bench_no_pipeline.json 2> /dev/null
-MG_NO_MARCH4=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass > $out/c2_bench_no_four_stage.json 2> /dev/null
+MG_NO_PIPELINE=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass > $out/c2_bench_no_pipeline.json 2> /dev/null
+MG_NO_MARCH4=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass > $out/c2_bench_no_four_stage.json 2> /dev/null
 echo "A/B done" >> $out/progress.txt
-python bench.py --cells 400 --steps 20 --warmup 5 --no-cpu-baseline --no-divsiggrad > $out/c2_400_bench.json 2> $out/c2_400_bench.err
+python bench.py --full --cells 400 --steps 20 --warmup 5 --no-cpu-baseline --no-divsiggrad > $out/c2_400_bench.json 2> $out/c2_400_bench.err
 echo "c2-400 done" >> $out/progress.txt
-python bench.py --force-sharded-path --no-cpu-baseline --steps 20 --warmup 5 > $out/c2_sharded_w1_bench.json 2> $out/c2_sharded_w1.err
-python bench.py --workload c5 --steps 10 --warmup 2 --no-cpu-baseline > $out/c5_bench.json 2> $out/c5_bench.err
+python bench.py --full --force-sharded-path --no-cpu-baseline --steps 20 --warmup 5 > $out/c2_sharded_w1_bench.json 2> $out/c2_sharded_w1.err
+python bench.py --full --workload c5 --steps 10 --warmup 2 --no-cpu-baseline > $out/c5_bench.json 2> $out/c5_bench.err
 echo "sharded, c5 done" >> $out/progress.txt
 fi
 if [ "$part" = "2" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c2 -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass > $out/prof_c2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c2 -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass > $out/prof_c2.log 2>&1
 f=$(find $out/prof_c2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/c2_kernel_stats.csv
 t=$(find $out/prof_c2 -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python3 profiles/summarize_trace.py $t > $out/c2_kernel_by_grid.md
 echo "kernel trace done" >> $out/progress.txt
@@ -38,7 +38,7 @@ bash scripts/pmc_sq4.sh ${1:-r04}/sq4 1024:0 > $out/sq4.log 2>&1
 echo "sq done" >> $out/progress.txt
 fi
 if [ "$part" = "3" ]; then
-python bench.py --cells 512 --steps 10 --warmup 2 --no-cpu-baseline --no-generic-pass > $out/c2_512_bench.json 2> $out/c2_512_bench.err
+python bench.py --full --cells 512 --steps 10 --warmup 2 --no-cpu-baseline --no-generic-pass > $out/c2_512_bench.json 2> $out/c2_512_bench.err
 echo "512 done" >> $out/progress.txt
 fi
 find $out -name "*.csv" -size +1M -delete

@@ -11,18 +11,18 @@ part=${2:-1}
 mkdir -p $out
 export TMPDIR=/tmp
 if [ "$part" = "1" ]; then
-python bench.py --steps 20 --warmup 5 > $out/c2_bench.json 2> $out/c2_bench.err
+python bench.py --full --steps 20 --warmup 5 > $out/c2_bench.json 2> $out/c2_bench.err
 echo "c2 done" > $out/progress.txt
-MG_NO_SMALL=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_no_small.json 2> /dev/null
-MG_SMALL_OVER_RC=300000 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_small_on_level3.json 2> /dev/null
-MG_NO_MARCH4=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_no_four_stage.json 2> /dev/null
-MG_NO_BAND_SYM=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-c5-leg > $out/c2_bench_no_band_sym.json 2> /dev/null
-MG_NO_CELL_PROLONG=1 MG_NO_WAVE_RESTRICT=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_old_transfers.json 2> /dev/null
-python bench.py > $out/c2_bench_default_run.json 2> /dev/null
+MG_NO_SMALL=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_no_small.json 2> /dev/null
+MG_SMALL_OVER_RC=300000 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_small_on_level3.json 2> /dev/null
+MG_NO_MARCH4=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_no_four_stage.json 2> /dev/null
+MG_NO_BAND_SYM=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-c5-leg > $out/c2_bench_no_band_sym.json 2> /dev/null
+MG_NO_CELL_PROLONG=1 MG_NO_WAVE_RESTRICT=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_bench_old_transfers.json 2> /dev/null
+python bench.py --full > $out/c2_bench_default_run.json 2> /dev/null
 echo "A/B done" >> $out/progress.txt
 fi
 if [ "$part" = "2" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c2 -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/prof_c2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c2 -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/prof_c2.log 2>&1
 f=$(find $out/prof_c2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/c2_kernel_stats.csv
 t=$(find $out/prof_c2 -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python3 profiles/summarize_trace.py $t > $out/c2_kernel_by_grid.md
 echo "kernel trace done" >> $out/progress.txt
@@ -39,30 +39,30 @@ bash scripts/pmc_sq4.sh ${1:-r05}/sq4 1024:0 > $out/sq4.log 2>&1
 echo "sq done" >> $out/progress.txt
 fi
 if [ "$part" = "3" ]; then
-python bench.py --force-sharded-path --steps 20 --warmup 5 > $out/c2_sharded_w1_ghost.json 2> $out/c2_sharded_w1_ghost.err
-python bench.py --force-sharded-path --sharded-form halo --steps 20 --warmup 5 > $out/c2_sharded_w1_halo.json 2> /dev/null
+python bench.py --full --force-sharded-path --steps 20 --warmup 5 > $out/c2_sharded_w1_ghost.json 2> $out/c2_sharded_w1_ghost.err
+python bench.py --full --force-sharded-path --sharded-form halo --steps 20 --warmup 5 > $out/c2_sharded_w1_halo.json 2> /dev/null
 echo "world-1 done" > $out/progress3.txt
-python bench.py --ghost-dry 0/8 --steps 20 --warmup 5 > $out/c4_dry_rank0_of_8.json 2> $out/c4_dry_rank0.err
-python bench.py --ghost-dry 7/8 --steps 20 --warmup 5 > $out/c4_dry_rank7_of_8.json 2> $out/c4_dry_rank7.err
-python bench.py --ghost-dry 1/2 --steps 20 --warmup 5 > $out/c4_dry_rank1_of_2.json 2> /dev/null
-python bench.py --ghost-dry 3/4 --steps 20 --warmup 5 > $out/c4_dry_rank3_of_4.json 2> /dev/null
+python bench.py --full --ghost-dry 0/8 --steps 20 --warmup 5 > $out/c4_dry_rank0_of_8.json 2> $out/c4_dry_rank0.err
+python bench.py --full --ghost-dry 7/8 --steps 20 --warmup 5 > $out/c4_dry_rank7_of_8.json 2> $out/c4_dry_rank7.err
+python bench.py --full --ghost-dry 1/2 --steps 20 --warmup 5 > $out/c4_dry_rank1_of_2.json 2> /dev/null
+python bench.py --full --ghost-dry 3/4 --steps 20 --warmup 5 > $out/c4_dry_rank3_of_4.json 2> /dev/null
 echo "dry ranks done" >> $out/progress3.txt
-python bench.py --cells 512 --steps 20 --warmup 3 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_512_bench.json 2> $out/c2_512_bench.err
+python bench.py --full --cells 512 --steps 20 --warmup 3 --no-cpu-baseline --no-generic-pass --no-divsiggrad --no-c5-leg > $out/c2_512_bench.json 2> $out/c2_512_bench.err
 echo "512 done" >> $out/progress3.txt
 python3 scripts/strong_ceiling.py $out > $out/strong_ceiling.json
 fi
 if [ "$part" = "4" ]; then
-python bench.py --workload c5 --steps 10 --warmup 2 --no-cpu-baseline > $out/c5_bench.json 2> $out/c5_bench.err
-MG_NO_COLUMNS=1 python bench.py --workload c5 --steps 10 --warmup 2 --no-cpu-baseline > $out/c5_bench_block_kernels.json 2> /dev/null
+python bench.py --full --workload c5 --steps 10 --warmup 2 --no-cpu-baseline > $out/c5_bench.json 2> $out/c5_bench.err
+MG_NO_COLUMNS=1 python bench.py --full --workload c5 --steps 10 --warmup 2 --no-cpu-baseline > $out/c5_bench_block_kernels.json 2> /dev/null
 echo "c5 done" > $out/progress4.txt
-python bench.py --cells 400 --steps 20 --warmup 5 --no-cpu-baseline --no-divsiggrad --no-generic-pass --no-c5-leg > $out/c2_400_bench.json 2> $out/c2_400_bench.err
+python bench.py --full --cells 400 --steps 20 --warmup 5 --no-cpu-baseline --no-divsiggrad --no-generic-pass --no-c5-leg > $out/c2_400_bench.json 2> $out/c2_400_bench.err
 echo "400 done" >> $out/progress4.txt
-python bench.py --workload c3 --cells 128 --steps 10 --warmup 2 --no-cpu-baseline > $out/c3_128_bench.json 2> $out/c3_128_bench.err
-MG_NO_LONGROW=1 python bench.py --workload c3 --cells 128 --steps 10 --warmup 2 --no-cpu-baseline > $out/c3_128_bench_no_longrow.json 2> /dev/null
+python bench.py --full --workload c3 --cells 128 --steps 10 --warmup 2 --no-cpu-baseline > $out/c3_128_bench.json 2> $out/c3_128_bench.err
+MG_NO_LONGROW=1 python bench.py --full --workload c3 --cells 128 --steps 10 --warmup 2 --no-cpu-baseline > $out/c3_128_bench_no_longrow.json 2> /dev/null
 echo "c3-128 done" >> $out/progress4.txt
 fi
 if [ "$part" = "5" ]; then
-OMP_NUM_THREADS=16 MG_HOST_THREADS=16 python bench.py --workload c3 --steps 10 --warmup 2 --no-cpu-baseline > $out/c3_256_bench.json 2> $out/c3_256_bench.err
+OMP_NUM_THREADS=16 MG_HOST_THREADS=16 python bench.py --full --workload c3 --steps 10 --warmup 2 --no-cpu-baseline > $out/c3_256_bench.json 2> $out/c3_256_bench.err
 echo "c3-256 done" > $out/progress5.txt
 fi
 find $out -name "*.csv" -size +1M -delete

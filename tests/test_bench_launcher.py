@@ -29,10 +29,11 @@ def test_launcher_refuses_more_ranks_than_gpus_unless_sharing_is_allowed():
 @pytest.mark.parametrize("form", ["ghost", "halo"])
 def test_bench_gpus2_from_a_bare_python_call(form):
     """Two fresh rank processes sharing the box's one GPU (host-staged plug-in transport), started by bench.py itself;
-    rank 0's single JSON line comes back with n_gpus = 2 and the launcher's N = 1 reference - in the ghost-layer form (default:
-    mg_ghost_*) and in the halo form of rounds 2-4 (mg_dist_*)."""
+    rank 0's single JSON line comes back with n_gpus = 2 and (--full) the launcher's N = 1 reference - in the ghost-layer form
+    (default: mg_ghost_*) and in the halo form of rounds 2-4 (mg_dist_*)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cells", "32", "--steps", "3",
-                        "--warmup", "1", "--sharded-form", form], capture_output=True, text=True, env=_clean_env(MG_BENCH_ALLOW_SHARE="1"),
+                        "--warmup", "1", "--sharded-form", form, "--full"], capture_output=True, text=True,
+                       env=_clean_env(MG_BENCH_ALLOW_SHARE="1"),
                        timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -65,3 +66,27 @@ def test_bench_dump_outputs_are_the_timed_solve(mg, built, tmp_path):
     A, _ = mg.poisson_shifted([32, 32, 32])
     b = mg.seeded_rhs(A)
     assert abs(np.linalg.norm(b - A @ x) - resvec[-1]) <= 1e-10 * resvec[0]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_full_adds_the_rest(built):
+    """A plain run prints the headline line alone (roofline and cpu_baseline null); --full adds the instrumented per-kernel pass,
+    the legs (at 32^3 cells: div sigma grad among them) and the CPU baseline after the same timed steps."""
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cells", "32", "--steps", "4",
+                            "--warmup", "1", *extra], capture_output=True, text=True, env=_clean_env(), timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    plain, full = run(), run("--full")
+    for out in (plain, full):
+        assert out["metric"] == "V-cycle DoF-updates/s" and out["unit"] == "DoF-updates/s" and out["dtype"] == "f64"
+        assert out["higher_is_better"] is True and out["steps"] == 4 and out["warmup"] == 1
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and len(out["timed_regions_ms_per_step"]) == 5
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None
+    assert full["roofline"]["kernels"] and full["roofline"]["achieved"] > 0
+    assert full["roofline"]["divsiggrad"]["ms_per_step"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["resvec_rel_diff_vs_gpu"] < 1e-10
+    assert full["relres_after_steps"] == pytest.approx(plain["relres_after_steps"], rel=1e-10)
