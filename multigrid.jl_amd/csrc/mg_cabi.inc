@@ -1,6 +1,82 @@
 // mg_cabi.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // The C ABI of the single-GPU hierarchy (include/mgvcycle.h): create / set / finalize / cycle / solve / Krylov / measurement, stand-alone operators, the factor applier, hybrid Kaczmarz.
 
+// ---- shared preambles and staging of the entry points (the value-type guards stay in the entry points: they name them) ----
+namespace {
+// Level `level` (1-based) of a handle: MG_ERR_INVALID for a null handle or a level outside 1..nlevels
+int find_level(mg_hierarchy* h, long long level, Level** L) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
+  *L = &h->lev[(size_t)level - 1];
+  return MG_OK;
+}
+
+// Operator `which` (MG_OP_A / _P / _R) of level `level`: MG_ERR_INVALID for a null handle or an operator that was not set
+int find_op(mg_hierarchy* h, long long level, long long which, Csr** M) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  *M = pick(h, level, which);
+  if (!*M || !(*M)->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  return MG_OK;
+}
+
+int need_finalized(mg_hierarchy* h) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
+  return MG_OK;
+}
+
+// the caller's initial guess into the staging buffer: x == 0 (the usual call) is a device memset instead of n*nrhs*8
+// bytes over PCIe (the scan of a zero vector runs at memory speed: host_all_zero)
+int upload_x_or_zero(mg_hierarchy* h, const double* x, long long n, long long nrhs) {
+  const long long len = n * nrhs;
+  if (host_all_zero(x, len)) {
+    HIP_TRY(hipMemsetAsync(h->stage_x.p, 0, sizeof(double) * (size_t)len, h->stream));
+    return MG_OK;
+  }
+  return upload_block(h, x, h->stage_x.p, n, nrhs);
+}
+
+// How staged() puts the caller's x on the device: upload_x_or_zero (the drivers that read x), or as mg_cycle_FP64 decided -
+// uploaded, or not at all when the cycle starts from x = 0
+enum class StageX { or_zero, upload, skip };
+
+// The host-pointer form of a device routine (b, x: column-major n x nrhs host blocks): b and x into the staging buffers,
+// run(stage_b, stage_x), x back, the profile.  The caller has checked the arguments and set the device.
+template <typename Run>
+int staged(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, StageX xs, Run run) {
+  MG_TRY(upload_block(h, b, h->stage_b.p, n, nrhs));
+  if (xs == StageX::or_zero) MG_TRY(upload_x_or_zero(h, x, n, nrhs));
+  if (xs == StageX::upload) MG_TRY(upload_block(h, x, h->stage_x.p, n, nrhs));
+  MG_TRY(run(h->stage_b.p, h->stage_x.p));
+  MG_TRY(download_block(h, h->stage_x.p, x, n, nrhs));
+  prof_collect(h);
+  return MG_OK;
+}
+
+// A Krylov entry point: check_ready and the arguments, then run(b, x) - the device form on the caller's vectors (sharded handles
+// too: the ghost-layer form runs the sharded drivers of mg_krylov.inc), the host form on the staging buffers
+template <typename Run>
+int krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long maxIter, bool device_form, Run run) {
+  MG_TRY(check_ready(h, n, nrhs, /*sharded_ok=*/device_form));
+  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
+  (void)hipSetDevice(h->device);
+  if (!device_form) return staged(h, b, x, n, nrhs, StageX::or_zero, run);
+  MG_TRY(run(b, x));
+  prof_collect(h);
+  return MG_OK;
+}
+
+// device_id a visible device, made current (the create entry points)
+int use_device(long long device_id) {
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the multigrid cycle has no CPU fallback");
+  if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
+  HIP_TRY(hipSetDevice((int)device_id));
+  return MG_OK;
+}
+}  // namespace
+
 // =================================================================================================
 // C ABI
 // =================================================================================================
@@ -14,11 +90,7 @@ int mg_create(long long nlevels, long long nrhs, long long device_id, mg_hierarc
   *out = nullptr;
   if (nlevels < 1 || nlevels > 64) return fail(MG_ERR_INVALID, "nlevels=%lld out of range [1,64]", nlevels);
   if (nrhs < 1) return fail(MG_ERR_INVALID, "nrhs=%lld must be >= 1", nrhs);
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the multigrid cycle has no CPU fallback");
-  if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
-  HIP_TRY(hipSetDevice((int)device_id));
+  MG_TRY(use_device(device_id));
   mg_hierarchy* h = new mg_hierarchy();
   h->opt = Options::from_env();   // the only place the environment is read for this handle
   h->device = (int)device_id;
@@ -101,9 +173,8 @@ int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
 
 int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   if (!out || nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
   (void)hipSetDevice(h->device);
   HIP_TRY(spin_sync(h->stream));
@@ -113,13 +184,12 @@ int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double
 
 int mg_get_relax_FP64(mg_hierarchy* h, long long level, double* out, long long n) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
-  Level& L = h->lev[(size_t)level - 1];
-  if (!out || !L.relax_set || n != (long long)L.d.n) return fail(MG_ERR_INVALID, "relaxPrecs[%lld] not set or wrong length", level);
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
+  if (!out || !L->relax_set || n != (long long)L->d.n) return fail(MG_ERR_INVALID, "relaxPrecs[%lld] not set or wrong length", level);
   (void)hipSetDevice(h->device);
   HIP_TRY(spin_sync(h->stream));
-  HIP_TRY(hipMemcpy(out, L.d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, L->d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MG_OK;
 }
 
@@ -214,18 +284,18 @@ int mg_set_relax_FP64(mg_hierarchy* h, long long level, const double* d, long lo
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
   if (!d || n < 1) return fail(MG_ERR_INVALID, "empty relaxPrec");
   if (relaxPre < 0 || relaxPost < 0) return fail(MG_ERR_INVALID, "negative sweep count");
   (void)hipSetDevice(h->device);
-  Level& L = h->lev[(size_t)level - 1];
-  MG_TRY(L.d.alloc((size_t)n));
-  HIP_TRY(hipMemcpy(L.d.p, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-  L.relax_set = true;
-  L.A.rc_has_d = false;   // re-derived by mg_finalize
-  L.A.sm_ok = false;      // (its records carry the relaxPrec: rebuilt by mg_finalize)
-  L.npre = relaxPre;
-  L.npost = relaxPost;
+  MG_TRY(L->d.alloc((size_t)n));
+  HIP_TRY(hipMemcpy(L->d.p, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  L->relax_set = true;
+  L->A.rc_has_d = false;   // re-derived by mg_finalize
+  L->A.sm_ok = false;      // (its records carry the relaxPrec: rebuilt by mg_finalize)
+  L->npre = relaxPre;
+  L->npost = relaxPost;
   h->finalized = false;
   return MG_OK;
 }
@@ -236,7 +306,7 @@ int mg_set_relax_FP64(mg_hierarchy* h, long long level, const double* d, long lo
 int mg_set_option(mg_hierarchy* h, const char* key, double value) {
   if (!h || !key) return fail(MG_ERR_INVALID, "null argument");
   graphs_clear(h);
-  if (!h->opt.set(key, value, false)) return fail(MG_ERR_INVALID, "unknown option '%s'", key);
+  if (!h->opt.set(key, value)) return fail(MG_ERR_INVALID, "unknown option '%s'", key);
   for (auto& L : h->lev) {
     L.A.opt = h->opt;
     L.P.opt = h->opt;
@@ -256,12 +326,12 @@ int mg_graph_launches(mg_hierarchy* h, long long* launches, long long* graphs) {
 int mg_set_grid_hint(mg_hierarchy* h, long long level, long long n1, long long n2, long long n3) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
   if (n1 < 1 || n2 < 1 || n3 < 1) return fail(MG_ERR_INVALID, "grid dimensions must be >= 1");
-  Level& L = h->lev[(size_t)level - 1];
-  L.grid[0] = n1;
-  L.grid[1] = n2;
-  L.grid[2] = n3;
+  L->grid[0] = n1;
+  L->grid[1] = n2;
+  L->grid[2] = n3;
   h->finalized = false;
   return MG_OK;
 }
@@ -502,8 +572,8 @@ int mg_replace_values_FP64(mg_hierarchy* h, long long level, long long which, co
   UploadFence upload_fence;
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
   (void)hipSetDevice(h->device);
   HIP_TRY(spin_sync(h->stream));
@@ -563,10 +633,9 @@ int mg_solve_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, 
 int mg_spmv_dev_FP64(mg_hierarchy* h, long long level, long long which, double alpha,
                      const double* x, double beta, double* y, long long nrhs) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  MG_TRY(need_finalized(h));
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   if (nrhs != h->nrhs) return fail(MG_ERR_INVALID, "nrhs=%lld but the scratch is sized for %lld", nrhs, h->nrhs);
   if (!x || !y) return fail(MG_ERR_INVALID, "null vector");
   if (x == y) return fail(MG_ERR_INVALID, "x and y must not alias");
@@ -580,18 +649,17 @@ int mg_spmv_dev_FP64(mg_hierarchy* h, long long level, long long which, double a
 int mg_fused_dev_FP64(mg_hierarchy* h, long long level, long long kernel, const double* b,
                       const double* x, double* out, long long nrhs) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
+  MG_TRY(need_finalized(h));
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
   if (nrhs != h->nrhs) return fail(MG_ERR_INVALID, "nrhs=%lld but the scratch is sized for %lld", nrhs, h->nrhs);
   if (!b || !x || !out || out == x) return fail(MG_ERR_INVALID, "null vector or out aliases x");
-  Level& L = h->lev[(size_t)level - 1];
   (void)hipSetDevice(h->device);
   if (kernel == MG_K_RESIDUAL) {
-    MG_TRY(k_residual(h, (int)level - 1, L.A, b, x, out));
+    MG_TRY(k_residual(h, (int)level - 1, L->A, b, x, out));
   } else if (kernel == MG_K_SMOOTH) {
-    if (!L.relax_set) return fail(MG_ERR_STATE, "relaxPrecs[%lld] was not set", level);
-    MG_TRY(k_smooth(h, (int)level - 1, L.A, L.d.p, b, x, out));
+    if (!L->relax_set) return fail(MG_ERR_STATE, "relaxPrecs[%lld] was not set", level);
+    MG_TRY(k_smooth(h, (int)level - 1, L->A, L->d.p, b, x, out));
   } else {
     return fail(MG_ERR_INVALID, "kernel must be MG_K_RESIDUAL or MG_K_SMOOTH");
   }
@@ -605,8 +673,7 @@ int mg_fused_dev_FP64(mg_hierarchy* h, long long level, long long kernel, const 
 int mg_sweep_residual_dev_FP64(mg_hierarchy* h, long long level, const double* b, const double* x, double* t, double* r,
                                double* xn, double* norm_r) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
+  MG_TRY(need_finalized(h));
   if (level < 1 || level >= h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
   if (!b || !x || !t) return fail(MG_ERR_INVALID, "null vector");
   (void)hipSetDevice(h->device);
@@ -623,8 +690,7 @@ int mg_sweep_residual_dev_FP64(mg_hierarchy* h, long long level, const double* b
 int mg_four_stage_dev_FP64(mg_hierarchy* h, long long level, const double* b, const double* x, double* tp, double* rp,
                            double* norm_r) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
+  MG_TRY(need_finalized(h));
   if (level < 1 || level >= h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
   if (!b || !x || !tp || !rp) return fail(MG_ERR_INVALID, "null vector");
   (void)hipSetDevice(h->device);
@@ -703,8 +769,7 @@ int transpose_longest_column_ok(const Csr& M) {
 int mg_transpose_hierarchy(mg_hierarchy* h) {
   MG_CF64_UNSUPPORTED(h);
   UploadFence upload_fence;
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
+  MG_TRY(need_finalized(h));
   if (h->ghost) return fail(MG_ERR_UNSUPPORTED, "a rank's part of a sharded hierarchy is transposed on the host (every rank re-uploads its part)");
   if (h->coarse_lu) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is held as sparse factors: re-upload the transposed hierarchy");
   (void)hipSetDevice(h->device);
@@ -746,8 +811,8 @@ int mg_transpose_hierarchy(mg_hierarchy* h) {
 int mg_operator_shape(mg_hierarchy* h, long long level, long long which, long long* shape) {
   MG_REAL_ONLY(h);
   if (!h || !shape) return fail(MG_ERR_INVALID, "null argument");
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   shape[0] = M->n_rows;
   shape[1] = M->n_cols;
   shape[2] = M->nnz;
@@ -756,8 +821,9 @@ int mg_operator_shape(mg_hierarchy* h, long long level, long long which, long lo
 int mg_four_stage_form(mg_hierarchy* h, long long level, long long* yes, long long* geometry) {
   MG_REAL_ONLY(h);
   if (!h || !yes || !geometry) return fail(MG_ERR_INVALID, "null argument");
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
-  const Csr& A = h->lev[(size_t)level - 1].A;
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
+  const Csr& A = L->A;
   *yes = (A.rc_march4 && !h->opt.no_march4) ? 1 : 0;
   for (int i = 0; i < 12; ++i) geometry[i] = 0;
   if (A.rc_march4) {
@@ -769,37 +835,6 @@ int mg_four_stage_form(mg_hierarchy* h, long long level, long long* yes, long lo
 }
 
 // ---- host-buffer hot path (what the Julia glue ccalls) ------------------------------------------
-// x == 0 everywhere?  Blocks of 4096 entries are OR-reduced bitwise (vectorises; the element-wise loop with its early
-// exit does not: 13 ms for 136 MB on the box's core) and only a block with a set bit - a non-zero or a -0.0 - is
-// looked at entry by entry.
-static bool host_all_zero(const double* x, long long len) {
-  const long long B = 4096;
-  for (long long i0 = 0; i0 < len; i0 += B) {
-    const long long i1 = std::min(len, i0 + B);
-    unsigned long long acc = 0;
-    for (long long i = i0; i < i1; ++i) {
-      unsigned long long bits;
-      std::memcpy(&bits, x + i, 8);
-      acc |= bits;
-    }
-    if (acc != 0)
-      for (long long i = i0; i < i1; ++i)
-        if (x[i] != 0.0) return false;
-  }
-  return true;
-}
-
-// the caller's initial guess into the staging buffer: x == 0 (the usual call) is a device memset instead of n*nrhs*8
-// bytes over PCIe (the scan of a zero vector runs at memory speed: host_all_zero)
-static int upload_x_or_zero(mg_hierarchy* h, const double* x, long long n, long long nrhs) {
-  const long long len = n * nrhs;
-  if (host_all_zero(x, len)) {
-    HIP_TRY(hipMemsetAsync(h->stage_x.p, 0, sizeof(double) * (size_t)len, h->stream));
-    return MG_OK;
-  }
-  return upload_block(h, x, h->stage_x.p, n, nrhs);
-}
-
 int mg_cycle_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
                   long long x_is_zero) {
   MG_REAL_ONLY(h);
@@ -808,12 +843,8 @@ int mg_cycle_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long
   (void)hipSetDevice(h->device);
   bool xz = (x_is_zero == 1);
   if (x_is_zero < 0) xz = host_all_zero(x, n * nrhs);   // norm(x) > 0.0 decides (MGcycle.jl:29)
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, nrhs));
-  if (!xz) MG_TRY(upload_block(h, x, h->stage_x.p, n, nrhs));
-  MG_TRY(cycle_dev(h, h->stage_b.p, h->stage_x.p, xz));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, nrhs));
-  prof_collect(h);
-  return MG_OK;
+  return staged(h, b, x, n, nrhs, xz ? StageX::skip : StageX::upload,
+                [&](const double* sb, double* sx) { return cycle_dev(h, sb, sx, xz); });
 }
 
 int mg_solve_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
@@ -823,161 +854,91 @@ int mg_solve_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
   (void)hipSetDevice(h->device);
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, nrhs));
-  MG_TRY(upload_x_or_zero(h, x, n, nrhs));
-  if (columns_ok(h)) MG_TRY(solve_dev_columns(h, h->stage_b.p, h->stage_x.p, tol, maxIter, iters, resvec));
-  else MG_TRY(solve_dev(h, h->stage_b.p, h->stage_x.p, tol, maxIter, iters, resvec));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, nrhs));
-  prof_collect(h);
-  return MG_OK;
+  return staged(h, b, x, n, nrhs, StageX::or_zero, [&](const double* sb, double* sx) {
+    return columns_ok(h) ? solve_dev_columns(h, sb, sx, tol, maxIter, iters, resvec) : solve_dev(h, sb, sx, tol, maxIter, iters, resvec);
+  });
 }
 
+// ---- Krylov drivers: host (column-major n x nrhs, staged) and device-resident (row-major [n][nrhs]) forms ---------------
 int mg_pcg_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol,
                     long long maxIter, long long* iters, long long* flag, double* resvec) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, 1, /*sharded_ok=*/true));   // (ghost-layer form: the sharded drivers of mg_krylov.inc)
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(pcg_dev(h, b, x, tol, maxIter, iters, flag, resvec));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, 1, maxIter, /*device_form=*/true,
+                [&](const double* bv, double* xv) { return pcg_dev(h, bv, xv, tol, maxIter, iters, flag, resvec); });
 }
 
 int mg_pcg_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter,
                 long long* iters, long long* flag, double* resvec) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, 1));
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, 1));
-  MG_TRY(upload_x_or_zero(h, x, n, 1));
-  MG_TRY(pcg_dev(h, h->stage_b.p, h->stage_x.p, tol, maxIter, iters, flag, resvec));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, 1));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, 1, maxIter, /*device_form=*/false,
+                [&](const double* bv, double* xv) { return pcg_dev(h, bv, xv, tol, maxIter, iters, flag, resvec); });
 }
 
 int mg_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol,
                    long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, 1));
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, 1));
-  MG_TRY(upload_x_or_zero(h, x, n, 1));
-  MG_TRY(fgmres_dev(h, h->stage_b.p, h->stage_x.p, inner, tol, maxIter, iters, flag, resvec, nres));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, 1));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, 1, maxIter, /*device_form=*/false,
+                [&](const double* bv, double* xv) { return fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
 }
 
 int mg_fgmres_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol,
                        long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, 1, /*sharded_ok=*/true));   // (ghost-layer form: the sharded drivers of mg_krylov.inc)
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(fgmres_dev(h, b, x, inner, tol, maxIter, iters, flag, resvec, nres));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, 1, maxIter, /*device_form=*/true,
+                [&](const double* bv, double* xv) { return fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
 }
 
 int mg_bicgstab_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol,
                          long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, 1, /*sharded_ok=*/true));   // (ghost-layer form: the sharded drivers of mg_krylov.inc)
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(bicgstab_dev(h, b, x, tol, maxIter, iters, flag, resvec, nres));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, 1, maxIter, /*device_form=*/true,
+                [&](const double* bv, double* xv) { return bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
 }
 
 int mg_bicgstab_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter,
                      long long* iters, long long* flag, double* resvec, long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, 1));
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, 1));
-  MG_TRY(upload_x_or_zero(h, x, n, 1));
-  MG_TRY(bicgstab_dev(h, h->stage_b.p, h->stage_x.p, tol, maxIter, iters, flag, resvec, nres));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, 1));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, 1, maxIter, /*device_form=*/false,
+                [&](const double* bv, double* xv) { return bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
 }
 
-// ---- block Krylov drivers: host (column-major n x nrhs) and device-resident (row-major [n][nrhs]) forms ---------------
 int mg_block_pcg_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                           long long maxIter, long long* iters, long long* flag, double* resmat) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, nrhs, /*sharded_ok=*/true));   // (ghost-layer form: the sharded block drivers of mg_krylov.inc)
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(block_pcg_dev(h, b, x, tol, maxIter, iters, flag, resmat));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, nrhs, maxIter, /*device_form=*/true,
+                [&](const double* bv, double* xv) { return block_pcg_dev(h, bv, xv, tol, maxIter, iters, flag, resmat); });
 }
 int mg_block_pcg_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                       long long maxIter, long long* iters, long long* flag, double* resmat) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, nrhs));
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, nrhs));
-  MG_TRY(upload_x_or_zero(h, x, n, nrhs));
-  MG_TRY(block_pcg_dev(h, h->stage_b.p, h->stage_x.p, tol, maxIter, iters, flag, resmat));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, nrhs));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, nrhs, maxIter, /*device_form=*/false,
+                [&](const double* bv, double* xv) { return block_pcg_dev(h, bv, xv, tol, maxIter, iters, flag, resmat); });
 }
 int mg_block_bicgstab_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                                long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, nrhs, /*sharded_ok=*/true));   // (ghost-layer form: the sharded block drivers of mg_krylov.inc)
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(block_bicgstab_dev(h, b, x, tol, maxIter, iters, flag, resvec, nres));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, nrhs, maxIter, /*device_form=*/true,
+                [&](const double* bv, double* xv) { return block_bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
 }
 int mg_block_bicgstab_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
                            long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, nrhs));
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, nrhs));
-  MG_TRY(upload_x_or_zero(h, x, n, nrhs));
-  MG_TRY(block_bicgstab_dev(h, h->stage_b.p, h->stage_x.p, tol, maxIter, iters, flag, resvec, nres));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, nrhs));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, nrhs, maxIter, /*device_form=*/false,
+                [&](const double* bv, double* xv) { return block_bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
 }
 int mg_block_fgmres_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long inner,
                              double tol, long long maxIter, long long* iters, long long* flag, double* resvec,
                              long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, nrhs, /*sharded_ok=*/true));   // (ghost-layer form: the sharded block drivers of mg_krylov.inc)
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(block_fgmres_dev(h, b, x, inner, tol, maxIter, iters, flag, resvec, nres));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, nrhs, maxIter, /*device_form=*/true,
+                [&](const double* bv, double* xv) { return block_fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
 }
 int mg_block_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long inner,
                          double tol, long long maxIter, long long* iters, long long* flag, double* resvec,
                          long long* nres) {
   MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, nrhs));
-  if (!b || !x || maxIter < 0) return fail(MG_ERR_INVALID, "null vector or maxIter < 0");
-  (void)hipSetDevice(h->device);
-  MG_TRY(upload_block(h, b, h->stage_b.p, n, nrhs));
-  MG_TRY(upload_x_or_zero(h, x, n, nrhs));
-  MG_TRY(block_fgmres_dev(h, h->stage_b.p, h->stage_x.p, inner, tol, maxIter, iters, flag, resvec, nres));
-  MG_TRY(download_block(h, h->stage_x.p, x, n, nrhs));
-  prof_collect(h);
-  return MG_OK;
+  return krylov(h, b, x, n, nrhs, maxIter, /*device_form=*/false,
+                [&](const double* bv, double* xv) { return block_fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
 }
 
 // Mixed-precision preconditioner hook (getMultigridPreconditioner, SolveFuncs.jl:52-58): the caller's block is Float32,
@@ -1154,10 +1115,9 @@ int mg_host_unregister(void* ptr) {
 int mg_spmv_FP64(mg_hierarchy* h, long long level, long long which, double alpha, const double* x,
                  double beta, double* y, long long nrhs) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  MG_TRY(need_finalized(h));
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   if (nrhs != h->nrhs) return fail(MG_ERR_INVALID, "nrhs=%lld but the scratch is sized for %lld", nrhs, h->nrhs);
   if (!x || !y) return fail(MG_ERR_INVALID, "null vector");
   (void)hipSetDevice(h->device);
@@ -1173,14 +1133,14 @@ int mg_spmv_FP64(mg_hierarchy* h, long long level, long long which, double alpha
 int mg_time_op_dev_FP64(mg_hierarchy* h, long long level, long long kernel, long long nrhs,
                         long long reps, double* ms_avg, double* bytes) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
+  MG_TRY(need_finalized(h));
+  Level* Lp;
+  MG_TRY(find_level(h, level, &Lp));
   if (nrhs != h->nrhs) return fail(MG_ERR_INVALID, "nrhs=%lld but the scratch is sized for %lld", nrhs, h->nrhs);
   if (reps < 1 || !ms_avg) return fail(MG_ERR_INVALID, "reps < 1 or null output");
   (void)hipSetDevice(h->device);
   const int l = (int)level - 1;
-  Level& L = h->lev[(size_t)l];
+  Level& L = *Lp;
   const bool coarsest = (l == (int)h->nlevels - 1);
   if (coarsest && kernel != MG_K_COARSE && kernel != MG_K_SPMV && kernel != MG_K_RESIDUAL)
     return fail(MG_ERR_INVALID, "kernel %lld does not run on the coarsest level", kernel);
@@ -1297,9 +1257,8 @@ int mg_profile_get_moved(mg_hierarchy* h, long long level, long long kernel, dou
 int mg_operator_format(mg_hierarchy* h, long long level, long long which, long long* npatterns,
                        long long* dict_entries, double* index_bytes_per_launch) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   if (npatterns) *npatterns = M->has_pat ? M->npat : 0;
   if (dict_entries) *dict_entries = M->has_pat ? M->dict_entries : 0;
   // bytes of row pointers + column information one nrhs=1 launch streams
@@ -1314,9 +1273,8 @@ int mg_operator_format(mg_hierarchy* h, long long level, long long which, long l
 int mg_operator_rowclasses(mg_hierarchy* h, long long level, long long which, long long* nclasses,
                            long long* dict_entries, double* matrix_bytes_per_launch) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   if (nclasses) *nclasses = M->has_rc ? M->rc_ncls : 0;
   if (dict_entries) *dict_entries = M->has_rc ? M->rc_entries : 0;
   if (matrix_bytes_per_launch) {
@@ -1335,9 +1293,8 @@ int mg_operator_rowclasses(mg_hierarchy* h, long long level, long long which, lo
 int mg_operator_rowclass_flags(mg_hierarchy* h, long long level, long long which, long long* implicit_first,
                                long long* class_relax, long long* kernel_variant, long long* exception_rows) {
   MG_REAL_ONLY(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  Csr* M = pick(h, level, which);
-  if (!M || !M->set) return fail(MG_ERR_INVALID, "operator (level=%lld, which=%lld) not set", level, which);
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
   if (implicit_first) *implicit_first = (M->has_rc && M->rc_implicit) ? 1 : 0;
   if (class_relax) *class_relax = (M->has_rc && M->rc_has_d) ? 1 : 0;
   if (kernel_variant) {
@@ -1366,8 +1323,9 @@ int mg_operator_rowclass_flags(mg_hierarchy* h, long long level, long long which
 int mg_sweep_residual_form(mg_hierarchy* h, long long level, long long* form, long long* geometry) {
   MG_REAL_ONLY(h);
   if (!h || !form) return fail(MG_ERR_INVALID, "null argument");
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
-  const Csr& A = h->lev[(size_t)level - 1].A;
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
+  const Csr& A = L->A;
   *form = 0;
   if (!A.set || h->nrhs != 1) return MG_OK;
   const bool band = A.rm3_var && A.rc_march3;
@@ -1395,8 +1353,9 @@ int mg_sweep_residual_form(mg_hierarchy* h, long long level, long long* form, lo
 int mg_band_form(mg_hierarchy* h, long long level, long long* info) {
   MG_REAL_ONLY(h);
   if (!h || !info) return fail(MG_ERR_INVALID, "null argument");
-  if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
-  const Csr& A = h->lev[(size_t)level - 1].A;
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
+  const Csr& A = L->A;
   const bool band = A.set && A.rm3_var && A.rc_march3;
   info[0] = band ? 1 : 0;
   info[1] = band && A.band_canon ? 1 : 0;
@@ -1460,11 +1419,7 @@ int mg_op_create_FP64_INT64(long long device_id, long long n_rows, long long n_c
   UploadFence upload_fence;
   if (!out) return fail(MG_ERR_INVALID, "out is null");
   *out = nullptr;
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the multigrid cycle has no CPU fallback");
-  if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
-  HIP_TRY(hipSetDevice((int)device_id));
+  MG_TRY(use_device(device_id));
   mg_operator* op = new mg_operator();
   op->device = (int)device_id;
   const int rc = upload_csr(&op->M, Options::from_env(), n_rows, n_cols, colptr, rowval, nzval);
@@ -1489,11 +1444,7 @@ int mg_op_create_box_FP64_INT64(long long device_id, long long n_rows, long long
   *out = nullptr;
   if (n_rows != n_cols || regular_cols < 1 || regular_cols > n_rows || n1 * n2 * n3 != regular_cols)
     return fail(MG_ERR_INVALID, "box operator must be square with n1*n2*n3 == regular_cols <= n_rows");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the multigrid cycle has no CPU fallback");
-  if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
-  HIP_TRY(hipSetDevice((int)device_id));
+  MG_TRY(use_device(device_id));
   mg_operator* op = new mg_operator();
   op->device = (int)device_id;
   int rc = upload_csr(&op->M, Options::from_env(), n_rows, n_cols, colptr, rowval, nzval, regular_cols);
@@ -1521,11 +1472,7 @@ int mg_op_create_grid_FP64_INT64(long long device_id, long long n_rows, long lon
   const bool hints = f1 != 0 || f2 != 0 || f3 != 0 || c1 != 0 || c2 != 0 || c3 != 0;   // (all zero: only the owned | halo split)
   if (regular_cols < 1 || regular_cols > n_cols || (hints && (f1 * f2 * f3 != n_rows || c1 * c2 * c3 != regular_cols)))
     return fail(MG_ERR_INVALID, "grid operator: f1*f2*f3 must equal n_rows and c1*c2*c3 regular_cols <= n_cols");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the multigrid cycle has no CPU fallback");
-  if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
-  HIP_TRY(hipSetDevice((int)device_id));
+  MG_TRY(use_device(device_id));
   mg_operator* op = new mg_operator();
   op->device = (int)device_id;
   int rc = upload_csr(&op->M, Options::from_env(), n_rows, n_cols, colptr, rowval, nzval, regular_cols, n_rows);
@@ -1876,73 +1823,68 @@ int mg_kaczmarz_destroy(mg_kaczmarz* k) {
   return MG_OK;
 }
 
-// numit sweeps on device-resident x (in/out) and b, column-major n x nrhs; one launch per sweep (the barrier the
-// reference's `omp for` has between sweeps).  sequential != 0: one wavefront walks all sub-domains in order (the
-// reference with one thread); otherwise one wavefront per sub-domain.
+// The arguments of an apply and the handle's value type (cx: the entry point's)
+static int kaczmarz_args(bool cx, mg_kaczmarz* k, const double* x, const double* b, long long nrhs, long long numit) {
+  if (!k || !x || !b || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
+  if (k->cx != cx)
+    return fail(MG_ERR_STATE, "%s", cx ? "CFP64 Kaczmarz entry point called on an FP64 handle (mg_kaczmarz_create_CFP64_INT64)"
+                                       : "FP64 Kaczmarz entry point called on a CFP64 handle (mg_kaczmarz_apply*_CFP64)");
+  (void)hipSetDevice(k->device);
+  return MG_OK;
+}
+
+// numit sweeps on device-resident x (in/out) and b, column-major n x nrhs (cx: complex, interleaved); one launch per sweep
+// (the barrier the reference's `omp for` has between sweeps).  sequential != 0: one wavefront walks all sub-domains in
+// order (the reference with one thread); otherwise one wavefront per sub-domain.
+static int kaczmarz_apply_dev(bool cx, mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
+                              long long sequential) {
+  MG_TRY(kaczmarz_args(cx, k, x_dev, b_dev, nrhs, numit));
+  const dim3 grid(sequential ? 1u : (unsigned)k->num_domains);
+  for (long long it = 0; it < numit; ++it) {
+    if (cx)
+      hipLaunchKernelGGL(mgk::hybrid_kaczmarz_c, grid, dim3(64), 0, k->stream, k->rowptr.p, k->col.p,
+                         reinterpret_cast<const mgk::d2_t*>(k->val.p), k->arr.p, (int)k->num_domains, (int)k->domain_length, x_dev,
+                         b_dev, (int)nrhs, k->n, reinterpret_cast<const mgk::d2_t*>(k->invD.p), sequential ? 1 : 0);
+    else
+      hipLaunchKernelGGL(mgk::hybrid_kaczmarz, grid, dim3(64), 0, k->stream, k->rowptr.p, k->col.p, k->val.p, k->arr.p,
+                         (int)k->num_domains, (int)k->domain_length, x_dev, b_dev, (int)nrhs, k->n, k->invD.p, sequential ? 1 : 0);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(spin_sync(k->stream));
+  return MG_OK;
+}
+
+// Host buffers, exactly the reference's call (parRelax.jl:61-64 / 71-74): x (in/out) and b are n x nrhs column-major.
+static int kaczmarz_apply_host(bool cx, mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit,
+                               long long sequential) {
+  MG_TRY(kaczmarz_args(cx, k, x, b, nrhs, numit));
+  const size_t len = (cx ? 2 : 1) * (size_t)k->n * (size_t)nrhs;   // doubles
+  if (k->x.n != len) {
+    MG_TRY(k->x.alloc(len));
+    MG_TRY(k->b.alloc(len));
+  }
+  HIP_TRY(hipMemcpyAsync(k->x.p, x, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
+  HIP_TRY(hipMemcpyAsync(k->b.p, b, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
+  MG_TRY(kaczmarz_apply_dev(cx, k, k->x.p, k->b.p, nrhs, numit, sequential));
+  HIP_TRY(hipMemcpyAsync(x, k->x.p, len * sizeof(double), hipMemcpyDeviceToHost, k->stream));
+  HIP_TRY(spin_sync(k->stream));
+  return MG_OK;
+}
+
 int mg_kaczmarz_apply_dev_FP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
                                long long sequential) {
-  if (!k || !x_dev || !b_dev || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
-  if (k->cx) return fail(MG_ERR_STATE, "FP64 Kaczmarz entry point called on a CFP64 handle (mg_kaczmarz_apply*_CFP64)");
-  (void)hipSetDevice(k->device);
-  for (long long it = 0; it < numit; ++it)
-    hipLaunchKernelGGL(mgk::hybrid_kaczmarz, dim3(sequential ? 1u : (unsigned)k->num_domains), dim3(64), 0, k->stream,
-                       k->rowptr.p, k->col.p, k->val.p, k->arr.p, (int)k->num_domains, (int)k->domain_length, x_dev, b_dev,
-                       (int)nrhs, k->n, k->invD.p, sequential ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(spin_sync(k->stream));
-  return MG_OK;
+  return kaczmarz_apply_dev(false, k, x_dev, b_dev, nrhs, numit, sequential);
 }
-
-// Host buffers, exactly the reference's call (parRelax.jl:61-64): x (in/out) and b are n x nrhs column-major.
 int mg_kaczmarz_apply_FP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit, long long sequential) {
-  if (!k || !x || !b || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
-  if (k->cx) return fail(MG_ERR_STATE, "FP64 Kaczmarz entry point called on a CFP64 handle (mg_kaczmarz_apply*_CFP64)");
-  (void)hipSetDevice(k->device);
-  const size_t len = (size_t)k->n * (size_t)nrhs;
-  if (k->x.n != len) {
-    MG_TRY(k->x.alloc(len));
-    MG_TRY(k->b.alloc(len));
-  }
-  HIP_TRY(hipMemcpyAsync(k->x.p, x, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
-  HIP_TRY(hipMemcpyAsync(k->b.p, b, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
-  MG_TRY(mg_kaczmarz_apply_dev_FP64(k, k->x.p, k->b.p, nrhs, numit, sequential));
-  HIP_TRY(hipMemcpyAsync(x, k->x.p, len * sizeof(double), hipMemcpyDeviceToHost, k->stream));
-  HIP_TRY(spin_sync(k->stream));
-  return MG_OK;
+  return kaczmarz_apply_host(false, k, x, b, nrhs, numit, sequential);
 }
-
-// The complex sweeps (applyHybridKaczmarz_CFP64_INT64): x_dev and b_dev are n x nrhs column-major complex, interleaved.
+// The complex sweeps (applyHybridKaczmarz_CFP64_INT64): x and b interleaved complex
 int mg_kaczmarz_apply_dev_CFP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
                                 long long sequential) {
-  if (!k || !x_dev || !b_dev || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
-  if (!k->cx) return fail(MG_ERR_STATE, "CFP64 Kaczmarz entry point called on an FP64 handle (mg_kaczmarz_create_CFP64_INT64)");
-  (void)hipSetDevice(k->device);
-  for (long long it = 0; it < numit; ++it)
-    hipLaunchKernelGGL(mgk::hybrid_kaczmarz_c, dim3(sequential ? 1u : (unsigned)k->num_domains), dim3(64), 0, k->stream,
-                       k->rowptr.p, k->col.p, reinterpret_cast<const mgk::d2_t*>(k->val.p), k->arr.p, (int)k->num_domains,
-                       (int)k->domain_length, x_dev, b_dev, (int)nrhs, k->n,
-                       reinterpret_cast<const mgk::d2_t*>(k->invD.p), sequential ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(spin_sync(k->stream));
-  return MG_OK;
+  return kaczmarz_apply_dev(true, k, x_dev, b_dev, nrhs, numit, sequential);
 }
-
-// Host buffers, exactly the reference's call (parRelax.jl:71-74): x (in/out) and b are n x nrhs column-major complex.
 int mg_kaczmarz_apply_CFP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit, long long sequential) {
-  if (!k || !x || !b || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
-  if (!k->cx) return fail(MG_ERR_STATE, "CFP64 Kaczmarz entry point called on an FP64 handle (mg_kaczmarz_create_CFP64_INT64)");
-  (void)hipSetDevice(k->device);
-  const size_t len = 2 * (size_t)k->n * (size_t)nrhs;   // doubles
-  if (k->x.n != len) {
-    MG_TRY(k->x.alloc(len));
-    MG_TRY(k->b.alloc(len));
-  }
-  HIP_TRY(hipMemcpyAsync(k->x.p, x, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
-  HIP_TRY(hipMemcpyAsync(k->b.p, b, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
-  MG_TRY(mg_kaczmarz_apply_dev_CFP64(k, k->x.p, k->b.p, nrhs, numit, sequential));
-  HIP_TRY(hipMemcpyAsync(x, k->x.p, len * sizeof(double), hipMemcpyDeviceToHost, k->stream));
-  HIP_TRY(spin_sync(k->stream));
-  return MG_OK;
+  return kaczmarz_apply_host(true, k, x, b, nrhs, numit, sequential);
 }
 
 }  // extern "C"

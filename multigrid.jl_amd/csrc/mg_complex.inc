@@ -267,12 +267,6 @@ int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs) {
   return MG_OK;
 }
 
-bool cx_host_zero(const double* x, long long n) {
-  for (long long i = 0; i < 2 * n; ++i)
-    if (x[i] != 0.0) return false;
-  return true;
-}
-
 // mg_finalize of a CF64 handle: shapes chain, every level complete, scratch allocated
 int cx_finalize(mg_hierarchy* h) {
   CxState& S = *h->cx;
@@ -438,7 +432,7 @@ int mg_cycle_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long
   CxState& S = *h->cx;
   CxLevel& L0 = S.lev[0];
   bool xz = (x_is_zero == 1);
-  if (x_is_zero < 0) xz = cx_host_zero(x, n);   // norm(x) > 0.0 decides (MGcycle.jl:29)
+  if (x_is_zero < 0) xz = host_all_zero(x, 2 * n);   // norm(x) > 0.0 decides (MGcycle.jl:29)
   const size_t bytes = 2 * sizeof(double) * (size_t)n;
   int xi = 0;
   HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->stream));
@@ -460,7 +454,7 @@ int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long
   const size_t bytes = 2 * sizeof(double) * (size_t)n;
   const cx_t* bd = cxp(S.stage_b);
   int xi = 0;
-  bool xz = cx_host_zero(x, n);
+  bool xz = host_all_zero(x, 2 * n);
   HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->stream));
   double res2 = 0.0;
   if (xz) {   // SolveFuncs.jl:14-21

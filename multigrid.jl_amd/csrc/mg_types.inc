@@ -26,140 +26,164 @@ static inline hipError_t spin_sync(hipStream_t s) {
   return e;
 }
 
+// x == 0 everywhere?  Blocks of 4096 entries are OR-reduced bitwise (vectorises; the element-wise loop with its early
+// exit does not: 13 ms for 136 MB on the box's core) and only a block with a set bit - a non-zero or a -0.0 - is
+// looked at entry by entry.
+bool host_all_zero(const double* x, long long len) {
+  const long long B = 4096;
+  for (long long i0 = 0; i0 < len; i0 += B) {
+    const long long i1 = std::min(len, i0 + B);
+    unsigned long long acc = 0;
+    for (long long i = i0; i < i1; ++i) {
+      unsigned long long bits;
+      std::memcpy(&bits, x + i, 8);
+      acc |= bits;
+    }
+    if (acc != 0)
+      for (long long i = i0; i < i1; ++i)
+        if (x[i] != 0.0) return false;
+  }
+  return true;
+}
 
 // Switches and thresholds of the format selection (A/B measurements, tests).  Read from the environment ONCE per
 // handle - at mg_create / mg_op_create - and kept in the handle; mg_set_option overrides single entries through the
 // API before the operators are uploaded.  Nothing on the launch path reads the environment.
+// One line per option, X(type, key, default): the field, the key mg_set_option takes and, in upper case behind "MG_",
+// the environment variable (no_tile: MG_NO_TILE).
+#define MG_OPTIONS(X) \
+  X(bool, no_rowclass, false) \
+  X(bool, no_implicit_first, false) \
+  X(bool, no_class_d, false) \
+  X(bool, no_tile, false) \
+  X(bool, no_window, false) \
+  X(bool, no_pattern, false) \
+  X(bool, no_runs, false) \
+  X(bool, no_sched, false) \
+  X(bool, no_pair, false) \
+  X(bool, no_fused_next, false) \
+  X(bool, no_march, false) \
+  X(bool, no_lane, false) \
+  X(bool, no_lane_mm, false) \
+  X(bool, no_tile_small, false) \
+  X(bool, no_march2, false)        /* never fuse a sweep with the residual that follows it (csr_rowclass_march2_spmv) */ \
+  X(bool, no_tile_lane, false) \
+  X(bool, no_winp, false) \
+  X(bool, no_band, false) \
+  X(bool, no_lane_rpl3, false) \
+  X(bool, no_march2_zero, false) \
+  X(bool, no_mgs_chain, false) \
+  X(bool, no_restrict_scale, false) \
+  X(long long, rap_chunk, 2048)    /* target columns of a coarse row the numeric Galerkin product accumulates at a time (<= 2048; tests) */ \
+  X(bool, no_dead_t, false)        /* solve loop: store the iterate of every step (A/B, bit-identity tests) */ \
+  X(bool, no_march3, false)        /* never use the 2-D tile form of the two-stage pass (csr_rowclass_march3_spmv) */ \
+  X(long long, march3_k1, 0)       /* rows of the stage-1 region per lane (0: by the fill estimate; 2..4): tile height = K1 * (NT / (TX + 2)) - 2 */ \
+  X(long long, march3_nt, 0)       /* threads per workgroup (0: by the fill estimate; 1024 or 768) */ \
+  X(long long, march3_tiles_x, 0)  /* 0: chosen by the fill estimate; > 0: this many tiles per grid line */ \
+  X(bool, no_march3_lockstep, false)      /* schedule of the 2-D tile form */ \
+  X(bool, march3_lockstep_force, false)   /* schedule of the 2-D tile form */ \
+  X(bool, no_pipeline, false)      /* solve loop: read a four-stage step's norm before the next step is enqueued (A/B) */ \
+  X(bool, no_march4, false)        /* solve loop: never run the two fine-level passes across the stopping test as one four-stage pass */ \
+  X(long long, march4_nt, 0)       /* threads per workgroup of the four-stage pass (0: default; 1024 / 768 / 512 = 2 / 3 / 4 rows per lane) */ \
+  X(long long, march4_tiles_x, 0)  /* 0: chosen by the fill estimate; > 0: this many tiles per grid line */ \
+  X(long long, march4_ty_max, 0)   /* tests: tallest tile (several tile rows on small grids) */ \
+  X(long long, march4_segs, 0)     /* A/B, tests: segments per tile (0: chosen by the cost model; tiles x segments may exceed the CUs) */ \
+  X(long long, columns_streams, 2) /* column-wise block solve: streams the columns take turns on (1: one stream; at most 8) */ \
+  X(bool, no_columns, false)       /* blocks of right-hand sides: never solve column by column on the single-vector kernels (A/B) */ \
+  X(bool, no_marchr, false)        /* restriction: the gather form (csr_rowclass_lane_spmv) on every level (A/B) */ \
+  X(long long, marchr_min_rows, 1000000)   /* coarse rows below which the gather form stays */ \
+  X(long long, marchr_segs, 0)     /* A/B, tests */ \
+  X(long long, marchr_tx, 0)       /* A/B, tests */ \
+  X(long long, marchr_ty, 0)       /* A/B, tests */ \
+  X(bool, no_march27, false)       /* 27-point levels: plane-tile kernel, sweep and residual as two launches (A/B) */ \
+  X(bool, no_defer_sum, false)     /* solve loop: the four-stage pass's final sum as a launch of its own instead of one more workgroup of the fine restriction (A/B) */ \
+  X(bool, no_small_fuse, false)    /* small levels: residual + restriction and prolongation + first post-sweep as two launches each (round 5's path; A/B) */ \
+  X(bool, no_march27_zero, false)  /* the 27-point pair of a level entered with x = 0 reads x1 = d.*b written by the restriction (round 5's path; A/B) */ \
+  X(long long, march27_nt, 0)      /* A/B, tests (0: chosen by the cost model) */ \
+  X(long long, march27_tiles_x, 0) /* A/B, tests (0: chosen by the cost model) */ \
+  X(long long, march27_segs, 0)    /* A/B, tests (0: chosen by the cost model) */ \
+  X(long long, march27_wgs, 0)     /* A/B, tests (0: chosen by the cost model) */ \
+  X(long long, march27_min_rows, 500000)   /* smaller levels are latency-bound: the 256-row plane tiles serve them */ \
+  X(long long, march4_k1, 0)       /* rows per lane (0: 2 / 3 / 4 at 1024 / 768 / 512 threads; 768 threads also take 4) */ \
+  X(bool, no_small, false)         /* small grid levels: never use the one-trip kernels of mg_small.hpp (A/B) */ \
+  X(long long, small_max_rows, 300000)     /* largest level (rows of A / coarse rows of R / fine rows of P) they serve */ \
+  X(bool, no_band27, false)        /* variable-coefficient 27-point grid levels: pattern-coded CSR kernels instead of the planar band-27 form (A/B) */ \
+  X(long long, band27_max_rows, 40000000)  /* largest operator held in band-27 form (216 B per row on top of the CSR arrays) */ \
+  X(bool, no_ci16, false)          /* long rows: keep 32-bit column indices (A/B) */ \
+  X(bool, force_rowptr64, false)   /* upload every operator with 64-bit row pointers (the path of operators with >= 2^31 non-zeros; tests) */ \
+  X(bool, no_longrow, false)       /* never use csr_longrow_spmv (one wavefront per row) for operators of long rows (A/B) */ \
+  X(long long, longrow_min_avg, 1000)      /* ... it serves operators without row classes whose rows average at least this many entries */ \
+  X(long long, small_p_max_rows, 4000000)  /* the arithmetic prolongation up to this many fine rows (C2: level 2 13.9 us against 19.0 for the staged \
+                                              windows, level 1 85.5 against 86.8 - left on the windows; profiles/r05_small_levels.md) */ \
+  X(long long, small_r_max_rows, 0)        /* A/B: the small restriction up to this many coarse rows (0: small_max_rows; 2.1 M rows: 64 us against 54 marching) */ \
+  X(long long, small_over_rc, 0)   /* ... also where the operator is stored as row classes, up to this many rows (A/B; by default the \
+                                      small kernels replace the STREAMING kernels of the levels below rowclass_min_rows) */ \
+  X(bool, debug_format, false) \
+  X(bool, debug_timing, false) \
+  X(int, nt, -1)                   /* -1: by operator size; 0 / 1: force the cache policy of the matrix stream */ \
+  X(long long, rowclass_min_rows, 100000) \
+  X(long long, rowclass_max_passes, 4) \
+  X(long long, rowclass_keep_singletons, 1024) \
+  X(long long, stage_min_len, 1) \
+  X(long long, tile_min_wg, 256) \
+  X(long long, window_min_wg, 2048) \
+  X(long long, pair_min_rows, 1000000) \
+  X(long long, march_min_wg, 256) \
+  X(long long, march_wg_per_cu, 2) /* resident workgroups per CU of the marching kernel (49 KB of LDS each) */ \
+  X(long long, winp_min_rows, 100000)      /* smallest prolongation-shaped operator served by csr_rowclass_winp_spmv */ \
+  X(bool, no_wave_restrict, false) /* restrictions of vertex-centred grid pairs: the marching / lane-per-row kernels instead of the wavefront form (A/B) */ \
+  X(long long, wave_restrict_min_rows, 0) \
+  X(bool, no_cell_prolong, false)  /* prolongations of vertex-centred grid pairs: the windowed / lane-per-row kernels instead of the lane-per-coarse-cell one (A/B) */ \
+  X(bool, no_band_sym, false)      /* band form: read all 7 planes even where the operator is symmetric */ \
+  X(bool, band_sym_tol, false)     /* band-27 levels: accept symmetry up to the rounding of the Galerkin product (2^-50 |a_ii|) for the symmetric reads - \
+                                      the operator applied then differs from the stored CSR at rounding level (default: bit-for-bit symmetry only) */ \
+  X(long long, band_min_rows, 100000)      /* smallest variable-coefficient grid operator held in band form (build_band) */ \
+  X(long long, march_max_len, 8)   /* longest class the marching kernel is used for (27-point levels: plane tiles, measured) */ \
+  X(bool, dist_tail_graph, false)  /* replay the replicated tail of the sharded sequencer as a HIP graph (measured slower) */ \
+  X(bool, no_graph, false) \
+  X(bool, no_lane_pairs, false) \
+  X(long long, graph_max_rows, 300000)     /* sub-cycles from the first level of at most this many rows*nrhs replay as one HIP graph */ \
+  X(long long, lu_multi_min_rows, 4096)    /* sparse coarse factors of this many rows: per-level launches + dense trailing inverse */ \
+  X(long long, lu_dense_tail_min, 64) \
+  X(long long, lu_dense_tail_max, 16384)   /* largest trailing block kept as an explicit inverse (8*M^2 bytes each for L and U: 2 x 2.1 GB) */ \
+  X(double, rowclass_min_cover, 0.9) \
+  X(double, sched_budget, 2.0e6)
+
 struct Options {
-  bool no_rowclass = false, no_implicit_first = false, no_class_d = false, no_tile = false, no_window = false;
-  bool no_pattern = false, no_runs = false, no_sched = false, no_pair = false, no_fused_next = false;
-  bool no_march = false, no_lane = false, no_lane_mm = false;
-  bool no_tile_small = false;
-  bool no_march2 = false, no_tile_lane = false, no_winp = false, no_band = false, no_lane_rpl3 = false, no_march2_zero = false, no_mgs_chain = false, no_restrict_scale = false;   // never fuse a sweep with the residual that follows it (csr_rowclass_march2_spmv)
-  long long rap_chunk = 2048;      // target columns of a coarse row the numeric Galerkin product accumulates at a time (<= 2048; tests)
-  bool no_dead_t = false;          // solve loop: store the iterate of every step (A/B, bit-identity tests)
-  bool no_march3 = false;          // never use the 2-D tile form of the two-stage pass (csr_rowclass_march3_spmv)
-  long long march3_k1 = 0;         // rows of the stage-1 region per lane (0: by the fill estimate; 2..4): tile height = K1 * (NT / (TX + 2)) - 2
-  long long march3_nt = 0;         // threads per workgroup (0: by the fill estimate; 1024 or 768)
-  long long march3_tiles_x = 0;    // 0: chosen by the fill estimate; > 0: this many tiles per grid line
-  bool no_march3_lockstep = false, march3_lockstep_force = false;   // schedule of the 2-D tile form
-  bool no_pipeline = false;        // solve loop: read a four-stage step's norm before the next step is enqueued (A/B)
-  bool no_march4 = false;          // solve loop: never run the two fine-level passes across the stopping test as one four-stage pass
-  long long march4_nt = 0;         // threads per workgroup of the four-stage pass (0: default; 1024 / 768 / 512 = 2 / 3 / 4 rows per lane)
-  long long march4_tiles_x = 0;    // 0: chosen by the fill estimate; > 0: this many tiles per grid line
-  long long march4_ty_max = 0;     // tests: tallest tile (several tile rows on small grids)
-  long long march4_segs = 0;       // A/B, tests: segments per tile (0: chosen by the cost model; tiles x segments may exceed the CUs)
-  long long columns_streams = 2;   // column-wise block solve: streams the columns take turns on (1: one stream; at most 8)
-  bool no_columns = false;         // blocks of right-hand sides: never solve column by column on the single-vector kernels (A/B)
-  bool no_marchr = false;          // restriction: the gather form (csr_rowclass_lane_spmv) on every level (A/B)
-  long long marchr_min_rows = 1000000, marchr_segs = 0, marchr_tx = 0, marchr_ty = 0;   // coarse rows below which the gather form stays; A/B, tests
-  bool no_march27 = false;         // 27-point levels: plane-tile kernel, sweep and residual as two launches (A/B)
-  bool no_defer_sum = false;       // solve loop: the four-stage pass's final sum as a launch of its own instead of one more workgroup of the fine restriction (A/B)
-  bool no_small_fuse = false;      // small levels: residual + restriction and prolongation + first post-sweep as two launches each (round 5's path; A/B)
-  bool no_march27_zero = false;    // the 27-point pair of a level entered with x = 0 reads x1 = d.*b written by the restriction (round 5's path; A/B)
-  long long march27_nt = 0, march27_tiles_x = 0, march27_segs = 0, march27_wgs = 0;   // A/B, tests (0: chosen by the cost model)
-  long long march27_min_rows = 500000;   // smaller levels are latency-bound: the 256-row plane tiles serve them
-  long long march4_k1 = 0;         // rows per lane (0: 2 / 3 / 4 at 1024 / 768 / 512 threads; 768 threads also take 4)
-  bool no_small = false;           // small grid levels: never use the one-trip kernels of mg_small.hpp (A/B)
-  long long small_max_rows = 300000;   // largest level (rows of A / coarse rows of R / fine rows of P) they serve
-  bool no_band27 = false;          // variable-coefficient 27-point grid levels: pattern-coded CSR kernels instead of the planar band-27 form (A/B)
-  long long band27_max_rows = 40000000;   // largest operator held in band-27 form (216 B per row on top of the CSR arrays)
-  bool no_ci16 = false;            // long rows: keep 32-bit column indices (A/B)
-  bool force_rowptr64 = false;     // upload every operator with 64-bit row pointers (the path of operators with >= 2^31 non-zeros; tests)
-  bool no_longrow = false;         // never use csr_longrow_spmv (one wavefront per row) for operators of long rows (A/B)
-  long long longrow_min_avg = 1000;  // ... it serves operators without row classes whose rows average at least this many entries
-  long long small_p_max_rows = 4000000;   // the arithmetic prolongation up to this many fine rows (C2: level 2 13.9 us against 19.0 for the staged
-                                          // windows, level 1 85.5 against 86.8 - left on the windows; profiles/r05_small_levels.md)
-  long long small_r_max_rows = 0;         // A/B: the small restriction up to this many coarse rows (0: small_max_rows; 2.1 M rows: 64 us against 54 marching)
-  long long small_over_rc = 0;         // ... also where the operator is stored as row classes, up to this many rows (A/B; by default the
-                                       // small kernels replace the STREAMING kernels of the levels below rowclass_min_rows)
-  bool debug_format = false, debug_timing = false;
-  int nt = -1;   // -1: by operator size; 0 / 1: force the cache policy of the matrix stream
-  long long rowclass_min_rows = 100000, rowclass_max_passes = 4, rowclass_keep_singletons = 1024;
-  long long stage_min_len = 1, tile_min_wg = 256, window_min_wg = 2048, pair_min_rows = 1000000, march_min_wg = 256;
-  long long march_wg_per_cu = 2;   // resident workgroups per CU of the marching kernel (49 KB of LDS each)
-  long long winp_min_rows = 100000;   // smallest prolongation-shaped operator served by csr_rowclass_winp_spmv
-  bool no_wave_restrict = false;      // restrictions of vertex-centred grid pairs: the marching / lane-per-row kernels instead of the wavefront form (A/B)
-  long long wave_restrict_min_rows = 0;
-  bool no_cell_prolong = false;       // prolongations of vertex-centred grid pairs: the windowed / lane-per-row kernels instead of the lane-per-coarse-cell one (A/B)
-  bool no_band_sym = false;           // band form: read all 7 planes even where the operator is symmetric
-  bool band_sym_tol = false;          // band-27 levels: accept symmetry up to the rounding of the Galerkin product (2^-50 |a_ii|) for the symmetric reads -
-                                      // the operator applied then differs from the stored CSR at rounding level (default: bit-for-bit symmetry only)
-  long long band_min_rows = 100000;   // smallest variable-coefficient grid operator held in band form (build_band)
-  long long march_max_len = 8;   // longest class the marching kernel is used for (27-point levels: plane tiles, measured)
-  bool dist_tail_graph = false;   // replay the replicated tail of the sharded sequencer as a HIP graph (measured slower)
-  bool no_graph = false, no_lane_pairs = false;
-  long long graph_max_rows = 300000;    // sub-cycles from the first level of at most this many rows*nrhs replay as one HIP graph
-  long long lu_multi_min_rows = 4096;   // sparse coarse factors of this many rows: per-level launches + dense trailing inverse
-  long long lu_dense_tail_min = 64;
-  long long lu_dense_tail_max = 16384;  // largest trailing block kept as an explicit inverse (8*M^2 bytes each for L and U: 2 x 2.1 GB)
-  double rowclass_min_cover = 0.9, sched_budget = 2.0e6;
-  struct Entry { const char* env; const char* key; int kind; size_t off; };   // kind 0 bool, 1 long long, 2 double, 3 int
-  static const Entry* table(size_t* n);
-  bool set(const char* key, double v, bool by_env);
+#define MG_OPT_FIELD(type, key, def) type key = def;
+  MG_OPTIONS(MG_OPT_FIELD)
+#undef MG_OPT_FIELD
+  bool set(const char* key, double v);   // false: no option of that key
   static Options from_env();
 };
-#define MG_OPT(env, key, kind, field) {env, key, kind, offsetof(Options, field)}
-const Options::Entry* Options::table(size_t* n) {
-  static const Entry t[] = {
-      MG_OPT("MG_NO_ROWCLASS", "no_rowclass", 0, no_rowclass), MG_OPT("MG_NO_IMPLICIT_FIRST", "no_implicit_first", 0, no_implicit_first),
-      MG_OPT("MG_NO_CLASS_D", "no_class_d", 0, no_class_d), MG_OPT("MG_NO_TILE", "no_tile", 0, no_tile),
-      MG_OPT("MG_NO_WINDOW", "no_window", 0, no_window), MG_OPT("MG_NO_PATTERN", "no_pattern", 0, no_pattern),
-      MG_OPT("MG_NO_RUNS", "no_runs", 0, no_runs), MG_OPT("MG_NO_SCHED", "no_sched", 0, no_sched),
-      MG_OPT("MG_NO_PAIR", "no_pair", 0, no_pair), MG_OPT("MG_NO_FUSED_NEXT", "no_fused_next", 0, no_fused_next),
-      MG_OPT("MG_NO_MARCH", "no_march", 0, no_march), MG_OPT("MG_NO_MARCH2", "no_march2", 0, no_march2), MG_OPT("MG_NO_TILE_LANE", "no_tile_lane", 0, no_tile_lane), MG_OPT("MG_NO_TILE_SMALL", "no_tile_small", 0, no_tile_small), MG_OPT("MG_NO_WINP", "no_winp", 0, no_winp), MG_OPT("MG_NO_BAND", "no_band", 0, no_band), MG_OPT("MG_NO_LANE_RPL3", "no_lane_rpl3", 0, no_lane_rpl3), MG_OPT("MG_NO_MARCH2_ZERO", "no_march2_zero", 0, no_march2_zero), MG_OPT("MG_NO_MGS_CHAIN", "no_mgs_chain", 0, no_mgs_chain), MG_OPT("MG_NO_RESTRICT_SCALE", "no_restrict_scale", 0, no_restrict_scale), MG_OPT("MG_NO_LANE", "no_lane", 0, no_lane), MG_OPT("MG_NO_LANE_MM", "no_lane_mm", 0, no_lane_mm),
-      MG_OPT("MG_RAP_CHUNK", "rap_chunk", 1, rap_chunk), MG_OPT("MG_NO_DEAD_T", "no_dead_t", 0, no_dead_t), MG_OPT("MG_NO_MARCH3", "no_march3", 0, no_march3), MG_OPT("MG_MARCH3_K1", "march3_k1", 1, march3_k1), MG_OPT("MG_MARCH3_TILES_X", "march3_tiles_x", 1, march3_tiles_x), MG_OPT("MG_MARCH3_NT", "march3_nt", 1, march3_nt),
-      MG_OPT("MG_NO_PIPELINE", "no_pipeline", 0, no_pipeline), MG_OPT("MG_NO_MARCH4", "no_march4", 0, no_march4), MG_OPT("MG_NO_WAVE_RESTRICT", "no_wave_restrict", 0, no_wave_restrict), MG_OPT("MG_WAVE_RESTRICT_MIN_ROWS", "wave_restrict_min_rows", 1, wave_restrict_min_rows), MG_OPT("MG_NO_CELL_PROLONG", "no_cell_prolong", 0, no_cell_prolong), MG_OPT("MG_NO_BAND_SYM", "no_band_sym", 0, no_band_sym), MG_OPT("MG_BAND_SYM_TOL", "band_sym_tol", 0, band_sym_tol), MG_OPT("MG_MARCH4_NT", "march4_nt", 1, march4_nt), MG_OPT("MG_MARCH4_TILES_X", "march4_tiles_x", 1, march4_tiles_x), MG_OPT("MG_MARCH4_K1", "march4_k1", 1, march4_k1), MG_OPT("MG_MARCH4_TY_MAX", "march4_ty_max", 1, march4_ty_max), MG_OPT("MG_MARCH4_SEGS", "march4_segs", 1, march4_segs),
-      MG_OPT("MG_NO_COLUMNS", "no_columns", 0, no_columns), MG_OPT("MG_COLUMNS_STREAMS", "columns_streams", 1, columns_streams), MG_OPT("MG_NO_MARCHR", "no_marchr", 0, no_marchr), MG_OPT("MG_MARCHR_MIN_ROWS", "marchr_min_rows", 1, marchr_min_rows), MG_OPT("MG_MARCHR_SEGS", "marchr_segs", 1, marchr_segs), MG_OPT("MG_MARCHR_TX", "marchr_tx", 1, marchr_tx), MG_OPT("MG_MARCHR_TY", "marchr_ty", 1, marchr_ty),
-      MG_OPT("MG_NO_MARCH27", "no_march27", 0, no_march27), MG_OPT("MG_NO_MARCH27_ZERO", "no_march27_zero", 0, no_march27_zero), MG_OPT("MG_NO_SMALL_FUSE", "no_small_fuse", 0, no_small_fuse), MG_OPT("MG_NO_DEFER_SUM", "no_defer_sum", 0, no_defer_sum), MG_OPT("MG_MARCH27_NT", "march27_nt", 1, march27_nt), MG_OPT("MG_MARCH27_TILES_X", "march27_tiles_x", 1, march27_tiles_x), MG_OPT("MG_MARCH27_SEGS", "march27_segs", 1, march27_segs), MG_OPT("MG_MARCH27_WGS", "march27_wgs", 1, march27_wgs), MG_OPT("MG_MARCH27_MIN_ROWS", "march27_min_rows", 1, march27_min_rows),
-      MG_OPT("MG_NO_MARCH3_LOCKSTEP", "no_march3_lockstep", 0, no_march3_lockstep), MG_OPT("MG_MARCH3_LOCKSTEP_FORCE", "march3_lockstep_force", 0, march3_lockstep_force),
-      MG_OPT("MG_NO_SMALL", "no_small", 0, no_small), MG_OPT("MG_SMALL_MAX_ROWS", "small_max_rows", 1, small_max_rows), MG_OPT("MG_NO_LONGROW", "no_longrow", 0, no_longrow), MG_OPT("MG_FORCE_ROWPTR64", "force_rowptr64", 0, force_rowptr64), MG_OPT("MG_NO_CI16", "no_ci16", 0, no_ci16), MG_OPT("MG_NO_BAND27", "no_band27", 0, no_band27), MG_OPT("MG_BAND27_MAX_ROWS", "band27_max_rows", 1, band27_max_rows), MG_OPT("MG_LONGROW_MIN_AVG", "longrow_min_avg", 1, longrow_min_avg), MG_OPT("MG_SMALL_OVER_RC", "small_over_rc", 1, small_over_rc), MG_OPT("MG_SMALL_P_MAX_ROWS", "small_p_max_rows", 1, small_p_max_rows), MG_OPT("MG_SMALL_R_MAX_ROWS", "small_r_max_rows", 1, small_r_max_rows),
-      MG_OPT("MG_DEBUG_FORMAT", "debug_format", 0, debug_format), MG_OPT("MG_DEBUG_TIMING", "debug_timing", 0, debug_timing),
-      MG_OPT("MG_NT", "nt", 3, nt),
-      MG_OPT("MG_ROWCLASS_MIN_ROWS", "rowclass_min_rows", 1, rowclass_min_rows),
-      MG_OPT("MG_ROWCLASS_MAX_PASSES", "rowclass_max_passes", 1, rowclass_max_passes),
-      MG_OPT("MG_ROWCLASS_KEEP_SINGLETONS", "rowclass_keep_singletons", 1, rowclass_keep_singletons),
-      MG_OPT("MG_STAGE_MIN_LEN", "stage_min_len", 1, stage_min_len), MG_OPT("MG_TILE_MIN_WG", "tile_min_wg", 1, tile_min_wg),
-      MG_OPT("MG_WINDOW_MIN_WG", "window_min_wg", 1, window_min_wg), MG_OPT("MG_PAIR_MIN_ROWS", "pair_min_rows", 1, pair_min_rows),
-      MG_OPT("MG_MARCH_MIN_WG", "march_min_wg", 1, march_min_wg), MG_OPT("MG_MARCH_MAX_LEN", "march_max_len", 1, march_max_len),
-      MG_OPT("MG_MARCH_WG_PER_CU", "march_wg_per_cu", 1, march_wg_per_cu), MG_OPT("MG_WINP_MIN_ROWS", "winp_min_rows", 1, winp_min_rows), MG_OPT("MG_BAND_MIN_ROWS", "band_min_rows", 1, band_min_rows),
-      MG_OPT("MG_NO_GRAPH", "no_graph", 0, no_graph), MG_OPT("MG_DIST_TAIL_GRAPH", "dist_tail_graph", 0, dist_tail_graph), MG_OPT("MG_NO_LANE_PAIRS", "no_lane_pairs", 0, no_lane_pairs), MG_OPT("MG_GRAPH_MAX_ROWS", "graph_max_rows", 1, graph_max_rows),
-      MG_OPT("MG_LU_MULTI_MIN_ROWS", "lu_multi_min_rows", 1, lu_multi_min_rows),
-      MG_OPT("MG_LU_DENSE_TAIL_MAX", "lu_dense_tail_max", 1, lu_dense_tail_max),
-      MG_OPT("MG_LU_DENSE_TAIL_MIN", "lu_dense_tail_min", 1, lu_dense_tail_min),
-      MG_OPT("MG_ROWCLASS_MIN_COVER", "rowclass_min_cover", 2, rowclass_min_cover),
-      MG_OPT("MG_SCHED_BUDGET", "sched_budget", 2, sched_budget),
-  };
-  *n = sizeof t / sizeof t[0];
-  return t;
-}
-#undef MG_OPT
-bool Options::set(const char* key, double v, bool by_env) {
-  size_t n = 0;
-  const Entry* t = table(&n);
-  for (size_t i = 0; i < n; ++i) {
-    if (std::strcmp(by_env ? t[i].env : t[i].key, key) != 0) continue;
-    char* base = reinterpret_cast<char*>(this) + t[i].off;
-    switch (t[i].kind) {
-      case 0: *reinterpret_cast<bool*>(base) = (v != 0.0); break;
-      case 1: *reinterpret_cast<long long*>(base) = (long long)v; break;
-      case 2: *reinterpret_cast<double*>(base) = v; break;
-      default: *reinterpret_cast<int*>(base) = (int)v; break;
-    }
-    return true;
+bool Options::set(const char* key, double v) {
+#define MG_OPT_SET(type, k, def)   \
+  if (std::strcmp(key, #k) == 0) { \
+    k = static_cast<type>(v);      \
+    return true;                   \
   }
+  MG_OPTIONS(MG_OPT_SET)
+#undef MG_OPT_SET
   return false;
 }
+// the environment variable of an option: "MG_" + the key in upper case
+std::string option_env(const char* key) {
+  std::string e = "MG_";
+  for (const char* c = key; *c; ++c) e += (*c >= 'a' && *c <= 'z') ? (char)(*c - 'a' + 'A') : *c;
+  return e;
+}
+// an option's value from its environment variable; historical semantics of the boolean switches: "1" switches on,
+// anything else off
+void env_value(bool& o, const char* e) { o = (e[0] == '1'); }
+template <typename T>
+void env_value(T& o, const char* e) { o = static_cast<T>(std::atof(e)); }
 Options Options::from_env() {
   Options o;
-  size_t n = 0;
-  const Entry* t = table(&n);
-  for (size_t i = 0; i < n; ++i)
-    if (const char* e = std::getenv(t[i].env)) {
-      // historical semantics of the boolean switches: "1" switches on, anything else off (MG_DEBUG_TIMING: any value)
-      if (t[i].kind == 0) o.set(t[i].env, (e[0] == '1' || std::strcmp(t[i].env, "MG_DEBUG_TIMING") == 0) ? 1.0 : 0.0, true);
-      else o.set(t[i].env, std::atof(e), true);
-    }
+#define MG_OPT_ENV(type, k, def) \
+  if (const char* e = std::getenv(option_env(#k).c_str())) env_value(o.k, e);
+  MG_OPTIONS(MG_OPT_ENV)
+#undef MG_OPT_ENV
+  if (std::getenv("MG_DEBUG_TIMING")) o.debug_timing = true;   // (any value)
   if (o.sched_budget < 1.0) o.sched_budget = 1.0;
   return o;
 }

@@ -432,60 +432,51 @@ class DeviceHierarchy:
                                                 int(maxIter), C.byref(iters), _f64(resvec)), "mg_solve")
         return x, int(iters.value), resvec[: iters.value + 1]
 
+    def _krylov(self, name, res, b, x, *args, nres=True):
+        """Call mg_<name>_FP64(handle, b, x, *args, &iters, &flag, res[, &nres]); returns (flag, iters, res cut to nres, or to
+        iters for the drivers without nres)."""
+        iters, flag, count = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        tail = (C.byref(count),) if nres else ()
+        fn = getattr(self.lib, f"mg_{name}_FP64")
+        _check(self.lib, fn(self.handle, b, x, *args, C.byref(iters), C.byref(flag), _f64(res), *tail), f"mg_{name}")
+        return int(flag.value), int(iters.value), res[: (count if nres else iters).value]
+
     def pcg(self, b, x, tol: float, maxIter: int):
         """KrylovMethods.cg / blockCG with the MG cycle as preconditioner; returns (x, flag, iters, resvec)
         (resvec: ||r||/||b|| per iteration; for a block the maximum over the columns)."""
         b = self._host_block(b)
         x = self._host_block(x, True)
         if b.ndim != 1 and b.shape[1] > 1:
-            iters, flag = C.c_longlong(0), C.c_longlong(0)
-            resmat = np.zeros((max(int(maxIter), 1), b.shape[1]))
-            _check(self.lib, self.lib.mg_block_pcg_FP64(self.handle, _f64(b), _f64(x), b.shape[0], b.shape[1], float(tol),
-                                                        int(maxIter), C.byref(iters), C.byref(flag), _f64(resmat)), "mg_block_pcg")
-            self.last_resmat = resmat[: iters.value]
-            return x, int(flag.value), int(iters.value), resmat[: iters.value].max(axis=1) if iters.value else np.zeros(0)
+            flag, iters, self.last_resmat = self._krylov("block_pcg", np.zeros((max(int(maxIter), 1), b.shape[1])), _f64(b), _f64(x),
+                                                         b.shape[0], b.shape[1], float(tol), int(maxIter), nres=False)
+            return x, flag, iters, self.last_resmat.max(axis=1) if iters else np.zeros(0)
         if b.ndim != 1:
             b, x = b[:, 0], x[:, 0]
-        iters, flag = C.c_longlong(0), C.c_longlong(0)
-        resvec = np.zeros(max(int(maxIter), 1))
-        _check(self.lib, self.lib.mg_pcg_FP64(self.handle, _f64(b), _f64(x), b.shape[0], float(tol), int(maxIter),
-                                              C.byref(iters), C.byref(flag), _f64(resvec)), "mg_pcg")
-        return x, int(flag.value), int(iters.value), resvec[: iters.value]
+        return (x,) + self._krylov("pcg", np.zeros(max(int(maxIter), 1)), _f64(b), _f64(x), b.shape[0], float(tol), int(maxIter),
+                                   nres=False)
 
     def bicgstab(self, b, x, tol: float, maxIter: int):
         """KrylovMethods.bicgstb with the MG cycle as M1; returns (x, flag, iters, resvec)."""
         b = self._host_block(b)
         x = self._host_block(x, True)
-        iters, flag, nres = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
         resvec = np.zeros(2 * int(maxIter) + 1)
         if b.ndim != 1 and b.shape[1] > 1:
-            _check(self.lib, self.lib.mg_block_bicgstab_FP64(self.handle, _f64(b), _f64(x), b.shape[0], b.shape[1], float(tol),
-                                                             int(maxIter), C.byref(iters), C.byref(flag), _f64(resvec),
-                                                             C.byref(nres)), "mg_block_bicgstab")
-            return x, int(flag.value), int(iters.value), resvec[: nres.value]
+            return (x,) + self._krylov("block_bicgstab", resvec, _f64(b), _f64(x), b.shape[0], b.shape[1], float(tol), int(maxIter))
         if b.ndim != 1:
             b, x = b[:, 0], x[:, 0]
-        _check(self.lib, self.lib.mg_bicgstab_FP64(self.handle, _f64(b), _f64(x), b.shape[0], float(tol), int(maxIter),
-                                                   C.byref(iters), C.byref(flag), _f64(resvec), C.byref(nres)), "mg_bicgstab")
-        return x, int(flag.value), int(iters.value), resvec[: nres.value]
+        return (x,) + self._krylov("bicgstab", resvec, _f64(b), _f64(x), b.shape[0], float(tol), int(maxIter))
 
     def fgmres(self, b, x, inner: int, tol: float, maxIter: int):
         """KrylovMethods.fgmres (flexible) with the MG cycle as preconditioner; returns (x, flag, iters, resvec)."""
         b = self._host_block(b)
         x = self._host_block(x, True)
-        iters, flag, nres = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
         resvec = np.zeros(max(1, int(inner) * int(maxIter)))
         if b.ndim != 1 and b.shape[1] > 1:
-            _check(self.lib, self.lib.mg_block_fgmres_FP64(self.handle, _f64(b), _f64(x), b.shape[0], b.shape[1], int(inner),
-                                                           float(tol), int(maxIter), C.byref(iters), C.byref(flag), _f64(resvec),
-                                                           C.byref(nres)), "mg_block_fgmres")
-            return x, int(flag.value), int(iters.value), resvec[: nres.value]
+            return (x,) + self._krylov("block_fgmres", resvec, _f64(b), _f64(x), b.shape[0], b.shape[1], int(inner), float(tol),
+                                       int(maxIter))
         if b.ndim != 1:
             b, x = b[:, 0], x[:, 0]
-        _check(self.lib, self.lib.mg_fgmres_FP64(self.handle, _f64(b), _f64(x), b.shape[0], int(inner), float(tol),
-                                                 int(maxIter), C.byref(iters), C.byref(flag), _f64(resvec), C.byref(nres)),
-               "mg_fgmres")
-        return x, int(flag.value), int(iters.value), resvec[: nres.value]
+        return (x,) + self._krylov("fgmres", resvec, _f64(b), _f64(x), b.shape[0], int(inner), float(tol), int(maxIter))
 
     def cycle_mixed_f32(self, b32, z32):
         """getMultigridPreconditioner's mixed-precision branch (SolveFuncs.jl:52-58): Float32 block, Float64 hierarchy."""
@@ -501,56 +492,38 @@ class DeviceHierarchy:
 
     def pcg_dev(self, b, x, tol: float, maxIter: int):
         _sync_torch(b, x)
-        iters, flag = C.c_longlong(0), C.c_longlong(0)
-        resvec = np.zeros(max(int(maxIter), 1))
-        _check(self.lib, self.lib.mg_pcg_dev_FP64(self.handle, _ptr(b), _ptr(x), self.n, float(tol), int(maxIter),
-                                                  C.byref(iters), C.byref(flag), _f64(resvec)), "mg_pcg_dev")
-        return int(flag.value), int(iters.value), resvec[: iters.value]
+        return self._krylov("pcg_dev", np.zeros(max(int(maxIter), 1)), _ptr(b), _ptr(x), self.n, float(tol), int(maxIter),
+                            nres=False)
 
     # -- block Krylov drivers on device tensors (row-major [n][nrhs]); KrylovMethods.blockCG / blockBiCGSTB / blockFGMRES ----------
     def block_pcg_dev(self, b, x, tol: float, maxIter: int):
         """returns (flag, iterations, resmat[iterations][nrhs] of ||r_j|| / ||b_j||)"""
         _sync_torch(b, x)
-        iters, flag = C.c_longlong(0), C.c_longlong(0)
-        resmat = np.zeros((max(int(maxIter), 1), self.nrhs))
-        _check(self.lib, self.lib.mg_block_pcg_dev_FP64(self.handle, _ptr(b), _ptr(x), self.n, self.nrhs, float(tol), int(maxIter),
-                                                        C.byref(iters), C.byref(flag), _f64(resmat)), "mg_block_pcg_dev")
-        return int(flag.value), int(iters.value), resmat[: iters.value]
+        return self._krylov("block_pcg_dev", np.zeros((max(int(maxIter), 1), self.nrhs)), _ptr(b), _ptr(x), self.n, self.nrhs,
+                            float(tol), int(maxIter), nres=False)
 
     def block_bicgstab_dev(self, b, x, tol: float, maxIter: int):
         _sync_torch(b, x)
-        iters, flag, nres = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        resvec = np.zeros(2 * max(int(maxIter), 1) + 1)
-        _check(self.lib, self.lib.mg_block_bicgstab_dev_FP64(self.handle, _ptr(b), _ptr(x), self.n, self.nrhs, float(tol), int(maxIter),
-                                                             C.byref(iters), C.byref(flag), _f64(resvec), C.byref(nres)), "mg_block_bicgstab_dev")
-        return int(flag.value), int(iters.value), resvec[: nres.value]
+        return self._krylov("block_bicgstab_dev", np.zeros(2 * max(int(maxIter), 1) + 1), _ptr(b), _ptr(x), self.n, self.nrhs,
+                            float(tol), int(maxIter))
 
     def block_fgmres_dev(self, b, x, inner: int, tol: float, maxIter: int):
         _sync_torch(b, x)
-        iters, flag, nres = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        resvec = np.zeros(max(int(inner) * int(maxIter), 1))
-        _check(self.lib, self.lib.mg_block_fgmres_dev_FP64(self.handle, _ptr(b), _ptr(x), self.n, self.nrhs, int(inner), float(tol), int(maxIter),
-                                                           C.byref(iters), C.byref(flag), _f64(resvec), C.byref(nres)), "mg_block_fgmres_dev")
-        return int(flag.value), int(iters.value), resvec[: nres.value]
+        return self._krylov("block_fgmres_dev", np.zeros(max(int(inner) * int(maxIter), 1)), _ptr(b), _ptr(x), self.n, self.nrhs,
+                            int(inner), float(tol), int(maxIter))
 
     def bicgstab_dev(self, b, x, tol: float, maxIter: int):
         """solveBiCGSTAB_MG on device tensors (one right-hand side); returns (flag, iterations, resvec: the entry at the start, then
         two per iteration)."""
         _sync_torch(b, x)
-        iters, flag, nres = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        resvec = np.zeros(2 * max(int(maxIter), 1) + 1)
-        _check(self.lib, self.lib.mg_bicgstab_dev_FP64(self.handle, _ptr(b), _ptr(x), self.n, float(tol), int(maxIter),
-                                                       C.byref(iters), C.byref(flag), _f64(resvec), C.byref(nres)), "mg_bicgstab_dev")
-        return int(flag.value), int(iters.value), resvec[: nres.value]
+        return self._krylov("bicgstab_dev", np.zeros(2 * max(int(maxIter), 1) + 1), _ptr(b), _ptr(x), self.n, float(tol),
+                            int(maxIter))
 
     def fgmres_dev(self, b, x, inner: int, tol: float, maxIter: int):
         """solveGMRES_MG on device tensors (one right-hand side); returns (flag, inner steps, resvec)."""
         _sync_torch(b, x)
-        iters, flag, nres = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        resvec = np.zeros(max(int(inner) * int(maxIter), 1))
-        _check(self.lib, self.lib.mg_fgmres_dev_FP64(self.handle, _ptr(b), _ptr(x), self.n, int(inner), float(tol), int(maxIter),
-                                                     C.byref(iters), C.byref(flag), _f64(resvec), C.byref(nres)), "mg_fgmres_dev")
-        return int(flag.value), int(iters.value), resvec[: nres.value]
+        return self._krylov("fgmres_dev", np.zeros(max(int(inner) * int(maxIter), 1)), _ptr(b), _ptr(x), self.n, int(inner),
+                            float(tol), int(maxIter))
 
     def spmv(self, level: int, which: int, alpha: float, x, beta: float, y):
         x = self._host_block(x)
