@@ -1,0 +1,91 @@
+"""The row-by-row checker of tests/test_default_paths.py on the host: scipy's fp64 products pass its componentwise bounds,
+a 1e-12 relative error in one small-magnitude row fails them (while a 1e-13 max-norm check on the whole vector passes it),
+and a NaN in an output or a changed guard word fails."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import default_paths_check as C
+
+
+def _operator(mg):
+    A, _ = mg.poisson_shifted([20, 17, 9])
+    A = A.tolil()
+    A[5, :] = 0.0          # (an empty row: the reference must give 0 there)
+    A = A.tocsr()
+    A.eliminate_zeros()
+    A.sort_indices()
+    assert np.diff(A.indptr)[5] == 0
+    return A
+
+
+def _inputs(A, seed=3):
+    rng = np.random.default_rng(seed)
+    n = A.shape[0]
+    x = rng.standard_normal(n) * np.exp2(rng.integers(-8, 9, n))
+    b = rng.standard_normal(n) * np.exp2(rng.integers(-8, 9, n))
+    d = 0.8 / np.where(A.diagonal() != 0, A.diagonal(), 1.0)
+    return x, b, d
+
+
+def test_fp64_products_pass(mg, monkeypatch):
+    A = _operator(mg)
+    monkeypatch.setattr(C, "CHUNK", 1000)        # (several pieces, several threads)
+    x, b, d = _inputs(A)
+    pr = C.Product(A, x)
+    assert pr.ax[5] == 0 and pr.abs[5] == 0
+    C.check_residual("residual", b - A @ x, b, pr)
+    C.check_sweep("sweep", x + d * (b - A @ x), x, d, b, pr)
+    C.check_spmv("spmv", -(A @ x) + b, -1.0, pr, 1.0, b)
+    C.check_spmv("spmv", 0.5 * (A @ x) - 2.0 * b, 0.5, pr, -2.0, b)
+    C.check_spmv("spmv beta 0", A @ x, 1.0, pr)
+    P = sp.random(A.shape[0], 300, density=0.01, random_state=4, format="csr")
+    xc = np.random.default_rng(5).standard_normal(300)
+    C.check_spmv("transfer", P @ xc, 1.0, C.Product(P, xc))
+    r = b - A @ x
+    t = x + d * r
+    C.check_xpdr("xpdr", t + d * r, t, d, r)
+    assert abs(C.norm_ld(r) - np.linalg.norm(r)) <= 1e-14 * np.linalg.norm(r)
+
+
+def test_small_row_error_fails_where_the_max_norm_check_passes(mg):
+    A = _operator(mg)
+    x, b, _ = _inputs(A)
+    pr = C.Product(A, x)
+    want = b - A @ x
+    # a row of small magnitude against the vector's largest, without much cancellation inside the row
+    scale = np.abs(b) + abs(A) @ np.abs(x)
+    row = int(np.argmin(np.where(np.abs(want) >= 0.25 * scale, np.abs(want), np.inf)))
+    assert np.abs(want[row]) <= 1e-3 * np.abs(want).max()
+    got = want.copy()
+    got[row] *= 1.0 + 1e-12
+    assert got[row] != want[row]
+    assert np.abs(got - want).max() <= 1e-13 * np.abs(want).max()     # the vector-wide check of the older tests lets it pass
+    with pytest.raises(AssertionError, match=f"first row {row}:"):
+        C.check_residual("residual", got, b, pr)
+
+
+def test_nan_or_changed_guard_fails(mg):
+    A = _operator(mg)
+    x, b, _ = _inputs(A)
+    pr = C.Product(A, x)
+    got = b - A @ x
+    got[17] = np.nan
+    with pytest.raises(AssertionError, match="first row 17:"):
+        C.check_residual("residual", got, b, pr)
+    n = 100
+    base = np.full(n + 2 * C.GUARD, np.nan)
+    base.view(np.int64)[: C.GUARD] = C.SENTINEL
+    base.view(np.int64)[-C.GUARD:] = C.SENTINEL
+    assert C.host_checked(base.copy()).shape == (n,)
+    for pos in (C.GUARD - 1, C.GUARD + n):                             # the word just before / just after the view
+        bad = base.copy()
+        bad[pos] = 0.0
+        with pytest.raises(AssertionError, match="guard"):
+            C.host_checked(bad)
+    inp = np.full(n + 2 * C.GUARD, np.nan)
+    inp[C.GUARD:C.GUARD + n] = 1.0
+    assert C.host_checked(inp.copy(), out=False).shape == (n,)
+    inp[C.GUARD + n] = 1.0
+    with pytest.raises(AssertionError, match="guard"):
+        C.host_checked(inp, out=False)
