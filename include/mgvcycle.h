@@ -165,7 +165,7 @@ int mg_solve_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long
 
 /* solveCG_MG (SolveFuncs.jl:104-116): KrylovMethods.cg (v0.6.0, external) preconditioned with one cycle
  * from x = 0 (getMultigridPreconditioner, SolveFuncs.jl:59), vectors resident on device across iterations.
- * nrhs = 1 (blockCG is not on the device path).  resvec (length maxIter) receives ||r||/||b|| per iteration;
+ * nrhs = 1 (a block of right-hand sides: mg_block_pcg_FP64 / mg_block_pcg_dev_FP64 below).  resvec (length maxIter) receives ||r||/||b|| per iteration;
  * flag: 0 converged, -1 maxIter reached, -2 breakdown (alpha = Inf or < 0), -9 b = 0. */
 int mg_pcg_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol,
                 long long maxIter, long long* iters, long long* flag, double* resvec);
@@ -174,7 +174,7 @@ int mg_pcg_dev_FP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long lo
 
 /* solveBiCGSTAB_MG (SolveFuncs.jl:87-101): KrylovMethods.bicgstb (external) with M1 = one cycle from x = 0,
  * M2 = identity.  resvec (length 2*maxIter+1) receives ||r0||/||b|| and two entries per iteration; *nres their
- * number.  flag: 0 converged, -1 maxIter, -2 breakdown, -3 converged on the half step, -9 b = 0.  nrhs = 1. */
+ * number.  flag: 0 converged, -1 maxIter, -2 breakdown, -3 converged on the half step, -9 b = 0.  nrhs = 1 (blocks: mg_block_bicgstab_*). */
 int mg_bicgstab_FP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol,
                      long long maxIter, long long* iters, long long* flag, double* resvec,
                      long long* nres);
@@ -184,7 +184,7 @@ int mg_bicgstab_dev_FP64(mg_hierarchy* h, const double* b_dev, double* x_dev, lo
 
 /* solveGMRES_MG (SolveFuncs.jl:119-133): KrylovMethods.fgmres (external), flexible restarted GMRES(inner) with one
  * cycle from x = 0 as preconditioner.  maxIter counts restarts; resvec (length inner*maxIter) receives the residual
- * estimate after every inner step, *nres their number, *iters the total number of inner steps.  nrhs = 1. */
+ * estimate after every inner step, *nres their number, *iters the total number of inner steps.  nrhs = 1 (blocks: mg_block_fgmres_*). */
 int mg_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol,
                    long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
 /* the same with b and x in HBM (device pointers), like mg_pcg_dev_FP64 / mg_bicgstab_dev_FP64 */
@@ -370,6 +370,11 @@ int mg_sweep_residual_form(mg_hierarchy* h, long long level, long long* form, lo
  * entries of a row from the upper ones of its neighbours; info[3] = value planes streamed from HBM per pass (7, or 4).
  * info[0] = 2: the level holds the band-27 form (27 planar arrays, kernel_variant 9); info[2] / info[3] likewise (27, or 14). */
 int mg_band_form(mg_hierarchy* h, long long level, long long* info);
+/* The kernel that serves an operator without row classes or grid records (kernel_variant -1), for the handle's nrhs.  info[0]:
+ * 0 none of these, 1 csr_pattern_spmv, 2 csr_stream_spmv, 3 csr_longrow_spmv, 4 csr_stream_spmm (nrhs > 1), 5 csr_rowclass_lane_spmm,
+ * 6 csr_rowclass_lane_spmm2; info[1]: non-temporal matrix loads (1-4), rows per lane (6); info[2]: 16-bit column offsets (3);
+ * info[3]: entries of the longest row.  Read-only. */
+int mg_operator_stream_kernel(mg_hierarchy* h, long long level, long long which, long long* info);
 /* kernel variant serving the operator at nrhs == 1 (as mg_operator_rowclass_flags) and its exception rows */
 int mg_op_kernel_variant(mg_operator* op, long long* variant, long long* exception_rows);
 int mg_op_destroy(mg_operator* op);

@@ -1315,6 +1315,36 @@ int mg_operator_rowclass_flags(mg_hierarchy* h, long long level, long long which
   return MG_OK;
 }
 
+// Which kernel serves an operator that is NOT stored as row classes / grid records (kernel_variant -1 above), as launch_csr picks it
+// for the handle's nrhs.  info[0]: 0 none of these (a row-class or grid kernel serves it), 1 csr_pattern_spmv, 2 csr_stream_spmv,
+// 3 csr_longrow_spmv, 4 csr_stream_spmm; 5 csr_rowclass_lane_spmm, 6 csr_rowclass_lane_spmm2 (nrhs > 1, row classes).  info[1]: the
+// NT template argument (non-temporal loads of the matrix stream) of 1-4, rows per lane (2 or 3) of 6.  info[2]: 16-bit column
+// offsets (kernel 3).  info[3]: longest row.  Read-only.  It MIRRORS launch_csr's choice from the operator's flags, it does not record a
+// launch: the answer holds for the calls the cycle and mg_spmv_dev / mg_fused_dev make - the whole product (phase 0), y != x, no ||out||^2
+// partials, and for kernel 6 vectors at 16-byte aligned addresses (otherwise launch_csr takes csr_stream_spmm).  A wide operator (64-bit row
+// pointers) serves one right-hand side only: 0 for nrhs > 1.
+int mg_operator_stream_kernel(mg_hierarchy* h, long long level, long long which, long long* info) {
+  MG_REAL_ONLY(h);
+  if (!info) return fail(MG_ERR_INVALID, "null argument");
+  Csr* M;
+  MG_TRY(find_op(h, level, which, &M));
+  long long variant = 0;
+  MG_TRY(mg_operator_rowclass_flags(h, level, which, nullptr, nullptr, &variant, nullptr));
+  info[0] = info[1] = info[2] = 0;
+  info[3] = M->max_row_nnz;
+  if (h->nrhs > 1 && M->wide) return MG_OK;
+  if (h->nrhs > 1) {
+    const bool lane = M->rc_lane_mm() && M->ln_blocks > 0 && M->ln_rows == lane_mm_rpl(*M, h->nrhs) * (mgk::BLK / lane_mm_group(*M, h->nrhs));
+    info[0] = lane ? (lane_mm_pairs(*M, h->nrhs) ? 6 : 5) : 4;
+    info[1] = lane ? (lane_mm_pairs(*M, h->nrhs) ? lane_mm_rpl(*M, h->nrhs) : 2) : (M->nt ? 1 : 0);
+  } else if (M->wide || variant == -1) {
+    info[0] = M->longrow() ? 3 : (!M->wide && M->has_pat) ? 1 : 2;
+    info[1] = M->nt ? 1 : 0;
+    info[2] = (info[0] == 3 && !M->wide && M->has_ci16) ? 1 : 0;
+  }
+  return MG_OK;
+}
+
 // Which kernel fuses a sweep with the residual that follows it on this level's A (one right-hand side): *form = 0 none
 // (two launches), 2 csr_rowclass_march2_spmv (1-D chunks), 3 csr_rowclass_march3_spmv (2-D in-plane tiles).  geometry
 // (optional, 12 entries, form 3): tiles per line, tiles per column, TX, TY, rows of the stage-1 region per lane (K1),

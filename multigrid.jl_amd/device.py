@@ -49,6 +49,7 @@ SIGNATURES = {
     "mg_finalize": (C.c_int, [_vp]),
     "mg_set_nrhs": (C.c_int, [_vp, _ll]),
     "mg_band_form": (C.c_int, [_vp, _ll, C.POINTER(C.c_longlong)]),
+    "mg_operator_stream_kernel": (C.c_int, [_vp, _ll, _ll, C.POINTER(C.c_longlong)]),
     "mg_replace_values_FP64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
     "mg_rap_FP64": (C.c_int, [_vp, _dp, _ll, _ll, _dp, _lp]),
     "mg_get_values_FP64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
@@ -681,6 +682,13 @@ class DeviceHierarchy:
         """[held, canonical slots, symmetric reads, value planes streamed per pass] of the level's band form (mg_band_form)."""
         g = (C.c_longlong * 4)()
         _check(self.lib, self.lib.mg_band_form(self.handle, level, g), "mg_band_form")
+        return [int(v) for v in g]
+
+    def operator_stream_kernel(self, level: int, which: int):
+        """[kernel, NT / rows per lane, 16-bit column offsets, longest row] (mg_operator_stream_kernel): 0 a row-class or grid kernel,
+        1 csr_pattern_spmv, 2 csr_stream_spmv, 3 csr_longrow_spmv, 4 csr_stream_spmm, 5 csr_rowclass_lane_spmm, 6 csr_rowclass_lane_spmm2."""
+        g = (C.c_longlong * 4)()
+        _check(self.lib, self.lib.mg_operator_stream_kernel(self.handle, level, which, g), "mg_operator_stream_kernel")
         return [int(v) for v in g]
 
     def operator_kernel_variant(self, level: int, which: int) -> int:

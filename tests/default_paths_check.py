@@ -33,14 +33,16 @@ def _threads():
     return max(1, min(16, n))
 
 
-def _chunked(n, fn):
-    """fn(r0, r1) over pieces of at most CHUNK rows (cache-sized), in contiguous blocks, one per thread (numpy releases the
-    GIL in these loops); the results in row order."""
-    nt = _threads() if n > 4 * CHUNK else 1
+def _chunked(n, fn, chunk=None, work=None):
+    """fn(r0, r1) over pieces of at most `chunk` rows (default CHUNK: cache-sized), in contiguous blocks, one per thread (numpy
+    releases the GIL in these loops); the results in row order.  work: what decides whether threads pay (default: the rows)."""
+    chunk = CHUNK if chunk is None else max(1, int(chunk))
+    nt = _threads() if (n if work is None else work) > 4 * CHUNK else 1
+    nt = max(1, min(nt, -(-n // chunk)))
     step = -(-n // nt)
 
     def block(b0):
-        return [fn(r0, min(n, b0 + step, r0 + CHUNK)) for r0 in range(b0, min(n, b0 + step), CHUNK)]
+        return [fn(r0, min(n, b0 + step, r0 + chunk)) for r0 in range(b0, min(n, b0 + step), chunk)]
 
     if nt == 1:
         return block(0)
@@ -77,7 +79,9 @@ class Product:
                 self.ax[r0:r1][nz] = np.add.reduceat(prod, starts[nz])
                 self.abs[r0:r1][nz] = np.add.reduceat(aprod, starts[nz])
 
-        _chunked(n, piece)
+        # pieces of about 8 CHUNK entries (rows are never split: a row's sum does not depend on the pieces), threads by entries - an
+        # SA-AMG level of 40 000 rows holds 10^8 of them
+        _chunked(n, piece, chunk=CHUNK if A.nnz <= 8 * n else max(16, 8 * CHUNK * n // A.nnz), work=max(n, A.nnz // 8))
 
 
 def _check(name, got, ref_bound):
@@ -139,6 +143,41 @@ def check_xpdr(name, got, t, d, r):
                                              gamma(2) * (np.abs(t[r0:r1]) + np.abs(d[r0:r1] * r[r0:r1]))))
 
 
+def check_block(name, kind, got, A, X, cols=None, B=None, d=None, alpha=1.0, beta=0.0, Y0=None, prods=None):
+    """A block of right-hand sides, column by column: got, X, B, Y0 are (rows, nrhs) arrays (any strides), kind is
+    "residual" (B - A X), "sweep" (X + d.*(B - A X)) or "spmv" (alpha A X + beta Y0).  Every column of `cols` (default: all)
+    is checked against Product(A, X[:, j]) with the single-vector bounds.  A column of X that is exactly zero must give
+    exactly B (residual) or exactly beta * Y0 (spmv; 0 for beta = 0, where Y0 may be NaN): compared by value, so a NaN fails and
+    -0.0 equals 0.0.  prods: a dict that keeps the Product of a column from one call to the next (same A and X)."""
+    got, X = np.asarray(got, dtype=np.float64), np.asarray(X, dtype=np.float64)
+    assert got.ndim == 2 and X.ndim == 2 and got.shape == (A.shape[0], X.shape[1]) and X.shape[0] == A.shape[1], (got.shape, X.shape, A.shape)
+    rows = 0
+    for j in (range(X.shape[1]) if cols is None else cols):
+        x, g = np.ascontiguousarray(X[:, j]), np.ascontiguousarray(got[:, j])
+        col = lambda M: None if M is None else np.ascontiguousarray(M[:, j])
+        if kind != "sweep" and not x.any():
+            want = col(B) if kind == "residual" else (np.zeros_like(g) if beta == 0.0 else beta * col(Y0))
+            same = g == want
+            if not same.all():
+                i = int(np.flatnonzero(~same)[0])
+                raise AssertionError(f"{name} column {j} (x = 0): row {i} is {g[i]!r}, not exactly {want[i]!r}")
+            rows += g.shape[0]
+            continue
+        pr = prods.get(j) if prods is not None else None
+        if pr is None:
+            pr = Product(A, x)
+            if prods is not None:
+                prods[j] = pr
+        if kind == "residual":
+            rows += check_residual(f"{name} column {j}", g, col(B), pr)
+        elif kind == "sweep":
+            rows += check_sweep(f"{name} column {j}", g, x, d, col(B), pr)
+        else:
+            assert kind == "spmv", kind
+            rows += check_spmv(f"{name} column {j}", g, alpha, pr, beta, col(Y0))
+    return rows
+
+
 def norm_ld(v):
     """sqrt(sum v^2) in long double."""
     v = np.asarray(v, dtype=np.float64)
@@ -165,6 +204,20 @@ class Guarded:
             self.v = self.base[GUARD:GUARD + self.n]
             self.v.copy_(torch.from_numpy(np.ascontiguousarray(data, dtype=np.float64)))
         assert self.v.data_ptr() % 16 == 0
+
+    @classmethod
+    def block(cls, n, nrhs, data=None, out=True):
+        """A block of nrhs columns as the device-resident entry points take it: one buffer of n * nrhs doubles between the
+        guard zones, entry (i, j) at i * nrhs + j (the host-pointer entry points transpose a column-major n x nrhs host block
+        into this).  data: an (n, nrhs) array.  host2d() returns the checked view as an (n, nrhs) array."""
+        if data is not None:
+            data = np.ascontiguousarray(np.asarray(data, dtype=np.float64).reshape(int(n), int(nrhs)))   # C order: i * nrhs + j
+        g = cls(int(n) * int(nrhs), None if data is None else data.ravel(), out)
+        g.shape = (int(n), int(nrhs))
+        return g
+
+    def host2d(self):
+        return self.host().reshape(self.shape)
 
     def host_guards(self):
         """Check the guard zones alone (no copy of the view)."""

@@ -89,3 +89,46 @@ def test_nan_or_changed_guard_fails(mg):
     inp[C.GUARD + n] = 1.0
     with pytest.raises(AssertionError, match="guard"):
         C.host_checked(inp, out=False)
+
+
+def test_block_checker_on_a_10k_row_matrix(monkeypatch):
+    """check_block against scipy's fp64 block product on 10^4 rows: passes; a value written to the neighbouring column, a
+    NaN in the zero column and a -1e-300 there fail; the long-double product agrees with scipy's to fp64 rounding."""
+    monkeypatch.setattr(C, "CHUNK", 1500)
+    rng = np.random.default_rng(8)
+    n, nrhs = 10_000, 5
+    A = (sp.random(n, n, density=8.0 / n, random_state=9, format="csr") + sp.identity(n, format="csr") * 4.0).tocsr()
+    A.sort_indices()
+    X = rng.standard_normal((n, nrhs)) * np.exp2(3.0 * np.arange(nrhs) - 20.0)      # (column j scaled by 2^(3j - 20))
+    X[:, 3] = 0.0
+    B, Y0 = rng.standard_normal((n, nrhs)), rng.standard_normal((n, nrhs))
+    d = 0.8 / A.diagonal()
+    AX = A @ X
+    pr = C.Product(A, X[:, 1])
+    assert np.abs(pr.ax.astype(np.float64) - AX[:, 1]).max() <= 1e-14 * np.abs(pr.abs).max()
+    assert C.check_block("residual", "residual", B - AX, A, X, B=B) == n * nrhs
+    C.check_block("sweep", "sweep", X + d[:, None] * (B - AX), A, X, B=B, d=d)
+    C.check_block("spmv", "spmv", 0.5 * AX - 2.0 * Y0, A, X, alpha=0.5, beta=-2.0, Y0=Y0)
+    C.check_block("spmv beta 0", "spmv", AX, A, X, cols=(0, 3, 4))
+    swapped = (B - AX).copy()
+    swapped[77, 1], swapped[77, 2] = swapped[77, 2], swapped[77, 1]
+    with pytest.raises(AssertionError, match="column 1: 1 of 10000 rows .* first row 77:"):
+        C.check_block("residual", "residual", swapped, A, X, B=B)
+    C.check_block("residual", "residual", swapped, A, X, cols=(0, 3, 4), B=B)        # (only the named columns are looked at)
+    for bad in (np.nan, -1e-300):
+        got = AX.copy()
+        got[5, 3] = bad
+        with pytest.raises(AssertionError, match=r"column 3 \(x = 0\): row 5 "):
+            C.check_block("spmv", "spmv", got, A, X)
+    got = AX.copy()
+    got[5, 3] = -0.0
+    C.check_block("spmv", "spmv", got, A, X)
+
+
+def test_guarded_block_layout_on_the_host():
+    """Guarded.block stores entry (i, j) at i * nrhs + j: checked through the host-side reshape it uses (no device here)."""
+    data = np.arange(12.0).reshape(4, 3)
+    flat = np.ascontiguousarray(data).ravel()
+    assert flat[2 * 3 + 1] == data[2, 1]
+    base = np.concatenate([np.full(C.GUARD, np.nan), flat, np.full(C.GUARD, np.nan)])
+    assert np.array_equal(C.host_checked(base, out=False).reshape(4, 3), data)
