@@ -530,6 +530,52 @@ int mg_dist_finalize(mg_dist* h);
 int mg_dist_cycle_dev_FP64(mg_dist* h, const double* b_loc, double* x_loc, long long n_own, long long x_is_zero);
 int mg_dist_solve_dev_FP64(mg_dist* h, const double* b_loc, double* x_loc, long long n_own, double tol, long long maxIter,
                            long long* iters, double* resvec);
+/* MG-preconditioned Krylov drivers on the halo form (solveCG_MG / solveBiCGSTAB_MG / solveGMRES_MG, SolveFuncs.jl:74-133;
+ * the way an SA-AMG hierarchy is used: SAAMGWrapper.jl:61-73): b_loc / x_loc as for the cycle (x in and out), every other
+ * argument, the flags and the layout of resvec as for mg_pcg_dev_FP64 / mg_bicgstab_dev_FP64 / mg_fgmres_dev_FP64.  One
+ * right-hand side (MG_ERR_UNSUPPORTED otherwise); inner in [1,64].  A product with A = one exchange of level 1's halo, the
+ * preconditioner = the sharded cycle from x = 0, every scalar = a sum over the owned rows + an all-reduce (RCCL or the
+ * plug-in's op 1), the scalars due at the same point of an iteration in ONE all-reduce: outside the cycle 2 per PCG
+ * iteration, 3 per BiCGSTAB iteration, 2 per FGMRES inner step (inner <= 8; 1 + ceil(i/8) for the i-th step).  Every rank
+ * returns the same flag, count and resvec.  PCG's stopping test uses ||r||^2 = r'r - 2 alpha r'q + alpha^2 q'q from all-reduced
+ * scalars (resvec's entries are replaced by the summed norm one all-reduce later); BiCGSTAB's half-step exit (flag -3) is
+ * taken behind the second cycle; FGMRES takes the Gram-Schmidt dots of one step together.  The work space is allocated at the
+ * first call and released by mg_dist_destroy. */
+int mg_dist_pcg_dev_FP64(mg_dist* h, const double* b_loc, double* x_loc, long long n_own, double tol, long long maxIter,
+                         long long* iters, long long* flag, double* resvec);
+int mg_dist_bicgstab_dev_FP64(mg_dist* h, const double* b_loc, double* x_loc, long long n_own, double tol, long long maxIter,
+                              long long* iters, long long* flag, double* resvec, long long* nres);
+int mg_dist_fgmres_dev_FP64(mg_dist* h, const double* b_loc, double* x_loc, long long n_own, long long inner, double tol,
+                            long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
+/* Halo exchanges started and all-reduces entered by this rank since mg_dist_create (cycle, solve and the drivers above). */
+int mg_dist_stats(mg_dist* h, long long* exchanges, long long* allreduces);
+/* The fused vector passes of those drivers on their own: one pass over the vectors does the update and leaves the sums due
+ * at that point in out_dev (device), asynchronously on `stream`.  16-byte accesses where all vectors of a pass share their
+ * alignment modulo 16 bytes, deterministic two-pass sums (no atomics).  workspace_dev: 8192 doubles.  xs_dev / ys_dev /
+ * vs_dev and h_host are HOST arrays (of device pointers / coefficients).
+ *   dots: out[c] = xs[c]'ys[c], c < k <= 8          pcg_dots: out = (p'q, r'q, q'q)
+ *   pcg_update: x += alpha p, r -= alpha q, out = r'r   xpby: y = x + beta y         scale: y = a x
+ *   bicg_p: p = r + beta (p - omega v)              bicg_s: r -= alpha v, out = r'r   bicg_ts: out = (t's, t't)
+ *   bicg_xr: x += alpha phat + omega shat, r -= omega t, out = (r'r, rtld'r)
+ *   gs_update: w -= sum_{j<m} h[j] vs[j] (m <= 64, 8 per pass), out (optional) = w'w */
+int mg_vec_dots_dev_FP64(long long k, const double* const* xs_dev, const double* const* ys_dev, long long n,
+                         double* workspace_dev, double* out_dev, void* stream);
+int mg_vec_pcg_dots_dev_FP64(const double* p, const double* q, const double* r, long long n, double* workspace_dev,
+                             double* out_dev, void* stream);
+int mg_vec_pcg_update_dev_FP64(double alpha, const double* p, const double* q, double* x, double* r, long long n,
+                               double* workspace_dev, double* out_dev, void* stream);
+int mg_vec_xpby_dev_FP64(const double* x, double beta, double* y, long long n, void* stream);
+int mg_vec_scale_dev_FP64(double a, const double* x, double* y, long long n, void* stream);
+int mg_vec_bicg_p_dev_FP64(double beta, double omega, const double* r, const double* v, double* p, long long n, void* stream);
+int mg_vec_bicg_s_dev_FP64(double alpha, const double* v, double* r, long long n, double* workspace_dev, double* out_dev,
+                           void* stream);
+int mg_vec_bicg_ts_dev_FP64(const double* t, const double* s, long long n, double* workspace_dev, double* out_dev,
+                            void* stream);
+int mg_vec_bicg_xr_dev_FP64(double alpha, double omega, const double* phat, const double* shat, const double* t,
+                            const double* rtld, double* x, double* r, long long n, double* workspace_dev, double* out_dev,
+                            void* stream);
+int mg_vec_gs_update_dev_FP64(long long m, const double* h_host, const double* const* vs_dev, double* w, long long n,
+                              double* workspace_dev, double* out_dev, void* stream);
 /* Number of ranks of the handle's RCCL communicator as the library itself reports it (ncclCommCount); 0 for the
  * host-staged plug-in transport. */
 int mg_dist_comm_count(mg_dist* h, long long* count);

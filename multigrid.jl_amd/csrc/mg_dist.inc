@@ -32,6 +32,20 @@ struct DistLevel {
   DevBuf<double> x0, x1, r, b;
   DevBuf<double> x2;   // fine level, solve loop: third rotating buffer of the fused last sweep + residual (allocated on first use)
 };
+// Work space of the sharded Krylov drivers (mg_dist_krylov.inc), allocated at their first call and kept on the handle
+struct DistKrylov {
+  DevBuf<double> vec;      // the drivers' vectors, carved out of one allocation
+  DevBuf<double> part;     // partial sums of the fused passes: MAXS scalars x MAXB workgroups
+  DevBuf<double> scal;     // MAXS scalars, all-reduced in place
+  double* h_scal = nullptr;   // pinned: [0, MAXS) the scalars read back, [MAXS, 2 MAXS) the plug-in's result
+  void release() {
+    vec.release();
+    part.release();
+    scal.release();
+    if (h_scal) (void)hipHostFree(h_scal);
+    h_scal = nullptr;
+  }
+};
 }  // namespace
 
 // rows of a row-major block [n][k]: dst row i = src row idx[i]
@@ -78,6 +92,8 @@ struct mg_dist {
   double* h_scalar = nullptr;
   double* h_stage = nullptr;            // pinned staging for the plug-in collectives
   size_t h_stage_n = 0;
+  DistKrylov kry;
+  long long n_exchanges = 0, n_allreduce = 0;   // collectives this rank entered (mg_dist_stats)
 };
 
 namespace {
@@ -97,6 +113,7 @@ int dist_exchange_start(mg_dist* h, DistPlan& p, double* buf) {
   if (p.n_send > 0)
     hipLaunchKernelGGL(dist_pack, dim3((unsigned)((p.n_send * k + 255) / 256)), dim3(256), 0, h->stream, buf, p.send_idx.p, p.send_buf.p, p.n_send, (int)k);
   HIP_TRY(hipGetLastError());
+  ++h->n_exchanges;
   double* recv = buf + p.n_own_src * k;
   if (h->comm) {
     HIP_TRY(hipEventRecord(h->ev_packed, h->stream));
@@ -160,6 +177,7 @@ int dist_norm(mg_dist* h, const double* v, long long n, double* out) {
 
 // all-reduce h->scalar (a local sum of squares) and return its square root on the host
 int dist_reduce_scalar(mg_dist* h, double* out) {
+  if (h->comm || h->world > 1) ++h->n_allreduce;
   if (h->comm) {
     NCCL_TRY(g_rccl.AllReduce(h->scalar.p, h->scalar.p, 1, NCCL_DOUBLE, NCCL_SUM, h->comm, h->stream));
     HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -840,6 +858,7 @@ int mg_dist_destroy(mg_dist* h) {
   h->partial.release();
   h->partial2.release();
   h->scalar.release();
+  h->kry.release();
   if (h->h_scalar) (void)hipHostFree(h->h_scalar);
   if (h->h_stage) (void)hipHostFree(h->h_stage);
   if (h->ev_packed) (void)hipEventDestroy(h->ev_packed);

@@ -33,6 +33,7 @@
 #include "mg_marchr.hpp"
 #include "mg_small.hpp"
 #include "mg_complex.hpp"
+#include "mg_krvec.hpp"
 
 
 // One translation unit, nine parts (round 4: the 6 800-line file split by responsibility; the order is the dependency order):
@@ -45,3 +46,4 @@
 #include "mg_complex.inc"    // ComplexF64 hierarchies: generic-CSR kernels' launchers, cycle, solve, and their extern "C" entry points
 #include "mg_cabi.inc"       // extern "C": the single-GPU API
 #include "mg_dist.inc"       // extern "C": the native multi-GPU sequencer
+#include "mg_dist_krylov.inc"   // extern "C": PCG / BiCGSTAB / FGMRES on the sharded halo form, their fused vector passes

@@ -140,6 +140,20 @@ SIGNATURES = {
     "mg_dist_set_nrhs": (C.c_int, [_vp, _ll]),
     "mg_dist_release_tail": (C.c_int, [_vp]),
     "mg_dist_comm_count": (C.c_int, [_vp, _lp]),
+    "mg_dist_pcg_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, C.c_double, _ll, _lp, _lp, _dp]),
+    "mg_dist_bicgstab_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_dist_fgmres_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_dist_stats": (C.c_int, [_vp, _lp, _lp]),
+    "mg_vec_dots_dev_FP64": (C.c_int, [_ll, C.POINTER(_vp), C.POINTER(_vp), _ll, _vp, _vp, _vp]),
+    "mg_vec_pcg_dots_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_vec_pcg_update_dev_FP64": (C.c_int, [C.c_double, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_vec_xpby_dev_FP64": (C.c_int, [_vp, C.c_double, _vp, _ll, _vp]),
+    "mg_vec_scale_dev_FP64": (C.c_int, [C.c_double, _vp, _vp, _ll, _vp]),
+    "mg_vec_bicg_p_dev_FP64": (C.c_int, [C.c_double, C.c_double, _vp, _vp, _vp, _ll, _vp]),
+    "mg_vec_bicg_s_dev_FP64": (C.c_int, [C.c_double, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_vec_bicg_ts_dev_FP64": (C.c_int, [_vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_vec_bicg_xr_dev_FP64": (C.c_int, [C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_vec_gs_update_dev_FP64": (C.c_int, [_ll, _dp, C.POINTER(_vp), _vp, _ll, _vp, _vp, _vp]),
     "mg_dist_destroy": (C.c_int, [_vp]),
     "mg_ghost_attach": (C.c_int, [_vp, _ll, _ll, _ll, C.c_char_p]),
     "mg_ghost_set_exchange_plugin": (C.c_int, [_vp, _vp, _vp]),
@@ -997,3 +1011,69 @@ def vec_sumsq(x, length, workspace, out, stream=0):
     lib = load_library()
     _check(lib, lib.mg_vec_sumsq_dev_FP64(_ptr(x), int(length), _ptr(workspace), _ptr(out), _vp(stream)),
            "mg_vec_sumsq_dev")
+
+
+# ---- the fused vector passes of the sharded Krylov drivers (csrc/mg_krvec.hpp): device tensors, asynchronous on `stream`;
+#      workspace: KRV_WORKSPACE doubles, out: the pass's sums (device) --------------------------------------------------------
+KRV_WORKSPACE = 8192
+
+
+def _ptr_array(tensors):
+    return (_vp * len(tensors))(*[_ptr(t) for t in tensors])
+
+
+def vec_dots(xs, ys, n, workspace, out, stream=0):
+    """out[c] = xs[c]'ys[c] over n elements, c < len(xs) <= 8, in one pass."""
+    lib = load_library()
+    _check(lib, lib.mg_vec_dots_dev_FP64(len(xs), _ptr_array(xs), _ptr_array(ys), int(n), _ptr(workspace), _ptr(out), _vp(stream)),
+           "mg_vec_dots_dev")
+
+
+def vec_pcg_dots(p, q, r, n, workspace, out, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_pcg_dots_dev_FP64(_ptr(p), _ptr(q), _ptr(r), int(n), _ptr(workspace), _ptr(out), _vp(stream)), "mg_vec_pcg_dots_dev")
+
+
+def vec_pcg_update(alpha, p, q, x, r, n, workspace, out, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_pcg_update_dev_FP64(float(alpha), _ptr(p), _ptr(q), _ptr(x), _ptr(r), int(n), _ptr(workspace), _ptr(out),
+                                               _vp(stream)), "mg_vec_pcg_update_dev")
+
+
+def vec_xpby(x, beta, y, n, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_xpby_dev_FP64(_ptr(x), float(beta), _ptr(y), int(n), _vp(stream)), "mg_vec_xpby_dev")
+
+
+def vec_scale(a, x, y, n, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_scale_dev_FP64(float(a), _ptr(x), _ptr(y), int(n), _vp(stream)), "mg_vec_scale_dev")
+
+
+def vec_bicg_p(beta, omega, r, v, p, n, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_bicg_p_dev_FP64(float(beta), float(omega), _ptr(r), _ptr(v), _ptr(p), int(n), _vp(stream)), "mg_vec_bicg_p_dev")
+
+
+def vec_bicg_s(alpha, v, r, n, workspace, out, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_bicg_s_dev_FP64(float(alpha), _ptr(v), _ptr(r), int(n), _ptr(workspace), _ptr(out), _vp(stream)), "mg_vec_bicg_s_dev")
+
+
+def vec_bicg_ts(t, s, n, workspace, out, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_bicg_ts_dev_FP64(_ptr(t), _ptr(s), int(n), _ptr(workspace), _ptr(out), _vp(stream)), "mg_vec_bicg_ts_dev")
+
+
+def vec_bicg_xr(alpha, omega, phat, shat, t, rtld, x, r, n, workspace, out, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_vec_bicg_xr_dev_FP64(float(alpha), float(omega), _ptr(phat), _ptr(shat), _ptr(t), _ptr(rtld), _ptr(x), _ptr(r), int(n),
+                                            _ptr(workspace), _ptr(out), _vp(stream)), "mg_vec_bicg_xr_dev")
+
+
+def vec_gs_update(h, vs, w, n, workspace, out=None, stream=0):
+    """w -= sum_j h[j] vs[j]; out (optional, device) = w'w."""
+    lib = load_library()
+    hh = np.ascontiguousarray(h, dtype=np.float64)
+    _check(lib, lib.mg_vec_gs_update_dev_FP64(len(vs), _f64(hh), _ptr_array(vs), _ptr(w), int(n), _ptr(workspace),
+                                              _ptr(out) if out is not None else None, _vp(stream)), "mg_vec_gs_update_dev")

@@ -415,6 +415,9 @@ class DistributedHierarchy:
                  tail_counts, rows_fine, cycleType: str, nl_total: int, nrhs: int = 1):
         self.comm = comm
         self.be = be = backend
+        self.n_exchanges = 0          # halo exchanges started / all-reduces entered by cycle, solve and the Krylov drivers (comm_stats)
+        self.n_allreduces = 0
+        self._kry = None
         self.nrhs = k = int(nrhs)
         self.cycleType = cycleType
         self.relaxType = getattr(tail_param, "relaxType", "Jac")
@@ -580,6 +583,7 @@ class DistributedHierarchy:
         (one all_to_all_single); returns a handle for ``comm.finish``."""
         if plan is None or not plan.active:
             return None
+        self.n_exchanges += 1
         ns = int(plan.send_idx.size)
         send = plan.send_buf[:ns]
         if ns:
@@ -611,6 +615,7 @@ class DistributedHierarchy:
         """Global Frobenius norm of a sharded vector (SolveFuncs.jl:15,20,30): local sum of squares + all-reduce."""
         s = self.be.sumsq(v, n_own * self.nrhs)
         self.comm.all_reduce_sum(s)
+        self.n_allreduces += 1
         return float(s.item()) ** 0.5
 
     # ---- the cycle (mirror of csrc/mgvcycle.hip cycle_level; MGcycle.jl:1-118) ---------------------------
@@ -698,6 +703,212 @@ class DistributedHierarchy:
         x_loc.copy_(cur[: L.n_own])
         return it, np.array(resvec)
 
+    # ---- MG-preconditioned Krylov on this rank's rows (solveCG_MG / solveBiCGSTAB_MG / solveGMRES_MG, SolveFuncs.jl:74-133) ------
+    #      The same schedules as the native drivers (csrc/mg_dist_krylov.inc, where they are derived): a product with A behind one
+    #      exchange of level 1's halo, the sharded cycle from x = 0 as preconditioner, the scalars due at the same point of an
+    #      iteration in one all-reduce.  b_loc / x_loc: n_own long, x_loc updated in place; returns (flag, iters, resvec).
+    def comm_stats(self):
+        """(halo exchanges started, all-reduces entered) by this rank since the hierarchy was built."""
+        return self.n_exchanges, self.n_allreduces
+
+    def _krylov(self, b_loc):
+        self._python_sequencer_supported()
+        if self.nrhs != 1:
+            raise NotImplementedError("the sharded Krylov drivers of the halo form take one right-hand side")
+        if self._kry is None:
+            self._kry = _KrylovOps(self)
+        return self._kry
+
+    def _prec(self, v):
+        """z = M(v): one cycle from x = 0; returns the level-1 buffer (cap_x long) that holds it."""
+        L = self.levels[0]
+        return self._cycle(0, v, L.x0, L.x1, True, self.cycleType)
+
+    def _residual(self, b_loc, x_loc, r):
+        L = self.levels[0]
+        L.x0[: L.n_own].copy_(x_loc)
+        self.apply_A(L, D.MG_K_RESIDUAL, L.x0, r, b_loc)
+
+    def pcg(self, b_loc, x_loc, tol: float, maxIter: int):
+        K = self._krylov(b_loc)
+        L = self.levels[0]
+        n = L.n_own
+        r, q, p = K.vec(n), K.vec(n), K.vec(L.cap_x)
+        resvec = np.zeros(max(int(maxIter), 1))
+        K.dots([(b_loc, b_loc)])
+        nr0 = K.reduce(1)[0] ** 0.5
+        if nr0 == 0.0:
+            x_loc.zero_()
+            return -9, 0, resvec[:0]
+        self._residual(b_loc, x_loc, r)
+        z = self._prec(r)
+        K.dots([(r, z), (r, r)])
+        gamma, rr = K.reduce(2)
+        p[:n].copy_(z[:n])
+        it, flag = 0, -1
+        for k in range(1, int(maxIter) + 1):
+            it = k
+            self.apply_A(L, D.MG_K_SPMV, p, q, None)
+            K.pcg_dots(p, q, r)
+            pq, rq, qq = K.reduce(3)
+            alpha = gamma / pq if pq != 0.0 else float("inf")
+            if np.isinf(alpha) or alpha < 0.0:
+                flag = -2
+                break
+            K.pcg_update(alpha, p, q, x_loc, r)          # this rank's ||r||^2 -> scalar 0
+            rr_new = rr - 2.0 * alpha * rq + alpha * alpha * qq
+            summed = False
+            if not rr_new > 1e-8 * rr:                  # cancellation: the summed norm itself
+                rr_new = K.reduce(1)[0]
+                summed = True
+            resvec[k - 1] = rr_new ** 0.5 / nr0 if rr_new >= 0.0 else float("nan")
+            if resvec[k - 1] <= tol:
+                flag = 0
+                break
+            z = self._prec(r)
+            if summed:
+                K.dots([(z, r)])
+                zr = K.reduce(1)[0]
+                rr = rr_new
+            else:
+                K.dots([(z, r)], slot=1)
+                rr, zr = K.reduce(2)
+                resvec[k - 1] = rr ** 0.5 / nr0
+            beta = zr / gamma
+            gamma = zr
+            K.xpby(z, beta, p)
+        self.be.synchronize()
+        return flag, it, resvec[:it]
+
+    def bicgstab(self, b_loc, x_loc, tol: float, maxIter: int):
+        K = self._krylov(b_loc)
+        L = self.levels[0]
+        n = L.n_own
+        r, p, v, rtld, t, phat = (K.vec(n) for _ in range(6))
+        K.dots([(b_loc, b_loc)])
+        bn = K.reduce(1)[0] ** 0.5
+        if bn == 0.0:
+            x_loc.zero_()
+            return -9, 0, np.zeros(0)
+        self._residual(b_loc, x_loc, r)
+        K.dots([(r, r)])
+        rho = K.reduce(1)[0]
+        resvec = [rho ** 0.5 / bn]
+        if resvec[0] < tol:
+            return 0, 0, np.array(resvec)
+        rtld.copy_(r)
+        omega, alpha, rho1 = 1.0, 0.0, 0.0
+        it, flag = 0, -1
+        for k in range(1, int(maxIter) + 1):
+            it = k
+            if rho == 0.0:
+                flag = -2
+                break
+            if k > 1:
+                K.bicg_p((rho / rho1) * (alpha / omega), omega, r, v, p)
+            else:
+                p.copy_(r)
+            z = self._prec(p)
+            self.apply_A(L, D.MG_K_SPMV, z, v, None)     # v = A phat, multiplied where the cycle left it
+            phat.copy_(z[:n])
+            K.dots([(rtld, v)])
+            alpha = rho / K.reduce(1)[0]
+            K.bicg_s(alpha, v, r)                        # s (in r); this rank's ||s||^2 -> scalar 0
+            z = self._prec(r)
+            self.apply_A(L, D.MG_K_SPMV, z, t, None)
+            K.bicg_ts(t, r)                              # -> scalars 1, 2
+            ss, ts, tt = K.reduce(3)
+            sn = ss ** 0.5 / bn
+            resvec.append(sn)
+            if sn < tol:
+                K.gs_update([-alpha], [phat], x_loc)
+                flag = -3
+                break
+            omega = ts / tt
+            K.bicg_xr(alpha, omega, phat, z, t, rtld, x_loc, r)
+            rr, rho_next = K.reduce(2)
+            err = rr ** 0.5 / bn
+            resvec.append(err)
+            if err <= tol:
+                flag = 0
+                break
+            if omega == 0.0:
+                flag = -2
+                break
+            rho1, rho = rho, rho_next
+        self.be.synchronize()
+        return flag, it, np.array(resvec)
+
+    def fgmres(self, b_loc, x_loc, inner: int, tol: float, maxIter: int):
+        K = self._krylov(b_loc)
+        L = self.levels[0]
+        n, m = L.n_own, int(inner)
+        if m < 1 or m > 64:
+            raise ValueError("inner must be in [1,64]")
+        V = [K.vec(n) for _ in range(m + 1)]
+        Z = [K.vec(n) for _ in range(m)]
+        r = K.vec(n)
+        K.dots([(b_loc, b_loc)])
+        bn = K.reduce(1)[0] ** 0.5
+        if bn == 0.0:
+            x_loc.zero_()
+            return -9, 0, np.zeros(0)
+        self._residual(b_loc, x_loc, r)
+        K.dots([(r, r)])
+        rn = K.reduce(1)[0] ** 0.5
+        if rn / bn < tol:
+            return 0, 0, np.zeros(0)
+        resvec, flag, total = [], -1, 0
+        for _ in range(1, int(maxIter) + 1):
+            H = np.zeros((m + 1, m))
+            cs, sn, g = np.zeros(m), np.zeros(m), np.zeros(m + 1)
+            K.scale(1.0 / rn, r, V[0])
+            g[0] = rn
+            used = 0
+            for i in range(m):
+                w = V[i + 1]
+                z = self._prec(V[i])
+                self.apply_A(L, D.MG_K_SPMV, z, w, None)
+                Z[i].copy_(z[:n])
+                for k0 in range(0, i + 1, 8):            # the Gram-Schmidt dots of this step together, 8 per all-reduce
+                    cnt = min(8, i + 1 - k0)
+                    K.dots([(w, V[k0 + c]) for c in range(cnt)])
+                    H[k0:k0 + cnt, i] = K.reduce(cnt)
+                K.gs_update(H[:i + 1, i], V[:i + 1], w, True)
+                H[i + 1, i] = K.reduce(1)[0] ** 0.5
+                if H[i + 1, i] != 0.0:
+                    K.scale(1.0 / H[i + 1, i], w, w)
+                for k in range(i):
+                    tq = cs[k] * H[k, i] + sn[k] * H[k + 1, i]
+                    H[k + 1, i] = -sn[k] * H[k, i] + cs[k] * H[k + 1, i]
+                    H[k, i] = tq
+                rr = np.hypot(H[i, i], H[i + 1, i])
+                cs[i], sn[i] = (1.0, 0.0) if rr == 0 else (H[i, i] / rr, H[i + 1, i] / rr)
+                H[i, i], H[i + 1, i] = rr, 0.0
+                g[i + 1] = -sn[i] * g[i]
+                g[i] = cs[i] * g[i]
+                err = abs(g[i + 1]) / bn
+                resvec.append(err)
+                total += 1
+                used = i + 1
+                if err <= tol:
+                    flag = 0
+                    break
+            y = np.zeros(used)
+            for i in range(used - 1, -1, -1):
+                y[i] = (g[i] - H[i, i + 1:used] @ y[i + 1:]) / H[i, i]
+            K.gs_update(-y, Z[:used], x_loc)
+            if flag == 0:
+                break
+            self._residual(b_loc, x_loc, r)
+            K.dots([(r, r)])
+            rn = K.reduce(1)[0] ** 0.5
+            if rn / bn <= tol:
+                flag = 0
+                break
+        self.be.synchronize()
+        return flag, total, np.array(resvec)
+
     def local_algorithmic_bytes(self):
         """Per-rank algorithmic bytes of the sharded levels of one V-cycle from x=0."""
         k = self.nrhs
@@ -709,6 +920,131 @@ class DistributedHierarchy:
             t += 8.0 * n * (1 + 2 * k) + (L.npre - 1 + L.npost) * sweep + resid
             t += 12.0 * (L.nnzR + L.nnzP) + 8.0 * k * (3 * n)
         return t
+
+
+class _KrylovOps:
+    """Vector passes of the Python sequencer's Krylov drivers on this rank's rows: the fused HIP passes of csrc/mg_krvec.hpp on
+    device tensors (HipBackend), numpy on the tensors of a host checker backend.  Sums land in ``self.s`` (8 scalars, on the
+    backend's device) at the pass's slot; ``reduce(count)`` all-reduces the first ``count`` and returns them as floats."""
+
+    def __init__(self, H):
+        self.H = H
+        self.be = H.be
+        self.n = H.levels[0].n_own
+        self.s = H.be.zeros(8)
+        self.hip = bool(self.s.is_cuda)
+        self.ws = H.be.zeros(2 * D.KRV_WORKSPACE) if self.hip else None
+
+    def vec(self, length):
+        return self.be.zeros(int(length))
+
+    def reduce(self, count):
+        t = self.s[:count]
+        self.H.comm.all_reduce_sum(t)
+        self.H.n_allreduces += 1
+        return [float(v) for v in t.tolist()]
+
+    def _w(self, slot):
+        return self.ws[slot * 1024:]
+
+    def _st(self):
+        return self.be.stream()
+
+    @staticmethod
+    def _np(t, n):
+        return t.numpy()[:n]
+
+    def _put(self, slot, vals):
+        for c, v in enumerate(vals):
+            self.s[slot + c] = float(v)
+
+    def dots(self, pairs, slot=0):
+        n = self.n
+        if self.hip:
+            D.vec_dots([a[:n] for a, _ in pairs], [b[:n] for _, b in pairs], n, self._w(slot), self.s[slot:], self._st())
+        else:
+            self._put(slot, [np.dot(self._np(a, n), self._np(b, n)) for a, b in pairs])
+
+    def pcg_dots(self, p, q, r):
+        n = self.n
+        if self.hip:
+            D.vec_pcg_dots(p[:n], q, r, n, self._w(0), self.s, self._st())
+        else:
+            pn, qn, rn = self._np(p, n), self._np(q, n), self._np(r, n)
+            self._put(0, [pn @ qn, rn @ qn, qn @ qn])
+
+    def pcg_update(self, alpha, p, q, x, r):
+        n = self.n
+        if self.hip:
+            D.vec_pcg_update(alpha, p[:n], q, x, r, n, self._w(0), self.s, self._st())
+        else:
+            xn, rn = self._np(x, n), self._np(r, n)
+            xn += alpha * self._np(p, n)
+            rn -= alpha * self._np(q, n)
+            self._put(0, [rn @ rn])
+
+    def xpby(self, x, beta, y):
+        n = self.n
+        if self.hip:
+            D.vec_xpby(x[:n], beta, y[:n], n, self._st())
+        else:
+            yn = self._np(y, n)
+            yn[:] = self._np(x, n) + beta * yn
+
+    def scale(self, a, x, y):
+        n = self.n
+        if self.hip:
+            D.vec_scale(a, x[:n], y[:n], n, self._st())
+        else:
+            self._np(y, n)[:] = a * self._np(x, n)
+
+    def bicg_p(self, beta, omega, r, v, p):
+        n = self.n
+        if self.hip:
+            D.vec_bicg_p(beta, omega, r, v, p, n, self._st())
+        else:
+            pn = self._np(p, n)
+            pn[:] = self._np(r, n) + beta * (pn - omega * self._np(v, n))
+
+    def bicg_s(self, alpha, v, r):
+        n = self.n
+        if self.hip:
+            D.vec_bicg_s(alpha, v, r, n, self._w(0), self.s, self._st())
+        else:
+            rn = self._np(r, n)
+            rn -= alpha * self._np(v, n)
+            self._put(0, [rn @ rn])
+
+    def bicg_ts(self, t, s):
+        n = self.n
+        if self.hip:
+            D.vec_bicg_ts(t, s, n, self._w(1), self.s[1:], self._st())
+        else:
+            tn = self._np(t, n)
+            self._put(1, [tn @ self._np(s, n), tn @ tn])
+
+    def bicg_xr(self, alpha, omega, phat, shat, t, rtld, x, r):
+        n = self.n
+        if self.hip:
+            D.vec_bicg_xr(alpha, omega, phat, shat[:n], t, rtld, x, r, n, self._w(0), self.s, self._st())
+        else:
+            xn, rn = self._np(x, n), self._np(r, n)
+            xn += alpha * self._np(phat, n) + omega * self._np(shat, n)
+            rn -= omega * self._np(t, n)
+            self._put(0, [rn @ rn, self._np(rtld, n) @ rn])
+
+    def gs_update(self, h, vs, w, want_norm=False):
+        n = self.n
+        if len(vs) == 0:
+            return
+        if self.hip:
+            D.vec_gs_update(h, [v[:n] for v in vs], w[:n], n, self._w(0), self.s if want_norm else None, self._st())
+        else:
+            wn = self._np(w, n)
+            for hj, v in zip(h, vs):
+                wn -= hj * self._np(v, n)
+            if want_norm:
+                self._put(0, [wn @ wn])
 
 
 # ======================================================================================================
@@ -822,6 +1158,34 @@ class NativeDistributedHierarchy:
                                                            float(tol), int(maxIter), C.byref(iters), D._f64(resvec)),
                  "mg_dist_solve_dev")
         return int(iters.value), resvec[: iters.value + 1]
+
+    # -- MG-preconditioned Krylov on this rank's fine rows (mg_dist_pcg_dev_FP64 / mg_dist_bicgstab_dev_FP64 / mg_dist_fgmres_dev_FP64):
+    #    b_loc, x_loc device tensors of n_own doubles, x_loc updated in place; returns (flag, iterations, resvec)
+    def _krylov(self, name, resvec, b_loc, x_loc, *args, nres=True):
+        import ctypes as C
+        iters, flag, nr = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        self.H.be.synchronize()       # b_loc / x_loc must have landed before the library's streams read them
+        tail = (C.byref(nr),) if nres else ()
+        D._check(self.lib, getattr(self.lib, name)(self.handle, D._ptr(b_loc), D._ptr(x_loc), self.H.levels[0].n_own, *args,
+                                                   C.byref(iters), C.byref(flag), D._f64(resvec), *tail), name)
+        return int(flag.value), int(iters.value), resvec[: (int(nr.value) if nres else int(iters.value))]
+
+    def pcg(self, b_loc, x_loc, tol: float, maxIter: int):
+        return self._krylov("mg_dist_pcg_dev_FP64", np.zeros(max(int(maxIter), 1)), b_loc, x_loc, float(tol), int(maxIter), nres=False)
+
+    def bicgstab(self, b_loc, x_loc, tol: float, maxIter: int):
+        return self._krylov("mg_dist_bicgstab_dev_FP64", np.zeros(2 * max(int(maxIter), 1) + 1), b_loc, x_loc, float(tol), int(maxIter))
+
+    def fgmres(self, b_loc, x_loc, inner: int, tol: float, maxIter: int):
+        return self._krylov("mg_dist_fgmres_dev_FP64", np.zeros(max(int(inner) * int(maxIter), 1)), b_loc, x_loc, int(inner), float(tol),
+                            int(maxIter))
+
+    def comm_stats(self):
+        """(halo exchanges started, all-reduces entered) by this rank since the handle was created (mg_dist_stats)."""
+        import ctypes as C
+        e, a = C.c_longlong(0), C.c_longlong(0)
+        D._check(self.lib, self.lib.mg_dist_stats(self.handle, C.byref(e), C.byref(a)), "mg_dist_stats")
+        return int(e.value), int(a.value)
 
     def comm_count(self) -> int:
         """Ranks of the sequencer's RCCL communicator as the library reports them (0: plug-in transport)."""
