@@ -1,5 +1,6 @@
 // mg_cabi.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
-// The C ABI of the single-GPU hierarchy (include/mgvcycle.h): create / set / finalize / cycle / solve / Krylov / measurement, stand-alone operators, the factor applier, hybrid Kaczmarz.
+// The C ABI of the single-GPU hierarchy (include/mgvcycle.h): create / set / finalize / cycle / solve / Krylov / measurement, stand-alone operators, the factor applier, hybrid Kaczmarz,
+// and of its ghost-layer form (mg_ghost_*).
 
 // ---- shared preambles and staging of the entry points (the value-type guards stay in the entry points: they name them) ----
 namespace {
@@ -1915,6 +1916,261 @@ int mg_kaczmarz_apply_dev_CFP64(mg_kaczmarz* k, double* x_dev, const double* b_d
 }
 int mg_kaczmarz_apply_CFP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit, long long sequential) {
   return kaczmarz_apply_host(true, k, x, b, nrhs, numit, sequential);
+}
+
+// Run the hierarchy's kernels on the caller's stream (e.g. torch's current stream) instead of its own.
+int mg_set_stream(mg_hierarchy* h, void* stream) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  graphs_clear(h);
+  (void)hipSetDevice(h->device);
+  (void)spin_sync(h->stream);
+  if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
+  h->stream = reinterpret_cast<hipStream_t>(stream);
+  h->owns_stream = false;
+  return MG_OK;
+}
+
+// Enqueue one cycle and return without waiting (x_is_zero must be 0 or 1).
+int mg_cycle_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
+                            long long x_is_zero) {
+  MG_REAL_ONLY(h);
+  MG_TRY(check_ready(h, n, nrhs));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for the asynchronous cycle");
+  (void)hipSetDevice(h->device);
+  return cycle_dev(h, b, x, x_is_zero == 1);
+}
+
+// The K-cycle's step INTO this hierarchy's first level (MGcycle.jl:72-76): x = 2 steps of FGMRES on A_1 x = b from x = 0,
+// preconditioned by the K-cycle of level 1.  For a hierarchy that is the replicated tail of a sharded one (mg_dist_*): the
+// level above it is sharded and its K-branch lands here.  A one-level hierarchy just solves.  Asynchronous like
+// mg_cycle_async_dev_FP64 as far as the stream goes (the FGMRES dots are host-visible, as everywhere in a K-cycle).
+int mg_kcycle_step_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n) {
+  MG_CF64_UNSUPPORTED(h);
+  MG_TRY(check_ready(h, n, 1));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  (void)hipSetDevice(h->device);
+  if (h->nlevels < 2) return cycle_dev(h, b, x, true);
+  Level& L = h->lev[0];
+  if (h->kstepZ.n != (size_t)(2 * n)) {
+    MG_TRY(h->kstepZ.alloc((size_t)(2 * n)));
+    MG_TRY(h->kstepAZ.alloc((size_t)(2 * n)));
+    MG_TRY(h->kstepX.alloc((size_t)n));
+  }
+  auto kprec = [&](const double* v, double* z) {
+    double* res = nullptr;
+    MG_TRY(cycle_level(h, 0, v, h->kstepX.p, L.x1.p, true, 'K', &res));
+    HIP_TRY(hipMemcpyAsync(z, res, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+    return (int)MG_OK;
+  };
+  return fgmres_relax(h, 0, b, x, 2, kprec, 1e-5, h->kstepZ.p, h->kstepAZ.p, true);
+}
+
+// =================================================================================================================
+// Ghost-layer form of the sharded cycle (mg_ghost_*; mg_ghost.inc): the rank's hierarchy is an ordinary mg_hierarchy on
+// extended boxes; these calls attach the geometry, the exchange plans and the transport to it.  After mg_ghost_finalize
+// mg_cycle_dev_FP64 / mg_solve_dev_FP64 (one right-hand side) run the sharded cycle: b and x are n_ext long (the extended
+// fine box), b's owned rows must be valid, x's owned rows are valid on return; norms are over all ranks' owned rows.
+// =================================================================================================================
+int mg_ghost_attach(mg_hierarchy* h, long long rank, long long world, long long nlevels_sharded, const char* unique_id128) {
+  MG_CF64_UNSUPPORTED(h);
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (world < 1 || rank < 0 || rank >= world || nlevels_sharded < 1 || nlevels_sharded >= h->nlevels)
+    return fail(MG_ERR_INVALID, "bad rank/world/levels (%lld/%lld, %lld sharded of %lld)", rank, world, nlevels_sharded, h->nlevels);
+  if (h->coarse_gmres)
+    return fail(MG_ERR_UNSUPPORTED, "the ghost-layer form needs a direct coarsest solve (coarseSolveType GMRES: mg_dist_*)");
+  (void)hipSetDevice(h->device);
+  graphs_clear(h);
+  if (h->ghost) { gh_release(h->ghost); h->ghost = nullptr; }
+  mg_ghost* g = new mg_ghost();
+  g->T.rank = (int)rank;
+  g->T.world = (int)world;
+  g->a = (int)nlevels_sharded;
+  g->lev.resize((size_t)nlevels_sharded);
+  auto bail = [&](int rc) { gh_release(g); return rc; };
+  if (hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&g->h_norm), sizeof(double)) != hipSuccess)
+    return bail(fail(MG_ERR_HIP, "stream / scratch creation failed"));
+  if (unique_id128) {
+    const int rc = g->T.init_rccl(unique_id128);
+    if (rc != MG_OK) return bail(rc);
+  }
+  h->ghost = g;
+  return MG_OK;
+}
+
+// A second RCCL communicator (another id of mg_dist_unique_id, broadcast like the first) for the ghost-layer send / recv on the
+// side stream: RCCL serialises the operations of ONE communicator in issue order, whatever their streams; with its own
+// communicator the fine level's exchange runs beside the coarse cycle and its all-reduces instead of in front of them.
+int mg_ghost_set_side_comm(mg_hierarchy* h, const char* unique_id128) {
+  MG_CF64_UNSUPPORTED(h);
+  if (!h || !h->ghost || !unique_id128) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
+  (void)hipSetDevice(h->device);
+  return h->ghost->T.init_side(unique_id128);
+}
+
+int mg_ghost_set_exchange_plugin(mg_hierarchy* h, mg_exchange_fn fn, void* user) {
+  MG_CF64_UNSUPPORTED(h);
+  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
+  return h->ghost->T.set_plugin(fn, user);
+}
+
+// Sharded level `level` (1-based): extended box ext[3] (nodes per dimension, x fastest; 1 for unused dimensions), owned box
+// [own_lo, own_hi) inside it, gmin = the smallest ghost width over the cut sides OF ANY RANK (the schedule of exchanges must
+// be the same on every rank); send_idx: extended-box ids (0-based) of owned nodes grouped by destination rank
+// (send_splits[world]); recv_idx: extended-box ids of this rank's ghost nodes grouped by owner (recv_splits[world]), each
+// peer's part in ascending global id on both sides.
+int mg_ghost_set_level_INT64(mg_hierarchy* h, long long level, const long long* ext, const long long* own_lo, const long long* own_hi,
+                             long long gmin, long long n_send, const long long* send_idx, const long long* send_splits,
+                             long long n_recv, const long long* recv_idx, const long long* recv_splits) {
+  MG_CF64_UNSUPPORTED(h);
+  UploadFence upload_fence;
+  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
+  mg_ghost* g = h->ghost;
+  if (level < 1 || level > g->a) return fail(MG_ERR_INVALID, "bad level %lld", level);
+  if (!ext || !own_lo || !own_hi || !send_splits || !recv_splits || (n_send > 0 && !send_idx) || (n_recv > 0 && !recv_idx) || n_send < 0 || n_recv < 0 || gmin < 1)
+    return fail(MG_ERR_INVALID, "bad ghost-level arrays");
+  (void)hipSetDevice(h->device);
+  GhostLevel& L = g->lev[(size_t)level - 1];
+  long long n = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (ext[k] < 1 || own_lo[k] < 0 || own_hi[k] <= own_lo[k] || own_hi[k] > ext[k]) return fail(MG_ERR_INVALID, "ghost level %lld: bad boxes", level);
+    L.ext[k] = (int)ext[k]; L.lo[k] = (int)own_lo[k]; L.hi[k] = (int)own_hi[k];
+    n *= ext[k];
+  }
+  if (n != h->lev[(size_t)level - 1].A.n_rows && h->lev[(size_t)level - 1].A.set)
+    return fail(MG_ERR_INVALID, "ghost level %lld: the extended box has %lld nodes, As[%lld] %lld rows", level, n, level, h->lev[(size_t)level - 1].A.n_rows);
+  L.n = n;
+  L.gmin = (int)std::min<long long>(gmin, GH_FULL);
+  L.n_send = n_send;
+  L.n_recv = n_recv;
+  L.send_splits.assign(send_splits, send_splits + g->T.world);
+  L.recv_splits.assign(recv_splits, recv_splits + g->T.world);
+  long long ss = 0, rs = 0;
+  for (int q = 0; q < g->T.world; ++q) { ss += L.send_splits[(size_t)q]; rs += L.recv_splits[(size_t)q]; }
+  if (ss != n_send || rs != n_recv) return fail(MG_ERR_INVALID, "ghost plan: splits do not add up (send %lld/%lld, recv %lld/%lld)", ss, n_send, rs, n_recv);
+  auto in_own = [&](long long id) {
+    const long long x = id % L.ext[0], y = (id / L.ext[0]) % L.ext[1], z = id / ((long long)L.ext[0] * L.ext[1]);
+    return x >= L.lo[0] && x < L.hi[0] && y >= L.lo[1] && y < L.hi[1] && z >= L.lo[2] && z < L.hi[2];
+  };
+  std::vector<int> si((size_t)std::max<long long>(n_send, 1), 0), ri((size_t)std::max<long long>(n_recv, 1), 0);
+  for (long long i = 0; i < n_send; ++i) {
+    if (send_idx[i] < 0 || send_idx[i] >= n || !in_own(send_idx[i])) return fail(MG_ERR_INVALID, "ghost plan: a send index is not an owned node");
+    si[(size_t)i] = (int)send_idx[i];
+  }
+  for (long long i = 0; i < n_recv; ++i) {
+    if (recv_idx[i] < 0 || recv_idx[i] >= n || in_own(recv_idx[i])) return fail(MG_ERR_INVALID, "ghost plan: a receive index is not a ghost node");
+    ri[(size_t)i] = (int)recv_idx[i];
+  }
+  MG_TRY(L.send_idx.alloc(si.size()));
+  MG_TRY(L.recv_idx.alloc(ri.size()));
+  MG_TRY(L.send_buf.alloc(si.size()));
+  MG_TRY(L.recv_buf.alloc(ri.size()));
+  MG_TRY(L.send_buf2.alloc(si.size()));
+  MG_TRY(L.recv_buf2.alloc(ri.size()));
+  HIP_TRY(hipMemcpy(L.send_idx.p, si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(L.recv_idx.p, ri.data(), ri.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!L.ev_packed) HIP_TRY(hipEventCreateWithFlags(&L.ev_packed, hipEventDisableTiming));
+  if (!L.ev_landed) HIP_TRY(hipEventCreateWithFlags(&L.ev_landed, hipEventDisableTiming));
+  L.set = true;
+  g->finalized = false;
+  return MG_OK;
+}
+
+int mg_ghost_finalize(mg_hierarchy* h) {
+  MG_CF64_UNSUPPORTED(h);
+  UploadFence upload_fence;
+  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
+  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  mg_ghost* g = h->ghost;
+  (void)hipSetDevice(h->device);
+  graphs_clear(h);
+  MG_TRY(g->T.ready());
+  for (int l = 0; l < g->a; ++l) {
+    GhostLevel& L = g->lev[(size_t)l];
+    if (!L.set) return fail(MG_ERR_STATE, "ghost level %d was not set", l + 1);
+    if (L.n != h->lev[(size_t)l].n) return fail(MG_ERR_INVALID, "ghost level %d: the extended box has %lld nodes, the level %lld rows", l + 1, L.n, h->lev[(size_t)l].n);
+    L.active = g->T.world > 1;     // (every box of a partition into more than one has a neighbour)
+    L.depth.clear();
+    L.pending = nullptr;
+  }
+  MG_TRY(g->b0.alloc((size_t)g->lev[0].n));
+  HIP_TRY(hipMemset(g->b0.p, 0, g->b0.bytes()));
+  // ---- what EVERY rank's kernels can do (see mg_ghost): one all-reduce of 0/1 flags, a capability is kept where the sum is `world` ----
+  {
+    const int a = g->a;
+    std::vector<double> flags((size_t)(1 + 3 * a), 0.0);
+    {
+      Level& L0 = h->lev[0];
+      flags[0] = (h->nrhs >= 1 && march4_ok_static(h, 0)) ? 1.0 : 0.0;
+      for (int l = 0; l < a; ++l) {
+        Level& L = h->lev[(size_t)l];
+        const bool m2 = march2_ok_static(h, l);
+        flags[(size_t)(1 + 3 * l)] = m2 ? 1.0 : 0.0;
+        flags[(size_t)(2 + 3 * l)] = (m2 && zero_form_static(L.A)) ? 1.0 : 0.0;
+        flags[(size_t)(3 + 3 * l)] = restrict_can_scale_static(h, L.R) ? 1.0 : 0.0;
+      }
+      (void)L0;
+    }
+    // the flags travel like every other host-visible sum: staged through pinned memory and all-reduced on ONE stream.  Not a
+    // collective of the schedule: mg_ghost_allreduce_count leaves it out.
+    const size_t cnt = flags.size();
+    const long long counted = g->T.n_allreduce;
+    DevBuf<double> tmp;
+    MG_TRY(tmp.alloc(cnt));
+    MG_TRY(g->T.stage(cnt, h->stream));
+    double* sums = g->T.h_stage;
+    std::copy(flags.begin(), flags.end(), sums);
+    HIP_TRY(hipMemcpyAsync(tmp.p, sums, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    MG_TRY(g->T.allreduce_now(tmp.p, cnt, sums, h->stream));
+    tmp.release();
+    g->T.n_allreduce = counted;
+    const double ranks = g->T.sums_global() ? (double)g->T.world : 1.0;   // (how many ranks' flags a sum holds)
+    auto all = [&](size_t i) { return sums[i] > ranks - 0.5; };
+    g->agree4 = all(0);
+    g->agree2.assign((size_t)a, 1);
+    g->agree_zero.assign((size_t)a, 1);
+    g->agree_scale.assign((size_t)a, 1);
+    for (int l = 0; l < a; ++l) {
+      g->agree2[(size_t)l] = all((size_t)(1 + 3 * l)) ? 1 : 0;
+      g->agree_zero[(size_t)l] = all((size_t)(2 + 3 * l)) ? 1 : 0;
+      g->agree_scale[(size_t)l] = all((size_t)(3 + 3 * l)) ? 1 : 0;
+    }
+  }
+  g->finalized = true;               // (columns_ok reads the agreed flags through the finalized handle)
+  if (h->nrhs != 1 && !columns_ok(h)) {    // (every rank sees the same agreed flags: all of them fail here, or none)
+    g->finalized = false;
+    return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: a block of right-hand sides is solved column by column, which needs: %s", columns_why_not(h));
+  }
+  return MG_OK;
+}
+
+// Timing aid (bench.py --ghost-dry R/N): this process is rank R of a world of N ALONE on its GPU - every exchange runs its pack and
+// unpack kernels, nothing travels, sums stay local.  The numbers such a handle computes mean nothing; its step time is what one
+// GPU of the N spends on compute, redundant ghost rows included (the ceiling of the strong scaling with free communication).
+int mg_ghost_set_dry(mg_hierarchy* h, long long on) {
+  MG_CF64_UNSUPPORTED(h);
+  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
+  return h->ghost->T.set_dry(on != 0);
+}
+// exchanges started and doubles sent by this rank since mg_ghost_attach (what the schedule really communicates)
+int mg_ghost_stats(mg_hierarchy* h, long long* exchanges, long long* doubles_sent) {
+  MG_CF64_UNSUPPORTED(h);
+  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
+  if (exchanges) *exchanges = h->ghost->T.n_exchanges;
+  if (doubles_sent) *doubles_sent = h->ghost->T.n_sent;
+  return MG_OK;
+}
+int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count) {
+  MG_CF64_UNSUPPORTED(h);
+  if (!h || !h->ghost || !count) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
+  *count = h->ghost->T.n_allreduce;
+  return MG_OK;
+}
+// Ranks of this handle's communicator AS RCCL REPORTS THEM (ncclCommCount); 0 with the plug-in transport / a world of one without RCCL.
+int mg_ghost_comm_count(mg_hierarchy* h, long long* count) {
+  MG_CF64_UNSUPPORTED(h);
+  if (!h || !h->ghost || !count) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
+  return h->ghost->T.comm_count(count);
 }
 
 }  // extern "C"

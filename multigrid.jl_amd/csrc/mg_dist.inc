@@ -1,5 +1,5 @@
 // mg_dist.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
-// Native multi-GPU sequencer (mg_dist_*): sharded level schedule, RCCL halo exchange on a side stream, replicated tail.
+// Native multi-GPU sequencer (mg_dist_*), the halo form: sharded level schedule, halo exchange on a side stream, replicated tail.
 extern "C" {
 // =================================================================================================================
 // Native multi-GPU sequencer (one process per GPU): the level schedule of the sharded cycle in C++, halo exchange by
@@ -9,14 +9,12 @@ extern "C" {
 // local operators [owned | halo] and send lists; this code owns the vectors and the hot loop.
 // =================================================================================================================
 namespace {
-// (the RCCL loader g_rccl lives in mg_ghost.inc)
 struct DistPlan {
   bool set = false, active = false;
   long long n_own_src = 0, n_halo = 0, n_send = 0;
   DevBuf<int> send_idx;
   DevBuf<double> send_buf;
   std::vector<long long> send_splits, recv_splits;   // per peer
-  double *h_send = nullptr, *h_recv = nullptr;       // pinned staging (plug-in transport)
 };
 struct DistLevel {
   long long n_own = 0, n_int = 0;
@@ -37,7 +35,7 @@ struct DistKrylov {
   DevBuf<double> vec;      // the drivers' vectors, carved out of one allocation
   DevBuf<double> part;     // partial sums of the fused passes: MAXS scalars x MAXB workgroups
   DevBuf<double> scal;     // MAXS scalars, all-reduced in place
-  double* h_scal = nullptr;   // pinned: [0, MAXS) the scalars read back, [MAXS, 2 MAXS) the plug-in's result
+  double* h_scal = nullptr;   // pinned: the MAXS scalars summed over the ranks, as the host reads them
   void release() {
     vec.release();
     part.release();
@@ -67,10 +65,8 @@ __global__ __launch_bounds__(256) void dist_gather64(const double* __restrict__ 
 }
 
 struct mg_dist {
-  int device = 0, rank = 0, world = 1;
-  ncclComm_t comm = nullptr;            // RCCL transport
-  mg_exchange_fn plug = nullptr;        // host-staged transport (tests / one shared GPU)
-  void* plug_user = nullptr;
+  int device = 0;
+  Transport T;
   hipStream_t stream = nullptr, side = nullptr;
   hipEvent_t ev_packed = nullptr, ev_landed = nullptr;
   std::vector<DistLevel> lev;
@@ -90,21 +86,10 @@ struct mg_dist {
   // reductions
   DevBuf<double> partial, partial2, scalar;
   double* h_scalar = nullptr;
-  double* h_stage = nullptr;            // pinned staging for the plug-in collectives
-  size_t h_stage_n = 0;
   DistKrylov kry;
-  long long n_exchanges = 0, n_allreduce = 0;   // collectives this rank entered (mg_dist_stats)
 };
 
 namespace {
-int dist_stage(mg_dist* h, size_t n) {
-  if (h->h_stage_n >= n) return MG_OK;
-  if (h->h_stage) (void)hipHostFree(h->h_stage);
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_stage), sizeof(double) * n));
-  h->h_stage_n = n;
-  return MG_OK;
-}
-
 // Start filling the halo tail buf[n_own_src : n_own_src + n_halo] (values the peers need are packed first).
 // RCCL: pack on the compute stream, send/recv on the side stream; the compute stream goes on.  Plug-in: done on return.
 int dist_exchange_start(mg_dist* h, DistPlan& p, double* buf) {
@@ -113,39 +98,20 @@ int dist_exchange_start(mg_dist* h, DistPlan& p, double* buf) {
   if (p.n_send > 0)
     hipLaunchKernelGGL(dist_pack, dim3((unsigned)((p.n_send * k + 255) / 256)), dim3(256), 0, h->stream, buf, p.send_idx.p, p.send_buf.p, p.n_send, (int)k);
   HIP_TRY(hipGetLastError());
-  ++h->n_exchanges;
-  double* recv = buf + p.n_own_src * k;
-  if (h->comm) {
+  const bool hop = h->T.on_stream();
+  if (hop) {
     HIP_TRY(hipEventRecord(h->ev_packed, h->stream));
     HIP_TRY(hipStreamWaitEvent(h->side, h->ev_packed, 0));
-    NCCL_TRY(g_rccl.GroupStart());
-    long long so = 0, ro = 0;
-    for (int peer = 0; peer < h->world; ++peer) {
-      const long long ns = p.send_splits[(size_t)peer] * k, nr = p.recv_splits[(size_t)peer] * k;
-      if (ns > 0) NCCL_TRY(g_rccl.Send(p.send_buf.p + so, (size_t)ns, NCCL_DOUBLE, peer, h->comm, h->side));
-      if (nr > 0) NCCL_TRY(g_rccl.Recv(recv + ro, (size_t)nr, NCCL_DOUBLE, peer, h->comm, h->side));
-      so += ns;
-      ro += nr;
-    }
-    NCCL_TRY(g_rccl.GroupEnd());
-    HIP_TRY(hipEventRecord(h->ev_landed, h->side));
-    return MG_OK;
   }
-  // host-staged transport
-  if (p.n_send > 0) HIP_TRY(hipMemcpyAsync(p.h_send, p.send_buf.p, sizeof(double) * (size_t)(p.n_send * k), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
-  std::vector<long long> ssk(p.send_splits), rsk(p.recv_splits);     // (counts in doubles: rows x right-hand sides)
-  for (auto& c : ssk) c *= k;
-  for (auto& c : rsk) c *= k;
-  if (h->plug(h->plug_user, 0, p.h_send, ssk.data(), p.h_recv, rsk.data(), 0) != 0)
-    return fail(MG_ERR_HIP, "exchange plug-in failed (all_to_all)");
-  if (p.n_halo > 0) HIP_TRY(hipMemcpyAsync(recv, p.h_recv, sizeof(double) * (size_t)(p.n_halo * k), hipMemcpyHostToDevice, h->stream));
+  const Transport::Pair pair = {p.send_buf.p, buf + p.n_own_src * k};   // (received straight into the halo tail)
+  MG_TRY(h->T.exchange(&pair, 1, p.send_splits, p.recv_splits, k, hop ? h->side : h->stream));
+  if (hop) HIP_TRY(hipEventRecord(h->ev_landed, h->side));
   return MG_OK;
 }
 // Make the compute stream wait for the halo started by dist_exchange_start.
 int dist_exchange_finish(mg_dist* h, DistPlan& p) {
   if (!p.set || !p.active) return MG_OK;
-  if (h->comm) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_landed, 0));
+  if (h->T.on_stream()) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_landed, 0));
   return MG_OK;
 }
 
@@ -177,20 +143,7 @@ int dist_norm(mg_dist* h, const double* v, long long n, double* out) {
 
 // all-reduce h->scalar (a local sum of squares) and return its square root on the host
 int dist_reduce_scalar(mg_dist* h, double* out) {
-  if (h->comm || h->world > 1) ++h->n_allreduce;
-  if (h->comm) {
-    NCCL_TRY(g_rccl.AllReduce(h->scalar.p, h->scalar.p, 1, NCCL_DOUBLE, NCCL_SUM, h->comm, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(spin_sync(h->stream));
-  } else {
-    HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(spin_sync(h->stream));
-    if (h->world > 1) {
-      double in = *h->h_scalar, outv = 0.0;
-      if (h->plug(h->plug_user, 1, &in, nullptr, &outv, nullptr, 1) != 0) return fail(MG_ERR_HIP, "exchange plug-in failed (all_reduce)");
-      *h->h_scalar = outv;
-    }
-  }
+  MG_TRY(h->T.allreduce_now(h->scalar.p, 1, h->h_scalar, h->stream));
   *out = std::sqrt(*h->h_scalar);
   return MG_OK;
 }
@@ -438,19 +391,7 @@ int dist_cycle(mg_dist* h, int l, const double* b, double* xa, double* xb, bool 
   } else {
     // restrict into this rank's rows of the first replicated level, all-gather, run the tail replicated
     MG_TRY(restrict_to(h->bc_pad.p));
-    if (h->comm) {
-      NCCL_TRY(g_rccl.AllGather(h->bc_pad.p, h->bc_all.p, (size_t)(h->max_tail * h->nrhs), NCCL_DOUBLE, h->comm, h->stream));
-    } else if (h->world > 1) {
-      const long long mt = h->max_tail * h->nrhs;      // doubles per rank: padded share x right-hand sides
-      MG_TRY(dist_stage(h, (size_t)mt * (size_t)(h->world + 1)));
-      HIP_TRY(hipMemcpyAsync(h->h_stage, h->bc_pad.p, sizeof(double) * (size_t)mt, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(spin_sync(h->stream));
-      if (h->plug(h->plug_user, 2, h->h_stage, nullptr, h->h_stage + mt, nullptr, mt) != 0)
-        return fail(MG_ERR_HIP, "exchange plug-in failed (all_gather)");
-      HIP_TRY(hipMemcpyAsync(h->bc_all.p, h->h_stage + mt, sizeof(double) * (size_t)(mt * h->world), hipMemcpyHostToDevice, h->stream));
-    } else {
-      HIP_TRY(hipMemcpyAsync(h->bc_all.p, h->bc_pad.p, sizeof(double) * (size_t)(h->max_tail * h->nrhs), hipMemcpyDeviceToDevice, h->stream));
-    }
+    MG_TRY(h->T.allgather(h->bc_pad.p, h->bc_all.p, (size_t)(h->max_tail * h->nrhs), h->stream));   // (doubles per rank: padded share x right-hand sides)
     hipLaunchKernelGGL(dist_gather64, dim3((unsigned)((h->n_tail * h->nrhs + 255) / 256)), dim3(256), 0, h->stream, h->bc_all.p, h->gather_index.p, h->b_tail.p, h->n_tail, (int)h->nrhs);
     HIP_TRY(hipGetLastError());
     MG_TRY(mg_set_cycle_type(h->tail, ctype));
@@ -492,10 +433,10 @@ int dist_set_plan(mg_dist* h, DistPlan& p, long long n_own_src, long long n_halo
   p.n_own_src = n_own_src;
   p.n_halo = n_halo;
   p.n_send = n_send;
-  p.send_splits.assign(send_splits, send_splits + h->world);
-  p.recv_splits.assign(recv_splits, recv_splits + h->world);
+  p.send_splits.assign(send_splits, send_splits + h->T.world);
+  p.recv_splits.assign(recv_splits, recv_splits + h->T.world);
   long long ss = 0, rs = 0;
-  for (int q = 0; q < h->world; ++q) { ss += p.send_splits[(size_t)q]; rs += p.recv_splits[(size_t)q]; }
+  for (int q = 0; q < h->T.world; ++q) { ss += p.send_splits[(size_t)q]; rs += p.recv_splits[(size_t)q]; }
   if (ss != n_send || rs != n_halo) return fail(MG_ERR_INVALID, "halo plan: splits do not add up (send %lld/%lld, recv %lld/%lld)", ss, n_send, rs, n_halo);
   std::vector<int> idx((size_t)std::max<long long>(n_send, 1), 0);
   for (long long i = 0; i < n_send; ++i) {
@@ -505,18 +446,11 @@ int dist_set_plan(mg_dist* h, DistPlan& p, long long n_own_src, long long n_halo
   MG_TRY(p.send_idx.alloc(idx.size()));
   MG_TRY(p.send_buf.alloc(idx.size() * (size_t)h->nrhs));
   HIP_TRY(hipMemcpy(p.send_idx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
-  if (!h->comm) {
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p.h_send), sizeof(double) * (size_t)(std::max<long long>(n_send, 1) * h->nrhs)));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p.h_recv), sizeof(double) * (size_t)(std::max<long long>(n_halo, 1) * h->nrhs)));
-  }
   return MG_OK;
 }
 void dist_free_plan(DistPlan& p) {
   p.send_idx.release();
   p.send_buf.release();
-  if (p.h_send) (void)hipHostFree(p.h_send);
-  if (p.h_recv) (void)hipHostFree(p.h_recv);
-  p.h_send = p.h_recv = nullptr;
 }
 }  // namespace
 
@@ -543,8 +477,8 @@ int mg_dist_create(long long device_id, long long rank, long long world, const c
   HIP_TRY(hipSetDevice((int)device_id));
   mg_dist* h = new mg_dist();
   h->device = (int)device_id;
-  h->rank = (int)rank;
-  h->world = (int)world;
+  h->T.rank = (int)rank;
+  h->T.world = (int)world;
   h->cycle = (char)cycleType;
   h->nl_total = nl_total;
   h->lev.resize((size_t)nlevels);
@@ -555,11 +489,8 @@ int mg_dist_create(long long device_id, long long rank, long long world, const c
       h->partial.alloc(1024) != MG_OK || h->partial2.alloc(256) != MG_OK || h->scalar.alloc(1) != MG_OK || hipHostMalloc(reinterpret_cast<void**>(&h->h_scalar), sizeof(double)) != hipSuccess)
     return bail(fail(MG_ERR_HIP, "stream / event / scratch creation failed"));
   if (unique_id128) {
-    if (!g_rccl.load()) return bail(fail(MG_ERR_HIP, "librccl.so could not be loaded"));
-    Rccl::UniqueId u;
-    std::memcpy(u.internal, unique_id128, 128);
-    const ncclResult_t rc = g_rccl.CommInitRank(&h->comm, (int)world, u, (int)rank);
-    if (rc != ncclSuccess) return bail(dist_nccl(rc, "ncclCommInitRank"));
+    const int rc = h->T.init_rccl(unique_id128);
+    if (rc != MG_OK) return bail(rc);
   }
   *out = h;
   return MG_OK;
@@ -568,13 +499,7 @@ int mg_dist_create(long long device_id, long long rank, long long world, const c
 // Ranks of this handle's communicator AS RCCL REPORTS THEM (ncclCommCount); 0 when the handle uses the plug-in transport.
 int mg_dist_comm_count(mg_dist* h, long long* count) {
   if (!h || !count) return fail(MG_ERR_INVALID, "null argument");
-  *count = 0;
-  if (!h->comm) return MG_OK;
-  if (!g_rccl.CommCount) return fail(MG_ERR_UNSUPPORTED, "this librccl has no ncclCommCount");
-  int c = 0;
-  NCCL_TRY(g_rccl.CommCount(h->comm, &c));
-  *count = c;
-  return MG_OK;
+  return h->T.comm_count(count);
 }
 
 // Right-hand sides per call (default 1): blocks are row-major [n][nrhs] everywhere, as in mg_hierarchy (MGdef.jl:163-176: the
@@ -593,11 +518,8 @@ int mg_dist_set_nrhs(mg_dist* h, long long nrhs) {
 }
 
 int mg_dist_set_exchange_plugin(mg_dist* h, mg_exchange_fn fn, void* user) {
-  if (!h || !fn) return fail(MG_ERR_INVALID, "null argument");
-  if (h->comm) return fail(MG_ERR_STATE, "this handle was created with an RCCL communicator");
-  h->plug = fn;
-  h->plug_user = user;
-  return MG_OK;
+  if (!h) return fail(MG_ERR_INVALID, "null argument");
+  return h->T.set_plugin(fn, user);
 }
 
 int mg_dist_set_level(mg_dist* h, long long level, long long n_own, long long n_int, mg_operator* A_int, mg_operator* A_bnd,
@@ -666,13 +588,13 @@ int mg_dist_set_tail_INT64(mg_dist* h, mg_hierarchy* tail, long long n_tail, lon
   h->max_tail = max_tail;
   const size_t kk = (size_t)h->nrhs;
   MG_TRY(h->bc_pad.alloc((size_t)max_tail * kk));
-  MG_TRY(h->bc_all.alloc((size_t)max_tail * (size_t)h->world * kk));
+  MG_TRY(h->bc_all.alloc((size_t)max_tail * (size_t)h->T.world * kk));
   MG_TRY(h->b_tail.alloc((size_t)n_tail * kk));
   MG_TRY(h->x_tail.alloc((size_t)n_tail * kk));
   if (tail->nrhs != h->nrhs) return fail(MG_ERR_INVALID, "the tail hierarchy is set up for %lld right-hand sides, the sequencer for %lld", tail->nrhs, h->nrhs);
   MG_TRY(h->gather_index.alloc((size_t)n_tail));
   for (long long i = 0; i < n_tail; ++i)
-    if (gather_index[i] < 0 || gather_index[i] >= max_tail * h->world) return fail(MG_ERR_INVALID, "gather index out of range");
+    if (gather_index[i] < 0 || gather_index[i] >= max_tail * h->T.world) return fail(MG_ERR_INVALID, "gather index out of range");
   HIP_TRY(hipMemset(h->bc_pad.p, 0, h->bc_pad.bytes()));
   HIP_TRY(hipMemset(h->x_tail.p, 0, h->x_tail.bytes()));
   HIP_TRY(hipMemcpy(h->gather_index.p, gather_index, (size_t)n_tail * sizeof(long long), hipMemcpyHostToDevice));
@@ -705,7 +627,7 @@ int mg_dist_finalize(mg_dist* h) {
       (void)hipDeviceSynchronize();
       MG_TRY(derive_class_d_csr(L.A_int->M, L.d, (size_t)nreg));
     }
-  if (h->world > 1 && !h->comm && !h->plug) return fail(MG_ERR_STATE, "no transport: pass an RCCL unique id to mg_dist_create or set an exchange plug-in");
+  MG_TRY(h->T.ready());
   const int a = (int)h->lev.size();
   for (int l = 0; l < a; ++l) {
     DistLevel& L = h->lev[(size_t)l];
@@ -838,7 +760,7 @@ int mg_dist_destroy(mg_dist* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)spin_sync(h->stream);
   if (h->side) (void)spin_sync(h->side);
-  if (h->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(h->comm);
+  h->T.release();
   (void)mg_dist_release_tail(h);
   for (auto& L : h->lev) {
     dist_free_plan(L.planA);
@@ -860,293 +782,11 @@ int mg_dist_destroy(mg_dist* h) {
   h->scalar.release();
   h->kry.release();
   if (h->h_scalar) (void)hipHostFree(h->h_scalar);
-  if (h->h_stage) (void)hipHostFree(h->h_stage);
   if (h->ev_packed) (void)hipEventDestroy(h->ev_packed);
   if (h->ev_landed) (void)hipEventDestroy(h->ev_landed);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
-  return MG_OK;
-}
-
-// Run the hierarchy's kernels on the caller's stream (e.g. torch's current stream) instead of its own.
-int mg_set_stream(mg_hierarchy* h, void* stream) {
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  graphs_clear(h);
-  (void)hipSetDevice(h->device);
-  (void)spin_sync(h->stream);
-  if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  h->stream = reinterpret_cast<hipStream_t>(stream);
-  h->owns_stream = false;
-  return MG_OK;
-}
-
-// Enqueue one cycle and return without waiting (x_is_zero must be 0 or 1).
-int mg_cycle_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs,
-                            long long x_is_zero) {
-  MG_REAL_ONLY(h);
-  MG_TRY(check_ready(h, n, nrhs));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
-  if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for the asynchronous cycle");
-  (void)hipSetDevice(h->device);
-  return cycle_dev(h, b, x, x_is_zero == 1);
-}
-
-// The K-cycle's step INTO this hierarchy's first level (MGcycle.jl:72-76): x = 2 steps of FGMRES on A_1 x = b from x = 0,
-// preconditioned by the K-cycle of level 1.  For a hierarchy that is the replicated tail of a sharded one (mg_dist_*): the
-// level above it is sharded and its K-branch lands here.  A one-level hierarchy just solves.  Asynchronous like
-// mg_cycle_async_dev_FP64 as far as the stream goes (the FGMRES dots are host-visible, as everywhere in a K-cycle).
-int mg_kcycle_step_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n) {
-  MG_CF64_UNSUPPORTED(h);
-  MG_TRY(check_ready(h, n, 1));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
-  (void)hipSetDevice(h->device);
-  if (h->nlevels < 2) return cycle_dev(h, b, x, true);
-  Level& L = h->lev[0];
-  if (h->kstepZ.n != (size_t)(2 * n)) {
-    MG_TRY(h->kstepZ.alloc((size_t)(2 * n)));
-    MG_TRY(h->kstepAZ.alloc((size_t)(2 * n)));
-    MG_TRY(h->kstepX.alloc((size_t)n));
-  }
-  auto kprec = [&](const double* v, double* z) {
-    double* res = nullptr;
-    MG_TRY(cycle_level(h, 0, v, h->kstepX.p, L.x1.p, true, 'K', &res));
-    HIP_TRY(hipMemcpyAsync(z, res, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
-    return (int)MG_OK;
-  };
-  return fgmres_relax(h, 0, b, x, 2, kprec, 1e-5, h->kstepZ.p, h->kstepAZ.p, true);
-}
-
-// =================================================================================================================
-// Ghost-layer form of the sharded cycle (mg_ghost_*; mg_ghost.inc): the rank's hierarchy is an ordinary mg_hierarchy on
-// extended boxes; these calls attach the geometry, the exchange plans and the transport to it.  After mg_ghost_finalize
-// mg_cycle_dev_FP64 / mg_solve_dev_FP64 (one right-hand side) run the sharded cycle: b and x are n_ext long (the extended
-// fine box), b's owned rows must be valid, x's owned rows are valid on return; norms are over all ranks' owned rows.
-// =================================================================================================================
-int mg_ghost_attach(mg_hierarchy* h, long long rank, long long world, long long nlevels_sharded, const char* unique_id128) {
-  MG_CF64_UNSUPPORTED(h);
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (world < 1 || rank < 0 || rank >= world || nlevels_sharded < 1 || nlevels_sharded >= h->nlevels)
-    return fail(MG_ERR_INVALID, "bad rank/world/levels (%lld/%lld, %lld sharded of %lld)", rank, world, nlevels_sharded, h->nlevels);
-  if (h->coarse_gmres)
-    return fail(MG_ERR_UNSUPPORTED, "the ghost-layer form needs a direct coarsest solve (coarseSolveType GMRES: mg_dist_*)");
-  (void)hipSetDevice(h->device);
-  graphs_clear(h);
-  if (h->ghost) { gh_release(h->ghost); h->ghost = nullptr; }
-  mg_ghost* g = new mg_ghost();
-  g->rank = (int)rank;
-  g->world = (int)world;
-  g->a = (int)nlevels_sharded;
-  g->lev.resize((size_t)nlevels_sharded);
-  auto bail = [&](int rc) { gh_release(g); return rc; };
-  if (hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&g->h_norm), sizeof(double)) != hipSuccess)
-    return bail(fail(MG_ERR_HIP, "stream / scratch creation failed"));
-  if (unique_id128) {
-    if (!g_rccl.load()) return bail(fail(MG_ERR_HIP, "librccl.so could not be loaded"));
-    Rccl::UniqueId u;
-    std::memcpy(u.internal, unique_id128, 128);
-    const ncclResult_t rc = g_rccl.CommInitRank(&g->comm, (int)world, u, (int)rank);
-    if (rc != ncclSuccess) return bail(dist_nccl(rc, "ncclCommInitRank"));
-  }
-  h->ghost = g;
-  return MG_OK;
-}
-
-// A second RCCL communicator (another id of mg_dist_unique_id, broadcast like the first) for the ghost-layer send / recv on the
-// side stream: RCCL serialises the operations of ONE communicator in issue order, whatever their streams; with its own
-// communicator the fine level's exchange runs beside the coarse cycle and its all-reduces instead of in front of them.
-int mg_ghost_set_side_comm(mg_hierarchy* h, const char* unique_id128) {
-  MG_CF64_UNSUPPORTED(h);
-  if (!h || !h->ghost || !unique_id128) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
-  mg_ghost* g = h->ghost;
-  if (!g->comm) return fail(MG_ERR_STATE, "this handle was attached without an RCCL communicator");
-  if (g->comm_side) return fail(MG_ERR_STATE, "the side communicator is already set");
-  (void)hipSetDevice(h->device);
-  Rccl::UniqueId u;
-  std::memcpy(u.internal, unique_id128, 128);
-  NCCL_TRY(g_rccl.CommInitRank(&g->comm_side, g->world, u, g->rank));
-  return MG_OK;
-}
-
-int mg_ghost_set_exchange_plugin(mg_hierarchy* h, mg_exchange_fn fn, void* user) {
-  MG_CF64_UNSUPPORTED(h);
-  if (!h || !h->ghost || !fn) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
-  if (h->ghost->comm) return fail(MG_ERR_STATE, "this handle was attached with an RCCL communicator");
-  h->ghost->plug = fn;
-  h->ghost->plug_user = user;
-  return MG_OK;
-}
-
-// Sharded level `level` (1-based): extended box ext[3] (nodes per dimension, x fastest; 1 for unused dimensions), owned box
-// [own_lo, own_hi) inside it, gmin = the smallest ghost width over the cut sides OF ANY RANK (the schedule of exchanges must
-// be the same on every rank); send_idx: extended-box ids (0-based) of owned nodes grouped by destination rank
-// (send_splits[world]); recv_idx: extended-box ids of this rank's ghost nodes grouped by owner (recv_splits[world]), each
-// peer's part in ascending global id on both sides.
-int mg_ghost_set_level_INT64(mg_hierarchy* h, long long level, const long long* ext, const long long* own_lo, const long long* own_hi,
-                             long long gmin, long long n_send, const long long* send_idx, const long long* send_splits,
-                             long long n_recv, const long long* recv_idx, const long long* recv_splits) {
-  MG_CF64_UNSUPPORTED(h);
-  UploadFence upload_fence;
-  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
-  mg_ghost* g = h->ghost;
-  if (level < 1 || level > g->a) return fail(MG_ERR_INVALID, "bad level %lld", level);
-  if (!ext || !own_lo || !own_hi || !send_splits || !recv_splits || (n_send > 0 && !send_idx) || (n_recv > 0 && !recv_idx) || n_send < 0 || n_recv < 0 || gmin < 1)
-    return fail(MG_ERR_INVALID, "bad ghost-level arrays");
-  (void)hipSetDevice(h->device);
-  GhostLevel& L = g->lev[(size_t)level - 1];
-  long long n = 1;
-  for (int k = 0; k < 3; ++k) {
-    if (ext[k] < 1 || own_lo[k] < 0 || own_hi[k] <= own_lo[k] || own_hi[k] > ext[k]) return fail(MG_ERR_INVALID, "ghost level %lld: bad boxes", level);
-    L.ext[k] = (int)ext[k]; L.lo[k] = (int)own_lo[k]; L.hi[k] = (int)own_hi[k];
-    n *= ext[k];
-  }
-  if (n != h->lev[(size_t)level - 1].A.n_rows && h->lev[(size_t)level - 1].A.set)
-    return fail(MG_ERR_INVALID, "ghost level %lld: the extended box has %lld nodes, As[%lld] %lld rows", level, n, level, h->lev[(size_t)level - 1].A.n_rows);
-  L.n = n;
-  L.gmin = (int)std::min<long long>(gmin, GH_FULL);
-  L.n_send = n_send;
-  L.n_recv = n_recv;
-  L.send_splits.assign(send_splits, send_splits + g->world);
-  L.recv_splits.assign(recv_splits, recv_splits + g->world);
-  long long ss = 0, rs = 0;
-  for (int q = 0; q < g->world; ++q) { ss += L.send_splits[(size_t)q]; rs += L.recv_splits[(size_t)q]; }
-  if (ss != n_send || rs != n_recv) return fail(MG_ERR_INVALID, "ghost plan: splits do not add up (send %lld/%lld, recv %lld/%lld)", ss, n_send, rs, n_recv);
-  auto in_own = [&](long long id) {
-    const long long x = id % L.ext[0], y = (id / L.ext[0]) % L.ext[1], z = id / ((long long)L.ext[0] * L.ext[1]);
-    return x >= L.lo[0] && x < L.hi[0] && y >= L.lo[1] && y < L.hi[1] && z >= L.lo[2] && z < L.hi[2];
-  };
-  std::vector<int> si((size_t)std::max<long long>(n_send, 1), 0), ri((size_t)std::max<long long>(n_recv, 1), 0);
-  for (long long i = 0; i < n_send; ++i) {
-    if (send_idx[i] < 0 || send_idx[i] >= n || !in_own(send_idx[i])) return fail(MG_ERR_INVALID, "ghost plan: a send index is not an owned node");
-    si[(size_t)i] = (int)send_idx[i];
-  }
-  for (long long i = 0; i < n_recv; ++i) {
-    if (recv_idx[i] < 0 || recv_idx[i] >= n || in_own(recv_idx[i])) return fail(MG_ERR_INVALID, "ghost plan: a receive index is not a ghost node");
-    ri[(size_t)i] = (int)recv_idx[i];
-  }
-  MG_TRY(L.send_idx.alloc(si.size()));
-  MG_TRY(L.recv_idx.alloc(ri.size()));
-  MG_TRY(L.send_buf.alloc(si.size()));
-  MG_TRY(L.recv_buf.alloc(ri.size()));
-  MG_TRY(L.send_buf2.alloc(si.size()));
-  MG_TRY(L.recv_buf2.alloc(ri.size()));
-  HIP_TRY(hipMemcpy(L.send_idx.p, si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(L.recv_idx.p, ri.data(), ri.size() * sizeof(int), hipMemcpyHostToDevice));
-  if (L.h_send) (void)hipHostFree(L.h_send);
-  if (L.h_recv) (void)hipHostFree(L.h_recv);
-  L.h_send = L.h_recv = nullptr;
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&L.h_send), sizeof(double) * si.size()));
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&L.h_recv), sizeof(double) * ri.size()));
-  if (!L.ev_packed) HIP_TRY(hipEventCreateWithFlags(&L.ev_packed, hipEventDisableTiming));
-  if (!L.ev_landed) HIP_TRY(hipEventCreateWithFlags(&L.ev_landed, hipEventDisableTiming));
-  L.set = true;
-  g->finalized = false;
-  return MG_OK;
-}
-
-int mg_ghost_finalize(mg_hierarchy* h) {
-  MG_CF64_UNSUPPORTED(h);
-  UploadFence upload_fence;
-  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
-  if (!h->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
-  mg_ghost* g = h->ghost;
-  (void)hipSetDevice(h->device);
-  graphs_clear(h);
-  if (g->world > 1 && !g->comm && !g->plug && !g->dry) return fail(MG_ERR_STATE, "no transport: pass an RCCL unique id to mg_ghost_attach or set an exchange plug-in");
-  for (int l = 0; l < g->a; ++l) {
-    GhostLevel& L = g->lev[(size_t)l];
-    if (!L.set) return fail(MG_ERR_STATE, "ghost level %d was not set", l + 1);
-    if (L.n != h->lev[(size_t)l].n) return fail(MG_ERR_INVALID, "ghost level %d: the extended box has %lld nodes, the level %lld rows", l + 1, L.n, h->lev[(size_t)l].n);
-    L.active = g->world > 1;     // (every box of a partition into more than one has a neighbour)
-    L.depth.clear();
-    L.pending = nullptr;
-  }
-  MG_TRY(g->b0.alloc((size_t)g->lev[0].n));
-  HIP_TRY(hipMemset(g->b0.p, 0, g->b0.bytes()));
-  // ---- what EVERY rank's kernels can do (see mg_ghost): one all-reduce of 0/1 flags, a capability is kept where the sum is `world` ----
-  {
-    const int a = g->a;
-    std::vector<double> flags((size_t)(1 + 3 * a), 0.0), sums;
-    {
-      Level& L0 = h->lev[0];
-      flags[0] = (h->nrhs >= 1 && march4_ok_static(h, 0)) ? 1.0 : 0.0;
-      for (int l = 0; l < a; ++l) {
-        Level& L = h->lev[(size_t)l];
-        const bool m2 = march2_ok_static(h, l);
-        flags[(size_t)(1 + 3 * l)] = m2 ? 1.0 : 0.0;
-        flags[(size_t)(2 + 3 * l)] = (m2 && zero_form_static(L.A)) ? 1.0 : 0.0;
-        flags[(size_t)(3 + 3 * l)] = restrict_can_scale_static(h, L.R) ? 1.0 : 0.0;
-      }
-      (void)L0;
-    }
-    sums = flags;
-    if (g->world > 1 && !g->dry) {
-      const size_t cnt = flags.size();
-      if (g->comm) {
-        DevBuf<double> tmp;
-        MG_TRY(tmp.alloc(cnt));
-        HIP_TRY(hipMemcpy(tmp.p, flags.data(), cnt * sizeof(double), hipMemcpyHostToDevice));
-        NCCL_TRY(g_rccl.AllReduce(tmp.p, tmp.p, cnt, NCCL_DOUBLE, NCCL_SUM, g->comm, h->stream));
-        HIP_TRY(spin_sync(h->stream));
-        HIP_TRY(hipMemcpy(sums.data(), tmp.p, cnt * sizeof(double), hipMemcpyDeviceToHost));
-        tmp.release();
-      } else if (g->plug(g->plug_user, 1, flags.data(), nullptr, sums.data(), nullptr, (long long)cnt) != 0) {
-        return fail(MG_ERR_HIP, "exchange plug-in failed (all_reduce of the ranks' kernel capabilities)");
-      }
-    } else {
-      for (double& v : sums) v *= (double)((g->world > 1 && !g->dry) ? 1 : g->world);
-    }
-    auto all = [&](size_t i) { return sums[i] > (double)g->world - 0.5; };
-    g->agree4 = all(0);
-    g->agree2.assign((size_t)a, 1);
-    g->agree_zero.assign((size_t)a, 1);
-    g->agree_scale.assign((size_t)a, 1);
-    for (int l = 0; l < a; ++l) {
-      g->agree2[(size_t)l] = all((size_t)(1 + 3 * l)) ? 1 : 0;
-      g->agree_zero[(size_t)l] = all((size_t)(2 + 3 * l)) ? 1 : 0;
-      g->agree_scale[(size_t)l] = all((size_t)(3 + 3 * l)) ? 1 : 0;
-    }
-  }
-  g->finalized = true;
-  if (h->nrhs != 1 && !columns_ok(h))    // (every rank sees the same agreed flags: all of them fail here, or none)
-    return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: a block of right-hand sides is solved column by column, which needs: %s", columns_why_not(h));
-  return MG_OK;
-}
-
-// Timing aid (bench.py --ghost-dry R/N): this process is rank R of a world of N ALONE on its GPU - every exchange runs its pack and
-// unpack kernels, nothing travels, sums stay local.  The numbers such a handle computes mean nothing; its step time is what one
-// GPU of the N spends on compute, redundant ghost rows included (the ceiling of the strong scaling with free communication).
-int mg_ghost_set_dry(mg_hierarchy* h, long long on) {
-  MG_CF64_UNSUPPORTED(h);
-  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
-  if (h->ghost->comm) return fail(MG_ERR_STATE, "this handle was attached with an RCCL communicator");
-  h->ghost->dry = on != 0;
-  return MG_OK;
-}
-// exchanges started and doubles sent by this rank since mg_ghost_attach (what the schedule really communicates)
-int mg_ghost_stats(mg_hierarchy* h, long long* exchanges, long long* doubles_sent) {
-  MG_CF64_UNSUPPORTED(h);
-  if (!h || !h->ghost) return fail(MG_ERR_INVALID, "mg_ghost_attach was not called");
-  if (exchanges) *exchanges = h->ghost->n_exchanges;
-  if (doubles_sent) *doubles_sent = h->ghost->n_sent;
-  return MG_OK;
-}
-int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count) {
-  MG_CF64_UNSUPPORTED(h);
-  if (!h || !h->ghost || !count) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
-  *count = h->ghost->n_allreduce;
-  return MG_OK;
-}
-// Ranks of this handle's communicator AS RCCL REPORTS THEM (ncclCommCount); 0 with the plug-in transport / a world of one without RCCL.
-int mg_ghost_comm_count(mg_hierarchy* h, long long* count) {
-  MG_CF64_UNSUPPORTED(h);
-  if (!h || !h->ghost || !count) return fail(MG_ERR_INVALID, "null argument or mg_ghost_attach was not called");
-  *count = 0;
-  if (!h->ghost->comm) return MG_OK;
-  if (!g_rccl.CommCount) return fail(MG_ERR_UNSUPPORTED, "this librccl has no ncclCommCount");
-  int c = 0;
-  NCCL_TRY(g_rccl.CommCount(h->ghost->comm, &c));
-  *count = c;
   return MG_OK;
 }
 

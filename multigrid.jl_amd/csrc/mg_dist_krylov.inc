@@ -93,7 +93,7 @@ struct DistKry {
     if (K.part.n == 0) {
       MG_TRY(K.part.alloc((size_t)2 * mgkv::MAXS * mgkv::MAXB));
       MG_TRY(K.scal.alloc((size_t)mgkv::MAXS));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&K.h_scal), sizeof(double) * 2 * mgkv::MAXS));
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&K.h_scal), sizeof(double) * mgkv::MAXS));
     }
     if (K.vec.n < doubles) MG_TRY(K.vec.alloc(doubles));
     return MG_OK;
@@ -109,18 +109,8 @@ struct DistKry {
   }
   // the first `count` scalars summed over all ranks, on the host: one all-reduce, one read-back
   int reduce(int count, const double** out) {
-    if (h->comm) {
-      NCCL_TRY(g_rccl.AllReduce(K.scal.p, K.scal.p, (size_t)count, NCCL_DOUBLE, NCCL_SUM, h->comm, h->stream));
-      ++h->n_allreduce;
-    }
-    HIP_TRY(hipMemcpyAsync(K.h_scal, K.scal.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(spin_sync(h->stream));
+    MG_TRY(h->T.allreduce_now(K.scal.p, (size_t)count, K.h_scal, h->stream));
     *out = K.h_scal;
-    if (!h->comm && h->world > 1) {
-      if (h->plug(h->plug_user, 1, K.h_scal, nullptr, K.h_scal + mgkv::MAXS, nullptr, count) != 0) return fail(MG_ERR_HIP, "exchange plug-in failed (all_reduce)");
-      ++h->n_allreduce;
-      *out = K.h_scal + mgkv::MAXS;
-    }
     return MG_OK;
   }
   int copy(double* dst, const double* src) {
@@ -432,8 +422,8 @@ int mg_dist_fgmres_dev_FP64(mg_dist* h, const double* b_loc, double* x_loc, long
 // halo exchanges started and all-reduces entered by this rank since mg_dist_create (what the schedule really communicates)
 int mg_dist_stats(mg_dist* h, long long* exchanges, long long* allreduces) {
   if (!h) return fail(MG_ERR_INVALID, "null handle");
-  if (exchanges) *exchanges = h->n_exchanges;
-  if (allreduces) *allreduces = h->n_allreduce;
+  if (exchanges) *exchanges = h->T.n_exchanges;
+  if (allreduces) *allreduces = h->T.n_allreduce;
   return MG_OK;
 }
 

@@ -1,61 +1,9 @@
 // mg_ghost.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // Sharded cycle with deep ghost layers (mg_ghost_*): a rank's hierarchy is an ordinary mg_hierarchy on its box EXTENDED by ghost
-// layers; this part owns the exchange of those layers (RCCL send/recv on a side stream, or a host-staged plug-in), the validity
+// layers; this part owns the exchange of those layers (packing, streams and events; the wire is mg_transport.inc), the validity
 // bookkeeping that decides when an exchange is due, the all-reduce into the first replicated level and the global norms.
 // Reference: the `overlap` of src/DomainDecomposition/DDIndices.jl:61-92 (box rule l.41-47), fan-out DDParallel.jl:87-105,133-139.
 namespace {
-// RCCL is loaded lazily (dlopen) so that single-GPU users of the library do not depend on it.
-// Prototypes, handle types and enumerators come from the RCCL header this library is built against (rccl/rccl.h):
-// decltype(&ncclSend) etc. - if the ABI moves, the build follows it or fails, it cannot go silently wrong.
-struct Rccl {
-  typedef ncclUniqueId UniqueId;
-  void* lib = nullptr;
-  decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-  decltype(&ncclCommInitRank) CommInitRank = nullptr;
-  decltype(&ncclCommDestroy) CommDestroy = nullptr;
-  decltype(&ncclCommCount) CommCount = nullptr;
-  decltype(&ncclGroupStart) GroupStart = nullptr;
-  decltype(&ncclGroupEnd) GroupEnd = nullptr;
-  decltype(&ncclSend) Send = nullptr;
-  decltype(&ncclRecv) Recv = nullptr;
-  decltype(&ncclAllReduce) AllReduce = nullptr;
-  decltype(&ncclAllGather) AllGather = nullptr;
-  decltype(&ncclGetErrorString) GetErrorString = nullptr;
-  bool load() {
-    if (lib) return true;
-    for (const char* name : {"librccl.so.1", "librccl.so"}) {
-      lib = dlopen(name, RTLD_NOW | RTLD_NOLOAD);          // the copy torch already mapped, if any
-      if (!lib) lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-      if (lib) break;
-    }
-    if (!lib) return false;
-    auto sym = [&](const char* n) { return dlsym(lib, n); };
-    GetUniqueId = reinterpret_cast<decltype(GetUniqueId)>(sym("ncclGetUniqueId"));
-    CommInitRank = reinterpret_cast<decltype(CommInitRank)>(sym("ncclCommInitRank"));
-    CommDestroy = reinterpret_cast<decltype(CommDestroy)>(sym("ncclCommDestroy"));
-    CommCount = reinterpret_cast<decltype(CommCount)>(sym("ncclCommCount"));
-    GroupStart = reinterpret_cast<decltype(GroupStart)>(sym("ncclGroupStart"));
-    GroupEnd = reinterpret_cast<decltype(GroupEnd)>(sym("ncclGroupEnd"));
-    Send = reinterpret_cast<decltype(Send)>(sym("ncclSend"));
-    Recv = reinterpret_cast<decltype(Recv)>(sym("ncclRecv"));
-    AllReduce = reinterpret_cast<decltype(AllReduce)>(sym("ncclAllReduce"));
-    AllGather = reinterpret_cast<decltype(AllGather)>(sym("ncclAllGather"));
-    GetErrorString = reinterpret_cast<decltype(GetErrorString)>(sym("ncclGetErrorString"));
-    return GetUniqueId && CommInitRank && CommDestroy && GroupStart && GroupEnd && Send && Recv && AllReduce && AllGather;
-  }
-};
-Rccl g_rccl;
-constexpr ncclDataType_t NCCL_DOUBLE = ncclFloat64;
-constexpr ncclRedOp_t NCCL_SUM = ncclSum;
-static_assert(sizeof(ncclUniqueId) == 128, "mg_dist_unique_id / mg_dist_create exchange the RCCL id as 128 bytes");
-static_assert(ncclFloat64 == 8 && ncclSum == 0, "RCCL enumerators moved: check the glue in INTEGRATION.md");
-
-int dist_nccl(ncclResult_t rc, const char* what) {
-  if (rc == ncclSuccess) return MG_OK;
-  return fail(MG_ERR_HIP, "%s failed: %s", what, g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error");
-}
-#define NCCL_TRY(expr) MG_TRY(dist_nccl((expr), #expr))
-
 constexpr int GH_FULL = 1 << 20;   // validity depth of a vector whose every ghost layer is up to date
 
 struct GhostLevel {
@@ -66,36 +14,25 @@ struct GhostLevel {
   DevBuf<int> send_idx, recv_idx;
   DevBuf<double> send_buf, recv_buf, send_buf2, recv_buf2;   // (…2: the second vector of a two-vector exchange)
   std::vector<long long> send_splits, recv_splits;
-  double *h_send = nullptr, *h_recv = nullptr;       // pinned staging (plug-in transport)
   const double* pending2 = nullptr;                  // second vector of the exchange in flight
   hipEvent_t ev_packed = nullptr, ev_landed = nullptr;
   std::vector<std::pair<const double*, int>> depth;  // validity depth of the level's vectors (by address)
   const double* pending = nullptr;                   // vector whose ghost layers are in flight on the side stream
   DevBuf<double> send_blk, recv_blk;                 // a BLOCK's ghost layers (row-major [n][k]; the sharded block Krylov drivers)
-  double *h_send_blk = nullptr, *h_recv_blk = nullptr;
-  size_t h_blk_n = 0;
 };
 }  // namespace
 
 struct mg_ghost {
-  int rank = 0, world = 1, a = 0;       // a: sharded levels (0 .. a-1 live on extended boxes, a .. are replicated)
-  ncclComm_t comm = nullptr;            // RCCL transport: the collectives on the compute stream (all-reduces)
-  ncclComm_t comm_side = nullptr;       // ... and a second communicator for the ghost-layer send / recv on the side stream: operations on ONE
-                                        // communicator are serialised in issue order whatever their streams - the fine level's exchange would then sit
-                                        // in front of the next all-reduce instead of beside the coarse cycle (optional: mg_ghost_set_side_comm)
-  mg_exchange_fn plug = nullptr;        // host-staged transport (tests / ranks sharing one GPU)
-  void* plug_user = nullptr;
+  int a = 0;                            // sharded levels (0 .. a-1 live on extended boxes, a .. are replicated)
+  Transport T;                          // all-reduces on its communicator, the ghost-layer send / recv of the side stream on its side communicator: the
+                                        // fine level's exchange would else sit in front of the next all-reduce instead of beside the coarse cycle
   hipStream_t side = nullptr;
   std::vector<GhostLevel> lev;
   DevBuf<double> b0;                    // the fine right-hand side with its ghost layers (the caller's b is read-only)
-  double* h_red = nullptr;              // pinned: staging of the plug-in's all-reduce into the first replicated level
-  size_t h_red_n = 0;
   double* h_norm = nullptr;             // pinned scalar of gh_norm_own
-  long long n_exchanges = 0, n_sent = 0, n_allreduce = 0;
   DevBuf<double> kscal;                 // scalars of the sharded Krylov drivers (gh_dots_own), all-reduced in place
   double* h_kscal = nullptr;            // ... and their pinned mirror
   bool finalized = false;
-  bool dry = false;                     // timing aid: one rank of a larger world alone on its GPU - pack / unpack kernels run, nothing travels
   // What the kernels of a level can do decides where exchanges happen, and EVERY rank must take the same decisions (a collective is
   // entered by all or none): the boxes of two ranks differ by a line or two, so a format builder may serve one and not the other.
   // mg_ghost_finalize adds the ranks' 0/1 flags up (one all-reduce) and keeps a capability only where all `world` ranks have it.
@@ -119,7 +56,7 @@ void gh_own_box(const mg_hierarchy* h, int level, int* xl, int* xh, int* yl, int
   *xl = L->lo[0]; *xh = L->hi[0]; *yl = L->lo[1]; *yh = L->hi[1]; *zl = L->lo[2]; *zh = L->hi[2];
 }
 // norms are sums over several ranks (or go through RCCL at a world of one, as the sharded bench does)
-bool gh_global_scalars(const mg_hierarchy* h) { return h->ghost && h->ghost->finalized && (h->ghost->world > 1 || h->ghost->comm); }
+bool gh_global_scalars(const mg_hierarchy* h) { return h->ghost && h->ghost->finalized && h->ghost->T.sharded(); }
 inline bool gh_agree2(const mg_hierarchy* h, int l) { return !h->ghost || !h->ghost->finalized || l >= h->ghost->a || h->ghost->agree2[(size_t)l]; }
 inline bool gh_agree_zero(const mg_hierarchy* h, int l) { return !h->ghost || !h->ghost->finalized || l >= h->ghost->a || h->ghost->agree_zero[(size_t)l]; }
 inline bool gh_agree_scale(const mg_hierarchy* h, int l) { return !h->ghost || !h->ghost->finalized || l >= h->ghost->a || h->ghost->agree_scale[(size_t)l]; }
@@ -161,7 +98,7 @@ int gh_check_depths(const mg_hierarchy* h) {
 int gh_exchange_finish(mg_hierarchy* h, int l) {
   GhostLevel* L = gh_level(h, l);
   if (!L || !L->pending) return MG_OK;
-  if (h->ghost->comm) HIP_TRY(hipStreamWaitEvent(h->stream, L->ev_landed, 0));
+  HIP_TRY(hipStreamWaitEvent(h->stream, L->ev_landed, 0));   // (pending: the exchange went over the side stream)
   L->pending = nullptr;
   L->pending2 = nullptr;
   return MG_OK;
@@ -192,53 +129,23 @@ int gh_exchange_start(mg_hierarchy* h, int l, double* v, double* v2 = nullptr, b
     else hipLaunchKernelGGL(mgk::ghost_pack, dim3(nbs), dim3(mgk::BLK), 0, h->stream, v, L->send_idx.p, L->send_buf.p, L->n_send);
   }
   HIP_TRY(hipGetLastError());
-  ++g->n_exchanges;
-  g->n_sent += L->n_send * (v2 ? 2 : 1);
-  if (g->comm) {
-    hipStream_t xs = side ? g->side : h->stream;
-    if (side) {
-      HIP_TRY(hipEventRecord(L->ev_packed, h->stream));
-      HIP_TRY(hipStreamWaitEvent(g->side, L->ev_packed, 0));
-    }
-    ncclComm_t cs = (side && g->comm_side) ? g->comm_side : g->comm;
-    NCCL_TRY(g_rccl.GroupStart());
-    long long so = 0, ro = 0;
-    for (int peer = 0; peer < g->world; ++peer) {
-      const long long ns = L->send_splits[(size_t)peer], nr = L->recv_splits[(size_t)peer];
-      if (ns > 0) NCCL_TRY(g_rccl.Send(L->send_buf.p + so, (size_t)ns, NCCL_DOUBLE, peer, cs, xs));
-      if (nr > 0) NCCL_TRY(g_rccl.Recv(L->recv_buf.p + ro, (size_t)nr, NCCL_DOUBLE, peer, cs, xs));
-      if (v2 && ns > 0) NCCL_TRY(g_rccl.Send(L->send_buf2.p + so, (size_t)ns, NCCL_DOUBLE, peer, cs, xs));
-      if (v2 && nr > 0) NCCL_TRY(g_rccl.Recv(L->recv_buf2.p + ro, (size_t)nr, NCCL_DOUBLE, peer, cs, xs));
-      so += ns;
-      ro += nr;
-    }
-    NCCL_TRY(g_rccl.GroupEnd());
-    unpack(xs);
-    HIP_TRY(hipGetLastError());
-    if (side) {
-      HIP_TRY(hipEventRecord(L->ev_landed, g->side));
-      L->pending = v;
-      L->pending2 = v2;
-    }
-  } else if (g->dry) {
-    // (nothing travels: pack and unpack on the compute stream.  Measured, round 6: the unpack of the fine level's prefetch on the side
-    // stream - the RCCL transport's structure - costs the dry rank 26 us MORE than the 19 us of kernel time it moves out of the way:
-    // 0.5693 against 0.543 ms per step; with a wire to wait for the hop pays, without one it does not.)
-    unpack(h->stream);
-    HIP_TRY(hipGetLastError());
-  } else {
-    for (int pass = 0; pass < (v2 ? 2 : 1); ++pass) {   // (host-staged transport: one all_to_all per vector)
-      double* sb = pass ? L->send_buf2.p : L->send_buf.p;
-      double* rb = pass ? L->recv_buf2.p : L->recv_buf.p;
-      if (L->n_send > 0) HIP_TRY(hipMemcpyAsync(L->h_send, sb, sizeof(double) * (size_t)L->n_send, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(spin_sync(h->stream));
-      if (g->plug(g->plug_user, 0, L->h_send, L->send_splits.data(), L->h_recv, L->recv_splits.data(), 0) != 0)
-        return fail(MG_ERR_HIP, "exchange plug-in failed (all_to_all)");
-      if (L->n_recv > 0) HIP_TRY(hipMemcpyAsync(rb, L->h_recv, sizeof(double) * (size_t)L->n_recv, hipMemcpyHostToDevice, h->stream));
-      if (pass + 1 < (v2 ? 2 : 1)) HIP_TRY(spin_sync(h->stream));   // (the pinned buffers are reused by the second vector)
-    }
-    unpack(h->stream);
-    HIP_TRY(hipGetLastError());
+  // (the hop needs a wire to wait for.  Dry, nothing travels: pack and unpack on the compute stream.  Measured, round 6: the unpack of the
+  // fine level's prefetch on the side stream - the RCCL transport's structure - costs the dry rank 26 us MORE than the 19 us of kernel time it
+  // moves out of the way: 0.5693 against 0.543 ms per step; with a wire to wait for the hop pays, without one it does not.)
+  const bool hop = side && g->T.on_stream();
+  hipStream_t xs = hop ? g->side : h->stream;
+  if (hop) {
+    HIP_TRY(hipEventRecord(L->ev_packed, h->stream));
+    HIP_TRY(hipStreamWaitEvent(g->side, L->ev_packed, 0));
+  }
+  const Transport::Pair pairs[2] = {{L->send_buf.p, L->recv_buf.p}, {L->send_buf2.p, L->recv_buf2.p}};
+  MG_TRY(g->T.exchange(pairs, v2 ? 2 : 1, L->send_splits, L->recv_splits, 1, xs, /*side_comm=*/hop));
+  unpack(xs);
+  HIP_TRY(hipGetLastError());
+  if (hop) {
+    HIP_TRY(hipEventRecord(L->ev_landed, g->side));
+    L->pending = v;
+    L->pending2 = v2;
   }
   gh_set(h, l, v, GH_FULL);
   if (v2) gh_set(h, l, v2, GH_FULL);
@@ -273,47 +180,14 @@ int gh_prefetch(mg_hierarchy* h, int l, double* v, int want) {
 int gh_allreduce_tail(mg_hierarchy* h, double* v, long long n) {
   mg_ghost* g = h->ghost;
   if (!g || !g->finalized) return MG_OK;
-  if (g->comm) {
-    if (h->capturing) return fail(MG_ERR_STATE, "an all-reduce inside a graph capture");
-    NCCL_TRY(g_rccl.AllReduce(v, v, (size_t)n, NCCL_DOUBLE, NCCL_SUM, g->comm, h->stream));
-    ++g->n_allreduce;
-    return MG_OK;
-  }
-  if (g->world <= 1 || g->dry) return MG_OK;
-  ++g->n_allreduce;
-  if (g->h_red_n < (size_t)(2 * n)) {
-    if (g->h_red) (void)hipHostFree(g->h_red);
-    g->h_red = nullptr;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&g->h_red), sizeof(double) * (size_t)(2 * n)));
-    g->h_red_n = (size_t)(2 * n);
-  }
-  HIP_TRY(hipMemcpyAsync(g->h_red, v, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
-  if (g->plug(g->plug_user, 1, g->h_red, nullptr, g->h_red + n, nullptr, n) != 0) return fail(MG_ERR_HIP, "exchange plug-in failed (all_reduce)");
-  HIP_TRY(hipMemcpyAsync(v, g->h_red + n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  return MG_OK;
+  if (h->capturing && g->T.on_stream()) return fail(MG_ERR_STATE, "an all-reduce inside a graph capture");
+  return g->T.allreduce_dev(v, (size_t)n, h->stream);
 }
 // ---- global norms ------------------------------------------------------------------------------------------------------------------
 // h->scalar holds this rank's sum of squares over its OWNED rows: all-reduce it on the stream (RCCL) and copy it into `slot` (pinned);
 // with the plug-in the slot receives the local sum and gh_host_reduce adds the ranks' sums when the host reads it.
-int gh_scalar_to_slot(mg_hierarchy* h, double* slot) {
-  mg_ghost* g = h->ghost;
-  if (g && g->comm) {
-    NCCL_TRY(g_rccl.AllReduce(h->scalar.p, h->scalar.p, 1, NCCL_DOUBLE, NCCL_SUM, g->comm, h->stream));
-    ++g->n_allreduce;
-  }
-  HIP_TRY(hipMemcpyAsync(slot, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  return MG_OK;
-}
-int gh_host_reduce(mg_hierarchy* h, double* slot) {
-  mg_ghost* g = h->ghost;
-  if (!g || g->comm || g->world <= 1 || g->dry) return MG_OK;
-  double in = *slot, out = 0.0;
-  if (g->plug(g->plug_user, 1, &in, nullptr, &out, nullptr, 1) != 0) return fail(MG_ERR_HIP, "exchange plug-in failed (all_reduce)");
-  ++g->n_allreduce;
-  *slot = out;
-  return MG_OK;
-}
+int gh_scalar_to_slot(mg_hierarchy* h, double* slot) { return h->ghost->T.allreduce_start(h->scalar.p, 1, slot, h->stream); }
+int gh_host_reduce(mg_hierarchy* h, double* slot) { return h->ghost ? h->ghost->T.allreduce_finish(slot, 1) : MG_OK; }
 // enqueue: *slot (pinned) <- sum of squares of v over the owned rows [of every rank: RCCL; with the plug-in the local sum, to be passed
 // through gh_host_reduce once the stream has drained]
 int gh_sumsq_own_to_slot(mg_hierarchy* h, const double* v, double* slot) {
@@ -347,7 +221,7 @@ int gh_dots_own(mg_hierarchy* h, int count, const double* const* xs, const doubl
   if (count < 1 || count > 8) return fail(MG_ERR_INVALID, "gh_dots_own: 1 to 8 scalars");
   if (level < 0 || level >= g->a) return fail(MG_ERR_INVALID, "gh_dots_own: level %d is not sharded", level + 1);
   if (g->kscal.n < 8) MG_TRY(g->kscal.alloc(8));
-  if (!g->h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&g->h_kscal), 16 * sizeof(double)));
+  if (!g->h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&g->h_kscal), 8 * sizeof(double)));
   const GhostLevel& L = g->lev[(size_t)level];
   mgk::BoxDev B;
   B.n1 = L.ext[0]; B.n2 = L.ext[1]; B.n3 = L.ext[2];
@@ -359,19 +233,8 @@ int gh_dots_own(mg_hierarchy* h, int count, const double* const* xs, const doubl
     hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p + (size_t)c * nb, nb, g->kscal.p + c);
   }
   HIP_TRY(hipGetLastError());
-  if (g->comm) {
-    NCCL_TRY(g_rccl.AllReduce(g->kscal.p, g->kscal.p, (size_t)count, NCCL_DOUBLE, NCCL_SUM, g->comm, h->stream));
-    ++g->n_allreduce;
-  }
-  HIP_TRY(hipMemcpyAsync(g->h_kscal, g->kscal.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
-  if (!g->comm && g->world > 1 && !g->dry) {
-    if (g->plug(g->plug_user, 1, g->h_kscal, nullptr, g->h_kscal + 8, nullptr, count) != 0) return fail(MG_ERR_HIP, "exchange plug-in failed (all_reduce)");
-    ++g->n_allreduce;
-    for (int c = 0; c < count; ++c) out[c] = g->h_kscal[8 + c];
-  } else {
-    for (int c = 0; c < count; ++c) out[c] = g->h_kscal[c];
-  }
+  MG_TRY(g->T.allreduce_now(g->kscal.p, (size_t)count, g->h_kscal, h->stream));
+  for (int c = 0; c < count; ++c) out[c] = g->h_kscal[c];
   return MG_OK;
 }
 // ---- blocks of right-hand sides (sharded block Krylov drivers: blockCG / blockBiCGSTB / blockFGMRES, SolveFuncs.jl:95,113,130) -----------
@@ -389,37 +252,8 @@ int gh_exchange_block(mg_hierarchy* h, double* V, int k) {
   if (L->n_send > 0)
     hipLaunchKernelGGL(mgk::ghost_pack_block, dim3((unsigned)((L->n_send * k + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, h->stream, V, L->send_idx.p, L->send_blk.p, L->n_send, k);
   HIP_TRY(hipGetLastError());
-  ++g->n_exchanges;
-  g->n_sent += L->n_send * k;
-  if (g->comm) {
-    NCCL_TRY(g_rccl.GroupStart());
-    long long so = 0, ro = 0;
-    for (int peer = 0; peer < g->world; ++peer) {
-      const long long a = L->send_splits[(size_t)peer], b = L->recv_splits[(size_t)peer];
-      if (a > 0) NCCL_TRY(g_rccl.Send(L->send_blk.p + so * k, (size_t)(a * k), NCCL_DOUBLE, peer, g->comm, h->stream));
-      if (b > 0) NCCL_TRY(g_rccl.Recv(L->recv_blk.p + ro * k, (size_t)(b * k), NCCL_DOUBLE, peer, g->comm, h->stream));
-      so += a;
-      ro += b;
-    }
-    NCCL_TRY(g_rccl.GroupEnd());
-  } else if (!g->dry) {
-    const size_t need = std::max(ns, nr);
-    if (L->h_blk_n < need) {
-      if (L->h_send_blk) (void)hipHostFree(L->h_send_blk);
-      if (L->h_recv_blk) (void)hipHostFree(L->h_recv_blk);
-      L->h_send_blk = L->h_recv_blk = nullptr;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&L->h_send_blk), sizeof(double) * need));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&L->h_recv_blk), sizeof(double) * need));
-      L->h_blk_n = need;
-    }
-    std::vector<long long> ss(L->send_splits), rs(L->recv_splits);
-    for (auto& v : ss) v *= k;
-    for (auto& v : rs) v *= k;
-    if (L->n_send > 0) HIP_TRY(hipMemcpyAsync(L->h_send_blk, L->send_blk.p, sizeof(double) * (size_t)(L->n_send * k), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(spin_sync(h->stream));
-    if (g->plug(g->plug_user, 0, L->h_send_blk, ss.data(), L->h_recv_blk, rs.data(), 0) != 0) return fail(MG_ERR_HIP, "exchange plug-in failed (all_to_all)");
-    if (L->n_recv > 0) HIP_TRY(hipMemcpyAsync(L->recv_blk.p, L->h_recv_blk, sizeof(double) * (size_t)(L->n_recv * k), hipMemcpyHostToDevice, h->stream));
-  }
+  const Transport::Pair pair = {L->send_blk.p, L->recv_blk.p};
+  MG_TRY(g->T.exchange(&pair, 1, L->send_splits, L->recv_splits, k, h->stream));
   if (L->n_recv > 0)
     hipLaunchKernelGGL(mgk::ghost_unpack_block, dim3((unsigned)((L->n_recv * k + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, h->stream, L->recv_blk.p, L->recv_idx.p, V, L->n_recv, k);
   HIP_TRY(hipGetLastError());
@@ -440,25 +274,9 @@ int gh_gram_own(mg_hierarchy* h, const double* X, const double* Y, int k, double
   hipLaunchKernelGGL(mgk::blk_gram_box_partial, dim3(nb, k), dim3(mgk::BLK), 0, h->stream, X, Y, B, k, partial.p);
   hipLaunchKernelGGL(mgk::blk_gram_final, dim3(1), dim3(mgk::BLK), 0, h->stream, partial.p, nb, k, out);
   HIP_TRY(hipGetLastError());
-  if (g->comm) {
-    NCCL_TRY(g_rccl.AllReduce(out, out, kk, NCCL_DOUBLE, NCCL_SUM, g->comm, h->stream));
-    ++g->n_allreduce;
-  }
-  if (g->h_red_n < 2 * kk) {
-    if (g->h_red) (void)hipHostFree(g->h_red);
-    g->h_red = nullptr;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&g->h_red), sizeof(double) * 2 * kk));
-    g->h_red_n = 2 * kk;
-  }
-  HIP_TRY(hipMemcpyAsync(g->h_red, out, sizeof(double) * kk, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
-  if (!g->comm && g->world > 1 && !g->dry) {
-    if (g->plug(g->plug_user, 1, g->h_red, nullptr, g->h_red + kk, nullptr, (long long)kk) != 0) return fail(MG_ERR_HIP, "exchange plug-in failed (all_reduce)");
-    ++g->n_allreduce;
-    std::memcpy(G, g->h_red + kk, sizeof(double) * kk);
-  } else {
-    std::memcpy(G, g->h_red, sizeof(double) * kk);
-  }
+  MG_TRY(g->T.stage(kk, h->stream));
+  MG_TRY(g->T.allreduce_now(out, kk, g->T.h_stage, h->stream));
+  std::memcpy(G, g->T.h_stage, sizeof(double) * kk);
   return MG_OK;
 }
 // every ghost layer of the fine-level vector v from its owners (v valid on the owned rows): what a product with A needs of its input
@@ -502,20 +320,14 @@ int gh_begin_block(mg_hierarchy* h) {
 void gh_release(mg_ghost* g) {
   if (!g) return;
   if (g->side) (void)spin_sync(g->side);
-  if (g->comm_side && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(g->comm_side);
-  if (g->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(g->comm);
+  g->T.release();
   for (GhostLevel& L : g->lev) {
     L.send_idx.release(); L.recv_idx.release(); L.send_buf.release(); L.recv_buf.release(); L.send_buf2.release(); L.recv_buf2.release();
     L.send_blk.release(); L.recv_blk.release();
-    if (L.h_send_blk) (void)hipHostFree(L.h_send_blk);
-    if (L.h_recv_blk) (void)hipHostFree(L.h_recv_blk);
-    if (L.h_send) (void)hipHostFree(L.h_send);
-    if (L.h_recv) (void)hipHostFree(L.h_recv);
     if (L.ev_packed) (void)hipEventDestroy(L.ev_packed);
     if (L.ev_landed) (void)hipEventDestroy(L.ev_landed);
   }
   g->b0.release();
-  if (g->h_red) (void)hipHostFree(g->h_red);
   if (g->h_norm) (void)hipHostFree(g->h_norm);
   if (g->h_kscal) (void)hipHostFree(g->h_kscal);
   g->kscal.release();

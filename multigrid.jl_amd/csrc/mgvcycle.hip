@@ -36,14 +36,15 @@
 #include "mg_krvec.hpp"
 
 
-// One translation unit, nine parts (round 4: the 6 800-line file split by responsibility; the order is the dependency order):
+// One translation unit in parts (the 6 800-line file split by responsibility; the order is the dependency order):
 #include "mg_types.inc"      // Options, DevBuf, Csr, Level, mg_hierarchy
 #include "mg_launch.inc"     // byte accounting, profiling slots, kernel launchers
+#include "mg_transport.inc"  // RCCL loader, host-staged plug-in: the collectives of both sharded forms
 #include "mg_ghost.inc"      // ghost-layer form of the sharded cycle: exchange, validity bookkeeping, global norms
 #include "mg_schedule.inc"   // FGMRES relaxation, cycle_level, HIP graphs, solve loop
 #include "mg_krylov.inc"     // PCG / BiCGSTAB / FGMRES and block variants
 #include "mg_formats.inc"    // upload, format builders, scratch
 #include "mg_complex.inc"    // ComplexF64 hierarchies: generic-CSR kernels' launchers, cycle, solve, and their extern "C" entry points
-#include "mg_cabi.inc"       // extern "C": the single-GPU API
-#include "mg_dist.inc"       // extern "C": the native multi-GPU sequencer
+#include "mg_cabi.inc"       // extern "C": the single-GPU API and its ghost-layer form (mg_ghost_*)
+#include "mg_dist.inc"       // extern "C": the native multi-GPU sequencer (halo form)
 #include "mg_dist_krylov.inc"   // extern "C": PCG / BiCGSTAB / FGMRES on the sharded halo form, their fused vector passes

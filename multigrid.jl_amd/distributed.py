@@ -29,6 +29,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import device as D
+from . import transport as T
 from .mgdef import MGparam
 
 
@@ -1070,14 +1071,7 @@ class NativeDistributedHierarchy:
         self.handle = C.c_void_p()
         uid = None
         if transport == "rccl":
-            buf = C.create_string_buffer(128)
-            if rank == 0:
-                D._check(lib, lib.mg_dist_unique_id(buf), "mg_dist_unique_id")
-            box = [buf.raw if rank == 0 else None]
-            if size > 1:
-                import torch.distributed as dist
-                dist.broadcast_object_list(box, src=0, group=getattr(comm, "group", None))
-            uid = C.create_string_buffer(box[0], 128)
+            uid, = T.rccl_unique_ids(lib, 1, rank, size, getattr(comm, "group", None))
         nl_sh = len(H.levels)
         D._check(lib, lib.mg_dist_create(H.be.device_id, rank, size, uid, nl_sh, H.nl, ord(H.cycleType), C.byref(self.handle)),
                  "mg_dist_create")
@@ -1086,7 +1080,8 @@ class NativeDistributedHierarchy:
             D._check(lib, lib.mg_dist_set_nrhs(self.handle, int(H.nrhs)), "mg_dist_set_nrhs")
         self._cb = None
         if uid is None and size > 1:
-            self._install_plugin(comm)
+            self._cb = T.exchange_callback(size, T.TorchCollectives(comm.group))
+            D._check(lib, lib.mg_dist_set_exchange_plugin(self.handle, C.cast(self._cb, C.c_void_p), None), "mg_dist_set_exchange_plugin")
         i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
         for l, L in enumerate(H.levels, start=1):
             hA_int = L.A_int.handle if L.A_int is not None else None
@@ -1106,42 +1101,6 @@ class NativeDistributedHierarchy:
         D._check(lib, lib.mg_dist_set_tail_INT64(self.handle, H.tail.h.handle, H.n_tail, H.own_tail, H.max_tail, D._i64(gi)),
                  "mg_dist_set_tail")
         D._check(lib, lib.mg_dist_finalize(self.handle), "mg_dist_finalize")
-
-    def _install_plugin(self, comm):
-        import ctypes as C
-        import torch
-        size = comm.size
-        dp, lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
-        FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_longlong, dp, lp, dp, lp, C.c_longlong)
-        dist = comm.dist
-
-        def cb(_user, op, send, send_splits, recv, recv_splits, count):
-            try:
-                if op == 0:
-                    ss = [int(send_splits[i]) for i in range(size)]
-                    rs = [int(recv_splits[i]) for i in range(size)]
-                    s_t = torch.from_numpy(np.ctypeslib.as_array(send, shape=(max(sum(ss), 1),))[: sum(ss)].copy())
-                    r_t = torch.zeros(sum(rs), dtype=torch.float64)
-                    dist.all_to_all_single(r_t, s_t, rs, ss, group=comm.group)
-                    if sum(rs):
-                        np.ctypeslib.as_array(recv, shape=(sum(rs),))[:] = r_t.numpy()
-                elif op == 1:
-                    t = torch.from_numpy(np.ctypeslib.as_array(send, shape=(int(count),)).copy())
-                    dist.all_reduce(t, group=comm.group)
-                    np.ctypeslib.as_array(recv, shape=(int(count),))[:] = t.numpy()
-                else:
-                    t = torch.from_numpy(np.ctypeslib.as_array(send, shape=(int(count),)).copy())
-                    o = torch.zeros(int(count) * size, dtype=torch.float64)
-                    dist.all_gather_into_tensor(o, t, group=comm.group)
-                    np.ctypeslib.as_array(recv, shape=(int(count) * size,))[:] = o.numpy()
-                return 0
-            except Exception as e:          # never unwind through the C frame
-                print("exchange plug-in error:", repr(e), flush=True)
-                return 1
-
-        self._cb = FN(cb)
-        D._check(self.lib, self.lib.mg_dist_set_exchange_plugin(self.handle, C.cast(self._cb, C.c_void_p), None),
-                 "mg_dist_set_exchange_plugin")
 
     def cycle(self, b_loc, x_loc, x_is_zero: bool):
         self.H.be.synchronize()       # the library enqueues on its own streams: whatever torch still has in flight for

@@ -13,7 +13,7 @@ box rule l.41-47; fan-out DDParallel.jl:87-105,133-139).  Here the overlap is wh
   valid on v - 1 layers (the outermost layer of an extended box holds rows cut off at the artificial boundary: they
   compute bounded garbage nobody reads with a non-zero weight).  The library keeps the validity depth of every level
   buffer and refreshes ALL ghost layers of a vector in ONE exchange where the next operation needs more than is left
-  (``mg_ghost_*``, csrc/mg_dist.inc): per V(2,1) step one exchange on the fine level - started right behind the
+  (``mg_ghost_*``, csrc/mg_ghost.inc and mg_cabi.inc): per V(2,1) step one exchange on the fine level - started right behind the
   four-stage pass and overlapped with the restriction and the whole coarse cycle - and two small ones per coarser
   sharded level (the restricted right-hand side on the way down, the correction on the way up), where the halo form
   (``distributed.py``) needs five to six per level;
@@ -394,6 +394,7 @@ class NativeGhostHierarchy:
     def __init__(self, G: GhostSetup, device_id: int = 0, transport: str = "rccl", group=None, options=None, collectives=None):
         import ctypes as C
         from . import device as D
+        from . import transport as T
         self.G = G
         self.D = D
         self.group = group
@@ -407,15 +408,7 @@ class NativeGhostHierarchy:
         rank, size = G.rank, G.size
         uid = uid2 = None
         if transport == "rccl":      # two communicators: collectives on the compute stream, ghost-layer send / recv on the side stream
-            buf, buf2 = C.create_string_buffer(128), C.create_string_buffer(128)
-            if rank == 0:
-                D._check(lib, lib.mg_dist_unique_id(buf), "mg_dist_unique_id")
-                D._check(lib, lib.mg_dist_unique_id(buf2), "mg_dist_unique_id")
-            box = [buf.raw if rank == 0 else None, buf2.raw if rank == 0 else None]
-            if size > 1:
-                import torch.distributed as dist
-                dist.broadcast_object_list(box, src=0, group=group)
-            uid, uid2 = C.create_string_buffer(box[0], 128), C.create_string_buffer(box[1], 128)
+            uid, uid2 = T.rccl_unique_ids(lib, 2, rank, size, group)
         D._check(lib, lib.mg_ghost_attach(h, rank, size, G.a, uid), "mg_ghost_attach")
         if uid2 is not None and os.environ.get("MG_GHOST_ONE_COMM", "0") != "1":      # (=1: send / receive share the first communicator)
             D._check(lib, lib.mg_ghost_set_side_comm(h, uid2), "mg_ghost_set_side_comm")
@@ -423,7 +416,8 @@ class NativeGhostHierarchy:
         if transport == "dry":
             D._check(lib, lib.mg_ghost_set_dry(h, 1), "mg_ghost_set_dry")
         elif uid is None and size > 1:
-            self._install_plugin()
+            self._cb = T.exchange_callback(size, collectives if collectives is not None else T.TorchCollectives(group))
+            D._check(lib, lib.mg_ghost_set_exchange_plugin(h, C.cast(self._cb, C.c_void_p), None), "mg_ghost_set_exchange_plugin")
         i64 = lambda v: np.ascontiguousarray(v, dtype=np.int64)
         for l, L in enumerate(G.levels, start=1):
             pad = lambda v: i64(list(v) + [1] * (3 - len(v)))
@@ -435,48 +429,6 @@ class NativeGhostHierarchy:
                                                        ri.size, D._i64(ri) if ri.size else None, D._i64(rs)),
                      "mg_ghost_set_level")
         D._check(lib, lib.mg_ghost_finalize(h), "mg_ghost_finalize")
-
-    def _install_plugin(self):
-        import ctypes as C
-        import torch
-        import torch.distributed as dist
-        size, group = self.G.size, self.group
-        dp, lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
-        FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_longlong, dp, lp, dp, lp, C.c_longlong)
-
-        class _TorchCollectives:
-            def all_to_all(self, send, ss, rs):
-                r_t = torch.zeros(sum(rs), dtype=torch.float64)
-                dist.all_to_all_single(r_t, torch.from_numpy(send), rs, ss, group=group)
-                return r_t.numpy()
-
-            def all_reduce(self, values):
-                t = torch.from_numpy(values)
-                dist.all_reduce(t, group=group)
-                return t.numpy()
-
-        coll = self.collectives if self.collectives is not None else _TorchCollectives()
-
-        def cb(_user, op, send, send_splits, recv, recv_splits, count):
-            try:
-                if op == 0:
-                    ss = [int(send_splits[i]) for i in range(size)]
-                    rs = [int(recv_splits[i]) for i in range(size)]
-                    out = coll.all_to_all(np.ctypeslib.as_array(send, shape=(max(sum(ss), 1),))[: sum(ss)].copy(), ss, rs)
-                    if sum(rs):
-                        np.ctypeslib.as_array(recv, shape=(sum(rs),))[:] = out
-                elif op == 1:
-                    np.ctypeslib.as_array(recv, shape=(int(count),))[:] = coll.all_reduce(np.ctypeslib.as_array(send, shape=(int(count),)).copy())
-                else:
-                    return 1
-                return 0
-            except Exception as e:          # never unwind through the C frame
-                print("exchange plug-in error:", repr(e), flush=True)
-                return 1
-
-        self._cb = FN(cb)
-        self.D._check(self.lib, self.lib.mg_ghost_set_exchange_plugin(self.dev.handle, C.cast(self._cb, C.c_void_p), None),
-                      "mg_ghost_set_exchange_plugin")
 
     @property
     def n_ext(self):

@@ -522,6 +522,41 @@ def test_ghost_form_block_of_right_hand_sides(mg, world, cyc, nrhs, tol, x_nonze
     assert np.abs(X - Xo).max() <= 1e-10 * np.abs(Xo).max()
 
 
+@pytest.mark.gpu
+def test_ghost_form_refused_block_stays_unfinalized(mg):
+    """A block handle whose fine level the column-wise solve does not serve (here: the four-stage pass switched off) is refused by
+    mg_ghost_finalize with MG_ERR_UNSUPPORTED - and stays unfinalized: a solve on it returns a status and a message instead of running.
+    The three mg_ghost_* calls are made as NativeGhostHierarchy's constructor makes them (which raises on the refusal); a world of one."""
+    import ctypes as C
+    from multigrid_jl_amd import device as D
+    MG_ERR_UNSUPPORTED = 4
+    nrhs = 2
+    G, = _setup_all_ranks(mg, 1, "3d-a2", "V", nrhs=nrhs)
+    dev = D.DeviceHierarchy(G.param, 0, nrhs, options=dict(TEST_OPTS, rowclass_min_cover=0.05, march_max_len=64, march4_ty_max=12, no_march4=1))
+    try:
+        lib, h = dev.lib, dev.handle
+        i64 = lambda v: np.ascontiguousarray(v, dtype=np.int64)
+        D._check(lib, lib.mg_ghost_attach(h, 0, 1, G.a, None), "mg_ghost_attach")
+        for l, L in enumerate(G.levels, start=1):
+            pad = lambda v: i64(list(v) + [1] * (3 - len(v)))
+            lo, hi, ext = i64(list(L.own_lo) + [0] * (3 - len(L.own_lo))), pad(L.own_hi), pad(L.ext_n)
+            assert len(L.send_idx) == 0 and len(L.recv_idx) == 0           # (one rank: nothing to exchange)
+            D._check(lib, lib.mg_ghost_set_level_INT64(h, l, D._i64(ext), D._i64(lo), D._i64(hi), int(min(L.gmin, 1 << 20)), 0, None,
+                                                       D._i64(i64(L.send_splits)), 0, None, D._i64(i64(L.recv_splits))), "mg_ghost_set_level")
+        assert lib.mg_ghost_finalize(h) == MG_ERR_UNSUPPORTED
+        assert b"column by column" in lib.mg_last_error()
+        n = G.levels[0].n
+        bt = torch.ones(n, nrhs, dtype=torch.float64, device="cuda")
+        xt = torch.zeros_like(bt)
+        iters, resvec = C.c_longlong(0), np.zeros(3)
+        rc = lib.mg_solve_dev_FP64(h, D._ptr(bt), D._ptr(xt), n, nrhs, 1e-8, 2, C.byref(iters), D._f64(resvec))
+        assert rc != 0 and lib.mg_last_error()
+        torch.cuda.synchronize()
+        assert float(xt.abs().max()) == 0.0 and iters.value == 0        # (nothing ran)
+    finally:
+        dev.close()
+
+
 def _worker_c4box(rank, world, port, cells, levels, q, steps):
     """One rank of the C4-sized run in the ghost-layer form: its 257^3 box + ghost layers, plug-in transport."""
     try:
