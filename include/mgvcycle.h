@@ -481,6 +481,32 @@ int mg_lu_create_FP64_INT64(long long device_id, long long n, const long long* L
 int mg_lu_solve_FP64(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose);
 int mg_lu_solve_dev_FP64(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs,
                          long long doTranspose);
+/* ComplexF64 factors (applyLUsolve_CFP64_INT64, parLU.cpp:69-72; the complex systems src/ParallelJuliaSolver was written for):
+ * the same layout, limits and validation as mg_lu_create_FP64_INT64, with Lval, Uval, b and x interleaved (re, im) doubles
+ * (Julia ComplexF64).  Adjoint convention: doTranspose != 0 follows applyLUsolveTrans (parLU.cpp:193-260), which CONJUGATES
+ * for complex values - x[p] = L^H \ (U^H \ b[q]) solves A^H x = b, Julia's A' \ b, not the plain transpose.  The
+ * conjugate-transposed factors are built on the host at the first such solve and stay resident beside the plain ones.
+ * Factors of at least lu_multi_min_rows rows (MG_LU_MULTI_MIN_ROWS) take the chip-wide form - one launch per dependency
+ * level, the trailing chain through the explicit inverse of its dense block (MG_LU_DENSE_TAIL_MIN / _MAX bound its order) -
+ * smaller ones a single workgroup; nrhs columns travel together in both.  The handle records its value type: mg_lu_solve*_FP64
+ * on a complex handle and mg_lu_solve*_CFP64 on a real one fail with MG_ERR_STATE and leave the handle usable.
+ * mg_lu_destroy serves both kinds. */
+int mg_lu_create_CFP64_INT64(long long device_id, long long n, const long long* Lptr, const long long* Lcol,
+                             const double* Lval, const long long* Uptr, const long long* Ucol, const double* Uval,
+                             const long long* p, const long long* q, mg_lu** out);
+int mg_lu_solve_CFP64(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose);
+int mg_lu_solve_dev_CFP64(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs,
+                          long long doTranspose);
+/* The form a handle's factors are applied in, either value type; doTranspose selects the transposed (adjoint) set and builds
+ * it if needed.  info[0..7): value type (0 Float64, 1 ComplexF64); 1 for the chip-wide form; order of the dense trailing
+ * block; launched levels of L ahead of it and of U behind it; all dependency levels of L and of U. */
+int mg_lu_form(mg_lu* f, long long doTranspose, long long* info);
+/* Measurement: `warmup` untimed solves on device vectors (row-major [n][nrhs], as the _dev solve of the handle's value
+ * type), then `reps` solves, each enqueued between two events on the handle's stream - the second recorded before the host
+ * waits, so a sample is stream time without the host's wake-up; ms[0..reps) in milliseconds.  The factor set of the direction
+ * is built before the first sample. */
+int mg_lu_time_dev(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose,
+                   long long warmup, long long reps, double* ms);
 int mg_lu_destroy(mg_lu* f);
 
 /* ---- native multi-GPU sequencer (one process per GPU) ---------------------------------------------------------

@@ -428,6 +428,7 @@ int mg_set_coarse_lu_FP64_INT64(mg_hierarchy* h, long long n, const long long* L
   h->luML = h->luMU = 0;
   h->luInvL.release(); h->luInvU.release(); h->luTail.release();
   if (h->lu_multi) {
+    // (the complex applier's cxlu_upload, mg_complex.inc, carries the same estimate with 16-byte values: keep the two in step)
     // Size M of the trailing block: a level costs ~8 us of dependent latency whatever its width, the dense product
     // 8*M^2/2 bytes of traffic per factor - take the candidate with the smallest estimate.  (33^3 Poisson level under
     // a minimum-degree ordering: 3284 levels per factor at M = 0, 639 at M = 4096, 132 at M = 8192.)
@@ -988,6 +989,7 @@ struct mg_lu {
   std::vector<double> Lval, Uval;
   mg_hierarchy* fwd = nullptr;
   mg_hierarchy* trans = nullptr;
+  CxLu* cx = nullptr;   // a ComplexF64 handle (mg_lu_create_CFP64_INT64): the applier of mg_complex.inc, nothing above is used
 };
 namespace {
 // CSR (1-based) of the transpose of an n x n CSR (1-based) matrix; columns of every row come out ascending
@@ -1075,6 +1077,7 @@ int mg_lu_create_FP64_INT64(long long device_id, long long n, const long long* L
 // overwrites it, parLU.cpp:176)
 int mg_lu_solve_FP64(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose) {
   if (!f) return fail(MG_ERR_INVALID, "null factor handle");
+  if (f->cx) return fail(MG_ERR_STATE, "mg_lu_solve_FP64 on a handle of ComplexF64 factors (mg_lu_solve_CFP64)");
   if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
   if (nrhs < 1 || !b || !x) return fail(MG_ERR_INVALID, "bad argument");
   mg_hierarchy* h = nullptr;
@@ -1086,6 +1089,7 @@ int mg_lu_solve_FP64(mg_lu* f, const double* b, double* x, long long n, long lon
 // device-resident form: b_dev, x_dev row-major [n][nrhs] in HBM
 int mg_lu_solve_dev_FP64(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose) {
   if (!f) return fail(MG_ERR_INVALID, "null factor handle");
+  if (f->cx) return fail(MG_ERR_STATE, "mg_lu_solve_dev_FP64 on a handle of ComplexF64 factors (mg_lu_solve_dev_CFP64)");
   if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
   if (nrhs < 1 || !b_dev || !x_dev) return fail(MG_ERR_INVALID, "bad argument");
   mg_hierarchy* h = nullptr;
@@ -1094,8 +1098,123 @@ int mg_lu_solve_dev_FP64(mg_lu* f, const double* b_dev, double* x_dev, long long
   return mg_cycle_dev_FP64(h, b_dev, x_dev, n, nrhs, 1);
 }
 
+// ComplexF64 factors (applyLUsolve_CFP64_INT64, parLU.cpp:69-72): values, b and x interleaved (re, im).  doTranspose solves
+// with the ADJOINT, x[p] = L^H \ (U^H \ b[q]) (Julia's A'), from conjugate-transposed factors built on first use.
+int mg_lu_create_CFP64_INT64(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const double* Lval,
+                             const long long* Uptr, const long long* Ucol, const double* Uval, const long long* p,
+                             const long long* q, mg_lu** out) {
+  if (!out) return fail(MG_ERR_INVALID, "out is null");
+  *out = nullptr;
+  if (n < 1 || !Lptr || !Lcol || !Lval || !Uptr || !Ucol || !Uval || !p || !q) return fail(MG_ERR_INVALID, "null or empty factor");
+  if (Lptr[0] != 1 || Uptr[0] != 1 || Lptr[n] < 1 || Uptr[n] < 1) return fail(MG_ERR_INVALID, "row pointers must be 1-based");
+  CxLu* S = nullptr;
+  MG_TRY(cxlu_create(device_id, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, &S));
+  mg_lu* f = new mg_lu();
+  f->device = (int)device_id;
+  f->n = n;
+  f->cx = S;
+  *out = f;
+  return MG_OK;
+}
+
+namespace {
+int cxlu_entry(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose, bool host, const char* name) {
+  if (!f) return fail(MG_ERR_INVALID, "null factor handle");
+  if (!f->cx) return fail(MG_ERR_STATE, "%s on a handle of Float64 factors (create it with mg_lu_create_CFP64_INT64)", name);
+  if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
+  if (nrhs < 1 || !b || !x) return fail(MG_ERR_INVALID, "bad argument");
+  if (n * nrhs >= (1LL << 31)) return fail(MG_ERR_UNSUPPORTED, "n*nrhs=%lld exceeds int32 device indices", n * nrhs);
+  CxLu* S = f->cx;
+  (void)hipSetDevice(S->device);
+  CxLuSet* G = nullptr;
+  MG_TRY(cxlu_set(S, doTranspose != 0, &G));
+  if (host) return cxlu_solve_host(S, *G, b, x, (int)nrhs);
+  MG_TRY(cxlu_solve_dev(S, *G, reinterpret_cast<const cx_t*>(b), reinterpret_cast<cx_t*>(x), (int)nrhs));
+  HIP_TRY(spin_sync(S->stream));
+  return MG_OK;
+}
+}  // namespace
+
+// b, x: host, n x nrhs column-major ComplexF64; b is NOT used as work space
+int mg_lu_solve_CFP64(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose) {
+  return cxlu_entry(f, b, x, n, nrhs, doTranspose, true, "mg_lu_solve_CFP64");
+}
+
+// device-resident form: b_dev, x_dev row-major [n][nrhs] ComplexF64 in HBM
+int mg_lu_solve_dev_CFP64(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose) {
+  return cxlu_entry(f, b_dev, x_dev, n, nrhs, doTranspose, false, "mg_lu_solve_dev_CFP64");
+}
+
+// The form a handle's factors are applied in (either value type): info[0] value type (0 Float64, 1 ComplexF64), [1] 1 for
+// the chip-wide form, [2] order of the dense trailing block, [3] / [4] launched levels of L / U around it, [5] / [6] all
+// dependency levels of L / U.  doTranspose selects the transposed (adjoint) set, which is built if it was not yet.
+int mg_lu_form(mg_lu* f, long long doTranspose, long long* info) {
+  if (!f || !info) return fail(MG_ERR_INVALID, "null argument");
+  if (f->cx) {
+    (void)hipSetDevice(f->cx->device);
+    CxLuSet* G = nullptr;
+    MG_TRY(cxlu_set(f->cx, doTranspose != 0, &G));
+    info[0] = 1; info[1] = G->multi ? 1 : 0; info[2] = G->M;
+    info[3] = G->multi ? (long long)G->Llvl_h.size() - 1 : G->nLlvl;
+    info[4] = G->multi ? (long long)G->Ulvl_h.size() - 1 : G->nUlvl;
+    info[5] = G->nLlvl; info[6] = G->nUlvl;
+    return MG_OK;
+  }
+  mg_hierarchy* h = nullptr;
+  MG_TRY(lu_hierarchy(f, doTranspose != 0, &h));
+  info[0] = 0; info[1] = h->lu_multi ? 1 : 0; info[2] = h->luML;
+  info[3] = h->lu_multi ? (long long)h->luLlvl_h.size() - 1 : h->nLlvl;
+  info[4] = h->lu_multi ? (long long)h->luUlvl_h.size() - 1 : h->nUlvl;
+  info[5] = h->nLlvl; info[6] = h->nUlvl;
+  return MG_OK;
+}
+
+// Device time of one solve on device vectors (either value type; row-major [n][nrhs]): `warmup` untimed solves, then `reps`
+// solves, each enqueued between two events on the handle's stream (the second is recorded BEFORE the host waits, so a sample
+// is stream time - kernels and the gaps between their launches - without the host's wake-up); ms[0..reps) in milliseconds.
+// The factor set of the direction is built before the first sample, whatever `warmup` is.
+int mg_lu_time_dev(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose,
+                   long long warmup, long long reps, double* ms) {
+  if (!f || !ms || !b_dev || !x_dev || reps < 1 || warmup < 0 || nrhs < 1) return fail(MG_ERR_INVALID, "bad argument");
+  if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
+  (void)hipSetDevice(f->device);
+  hipStream_t stream;
+  mg_hierarchy* h = nullptr;
+  CxLuSet* G = nullptr;
+  if (f->cx) {
+    if (n * nrhs >= (1LL << 31)) return fail(MG_ERR_UNSUPPORTED, "n*nrhs=%lld exceeds int32 device indices", n * nrhs);
+    MG_TRY(cxlu_set(f->cx, doTranspose != 0, &G));
+    stream = f->cx->stream;
+  } else {
+    MG_TRY(lu_hierarchy(f, doTranspose != 0, &h));
+    MG_TRY(mg_set_nrhs(h, nrhs));
+    MG_TRY(check_ready(h, n, nrhs));
+    stream = h->stream;
+  }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = MG_OK;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventCreate failed");
+  for (long long it = 0; it < warmup + reps && rc == MG_OK; ++it) {
+    if (hipEventRecord(e0, stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
+    if (rc == MG_OK)
+      rc = f->cx ? cxlu_solve_dev(f->cx, *G, reinterpret_cast<const cx_t*>(b_dev), reinterpret_cast<cx_t*>(x_dev), (int)nrhs)
+                 : cycle_dev(h, b_dev, x_dev, true);
+    if (rc == MG_OK) {
+      float t = 0.f;
+      if (hipEventRecord(e1, stream) != hipSuccess || spin_sync(stream) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)
+        rc = fail(MG_ERR_HIP, "event timing failed");
+      if (it >= warmup) ms[it - warmup] = (double)t;
+    }
+  }
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (h) prof_collect(h);
+  return rc;
+}
+
 int mg_lu_destroy(mg_lu* f) {
   if (!f) return MG_OK;
+  if (f->cx) cxlu_destroy(f->cx);
   if (f->fwd) mg_destroy(f->fwd);
   if (f->trans) mg_destroy(f->trans);
   delete f;

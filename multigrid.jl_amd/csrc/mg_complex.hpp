@@ -1,4 +1,5 @@
-// mg_complex.hpp - gfx950 kernels of the ComplexF64 (CF64) cycle: generic CSR only.
+// mg_complex.hpp - gfx950 kernels of the ComplexF64 (CF64) cycle: generic CSR only; complex hybrid Kaczmarz; the chip-wide
+// complex triangular solve of the factor applier (cx_sptrsv_*, cx_tri_*, at the end).
 //
 // Complex values are interleaved (re, im) doubles - Julia ComplexF64, numpy complex128, hipDoubleComplex - and are
 // loaded as one 16-byte d2_t.  The operator A of a CF64 handle is stored conjugated at upload (nzval of the
@@ -254,6 +255,216 @@ __global__ __launch_bounds__(64) void hybrid_kaczmarz_c(const int* __restrict__ 
       }
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Chip-wide sparse triangular solve on complex factors (mg_lu_*_CFP64): the complex form of sptrsv_level /
+// sptrsv_tail_rhs / sptrsv_scatter / tri_gather_block / tri_inverse / tri_apply (mg_kernels.hpp), same layout and
+// scheduling - one wavefront per row, one launch per wide level, up to 4 right-hand-side columns travelling together,
+// the trailing chain of single-row levels replaced by the explicit inverse of its dense block, vectors row-major
+// [n][nrhs], no inter-workgroup waiting.  A row moves 20 bytes per entry (16 value + 4 index) against 12 for real
+// factors; a lane's gather of y is 16*nc contiguous bytes.  The adjoint solve needs no kernel of its own: the host
+// uploads the conjugate-transposed factors as a second resident set.
+// ------------------------------------------------------------------------------------------------
+typedef LuDevT<d2_t> CxLuDev;
+
+template <bool LOWER>
+__global__ __launch_bounds__(BLK) void cx_sptrsv_level(CxLuDev F, const int4* __restrict__ slots, int t0, int t1,
+                                                       const d2_t* __restrict__ b, d2_t* y, int nrhs) {
+  const int t = t0 + (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
+  const int lane = threadIdx.x & 63;
+  if (t >= t1) return;  // wave-uniform
+  const int* __restrict__ col = LOWER ? F.Lcol : F.Ucol;
+  const d2_t* __restrict__ val = LOWER ? F.Lval : F.Uval;
+  const int4 sl = slots[t];                       // (row, first and end of the off-diagonal entries, the diagonal entry)
+  const int row = sl.x, s = sl.y, e = sl.z;
+  const d2_t dg = val[sl.w];
+  for (int c0 = 0; c0 < nrhs; c0 += 4) {
+    const int nc = min(4, nrhs - c0);
+    d2_t acc[4] = {d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}};
+    for (int k = s + lane; k < e; k += 64) {
+      const d2_t v = val[k];
+      const d2_t* yy = y + (size_t)col[k] * nrhs + c0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (u < nc) acc[u] += cmul(v, yy[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      for (int o = 32; o > 0; o >>= 1) acc[u] += shfl_xor_v(acc[u], o);
+    if (lane < nc) {
+      const d2_t rhs = LOWER ? b[(size_t)F.p[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
+      const d2_t a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+      y[(size_t)row * nrhs + c0 + lane] = cdiv(rhs - a, dg);
+    }
+  }
+}
+
+// t = b[p] - L21*y1 for the rows n0.. of the trailing block of L
+__global__ __launch_bounds__(BLK) void cx_sptrsv_tail_rhs(CxLuDev F, int n0, const d2_t* __restrict__ b,
+                                                          const d2_t* __restrict__ y, d2_t* __restrict__ t, int nrhs) {
+  const int i = (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
+  const int lane = threadIdx.x & 63;
+  const int row = n0 + i;
+  if (row >= F.n) return;  // wave-uniform
+  const int s = F.Lptr[row], e = F.Lptr[row + 1] - 1;
+  for (int c0 = 0; c0 < nrhs; c0 += 4) {
+    const int nc = min(4, nrhs - c0);
+    d2_t acc[4] = {d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}};
+    for (int k = s + lane; k < e; k += 64) {
+      const int c = F.Lcol[k];
+      if (c >= n0) continue;                       // the trailing block itself is applied through its inverse
+      const d2_t v = F.Lval[k];
+      const d2_t* yy = y + (size_t)c * nrhs + c0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (u < nc) acc[u] += cmul(v, yy[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      for (int o = 32; o > 0; o >>= 1) acc[u] += shfl_xor_v(acc[u], o);
+    if (lane < nc) {
+      const d2_t a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+      t[(size_t)i * nrhs + c0 + lane] = b[(size_t)F.p[row] * nrhs + c0 + lane] - a;
+    }
+  }
+}
+
+// x[q[r]] = y[r]
+__global__ __launch_bounds__(BLK) void cx_sptrsv_scatter(const int* __restrict__ q, const d2_t* __restrict__ y,
+                                                         d2_t* __restrict__ x, int n, int nrhs) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i >= (long long)n * nrhs) return;
+  const int r = (int)(i / nrhs), u = (int)(i - (long long)r * nrhs);
+  x[(size_t)q[r] * nrhs + u] = y[i];
+}
+
+// Dense block (row-major, leading dimension ld = M rounded up to 64, zero outside the triangle, unit diagonal in the
+// padding) of the rows/columns n0.. of a complex factor in CSR; D was zeroed by the host.
+__global__ __launch_bounds__(BLK) void cx_tri_gather_block(const int* __restrict__ ptr, const int* __restrict__ col,
+                                                           const d2_t* __restrict__ val, int n0, int M, int ld,
+                                                           d2_t* __restrict__ D) {
+  const int i = (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= ld) return;
+  if (i >= M) {
+    if (lane == 0) D[(size_t)i * ld + i] = d2_t{1.0, 0.0};
+    return;
+  }
+  for (int k = ptr[n0 + i] + lane; k < ptr[n0 + i + 1]; k += 64) {
+    const int c = col[k] - n0;
+    if (c >= 0) D[(size_t)i * ld + c] = val[k];
+  }
+}
+
+// X = inv(D) for a dense complex triangular block (ld x ld, ld a multiple of 64): tri_inverse with 32 x 32 blocks
+// (16-byte values: the four LDS tiles of the 64 x 64 form would not fit a workgroup).  One 256-thread workgroup per
+// block of 32 columns of X walks the 32-row panels in substitution order; the contribution of the rows already known
+// is a 32 x K x 32 product through LDS tiles (each thread a 2 x 2 register tile), the 32 x 32 diagonal block is then
+// substituted in LDS by half a wavefront (a column per lane).  Setup-time kernel.
+constexpr int CX_TRI_NB = 32;
+template <bool LOWER>
+__global__ __launch_bounds__(256) void cx_tri_inverse(const d2_t* __restrict__ D, d2_t* X, int ld) {
+  constexpr int NB = CX_TRI_NB;
+  __shared__ d2_t As[NB][17];
+  __shared__ d2_t Bs[16][NB];
+  __shared__ d2_t Ts[NB][NB + 1];
+  __shared__ d2_t Ds[NB][NB + 1];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int C0 = blockIdx.x * NB, nP = ld / NB, cb = blockIdx.x;
+  // rows outside the triangle of this column block
+  for (int i = LOWER ? 0 : C0 + NB; i < (LOWER ? C0 : ld); i += 256 / NB) {
+    const int r = i + tid / NB;
+    if (r < (LOWER ? C0 : ld)) X[(size_t)r * ld + C0 + (tid & (NB - 1))] = d2_t{0.0, 0.0};
+  }
+  for (int pp = 0; pp < (LOWER ? nP - cb : cb + 1); ++pp) {
+    const int p = LOWER ? cb + pp : cb - pp;
+    const int I0 = p * NB;
+    const int K0 = LOWER ? C0 : I0 + NB, K1 = LOWER ? I0 : C0 + NB;
+    d2_t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = d2_t{0.0, 0.0};
+    for (int k0 = K0; k0 < K1; k0 += 16) {
+      // D[I0 + r][k0 + kk]: 32 x 16; X[k0 + kk][C0 + c]: 16 x 32 - two elements per thread each
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int e = tid + 256 * u;
+        As[e >> 4][e & 15] = D[(size_t)(I0 + (e >> 4)) * ld + k0 + (e & 15)];
+        Bs[e / NB][e & (NB - 1)] = X[(size_t)(k0 + e / NB) * ld + C0 + (e & (NB - 1))];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk) {
+        d2_t a[2], bb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[i] = As[ty * 2 + i][kk];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bb[j] = Bs[kk][tx * 2 + j];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[i][j] += cmul(a[i], bb[j]);
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int r = ty * 2 + i, c = tx * 2 + j;
+        Ts[r][c] = d2_t{(I0 + r == C0 + c) ? 1.0 : 0.0, 0.0} - acc[i][j];
+      }
+    for (int e = tid; e < NB * NB; e += 256) Ds[e / NB][e & (NB - 1)] = D[(size_t)(I0 + e / NB) * ld + I0 + (e & (NB - 1))];
+    __syncthreads();
+    if (tid < NB) {                                 // within one wavefront, a column per lane: no barriers needed inside
+      const int c = tid;
+      if (LOWER) {
+        for (int r = 0; r < NB; ++r) {
+          d2_t v = Ts[r][c];
+          for (int k = 0; k < r; ++k) v = v - cmul(Ds[r][k], Ts[k][c]);
+          Ts[r][c] = cdiv(v, Ds[r][r]);
+        }
+      } else {
+        for (int r = NB - 1; r >= 0; --r) {
+          d2_t v = Ts[r][c];
+          for (int k = r + 1; k < NB; ++k) v = v - cmul(Ds[r][k], Ts[k][c]);
+          Ts[r][c] = cdiv(v, Ds[r][r]);
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < NB * NB; e += 256) X[(size_t)(I0 + e / NB) * ld + C0 + (e & (NB - 1))] = Ts[e / NB][e & (NB - 1)];
+    __threadfence();                                // the next panel of this workgroup reads these rows back
+    __syncthreads();
+  }
+}
+
+// x = T * b for a dense complex TRIANGULAR M x M block (row-major, leading dimension ld): one wavefront per (row, column)
+template <bool LOWER>
+__global__ __launch_bounds__(BLK) void cx_tri_apply(const d2_t* __restrict__ T, int ld, const d2_t* __restrict__ b,
+                                                    d2_t* __restrict__ x, int M, int nrhs) {
+  const int wave = (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
+  const int lane = threadIdx.x & 63;
+  if (wave >= M * nrhs) return;  // wave-uniform
+  const int row = wave / nrhs, c = wave - row * nrhs;
+  const d2_t* __restrict__ a = T + (size_t)row * ld;
+  const int j0 = LOWER ? 0 : (row & ~63), j1 = LOWER ? row + 1 : M;
+  d2_t acc = d2_t{0.0, 0.0};
+  for (int j = j0 + lane; j < j1; j += 64) acc += cmul(a[j], b[(size_t)j * nrhs + c]);
+  for (int o = 32; o > 0; o >>= 1) acc += shfl_xor_v(acc, o);
+  if (lane == 0) x[(size_t)row * nrhs + c] = acc;
+}
+
+// column-major n x nrhs (the host's layout) <-> row-major [n][nrhs] (the device's), complex entries
+template <bool TO_ROWMAJOR>
+__global__ __launch_bounds__(BLK) void cx_relayout(const d2_t* __restrict__ src, d2_t* __restrict__ dst, long long n, int nrhs) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;   // index into the row-major array
+  if (i >= n * nrhs) return;
+  const long long r = i / nrhs, c = i - r * nrhs;
+  if (TO_ROWMAJOR) dst[i] = src[c * n + r];
+  else dst[c * n + r] = src[i];
 }
 
 }  // namespace mgk

@@ -2,6 +2,8 @@
 // ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F cycles,
 // pointwise relaxation, dense-inverse or sparse-LU coarsest solve.  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
+// Also here: the stand-alone ComplexF64 factor applier behind mg_lu_*_CFP64 (CxLu; its extern "C" entry points sit beside the
+// real applier's in mg_cabi.inc).
 //
 // Reference behaviour reproduced for VAL = ComplexF64:
 //   recursiveCycle  src/Multigrid/MGcycle.jl:1-118, relax l.122-136, solveCoarsest l.177
@@ -52,6 +54,32 @@ struct CxState {
     luLval.release(); luUval.release(); luWork.release();
     stage_b.release(); partial.release();
   }
+};
+
+// ---- stand-alone complex factor applier (mg_lu_*_CFP64): state of its own, apart from the CF64 hierarchies --------------
+// one resident set of factors: the plain ones (x[q] = U \ (L \ b[p])) or the conjugate-transposed ones of the adjoint solve
+struct CxLuSet {
+  DevBuf<int> Lptr, Lcol, Uptr, Ucol, P, Q, Lorder, Llvl, Uorder, Ulvl, Lslot, Uslot;
+  DevBuf<double> Lval, Uval, invL, invU;   // interleaved (re, im)
+  int nLlvl = 0, nUlvl = 0;                // dependency levels of the whole factors (single-workgroup form)
+  bool multi = false;                      // chip-wide form: per-level launches + dense trailing inverse
+  int M = 0;                               // order of the trailing block held as an explicit inverse
+  std::vector<int> Llvl_h, Ulvl_h;         // host copies of the level pointers ahead of / behind the trailing block
+  ~CxLuSet() {
+    for (DevBuf<int>* d : {&Lptr, &Lcol, &Uptr, &Ucol, &P, &Q, &Lorder, &Llvl, &Uorder, &Ulvl, &Lslot, &Uslot}) d->release();
+    for (DevBuf<double>* d : {&Lval, &Uval, &invL, &invU}) d->release();
+  }
+};
+struct CxLu {
+  int device = 0;
+  long long n = 0;
+  Options opt;
+  hipStream_t stream = nullptr;
+  std::vector<long long> Lptr, Lcol, Uptr, Ucol, p, q;   // the caller's factors (1-based): the adjoint set is derived from them
+  std::vector<double> Lval, Uval;
+  CxLuSet* fwd = nullptr;
+  CxLuSet* adj = nullptr;
+  DevBuf<double> work, tail, stage_b, stage_x, stage_t;
 };
 
 namespace {
@@ -311,6 +339,260 @@ int cx_finalize(mg_hierarchy* h) {
   if (S.partial.n < maxblocks) MG_TRY(S.partial.alloc(maxblocks));
   if (S.coarse_lu && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
   S.finalized = true;
+  return MG_OK;
+}
+
+// ---- the complex factor applier ------------------------------------------------------------------------------------------
+void cxlu_destroy(CxLu* S) {
+  if (!S) return;
+  (void)hipSetDevice(S->device);
+  if (S->stream) (void)spin_sync(S->stream);
+  delete S->fwd;
+  delete S->adj;
+  for (DevBuf<double>* d : {&S->work, &S->tail, &S->stage_b, &S->stage_x, &S->stage_t}) d->release();
+  if (S->stream) (void)hipStreamDestroy(S->stream);
+  delete S;
+}
+
+// Validate and upload one set of factors in parLU's layout (the checks and the form selection of
+// mg_set_coarse_lu_FP64_INT64, 16 bytes per value in the traffic term of the trailing block's estimate).
+int cxlu_upload(CxLu* S, CxLuSet* F, const long long* Lptr, const long long* Lcol, const double* Lval, const long long* Uptr,
+                const long long* Ucol, const double* Uval, const long long* p, const long long* q, const char* what) {
+  const long long n = S->n;
+  const size_t N = (size_t)n;
+  std::vector<int> LP, LC, LO, LL, UP, UC, UO, UL, pp(N), qq(N);
+  MG_TRY(lu_convert(n, Lptr, Lcol, true, LP, LC, LO, LL));
+  MG_TRY(lu_convert(n, Uptr, Ucol, false, UP, UC, UO, UL));
+  for (size_t i = 0; i < N; ++i) {
+    if (p[i] < 1 || p[i] > n || q[i] < 1 || q[i] > n) return fail(MG_ERR_INVALID, "permutation entry out of range");
+    pp[i] = (int)(p[i] - 1);
+    qq[i] = (int)(q[i] - 1);
+  }
+  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) -> int {
+    MG_TRY(d.alloc(v.size()));
+    HIP_TRY(hipMemcpy(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
+    return MG_OK;
+  };
+  MG_TRY(up_i(F->Lptr, LP)); MG_TRY(up_i(F->Lcol, LC)); MG_TRY(up_i(F->Lorder, LO)); MG_TRY(up_i(F->Llvl, LL));
+  MG_TRY(up_i(F->Uptr, UP)); MG_TRY(up_i(F->Ucol, UC)); MG_TRY(up_i(F->Uorder, UO)); MG_TRY(up_i(F->Ulvl, UL));
+  MG_TRY(up_i(F->P, pp)); MG_TRY(up_i(F->Q, qq));
+  MG_TRY(F->Lval.alloc(2 * LC.size()));
+  MG_TRY(F->Uval.alloc(2 * UC.size()));
+  HIP_TRY(hipMemcpy(F->Lval.p, Lval, 2 * LC.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(F->Uval.p, Uval, 2 * UC.size() * sizeof(double), hipMemcpyHostToDevice));
+  F->nLlvl = (int)LL.size() - 1;
+  F->nUlvl = (int)UL.size() - 1;
+  F->multi = n >= S->opt.lu_multi_min_rows;
+  F->M = 0;
+  if (!F->multi) return MG_OK;
+  // Size M of the trailing block: a level costs ~8 us of dependent latency whatever its width, the dense product
+  // 16*M^2/2 bytes of traffic per factor - the candidate with the smallest estimate
+  // (the estimate, the slots and the inversion sequence of mg_set_coarse_lu_FP64_INT64, mg_cabi.inc: keep the two in step)
+  const int cap = (int)std::min<long long>(S->opt.lu_dense_tail_max, n);
+  int M = 0;
+  double best = 0.0;
+  std::vector<int> o, lp;
+  for (int cand = 0; cand <= cap; cand = cand == 0 ? (int)std::max<long long>(S->opt.lu_dense_tail_min, 1) : cand * 2) {
+    lu_levels(n, LP, LC, true, cand, o, lp);
+    double est = 8e-6 * (double)(lp.size() - 1);
+    lu_levels(n, UP, UC, false, cand, o, lp);
+    est += 8e-6 * (double)(lp.size() - 1) + 2.0 * 8.0 * (double)cand * (double)cand / 4e12;
+    if (cand == 0 || est < best) { best = est; M = cand; }
+  }
+  auto slots = [&](const std::vector<int>& P, bool lower, const std::vector<int>& order, DevBuf<int>& d) -> int {
+    std::vector<int> sl(order.size() * 4);
+    for (size_t t = 0; t < order.size(); ++t) {
+      const int r = order[t];
+      sl[4 * t] = r;
+      sl[4 * t + 1] = lower ? P[(size_t)r] : P[(size_t)r] + 1;          // off-diagonal entries [s, e)
+      sl[4 * t + 2] = lower ? P[(size_t)r + 1] - 1 : P[(size_t)r + 1];
+      sl[4 * t + 3] = lower ? P[(size_t)r + 1] - 1 : P[(size_t)r];      // the diagonal entry
+    }
+    return up_i(d, sl);
+  };
+  lu_levels(n, LP, LC, true, M, o, F->Llvl_h);
+  MG_TRY(slots(LP, true, o, F->Lslot));
+  lu_levels(n, UP, UC, false, M, o, F->Ulvl_h);
+  MG_TRY(slots(UP, false, o, F->Uslot));
+  auto invert = [&](bool lower, const DevBuf<int>& ptr, const DevBuf<int>& col, const DevBuf<double>& val, DevBuf<double>& inv) -> int {
+    const int ld = (M + 63) / 64 * 64;
+    const size_t len = 2 * (size_t)ld * (size_t)ld;
+    DevBuf<double> D;
+    int rc = D.alloc(len);
+    if (rc == MG_OK) rc = inv.alloc(len);
+    if (rc == MG_OK && hipMemsetAsync(D.p, 0, len * sizeof(double), S->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipMemsetAsync failed");
+    if (rc == MG_OK) {
+      hipLaunchKernelGGL(mgk::cx_tri_gather_block, dim3(cx_grid((long long)ld * 64)), dim3(mgk::BLK), 0, S->stream, ptr.p, col.p,
+                         reinterpret_cast<const cx_t*>(val.p), (int)n - M, M, ld, cxp(D));
+      const dim3 g((unsigned)(ld / mgk::CX_TRI_NB));
+      if (lower) hipLaunchKernelGGL(mgk::cx_tri_inverse<true>, g, dim3(256), 0, S->stream, reinterpret_cast<const cx_t*>(D.p), cxp(inv), ld);
+      else hipLaunchKernelGGL(mgk::cx_tri_inverse<false>, g, dim3(256), 0, S->stream, reinterpret_cast<const cx_t*>(D.p), cxp(inv), ld);
+      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(S->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "inversion of the trailing block failed");
+    }
+    D.release();
+    return rc;
+  };
+  if (M > 0) {
+    MG_TRY(invert(true, F->Lptr, F->Lcol, F->Lval, F->invL));
+    MG_TRY(invert(false, F->Uptr, F->Ucol, F->Uval, F->invU));
+  }
+  F->M = M;
+  if (S->opt.debug_format)
+    std::fprintf(stderr, "[mgvcycle] complex LU (%s) n=%lld: dense trailing block %d, L %zu levels ahead of it (%d in all), U %zu behind it (%d)\n",
+                 what, n, M, F->Llvl_h.size() - 1, F->nLlvl, F->Ulvl_h.size() - 1, F->nUlvl);
+  return MG_OK;
+}
+
+// CSR (1-based) of the conjugate transpose of an n x n complex CSR (1-based) matrix; columns of every row come out ascending,
+// so U^H is lower triangular with its diagonal last and L^H upper triangular with its diagonal first
+void cx_adjoint_csr1(long long n, const std::vector<long long>& ptr, const std::vector<long long>& col, const std::vector<double>& val,
+                     std::vector<long long>& tp, std::vector<long long>& tc, std::vector<double>& tv) {
+  const size_t nnz = col.size();
+  tc.resize(nnz);
+  tv.resize(2 * nnz);
+  std::vector<long long> cnt((size_t)n, 0);
+  for (size_t k = 0; k < nnz; ++k) cnt[(size_t)col[k] - 1]++;
+  tp.assign((size_t)n + 1, 1);
+  for (long long c = 0; c < n; ++c) tp[(size_t)c + 1] = tp[(size_t)c] + cnt[(size_t)c];
+  std::vector<long long> pos(tp.begin(), tp.end() - 1);
+  for (long long r = 0; r < n; ++r)
+    for (long long k = ptr[(size_t)r] - 1; k < ptr[(size_t)r + 1] - 1; ++k) {
+      const long long c = col[(size_t)k] - 1;
+      const long long w = pos[(size_t)c]++ - 1;
+      tc[(size_t)w] = r + 1;
+      tv[2 * (size_t)w] = val[2 * (size_t)k];
+      tv[2 * (size_t)w + 1] = -val[2 * (size_t)k + 1];
+    }
+}
+
+// the resident set of one solve direction; the adjoint set is built on its first use and kept beside the plain one
+int cxlu_set(CxLu* S, bool adjoint, CxLuSet** out) {
+  CxLuSet*& F = adjoint ? S->adj : S->fwd;
+  if (!F) {
+    CxLuSet* G = new CxLuSet();
+    int rc;
+    if (!adjoint) {
+      rc = cxlu_upload(S, G, S->Lptr.data(), S->Lcol.data(), S->Lval.data(), S->Uptr.data(), S->Ucol.data(), S->Uval.data(), S->p.data(),
+                       S->q.data(), "plain");
+    } else {   // A^H = Q U^H L^H P with A[p,q] = L U: x[p] = L^H \ (U^H \ b[q])
+      std::vector<long long> lp, lc, up, uc;
+      std::vector<double> lv, uv;
+      cx_adjoint_csr1(S->n, S->Uptr, S->Ucol, S->Uval, lp, lc, lv);
+      cx_adjoint_csr1(S->n, S->Lptr, S->Lcol, S->Lval, up, uc, uv);
+      rc = cxlu_upload(S, G, lp.data(), lc.data(), lv.data(), up.data(), uc.data(), uv.data(), S->q.data(), S->p.data(), "adjoint");
+    }
+    if (rc != MG_OK) {
+      delete G;
+      return rc;
+    }
+    F = G;
+  }
+  *out = F;
+  return MG_OK;
+}
+
+// x = A \ b (or A^H \ b) on device vectors, row-major [n][nrhs]; enqueued on S->stream, no synchronisation
+int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr) {
+  const long long n = S->n;
+  const size_t wlen = 2 * (size_t)n * (size_t)nr, tlen = 2 * (size_t)std::max(G.M, 1) * (size_t)nr;
+  if (S->work.n < wlen) MG_TRY(S->work.alloc(wlen));
+  if (S->tail.n < tlen) MG_TRY(S->tail.alloc(tlen));
+  mgk::CxLuDev F;
+  F.n = (int)n;
+  F.Lptr = G.Lptr.p; F.Lcol = G.Lcol.p; F.Lval = reinterpret_cast<const cx_t*>(G.Lval.p);
+  F.Uptr = G.Uptr.p; F.Ucol = G.Ucol.p; F.Uval = reinterpret_cast<const cx_t*>(G.Uval.p);
+  F.p = G.P.p; F.q = G.Q.p;
+  F.Lorder = G.Lorder.p; F.Llvl = G.Llvl.p; F.nLlvl = G.nLlvl;
+  F.Uorder = G.Uorder.p; F.Ulvl = G.Ulvl.p; F.nUlvl = G.nUlvl;
+  cx_t* y = cxp(S->work);
+  if (!G.multi) {
+    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, S->stream, F, b, x, y, nr);
+    HIP_TRY(hipGetLastError());
+    return MG_OK;
+  }
+  auto wave_blocks = [](long long waves) { return dim3(cx_grid(waves * 64)); };
+  cx_t* t = cxp(S->tail);
+  const int M = G.M, n0 = (int)n - M, ld = (M + 63) / 64 * 64;
+  // y = L \ b[p]: the levels ahead of the trailing block one launch each, the block through its inverse
+  const int nLl = (int)G.Llvl_h.size() - 1, nUl = (int)G.Ulvl_h.size() - 1;
+  for (int l = 0; l < nLl; ++l) {
+    const int t0 = G.Llvl_h[(size_t)l], t1 = G.Llvl_h[(size_t)l + 1];
+    hipLaunchKernelGGL(mgk::cx_sptrsv_level<true>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, S->stream, F,
+                       reinterpret_cast<const int4*>(G.Lslot.p), t0, t1, b, y, nr);
+  }
+  if (M > 0) {
+    hipLaunchKernelGGL(mgk::cx_sptrsv_tail_rhs, wave_blocks(M), dim3(mgk::BLK), 0, S->stream, F, n0, b, y, t, nr);
+    hipLaunchKernelGGL(mgk::cx_tri_apply<true>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, S->stream,
+                       reinterpret_cast<const cx_t*>(G.invL.p), ld, t, y + (size_t)n0 * (size_t)nr, M, nr);
+    // y = U \ y: the trailing block first, then the levels behind it
+    HIP_TRY(hipMemcpyAsync(t, y + (size_t)n0 * (size_t)nr, (size_t)M * (size_t)nr * sizeof(cx_t), hipMemcpyDeviceToDevice, S->stream));
+    hipLaunchKernelGGL(mgk::cx_tri_apply<false>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, S->stream,
+                       reinterpret_cast<const cx_t*>(G.invU.p), ld, t, y + (size_t)n0 * (size_t)nr, M, nr);
+  }
+  for (int l = 0; l < nUl; ++l) {
+    const int t0 = G.Ulvl_h[(size_t)l], t1 = G.Ulvl_h[(size_t)l + 1];
+    hipLaunchKernelGGL(mgk::cx_sptrsv_level<false>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, S->stream, F,
+                       reinterpret_cast<const int4*>(G.Uslot.p), t0, t1, b, y, nr);
+  }
+  hipLaunchKernelGGL(mgk::cx_sptrsv_scatter, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, G.Q.p, y, x, (int)n, nr);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// host form: b, x column-major n x nrhs interleaved complex; b is only read
+int cxlu_solve_host(CxLu* S, CxLuSet& G, const double* b, double* x, int nr) {
+  const long long n = S->n;
+  const size_t len = 2 * (size_t)n * (size_t)nr, bytes = len * sizeof(double);
+  if (S->stage_b.n < len) MG_TRY(S->stage_b.alloc(len));
+  if (S->stage_x.n < len) MG_TRY(S->stage_x.alloc(len));
+  if (nr > 1 && S->stage_t.n < len) MG_TRY(S->stage_t.alloc(len));
+  if (nr == 1) {
+    HIP_TRY(hipMemcpyAsync(S->stage_b.p, b, bytes, hipMemcpyHostToDevice, S->stream));
+    MG_TRY(cxlu_solve_dev(S, G, cxp(S->stage_b), cxp(S->stage_x), 1));
+    HIP_TRY(hipMemcpyAsync(x, S->stage_x.p, bytes, hipMemcpyDeviceToHost, S->stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(S->stage_t.p, b, bytes, hipMemcpyHostToDevice, S->stream));
+    hipLaunchKernelGGL(mgk::cx_relayout<true>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, cxp(S->stage_t), cxp(S->stage_b), n, nr);
+    MG_TRY(cxlu_solve_dev(S, G, cxp(S->stage_b), cxp(S->stage_x), nr));
+    hipLaunchKernelGGL(mgk::cx_relayout<false>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, cxp(S->stage_x), cxp(S->stage_t), n, nr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(x, S->stage_t.p, bytes, hipMemcpyDeviceToHost, S->stream));
+  }
+  HIP_TRY(spin_sync(S->stream));
+  return MG_OK;
+}
+
+// the create step behind mg_lu_create_CFP64_INT64: arguments already checked for null / 1-based pointers
+int cxlu_create(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const double* Lval, const long long* Uptr,
+                const long long* Ucol, const double* Uval, const long long* p, const long long* q, CxLu** out) {
+  if (n >= (1LL << 31) - 1 || Lptr[n] - 1 >= (1LL << 31) || Uptr[n] - 1 >= (1LL << 31))
+    return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the factor applier has no CPU fallback");
+  if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
+  HIP_TRY(hipSetDevice((int)device_id));
+  CxLu* S = new CxLu();
+  S->opt = Options::from_env();   // the only place the environment is read for this handle
+  S->device = (int)device_id;
+  S->n = n;
+  S->Lptr.assign(Lptr, Lptr + n + 1);
+  S->Uptr.assign(Uptr, Uptr + n + 1);
+  S->Lcol.assign(Lcol, Lcol + (Lptr[n] - 1));
+  S->Lval.assign(Lval, Lval + 2 * (Lptr[n] - 1));
+  S->Ucol.assign(Ucol, Ucol + (Uptr[n] - 1));
+  S->Uval.assign(Uval, Uval + 2 * (Uptr[n] - 1));
+  S->p.assign(p, p + n);
+  S->q.assign(q, q + n);
+  int rc = MG_OK;
+  if (hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(MG_ERR_HIP, "hipStreamCreate failed");
+  CxLuSet* F = nullptr;
+  if (rc == MG_OK) rc = cxlu_set(S, false, &F);   // validates and uploads the factors
+  if (rc != MG_OK) {
+    cxlu_destroy(S);
+    return rc;
+  }
+  *out = S;
   return MG_OK;
 }
 

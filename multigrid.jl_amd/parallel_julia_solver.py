@@ -5,6 +5,8 @@ triangular factors with its own native code (back end 3: ``applyLUsolve_FP64_INT
 120-260; one OpenMP task per right-hand side).  Here the factorisation comes from SuperLU (scipy; no UMFPACK in this
 image) in the same layout - L and U in CSR, 1-based Int64, L's diagonal last and U's diagonal first, A[p,q] = L*U -
 and ``mg_lu_*`` applies them on the GPU, including the solve with the transposed matrix (``doTranspose``).
+VAL = ComplexF64 (``applyLUsolve_CFP64_INT64``, the complex Helmholtz systems the module was written for) goes through
+``mg_lu_*_CFP64``; there ``doTranspose`` solves with the ADJOINT, x[p] = L^H \\ (U^H \\ b[q]) - Julia's ``A'``.
 Same names and argument meaning as the reference; ``solveLinearSystem_`` is Julia's ``solveLinearSystem!``.
 """
 import ctypes as C
@@ -52,8 +54,10 @@ class parallelJuliaSolver:
 
 def getParallelJuliaSolver(VAL=np.float64, IND=np.int64, numCores: int = 1, backend: int = 1) -> parallelJuliaSolver:
     """parallelJuliaSolver.jl:63-70."""
-    if np.dtype(VAL) != np.float64:
-        raise TypeError("only Float64 factors are supported on the device path")
+    if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
+        raise TypeError("only Float64 and ComplexF64 factors are supported on the device path")
+    if np.dtype(VAL) == np.complex128 and np.dtype(IND) != np.int64:
+        raise TypeError("ComplexF64 factors take Int64 indices")
     return parallelJuliaSolver(VAL=VAL, IND=IND, numCores=numCores, backend=backend)
 
 
@@ -65,17 +69,34 @@ def clear_(param: parallelJuliaSolver):
     return param
 
 
+def _is_complex(param: "parallelJuliaSolver") -> bool:
+    return np.dtype(param.VAL) == np.complex128
+
+
+def _check_dtype(a, param: "parallelJuliaSolver", name: str) -> None:
+    """ComplexF64 solver: complex128 arrays only; Float64 solver: no complex array.  Nothing is cast between the two."""
+    dt = np.asarray(a).dtype if not sp.issparse(a) else a.dtype
+    if _is_complex(param):
+        if dt != np.complex128:
+            raise TypeError(f"{name} has dtype {dt}, but the solver holds ComplexF64 factors")
+    elif dt.kind == "c":
+        raise TypeError(f"{name} has dtype {dt}, but the solver holds Float64 factors")
+
+
 def _upload_factors(param: "parallelJuliaSolver") -> None:
     """(Re)create the device applier from param.L / U / p / q (the layout of setupLUFactor)."""
     lib = D.load_library()
     L, U = param.L, param.U
+    VAL = np.dtype(param.VAL)
     a64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
-    Lp, Lc, Lv = a64(L.indptr) + 1, a64(L.indices) + 1, np.ascontiguousarray(L.data, dtype=np.float64)
-    Up, Uc, Uv = a64(U.indptr) + 1, a64(U.indices) + 1, np.ascontiguousarray(U.data, dtype=np.float64)
+    Lp, Lc, Lv = a64(L.indptr) + 1, a64(L.indices) + 1, np.ascontiguousarray(L.data, dtype=VAL)
+    Up, Uc, Uv = a64(U.indptr) + 1, a64(U.indices) + 1, np.ascontiguousarray(U.data, dtype=VAL)
     param.close()
     h = C.c_void_p()
-    D._check(lib, lib.mg_lu_create_FP64_INT64(0, L.shape[0], D._i64(Lp), D._i64(Lc), D._f64(Lv), D._i64(Up), D._i64(Uc),
-                                              D._f64(Uv), D._i64(param.p), D._i64(param.q), C.byref(h)), "mg_lu_create")
+    create, what = ((lib.mg_lu_create_CFP64_INT64, "mg_lu_create_CFP64") if _is_complex(param)
+                    else (lib.mg_lu_create_FP64_INT64, "mg_lu_create"))
+    D._check(lib, create(0, L.shape[0], D._i64(Lp), D._i64(Lc), D._f64(Lv), D._i64(Up), D._i64(Uc), D._f64(Uv),
+                         D._i64(param.p), D._i64(param.q), C.byref(h)), what)
     param._handle = h
 
 
@@ -91,7 +112,12 @@ def copySolver(param: parallelJuliaSolver) -> parallelJuliaSolver:
 
 def setupLUFactor(AI, param: parallelJuliaSolver) -> parallelJuliaSolver:
     """Factor and convert to the native applier's layout (parallelJuliaSolver.jl:113-148, convertCSC2MyCSR l.26-31)."""
-    lu = spla.splu(sp.csc_matrix(AI), permc_spec="MMD_AT_PLUS_A")
+    AI = sp.csc_matrix(AI)
+    if _is_complex(param):
+        AI = AI.astype(np.complex128)             # a real matrix through a ComplexF64 solver (the reference converts too)
+    elif AI.dtype.kind == "c":
+        raise TypeError("a complex matrix needs a ComplexF64 solver")
+    lu = spla.splu(AI, permc_spec="MMD_AT_PLUS_A")
     L = sp.csr_matrix(lu.L)
     U = sp.csr_matrix(lu.U)
     L.sort_indices()                              # lower: the diagonal is the last entry of every row
@@ -109,21 +135,27 @@ def setupSolver(AI, param: parallelJuliaSolver) -> parallelJuliaSolver:
 
 
 def solve(b: np.ndarray, x: np.ndarray, LU: parallelJuliaSolver, doTranspose: int = 0) -> np.ndarray:
-    """x[q] = U \\ (L \\ b[p]), or with doTranspose x[p] = L' \\ (U' \\ b[q]) (parallelJuliaSolver.jl:151-207); x is
-    written in place (column-major, as Julia holds it)."""
+    """x[q] = U \\ (L \\ b[p]), or with doTranspose x[p] = L' \\ (U' \\ b[q]) (parallelJuliaSolver.jl:151-207; ' is the
+    adjoint for ComplexF64); x is written in place (column-major, as Julia holds it)."""
+    _check_dtype(b, LU, "b")
+    _check_dtype(x, LU, "x")
     if LU._handle is None:
         if LU.L is None:
             raise RuntimeError("the factors were not set up")
         _upload_factors(LU)          # a copySolver() copy: factors present, device applier not yet created
     lib = D.load_library()
-    bb = np.asfortranarray(b, dtype=np.float64)
-    if x.dtype != np.float64 or (x.ndim == 2 and not x.flags.f_contiguous) or not x.flags.writeable:
-        raise ValueError("x must be a writable Float64 array in column-major (Julia) layout")
+    VAL = np.dtype(LU.VAL)
+    bb = np.asfortranarray(b, dtype=VAL)
+    if x.dtype != VAL or (x.ndim == 2 and not x.flags.f_contiguous) or not x.flags.writeable:
+        raise ValueError("x must be a writable array of the solver's value type in column-major (Julia) layout")
     if bb.shape != x.shape:
         raise ValueError("b and x differ in shape")
     n = bb.shape[0]
     nrhs = 1 if bb.ndim == 1 else bb.shape[1]
-    D._check(lib, lib.mg_lu_solve_FP64(LU._handle, D._f64(bb), D._f64(x), n, nrhs, int(doTranspose)), "mg_lu_solve")
+    if _is_complex(LU):
+        D._check(lib, lib.mg_lu_solve_CFP64(LU._handle, D._f64(bb), D._f64(x), n, nrhs, int(doTranspose)), "mg_lu_solve_CFP64")
+    else:
+        D._check(lib, lib.mg_lu_solve_FP64(LU._handle, D._f64(bb), D._f64(x), n, nrhs, int(doTranspose)), "mg_lu_solve")
     return x
 
 
@@ -148,5 +180,6 @@ def solveLinearSystem_(A, B, X: np.ndarray, param: parallelJuliaSolver, doTransp
 
 def solveLinearSystem(A, B, param: parallelJuliaSolver, doTranspose: int = 0):
     """``solveLinearSystem(A,B,param,doTranspose)`` (parallelJuliaSolver.jl:75-83): X is a fresh copy of B's shape."""
-    Bd = np.asfortranarray(B.toarray() if sp.issparse(B) else B, dtype=np.float64)
+    _check_dtype(B, param, "B")
+    Bd = np.asfortranarray(B.toarray() if sp.issparse(B) else B, dtype=np.dtype(param.VAL))
     return solveLinearSystem_(A, Bd, Bd.copy(order="F"), param, doTranspose)
