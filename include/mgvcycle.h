@@ -509,6 +509,57 @@ int mg_lu_time_dev(mg_lu* f, const double* b_dev, double* x_dev, long long n, lo
                    long long warmup, long long reps, double* ms);
 int mg_lu_destroy(mg_lu* f);
 
+/* ---- multiplicative Schwarz preconditioner (src/DomainDecomposition) --------------------------------------------------
+ * Device form of solveDDSerial (DDSerial.jl:108-139; getDDpreconditioner, DomainDecomposition.jl:136-146) on what
+ * setupDDSerial leaves (DDSerial.jl:81-106, sparse-matrix branch): for niter sweeps, for every colour in ascending order
+ * (cellColor, Vanka.jl:105-130: 1..2^dim), for every sub-domain of the colour in linear order:
+ *   r = (b - A x)[I]  (computeResidualAtIdx, DDSerial.jl:4-20),  t = A_I \ r  (solveSubDomain, l.183-187),  x[I] += t  (l.129).
+ * create: rowptr / colA / valA are the CSR of the applied operator A, 1-based Int64 - the reference's AT.colptr, AT.rowval
+ * and conj(AT.nzval) (interleaved (re, im) doubles for CFP64); idx holds the lists GlobalIndices[ic] (DDIndType = UInt32,
+ * 1-based, DomainDecomposition.jl:15) back to back, sub-domain ic at idxptr[ic] .. idxptr[ic+1]-1 (idxptr 1-based, numSub+1
+ * entries); color[ic] >= 1 is its colour.  set_factor: sub-domain ic's factors of A[I,I] in parLU's layout, exactly the
+ * arguments of mg_lu_create_* (n_i must equal the length of its list).  finalize: every sub-domain needs its factors
+ * (MG_ERR_STATE otherwise); decides per colour whether its members are INDEPENDENT - index sets pairwise disjoint and no
+ * row listed by one member stores a column listed by another (nodal boxes, radius-1 stencil: cellSize - 2*overlap >= 2).
+ * An independent colour is one launch, one 1024-thread workgroup per sub-domain; a dependent one, or one with a member of
+ * at least lu_multi_min_rows rows (MG_LU_MULTI_MIN_ROWS, read once at create), runs its members one after another:
+ * residual gather, the applier's solve (single workgroup; chip-wide form for those large members), scatter-add.
+ * apply: b and x are vectors of n values (one right-hand side: the reference indexes b[Idxs]), x in/out, b != x; host
+ * pointers, or HBM for the _dev forms.  doTranspose != 0 reaches the sub-domain solves only (transposed factors, the
+ * ADJOINT for CFP64, built on first use); the residual always uses A (DDSerial.jl:123,128).  The handle records its value
+ * type: an FP64 entry point on a CFP64 handle, or the reverse, fails with MG_ERR_STATE and leaves the handle usable.
+ * Invalid arguments (null, empty, an index outside 1..n, an index listed twice by one sub-domain, n_i differing from the
+ * list) give MG_ERR_INVALID; sizes beyond int32 device indices MG_ERR_UNSUPPORTED.
+ * Not served: the operator-constructor / Dirichlet-mass branch (DDSerial.jl:42-61), DDParallel.jl, solveGSDDSerial. */
+typedef struct mg_dd mg_dd;
+int mg_dd_create_FP64_INT64(long long device_id, long long n, const long long* rowptr, const long long* colA,
+                            const double* valA, long long numSub, const long long* idxptr, const unsigned int* idx,
+                            const long long* color, mg_dd** out);
+int mg_dd_create_CFP64_INT64(long long device_id, long long n, const long long* rowptr, const long long* colA,
+                             const double* valA, long long numSub, const long long* idxptr, const unsigned int* idx,
+                             const long long* color, mg_dd** out);
+int mg_dd_set_factor_FP64_INT64(mg_dd* dd, long long ic, long long n_i, const long long* Lptr, const long long* Lcol,
+                                const double* Lval, const long long* Uptr, const long long* Ucol, const double* Uval,
+                                const long long* p, const long long* q);
+int mg_dd_set_factor_CFP64_INT64(mg_dd* dd, long long ic, long long n_i, const long long* Lptr, const long long* Lcol,
+                                 const double* Lval, const long long* Uptr, const long long* Ucol, const double* Uval,
+                                 const long long* p, const long long* q);
+int mg_dd_finalize(mg_dd* dd);
+int mg_dd_apply_FP64(mg_dd* dd, const double* b, double* x, long long n, long long niter, long long doTranspose);
+int mg_dd_apply_dev_FP64(mg_dd* dd, const double* b_dev, double* x_dev, long long n, long long niter,
+                         long long doTranspose);
+int mg_dd_apply_CFP64(mg_dd* dd, const double* b, double* x, long long n, long long niter, long long doTranspose);
+int mg_dd_apply_dev_CFP64(mg_dd* dd, const double* b_dev, double* x_dev, long long n, long long niter,
+                          long long doTranspose);
+/* info[0..6): value type (0 Float64, 1 ComplexF64); sub-domains; colours present; colours run batched; colours run in
+ * sequence; kernel launches of one sweep (doTranspose = 0; a chip-wide member counts one launch per level it launches). */
+int mg_dd_info(mg_dd* dd, long long* info);
+/* Measurement, as mg_lu_time_dev: `warmup` untimed sweeps on device vectors of the handle's value type, then `reps` sweeps,
+ * each between two events on the handle's stream; ms[0..reps) in milliseconds.  x_dev is swept in place. */
+int mg_dd_time_dev(mg_dd* dd, const double* b_dev, double* x_dev, long long n, long long doTranspose, long long warmup,
+                   long long reps, double* ms);
+int mg_dd_destroy(mg_dd* dd);
+
 /* ---- native multi-GPU sequencer (one process per GPU) ---------------------------------------------------------
  * The sharded cycle of src/DomainDecomposition's partition (box rule DDIndices.jl:41-47, numbering DDService.jl:27-48;
  * worker map analogue DDParallel.jl:105,133-139) behind the C ABI: the host cuts every sharded level into local

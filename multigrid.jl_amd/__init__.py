@@ -20,9 +20,13 @@ from .par_relax import (hybridKaczmarz, getHybridKaczmarz, setupHybridKaczmarz, 
                         applyHybridKaczmarz)
 from .dd_indices import (getIndicesOfCellsArray, getNodalIndicesOfCell, getOriginalBoundingBoxCells, getBoxWithOverlap,
                          cs2loc, loc2cs)
+from .domain_decomposition import (DomainDecompositionParam, DomainDecompositionPreconditionerParam, getDomainDecompositionParam,
+                                   cellColor, setupDDSerial, solveDDSerial, getDDpreconditioner, coloursIndependent)
 from . import device
 
 __all__ = [n for n in dir() if not n.startswith("_")]
 
 # src/ParallelJuliaSolver is a sub-module of the reference package too (Multigrid.ParallelJuliaSolver)
 from . import parallel_julia_solver as ParallelJuliaSolver
+# ... and so is src/DomainDecomposition (Multigrid.DomainDecomposition)
+from . import domain_decomposition as DomainDecomposition

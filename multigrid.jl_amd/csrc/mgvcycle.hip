@@ -34,6 +34,7 @@
 #include "mg_small.hpp"
 #include "mg_complex.hpp"
 #include "mg_krvec.hpp"
+#include "mg_dd.hpp"
 
 
 // One translation unit in parts (the 6 800-line file split by responsibility; the order is the dependency order):
@@ -48,3 +49,4 @@
 #include "mg_cabi.inc"       // extern "C": the single-GPU API and its ghost-layer form (mg_ghost_*)
 #include "mg_dist.inc"       // extern "C": the native multi-GPU sequencer (halo form)
 #include "mg_dist_krylov.inc"   // extern "C": PCG / BiCGSTAB / FGMRES on the sharded halo form, their fused vector passes
+#include "mg_dd.inc"         // extern "C": the multiplicative Schwarz preconditioner of src/DomainDecomposition (mg_dd_*)

@@ -126,6 +126,18 @@ SIGNATURES = {
     "mg_lu_form": (C.c_int, [_vp, _ll, _lp]),
     "mg_lu_time_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _ll, _dp]),
     "mg_lu_destroy": (C.c_int, [_vp]),
+    "mg_dd_create_FP64_INT64": (C.c_int, [_ll, _ll, _lp, _lp, _dp, _ll, _lp, C.POINTER(C.c_uint), _lp, C.POINTER(_vp)]),
+    "mg_dd_create_CFP64_INT64": (C.c_int, [_ll, _ll, _lp, _lp, _dp, _ll, _lp, C.POINTER(C.c_uint), _lp, C.POINTER(_vp)]),
+    "mg_dd_set_factor_FP64_INT64": (C.c_int, [_vp, _ll, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
+    "mg_dd_set_factor_CFP64_INT64": (C.c_int, [_vp, _ll, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
+    "mg_dd_finalize": (C.c_int, [_vp]),
+    "mg_dd_apply_FP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_dd_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_dd_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_dd_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_dd_info": (C.c_int, [_vp, _lp]),
+    "mg_dd_time_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _dp]),
+    "mg_dd_destroy": (C.c_int, [_vp]),
     "mg_kaczmarz_create_FP64_INT64": (C.c_int, [_ll, _ll, _lp, _dp, _lp, _ll, _ll, C.POINTER(C.c_uint), _dp, C.POINTER(_vp)]),
     "mg_kaczmarz_apply_FP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_kaczmarz_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),

@@ -110,8 +110,10 @@ def copySolver(param: parallelJuliaSolver) -> parallelJuliaSolver:
     return new
 
 
-def setupLUFactor(AI, param: parallelJuliaSolver) -> parallelJuliaSolver:
-    """Factor and convert to the native applier's layout (parallelJuliaSolver.jl:113-148, convertCSC2MyCSR l.26-31)."""
+def setupLUFactor(AI, param: parallelJuliaSolver, upload: bool = True) -> parallelJuliaSolver:
+    """Factor and convert to the native applier's layout (parallelJuliaSolver.jl:113-148, convertCSC2MyCSR l.26-31).
+    upload = False (not in the reference's signature) leaves the device applier to the first solve: the Schwarz sweep
+    packs the factors of all its sub-domains into one handle of its own (domain_decomposition.py)."""
     AI = sp.csc_matrix(AI)
     if _is_complex(param):
         AI = AI.astype(np.complex128)             # a real matrix through a ComplexF64 solver (the reference converts too)
@@ -125,7 +127,10 @@ def setupLUFactor(AI, param: parallelJuliaSolver) -> parallelJuliaSolver:
     param.L, param.U = L, U
     param.p = (np.argsort(lu.perm_r) + 1).astype(np.int64)
     param.q = (np.argsort(lu.perm_c) + 1).astype(np.int64)
-    _upload_factors(param)
+    if upload:
+        _upload_factors(param)
+    else:
+        param.close()
     return param
 
 
