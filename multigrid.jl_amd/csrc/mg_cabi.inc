@@ -31,7 +31,7 @@ int need_finalized(mg_hierarchy* h) {
 int upload_x_or_zero(mg_hierarchy* h, const double* x, long long n, long long nrhs) {
   const long long len = n * nrhs;
   if (host_all_zero(x, len)) {
-    HIP_TRY(hipMemsetAsync(h->stage_x.p, 0, sizeof(double) * (size_t)len, h->stream));
+    HIP_TRY(hipMemsetAsync(h->stage_x.p, 0, sizeof(double) * (size_t)len, h->play->stream));
     return MG_OK;
   }
   return upload_block(h, x, h->stage_x.p, n, nrhs);
@@ -99,12 +99,12 @@ int mg_create(long long nlevels, long long nrhs, long long device_id, mg_hierarc
   h->nrhs = nrhs;
   h->lev.resize((size_t)nlevels);
   h->slots.resize((size_t)nlevels * MG_K_COUNT);
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(&h->lane0.stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     delete h;
     return fail(MG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
   }
-  if (h->partial.alloc((size_t)h->nred_blocks) != MG_OK || h->partial2.alloc(256) != MG_OK || h->scalar.alloc(1) != MG_OK ||
+  if (h->lane0.partial.alloc((size_t)h->nred_blocks) != MG_OK || h->lane0.partial2.alloc(256) != MG_OK || h->lane0.scalar.alloc(1) != MG_OK ||
       hipHostMalloc(reinterpret_cast<void**>(&h->h_scalar), 4 * sizeof(double)) != hipSuccess) {
     mg_destroy(h);
     return fail(MG_ERR_HIP, "allocation of reduction scratch failed");
@@ -133,25 +133,25 @@ int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   for (int l = 0; l < nl; ++l)
     if (h->lev[(size_t)l].A.wide || h->lev[(size_t)l].P.wide || h->lev[(size_t)l].R.wide)
       return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers (>= 2^31 non-zeros): the numeric Galerkin product on the device serves int32 operators", l + 1);
-  HIP_TRY(spin_sync(h->stream));
-  HIP_TRY(hipMemcpyAsync(L0.A.val.p, fine_nzval, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
+  HIP_TRY(hipMemcpyAsync(L0.A.val.p, fine_nzval, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, h->play->stream));
   for (int l = 0; l + 1 < nl; ++l) {
     Level& L = h->lev[(size_t)l];
     Level& C = h->lev[(size_t)l + 1];
     const int nb = (int)((L.n + mgk::BLK - 1) / mgk::BLK);
     if (relaxKind == 0) {
-      hipLaunchKernelGGL(mgk::relax_jacobi, dim3(nb), dim3(mgk::BLK), 0, h->stream, L.A.dev(), omega[l], L.d.p);
+      hipLaunchKernelGGL(mgk::relax_jacobi, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, L.A.dev(), omega[l], L.d.p);
     } else {
       MG_TRY(build_transposed_pattern(L.A));   // (first SPAI re-setup of this level only)
-      hipLaunchKernelGGL(mgk::colsumsq_kernel, dim3(nb), dim3(mgk::BLK), 0, h->stream, L.A.val.p, L.A.t_ptr.p, L.A.t_perm.p,
-                         (int)L.A.n_cols, L.r.p);   // L.r as scratch for the column sums
-      hipLaunchKernelGGL(mgk::relax_spai, dim3(nb), dim3(mgk::BLK), 0, h->stream, L.A.dev(), omega[l], L.r.p, L.d.p);
+      hipLaunchKernelGGL(mgk::colsumsq_kernel, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, L.A.val.p, L.A.t_ptr.p, L.A.t_perm.p,
+                         (int)L.A.n_cols, h->play->lev[(size_t)l].r.p);   // the level's r as scratch for the column sums
+      hipLaunchKernelGGL(mgk::relax_spai, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, L.A.dev(), omega[l], h->play->lev[(size_t)l].r.p, L.d.p);
     }
-    hipLaunchKernelGGL(mgk::rap_numeric, dim3((unsigned)C.n), dim3(64), 0, h->stream, L.R.dev(), L.A.dev(), L.P.dev(),
+    hipLaunchKernelGGL(mgk::rap_numeric, dim3((unsigned)C.n), dim3(64), 0, h->play->stream, L.R.dev(), L.A.dev(), L.P.dev(),
                        C.A.rowptr.p, C.A.colidx.p, C.A.val.p, (int)std::max<long long>(1, std::min<long long>(h->opt.rap_chunk, mgk::RAP_CAP)));
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   // row-class dictionaries follow the new values (coarse values come back from HBM; rap_numeric adds every entry in a
   // fixed order, so rows that were bit-identical before a constant-coefficient update still are afterwards)
   MG_TRY(refresh_rowclasses(&L0.A, fine_nzval));
@@ -178,7 +178,7 @@ int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double
   MG_TRY(find_op(h, level, which, &M));
   if (!out || nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
   (void)hipSetDevice(h->device);
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   HIP_TRY(hipMemcpy(out, M->val.p, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost));
   return MG_OK;
 }
@@ -189,7 +189,7 @@ int mg_get_relax_FP64(mg_hierarchy* h, long long level, double* out, long long n
   MG_TRY(find_level(h, level, &L));
   if (!out || !L->relax_set || n != (long long)L->d.n) return fail(MG_ERR_INVALID, "relaxPrecs[%lld] not set or wrong length", level);
   (void)hipSetDevice(h->device);
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   HIP_TRY(hipMemcpy(out, L->d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return MG_OK;
 }
@@ -198,7 +198,7 @@ int mg_destroy(mg_hierarchy* h) {
   if (!h) return MG_OK;
   graphs_clear(h);
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)spin_sync(h->stream);
+  if (h->play->stream) (void)spin_sync(h->play->stream);
   if (h->ghost) { gh_release(h->ghost); h->ghost = nullptr; }
   if (h->cx) { cx_destroy(h->cx); h->cx = nullptr; }
   prof_collect(h);
@@ -208,10 +208,6 @@ int mg_destroy(mg_hierarchy* h) {
     L.P.release();
     L.R.release();
     L.d.release();
-    L.b.release();
-    L.r.release();
-    L.x0.release();
-    L.x1.release();
     L.x2.release();
     L.x3.release();
   }
@@ -226,9 +222,6 @@ int mg_destroy(mg_hierarchy* h) {
   h->luInvL.release(); h->luInvU.release(); h->luTail.release(); h->luLslot.release(); h->luUslot.release();
   h->kwc.release();
   h->coarse_d.release();
-  h->partial.release();
-  h->partial2.release();
-  h->scalar.release();
   h->stage_b.release();
   h->stage_x.release();
   h->stage_t.release();
@@ -240,24 +233,18 @@ int mg_destroy(mg_hierarchy* h) {
   if (h->h_scalar) (void)hipHostFree(h->h_scalar);
   if (h->h_cols) (void)hipHostFree(h->h_cols);
   for (auto& cb : h->colbuf) cb.release();
-  for (mg_hierarchy::ColSet* cs : h->colsets) {
-    if (cs->ready) (void)hipEventDestroy(cs->ready);
-    if (cs->stream) (void)hipStreamDestroy(cs->stream);
-    for (auto* v : {&cs->b, &cs->r, &cs->x0, &cs->x1})
-      for (auto& d : *v) d.release();
-    cs->partial.release();
-    cs->partial2.release();
-    cs->scalar.release();
-    delete cs;
-  }
-  h->colsets.clear();
+  for (hipEvent_t e : h->lane_ready) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t& e : h->pipe_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (h->h_blk) (void)hipHostFree(h->h_blk);
   if (h->h_kscal) (void)hipHostFree(h->h_kscal);
   if (h->h_blk_c) (void)hipHostFree(h->h_blk_c);
   h->blk_partial.release();
   h->blk_c.release();
-  if (h->stream && h->owns_stream) (void)hipStreamDestroy(h->stream);
+  h->lane0.release();
+  for (Play* p : h->lanes) {
+    p->release();
+    delete p;
+  }
   delete h;
   return MG_OK;
 }
@@ -465,13 +452,13 @@ int mg_set_coarse_lu_FP64_INT64(mg_hierarchy* h, long long n, const long long* L
       DevBuf<double> D;
       MG_TRY(D.alloc((size_t)ld * (size_t)ld));
       MG_TRY(inv.alloc((size_t)ld * (size_t)ld));
-      HIP_TRY(hipMemsetAsync(D.p, 0, (size_t)ld * (size_t)ld * sizeof(double), h->stream));
+      HIP_TRY(hipMemsetAsync(D.p, 0, (size_t)ld * (size_t)ld * sizeof(double), h->play->stream));
       hipLaunchKernelGGL(mgk::tri_gather_block, dim3((unsigned)(((long long)ld * 64 + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK),
-                         0, h->stream, ptr.p, col.p, val.p, (int)n - M, M, ld, D.p);
-      if (lower) hipLaunchKernelGGL(mgk::tri_inverse<true>, dim3((unsigned)(ld / 64)), dim3(256), 0, h->stream, D.p, inv.p, ld);
-      else hipLaunchKernelGGL(mgk::tri_inverse<false>, dim3((unsigned)(ld / 64)), dim3(256), 0, h->stream, D.p, inv.p, ld);
+                         0, h->play->stream, ptr.p, col.p, val.p, (int)n - M, M, ld, D.p);
+      if (lower) hipLaunchKernelGGL(mgk::tri_inverse<true>, dim3((unsigned)(ld / 64)), dim3(256), 0, h->play->stream, D.p, inv.p, ld);
+      else hipLaunchKernelGGL(mgk::tri_inverse<false>, dim3((unsigned)(ld / 64)), dim3(256), 0, h->play->stream, D.p, inv.p, ld);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(h->stream));
+      HIP_TRY(hipStreamSynchronize(h->play->stream));
       return MG_OK;
     };
     if (ML > 0) MG_TRY(invert(true, ML, h->luLptr, h->luLcol, h->luLval, h->luInvL));
@@ -562,7 +549,7 @@ int mg_set_nrhs(mg_hierarchy* h, long long nrhs) {
   (void)hipSetDevice(h->device);
   h->nrhs = nrhs;
   if (h->finalized) {
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     MG_TRY(alloc_scratch(h));
   }
   return MG_OK;
@@ -578,7 +565,7 @@ int mg_replace_values_FP64(mg_hierarchy* h, long long level, long long which, co
   MG_TRY(find_op(h, level, which, &M));
   if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
   (void)hipSetDevice(h->device);
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   HIP_TRY(hipMemcpy(M->val.p, nzval, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
   MG_TRY(refresh_rowclasses(M, nzval));
   if (which == MG_OP_A) {
@@ -611,7 +598,7 @@ int mg_cycle_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, 
   }
   if (h->ghost && nrhs != 1) MG_TRY(cycle_dev_columns(h, b, x, xz));   // (ghost-layer form: a block cycle is its columns' cycles)
   else MG_TRY(cycle_dev(h, b, x, xz));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   prof_collect(h);
   return MG_OK;
 }
@@ -627,7 +614,7 @@ int mg_solve_dev_FP64(mg_hierarchy* h, const double* b, double* x, long long n, 
     return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: a block of right-hand sides needs the column-wise solve (constant-coefficient fine level with the four-stage pass, V(2,*) pointwise smoother)");
   if (columns_ok(h)) MG_TRY(solve_dev_columns(h, b, x, tol, maxIter, iters, resvec));
   else MG_TRY(solve_dev(h, b, x, tol, maxIter, iters, resvec));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   prof_collect(h);
   return MG_OK;
 }
@@ -643,7 +630,7 @@ int mg_spmv_dev_FP64(mg_hierarchy* h, long long level, long long which, double a
   if (x == y) return fail(MG_ERR_INVALID, "x and y must not alias");
   (void)hipSetDevice(h->device);
   MG_TRY(k_spmv(h, (int)level - 1, MG_K_SPMV, *M, alpha, x, beta, y));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   prof_collect(h);
   return MG_OK;
 }
@@ -665,7 +652,7 @@ int mg_fused_dev_FP64(mg_hierarchy* h, long long level, long long kernel, const 
   } else {
     return fail(MG_ERR_INVALID, "kernel must be MG_K_RESIDUAL or MG_K_SMOOTH");
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   prof_collect(h);
   return MG_OK;
 }
@@ -684,7 +671,7 @@ int mg_sweep_residual_dev_FP64(mg_hierarchy* h, long long level, const double* b
                 "smoother, grid operator without exception rows, distinct 16-byte aligned buffers)", level);
   MG_TRY(k_smooth_residual(h, (int)level - 1, b, x, t, r, xn, norm_r != nullptr));
   if (norm_r) MG_TRY(scalar_sync(h, norm_r));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   prof_collect(h);
   return MG_OK;
 }
@@ -701,7 +688,7 @@ int mg_four_stage_dev_FP64(mg_hierarchy* h, long long level, const double* b, co
                 "pre-smoothing sweeps, z-star grid operator without exception rows, distinct 16-byte aligned buffers)", level);
   MG_TRY(k_four_stage(h, (int)level - 1, b, x, tp, rp));
   if (norm_r) MG_TRY(scalar_sync(h, norm_r));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   prof_collect(h);
   return MG_OK;
 }
@@ -776,7 +763,7 @@ int mg_transpose_hierarchy(mg_hierarchy* h) {
   if (h->coarse_lu) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is held as sparse factors: re-upload the transposed hierarchy");
   (void)hipSetDevice(h->device);
   graphs_clear(h);
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   const int nl = (int)h->nlevels;
   std::vector<long long> cp, rv;
   std::vector<double> nz;
@@ -952,24 +939,24 @@ int mg_cycle_mixed_FP32(mg_hierarchy* h, const float* b32, float* z32, long long
   (void)hipSetDevice(h->device);
   const long long len = n * nrhs;
   float* f32 = reinterpret_cast<float*>(h->stage_t.p);              // n*nrhs doubles of scratch hold n*nrhs floats twice over
-  HIP_TRY(hipMemcpyAsync(f32, b32, sizeof(float) * (size_t)len, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(f32, b32, sizeof(float) * (size_t)len, hipMemcpyHostToDevice, h->play->stream));
   if (nrhs == 1) {
-    hipLaunchKernelGGL(mgk::f32_to_f64, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->stream, f32, h->stage_b.p, len);
+    hipLaunchKernelGGL(mgk::f32_to_f64, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->play->stream, f32, h->stage_b.p, len);
   } else {   // column-major float -> row-major double through stage_x
-    hipLaunchKernelGGL(mgk::f32_to_f64, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->stream, f32, h->stage_x.p, len);
-    hipLaunchKernelGGL(mgk::colmajor_to_rowmajor, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->stream, h->stage_x.p, h->stage_b.p, n, (int)nrhs);
+    hipLaunchKernelGGL(mgk::f32_to_f64, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->play->stream, f32, h->stage_x.p, len);
+    hipLaunchKernelGGL(mgk::colmajor_to_rowmajor, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->play->stream, h->stage_x.p, h->stage_b.p, n, (int)nrhs);
   }
   HIP_TRY(hipGetLastError());
   MG_TRY(cycle_dev(h, h->stage_b.p, h->stage_x.p, true));
   if (nrhs == 1) {
-    hipLaunchKernelGGL(mgk::f64_to_f32, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->stream, h->stage_x.p, f32, len);
+    hipLaunchKernelGGL(mgk::f64_to_f32, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->play->stream, h->stage_x.p, f32, len);
   } else {
-    hipLaunchKernelGGL(mgk::rowmajor_to_colmajor, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->stream, h->stage_x.p, h->stage_b.p, n, (int)nrhs);
-    hipLaunchKernelGGL(mgk::f64_to_f32, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->stream, h->stage_b.p, f32, len);
+    hipLaunchKernelGGL(mgk::rowmajor_to_colmajor, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->play->stream, h->stage_x.p, h->stage_b.p, n, (int)nrhs);
+    hipLaunchKernelGGL(mgk::f64_to_f32, dim3(grid_for(len)), dim3(mgk::BLK), 0, h->play->stream, h->stage_b.p, f32, len);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(z32, f32, sizeof(float) * (size_t)len, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(hipMemcpyAsync(z32, f32, sizeof(float) * (size_t)len, hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   prof_collect(h);
   return MG_OK;
 }
@@ -1189,7 +1176,7 @@ int mg_lu_time_dev(mg_lu* f, const double* b_dev, double* x_dev, long long n, lo
     MG_TRY(lu_hierarchy(f, doTranspose != 0, &h));
     MG_TRY(mg_set_nrhs(h, nrhs));
     MG_TRY(check_ready(h, n, nrhs));
-    stream = h->stream;
+    stream = h->play->stream;
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = MG_OK;
@@ -1265,9 +1252,11 @@ int mg_time_op_dev_FP64(mg_hierarchy* h, long long level, long long kernel, long
   if (coarsest && kernel != MG_K_COARSE && kernel != MG_K_SPMV && kernel != MG_K_RESIDUAL)
     return fail(MG_ERR_INVALID, "kernel %lld does not run on the coarsest level", kernel);
   // operands: the level's own scratch (contents are whatever the last cycle left: finite values)
-  const double* bvec = (l == 0) ? (h->last_b ? h->last_b : h->stage_b.p) : L.b.p;
-  double* xa = (l == 0) ? (h->last_x ? h->last_x : h->stage_x.p) : L.x0.p;
-  double* xb = L.x1.p;
+  Play::Vecs& V = h->play->lev[(size_t)l];
+  double* const Lr = h->play->res(l);
+  const double* bvec = (l == 0) ? (h->last_b ? h->last_b : h->stage_b.p) : V.b.p;
+  double* xa = (l == 0) ? (h->last_x ? h->last_x : h->stage_x.p) : V.x0.p;
+  double* xb = V.x1.p;
   const bool was_prof = h->prof;
   h->prof = false;
   hipEvent_t e0, e1;
@@ -1276,14 +1265,14 @@ int mg_time_op_dev_FP64(mg_hierarchy* h, long long level, long long kernel, long
   double bts = 0.0;
   int rc = MG_OK;
   for (long long it = -2; it < reps && rc == MG_OK; ++it) {  // two untimed warm-up launches
-    if (it == 0) (void)hipEventRecord(e0, h->stream);
+    if (it == 0) (void)hipEventRecord(e0, h->play->stream);
     switch (kernel) {
       case MG_K_SPMV:
-        rc = k_spmv(h, l, MG_K_SPMV, L.A, 1.0, xa, 0.0, L.r.p);
+        rc = k_spmv(h, l, MG_K_SPMV, L.A, 1.0, xa, 0.0, Lr);
         bts = spmv_bytes(L.A, nrhs, false, false);
         break;
       case MG_K_RESIDUAL:
-        rc = k_residual(h, l, L.A, bvec, xa, L.r.p);
+        rc = k_residual(h, l, L.A, bvec, xa, Lr);
         bts = spmv_bytes(L.A, nrhs, true, false);
         break;
       case MG_K_SMOOTH:
@@ -1291,21 +1280,21 @@ int mg_time_op_dev_FP64(mg_hierarchy* h, long long level, long long kernel, long
         bts = spmv_bytes(L.A, nrhs, true, true);
         break;
       case MG_K_RESTRICT:
-        rc = k_spmv(h, l, MG_K_RESTRICT, L.R, 1.0, L.r.p, 0.0, h->lev[(size_t)l + 1].b.p);
+        rc = k_spmv(h, l, MG_K_RESTRICT, L.R, 1.0, Lr, 0.0, h->play->lev[(size_t)l + 1].b.p);
         bts = spmv_bytes(L.R, nrhs, false, false);
         break;
       case MG_K_SMOOTH_RESIDUAL:
-        if (!march2_ok(h, l, xa, xb, L.r.p, nullptr)) rc = fail(MG_ERR_UNSUPPORTED, "level %lld is not served by the two-stage marching kernel", level);
-        else rc = k_smooth_residual(h, l, bvec, xa, xb, L.r.p, nullptr, false);
+        if (!march2_ok(h, l, xa, xb, Lr, nullptr)) rc = fail(MG_ERR_UNSUPPORTED, "level %lld is not served by the two-stage marching kernel", level);
+        else rc = k_smooth_residual(h, l, bvec, xa, xb, Lr, nullptr, false);
         bts = spmv_bytes(L.A, nrhs, true, true) + spmv_bytes(L.A, nrhs, true, false);
         break;
       case MG_K_FOUR_STAGE:
-        if (!march4_ok(h, l, xa, xb, L.r.p)) rc = fail(MG_ERR_UNSUPPORTED, "level %lld is not served by the four-stage pass", level);
-        else rc = k_four_stage(h, l, bvec, xa, xb, L.r.p);
+        if (!march4_ok(h, l, xa, xb, Lr)) rc = fail(MG_ERR_UNSUPPORTED, "level %lld is not served by the four-stage pass", level);
+        else rc = k_four_stage(h, l, bvec, xa, xb, Lr);
         bts = 2.0 * (spmv_bytes(L.A, nrhs, true, true) + spmv_bytes(L.A, nrhs, true, false));
         break;
       case MG_K_PROLONG:
-        rc = k_spmv(h, l, MG_K_PROLONG, L.P, 0.0, h->lev[(size_t)l + 1].x0.p, 1.0, xb);
+        rc = k_spmv(h, l, MG_K_PROLONG, L.P, 0.0, h->play->lev[(size_t)l + 1].x0.p, 1.0, xb);
         bts = spmv_bytes(L.P, nrhs, true, false);
         break;
       case MG_K_DSCALE:
@@ -1314,12 +1303,12 @@ int mg_time_op_dev_FP64(mg_hierarchy* h, long long level, long long kernel, long
         break;
       case MG_K_COARSE:
         if (!coarsest) rc = fail(MG_ERR_INVALID, "MG_K_COARSE runs on the coarsest level only");
-        else rc = k_coarse(h, l, L.b.p, L.x0.p);
+        else rc = k_coarse(h, l, V.b.p, V.x0.p);
         bts = h->coarse_lu ? 12.0 * (double)(h->luLval.n + h->luUval.n) + 16.0 * (double)L.n * (double)nrhs
                            : 8.0 * ((double)L.n * (double)L.n + 2.0 * (double)L.n * (double)nrhs);
         break;
       case MG_K_NORM:
-        rc = k_sumsq(h, L.r.p, L.n * nrhs);
+        rc = k_sumsq(h, Lr, L.n * nrhs);
         bts = 8.0 * (double)L.n * (double)nrhs;
         break;
       default:
@@ -1327,15 +1316,15 @@ int mg_time_op_dev_FP64(mg_hierarchy* h, long long level, long long kernel, long
     }
   }
   if (rc == MG_OK) {
-    (void)hipEventRecord(e1, h->stream);
-    hipError_t e = spin_sync(h->stream);
+    (void)hipEventRecord(e1, h->play->stream);
+    hipError_t e = spin_sync(h->play->stream);
     float ms = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
     if (e != hipSuccess) rc = fail(MG_ERR_HIP, "event timing failed: %s", hipGetErrorString(e));
     *ms_avg = (double)ms / (double)reps;
     if (bytes) *bytes = bts;
   }
-  (void)spin_sync(h->stream);
+  (void)spin_sync(h->play->stream);
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   h->prof = was_prof;
@@ -1548,9 +1537,8 @@ int mg_device_bytes(mg_hierarchy* h, double* bytes) {
   MG_REAL_ONLY(h);
   if (!h || !bytes) return fail(MG_ERR_INVALID, "null argument");
   double t = 0.0;
-  for (auto& L : h->lev)
-    t += (double)(L.A.bytes() + L.P.bytes() + L.R.bytes() + L.d.bytes() + L.b.bytes() + L.r.bytes() +
-                  L.x0.bytes() + L.x1.bytes());
+  for (auto& L : h->lev) t += (double)(L.A.bytes() + L.P.bytes() + L.R.bytes() + L.d.bytes());
+  for (auto& V : h->lane0.lev) t += (double)(V.b.bytes() + V.r.bytes() + V.x0.bytes() + V.x1.bytes());
   t += (double)(h->Ainv.bytes() + h->stage_b.bytes() + h->stage_x.bytes() + h->stage_t.bytes());
   *bytes = t;
   return MG_OK;
@@ -2042,10 +2030,10 @@ int mg_set_stream(mg_hierarchy* h, void* stream) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
   (void)hipSetDevice(h->device);
-  (void)spin_sync(h->stream);
-  if (h->owns_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  h->stream = reinterpret_cast<hipStream_t>(stream);
-  h->owns_stream = false;
+  (void)spin_sync(h->lane0.stream);
+  if (h->lane0.owns_stream && h->lane0.stream) (void)hipStreamDestroy(h->lane0.stream);
+  h->lane0.stream = reinterpret_cast<hipStream_t>(stream);
+  h->lane0.owns_stream = false;
   return MG_OK;
 }
 
@@ -2070,7 +2058,6 @@ int mg_kcycle_step_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, l
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   (void)hipSetDevice(h->device);
   if (h->nlevels < 2) return cycle_dev(h, b, x, true);
-  Level& L = h->lev[0];
   if (h->kstepZ.n != (size_t)(2 * n)) {
     MG_TRY(h->kstepZ.alloc((size_t)(2 * n)));
     MG_TRY(h->kstepAZ.alloc((size_t)(2 * n)));
@@ -2078,8 +2065,8 @@ int mg_kcycle_step_async_dev_FP64(mg_hierarchy* h, const double* b, double* x, l
   }
   auto kprec = [&](const double* v, double* z) {
     double* res = nullptr;
-    MG_TRY(cycle_level(h, 0, v, h->kstepX.p, L.x1.p, true, 'K', &res));
-    HIP_TRY(hipMemcpyAsync(z, res, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+    MG_TRY(cycle_level(h, 0, v, h->kstepX.p, h->play->lev[0].x1.p, true, 'K', &res));
+    HIP_TRY(hipMemcpyAsync(z, res, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, h->play->stream));
     return (int)MG_OK;
   };
   return fgmres_relax(h, 0, b, x, 2, kprec, 1e-5, h->kstepZ.p, h->kstepAZ.p, true);
@@ -2236,11 +2223,11 @@ int mg_ghost_finalize(mg_hierarchy* h) {
     const long long counted = g->T.n_allreduce;
     DevBuf<double> tmp;
     MG_TRY(tmp.alloc(cnt));
-    MG_TRY(g->T.stage(cnt, h->stream));
+    MG_TRY(g->T.stage(cnt, h->play->stream));
     double* sums = g->T.h_stage;
     std::copy(flags.begin(), flags.end(), sums);
-    HIP_TRY(hipMemcpyAsync(tmp.p, sums, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    MG_TRY(g->T.allreduce_now(tmp.p, cnt, sums, h->stream));
+    HIP_TRY(hipMemcpyAsync(tmp.p, sums, cnt * sizeof(double), hipMemcpyHostToDevice, h->play->stream));
+    MG_TRY(g->T.allreduce_now(tmp.p, cnt, sums, h->play->stream));
     tmp.release();
     g->T.n_allreduce = counted;
     const double ranks = g->T.sums_global() ? (double)g->T.world : 1.0;   // (how many ranks' flags a sum holds)

@@ -179,7 +179,7 @@ void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::Cx
   D.blk_row = M.blk_row.p;
   D.nblocks = M.nblocks;
   D.n_rows = (int)M.n_rows;
-  hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<MODE, PTR, VT>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->stream, D, v);
+  hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<MODE, PTR, VT>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
 }
 
 template <int MODE>
@@ -204,11 +204,11 @@ int cx_spmv(mg_hierarchy* h, const CxMat& M, const cx_t* x, cx_t* y, const cx_t*
 // ||z||^2 = sum |z_i|^2 into the pinned host scalar: the two-pass deterministic sum
 int cx_norm2(mg_hierarchy* h, const cx_t* z, long long n, double* out) {
   const int np = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n + mgk::BLK - 1) / mgk::BLK));
-  hipLaunchKernelGGL(mgk::cx_sumsq_partial, dim3((unsigned)np), dim3(mgk::BLK), 0, h->stream, z, n, h->partial.p);
-  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, np, h->scalar.p);
+  hipLaunchKernelGGL(mgk::cx_sumsq_partial, dim3((unsigned)np), dim3(mgk::BLK), 0, h->play->stream, z, n, h->play->partial.p);
+  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, np, h->play->scalar.p);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(hipMemcpyAsync(h->h_scalar, h->play->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   *out = h->h_scalar[0];
   return MG_OK;
 }
@@ -217,10 +217,10 @@ int cx_norm2(mg_hierarchy* h, const cx_t* z, long long n, double* out) {
 int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const cx_t* b, const cx_t* x, cx_t* r, double* out) {
   CxState& S = *h->cx;
   MG_TRY(cx_spmv<mgk::RESID>(h, L.A, x, r, b, nullptr, S.partial.p));
-  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, S.partial.p, L.A.nblocks, h->scalar.p);
+  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, S.partial.p, L.A.nblocks, h->play->scalar.p);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(hipMemcpyAsync(h->h_scalar, h->play->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   *out = h->h_scalar[0];
   return MG_OK;
 }
@@ -237,9 +237,9 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x) {
     F.p = S.luP.p; F.q = S.luQ.p;
     F.Lorder = S.luLorder.p; F.Llvl = S.luLlvl.p; F.nLlvl = S.nLlvl;
     F.Uorder = S.luUorder.p; F.Ulvl = S.luUlvl.p; F.nUlvl = S.nUlvl;
-    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, h->stream, F, b, x, cxp(S.luWork), 1);
+    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, h->play->stream, F, b, x, cxp(S.luWork), 1);
   } else {
-    hipLaunchKernelGGL(mgk::cx_dense_matvec, dim3(cx_grid(n * 64)), dim3(mgk::BLK), 0, h->stream,
+    hipLaunchKernelGGL(mgk::cx_dense_matvec, dim3(cx_grid(n * 64)), dim3(mgk::BLK), 0, h->play->stream,
                        reinterpret_cast<const cx_t*>(S.Ainv.p), b, x, (int)n);
   }
   HIP_TRY(hipGetLastError());
@@ -251,7 +251,7 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x) {
 int cx_relax(mg_hierarchy* h, CxLevel& L, const cx_t* b, int& xi, bool xzero, long long numit) {
   long long sweeps = std::max<long long>(numit, 1);
   if (xzero) {
-    hipLaunchKernelGGL(mgk::cx_dscale, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->stream, reinterpret_cast<const cx_t*>(L.d.p), b,
+    hipLaunchKernelGGL(mgk::cx_dscale, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->play->stream, reinterpret_cast<const cx_t*>(L.d.p), b,
                        cxp(L.x[xi]), L.n);
     HIP_TRY(hipGetLastError());
     --sweeps;
@@ -717,11 +717,11 @@ int mg_cycle_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long
   if (x_is_zero < 0) xz = host_all_zero(x, 2 * n);   // norm(x) > 0.0 decides (MGcycle.jl:29)
   const size_t bytes = 2 * sizeof(double) * (size_t)n;
   int xi = 0;
-  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->stream));
-  if (!xz) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
+  if (!xz) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
   MG_TRY(cx_cycle(h, 0, cxp(S.stage_b), xi, xz, h->cycle));
-  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   return MG_OK;
 }
 
@@ -737,12 +737,12 @@ int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long
   const cx_t* bd = cxp(S.stage_b);
   int xi = 0;
   bool xz = host_all_zero(x, 2 * n);
-  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
   double res2 = 0.0;
   if (xz) {   // SolveFuncs.jl:14-21
     MG_TRY(cx_norm2(h, bd, n, &res2));
   } else {
-    HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
     MG_TRY(cx_residual_norm2(h, L0, bd, cxp(L0.x[xi]), cxp(L0.r), &res2));
   }
   const double res0 = std::sqrt(res2);
@@ -757,9 +757,9 @@ int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long
     if (resvec) resvec[count] = res;
     if (res / res0 < tol) break;
   }
-  if (xz) HIP_TRY(hipMemsetAsync(L0.x[xi].p, 0, bytes, h->stream));   // maxIter = 0 from x = 0
-  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
+  if (xz) HIP_TRY(hipMemsetAsync(L0.x[xi].p, 0, bytes, h->play->stream));   // maxIter = 0 from x = 0
+  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   if (iters) *iters = it;
   return MG_OK;
 }
@@ -782,14 +782,14 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
   DevBuf<double> dx, dy;   // (released below on every path)
   int rc = dx.alloc(2 * (size_t)nc);
   if (rc == MG_OK) rc = dy.alloc(2 * (size_t)nr);
-  if (rc == MG_OK && hipMemcpyAsync(dx.p, x, 2 * sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+  if (rc == MG_OK && hipMemcpyAsync(dx.p, x, 2 * sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
     rc = fail(MG_ERR_HIP, "upload of x failed");
-  if (rc == MG_OK && !bz && hipMemcpyAsync(dy.p, y, 2 * sizeof(double) * (size_t)nr, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+  if (rc == MG_OK && !bz && hipMemcpyAsync(dy.p, y, 2 * sizeof(double) * (size_t)nr, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
     rc = fail(MG_ERR_HIP, "upload of y failed");
   if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxp(dx), cxp(dy), nullptr, nullptr, nullptr, a, bt);
-  if (rc == MG_OK && hipMemcpyAsync(y, dy.p, 2 * sizeof(double) * (size_t)nr, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+  if (rc == MG_OK && hipMemcpyAsync(y, dy.p, 2 * sizeof(double) * (size_t)nr, hipMemcpyDeviceToHost, h->play->stream) != hipSuccess)
     rc = fail(MG_ERR_HIP, "download of the product failed");
-  if (spin_sync(h->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_spmv_CF64: stream failed");
+  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_spmv_CF64: stream failed");
   dx.release();
   dy.release();
   return rc;

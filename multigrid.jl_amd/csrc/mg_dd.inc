@@ -367,7 +367,7 @@ int dd_sweeps(mg_dd* d, mg_dd::Set& G, const mgk::DdSub* desc_dev, const T* b, T
             mg_hierarchy* h = nullptr;
             MG_TRY(lu_hierarchy(S.big, adjoint, &h));
             MG_TRY(check_ready(h, n_i, 1));   // (created for one right-hand side and private to this handle: nrhs stays 1)
-            theirs = h->stream;
+            theirs = h->play->stream;
             HIP_TRY(hipStreamWaitEvent(theirs, d->ev_mine, 0));
             MG_TRY(cycle_dev(h, reinterpret_cast<const double*>(r), reinterpret_cast<double*>(t), true));
           }

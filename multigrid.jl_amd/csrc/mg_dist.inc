@@ -601,13 +601,13 @@ int mg_dist_set_tail_INT64(mg_dist* h, mg_hierarchy* tail, long long n_tail, lon
   // The tail enqueues on this sequencer's stream from now on.  Its own stream (if it owns one) is parked, not destroyed,
   // and comes back with mg_dist_release_tail / mg_dist_destroy - the handle stays usable by its owner afterwards.
   graphs_clear(tail);
-  (void)spin_sync(tail->stream);
-  h->tail_prev_stream = tail->stream;
-  h->tail_prev_owns = tail->owns_stream;
+  (void)spin_sync(tail->lane0.stream);
+  h->tail_prev_stream = tail->lane0.stream;
+  h->tail_prev_owns = tail->lane0.owns_stream;
   h->tail_prev_no_graph = tail->opt.no_graph;
   h->tail_borrowed = true;
-  tail->stream = h->stream;
-  tail->owns_stream = false;
+  tail->lane0.stream = h->stream;
+  tail->lane0.owns_stream = false;
   // Measured at world size 1 on 256^3 (bench.py --force-sharded-path): replaying the tail as a HIP graph between the
   // all-gather and the prolongation costs 40-80 us per step (0.98 -> 1.02-1.06 ms) where the single-GPU cycle gains 23:
   // off unless the tail's handle asks for it (mg_set_option(tail, "dist_tail_graph", 1) / MG_DIST_TAIL_GRAPH=1).
@@ -745,8 +745,8 @@ int mg_dist_release_tail(mg_dist* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)spin_sync(h->stream);
     graphs_clear(h->tail);
-    h->tail->stream = h->tail_prev_stream;
-    h->tail->owns_stream = h->tail_prev_owns;
+    h->tail->lane0.stream = h->tail_prev_stream;
+    h->tail->lane0.owns_stream = h->tail_prev_owns;
     h->tail->opt.no_graph = h->tail_prev_no_graph;
   }
   h->tail = nullptr;

@@ -5,10 +5,10 @@ namespace {
 int upload_block(mg_hierarchy* h, const double* host, double* dev, long long n, long long nrhs) {
   const size_t bytes = sizeof(double) * (size_t)n * (size_t)nrhs;
   if (nrhs == 1) {
-    HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->play->stream));
   } else {
-    HIP_TRY(hipMemcpyAsync(h->stage_t.p, host, bytes, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(mgk::colmajor_to_rowmajor, dim3(grid_for(n * nrhs)), dim3(mgk::BLK), 0, h->stream,
+    HIP_TRY(hipMemcpyAsync(h->stage_t.p, host, bytes, hipMemcpyHostToDevice, h->play->stream));
+    hipLaunchKernelGGL(mgk::colmajor_to_rowmajor, dim3(grid_for(n * nrhs)), dim3(mgk::BLK), 0, h->play->stream,
                        h->stage_t.p, dev, n, (int)nrhs);
     HIP_TRY(hipGetLastError());
   }
@@ -17,14 +17,14 @@ int upload_block(mg_hierarchy* h, const double* host, double* dev, long long n, 
 int download_block(mg_hierarchy* h, const double* dev, double* host, long long n, long long nrhs) {
   const size_t bytes = sizeof(double) * (size_t)n * (size_t)nrhs;
   if (nrhs == 1) {
-    HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->play->stream));
   } else {
-    hipLaunchKernelGGL(mgk::rowmajor_to_colmajor, dim3(grid_for(n * nrhs)), dim3(mgk::BLK), 0, h->stream,
+    hipLaunchKernelGGL(mgk::rowmajor_to_colmajor, dim3(grid_for(n * nrhs)), dim3(mgk::BLK), 0, h->play->stream,
                        dev, h->stage_t.p, n, (int)nrhs);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host, h->stage_t.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(host, h->stage_t.p, bytes, hipMemcpyDeviceToHost, h->play->stream));
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   return MG_OK;
 }
 
@@ -1464,21 +1464,13 @@ int alloc_scratch(mg_hierarchy* h) {
       MG_TRY(build_small_prolong(L.P, L.grid, h->lev[(size_t)l + 1].grid));
     }
   }
+  h->lane0.release_vectors();   // (every finalize starts from zeroed vectors)
+  MG_TRY(h->lane0.alloc(h, k, /*fine=*/true));
   long long nmax = 0;
   for (int l = 0; l < (int)h->nlevels; ++l) {
     Level& L = h->lev[l];
     const size_t len = (size_t)L.n * (size_t)k;
     nmax = std::max(nmax, L.n);
-    MG_TRY(L.r.alloc(len));
-    MG_TRY(L.x1.alloc(len));
-    HIP_TRY(hipMemset(L.r.p, 0, L.r.bytes()));
-    HIP_TRY(hipMemset(L.x1.p, 0, L.x1.bytes()));
-    if (l > 0) {
-      MG_TRY(L.b.alloc(len));
-      MG_TRY(L.x0.alloc(len));
-      HIP_TRY(hipMemset(L.b.p, 0, L.b.bytes()));
-      HIP_TRY(hipMemset(L.x0.p, 0, L.x0.bytes()));
-    }
     // FGMRESmem (MGsetup.jl:190-215): memRelax[l] for Jac-GMRES, memKcycle for levels 2..nl-1 of a K-cycle
     L.relaxZ.release();
     L.relaxAZ.release();
@@ -1493,10 +1485,6 @@ int alloc_scratch(mg_hierarchy* h) {
       MG_TRY(L.kZ.alloc(len * 2));
       MG_TRY(L.kAZ.alloc(len * 2));
     }
-  }
-  {  // the fused residual+norm writes one partial per row block
-    const size_t need = (size_t)std::max(h->lev[0].A.nblocks, h->lev[0].A.ln_blocks);
-    if (need > h->partial.n) MG_TRY(h->partial.alloc(need));
   }
   // store sink of the tile-form passes, at its largest size (12 stores x 32 slabs x 1024 lanes = 3 MB): never (re)allocated
   // on the launch path - a launch may sit inside a stream capture, and earlier graphs hold the pointer

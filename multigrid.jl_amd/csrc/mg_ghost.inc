@@ -98,7 +98,7 @@ int gh_check_depths(const mg_hierarchy* h) {
 int gh_exchange_finish(mg_hierarchy* h, int l) {
   GhostLevel* L = gh_level(h, l);
   if (!L || !L->pending) return MG_OK;
-  HIP_TRY(hipStreamWaitEvent(h->stream, L->ev_landed, 0));   // (pending: the exchange went over the side stream)
+  HIP_TRY(hipStreamWaitEvent(h->play->stream, L->ev_landed, 0));   // (pending: the exchange went over the side stream)
   L->pending = nullptr;
   L->pending2 = nullptr;
   return MG_OK;
@@ -125,17 +125,17 @@ int gh_exchange_start(mg_hierarchy* h, int l, double* v, double* v2 = nullptr, b
     else hipLaunchKernelGGL(mgk::ghost_unpack, dim3(nbr), dim3(mgk::BLK), 0, st, L->recv_buf.p, L->recv_idx.p, v, L->n_recv);
   };
   if (L->n_send > 0) {
-    if (v2) hipLaunchKernelGGL(mgk::ghost_pack2, dim3(nbs), dim3(mgk::BLK), 0, h->stream, v, v2, L->send_idx.p, L->send_buf.p, L->send_buf2.p, L->n_send);
-    else hipLaunchKernelGGL(mgk::ghost_pack, dim3(nbs), dim3(mgk::BLK), 0, h->stream, v, L->send_idx.p, L->send_buf.p, L->n_send);
+    if (v2) hipLaunchKernelGGL(mgk::ghost_pack2, dim3(nbs), dim3(mgk::BLK), 0, h->play->stream, v, v2, L->send_idx.p, L->send_buf.p, L->send_buf2.p, L->n_send);
+    else hipLaunchKernelGGL(mgk::ghost_pack, dim3(nbs), dim3(mgk::BLK), 0, h->play->stream, v, L->send_idx.p, L->send_buf.p, L->n_send);
   }
   HIP_TRY(hipGetLastError());
   // (the hop needs a wire to wait for.  Dry, nothing travels: pack and unpack on the compute stream.  Measured, round 6: the unpack of the
   // fine level's prefetch on the side stream - the RCCL transport's structure - costs the dry rank 26 us MORE than the 19 us of kernel time it
   // moves out of the way: 0.5693 against 0.543 ms per step; with a wire to wait for the hop pays, without one it does not.)
   const bool hop = side && g->T.on_stream();
-  hipStream_t xs = hop ? g->side : h->stream;
+  hipStream_t xs = hop ? g->side : h->play->stream;
   if (hop) {
-    HIP_TRY(hipEventRecord(L->ev_packed, h->stream));
+    HIP_TRY(hipEventRecord(L->ev_packed, h->play->stream));
     HIP_TRY(hipStreamWaitEvent(g->side, L->ev_packed, 0));
   }
   const Transport::Pair pairs[2] = {{L->send_buf.p, L->recv_buf.p}, {L->send_buf2.p, L->recv_buf2.p}};
@@ -181,12 +181,12 @@ int gh_allreduce_tail(mg_hierarchy* h, double* v, long long n) {
   mg_ghost* g = h->ghost;
   if (!g || !g->finalized) return MG_OK;
   if (h->capturing && g->T.on_stream()) return fail(MG_ERR_STATE, "an all-reduce inside a graph capture");
-  return g->T.allreduce_dev(v, (size_t)n, h->stream);
+  return g->T.allreduce_dev(v, (size_t)n, h->play->stream);
 }
 // ---- global norms ------------------------------------------------------------------------------------------------------------------
-// h->scalar holds this rank's sum of squares over its OWNED rows: all-reduce it on the stream (RCCL) and copy it into `slot` (pinned);
+// h->play->scalar holds this rank's sum of squares over its OWNED rows: all-reduce it on the stream (RCCL) and copy it into `slot` (pinned);
 // with the plug-in the slot receives the local sum and gh_host_reduce adds the ranks' sums when the host reads it.
-int gh_scalar_to_slot(mg_hierarchy* h, double* slot) { return h->ghost->T.allreduce_start(h->scalar.p, 1, slot, h->stream); }
+int gh_scalar_to_slot(mg_hierarchy* h, double* slot) { return h->ghost->T.allreduce_start(h->play->scalar.p, 1, slot, h->play->stream); }
 int gh_host_reduce(mg_hierarchy* h, double* slot) { return h->ghost ? h->ghost->T.allreduce_finish(slot, 1) : MG_OK; }
 // enqueue: *slot (pinned) <- sum of squares of v over the owned rows [of every rank: RCCL; with the plug-in the local sum, to be passed
 // through gh_host_reduce once the stream has drained]
@@ -198,8 +198,8 @@ int gh_sumsq_own_to_slot(mg_hierarchy* h, const double* v, double* slot) {
   for (int k = 0; k < 3; ++k) { B.lo[k] = L.lo[k]; B.hi[k] = L.hi[k]; }
   const long long lines = (long long)(L.hi[1] - L.lo[1]) * (L.hi[2] - L.lo[2]);
   const int nb = (int)std::max<long long>(1, std::min<long long>(h->nred_blocks, (lines + 3) / 4));
-  hipLaunchKernelGGL(mgk::sumsq_box_partial, dim3(nb), dim3(mgk::BLK), 0, h->stream, v, B, h->partial.p);
-  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, nb, h->scalar.p);
+  hipLaunchKernelGGL(mgk::sumsq_box_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, v, B, h->play->partial.p);
+  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, h->play->scalar.p);
   HIP_TRY(hipGetLastError());
   return gh_scalar_to_slot(h, slot);
 }
@@ -207,7 +207,7 @@ int gh_sumsq_own_to_slot(mg_hierarchy* h, const double* v, double* slot) {
 int gh_norm_own(mg_hierarchy* h, const double* v, double* out) {
   mg_ghost* g = h->ghost;
   MG_TRY(gh_sumsq_own_to_slot(h, v, g->h_norm));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   MG_TRY(gh_host_reduce(h, g->h_norm));
   *out = std::sqrt(*g->h_norm);
   return MG_OK;
@@ -229,11 +229,11 @@ int gh_dots_own(mg_hierarchy* h, int count, const double* const* xs, const doubl
   const long long lines = (long long)(L.hi[1] - L.lo[1]) * (L.hi[2] - L.lo[2]);
   const int nb = (int)std::max<long long>(1, std::min<long long>(h->nred_blocks / 8, (lines + 3) / 4));
   for (int c = 0; c < count; ++c) {
-    hipLaunchKernelGGL(mgk::dot_box_partial, dim3(nb), dim3(mgk::BLK), 0, h->stream, xs[c], ys[c], B, h->partial.p + (size_t)c * nb);
-    hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p + (size_t)c * nb, nb, g->kscal.p + c);
+    hipLaunchKernelGGL(mgk::dot_box_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, xs[c], ys[c], B, h->play->partial.p + (size_t)c * nb);
+    hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p + (size_t)c * nb, nb, g->kscal.p + c);
   }
   HIP_TRY(hipGetLastError());
-  MG_TRY(g->T.allreduce_now(g->kscal.p, (size_t)count, g->h_kscal, h->stream));
+  MG_TRY(g->T.allreduce_now(g->kscal.p, (size_t)count, g->h_kscal, h->play->stream));
   for (int c = 0; c < count; ++c) out[c] = g->h_kscal[c];
   return MG_OK;
 }
@@ -250,12 +250,12 @@ int gh_exchange_block(mg_hierarchy* h, double* V, int k) {
   if (L->recv_blk.n < nr) MG_TRY(L->recv_blk.alloc(nr));
   ProfScope ps(h, 0, MG_K_GHOST, 20.0 * (double)k * (double)(L->n_send + L->n_recv));
   if (L->n_send > 0)
-    hipLaunchKernelGGL(mgk::ghost_pack_block, dim3((unsigned)((L->n_send * k + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, h->stream, V, L->send_idx.p, L->send_blk.p, L->n_send, k);
+    hipLaunchKernelGGL(mgk::ghost_pack_block, dim3((unsigned)((L->n_send * k + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, h->play->stream, V, L->send_idx.p, L->send_blk.p, L->n_send, k);
   HIP_TRY(hipGetLastError());
   const Transport::Pair pair = {L->send_blk.p, L->recv_blk.p};
-  MG_TRY(g->T.exchange(&pair, 1, L->send_splits, L->recv_splits, k, h->stream));
+  MG_TRY(g->T.exchange(&pair, 1, L->send_splits, L->recv_splits, k, h->play->stream));
   if (L->n_recv > 0)
-    hipLaunchKernelGGL(mgk::ghost_unpack_block, dim3((unsigned)((L->n_recv * k + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, h->stream, L->recv_blk.p, L->recv_idx.p, V, L->n_recv, k);
+    hipLaunchKernelGGL(mgk::ghost_unpack_block, dim3((unsigned)((L->n_recv * k + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, h->play->stream, L->recv_blk.p, L->recv_idx.p, V, L->n_recv, k);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -271,11 +271,11 @@ int gh_gram_own(mg_hierarchy* h, const double* X, const double* Y, int k, double
   const size_t kk = (size_t)k * k;
   if (partial.n < (size_t)nb * kk + kk) MG_TRY(partial.alloc((size_t)nb * kk + kk));
   double* out = partial.p + (size_t)nb * kk;
-  hipLaunchKernelGGL(mgk::blk_gram_box_partial, dim3(nb, k), dim3(mgk::BLK), 0, h->stream, X, Y, B, k, partial.p);
-  hipLaunchKernelGGL(mgk::blk_gram_final, dim3(1), dim3(mgk::BLK), 0, h->stream, partial.p, nb, k, out);
+  hipLaunchKernelGGL(mgk::blk_gram_box_partial, dim3(nb, k), dim3(mgk::BLK), 0, h->play->stream, X, Y, B, k, partial.p);
+  hipLaunchKernelGGL(mgk::blk_gram_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, partial.p, nb, k, out);
   HIP_TRY(hipGetLastError());
-  MG_TRY(g->T.stage(kk, h->stream));
-  MG_TRY(g->T.allreduce_now(out, kk, g->T.h_stage, h->stream));
+  MG_TRY(g->T.stage(kk, h->play->stream));
+  MG_TRY(g->T.allreduce_now(out, kk, g->T.h_stage, h->play->stream));
   std::memcpy(G, g->T.h_stage, sizeof(double) * kk);
   return MG_OK;
 }
@@ -298,7 +298,7 @@ int gh_begin(mg_hierarchy* h, const double** b, double* x, bool x_zero) {
     g->lev[(size_t)l].depth.clear();
   }
   if (!gh_level(h, 0)) return MG_OK;
-  HIP_TRY(hipMemcpyAsync(g->b0.p, *b, sizeof(double) * (size_t)g->lev[0].n, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(g->b0.p, *b, sizeof(double) * (size_t)g->lev[0].n, hipMemcpyDeviceToDevice, h->play->stream));
   gh_set(h, 0, g->b0.p, 0);
   MG_TRY(gh_need(h, 0, g->b0.p, GH_FULL));
   *b = g->b0.p;

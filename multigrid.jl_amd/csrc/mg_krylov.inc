@@ -55,7 +55,7 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
             long long* flag_out, double* resvec) {
   Level& L = h->lev[0];
   const long long n = L.n;
-  if (h->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "mg_pcg: block right-hand sides (KrylovMethods.blockCG) are not on the device path yet");
+  if (h->play->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "mg_pcg: block right-hand sides (KrylovMethods.blockCG) are not on the device path yet");
   if (h->kr.n != (size_t)n) {
     MG_TRY(h->kr.alloc((size_t)n));
     MG_TRY(h->kz.alloc((size_t)n));
@@ -72,20 +72,20 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
   long long it = 0, flag = -1;
   if (nr0 == 0.0) {  // cg returns zeros, flag -9
     MG_TRY(k_fill(h, x, n, 0.0));
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     if (iters) *iters = 0;
     if (flag_out) *flag_out = -9;
     return MG_OK;
   }
   MG_TRY(K.residual(b, x, r));                                         // r = b - A(x)
   MG_TRY(cycle_dev(h, r, z, true));                                    // z = M(r), x = 0 on entry
-  HIP_TRY(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(p, z, sizeof(double) * n, hipMemcpyDeviceToDevice, h->play->stream));
   // Three passes of the textbook loop are folded into their neighbours (same values, fewer sweeps over the vectors and one
   // host synchronisation less per iteration): gamma = r'z of iteration k+1 IS z'r of iteration k (computed once); p'Ap comes
   // out of the product kernel where the marching kernel serves A (partials of p[row]*Ap[row]); ||r||^2 out of the update.
   double gamma = 0.0;
   MG_TRY(K.dot(r, z, &gamma));
-  const int nb_upd = (int)std::min<long long>(grid_for(n), (long long)h->partial.n);
+  const int nb_upd = (int)std::min<long long>(grid_for(n), (long long)h->play->partial.n);
   for (long long k = 1; k <= maxIter; ++k) {
     it = k;
     double pAp = 0.0, rn = 0.0;
@@ -98,12 +98,12 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
     const double alpha = gamma / pAp;
     if (std::isinf(alpha) || alpha < 0.0) { flag = -2; break; }
     if (K.ghs) {
-      hipLaunchKernelGGL(mgk::cg_update_xr, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->stream, alpha, p, Ap, x, r, n);
+      hipLaunchKernelGGL(mgk::cg_update_xr, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, alpha, p, Ap, x, r, n);
       HIP_TRY(hipGetLastError());
       MG_TRY(K.norm(r, &rn));
     } else {
-      hipLaunchKernelGGL(mgk::cg_update_xr_norm, dim3(nb_upd), dim3(mgk::BLK), 0, h->stream, alpha, p, Ap, x, r, n, h->partial.p);
-      launch_sum_final(h, h->partial.p, nb_upd);
+      hipLaunchKernelGGL(mgk::cg_update_xr_norm, dim3(nb_upd), dim3(mgk::BLK), 0, h->play->stream, alpha, p, Ap, x, r, n, h->play->partial.p);
+      launch_sum_final(h, h->play->partial.p, nb_upd);
       HIP_TRY(hipGetLastError());
       MG_TRY(scalar_sync(h, &rn));
     }
@@ -114,10 +114,10 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
     MG_TRY(K.dot(z, r, &zr));
     const double beta = zr / gamma;
     gamma = zr;                                                        // = r'z at the top of the next iteration
-    hipLaunchKernelGGL(mgk::cg_update_p, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->stream, beta, z, p, n);
+    hipLaunchKernelGGL(mgk::cg_update_p, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, beta, z, p, n);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   if (iters) *iters = it;
   if (flag_out) *flag_out = flag;
   return K.done();
@@ -132,7 +132,7 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
                  long long* flag_out, double* resvec, long long* nres) {
   Level& L = h->lev[0];
   const long long n = L.n;
-  if (h->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "mg_bicgstab: block right-hand sides (blockBiCGSTB) are not on the device path yet");
+  if (h->play->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "mg_bicgstab: block right-hand sides (blockBiCGSTB) are not on the device path yet");
   if (h->kr.n != (size_t)n) {
     MG_TRY(h->kr.alloc((size_t)n));
     MG_TRY(h->kz.alloc((size_t)n));
@@ -153,7 +153,7 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
   long long it = 0, flag = -1, nr = 0;
   if (bn == 0.0) {
     MG_TRY(k_fill(h, x, n, 0.0));
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     if (iters) *iters = 0;
     if (flag_out) *flag_out = -9;
     if (nres) *nres = 0;
@@ -170,7 +170,7 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
     if (nres) *nres = nr;
     return MG_OK;
   }
-  HIP_TRY(hipMemcpyAsync(rtld, r, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(rtld, r, sizeof(double) * n, hipMemcpyDeviceToDevice, h->play->stream));
   double omega = 1.0, alpha = 0.0, rho1 = 0.0;
   for (long long k = 1; k <= maxIter; ++k) {
     it = k;
@@ -182,7 +182,7 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
       MG_TRY(k_axpby(h, -omega, v, 1.0, p, n));      // p = p - omega v
       MG_TRY(k_axpby(h, 1.0, r, beta, p, n));        // p = r + beta p
     } else {
-      HIP_TRY(hipMemcpyAsync(p, r, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+      HIP_TRY(hipMemcpyAsync(p, r, sizeof(double) * n, hipMemcpyDeviceToDevice, h->play->stream));
     }
     MG_TRY(cycle_dev(h, p, phat, true));              // p_hat = M1(p)
     MG_TRY(K.apply(phat, v));
@@ -215,7 +215,7 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
     if (omega == 0.0) { flag = -2; break; }
     rho1 = rho;
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   if (iters) *iters = it;
   if (flag_out) *flag_out = flag;
   if (nres) *nres = nr;
@@ -233,7 +233,7 @@ int fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBu
                 double* resvec, long long* nres) {
   Level& L = h->lev[(size_t)lv];
   const long long n = L.n;
-  if (h->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "fgmres: block right-hand sides (blockFGMRES) are not on the device path yet");
+  if (h->play->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "fgmres: block right-hand sides (blockFGMRES) are not on the device path yet");
   if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
   const int m = (int)inner;
   if (work.n != (size_t)n * (size_t)(2 * m + 2)) MG_TRY(work.alloc((size_t)n * (size_t)(2 * m + 2)));
@@ -248,7 +248,7 @@ int fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBu
   long long nr = 0, flag = -1, total = 0;
   if (bn == 0.0) {
     MG_TRY(k_fill(h, x, n, 0.0));
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     if (iters) *iters = 0;
     if (flag_out) *flag_out = -9;
     if (nres) *nres = 0;
@@ -300,17 +300,17 @@ int fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBu
         if (!h->h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_kscal), sizeof(double) * 66));
         const int nb = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n / 2 + mgk::BLK - 1) / mgk::BLK));
         double* hd = h->kscal.p;
-        hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->stream, w, V, n, h->partial.p);
-        hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, nb, hd);
+        hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, w, V, n, h->play->partial.p);
+        hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd);
         for (int k = 0; k <= i; ++k) {
-          hipLaunchKernelGGL(mgk::mgs_step, dim3(nb), dim3(mgk::BLK), 0, h->stream, hd + k, V + (size_t)k * n, w,
-                             k < i ? V + (size_t)(k + 1) * n : (const double*)nullptr, n, h->partial.p);
-          hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, nb, hd + k + 1);
+          hipLaunchKernelGGL(mgk::mgs_step, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, hd + k, V + (size_t)k * n, w,
+                             k < i ? V + (size_t)(k + 1) * n : (const double*)nullptr, n, h->play->partial.p);
+          hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd + k + 1);
         }
-        hipLaunchKernelGGL(mgk::scale_rsqrt, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->stream, hd + i + 1, w, n);
+        hipLaunchKernelGGL(mgk::scale_rsqrt, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, hd + i + 1, w, n);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h->h_kscal, hd, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(spin_sync(h->stream));
+        HIP_TRY(hipMemcpyAsync(h->h_kscal, hd, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, h->play->stream));
+        HIP_TRY(spin_sync(h->play->stream));
         for (int k = 0; k <= i; ++k) Hat(k, i) = h->h_kscal[k];
         Hat(i + 1, i) = std::sqrt(h->h_kscal[i + 1]);
       }
@@ -347,7 +347,7 @@ int fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBu
     err = rn / bn;
     if (err <= tol) { flag = 0; break; }
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   if (iters) *iters = total;
   if (flag_out) *flag_out = flag;
   if (nres) *nres = nr;
@@ -498,11 +498,11 @@ int blk_gram(mg_hierarchy* h, const double* X, const double* Y, long long n, int
   if (h->blk_partial.n < (size_t)nb * k * k + (size_t)k * k) MG_TRY(h->blk_partial.alloc((size_t)nb * k * k + (size_t)k * k));
   if (!h->h_blk) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_blk), sizeof(double) * mgk::BLK_KMAX * mgk::BLK_KMAX));
   double* out = h->blk_partial.p + (size_t)nb * k * k;
-  hipLaunchKernelGGL(mgk::blk_gram_partial, dim3(nb, k), dim3(mgk::BLK), 0, h->stream, X, Y, n, k, h->blk_partial.p);
-  hipLaunchKernelGGL(mgk::blk_gram_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->blk_partial.p, nb, k, out);
+  hipLaunchKernelGGL(mgk::blk_gram_partial, dim3(nb, k), dim3(mgk::BLK), 0, h->play->stream, X, Y, n, k, h->blk_partial.p);
+  hipLaunchKernelGGL(mgk::blk_gram_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->blk_partial.p, nb, k, out);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_blk, out, sizeof(double) * k * k, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(hipMemcpyAsync(h->h_blk, out, sizeof(double) * k * k, hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   G = SmallMat(k, k);
   std::memcpy(G.a.data(), h->h_blk, sizeof(double) * k * k);
   return MG_OK;
@@ -515,11 +515,11 @@ int blk_comb(mg_hierarchy* h, double* out, const double* add, double s, const do
   constexpr size_t SLOT = (size_t)mgk::BLK_KMAX * mgk::BLK_KMAX;
   if (!h->h_blk_c) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_blk_c), sizeof(double) * SLOT * 8));
   const unsigned si = h->blk_c_next++ % 8;
-  if (si == 0 && h->blk_c_next > 1) HIP_TRY(spin_sync(h->stream));
+  if (si == 0 && h->blk_c_next > 1) HIP_TRY(spin_sync(h->play->stream));
   double* slot = h->blk_c.p + si * SLOT;
   std::memcpy(h->h_blk_c + si * SLOT, Cm.a.data(), sizeof(double) * k * k);
-  HIP_TRY(hipMemcpyAsync(slot, h->h_blk_c + si * SLOT, sizeof(double) * k * k, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(mgk::blk_comb, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->stream, out, add, s, in, slot, n, k);
+  HIP_TRY(hipMemcpyAsync(slot, h->h_blk_c + si * SLOT, sizeof(double) * k * k, hipMemcpyHostToDevice, h->play->stream));
+  hipLaunchKernelGGL(mgk::blk_comb, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, out, add, s, in, slot, n, k);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -545,11 +545,11 @@ int blk_work(mg_hierarchy* h, size_t nblocks, long long n, int k, double** base)
 // Sharded (ghost-layer form, round 6): the blocks are [n_ext][k] with their owned rows valid - a product with A follows ONE exchange of
 // the block's ghost layers, the preconditioner is the block's columns through the sharded cycle, Gram matrices are sums over owned rows.
 int blk_apply(mg_hierarchy* h, int lv, double* P, double* Q) {
-  if (lv == 0 && gh_global_scalars(h)) MG_TRY(gh_exchange_block(h, P, (int)h->nrhs));
+  if (lv == 0 && gh_global_scalars(h)) MG_TRY(gh_exchange_block(h, P, (int)h->play->nrhs));
   return k_spmv(h, lv, MG_K_SPMV, h->lev[(size_t)lv].A, 1.0, P, 0.0, Q);
 }
 int blk_residual(mg_hierarchy* h, int lv, const double* B, double* X, double* R) {
-  if (lv == 0 && gh_global_scalars(h)) MG_TRY(gh_exchange_block(h, X, (int)h->nrhs));
+  if (lv == 0 && gh_global_scalars(h)) MG_TRY(gh_exchange_block(h, X, (int)h->play->nrhs));
   return k_residual(h, lv, h->lev[(size_t)lv].A, B, X, R);
 }
 int blk_cycle(mg_hierarchy* h, const double* R, double* Z) {
@@ -562,7 +562,7 @@ int block_pcg_dev(mg_hierarchy* h, const double* B, double* X, double tol, long 
                   long long* flag_out, double* resmat) {
   Level& L = h->lev[0];
   const long long n = L.n;
-  const int k = (int)h->nrhs;
+  const int k = (int)h->play->nrhs;
   if (k > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "block Krylov drivers hold at most %d right-hand sides", mgk::BLK_KMAX);
   const size_t len = (size_t)n * k;
   double* w = nullptr;
@@ -575,7 +575,7 @@ int block_pcg_dev(mg_hierarchy* h, const double* B, double* X, double tol, long 
   for (double v : nb) any = any || v > 0.0;
   if (!any) {
     MG_TRY(k_fill(h, X, (long long)len, 0.0));
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     if (iters) *iters = 0;
     if (flag_out) *flag_out = -9;
     return MG_OK;
@@ -583,7 +583,7 @@ int block_pcg_dev(mg_hierarchy* h, const double* B, double* X, double tol, long 
   for (double& v : nb) if (!(v > 0.0)) v = 1.0;
   MG_TRY(blk_residual(h, 0, B, X, R));                         // R = B - A X
   MG_TRY(blk_cycle(h, R, Z));                               // Z = M(R)
-  HIP_TRY(hipMemcpyAsync(P, Z, sizeof(double) * len, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(P, Z, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
   for (long long iter = 1; iter <= maxIter; ++iter) {
     it = iter;
     MG_TRY(blk_apply(h, 0, P, Q));         // Q = A P
@@ -615,7 +615,7 @@ int block_pcg_dev(mg_hierarchy* h, const double* B, double* X, double tol, long 
     for (double& v : Beta.a) v = -v;
     MG_TRY(blk_comb(h, P, Z, 1.0, P, Beta, n, k));                // P = Z + P Beta
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   if (iters) *iters = it;
   if (flag_out) *flag_out = flag;
   return MG_OK;
@@ -626,7 +626,7 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
                        long long* flag_out, double* resvec, long long* nres) {
   Level& L = h->lev[0];
   const long long n = L.n;
-  const int k = (int)h->nrhs;
+  const int k = (int)h->play->nrhs;
   if (k > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "block Krylov drivers hold at most %d right-hand sides", mgk::BLK_KMAX);
   const size_t len = (size_t)n * k;
   double* w = nullptr;
@@ -645,7 +645,7 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
   };
   if (!any) {
     MG_TRY(k_fill(h, X, (long long)len, 0.0));
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     return finish(-9);
   }
   for (double& v : nb) if (!(v > 0.0)) v = 1.0;
@@ -662,8 +662,8 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
   if (resvec) resvec[nr] = err;
   ++nr;
   if (err < tol) return finish(0);
-  HIP_TRY(hipMemcpyAsync(R0, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(P, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(R0, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
+  HIP_TRY(hipMemcpyAsync(P, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
   const SmallMat I1 = sm_scaled_identity(k, 1.0);
   for (long long iter = 1; iter <= maxIter; ++iter) {
     it = iter;
@@ -709,7 +709,7 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
     MG_TRY(blk_comb(h, P, P, 1.0, V, sm_scaled_identity(k, -omega), n, k));   // P - omega V
     MG_TRY(blk_comb(h, P, R, 1.0, P, beta, n, k));                // P = R + (P - omega V) beta
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   return finish(flag);
 }
 
@@ -734,7 +734,7 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
                       double* resvec, long long* nres) {
   Level& L = h->lev[(size_t)lv];
   const long long n = L.n;
-  const int k = (int)h->nrhs;
+  const int k = (int)h->play->nrhs;
   if (k > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "block Krylov drivers hold at most %d right-hand sides", mgk::BLK_KMAX);
   if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
   if (precond == 0 && lv != 0) return fail(MG_ERR_INVALID, "the cycle preconditions the fine level only");
@@ -770,7 +770,7 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
   MG_TRY(fro(B, &bn));
   if (bn == 0.0) {
     MG_TRY(k_fill(h, X, (long long)len, 0.0));
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     return finish(-9);
   }
   MG_TRY(blk_residual(h, lv, B, X, R));
@@ -778,7 +778,7 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
   if (rn / bn < tol) return finish(0);
   for (long long it = 1; it <= maxIter && flag != 0; ++it) {
     SmallMat H((m + 1) * k, m * k), xi((m + 1) * k, k), Rf, Y;
-    HIP_TRY(hipMemcpyAsync(Vb, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(Vb, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
     MG_TRY(blk_cholqr(h, Vb, n, k, Rf));
     for (int i = 0; i < k; ++i)
       for (int j = 0; j < k; ++j) xi(i, j) = Rf(i, j);
@@ -825,7 +825,7 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
     MG_TRY(fro(R, &rn));
     if (rn / bn <= tol) { flag = 0; break; }
   }
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   return finish(flag);
 }
 int block_fgmres_dev(mg_hierarchy* h, const double* B, double* X, long long inner, double tol, long long maxIter,

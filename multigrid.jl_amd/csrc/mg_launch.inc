@@ -60,10 +60,10 @@ hipEvent_t get_event(mg_hierarchy* h) {
   return e;
 }
 
-// h->scalar = sum of np partials, also stored straight into the pinned h_scalar (scalar_sync then needs no copy)
+// h->play->scalar = sum of np partials, also stored straight into the pinned h_scalar (scalar_sync then needs no copy)
 void launch_sum_final(mg_hierarchy* h, const double* partial, int np) {
-  hipLaunchKernelGGL(mgk::sum_final_mirror, dim3(1), dim3(mgk::BLK), 0, h->stream, partial, np, h->scalar.p, h->h_scalar);
-  h->scalar_mirrored = !h->capturing;
+  hipLaunchKernelGGL(mgk::sum_final_mirror, dim3(1), dim3(mgk::BLK), 0, h->play->stream, partial, np, h->play->scalar.p, h->h_scalar);
+  h->play->scalar_mirrored = !h->capturing;
 }
 struct ProfScope {
   mg_hierarchy* h;
@@ -77,11 +77,11 @@ struct ProfScope {
     p.kernel = kernel;
     p.bytes = bytes;
     p.moved = moved < 0.0 ? bytes : moved;
-    (void)hipEventRecord(p.a, h->stream);
+    (void)hipEventRecord(p.a, h->play->stream);
   }
   ~ProfScope() {
     if (!on) return;
-    (void)hipEventRecord(p.b, h->stream);
+    (void)hipEventRecord(p.b, h->play->stream);
     h->pending.push_back(p);
   }
 };
@@ -460,9 +460,9 @@ int launch_csr(hipStream_t stream, const Csr& M, const mgk::VecArgs& v, int* npa
 int flush_deferred_sum(mg_hierarchy* h) {
   if (!h->dsum.on) return MG_OK;
   h->dsum.on = false;
-  hipLaunchKernelGGL(mgk::sum_final_mirror, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, h->dsum.np, h->scalar.p, h->dsum.host);
+  hipLaunchKernelGGL(mgk::sum_final_mirror, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, h->dsum.np, h->play->scalar.p, h->dsum.host);
   HIP_TRY(hipGetLastError());
-  if (h->dsum.ev) HIP_TRY(hipEventRecord(h->dsum.ev, h->stream));
+  if (h->dsum.ev) HIP_TRY(hipEventRecord(h->dsum.ev, h->play->stream));
   return MG_OK;
 }
 // y = alpha*M*x + beta*y
@@ -471,13 +471,13 @@ int k_spmv(mg_hierarchy* h, int level, int kind, const Csr& M, double alpha, con
            double beta, double* y, const double* d2 = nullptr, double* y2 = nullptr) {
   if (h->dsum.on) {
     // the fine restriction behind a four-stage pass: its grid takes one more workgroup, which adds up the pass's partial sums
-    if (kind == MG_K_RESTRICT && level == 0 && h->nrhs == 1 && M.waver_ok && !M.wide && alpha == 1.0 && beta == 0.0 && y && y != x && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !h->prof && !h->capturing) {
+    if (kind == MG_K_RESTRICT && level == 0 && h->play->nrhs == 1 && M.waver_ok && !M.wide && alpha == 1.0 && beta == 0.0 && y && y != x && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !h->prof && !h->capturing) {
       const long long waves = (M.n_rows + 61) / 62;
       h->dsum.on = false;
-      hipLaunchKernelGGL(mgk::grid_wave_restrict, dim3((unsigned)((waves + 3) / 4 + 1)), dim3(256), 0, h->stream, M.smr, M.waver_scale, x, y,
-                         y2 ? d2 : nullptr, y2, mgk::FinalSum{h->partial.p, h->dsum.np, h->scalar.p, h->dsum.host});
+      hipLaunchKernelGGL(mgk::grid_wave_restrict, dim3((unsigned)((waves + 3) / 4 + 1)), dim3(256), 0, h->play->stream, M.smr, M.waver_scale, x, y,
+                         y2 ? d2 : nullptr, y2, mgk::FinalSum{h->play->partial.p, h->dsum.np, h->play->scalar.p, h->dsum.host});
       HIP_TRY(hipGetLastError());
-      if (h->dsum.ev) HIP_TRY(hipEventRecord(h->dsum.ev, h->stream));
+      if (h->dsum.ev) HIP_TRY(hipEventRecord(h->dsum.ev, h->play->stream));
       return MG_OK;
     }
     MG_TRY(flush_deferred_sum(h));
@@ -487,17 +487,17 @@ int k_spmv(mg_hierarchy* h, int level, int kind, const Csr& M, double alpha, con
   v.y = y;
   v.alpha = alpha;
   v.beta = beta;
-  v.nrhs = (int)h->nrhs;
+  v.nrhs = (int)h->play->nrhs;
   v.d_full = d2;
   v.y2 = y2;
   const double extra = y2 ? 16.0 * (double)M.n_rows : 0.0;
-  ProfScope ps(h, level, kind, spmv_bytes(M, h->nrhs, beta != 0.0, false) + extra, moved_bytes(M, h->nrhs, beta != 0.0, false) + extra);
-  return launch_csr<mgk::AXPBY>(h->stream, M, v);
+  ProfScope ps(h, level, kind, spmv_bytes(M, h->play->nrhs, beta != 0.0, false) + extra, moved_bytes(M, h->play->nrhs, beta != 0.0, false) + extra);
+  return launch_csr<mgk::AXPBY>(h->play->stream, M, v);
 }
 // Is the product with M served, for one right-hand side, by a kernel that can write d.*out too (csr_rowclass_lane_spmv, or the
 // streaming kernels csr_pattern_spmv / csr_stream_spmv for operators without row classes)?
 bool restrict_can_scale(const mg_hierarchy* h, const Csr& M) {
-  if (h->nrhs != 1 || h->opt.no_restrict_scale) return false;
+  if (h->play->nrhs != 1 || h->opt.no_restrict_scale) return false;
   if (M.smr_use() || M.waver_ok) return true;
   if (!M.has_rc) return M.max_row_nnz <= mgk::CHUNK - 2;   // the streaming kernels (pattern-coded or plain CSR), short rows: epilogue output
   if (M.rc_marchr && !M.opt.no_marchr) return true;
@@ -510,15 +510,15 @@ int k_residual(mg_hierarchy* h, int level, const Csr& A, const double* b, const 
   v.x = x;
   v.y = out;
   v.b = b;
-  v.nrhs = (int)h->nrhs;
-  ProfScope ps(h, level, MG_K_RESIDUAL, spmv_bytes(A, h->nrhs, true, false), moved_bytes(A, h->nrhs, true, false));
-  return launch_csr<mgk::RESID>(h->stream, A, v);
+  v.nrhs = (int)h->play->nrhs;
+  ProfScope ps(h, level, MG_K_RESIDUAL, spmv_bytes(A, h->play->nrhs, true, false), moved_bytes(A, h->play->nrhs, true, false));
+  return launch_csr<mgk::RESID>(h->play->stream, A, v);
 }
 // ---- two launches of a small level as one (mg_small.hpp: grid27_small_resid_restrict / grid27_small_prolong_smooth) -----------------
 // the level's A has position-class records whose relaxPrec is the level's, its transfers are the verified arithmetic forms of an
 // ORDINARY grid pair (not an embedded one), one right-hand side (the caller keeps sharded levels out)
 bool small_fuse_rr_ok(const mg_hierarchy* h, int level) {
-  if (h->opt.no_small_fuse || h->nrhs != 1 || level + 1 >= (int)h->nlevels) return false;
+  if (h->opt.no_small_fuse || h->play->nrhs != 1 || level + 1 >= (int)h->nlevels) return false;
   const Level& L = h->lev[(size_t)level];
   const Csr &A = L.A, &R = L.R;
   if (!A.sm_ok || !R.waver_ok || R.waver_scale == 0.0) return false;
@@ -527,7 +527,7 @@ bool small_fuse_rr_ok(const mg_hierarchy* h, int level) {
          T.nf1 == 2 * T.nc1 - 1 && T.nf2 == 2 * T.nc2 - 1 && T.nf3 == 2 * T.nc3 - 1;
 }
 bool small_fuse_ps_ok(const mg_hierarchy* h, int level) {
-  if (h->opt.no_small_fuse || h->nrhs != 1 || level + 1 >= (int)h->nlevels || h->relax_type != 0) return false;
+  if (h->opt.no_small_fuse || h->play->nrhs != 1 || level + 1 >= (int)h->nlevels || h->relax_type != 0) return false;
   const Level& L = h->lev[(size_t)level];
   const Csr &A = L.A, &P = L.P;
   if (!A.sm_ok || !A.sm_d_bound || A.sm_d_bound != L.d.p || !(P.cellp_ok || P.smp_ok)) return false;
@@ -541,7 +541,7 @@ int k_small_resid_restrict(mg_hierarchy* h, int level, const double* b, const do
   const double bytes = 8.0 * (2.0 * (double)L.A.n_rows + (double)L.R.n_rows * (y2 ? 3.0 : 1.0));
   ProfScope ps(h, level, MG_K_RESTRICT, bytes, bytes);
   const unsigned nb = (unsigned)(((T.nc1 + mgk::SRR_CT - 1) / mgk::SRR_CT) * ((T.nc2 + mgk::SRR_CT - 1) / mgk::SRR_CT) * ((T.nc3 + mgk::SRR_CT - 1) / mgk::SRR_CT));
-  hipLaunchKernelGGL(mgk::grid27_small_resid_restrict, dim3(nb), dim3(256), 0, h->stream, L.A.sm, T, L.R.waver_scale, x, b, bc, y2 ? d2 : nullptr, y2);
+  hipLaunchKernelGGL(mgk::grid27_small_resid_restrict, dim3(nb), dim3(256), 0, h->play->stream, L.A.sm, T, L.R.waver_scale, x, b, bc, y2 ? d2 : nullptr, y2);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -552,12 +552,12 @@ int k_small_prolong_smooth(mg_hierarchy* h, int level, const double* xc, const d
   const double bytes = 8.0 * (3.0 * (double)L.A.n_rows + (double)L.P.n_cols);
   ProfScope ps(h, level, MG_K_SMOOTH_PROLONG, bytes, bytes);
   const unsigned nb = (unsigned)(((A.n1 + mgk::SPS_TX - 1) / mgk::SPS_TX) * ((A.n2 + mgk::SPS_TY - 1) / mgk::SPS_TY) * ((A.n3 + mgk::SPS_TZ - 1) / mgk::SPS_TZ));
-  hipLaunchKernelGGL(mgk::grid27_small_prolong_smooth, dim3(nb), dim3(256), 0, h->stream, A, L.P.smp, xc, x, b, y);
+  hipLaunchKernelGGL(mgk::grid27_small_prolong_smooth, dim3(nb), dim3(256), 0, h->play->stream, A, L.P.smp, xc, x, b, y);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 int k_sumsq(mg_hierarchy* h, const double* x, long long len);
-// out = b - A*x and h->scalar = ||out||^2 in the same pass (nrhs == 1); falls back to two kernels for blocks
+// out = b - A*x and h->play->scalar = ||out||^2 in the same pass (nrhs == 1); falls back to two kernels for blocks
 // xnext (optional): also write x + d.*(b - A x), the first damped-Jacobi update of the next cycle, when the kernel
 // that serves A can do it (plane-tile row-class kernel, level's own relaxPrec); *xnext_done reports whether it was.
 // r_dead: the caller will not read `out` when xnext was written (the solve loop: the next cycle starts from xnext and
@@ -569,19 +569,19 @@ int k_residual_sumsq(mg_hierarchy* h, int level, const Csr& A, const double* b, 
   v.x = x;
   v.y = out;
   v.b = b;
-  v.nrhs = (int)h->nrhs;
-  if (h->nrhs != 1) {
+  v.nrhs = (int)h->play->nrhs;
+  if (h->play->nrhs != 1) {
     // block right-hand sides: the paired-column lane SpMM writes ||r||^2 partials and, optionally, x + d.*r
-    const bool fused = A.rc_lane_mm() && A.ln_blocks > 0 && lane_mm_pairs(A, h->nrhs) &&
-                       A.ln_rows == lane_mm_rpl(A, h->nrhs) * (mgk::BLK / lane_mm_group(A, h->nrhs)) && (size_t)A.ln_blocks <= h->partial.n;
+    const bool fused = A.rc_lane_mm() && A.ln_blocks > 0 && lane_mm_pairs(A, h->play->nrhs) &&
+                       A.ln_rows == lane_mm_rpl(A, h->play->nrhs) * (mgk::BLK / lane_mm_group(A, h->play->nrhs)) && (size_t)A.ln_blocks <= h->play->partial.n;
     mgk::VecArgs t = v;
     t.xs = x;
     if (xnext) t.y2 = xnext;
     if (!fused || !aligned16(t) || (xnext && (reinterpret_cast<uintptr_t>(xnext) & 15u))) {
       MG_TRY(k_residual(h, level, A, b, x, out));
-      return k_sumsq(h, out, A.n_rows * h->nrhs);
+      return k_sumsq(h, out, A.n_rows * h->play->nrhs);
     }
-    v.sumsq = h->partial.p;
+    v.sumsq = h->play->partial.p;
     if (xnext && out != x && xnext != x && h->relax_type == 0 && &A == &h->lev[(size_t)level].A && !h->opt.no_fused_next) {
       v.y2 = xnext;
       if (r_dead) v.y = nullptr;
@@ -591,23 +591,23 @@ int k_residual_sumsq(mg_hierarchy* h, int level, const Csr& A, const double* b, 
     }
     int nb1 = 0;
     {
-      const double vec = 8.0 * (double)A.n_rows * (double)h->nrhs;
-      ProfScope ps(h, level, MG_K_RESIDUAL, spmv_bytes(A, h->nrhs, true, false) + ((v.y2 && v.y) ? vec : 0.0),
-                   moved_bytes(A, h->nrhs, true, false) - (v.y ? 0.0 : vec) + (v.y2 ? vec : 0.0));
-      MG_TRY(launch_csr<mgk::RESID>(h->stream, A, v, &nb1));
+      const double vec = 8.0 * (double)A.n_rows * (double)h->play->nrhs;
+      ProfScope ps(h, level, MG_K_RESIDUAL, spmv_bytes(A, h->play->nrhs, true, false) + ((v.y2 && v.y) ? vec : 0.0),
+                   moved_bytes(A, h->play->nrhs, true, false) - (v.y ? 0.0 : vec) + (v.y2 ? vec : 0.0));
+      MG_TRY(launch_csr<mgk::RESID>(h->play->stream, A, v, &nb1));
     }
     ProfScope ps2(h, level, MG_K_NORM, 8.0 * (double)nb1, 8.0 * (double)nb1);
     const int nb2 = std::min(256, (nb1 + mgk::BLK - 1) / mgk::BLK);
-    hipLaunchKernelGGL(mgk::sum_partial, dim3(nb2), dim3(mgk::BLK), 0, h->stream, h->partial.p, (long long)nb1, h->partial2.p);
-    launch_sum_final(h, h->partial2.p, nb2);
+    hipLaunchKernelGGL(mgk::sum_partial, dim3(nb2), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, (long long)nb1, h->play->partial2.p);
+    launch_sum_final(h, h->play->partial2.p, nb2);
     HIP_TRY(hipGetLastError());
     return MG_OK;
   }
-  if ((size_t)std::max(A.blocks1(), A.nblocks) > h->partial.n) {
+  if ((size_t)std::max(A.blocks1(), A.nblocks) > h->play->partial.n) {
     MG_TRY(k_residual(h, level, A, b, x, out));
-    return k_sumsq(h, out, A.n_rows * h->nrhs);
+    return k_sumsq(h, out, A.n_rows * h->play->nrhs);
   }
-  v.sumsq = h->partial.p;
+  v.sumsq = h->play->partial.p;
   // the LDS-staged row-class kernels (march, tile) have x, r and the class's relaxPrec at hand: second output
   if (xnext && A.has_rc && (A.rc_tile || march_ok(A, v)) && A.rc_nexc == 0 && out != x && xnext != x && h->relax_type == 0 &&
       &A == &h->lev[(size_t)level].A && !h->opt.no_fused_next) {
@@ -622,12 +622,12 @@ int k_residual_sumsq(mg_hierarchy* h, int level, const Csr& A, const double* b, 
   {
     ProfScope ps(h, level, MG_K_RESIDUAL, spmv_bytes(A, 1, true, false) + ((v.y2 && v.y) ? 8.0 * (double)A.n_rows : 0.0),
                  moved_bytes(A, 1, true, false) - (v.y ? 0.0 : 8.0 * (double)A.n_rows) + (v.y2 ? 8.0 * (double)A.n_rows : 0.0));
-    MG_TRY(launch_csr<mgk::RESID>(h->stream, A, v, &nb1));
+    MG_TRY(launch_csr<mgk::RESID>(h->play->stream, A, v, &nb1));
   }
   ProfScope ps2(h, level, MG_K_NORM, 8.0 * (double)nb1, 8.0 * (double)nb1);
   const int nb2 = std::min(256, (nb1 + mgk::BLK - 1) / mgk::BLK);
-  hipLaunchKernelGGL(mgk::sum_partial, dim3(nb2), dim3(mgk::BLK), 0, h->stream, h->partial.p, (long long)nb1, h->partial2.p);
-  launch_sum_final(h, h->partial2.p, nb2);
+  hipLaunchKernelGGL(mgk::sum_partial, dim3(nb2), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, (long long)nb1, h->play->partial2.p);
+  launch_sum_final(h, h->play->partial2.p, nb2);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -645,18 +645,18 @@ int k_smooth(mg_hierarchy* h, int level, const Csr& A, const double* d, const do
   v.d = d;
   v.d_full = d;
   // the level's own relaxPrec, constant per row class: read from the dictionary instead of streamed (rc_d)
-  if (h->nrhs == 1 && A.has_rc && A.rc_has_d && d == h->lev[(size_t)level].d.p && &A == &h->lev[(size_t)level].A) v.d = nullptr;
-  if (h->nrhs == 1 && A.sm_use() && A.sm_d_bound == d && d == h->lev[(size_t)level].d.p && &A == &h->lev[(size_t)level].A) v.d = nullptr;
-  v.nrhs = (int)h->nrhs;
-  ProfScope ps(h, level, MG_K_SMOOTH, spmv_bytes(A, h->nrhs, true, true), moved_bytes(A, h->nrhs, true, true, v.d == nullptr));
-  return launch_csr<mgk::SMOOTH>(h->stream, A, v);
+  if (h->play->nrhs == 1 && A.has_rc && A.rc_has_d && d == h->lev[(size_t)level].d.p && &A == &h->lev[(size_t)level].A) v.d = nullptr;
+  if (h->play->nrhs == 1 && A.sm_use() && A.sm_d_bound == d && d == h->lev[(size_t)level].d.p && &A == &h->lev[(size_t)level].A) v.d = nullptr;
+  v.nrhs = (int)h->play->nrhs;
+  ProfScope ps(h, level, MG_K_SMOOTH, spmv_bytes(A, h->play->nrhs, true, true), moved_bytes(A, h->play->nrhs, true, true, v.d == nullptr));
+  return launch_csr<mgk::SMOOTH>(h->play->stream, A, v);
 }
 // One sweep and the residual of its result in one pass (csr_rowclass_march2_spmv):
 //   t = x + d.*(b - A x) ;  r = b - A t  [; xn = t + d.*r ; ||r||^2 partials]
 // for the level's own A with its own relaxPrec read from the class dictionary.  x, t, r, xn: four different buffers.
 bool march2_ok(const mg_hierarchy* h, int level, const double* x, const double* t, const double* r, const double* xn) {
   const Level& L = h->lev[(size_t)level];
-  if (h->nrhs != 1 || h->relax_type != 0) return false;
+  if (h->play->nrhs != 1 || h->relax_type != 0) return false;
   if (L.A.rm3_var && L.A.rc_march3) {        // band form: values and relaxPrec are streamed per row
     if (!L.relax_set) return false;
   } else {
@@ -723,7 +723,7 @@ int k_smooth_residual3(mg_hierarchy* h, int level, const Csr& A, const mgk::Marc
   if (h->m3sink.n < M3_SINK_DOUBLES) return fail(MG_ERR_STATE, "the store sink of the tile-form pass is missing (mg_finalize allocates it)");
   a.sink = h->m3sink.p;
   a.d = h->lev[(size_t)level].d.p;
-  if (a.sumsq && (size_t)nb1 > h->partial.n) return fail(MG_ERR_STATE, "partial-sum buffer too small for the fused sweep + residual");
+  if (a.sumsq && (size_t)nb1 > h->play->partial.n) return fail(MG_ERR_STATE, "partial-sum buffer too small for the fused sweep + residual");
   const double n8 = 8.0 * (double)A.n_rows;
   {
     // moved: no class-id stream in this form (the ids come from the product map) - the class records, the index maps, x and b
@@ -742,11 +742,11 @@ int k_smooth_residual3(mg_hierarchy* h, int level, const Csr& A, const mgk::Marc
       if (L.x3.n != (size_t)A.n_rows) MG_TRY(L.x3.alloc((size_t)A.n_rows));
       scratch = L.x3.p;
     }
-    MG_TRY(launch_march3_any(h->stream, A, a, from_zero, scratch));
+    MG_TRY(launch_march3_any(h->play->stream, A, a, from_zero, scratch));
   }
   if (a.sumsq) {
     ProfScope ps2(h, level, MG_K_NORM, 8.0 * (double)nb1, 8.0 * (double)nb1);
-    launch_sum_final(h, h->partial.p, nb1);
+    launch_sum_final(h, h->play->partial.p, nb1);
     HIP_TRY(hipGetLastError());
   }
   return MG_OK;
@@ -761,19 +761,19 @@ int k_smooth_residual(mg_hierarchy* h, int level, const double* b, const double*
   a.t = t;
   a.r = r;
   a.xn = xn;
-  a.sumsq = want_sumsq ? h->partial.p : nullptr;
+  a.sumsq = want_sumsq ? h->play->partial.p : nullptr;
   if (A.rc_march3) return k_smooth_residual3(h, level, A, a, from_zero);
   if (A.rc_march27 && !A.opt.no_march27 && t && r && !xn && !want_sumsq && (!from_zero || !A.opt.no_march27_zero)) {
     const double n8 = 8.0 * (double)A.n_rows;
     const double tables = (double)A.rc_ncls * 224.0 + 2.0 * (double)(A.rm27[1].n1 + A.rm27[1].n2 + A.rm27[1].nplanes + A.rm27[1].ntab);
     ProfScope ps(h, level, MG_K_SMOOTH_RESIDUAL, spmv_bytes(A, 1, true, true) + spmv_bytes(A, 1, true, false), tables + (from_zero ? 3.0 : 4.0) * n8);
-    if (from_zero) return launch_march27<true, mgk::SMOOTH, true>(h->stream, A, a);   // x1 = d.*b inside the walk: x is not read
-    return launch_march27<true, mgk::SMOOTH>(h->stream, A, a);
+    if (from_zero) return launch_march27<true, mgk::SMOOTH, true>(h->play->stream, A, a);   // x1 = d.*b inside the walk: x is not read
+    return launch_march27<true, mgk::SMOOTH>(h->play->stream, A, a);
   }
   if (!(A.rc_march && A.rc_march2)) return fail(MG_ERR_UNSUPPORTED, "this combination of outputs is not served by a two-stage pass on level %d", level + 1);
   mgk::MarchDev T = A.marchdev();
   T.nblocks = A.rm2_nblocks;
-  if (want_sumsq && (size_t)T.nblocks > h->partial.n) return fail(MG_ERR_STATE, "partial-sum buffer too small for the fused sweep + residual");
+  if (want_sumsq && (size_t)T.nblocks > h->play->partial.n) return fail(MG_ERR_STATE, "partial-sum buffer too small for the fused sweep + residual");
   const size_t lds = march2_lds_bytes(A.rm_halo);
   static bool lds_attr_set = false;
   if (!lds_attr_set) {
@@ -787,14 +787,14 @@ int k_smooth_residual(mg_hierarchy* h, int level, const double* b, const double*
     // algorithmic: the two products; moved: class ids + x + b in, t and r (and/or xn) out
     ProfScope ps(h, level, want_sumsq ? MG_K_SMOOTH_RESIDUAL_NORM : MG_K_SMOOTH_RESIDUAL, spmv_bytes(A, 1, true, true) + spmv_bytes(A, 1, true, false) + (xn && r ? n8 : 0.0),
                  format_bytes(A, 1) + n8 * (2.0 + (t ? 1.0 : 0.0) + (r ? 1.0 : 0.0) + (xn ? 1.0 : 0.0)));
-    if (from_zero) hipLaunchKernelGGL((mgk::csr_rowclass_march2_spmv<true>), dim3(T.nblocks), dim3(mgk::RM_C), lds, h->stream, A.rcdev(), a, T);
-    else hipLaunchKernelGGL((mgk::csr_rowclass_march2_spmv<false>), dim3(T.nblocks), dim3(mgk::RM_C), lds, h->stream, A.rcdev(), a, T);
+    if (from_zero) hipLaunchKernelGGL((mgk::csr_rowclass_march2_spmv<true>), dim3(T.nblocks), dim3(mgk::RM_C), lds, h->play->stream, A.rcdev(), a, T);
+    else hipLaunchKernelGGL((mgk::csr_rowclass_march2_spmv<false>), dim3(T.nblocks), dim3(mgk::RM_C), lds, h->play->stream, A.rcdev(), a, T);
     HIP_TRY(hipGetLastError());
   }
   if (want_sumsq) {   // one partial per workgroup (<= one per CU): a single-workgroup final sum
     const int nb1 = T.nblocks;
     ProfScope ps2(h, level, MG_K_NORM, 8.0 * (double)nb1, 8.0 * (double)nb1);
-    launch_sum_final(h, h->partial.p, nb1);
+    launch_sum_final(h, h->play->partial.p, nb1);
     HIP_TRY(hipGetLastError());
   }
   return MG_OK;
@@ -824,7 +824,7 @@ int launch_march4(hipStream_t stream, const Csr& A, const mgk::March2Args& a, co
 }
 bool march4_ok(const mg_hierarchy* h, int level, const double* x, const double* tp, const double* rp) {
   const Level& L = h->lev[(size_t)level];
-  if (h->nrhs != 1 || h->relax_type != 0 || h->opt.no_march4) return false;
+  if (h->play->nrhs != 1 || h->relax_type != 0 || h->opt.no_march4) return false;
   if (!L.A.rc_march4 || !L.A.has_rc || !L.A.rc_has_d || L.A.rc_nexc != 0 || L.A.d_bound != L.d.p) return false;
   if (std::max<long long>(1, L.npre) != 2) return false;   // (xn is the input of the LAST pre-smoothing sweep)
   if (x == tp || x == rp || tp == rp) return false;
@@ -856,7 +856,7 @@ inline bool gh_agree2(const mg_hierarchy* h, int l);
 // known before the launch: the restriction INTO the level then writes no x1)
 bool from_zero_static(const mg_hierarchy* h, int level) {
   const Level& L = h->lev[(size_t)level];
-  return h->nrhs == 1 && std::max<long long>(1, L.npre) == 2 && !h->opt.no_march2_zero && march2_ok_static(h, level) && zero_form_static(L.A) &&
+  return h->play->nrhs == 1 && std::max<long long>(1, L.npre) == 2 && !h->opt.no_march2_zero && march2_ok_static(h, level) && zero_form_static(L.A) &&
          gh_agree_zero(h, level) && gh_agree2(h, level);
 }
 bool restrict_can_scale_static(const mg_hierarchy* h, const Csr& M) {
@@ -878,12 +878,12 @@ int k_four_stage(mg_hierarchy* h, int level, const double* b, const double* x, d
   a.b = b;
   a.t = tp;
   a.r = rp;
-  a.sumsq = h->partial.p;
+  a.sumsq = h->play->partial.p;
   if (h->m3sink.n < M3_SINK_DOUBLES) return fail(MG_ERR_STATE, "the store sink of the tile-form pass is missing (mg_finalize allocates it)");
   a.sink = h->m3sink.p;
   a.d = h->lev[(size_t)level].d.p;
   const int nb1 = A.rm4.nblocks;
-  if ((size_t)nb1 > h->partial.n) return fail(MG_ERR_STATE, "partial-sum buffer too small for the four-stage pass");
+  if ((size_t)nb1 > h->play->partial.n) return fail(MG_ERR_STATE, "partial-sum buffer too small for the four-stage pass");
   const double n8 = 8.0 * (double)A.n_rows;
   {
     const double tables = (double)A.rc_ncls * 88.0 + 2.0 * (double)(A.rm4.n1 + A.rm4.n2 + A.rm4.nplanes + A.rm4.ntab);
@@ -891,17 +891,17 @@ int k_four_stage(mg_hierarchy* h, int level, const double* b, const double* x, d
     ProfScope ps(h, level, MG_K_FOUR_STAGE, 2.0 * (spmv_bytes(A, 1, true, true) + spmv_bytes(A, 1, true, false)), tables + 4.0 * n8);
     mgk::March4Dev T = A.rm4;
     gh_own_box(h, level, &T.oxl, &T.oxh, &T.oyl, &T.oyh, &T.ozl, &T.ozh);   // (ghost-layer form: ||r||^2 over this rank's owned rows)
-    if (A.rm4_nt == 1024) MG_TRY((launch_march4<1024, 2, 2>(h->stream, A, a, T)));
-    else if (A.rm4_nt == 768 && A.rm4_k1 == 3) MG_TRY((launch_march4<768, 3, 2>(h->stream, A, a, T)));
-    else if (A.rm4_nt == 768) MG_TRY((launch_march4<768, 4, 3>(h->stream, A, a, T)));
-    else MG_TRY((launch_march4<512, 4, 3>(h->stream, A, a, T)));
+    if (A.rm4_nt == 1024) MG_TRY((launch_march4<1024, 2, 2>(h->play->stream, A, a, T)));
+    else if (A.rm4_nt == 768 && A.rm4_k1 == 3) MG_TRY((launch_march4<768, 3, 2>(h->play->stream, A, a, T)));
+    else if (A.rm4_nt == 768) MG_TRY((launch_march4<768, 4, 3>(h->play->stream, A, a, T)));
+    else MG_TRY((launch_march4<512, 4, 3>(h->play->stream, A, a, T)));
   }
   ProfScope ps2(h, level, MG_K_NORM, 8.0 * (double)nb1, 8.0 * (double)nb1);
   if (gh_global_scalars(h)) {         // sharded: the ranks' sums are added before the host sees the norm (RCCL on the stream; plug-in: when it is read)
-    hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, nb1, h->scalar.p);
+    hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb1, h->play->scalar.p);
     HIP_TRY(hipGetLastError());
     MG_TRY(gh_scalar_to_slot(h, host_slot ? host_slot : h->h_scalar));
-    h->scalar_mirrored = true;
+    h->play->scalar_mirrored = true;
   } else if (host_slot && !h->capturing && deferred && !h->prof && !h->opt.no_defer_sum) {
     h->dsum.on = true;
     h->dsum.np = nb1;
@@ -909,39 +909,39 @@ int k_four_stage(mg_hierarchy* h, int level, const double* b, const double* x, d
     h->dsum.ev = defer_ev;
     *deferred = true;
   } else if (host_slot && !h->capturing) {   // (the pipelined stopping test: a pinned slot per step in flight)
-    hipLaunchKernelGGL(mgk::sum_final_mirror, dim3(1), dim3(mgk::BLK), 0, h->stream, h->partial.p, nb1, h->scalar.p, host_slot);
+    hipLaunchKernelGGL(mgk::sum_final_mirror, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb1, h->play->scalar.p, host_slot);
   } else {
-    launch_sum_final(h, h->partial.p, nb1);
+    launch_sum_final(h, h->play->partial.p, nb1);
   }
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 int k_dscale(mg_hierarchy* h, int level, const double* d, const double* b, double* x, long long n) {
-  ProfScope ps(h, level, MG_K_DSCALE, 8.0 * (double)n * (1.0 + 2.0 * (double)h->nrhs));
-  hipLaunchKernelGGL(mgk::dscale_kernel, dim3(grid_for(n * h->nrhs / 2 + 1)), dim3(mgk::BLK), 0,
-                     h->stream, d, b, x, n, (int)h->nrhs);
+  ProfScope ps(h, level, MG_K_DSCALE, 8.0 * (double)n * (1.0 + 2.0 * (double)h->play->nrhs));
+  hipLaunchKernelGGL(mgk::dscale_kernel, dim3(grid_for(n * h->play->nrhs / 2 + 1)), dim3(mgk::BLK), 0,
+                     h->play->stream, d, b, x, n, (int)h->play->nrhs);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 // xout = x + d.*r (first sweep when r = b - A x is already known)
 int k_xpdr(mg_hierarchy* h, int level, const double* x, const double* d, const double* r, double* xout,
            long long n) {
-  ProfScope ps(h, level, MG_K_DSCALE, 8.0 * (double)n * (1.0 + 3.0 * (double)h->nrhs));
+  ProfScope ps(h, level, MG_K_DSCALE, 8.0 * (double)n * (1.0 + 3.0 * (double)h->play->nrhs));
   const Csr& A = h->lev[(size_t)level].A;
-  if (h->nrhs == 1 && A.has_rc && A.rc_has_d && d == h->lev[(size_t)level].d.p && n == A.n_rows) {
+  if (h->play->nrhs == 1 && A.has_rc && A.rc_has_d && d == h->lev[(size_t)level].d.p && n == A.n_rows) {
     // the level's relaxPrec is constant per row class: stream the 2-byte class ids instead of d
-    hipLaunchKernelGGL(mgk::xpdr_cls_kernel, dim3(grid_for(n / 2 + 1)), dim3(mgk::BLK), 0, h->stream, x, A.rc_cls.p,
+    hipLaunchKernelGGL(mgk::xpdr_cls_kernel, dim3(grid_for(n / 2 + 1)), dim3(mgk::BLK), 0, h->play->stream, x, A.rc_cls.p,
                        A.rc_d.p, d, r, xout, n);
     HIP_TRY(hipGetLastError());
     return MG_OK;
   }
-  hipLaunchKernelGGL(mgk::xpdr_kernel, dim3(grid_for(n * h->nrhs / 2 + 1)), dim3(mgk::BLK), 0,
-                     h->stream, x, d, r, xout, n, (int)h->nrhs);
+  hipLaunchKernelGGL(mgk::xpdr_kernel, dim3(grid_for(n * h->play->nrhs / 2 + 1)), dim3(mgk::BLK), 0,
+                     h->play->stream, x, d, r, xout, n, (int)h->play->nrhs);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 int k_fill(mg_hierarchy* h, double* x, long long n, double val) {
-  hipLaunchKernelGGL(mgk::fill_kernel, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->stream, x, n, val);
+  hipLaunchKernelGGL(mgk::fill_kernel, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, x, n, val);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -957,13 +957,13 @@ int k_coarse(mg_hierarchy* h, int level, const double* b, double* x) {
     // coarseSolveType "GMRES" (MGcycle.jl:152-168): x = 0; one restart of FGMRES(10), tol 0.01, M = d .* v with
     // d = relaxParam ./ diag(A_c) (defineCoarsestAinv, MGsetup.jl:334)
     ProfScope ps(h, level, MG_K_COARSE, 0.0);
-    MG_TRY(k_fill(h, x, n * h->nrhs, 0.0));
-    if (h->nrhs != 1)   // MGcycle.jl:166: KrylovMethods.blockFGMRES(Afun, b, 10, tol = 0.01, maxIter = 1, M = M2, X = x)
+    MG_TRY(k_fill(h, x, n * h->play->nrhs, 0.0));
+    if (h->play->nrhs != 1)   // MGcycle.jl:166: KrylovMethods.blockFGMRES(Afun, b, 10, tol = 0.01, maxIter = 1, M = M2, X = x)
       return block_fgmres_core(h, level, 1, h->coarse_d.p, &h->kwc_blk, b, x, 10, 0.01, 1, nullptr, nullptr, nullptr, nullptr);
     return fgmres_core(h, level, 1, h->coarse_d.p, h->kwc, b, x, 10, 0.01, 1, nullptr, nullptr, nullptr, nullptr);
   }
   if (h->coarse_lu) {
-    ProfScope ps(h, level, MG_K_COARSE, 12.0 * (double)(h->luLval.n + h->luUval.n) + 16.0 * (double)n * (double)h->nrhs);
+    ProfScope ps(h, level, MG_K_COARSE, 12.0 * (double)(h->luLval.n + h->luUval.n) + 16.0 * (double)n * (double)h->play->nrhs);
     mgk::LuDev F;
     F.n = (int)n;
     F.Lptr = h->luLptr.p; F.Lcol = h->luLcol.p; F.Lval = h->luLval.p;
@@ -972,69 +972,69 @@ int k_coarse(mg_hierarchy* h, int level, const double* b, double* x) {
     F.Lorder = h->luLorder.p; F.Llvl = h->luLlvl.p; F.nLlvl = h->nLlvl;
     F.Uorder = h->luUorder.p; F.Ulvl = h->luUlvl.p; F.nUlvl = h->nUlvl;
     if (!h->lu_multi) {
-      hipLaunchKernelGGL(mgk::sptrsv_lu<double>, dim3(1), dim3(1024), 0, h->stream, F, b, x, h->luWork.p, (int)h->nrhs);
+      hipLaunchKernelGGL(mgk::sptrsv_lu<double>, dim3(1), dim3(1024), 0, h->play->stream, F, b, x, h->luWork.p, (int)h->play->nrhs);
       HIP_TRY(hipGetLastError());
       return MG_OK;
     }
-    const int nr = (int)h->nrhs;
+    const int nr = (int)h->play->nrhs;
     double* y = h->luWork.p;
     auto wave_blocks = [](long long waves) { return dim3((unsigned)((waves * 64 + mgk::BLK - 1) / mgk::BLK)); };
     // y = L \ b[p]: the levels ahead of the trailing block one launch each, the block through its inverse
     const int nLl = (int)h->luLlvl_h.size() - 1, nUl = (int)h->luUlvl_h.size() - 1;
     for (int l = 0; l < nLl; ++l) {
       const int t0 = h->luLlvl_h[(size_t)l], t1 = h->luLlvl_h[(size_t)l + 1];
-      hipLaunchKernelGGL(mgk::sptrsv_level<true>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, h->stream, F,
+      hipLaunchKernelGGL(mgk::sptrsv_level<true>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, h->play->stream, F,
                          reinterpret_cast<const int4*>(h->luLslot.p), t0, t1, b, y, nr);
     }
     if (h->luML > 0) {
       const int n0 = (int)n - h->luML;
-      hipLaunchKernelGGL(mgk::sptrsv_tail_rhs, wave_blocks(h->luML), dim3(mgk::BLK), 0, h->stream, F, n0, b, y, h->luTail.p, nr);
-      hipLaunchKernelGGL(mgk::tri_apply<true>, wave_blocks((long long)h->luML * nr), dim3(mgk::BLK), 0, h->stream,
+      hipLaunchKernelGGL(mgk::sptrsv_tail_rhs, wave_blocks(h->luML), dim3(mgk::BLK), 0, h->play->stream, F, n0, b, y, h->luTail.p, nr);
+      hipLaunchKernelGGL(mgk::tri_apply<true>, wave_blocks((long long)h->luML * nr), dim3(mgk::BLK), 0, h->play->stream,
                          h->luInvL.p, (h->luML + 63) / 64 * 64, h->luTail.p, y + (size_t)n0 * (size_t)nr, h->luML, nr);
     }
     // y = U \ y: the trailing block first, then the levels behind it
     if (h->luMU > 0) {
       const int n0 = (int)n - h->luMU;
       HIP_TRY(hipMemcpyAsync(h->luTail.p, y + (size_t)n0 * (size_t)nr, (size_t)h->luMU * (size_t)nr * sizeof(double),
-                             hipMemcpyDeviceToDevice, h->stream));
-      hipLaunchKernelGGL(mgk::tri_apply<false>, wave_blocks((long long)h->luMU * nr), dim3(mgk::BLK), 0, h->stream,
+                             hipMemcpyDeviceToDevice, h->play->stream));
+      hipLaunchKernelGGL(mgk::tri_apply<false>, wave_blocks((long long)h->luMU * nr), dim3(mgk::BLK), 0, h->play->stream,
                          h->luInvU.p, (h->luMU + 63) / 64 * 64, h->luTail.p, y + (size_t)n0 * (size_t)nr, h->luMU, nr);
     }
     for (int l = 0; l < nUl; ++l) {
       const int t0 = h->luUlvl_h[(size_t)l], t1 = h->luUlvl_h[(size_t)l + 1];
-      hipLaunchKernelGGL(mgk::sptrsv_level<false>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, h->stream, F,
+      hipLaunchKernelGGL(mgk::sptrsv_level<false>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, h->play->stream, F,
                          reinterpret_cast<const int4*>(h->luUslot.p), t0, t1, b, y, nr);
     }
     hipLaunchKernelGGL(mgk::sptrsv_scatter, dim3((unsigned)((n * nr + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0,
-                       h->stream, h->luQ.p, y, x, (int)n, nr);
+                       h->play->stream, h->luQ.p, y, x, (int)n, nr);
     HIP_TRY(hipGetLastError());
     return MG_OK;
   }
   ProfScope ps(h, level, MG_K_COARSE,
-               8.0 * ((double)n * (double)n + 2.0 * (double)n * (double)h->nrhs));
-  const long long waves = n * h->nrhs;
+               8.0 * ((double)n * (double)n + 2.0 * (double)n * (double)h->play->nrhs));
+  const long long waves = n * h->play->nrhs;
   const long long blocks = (waves * 64 + mgk::BLK - 1) / mgk::BLK;
-  hipLaunchKernelGGL(mgk::dense_apply, dim3((unsigned)blocks), dim3(mgk::BLK), 0, h->stream,
-                     h->Ainv.p, b, x, (int)n, (int)h->nrhs);
+  hipLaunchKernelGGL(mgk::dense_apply, dim3((unsigned)blocks), dim3(mgk::BLK), 0, h->play->stream,
+                     h->Ainv.p, b, x, (int)n, (int)h->play->nrhs);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
-// sum of squares of x[0..len) -> h->scalar (device); no sync
+// sum of squares of x[0..len) -> h->play->scalar (device); no sync
 int k_sumsq(mg_hierarchy* h, const double* x, long long len) {
   ProfScope ps(h, 0, MG_K_NORM, 8.0 * (double)len);
   const int nb = std::min<long long>(h->nred_blocks, std::max<long long>(1, (len / 2 + mgk::BLK - 1) / mgk::BLK));
-  hipLaunchKernelGGL(mgk::sumsq_partial, dim3(nb), dim3(mgk::BLK), 0, h->stream, x, len,
-                     h->partial.p);
-  launch_sum_final(h, h->partial.p, nb);
+  hipLaunchKernelGGL(mgk::sumsq_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, x, len,
+                     h->play->partial.p);
+  launch_sum_final(h, h->play->partial.p, nb);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
-// host value of sqrt(h->scalar); synchronises the stream
-// h->scalar on the host (*h->h_scalar) once the stream has drained
+// host value of sqrt(h->play->scalar); synchronises the stream
+// h->play->scalar on the host (*h->h_scalar) once the stream has drained
 int scalar_wait(mg_hierarchy* h) {
-  if (!h->scalar_mirrored) HIP_TRY(hipMemcpyAsync(h->h_scalar, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  h->scalar_mirrored = false;
-  HIP_TRY(spin_sync(h->stream));
+  if (!h->play->scalar_mirrored) HIP_TRY(hipMemcpyAsync(h->h_scalar, h->play->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->play->stream));
+  h->play->scalar_mirrored = false;
+  HIP_TRY(spin_sync(h->play->stream));
   return MG_OK;
 }
 int scalar_sync(mg_hierarchy* h, double* out) {

@@ -49,7 +49,7 @@ void pinv_sym(const std::vector<double>& H, int k, std::vector<double>& Pinv) {
 }
 
 int k_axpby(mg_hierarchy* h, double a, const double* x, double b, double* y, long long n) {
-  hipLaunchKernelGGL(mgk::axpby_kernel, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->stream, a, x, b, y, n);
+  hipLaunchKernelGGL(mgk::axpby_kernel, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, a, x, b, y, n);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -63,7 +63,7 @@ template <class Prec>
 int fgmres_relax(mg_hierarchy* h, int lv, const double* r0, double* x0, long long inner, Prec prec,
                  double TOL, double* Zb, double* AZb, bool x0_is_zero) {
   Level& L = h->lev[(size_t)lv];
-  const long long len = L.n * h->nrhs;
+  const long long len = L.n * h->play->nrhs;
   if (inner <= 0) {
     if (x0_is_zero) MG_TRY(k_fill(h, x0, len, 0.0));
     return MG_OK;  // w = Z*t with no columns: x0 unchanged (FGMRES.jl:119-121)
@@ -72,7 +72,7 @@ int fgmres_relax(mg_hierarchy* h, int lv, const double* r0, double* x0, long lon
   // Ghost-layer form (a sharded level of one rank's extended boxes; round 6): norms and dots are sums over the owned rows of all ranks,
   // z's ghost layers travel in front of the product (one exchange per direction), the results are valid on the owned rows.
   const bool ghs = gh_sharded_sums(h, lv);
-  if (ghs && h->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: the FGMRES relaxation runs on single vectors");
+  if (ghs && h->play->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: the FGMRES relaxation runs on single vectors");
   auto gdot = [&](const double* x, const double* y, double* out) { return ghs ? gh_dots_own(h, 1, &x, &y, out, lv) : dot_sync(h, x, y, len, out); };
   double rnorm0 = 0.0;
   if (ghs) {
@@ -145,7 +145,9 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
   }
   Level& L = h->lev[l];
   Level& C = h->lev[l + 1];
-  const long long len = L.n * h->nrhs;
+  Play::Vecs& VC = h->play->lev[(size_t)l + 1];   // the coarse level's vectors and this level's residual, of the lane being played
+  double* const Lr = h->play->res(l);
+  const long long len = L.n * h->play->nrhs;
   double* cur = xa;
   double* alt = xb;
   const double gmresTol = 1e-5;  // MGcycle.jl:5
@@ -175,17 +177,17 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
     } else {
       if (!r_valid) {
         MG_TRY(need(cur, 1));
-        MG_TRY(need(L.r.p, 0));
-        MG_TRY(k_residual(h, l, L.A, b, cur, L.r.p));
-        setd(L.r.p, std::min(dec(dep(cur)), dep(b)));
+        MG_TRY(need(Lr, 0));
+        MG_TRY(k_residual(h, l, L.A, b, cur, Lr));
+        setd(Lr, std::min(dec(dep(cur)), dep(b)));
       }
-      r0 = L.r.p;
+      r0 = Lr;
     }
     MG_TRY(fgmres_relax(h, l, r0, cur, L.npre, diag_prec, gmresTol, L.relaxZ.p, L.relaxAZ.p, false));
     npre = 0;
   } else if (x_zero) {
     // two sweeps from x = 0 on a level the two-stage pass serves: x1 = d.*b is formed inside that pass
-    from_zero = !x1_given && npre == 2 && !h->opt.no_march2_zero && march2_ok(h, l, cur, alt, L.r.p, nullptr) && zero_form_static(L.A) &&
+    from_zero = !x1_given && npre == 2 && !h->opt.no_march2_zero && march2_ok(h, l, cur, alt, Lr, nullptr) && zero_form_static(L.A) &&
                 gh_agree_zero(h, l) && gh_agree2(h, l);                  // (sharded: what every rank's kernels can do)
     MG_TRY(need(b, 0));
     if (!from_zero && !x1_given) {
@@ -197,10 +199,10 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
   } else if (r_valid) {
     if (!x1_ready) {
       MG_TRY(need(cur, 0));
-      MG_TRY(need(L.r.p, 0));
+      MG_TRY(need(Lr, 0));
       MG_TRY(need(alt, 0));
-      MG_TRY(k_xpdr(h, l, cur, L.d.p, L.r.p, alt, L.n));
-      setd(alt, std::min(dep(cur), dep(L.r.p)));
+      MG_TRY(k_xpdr(h, l, cur, L.d.p, Lr, alt, L.n));
+      setd(alt, std::min(dep(cur), dep(Lr)));
     }
     std::swap(cur, alt);
     --npre;
@@ -215,7 +217,7 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
     return MG_OK;
   };
   // the last pre-smoothing sweep and r = b - A x (MGcycle.jl:58-60) in one pass where the marching kernel allows
-  const bool fuse_pre = npre >= 1 && march2_ok(h, l, cur, alt, L.r.p, nullptr) && gh_agree2(h, l);
+  const bool fuse_pre = npre >= 1 && march2_ok(h, l, cur, alt, Lr, nullptr) && gh_agree2(h, l);
   for (long long s = 0; s < npre - (fuse_pre ? 1 : 0); ++s) {
     MG_TRY(sweep(cur, alt));
     std::swap(cur, alt);
@@ -228,27 +230,27 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
     if (from_zero) MG_TRY(need(b, 2));
     else { MG_TRY(need(cur, 2)); MG_TRY(need(b, 1)); }
     MG_TRY(need(alt, 0));
-    MG_TRY(need(L.r.p, 0));
-    MG_TRY(k_smooth_residual(h, l, b, cur, alt, L.r.p, nullptr, false, from_zero));
+    MG_TRY(need(Lr, 0));
+    MG_TRY(k_smooth_residual(h, l, b, cur, alt, Lr, nullptr, false, from_zero));
     const int dt = std::min(dec(from_zero ? dep(b) : dep(cur)), dep(b));
     setd(alt, dt);
-    setd(L.r.p, std::min(dec(dt), dep(b)));
+    setd(Lr, std::min(dec(dt), dep(b)));
     std::swap(cur, alt);
   } else if (small_rr) {
     // (a small level: the residual is formed inside the restriction's launch, in LDS - grid27_small_resid_restrict)
   } else {
     MG_TRY(need(cur, 1));
     MG_TRY(need(b, 0));
-    MG_TRY(need(L.r.p, 0));
-    MG_TRY(k_residual(h, l, L.A, b, cur, L.r.p));
-    setd(L.r.p, std::min(dec(dep(cur)), dep(b)));
+    MG_TRY(need(Lr, 0));
+    MG_TRY(k_residual(h, l, L.A, b, cur, Lr));
+    setd(Lr, std::min(dec(dep(cur)), dep(b)));
   }
   if (gh) {
     // x comes back at the prolongation, a whole coarse cycle away: if it will not carry the post-smoothing (and the caller's fused
     // pass behind a deferred last sweep: four stages + the layer its restriction reads), its ghost layers travel meanwhile
     const long long inside = std::max<long long>(1, L.npost) - ((defer_post && *defer_post) ? 1 : 0);
     MG_TRY(gh_prefetch(h, l, cur, (int)inside + ((defer_post && *defer_post) ? 5 : 0)));
-    MG_TRY(need(L.r.p, 1));     // the restriction reads the residual one layer around the owned coarse nodes
+    MG_TRY(need(Lr, 1));     // the restriction reads the residual one layer around the owned coarse nodes
   }
   // the restriction also writes the coarse level's first update x = d.*bc where its kernel can (no dscale launch there)
   // (not into a sharded or just all-reduced level: its bc is complete only behind the exchange)
@@ -256,25 +258,25 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
   // (nor where the coarse level's first fused pass forms x1 itself - its from-zero form: one vector less to write, read and exchange)
   const bool give_x1 = (!gh_any || l + 1 < h->ghost->a) && h->relax_type == 0 && !(ctype == 'K') && l + 1 < nl - 1 && C.relax_set && restrict_can_scale(h, L.R) && gh_agree_scale(h, l) &&
                        !from_zero_static(h, l + 1);
-  if (small_rr) MG_TRY(k_small_resid_restrict(h, l, b, cur, C.b.p, give_x1 ? C.d.p : nullptr, give_x1 ? C.x0.p : nullptr));
-  else MG_TRY(k_spmv(h, l, MG_K_RESTRICT, L.R, 1.0, L.r.p, 0.0, C.b.p, give_x1 ? C.d.p : nullptr, give_x1 ? C.x0.p : nullptr));
+  if (small_rr) MG_TRY(k_small_resid_restrict(h, l, b, cur, VC.b.p, give_x1 ? C.d.p : nullptr, give_x1 ? VC.x0.p : nullptr));
+  else MG_TRY(k_spmv(h, l, MG_K_RESTRICT, L.R, 1.0, Lr, 0.0, VC.b.p, give_x1 ? C.d.p : nullptr, give_x1 ? VC.x0.p : nullptr));
   if (gh_any) {
     if (l + 1 < h->ghost->a) {   // the coarse right-hand side: valid where the residual reached, then every ghost layer at once
       if (gh_level(h, l + 1)) {
-        const int dr = std::min(dep(L.r.p), gh_level(h, l)->gmin);
-        gh_set(h, l + 1, C.b.p, (dr - 1) / 2);
+        const int dr = std::min(dep(Lr), gh_level(h, l)->gmin);
+        gh_set(h, l + 1, VC.b.p, (dr - 1) / 2);
         if (give_x1) {   // bc and x1 = d.*bc in one exchange
-          gh_set(h, l + 1, C.x0.p, (dr - 1) / 2);
-          MG_TRY(gh_touch(h, l + 1, C.b.p));
-          MG_TRY(gh_touch(h, l + 1, C.x0.p));
-          MG_TRY(gh_exchange_start(h, l + 1, C.b.p, C.x0.p));
+          gh_set(h, l + 1, VC.x0.p, (dr - 1) / 2);
+          MG_TRY(gh_touch(h, l + 1, VC.b.p));
+          MG_TRY(gh_touch(h, l + 1, VC.x0.p));
+          MG_TRY(gh_exchange_start(h, l + 1, VC.b.p, VC.x0.p));
           MG_TRY(gh_exchange_finish(h, l + 1));
         } else {
-          MG_TRY(gh_need(h, l + 1, C.b.p, GH_FULL));
+          MG_TRY(gh_need(h, l + 1, VC.b.p, GH_FULL));
         }
       }
     } else {
-      MG_TRY(gh_allreduce_tail(h, C.b.p, C.n));   // rows of the first replicated level: every rank contributed the nodes it owns
+      MG_TRY(gh_allreduce_tail(h, VC.b.p, C.n));   // rows of the first replicated level: every rank contributed the nodes it owns
     }
   }
   double* xc = nullptr;
@@ -282,24 +284,24 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
     // K-cycle (MGcycle.jl:72-76): 2 steps of FGMRES on A_{l+1} xc = bc, preconditioned by the K-cycle of level l+1
     auto kprec = [&](const double* v, double* z) {
       double* res = nullptr;
-      MG_TRY(cycle_level(h, l + 1, v, C.x0.p, C.x1.p, true, 'K', &res));
+      MG_TRY(cycle_level(h, l + 1, v, VC.x0.p, VC.x1.p, true, 'K', &res));
       MG_TRY(gh_touch(h, l + 1, res));
-      HIP_TRY(hipMemcpyAsync(z, res, sizeof(double) * C.n * h->nrhs, hipMemcpyDeviceToDevice, h->stream));
+      HIP_TRY(hipMemcpyAsync(z, res, sizeof(double) * C.n * h->play->nrhs, hipMemcpyDeviceToDevice, h->play->stream));
       if (gh_level(h, l + 1)) gh_set(h, l + 1, z, gh_depth(h, l + 1, res));
       return (int)MG_OK;
     };
-    MG_TRY(fgmres_relax(h, l + 1, C.b.p, C.x0.p, 2, kprec, gmresTol, C.kZ.p, C.kAZ.p, true));
-    xc = C.x0.p;
+    MG_TRY(fgmres_relax(h, l + 1, VC.b.p, VC.x0.p, 2, kprec, gmresTol, C.kZ.p, C.kAZ.p, true));
+    xc = VC.x0.p;
   } else {
-    MG_TRY(cycle_sub(h, l + 1, C.b.p, C.x0.p, C.x1.p, true, ctype, &xc, give_x1));
+    MG_TRY(cycle_sub(h, l + 1, VC.b.p, VC.x0.p, VC.x1.p, true, ctype, &xc, give_x1));
   }
   if (l + 1 < nl - 1) {  // MGcycle.jl:78-85
     if (ctype == 'W') {
-      double* other = (xc == C.x0.p) ? C.x1.p : C.x0.p;
-      MG_TRY(cycle_sub(h, l + 1, C.b.p, xc, other, false, 'W', &xc));
+      double* other = (xc == VC.x0.p) ? VC.x1.p : VC.x0.p;
+      MG_TRY(cycle_sub(h, l + 1, VC.b.p, xc, other, false, 'W', &xc));
     } else if (ctype == 'F') {
-      double* other = (xc == C.x0.p) ? C.x1.p : C.x0.p;
-      MG_TRY(cycle_sub(h, l + 1, C.b.p, xc, other, false, 'V', &xc));
+      double* other = (xc == VC.x0.p) ? VC.x1.p : VC.x0.p;
+      MG_TRY(cycle_sub(h, l + 1, VC.b.p, xc, other, false, 'V', &xc));
     }
   }
   // x += P xc (MGcycle.jl:90) and post-smoothing (l.92-102)
@@ -335,10 +337,10 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
   if (h->relax_type == 1) {
     MG_TRY(need(cur, 1));
     MG_TRY(need(b, 0));
-    MG_TRY(need(L.r.p, 0));
-    MG_TRY(k_residual(h, l, L.A, b, cur, L.r.p));
-    setd(L.r.p, std::min(dec(dep(cur)), dep(b)));
-    MG_TRY(fgmres_relax(h, l, L.r.p, cur, L.npost, diag_prec, gmresTol, L.relaxZ.p, L.relaxAZ.p, false));
+    MG_TRY(need(Lr, 0));
+    MG_TRY(k_residual(h, l, L.A, b, cur, Lr));
+    setd(Lr, std::min(dec(dep(cur)), dep(b)));
+    MG_TRY(fgmres_relax(h, l, Lr, cur, L.npost, diag_prec, gmresTol, L.relaxZ.p, L.relaxAZ.p, false));
   } else {
     if (!(defer_post && *defer_post && post_done < npost) && defer_post) *defer_post = false;
     for (long long s = swept; s < nlast; ++s) {
@@ -377,9 +379,9 @@ int check_ready(mg_hierarchy* h, long long n, long long nrhs, bool sharded_ok = 
 
 void graphs_clear(mg_hierarchy* h) {
   if (h->graphs.empty()) return;
-  if (h->stream) (void)spin_sync(h->stream);   // a replay may still be running
-  for (mg_hierarchy::ColSet* cs : h->colsets)  // (the column-wise block solve replays graphs on its own streams too)
-    if (cs && cs->stream) (void)spin_sync(cs->stream);
+  if (h->play->stream) (void)spin_sync(h->play->stream);   // a replay may still be running
+  for (Play* p : h->lanes)   // (the column-wise block solve replays graphs on its own streams too)
+    if (p->stream) (void)spin_sync(p->stream);
   for (auto& kv : h->graphs) {
     if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
     if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
@@ -395,24 +397,24 @@ bool graph_ok(const mg_hierarchy* h, int l, char ctype) {
   if (h->opt.no_graph || h->prof || h->capturing || h->relax_type == 1 || ctype == 'K' || h->coarse_gmres) return false;
   // a caller's stream (mg_set_stream) may be the legacy null stream, which cannot capture, or be part of a capture of
   // the caller's own: only the hierarchy's own stream is captured, unless the caller vouches for its stream (dist tail)
-  if (!h->stream || (!h->owns_stream && !h->opt.dist_tail_graph)) return false;
-  if (h->lev[(size_t)l].n * h->nrhs > h->opt.graph_max_rows) return false;
+  if (!h->play->stream || (!h->play->owns_stream && !h->opt.dist_tail_graph)) return false;
+  if (h->lev[(size_t)l].n * h->play->nrhs > h->opt.graph_max_rows) return false;
   if (h->ghost && l < h->ghost->a) return false;   // sharded levels: exchanges and an all-reduce inside (the replicated levels below replay as a graph)
   return (int)h->nlevels - l >= 2 || (h->coarse_lu && h->lu_multi);
 }
 int cycle_sub(mg_hierarchy* h, int l, const double* b, double* xa, double* xb, bool x_zero, char ctype, double** result,
               bool x1_given) {
   if (!graph_ok(h, l, ctype)) return cycle_level(h, l, b, xa, xb, x_zero, ctype, result, false, false, nullptr, x1_given);
-  const mg_hierarchy::GraphKey key{l, x_zero, ctype, b, xa, xb, x1_given, h->nrhs};
+  const mg_hierarchy::GraphKey key{l, x_zero, ctype, b, xa, xb, x1_given, h->play->nrhs};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() >= 64) graphs_clear(h);   // callers cycling through many buffers: start over
     mg_hierarchy::GraphEntry e;
-    HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    HIP_TRY(hipStreamBeginCapture(h->play->stream, hipStreamCaptureModeThreadLocal));
     h->capturing = true;
     const int rc = cycle_level(h, l, b, xa, xb, x_zero, ctype, &e.result, false, false, nullptr, x1_given);
     h->capturing = false;
-    const hipError_t ce = hipStreamEndCapture(h->stream, &e.graph);
+    const hipError_t ce = hipStreamEndCapture(h->play->stream, &e.graph);
     if (rc != MG_OK || ce != hipSuccess) {
       if (e.graph) (void)hipGraphDestroy(e.graph);
       if (rc != MG_OK) return rc;
@@ -421,7 +423,7 @@ int cycle_sub(mg_hierarchy* h, int l, const double* b, double* xa, double* xb, b
     HIP_TRY(hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
     it = h->graphs.emplace(key, e).first;
   }
-  HIP_TRY(hipGraphLaunch(it->second.exec, h->stream));
+  HIP_TRY(hipGraphLaunch(it->second.exec, h->play->stream));
   ++h->graph_launches;
   *result = it->second.result;
   return MG_OK;
@@ -433,9 +435,9 @@ int cycle_dev(mg_hierarchy* h, const double* b, double* x, bool x_zero) {
   MG_TRY(gh_begin(h, &b, x, x_zero));   // (ghost-layer form: b with its ghost layers, bookkeeping reset)
   h->last_b = b;
   h->last_x = x;
-  MG_TRY(cycle_sub(h, 0, b, x, h->lev[0].x1.p, x_zero, h->cycle, &res));
+  MG_TRY(cycle_sub(h, 0, b, x, h->play->lev[0].x1.p, x_zero, h->cycle, &res));
   if (res != x)
-    HIP_TRY(hipMemcpyAsync(x, res, sizeof(double) * h->lev[0].n * h->nrhs, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(x, res, sizeof(double) * h->lev[0].n * h->play->nrhs, hipMemcpyDeviceToDevice, h->play->stream));
   return gh_check_depths(h);
 }
 
@@ -457,6 +459,7 @@ int cycle_dev(mg_hierarchy* h, const double* b, double* x, bool x_zero) {
 struct SolveLoop {
   mg_hierarchy* h;
   Level& L;
+  double* const Lr;                        // the fine-level residual of the lane being played
   const double* b;
   double* x;
   const double tol;
@@ -476,7 +479,7 @@ struct SolveLoop {
   int pending_slot = 0;
 
   SolveLoop(mg_hierarchy* h_, const double* b_, double* x_, double tol_, long long maxIter_, double* resvec_)
-      : h(h_), L(h_->lev[0]), b(b_), x(x_), tol(tol_), maxIter(maxIter_), resvec(resvec_), len(h_->lev[0].n * h_->nrhs) {}
+      : h(h_), L(h_->lev[0]), Lr(h_->play->res(0)), b(b_), x(x_), tol(tol_), maxIter(maxIter_), resvec(resvec_), len(h_->lev[0].n * h_->play->nrhs) {}
 
   int depth(const double* v) const { return gh_depth(h, 0, v); }
   int dec(int d) const { return gh_dec(h, 0, d); }
@@ -498,22 +501,22 @@ struct SolveLoop {
       MG_TRY(norm_of(b, &res0));
     } else if (ghs) {
       MG_TRY(need(x, 1));
-      MG_TRY(need(L.r.p, 0));
-      MG_TRY(k_residual(h, 0, L.A, b, x, L.r.p));
-      valid_on(L.r.p, std::min(dec(depth(x)), depth(b)));
-      MG_TRY(gh_norm_own(h, L.r.p, &res0));
+      MG_TRY(need(Lr, 0));
+      MG_TRY(k_residual(h, 0, L.A, b, x, Lr));
+      valid_on(Lr, std::min(dec(depth(x)), depth(b)));
+      MG_TRY(gh_norm_own(h, Lr, &res0));
     } else {
-      MG_TRY(k_residual_sumsq(h, 0, L.A, b, x, L.r.p));
+      MG_TRY(k_residual_sumsq(h, 0, L.A, b, x, Lr));
       MG_TRY(scalar_sync(h, &res0));
     }
     res = res0;
     if (resvec) resvec[0] = res0;
     cur = x;
-    alt = L.x1.p;
-    if (h->nrhs == 1 && !h->opt.no_march2 && !h->opt.no_fused_next && (L.A.rc_march2 || L.A.rc_march3) && std::max<long long>(1, L.npost) >= 1) {
+    alt = h->play->lev[0].x1.p;
+    if (h->play->nrhs == 1 && !h->opt.no_march2 && !h->opt.no_fused_next && (L.A.rc_march2 || L.A.rc_march3) && std::max<long long>(1, L.npost) >= 1) {
       if (L.x2.n != (size_t)len) {
         MG_TRY(L.x2.alloc((size_t)len));
-        HIP_TRY(hipMemsetAsync(L.x2.p, 0, L.x2.bytes(), h->stream));
+        HIP_TRY(hipMemsetAsync(L.x2.p, 0, L.x2.bytes(), h->play->stream));
       }
       spare = L.x2.p;
       fuse_post = march2_ok(h, 0, cur, alt, nullptr, spare) && march2_ok(h, 0, alt, spare, nullptr, cur) && march2_ok(h, 0, spare, cur, nullptr, alt) && gh_agree2(h, 0) && gh_agree_zero(h, 0);
@@ -553,7 +556,7 @@ struct SolveLoop {
   // the loop ended at the step whose input is `keep`: whatever was enqueued behind it is dropped, its iterate re-created
   int finish_from_keep() {
     MG_TRY(flush_deferred_sum(h));   // (the dropped step's sum: nobody reads it, but nothing may stay pending)
-    HIP_TRY(spin_sync(h->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     double* dst = cur == keep ? alt : cur;
     MG_TRY(need(keep, 1));
     MG_TRY(need(dst, 0));
@@ -566,7 +569,7 @@ struct SolveLoop {
 
   // (ghost-layer form: the pass consumes FOUR ghost layers of x in one kernel - a fine level with fewer takes the two-stage steps)
   bool four_stage_serves(long long count, bool deferred) const {
-    return deferred && count < maxIter && !h->opt.no_dead_t && march4_ok(h, 0, cur, alt, L.r.p) && (!gh0 || gh_level(h, 0)->gmin >= 4) && gh_agree4(h);
+    return deferred && count < maxIter && !h->opt.no_dead_t && march4_ok(h, 0, cur, alt, Lr) && (!gh0 || gh_level(h, 0)->gmin >= 4) && gh_agree4(h);
   }
 
   // cur (x before the last sweep) -> alt = t' (x after the next cycle's pre-smoothing), L.r = b - A t', ||r|| of THIS step into a
@@ -577,16 +580,16 @@ struct SolveLoop {
     MG_TRY(need(cur, 5));          // four products deep (+ the layer the restriction behind it reads, if the ghost layers reach that far)
     MG_TRY(need(b, 4));
     MG_TRY(need(alt, 0));
-    MG_TRY(need(L.r.p, 0));
+    MG_TRY(need(Lr, 0));
     bool sum_deferred = false;      // (single GPU: the partial sums are added up by one more workgroup of the next cycle's restriction)
-    MG_TRY(k_four_stage(h, 0, b, cur, alt, L.r.p, h->h_scalar + 1 + slot, gh0 || h->ghost ? nullptr : h->pipe_ev[slot], gh0 || h->ghost ? nullptr : &sum_deferred));   // alt: neither cur nor keep
+    MG_TRY(k_four_stage(h, 0, b, cur, alt, Lr, h->h_scalar + 1 + slot, gh0 || h->ghost ? nullptr : h->pipe_ev[slot], gh0 || h->ghost ? nullptr : &sum_deferred));   // alt: neither cur nor keep
     if (gh0) {
       const int db = depth(b), dt = std::min(dec(depth(cur)), db), dr = std::min(dec(dt), db), dn = std::min(dt, dr);
       const int dp = std::min(dec(dn), db);
       valid_on(alt, dp);
-      valid_on(L.r.p, std::min(dec(dp), db));
+      valid_on(Lr, std::min(dec(dp), db));
     }
-    if (!sum_deferred) HIP_TRY(hipEventRecord(h->pipe_ev[slot], h->stream));
+    if (!sum_deferred) HIP_TRY(hipEventRecord(h->pipe_ev[slot], h->play->stream));
     MG_TRY(read_pending(stop));
     if (*stop) return finish_from_keep();
     double* freed = keep;                           // (verified: the previous step's input is free again)
@@ -616,15 +619,15 @@ struct SolveLoop {
     if (ghs) {   // sharded: the residual is stored and its norm taken over the owned rows of all ranks
       MG_TRY(need(cur, 2));
       MG_TRY(need(b, 1));
-      for (double* v : {alt, L.r.p, spare}) MG_TRY(need(v, 0));
-      MG_TRY(k_smooth_residual(h, 0, b, cur, last ? alt : nullptr, L.r.p, next, false));
+      for (double* v : {alt, Lr, spare}) MG_TRY(need(v, 0));
+      MG_TRY(k_smooth_residual(h, 0, b, cur, last ? alt : nullptr, Lr, next, false));
       if (gh0) {
         const int db = depth(b), dt = std::min(dec(depth(cur)), db), dr = std::min(dec(dt), db);
         if (last) valid_on(alt, dt);
-        valid_on(L.r.p, dr);
+        valid_on(Lr, dr);
         if (next) valid_on(spare, std::min(dt, dr));
       }
-      MG_TRY(gh_norm_own(h, L.r.p, norm));
+      MG_TRY(gh_norm_own(h, Lr, norm));
     } else {
       MG_TRY(k_smooth_residual(h, 0, b, cur, last ? alt : nullptr, nullptr, next, true));
       MG_TRY(scalar_sync(h, norm));
@@ -643,13 +646,13 @@ struct SolveLoop {
   int step_residual(long long count, double* norm) {
     if (ghs) {
       MG_TRY(need(cur, 1));
-      MG_TRY(need(L.r.p, 0));
-      MG_TRY(k_residual(h, 0, L.A, b, cur, L.r.p));
-      valid_on(L.r.p, std::min(dec(depth(cur)), depth(b)));
+      MG_TRY(need(Lr, 0));
+      MG_TRY(k_residual(h, 0, L.A, b, cur, Lr));
+      valid_on(Lr, std::min(dec(depth(cur)), depth(b)));
       x1_ready = false;
-      return gh_norm_own(h, L.r.p, norm);
+      return gh_norm_own(h, Lr, norm);
     }
-    MG_TRY(k_residual_sumsq(h, 0, L.A, b, cur, L.r.p, count < maxIter ? alt : nullptr, &x1_ready, /*r_dead=*/true));
+    MG_TRY(k_residual_sumsq(h, 0, L.A, b, cur, Lr, count < maxIter ? alt : nullptr, &x1_ready, /*r_dead=*/true));
     return scalar_sync(h, norm);
   }
 
@@ -700,8 +703,8 @@ struct SolveLoop {
       MG_TRY(k_smooth(h, 0, L.A, L.d.p, b, spare, cur));
     }
     if (cur != x) {
-      HIP_TRY(hipMemcpyAsync(x, cur, sizeof(double) * len, hipMemcpyDeviceToDevice, h->stream));
-      HIP_TRY(spin_sync(h->stream));
+      HIP_TRY(hipMemcpyAsync(x, cur, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
+      HIP_TRY(spin_sync(h->play->stream));
     }
     if (iters) *iters = it;
     return gh_check_depths(h);
@@ -730,7 +733,7 @@ const char* columns_why_not(const mg_hierarchy* h) {
   if (h->nrhs < 2 || h->nrhs > 24) return "2 to 24 columns";
   if (h->opt.no_columns) return "switched off (MG_NO_COLUMNS)";
   if (h->relax_type != 0 || h->cycle == 'K' || h->coarse_gmres) return "pointwise smoother, V/W/F cycle, direct coarsest solve";
-  if (h->nlevels < 2 || !h->stream) return "two levels or more on a stream of the handle";
+  if (h->nlevels < 2 || !h->play->stream) return "two levels or more on a stream of the handle";
   const Level& L = h->lev[0];
   if (h->opt.no_march2 || h->opt.no_fused_next || h->opt.no_dead_t || h->opt.no_march4) return "the fused passes are switched off";
   if (!gh_agree4(h) || !gh_agree2(h, 0)) return "a rank of the sharded run whose fine level has no four-stage pass";
@@ -764,7 +767,7 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
     if (x_zero) {
       MG_TRY(norm_sync(h, b, len, &res0));
     } else {
-      MG_TRY(k_residual_sumsq(h, 0, L.A, b, x, L.r.p));
+      MG_TRY(k_residual_sumsq(h, 0, L.A, b, x, h->play->r0));
       MG_TRY(scalar_sync(h, &res0));
     }
     if (resvec) resvec[0] = res0;
@@ -774,7 +777,7 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
   for (auto& cb : h->colbuf)
     if (cb.n != (size_t)(ns * k)) {
       MG_TRY(cb.alloc((size_t)(ns * k)));
-      HIP_TRY(hipMemsetAsync(cb.p, 0, cb.bytes(), h->stream));
+      HIP_TRY(hipMemsetAsync(cb.p, 0, cb.bytes(), h->play->stream));
     }
   if (h->h_cols_n < k) {
     if (h->h_cols) (void)hipHostFree(h->h_cols);
@@ -785,14 +788,14 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
   double *colB = h->colbuf[0].p, *colX = h->colbuf[1].p, *colA = h->colbuf[2].p, *colR = h->colbuf[3].p;
   const unsigned tb = (unsigned)((n + 255) / 256);
   const size_t tlds = (size_t)k * 257 * sizeof(double);
-  hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->stream, b, colB, n, (int)k, ns);
-  if (x_zero) HIP_TRY(hipMemsetAsync(colX, 0, (size_t)(ns * k) * sizeof(double), h->stream));
-  else hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->stream, x, colX, n, (int)k, ns);
+  hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->play->stream, b, colB, n, (int)k, ns);
+  if (x_zero) HIP_TRY(hipMemsetAsync(colX, 0, (size_t)(ns * k) * sizeof(double), h->play->stream));
+  else hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->play->stream, x, colX, n, (int)k, ns);
   HIP_TRY(hipGetLastError());
   if (ghs) {   // SolveFuncs.jl:14-22 on the block: norms over the owned rows of all ranks, column by column
     auto block_norm = [&](const double* cols, double* out) -> int {
       for (long long c = 0; c < k; ++c) MG_TRY(gh_sumsq_own_to_slot(h, cols + c * ns, h->h_cols + c));
-      HIP_TRY(spin_sync(h->stream));
+      HIP_TRY(spin_sync(h->play->stream));
       double ss = 0.0;
       for (long long c = 0; c < k; ++c) {
         MG_TRY(gh_host_reduce(h, h->h_cols + c));
@@ -812,13 +815,10 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
     if (x_zero) {
       MG_TRY(block_norm(colB, &res0));
     } else {
+      Lane lane(h, 0, 1);
       for (long long c = 0; c < k; ++c) {
         if (gh0) MG_TRY(gh_need(h, 0, colX + c * ns, 1));
-        const long long keep_nrhs = h->nrhs;
-        h->nrhs = 1;
-        const int rc0 = k_residual(h, 0, L.A, colB + c * ns, colX + c * ns, colR + c * ns);
-        h->nrhs = keep_nrhs;
-        MG_TRY(rc0);
+        MG_TRY(k_residual(h, 0, L.A, colB + c * ns, colX + c * ns, colR + c * ns));
         if (gh0) gh_set(h, 0, colR + c * ns, std::min(gdec(gdep(colX + c * ns)), gdep(colB + c * ns)));
       }
       MG_TRY(block_norm(colR, &res0));
@@ -827,71 +827,33 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
     if (iters) *iters = 0;
     if (maxIter == 0) return MG_OK;
   }
-  // More streams (see mg_hierarchy::ColSet): column c plays in buffer set c mod S on that set's stream (set 0: the hierarchy's own).
-  const int nl = (int)h->nlevels;
-  const int S = (h->owns_stream && !h->coarse_lu && !h->prof && !h->ghost) ? (int)std::max<long long>(1, std::min<long long>({h->opt.columns_streams, 8LL, k})) : 1;
-  const bool two = S >= 2;
-  while ((int)h->colsets.size() < S - 1) h->colsets.push_back(new mg_hierarchy::ColSet());
+  // More streams: column c plays in lane c mod S, one vector at a time, on that lane's stream (lane 0: the hierarchy's own), its fine
+  // residual the column's slice of colR.
+  const int S = (h->play->owns_stream && !h->coarse_lu && !h->prof && !h->ghost) ? (int)std::max<long long>(1, std::min<long long>({h->opt.columns_streams, 8LL, k})) : 1;
+  while ((int)h->lanes.size() < S - 1) {
+    h->lanes.push_back(new Play());
+    h->lane_ready.push_back(nullptr);
+  }
   for (int si = 0; si < S - 1; ++si) {
-    mg_hierarchy::ColSet& cs = *h->colsets[(size_t)si];
-    if (!cs.stream) HIP_TRY(hipStreamCreateWithFlags(&cs.stream, hipStreamNonBlocking));
-    if (!cs.ready) HIP_TRY(hipEventCreateWithFlags(&cs.ready, hipEventDisableTiming));
-    for (auto* v : {&cs.b, &cs.r, &cs.x0, &cs.x1}) v->resize((size_t)nl);
-    for (int l = 1; l < nl; ++l)
-      for (auto* v : {&cs.b, &cs.r, &cs.x0, &cs.x1}) {
-        DevBuf<double>& d = (*v)[(size_t)l];
-        if (d.n != (size_t)h->lev[(size_t)l].n) {
-          MG_TRY(d.alloc((size_t)h->lev[(size_t)l].n));
-          HIP_TRY(hipMemset(d.p, 0, d.bytes()));
-        }
-      }
-    if (cs.partial.n != h->partial.n) MG_TRY(cs.partial.alloc(h->partial.n));
-    if (cs.partial2.n != std::max<size_t>(1, h->partial2.n)) MG_TRY(cs.partial2.alloc(std::max<size_t>(1, h->partial2.n)));
-    if (cs.scalar.n != std::max<size_t>(1, h->scalar.n)) MG_TRY(cs.scalar.alloc(std::max<size_t>(1, h->scalar.n)));
+    MG_TRY(h->lanes[(size_t)si]->alloc(h, 1, /*fine=*/false));
+    if (!h->lane_ready[(size_t)si]) HIP_TRY(hipEventCreateWithFlags(&h->lane_ready[(size_t)si], hipEventDisableTiming));
   }
-  // from here on the hierarchy plays one vector at a time; L.r points at the column's own residual
-  struct Restore {
-    mg_hierarchy* h; Level& L; long long nrhs; double* r;
-    hipStream_t stream; double *partial, *partial2, *scalar;
-    std::vector<std::array<double*, 4>> lv;
-    void set0() {
-      h->stream = stream; h->partial.p = partial; h->partial2.p = partial2; h->scalar.p = scalar;
-      for (size_t l = 1; l < lv.size(); ++l) {
-        Level& V = h->lev[l];
-        V.b.p = lv[l][0]; V.r.p = lv[l][1]; V.x0.p = lv[l][2]; V.x1.p = lv[l][3];
-      }
+  // (also the error path: nothing of a column may still be in flight on another lane's stream once this returns)
+  struct Drain {
+    mg_hierarchy* h;
+    ~Drain() {
+      for (Play* p : h->lanes)
+        if (p->stream) (void)spin_sync(p->stream);
     }
-    void set(int si) {
-      if (si == 0) { set0(); return; }
-      mg_hierarchy::ColSet& cs = *h->colsets[(size_t)si - 1];
-      h->stream = cs.stream; h->partial.p = cs.partial.p; h->partial2.p = cs.partial2.p; h->scalar.p = cs.scalar.p;
-      for (size_t l = 1; l < lv.size(); ++l) {
-        Level& V = h->lev[l];
-        V.b.p = cs.b[l].p; V.r.p = cs.r[l].p; V.x0.p = cs.x0[l].p; V.x1.p = cs.x1[l].p;
-      }
-    }
-    ~Restore() {
-      // (also the error path: nothing of a column may still be in flight on a second stream once the pointers are back, and the
-      // pinned scalar slot is no longer a mirror of h->scalar - the column norms were read with copies of their own)
-      for (mg_hierarchy::ColSet* cs : h->colsets)
-        if (cs && cs->stream) (void)spin_sync(cs->stream);
-      set0(); h->nrhs = nrhs; L.r.p = r; h->scalar_mirrored = false;
-    }
-  } restore{h, L, h->nrhs, L.r.p, h->stream, h->partial.p, h->partial2.p, h->scalar.p, {}};
-  restore.lv.resize((size_t)nl);
-  for (int l = 1; l < nl; ++l) {
-    Level& V = h->lev[(size_t)l];
-    restore.lv[(size_t)l] = {V.b.p, V.r.p, V.x0.p, V.x1.p};
-  }
-  h->nrhs = 1;
+  } drain{h};
   double *cur = colX, *alt = colA;               // (every column makes the same swaps: the columns of a role share an array)
-  int rc = MG_OK;
-  if (!x_zero && !ghs)      // (sharded: the residuals of the initial norm are those)
-    for (long long c = 0; c < k && rc == MG_OK; ++c) rc = k_residual(h, 0, L.A, colB + c * ns, cur + c * ns, colR + c * ns);
-  MG_TRY(rc);
-  for (int si = 0; si < S - 1; ++si) {   // (the columns of the other streams wait for the transposes)
-    HIP_TRY(hipEventRecord(h->colsets[(size_t)si]->ready, h->stream));
-    HIP_TRY(hipStreamWaitEvent(h->colsets[(size_t)si]->stream, h->colsets[(size_t)si]->ready, 0));
+  if (!x_zero && !ghs) {    // (sharded: the residuals of the initial norm are those)
+    Lane lane(h, 0, 1);
+    for (long long c = 0; c < k; ++c) MG_TRY(k_residual(h, 0, L.A, colB + c * ns, cur + c * ns, colR + c * ns));
+  }
+  for (int si = 0; si < S - 1; ++si) {   // (the columns of the other lanes wait for the transposes)
+    HIP_TRY(hipEventRecord(h->lane_ready[(size_t)si], h->play->stream));
+    HIP_TRY(hipStreamWaitEvent(h->lanes[(size_t)si]->stream, h->lane_ready[(size_t)si], 0));
   }
   bool pre_done = false;
   long long it = 0;
@@ -899,10 +861,9 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
     const bool last = count == maxIter;
     bool swapped = false;
     for (long long c = 0; c < k; ++c) {
-      if (two) restore.set((int)(c % S));
       const double* bc = colB + c * ns;
-      double *xc = cur + c * ns, *ac = alt + c * ns, *out = nullptr;
-      L.r.p = colR + c * ns;
+      double *xc = cur + c * ns, *ac = alt + c * ns, *rc = colR + c * ns, *out = nullptr;
+      Lane lane(h, (int)(c % S), 1, rc);
       bool deferred = true;
       MG_TRY(cycle_level(h, 0, bc, xc, ac, x_zero && count == 1, h->cycle, &out, /*r_valid=*/count > 1 || !x_zero, false, &deferred, false, pre_done));
       if (!deferred) return fail(MG_ERR_STATE, "column-wise solve: the fine level left its last sweep inside the cycle");
@@ -910,45 +871,43 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
       else if (swapped != (out != xc)) return fail(MG_ERR_STATE, "column-wise solve: columns disagree on their buffers");
       double *xin = swapped ? ac : xc, *xout = swapped ? xc : ac;     // xin: x before the last sweep
       if (!last) {
-        if (!march4_ok(h, 0, xin, xout, L.r.p)) return fail(MG_ERR_STATE, "column-wise solve: the four-stage pass does not serve the fine level");
+        if (!march4_ok(h, 0, xin, xout, rc)) return fail(MG_ERR_STATE, "column-wise solve: the four-stage pass does not serve the fine level");
         if (gh0) {
           MG_TRY(gh_need(h, 0, xin, 5));
           MG_TRY(gh_need(h, 0, bc, 4));
           MG_TRY(gh_need(h, 0, xout, 0));
-          MG_TRY(gh_need(h, 0, L.r.p, 0));
+          MG_TRY(gh_need(h, 0, rc, 0));
         }
-        MG_TRY(k_four_stage(h, 0, bc, xin, xout, L.r.p, h->h_cols + c));       // xout = t', L.r = r', ||r_c||^2 of this step
+        MG_TRY(k_four_stage(h, 0, bc, xin, xout, rc, h->h_cols + c));       // xout = t', rc = r', ||r_c||^2 of this step
         if (gh0) {
           const int db = gdep(bc), dt = std::min(gdec(gdep(xin)), db), dr = std::min(gdec(dt), db), dn = std::min(dt, dr);
           const int dp = std::min(gdec(dn), db);
           gh_set(h, 0, xout, dp);
-          gh_set(h, 0, L.r.p, std::min(gdec(dp), db));
+          gh_set(h, 0, rc, std::min(gdec(dp), db));
         }
       } else if (ghs) {   // sharded: the residual is stored, its norm taken over the owned rows of all ranks
         if (gh0) {
           MG_TRY(gh_need(h, 0, xin, 2));
           MG_TRY(gh_need(h, 0, bc, 1));
           MG_TRY(gh_need(h, 0, xout, 0));
-          MG_TRY(gh_need(h, 0, L.r.p, 0));
+          MG_TRY(gh_need(h, 0, rc, 0));
         }
-        MG_TRY(k_smooth_residual(h, 0, bc, xin, xout, L.r.p, nullptr, false));
+        MG_TRY(k_smooth_residual(h, 0, bc, xin, xout, rc, nullptr, false));
         if (gh0) {
           const int db = gdep(bc), dt = std::min(gdec(gdep(xin)), db);
           gh_set(h, 0, xout, dt);
-          gh_set(h, 0, L.r.p, std::min(gdec(dt), db));
+          gh_set(h, 0, rc, std::min(gdec(dt), db));
         }
-        MG_TRY(gh_sumsq_own_to_slot(h, L.r.p, h->h_cols + c));
+        MG_TRY(gh_sumsq_own_to_slot(h, rc, h->h_cols + c));
       } else {
         MG_TRY(k_smooth_residual(h, 0, bc, xin, xout, nullptr, nullptr, true));  // xout = the iterate, ||r_c||^2
-        HIP_TRY(hipMemcpyAsync(h->h_cols + c, h->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->h_cols + c, h->play->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->play->stream));
+        h->play->scalar_mirrored = false;   // (the lanes share the pinned slot: read with a copy of its own, it mirrors none of them)
       }
     }
     if (swapped) std::swap(cur, alt);              // cur: x before the last sweep (every column); alt: t' / the iterate
-    if (two) {
-      restore.set0();
-      for (int si = 0; si < S - 1; ++si) HIP_TRY(spin_sync(h->colsets[(size_t)si]->stream));
-    }
-    HIP_TRY(spin_sync(h->stream));
+    for (int si = 0; si < S - 1; ++si) HIP_TRY(spin_sync(h->lanes[(size_t)si]->stream));
+    HIP_TRY(spin_sync(h->play->stream));
     double ss = 0.0;
     for (long long c = 0; c < k; ++c) {
       if (ghs) MG_TRY(gh_host_reduce(h, h->h_cols + c));   // (host-staged transport: the ranks' sums are added here)
@@ -960,6 +919,7 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
     const bool stop = res / res0 < tol;            // SolveFuncs.jl:34-36
     if (last) { std::swap(cur, alt); break; }      // (the iterate was written)
     if (stop) {                                    // the two speculative stages are dropped: the iterate from the pass's input
+      Lane lane(h, 0, 1);
       for (long long c = 0; c < k; ++c) {
         if (gh0) { MG_TRY(gh_need(h, 0, cur + c * ns, 1)); MG_TRY(gh_need(h, 0, alt + c * ns, 0)); }
         MG_TRY(k_smooth(h, 0, L.A, L.d.p, colB + c * ns, cur + c * ns, alt + c * ns));
@@ -970,9 +930,9 @@ int solve_dev_columns(mg_hierarchy* h, const double* b, double* x, double tol, l
     std::swap(cur, alt);                           // t': the next cycle's x after its pre-smoothing
     pre_done = true;
   }
-  hipLaunchKernelGGL((mgk::block_columns_transpose<false>), dim3(tb), dim3(256), tlds, h->stream, cur, x, n, (int)k, ns);
+  hipLaunchKernelGGL((mgk::block_columns_transpose<false>), dim3(tb), dim3(256), tlds, h->play->stream, cur, x, n, (int)k, ns);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(spin_sync(h->stream));
+  HIP_TRY(spin_sync(h->play->stream));
   if (iters) *iters = it;
   return gh_check_depths(h);
 }
@@ -985,20 +945,20 @@ int cycle_dev_columns(mg_hierarchy* h, const double* b, double* x, bool x_zero) 
   for (int i = 0; i < 2; ++i)
     if (h->colbuf[i].n != (size_t)(ns * k)) {
       MG_TRY(h->colbuf[i].alloc((size_t)(ns * k)));
-      HIP_TRY(hipMemsetAsync(h->colbuf[i].p, 0, h->colbuf[i].bytes(), h->stream));
+      HIP_TRY(hipMemsetAsync(h->colbuf[i].p, 0, h->colbuf[i].bytes(), h->play->stream));
     }
   double *colB = h->colbuf[0].p, *colX = h->colbuf[1].p;
   const unsigned tb = (unsigned)((n + 255) / 256);
   const size_t tlds = (size_t)k * 257 * sizeof(double);
-  hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->stream, b, colB, n, (int)k, ns);
-  if (x_zero) HIP_TRY(hipMemsetAsync(colX, 0, (size_t)(ns * k) * sizeof(double), h->stream));
-  else hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->stream, x, colX, n, (int)k, ns);
+  hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->play->stream, b, colB, n, (int)k, ns);
+  if (x_zero) HIP_TRY(hipMemsetAsync(colX, 0, (size_t)(ns * k) * sizeof(double), h->play->stream));
+  else hipLaunchKernelGGL((mgk::block_columns_transpose<true>), dim3(tb), dim3(256), tlds, h->play->stream, x, colX, n, (int)k, ns);
   HIP_TRY(hipGetLastError());
-  struct Restore { mg_hierarchy* h; long long nrhs; ~Restore() { h->nrhs = nrhs; } } restore{h, h->nrhs};
-  h->nrhs = 1;
-  for (long long c = 0; c < k; ++c) MG_TRY(cycle_dev(h, colB + c * ns, colX + c * ns, x_zero));
-  h->nrhs = k;
-  hipLaunchKernelGGL((mgk::block_columns_transpose<false>), dim3(tb), dim3(256), tlds, h->stream, colX, x, n, (int)k, ns);
+  {
+    Lane lane(h, 0, 1);
+    for (long long c = 0; c < k; ++c) MG_TRY(cycle_dev(h, colB + c * ns, colX + c * ns, x_zero));
+  }
+  hipLaunchKernelGGL((mgk::block_columns_transpose<false>), dim3(tb), dim3(256), tlds, h->play->stream, colX, x, n, (int)k, ns);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -1006,8 +966,8 @@ int cycle_dev_columns(mg_hierarchy* h, const double* b, double* x, bool x_zero) 
 // dot(x,y) on the host; synchronises the stream
 int dot_sync(mg_hierarchy* h, const double* x, const double* y, long long len, double* out) {
   const int nb = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (len / 2 + mgk::BLK - 1) / mgk::BLK));
-  hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->stream, x, y, len, h->partial.p);
-  launch_sum_final(h, h->partial.p, nb);
+  hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, x, y, len, h->play->partial.p);
+  launch_sum_final(h, h->play->partial.p, nb);
   HIP_TRY(hipGetLastError());
   MG_TRY(scalar_wait(h));
   *out = *h->h_scalar;
@@ -1022,23 +982,23 @@ int k_spmv_dot(mg_hierarchy* h, int level, const Csr& A, const double* x, double
   v.y = y;
   v.alpha = 1.0;
   v.beta = 0.0;
-  v.nrhs = (int)h->nrhs;
-  if (h->nrhs == 1 && march_ok(A, v) && A.rc_nexc == 0 && (size_t)A.rm_nblocks <= h->partial.n) {
-    v.sumsq = h->partial.p;
+  v.nrhs = (int)h->play->nrhs;
+  if (h->play->nrhs == 1 && march_ok(A, v) && A.rc_nexc == 0 && (size_t)A.rm_nblocks <= h->play->partial.n) {
+    v.sumsq = h->play->partial.p;
     v.dotx = 1;
     int nb1 = 0;
     {
       ProfScope ps(h, level, MG_K_SPMV, spmv_bytes(A, 1, false, false), moved_bytes(A, 1, false, false));
-      MG_TRY(launch_csr<mgk::AXPBY>(h->stream, A, v, &nb1));
+      MG_TRY(launch_csr<mgk::AXPBY>(h->play->stream, A, v, &nb1));
     }
-    launch_sum_final(h, h->partial.p, nb1);
+    launch_sum_final(h, h->play->partial.p, nb1);
     HIP_TRY(hipGetLastError());
     MG_TRY(scalar_wait(h));
     *out = *h->h_scalar;
     return MG_OK;
   }
   MG_TRY(k_spmv(h, level, MG_K_SPMV, A, 1.0, x, 0.0, y));
-  return dot_sync(h, x, y, (long long)A.n_rows * h->nrhs, out);
+  return dot_sync(h, x, y, (long long)A.n_rows * h->play->nrhs, out);
 }
 
 }  // namespace

@@ -604,14 +604,46 @@ struct Level {
   bool relax_set = false;
   long long npre = 1, npost = 1;
   long long n = 0;
-  // CYCLEmem (MGdef.jl:56-60) plus the Jacobi ping-pong partner of x
-  DevBuf<double> b, r, x0, x1;
+  // (the vectors a cycle plays in - b, r, x0, x1 - are per lane: Play)
   DevBuf<double> x2;   // fine level, solve loop: third rotating buffer of the fused last sweep + residual (allocated on first use)
   DevBuf<double> x3;   // scratch for outputs of the fused sweep + residual nobody asked for (test entry point only)
   // FGMRESmem (FGMRES.jl:3-8): Z and A*Z bases, `inner` contiguous vectors of n*nrhs each.
   // relaxZ/relaxAZ: memRelax[level] (Jac-GMRES smoother); kZ/kAZ: memKcycle (K-cycle recursion INTO this level)
   DevBuf<double> relaxZ, relaxAZ, kZ, kAZ;
   long long relax_inner = 0;
+};
+
+// What a cycle plays in: a stream, the reduction buffers and the vectors of every level.  The handle's own lane (lane 0) is as wide
+// as the handle; the further lanes of the column-wise block solve (solve_dev_columns) hold one column each, so that one column's
+// launch-bound coarse levels and kernel ramps run under another's fine-level kernels.
+struct Play {
+  hipStream_t stream = nullptr;
+  bool owns_stream = true;         // the library created it (mg_set_stream: the caller's)
+  DevBuf<double> partial, partial2, scalar;   // reductions
+  bool scalar_mirrored = false;    // the kernel that produced `scalar` also stored it into the handle's pinned h_scalar (sum_final_mirror)
+  // CYCLEmem (MGdef.jl:56-60) plus the Jacobi ping-pong partner of x
+  struct Vecs { DevBuf<double> b, r, x0, x1; };
+  std::vector<Vecs> lev;
+  // not owned
+  long long nrhs = 1;              // columns per vector the kernels see: 1 while a block is played column by column, else the handle's
+  double* r0 = nullptr;            // fine-level residual in use: the lane's own, or a column's slice of colbuf[3]
+  double* res(int l) const { return l == 0 ? r0 : lev[(size_t)l].r.p; }
+  void rest(long long width) {     // (no column in play)
+    nrhs = width;
+    r0 = lev.empty() ? nullptr : lev[0].r.p;
+  }
+  int alloc(const mg_hierarchy* h, long long width, bool fine);
+  void release_vectors() {
+    for (Vecs& V : lev)
+      for (DevBuf<double>* d : {&V.b, &V.r, &V.x0, &V.x1}) d->release();
+    r0 = nullptr;
+  }
+  void release() {
+    release_vectors();
+    for (DevBuf<double>* d : {&partial, &partial2, &scalar}) d->release();
+    if (stream && owns_stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+  }
 };
 
 struct ProfSlot {
@@ -656,7 +688,7 @@ struct mg_hierarchy {
   // launch-bound coarse sub-cycles replay as HIP graphs (captured on first use; keyed by level, buffers and cycle)
   struct GraphKey {
     int level; bool x_zero; char ctype; const void* b; const void* xa; const void* xb; bool x1_given;
-    long long nrhs;   // (the column-wise block solve plays one vector at a time on the block's own level buffers: same pointers, other kernels)
+    long long nrhs;
     bool operator<(const GraphKey& o) const {
       return std::tie(level, x_zero, ctype, b, xa, xb, x1_given, nrhs) < std::tie(o.level, o.x_zero, o.ctype, o.b, o.xa, o.xb, o.x1_given, o.nrhs);
     }
@@ -665,27 +697,16 @@ struct mg_hierarchy {
   std::map<GraphKey, GraphEntry> graphs;
   bool capturing = false;
   long long graph_launches = 0;
-  hipStream_t stream = nullptr;
-  bool owns_stream = true;
-  // reductions
-  DevBuf<double> partial, partial2, scalar;
+  Play lane0;                  // the handle's own lane
+  std::vector<Play*> lanes;    // solve_dev_columns: lanes 1..S-1 (column c plays in lane c mod S), without fine-level vectors
+  std::vector<hipEvent_t> lane_ready;   // ... and the event behind which each of them starts (the transposes)
+  Play* play = &lane0;         // not owned: the lane being played (set for a scope by Lane)
   DevBuf<double> m3sink;       // csr_rowclass_march3_spmv: one slot per lane for the stores of lanes with nothing to store
-  // solve_dev_columns, second stream: a second set of the buffers a cycle plays in below the fine level, of the norm's partial sums,
-  // and a stream of its own - consecutive columns alternate between the two sets, so that one column's launch-bound coarse levels
-  // and kernel ramps run under the other's fine-level kernels
-  struct ColSet {
-    hipStream_t stream = nullptr;
-    std::vector<DevBuf<double>> b, r, x0, x1;   // per level (index 0 unused)
-    DevBuf<double> partial, partial2, scalar;
-    hipEvent_t ready = nullptr;
-  };
-  std::vector<ColSet*> colsets;   // (streams - 1 of them)
   DevBuf<double> colbuf[4];    // solve_dev_columns: b, x, the second iterate buffer and r as k columns of stride ns
   double* h_cols = nullptr;    // pinned: ||r_c||^2 of every column of the step in flight
   long long h_cols_n = 0;
   double* h_scalar = nullptr;  // pinned: [0] the scalar of scalar_sync / dot_sync; [1], [2] the norms of the pipelined solve loop
   hipEvent_t pipe_ev[2] = {nullptr, nullptr};   // ... and the events behind them
-  bool scalar_mirrored = false;   // the kernel that produced h->scalar also stored it into h_scalar (sum_final_mirror)
   struct DeferredSum { bool on = false; int np = 0; double* host = nullptr; hipEvent_t ev = nullptr; } dsum;   // the four-stage pass's final sum, left to the next launch (k_four_stage / k_spmv)
   int nred_blocks = 1024;
   // staging for the host-pointer API
@@ -717,3 +738,44 @@ struct mg_hierarchy {
   std::vector<hipEvent_t> ev_pool;
 };
 
+namespace {
+// The lane's level vectors for `width` columns (fine: the fine level's r and x1 too), its reduction buffers as large as lane 0's and,
+// unless it plays on a caller's stream, a stream of its own.  A buffer whose size changes is allocated anew and zeroed.
+int Play::alloc(const mg_hierarchy* h, long long width, bool fine) {
+  if (!stream && owns_stream) HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  lev.resize((size_t)h->nlevels);
+  for (int l = fine ? 0 : 1; l < (int)h->nlevels; ++l) {
+    const size_t len = (size_t)h->lev[(size_t)l].n * (size_t)width;
+    Vecs& V = lev[(size_t)l];
+    for (DevBuf<double>* d : {&V.r, &V.x1, &V.b, &V.x0}) {
+      if (l == 0 && (d == &V.b || d == &V.x0)) continue;   // (the fine b and x are the caller's)
+      if (d->n == std::max<size_t>(1, len)) continue;
+      MG_TRY(d->alloc(len));
+      HIP_TRY(hipMemset(d->p, 0, d->bytes()));
+    }
+  }
+  // (the fused residual + norm writes one partial per row block of the fine operator)
+  const size_t np = std::max({h->lane0.partial.n, (size_t)h->nred_blocks, (size_t)h->lev[0].A.nblocks, (size_t)h->lev[0].A.ln_blocks});
+  if (partial.n != np) MG_TRY(partial.alloc(np));
+  if (partial2.n != 256) MG_TRY(partial2.alloc(256));
+  if (scalar.n != 1) MG_TRY(scalar.alloc(1));
+  rest(width);
+  return MG_OK;
+}
+
+// Plays lane `si` for its lifetime, `width` columns per vector, the fine-level residual at r (nullptr: the lane's own).  Afterwards the
+// handle plays its own lane again, at its own width.
+struct Lane {
+  mg_hierarchy* h;
+  Lane(mg_hierarchy* h_, int si, long long width, double* r = nullptr) : h(h_) {
+    h->play = si == 0 ? &h->lane0 : h->lanes[(size_t)si - 1];
+    h->play->nrhs = width;
+    if (r) h->play->r0 = r;
+  }
+  Lane(const Lane&) = delete;
+  ~Lane() {
+    h->play = &h->lane0;
+    h->lane0.rest(h->nrhs);
+  }
+};
+}  // namespace

@@ -95,3 +95,67 @@ def test_block_cycle_and_column_solve_share_one_handle(mg, built, monkeypatch):
         assert np.abs(X - Xo).max() <= RES_TOL * np.abs(Xo).max(), rep
     assert h.graph_launches()[1] >= 2          # (graphs of both kinds are cached side by side)
     mg.clear_(p)
+
+
+@pytest.mark.gpu
+def test_stream_count_does_not_change_a_bit(mg, built, monkeypatch):
+    """Column c plays in lane c mod S: one, two and three streams over five columns (lanes of 2, 2 and 1 columns with three) give the
+    same bits - and every column those of solveMG on that column alone.  The grid of the shared-handle test: the sub-cycle's graph
+    starts at level 1, the four-stage pass serves the fine level."""
+    _env(monkeypatch)
+    monkeypatch.setenv("MG_NO_COLUMNS", "0")
+    cells, levels, nrhs, steps = [24, 19, 16], 3, 5, 3
+    runs = {}
+    for streams in (1, 2, 3):
+        monkeypatch.setenv("MG_COLUMNS_STREAMS", str(streams))
+        A, p, B = _setup(mg, cells, levels, nrhs, cyc="W", tol=0.0, maxIter=steps)
+        h = mg.to_device(p)
+        assert h.four_stage_form(1)[0]
+        X = np.zeros_like(B)
+        _, _, it = mg.solveMG(p, B, X)
+        assert it == steps
+        if streams == 1:
+            hist = {}
+            Xo = np.zeros_like(B)
+            orc.solveMG(p, B, Xo, False, hist)
+            assert np.abs(p.resvec - hist["resvec"]).max() / hist["resvec"][0] < RES_TOL
+            assert np.abs(X - Xo).max() <= RES_TOL * np.abs(Xo).max()
+        runs[streams] = (X.copy(), np.asarray(p.resvec).copy())
+        mg.clear_(p)
+    for streams in (2, 3):
+        assert np.array_equal(runs[streams][0], runs[1][0]), streams
+        assert np.array_equal(runs[streams][1], runs[1][1]), streams
+    A, p1, _ = _setup(mg, cells, levels, 1, cyc="W", tol=0.0, maxIter=steps)
+    for c in range(nrhs):
+        xc = np.zeros(A.shape[0])
+        mg.solveMG(p1, np.ascontiguousarray(B[:, c]), xc)
+        for streams in (1, 2, 3):
+            assert np.array_equal(xc, runs[streams][0][:, c]), (c, streams)
+    mg.clear_(p1)
+
+
+@pytest.mark.gpu
+def test_handle_is_itself_again_after_a_column_solve(mg, built, monkeypatch):
+    """Column-wise solve on three lanes, a block cycle (SpMM kernels, width 4), the column-wise solve again, on ONE handle: the two
+    solves give the same bits and the block cycle between them is the oracle's - the solve leaves the handle playing its own lane
+    at its own width."""
+    _env(monkeypatch)
+    monkeypatch.setenv("MG_NO_COLUMNS", "0")
+    monkeypatch.setenv("MG_COLUMNS_STREAMS", "3")
+    A, p, B = _setup(mg, [24, 19, 16], 3, 4, cyc="W", tol=0.0, maxIter=3)
+    h = mg.to_device(p)
+    assert h.four_stage_form(1)[0]
+    solves = []
+    for rep in range(2):
+        X = np.zeros_like(B)
+        mg.solveMG(p, B, X)
+        solves.append((X, np.asarray(p.resvec).copy()))
+        if rep == 0:
+            Z = np.zeros_like(B)
+            mg.recursiveCycle(p, B, Z, 1)
+            Zo = orc.recursiveCycle(p, B, np.zeros_like(B), 1, None, "W")
+            assert np.abs(Z - Zo).max() <= RES_TOL * np.abs(Zo).max()
+    assert np.array_equal(solves[0][0], solves[1][0])
+    assert np.array_equal(solves[0][1], solves[1][1])
+    assert h.graph_launches()[1] >= 2
+    mg.clear_(p)
