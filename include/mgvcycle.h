@@ -102,8 +102,18 @@ int mg_set_option(mg_hierarchy* h, const char* key, double value);
 
 /* relaxType: 0 = pointwise relaxPrecs ("Jac", "SPAI": relax(), MGcycle.jl:122-136);
  * 1 = "Jac-GMRES": FGMRES_relaxation with npre/npost inner directions, preconditioned by relaxPrecs
- * (FGMRES.jl:48-126, MGcycle.jl:35-38,48-50,96-98).  Call before mg_finalize. */
+ * (FGMRES.jl:48-126, MGcycle.jl:35-38,48-50,96-98);
+ * 2 = the Vanka cell-block smoother (RelaxVankaFacesColor, MGcycle.jl:51-52,99-100) with the blocks mg_set_vanka_FP64 bound to
+ * every non-coarsest level: npre / npost in-place iterations (a count of 0: no sweep), no fused passes and no graph replay.
+ * FP64 handles, one right-hand side, V / W / F cycles (MG_ERR_UNSUPPORTED otherwise).  Call before mg_finalize. */
 int mg_set_relax_type(mg_hierarchy* h, long long relaxType);
+
+/* Bind the Vanka blocks of `level` (relaxation type 2): n[dim] cells of the level's RegularMesh, VankaType 1 (FULL_VANKA_RB),
+ * 3 (ECON_VANKA_RB) or 5 (FULL_VANKA_ADD), D_blocks as for mg_vanka_create_FP64_INT64.  The level's operator must have been
+ * uploaded (mg_set_operator_FP64_INT64) and have sum(nf) [+ prod(n)] rows; the sweep counts are those of mg_set_relax_FP64.
+ * mg_finalize fails with MG_ERR_STATE if type 2 is set and a non-coarsest level has no blocks. */
+int mg_set_vanka_FP64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
+                      long long VankaType, const float* D_blocks);
 
 /* cycleType: 'V', 'W', 'F' (MGcycle.jl:78-85) or 'K' (2-step FGMRES recursion, MGcycle.jl:72-76). */
 int mg_set_cycle_type(mg_hierarchy* h, long long cycleType);
@@ -559,6 +569,37 @@ int mg_dd_info(mg_dd* dd, long long* info);
 int mg_dd_time_dev(mg_dd* dd, const double* b_dev, double* x_dev, long long n, long long doTranspose, long long warmup,
                    long long reps, double* ms);
 int mg_dd_destroy(mg_dd* dd);
+
+/* ---- Vanka cell-block smoother (src/Multigrid/Vanka.jl) ----------------------------------------------------------
+ * RelaxVankaFacesColor's Julia serial path (Vanka.jl:383-425) on the device, for staggered-grid systems whose unknowns are
+ * ordered x-faces, y-faces [, z-faces] [, cell pressures] of a RegularMesh of n cells.  The handle holds the CSR of the
+ * applied operator A (1-based Int64; valA the values of A's rows, CFP64: interleaved complex doubles) and LocalBlocks of
+ * setupVankaFacesPreconditioner, (bs*bs) x prod(n) column-major Float32 (CFP64: ComplexF32), bs = 2*dim + includePressure.
+ * VankaType: 1 FULL_VANKA_RB and 3 ECON_VANKA_RB (2^dim coloured passes per iteration, each from a snapshot of x),
+ * 5 FULL_VANKA_ADD (corrections formed once per call from the incoming x, added numit times); 4 (FULL_VANKA_LEX), 2 and
+ * unknown types: MG_ERR_UNSUPPORTED.  nrows != sum(nf) [+ prod(n)] and other inconsistent sizes: MG_ERR_INVALID.  numit = 0
+ * does nothing.  The result does not depend on the order the cells run in (no atomics: identical bits on every run).  A
+ * handle is bound to its value type as mg_dd is (MG_ERR_STATE).  x (in/out) and b are two different vectors of nrows values. */
+typedef struct mg_vanka mg_vanka;
+int mg_vanka_create_FP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure,
+                               long long nrows, const long long* rowptr, const long long* colA, const double* valA,
+                               const float* D_blocks, mg_vanka** out);
+int mg_vanka_create_CFP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure,
+                                long long nrows, const long long* rowptr, const long long* colA, const double* valA,
+                                const float* D_blocks, mg_vanka** out);
+int mg_vanka_apply_FP64(mg_vanka* v, double* x, const double* b, long long numit, long long VankaType);
+int mg_vanka_apply_dev_FP64(mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long VankaType);
+int mg_vanka_apply_CFP64(mg_vanka* v, double* x, const double* b, long long numit, long long VankaType);
+int mg_vanka_apply_dev_CFP64(mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long VankaType);
+/* info[0..8): value type (0 Float64, 1 ComplexF64); blockSize; cells; colours (2^dim); kernel launches of one RB / ECON
+ * iteration (two per colour that holds a cell); of one ADD iteration (one, plus one per call); unknowns; kernels the handle
+ * has enqueued so far. */
+int mg_vanka_info(mg_vanka* v, long long* info);
+/* Measurement, as mg_dd_time_dev: `warmup` untimed iterations on device vectors, then `reps`, each between two events on
+ * the handle's stream; ms[0..reps) in milliseconds.  x_dev is relaxed in place. */
+int mg_vanka_time_dev(mg_vanka* v, double* x_dev, const double* b_dev, long long VankaType, long long warmup, long long reps,
+                      double* ms);
+int mg_vanka_destroy(mg_vanka* v);
 
 /* ---- native multi-GPU sequencer (one process per GPU) ---------------------------------------------------------
  * The sharded cycle of src/DomainDecomposition's partition (box rule DDIndices.jl:41-47, numbering DDService.jl:27-48;

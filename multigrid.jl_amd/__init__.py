@@ -18,6 +18,14 @@ from .wrappers import (MGsolver, getMGsolver, getSA_AMGsolver, solveLinearSystem
                        clearSolver_)
 from .par_relax import (hybridKaczmarz, getHybridKaczmarz, setupHybridKaczmarz, getHybridKaczmarzPrecond,
                         applyHybridKaczmarz)
+from .vanka import (FULL_VANKA_RB, KACMARZ_VANKA, ECON_VANKA_RB, FULL_VANKA_LEX, FULL_VANKA_ADD, getVankaRelaxType,
+                    getVankaBlockSize, getVankaVariablesOfCell, cellRBColor, setupVankaFacesPreconditioner,
+                    RelaxVankaFacesColor)
+from .systems import (get1DNodeInjection, get1DNodeFullWeightRestriction, get1DProlongationCellCentered,
+                      get1DRestrictionCells, get1DProlongationNodes, getRestrictionFacesInjectionUj,
+                      getRestrictionFacesFullWeightUj, getLinearInterpolationFacesUj, getLinearInterpolationCellCentered,
+                      getLinearOperatorsSystemsFaces, getInjectionOperatorsSystemsFaces)
+# (getRestrictionCellCentered of Systems.jl is the one transfer_operators already exports above: same kron of the 1-D cell aggregations)
 from .dd_indices import (getIndicesOfCellsArray, getNodalIndicesOfCell, getOriginalBoundingBoxCells, getBoxWithOverlap,
                          cs2loc, loc2cs)
 from .domain_decomposition import (DomainDecompositionParam, DomainDecompositionPreconditionerParam, getDomainDecompositionParam,

@@ -204,6 +204,7 @@ int mg_destroy(mg_hierarchy* h) {
   prof_collect(h);
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   for (auto& L : h->lev) {
+    if (L.vanka) { L.vanka->release(); delete L.vanka; L.vanka = nullptr; }
     L.A.release();
     L.P.release();
     L.R.release();
@@ -327,9 +328,41 @@ int mg_set_grid_hint(mg_hierarchy* h, long long level, long long n1, long long n
 int mg_set_relax_type(mg_hierarchy* h, long long relaxType) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   graphs_clear(h);
-  if (relaxType != 0 && relaxType != 1) return fail(MG_ERR_INVALID, "relaxType must be 0 (Jac/SPAI) or 1 (Jac-GMRES)");
+  if (relaxType != 0 && relaxType != 1 && relaxType != 2) return fail(MG_ERR_INVALID, "relaxType must be 0 (Jac/SPAI), 1 (Jac-GMRES) or 2 (Vanka)");
   if (h->cx && relaxType == 1) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF64 handles");
+  if (h->cx && relaxType == 2) return fail(MG_ERR_UNSUPPORTED, "relaxation type 2 (Vanka) is not served for CF64 handles");
   h->relax_type = (int)relaxType;
+  h->finalized = false;
+  return MG_OK;
+}
+
+// The Vanka blocks of one level (relaxation type 2), built from the operator the level already holds
+int mg_set_vanka_FP64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
+                      long long VankaType, const float* D_blocks) {
+  MG_CF64_UNSUPPORTED(h);
+  UploadFence upload_fence;
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  graphs_clear(h);
+  Level* L;
+  MG_TRY(find_level(h, level, &L));
+  if (!L->A.set) return fail(MG_ERR_STATE, "As[%lld] was not set: upload the operator before its Vanka blocks", level);
+  if (L->A.wide) return fail(MG_ERR_UNSUPPORTED, "operators with 64-bit row pointers are not served by the Vanka smoother");
+  if (L->A.n_rows != L->A.n_cols) return fail(MG_ERR_INVALID, "As[%lld] is not square", level);
+  MG_TRY(vanka_type_served(VankaType));
+  mgk::VankaGeo G;
+  MG_TRY(vanka_geometry(dim, n, includePressure, L->A.n_rows, &G));
+  (void)hipSetDevice(h->device);
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  if (L->vanka) { L->vanka->release(); delete L->vanka; L->vanka = nullptr; }
+  VankaCore* V = new VankaCore();
+  const int rc = vanka_core_init(V, false, G, D_blocks);
+  if (rc != MG_OK) {
+    V->release();
+    delete V;
+    return rc;
+  }
+  L->vanka = V;
+  L->vanka_type = (int)VankaType;
   h->finalized = false;
   return MG_OK;
 }
@@ -528,6 +561,12 @@ int mg_finalize(mg_hierarchy* h) {
     if (L.R.n_rows != nc || L.R.n_cols != L.n)
       return fail(MG_ERR_INVALID, "Rs[%d] is %lldx%lld, expected %lldx%lld", l + 1, L.R.n_rows, L.R.n_cols, nc, L.n);
   }
+  if (h->relax_type == 2)
+    for (int l = 0; l < nl - 1; ++l) {
+      const Level& L = h->lev[(size_t)l];
+      if (!L.vanka) return fail(MG_ERR_STATE, "relaxation type 2 (Vanka) is set, but level %d has no blocks (mg_set_vanka_FP64)", l + 1);
+      if (L.vanka->G.N != L.n) return fail(MG_ERR_INVALID, "the Vanka blocks of level %d serve %d unknowns, As[%d] has %lld rows", l + 1, L.vanka->G.N, l + 1, L.n);
+    }
   if (!h->coarse_set) return fail(MG_ERR_STATE, "the coarsest solve was not set");
   if (h->n_coarse != h->lev[nl - 1].n)
     return fail(MG_ERR_INVALID, "coarse inverse order %lld != coarsest level size %lld", h->n_coarse, h->lev[nl - 1].n);

@@ -120,6 +120,13 @@ int fgmres_relax(mg_hierarchy* h, int lv, const double* r0, double* x0, long lon
   return MG_OK;
 }
 
+// relaxation type 2: numit Vanka iterations of x in place on level l, from the operator the level already holds
+int vanka_relax(mg_hierarchy* h, int l, const double* b, double* x, long long numit) {
+  Level& L = h->lev[(size_t)l];
+  if (!L.vanka) return fail(MG_ERR_STATE, "level %d has no Vanka blocks (mg_set_vanka_FP64)", l + 1);
+  return vanka_run(L.vanka, L.A.rowptr.p, L.A.colidx.p, L.A.val.p, b, x, numit, L.vanka_type, h->play->stream);
+}
+
 // ---- the cycle ------------------------------------------------------------------------------------
 // Returns in *result the buffer (xa or xb) that holds the level's x after the cycle.
 // l is 0-based.  xa holds the incoming x when !x_zero; xb is the Jacobi ping-pong partner.
@@ -166,6 +173,10 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
   auto need = [&](const double* v, int want) { return gh ? gh_need(h, l, v, want) : (int)MG_OK; };
   // pre-smoothing (MGcycle.jl:26-31,54).  x == 0: r = b, so the first sweep is x = d.*b.
   if (pre_done) {
+    npre = 0;
+  } else if (h->relax_type == 2) {  // Vanka (MGcycle.jl:51-52): npre in-place iterations, none for a count of 0
+    if (x_zero) MG_TRY(k_fill(h, cur, len, 0.0));
+    MG_TRY(vanka_relax(h, l, b, cur, L.npre));
     npre = 0;
   } else if (h->relax_type == 1) {  // Jac-GMRES (MGcycle.jl:48-50): FGMRES on the residual, preconditioned by D
     const double* r0 = b;
@@ -334,7 +345,9 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
     MG_TRY(k_spmv(h, l, MG_K_PROLONG, L.P, 1.0, xc, 1.0, cur));
   }
   if (gh) setd(cur, std::min(dep(cur), gh_after_p));
-  if (h->relax_type == 1) {
+  if (h->relax_type == 2) {   // MGcycle.jl:99-100
+    MG_TRY(vanka_relax(h, l, b, cur, L.npost));
+  } else if (h->relax_type == 1) {
     MG_TRY(need(cur, 1));
     MG_TRY(need(b, 0));
     MG_TRY(need(Lr, 0));
@@ -348,7 +361,7 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
       std::swap(cur, alt);
     }
   }
-  if (defer_post && h->relax_type == 1) *defer_post = false;
+  if (defer_post && h->relax_type != 0) *defer_post = false;
   *result = cur;
   return MG_OK;
 }
@@ -372,6 +385,8 @@ int check_ready(mg_hierarchy* h, long long n, long long nrhs, bool sharded_ok = 
     return fail(MG_ERR_UNSUPPORTED, "this handle is one rank's part of a sharded hierarchy (mg_ghost_attach): mg_cycle_dev_FP64, mg_solve_dev_FP64 and the device Krylov drivers (mg_pcg_dev / mg_bicgstab_dev / mg_fgmres_dev and their block forms) run on it");
   if (h->ghost && !h->ghost->finalized) return fail(MG_ERR_STATE, "mg_ghost_finalize was not called");
   if (n != h->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->lev[0].n);
+  if (h->relax_type == 2 && (h->nrhs != 1 || h->cycle == 'K' || h->ghost))
+    return fail(MG_ERR_UNSUPPORTED, "Vanka relaxation (type 2): one right-hand side, V / W / F cycles, unsharded handles");
   if (nrhs != h->nrhs)
     return fail(MG_ERR_INVALID, "nrhs=%lld but the scratch is sized for %lld: call mg_set_nrhs (adjustMemoryForNumRHS)", nrhs, h->nrhs);
   return MG_OK;
@@ -394,7 +409,7 @@ void graphs_clear(mg_hierarchy* h) {
 // arguments on hierarchy-owned buffers - is captured once into a HIP graph and replayed.  Not for cycles with host
 // decisions inside (Jac-GMRES smoothing, K-cycles, GMRES coarsest solve) and not while profiling (events per launch).
 bool graph_ok(const mg_hierarchy* h, int l, char ctype) {
-  if (h->opt.no_graph || h->prof || h->capturing || h->relax_type == 1 || ctype == 'K' || h->coarse_gmres) return false;
+  if (h->opt.no_graph || h->prof || h->capturing || h->relax_type != 0 || ctype == 'K' || h->coarse_gmres) return false;
   // a caller's stream (mg_set_stream) may be the legacy null stream, which cannot capture, or be part of a capture of
   // the caller's own: only the hierarchy's own stream is captured, unless the caller vouches for its stream (dist tail)
   if (!h->play->stream || (!h->play->owns_stream && !h->opt.dist_tail_graph)) return false;

@@ -597,7 +597,11 @@ struct Csr {
   }
 };
 
+struct VankaCore;   // mg_vanka.inc: geometry, blocks and delta buffer of the Vanka smoother
+
 struct Level {
+  VankaCore* vanka = nullptr;   // relaxation type 2: bound by mg_set_vanka_FP64, released by mg_destroy
+  int vanka_type = 0;
   long long grid[3] = {0, 0, 0};  // optional hint: the rows are an x-fastest n1 x n2 x n3 nodal grid
   Csr A, P, R;  // P, R: transfer to/from the next coarser level (unset on the coarsest)
   DevBuf<double> d;
@@ -666,7 +670,7 @@ struct mg_hierarchy {
   long long nlevels = 0;
   long long nrhs = 1;
   char cycle = 'V';
-  int relax_type = 0;  // 0: pointwise d (Jac / SPAI, MGcycle.jl:122-136); 1: Jac-GMRES (FGMRES.jl:48-126)
+  int relax_type = 0;  // 0: pointwise d (Jac / SPAI, MGcycle.jl:122-136); 1: Jac-GMRES (FGMRES.jl:48-126); 2: Vanka (Vanka.jl:372-434)
   bool finalized = false;
   std::vector<Level> lev;
   DevBuf<double> Ainv;  // row-major n_c x n_c

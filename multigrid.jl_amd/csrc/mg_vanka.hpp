@@ -1,0 +1,136 @@
+// mg_vanka.hpp - kernels of the Vanka cell-block smoother (mg_vanka_*): the device form of the Julia serial path of
+// RelaxVankaFacesColor (src/Multigrid/Vanka.jl:383-425; `parallel = false`, l.10 - the red-black C path of Vanka.c never runs).
+// Per cell i with unknowns I (2*dim faces [+ its pressure], ascending): r = (b - A y)[I], x[I] += M_i r, where
+// M_i = reshape(D[:, i], bs, bs)' is the single-precision w*inv(A[I, I]) promoted to double.
+//
+// Lane mapping: eight lanes per cell, one lane per ROW of the cell (bs = 4..7 of them busy).  A lane walks its row's
+// products in stored order and keeps the sum to itself - no split of a row, so the residual is the serial sum.  The dense
+// bs x bs product is taken inside the group of eight: lane t reads M's row t (bs consecutive single-precision values of
+// the cell's block, promoted) and fetches r_j from lane j by shuffle, j = 0..bs-1 in order.  One lane per cell would keep
+// 4-7 rows of 5-13 entries serial in a lane and make every load of the block strided by bs*bs values; a group of eight
+// shares the cell's index arithmetic, reads the block as one contiguous run and keeps 4-7 of 8 lanes busy.
+//
+// Order independence: a colour's residuals read unknowns that other cells of the SAME colour own (the left-face row of cell
+// i1 reaches the right face of cell i1 - 2), so the colour is two launches: vanka_delta reads x only and writes M r into a
+// cells x bs buffer; vanka_apply_colour adds a colour's deltas into x (cells of a colour own disjoint unknowns: disjoint
+// writes).  The launch boundary is the reference's snapshot y = x.  FULL_VANKA_ADD: y is taken once per call, so the deltas of
+// ALL cells are formed once; each iteration is one per-unknown gather (vanka_apply_add) of at most two cells' deltas, the
+// lower cell first - the order the reference's linear walk adds them in.  No atomics; identical bits on every run.
+//
+// Cell and unknown indices are arithmetic on (dim, n, nf): nothing is uploaded but the operator and the blocks.
+// T = double or the interleaved complex d2_t (blocks: float or float2, applied conjugated - the stored block is the adjoint).
+#pragma once
+#include "mg_kernels.hpp"
+
+namespace mgk {
+
+struct VankaGeo {
+  int dim, ip, bs;          // ip: includePressure
+  int n[3];                 // cells per dimension (n[2] = 1 in 2-D)
+  int nf[3];                // faces per direction (nf[2] = 0 in 2-D)
+  int cells, N;             // prod(n), sum(nf) [+ cells]
+};
+
+template <typename T> struct VankaBlk;
+template <> struct VankaBlk<double> { typedef float type; };
+template <> struct VankaBlk<d2_t> { typedef float2 type; };
+
+__device__ __forceinline__ double vk_mul(double a, double b) { return a * b; }
+__device__ __forceinline__ d2_t vk_mul(d2_t a, d2_t b) { return d2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ double vk_adj(float a) { return (double)a; }                       // promoted, nothing rounded
+__device__ __forceinline__ d2_t vk_adj(float2 a) { return d2_t{(double)a.x, -(double)a.y}; }  // reshape(D)' conjugates
+__device__ __forceinline__ double vk_shfl8(double a, int j) { return __shfl(a, j, 8); }
+__device__ __forceinline__ d2_t vk_shfl8(d2_t a, int j) { return d2_t{__shfl(a.x, j, 8), __shfl(a.y, j, 8)}; }
+
+// unknown t of cell (c1, c2, c3), 0-based (getVankaVariablesOfCell, Vanka.jl:45-95)
+__device__ __forceinline__ int vanka_unknown(const VankaGeo& G, int c1, int c2, int c3, int t) {
+  const int n1 = G.n[0], n2 = G.n[1];
+  if (t < 2) return c1 + (n1 + 1) * (c2 + n2 * c3) + t;
+  if (t < 4) return G.nf[0] + c1 + n1 * (c2 + (n2 + 1) * c3) + (t == 3 ? n1 : 0);
+  const int cell = c1 + n1 * (c2 + n2 * c3);
+  if (G.dim == 3 && t < 6) return G.nf[0] + G.nf[1] + cell + (t == 5 ? n1 * n2 : 0);
+  return G.nf[0] + G.nf[1] + G.nf[2] + cell;   // the pressure
+}
+
+// delta[cell][t] = (M_cell (b - A x)[I])_t for the `count` cells of one colour (parity p[d] in dimension d, m[d] cells
+// of that parity per dimension), or for all cells (all != 0: m = n, p ignored).
+template <typename T>
+__global__ __launch_bounds__(BLK) void vanka_delta(VankaGeo G, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                   const T* __restrict__ val, const typename VankaBlk<T>::type* __restrict__ D,
+                                                   const T* __restrict__ b, const T* __restrict__ x, T* __restrict__ delta,
+                                                   int count, int m1, int m2, int p1, int p2, int p3, int all) {
+  const long long gid = (long long)blockIdx.x * BLK + threadIdx.x;
+  const int t = (int)(gid & 7);
+  const bool live = (gid >> 3) < count;   // (whole groups of eight: the shuffles below run with every lane of a live group)
+  int c1 = 0, c2 = 0, c3 = 0;
+  if (live) {
+    const int g = (int)(gid >> 3);        // < count: 32-bit divisions
+    const int k1 = g % m1, q = g / m1, k2 = q % m2, k3 = q / m2;
+    c1 = all ? k1 : 2 * k1 + p1;
+    c2 = all ? k2 : 2 * k2 + p2;
+    c3 = all ? k3 : 2 * k3 + p3;
+  }
+  const int cell = c1 + G.n[0] * (c2 + G.n[1] * c3);
+  T r = T{};
+  if (live && t < G.bs) {
+    const int row = vanka_unknown(G, c1, c2, c3, t);
+    T acc = T{};
+    for (int k = rowptr[row], e = rowptr[row + 1]; k < e; ++k) acc += vk_mul(val[k], x[col[k]]);   // stored order, one lane
+    r = b[row] - acc;
+  }
+  T out = T{};
+  const typename VankaBlk<T>::type* Mrow = D + (size_t)cell * (size_t)(G.bs * G.bs) + (size_t)(t < G.bs ? t : 0) * (size_t)G.bs;
+  for (int j = 0; j < G.bs; ++j) {
+    const T rj = vk_shfl8(r, j);
+    if (live && t < G.bs) out += vk_mul(vk_adj(Mrow[j]), rj);
+  }
+  if (live && t < G.bs) delta[(size_t)cell * (size_t)G.bs + (size_t)t] = out;
+}
+
+// x[I] += delta[cell] for the cells of one colour
+template <typename T>
+__global__ __launch_bounds__(BLK) void vanka_apply_colour(VankaGeo G, const T* __restrict__ delta, T* __restrict__ x, int count, int m1,
+                                                          int m2, int p1, int p2, int p3) {
+  const long long gid = (long long)blockIdx.x * BLK + threadIdx.x;
+  const int t = (int)(gid & 7);
+  if ((gid >> 3) >= count || t >= G.bs) return;
+  const int g = (int)(gid >> 3), q = g / m1;   // < count: 32-bit divisions
+  const int c1 = 2 * (g % m1) + p1, c2 = 2 * (q % m2) + p2, c3 = 2 * (q / m2) + p3;
+  const int cell = c1 + G.n[0] * (c2 + G.n[1] * c3);
+  const int u = vanka_unknown(G, c1, c2, c3, t);
+  x[u] = x[u] + delta[(size_t)cell * (size_t)G.bs + (size_t)t];
+}
+
+// FULL_VANKA_ADD: x[u] += delta of the lower cell that lists u, then of the upper one (a face has at most two)
+template <typename T>
+__global__ __launch_bounds__(BLK) void vanka_apply_add(VankaGeo G, const T* __restrict__ delta, T* __restrict__ x) {
+  const long long gid = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (gid >= G.N) return;   // (compared before narrowing: N may be within BLK of 2^31)
+  const int u = (int)gid;
+  const int n1 = G.n[0], n2 = G.n[1], n3 = G.n[2];
+  int lo = -1, hi = -1, tlo = 0, thi = 0;   // cells and the unknown's slot in each
+  if (u < G.nf[0]) {
+    const int f = u % (n1 + 1), rest = u / (n1 + 1);   // rest = c2 + n2 * c3
+    if (f >= 1) { lo = (f - 1) + n1 * rest; tlo = 1; }
+    if (f < n1) { hi = f + n1 * rest; thi = 0; }
+  } else if (u < G.nf[0] + G.nf[1]) {
+    const int v = u - G.nf[0];
+    const int c1 = v % n1, f = (v / n1) % (n2 + 1), c3 = v / (n1 * (n2 + 1));
+    if (f >= 1) { lo = c1 + n1 * ((f - 1) + n2 * c3); tlo = 3; }
+    if (f < n2) { hi = c1 + n1 * (f + n2 * c3); thi = 2; }
+  } else if (u < G.nf[0] + G.nf[1] + G.nf[2]) {
+    const int v = u - G.nf[0] - G.nf[1];
+    const int inplane = v % (n1 * n2), f = v / (n1 * n2);
+    if (f >= 1) { lo = inplane + n1 * n2 * (f - 1); tlo = 5; }
+    if (f < n3) { hi = inplane + n1 * n2 * f; thi = 4; }
+  } else {
+    lo = u - G.nf[0] - G.nf[1] - G.nf[2];
+    tlo = G.bs - 1;
+  }
+  T v = x[u];
+  if (lo >= 0) v = v + delta[(size_t)lo * (size_t)G.bs + (size_t)tlo];
+  if (hi >= 0) v = v + delta[(size_t)hi * (size_t)G.bs + (size_t)thi];
+  x[u] = v;
+}
+
+}  // namespace mgk

@@ -1,0 +1,299 @@
+// mg_vanka.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip; not compiled on its own).
+// The Vanka cell-block smoother of src/Multigrid/Vanka.jl on the device: the stand-alone handle (mg_vanka_*, extern "C"
+// below) and the per-level form the cycle runs as relaxation type 2 (VankaCore, bound by mg_set_vanka_FP64, mg_cabi.inc).
+// Kernels and the lane mapping: mg_vanka.hpp.
+namespace {
+
+constexpr int VANKA_FULL_RB = 1, VANKA_KACMARZ = 2, VANKA_ECON_RB = 3, VANKA_FULL_LEX = 4, VANKA_FULL_ADD = 5;   // Vanka.jl:13-17
+
+// Geometry, the cells' blocks and the delta buffer: everything of the smoother but the operator's CSR arrays
+struct VankaCore {
+  mgk::VankaGeo G{};
+  bool cx = false;
+  DevBuf<float> D;         // LocalBlocks: bs*bs single-precision values per cell (complex: interleaved pairs)
+  DevBuf<double> delta;    // cells x bs values of the operator's type
+  long long launches = 0;  // kernels enqueued so far
+  int colours_live = 0;    // colours that hold a cell (n[d] = 1 leaves the even parity of d empty)
+  void release() { D.release(); delta.release(); }
+};
+
+// (dim, n, includePressure) -> geometry; nrows must be sum(nf) [+ prod(n)] (getVankaBlockSize, Vanka.jl:211-222)
+int vanka_geometry(long long dim, const long long* n, long long includePressure, long long nrows, mgk::VankaGeo* G) {
+  if (dim != 2 && dim != 3) return fail(MG_ERR_INVALID, "dim=%lld: the face smoother serves 2-D and 3-D meshes", dim);
+  if (!n) return fail(MG_ERR_INVALID, "n is null");
+  if (includePressure != 0 && includePressure != 1) return fail(MG_ERR_INVALID, "includePressure must be 0 or 1");
+  long long nn[3] = {n[0], n[1], dim == 3 ? n[2] : 1};
+  for (int d = 0; d < 3; ++d)
+    if (nn[d] < 1 || nn[d] >= (1LL << 30)) return fail(MG_ERR_INVALID, "n[%d]=%lld", d + 1, nn[d]);
+  const long long cells = nn[0] * nn[1] * nn[2];
+  const long long nf[3] = {(nn[0] + 1) * nn[1] * nn[2], nn[0] * (nn[1] + 1) * nn[2], dim == 3 ? nn[0] * nn[1] * (nn[2] + 1) : 0};
+  const long long N = nf[0] + nf[1] + nf[2] + (includePressure ? cells : 0);
+  if (N >= (1LL << 31) - 1 || cells * 8 >= (1LL << 40)) return fail(MG_ERR_UNSUPPORTED, "the mesh exceeds int32 device indices");
+  if (nrows != N) return fail(MG_ERR_INVALID, "the operator has %lld rows, but a mesh of %lldx%lldx%lld cells has %lld unknowns (includePressure=%lld)", nrows, nn[0], nn[1], nn[2], N, includePressure);
+  G->dim = (int)dim;
+  G->ip = (int)includePressure;
+  G->bs = 2 * (int)dim + (int)includePressure;
+  for (int d = 0; d < 3; ++d) { G->n[d] = (int)nn[d]; G->nf[d] = (int)nf[d]; }
+  G->cells = (int)cells;
+  G->N = (int)N;
+  return MG_OK;
+}
+
+int vanka_type_served(long long type) {
+  if (type == VANKA_FULL_RB || type == VANKA_ECON_RB || type == VANKA_FULL_ADD) return MG_OK;
+  if (type == VANKA_FULL_LEX) return fail(MG_ERR_UNSUPPORTED, "FULL_VANKA_LEX is a sequential sweep over the cells: not served on the device");
+  if (type == VANKA_KACMARZ) return fail(MG_ERR_UNSUPPORTED, "KACMARZ_VANKA belongs to the hybrid cell-wise path: not served");
+  return fail(MG_ERR_UNSUPPORTED, "unknown Vanka type %lld", type);
+}
+
+// D_blocks: (bs*bs) x cells column-major, Float32 (cx: ComplexF32) - the caller's LocalBlocks as they are
+int vanka_core_init(VankaCore* V, bool cx, const mgk::VankaGeo& G, const void* D_blocks) {
+  if (!D_blocks) return fail(MG_ERR_INVALID, "D_blocks is null");
+  const size_t vw = cx ? 2 : 1;
+  V->G = G;
+  V->cx = cx;
+  V->colours_live = 1;
+  for (int d = 0; d < G.dim; ++d) V->colours_live *= G.n[d] >= 2 ? 2 : 1;
+  const size_t nD = vw * (size_t)G.bs * (size_t)G.bs * (size_t)G.cells;
+  MG_TRY(V->D.alloc(nD));
+  MG_TRY(V->delta.alloc(vw * (size_t)G.bs * (size_t)G.cells));
+  HIP_TRY(hipMemcpy(V->D.p, D_blocks, nD * sizeof(float), hipMemcpyHostToDevice));
+  return MG_OK;
+}
+
+// numit relaxations of x (in place) on `stream`, no synchronisation.  The caller has checked the type (vanka_type_served).
+template <typename T>
+int vanka_sweeps(VankaCore* V, const int* rowptr, const int* col, const T* val, const T* b, T* x, long long numit, int type,
+                 hipStream_t stream) {
+  typedef typename mgk::VankaBlk<T>::type B;
+  const mgk::VankaGeo& G = V->G;
+  const B* D = reinterpret_cast<const B*>(V->D.p);
+  T* delta = reinterpret_cast<T*>(V->delta.p);
+  if (numit <= 0) return MG_OK;   // numit = 0 does nothing (Vanka.jl:397,408), unlike relax
+  auto blocks = [](long long groups) { return dim3((unsigned)((groups * 8 + mgk::BLK - 1) / mgk::BLK)); };
+  if (type == VANKA_FULL_ADD) {
+    // y = copy(x) once per call (Vanka.jl:396): every iteration adds the same corrections
+    hipLaunchKernelGGL(mgk::vanka_delta<T>, blocks(G.cells), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, G.cells,
+                       G.n[0], G.n[1], 0, 0, 0, 1);
+    ++V->launches;
+    for (long long it = 0; it < numit; ++it) {
+      hipLaunchKernelGGL(mgk::vanka_apply_add<T>, dim3((unsigned)(((long long)G.N + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, stream, G,
+                         delta, x);
+      ++V->launches;
+    }
+    HIP_TRY(hipGetLastError());
+    return MG_OK;
+  }
+  const int ncol = 1 << G.dim;
+  for (long long it = 0; it < numit; ++it)
+    for (int c = 0; c < ncol; ++c) {
+      // cellColor (Vanka.jl:105-127): the first dimension's parity is the most significant bit; odd 1-based = even 0-based first
+      int p[3] = {0, 0, 0}, m[3] = {1, 1, 1};
+      for (int d = 0; d < G.dim; ++d) {
+        p[d] = (c >> (G.dim - 1 - d)) & 1;
+        m[d] = (G.n[d] + 1 - p[d]) / 2;
+      }
+      const long long count = (long long)m[0] * m[1] * m[2];
+      if (count == 0) continue;
+      hipLaunchKernelGGL(mgk::vanka_delta<T>, blocks(count), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, (int)count,
+                         m[0], m[1], p[0], p[1], p[2], 0);
+      hipLaunchKernelGGL(mgk::vanka_apply_colour<T>, blocks(count), dim3(mgk::BLK), 0, stream, G, delta, x, (int)count, m[0], m[1], p[0],
+                         p[1], p[2]);
+      V->launches += 2;
+    }
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+int vanka_run(VankaCore* V, const int* rowptr, const int* col, const double* val, const double* b, double* x, long long numit, int type,
+              hipStream_t stream) {
+  if (V->cx)
+    return vanka_sweeps<mgk::d2_t>(V, rowptr, col, reinterpret_cast<const mgk::d2_t*>(val), reinterpret_cast<const mgk::d2_t*>(b),
+                                   reinterpret_cast<mgk::d2_t*>(x), numit, type, stream);
+  return vanka_sweeps<double>(V, rowptr, col, val, b, x, numit, type, stream);
+}
+
+}  // namespace
+
+struct mg_vanka {
+  int device = 0;
+  long long n = 0, nnz = 0;
+  VankaCore core;
+  DevBuf<int> rowptr, col;
+  DevBuf<double> val, stage_x, stage_b;
+  hipStream_t stream = nullptr;
+};
+
+namespace {
+
+int vanka_create(bool cx, long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
+                 const long long* rowptr, const long long* colA, const double* valA, const void* D_blocks, mg_vanka** out) {
+  const size_t vw = cx ? 2 : 1;
+  if (!out) return fail(MG_ERR_INVALID, "out is null");
+  *out = nullptr;
+  if (nrows < 1 || !rowptr || !colA || !valA || !D_blocks) return fail(MG_ERR_INVALID, "null or empty argument");
+  mgk::VankaGeo G;
+  MG_TRY(vanka_geometry(dim, n, includePressure, nrows, &G));
+  if (rowptr[0] != 1) return fail(MG_ERR_INVALID, "rowptr[1] must be 1 (1-based Julia arrays expected)");
+  const long long nnz = rowptr[nrows] - 1;
+  if (nnz < 0 || nnz >= (1LL << 31) - 1) return fail(MG_ERR_UNSUPPORTED, "nnz does not fit int32");
+  std::vector<int> rp((size_t)nrows + 1), ci((size_t)std::max<long long>(nnz, 1));
+  for (long long i = 0; i <= nrows; ++i) {
+    const long long v = rowptr[i] - 1;
+    if (v < 0 || v > nnz || (i > 0 && v < rp[(size_t)i - 1])) return fail(MG_ERR_INVALID, "rowptr is not a monotone 1-based pointer array");
+    rp[(size_t)i] = (int)v;
+  }
+  for (long long k = 0; k < nnz; ++k) {
+    const long long c = colA[k] - 1;
+    if (c < 0 || c >= nrows) return fail(MG_ERR_INVALID, "column index out of range");
+    ci[(size_t)k] = (int)c;
+  }
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the Vanka smoother has no CPU fallback");
+  if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
+  HIP_TRY(hipSetDevice((int)device_id));
+  mg_vanka* v = new mg_vanka();
+  v->device = (int)device_id;
+  v->n = nrows;
+  v->nnz = nnz;
+  auto up = [&]() -> int {
+    MG_TRY(v->rowptr.alloc(rp.size()));
+    MG_TRY(v->col.alloc(ci.size()));
+    MG_TRY(v->val.alloc(vw * (size_t)std::max<long long>(nnz, 1)));
+    HIP_TRY(hipMemcpy(v->rowptr.p, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v->col.p, ci.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v->val.p, valA, vw * (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+    MG_TRY(vanka_core_init(&v->core, cx, G, D_blocks));
+    HIP_TRY(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+    return MG_OK;
+  };
+  const int rc = up();
+  (void)hipDeviceSynchronize();   // the blocking copies above ran on the NULL stream; the kernels run on the handle's own
+  if (rc != MG_OK) {
+    mg_vanka_destroy(v);
+    return rc;
+  }
+  *out = v;
+  return MG_OK;
+}
+
+// The arguments of an apply and the handle's value type (cx: the entry point's)
+int vanka_args(bool cx, mg_vanka* v, const double* x, const double* b, long long numit, long long type, const char* name) {
+  if (!v) return fail(MG_ERR_INVALID, "null handle");
+  if (v->core.cx != cx)
+    return fail(MG_ERR_STATE, "%s on a handle of %s values (%s)", name, v->core.cx ? "ComplexF64" : "Float64",
+                v->core.cx ? "mg_vanka_apply*_CFP64" : "mg_vanka_apply*_FP64");
+  if (!x || !b || x == b || numit < 0) return fail(MG_ERR_INVALID, "bad argument (x and b must be two vectors, numit >= 0)");
+  MG_TRY(vanka_type_served(type));
+  (void)hipSetDevice(v->device);
+  return MG_OK;
+}
+
+int vanka_apply_dev(bool cx, mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long type, const char* name) {
+  MG_TRY(vanka_args(cx, v, x_dev, b_dev, numit, type, name));
+  MG_TRY(vanka_run(&v->core, v->rowptr.p, v->col.p, v->val.p, b_dev, x_dev, numit, (int)type, v->stream));
+  HIP_TRY(spin_sync(v->stream));
+  return MG_OK;
+}
+
+int vanka_apply_host(bool cx, mg_vanka* v, double* x, const double* b, long long numit, long long type, const char* name) {
+  MG_TRY(vanka_args(cx, v, x, b, numit, type, name));
+  if (numit == 0) return MG_OK;
+  const size_t len = (cx ? 2 : 1) * (size_t)v->n;   // doubles
+  if (v->stage_x.n != len) {
+    MG_TRY(v->stage_x.alloc(len));
+    MG_TRY(v->stage_b.alloc(len));
+  }
+  HIP_TRY(hipMemcpyAsync(v->stage_x.p, x, len * sizeof(double), hipMemcpyHostToDevice, v->stream));
+  HIP_TRY(hipMemcpyAsync(v->stage_b.p, b, len * sizeof(double), hipMemcpyHostToDevice, v->stream));
+  MG_TRY(vanka_run(&v->core, v->rowptr.p, v->col.p, v->val.p, v->stage_b.p, v->stage_x.p, numit, (int)type, v->stream));
+  HIP_TRY(hipMemcpyAsync(x, v->stage_x.p, len * sizeof(double), hipMemcpyDeviceToHost, v->stream));
+  HIP_TRY(spin_sync(v->stream));
+  return MG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// rowptr / colA / valA: CSR of the applied operator A (1-based Int64; valA the values of A's rows - the reference's
+// conj(AT.nzval), computeResidualAtIdx, Vanka.jl:192-198).  n[dim]: cells of the RegularMesh.  D_blocks: LocalBlocks of
+// setupVankaFacesPreconditioner (Vanka.jl:294-370), (bs*bs) x prod(n) column-major Float32 (CFP64: ComplexF32).
+int mg_vanka_create_FP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
+                               const long long* rowptr, const long long* colA, const double* valA, const float* D_blocks, mg_vanka** out) {
+  return vanka_create(false, device_id, dim, n, includePressure, nrows, rowptr, colA, valA, D_blocks, out);
+}
+int mg_vanka_create_CFP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
+                                const long long* rowptr, const long long* colA, const double* valA, const float* D_blocks, mg_vanka** out) {
+  return vanka_create(true, device_id, dim, n, includePressure, nrows, rowptr, colA, valA, D_blocks, out);
+}
+
+int mg_vanka_apply_FP64(mg_vanka* v, double* x, const double* b, long long numit, long long VankaType) {
+  return vanka_apply_host(false, v, x, b, numit, VankaType, "mg_vanka_apply_FP64");
+}
+int mg_vanka_apply_CFP64(mg_vanka* v, double* x, const double* b, long long numit, long long VankaType) {
+  return vanka_apply_host(true, v, x, b, numit, VankaType, "mg_vanka_apply_CFP64");
+}
+int mg_vanka_apply_dev_FP64(mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long VankaType) {
+  return vanka_apply_dev(false, v, x_dev, b_dev, numit, VankaType, "mg_vanka_apply_dev_FP64");
+}
+int mg_vanka_apply_dev_CFP64(mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long VankaType) {
+  return vanka_apply_dev(true, v, x_dev, b_dev, numit, VankaType, "mg_vanka_apply_dev_CFP64");
+}
+
+// info[0..8): value type (0 Float64, 1 ComplexF64); blockSize; cells; colours (2^dim); kernel launches of one
+// FULL_VANKA_RB / ECON_VANKA_RB iteration (two per colour that holds a cell); of one FULL_VANKA_ADD iteration (one, plus one
+// per call for the deltas); unknowns; kernels this handle has enqueued so far
+int mg_vanka_info(mg_vanka* v, long long* info) {
+  if (!v || !info) return fail(MG_ERR_INVALID, "null argument");
+  info[0] = v->core.cx ? 1 : 0;
+  info[1] = v->core.G.bs;
+  info[2] = v->core.G.cells;
+  info[3] = 1LL << v->core.G.dim;
+  info[4] = 2LL * v->core.colours_live;
+  info[5] = 1;
+  info[6] = v->core.G.N;
+  info[7] = v->core.launches;
+  return MG_OK;
+}
+
+// Measurement: device time of one iteration on device vectors, as mg_dd_time_dev measures a sweep - `warmup` untimed
+// iterations, then `reps`, each between two events on the handle's stream; ms[0..reps) in milliseconds.  x is relaxed in place.
+int mg_vanka_time_dev(mg_vanka* v, double* x_dev, const double* b_dev, long long VankaType, long long warmup, long long reps, double* ms) {
+  if (!v || !ms || reps < 1 || warmup < 0) return fail(MG_ERR_INVALID, "bad argument");
+  MG_TRY(vanka_args(v->core.cx, v, x_dev, b_dev, 1, VankaType, "mg_vanka_time_dev"));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = MG_OK;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventCreate failed");
+  for (long long it = 0; it < warmup + reps && rc == MG_OK; ++it) {
+    if (hipEventRecord(e0, v->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
+    if (rc == MG_OK) rc = vanka_run(&v->core, v->rowptr.p, v->col.p, v->val.p, b_dev, x_dev, 1, (int)VankaType, v->stream);
+    if (rc == MG_OK) {
+      float t = 0.f;
+      if (hipEventRecord(e1, v->stream) != hipSuccess || spin_sync(v->stream) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)
+        rc = fail(MG_ERR_HIP, "event timing failed");
+      if (it >= warmup) ms[it - warmup] = (double)t;
+    }
+  }
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
+}
+
+int mg_vanka_destroy(mg_vanka* v) {
+  if (!v) return MG_OK;
+  (void)hipSetDevice(v->device);
+  if (v->stream) {
+    (void)spin_sync(v->stream);
+    (void)hipStreamDestroy(v->stream);
+  }
+  v->core.release();
+  v->rowptr.release();
+  v->col.release();
+  for (DevBuf<double>* b : {&v->val, &v->stage_x, &v->stage_b}) b->release();
+  delete v;
+  return MG_OK;
+}
+
+}  // extern "C"

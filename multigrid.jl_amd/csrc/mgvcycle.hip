@@ -35,6 +35,7 @@
 #include "mg_complex.hpp"
 #include "mg_krvec.hpp"
 #include "mg_dd.hpp"
+#include "mg_vanka.hpp"
 
 
 // One translation unit in parts (the 6 800-line file split by responsibility; the order is the dependency order):
@@ -42,6 +43,7 @@
 #include "mg_launch.inc"     // byte accounting, profiling slots, kernel launchers
 #include "mg_transport.inc"  // RCCL loader, host-staged plug-in: the collectives of both sharded forms
 #include "mg_ghost.inc"      // ghost-layer form of the sharded cycle: exchange, validity bookkeeping, global norms
+#include "mg_vanka.inc"      // the Vanka cell-block smoother: per-level core of relaxation type 2, extern "C" mg_vanka_*
 #include "mg_schedule.inc"   // FGMRES relaxation, cycle_level, HIP graphs, solve loop
 #include "mg_krylov.inc"     // PCG / BiCGSTAB / FGMRES and block variants
 #include "mg_formats.inc"    // upload, format builders, scratch

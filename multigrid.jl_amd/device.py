@@ -145,6 +145,16 @@ SIGNATURES = {
     "mg_kaczmarz_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_kaczmarz_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
     "mg_kaczmarz_destroy": (C.c_int, [_vp]),
+    "mg_set_vanka_FP64": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, C.POINTER(C.c_float)]),
+    "mg_vanka_create_FP64_INT64": (C.c_int, [_ll, _ll, _lp, _ll, _ll, _lp, _lp, _dp, C.POINTER(C.c_float), C.POINTER(_vp)]),
+    "mg_vanka_create_CFP64_INT64": (C.c_int, [_ll, _ll, _lp, _ll, _ll, _lp, _lp, _dp, C.POINTER(C.c_float), C.POINTER(_vp)]),
+    "mg_vanka_apply_FP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll]),
+    "mg_vanka_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_vanka_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll]),
+    "mg_vanka_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_vanka_info": (C.c_int, [_vp, _lp]),
+    "mg_vanka_time_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _dp]),
+    "mg_vanka_destroy": (C.c_int, [_vp]),
     "mg_dist_unique_id": (C.c_int, [C.c_char_p]),
     "mg_dist_create": (C.c_int, [_ll, _ll, _ll, C.c_char_p, _ll, _ll, _ll, C.POINTER(_vp)]),
     "mg_dist_set_exchange_plugin": (C.c_int, [_vp, _vp, _vp]),
@@ -268,6 +278,30 @@ def _sync_torch(*tensors):
 DENSE_COARSE_MAX = 16384
 
 
+def _relax_type_code(param) -> int:
+    """mg_set_relax_type: 0 pointwise (Jac / SPAI), 1 Jac-GMRES, 2 the Vanka smoothers."""
+    from .vanka import getVankaRelaxType
+    if getVankaRelaxType(param.relaxType)[0]:
+        return 2
+    return 1 if param.relaxType == "Jac-GMRES" else 0
+
+
+def _vanka_guard(param, nrhs: int):
+    """What a Vanka hierarchy does not serve, refused before the device is touched."""
+    from .vanka import getVankaRelaxType, FULL_VANKA_LEX
+    isVanka, vtype = getVankaRelaxType(param.relaxType)
+    if not isVanka:
+        return
+    if vtype == FULL_VANKA_LEX:
+        raise NotImplementedError("FULL_VANKA_LEX is a sequential sweep over the cells; the package keeps no CPU fallback")
+    if int(nrhs) != 1:
+        raise NotImplementedError("Vanka hierarchies serve one right-hand side (blocks of right-hand sides are out of scope)")
+    if param.cycleType == "K":
+        raise NotImplementedError("Vanka hierarchies serve the V, W and F cycles (cycleType='K' is out of scope)")
+    if param.transferOperatorType not in ("SystemsFacesLinear", "SystemsFacesMixedLinear") or not param.Meshes:
+        raise NotImplementedError("Vanka hierarchies need the staggered meshes of MGsetup with a Systems transfer operator")
+
+
 class DeviceHierarchy:
     """Owns one ``mg_hierarchy`` handle (HBM copy of As/Ps/Rs/relaxPrecs + coarse inverse).
 
@@ -302,25 +336,41 @@ class DeviceHierarchy:
                                                  _i64(colptr), _i64(rowval), _f64(nzval))
         _check(self.lib, rc, f"mg_set_operator(level={level}, which={which})")
 
+    def _set_relax_level(self, param, l, pre, post):
+        """relaxPrecs[l]: the pointwise vector, or (Vanka) the cells' blocks - then the pointwise slot holds zeros, which
+        nothing reads, and carries the sweep counts."""
+        lib = self.lib
+        if self._vanka:
+            from .vanka import getVankaRelaxType
+            blk = np.asfortranarray(param.relaxPrecs[l - 1], dtype=np.float32)
+            nn = np.ascontiguousarray(param.Meshes[l - 1].n, dtype=np.int64)
+            mixed = param.transferOperatorType == "SystemsFacesMixedLinear"
+            _check(lib, lib.mg_set_vanka_FP64(self.handle, l, nn.size, _i64(nn), 1 if mixed else 0,
+                                              getVankaRelaxType(param.relaxType)[1], blk.ctypes.data_as(C.POINTER(C.c_float))),
+                   f"mg_set_vanka(level={l})")
+            d = np.zeros(param.As[l - 1].shape[0], dtype=np.float64)
+        else:
+            d = np.ascontiguousarray(param.relaxPrecs[l - 1], dtype=np.float64)
+        _check(lib, lib.mg_set_relax_FP64(self.handle, l, _f64(d), d.size, int(pre), int(post)), f"mg_set_relax(level={l})")
+
     def _upload(self, param):
         lib = self.lib
         nl = self.nlevels
+        _vanka_guard(param, self.nrhs)
+        self._vanka = _relax_type_code(param) == 2
         for l in range(1, nl + 1):
             self._set_op(l, MG_OP_A, param.As[l - 1])
             if l < nl:
                 self._set_op(l, MG_OP_P, param.Ps[l - 1])
                 self._set_op(l, MG_OP_R, param.Rs[l - 1])
-                d = np.ascontiguousarray(param.relaxPrecs[l - 1], dtype=np.float64)
-                _check(lib, lib.mg_set_relax_FP64(self.handle, l, _f64(d), d.size,
-                                                  int(param.relaxPre(l)), int(param.relaxPost(l))),
-                       f"mg_set_relax(level={l})")
+                self._set_relax_level(param, l, param.relaxPre(l), param.relaxPost(l))
         # performance hint only: GMG levels are regular nodal grids (param.Meshes, MGsetup.jl:54)
         for l, mesh in enumerate(getattr(param, "Meshes", []) or []):
             if l < nl and mesh is not None:
                 nn = [int(k) + 1 for k in mesh.n] + [1]
-                if int(np.prod(nn)) == param.As[l].shape[0]:
+                if int(np.prod(nn)) == param.As[l].shape[0] and not self._vanka:
                     _check(lib, lib.mg_set_grid_hint(self.handle, l + 1, nn[0], nn[1], nn[2]), "mg_set_grid_hint")
-        _check(lib, lib.mg_set_relax_type(self.handle, 1 if param.relaxType == "Jac-GMRES" else 0), "mg_set_relax_type")
+        _check(lib, lib.mg_set_relax_type(self.handle, _relax_type_code(param)), "mg_set_relax_type")
         _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
         if param.LU is None:
             raise MGDeviceError("param.LU is empty: run MGsetup / SA_AMGsetup first")
@@ -342,14 +392,16 @@ class DeviceHierarchy:
         lib = self.lib
         old = self._schedule
         refinalize = False
+        _vanka_guard(param, self.nrhs)
+        if (_relax_type_code(param) == 2) != self._vanka or (self._vanka and sig[1] != old[1]):
+            raise NotImplementedError("relaxType changed to or from a Vanka smoother after the setup: relaxPrecs hold the other "
+                                      "smoother's data - run MGsetup again")
         if sig[1] != old[1]:
-            _check(lib, lib.mg_set_relax_type(self.handle, 1 if param.relaxType == "Jac-GMRES" else 0), "mg_set_relax_type")
+            _check(lib, lib.mg_set_relax_type(self.handle, _relax_type_code(param)), "mg_set_relax_type")
             refinalize = True
         if sig[2] != old[2] or sig[3] != old[3]:
             for l in range(1, self.nlevels):
-                d = np.ascontiguousarray(param.relaxPrecs[l - 1], dtype=np.float64)
-                _check(lib, lib.mg_set_relax_FP64(self.handle, l, _f64(d), d.size, sig[2][l - 1], sig[3][l - 1]),
-                       f"mg_set_relax(level={l})")
+                self._set_relax_level(param, l, sig[2][l - 1], sig[3][l - 1])
             refinalize = True
         if sig[0] != old[0]:
             _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
@@ -386,6 +438,8 @@ class DeviceHierarchy:
                                                     _f64(Uv), _i64(p), _i64(q)), "mg_set_coarse_lu")
 
     def set_nrhs(self, nrhs: int):
+        if getattr(self, "_vanka", False) and int(nrhs) != 1:
+            raise NotImplementedError("Vanka hierarchies serve one right-hand side (blocks of right-hand sides are out of scope)")
         _check(self.lib, self.lib.mg_set_nrhs(self.handle, int(nrhs)), "mg_set_nrhs")
         self.nrhs = int(nrhs)
 
@@ -799,6 +853,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     def _upload(self, param):
         lib = self.lib
         nl = self.nlevels
+        if _relax_type_code(param) == 2:
+            raise NotImplementedError("ComplexF64 hierarchies: the Vanka smoothers serve VAL=Float64 hierarchies (complex operators: "
+                                      "the stand-alone RelaxVankaFacesColor)")
         if param.cycleType == "K" or param.relaxType == "Jac-GMRES":
             raise NotImplementedError("ComplexF64 hierarchies: cycles V, W, F with the Jac / SPAI smoothers")
         for l in range(1, nl + 1):

@@ -514,6 +514,9 @@ class DistributedHierarchy:
             raise NotImplementedError("ComplexF64 hierarchies run on one GPU: the multi-GPU cycle serves VAL=Float64")
         relax_ok = ("Jac", "SPAI", "Jac-GMRES") if native else ("Jac", "SPAI")
         cycle_ok = ("V", "W", "F", "K") if native else ("V", "W", "F")
+        from .vanka import getVankaRelaxType
+        if getVankaRelaxType(param.relaxType)[0]:
+            raise NotImplementedError("the Vanka smoothers run on one GPU: the multi-GPU cycle serves the pointwise smoothers")
         if param.relaxType not in relax_ok:
             raise NotImplementedError(f"relaxType={param.relaxType!r} is not implemented in the multi-GPU cycle"
                                       + ("" if native else " of the Python sequencer (the native one, mg_dist_*, has Jac-GMRES)"))

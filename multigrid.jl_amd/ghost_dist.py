@@ -220,6 +220,9 @@ def ghost_gmg(global_cells, numDomains, rank: int, size: int, param: MGparam, op
     from .structured_setup import setup_on_margin_box
     if np.dtype(getattr(param, "VAL", np.float64)) == np.complex128:
         raise NotImplementedError("ComplexF64 hierarchies run on one GPU: the ghost-layer form serves VAL=Float64")
+    from .vanka import getVankaRelaxType
+    if getVankaRelaxType(param.relaxType)[0]:
+        raise NotImplementedError("the Vanka smoothers run on one GPU: the ghost-layer form serves the pointwise smoothers")
     if param.relaxType not in ("Jac", "SPAI", "Jac-GMRES") or param.cycleType not in ("V", "W", "F", "K"):
         raise NotImplementedError(f"the ghost-layer form does not know relaxType {param.relaxType!r} / cycleType {param.cycleType!r}")
     S = setup_on_margin_box(global_cells, numDomains, rank, size, param, operator, domain, replicate_below)

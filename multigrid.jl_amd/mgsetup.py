@@ -61,12 +61,21 @@ def getSPAIprec(A):
     return A.diagonal() / s
 
 
-def getRelaxPrec(A, relaxType: str, relaxParam=1.0):
-    """Jac: d = omega/diag (MGsetup.jl:145-147).  SPAI: d = omega*diag/colnorm^2 (l.148-149).
+def getRelaxPrec(A, relaxType: str, relaxParam=1.0, Mesh_l=None, withCellsBlock: bool = False):
+    """Jac: d = omega/diag (MGsetup.jl:145-147).  SPAI: d = omega*diag/colnorm^2 (l.148-149).  The Vanka types: the cells'
+    blocks of setupVankaFacesPreconditioner on the level's mesh (l.153-154; relaxParam a float or a tuple of two).
 
     Complex A (the applied operator, = the reference's AT^H): the reference's d = conj(relaxParam ./ diag(AT)) and
     conj(relaxParam*getSPAIprec(AT)) become d = omega/diag(A) and d = omega*conj(diag(A))/colsumsq|A| - for a real A both
     are the formulas above."""
+    from .vanka import getVankaRelaxType, setupVankaFacesPreconditioner
+    isVanka, VankaType = getVankaRelaxType(relaxType)
+    if isVanka:
+        if Mesh_l is None:
+            raise ValueError(f"relaxType={relaxType!r} needs the level's mesh (getRelaxPrec(A, relaxType, relaxParam, Mesh_l, withCellsBlock))")
+        return setupVankaFacesPreconditioner(A, Mesh_l, relaxParam, withCellsBlock, VankaType)
+    if relaxType == "hybridVankaFacesKaczmarz":
+        raise NotImplementedError("RelaxHybridVanka / getHybridVankaFaces are out of scope (the cycle's call is commented out in the reference)")
     if np.iscomplexobj(A.data if sp.issparse(A) else A):
         A = _as_csr(A)
         if relaxType in ("Jac", "Jac-GMRES"):
@@ -81,7 +90,16 @@ def getRelaxPrec(A, relaxType: str, relaxParam=1.0):
     raise ValueError("Unknown relaxation type !!!!")
 
 
+def _is_vanka(param: MGparam) -> bool:
+    from .vanka import getVankaRelaxType
+    return getVankaRelaxType(param.relaxType)[0]
+
+
 def _relax_param_arr(param: MGparam):
+    rp = param.relaxParam
+    if _is_vanka(param) and isinstance(rp, tuple) and len(rp) == 2 and all(np.isscalar(w) for w in rp):
+        return [rp] * param.levels      # one (w1, w2) pair, not an Array: copied to every level (MGsetup.jl:15-19)
+    # (any other sequence holds one entry per level, each a float or a (w1, w2) pair)
     if isinstance(param.relaxParam, (list, tuple, np.ndarray)):
         return list(param.relaxParam)
     return [param.relaxParam] * param.levels
@@ -147,8 +165,14 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
     ``ATf`` is either the fine operator A (any scipy sparse; held as CSR = the reference's transposed CSC)
     or a ``multilevelOperatorConstructor`` (rediscretisation; then ``geometric=True``, l.53).
     """
-    if param.transferOperatorType != "FullWeighting":
-        raise NotImplementedError("only transferOperatorType='FullWeighting' (Systems.jl operators are out of scope)")
+    systems = param.transferOperatorType in ("SystemsFacesLinear", "SystemsFacesMixedLinear")
+    withCellsBlock = param.transferOperatorType == "SystemsFacesMixedLinear"
+    if param.transferOperatorType != "FullWeighting" and not systems:
+        raise NotImplementedError("transferOperatorType is 'FullWeighting', 'SystemsFacesLinear' or 'SystemsFacesMixedLinear'")
+    if param.coarseSolveType == "VankaFaces":
+        raise NotImplementedError("coarseSolveType='VankaFaces' calls functions that are commented out in the reference")
+    if _is_vanka(param) and is_complex(param):
+        raise NotImplementedError("Vanka hierarchies serve VAL=Float64 (the stand-alone RelaxVankaFacesColor takes complex operators)")
     _release_device(param)
     levels = param.levels
     relaxParamArr = _relax_param_arr(param)
@@ -159,6 +183,13 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
         PDEparam = ATf.param
     else:
         As = [_of_val(param, ATf)]
+    if systems:
+        from .vanka import getVankaBlockSize
+        N = int(getVankaBlockSize(Mesh.n, withCellsBlock)[1].sum()) + (int(np.prod(Mesh.n)) if withCellsBlock else 0)
+        if As[0].shape[0] != N:
+            raise NotImplementedError(f"transferOperatorType={param.transferOperatorType!r} serves staggered-grid operators: a mesh of "
+                                      f"{list(map(int, Mesh.n))} cells has {N} face{' and cell' if withCellsBlock else ''} unknowns, "
+                                      f"the operator has {As[0].shape[0]} rows")
     from .operators import getRegularMesh
     Meshes = [Mesh]
     Ps, Rs, relaxPrecs = [], [], []
@@ -167,11 +198,16 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
     for l in range(1, levels):                      # l is the reference's 1-based level
         t0 = time.perf_counter()
         A = As[l - 1]
-        P, nc_nodes = getFWInterp(n + 1, geometric)
-        nc = nc_nodes - 1
-        R = (P.T * (0.5 ** Meshes[l - 1].dim)).tocsr()      # RT = P*0.5^dim always (MGsetup.jl:56-60)
+        if systems:                                         # MGsetup.jl:63-73
+            from .systems import getLinearOperatorsSystemsFaces
+            P, R, nc = getLinearOperatorsSystemsFaces(n, withCellsBlock)
+            R = (R * (0.5 ** Meshes[l - 1].dim)).tocsr()
+        else:
+            P, nc_nodes = getFWInterp(n + 1, geometric)
+            nc = nc_nodes - 1
+            R = (P.T * (0.5 ** Meshes[l - 1].dim)).tocsr()      # RT = P*0.5^dim always (MGsetup.jl:56-60)
         R.sort_indices()
-        relaxPrecs.append(getRelaxPrec(A, param.relaxType, relaxParamArr[l - 1]))
+        relaxPrecs.append(getRelaxPrec(A, param.relaxType, relaxParamArr[l - 1], Meshes[l - 1], withCellsBlock))
         if P.shape[0] == P.shape[1]:
             if verbose:
                 print(f"Stopped Coarsening at level {l}")
@@ -240,7 +276,9 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
     param.As[0] = A
     for l in range(1, param.levels):
         Al = param.As[l - 1]
-        param.relaxPrecs[l - 1] = getRelaxPrec(Al, param.relaxType, relaxParamArr[l - 1])
+        Mesh_l = param.Meshes[l - 1] if param.Meshes else None      # MGsetup.jl:247-252
+        param.relaxPrecs[l - 1] = getRelaxPrec(Al, param.relaxType, relaxParamArr[l - 1], Mesh_l,
+                                               param.transferOperatorType == "SystemsFacesMixedLinear")
         param.As[l] = galerkin(param.Rs[l - 1], Al, param.Ps[l - 1])
     defineCoarsestAinv(param, param.As[-1])
     param.doTranspose = 0
@@ -251,6 +289,8 @@ def transposeHierarchy(param: MGparam, verbose: bool = False) -> None:
     """Transpose every operator, swap P<->R roles (MGsetup.jl:274-318).  Real VAL: conj is a no-op."""
     if is_complex(param):
         raise NotImplementedError("transposeHierarchy of a ComplexF64 hierarchy (the device transpose serves FP64 handles)")
+    if _is_vanka(param):
+        raise NotImplementedError("transposeHierarchy of a Vanka hierarchy (the reference refuses it too: MGsetup.jl:288-292)")
     if param.relaxType not in ("Jac", "Jac-GMRES", "SPAI"):
         raise RuntimeError("Not supported")
     param.As[0] = _as_csr(param.As[0].T)

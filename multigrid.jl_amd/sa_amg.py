@@ -81,6 +81,9 @@ def SA_AMGsetup(A, param: MGparam, symm: bool = True, nrhs: int = 1, verbose: bo
     """Build the SA-AMG hierarchy (SA-AMG.jl:8-76)."""
     if not symm:
         raise RuntimeError("not supported yet...")
+    from .vanka import getVankaRelaxType
+    if getVankaRelaxType(param.relaxType)[0]:
+        raise NotImplementedError("the Vanka smoothers need the staggered mesh of every level: SA-AMG hierarchies have none")
     if param.relaxType not in ("Jac", "Jac-GMRES", "SPAI"):
         raise ValueError("Unknown relaxation type !!!!")
     _release_device(param)

@@ -27,6 +27,8 @@ def to_device(param: MGparam, device_id: int = 0) -> DeviceHierarchy:
     """Upload the hierarchy (lifecycle hook at the end of MGsetup/SA_AMGsetup, MGsetup.jl:135-137)."""
     if not hierarchyExists(param):
         raise RuntimeError("The Hierarchy is empty - run a setup first.")
+    from .device import _vanka_guard
+    _vanka_guard(param, max(1, param.nrhs))       # what a Vanka hierarchy does not serve: refused before the device is touched
     if param.device is None:
         param.device = DeviceHierarchy(param, device_id=device_id, nrhs=max(1, param.nrhs))
     else:
