@@ -774,8 +774,8 @@ int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count);
  *   called with a CF64 handle fails with MG_ERR_STATE, and every CF64 entry point called with an FP64 handle fails with
  *   MG_ERR_STATE too; nothing is changed.
  * Refused with MG_ERR_UNSUPPORTED (and a mg_last_error message): cycle 'K', relaxType 1 (Jac-GMRES), the GMRES coarse solve
- *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries), the Krylov drivers
- *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*), mg_rap_FP64, mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
+ *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries), the _FP64 Krylov drivers
+ *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64, mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
  *   mg_ghost_* call and mg_dist_set_tail_INT64 with a CF64 tail (the mg_dist_* handles are FP64 by construction).
  * Formats.  Generic CSR only, one streaming kernel (int32 row pointers; 64-bit beyond 2^31 - 4096 non-zeros or with the option
  *   "force_rowptr64"); the row-class, band, tile, march and small-level formats are real-valued and not used.  No HIP graphs. */
@@ -798,6 +798,62 @@ int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long
 /* target = beta*target + alpha*Op*x on one level; alpha and beta are complex, each a (re, im) pair. */
 int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* x,
                  const double* beta, double* y, long long nrhs);
+
+/* ---- ComplexF64 Krylov drivers on a CF64 handle (suffix CFP64, the reference's own) ---------------------------------------
+ * solveBiCGSTAB_MG / solveGMRES_MG (SolveFuncs.jl:85-133) for VAL = ComplexF64: KrylovMethods.bicgstb / fgmres with one cycle
+ * of the handle's hierarchy from x = 0 as preconditioner, every vector resident in HBM across iterations.  The way Helmholtz
+ * problems are solved: the Krylov method runs on the (nearly) undamped operator - the handle's KRYLOV OPERATOR - and the
+ * hierarchy is built on a damped (shifted) copy of it.
+ *
+ * mg_set_krylov_operator_CFP64_INT64 takes the CSC arrays of the system operator's AT, exactly as mg_set_operator_CF64_INT64
+ * takes As (values conjugated once at upload, the same rule for the width of the row pointers); n must be the fine level's
+ * (MG_ERR_INVALID).  colptr == NULL clears it (also on a handle that is not finalized); without one the drivers apply As[1].
+ * Setting one needs a finalized handle (MG_ERR_STATE otherwise) and leaves it finalized.  mg_finalize refuses (MG_ERR_INVALID) a
+ * handle whose As[1] was re-set with another order than its Krylov operator's: clear the operator, finalize, set a matching one.
+ *
+ * Arguments, flags and the layout of resvec of the drivers are those of mg_bicgstab_FP64 / mg_fgmres_FP64 (above); b and x hold
+ * n complex values, interleaved (re, im); x goes in and out; the _dev forms take device pointers on a 16-byte boundary.  Dots
+ * are Julia's, dot(a, b) = sum conj(a_i) b_i; BiCGSTAB breaks down (flag -2) on rho == 0 or omega == 0 as complex numbers; the
+ * FGMRES rotations have a complex cosine and a real sine.  inner in [1,64]; the work space ((2*inner+2) complex vectors of n
+ * for FGMRES, 6 for BiCGSTAB) is allocated at the first call and released with the handle.  Host synchronisations per
+ * iteration: BiCGSTAB 4, FGMRES 1 per inner step.  Refused: an FP64 handle or a handle not finalized (MG_ERR_STATE); a null
+ * vector, maxIter < 0, a wrong n, inner outside [1,64], a device vector off a 16-byte boundary (MG_ERR_INVALID).  Not served
+ * for complex values: PCG (the operators in question are not Hermitian positive definite), blocks of right-hand sides. */
+int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long long* colptr, const long long* rowval,
+                                       const double* nzval);
+int mg_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter,
+                      long long* iters, long long* flag, double* resvec, long long* nres);
+int mg_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, double tol, long long maxIter,
+                          long long* iters, long long* flag, double* resvec, long long* nres);
+int mg_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol,
+                    long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
+int mg_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long inner, double tol,
+                        long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
+/* One cycle on device vectors (x_is_zero: 0 or 1), enqueued on the handle's stream: no host copy, no synchronisation. */
+int mg_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long x_is_zero);
+/* The fused complex vector passes of those drivers on their own (csrc/mg_cxvec.hpp): device vectors of n complex values on a
+ * 16-byte boundary (MG_ERR_INVALID otherwise), asynchronous on `stream`, deterministic two-pass sums (no atomics) into out_dev
+ * (device doubles).  workspace_dev: 8192 doubles.  Complex scalars are (re, im) pairs in HOST memory; xs_dev / ys_dev / vs_dev
+ * are HOST arrays of device pointers, h_host holds m complex coefficients.
+ *   dots: out[2c], out[2c+1] = dot(xs[c], ys[c]), c < k <= 4          scale: y = a x
+ *   bicg_p: p = r + beta (p - omega v)                                bicg_s: r -= alpha v, out[0] = ||r||^2
+ *   bicg_ts: out = (re, im of dot(t, s), dot(t, t))
+ *   bicg_xr: x += alpha phat + omega shat, r -= omega t, out = (||r||^2, re, im of dot(rtld, r))
+ *   gs_update: w -= sum_{j<m} h[j] vs[j] one after the other (m <= 64, 8 per pass), out (optional) = ||w||^2 */
+int mg_cvec_dots_dev_CFP64(long long k, const double* const* xs_dev, const double* const* ys_dev, long long n,
+                           double* workspace_dev, double* out_dev, void* stream);
+int mg_cvec_scale_dev_CFP64(const double* a, const double* x, double* y, long long n, void* stream);
+int mg_cvec_bicg_p_dev_CFP64(const double* beta, const double* omega, const double* r, const double* v, double* p,
+                             long long n, void* stream);
+int mg_cvec_bicg_s_dev_CFP64(const double* alpha, const double* v, double* r, long long n, double* workspace_dev,
+                             double* out_dev, void* stream);
+int mg_cvec_bicg_ts_dev_CFP64(const double* t, const double* s, long long n, double* workspace_dev, double* out_dev,
+                              void* stream);
+int mg_cvec_bicg_xr_dev_CFP64(const double* alpha, const double* omega, const double* phat, const double* shat,
+                              const double* t, const double* rtld, double* x, double* r, long long n,
+                              double* workspace_dev, double* out_dev, void* stream);
+int mg_cvec_gs_update_dev_CFP64(long long m, const double* h_host, const double* const* vs_dev, double* w, long long n,
+                                double* workspace_dev, double* out_dev, void* stream);
 
 const char* mg_last_error(void);
 const char* mg_version(void);

@@ -2,6 +2,7 @@
 // ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F cycles,
 // pointwise relaxation, dense-inverse or sparse-LU coarsest solve.  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
+// The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
 // Also here: the stand-alone ComplexF64 factor applier behind mg_lu_*_CFP64 (CxLu; its extern "C" entry points sit beside the
 // real applier's in mg_cabi.inc).
 //
@@ -44,6 +45,12 @@ struct CxState {
   DevBuf<double> luLval, luUval, luWork;
   int nLlvl = 0, nUlvl = 0;
   DevBuf<double> stage_b, partial;   // the fine right-hand side; per-row-block partials of ||r||^2
+  // the Krylov drivers (mg_complex_krylov.inc): their system operator (unset: As[1]), work vectors, the partials and scalars of
+  // the fused passes with the scalars' pinned readback, the iterate of the host-pointer forms
+  static constexpr size_t KSCAL = 136;   // 2 * (64 + 2) doubles of an FGMRES(64) inner step, rounded up
+  CxMat K;
+  DevBuf<double> kwork, kpart, kscal, stage_x;
+  double* h_kscal = nullptr;
   ~CxState() {
     for (auto& L : lev) {
       L.A.release(); L.P.release(); L.R.release();
@@ -53,6 +60,9 @@ struct CxState {
     for (DevBuf<int>* d : {&luLptr, &luLcol, &luUptr, &luUcol, &luP, &luQ, &luLorder, &luLlvl, &luUorder, &luUlvl}) d->release();
     luLval.release(); luUval.release(); luWork.release();
     stage_b.release(); partial.release();
+    K.release();
+    kwork.release(); kpart.release(); kscal.release(); stage_x.release();
+    if (h_kscal) (void)hipHostFree(h_kscal);
   }
 };
 
@@ -323,6 +333,8 @@ int cx_finalize(mg_hierarchy* h) {
     if (L.R.n_rows != nc || L.R.n_cols != L.n)
       return fail(MG_ERR_INVALID, "Rs[%d] is %lldx%lld, expected %lldx%lld", l + 1, L.R.n_rows, L.R.n_cols, nc, L.n);
   }
+  if (S.K.set && S.K.n_rows != S.lev[0].n)
+    return fail(MG_ERR_INVALID, "the Krylov operator has order %lld, As[1] %lld rows (clear it with mg_set_krylov_operator_CFP64_INT64(h, n, NULL, ...), finalize, then set a matching one)", S.K.n_rows, S.lev[0].n);
   if (!S.coarse_set) return fail(MG_ERR_STATE, "the coarsest solve was not set");
   if (S.n_coarse != S.lev[(size_t)nl - 1].n)
     return fail(MG_ERR_INVALID, "coarse solve order %lld != coarsest level size %lld", S.n_coarse, S.lev[(size_t)nl - 1].n);

@@ -1,0 +1,437 @@
+// mg_complex_krylov.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip behind mg_complex.inc; not compiled on its own).
+// ComplexF64 BiCGSTAB and FGMRES with one cycle of a CF64 hierarchy as preconditioner, vectors resident in HBM across iterations:
+// solveBiCGSTAB_MG / solveGMRES_MG (SolveFuncs.jl:85-133) for VAL = ComplexF64 with an Afun of their own - the way Helmholtz problems
+// are solved: the Krylov method runs on the (nearly) undamped operator, the hierarchy is built on a damped copy of it.
+//   * The system operator is the handle's Krylov operator (mg_set_krylov_operator_CFP64_INT64; uploaded like As, conjugated once) or,
+//     without one, As[1].  Products with it are cx_spmv<AXPBY> / <RESID>.
+//   * The preconditioner is cx_cycle from x = 0 on the input vector.  Its result lives in lev[0].x[xi] and the next cycle overwrites
+//     it, so it is COPIED OUT where it outlives the next cycle (BiCGSTAB's phat, FGMRES's Z_i; cx_cycle is left as it is); BiCGSTAB's
+//     shat is consumed before the next cycle and is read where the cycle left it.
+//   * The algorithms are bicgstab_dev / fgmres_core of mg_krylov.inc with complex scalars and conjugated dots (dot(a, b) = sum conj(a_i) b_i);
+//     flags, stopping tests and the layout of resvec are theirs.  Every vector update and every scalar is one fused pass of mg_cxvec.hpp.
+//   * Host synchronisations per iteration: BiCGSTAB 4 (dot(rtld, v) ; ||s|| ; (dot(t, s), dot(t, t)) ; (||r||, the next rho)), FGMRES 1 per
+//     inner step (the chained Gram-Schmidt leaves the i + 2 scalars of a step in HBM; one readback).
+// Also here: the stand-alone entry points of the passes (mg_cvec_*_dev_CFP64) and mg_cycle_dev_CFP64.
+namespace {
+
+typedef std::complex<double> zc;
+inline cx_t cxv(zc a) { return cx_t{a.real(), a.imag()}; }
+inline const cx_t* ccx(const double* p) { return reinterpret_cast<const cx_t*>(p); }
+inline cx_t* mcx(double* p) { return reinterpret_cast<cx_t*>(p); }
+
+// every vector of a complex pass starts on a 16-byte boundary
+int cxv_aligned(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if (!a || (a & 15)) return fail(MG_ERR_INVALID, "a vector of a complex pass is null or not 16-byte aligned");
+  }
+  return MG_OK;
+}
+// one pass + (ns > 0) the sums of its first ns scalars into out[0 .. ns)
+template <class Op>
+int cxv_launch(const Op& op, long long n, std::initializer_list<const void*> ptrs, double* part, int ns, double* out, hipStream_t s) {
+  if (n < 1) return fail(MG_ERR_INVALID, "a complex pass needs n >= 1");
+  if (Op::NS > 0 && (!part || (ns > 0 && !out))) return fail(MG_ERR_INVALID, "a complex pass with sums needs its work space and output");
+  MG_TRY(cxv_aligned(ptrs));
+  const int nb = mgcv::cxv_grid(n);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(mgcv::cxv_pass<Op>), dim3(nb), dim3(mgcv::KB), 0, s, op, n, part);
+  if (Op::NS > 0 && ns > 0) hipLaunchKernelGGL(mgkv::krv_final, dim3(ns), dim3(mgcv::KB), 0, s, part, nb, out);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+// out[2c], out[2c+1] = dot(xs[c], ys[c]), c < k <= 4
+int cxv_dots(int k, const double* const* xs, const double* const* ys, long long n, double* part, double* out, hipStream_t s) {
+  if (k < 1 || k > mgcv::MAXD || !xs || !ys) return fail(MG_ERR_INVALID, "complex dots: 1 to %d pairs", mgcv::MAXD);
+  if (!part || !out) return fail(MG_ERR_INVALID, "complex dots: null work space or output");
+  mgcv::OpCDots op;
+  op.k = k;
+  for (int c = 0; c < mgcv::MAXD; ++c) {
+    op.x[c] = ccx(xs[c < k ? c : 0]);
+    op.y[c] = ccx(ys[c < k ? c : 0]);
+  }
+  return cxv_launch(op, n, {op.x[0], op.x[1], op.x[2], op.x[3], op.y[0], op.y[1], op.y[2], op.y[3]}, part, 2 * k, out, s);
+}
+// w -= sum_j h_j v_j over any number of vectors, 8 per pass; the last pass leaves ||w||^2 in out[0] when out is given.
+// hcoef: m complex coefficients, interleaved.
+int cxv_gs_update(int m, const double* hcoef, const double* const* vs, double* w, long long n, double* part, double* out, hipStream_t s) {
+  for (int j0 = 0; j0 < m; j0 += mgcv::MAXV) {
+    mgcv::OpCGsUpdate op;
+    op.m = std::min(mgcv::MAXV, m - j0);
+    op.w = mcx(w);
+    for (int j = 0; j < mgcv::MAXV; ++j) {
+      const int jj = j0 + (j < op.m ? j : 0);
+      op.h[j] = j < op.m ? cx_t{hcoef[2 * jj], hcoef[2 * jj + 1]} : cx_t{0.0, 0.0};
+      op.v[j] = ccx(vs[jj]);
+    }
+    const bool last = j0 + mgcv::MAXV >= m;
+    MG_TRY(cxv_launch(op, n, {op.v[0], op.v[1], op.v[2], op.v[3], op.v[4], op.v[5], op.v[6], op.v[7], op.w}, part, (last && out) ? 1 : 0, out, s));
+  }
+  return MG_OK;
+}
+
+// ---- what the two drivers share ----
+struct CxKry {
+  mg_hierarchy* h;
+  CxState& S;
+  const long long n;
+  const CxMat& A;      // the system operator
+  hipStream_t st;
+  explicit CxKry(mg_hierarchy* h_) : h(h_), S(*h_->cx), n(h_->cx->lev[0].n), A(h_->cx->K.set ? h_->cx->K : h_->cx->lev[0].A), st(h_->play->stream) {}
+  double* part() { return S.kpart.p; }
+  double* scal() { return S.kscal.p; }
+  // work space: `vecs` complex vectors of n and the scalars' buffers, allocated at the first call and kept with the handle
+  int ensure(size_t vecs) {
+    if (S.kpart.n == 0) MG_TRY(S.kpart.alloc((size_t)mgcv::MAXS * mgcv::MAXB));
+    if (S.kscal.n == 0) MG_TRY(S.kscal.alloc(CxState::KSCAL));
+    if (!S.h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_kscal), sizeof(double) * CxState::KSCAL));
+    const size_t need = vecs * 2 * (size_t)n;
+    if (S.kwork.n < need) MG_TRY(S.kwork.alloc(need));
+    return MG_OK;
+  }
+  cx_t* vec(size_t i) { return cxp(S.kwork) + i * (size_t)n; }
+  template <class Op> int pass(const Op& op, std::initializer_list<const void*> ptrs, int ns = Op::NS) {
+    return cxv_launch(op, n, ptrs, part(), ns, scal(), st);
+  }
+  int dot1(const cx_t* x, const cx_t* y) {
+    const double* xs[1] = {reinterpret_cast<const double*>(x)};
+    const double* ys[1] = {reinterpret_cast<const double*>(y)};
+    return cxv_dots(1, xs, ys, n, part(), scal(), st);
+  }
+  // the first `count` doubles of the scalar buffer on the host: one readback, one synchronisation
+  int read(int count, const double** out) {
+    HIP_TRY(hipMemcpyAsync(S.h_kscal, S.kscal.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(spin_sync(st));
+    *out = S.h_kscal;
+    return MG_OK;
+  }
+  int copy(cx_t* dst, const cx_t* src) {
+    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(cx_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    return MG_OK;
+  }
+  // *z = M(v): one cycle from x = 0; *z is the level buffer the cycle left its result in (valid until the next cycle)
+  int prec(const cx_t* v, const cx_t** z) {
+    int xi = 0;
+    MG_TRY(cx_cycle(h, 0, v, xi, true, h->cycle));
+    *z = cxp(S.lev[0].x[xi]);
+    return MG_OK;
+  }
+  int product(const cx_t* x, cx_t* y) { return cx_spmv<mgk::AXPBY>(h, A, x, y, nullptr, nullptr, nullptr); }
+  int residual(const cx_t* b, const cx_t* x, cx_t* r) { return cx_spmv<mgk::RESID>(h, A, x, r, b, nullptr, nullptr); }
+  int zero(cx_t* x) {
+    HIP_TRY(hipMemsetAsync(x, 0, sizeof(cx_t) * (size_t)n, st));
+    return MG_OK;
+  }
+};
+
+// bicgstab_dev (mg_krylov.inc) for complex vectors.  rho = dot(rtld, r), alpha = rho / dot(rtld, v), omega = dot(t, s) / dot(t, t),
+// beta = (rho / rho1)(alpha / omega); breakdown is rho == 0 or omega == 0 as complex numbers.  The pass that ends an iteration
+// (bicg_xr) also delivers dot(rtld, r) of the new r: the next iteration starts without a dot of its own.
+int cx_bicgstab_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, double tol, long long maxIter, long long* iters, long long* flag_out,
+                    double* resvec, long long* nres) {
+  CxKry K(h);
+  MG_TRY(K.ensure(6));
+  cx_t *r = K.vec(0), *p = K.vec(1), *v = K.vec(2), *rtld = K.vec(3), *t = K.vec(4), *phat = K.vec(5);
+  const double* sc = nullptr;
+  long long it = 0, flag = -1, nr = 0;
+  auto finish = [&](long long f) {
+    if (iters) *iters = it;
+    if (flag_out) *flag_out = f;
+    if (nres) *nres = nr;
+    return (int)MG_OK;
+  };
+  MG_TRY(K.dot1(b, b));
+  MG_TRY(K.read(1, &sc));
+  const double bn = std::sqrt(sc[0]);
+  if (bn == 0.0) {
+    MG_TRY(K.zero(x));
+    HIP_TRY(spin_sync(K.st));
+    return finish(-9);
+  }
+  MG_TRY(K.residual(b, x, r));
+  MG_TRY(K.dot1(r, r));                               // ||r0||^2, and rho of the first iteration (rtld = r0)
+  MG_TRY(K.read(2, &sc));
+  double err = std::sqrt(sc[0]) / bn;
+  zc rho(sc[0], sc[1]), rho1(0.0, 0.0), alpha(0.0, 0.0), omega(1.0, 0.0);
+  if (resvec) resvec[nr] = err;
+  ++nr;
+  if (err < tol) return finish(0);
+  MG_TRY(K.copy(rtld, r));
+  for (long long k = 1; k <= maxIter; ++k) {
+    it = k;
+    if (rho == zc(0.0, 0.0)) { flag = -2; break; }
+    if (k > 1) {
+      const zc beta = (rho / rho1) * (alpha / omega);
+      MG_TRY(K.pass(mgcv::OpCBicgP{cxv(beta), cxv(omega), r, v, p}, {r, v, p}));       // p = r + beta (p - omega v)
+    } else {
+      MG_TRY(K.copy(p, r));
+    }
+    const cx_t* z = nullptr;
+    MG_TRY(K.prec(p, &z));                                                              // p_hat = M1(p)
+    MG_TRY(K.copy(phat, z));
+    MG_TRY(K.product(phat, v));
+    MG_TRY(K.dot1(rtld, v));
+    MG_TRY(K.read(2, &sc));                                                             // synchronisation 1
+    alpha = rho / zc(sc[0], sc[1]);
+    MG_TRY(K.pass(mgcv::OpCBicgS{cxv(alpha), v, r}, {v, r}));                           // s = r - alpha v (in r) ; ||s||^2
+    MG_TRY(K.read(1, &sc));                                                             // synchronisation 2
+    const double sn = std::sqrt(sc[0]) / bn;
+    if (resvec) resvec[nr] = sn;
+    ++nr;
+    if (sn < tol) {                                                                     // converged on the half step
+      const double ma[2] = {-alpha.real(), -alpha.imag()};
+      const double* vs[1] = {reinterpret_cast<const double*>(phat)};
+      MG_TRY(cxv_gs_update(1, ma, vs, reinterpret_cast<double*>(x), K.n, K.part(), nullptr, K.st));   // x += alpha p_hat
+      flag = -3;
+      break;
+    }
+    MG_TRY(K.prec(r, &z));                                                              // s_hat = M1(s), read where the cycle left it
+    MG_TRY(K.product(z, t));
+    MG_TRY(K.pass(mgcv::OpCBicgTS{t, r}, {t, r}));
+    MG_TRY(K.read(3, &sc));                                                             // synchronisation 3
+    omega = zc(sc[0], sc[1]) / sc[2];
+    MG_TRY(K.pass(mgcv::OpCBicgXR{cxv(alpha), cxv(omega), phat, z, t, rtld, x, r}, {phat, z, t, rtld, x, r}));
+    MG_TRY(K.read(3, &sc));                                                             // synchronisation 4: ||r||^2 and the next rho
+    err = std::sqrt(sc[0]) / bn;
+    if (resvec) resvec[nr] = err;
+    ++nr;
+    if (err <= tol) { flag = 0; break; }
+    if (omega == zc(0.0, 0.0)) { flag = -2; break; }
+    rho1 = rho;
+    rho = zc(sc[1], sc[2]);
+  }
+  HIP_TRY(spin_sync(K.st));
+  return finish(flag);
+}
+
+// fgmres_core (mg_krylov.inc) for complex vectors.  H[k,i] = dot(V_k, w), H[i+1,i] = ||w|| (real).  The rotation of column i has a
+// complex cosine and a real sine: rr = sqrt(|a|^2 + b^2), c = a / rr, s = b / rr with a = H[i,i], b = H[i+1,i]; it is applied as
+// t = conj(c) H[k] + s H[k+1] ; H[k+1] = -s H[k] + c H[k+1] ; H[k] = t, and to the right-hand side as s_{i+1} = -s s_i ; s_i = conj(c) s_i.
+int cx_fgmres_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, long long inner, double tol, long long maxIter, long long* iters,
+                  long long* flag_out, double* resvec, long long* nres) {
+  const int m = (int)inner;
+  CxKry K(h);
+  MG_TRY(K.ensure((size_t)(2 * m + 2)));
+  const long long n = K.n;
+  cx_t* V = K.vec(0);                    // m+1 basis vectors
+  cx_t* Z = K.vec((size_t)m + 1);        // m preconditioned vectors
+  cx_t* r = K.vec((size_t)2 * m + 1);    // residual
+  const double* sc = nullptr;
+  long long nr = 0, flag = -1, total = 0;
+  auto finish = [&](long long f) {
+    if (iters) *iters = total;
+    if (flag_out) *flag_out = f;
+    if (nres) *nres = nr;
+    return (int)MG_OK;
+  };
+  MG_TRY(K.dot1(b, b));
+  MG_TRY(K.read(1, &sc));
+  const double bn = std::sqrt(sc[0]);
+  if (bn == 0.0) {
+    MG_TRY(K.zero(x));
+    HIP_TRY(spin_sync(K.st));
+    return finish(-9);
+  }
+  MG_TRY(K.residual(b, x, r));
+  MG_TRY(K.dot1(r, r));
+  MG_TRY(K.read(1, &sc));
+  double rn = std::sqrt(sc[0]);
+  double err = rn / bn;
+  if (err < tol) return finish(0);
+  std::vector<zc> H((size_t)(m + 1) * m), cs((size_t)m), s((size_t)m + 1), y((size_t)m);
+  std::vector<double> sn((size_t)m, 0.0), ny((size_t)2 * m);
+  std::vector<const double*> zp((size_t)m);
+  for (int i = 0; i < m; ++i) zp[(size_t)i] = reinterpret_cast<const double*>(Z + (size_t)i * n);
+  auto Hat = [&](int i, int j) -> zc& { return H[(size_t)i * m + j]; };
+  double* hd = K.scal();
+  for (long long it = 1; it <= maxIter && flag != 0; ++it) {
+    MG_TRY(K.pass(mgcv::OpCScale{cx_t{1.0 / rn, 0.0}, r, V}, {r, V}));               // V[:,1] = r/||r||
+    std::fill(H.begin(), H.end(), zc(0.0, 0.0));
+    std::fill(s.begin(), s.end(), zc(0.0, 0.0));
+    s[0] = rn;
+    int used = 0;
+    for (int i = 0; i < m; ++i) {
+      cx_t* vi = V + (size_t)i * n;
+      cx_t* zi = Z + (size_t)i * n;
+      cx_t* w = V + (size_t)(i + 1) * n;
+      const cx_t* z = nullptr;
+      MG_TRY(K.prec(vi, &z));                                                         // z = M(V[:,i])
+      MG_TRY(K.copy(zi, z));
+      MG_TRY(K.product(zi, w));                                                       // w = A z
+      // modified Gram-Schmidt as one chain on the device: h_k = dot(V_k, w) stays in HBM, the update w -= h_k V_k reads it there and
+      // leaves the partials of the next dot (or of ||w||^2) in the same pass; the i + 2 scalars come back in ONE readback
+      MG_TRY(K.dot1(V, w));
+      for (int k = 0; k <= i; ++k) {
+        const cx_t* vk = V + (size_t)k * n;
+        const cx_t* u = k < i ? V + (size_t)(k + 1) * n : nullptr;
+        MG_TRY(cxv_launch(mgcv::OpCMgsStep{hd + 2 * k, vk, u, w}, n, {vk, u ? u : vk, w}, K.part(), 2, hd + 2 * (k + 1), K.st));
+      }
+      MG_TRY(K.read(2 * (i + 2), &sc));
+      for (int k = 0; k <= i; ++k) Hat(k, i) = zc(sc[2 * k], sc[2 * k + 1]);
+      const double wn = std::sqrt(sc[2 * (i + 1)]);
+      Hat(i + 1, i) = wn;
+      if (wn != 0.0) MG_TRY(K.pass(mgcv::OpCScale{cx_t{1.0 / wn, 0.0}, w, w}, {w}));  // V[:,i+1] = w/||w||
+      for (int k = 0; k < i; ++k) {                                                   // previous rotations
+        const zc t = std::conj(cs[(size_t)k]) * Hat(k, i) + sn[(size_t)k] * Hat(k + 1, i);
+        Hat(k + 1, i) = -sn[(size_t)k] * Hat(k, i) + cs[(size_t)k] * Hat(k + 1, i);
+        Hat(k, i) = t;
+      }
+      const zc a = Hat(i, i);
+      const double rr = std::sqrt(std::norm(a) + wn * wn);
+      cs[(size_t)i] = (rr == 0.0) ? zc(1.0, 0.0) : a / rr;
+      sn[(size_t)i] = (rr == 0.0) ? 0.0 : wn / rr;
+      Hat(i, i) = rr;
+      Hat(i + 1, i) = 0.0;
+      s[(size_t)i + 1] = -sn[(size_t)i] * s[(size_t)i];
+      s[(size_t)i] = std::conj(cs[(size_t)i]) * s[(size_t)i];
+      err = std::abs(s[(size_t)i + 1]) / bn;
+      if (resvec) resvec[nr] = err;
+      ++nr;
+      ++total;
+      used = i + 1;
+      if (err <= tol) { flag = 0; break; }
+    }
+    for (int i = used - 1; i >= 0; --i) {                                             // y = H \ s (upper triangular)
+      zc acc = s[(size_t)i];
+      for (int k = i + 1; k < used; ++k) acc -= Hat(i, k) * y[(size_t)k];
+      y[(size_t)i] = acc / Hat(i, i);
+      ny[2 * (size_t)i] = -y[(size_t)i].real();
+      ny[2 * (size_t)i + 1] = -y[(size_t)i].imag();
+    }
+    if (used > 0) MG_TRY(cxv_gs_update(used, ny.data(), zp.data(), reinterpret_cast<double*>(x), n, K.part(), nullptr, K.st));   // x += Z y
+    if (flag == 0) break;
+    MG_TRY(K.residual(b, x, r));
+    MG_TRY(K.dot1(r, r));
+    MG_TRY(K.read(1, &sc));
+    rn = std::sqrt(sc[0]);
+    err = rn / bn;
+    if (err <= tol) { flag = 0; break; }
+  }
+  HIP_TRY(spin_sync(K.st));
+  return finish(flag);
+}
+
+// the checks every driver entry point shares; host form: b, x staged through the handle's device buffers
+template <class F>
+int cx_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long maxIter, bool device_form, F&& run) {
+  MG_TRY(cx_check_ready(h, n, 1));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  if (device_form) {
+    MG_TRY(cxv_aligned({b, x}));
+    return run(ccx(b), mcx(x));
+  }
+  const size_t len = 2 * (size_t)n, bytes = len * sizeof(double);
+  if (S.stage_x.n != len) MG_TRY(S.stage_x.alloc(len));
+  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
+  HIP_TRY(hipMemcpyAsync(S.stage_x.p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
+  MG_TRY(run(cxp(S.stage_b), cxp(S.stage_x)));
+  HIP_TRY(hipMemcpyAsync(x, S.stage_x.p, bytes, hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
+  return MG_OK;
+}
+
+}  // namespace
+
+// =================================================================================================
+// C ABI: the ComplexF64 Krylov drivers, their system operator, the device-pointer cycle and the passes on their own
+// =================================================================================================
+extern "C" {
+
+int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long long* colptr, const long long* rowval,
+                                       const double* nzval) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, 1));
+  CxState& S = *h->cx;
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));
+  if (!colptr) {   // back to As[1]; also on a handle that is not finalized (the way out when mg_finalize refuses a stale operator)
+    S.K.release();
+    return MG_OK;
+  }
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize before setting a Krylov operator");
+  if (n != S.lev[0].n) return fail(MG_ERR_INVALID, "Krylov operator of order %lld on a fine level of %lld rows", n, S.lev[0].n);
+  return cx_upload(&S.K, h->opt, n, n, colptr, rowval, nzval, true);   // (a failed upload leaves the handle on As[1])
+}
+
+int mg_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long x_is_zero) {
+  MG_TRY(cx_check_ready(h, n, 1));
+  if (!b_dev || !x_dev) return fail(MG_ERR_INVALID, "null vector");
+  if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for device vectors");
+  MG_TRY(cxv_aligned({b_dev, x_dev}));
+  (void)hipSetDevice(h->device);
+  CxLevel& L0 = h->cx->lev[0];
+  const size_t bytes = 2 * sizeof(double) * (size_t)n;
+  int xi = 0;
+  if (!x_is_zero) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x_dev, bytes, hipMemcpyDeviceToDevice, h->play->stream));
+  MG_TRY(cx_cycle(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle));
+  HIP_TRY(hipMemcpyAsync(x_dev, L0.x[xi].p, bytes, hipMemcpyDeviceToDevice, h->play->stream));
+  return MG_OK;
+}
+
+int mg_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, double tol, long long maxIter,
+                          long long* iters, long long* flag, double* resvec, long long* nres) {
+  return cx_krylov(h, b_dev, x_dev, n, maxIter, true,
+                   [&](const cx_t* bv, cx_t* xv) { return cx_bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
+}
+int mg_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter, long long* iters,
+                      long long* flag, double* resvec, long long* nres) {
+  return cx_krylov(h, b, x, n, maxIter, false,
+                   [&](const cx_t* bv, cx_t* xv) { return cx_bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
+}
+int mg_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long inner, double tol,
+                        long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
+  return cx_krylov(h, b_dev, x_dev, n, maxIter, true,
+                   [&](const cx_t* bv, cx_t* xv) { return cx_fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
+}
+int mg_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol, long long maxIter,
+                    long long* iters, long long* flag, double* resvec, long long* nres) {
+  if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
+  return cx_krylov(h, b, x, n, maxIter, false,
+                   [&](const cx_t* bv, cx_t* xv) { return cx_fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
+}
+
+// ---- the passes on their own (tests, callers with Krylov loops of their own): asynchronous on `stream`; workspace_dev >= 8192
+//      doubles, out_dev receives the pass's sums over the n elements; complex scalars are (re, im) pairs on the host ----
+#define CXV_STREAM reinterpret_cast<hipStream_t>(stream)
+#define CXV_C(p) cx_t{(p)[0], (p)[1]}
+int mg_cvec_dots_dev_CFP64(long long k, const double* const* xs_dev, const double* const* ys_dev, long long n, double* workspace_dev,
+                           double* out_dev, void* stream) {
+  return cxv_dots((int)std::min<long long>(std::max<long long>(k, 0), mgcv::MAXD + 1), xs_dev, ys_dev, n, workspace_dev, out_dev, CXV_STREAM);
+}
+int mg_cvec_scale_dev_CFP64(const double* a, const double* x, double* y, long long n, void* stream) {
+  if (!a) return fail(MG_ERR_INVALID, "null scalar");
+  return cxv_launch(mgcv::OpCScale{CXV_C(a), ccx(x), mcx(y)}, n, {x, y}, nullptr, 0, nullptr, CXV_STREAM);
+}
+int mg_cvec_bicg_p_dev_CFP64(const double* beta, const double* omega, const double* r, const double* v, double* p, long long n,
+                             void* stream) {
+  if (!beta || !omega) return fail(MG_ERR_INVALID, "null scalar");
+  return cxv_launch(mgcv::OpCBicgP{CXV_C(beta), CXV_C(omega), ccx(r), ccx(v), mcx(p)}, n, {r, v, p}, nullptr, 0, nullptr, CXV_STREAM);
+}
+int mg_cvec_bicg_s_dev_CFP64(const double* alpha, const double* v, double* r, long long n, double* workspace_dev, double* out_dev,
+                             void* stream) {
+  if (!alpha) return fail(MG_ERR_INVALID, "null scalar");
+  return cxv_launch(mgcv::OpCBicgS{CXV_C(alpha), ccx(v), mcx(r)}, n, {v, r}, workspace_dev, 1, out_dev, CXV_STREAM);
+}
+int mg_cvec_bicg_ts_dev_CFP64(const double* t, const double* s, long long n, double* workspace_dev, double* out_dev, void* stream) {
+  return cxv_launch(mgcv::OpCBicgTS{ccx(t), ccx(s)}, n, {t, s}, workspace_dev, 3, out_dev, CXV_STREAM);
+}
+int mg_cvec_bicg_xr_dev_CFP64(const double* alpha, const double* omega, const double* phat, const double* shat, const double* t,
+                              const double* rtld, double* x, double* r, long long n, double* workspace_dev, double* out_dev,
+                              void* stream) {
+  if (!alpha || !omega) return fail(MG_ERR_INVALID, "null scalar");
+  return cxv_launch(mgcv::OpCBicgXR{CXV_C(alpha), CXV_C(omega), ccx(phat), ccx(shat), ccx(t), ccx(rtld), mcx(x), mcx(r)}, n,
+                    {phat, shat, t, rtld, x, r}, workspace_dev, 3, out_dev, CXV_STREAM);
+}
+int mg_cvec_gs_update_dev_CFP64(long long m, const double* h_host, const double* const* vs_dev, double* w, long long n,
+                                double* workspace_dev, double* out_dev, void* stream) {
+  if (m < 1 || m > 64 || !h_host || !vs_dev || !w || n < 1 || !workspace_dev)
+    return fail(MG_ERR_INVALID, "gs_update: 1 to 64 vectors, non-null arguments");
+  return cxv_gs_update((int)m, h_host, vs_dev, w, n, workspace_dev, out_dev, CXV_STREAM);
+}
+#undef CXV_C
+#undef CXV_STREAM
+
+}  // extern "C"

@@ -14,6 +14,7 @@
 #include <array>
 #include <atomic>
 #include <cmath>
+#include <complex>
 #include <cstdarg>
 #include <cstdint>
 #include <cstddef>
@@ -34,6 +35,7 @@
 #include "mg_small.hpp"
 #include "mg_complex.hpp"
 #include "mg_krvec.hpp"
+#include "mg_cxvec.hpp"
 #include "mg_dd.hpp"
 #include "mg_vanka.hpp"
 
@@ -48,6 +50,7 @@
 #include "mg_krylov.inc"     // PCG / BiCGSTAB / FGMRES and block variants
 #include "mg_formats.inc"    // upload, format builders, scratch
 #include "mg_complex.inc"    // ComplexF64 hierarchies: generic-CSR kernels' launchers, cycle, solve, and their extern "C" entry points
+#include "mg_complex_krylov.inc"   // extern "C": ComplexF64 BiCGSTAB / FGMRES on a system operator of their own, their fused vector passes
 #include "mg_cabi.inc"       // extern "C": the single-GPU API and its ghost-layer form (mg_ghost_*)
 #include "mg_dist.inc"       // extern "C": the native multi-GPU sequencer (halo form)
 #include "mg_dist_krylov.inc"   // extern "C": PCG / BiCGSTAB / FGMRES on the sharded halo form, their fused vector passes

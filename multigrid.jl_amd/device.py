@@ -199,6 +199,19 @@ SIGNATURES = {
     "mg_cycle_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_solve_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
     "mg_spmv_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _dp, _dp, _dp, _ll]),
+    "mg_set_krylov_operator_CFP64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp]),
+    "mg_bicgstab_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_bicgstab_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_fgmres_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_fgmres_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_cycle_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_cvec_dots_dev_CFP64": (C.c_int, [_ll, C.POINTER(_vp), C.POINTER(_vp), _ll, _vp, _vp, _vp]),
+    "mg_cvec_scale_dev_CFP64": (C.c_int, [_dp, _vp, _vp, _ll, _vp]),
+    "mg_cvec_bicg_p_dev_CFP64": (C.c_int, [_dp, _dp, _vp, _vp, _vp, _ll, _vp]),
+    "mg_cvec_bicg_s_dev_CFP64": (C.c_int, [_dp, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_cvec_bicg_ts_dev_CFP64": (C.c_int, [_vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_cvec_bicg_xr_dev_CFP64": (C.c_int, [_dp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "mg_cvec_gs_update_dev_CFP64": (C.c_int, [_ll, _dp, C.POINTER(_vp), _vp, _ll, _vp, _vp, _vp]),
     "mg_last_error": (C.c_char_p, []),
     "mg_version": (C.c_char_p, []),
 }
@@ -943,12 +956,92 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
                "mg_spmv_CF64")
         return y
 
-    def _refuse(self, *args, **kwargs):
-        raise NotImplementedError("the device Krylov drivers, the replace / transpose updates and the device-pointer entry points "
-                                  "serve FP64 hierarchies only; precondition a Krylov method with getMultigridPreconditioner")
+    # -- the ComplexF64 Krylov drivers (mg_*_CFP64): BiCGSTAB / FGMRES on a system operator of their own ------------------------
+    def set_krylov_operator(self, A):
+        """The operator the Krylov drivers apply: a scipy sparse matrix (the APPLIED operator, as ``param.As``; real or complex),
+        or None for the hierarchy's own fine level.  The cycle stays the preconditioner.  ``krylov_operator`` is the object
+        uploaded last; a refused upload (wrong order) leaves the operator that was there."""
+        if A is None:
+            self._krylov_operator = None        # (whatever happens below, the object recorded is never one that is not uploaded)
+            _check(self.lib, self.lib.mg_set_krylov_operator_CFP64_INT64(self.handle, self.n, None, None, None),
+                   "mg_set_krylov_operator_CFP64")
+            return
+        import scipy.sparse as sp
+        M = sp.csr_matrix(A, dtype=np.complex128, copy=True)
+        M.sum_duplicates()
+        M.sort_indices()
+        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64) + 1
+        rowval = np.ascontiguousarray(M.indices, dtype=np.int64) + 1
+        nzval = np.ascontiguousarray(np.conj(M.data), dtype=np.complex128)     # the reference's AT values
+        if M.shape[0] != M.shape[1]:
+            raise ValueError("the Krylov operator must be square")
+        _check(self.lib, self.lib.mg_set_krylov_operator_CFP64_INT64(self.handle, M.shape[0], _i64(colptr), _i64(rowval), _c128(nzval)),
+               "mg_set_krylov_operator_CFP64")
+        self._krylov_operator = A               # the object uploaded last (None: the fine level), whoever asked for it
 
-    pcg = bicgstab = fgmres = cycle_mixed_f32 = pcg_dev = block_pcg_dev = block_bicgstab_dev = block_fgmres_dev = _refuse
-    bicgstab_dev = fgmres_dev = cycle_dev = solve_dev = spmv_dev = fused_dev = sweep_residual_dev = four_stage_dev = _refuse
+    _krylov_operator = None
+
+    @property
+    def krylov_operator(self):
+        """The object handed to ``set_krylov_operator`` last (None: the drivers apply the hierarchy's fine level)."""
+        return self._krylov_operator
+
+    def _krylov_c(self, name, res, b, x, *args):
+        iters, flag, count = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        fn = getattr(self.lib, f"mg_{name}_CFP64")
+        _check(self.lib, fn(self.handle, b, x, self.n, *args, C.byref(iters), C.byref(flag), _f64(res), C.byref(count)), f"mg_{name}_CFP64")
+        return int(flag.value), int(iters.value), res[: count.value]
+
+    def _host_pair(self, b, x):
+        b = self._host_block(b)
+        x = self._host_block(x, True)
+        if b.shape[0] != self.n or x.shape[0] != self.n:
+            raise ValueError(f"vectors of {self.n} complex values expected")
+        return b, x
+
+    @staticmethod
+    def _dev_pair(b, x):
+        for t in (b, x):
+            if hasattr(t, "dtype") and hasattr(t, "data_ptr"):
+                import torch
+                if t.dtype != torch.complex128:
+                    raise TypeError("expected torch.complex128 tensors for a ComplexF64 hierarchy")
+        _sync_torch(b, x)
+        return _ptr(b), _ptr(x)
+
+    def bicgstab(self, b, x, tol: float, maxIter: int):
+        """KrylovMethods.bicgstb on the Krylov operator with the cycle as M1; returns (x, flag, iters, resvec)."""
+        b, x = self._host_pair(b, x)
+        return (x,) + self._krylov_c("bicgstab", np.zeros(2 * max(int(maxIter), 0) + 1), _c128(b), _c128(x), float(tol), int(maxIter))
+
+    def fgmres(self, b, x, inner: int, tol: float, maxIter: int):
+        """KrylovMethods.fgmres (flexible, restarted) on the Krylov operator with the cycle as preconditioner; returns
+        (x, flag, inner steps, resvec)."""
+        b, x = self._host_pair(b, x)
+        return (x,) + self._krylov_c("fgmres", np.zeros(max(1, int(inner) * int(maxIter))), _c128(b), _c128(x), int(inner), float(tol),
+                                     int(maxIter))
+
+    def bicgstab_dev(self, b, x, tol: float, maxIter: int):
+        """The same on torch.complex128 device tensors; returns (flag, iters, resvec)."""
+        pb, px = self._dev_pair(b, x)
+        return self._krylov_c("bicgstab_dev", np.zeros(2 * max(int(maxIter), 0) + 1), pb, px, float(tol), int(maxIter))
+
+    def fgmres_dev(self, b, x, inner: int, tol: float, maxIter: int):
+        pb, px = self._dev_pair(b, x)
+        return self._krylov_c("fgmres_dev", np.zeros(max(1, int(inner) * int(maxIter))), pb, px, int(inner), float(tol), int(maxIter))
+
+    def cycle_dev(self, b, x, x_is_zero: int):
+        """One cycle on torch.complex128 device tensors (x_is_zero 0 or 1), enqueued on the library's stream without a
+        synchronisation: synchronise the device before reading x."""
+        pb, px = self._dev_pair(b, x)
+        _check(self.lib, self.lib.mg_cycle_dev_CFP64(self.handle, pb, px, self.n, int(x_is_zero)), "mg_cycle_dev_CFP64")
+
+    def _refuse(self, *args, **kwargs):
+        raise NotImplementedError("PCG, the block Krylov drivers, the replace / transpose updates and the other device-pointer entry "
+                                  "points serve FP64 hierarchies only (ComplexF64: bicgstab, fgmres, cycle_dev and their _dev forms)")
+
+    pcg = cycle_mixed_f32 = pcg_dev = block_pcg_dev = block_bicgstab_dev = block_fgmres_dev = _refuse
+    solve_dev = spmv_dev = fused_dev = sweep_residual_dev = four_stage_dev = _refuse
     replace_values = replace_matrix = transpose_hierarchy = get_values = cycle_async_dev = _refuse
 
 
@@ -1151,3 +1244,53 @@ def vec_gs_update(h, vs, w, n, workspace, out=None, stream=0):
     hh = np.ascontiguousarray(h, dtype=np.float64)
     _check(lib, lib.mg_vec_gs_update_dev_FP64(len(vs), _f64(hh), _ptr_array(vs), _ptr(w), int(n), _ptr(workspace),
                                               _ptr(out) if out is not None else None, _vp(stream)), "mg_vec_gs_update_dev")
+
+
+# ---- the fused ComplexF64 vector passes of the complex Krylov drivers (csrc/mg_cxvec.hpp): torch.complex128 device tensors on a
+#      16-byte boundary, asynchronous on `stream`; workspace: KRV_WORKSPACE doubles, out: the pass's sums (device doubles) ----------
+def _cpair(a):
+    a = complex(a)
+    return _f64(np.array([a.real, a.imag]))
+
+
+def cvec_dots(xs, ys, n, workspace, out, stream=0):
+    """out[2c], out[2c+1] = re, im of dot(xs[c], ys[c]) = sum conj(xs[c]) ys[c] over n elements, c < len(xs) <= 4, in one pass."""
+    lib = load_library()
+    _check(lib, lib.mg_cvec_dots_dev_CFP64(len(xs), _ptr_array(xs), _ptr_array(ys), int(n), _ptr(workspace), _ptr(out), _vp(stream)),
+           "mg_cvec_dots_dev")
+
+
+def cvec_scale(a, x, y, n, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_cvec_scale_dev_CFP64(_cpair(a), _ptr(x), _ptr(y), int(n), _vp(stream)), "mg_cvec_scale_dev")
+
+
+def cvec_bicg_p(beta, omega, r, v, p, n, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_cvec_bicg_p_dev_CFP64(_cpair(beta), _cpair(omega), _ptr(r), _ptr(v), _ptr(p), int(n), _vp(stream)), "mg_cvec_bicg_p_dev")
+
+
+def cvec_bicg_s(alpha, v, r, n, workspace, out, stream=0):
+    lib = load_library()
+    _check(lib, lib.mg_cvec_bicg_s_dev_CFP64(_cpair(alpha), _ptr(v), _ptr(r), int(n), _ptr(workspace), _ptr(out), _vp(stream)), "mg_cvec_bicg_s_dev")
+
+
+def cvec_bicg_ts(t, s, n, workspace, out, stream=0):
+    """out = (re, im of dot(t, s), dot(t, t))."""
+    lib = load_library()
+    _check(lib, lib.mg_cvec_bicg_ts_dev_CFP64(_ptr(t), _ptr(s), int(n), _ptr(workspace), _ptr(out), _vp(stream)), "mg_cvec_bicg_ts_dev")
+
+
+def cvec_bicg_xr(alpha, omega, phat, shat, t, rtld, x, r, n, workspace, out, stream=0):
+    """x += alpha phat + omega shat ; r -= omega t ; out = (||r||^2, re, im of dot(rtld, r))."""
+    lib = load_library()
+    _check(lib, lib.mg_cvec_bicg_xr_dev_CFP64(_cpair(alpha), _cpair(omega), _ptr(phat), _ptr(shat), _ptr(t), _ptr(rtld), _ptr(x), _ptr(r),
+                                              int(n), _ptr(workspace), _ptr(out), _vp(stream)), "mg_cvec_bicg_xr_dev")
+
+
+def cvec_gs_update(h, vs, w, n, workspace, out=None, stream=0):
+    """w -= sum_j h[j] vs[j] (complex h, one vs[j] after the other); out (optional, device) = ||w||^2."""
+    lib = load_library()
+    hh = np.ascontiguousarray(h, dtype=np.complex128)
+    _check(lib, lib.mg_cvec_gs_update_dev_CFP64(len(vs), _c128(hh), _ptr_array(vs), _ptr(w), int(n), _ptr(workspace),
+                                                _ptr(out) if out is not None else None, _vp(stream)), "mg_cvec_gs_update_dev")

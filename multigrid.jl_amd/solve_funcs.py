@@ -15,8 +15,8 @@ from .mgsetup import adjustMemoryForNumRHS
 
 def _real_only(param: MGparam, what: str):
     if is_complex(param):
-        raise NotImplementedError(f"{what}: the device Krylov drivers serve VAL=Float64; for a ComplexF64 hierarchy precondition "
-                                  "a Krylov method with getMultigridPreconditioner")
+        raise NotImplementedError(f"{what}: this driver serves VAL=Float64; a ComplexF64 hierarchy takes solveBiCGSTAB_MG_CFP64 / "
+                                  "solveGMRES_MG_CFP64 (or precondition a Krylov method of your own with getMultigridPreconditioner)")
 
 
 def _ncols(b):
@@ -125,6 +125,52 @@ def solveGMRES_MG(A, param: MGparam, b: np.ndarray, x0: np.ndarray, flexible: bo
     param.resvec = resvec
     param.flag = flag
     return x, param, it, resvec
+
+
+def _complex_krylov_device(A, param: MGparam, b, x0, what: str):
+    """What the two _CFP64 functions share: the checks, the upload of the hierarchy and - when it is not the object uploaded
+    last - of the system operator A (None or ``param.As[0]`` itself: the hierarchy's own fine level)."""
+    if not is_complex(param):
+        raise TypeError(f"{what} serves VAL=ComplexF64 hierarchies; a Float64 hierarchy goes to {what[:-len('_CFP64')]}")
+    if _ncols(b) != 1 or _ncols(x0) != 1:
+        raise NotImplementedError(f"{what}: one right-hand side (blocks of right-hand sides are not served for complex values)")
+    adjustMemoryForNumRHS(param, 1)
+    dev = to_device(param)
+    if A is not None and param.As and A is param.As[0]:
+        A = None
+    if A is not dev.krylov_operator:          # recorded by set_krylov_operator itself: a direct call to it is seen here
+        dev.set_krylov_operator(A)
+    return dev, b.reshape(-1) if b.ndim == 2 else b, x0.reshape(-1) if x0.ndim == 2 else x0
+
+
+def solveBiCGSTAB_MG_CFP64(A, param: MGparam, b: np.ndarray, x0: np.ndarray, verbose: bool = False):
+    """``(x, param, iter, nprec) = solveBiCGSTAB_MG(Afun,param,b,x0,verbose)`` (SolveFuncs.jl:87-101) for VAL = ComplexF64 on the
+    device: KrylovMethods.bicgstb on the system operator ``A`` - the APPLIED operator, the convention of ``param.As``: a scipy
+    sparse matrix, complex or real; None or ``param.As[0]`` for the hierarchy's own fine level - with one cycle of ``param``'s
+    hierarchy (typically built on a damped copy of A) as M1.  x0 is updated in place; one right-hand side."""
+    dev, bv, xv = _complex_krylov_device(A, param, b, x0, "solveBiCGSTAB_MG_CFP64")
+    _, flag, it, resvec = dev.bicgstab(bv, xv, param.relativeTol, param.maxOuterIter)
+    param.resvec = resvec
+    param.flag = flag
+    if verbose:
+        for k, r in enumerate(resvec):
+            print(f"{k:3d}\t{r:1.2e}")
+    nprec = 2 * it + (flag == -3)                                   # SolveFuncs.jl:99 as written
+    return x0, param, it, nprec
+
+
+def solveGMRES_MG_CFP64(A, param: MGparam, b: np.ndarray, x0: np.ndarray, flexible: bool, inner: int, verbose: bool = False):
+    """``(x, param, iter, resvec) = solveGMRES_MG(Afun,param,b,x0,flexible,inner,verbose)`` (SolveFuncs.jl:119-133) for
+    VAL = ComplexF64 on the device: KrylovMethods.fgmres(inner) on the system operator ``A`` (as for solveBiCGSTAB_MG_CFP64)
+    with one cycle as preconditioner; always the flexible variant, as solveGMRES_MG.  x0 is updated in place."""
+    dev, bv, xv = _complex_krylov_device(A, param, b, x0, "solveGMRES_MG_CFP64")
+    _, flag, it, resvec = dev.fgmres(bv, xv, inner, param.relativeTol, param.maxOuterIter)
+    param.resvec = resvec
+    param.flag = flag
+    if verbose:
+        for k, r in enumerate(resvec):
+            print(f"{k + 1:3d}\t{r:1.2e}")
+    return x0, param, it, resvec
 
 
 _WHICH = {"A": MG_OP_A, "P": MG_OP_P, "R": MG_OP_R}

@@ -15,10 +15,10 @@ from typing import Any
 import numpy as np
 import scipy.sparse as sp
 
-from .mgdef import MGparam, clear_, copySolver as _copy_param, hierarchyExists
+from .mgdef import MGparam, clear_, copySolver as _copy_param, hierarchyExists, is_complex
 from .mgsetup import MGsetup, transposeHierarchy
 from .sa_amg import SA_AMGsetup
-from .solve_funcs import solveBiCGSTAB_MG, solveCG_MG, solveGMRES_MG, solveMG
+from .solve_funcs import solveBiCGSTAB_MG, solveBiCGSTAB_MG_CFP64, solveCG_MG, solveGMRES_MG, solveGMRES_MG_CFP64, solveMG
 
 
 @dataclass
@@ -86,7 +86,12 @@ def solveLinearSystem_(A, B: np.ndarray, X: np.ndarray, param: MGsolver, doTrans
         param.timeSetup += time.perf_counter() - t0
     t0 = time.perf_counter()
     Bf = np.asfortranarray(B)
-    if param.Krylov == "BiCGSTAB":
+    cplx = is_complex(param.MG)          # ComplexF64: the device drivers of their own, on the hierarchy's fine level
+    if param.Krylov == "BiCGSTAB" and cplx:
+        _, _, num_iter, _ = solveBiCGSTAB_MG_CFP64(param.MG.As[0], param.MG, Bf, Xv, verbose)
+    elif param.Krylov == "GMRES" and cplx and param.kind != "SA":
+        _, _, num_iter, _ = solveGMRES_MG_CFP64(param.MG.As[0], param.MG, Bf, Xv, True, 5, verbose)   # MGWrapper.jl:69-71
+    elif param.Krylov == "BiCGSTAB":
         _, _, num_iter, _ = solveBiCGSTAB_MG(param.MG.As[0], param.MG, Bf, Xv, verbose)
     elif param.Krylov == "PCG":
         _, _, num_iter = solveCG_MG(param.MG.As[0], param.MG, Bf, Xv, verbose)
