@@ -561,6 +561,31 @@ int mg_dd_apply_dev_FP64(mg_dd* dd, const double* b_dev, double* x_dev, long lon
 int mg_dd_apply_CFP64(mg_dd* dd, const double* b, double* x, long long n, long long niter, long long doTranspose);
 int mg_dd_apply_dev_CFP64(mg_dd* dd, const double* b_dev, double* x_dev, long long n, long long niter,
                           long long doTranspose);
+/* One sweep from x = 0 (getDDpreconditioner, DomainDecomposition.jl:136-146; the coarsest solve of a cycle, MGcycle.jl:63-64):
+ * x is output only and need not be initialised - it is zero-filled on the stream, then swept: the result is that of
+ * mg_dd_apply* with niter = 1 from a zero-filled x.  (A first colour that skips its residual rows was measured and is not
+ * faster: profiles/coarse_solver.md.)
+ * Arguments are validated as for mg_dd_apply*.  (A family of its own, mg_dd0_*: the set of mg_dd_* names is pinned by
+ * tests/test_dd_host.py, as the _CF64 set is by tests/test_parlu_complex_host.py.) */
+int mg_dd0_apply_FP64(mg_dd* dd, const double* b, double* x, long long n, long long doTranspose);
+int mg_dd0_apply_CFP64(mg_dd* dd, const double* b, double* x, long long n, long long doTranspose);
+int mg_dd0_apply_dev_FP64(mg_dd* dd, const double* b_dev, double* x_dev, long long n, long long doTranspose);
+int mg_dd0_apply_dev_CFP64(mg_dd* dd, const double* b_dev, double* x_dev, long long n, long long doTranspose);
+/* The coarsest solve of a hierarchy by a solver object (param.LU a DomainDecompositionParam: MGsetup.jl:323-326,
+ * MGcycle.jl:140-143): one sweep of a finalized handle, from zero inside a cycle, from the caller's x on a hierarchy of one
+ * level (MGcycle.jl:13-18), with doTranspose = 0 in the sub-domain solves, enqueued on the hierarchy's stream without a host
+ * synchronisation.  The handle's value type must be the hierarchy's (MG_ERR_STATE otherwise); its order must be the coarsest
+ * level's (mg_finalize: MG_ERR_INVALID).  The hierarchy BORROWS the handle: mg_dd_destroy of an attached handle fails with
+ * MG_ERR_STATE and leaves both usable; mg_destroy, another mg_set_coarse_* call or dd == NULL detach it (dd == NULL leaves
+ * the coarsest solve unset).  Stand-alone mg_dd_apply* calls on an attached handle stay legal: they are ordered behind the
+ * work the hierarchy has enqueued.  Such a hierarchy's sub-cycles are not captured into HIP graphs.  Refused with
+ * MG_ERR_UNSUPPORTED: more than one right-hand side (mg_set_nrhs, mg_finalize), mg_ghost_attach, mg_dist_set_tail_INT64,
+ * mg_transpose_hierarchy. */
+int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* dd);
+/* Which coarsest solve a hierarchy of either value type runs.  info[0]: 0 dense inverse, 1 sparse LU in one workgroup, 2 sparse
+ * LU chip-wide (per-level launches and a dense trailing inverse), 3 GMRES, 4 Schwarz sweep; info[1]: its order; info[2]:
+ * kernel launches per solve (GMRES: 0 - it depends on the right-hand side).  MG_ERR_STATE when none is set. */
+int mg_coarse_form(mg_hierarchy* h, long long* info);
 /* info[0..6): value type (0 Float64, 1 ComplexF64); sub-domains; colours present; colours run batched; colours run in
  * sequence; kernel launches of one sweep (doTranspose = 0; a chip-wide member counts one launch per level it launches). */
 int mg_dd_info(mg_dd* dd, long long* info);
@@ -787,6 +812,8 @@ int mg_set_operator_CF64_INT64(mg_hierarchy* h, long long level, long long which
 int mg_set_relax_CF64(mg_hierarchy* h, long long level, const double* d, long long n, long long relaxPre,
                       long long relaxPost);
 int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double* Ainv_colmajor);
+/* Factors of at least lu_multi_min_rows rows (the option of the real hierarchy) run chip-wide, as mg_lu_*_CFP64 applies them,
+ * on the hierarchy's stream; smaller ones in one workgroup (mg_coarse_form tells which). */
 int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* Lptr, const long long* Lcol,
                                 const double* Lval, const long long* Uptr, const long long* Ucol,
                                 const double* Uval, const long long* p, const long long* q);

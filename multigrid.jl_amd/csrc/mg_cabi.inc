@@ -199,6 +199,7 @@ int mg_destroy(mg_hierarchy* h) {
   graphs_clear(h);
   (void)hipSetDevice(h->device);
   if (h->play->stream) (void)spin_sync(h->play->stream);
+  dd_detach(h);   // (a borrowed Schwarz handle stays its owner's)
   if (h->ghost) { gh_release(h->ghost); h->ghost = nullptr; }
   if (h->cx) { cx_destroy(h->cx); h->cx = nullptr; }
   prof_collect(h);
@@ -393,6 +394,7 @@ int mg_set_coarse_dense_inverse_FP64(mg_hierarchy* h, long long n, const double*
     for (long long i = 0; i < n; ++i) rm[(size_t)i * n + j] = Ainv[(size_t)j * n + i];
   MG_TRY(h->Ainv.alloc(rm.size()));
   HIP_TRY(hipMemcpy(h->Ainv.p, rm.data(), rm.size() * sizeof(double), hipMemcpyHostToDevice));
+  dd_detach(h);
   h->n_coarse = n;
   h->coarse_set = true;
   h->coarse_lu = false;
@@ -502,6 +504,7 @@ int mg_set_coarse_lu_FP64_INT64(mg_hierarchy* h, long long n, const long long* L
       std::fprintf(stderr, "[mgvcycle] coarse LU n=%lld: dense trailing block %d, L %zu levels ahead of it (%d in all), U %zu behind it (%d)\n",
                    n, M, h->luLlvl_h.size() - 1, h->nLlvl, h->luUlvl_h.size() - 1, h->nUlvl);
   }
+  dd_detach(h);
   h->n_coarse = n;
   h->coarse_set = true;
   h->coarse_lu = true;
@@ -522,6 +525,7 @@ int mg_set_coarse_gmres_FP64(mg_hierarchy* h, long long n, const double* d) {
   (void)hipSetDevice(h->device);
   MG_TRY(h->coarse_d.alloc((size_t)n));
   HIP_TRY(hipMemcpy(h->coarse_d.p, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  dd_detach(h);
   h->n_coarse = n;
   h->coarse_set = true;
   h->coarse_gmres = true;
@@ -570,6 +574,8 @@ int mg_finalize(mg_hierarchy* h) {
   if (!h->coarse_set) return fail(MG_ERR_STATE, "the coarsest solve was not set");
   if (h->n_coarse != h->lev[nl - 1].n)
     return fail(MG_ERR_INVALID, "coarse inverse order %lld != coarsest level size %lld", h->n_coarse, h->lev[nl - 1].n);
+  if (h->coarse_dd && h->nrhs != 1)
+    return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%lld): the reference's sweep indexes b[Idxs]", h->nrhs);
   for (int l = 0; l < nl - 1; ++l) MG_TRY(derive_class_d(h->lev[(size_t)l]));
   MG_TRY(alloc_scratch(h));
 
@@ -584,6 +590,8 @@ int mg_set_nrhs(mg_hierarchy* h, long long nrhs) {
   if (nrhs < 1) return fail(MG_ERR_INVALID, "nrhs must be >= 1");
   if (h->cx && nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
   if (nrhs == h->nrhs) return MG_OK;
+  if (h->coarse_dd && nrhs != 1)
+    return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%lld): the reference's sweep indexes b[Idxs]", nrhs);
   if (h->ghost && nrhs > 24) return fail(MG_ERR_UNSUPPORTED, "ghost-layer form: blocks of up to 24 columns (column-wise solve)");
   (void)hipSetDevice(h->device);
   h->nrhs = nrhs;
@@ -800,6 +808,7 @@ int mg_transpose_hierarchy(mg_hierarchy* h) {
   MG_TRY(need_finalized(h));
   if (h->ghost) return fail(MG_ERR_UNSUPPORTED, "a rank's part of a sharded hierarchy is transposed on the host (every rank re-uploads its part)");
   if (h->coarse_lu) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is held as sparse factors: re-upload the transposed hierarchy");
+  if (h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is a Schwarz sweep (mg_set_coarse_dd): set the transposed hierarchy up again");
   (void)hipSetDevice(h->device);
   graphs_clear(h);
   HIP_TRY(spin_sync(h->play->stream));
@@ -2124,6 +2133,7 @@ int mg_ghost_attach(mg_hierarchy* h, long long rank, long long world, long long 
     return fail(MG_ERR_INVALID, "bad rank/world/levels (%lld/%lld, %lld sharded of %lld)", rank, world, nlevels_sharded, h->nlevels);
   if (h->coarse_gmres)
     return fail(MG_ERR_UNSUPPORTED, "the ghost-layer form needs a direct coarsest solve (coarseSolveType GMRES: mg_dist_*)");
+  if (h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve (mg_set_coarse_dd) is not served on sharded hierarchies");
   (void)hipSetDevice(h->device);
   graphs_clear(h);
   if (h->ghost) { gh_release(h->ghost); h->ghost = nullptr; }

@@ -39,6 +39,7 @@ struct CxState {
   std::vector<CxLevel> lev;
   bool finalized = false;
   bool coarse_set = false, coarse_lu = false;
+  struct CxLu* coarse_multi = nullptr;   // sparse factors of >= lu_multi_min_rows rows: the chip-wide form of the factor applier
   long long n_coarse = 0;
   DevBuf<double> Ainv;         // row-major n_c x n_c complex
   DevBuf<int> luLptr, luLcol, luUptr, luUcol, luP, luQ, luLorder, luLlvl, luUorder, luUlvl;
@@ -94,7 +95,11 @@ struct CxLu {
 
 namespace {
 
-void cx_destroy(CxState* s) { delete s; }
+void cxlu_destroy(CxLu* S);
+void cx_destroy(CxState* s) {
+  if (s->coarse_multi) cxlu_destroy(s->coarse_multi);
+  delete s;
+}
 
 inline cx_t* cxp(DevBuf<double>& b) { return reinterpret_cast<cx_t*>(b.p); }
 inline unsigned cx_grid(long long n) { return (unsigned)((n + mgk::BLK - 1) / mgk::BLK); }
@@ -235,10 +240,15 @@ int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const cx_t* b, const cx
   return MG_OK;
 }
 
-// z = param.LU \ b (MGcycle.jl:177): explicit inverse, or x[q] = U \ (L \ b[p]) by the level-scheduled sptrsv_lu
-int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x) {
+int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr, const hipStream_t* on);
+
+// z = param.LU \ b (MGcycle.jl:177): explicit inverse, or x[q] = U \ (L \ b[p]) by the level-scheduled sptrsv_lu (one workgroup;
+// chip-wide for factors of >= lu_multi_min_rows rows), or one Schwarz sweep (MGcycle.jl:140-143; xzero: x need not be read)
+int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true) {
   CxState& S = *h->cx;
   const long long n = S.n_coarse;
+  if (h->coarse_dd) return dd_coarse(h, reinterpret_cast<const double*>(b), reinterpret_cast<double*>(x), xzero);
+  if (S.coarse_multi) return cxlu_solve_dev(S.coarse_multi, *S.coarse_multi->fwd, b, x, 1, &h->play->stream);
   if (S.coarse_lu) {
     mgk::LuDevT<cx_t> F;
     F.n = (int)n;
@@ -278,7 +288,7 @@ int cx_cycle(mg_hierarchy* h, int l, const cx_t* b, int& xi, bool xzero, char ct
   CxState& S = *h->cx;
   const int nl = (int)h->nlevels;
   CxLevel& L = S.lev[(size_t)l];
-  if (l == nl - 1) return cx_coarse(h, b, cxp(L.x[xi]));                               // l.13-18
+  if (l == nl - 1) return cx_coarse(h, b, cxp(L.x[xi]), xzero);                               // l.13-18
   MG_TRY(cx_relax(h, L, b, xi, xzero, L.npre));                                         // l.26-31, 54
   MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxp(L.x[xi]), cxp(L.r), b, nullptr, nullptr));     // l.58-60
   CxLevel& C = S.lev[(size_t)l + 1];
@@ -349,7 +359,7 @@ int cx_finalize(mg_hierarchy* h) {
   const size_t n0 = 2 * (size_t)S.lev[0].n;
   if (S.stage_b.n != n0) MG_TRY(S.stage_b.alloc(n0));
   if (S.partial.n < maxblocks) MG_TRY(S.partial.alloc(maxblocks));
-  if (S.coarse_lu && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
+  if (S.coarse_lu && !S.coarse_multi && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
   S.finalized = true;
   return MG_OK;
 }
@@ -503,8 +513,10 @@ int cxlu_set(CxLu* S, bool adjoint, CxLuSet** out) {
   return MG_OK;
 }
 
-// x = A \ b (or A^H \ b) on device vectors, row-major [n][nrhs]; enqueued on S->stream, no synchronisation
-int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr) {
+// x = A \ b (or A^H \ b) on device vectors, row-major [n][nrhs]; enqueued on S->stream (on: on *on, a borrower's stream), no
+// synchronisation
+int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr, const hipStream_t* on = nullptr) {
+  const hipStream_t st = on ? *on : S->stream;
   const long long n = S->n;
   const size_t wlen = 2 * (size_t)n * (size_t)nr, tlen = 2 * (size_t)std::max(G.M, 1) * (size_t)nr;
   if (S->work.n < wlen) MG_TRY(S->work.alloc(wlen));
@@ -518,7 +530,7 @@ int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr) {
   F.Uorder = G.Uorder.p; F.Ulvl = G.Ulvl.p; F.nUlvl = G.nUlvl;
   cx_t* y = cxp(S->work);
   if (!G.multi) {
-    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, S->stream, F, b, x, y, nr);
+    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, st, F, b, x, y, nr);
     HIP_TRY(hipGetLastError());
     return MG_OK;
   }
@@ -529,24 +541,24 @@ int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr) {
   const int nLl = (int)G.Llvl_h.size() - 1, nUl = (int)G.Ulvl_h.size() - 1;
   for (int l = 0; l < nLl; ++l) {
     const int t0 = G.Llvl_h[(size_t)l], t1 = G.Llvl_h[(size_t)l + 1];
-    hipLaunchKernelGGL(mgk::cx_sptrsv_level<true>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, S->stream, F,
+    hipLaunchKernelGGL(mgk::cx_sptrsv_level<true>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, st, F,
                        reinterpret_cast<const int4*>(G.Lslot.p), t0, t1, b, y, nr);
   }
   if (M > 0) {
-    hipLaunchKernelGGL(mgk::cx_sptrsv_tail_rhs, wave_blocks(M), dim3(mgk::BLK), 0, S->stream, F, n0, b, y, t, nr);
-    hipLaunchKernelGGL(mgk::cx_tri_apply<true>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, S->stream,
+    hipLaunchKernelGGL(mgk::cx_sptrsv_tail_rhs, wave_blocks(M), dim3(mgk::BLK), 0, st, F, n0, b, y, t, nr);
+    hipLaunchKernelGGL(mgk::cx_tri_apply<true>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, st,
                        reinterpret_cast<const cx_t*>(G.invL.p), ld, t, y + (size_t)n0 * (size_t)nr, M, nr);
     // y = U \ y: the trailing block first, then the levels behind it
-    HIP_TRY(hipMemcpyAsync(t, y + (size_t)n0 * (size_t)nr, (size_t)M * (size_t)nr * sizeof(cx_t), hipMemcpyDeviceToDevice, S->stream));
-    hipLaunchKernelGGL(mgk::cx_tri_apply<false>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, S->stream,
+    HIP_TRY(hipMemcpyAsync(t, y + (size_t)n0 * (size_t)nr, (size_t)M * (size_t)nr * sizeof(cx_t), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(mgk::cx_tri_apply<false>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, st,
                        reinterpret_cast<const cx_t*>(G.invU.p), ld, t, y + (size_t)n0 * (size_t)nr, M, nr);
   }
   for (int l = 0; l < nUl; ++l) {
     const int t0 = G.Ulvl_h[(size_t)l], t1 = G.Ulvl_h[(size_t)l + 1];
-    hipLaunchKernelGGL(mgk::cx_sptrsv_level<false>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, S->stream, F,
+    hipLaunchKernelGGL(mgk::cx_sptrsv_level<false>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, st, F,
                        reinterpret_cast<const int4*>(G.Uslot.p), t0, t1, b, y, nr);
   }
-  hipLaunchKernelGGL(mgk::cx_sptrsv_scatter, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, G.Q.p, y, x, (int)n, nr);
+  hipLaunchKernelGGL(mgk::cx_sptrsv_scatter, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, st, G.Q.p, y, x, (int)n, nr);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -576,7 +588,8 @@ int cxlu_solve_host(CxLu* S, CxLuSet& G, const double* b, double* x, int nr) {
 
 // the create step behind mg_lu_create_CFP64_INT64: arguments already checked for null / 1-based pointers
 int cxlu_create(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const double* Lval, const long long* Uptr,
-                const long long* Ucol, const double* Uval, const long long* p, const long long* q, CxLu** out) {
+                const long long* Ucol, const double* Uval, const long long* p, const long long* q, CxLu** out,
+                const Options* opt = nullptr) {
   if (n >= (1LL << 31) - 1 || Lptr[n] - 1 >= (1LL << 31) || Uptr[n] - 1 >= (1LL << 31))
     return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
   int ndev = 0;
@@ -585,7 +598,7 @@ int cxlu_create(long long device_id, long long n, const long long* Lptr, const l
   if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
   HIP_TRY(hipSetDevice((int)device_id));
   CxLu* S = new CxLu();
-  S->opt = Options::from_env();   // the only place the environment is read for this handle
+  S->opt = opt ? *opt : Options::from_env();   // the only place the environment is read for this handle (opt: a hierarchy's own)
   S->device = (int)device_id;
   S->n = n;
   S->Lptr.assign(Lptr, Lptr + n + 1);
@@ -670,6 +683,8 @@ int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double*
     }
   MG_TRY(S.Ainv.alloc(rm.size()));
   HIP_TRY(hipMemcpy(S.Ainv.p, rm.data(), rm.size() * sizeof(double), hipMemcpyHostToDevice));
+  dd_detach(h);
+  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
   S.n_coarse = n;
   S.coarse_set = true;
   S.coarse_lu = false;
@@ -688,6 +703,30 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
   if (Lptr[0] != 1 || Uptr[0] != 1) return fail(MG_ERR_INVALID, "row pointers must be 1-based");
   (void)hipSetDevice(h->device);
   CxState& S = *h->cx;
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  if (n >= h->opt.lu_multi_min_rows) {
+    // the chip-wide form, as the real hierarchy selects it (mg_set_coarse_lu_FP64_INT64): per-level launches and a dense trailing
+    // inverse, held by a factor applier of the hierarchy's own and enqueued on the hierarchy's stream (cx_coarse)
+    CxLu* F = nullptr;
+    MG_TRY(cxlu_create(h->device, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, &F, &h->opt));
+    const size_t wlen = 2 * (size_t)n, tlen = 2 * (size_t)std::max(F->fwd->M, 1);   // (no allocation inside the cycle)
+    if (F->work.alloc(wlen) != MG_OK || F->tail.alloc(tlen) != MG_OK) {
+      cxlu_destroy(F);
+      return fail(MG_ERR_HIP, "allocation of the coarsest solve's work vectors failed");
+    }
+    if (S.coarse_multi) cxlu_destroy(S.coarse_multi);
+    S.coarse_multi = F;
+    for (DevBuf<int>* d : {&S.luLptr, &S.luLcol, &S.luUptr, &S.luUcol, &S.luP, &S.luQ, &S.luLorder, &S.luLlvl, &S.luUorder, &S.luUlvl}) d->release();
+    S.luLval.release(); S.luUval.release(); S.luWork.release();
+    dd_detach(h);
+    S.n_coarse = n;
+    S.coarse_set = true;
+    S.coarse_lu = true;
+    S.Ainv.release();
+    S.finalized = false;
+    return MG_OK;
+  }
+  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
   const size_t N = (size_t)n;
   std::vector<int> LP, LC, LO, LL, UP, UC, UO, UL, pp(N), qq(N);
   MG_TRY(lu_convert(n, Lptr, Lcol, true, LP, LC, LO, LL));
@@ -711,6 +750,7 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
   HIP_TRY(hipMemcpy(S.luUval.p, Uval, 2 * UC.size() * sizeof(double), hipMemcpyHostToDevice));
   S.nLlvl = (int)LL.size() - 1;
   S.nUlvl = (int)UL.size() - 1;
+  dd_detach(h);
   S.n_coarse = n;
   S.coarse_set = true;
   S.coarse_lu = true;

@@ -18,6 +18,8 @@ struct mg_dd {
   bool finalized = false;
   hipStream_t stream = nullptr;
   hipEvent_t ev_mine = nullptr, ev_theirs = nullptr;   // ordering against the stream of a member's own applier
+  mg_hierarchy* owner = nullptr;   // mg_set_coarse_dd: the hierarchy that borrows this handle as its coarsest solve
+  hipEvent_t ev_owner = nullptr;   // ... and the event that orders a stand-alone sweep behind that hierarchy's enqueued work
   DevBuf<int> rowptr, col, idx, members;
   DevBuf<double> val, r, y, w, stage_b, stage_x;
   struct Sub {
@@ -145,6 +147,7 @@ int dd_create(bool cx, long long device_id, long long n, const long long* rowptr
     HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&d->ev_mine, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d->ev_theirs, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&d->ev_owner, hipEventDisableTiming));
     return MG_OK;
   };
   const int rc = up();
@@ -182,6 +185,7 @@ int dd_set_factor(bool cx, mg_dd* d, long long ic, long long n_i, const long lon
     if (p[i] < 1 || p[i] > n_i || q[i] < 1 || q[i] > n_i) return fail(MG_ERR_INVALID, "permutation entry out of range");
   (void)hipSetDevice(d->device);
   if (d->stream) (void)spin_sync(d->stream);
+  if (d->owner && d->owner->play->stream) (void)spin_sync(d->owner->play->stream);   // (a borrowing hierarchy's sweeps read the sets)
   dd_drop_sets(d);   // (a factor replaced after mg_dd_finalize: finalize again)
   const size_t vw = cx ? 2 : 1;
   const size_t ln = (size_t)(Lptr[n_i] - 1), un = (size_t)(Uptr[n_i] - 1);
@@ -318,8 +322,12 @@ int dd_set(mg_dd* d, bool adjoint, mg_dd::Set** out, const mgk::DdSub** desc_dev
   return MG_OK;
 }
 
+// niter sweeps enqueued on `stream` (the handle's own, or the stream a borrowing hierarchy plays on).  from_zero: x is zero-filled
+// on the stream first, so the caller's x is never read.  (A first colour that takes r = b[I] instead of (b - A x)[I] was measured
+// and is not faster: profiles/coarse_solver.md, the variant in profiles/coarse_solver_from_zero_variant.patch.)
 template <typename T>
-int dd_sweeps(mg_dd* d, mg_dd::Set& G, const mgk::DdSub* desc_dev, const T* b, T* x, long long niter, bool adjoint) {
+int dd_sweeps(mg_dd* d, hipStream_t stream, mg_dd::Set& G, const mgk::DdSub* desc_dev, const T* b, T* x, long long niter, bool adjoint,
+              bool from_zero) {
   mgk::DdDevT<T> D;
   D.rowptr = d->rowptr.p; D.col = d->col.p; D.val = reinterpret_cast<const T*>(d->val.p);
   D.idx = d->idx.p; D.sub = desc_dev; D.members = d->members.p;
@@ -328,10 +336,11 @@ int dd_sweeps(mg_dd* d, mg_dd::Set& G, const mgk::DdSub* desc_dev, const T* b, T
   D.p = G.P.p; D.q = G.Q.p;
   D.r = reinterpret_cast<T*>(d->r.p); D.y = reinterpret_cast<T*>(d->y.p);
   T* w = reinterpret_cast<T*>(d->w.p);
+  if (from_zero) HIP_TRY(hipMemsetAsync(x, 0, (size_t)d->n * sizeof(T), stream));
   for (long long it = 0; it < niter; ++it)
     for (const mg_dd::Colour& c : d->colours) {
       if (c.batched) {
-        hipLaunchKernelGGL(mgk::dd_color_sweep<T>, dim3((unsigned)c.count), dim3(1024), 0, d->stream, D, c.m0, b, x);
+        hipLaunchKernelGGL(mgk::dd_color_sweep<T>, dim3((unsigned)c.count), dim3(1024), 0, stream, D, c.m0, b, x);
         continue;
       }
       for (int m = 0; m < c.count; ++m) {
@@ -343,7 +352,7 @@ int dd_sweeps(mg_dd* d, mg_dd::Set& G, const mgk::DdSub* desc_dev, const T* b, T
         T* r = D.r + e.vec0;
         T* t = D.y + e.vec0;
         hipLaunchKernelGGL(mgk::dd_gather_residual<T>, dim3((unsigned)(((long long)n_i * 8 + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0,
-                           d->stream, D.rowptr, D.col, D.val, I, n_i, b, x, r);
+                           stream, D.rowptr, D.col, D.val, I, n_i, b, x, r);
         if (!S.big) {
           mgk::LuDevT<T> F;
           F.n = n_i;
@@ -352,11 +361,11 @@ int dd_sweeps(mg_dd* d, mg_dd::Set& G, const mgk::DdSub* desc_dev, const T* b, T
           F.p = D.p + e.vec0; F.q = D.q + e.vec0;
           F.Lorder = D.Lorder + e.vec0; F.Llvl = D.Llvl + e.Llvl0; F.nLlvl = e.nLlvl;
           F.Uorder = D.Uorder + e.vec0; F.Ulvl = D.Ulvl + e.Ulvl0; F.nUlvl = e.nUlvl;
-          hipLaunchKernelGGL(mgk::sptrsv_lu<T>, dim3(1), dim3(1024), 0, d->stream, F, r, t, w, 1);
+          hipLaunchKernelGGL(mgk::sptrsv_lu<T>, dim3(1), dim3(1024), 0, stream, F, r, t, w, 1);
         } else {
           // the member's own applier enqueues on a stream of its own: order it behind the gather, and the scatter behind it
           hipStream_t theirs;
-          HIP_TRY(hipEventRecord(d->ev_mine, d->stream));
+          HIP_TRY(hipEventRecord(d->ev_mine, stream));
           if (S.big->cx) {
             CxLuSet* LS = nullptr;
             MG_TRY(cxlu_set(S.big->cx, adjoint, &LS));
@@ -372,9 +381,9 @@ int dd_sweeps(mg_dd* d, mg_dd::Set& G, const mgk::DdSub* desc_dev, const T* b, T
             MG_TRY(cycle_dev(h, reinterpret_cast<const double*>(r), reinterpret_cast<double*>(t), true));
           }
           HIP_TRY(hipEventRecord(d->ev_theirs, theirs));
-          HIP_TRY(hipStreamWaitEvent(d->stream, d->ev_theirs, 0));
+          HIP_TRY(hipStreamWaitEvent(stream, d->ev_theirs, 0));
         }
-        hipLaunchKernelGGL(mgk::dd_scatter_add<T>, dim3((unsigned)((n_i + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, d->stream, I,
+        hipLaunchKernelGGL(mgk::dd_scatter_add<T>, dim3((unsigned)((n_i + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, stream, I,
                            n_i, t, x);
       }
     }
@@ -395,34 +404,60 @@ int dd_args(bool cx, mg_dd* d, const double* b, const double* x, long long n, lo
   return MG_OK;
 }
 
-// niter sweeps on device vectors, enqueued on the handle's stream (no synchronisation)
-int dd_run(mg_dd* d, const double* b_dev, double* x_dev, long long niter, long long doTranspose) {
+// niter sweeps on device vectors, enqueued on `stream` (no synchronisation); from_zero: from x = 0, whatever x holds
+int dd_run(mg_dd* d, hipStream_t stream, const double* b_dev, double* x_dev, long long niter, long long doTranspose, bool from_zero = false) {
   mg_dd::Set* G = nullptr;
   const mgk::DdSub* desc_dev = nullptr;
   MG_TRY(dd_set(d, doTranspose != 0, &G, &desc_dev));
   if (d->cx)
-    return dd_sweeps<cx_t>(d, *G, desc_dev, reinterpret_cast<const cx_t*>(b_dev), reinterpret_cast<cx_t*>(x_dev), niter, doTranspose != 0);
-  return dd_sweeps<double>(d, *G, desc_dev, b_dev, x_dev, niter, doTranspose != 0);
+    return dd_sweeps<cx_t>(d, stream, *G, desc_dev, reinterpret_cast<const cx_t*>(b_dev), reinterpret_cast<cx_t*>(x_dev), niter,
+                           doTranspose != 0, from_zero);
+  return dd_sweeps<double>(d, stream, *G, desc_dev, b_dev, x_dev, niter, doTranspose != 0, from_zero);
+}
+
+// A stand-alone sweep on a handle that a hierarchy borrows shares the handle's scratch with that hierarchy's cycles: the
+// handle's stream waits for what the hierarchy has enqueued so far (the stand-alone entry points synchronise before they return,
+// so the hierarchy's next cycle is behind them)
+int dd_behind_owner(mg_dd* d) {
+  if (!d->owner) return MG_OK;
+  HIP_TRY(hipEventRecord(d->ev_owner, d->owner->play->stream));
+  HIP_TRY(hipStreamWaitEvent(d->stream, d->ev_owner, 0));
+  return MG_OK;
+}
+
+// the coarsest solve of a hierarchy (k_coarse / cx_coarse): one sweep with doTranspose = 0 on the stream being played - from
+// zero, or (one level only, MGcycle.jl:13-18) from the caller's x
+int dd_coarse(mg_hierarchy* h, const double* b, double* x, bool x_zero) {
+  if (!h->coarse_dd->finalized) return fail(MG_ERR_STATE, "the sweep handle of the coarsest solve is not finalized (mg_dd_finalize)");
+  return dd_run(h->coarse_dd, h->play->stream, b, x, 1, 0, x_zero);
+}
+void dd_detach(mg_hierarchy* h) {
+  if (!h->coarse_dd) return;
+  h->coarse_dd->owner = nullptr;
+  h->coarse_dd = nullptr;
 }
 
 int dd_apply_dev(bool cx, mg_dd* d, const double* b_dev, double* x_dev, long long n, long long niter, long long doTranspose,
-                 const char* name) {
+                 const char* name, bool from_zero = false) {
   MG_TRY(dd_args(cx, d, b_dev, x_dev, n, niter, name));
-  MG_TRY(dd_run(d, b_dev, x_dev, niter, doTranspose));
+  MG_TRY(dd_behind_owner(d));
+  MG_TRY(dd_run(d, d->stream, b_dev, x_dev, niter, doTranspose, from_zero));
   HIP_TRY(spin_sync(d->stream));
   return MG_OK;
 }
 
-int dd_apply_host(bool cx, mg_dd* d, const double* b, double* x, long long n, long long niter, long long doTranspose, const char* name) {
+int dd_apply_host(bool cx, mg_dd* d, const double* b, double* x, long long n, long long niter, long long doTranspose, const char* name,
+                  bool from_zero = false) {
   MG_TRY(dd_args(cx, d, b, x, n, niter, name));
   const size_t len = (cx ? 2 : 1) * (size_t)n;   // doubles
   if (d->stage_b.n != len) {
     MG_TRY(d->stage_b.alloc(len));
     MG_TRY(d->stage_x.alloc(len));
   }
+  MG_TRY(dd_behind_owner(d));
   HIP_TRY(hipMemcpyAsync(d->stage_b.p, b, len * sizeof(double), hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(d->stage_x.p, x, len * sizeof(double), hipMemcpyHostToDevice, d->stream));
-  MG_TRY(dd_run(d, d->stage_b.p, d->stage_x.p, niter, doTranspose));
+  if (!from_zero) HIP_TRY(hipMemcpyAsync(d->stage_x.p, x, len * sizeof(double), hipMemcpyHostToDevice, d->stream));
+  MG_TRY(dd_run(d, d->stream, d->stage_b.p, d->stage_x.p, niter, doTranspose, from_zero));
   HIP_TRY(hipMemcpyAsync(x, d->stage_x.p, len * sizeof(double), hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(spin_sync(d->stream));
   return MG_OK;
@@ -460,6 +495,7 @@ int mg_dd_finalize(mg_dd* d) {
     if (!d->sub[(size_t)s].set) return fail(MG_ERR_STATE, "sub-domain %lld has no factors (mg_dd_set_factor_*)", s + 1);
   (void)hipSetDevice(d->device);
   if (d->stream) (void)spin_sync(d->stream);
+  if (d->owner && d->owner->play->stream) (void)spin_sync(d->owner->play->stream);
   dd_drop_sets(d);
   long long wmax = 0;
   std::vector<int> owner((size_t)d->n, -1);
@@ -505,6 +541,100 @@ int mg_dd_apply_dev_CFP64(mg_dd* d, const double* b_dev, double* x_dev, long lon
   return dd_apply_dev(true, d, b_dev, x_dev, n, niter, doTranspose, "mg_dd_apply_dev_CFP64");
 }
 
+// One sweep from x = 0 (what getDDpreconditioner and the cycle's coarsest solve ask for): x is output only - it is zero-filled on
+// the stream, then swept.
+int mg_dd0_apply_FP64(mg_dd* d, const double* b, double* x, long long n, long long doTranspose) {
+  return dd_apply_host(false, d, b, x, n, 1, doTranspose, "mg_dd0_apply_FP64", true);
+}
+int mg_dd0_apply_CFP64(mg_dd* d, const double* b, double* x, long long n, long long doTranspose) {
+  return dd_apply_host(true, d, b, x, n, 1, doTranspose, "mg_dd0_apply_CFP64", true);
+}
+int mg_dd0_apply_dev_FP64(mg_dd* d, const double* b_dev, double* x_dev, long long n, long long doTranspose) {
+  return dd_apply_dev(false, d, b_dev, x_dev, n, 1, doTranspose, "mg_dd0_apply_dev_FP64", true);
+}
+int mg_dd0_apply_dev_CFP64(mg_dd* d, const double* b_dev, double* x_dev, long long n, long long doTranspose) {
+  return dd_apply_dev(true, d, b_dev, x_dev, n, 1, doTranspose, "mg_dd0_apply_dev_CFP64", true);
+}
+
+// The coarsest solve of a hierarchy by one sweep of a finalized handle (MGsetup.jl:323-326, MGcycle.jl:140-143).  The hierarchy
+// borrows the handle; dd == NULL detaches it and leaves the coarsest solve unset.
+int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* d) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  (void)hipSetDevice(h->device);
+  graphs_clear(h);
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  if (!d) {
+    const bool was = h->coarse_dd != nullptr;
+    dd_detach(h);
+    if (was) {
+      if (h->cx) { h->cx->coarse_set = false; h->cx->finalized = false; }
+      else { h->coarse_set = false; h->finalized = false; }
+    }
+    return MG_OK;
+  }
+  if (d->cx != (h->cx != nullptr))
+    return fail(MG_ERR_STATE, "mg_set_coarse_dd: a sweep handle of %s values on a hierarchy of %s values", d->cx ? "ComplexF64" : "Float64",
+                h->cx ? "ComplexF64" : "Float64");
+  if (!d->finalized) return fail(MG_ERR_STATE, "mg_set_coarse_dd before mg_dd_finalize");
+  if (d->owner && d->owner != h) return fail(MG_ERR_STATE, "the sweep handle is the coarsest solve of another hierarchy");
+  if (d->device != h->device) return fail(MG_ERR_INVALID, "the sweep handle lives on device %d, the hierarchy on device %d", d->device, h->device);
+  if (h->ghost) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve is not served on sharded hierarchies");
+  if (h->lu_only) return fail(MG_ERR_INVALID, "a factor applier's handle has no coarsest solve to replace");
+  dd_detach(h);
+  h->coarse_dd = d;
+  d->owner = h;
+  if (h->cx) {
+    CxState& S = *h->cx;
+    if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+    S.n_coarse = d->n;
+    S.coarse_set = true;
+    S.coarse_lu = false;
+    S.Ainv.release();
+    S.finalized = false;
+  } else {
+    h->n_coarse = d->n;
+    h->coarse_set = true;
+    h->coarse_lu = false;
+    h->coarse_gmres = false;
+    h->Ainv.release();
+    h->finalized = false;
+  }
+  return MG_OK;
+}
+
+// info[0]: the coarsest solve in use - 0 dense inverse, 1 sparse LU in one workgroup, 2 sparse LU chip-wide, 3 GMRES, 4 Schwarz
+// sweep; info[1]: its order; info[2]: kernel launches per solve (GMRES: 0, it depends on the right-hand side)
+int mg_coarse_form(mg_hierarchy* h, long long* info) {
+  if (!h || !info) return fail(MG_ERR_INVALID, "null argument");
+  const bool set = h->cx ? h->cx->coarse_set : h->coarse_set;
+  if (!set) return fail(MG_ERR_STATE, "the coarsest solve was not set");
+  info[1] = h->cx ? h->cx->n_coarse : h->n_coarse;
+  if (h->coarse_dd) {
+    long long f[6];
+    MG_TRY(mg_dd_info(h->coarse_dd, f));
+    info[0] = 4;
+    info[2] = f[5];
+  } else if (h->cx) {
+    const CxState& S = *h->cx;
+    info[0] = S.coarse_multi ? 2 : S.coarse_lu ? 1 : 0;
+    info[2] = 1;
+    if (S.coarse_multi) {
+      const CxLuSet& G = *S.coarse_multi->fwd;
+      info[2] = G.multi ? (long long)(G.Llvl_h.size() - 1) + (long long)(G.Ulvl_h.size() - 1) + (G.M > 0 ? 3 : 0) + 1 : 1;
+    }
+  } else if (h->coarse_gmres) {
+    info[0] = 3;
+    info[2] = 0;
+  } else if (h->coarse_lu) {
+    info[0] = h->lu_multi ? 2 : 1;
+    info[2] = h->lu_multi ? (long long)(h->luLlvl_h.size() - 1) + (long long)(h->luUlvl_h.size() - 1) + (h->luML > 0 ? 2 : 0) + (h->luMU > 0 ? 1 : 0) + 1 : 1;
+  } else {
+    info[0] = 0;
+    info[2] = 1;
+  }
+  return MG_OK;
+}
+
 // info[0..6): value type (0 Float64, 1 ComplexF64); sub-domains; colours present; colours run batched; colours run in
 // sequence; kernel launches of one sweep (doTranspose = 0; a chip-wide member counts its levels)
 int mg_dd_info(mg_dd* d, long long* info) {
@@ -537,13 +667,14 @@ int mg_dd_time_dev(mg_dd* d, const double* b_dev, double* x_dev, long long n, lo
                    double* ms) {
   if (!d || !ms || reps < 1 || warmup < 0) return fail(MG_ERR_INVALID, "bad argument");
   MG_TRY(dd_args(d->cx, d, b_dev, x_dev, n, 0, "mg_dd_time_dev"));
-  MG_TRY(dd_run(d, b_dev, x_dev, 0, doTranspose));   // the direction's set is built before the first sample
+  MG_TRY(dd_behind_owner(d));
+  MG_TRY(dd_run(d, d->stream, b_dev, x_dev, 0, doTranspose));   // the direction's set is built before the first sample
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = MG_OK;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventCreate failed");
   for (long long it = 0; it < warmup + reps && rc == MG_OK; ++it) {
     if (hipEventRecord(e0, d->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
-    if (rc == MG_OK) rc = dd_run(d, b_dev, x_dev, 1, doTranspose);
+    if (rc == MG_OK) rc = dd_run(d, d->stream, b_dev, x_dev, 1, doTranspose);
     if (rc == MG_OK) {
       float t = 0.f;
       if (hipEventRecord(e1, d->stream) != hipSuccess || spin_sync(d->stream) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)
@@ -558,11 +689,13 @@ int mg_dd_time_dev(mg_dd* d, const double* b_dev, double* x_dev, long long n, lo
 
 int mg_dd_destroy(mg_dd* d) {
   if (!d) return MG_OK;
+  if (d->owner) return fail(MG_ERR_STATE, "the sweep handle is the coarsest solve of a hierarchy: detach it first (mg_set_coarse_dd(h, NULL) or mg_destroy)");
   (void)hipSetDevice(d->device);
   if (d->stream) (void)spin_sync(d->stream);
   dd_drop_sets(d);
   if (d->ev_mine) (void)hipEventDestroy(d->ev_mine);
   if (d->ev_theirs) (void)hipEventDestroy(d->ev_theirs);
+  if (d->ev_owner) (void)hipEventDestroy(d->ev_owner);
   if (d->stream) (void)hipStreamDestroy(d->stream);
   for (DevBuf<int>* b : {&d->rowptr, &d->col, &d->idx, &d->members}) b->release();
   for (DevBuf<double>* b : {&d->val, &d->r, &d->y, &d->w, &d->stage_b, &d->stage_x}) b->release();

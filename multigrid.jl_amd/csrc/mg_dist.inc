@@ -581,6 +581,7 @@ int mg_dist_set_tail_INT64(mg_dist* h, mg_hierarchy* tail, long long n_tail, lon
   UploadFence upload_fence;
   if (!h || !tail || !gather_index || n_tail < 1 || max_tail < 1 || own_tail < 0 || own_tail > max_tail) return fail(MG_ERR_INVALID, "bad tail description");
   MG_CF64_UNSUPPORTED(tail);
+  if (tail->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "a hierarchy whose coarsest solve is a Schwarz sweep (mg_set_coarse_dd) is not served as the tail of a sharded one");
   (void)hipSetDevice(h->device);
   h->tail = tail;
   h->n_tail = n_tail;

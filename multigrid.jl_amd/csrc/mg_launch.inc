@@ -951,8 +951,16 @@ int fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBu
 int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBuf<double>* work, const double* B,
                       double* X, long long inner, double tol, long long maxIter, long long* iters, long long* flag_out,
                       double* resvec, long long* nres);
-int k_coarse(mg_hierarchy* h, int level, const double* b, double* x) {
+// (mg_dd.inc) the Schwarz sweep as coarsest solve, enqueued on the stream being played; giving a borrowed handle back
+int dd_coarse(mg_hierarchy* h, const double* b, double* x, bool x_zero);
+void dd_detach(mg_hierarchy* h);
+// x_zero: x holds zeros or need not be read (always so below a finer level, MGcycle.jl:63-64); only the Schwarz sweep reads x
+int k_coarse(mg_hierarchy* h, int level, const double* b, double* x, bool x_zero = true) {
   const long long n = h->n_coarse;
+  if (h->coarse_dd) {   // solveDDSerial(AT, b, x, LU, 1) (MGcycle.jl:140-143)
+    ProfScope ps(h, level, MG_K_COARSE, 0.0);
+    return dd_coarse(h, b, x, x_zero);
+  }
   if (h->coarse_gmres) {
     // coarseSolveType "GMRES" (MGcycle.jl:152-168): x = 0; one restart of FGMRES(10), tol 0.01, M = d .* v with
     // d = relaxParam ./ diag(A_c) (defineCoarsestAinv, MGsetup.jl:334)

@@ -146,7 +146,7 @@ int cycle_level(mg_hierarchy* h, int l, const double* b, double* xa, double* xb,
                 bool x1_given = false, bool pre_done = false) {
   const int nl = (int)h->nlevels;
   if (l == nl - 1) {  // solveCoarsest (MGcycle.jl:13-18,67-69,177): x = LU \ b
-    MG_TRY(k_coarse(h, l, b, xa));
+    MG_TRY(k_coarse(h, l, b, xa, x_zero));
     *result = xa;
     return MG_OK;
   }
@@ -407,9 +407,10 @@ void graphs_clear(mg_hierarchy* h) {
 // The levels below a few hundred thousand rows are launch-bound (8-14 us per kernel for microseconds of work): the
 // whole sub-cycle from the first such level down - smoothers, transfers, coarsest solve, every launch with fixed
 // arguments on hierarchy-owned buffers - is captured once into a HIP graph and replayed.  Not for cycles with host
-// decisions inside (Jac-GMRES smoothing, K-cycles, GMRES coarsest solve) and not while profiling (events per launch).
+// decisions inside (Jac-GMRES smoothing, K-cycles, GMRES coarsest solve), not with a Schwarz sweep as coarsest solve (its large
+// members run on their appliers' own streams) and not while profiling (events per launch).
 bool graph_ok(const mg_hierarchy* h, int l, char ctype) {
-  if (h->opt.no_graph || h->prof || h->capturing || h->relax_type != 0 || ctype == 'K' || h->coarse_gmres) return false;
+  if (h->opt.no_graph || h->prof || h->capturing || h->relax_type != 0 || ctype == 'K' || h->coarse_gmres || h->coarse_dd) return false;
   // a caller's stream (mg_set_stream) may be the legacy null stream, which cannot capture, or be part of a capture of
   // the caller's own: only the hierarchy's own stream is captured, unless the caller vouches for its stream (dist tail)
   if (!h->play->stream || (!h->play->owns_stream && !h->opt.dist_tail_graph)) return false;

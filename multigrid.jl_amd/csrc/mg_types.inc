@@ -661,6 +661,7 @@ struct ProfSlot {
 
 struct mg_ghost;   // (mg_ghost.inc) geometry, plans and transport of the ghost-layer form of the sharded cycle
 struct CxState;   // mg_complex.inc: the levels of a ComplexF64 handle
+struct mg_dd;     // mg_dd.inc: the multiplicative Schwarz sweep (a hierarchy may borrow one as its coarsest solve)
 
 struct mg_hierarchy {
   Options opt;
@@ -727,6 +728,7 @@ struct mg_hierarchy {
   DevBuf<double> kstepZ, kstepAZ, kstepX;   // mg_kcycle_step_async_dev_FP64: the K-step INTO this hierarchy's first level
   DevBuf<double> kwc, coarse_d;   // coarseSolveType "GMRES": FGMRES work space and the Jacobi preconditioner of the coarsest level
   bool coarse_gmres = false;
+  mg_dd* coarse_dd = nullptr;   // mg_set_coarse_dd: the coarsest solve is one Schwarz sweep of this (borrowed) handle; both value types
   // fine-level operands of the last cycle/solve (used as inputs by mg_time_op_dev_FP64)
   const double* last_b = nullptr;
   double* last_x = nullptr;

@@ -135,6 +135,12 @@ SIGNATURES = {
     "mg_dd_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
     "mg_dd_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_dd_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_dd0_apply_FP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll]),
+    "mg_dd0_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_dd0_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll]),
+    "mg_dd0_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_set_coarse_dd": (C.c_int, [_vp, _vp]),
+    "mg_coarse_form": (C.c_int, [_vp, _lp]),
     "mg_dd_info": (C.c_int, [_vp, _lp]),
     "mg_dd_time_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _dp]),
     "mg_dd_destroy": (C.c_int, [_vp]),
@@ -429,6 +435,8 @@ class DeviceHierarchy:
         import scipy.sparse as sp
         lib = self.lib
         nc = int(param.As[-1].shape[0])
+        if self._set_coarse_solver(param):
+            return
         if param.coarseSolveType == "GMRES":                            # param.LU = relaxParam ./ diag(A_c)
             d = np.ascontiguousarray(param.LU, dtype=np.float64)
             _check(lib, lib.mg_set_coarse_gmres_FP64(self.handle, nc, _f64(d)), "mg_set_coarse_gmres")
@@ -450,9 +458,68 @@ class DeviceHierarchy:
         _check(lib, lib.mg_set_coarse_lu_FP64_INT64(self.handle, nc, _i64(Lp), _i64(Lc), _f64(Lv), _i64(Up), _i64(Uc),
                                                     _f64(Uv), _i64(p), _i64(q)), "mg_set_coarse_lu")
 
+    _coarse_dd = None        # the DomainDecompositionParam whose device handle this hierarchy borrows as its coarsest solve
+
+    def _set_coarse_solver(self, param) -> bool:
+        """param.LU a solver object (MGsetup.jl:323-331, MGcycle.jl:138-148): a DomainDecompositionParam is attached as one
+        Schwarz sweep (mg_set_coarse_dd), a parallelJuliaSolver hands over its sparse factors (never an explicit inverse).
+        False: param.LU is a plain factorisation."""
+        from . import domain_decomposition as DD
+        from . import parallel_julia_solver as PJS
+        LU, lib = param.LU, self.lib
+        if isinstance(LU, DD.DomainDecompositionParam):
+            if self.nrhs != 1:
+                raise NotImplementedError("a DomainDecompositionParam as coarsest solver serves one right-hand side "
+                                          "(the reference's sweep indexes b[Idxs])")
+            if np.dtype(LU.VAL) != np.dtype(param.VAL):
+                raise TypeError("param.LU holds %s values, the hierarchy %s" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
+            h = DD._device_handle(LU, param.As[-1])
+            self._detach_dd()
+            _check(lib, lib.mg_set_coarse_dd(self.handle, h), "mg_set_coarse_dd")
+            self._coarse_dd = LU
+            LU._borrowers.append(self)
+            return True
+        if isinstance(LU, PJS.parallelJuliaSolver):
+            if LU.L is None:
+                raise MGDeviceError("param.LU is a parallelJuliaSolver without factors: run MGsetup / SA_AMGsetup first")
+            if np.dtype(LU.VAL) != np.dtype(param.VAL):
+                raise TypeError("param.LU holds %s factors, the hierarchy %s values" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
+            VAL = np.dtype(param.VAL)
+            a64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+            L, U = LU.L, LU.U
+            Lp, Lc, Lv = a64(L.indptr) + 1, a64(L.indices) + 1, np.ascontiguousarray(L.data, dtype=VAL)
+            Up, Uc, Uv = a64(U.indptr) + 1, a64(U.indices) + 1, np.ascontiguousarray(U.data, dtype=VAL)
+            cx = VAL == np.complex128
+            fn, what = (lib.mg_set_coarse_lu_CF64_INT64, "mg_set_coarse_lu_CF64") if cx else (lib.mg_set_coarse_lu_FP64_INT64, "mg_set_coarse_lu")
+            self._detach_dd()
+            _check(lib, fn(self.handle, L.shape[0], _i64(Lp), _i64(Lc), _f64(Lv), _i64(Up), _i64(Uc), _f64(Uv), _i64(a64(LU.p)), _i64(a64(LU.q))), what)
+            return True
+        self._detach_dd()
+        return False
+
+    def _detach_dd(self):
+        """Give a borrowed Schwarz handle back (before it is destroyed, or before another coarsest solve is set)."""
+        p = self._coarse_dd
+        if p is not None:
+            self._coarse_dd = None
+            if self in p._borrowers:
+                p._borrowers.remove(self)
+            if self.handle:
+                self.lib.mg_set_coarse_dd(self.handle, None)
+
+    def coarse_form(self) -> dict:
+        """What ``mg_coarse_form`` reports: kind (0 dense inverse, 1 sparse LU in one workgroup, 2 sparse LU chip-wide, 3 GMRES,
+        4 Schwarz sweep), order, kernel launches per solve."""
+        info = (C.c_longlong * 3)()
+        _check(self.lib, self.lib.mg_coarse_form(self.handle, info), "mg_coarse_form")
+        return dict(kind=int(info[0]), order=int(info[1]), launches=int(info[2]))
+
     def set_nrhs(self, nrhs: int):
         if getattr(self, "_vanka", False) and int(nrhs) != 1:
             raise NotImplementedError("Vanka hierarchies serve one right-hand side (blocks of right-hand sides are out of scope)")
+        if self._coarse_dd is not None and int(nrhs) != 1:
+            raise NotImplementedError("a DomainDecompositionParam as coarsest solver serves one right-hand side "
+                                      "(the reference's sweep indexes b[Idxs])")
         _check(self.lib, self.lib.mg_set_nrhs(self.handle, int(nrhs)), "mg_set_nrhs")
         self.nrhs = int(nrhs)
 
@@ -491,6 +558,7 @@ class DeviceHierarchy:
 
     def close(self):
         if self.handle:
+            self._detach_dd()
             self.lib.mg_destroy(self.handle)
             self.handle = _vp()
 
@@ -905,6 +973,8 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         import scipy.sparse as sp
         lib = self.lib
         nc = int(param.As[-1].shape[0])
+        if self._set_coarse_solver(param):
+            return
         if param.coarseSolveType == "GMRES":
             raise NotImplementedError("coarseSolveType='GMRES' is not served for ComplexF64 hierarchies")
         if nc <= DENSE_COARSE_MAX and not force_sparse:

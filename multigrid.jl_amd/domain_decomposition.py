@@ -10,9 +10,10 @@ launch, the others run one after another.  There is no CPU fallback.  ``A`` is t
 ``param.As[l]`` holds in this package where Julia holds the CSC of A' (MGdef.jl:75-77).
 
 Not mirrored: the operator-constructor / Dirichlet-mass branch (DDSerial.jl:42-61), DDParallel.jl, ``solveGSDDSerial``,
-the reference's ``solveLinearSystem!`` for a ``DomainDecompositionParam`` (it calls an undefined ``Prec`` at this commit,
-DomainDecomposition.jl:126-129) and the ``solveCoarsest`` branch that runs a DD solver inside a hierarchy
-(MGcycle.jl:140-143).
+and the reference's ``solveLinearSystem!`` for a ``DomainDecompositionParam`` (it calls an undefined ``Prec`` at this commit,
+DomainDecomposition.jl:126-129).  A ``DomainDecompositionParam`` preset as ``param.LU`` of a hierarchy is its coarsest
+solve (MGsetup.jl:323-326, MGcycle.jl:140-143): mgsetup.defineCoarsestAinv sets it up, the device hierarchy borrows
+its handle.
 """
 from __future__ import annotations
 
@@ -77,12 +78,15 @@ class DomainDecompositionParam:
     solveTime: float = 0.0
     _handle: Any = field(default=None, repr=False)
     _key: Any = field(default=None, repr=False)
+    _borrowers: list = field(default_factory=list, repr=False)   # device hierarchies whose coarsest solve is this handle
 
     @property
     def is_complex(self) -> bool:
         return np.dtype(self.VAL) == np.complex128
 
     def close(self):
+        for h in list(self._borrowers):      # an attached handle cannot be destroyed: the hierarchies give it back first
+            h._detach_dd()
         if self._handle is not None:
             D.load_library().mg_dd_destroy(self._handle)
             self._handle = None
@@ -100,6 +104,22 @@ def getDomainDecompositionParam(VAL, IND, Mesh, numDomains, overlap, getIndicesO
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only Float64 and ComplexF64 are supported on the device path")
     return DomainDecompositionParam(VAL, IND, Mesh, [int(k) for k in numDomains], [int(k) for k in overlap], getIndicesOfCell, Ainv)
+
+
+def copySolver(p: DomainDecompositionParam) -> DomainDecompositionParam:
+    """DomainDecomposition.jl:75-78: the settings and a copy of the sub-domain solver, without the setup."""
+    Ainv = PJS.copySolver(p.Ainv) if isinstance(p.Ainv, PJS.parallelJuliaSolver) else p.Ainv
+    return getDomainDecompositionParam(p.VAL, p.IND, p.Mesh, p.numDomains, p.overlap, p.getIndicesOfCell, Ainv)
+
+
+def clear_(p: DomainDecompositionParam) -> DomainDecompositionParam:
+    """``clear!(param)`` (DomainDecomposition.jl:59-67 names a field that does not exist; its intent): drop the sub-domain
+    factors, the index lists and the device handle; the settings stay."""
+    p.close()
+    p.PrecParams = []
+    p.GlobalIndices = []
+    p.doClear = 0
+    return p
 
 
 def isempty(p: DomainDecompositionParam) -> bool:

@@ -88,8 +88,31 @@ def hierarchyExists(param: MGparam) -> bool:
     return len(param.As) > 0
 
 
+def _solver_object(LU):
+    """param.LU as a solver object preset before the setup (MGsetup.jl:323-331): 'dd', 'pjs' or None (a plain factorisation)."""
+    from . import domain_decomposition as DD
+    from . import parallel_julia_solver as PJS
+    if isinstance(LU, DD.DomainDecompositionParam):
+        return "dd"
+    if isinstance(LU, PJS.parallelJuliaSolver):
+        return "pjs"
+    return None
+
+
 def destroyCoarsestLU(param: MGparam) -> None:
-    param.LU = None
+    """MGdef.jl:191-206: a solver object is cleared and kept (l.200-201), a plain factorisation dropped."""
+    kind = _solver_object(param.LU)
+    if kind is None:
+        param.LU = None
+        return
+    if param.device is not None:       # (the hierarchy gives a borrowed handle back before it is destroyed)
+        _release_device(param)
+    if kind == "dd":
+        from .domain_decomposition import clear_ as clear_dd
+        clear_dd(param.LU)
+    else:
+        from .parallel_julia_solver import clear_ as clear_pjs
+        clear_pjs(param.LU)
 
 
 def _release_device(param: MGparam) -> None:
@@ -109,7 +132,16 @@ def clear_(param: MGparam) -> None:
 
 
 def copySolver(MG: MGparam) -> MGparam:
-    """Copies the solver parameters without the setup and allocated memory (MGdef.jl:138-145)."""
-    return getMGparam(MG.VAL, MG.IND, MG.levels, MG.numCores, MG.maxOuterIter, MG.relativeTol, MG.relaxType,
-                      MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
-                      MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType)
+    """Copies the solver parameters without the setup and allocated memory (MGdef.jl:138-145); a solver-object ``LU`` is
+    copied by its own ``copySolver`` (l.141-143), a plain factorisation is not."""
+    new = getMGparam(MG.VAL, MG.IND, MG.levels, MG.numCores, MG.maxOuterIter, MG.relativeTol, MG.relaxType,
+                     MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
+                     MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType)
+    kind = _solver_object(MG.LU)
+    if kind == "dd":
+        from .domain_decomposition import copySolver as copy_dd
+        new.LU = copy_dd(MG.LU)
+    elif kind == "pjs":
+        from .parallel_julia_solver import copySolver as copy_pjs
+        new.LU = copy_pjs(MG.LU)
+    return new

@@ -127,7 +127,26 @@ def galerkin(R, A, P):
 
 
 def defineCoarsestAinv(param: MGparam, Ac) -> None:
-    """Coarsest-level factorisation (MGsetup.jl:323-355).  Default branch: ``lu(sparse(AT'))`` (l.350)."""
+    """Coarsest-level factorisation (MGsetup.jl:323-355).  Default branch: ``lu(sparse(AT'))`` (l.350).  A solver object
+    preset in ``param.LU`` is set up on the coarsest matrix and stays the object the caller put there (l.323-331)."""
+    from .mgdef import _solver_object
+    kind = _solver_object(param.LU)
+    if kind == "dd":                              # LU.Mesh = Meshes[end]; setupDDSerial(AT, LU)
+        from .domain_decomposition import setupDDSerial
+        LU = param.LU
+        if not param.Meshes:
+            raise ValueError("a DomainDecompositionParam as coarsest solver needs the coarsest mesh: the hierarchy has none (SA-AMG)")
+        if np.dtype(LU.VAL) != np.dtype(param.VAL):
+            raise TypeError("param.LU is a DomainDecompositionParam of %s, the hierarchy of %s" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
+        LU.Mesh = param.Meshes[-1]
+        setupDDSerial(_as_csr(Ac), LU)            # (closes LU's device handle first: a resident hierarchy that borrows it gives it back)
+        return
+    if kind == "pjs":                             # setupSolver(sparse(AT'), LU)
+        from .parallel_julia_solver import setupLUFactor
+        if np.dtype(param.LU.VAL) != np.dtype(param.VAL):
+            raise TypeError("param.LU is a parallelJuliaSolver of %s, the hierarchy of %s" % (np.dtype(param.LU.VAL), np.dtype(param.VAL)))
+        setupLUFactor(_as_csr(Ac), param.LU, upload=False)
+        return
     if param.coarseSolveType == "MUMPS":
         raise NotImplementedError("MUMPS coarse solve is dead code in the reference (Multigrid.jl:29-40)")
     if param.coarseSolveType == "GMRES":
@@ -303,6 +322,7 @@ def transposeHierarchy(param: MGparam, verbose: bool = False) -> None:
         param.Rs[l - 1] = _as_csr(newP.T)
         param.As[l] = _as_csr(param.As[l].T)
     destroyCoarsestLU(param)
+    param.LU = None        # MGsetup.jl:310-311 factors the transposed coarsest matrix itself: a solver object is replaced
     defineCoarsestAinv(param, param.As[-1])
     # The resident hierarchy is transposed in HBM (mg_transpose_hierarchy: counting-sort CSR transposes, dense coarsest inverse
     # transposed in place, device formats rebuilt) instead of being dropped and uploaded again; what the library cannot do there

@@ -119,7 +119,7 @@ def SA_AMGsetup(A, param: MGparam, symm: bool = True, nrhs: int = 1, verbose: bo
         print("MG Setup: Operator complexity = ", Cop / As[0].nnz)
     nc = As[-1].shape[0]
     As[-1] = _as_csr(As[-1] + 1e-8 * float(abs(As[-1]).sum()) * sp.identity(nc, format="csr"))   # l.63
+    param.Meshes = []                 # (before the coarsest solve is defined: a DomainDecompositionParam LU finds no mesh, as in the reference)
     defineCoarsestAinv(param, As[-1])
     param.As, param.Ps, param.Rs, param.relaxPrecs = As, Ps, Rs, relaxPrecs
-    param.Meshes = []
     adjustMemoryForNumRHS(param, nrhs, verbose)
