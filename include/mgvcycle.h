@@ -800,7 +800,7 @@ int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count);
  *   MG_ERR_STATE too; nothing is changed.
  * Refused with MG_ERR_UNSUPPORTED (and a mg_last_error message): cycle 'K', relaxType 1 (Jac-GMRES), the GMRES coarse solve
  *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries), the _FP64 Krylov drivers
- *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64, mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
+ *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64 (mg_rap_CF64 serves them), mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
  *   mg_ghost_* call and mg_dist_set_tail_INT64 with a CF64 tail (the mg_dist_* handles are FP64 by construction).
  * Formats.  Generic CSR only, one streaming kernel (int32 row pointers; 64-bit beyond 2^31 - 4096 non-zeros or with the option
  *   "force_rowptr64"); the row-class, band, tile, march and small-level formats are real-valued and not used.  No HIP graphs. */
@@ -826,6 +826,41 @@ int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long
 int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* x,
                  const double* beta, double* y, long long nrhs);
 
+/* ---- replaceMatrixInHierarchy on a CF64 handle (MGsetup.jl:226-270) ---------------------------------------------------------
+ * A matrix whose values change and whose pattern does not (one call per outer iteration of an inversion: new medium, same
+ * shifted Laplacian pattern, same P and R) is re-set-up in HBM; nothing is uploaded again and nothing re-blocked.  Value arrays
+ * are in the convention of mg_set_operator_CF64_INT64: interleaved (re, im) doubles of the reference's AT (conjugated by the
+ * library on the way in and back on the way out) for A, real doubles for P and R; nnz counts values and must be the stored
+ * pattern's (MG_ERR_INVALID otherwise).  Common refusals: a null handle or array MG_ERR_INVALID, an FP64 handle MG_ERR_STATE.
+ *
+ * mg_rap_CF64 is mg_rap_FP64 for complex values: it writes the new fine values, then per level recomputes relaxPrecs[l]
+ * (relaxKind 0: Jac, d = omega/a_ii; 1: SPAI, d = omega*conj(a_ii)/s_i with s_i the sum of re^2 + im^2 over COLUMN i in ascending
+ * row order; omega[l] real, one per level) and As[l+1] = Rs[l]*(As[l]*Ps[l]) on its fixed pattern (csrc/mg_complex.hpp,
+ * cx_rap_numeric: deterministic, no atomics; rows of any length, at most the option rap_chunk target columns at a time; the
+ * option rap_groups sets how many rows of A a wavefront walks side by side, 1 being the order of mg_rap_FP64's kernel).  The
+ * coarsest factorisation stays with the host, as for FP64: mg_get_values_CF64 of the coarsest level, factor, hand the solve
+ * back (mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64), mg_finalize.  Also refused: a handle that is not
+ * finalized (MG_ERR_STATE), relaxKind other than 0 or 1 (MG_ERR_INVALID), any operator with 64-bit row pointers
+ * (MG_ERR_UNSUPPORTED).  These checks of arguments and state precede the first write: after such a refusal the handle cycles
+ * with its old values.  (A HIP error in the middle of the re-setup, MG_ERR_HIP, may leave some levels refreshed, as for FP64.)
+ * mg_rap_level_ms_CF64: device time of the last mg_rap_CF64 per level (relaxPrecs[l] and As[l+1]), out[0 .. nlevels-1), ms;
+ * n must be nlevels - 1 (MG_ERR_INVALID), and a mg_rap_CF64 must have completed on the handle (MG_ERR_STATE).
+ * mg_get_values_CF64 / mg_replace_values_CF64: one operator's values in stored CSR order (A: nnz complex; P, R: nnz real).
+ * mg_get_relax_CF64: relaxPrecs[level], n complex values, as mg_set_relax_CF64 takes them.
+ * Assumed, as by mg_rap_FP64, and not validated at upload for hand-built hierarchies: the rows of every As[l+1] are sorted, hold
+ * no column twice and contain every column the product reaches; no row of P holds a column twice.
+ * Determinism is per configuration: the order of the sums depends on the number of lane groups, which follows rap_groups and is
+ * halved while the accumulator copies of a level's longest row exceed 32 KB of LDS - the same handle gives the same bits on
+ * every run; handles with other options or other row lengths may differ in the last bits.
+ * These return mg_status (below): MG_OK or an MG_ERR_* code, as every entry point of this header does. */
+typedef int mg_status;   /* the status every entry point returns (MG_OK, MG_ERR_*); the older prototypes spell it int */
+mg_status mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind, const double* omega,
+                      long long* levels_done);
+mg_status mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n);
+mg_status mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
+mg_status mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n);
+mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz);
+
 /* ---- ComplexF64 Krylov drivers on a CF64 handle (suffix CFP64, the reference's own) ---------------------------------------
  * solveBiCGSTAB_MG / solveGMRES_MG (SolveFuncs.jl:85-133) for VAL = ComplexF64: KrylovMethods.bicgstb / fgmres with one cycle
  * of the handle's hierarchy from x = 0 as preconditioner, every vector resident in HBM across iterations.  The way Helmholtz
@@ -848,6 +883,9 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
  * for complex values: PCG (the operators in question are not Hermitian positive definite), blocks of right-hand sides. */
 int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long long* colptr, const long long* rowval,
                                        const double* nzval);
+/* New values (nnz complex, the AT convention) on the pattern of the Krylov operator set last: a copy and one conjugation in HBM,
+ * no re-blocking.  No operator set: MG_ERR_STATE; nnz different from its pattern: MG_ERR_INVALID. */
+int mg_replace_krylov_values_CFP64(mg_hierarchy* h, const double* nzval, long long nnz);
 int mg_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter,
                       long long* iters, long long* flag, double* resvec, long long* nres);
 int mg_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, double tol, long long maxIter,

@@ -187,6 +187,130 @@ __global__ __launch_bounds__(BLK) void cx_dense_matvec(const d2_t* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
+// replaceMatrixInHierarchy on a CF64 hierarchy (mg_rap_CF64; MGsetup.jl:226-270): the numeric Galerkin product on C's fixed
+// pattern and getRelaxPrec for complex values.  Device A holds the APPLIED values (conjugated once at upload) and R, P are
+// real, so C = R*(A*P) needs no conjugation anywhere.
+//
+// cx_rap_numeric: the walk of rap_numeric (mg_kernels.hpp) with complex sums and with `groups` rows of A side by side.  One
+// wavefront per coarse row i.  The entries (i,k) of R's row are walked one after the other in stored order.  The wavefront is
+// cut into `groups` lane groups of 64/groups lanes: group g takes the entries (k,j) of A's row number g, g + groups, ... in
+// stored order, and spreads the entries (j,c) of ONE row of P - distinct target columns - over its lanes; each lane finds its
+// column in C's sorted row by binary search in LDS and adds into ITS GROUP'S copy of the accumulator, without atomics.  The
+// copies are summed in group order at the end.  Every entry of C is therefore the same sum in the same order on every run
+// of one configuration (groups = 1 is rap_numeric's order exactly; another group count is another, equally fixed order).  On a GMG level a row of P holds at most 8 entries: one group of 64 lanes
+// leaves 56 idle, 8 groups of 8 walk 8 rows of A at once.
+// The accumulator is dynamic LDS, (16 * groups + 4) bytes per target column, sized by the host to min(rap_chunk, the level's
+// longest row of C) columns - 3.6 KB on a GMG level (27-entry rows, 8 groups), where a fixed RAP_CAP of complex sums would
+// take 40 KB per wavefront; longer rows are accumulated `chunk` target columns at a time by the same walk.  Rows of R, A, P
+// and C may be empty.
+// ------------------------------------------------------------------------------------------------
+constexpr int CX_RAP_GROUPS = 8;   // lane groups of cx_rap_numeric unless the option rap_groups says otherwise
+template <typename VT>
+struct CxCsr32 {
+  const int* rowptr;
+  const int* colidx;
+  const VT* val;
+};
+
+__global__ __launch_bounds__(64) void cx_rap_numeric(CxCsr32<double> R, CxCsr32<d2_t> A, CxCsr32<double> P,
+                                                     const int* __restrict__ Crowptr, const int* __restrict__ Ccol,
+                                                     d2_t* __restrict__ Cval, int chunk, int groups) {
+  extern __shared__ d2_t cx_rap_lds[];   // groups copies of chunk sums, then chunk column indices
+  d2_t* sacc = cx_rap_lds;
+  int* scol = reinterpret_cast<int*>(cx_rap_lds + (size_t)groups * chunk);
+  const int i = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int W = 64 / groups;             // lanes per group (groups is a power of two <= 64: host)
+  const int g = lane / W, sub = lane - g * W;
+  d2_t* mine = sacc + (size_t)g * chunk;
+  const int c0 = Crowptr[i];
+  const int len = Crowptr[i + 1] - c0;
+  for (int t0 = 0; t0 < len; t0 += chunk) {
+    const int clen = len - t0 < chunk ? len - t0 : chunk;
+    __syncthreads();
+    for (int t = lane; t < clen; t += 64) scol[t] = Ccol[c0 + t0 + t];
+    for (int t = lane; t < groups * chunk; t += 64) sacc[t] = d2_t{0.0, 0.0};
+    __syncthreads();
+    const int cmin = scol[0], cmax = scol[clen - 1];
+    for (int kk = R.rowptr[i]; kk < R.rowptr[i + 1]; ++kk) {        // wave-uniform, stored order
+      const int k = R.colidx[kk];
+      const double rv = R.val[kk];
+      const int a1 = A.rowptr[k + 1];
+      for (int jj0 = A.rowptr[k]; jj0 < a1; jj0 += groups) {        // wave-uniform; group g: entry jj0 + g
+        const int jj = jj0 + g;
+        if (jj < a1) {
+          const int j = A.colidx[jj];
+          const d2_t ra = cmul(rv, A.val[jj]);
+          for (int pp = P.rowptr[j] + sub; pp < P.rowptr[j + 1]; pp += W) {   // distinct columns: one lane each
+            const int c = P.colidx[pp];
+            if (c < cmin || c > cmax) continue;                     // (another chunk's column)
+            int lo = 0, hi = clen - 1;
+            while (lo < hi) {
+              const int mid = (lo + hi) >> 1;
+              if (scol[mid] < c) lo = mid + 1;
+              else hi = mid;
+            }
+            if (scol[lo] == c) mine[lo] += cmul(P.val[pp], ra);
+          }
+        }
+        __builtin_amdgcn_wave_barrier();   // one wavefront: LDS accesses of the next rows of P follow in program order
+      }
+    }
+    __syncthreads();
+    for (int t = lane; t < clen; t += 64) {
+      d2_t s = sacc[t];
+      for (int q = 1; q < groups; ++q) s += sacc[(size_t)q * chunk + t];   // group order
+      Cval[c0 + t0 + t] = s;
+    }
+  }
+}
+
+// z_k = conj(z_k) in place: the reference's AT values <-> the applied values the kernels hold
+__global__ __launch_bounds__(BLK) void cx_conj(d2_t* __restrict__ z, long long n) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i < n) z[i].y = -z[i].y;
+}
+
+__device__ __forceinline__ d2_t cx_diag(const CxCsr32<d2_t>& A, int i) {
+  d2_t diag = d2_t{0.0, 0.0};
+  for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
+    if (A.colidx[k] == i) diag = A.val[k];
+  return diag;
+}
+// d_i = omega / a_ii  (getRelaxPrec "Jac" for complex values: conj(relaxParam ./ diag(AT)), MGsetup.jl:145-147)
+__global__ __launch_bounds__(BLK) void cx_relax_jacobi(CxCsr32<d2_t> A, int n, double omega, d2_t* __restrict__ d) {
+  const int i = blockIdx.x * BLK + threadIdx.x;
+  if (i >= n) return;
+  d[i] = cdiv(d2_t{omega, 0.0}, cx_diag(A, i));
+}
+// s_j = sum over the entries of COLUMN j of re^2 + im^2 in ascending row order (getSPAIprec, MGsetup.jl:359-362: row j of AT):
+// squares rounded, then summed, as colsumsq_kernel does - no atomics, the same bits on every run and as the host's bincount.
+__global__ __launch_bounds__(BLK) void cx_colsumsq(const d2_t* __restrict__ val, const int* __restrict__ tptr,
+                                                   const int* __restrict__ tperm, int n_cols, double* __restrict__ s) {
+#pragma clang fp contract(off)
+  const int j = blockIdx.x * BLK + threadIdx.x;
+  if (j >= n_cols) return;
+  double acc = 0.0;
+  for (int k = tptr[j]; k < tptr[j + 1]; ++k) {
+    const d2_t a = val[tperm[k]];
+    const double re2 = a.x * a.x;
+    const double im2 = a.y * a.y;
+    const double sq = re2 + im2;
+    acc = acc + sq;
+  }
+  s[j] = acc;
+}
+// d_i = omega * conj(a_ii) / s_i  (conj(relaxParam * getSPAIprec(AT)), MGsetup.jl:148-149): the quotient first
+__global__ __launch_bounds__(BLK) void cx_relax_spai(CxCsr32<d2_t> A, int n, double omega, const double* __restrict__ s,
+                                                     d2_t* __restrict__ d) {
+  const int i = blockIdx.x * BLK + threadIdx.x;
+  if (i >= n) return;
+  const d2_t diag = cx_diag(A, i);
+  const double si = s[i];
+  d[i] = d2_t{omega * (diag.x / si), omega * (-diag.y / si)};
+}
+
+// ------------------------------------------------------------------------------------------------
 // Complex hybrid Kaczmarz relaxation (reference native: deps/src/parRelax.h:7-43 built with spValType = double complex,
 // applyHybridKaczmarz_CFP64_INT64).  The schedule of the real hybrid_kaczmarz (mg_kernels.hpp): one wavefront per
 // sub-domain, or one wavefront for all sub-domains in order when `sequential` is set; rows in list order, zero padding

@@ -18,12 +18,17 @@ struct CxMat {
   bool set = false, cplx = false, wide = false;
   long long n_rows = 0, n_cols = 0, nnz = 0;
   int nblocks = 0;
+  long long max_row = 0;        // the longest row (sizes the accumulator of cx_rap_numeric)
   DevBuf<int> rowptr, colidx, blk_row;
   DevBuf<long long> rowptr64;   // wide: >= 2^31 - 4096 non-zeros (or the option force_rowptr64)
   DevBuf<double> val;           // nnz real values, or 2*nnz interleaved (re, im)
+  bool has_t = false;           // the transposed pattern of cx_colsumsq (built on the first SPAI re-setup of the level)
+  DevBuf<int> t_ptr, t_perm;
   void release() {
     rowptr.release(); colidx.release(); blk_row.release(); rowptr64.release(); val.release();
+    t_ptr.release(); t_perm.release();
     set = false;
+    has_t = false;
   }
 };
 
@@ -52,7 +57,10 @@ struct CxState {
   CxMat K;
   DevBuf<double> kwork, kpart, kscal, stage_x;
   double* h_kscal = nullptr;
+  std::vector<hipEvent_t> rap_ev;   // mg_rap_CF64: one event ahead of every level's kernels and one behind the last (mg_rap_level_ms_CF64)
+  bool rap_timed = false;
   ~CxState() {
+    for (hipEvent_t e : rap_ev) (void)hipEventDestroy(e);
     for (auto& L : lev) {
       L.A.release(); L.P.release(); L.R.release();
       L.d.release(); L.b.release(); L.r.release(); L.x[0].release(); L.x[1].release();
@@ -151,6 +159,8 @@ int cx_upload(CxMat* M, const Options& opt, long long n_rows, long long n_cols, 
   M->n_cols = n_cols;
   M->nnz = nnz;
   M->nblocks = (int)blk.size() - 1;
+  M->max_row = 0;
+  for (long long i = 0; i < n_rows; ++i) M->max_row = std::max(M->max_row, rp[(size_t)i + 1] - rp[(size_t)i]);
   if (M->wide) {
     MG_TRY(M->rowptr64.alloc(rp.size()));
     HIP_TRY(hipMemcpy(M->rowptr64.p, rp.data(), rp.size() * sizeof(long long), hipMemcpyHostToDevice));
@@ -621,6 +631,61 @@ int cxlu_create(long long device_id, long long n, const long long* Lptr, const l
   return MG_OK;
 }
 
+
+// ---- replaceMatrixInHierarchy on the device (mg_rap_CF64 and the value replacements) -------------------------------------
+// column -> entries in ascending row order (stable counting sort of the stored pattern), for cx_colsumsq: build_transposed_pattern
+// of the real operators, on a CxMat
+int cx_build_transposed_pattern(CxMat& A) {
+  if (A.wide) return fail(MG_ERR_UNSUPPORTED, "operators with 64-bit row pointers are not transposed on the device");
+  if (A.has_t) return MG_OK;
+  std::vector<int> rp((size_t)A.n_rows + 1), ci((size_t)std::max<long long>(A.nnz, 1));
+  HIP_TRY(hipMemcpy(rp.data(), A.rowptr.p, rp.size() * sizeof(int), hipMemcpyDeviceToHost));
+  if (A.nnz > 0) HIP_TRY(hipMemcpy(ci.data(), A.colidx.p, (size_t)A.nnz * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<int> tp((size_t)A.n_cols + 1, 0), perm((size_t)std::max<long long>(A.nnz, 1));
+  for (long long k = 0; k < A.nnz; ++k) ++tp[(size_t)ci[(size_t)k] + 1];
+  for (long long j = 0; j < A.n_cols; ++j) tp[(size_t)j + 1] += tp[(size_t)j];
+  std::vector<int> next(tp.begin(), tp.end() - 1);
+  for (long long i = 0; i < A.n_rows; ++i)
+    for (int k = rp[(size_t)i]; k < rp[(size_t)i + 1]; ++k) perm[(size_t)next[(size_t)ci[(size_t)k]]++] = k;
+  MG_TRY(A.t_ptr.alloc(tp.size()));
+  MG_TRY(A.t_perm.alloc(perm.size()));
+  HIP_TRY(hipMemcpy(A.t_ptr.p, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.t_perm.p, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice));
+  A.has_t = true;
+  return MG_OK;
+}
+
+template <typename VT>
+mgk::CxCsr32<VT> cx_csr32(const CxMat& M) {
+  return mgk::CxCsr32<VT>{M.rowptr.p, M.colidx.p, reinterpret_cast<const VT*>(M.val.p)};
+}
+
+// New values on M's unchanged pattern from host memory, on h's stream and waited for: complex values arrive in the reference's
+// AT convention and are conjugated in HBM (cx_conj), real ones are copied.
+int cx_write_values(mg_hierarchy* h, CxMat& M, const double* nzval) {
+  const hipStream_t st = h->play->stream;
+  HIP_TRY(spin_sync(st));
+  if (M.nnz > 0) {
+    HIP_TRY(hipMemcpyAsync(M.val.p, nzval, (size_t)M.nnz * (M.cplx ? 2 : 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    if (M.cplx) hipLaunchKernelGGL(mgk::cx_conj, dim3(cx_grid(M.nnz)), dim3(mgk::BLK), 0, st, cxp(M.val), M.nnz);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(spin_sync(st));
+  return MG_OK;
+}
+
+// the operator `which` of `level` of a CF64 handle, set
+int cx_find_op(mg_hierarchy* h, long long level, long long which, CxMat** out) {
+  MG_TRY(cx_level_ok(h, level));
+  if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
+  if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  CxMat* M = which == MG_OP_A ? &L.A : which == MG_OP_P ? &L.P : &L.R;
+  if (!M->set) return fail(MG_ERR_STATE, "operator %lld of level %lld was not set", which, level);
+  *out = M;
+  return MG_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -845,6 +910,128 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
   dx.release();
   dy.release();
   return rc;
+}
+
+// replaceMatrixInHierarchy on the device (MGsetup.jl:226-270) for VAL = ComplexF64: new fine values on the stored pattern, then per
+// level relaxPrecs[l] = getRelaxPrec(As[l]) and As[l+1] = Rs[l]*(As[l]*Ps[l]) on the fixed patterns.  Generic CSR has no derived
+// formats to rebuild.  The coarsest factorisation stays with the host: mg_get_values_CF64 of the coarsest level, factor,
+// mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64, mg_finalize.  The checks of arguments and state precede the first write.
+int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind, const double* omega,
+                long long* levels_done) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!fine_nzval || !omega) return fail(MG_ERR_INVALID, "null argument");
+  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  if (nnz != S.lev[0].A.nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored fine pattern (%lld)", nnz, S.lev[0].A.nnz);
+  if (relaxKind != 0 && relaxKind != 1) return fail(MG_ERR_INVALID, "relaxKind must be 0 (Jac) or 1 (SPAI)");
+  const int nl = (int)h->nlevels;
+  for (int l = 0; l < nl; ++l) {
+    const CxLevel& L = S.lev[(size_t)l];
+    if (L.A.wide || (l + 1 < nl && (L.P.wide || L.R.wide)))
+      return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers: the numeric Galerkin product on the device serves int32 operators", l + 1);
+  }
+  (void)hipSetDevice(h->device);
+  const hipStream_t st = h->play->stream;
+  if (relaxKind == 1)
+    for (int l = 0; l + 1 < nl; ++l) MG_TRY(cx_build_transposed_pattern(S.lev[(size_t)l].A));   // (first SPAI re-setup only)
+  while (S.rap_ev.size() < (size_t)nl) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreate(&e));
+    S.rap_ev.push_back(e);
+  }
+  S.rap_timed = false;
+  MG_TRY(cx_write_values(h, S.lev[0].A, fine_nzval));
+  for (int l = 0; l + 1 < nl; ++l) {
+    CxLevel& L = S.lev[(size_t)l];
+    CxMat& Cm = S.lev[(size_t)l + 1].A;
+    const unsigned nb = cx_grid(L.n);
+    const mgk::CxCsr32<cx_t> Ad = cx_csr32<cx_t>(L.A);
+    HIP_TRY(hipEventRecord(S.rap_ev[(size_t)l], st));
+    if (relaxKind == 0) {
+      hipLaunchKernelGGL(mgk::cx_relax_jacobi, dim3(nb), dim3(mgk::BLK), 0, st, Ad, (int)L.n, omega[l], cxp(L.d));
+    } else {   // the level's r as scratch for the column sums
+      hipLaunchKernelGGL(mgk::cx_colsumsq, dim3(nb), dim3(mgk::BLK), 0, st, reinterpret_cast<const cx_t*>(L.A.val.p), L.A.t_ptr.p,
+                         L.A.t_perm.p, (int)L.A.n_cols, L.r.p);
+      hipLaunchKernelGGL(mgk::cx_relax_spai, dim3(nb), dim3(mgk::BLK), 0, st, Ad, (int)L.n, omega[l], L.r.p, cxp(L.d));
+    }
+    const long long cap = std::max<long long>(1, std::min<long long>(h->opt.rap_chunk, mgk::RAP_CAP));
+    const int chunk = (int)std::max<long long>(1, std::min<long long>(cap, Cm.max_row));
+    // lane groups: the default (option rap_groups: 1, 2, 4, 8, 16), halved while the accumulator copies exceed 32 KB of LDS
+    int groups = 1;
+    while (groups * 2 <= std::min<long long>(h->opt.rap_groups > 0 ? h->opt.rap_groups : mgk::CX_RAP_GROUPS, 16)) groups *= 2;
+    while (groups > 1 && (size_t)chunk * ((size_t)groups * sizeof(cx_t) + sizeof(int)) > 32768) groups /= 2;
+    hipLaunchKernelGGL(mgk::cx_rap_numeric, dim3((unsigned)Cm.n_rows), dim3(64), (size_t)chunk * ((size_t)groups * sizeof(cx_t) + sizeof(int)), st,
+                       cx_csr32<double>(L.R), Ad, cx_csr32<double>(L.P), Cm.rowptr.p, Cm.colidx.p, cxp(Cm.val), chunk, groups);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(S.rap_ev[(size_t)nl - 1], st));
+  HIP_TRY(spin_sync(st));
+  S.rap_timed = true;
+  if (levels_done) *levels_done = nl - 1;
+  return MG_OK;
+}
+
+// Device time of the last mg_rap_CF64, level by level (relaxPrecs[l] and As[l+1] together), in milliseconds: out[0 .. nlevels-1).
+int mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n) {
+  MG_TRY(cx_level_ok(h, 1));
+  CxState& S = *h->cx;
+  if (!out || n != h->nlevels - 1) return fail(MG_ERR_INVALID, "out must hold nlevels - 1 = %lld values", h->nlevels - 1);
+  if (!S.rap_timed) return fail(MG_ERR_STATE, "no completed mg_rap_CF64 on this handle");
+  for (long long l = 0; l < n; ++l) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, S.rap_ev[(size_t)l], S.rap_ev[(size_t)l + 1]));
+    out[l] = (double)ms;
+  }
+  return MG_OK;
+}
+
+int mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!out) return fail(MG_ERR_INVALID, "null argument");
+  CxMat* M;
+  MG_TRY(cx_find_op(h, level, which, &M));
+  if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));
+  const size_t len = (size_t)nnz * (M->cplx ? 2 : 1);
+  if (len > 0) HIP_TRY(hipMemcpy(out, M->val.p, len * sizeof(double), hipMemcpyDeviceToHost));
+  if (M->cplx)   // back to the reference's AT convention
+    for (size_t k = 1; k < len; k += 2) out[k] = -out[k];
+  return MG_OK;
+}
+
+int mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!out) return fail(MG_ERR_INVALID, "null argument");
+  MG_TRY(cx_level_ok(h, level));
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  if (!L.relax_set || 2 * n != (long long)L.d.n) return fail(MG_ERR_INVALID, "relaxPrecs[%lld] not set or wrong length", level);
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));
+  HIP_TRY(hipMemcpy(out, L.d.p, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return MG_OK;
+}
+
+int mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!nzval) return fail(MG_ERR_INVALID, "null argument");
+  CxMat* M;
+  MG_TRY(cx_find_op(h, level, which, &M));
+  if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
+  (void)hipSetDevice(h->device);
+  return cx_write_values(h, *M, nzval);
+}
+
+int mg_replace_krylov_values_CFP64(mg_hierarchy* h, const double* nzval, long long nnz) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!nzval) return fail(MG_ERR_INVALID, "null argument");
+  MG_TRY(cx_level_ok(h, 1));
+  CxState& S = *h->cx;
+  if (!S.K.set) return fail(MG_ERR_STATE, "no Krylov operator set (mg_set_krylov_operator_CFP64_INT64)");
+  if (nnz != S.K.nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the Krylov operator's pattern (%lld)", nnz, S.K.nnz);
+  (void)hipSetDevice(h->device);
+  return cx_write_values(h, S.K, nzval);
 }
 
 }  // extern "C"

@@ -75,6 +75,7 @@ bool host_all_zero(const double* x, long long len) {
   X(bool, no_mgs_chain, false) \
   X(bool, no_restrict_scale, false) \
   X(long long, rap_chunk, 2048)    /* target columns of a coarse row the numeric Galerkin product accumulates at a time (<= 2048; tests) */ \
+  X(long long, rap_groups, 0)      /* CF64 numeric Galerkin product: rows of A walked side by side by a wavefront (0: default; 1, 2, 4, 8, 16; A/B, tests) */ \
   X(bool, no_dead_t, false)        /* solve loop: store the iterate of every step (A/B, bit-identity tests) */ \
   X(bool, no_march3, false)        /* never use the 2-D tile form of the two-stage pass (csr_rowclass_march3_spmv) */ \
   X(long long, march3_k1, 0)       /* rows of the stage-1 region per lane (0: by the fill estimate; 2..4): tile height = K1 * (NT / (TX + 2)) - 2 */ \

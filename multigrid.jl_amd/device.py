@@ -206,6 +206,12 @@ SIGNATURES = {
     "mg_solve_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
     "mg_spmv_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _dp, _dp, _dp, _ll]),
     "mg_set_krylov_operator_CFP64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp]),
+    "mg_replace_krylov_values_CFP64": (C.c_int, [_vp, _dp, _ll]),
+    "mg_rap_CF64": (C.c_int, [_vp, _dp, _ll, _ll, _dp, _lp]),
+    "mg_rap_level_ms_CF64": (C.c_int, [_vp, _dp, _ll]),
+    "mg_get_values_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
+    "mg_get_relax_CF64": (C.c_int, [_vp, _ll, _dp, _ll]),
+    "mg_replace_values_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
     "mg_bicgstab_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_bicgstab_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_fgmres_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
@@ -904,6 +910,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         self.nrhs = int(nrhs if nrhs is not None else max(1, param.nrhs))
         if self.nrhs != 1:
             raise NotImplementedError("ComplexF64 hierarchies serve one right-hand side on the device")
+        self._op_nnz = {}
         lib = self.lib
         _check(lib, lib.mg_create_CF64(self.nlevels, 1, int(device_id), C.byref(self.handle)), "mg_create_CF64")
         try:
@@ -915,6 +922,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             raise
 
     def _set_op(self, level, which, M):
+        self._op_nnz[(int(level), int(which))] = int(M.nnz)     # (get_values sizes its array by it; patterns never change)
         if which != MG_OP_A:
             if np.iscomplexobj(M.data):
                 raise TypeError("P and R of a ComplexF64 hierarchy are real")
@@ -1033,6 +1041,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         uploaded last; a refused upload (wrong order) leaves the operator that was there."""
         if A is None:
             self._krylov_operator = None        # (whatever happens below, the object recorded is never one that is not uploaded)
+            self._krylov_pattern = None
             _check(self.lib, self.lib.mg_set_krylov_operator_CFP64_INT64(self.handle, self.n, None, None, None),
                    "mg_set_krylov_operator_CFP64")
             return
@@ -1045,11 +1054,32 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         nzval = np.ascontiguousarray(np.conj(M.data), dtype=np.complex128)     # the reference's AT values
         if M.shape[0] != M.shape[1]:
             raise ValueError("the Krylov operator must be square")
+        self._krylov_pattern = None             # (refused or not, the next update_krylov_operator uploads whole)
         _check(self.lib, self.lib.mg_set_krylov_operator_CFP64_INT64(self.handle, M.shape[0], _i64(colptr), _i64(rowval), _c128(nzval)),
                "mg_set_krylov_operator_CFP64")
         self._krylov_operator = A               # the object uploaded last (None: the fine level), whoever asked for it
+        self._krylov_pattern = (M.shape, M.indptr, M.indices)
+
+    def update_krylov_operator(self, A):
+        """``set_krylov_operator`` for an operator that usually changes its values only (a new medium on the same grid): when A
+        has - after the same sum_duplicates / sort_indices - the pattern uploaded last, its values replace the resident ones
+        (mg_replace_krylov_values_CFP64: a copy, nothing re-blocked); any other A, None included, is uploaded whole.  Either way
+        ``krylov_operator`` becomes A; a refused call leaves what was there."""
+        pat = self._krylov_pattern
+        if A is None or pat is None or self._krylov_operator is None:
+            return self.set_krylov_operator(A)
+        import scipy.sparse as sp
+        M = sp.csr_matrix(A, dtype=np.complex128, copy=True)
+        M.sum_duplicates()
+        M.sort_indices()
+        if M.shape != pat[0] or M.nnz != pat[2].size or not (np.array_equal(M.indptr, pat[1]) and np.array_equal(M.indices, pat[2])):
+            return self.set_krylov_operator(A)
+        nzval = np.ascontiguousarray(np.conj(M.data), dtype=np.complex128)     # the reference's AT values
+        _check(self.lib, self.lib.mg_replace_krylov_values_CFP64(self.handle, _c128(nzval), nzval.size), "mg_replace_krylov_values_CFP64")
+        self._krylov_operator = A
 
     _krylov_operator = None
+    _krylov_pattern = None                      # (shape, indptr, indices) of the operator uploaded last
 
     @property
     def krylov_operator(self):
@@ -1106,13 +1136,72 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         pb, px = self._dev_pair(b, x)
         _check(self.lib, self.lib.mg_cycle_dev_CFP64(self.handle, pb, px, self.n, int(x_is_zero)), "mg_cycle_dev_CFP64")
 
+    # -- replaceMatrixInHierarchy on the device (mg_rap_CF64 and the value replacements) ---------------------------------------
+    def replace_values(self, level: int, which: int, M):
+        """New values of one operator on its unchanged pattern: M.data complex (the applied A) for MG_OP_A, real for P and R."""
+        if which == MG_OP_A:
+            nz = np.ascontiguousarray(np.conj(M.data), dtype=np.complex128)     # the reference's AT values
+        else:
+            if np.iscomplexobj(M.data):
+                raise TypeError("P and R of a ComplexF64 hierarchy are real")
+            nz = np.ascontiguousarray(M.data, dtype=np.float64)
+        _check(self.lib, self.lib.mg_replace_values_CF64(self.handle, int(level), int(which), _f64(nz), M.data.size), "mg_replace_values_CF64")
+
+    def get_values(self, level: int, which: int) -> np.ndarray:
+        """Values of operator `which` of `level` as applied (stored CSR order): complex128 for A, float64 for P and R."""
+        if (int(level), int(which)) not in self._op_nnz:
+            raise MGDeviceError(f"get_values: level {level} holds no operator {which}")
+        vals = np.zeros(self._op_nnz[(int(level), int(which))], dtype=np.complex128 if which == MG_OP_A else np.float64)
+        _check(self.lib, self.lib.mg_get_values_CF64(self.handle, int(level), int(which), _f64(vals), vals.size), "mg_get_values_CF64")
+        return np.conjugate(vals, out=vals) if which == MG_OP_A else vals
+
+    def replace_matrix(self, param, A_new, timings: Optional[dict] = None) -> None:
+        """replaceMatrixInHierarchy on the device, the complex twin of DeviceHierarchy.replace_matrix: numeric Galerkin products
+        and relaxPrecs on the fixed patterns (mg_rap_CF64), host copies of the hierarchy refreshed from HBM, coarsest level
+        re-factored on the host.  ``timings`` (a dict) receives the seconds of the three parts."""
+        import time
+        lib = self.lib
+        t0 = time.perf_counter()
+        nz = np.ascontiguousarray(np.conj(A_new.data), dtype=np.complex128)     # the reference's AT values
+        rp = param.relaxParam
+        omega = np.ascontiguousarray([float(rp[l]) if isinstance(rp, (list, tuple, np.ndarray)) else float(rp)
+                                      for l in range(self.nlevels)], dtype=np.float64)
+        kind = 1 if param.relaxType == "SPAI" else 0
+        done = C.c_longlong(0)
+        _check(lib, lib.mg_rap_CF64(self.handle, _c128(nz), nz.size, kind, _f64(omega), C.byref(done)), "mg_rap_CF64")
+        t1 = time.perf_counter()
+        param.As[0] = A_new
+        for l in range(2, self.nlevels + 1):                       # refresh the host copies (same patterns)
+            M = param.As[l - 1]
+            vals = np.empty(M.nnz, dtype=np.complex128)
+            _check(lib, lib.mg_get_values_CF64(self.handle, l, MG_OP_A, _c128(vals), vals.size), "mg_get_values_CF64")
+            np.conjugate(vals, out=M.data)
+        for l in range(1, self.nlevels):
+            d = np.empty(param.As[l - 1].shape[0], dtype=np.complex128)
+            _check(lib, lib.mg_get_relax_CF64(self.handle, l, _c128(d), d.size), "mg_get_relax_CF64")
+            param.relaxPrecs[l - 1] = d
+        t2 = time.perf_counter()
+        from .mgsetup import defineCoarsestAinv
+        defineCoarsestAinv(param, param.As[-1])                      # (MGsetup.jl:323-355)
+        self._set_coarse(param)
+        _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        if timings is not None:
+            timings.update(rap=t1 - t0, readback=t2 - t1, coarsest=time.perf_counter() - t2)
+
+    def rap_level_ms(self) -> np.ndarray:
+        """Device milliseconds of the last replace_matrix per level (relaxPrecs[l] and As[l+1] together; mg_rap_level_ms_CF64)."""
+        out = np.zeros(self.nlevels - 1)
+        _check(self.lib, self.lib.mg_rap_level_ms_CF64(self.handle, _f64(out), out.size), "mg_rap_level_ms_CF64")
+        return out
+
     def _refuse(self, *args, **kwargs):
-        raise NotImplementedError("PCG, the block Krylov drivers, the replace / transpose updates and the other device-pointer entry "
-                                  "points serve FP64 hierarchies only (ComplexF64: bicgstab, fgmres, cycle_dev and their _dev forms)")
+        raise NotImplementedError("PCG, the block Krylov drivers, transposeHierarchy and the other device-pointer entry points serve "
+                                  "FP64 hierarchies only (ComplexF64: bicgstab, fgmres, cycle_dev and their _dev forms; replace_matrix, "
+                                  "replace_values, get_values)")
 
     pcg = cycle_mixed_f32 = pcg_dev = block_pcg_dev = block_bicgstab_dev = block_fgmres_dev = _refuse
     solve_dev = spmv_dev = fused_dev = sweep_residual_dev = four_stage_dev = _refuse
-    replace_values = replace_matrix = transpose_hierarchy = get_values = cycle_async_dev = _refuse
+    transpose_hierarchy = cycle_async_dev = _refuse
 
 
 def complex_lu_arrays(lu):

@@ -280,7 +280,12 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
     """New fine matrix, same P/R: recompute relaxPrecs, Galerkin products and the coarse LU (MGsetup.jl:226-270)."""
     relaxParamArr = _relax_param_arr(param)
     A = _of_val(param, A)
-    if param.device is not None and not is_complex(param) and param.relaxType in ("Jac", "Jac-GMRES", "SPAI"):
+    on_device = param.device is not None and param.relaxType in ("Jac", "Jac-GMRES", "SPAI")
+    if on_device and is_complex(param):
+        # (mg_rap_CF64.  A Schwarz coarsest solver borrows a device handle of its own, set up on the coarsest matrix: host path)
+        from .mgdef import _solver_object
+        on_device = param.relaxType != "Jac-GMRES" and _solver_object(param.LU) != "dd"
+    if on_device:
         old = param.As[0]
         same = (A.shape == old.shape and A.nnz == old.nnz and np.array_equal(A.indptr, old.indptr)
                 and np.array_equal(A.indices, old.indices))

@@ -139,7 +139,7 @@ def _complex_krylov_device(A, param: MGparam, b, x0, what: str):
     if A is not None and param.As and A is param.As[0]:
         A = None
     if A is not dev.krylov_operator:          # recorded by set_krylov_operator itself: a direct call to it is seen here
-        dev.set_krylov_operator(A)
+        dev.update_krylov_operator(A)         # (the pattern uploaded last: new values only)
     return dev, b.reshape(-1) if b.ndim == 2 else b, x0.reshape(-1) if x0.ndim == 2 else x0
 
 
