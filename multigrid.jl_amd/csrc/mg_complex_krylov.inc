@@ -7,8 +7,9 @@
 //   * The preconditioner is cx_cycle from x = 0 on the input vector.  Its result lives in lev[0].x[xi] and the next cycle overwrites
 //     it, so it is COPIED OUT where it outlives the next cycle (BiCGSTAB's phat, FGMRES's Z_i; cx_cycle is left as it is); BiCGSTAB's
 //     shat is consumed before the next cycle and is read where the cycle left it.
-//   * The algorithms are bicgstab_dev / fgmres_core of mg_krylov.inc with complex scalars and conjugated dots (dot(a, b) = sum conj(a_i) b_i);
-//     flags, stopping tests and the layout of resvec are theirs.  Every vector update and every scalar is one fused pass of mg_cxvec.hpp.
+//   * BiCGSTAB is bicgstab_dev of mg_krylov.inc with complex scalars and conjugated dots (dot(a, b) = sum conj(a_i) b_i); FGMRES is
+//     fgmres_loop of mg_krylov.inc itself, on the space CxFgmres with HessenbergLsq<std::complex<double>> (mg_krylov_host.hpp).  Flags,
+//     stopping tests and the layout of resvec are theirs.  Every vector update and every scalar is one fused pass of mg_cxvec.hpp.
 //   * Host synchronisations per iteration: BiCGSTAB 4 (dot(rtld, v) ; ||s|| ; (dot(t, s), dot(t, t)) ; (||r||, the next rho)), FGMRES 1 per
 //     inner step (the chained Gram-Schmidt leaves the i + 2 scalars of a step in HBM; one readback).
 // Also here: the stand-alone entry points of the passes (mg_cvec_*_dev_CFP64) and mg_cycle_dev_CFP64.
@@ -132,29 +133,23 @@ int cx_bicgstab_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, double tol, long lo
   MG_TRY(K.ensure(6));
   cx_t *r = K.vec(0), *p = K.vec(1), *v = K.vec(2), *rtld = K.vec(3), *t = K.vec(4), *phat = K.vec(5);
   const double* sc = nullptr;
-  long long it = 0, flag = -1, nr = 0;
-  auto finish = [&](long long f) {
-    if (iters) *iters = it;
-    if (flag_out) *flag_out = f;
-    if (nres) *nres = nr;
-    return (int)MG_OK;
-  };
+  long long it = 0, flag = -1;
+  KrylovReport rep(iters, flag_out, resvec, nres);
   MG_TRY(K.dot1(b, b));
   MG_TRY(K.read(1, &sc));
   const double bn = std::sqrt(sc[0]);
   if (bn == 0.0) {
     MG_TRY(K.zero(x));
     HIP_TRY(spin_sync(K.st));
-    return finish(-9);
+    return rep.finish(0, -9);
   }
   MG_TRY(K.residual(b, x, r));
   MG_TRY(K.dot1(r, r));                               // ||r0||^2, and rho of the first iteration (rtld = r0)
   MG_TRY(K.read(2, &sc));
   double err = std::sqrt(sc[0]) / bn;
   zc rho(sc[0], sc[1]), rho1(0.0, 0.0), alpha(0.0, 0.0), omega(1.0, 0.0);
-  if (resvec) resvec[nr] = err;
-  ++nr;
-  if (err < tol) return finish(0);
+  rep.record(err);
+  if (err < tol) return rep.finish(0, 0);
   MG_TRY(K.copy(rtld, r));
   for (long long k = 1; k <= maxIter; ++k) {
     it = k;
@@ -175,8 +170,7 @@ int cx_bicgstab_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, double tol, long lo
     MG_TRY(K.pass(mgcv::OpCBicgS{cxv(alpha), v, r}, {v, r}));                           // s = r - alpha v (in r) ; ||s||^2
     MG_TRY(K.read(1, &sc));                                                             // synchronisation 2
     const double sn = std::sqrt(sc[0]) / bn;
-    if (resvec) resvec[nr] = sn;
-    ++nr;
+    rep.record(sn);
     if (sn < tol) {                                                                     // converged on the half step
       const double ma[2] = {-alpha.real(), -alpha.imag()};
       const double* vs[1] = {reinterpret_cast<const double*>(phat)};
@@ -192,122 +186,92 @@ int cx_bicgstab_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, double tol, long lo
     MG_TRY(K.pass(mgcv::OpCBicgXR{cxv(alpha), cxv(omega), phat, z, t, rtld, x, r}, {phat, z, t, rtld, x, r}));
     MG_TRY(K.read(3, &sc));                                                             // synchronisation 4: ||r||^2 and the next rho
     err = std::sqrt(sc[0]) / bn;
-    if (resvec) resvec[nr] = err;
-    ++nr;
+    rep.record(err);
     if (err <= tol) { flag = 0; break; }
     if (omega == zc(0.0, 0.0)) { flag = -2; break; }
     rho1 = rho;
     rho = zc(sc[1], sc[2]);
   }
   HIP_TRY(spin_sync(K.st));
-  return finish(flag);
+  return rep.finish(it, flag);
 }
 
-// fgmres_core (mg_krylov.inc) for complex vectors.  H[k,i] = dot(V_k, w), H[i+1,i] = ||w|| (real).  The rotation of column i has a
-// complex cosine and a real sine: rr = sqrt(|a|^2 + b^2), c = a / rr, s = b / rr with a = H[i,i], b = H[i+1,i]; it is applied as
-// t = conj(c) H[k] + s H[k+1] ; H[k+1] = -s H[k] + c H[k+1] ; H[k] = t, and to the right-hand side as s_{i+1} = -s s_i ; s_i = conj(c) s_i.
+// The space fgmres_loop (mg_krylov.inc) runs on for complex vectors: H[k,i] = dot(V_k, w), H[i+1,i] = ||w|| (real); the rotations with
+// a complex cosine and a real sine are HessenbergLsq<std::complex<double>> (mg_krylov_host.hpp).
+struct CxFgmres {
+  CxKry& K;
+  const long long n;
+  const int m;
+  const cx_t* b;
+  cx_t* x;
+  cx_t *V, *Z, *r;                       // m+1 basis vectors, m preconditioned vectors, residual
+  std::vector<double> ny;
+  std::vector<const double*> zp;
+  CxFgmres(CxKry& K_, int m_, const cx_t* b_, cx_t* x_)
+      : K(K_), n(K_.n), m(m_), b(b_), x(x_), V(K_.vec(0)), Z(K_.vec((size_t)m_ + 1)), r(K_.vec((size_t)2 * m_ + 1)), ny((size_t)2 * m_), zp((size_t)m_) {
+    for (int i = 0; i < m; ++i) zp[(size_t)i] = reinterpret_cast<const double*>(Z + (size_t)i * n);
+  }
+  int norm(const cx_t* v, double* out) {
+    const double* sc = nullptr;
+    MG_TRY(K.dot1(v, v));
+    MG_TRY(K.read(1, &sc));
+    *out = std::sqrt(sc[0]);
+    return MG_OK;
+  }
+  int norm_b(double* out) { return norm(b, out); }
+  int zero_x() { return K.zero(x); }
+  int sync() {
+    HIP_TRY(spin_sync(K.st));
+    return MG_OK;
+  }
+  int done() { return MG_OK; }
+  int residual(double* rn) {
+    MG_TRY(K.residual(b, x, r));
+    return norm(r, rn);
+  }
+  int start_basis(double rn) { return K.pass(mgcv::OpCScale{cx_t{1.0 / rn, 0.0}, r, V}, {r, V}); }
+  int arnoldi(int i, HessenbergLsq<zc>& G) {
+    const double* sc = nullptr;
+    double* hd = K.scal();
+    cx_t* vi = V + (size_t)i * n;
+    cx_t* zi = Z + (size_t)i * n;
+    cx_t* w = V + (size_t)(i + 1) * n;
+    const cx_t* z = nullptr;
+    MG_TRY(K.prec(vi, &z));                                                         // z = M(V[:,i])
+    MG_TRY(K.copy(zi, z));
+    MG_TRY(K.product(zi, w));                                                       // w = A z
+    // modified Gram-Schmidt as one chain on the device: h_k = dot(V_k, w) stays in HBM, the update w -= h_k V_k reads it there and
+    // leaves the partials of the next dot (or of ||w||^2) in the same pass; the i + 2 scalars come back in ONE readback
+    MG_TRY(K.dot1(V, w));
+    for (int k = 0; k <= i; ++k) {
+      const cx_t* vk = V + (size_t)k * n;
+      const cx_t* u = k < i ? V + (size_t)(k + 1) * n : nullptr;
+      MG_TRY(cxv_launch(mgcv::OpCMgsStep{hd + 2 * k, vk, u, w}, n, {vk, u ? u : vk, w}, K.part(), 2, hd + 2 * (k + 1), K.st));
+    }
+    MG_TRY(K.read(2 * (i + 2), &sc));
+    for (int k = 0; k <= i; ++k) G.h(k, i) = zc(sc[2 * k], sc[2 * k + 1]);
+    const double wn = std::sqrt(sc[2 * (i + 1)]);
+    G.hsub(i) = wn;
+    if (wn != 0.0) MG_TRY(K.pass(mgcv::OpCScale{cx_t{1.0 / wn, 0.0}, w, w}, {w}));  // V[:,i+1] = w/||w||
+    return MG_OK;
+  }
+  int update_x(int used, const zc* y) {
+    for (int i = 0; i < used; ++i) {
+      ny[2 * (size_t)i] = -y[i].real();
+      ny[2 * (size_t)i + 1] = -y[i].imag();
+    }
+    if (used > 0) MG_TRY(cxv_gs_update(used, ny.data(), zp.data(), reinterpret_cast<double*>(x), n, K.part(), nullptr, K.st));
+    return MG_OK;
+  }
+};
 int cx_fgmres_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, long long inner, double tol, long long maxIter, long long* iters,
                   long long* flag_out, double* resvec, long long* nres) {
   const int m = (int)inner;
   CxKry K(h);
   MG_TRY(K.ensure((size_t)(2 * m + 2)));
-  const long long n = K.n;
-  cx_t* V = K.vec(0);                    // m+1 basis vectors
-  cx_t* Z = K.vec((size_t)m + 1);        // m preconditioned vectors
-  cx_t* r = K.vec((size_t)2 * m + 1);    // residual
-  const double* sc = nullptr;
-  long long nr = 0, flag = -1, total = 0;
-  auto finish = [&](long long f) {
-    if (iters) *iters = total;
-    if (flag_out) *flag_out = f;
-    if (nres) *nres = nr;
-    return (int)MG_OK;
-  };
-  MG_TRY(K.dot1(b, b));
-  MG_TRY(K.read(1, &sc));
-  const double bn = std::sqrt(sc[0]);
-  if (bn == 0.0) {
-    MG_TRY(K.zero(x));
-    HIP_TRY(spin_sync(K.st));
-    return finish(-9);
-  }
-  MG_TRY(K.residual(b, x, r));
-  MG_TRY(K.dot1(r, r));
-  MG_TRY(K.read(1, &sc));
-  double rn = std::sqrt(sc[0]);
-  double err = rn / bn;
-  if (err < tol) return finish(0);
-  std::vector<zc> H((size_t)(m + 1) * m), cs((size_t)m), s((size_t)m + 1), y((size_t)m);
-  std::vector<double> sn((size_t)m, 0.0), ny((size_t)2 * m);
-  std::vector<const double*> zp((size_t)m);
-  for (int i = 0; i < m; ++i) zp[(size_t)i] = reinterpret_cast<const double*>(Z + (size_t)i * n);
-  auto Hat = [&](int i, int j) -> zc& { return H[(size_t)i * m + j]; };
-  double* hd = K.scal();
-  for (long long it = 1; it <= maxIter && flag != 0; ++it) {
-    MG_TRY(K.pass(mgcv::OpCScale{cx_t{1.0 / rn, 0.0}, r, V}, {r, V}));               // V[:,1] = r/||r||
-    std::fill(H.begin(), H.end(), zc(0.0, 0.0));
-    std::fill(s.begin(), s.end(), zc(0.0, 0.0));
-    s[0] = rn;
-    int used = 0;
-    for (int i = 0; i < m; ++i) {
-      cx_t* vi = V + (size_t)i * n;
-      cx_t* zi = Z + (size_t)i * n;
-      cx_t* w = V + (size_t)(i + 1) * n;
-      const cx_t* z = nullptr;
-      MG_TRY(K.prec(vi, &z));                                                         // z = M(V[:,i])
-      MG_TRY(K.copy(zi, z));
-      MG_TRY(K.product(zi, w));                                                       // w = A z
-      // modified Gram-Schmidt as one chain on the device: h_k = dot(V_k, w) stays in HBM, the update w -= h_k V_k reads it there and
-      // leaves the partials of the next dot (or of ||w||^2) in the same pass; the i + 2 scalars come back in ONE readback
-      MG_TRY(K.dot1(V, w));
-      for (int k = 0; k <= i; ++k) {
-        const cx_t* vk = V + (size_t)k * n;
-        const cx_t* u = k < i ? V + (size_t)(k + 1) * n : nullptr;
-        MG_TRY(cxv_launch(mgcv::OpCMgsStep{hd + 2 * k, vk, u, w}, n, {vk, u ? u : vk, w}, K.part(), 2, hd + 2 * (k + 1), K.st));
-      }
-      MG_TRY(K.read(2 * (i + 2), &sc));
-      for (int k = 0; k <= i; ++k) Hat(k, i) = zc(sc[2 * k], sc[2 * k + 1]);
-      const double wn = std::sqrt(sc[2 * (i + 1)]);
-      Hat(i + 1, i) = wn;
-      if (wn != 0.0) MG_TRY(K.pass(mgcv::OpCScale{cx_t{1.0 / wn, 0.0}, w, w}, {w}));  // V[:,i+1] = w/||w||
-      for (int k = 0; k < i; ++k) {                                                   // previous rotations
-        const zc t = std::conj(cs[(size_t)k]) * Hat(k, i) + sn[(size_t)k] * Hat(k + 1, i);
-        Hat(k + 1, i) = -sn[(size_t)k] * Hat(k, i) + cs[(size_t)k] * Hat(k + 1, i);
-        Hat(k, i) = t;
-      }
-      const zc a = Hat(i, i);
-      const double rr = std::sqrt(std::norm(a) + wn * wn);
-      cs[(size_t)i] = (rr == 0.0) ? zc(1.0, 0.0) : a / rr;
-      sn[(size_t)i] = (rr == 0.0) ? 0.0 : wn / rr;
-      Hat(i, i) = rr;
-      Hat(i + 1, i) = 0.0;
-      s[(size_t)i + 1] = -sn[(size_t)i] * s[(size_t)i];
-      s[(size_t)i] = std::conj(cs[(size_t)i]) * s[(size_t)i];
-      err = std::abs(s[(size_t)i + 1]) / bn;
-      if (resvec) resvec[nr] = err;
-      ++nr;
-      ++total;
-      used = i + 1;
-      if (err <= tol) { flag = 0; break; }
-    }
-    for (int i = used - 1; i >= 0; --i) {                                             // y = H \ s (upper triangular)
-      zc acc = s[(size_t)i];
-      for (int k = i + 1; k < used; ++k) acc -= Hat(i, k) * y[(size_t)k];
-      y[(size_t)i] = acc / Hat(i, i);
-      ny[2 * (size_t)i] = -y[(size_t)i].real();
-      ny[2 * (size_t)i + 1] = -y[(size_t)i].imag();
-    }
-    if (used > 0) MG_TRY(cxv_gs_update(used, ny.data(), zp.data(), reinterpret_cast<double*>(x), n, K.part(), nullptr, K.st));   // x += Z y
-    if (flag == 0) break;
-    MG_TRY(K.residual(b, x, r));
-    MG_TRY(K.dot1(r, r));
-    MG_TRY(K.read(1, &sc));
-    rn = std::sqrt(sc[0]);
-    err = rn / bn;
-    if (err <= tol) { flag = 0; break; }
-  }
-  HIP_TRY(spin_sync(K.st));
-  return finish(flag);
+  CxFgmres sp(K, m, b, x);
+  KrylovReport rep(iters, flag_out, resvec, nres);
+  return fgmres_loop<zc>(sp, m, tol, maxIter, rep);
 }
 
 // the checks every driver entry point shares; host form: b, x staged through the handle's device buffers

@@ -241,7 +241,7 @@ int dist_fill(mg_dist* h, double* x, long long n, double val) {
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
-// FGMRES_relaxation (FGMRES.jl:48-126) on a sharded level - the mirror of fgmres_relax: x0 += Z*t where t minimises
+// FGMRES_relaxation (FGMRES.jl:48-126) on a sharded level - the mirror of fgmres_relax, sharing its least squares (RelaxLsq): x0 += Z*t where t minimises
 // ||r0 - A Z t|| over the `inner` directions z_1 = M r0, z_j = M (A z_{j-1}).  Products with A exchange the halo of z (the
 // vectors of Z are cap_x long: owned rows + halo tail), dots are all-reduced, so the small pseudo-inverse and the
 // data-dependent exit (l.114-117) come out identical on every rank.
@@ -262,7 +262,7 @@ int dist_fgmres_relax(mg_dist* h, DistLevel& L, const double* r0, double* x0, lo
   if (AZbuf.n < (size_t)k * (size_t)n) MG_TRY(AZbuf.alloc((size_t)k * (size_t)n));
   double rnorm0 = 0.0;
   MG_TRY(dist_norm(h, r0, n, &rnorm0));
-  std::vector<double> H((size_t)k * k, 0.0), xi((size_t)k, 0.0), t((size_t)k, 0.0), Pinv;
+  RelaxLsq Q(k);
   int used = 0;
   for (int j = 0; j < k; ++j) {
     double* z = Zbuf.p + (size_t)j * (size_t)L.cap_x;
@@ -273,28 +273,14 @@ int dist_fgmres_relax(mg_dist* h, DistLevel& L, const double* r0, double* x0, lo
     for (int i = 0; i <= j; ++i) {                                           // t = AZ' * w              (l.95)
       double d = 0.0;
       MG_TRY(dist_dot(h, AZbuf.p + (size_t)i * (size_t)n, w, n, &d));
-      H[(size_t)i * k + j] = d;
-      H[(size_t)j * k + i] = d;
+      Q.set(i, j, d);
     }
-    MG_TRY(dist_dot(h, w, r0, n, &xi[(size_t)j]));                           // xi[j] = dot(w, r0)       (l.97)
-    pinv_sym(H, k, Pinv);                                                    // t = pinv(H)*xi           (l.102)
-    double tHt = 0.0, txi = 0.0;
-    for (int a = 0; a < k; ++a) {
-      double sacc = 0.0;
-      for (int b = 0; b < k; ++b) sacc += Pinv[(size_t)a * k + b] * xi[(size_t)b];
-      t[(size_t)a] = sacc;
-    }
-    for (int a = 0; a < k; ++a) {
-      double sacc = 0.0;
-      for (int b = 0; b < k; ++b) sacc += H[(size_t)a * k + b] * t[(size_t)b];
-      tHt += t[(size_t)a] * sacc;
-      txi += t[(size_t)a] * xi[(size_t)a];
-    }
-    const double rn = std::sqrt(std::fabs(tHt - 2.0 * txi + rnorm0 * rnorm0));   // l.104
+    MG_TRY(dist_dot(h, w, r0, n, &Q.xi[(size_t)j]));                         // xi[j] = dot(w, r0)       (l.97)
+    const double rn = Q.step(rnorm0);                                        // t = pinv(H)*xi, ||r0 - AZ t||  (l.102-104)
     if (rn < TOL) break;                                                          // l.114-117
   }
   for (int j = 0; j < used; ++j)                                             // x0 += Z*t                (l.121-123)
-    MG_TRY(dist_axpby(h, t[(size_t)j], Zbuf.p + (size_t)j * (size_t)L.cap_x, (j == 0 && x0_is_zero) ? 0.0 : 1.0, x0, n));
+    MG_TRY(dist_axpby(h, Q.t()[(size_t)j], Zbuf.p + (size_t)j * (size_t)L.cap_x, (j == 0 && x0_is_zero) ? 0.0 : 1.0, x0, n));
   return MG_OK;
 }
 }  // extern "C++"

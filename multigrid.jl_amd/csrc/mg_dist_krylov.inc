@@ -1,7 +1,8 @@
 // mg_dist_krylov.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip behind mg_dist.inc; not compiled on its own).
 // MG-preconditioned Krylov drivers on the HALO form of the sharded hierarchy (mg_dist_*): solveCG_MG / solveBiCGSTAB_MG / solveGMRES_MG
 // (SolveFuncs.jl:74-133) for hierarchies of general CSR operators (SA-AMG: SAAMGWrapper.jl:61-73 enters through PCG and BiCGSTAB only).
-// The algorithms, flags and resvec layouts are those of pcg_dev / bicgstab_dev / fgmres_core in mg_krylov.inc.  On this form
+// The algorithms, flags and resvec layouts are those of pcg_dev / bicgstab_dev / fgmres_core in mg_krylov.inc; FGMRES IS that file's
+// fgmres_loop on the space DistFgmres, and every driver reports through KrylovReport (mg_krylov_host.hpp).  On this form
 //   * a product with A is dist_apply_A on level 1: ONE halo exchange of its input, overlapped with the interior rows.  The inputs are the
 //     cycle's own level-1 buffers (x0 / x1, cap_x long: the preconditioned vector is multiplied where the cycle left it) and PCG's p;
 //   * the preconditioner is one dist_cycle from x = 0;
@@ -25,16 +26,20 @@ int krv_head(const void* const* ptrs, int np, long long n, long long* head) {
 }
 // one pass + (ns > 0) the sums of its first ns scalars into out[0 .. ns)
 template <class Op>
-int krv_launch(const Op& op, long long n, std::initializer_list<const void*> ptrs, double* part, int ns, double* out, hipStream_t s) {
+int krv_launch(const Op& op, long long n, const void* const* ptrs, int np, double* part, int ns, double* out, hipStream_t s) {
   if (n < 1) return fail(MG_ERR_INVALID, "a fused pass needs n >= 1");
   if (Op::NS > 0 && (!part || (ns > 0 && !out))) return fail(MG_ERR_INVALID, "a fused pass with sums needs its work space and output");
   long long head = 0;
-  MG_TRY(krv_head(ptrs.begin(), (int)ptrs.size(), n, &head));
+  MG_TRY(krv_head(ptrs, np, n, &head));
   const int nb = mgkv::krv_grid(n);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(mgkv::krv_pass<Op>), dim3(nb), dim3(mgkv::KB), 0, s, op, n, head, part);
   if (Op::NS > 0 && ns > 0) hipLaunchKernelGGL(mgkv::krv_final, dim3(ns), dim3(mgkv::KB), 0, s, part, nb, out);
   HIP_TRY(hipGetLastError());
   return MG_OK;
+}
+template <class Op>
+int krv_launch(const Op& op, long long n, std::initializer_list<const void*> ptrs, double* part, int ns, double* out, hipStream_t s) {
+  return krv_launch(op, n, ptrs.begin(), (int)ptrs.size(), part, ns, out, s);
 }
 int krv_dots(int k, const double* const* xs, const double* const* ys, long long n, double* part, double* out, hipStream_t s) {
   if (k < 1 || k > mgkv::MAXS || !xs || !ys) return fail(MG_ERR_INVALID, "dots: 1 to %d pairs", mgkv::MAXS);
@@ -48,13 +53,7 @@ int krv_dots(int k, const double* const* xs, const double* const* ys, long long 
     ptrs[2 * c] = op.x[c];
     ptrs[2 * c + 1] = op.y[c];
   }
-  long long head = 0;
-  MG_TRY(krv_head(ptrs, 2 * mgkv::MAXS, n, &head));
-  const int nb = mgkv::krv_grid(n);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(mgkv::krv_pass<mgkv::OpDots>), dim3(nb), dim3(mgkv::KB), 0, s, op, n, head, part);
-  hipLaunchKernelGGL(mgkv::krv_final, dim3(k), dim3(mgkv::KB), 0, s, part, nb, out);
-  HIP_TRY(hipGetLastError());
-  return MG_OK;
+  return krv_launch(op, n, ptrs, 2 * mgkv::MAXS, part, k, out, s);
 }
 // w -= sum_j h_j v_j over any number of vectors, 8 per pass; the last pass leaves ||w||^2 in out[0] when out is given
 int krv_gs_update(int m, const double* hcoef, const double* const* vs, double* w, long long n, double* part, double* out, hipStream_t s) {
@@ -70,13 +69,8 @@ int krv_gs_update(int m, const double* hcoef, const double* const* vs, double* w
     const void* ptrs[mgkv::MAXS + 1];
     for (int j = 0; j < mgkv::MAXS; ++j) ptrs[j] = op.v[j];
     ptrs[mgkv::MAXS] = w;
-    long long head = 0;
-    MG_TRY(krv_head(ptrs, mgkv::MAXS + 1, n, &head));
-    const int nb = mgkv::krv_grid(n);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(mgkv::krv_pass<mgkv::OpGsUpdate>), dim3(nb), dim3(mgkv::KB), 0, s, op, n, head, part);
-    if (last && out) hipLaunchKernelGGL(mgkv::krv_final, dim3(1), dim3(mgkv::KB), 0, s, part, nb, out);
+    MG_TRY(krv_launch(op, n, ptrs, mgkv::MAXS + 1, part, (last && out) ? 1 : 0, out, s));
   }
-  HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 
@@ -125,6 +119,11 @@ struct DistKry {
     MG_TRY(copy(L.x0.p, x_own));
     return dist_apply_A(h, L, MG_K_RESIDUAL, L.x0.p, r, b);
   }
+  int zero(double* x) {                          // the b = 0 exit: zeros, stream drained (flag -9 is the driver's)
+    MG_TRY(dist_fill(h, x, n, 0.0));
+    HIP_TRY(spin_sync(h->stream));
+    return MG_OK;
+  }
 };
 
 int dist_krylov_ready(mg_dist* h, const double* b, double* x, long long n_own, long long maxIter) {
@@ -133,14 +132,6 @@ int dist_krylov_ready(mg_dist* h, const double* b, double* x, long long n_own, l
   if (h->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "the sharded Krylov drivers of the halo form take one right-hand side (this handle: %lld)", h->nrhs);
   if (n_own != h->lev[0].n_own) return fail(MG_ERR_INVALID, "n_own=%lld but this rank owns %lld fine rows", n_own, h->lev[0].n_own);
   (void)hipSetDevice(h->device);
-  return MG_OK;
-}
-int dist_krylov_zero_rhs(DistKry& D, double* x, long long* iters, long long* flag, long long* nres) {   // b = 0: zeros, flag -9
-  MG_TRY(dist_fill(D.h, x, D.n, 0.0));
-  HIP_TRY(spin_sync(D.h->stream));
-  if (iters) *iters = 0;
-  if (flag) *flag = -9;
-  if (nres) *nres = 0;
   return MG_OK;
 }
 
@@ -163,7 +154,11 @@ int dist_pcg(mg_dist* h, const double* b, double* x, double tol, long long maxIt
   MG_TRY(D.dot1(b, b, 0));
   MG_TRY(D.reduce(1, &s));
   const double nr0 = std::sqrt(s[0]);
-  if (nr0 == 0.0) return dist_krylov_zero_rhs(D, x, iters, flag_out, nullptr);
+  KrylovReport rep(iters, flag_out, resvec, nullptr);
+  if (nr0 == 0.0) {
+    MG_TRY(D.zero(x));
+    return rep.finish(0, -9);
+  }
   MG_TRY(D.residual(b, x, r));                                        // r = b - A(x)
   double* z = nullptr;
   MG_TRY(D.prec(r, &z));                                              // z = M(r)
@@ -189,7 +184,7 @@ int dist_pcg(mg_dist* h, const double* b, double* x, double tol, long long maxIt
       summed = true;
     }
     double rel = std::sqrt(rr_new) / nr0;
-    if (resvec) resvec[k - 1] = rel;
+    rep.set(k - 1, rel);
     if (rel <= tol) { flag = 0; break; }
     MG_TRY(D.prec(r, &z));                                            // z = M(r)
     double zr = 0.0;
@@ -203,16 +198,14 @@ int dist_pcg(mg_dist* h, const double* b, double* x, double tol, long long maxIt
       MG_TRY(D.reduce(2, &s));
       rr = s[0];
       zr = s[1];
-      if (resvec) resvec[k - 1] = std::sqrt(rr) / nr0;
+      rep.set(k - 1, std::sqrt(rr) / nr0);
     }
     const double beta = zr / gamma;
     gamma = zr;
     MG_TRY(D.pass(mgkv::OpXpby{beta, z, p}, {z, p}));                 // p = z + beta p
   }
   HIP_TRY(spin_sync(h->stream));
-  if (iters) *iters = it;
-  if (flag_out) *flag_out = flag;
-  return MG_OK;
+  return rep.finish(it, flag);
 }
 
 // KrylovMethods.bicgstb (M1 = the cycle, M2 = identity) as restated above bicgstab_dev.  Scalars per iteration:
@@ -237,20 +230,20 @@ int dist_bicgstab(mg_dist* h, const double* b, double* x, double tol, long long 
   MG_TRY(D.dot1(b, b, 0));
   MG_TRY(D.reduce(1, &s));
   const double bn = std::sqrt(s[0]);
-  if (bn == 0.0) return dist_krylov_zero_rhs(D, x, iters, flag_out, nres);
+  KrylovReport rep(iters, flag_out, resvec, nres);
+  if (bn == 0.0) {
+    MG_TRY(D.zero(x));
+    return rep.finish(0, -9);
+  }
   MG_TRY(D.residual(b, x, r));
   MG_TRY(D.dot1(r, r, 0));
   MG_TRY(D.reduce(1, &s));
   double rho = s[0], err = std::sqrt(s[0]) / bn;
-  long long it = 0, flag = -1, nr = 0;
-  if (resvec) resvec[nr] = err;
-  ++nr;
+  long long it = 0, flag = -1;
+  rep.record(err);
   if (err < tol) {
     HIP_TRY(spin_sync(h->stream));
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = 0;
-    if (nres) *nres = nr;
-    return MG_OK;
+    return rep.finish(0, 0);
   }
   MG_TRY(D.copy(rtld, r));
   double omega = 1.0, alpha = 0.0, rho1 = 0.0;
@@ -276,8 +269,7 @@ int dist_bicgstab(mg_dist* h, const double* b, double* x, double tol, long long 
     MG_TRY(D.pass(mgkv::OpBicgTS{t, r}, {t, r}, 1));                  // t's, t't -> scalars 1, 2
     MG_TRY(D.reduce(3, &s));
     const double sn = std::sqrt(s[0]) / bn, ts = s[1], tt = s[2];
-    if (resvec) resvec[nr] = sn;
-    ++nr;
+    rep.record(sn);
     if (sn < tol) {                                                   // converged on the half step
       const double ma = -alpha;
       const double* vs[1] = {phat};
@@ -289,117 +281,89 @@ int dist_bicgstab(mg_dist* h, const double* b, double* x, double tol, long long 
     MG_TRY(D.pass(mgkv::OpBicgXR{alpha, omega, phat, z, t, rtld, x, r}, {phat, z, t, rtld, x, r}));   // x += alpha phat + omega shat ; r = s - omega t
     MG_TRY(D.reduce(2, &s));
     err = std::sqrt(s[0]) / bn;
-    if (resvec) resvec[nr] = err;
-    ++nr;
+    rep.record(err);
     if (err <= tol) { flag = 0; break; }
     if (omega == 0.0) { flag = -2; break; }
     rho1 = rho;
     rho = s[1];
   }
   HIP_TRY(spin_sync(h->stream));
-  if (iters) *iters = it;
-  if (flag_out) *flag_out = flag;
-  if (nres) *nres = nr;
-  return MG_OK;
+  return rep.finish(it, flag);
 }
 
 // KrylovMethods.fgmres as restated above fgmres_core (precond 0).  The Arnoldi step orthogonalises w = A z against v_1 .. v_{i+1} with the
 // i + 1 dots taken TOGETHER on the incoming w (one pass, one all-reduce per 8 of them) and the update w -= sum h_k v_k fused with ||w||^2
 // (second all-reduce): 2 all-reduces per inner step for inner <= 8 where taking each dot behind the previous update costs i + 2.  The two
 // orderings differ by the loss of orthogonality of v_1 .. v_{i+1} times rounding, far below the 1e-10 the drivers are held to.
+struct DistFgmres {   // the space fgmres_loop (mg_krylov.inc) runs on
+  DistKry& D;
+  mg_dist* h;
+  const long long n;
+  const int m;
+  const double* b;
+  double* x;
+  double *V, *Z, *r;                              // m+1 basis vectors, m preconditioned vectors, residual
+  std::vector<double> hc;
+  std::vector<const double*> vp, wp;
+  DistFgmres(DistKry& D_, int m_, const double* b_, double* x_)
+      : D(D_), h(D_.h), n(D_.n), m(m_), b(b_), x(x_), V(D_.K.vec.p), Z(V + (size_t)(m_ + 1) * n), r(Z + (size_t)m_ * n),
+        hc((size_t)m_ + 1, 0.0), vp((size_t)m_ + 1, nullptr), wp((size_t)m_ + 1, nullptr) {}
+  int norm(const double* v, double* out) {
+    const double* s = nullptr;
+    MG_TRY(D.dot1(v, v, 0));
+    MG_TRY(D.reduce(1, &s));
+    *out = std::sqrt(s[0]);
+    return MG_OK;
+  }
+  int norm_b(double* out) { return norm(b, out); }
+  int zero_x() { return dist_fill(h, x, n, 0.0); }
+  int sync() {
+    HIP_TRY(spin_sync(h->stream));
+    return MG_OK;
+  }
+  int done() { return MG_OK; }
+  int residual(double* rn) {
+    MG_TRY(D.residual(b, x, r));
+    return norm(r, rn);
+  }
+  int start_basis(double rn) { return D.pass(mgkv::OpScale{1.0 / rn, r, V}, {r, V}); }
+  int arnoldi(int i, HessenbergLsq<double>& G) {
+    const double* s = nullptr;
+    double* vi = V + (size_t)i * n;
+    double* w = V + (size_t)(i + 1) * n;
+    double* z = nullptr;
+    MG_TRY(D.prec(vi, &z));                                              // z = M(V[:,i])
+    MG_TRY(D.product(z, w));                                             // w = A z
+    MG_TRY(D.copy(Z + (size_t)i * n, z));
+    for (int k = 0; k <= i; ++k) { vp[(size_t)k] = V + (size_t)k * n; wp[(size_t)k] = w; }
+    for (int k0 = 0; k0 <= i; k0 += mgkv::MAXS) {                        // h_k = w'v_k
+      const int cnt = std::min(mgkv::MAXS, i + 1 - k0);
+      MG_TRY(krv_dots(cnt, wp.data() + k0, vp.data() + k0, n, D.part(0), D.scal(0), h->stream));
+      MG_TRY(D.reduce(cnt, &s));
+      for (int c = 0; c < cnt; ++c) hc[(size_t)(k0 + c)] = G.h(k0 + c, i) = s[c];
+    }
+    MG_TRY(krv_gs_update(i + 1, hc.data(), vp.data(), w, n, D.part(0), D.scal(0), h->stream));   // w -= sum h_k v_k ; ||w||^2
+    MG_TRY(D.reduce(1, &s));
+    const double wn = std::sqrt(s[0]);
+    G.hsub(i) = wn;
+    if (wn != 0.0) MG_TRY(D.pass(mgkv::OpScale{1.0 / wn, w, w}, {w}));
+    return MG_OK;
+  }
+  int update_x(int used, const double* y) {
+    for (int i = 0; i < used; ++i) { hc[(size_t)i] = -y[i]; vp[(size_t)i] = Z + (size_t)i * n; }
+    if (used > 0) MG_TRY(krv_gs_update(used, hc.data(), vp.data(), x, n, D.part(0), nullptr, h->stream));
+    return MG_OK;
+  }
+};
 int dist_fgmres(mg_dist* h, const double* b, double* x, long long inner, double tol, long long maxIter, long long* iters, long long* flag_out,
                 double* resvec, long long* nres) {
   if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
   DistKry D(h);
-  const long long n = D.n;
   const int m = (int)inner;
-  MG_TRY(D.ensure((size_t)n * (size_t)(2 * m + 2)));
-  double* V = D.K.vec.p;                        // m+1 basis vectors
-  double* Z = V + (size_t)(m + 1) * n;          // m preconditioned vectors
-  double* r = Z + (size_t)m * n;
-  const double* s = nullptr;
-  MG_TRY(D.dot1(b, b, 0));
-  MG_TRY(D.reduce(1, &s));
-  const double bn = std::sqrt(s[0]);
-  if (bn == 0.0) return dist_krylov_zero_rhs(D, x, iters, flag_out, nres);
-  MG_TRY(D.residual(b, x, r));
-  MG_TRY(D.dot1(r, r, 0));
-  MG_TRY(D.reduce(1, &s));
-  double rn = std::sqrt(s[0]), err = rn / bn;
-  long long nr = 0, flag = -1, total = 0;
-  if (err < tol) {
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = 0;
-    if (nres) *nres = 0;
-    return MG_OK;
-  }
-  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs((size_t)m, 0.0), sn((size_t)m, 0.0), g((size_t)m + 1, 0.0), y((size_t)m, 0.0), hc((size_t)m + 1, 0.0);
-  std::vector<const double*> vp((size_t)m + 1, nullptr), wp((size_t)m + 1, nullptr);
-  auto Hat = [&](int i, int j) -> double& { return H[(size_t)i * m + j]; };
-  for (long long it = 1; it <= maxIter && flag != 0; ++it) {
-    MG_TRY(D.pass(mgkv::OpScale{1.0 / rn, r, V}, {r, V}));                 // V[:,1] = r/||r||
-    std::fill(g.begin(), g.end(), 0.0);
-    g[0] = rn;
-    int used = 0;
-    for (int i = 0; i < m; ++i) {
-      double* vi = V + (size_t)i * n;
-      double* w = V + (size_t)(i + 1) * n;
-      double* z = nullptr;
-      MG_TRY(D.prec(vi, &z));                                              // z = M(V[:,i])
-      MG_TRY(D.product(z, w));                                             // w = A z
-      MG_TRY(D.copy(Z + (size_t)i * n, z));
-      for (int k = 0; k <= i; ++k) { vp[(size_t)k] = V + (size_t)k * n; wp[(size_t)k] = w; }
-      for (int k0 = 0; k0 <= i; k0 += mgkv::MAXS) {                        // h_k = w'v_k
-        const int cnt = std::min(mgkv::MAXS, i + 1 - k0);
-        MG_TRY(krv_dots(cnt, wp.data() + k0, vp.data() + k0, n, D.part(0), D.scal(0), h->stream));
-        MG_TRY(D.reduce(cnt, &s));
-        for (int c = 0; c < cnt; ++c) hc[(size_t)(k0 + c)] = Hat(k0 + c, i) = s[c];
-      }
-      MG_TRY(krv_gs_update(i + 1, hc.data(), vp.data(), w, n, D.part(0), D.scal(0), h->stream));   // w -= sum h_k v_k ; ||w||^2
-      MG_TRY(D.reduce(1, &s));
-      const double wn = std::sqrt(s[0]);
-      Hat(i + 1, i) = wn;
-      if (wn != 0.0) MG_TRY(D.pass(mgkv::OpScale{1.0 / wn, w, w}, {w}));
-      for (int k = 0; k < i; ++k) {                                        // previous rotations
-        const double tq = cs[(size_t)k] * Hat(k, i) + sn[(size_t)k] * Hat(k + 1, i);
-        Hat(k + 1, i) = -sn[(size_t)k] * Hat(k, i) + cs[(size_t)k] * Hat(k + 1, i);
-        Hat(k, i) = tq;
-      }
-      const double a = Hat(i, i), bq = Hat(i + 1, i);
-      const double rr = std::hypot(a, bq);
-      cs[(size_t)i] = (rr == 0.0) ? 1.0 : a / rr;
-      sn[(size_t)i] = (rr == 0.0) ? 0.0 : bq / rr;
-      Hat(i, i) = rr;
-      Hat(i + 1, i) = 0.0;
-      g[(size_t)i + 1] = -sn[(size_t)i] * g[(size_t)i];
-      g[(size_t)i] = cs[(size_t)i] * g[(size_t)i];
-      err = std::fabs(g[(size_t)i + 1]) / bn;
-      if (resvec) resvec[nr] = err;
-      ++nr;
-      ++total;
-      used = i + 1;
-      if (err <= tol) { flag = 0; break; }
-    }
-    for (int i = used - 1; i >= 0; --i) {                                  // y = H \ g (upper triangular)
-      double acc = g[(size_t)i];
-      for (int k = i + 1; k < used; ++k) acc -= Hat(i, k) * y[(size_t)k];
-      y[(size_t)i] = acc / Hat(i, i);
-    }
-    for (int i = 0; i < used; ++i) { hc[(size_t)i] = -y[(size_t)i]; vp[(size_t)i] = Z + (size_t)i * n; }
-    if (used > 0) MG_TRY(krv_gs_update(used, hc.data(), vp.data(), x, n, D.part(0), nullptr, h->stream));   // x += Z y
-    if (flag == 0) break;
-    MG_TRY(D.residual(b, x, r));
-    MG_TRY(D.dot1(r, r, 0));
-    MG_TRY(D.reduce(1, &s));
-    rn = std::sqrt(s[0]);
-    err = rn / bn;
-    if (err <= tol) { flag = 0; break; }
-  }
-  HIP_TRY(spin_sync(h->stream));
-  if (iters) *iters = total;
-  if (flag_out) *flag_out = flag;
-  if (nres) *nres = nr;
-  return MG_OK;
+  MG_TRY(D.ensure((size_t)D.n * (size_t)(2 * m + 2)));
+  DistFgmres sp(D, m, b, x);
+  KrylovReport rep(iters, flag_out, resvec, nres);
+  return fgmres_loop<double>(sp, m, tol, maxIter, rep);
 }
 }  // namespace
 

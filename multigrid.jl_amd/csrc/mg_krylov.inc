@@ -1,5 +1,8 @@
 // mg_krylov.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // Device-resident Krylov drivers with the cycle as preconditioner: PCG, BiCGSTAB, FGMRES and their block variants.
+// FGMRES(m) is written once: fgmres_loop below runs the single-GPU / ghost-layer space (FgmresCore, here), the halo form's (mg_dist_krylov.inc)
+// and the ComplexF64 one (mg_complex_krylov.inc).  The host algebra - KrylovReport (the outputs and the epilogue of every driver),
+// HessenbergLsq, SmallMat / sm_*, pinv_sym - is mg_krylov_host.hpp.
 namespace {
 // Where the handle is one rank's extended boxes (ghost-layer form, mg_ghost.inc; round 6) the drivers below run SHARDED: every vector
 // is n_ext long with its owned rows valid, a dot or norm is the sum over the owned rows of all ranks (box dot + one all-reduce; scalars
@@ -70,12 +73,11 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
   double nr0 = 0.0;
   MG_TRY(K.norm(b, &nr0));
   long long it = 0, flag = -1;
+  KrylovReport rep(iters, flag_out, resvec, nullptr);
   if (nr0 == 0.0) {  // cg returns zeros, flag -9
     MG_TRY(k_fill(h, x, n, 0.0));
     HIP_TRY(spin_sync(h->play->stream));
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = -9;
-    return MG_OK;
+    return rep.finish(0, -9);
   }
   MG_TRY(K.residual(b, x, r));                                         // r = b - A(x)
   MG_TRY(cycle_dev(h, r, z, true));                                    // z = M(r), x = 0 on entry
@@ -107,7 +109,7 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
       HIP_TRY(hipGetLastError());
       MG_TRY(scalar_sync(h, &rn));
     }
-    if (resvec) resvec[k - 1] = rn / nr0;
+    rep.set(k - 1, rn / nr0);
     if (rn / nr0 <= tol) { flag = 0; break; }
     MG_TRY(cycle_dev(h, r, z, true));
     double zr = 0.0;
@@ -118,8 +120,7 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(spin_sync(h->play->stream));
-  if (iters) *iters = it;
-  if (flag_out) *flag_out = flag;
+  rep.finish(it, flag);
   return K.done();
 }
 
@@ -150,26 +151,18 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
   KrylovSpace K(h);
   double bn = 0.0, err = 0.0;
   MG_TRY(K.norm(b, &bn));
-  long long it = 0, flag = -1, nr = 0;
+  long long it = 0, flag = -1;
+  KrylovReport rep(iters, flag_out, resvec, nres);
   if (bn == 0.0) {
     MG_TRY(k_fill(h, x, n, 0.0));
     HIP_TRY(spin_sync(h->play->stream));
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = -9;
-    if (nres) *nres = 0;
-    return MG_OK;
+    return rep.finish(0, -9);
   }
   MG_TRY(K.residual(b, x, r));
   MG_TRY(K.norm(r, &err));
   err /= bn;
-  if (resvec) resvec[nr] = err;
-  ++nr;
-  if (err < tol) {
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = 0;
-    if (nres) *nres = nr;
-    return MG_OK;
-  }
+  rep.record(err);
+  if (err < tol) return rep.finish(0, 0);
   HIP_TRY(hipMemcpyAsync(rtld, r, sizeof(double) * n, hipMemcpyDeviceToDevice, h->play->stream));
   double omega = 1.0, alpha = 0.0, rho1 = 0.0;
   for (long long k = 1; k <= maxIter; ++k) {
@@ -192,8 +185,7 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
     MG_TRY(k_axpby(h, -alpha, v, 1.0, r, n));         // s = r - alpha v (in r)
     double sn = 0.0;
     MG_TRY(K.norm(r, &sn));
-    if (resvec) resvec[nr] = sn / bn;
-    ++nr;
+    rep.record(sn / bn);
     if (sn / bn < tol) {                              // converged on the half step
       MG_TRY(k_axpby(h, alpha, phat, 1.0, x, n));
       flag = -3;
@@ -209,149 +201,156 @@ int bicgstab_dev(mg_hierarchy* h, const double* b, double* x, double tol, long l
     MG_TRY(k_axpby(h, -omega, t, 1.0, r, n));         // r = s - omega t
     MG_TRY(K.norm(r, &err));
     err /= bn;
-    if (resvec) resvec[nr] = err;
-    ++nr;
+    rep.record(err);
     if (err <= tol) { flag = 0; break; }
     if (omega == 0.0) { flag = -2; break; }
     rho1 = rho;
   }
   HIP_TRY(spin_sync(h->play->stream));
-  if (iters) *iters = it;
-  if (flag_out) *flag_out = flag;
-  if (nres) *nres = nr;
+  rep.finish(it, flag);
   return K.done();
 }
 
-// Flexible restarted GMRES with the multigrid cycle as (right) preconditioner: solveGMRES_MG (SolveFuncs.jl:119-133)
-// -> KrylovMethods.fgmres (v0.6.0, un-vendored), restated from the published algorithm (Saad's FGMRES(m): modified
-// Gram-Schmidt Arnoldi, Givens rotations, residual estimate |s_{i+1}|/||b|| after every inner step).  maxIter counts
-// restarts, `inner` is the Krylov dimension; resvec gets one entry per inner step; flag 0 converged, -1 not, -9 b = 0.
-// Flexible restarted GMRES on level `lv` (0-based).  precond 0: one multigrid cycle from level 0 (solveGMRES_MG,
-// lv must be 0); precond 1: z = dprec .* v (the Jacobi-preconditioned coarsest solve, MGcycle.jl:152-168).
-int fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBuf<double>& work, const double* b,
-                double* x, long long inner, double tol, long long maxIter, long long* iters, long long* flag_out,
-                double* resvec, long long* nres) {
-  Level& L = h->lev[(size_t)lv];
-  const long long n = L.n;
-  if (h->play->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "fgmres: block right-hand sides (blockFGMRES) are not on the device path yet");
-  if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
-  const int m = (int)inner;
-  if (work.n != (size_t)n * (size_t)(2 * m + 2)) MG_TRY(work.alloc((size_t)n * (size_t)(2 * m + 2)));
-  double* V = work.p;                         // m+1 basis vectors
-  double* Z = work.p + (size_t)(m + 1) * n;   // m preconditioned vectors
-  double* r = Z + (size_t)m * n;               // residual / w
-  KrylovSpace K(h);
-  const bool ghs = K.ghs && lv == 0;          // (sharded: the fine level of one rank's extended boxes)
-  auto knorm = [&](const double* v, double* out) { return ghs ? K.norm(v, out) : norm_sync(h, v, n, out); };
+// Flexible restarted GMRES with a (right) preconditioner: solveGMRES_MG (SolveFuncs.jl:119-133) -> KrylovMethods.fgmres (v0.6.0,
+// un-vendored), restated from the published algorithm (Saad's FGMRES(m): Gram-Schmidt Arnoldi, Givens rotations, residual estimate
+// |s_{i+1}|/||b|| after every inner step).  maxIter counts restarts, m is the Krylov dimension; resvec gets one entry per inner step;
+// flag 0 converged, -1 not, -9 b = 0.  This is the ONE outer loop of every form - single GPU and ghost-layer (FgmresCore below), halo
+// (DistFgmres, mg_dist_krylov.inc), ComplexF64 (CxFgmres, mg_complex_krylov.inc).  The small least squares is HessenbergLsq<S>
+// (mg_krylov_host.hpp); everything that touches a vector is the space's:
+//   norm_b(&bn)          ||b||                                     zero_x()             x = 0 (the b = 0 exit)
+//   residual(&rn)        r = b - A x and ||r||                     start_basis(rn)      V_0 = r / ||r||
+//   arnoldi(i, G)        z = M v_i, w = A z, orthogonalise against v_0 .. v_i, normalise into v_{i+1}; G.h(0..i, i) and G.hsub(i) = ||w||
+//   update_x(used, y)    x += Z y                                  sync(), done()       drain the stream; what the exit owes
+template <class S, class Space>
+int fgmres_loop(Space& sp, int m, double tol, long long maxIter, KrylovReport& rep) {
   double bn = 0.0, rn = 0.0;
-  MG_TRY(knorm(b, &bn));
-  long long nr = 0, flag = -1, total = 0;
+  MG_TRY(sp.norm_b(&bn));
   if (bn == 0.0) {
-    MG_TRY(k_fill(h, x, n, 0.0));
-    HIP_TRY(spin_sync(h->play->stream));
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = -9;
-    if (nres) *nres = 0;
-    return MG_OK;
+    MG_TRY(sp.zero_x());
+    MG_TRY(sp.sync());
+    return rep.finish(0, -9);
   }
-  if (ghs) MG_TRY(gh_refresh(h, x));
-  MG_TRY(k_residual(h, lv, L.A, b, x, r));
-  MG_TRY(knorm(r, &rn));
+  MG_TRY(sp.residual(&rn));
   double err = rn / bn;
-  if (err < tol) {
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = 0;
-    if (nres) *nres = 0;
-    return MG_OK;
-  }
-  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs((size_t)m, 0.0), sn((size_t)m, 0.0), s((size_t)m + 1, 0.0), y((size_t)m, 0.0);
-  auto Hat = [&](int i, int j) -> double& { return H[(size_t)i * m + j]; };
+  if (err < tol) return rep.finish(0, 0);
+  HessenbergLsq<S> G(m);
+  long long flag = -1, total = 0;
   for (long long it = 1; it <= maxIter && flag != 0; ++it) {
-    MG_TRY(k_axpby(h, 1.0 / rn, r, 0.0, V, n));                          // V[:,1] = r/||r||
-    std::fill(s.begin(), s.end(), 0.0);
-    s[0] = rn;
+    MG_TRY(sp.start_basis(rn));                                            // V[:,1] = r/||r||
+    G.begin(rn);
     int used = 0;
     for (int i = 0; i < m; ++i) {
-      double* vi = V + (size_t)i * n;
-      double* zi = Z + (size_t)i * n;
-      double* w = V + (size_t)(i + 1) * n;
-      if (precond == 0) MG_TRY(cycle_dev(h, vi, zi, true));               // z = M(V[:,i])
-      else MG_TRY(k_dscale(h, lv, dprec, vi, zi, n));
-      if (ghs) MG_TRY(gh_refresh(h, zi));                                 // (sharded: z's ghost layers from their owners)
-      MG_TRY(k_spmv(h, lv, MG_K_SPMV, L.A, 1.0, zi, 0.0, w));             // w = A z
-      // modified Gram-Schmidt with the chain dot -> update -> dot on the device: h_k = w.V_k stays in HBM, the update
-      // w -= h_k V_k reads it there and produces the partials of the next dot (or of ||w||^2) in the same pass; the i+2
-      // scalars come back in ONE readback per inner step (round 2: one host synchronisation instead of i+2)
-      if (h->opt.no_mgs_chain || ghs) {   // (A/B: one dot, one host synchronisation and one update per basis vector; sharded: every
-                                          // dot is a sum over the owned rows of all ranks - one all-reduce per basis vector, as MGS orders them)
-        for (int k = 0; k <= i; ++k) {
-          double hk = 0.0;
-          if (ghs) MG_TRY(K.dot(w, V + (size_t)k * n, &hk));
-          else MG_TRY(dot_sync(h, w, V + (size_t)k * n, n, &hk));
-          Hat(k, i) = hk;
-          MG_TRY(k_axpby(h, -hk, V + (size_t)k * n, 1.0, w, n));
-        }
-        double wn = 0.0;
-        MG_TRY(knorm(w, &wn));
-        Hat(i + 1, i) = wn;
-        if (wn != 0.0) MG_TRY(k_axpby(h, 1.0 / wn, w, 0.0, w, n));
-      } else {
-        if (h->kscal.n < (size_t)m + 2) MG_TRY(h->kscal.alloc((size_t)m + 2));
-        if (!h->h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_kscal), sizeof(double) * 66));
-        const int nb = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n / 2 + mgk::BLK - 1) / mgk::BLK));
-        double* hd = h->kscal.p;
-        hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, w, V, n, h->play->partial.p);
-        hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd);
-        for (int k = 0; k <= i; ++k) {
-          hipLaunchKernelGGL(mgk::mgs_step, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, hd + k, V + (size_t)k * n, w,
-                             k < i ? V + (size_t)(k + 1) * n : (const double*)nullptr, n, h->play->partial.p);
-          hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd + k + 1);
-        }
-        hipLaunchKernelGGL(mgk::scale_rsqrt, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, hd + i + 1, w, n);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h->h_kscal, hd, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, h->play->stream));
-        HIP_TRY(spin_sync(h->play->stream));
-        for (int k = 0; k <= i; ++k) Hat(k, i) = h->h_kscal[k];
-        Hat(i + 1, i) = std::sqrt(h->h_kscal[i + 1]);
-      }
-      for (int k = 0; k < i; ++k) {                                       // previous rotations
-        const double t = cs[(size_t)k] * Hat(k, i) + sn[(size_t)k] * Hat(k + 1, i);
-        Hat(k + 1, i) = -sn[(size_t)k] * Hat(k, i) + cs[(size_t)k] * Hat(k + 1, i);
-        Hat(k, i) = t;
-      }
-      const double a = Hat(i, i), bq = Hat(i + 1, i);
-      const double rr = std::hypot(a, bq);
-      cs[(size_t)i] = (rr == 0.0) ? 1.0 : a / rr;
-      sn[(size_t)i] = (rr == 0.0) ? 0.0 : bq / rr;
-      Hat(i, i) = rr;
-      Hat(i + 1, i) = 0.0;
-      s[(size_t)i + 1] = -sn[(size_t)i] * s[(size_t)i];
-      s[(size_t)i] = cs[(size_t)i] * s[(size_t)i];
-      err = std::fabs(s[(size_t)i + 1]) / bn;
-      if (resvec) resvec[nr] = err;
-      ++nr;
+      MG_TRY(sp.arnoldi(i, G));
+      err = G.close_column(i) / bn;
+      rep.record(err);
       ++total;
       used = i + 1;
       if (err <= tol) { flag = 0; break; }
     }
-    for (int i = used - 1; i >= 0; --i) {                                 // y = H \ s (upper triangular)
-      double acc = s[(size_t)i];
-      for (int k = i + 1; k < used; ++k) acc -= Hat(i, k) * y[(size_t)k];
-      y[(size_t)i] = acc / Hat(i, i);
-    }
-    for (int i = 0; i < used; ++i) MG_TRY(k_axpby(h, y[(size_t)i], Z + (size_t)i * n, 1.0, x, n));   // x += Z y
+    MG_TRY(sp.update_x(used, G.solve(used).data()));                       // x += Z y
     if (flag == 0) break;
-    if (ghs) MG_TRY(gh_refresh(h, x));
-    MG_TRY(k_residual(h, lv, L.A, b, x, r));
-    MG_TRY(knorm(r, &rn));
+    MG_TRY(sp.residual(&rn));
     err = rn / bn;
     if (err <= tol) { flag = 0; break; }
   }
-  HIP_TRY(spin_sync(h->play->stream));
-  if (iters) *iters = total;
-  if (flag_out) *flag_out = flag;
-  if (nres) *nres = nr;
-  return ghs ? K.done() : (int)MG_OK;
+  MG_TRY(sp.sync());
+  rep.finish(total, flag);
+  return sp.done();
+}
+
+// The space of fgmres_core: level `lv` (0-based) of a single-GPU handle, or the fine level of one rank's extended boxes.
+// precond 0: one multigrid cycle from level 0 (solveGMRES_MG, lv must be 0); precond 1: z = dprec .* v (the Jacobi-preconditioned
+// coarsest solve, MGcycle.jl:152-168).
+struct FgmresCore {
+  mg_hierarchy* h;
+  const int lv, precond, m;
+  const double* dprec;
+  const double* b;
+  double* x;
+  Level& L;
+  const long long n;
+  KrylovSpace K;
+  const bool ghs;                             // (sharded: the fine level of one rank's extended boxes)
+  double *V, *Z, *r;                          // m+1 basis vectors, m preconditioned vectors, residual / w
+  FgmresCore(mg_hierarchy* h_, int lv_, int precond_, int m_, const double* dprec_, const double* b_, double* x_, double* work)
+      : h(h_), lv(lv_), precond(precond_), m(m_), dprec(dprec_), b(b_), x(x_), L(h_->lev[(size_t)lv_]), n(L.n), K(h_), ghs(K.ghs && lv_ == 0),
+        V(work), Z(work + (size_t)(m_ + 1) * n), r(Z + (size_t)m_ * n) {}
+  int knorm(const double* v, double* out) { return ghs ? K.norm(v, out) : norm_sync(h, v, n, out); }
+  int norm_b(double* out) { return knorm(b, out); }
+  int zero_x() { return k_fill(h, x, n, 0.0); }
+  int sync() {
+    HIP_TRY(spin_sync(h->play->stream));
+    return MG_OK;
+  }
+  int done() { return ghs ? K.done() : (int)MG_OK; }
+  int residual(double* rn) {
+    if (ghs) MG_TRY(gh_refresh(h, x));
+    MG_TRY(k_residual(h, lv, L.A, b, x, r));
+    return knorm(r, rn);
+  }
+  int start_basis(double rn) { return k_axpby(h, 1.0 / rn, r, 0.0, V, n); }
+  int arnoldi(int i, HessenbergLsq<double>& G) {
+    double* vi = V + (size_t)i * n;
+    double* zi = Z + (size_t)i * n;
+    double* w = V + (size_t)(i + 1) * n;
+    if (precond == 0) MG_TRY(cycle_dev(h, vi, zi, true));               // z = M(V[:,i])
+    else MG_TRY(k_dscale(h, lv, dprec, vi, zi, n));
+    if (ghs) MG_TRY(gh_refresh(h, zi));                                 // (sharded: z's ghost layers from their owners)
+    MG_TRY(k_spmv(h, lv, MG_K_SPMV, L.A, 1.0, zi, 0.0, w));             // w = A z
+    // modified Gram-Schmidt with the chain dot -> update -> dot on the device: h_k = w.V_k stays in HBM, the update
+    // w -= h_k V_k reads it there and produces the partials of the next dot (or of ||w||^2) in the same pass; the i+2
+    // scalars come back in ONE readback per inner step (round 2: one host synchronisation instead of i+2)
+    if (h->opt.no_mgs_chain || ghs) {   // (A/B: one dot, one host synchronisation and one update per basis vector; sharded: every
+                                        // dot is a sum over the owned rows of all ranks - one all-reduce per basis vector, as MGS orders them)
+      for (int k = 0; k <= i; ++k) {
+        double hk = 0.0;
+        if (ghs) MG_TRY(K.dot(w, V + (size_t)k * n, &hk));
+        else MG_TRY(dot_sync(h, w, V + (size_t)k * n, n, &hk));
+        G.h(k, i) = hk;
+        MG_TRY(k_axpby(h, -hk, V + (size_t)k * n, 1.0, w, n));
+      }
+      double wn = 0.0;
+      MG_TRY(knorm(w, &wn));
+      G.hsub(i) = wn;
+      if (wn != 0.0) MG_TRY(k_axpby(h, 1.0 / wn, w, 0.0, w, n));
+    } else {
+      if (h->kscal.n < (size_t)m + 2) MG_TRY(h->kscal.alloc((size_t)m + 2));
+      if (!h->h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_kscal), sizeof(double) * 66));
+      const int nb = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n / 2 + mgk::BLK - 1) / mgk::BLK));
+      double* hd = h->kscal.p;
+      hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, w, V, n, h->play->partial.p);
+      hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd);
+      for (int k = 0; k <= i; ++k) {
+        hipLaunchKernelGGL(mgk::mgs_step, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, hd + k, V + (size_t)k * n, w,
+                           k < i ? V + (size_t)(k + 1) * n : (const double*)nullptr, n, h->play->partial.p);
+        hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd + k + 1);
+      }
+      hipLaunchKernelGGL(mgk::scale_rsqrt, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, hd + i + 1, w, n);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(h->h_kscal, hd, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, h->play->stream));
+      HIP_TRY(spin_sync(h->play->stream));
+      for (int k = 0; k <= i; ++k) G.h(k, i) = h->h_kscal[k];
+      G.hsub(i) = std::sqrt(h->h_kscal[i + 1]);
+    }
+    return MG_OK;
+  }
+  int update_x(int used, const double* y) {
+    for (int i = 0; i < used; ++i) MG_TRY(k_axpby(h, y[i], Z + (size_t)i * n, 1.0, x, n));
+    return MG_OK;
+  }
+};
+
+int fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec, DevBuf<double>& work, const double* b,
+                double* x, long long inner, double tol, long long maxIter, long long* iters, long long* flag_out,
+                double* resvec, long long* nres) {
+  const long long n = h->lev[(size_t)lv].n;
+  if (h->play->nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "fgmres: block right-hand sides (blockFGMRES) are not on the device path yet");
+  if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
+  const int m = (int)inner;
+  if (work.n != (size_t)n * (size_t)(2 * m + 2)) MG_TRY(work.alloc((size_t)n * (size_t)(2 * m + 2)));
+  FgmresCore sp(h, lv, precond, m, dprec, b, x, work.p);
+  KrylovReport rep(iters, flag_out, resvec, nres);
+  return fgmres_loop<double>(sp, m, tol, maxIter, rep);
 }
 
 int fgmres_dev(mg_hierarchy* h, const double* b, double* x, long long inner, double tol, long long maxIter,
@@ -364,130 +363,7 @@ int fgmres_dev(mg_hierarchy* h, const double* b, double* x, long long inner, dou
 // Sadok block BiCGSTAB, block flexible GMRES) are implemented here with every n x k block resident in HBM (row-major [n][k], k <= 16): products with A
 // are SpMM launches, the preconditioner is one cycle on the whole block, k x k Gram matrices come back through one
 // 8*k*k-byte readback each, and the small dense algebra (pseudo-inverse, LU solve, triangular factor, block least
-// squares) runs on the host.
-struct SmallMat {   // row-major dense helper, host
-  int r = 0, c = 0;
-  std::vector<double> a;
-  SmallMat() {}
-  SmallMat(int r_, int c_) : r(r_), c(c_), a((size_t)r_ * c_, 0.0) {}
-  double& operator()(int i, int j) { return a[(size_t)i * c + j]; }
-  double operator()(int i, int j) const { return a[(size_t)i * c + j]; }
-};
-SmallMat sm_mul(const SmallMat& A, const SmallMat& B) {
-  SmallMat C(A.r, B.c);
-  for (int i = 0; i < A.r; ++i)
-    for (int k = 0; k < A.c; ++k) {
-      const double v = A(i, k);
-      for (int j = 0; j < B.c; ++j) C(i, j) += v * B(k, j);
-    }
-  return C;
-}
-SmallMat sm_T(const SmallMat& A) {
-  SmallMat C(A.c, A.r);
-  for (int i = 0; i < A.r; ++i)
-    for (int j = 0; j < A.c; ++j) C(j, i) = A(i, j);
-  return C;
-}
-// X = A \ B by Gaussian elimination with partial pivoting (A k x k); false if singular
-bool sm_solve(SmallMat A, SmallMat B, SmallMat& X) {
-  const int k = A.r;
-  for (int p = 0; p < k; ++p) {
-    int piv = p;
-    for (int i = p + 1; i < k; ++i)
-      if (std::fabs(A(i, p)) > std::fabs(A(piv, p))) piv = i;
-    if (A(piv, p) == 0.0) return false;
-    if (piv != p) {
-      for (int j = 0; j < k; ++j) std::swap(A(p, j), A(piv, j));
-      for (int j = 0; j < B.c; ++j) std::swap(B(p, j), B(piv, j));
-    }
-    for (int i = p + 1; i < k; ++i) {
-      const double f = A(i, p) / A(p, p);
-      if (f == 0.0) continue;
-      for (int j = p; j < k; ++j) A(i, j) -= f * A(p, j);
-      for (int j = 0; j < B.c; ++j) B(i, j) -= f * B(p, j);
-    }
-  }
-  X = SmallMat(k, B.c);
-  for (int j = 0; j < B.c; ++j)
-    for (int i = k - 1; i >= 0; --i) {
-      double acc = B(i, j);
-      for (int t = i + 1; t < k; ++t) acc -= A(i, t) * X(t, j);
-      X(i, j) = acc / A(i, i);
-    }
-  return true;
-}
-// upper triangular Rf with G = Rf'Rf for a positive SEMI-definite Gram matrix
-SmallMat sm_chol_semidefinite(const SmallMat& G, double rtol = 1e-14) {
-  const int k = G.r;
-  SmallMat R(k, k);
-  for (int c = 0; c < k; ++c) {
-    double d = G(c, c);
-    for (int a = 0; a < c; ++a) d -= R(a, c) * R(a, c);
-    if (G(c, c) <= 0.0 || d <= rtol * G(c, c)) continue;
-    R(c, c) = std::sqrt(d);
-    for (int j = c + 1; j < k; ++j) {
-      double t = G(c, j);
-      for (int a = 0; a < c; ++a) t -= R(a, c) * R(a, j);
-      R(c, j) = t / R(c, c);
-    }
-  }
-  return R;
-}
-// T with W*T = W*Rf^+: T[:,c] = (e_c - T[:,:c] Rf[:c,c]) / Rf[c,c], zero for zero pivots
-SmallMat sm_tri_pinv(const SmallMat& R) {
-  const int k = R.r;
-  SmallMat T(k, k);
-  for (int c = 0; c < k; ++c) {
-    if (R(c, c) == 0.0) continue;
-    for (int i = 0; i < k; ++i) {
-      double t = (i == c) ? 1.0 : 0.0;
-      for (int a = 0; a < c; ++a) t -= T(i, a) * R(a, c);
-      T(i, c) = t / R(c, c);
-    }
-  }
-  return T;
-}
-// min || xi - H Y ||_F over Y by Householder QR of H (rows x cols, rows >= cols); returns the residual norm
-double sm_lstsq(SmallMat H, SmallMat xi, SmallMat& Y) {
-  const int m = H.r, n = H.c, k = xi.c;
-  for (int j = 0; j < n; ++j) {
-    double nrm = 0.0;
-    for (int i = j; i < m; ++i) nrm += H(i, j) * H(i, j);
-    nrm = std::sqrt(nrm);
-    if (nrm == 0.0) continue;
-    const double alpha = H(j, j) > 0 ? -nrm : nrm;
-    std::vector<double> v((size_t)m, 0.0);
-    for (int i = j; i < m; ++i) v[(size_t)i] = H(i, j);
-    v[(size_t)j] -= alpha;
-    double vn = 0.0;
-    for (int i = j; i < m; ++i) vn += v[(size_t)i] * v[(size_t)i];
-    if (vn == 0.0) continue;
-    for (int c = j; c < n; ++c) {
-      double d = 0.0;
-      for (int i = j; i < m; ++i) d += v[(size_t)i] * H(i, c);
-      d *= 2.0 / vn;
-      for (int i = j; i < m; ++i) H(i, c) -= d * v[(size_t)i];
-    }
-    for (int c = 0; c < k; ++c) {
-      double d = 0.0;
-      for (int i = j; i < m; ++i) d += v[(size_t)i] * xi(i, c);
-      d *= 2.0 / vn;
-      for (int i = j; i < m; ++i) xi(i, c) -= d * v[(size_t)i];
-    }
-  }
-  Y = SmallMat(n, k);
-  for (int c = 0; c < k; ++c)
-    for (int i = n - 1; i >= 0; --i) {
-      double acc = xi(i, c);
-      for (int t = i + 1; t < n; ++t) acc -= H(i, t) * Y(t, c);
-      Y(i, c) = (H(i, i) != 0.0) ? acc / H(i, i) : 0.0;
-    }
-  double res = 0.0;
-  for (int i = n; i < m; ++i)
-    for (int c = 0; c < k; ++c) res += xi(i, c) * xi(i, c);
-  return std::sqrt(res);
-}
-
+// squares) runs on the host: SmallMat, sm_* and pinv_sym of mg_krylov_host.hpp.
 // G = X'Y (k x k) to the host; synchronises the stream
 int blk_gram(mg_hierarchy* h, const double* X, const double* Y, long long n, int k, SmallMat& G) {
   if (gh_global_scalars(h) && n == h->lev[0].n) {   // sharded: the Gram matrix over the owned rows of all ranks (one all-reduce of k*k doubles)
@@ -522,11 +398,6 @@ int blk_comb(mg_hierarchy* h, double* out, const double* add, double s, const do
   hipLaunchKernelGGL(mgk::blk_comb, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, out, add, s, in, slot, n, k);
   HIP_TRY(hipGetLastError());
   return MG_OK;
-}
-SmallMat sm_scaled_identity(int k, double v) {
-  SmallMat I(k, k);
-  for (int i = 0; i < k; ++i) I(i, i) = v;
-  return I;
 }
 int blk_colnorms(mg_hierarchy* h, const double* X, long long n, int k, std::vector<double>& out) {
   SmallMat G;
@@ -571,14 +442,13 @@ int block_pcg_dev(mg_hierarchy* h, const double* B, double* X, double tol, long 
   std::vector<double> nb, rn;
   MG_TRY(blk_colnorms(h, B, n, k, nb));
   long long it = 0, flag = -1;
+  KrylovReport rep(iters, flag_out, nullptr, nullptr);   // (resmat is iterations x k, written where it is computed)
   bool any = false;
   for (double v : nb) any = any || v > 0.0;
   if (!any) {
     MG_TRY(k_fill(h, X, (long long)len, 0.0));
     HIP_TRY(spin_sync(h->play->stream));
-    if (iters) *iters = 0;
-    if (flag_out) *flag_out = -9;
-    return MG_OK;
+    return rep.finish(0, -9);
   }
   for (double& v : nb) if (!(v > 0.0)) v = 1.0;
   MG_TRY(blk_residual(h, 0, B, X, R));                         // R = B - A X
@@ -616,9 +486,7 @@ int block_pcg_dev(mg_hierarchy* h, const double* B, double* X, double tol, long 
     MG_TRY(blk_comb(h, P, Z, 1.0, P, Beta, n, k));                // P = Z + P Beta
   }
   HIP_TRY(spin_sync(h->play->stream));
-  if (iters) *iters = it;
-  if (flag_out) *flag_out = flag;
-  return MG_OK;
+  return rep.finish(it, flag);
 }
 
 // blockBiCGSTB (El Guennouni, Jbilou, Sadok 2003), right-preconditioned by the cycle
@@ -634,19 +502,14 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
   double *R = w, *R0 = w + len, *P = w + 2 * len, *Ph = w + 3 * len, *V = w + 4 * len, *Sh = w + 5 * len, *T = w + 6 * len;
   std::vector<double> nb, rn;
   MG_TRY(blk_colnorms(h, B, n, k, nb));
-  long long it = 0, flag = -1, nr = 0;
+  long long it = 0, flag = -1;
+  KrylovReport rep(iters, flag_out, resvec, nres);
   bool any = false;
   for (double v : nb) any = any || v > 0.0;
-  auto finish = [&](long long f) {
-    if (iters) *iters = it;
-    if (flag_out) *flag_out = f;
-    if (nres) *nres = nr;
-    return (int)MG_OK;
-  };
   if (!any) {
     MG_TRY(k_fill(h, X, (long long)len, 0.0));
     HIP_TRY(spin_sync(h->play->stream));
-    return finish(-9);
+    return rep.finish(0, -9);
   }
   for (double& v : nb) if (!(v > 0.0)) v = 1.0;
   auto worst_rel = [&](const double* blk, double* out) -> int {
@@ -659,9 +522,8 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
   MG_TRY(blk_residual(h, 0, B, X, R));
   double err = 0.0;
   MG_TRY(worst_rel(R, &err));
-  if (resvec) resvec[nr] = err;
-  ++nr;
-  if (err < tol) return finish(0);
+  rep.record(err);
+  if (err < tol) return rep.finish(0, 0);
   HIP_TRY(hipMemcpyAsync(R0, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
   HIP_TRY(hipMemcpyAsync(P, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
   const SmallMat I1 = sm_scaled_identity(k, 1.0);
@@ -678,8 +540,7 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
     MG_TRY(blk_comb(h, R, R, 1.0, V, nalpha, n, k));              // S = R - V alpha   (in R)
     double sn = 0.0;
     MG_TRY(worst_rel(R, &sn));
-    if (resvec) resvec[nr] = sn;
-    ++nr;
+    rep.record(sn);
     if (sn < tol) {
       MG_TRY(blk_comb(h, X, X, 1.0, Ph, alpha, n, k));
       flag = -3;
@@ -698,8 +559,7 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
     MG_TRY(blk_comb(h, X, X, 1.0, Sh, sm_scaled_identity(k, omega), n, k));
     MG_TRY(blk_comb(h, R, R, 1.0, T, sm_scaled_identity(k, -omega), n, k));   // R = S - omega T
     MG_TRY(worst_rel(R, &err));
-    if (resvec) resvec[nr] = err;
-    ++nr;
+    rep.record(err);
     if (err <= tol) { flag = 0; break; }
     if (omega == 0.0) { flag = -2; break; }
     SmallMat RtT, beta;
@@ -710,7 +570,7 @@ int block_bicgstab_dev(mg_hierarchy* h, const double* B, double* X, double tol, 
     MG_TRY(blk_comb(h, P, R, 1.0, P, beta, n, k));                // P = R + (P - omega V) beta
   }
   HIP_TRY(spin_sync(h->play->stream));
-  return finish(flag);
+  return rep.finish(it, flag);
 }
 
 // W -> orthonormal block (in place) by Cholesky QR applied twice; Rf with W_in = Q Rf
@@ -751,13 +611,8 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
   double* Vb = w;                              // m+1 blocks
   double* Zb = w + (size_t)(m + 1) * len;      // m blocks
   double* R = Zb + (size_t)m * len;            // residual / W
-  long long nr = 0, flag = -1, total = 0;
-  auto finish = [&](long long f) {
-    if (iters) *iters = total;
-    if (flag_out) *flag_out = f;
-    if (nres) *nres = nr;
-    return (int)MG_OK;
-  };
+  long long flag = -1, total = 0;
+  KrylovReport rep(iters, flag_out, resvec, nres);
   auto fro = [&](const double* blk, double* out) -> int {
     std::vector<double> cn;
     MG_TRY(blk_colnorms(h, blk, n, k, cn));
@@ -771,11 +626,11 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
   if (bn == 0.0) {
     MG_TRY(k_fill(h, X, (long long)len, 0.0));
     HIP_TRY(spin_sync(h->play->stream));
-    return finish(-9);
+    return rep.finish(0, -9);
   }
   MG_TRY(blk_residual(h, lv, B, X, R));
   MG_TRY(fro(R, &rn));
-  if (rn / bn < tol) return finish(0);
+  if (rn / bn < tol) return rep.finish(0, 0);
   for (long long it = 1; it <= maxIter && flag != 0; ++it) {
     SmallMat H((m + 1) * k, m * k), xi((m + 1) * k, k), Rf, Y;
     HIP_TRY(hipMemcpyAsync(Vb, R, sizeof(double) * len, hipMemcpyDeviceToDevice, h->play->stream));
@@ -808,8 +663,7 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
         for (int b = 0; b < k; ++b) xb(a, b) = xi(a, b);
       }
       const double err = sm_lstsq(Hb, xb, Y) / bn;
-      if (resvec) resvec[nr] = err;
-      ++nr;
+      rep.record(err);
       ++total;
       used = j + 1;
       if (err <= tol) { flag = 0; break; }
@@ -826,7 +680,7 @@ int block_fgmres_core(mg_hierarchy* h, int lv, int precond, const double* dprec,
     if (rn / bn <= tol) { flag = 0; break; }
   }
   HIP_TRY(spin_sync(h->play->stream));
-  return finish(flag);
+  return rep.finish(total, flag);
 }
 int block_fgmres_dev(mg_hierarchy* h, const double* B, double* X, long long inner, double tol, long long maxIter,
                      long long* iters, long long* flag_out, double* resvec, long long* nres) {

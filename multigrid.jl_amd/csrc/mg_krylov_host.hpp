@@ -1,0 +1,294 @@
+// mg_krylov_host.hpp - the small HOST algebra of the Krylov drivers (mg_krylov.inc, mg_dist_krylov.inc, mg_complex_krylov.inc) and of the
+// FGMRES relaxation (mg_schedule.inc, mg_dist.inc).  Plain C++17 with no HIP header: mgvcycle.hip includes it in front of its parts, and
+// tests/native/krylov_host_algebra.cpp builds it on its own.  Nothing here touches a device vector.
+//   KrylovReport        where a driver writes iters / flag / resvec / nres, and its epilogue
+//   HessenbergLsq<S>    the Givens least squares of FGMRES(m), S = double or std::complex<double>
+//   pinv_sym, RelaxLsq  the normal-equations step of FGMRES_relaxation (Jac-GMRES smoother, K-cycle)
+//   SmallMat, sm_*      row-major dense helpers of the block drivers
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <complex>
+#include <cstddef>
+#include <utility>
+#include <vector>
+
+// ---- a driver's outputs: any pointer may be null ----------------------------------------------------------------------------------
+struct KrylovReport {
+  long long* iters = nullptr;
+  long long* flag = nullptr;
+  double* resvec = nullptr;
+  long long* nres = nullptr;
+  long long nr = 0;   // entries appended so far
+  KrylovReport(long long* iters_, long long* flag_, double* resvec_, long long* nres_) : iters(iters_), flag(flag_), resvec(resvec_), nres(nres_) {}
+  void record(double err) {
+    if (resvec) resvec[nr] = err;
+    ++nr;
+  }
+  // indexed, not appended: PCG's one entry per iteration (and the halo form's later overwrite of it); nres does not count these
+  void set(long long k, double err) {
+    if (resvec) resvec[k] = err;
+  }
+  int finish(long long it, long long f) {
+    if (iters) *iters = it;
+    if (flag) *flag = f;
+    if (nres) *nres = nr;
+    return 0;   // MG_OK
+  }
+};
+
+// ---- FGMRES(m): min || beta e_1 - Hbar y || by Givens rotations, column by column -------------------------------------------------
+// Column i holds h_0 .. h_i (S) and the real h_{i+1,i} = ||w||.  Its rotation has a cosine of type S and a real sine:
+//   rr = radius(a, b), c = a / rr, s = b / rr with a = h_i (rotated by the columns before it), b = h_{i+1,i}; rr == 0: c = 1, s = 0.
+inline double krylov_conj(double a) { return a; }
+inline std::complex<double> krylov_conj(const std::complex<double>& a) { return std::conj(a); }
+inline double krylov_radius(double a, double b) { return std::hypot(a, b); }
+inline double krylov_radius(const std::complex<double>& a, double b) { return std::sqrt(std::norm(a) + b * b); }
+inline double krylov_abs(double a) { return std::fabs(a); }
+inline double krylov_abs(const std::complex<double>& a) { return std::abs(a); }
+
+template <class S>
+struct HessenbergLsq {
+  const int m;
+  std::vector<S> H, cs, s, y;     // H: m x m, row-major (rotated columns are upper triangular); s: the rotated right-hand side
+  std::vector<double> sn, sub;    // sines; sub[i] = h_{i+1,i} as the Arnoldi step left it
+  explicit HessenbergLsq(int m_)
+      : m(m_), H((size_t)m_ * m_, S(0.0)), cs((size_t)m_, S(0.0)), s((size_t)m_ + 1, S(0.0)), y((size_t)m_, S(0.0)), sn((size_t)m_, 0.0), sub((size_t)m_, 0.0) {}
+  void begin(double rnorm) {      // a restart: s = ||r|| e_1
+    std::fill(s.begin(), s.end(), S(0.0));
+    s[0] = rnorm;
+  }
+  S& h(int k, int i) { return H[(size_t)k * m + i]; }      // k <= i
+  double& hsub(int i) { return sub[(size_t)i]; }
+  // rotates column i and the right-hand side; returns |s_{i+1}|, the residual norm of the least squares over columns 0 .. i
+  double close_column(int i) {
+    for (int k = 0; k < i; ++k) {                           // previous rotations
+      const S t = krylov_conj(cs[(size_t)k]) * h(k, i) + sn[(size_t)k] * h(k + 1, i);
+      h(k + 1, i) = -sn[(size_t)k] * h(k, i) + cs[(size_t)k] * h(k + 1, i);
+      h(k, i) = t;
+    }
+    const S a = h(i, i);
+    const double bq = sub[(size_t)i];
+    const double rr = krylov_radius(a, bq);
+    cs[(size_t)i] = (rr == 0.0) ? S(1.0) : a / rr;
+    sn[(size_t)i] = (rr == 0.0) ? 0.0 : bq / rr;
+    h(i, i) = rr;
+    s[(size_t)i + 1] = -sn[(size_t)i] * s[(size_t)i];
+    s[(size_t)i] = krylov_conj(cs[(size_t)i]) * s[(size_t)i];
+    return krylov_abs(s[(size_t)i + 1]);
+  }
+  const std::vector<S>& solve(int used) {
+    for (int i = used - 1; i >= 0; --i) {                   // y = H \ s (upper triangular)
+      S acc = s[(size_t)i];
+      for (int k = i + 1; k < used; ++k) acc -= h(i, k) * y[(size_t)k];
+      y[(size_t)i] = acc / h(i, i);
+    }
+    return y;
+  }
+};
+
+// ---- FGMRES_relaxation (FGMRES.jl:48-126): the normal equations of min || r0 - A Z t || ---------------------------------------------
+// Moore-Penrose inverse of a small symmetric matrix (H = (AZ)'(AZ), k <= 16) by cyclic Jacobi rotations;
+// cut-off as Julia's pinv: rtol = eps * k relative to the largest singular value.
+inline void pinv_sym(const std::vector<double>& H, int k, std::vector<double>& Pinv) {
+  std::vector<double> A(H), V((size_t)k * k, 0.0);
+  for (int i = 0; i < k; ++i) V[(size_t)i * k + i] = 1.0;
+  for (int sweep = 0; sweep < 100; ++sweep) {
+    double off = 0.0;
+    for (int p = 0; p < k; ++p)
+      for (int q = p + 1; q < k; ++q) off += A[(size_t)p * k + q] * A[(size_t)p * k + q];
+    if (off < 1e-300) break;
+    for (int p = 0; p < k; ++p)
+      for (int q = p + 1; q < k; ++q) {
+        const double apq = A[(size_t)p * k + q];
+        if (apq == 0.0) continue;
+        const double theta = (A[(size_t)q * k + q] - A[(size_t)p * k + p]) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (int i = 0; i < k; ++i) {
+          const double aip = A[(size_t)i * k + p], aiq = A[(size_t)i * k + q];
+          A[(size_t)i * k + p] = c * aip - sn * aiq;
+          A[(size_t)i * k + q] = sn * aip + c * aiq;
+        }
+        for (int i = 0; i < k; ++i) {
+          const double api = A[(size_t)p * k + i], aqi = A[(size_t)q * k + i];
+          A[(size_t)p * k + i] = c * api - sn * aqi;
+          A[(size_t)q * k + i] = sn * api + c * aqi;
+        }
+        for (int i = 0; i < k; ++i) {
+          const double vip = V[(size_t)i * k + p], viq = V[(size_t)i * k + q];
+          V[(size_t)i * k + p] = c * vip - sn * viq;
+          V[(size_t)i * k + q] = sn * vip + c * viq;
+        }
+      }
+  }
+  double smax = 0.0;
+  for (int i = 0; i < k; ++i) smax = std::max(smax, std::fabs(A[(size_t)i * k + i]));
+  const double tol = 2.220446049250313e-16 * k * smax;
+  Pinv.assign((size_t)k * k, 0.0);
+  for (int e = 0; e < k; ++e) {
+    const double lam = A[(size_t)e * k + e];
+    if (std::fabs(lam) <= tol) continue;
+    for (int i = 0; i < k; ++i)
+      for (int j = 0; j < k; ++j) Pinv[(size_t)i * k + j] += V[(size_t)i * k + e] * V[(size_t)j * k + e] / lam;
+  }
+}
+
+// H = (AZ)'(AZ) and xi = (AZ)'r0 grow by one direction per step (the rest stays zero); step() gives t = pinv(H) xi over all k and the
+// residual estimate rn = sqrt(|t'Ht - 2 t'xi + ||r0||^2|).
+struct RelaxLsq {
+  const int k;
+  std::vector<double> H, xi, tv, Pinv;
+  explicit RelaxLsq(int k_) : k(k_), H((size_t)k_ * k_, 0.0), xi((size_t)k_, 0.0), tv((size_t)k_, 0.0) {}
+  void set(int i, int j, double d) {                                       // H[:,j] = t; H[j,:] = t'  (l.99-101)
+    H[(size_t)i * k + j] = d;
+    H[(size_t)j * k + i] = d;
+  }
+  const std::vector<double>& t() const { return tv; }
+  double step(double rnorm0) {
+    pinv_sym(H, k, Pinv);                                                  // t = pinv(H)*xi           (l.102)
+    double tHt = 0.0, txi = 0.0;
+    for (int a = 0; a < k; ++a) {
+      double s = 0.0;
+      for (int b = 0; b < k; ++b) s += Pinv[(size_t)a * k + b] * xi[(size_t)b];
+      tv[(size_t)a] = s;
+    }
+    for (int a = 0; a < k; ++a) {
+      double s = 0.0;
+      for (int b = 0; b < k; ++b) s += H[(size_t)a * k + b] * tv[(size_t)b];
+      tHt += tv[(size_t)a] * s;
+      txi += tv[(size_t)a] * xi[(size_t)a];
+    }
+    return std::sqrt(std::fabs(tHt - 2.0 * txi + rnorm0 * rnorm0));       // l.104
+  }
+};
+
+// ---- dense helpers of the block drivers ---------------------------------------------------------------------------------------------
+struct SmallMat {   // row-major dense helper, host
+  int r = 0, c = 0;
+  std::vector<double> a;
+  SmallMat() {}
+  SmallMat(int r_, int c_) : r(r_), c(c_), a((size_t)r_ * c_, 0.0) {}
+  double& operator()(int i, int j) { return a[(size_t)i * c + j]; }
+  double operator()(int i, int j) const { return a[(size_t)i * c + j]; }
+};
+inline SmallMat sm_mul(const SmallMat& A, const SmallMat& B) {
+  SmallMat C(A.r, B.c);
+  for (int i = 0; i < A.r; ++i)
+    for (int k = 0; k < A.c; ++k) {
+      const double v = A(i, k);
+      for (int j = 0; j < B.c; ++j) C(i, j) += v * B(k, j);
+    }
+  return C;
+}
+inline SmallMat sm_T(const SmallMat& A) {
+  SmallMat C(A.c, A.r);
+  for (int i = 0; i < A.r; ++i)
+    for (int j = 0; j < A.c; ++j) C(j, i) = A(i, j);
+  return C;
+}
+// X = A \ B by Gaussian elimination with partial pivoting (A k x k); false if singular
+inline bool sm_solve(SmallMat A, SmallMat B, SmallMat& X) {
+  const int k = A.r;
+  for (int p = 0; p < k; ++p) {
+    int piv = p;
+    for (int i = p + 1; i < k; ++i)
+      if (std::fabs(A(i, p)) > std::fabs(A(piv, p))) piv = i;
+    if (A(piv, p) == 0.0) return false;
+    if (piv != p) {
+      for (int j = 0; j < k; ++j) std::swap(A(p, j), A(piv, j));
+      for (int j = 0; j < B.c; ++j) std::swap(B(p, j), B(piv, j));
+    }
+    for (int i = p + 1; i < k; ++i) {
+      const double f = A(i, p) / A(p, p);
+      if (f == 0.0) continue;
+      for (int j = p; j < k; ++j) A(i, j) -= f * A(p, j);
+      for (int j = 0; j < B.c; ++j) B(i, j) -= f * B(p, j);
+    }
+  }
+  X = SmallMat(k, B.c);
+  for (int j = 0; j < B.c; ++j)
+    for (int i = k - 1; i >= 0; --i) {
+      double acc = B(i, j);
+      for (int t = i + 1; t < k; ++t) acc -= A(i, t) * X(t, j);
+      X(i, j) = acc / A(i, i);
+    }
+  return true;
+}
+// upper triangular Rf with G = Rf'Rf for a positive SEMI-definite Gram matrix
+inline SmallMat sm_chol_semidefinite(const SmallMat& G, double rtol = 1e-14) {
+  const int k = G.r;
+  SmallMat R(k, k);
+  for (int c = 0; c < k; ++c) {
+    double d = G(c, c);
+    for (int a = 0; a < c; ++a) d -= R(a, c) * R(a, c);
+    if (G(c, c) <= 0.0 || d <= rtol * G(c, c)) continue;
+    R(c, c) = std::sqrt(d);
+    for (int j = c + 1; j < k; ++j) {
+      double t = G(c, j);
+      for (int a = 0; a < c; ++a) t -= R(a, c) * R(a, j);
+      R(c, j) = t / R(c, c);
+    }
+  }
+  return R;
+}
+// T with W*T = W*Rf^+: T[:,c] = (e_c - T[:,:c] Rf[:c,c]) / Rf[c,c], zero for zero pivots
+inline SmallMat sm_tri_pinv(const SmallMat& R) {
+  const int k = R.r;
+  SmallMat T(k, k);
+  for (int c = 0; c < k; ++c) {
+    if (R(c, c) == 0.0) continue;
+    for (int i = 0; i < k; ++i) {
+      double t = (i == c) ? 1.0 : 0.0;
+      for (int a = 0; a < c; ++a) t -= T(i, a) * R(a, c);
+      T(i, c) = t / R(c, c);
+    }
+  }
+  return T;
+}
+// min || xi - H Y ||_F over Y by Householder QR of H (rows x cols, rows >= cols); returns the residual norm
+inline double sm_lstsq(SmallMat H, SmallMat xi, SmallMat& Y) {
+  const int m = H.r, n = H.c, k = xi.c;
+  for (int j = 0; j < n; ++j) {
+    double nrm = 0.0;
+    for (int i = j; i < m; ++i) nrm += H(i, j) * H(i, j);
+    nrm = std::sqrt(nrm);
+    if (nrm == 0.0) continue;
+    const double alpha = H(j, j) > 0 ? -nrm : nrm;
+    std::vector<double> v((size_t)m, 0.0);
+    for (int i = j; i < m; ++i) v[(size_t)i] = H(i, j);
+    v[(size_t)j] -= alpha;
+    double vn = 0.0;
+    for (int i = j; i < m; ++i) vn += v[(size_t)i] * v[(size_t)i];
+    if (vn == 0.0) continue;
+    for (int c = j; c < n; ++c) {
+      double d = 0.0;
+      for (int i = j; i < m; ++i) d += v[(size_t)i] * H(i, c);
+      d *= 2.0 / vn;
+      for (int i = j; i < m; ++i) H(i, c) -= d * v[(size_t)i];
+    }
+    for (int c = 0; c < k; ++c) {
+      double d = 0.0;
+      for (int i = j; i < m; ++i) d += v[(size_t)i] * xi(i, c);
+      d *= 2.0 / vn;
+      for (int i = j; i < m; ++i) xi(i, c) -= d * v[(size_t)i];
+    }
+  }
+  Y = SmallMat(n, k);
+  for (int c = 0; c < k; ++c)
+    for (int i = n - 1; i >= 0; --i) {
+      double acc = xi(i, c);
+      for (int t = i + 1; t < n; ++t) acc -= H(i, t) * Y(t, c);
+      Y(i, c) = (H(i, i) != 0.0) ? acc / H(i, i) : 0.0;
+    }
+  double res = 0.0;
+  for (int i = n; i < m; ++i)
+    for (int c = 0; c < k; ++c) res += xi(i, c) * xi(i, c);
+  return std::sqrt(res);
+}
+inline SmallMat sm_scaled_identity(int k, double v) {
+  SmallMat I(k, k);
+  for (int i = 0; i < k; ++i) I(i, i) = v;
+  return I;
+}

@@ -1,53 +1,8 @@
 // mg_schedule.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
-// FGMRES relaxation (Jac-GMRES smoother, K-cycle), the level schedule (cycle_level, HIP graphs of the coarse sub-cycle), the solve loop.
+// FGMRES relaxation (Jac-GMRES smoother, K-cycle; its least squares is RelaxLsq of mg_krylov_host.hpp), the level schedule (cycle_level, HIP graphs of the coarse sub-cycle), the solve loop.
 namespace {
 // ---- FGMRES_relaxation (FGMRES.jl:48-126) --------------------------------------------------------------
-// Moore-Penrose inverse of a small symmetric matrix (H = (AZ)'(AZ), k <= 16) by cyclic Jacobi rotations;
-// cut-off as Julia's pinv: rtol = eps * k relative to the largest singular value.
-void pinv_sym(const std::vector<double>& H, int k, std::vector<double>& Pinv) {
-  std::vector<double> A(H), V((size_t)k * k, 0.0);
-  for (int i = 0; i < k; ++i) V[(size_t)i * k + i] = 1.0;
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < k; ++p)
-      for (int q = p + 1; q < k; ++q) off += A[(size_t)p * k + q] * A[(size_t)p * k + q];
-    if (off < 1e-300) break;
-    for (int p = 0; p < k; ++p)
-      for (int q = p + 1; q < k; ++q) {
-        const double apq = A[(size_t)p * k + q];
-        if (apq == 0.0) continue;
-        const double theta = (A[(size_t)q * k + q] - A[(size_t)p * k + p]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-        for (int i = 0; i < k; ++i) {
-          const double aip = A[(size_t)i * k + p], aiq = A[(size_t)i * k + q];
-          A[(size_t)i * k + p] = c * aip - sn * aiq;
-          A[(size_t)i * k + q] = sn * aip + c * aiq;
-        }
-        for (int i = 0; i < k; ++i) {
-          const double api = A[(size_t)p * k + i], aqi = A[(size_t)q * k + i];
-          A[(size_t)p * k + i] = c * api - sn * aqi;
-          A[(size_t)q * k + i] = sn * api + c * aqi;
-        }
-        for (int i = 0; i < k; ++i) {
-          const double vip = V[(size_t)i * k + p], viq = V[(size_t)i * k + q];
-          V[(size_t)i * k + p] = c * vip - sn * viq;
-          V[(size_t)i * k + q] = sn * vip + c * viq;
-        }
-      }
-  }
-  double smax = 0.0;
-  for (int i = 0; i < k; ++i) smax = std::max(smax, std::fabs(A[(size_t)i * k + i]));
-  const double tol = 2.220446049250313e-16 * k * smax;
-  Pinv.assign((size_t)k * k, 0.0);
-  for (int e = 0; e < k; ++e) {
-    const double lam = A[(size_t)e * k + e];
-    if (std::fabs(lam) <= tol) continue;
-    for (int i = 0; i < k; ++i)
-      for (int j = 0; j < k; ++j) Pinv[(size_t)i * k + j] += V[(size_t)i * k + e] * V[(size_t)j * k + e] / lam;
-  }
-}
-
+// The small least squares (pinv_sym, RelaxLsq) is host algebra: mg_krylov_host.hpp.
 int k_axpby(mg_hierarchy* h, double a, const double* x, double b, double* y, long long n) {
   hipLaunchKernelGGL(mgk::axpby_kernel, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, a, x, b, y, n);
   HIP_TRY(hipGetLastError());
@@ -81,7 +36,7 @@ int fgmres_relax(mg_hierarchy* h, int lv, const double* r0, double* x0, long lon
   } else {
     MG_TRY(norm_sync(h, r0, len, &rnorm0));
   }
-  std::vector<double> H((size_t)k * k, 0.0), xi((size_t)k, 0.0), t((size_t)k, 0.0), Pinv;
+  RelaxLsq Q(k);
   int used = 0;
   for (int j = 0; j < k; ++j) {
     double* z = Zb + (size_t)j * len;
@@ -94,28 +49,14 @@ int fgmres_relax(mg_hierarchy* h, int lv, const double* r0, double* x0, long lon
     for (int i = 0; i <= j; ++i) {                                       // t = AZ' * w              (l.95)
       double d = 0.0;
       MG_TRY(gdot(AZb + (size_t)i * len, w, &d));
-      H[(size_t)i * k + j] = d;
-      H[(size_t)j * k + i] = d;                                          // H[:,j] = t; H[j,:] = t'  (l.99-101)
+      Q.set(i, j, d);
     }
-    MG_TRY(gdot(w, r0, &xi[(size_t)j]));                                 // xi[j] = dot(w, r0)       (l.97)
-    pinv_sym(H, k, Pinv);                                                // t = pinv(H)*xi           (l.102)
-    double tHt = 0.0, txi = 0.0;
-    for (int a = 0; a < k; ++a) {
-      double s = 0.0;
-      for (int b = 0; b < k; ++b) s += Pinv[(size_t)a * k + b] * xi[(size_t)b];
-      t[(size_t)a] = s;
-    }
-    for (int a = 0; a < k; ++a) {
-      double s = 0.0;
-      for (int b = 0; b < k; ++b) s += H[(size_t)a * k + b] * t[(size_t)b];
-      tHt += t[(size_t)a] * s;
-      txi += t[(size_t)a] * xi[(size_t)a];
-    }
-    const double rn = std::sqrt(std::fabs(tHt - 2.0 * txi + rnorm0 * rnorm0));   // l.104
+    MG_TRY(gdot(w, r0, &Q.xi[(size_t)j]));                               // xi[j] = dot(w, r0)       (l.97)
+    const double rn = Q.step(rnorm0);                                    // t = pinv(H)*xi, ||r0 - AZ t||  (l.102-104)
     if (rn < TOL) break;                                                          // l.114-117
   }
   for (int j = 0; j < used; ++j)                                         // x0 += Z*t                (l.121-123)
-    MG_TRY(k_axpby(h, t[(size_t)j], Zb + (size_t)j * len, (j == 0 && x0_is_zero) ? 0.0 : 1.0, x0, len));
+    MG_TRY(k_axpby(h, Q.t()[(size_t)j], Zb + (size_t)j * len, (j == 0 && x0_is_zero) ? 0.0 : 1.0, x0, len));
   if (ghs) gh_set(h, lv, x0, 0);      // (what is claimed of the result: its owned rows)
   return MG_OK;
 }

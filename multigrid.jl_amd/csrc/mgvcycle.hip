@@ -38,6 +38,7 @@
 #include "mg_cxvec.hpp"
 #include "mg_dd.hpp"
 #include "mg_vanka.hpp"
+#include "mg_krylov_host.hpp"   // host only: KrylovReport, HessenbergLsq, RelaxLsq / pinv_sym, SmallMat / sm_*
 
 
 // One translation unit in parts (the 6 800-line file split by responsibility; the order is the dependency order):

@@ -161,6 +161,34 @@ def test_device_fgmres_matches_oracle(mg, built, inner):
     mg.clear_(p)
 
 
+@pytest.mark.gpu
+def test_device_fgmres_per_vector_orthogonalisation(mg, built, monkeypatch):
+    """The per-vector Gram-Schmidt route of the FGMRES space (option no_mgs_chain: one dot, one synchronisation and one update per basis
+    vector) against the oracle, within the bounds of test_device_fgmres_matches_oracle, and against the chained route on the same
+    problem: the two take the same sums in another order, 1e-10 (BASELINE.json)."""
+    A, mesh = mg.poisson_shifted([8, 8, 8])
+    b = mg.seeded_rhs(A)
+
+    def solve():
+        p = mg.getMGparam(np.float64, np.int64, 2, 8, 20, 1e-9, "Jac", 0.8, 1, 1, "V", "NoMUMPS", 0.5, 0.0)
+        mg.MGsetup(A, mesh, p)
+        x, _, it, rv = mg.solveGMRES_MG(A, p, b, np.zeros_like(b), True, 3)
+        return p, x, it, np.asarray(rv)
+
+    pc, xc, itc, rvc = solve()                             # the chained route
+    flagc = pc.flag
+    mg.clear_(pc)
+    monkeypatch.setenv("MG_NO_MGS_CHAIN", "1")             # read when the handle is created
+    p, x, it, rv = solve()
+    xo, flag, ito, rvo = orc.solveGMRES_MG(p, b, np.zeros_like(b), 3)
+    assert it == ito and p.flag == flag == 0 and len(rv) == len(rvo)
+    assert np.abs(rv - rvo).max() / rvo[0] < 1e-8
+    assert np.abs(x - xo).max() <= 1e-8 * np.abs(xo).max()
+    assert it == itc and flagc == 0 and len(rv) == len(rvc)
+    assert np.abs(rv - rvc).max() <= 1e-10 * rvc[0]
+    mg.clear_(p)
+
+
 # ---- block branches (SolveFuncs.jl:95,113,130), mixed precision hook (l.52-58), wrapper transposition -----------------
 def test_oracle_block_methods_converge(mg, built):
     """The restated blockCG / blockBiCGSTB / blockFGMRES with the oracle's multigrid cycle as preconditioner solve a
