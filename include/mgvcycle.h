@@ -920,6 +920,45 @@ int mg_cvec_bicg_xr_dev_CFP64(const double* alpha, const double* omega, const do
 int mg_cvec_gs_update_dev_CFP64(long long m, const double* h_host, const double* const* vs_dev, double* w, long long n,
                                 double* workspace_dev, double* out_dev, void* stream);
 
+/* ---- ComplexF32 hierarchies (CF32): the single-precision cycle inside the ComplexF64 Krylov drivers ------------------------
+ * The reference's VAL = ComplexF32 (getMGparam: singlePrecision, MGdef.jl:151; MGsetup.jl:31-33, 79-82, 108-110): As and relaxPrecs
+ * are ComplexF32, Ps / Rs Float32, every level vector ComplexF32; products and row sums are formed in single precision in stored
+ * order by the same kernels, the same row blocks and the same cycle code as a CF64 handle's (csrc/mg_complex.hpp).  Per non-zero
+ * the stream kernel moves 12 B for A (8 value + 4 index) against 20, 8 B for P / R against 12, and 8 B per vector element against
+ * 16.  ||r||^2 of mg_solve_CF32 is summed in double.
+ *
+ * mg_create_CF32 makes the handle.  mg_set_operator_CF32_INT64 takes the reference's AT arrays as the CF64 entry does: for MG_OP_A
+ * nzval holds nnz interleaved (re, im) float pairs (conjugated here once), for MG_OP_P / MG_OP_R nnz floats.  mg_set_relax_CF32
+ * takes n (re, im) float pairs.  mg_cycle_CF32 / mg_solve_CF32 / mg_spmv_CF32 take host vectors of (re, im) float pairs; alpha and
+ * beta are (re, im) float pairs; resvec is double.
+ *
+ * The coarsest solve stays ComplexF64, as Julia's lu of a ComplexF32 matrix does (UMFPACK has no single form; MGsetup.jl:350,
+ * MGcycle.jl:177-178): set it with mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64 (double factors); the cycle
+ * widens bc, runs the CF64 coarsest kernels and narrows xc.
+ *
+ * The mixed branch of getMultigridPreconditioner (SolveFuncs.jl:52-58) is served by the ComplexF64 Krylov entry points above, which
+ * accept a CF32 handle: mg_set_krylov_operator_CFP64_INT64, mg_replace_krylov_values_CFP64, mg_bicgstab[_dev]_CFP64,
+ * mg_fgmres[_dev]_CFP64.  The system operator, every Krylov vector, dot and scalar stay ComplexF64; the preconditioner narrows its
+ * input into the fine level's b, runs the single cycle from zero and widens the result (the widening pass is the copy-out the
+ * drivers make anyway; BiCGSTAB's s_hat takes one more vector).  Without a Krylov operator set, As[1] is widened once into the
+ * Krylov operator at the first driver call - the Krylov product is never single.  mg_cycle_dev_CFP64 on a CF32 handle is that
+ * closure on ComplexF64 device vectors, from zero: x_is_zero = 0 returns MG_ERR_UNSUPPORTED.
+ *
+ * Refusals.  A _CF32 entry point on a CF64 or FP64 handle, and mg_set_operator_CF64_INT64 / mg_set_relax_CF64 / mg_cycle_CF64 /
+ * mg_solve_CF64 / mg_spmv_CF64 / mg_set_operator_FP64_INT64 on a CF32 handle: MG_ERR_STATE.  Not served for a CF32 handle
+ * (MG_ERR_UNSUPPORTED): mg_rap_CF64, mg_rap_level_ms_CF64, mg_get_values_CF64, mg_get_relax_CF64, mg_replace_values_CF64 (the
+ * hierarchy is set up again on the host and uploaded), mg_set_coarse_dd (a Schwarz coarsest solve), the K-cycle, Jac-GMRES,
+ * nrhs > 1, and whatever a CF64 handle does not serve. */
+int mg_create_CF32(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out);
+int mg_set_operator_CF32_INT64(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols,
+                               const long long* colptr, const long long* rowval, const float* nzval);
+int mg_set_relax_CF32(mg_hierarchy* h, long long level, const float* d, long long n, long long relaxPre, long long relaxPost);
+int mg_cycle_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long long nrhs, long long x_is_zero);
+int mg_solve_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long long nrhs, double tol, long long maxIter,
+                  long long* iters, double* resvec);
+int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float* alpha, const float* x, const float* beta,
+                 float* y, long long nrhs);
+
 const char* mg_last_error(void);
 const char* mg_version(void);
 

@@ -1,5 +1,6 @@
-// mg_complex.hpp - gfx950 kernels of the ComplexF64 (CF64) cycle: generic CSR only; complex hybrid Kaczmarz; the chip-wide
-// complex triangular solve of the factor applier (cx_sptrsv_*, cx_tri_*, at the end).
+// mg_complex.hpp - gfx950 kernels of the ComplexF64 (CF64) cycle and of its single-precision form (CF32: the same kernels on
+// float pairs, see f2_t below): generic CSR only; complex hybrid Kaczmarz; the chip-wide complex triangular solve of the factor
+// applier (cx_sptrsv_*, cx_tri_*, at the end).
 //
 // Complex values are interleaved (re, im) doubles - Julia ComplexF64, numpy complex128, hipDoubleComplex - and are
 // loaded as one 16-byte d2_t.  The operator A of a CF64 handle is stored conjugated at upload (nzval of the
@@ -18,16 +19,29 @@
 namespace mgk {
 
 constexpr int CX_ITEMS = 4;                 // complex products per thread per chunk
-constexpr int CX_CHUNK = BLK * CX_ITEMS;    // 1024 products = 16 KiB of LDS per workgroup
+constexpr int CX_CHUNK = BLK * CX_ITEMS;    // 1024 products: 16 KiB of LDS per workgroup in double, 8 KiB in single (one row-block
+                                            // scheme for both precisions: the widened copy of a single operator keeps its blocks)
+
+// A ComplexF32 (CF32) hierarchy runs the same kernels on (re, im) float pairs: every kernel of the cycle below is written once
+// over the pair type C (d2_t or f2_t) with its scalar cx_scalar<C>.  Products and row sums are formed in C's precision, in stored
+// order (the reference's arithmetic for VAL = ComplexF32); the partials of ||r||^2 are double for both.
+typedef float f2_t __attribute__((ext_vector_type(2)));
+template <typename C> struct cx_scalar;
+template <> struct cx_scalar<d2_t> { typedef double type; };
+template <> struct cx_scalar<f2_t> { typedef float type; };
 
 __device__ __forceinline__ d2_t cmul(d2_t a, d2_t b) { return d2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 __device__ __forceinline__ d2_t cmul(double a, d2_t b) { return d2_t{a * b.x, a * b.y}; }
+__device__ __forceinline__ f2_t cmul(f2_t a, f2_t b) { return f2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+__device__ __forceinline__ f2_t cmul(float a, f2_t b) { return f2_t{a * b.x, a * b.y}; }
 __device__ __forceinline__ d2_t cdiv(d2_t a, d2_t b) {
   const double s = b.x * b.x + b.y * b.y;
   return d2_t{(a.x * b.x + a.y * b.y) / s, (a.y * b.x - a.x * b.y) / s};
 }
 __device__ __forceinline__ double cabs2(d2_t a) { return a.x * a.x + a.y * a.y; }
+__device__ __forceinline__ double cabs2(f2_t a) { return (double)a.x * (double)a.x + (double)a.y * (double)a.y; }   // exact products
 __device__ __forceinline__ d2_t shfl_xor_v(d2_t a, int o) { return d2_t{__shfl_xor(a.x, o), __shfl_xor(a.y, o)}; }
+__device__ __forceinline__ f2_t shfl_xor_v(f2_t a, int o) { return f2_t{__shfl_xor(a.x, o), __shfl_xor(a.y, o)}; }
 
 // the value stream of an operator: complex (A, conj'd at upload) or real (P, R)
 template <typename PTR, typename VT>
@@ -40,27 +54,29 @@ struct CxCsrDev {
   int n_rows;
 };
 
-struct CxVecArgs {
-  const d2_t* x;   // gathered vector  [n_cols]
-  d2_t* y;         // output           [n_rows]
-  const d2_t* b;   // RESID / SMOOTH   [n_rows]
-  const d2_t* d;   // SMOOTH: relaxPrec [n_rows]
+template <typename C>
+struct CxVecArgsT {
+  const C* x;      // gathered vector  [n_cols]
+  C* y;            // output           [n_rows]
+  const C* b;      // RESID / SMOOTH   [n_rows]
+  const C* d;      // SMOOTH: relaxPrec [n_rows]
   double* sumsq;   // optional: per-row-block sum of |out|^2 (summed by sum_final)
-  d2_t alpha;      // AXPBY
-  d2_t beta;       // AXPBY (beta == 0: y is not read)
+  C alpha;         // AXPBY
+  C beta;          // AXPBY (beta == 0: y is not read)
   int beta_zero;
 };
+typedef CxVecArgsT<d2_t> CxVecArgs;
 
 // pb: beta*y (AXPBY) or b (RESID, SMOOTH); px, pd: the row's x and d (SMOOTH; x is the gathered vector itself)
-template <int MODE>
-__device__ __forceinline__ d2_t cx_epilogue(const CxVecArgs& v, d2_t acc, d2_t pb, d2_t pd, d2_t px) {
+template <int MODE, typename C>
+__device__ __forceinline__ C cx_epilogue(const CxVecArgsT<C>& v, C acc, C pb, C pd, C px) {
   if (MODE == AXPBY) return cmul(v.alpha, acc) + pb;
   if (MODE == RESID) return pb - acc;
   return px + cmul(pd, pb - acc);   // SMOOTH: x + d.*(b - A x)   (MGcycle.jl:129-131)
 }
 
-template <int MODE>
-__device__ __forceinline__ void cx_operands(const CxVecArgs& v, int row, d2_t& pb, d2_t& pd, d2_t& px) {
+template <int MODE, typename C>
+__device__ __forceinline__ void cx_operands(const CxVecArgsT<C>& v, int row, C& pb, C& pd, C& px) {
   if (MODE == AXPBY) {
     if (!v.beta_zero) pb = cmul(v.beta, v.y[row]);
   } else {
@@ -72,9 +88,10 @@ __device__ __forceinline__ void cx_operands(const CxVecArgs& v, int row, d2_t& p
   }
 }
 
-template <int MODE, typename PTR, typename VT>
-__global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, CxVecArgs v) {
-  __shared__ d2_t prod[CX_CHUNK];
+template <int MODE, typename PTR, typename VT, typename C>
+__global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, CxVecArgsT<C> v) {
+  typedef typename cx_scalar<C>::type T;
+  __shared__ C prod[CX_CHUNK];
   __shared__ int srow[MAXROWS + 1];
   __shared__ double red[2 * (BLK / 64)];
 
@@ -88,20 +105,20 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
 
   if (nrows == 1 && (k1 - k0) > CX_CHUNK) {
     // one row longer than a chunk: the whole workgroup strides over it
-    d2_t acc = d2_t{0.0, 0.0};
+    C acc = C{};
     for (PTR k = k0 + tid; k < k1; k += BLK) acc += cmul(A.val[k], v.x[A.colidx[k]]);
     for (int o = 32; o > 0; o >>= 1) acc += shfl_xor_v(acc, o);
-    if ((tid & 63) == 0) {
+    if ((tid & 63) == 0) {   // (a float travels through a double slot unchanged)
       red[2 * (tid >> 6)] = acc.x;
       red[2 * (tid >> 6) + 1] = acc.y;
     }
     __syncthreads();
     if (tid == 0) {
-      d2_t s = d2_t{0.0, 0.0};
-      for (int w = 0; w < BLK / 64; ++w) s += d2_t{red[2 * w], red[2 * w + 1]};
-      d2_t pb = d2_t{0.0, 0.0}, pd = pb, px = pb;
+      C s = C{};
+      for (int w = 0; w < BLK / 64; ++w) s += C{(T)red[2 * w], (T)red[2 * w + 1]};
+      C pb = C{}, pd = pb, px = pb;
       cx_operands<MODE>(v, r0, pb, pd, px);
-      const d2_t o = cx_epilogue<MODE>(v, s, pb, pd, px);
+      const C o = cx_epilogue<MODE>(v, s, pb, pd, px);
       v.y[r0] = o;
       if (v.sumsq) v.sumsq[bid] = cabs2(o);
     }
@@ -125,7 +142,7 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
   if (tid <= nrows) srow[tid] = (int)(A.rowptr[r0 + tid] - k0);
   if (tid == 0 && nrows == MAXROWS) srow[MAXROWS] = (int)(k1 - k0);
   const bool owner = tid < nrows;
-  d2_t pb = d2_t{0.0, 0.0}, pd = pb, px = pb;
+  C pb = C{}, pd = pb, px = pb;
   if (owner) cx_operands<MODE>(v, r0 + tid, pb, pd, px);
   // ---- gather x and stage the products -----------------------------------------------------------
 #pragma unroll
@@ -135,9 +152,9 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
   }
   __syncthreads();
   // ---- one lane per row: the row's products in stored order, fused epilogue ------------------------
-  d2_t outv = d2_t{0.0, 0.0};
+  C outv = C{};
   if (owner) {
-    d2_t acc = d2_t{0.0, 0.0};
+    C acc = C{};
     const int s = srow[tid], e = srow[tid + 1];
     for (int k = s; k < e; ++k) acc += prod[k];
     outv = cx_epilogue<MODE>(v, acc, pb, pd, px);
@@ -157,20 +174,38 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
 }
 
 // x = d.*b: relax's only update when the sweep starts from x = 0 (MGcycle.jl:134 with r = b)
-__global__ __launch_bounds__(BLK) void cx_dscale(const d2_t* __restrict__ d, const d2_t* __restrict__ b, d2_t* __restrict__ x,
-                                                 long long n) {
+template <typename C>
+__global__ __launch_bounds__(BLK) void cx_dscale(const C* __restrict__ d, const C* __restrict__ b, C* __restrict__ x, long long n) {
   const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
   if (i < n) x[i] = cmul(d[i], b[i]);
 }
 
 // first pass of the deterministic sum of |z_i|^2: one partial per workgroup (second pass: sum_final)
-__global__ __launch_bounds__(BLK) void cx_sumsq_partial(const d2_t* __restrict__ z, long long n, double* __restrict__ partial) {
+template <typename C>
+__global__ __launch_bounds__(BLK) void cx_sumsq_partial(const C* __restrict__ z, long long n, double* __restrict__ partial) {
   __shared__ double red[BLK / 64];
   const long long stride = (long long)gridDim.x * BLK;
   double acc = 0.0;
   for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) acc += cabs2(z[i]);
   const double s = block_sum(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// The two conversion passes of the mixed-precision preconditioner (SolveFuncs.jl:52-58: bl .= b ... z2 .= z), one element per
+// lane: the ComplexF64 side is one 16-byte access, the ComplexF32 side one 8-byte access.
+__global__ __launch_bounds__(BLK) void cx_narrow(const d2_t* __restrict__ src, f2_t* __restrict__ dst, long long n) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i < n) {
+    const d2_t a = src[i];
+    dst[i] = f2_t{(float)a.x, (float)a.y};
+  }
+}
+__global__ __launch_bounds__(BLK) void cx_widen(const f2_t* __restrict__ src, d2_t* __restrict__ dst, long long n) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i < n) {
+    const f2_t a = src[i];
+    dst[i] = d2_t{(double)a.x, (double)a.y};
+  }
 }
 
 // coarsest solve from the explicit inverse: x = Ainv * b, Ainv row-major n x n complex; one wavefront per row

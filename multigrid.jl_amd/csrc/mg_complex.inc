@@ -3,6 +3,11 @@
 // pointwise relaxation, dense-inverse or sparse-LU coarsest solve.  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
 // The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
+// ComplexF32 / Int64 hierarchies (the _CF32 entry points; the reference's VAL = ComplexF32, singlePrecision) share all of it: the
+// same CxState / CxLevel / CxMat with single values, and cx_upload, cx_spmv, cx_relax, cx_cycle, cx_finalize and the host forms of
+// cycle / solve / spmv written once over the pair type (cx_t or cf_t).  Their coarsest solve stays ComplexF64 (widen bc, the CF64
+// kernels, narrow xc), and the _CFP64 Krylov drivers take them with the single cycle as preconditioner (the mixed branch of
+// getMultigridPreconditioner, SolveFuncs.jl:52-58).
 // Also here: the stand-alone ComplexF64 factor applier behind mg_lu_*_CFP64 (CxLu; its extern "C" entry points sit beside the
 // real applier's in mg_cabi.inc).
 //
@@ -11,21 +16,25 @@
 //   solveMG         src/Multigrid/SolveFuncs.jl:3-39 (norm: sqrt(sum |r_i|^2))
 //   SpMatMul        src/Multigrid/SpMatMul.jl:4-13: mul!(target, adjoint(AT), x, alpha, beta) - A = AT^H, conj'd at upload
 typedef mgk::d2_t cx_t;
+typedef mgk::f2_t cf_t;   // the pair type of a ComplexF32 (CF32) handle: the same state, cycle and kernels in single precision
 
 // (the state types live beside mg_hierarchy, outside the anonymous namespace: the handle holds a CxState*)
 // one operator of a CF64 hierarchy, generic CSR: complex values (A = AT^H) or real values (P, R)
 struct CxMat {
   bool set = false, cplx = false, wide = false;
+  bool single = false;          // values in valf (a CF32 handle's operators); val otherwise
   long long n_rows = 0, n_cols = 0, nnz = 0;
   int nblocks = 0;
   long long max_row = 0;        // the longest row (sizes the accumulator of cx_rap_numeric)
   DevBuf<int> rowptr, colidx, blk_row;
   DevBuf<long long> rowptr64;   // wide: >= 2^31 - 4096 non-zeros (or the option force_rowptr64)
   DevBuf<double> val;           // nnz real values, or 2*nnz interleaved (re, im)
+  DevBuf<float> valf;           // the same in single
+  const void* vals() const { return single ? static_cast<const void*>(valf.p) : static_cast<const void*>(val.p); }
   bool has_t = false;           // the transposed pattern of cx_colsumsq (built on the first SPAI re-setup of the level)
   DevBuf<int> t_ptr, t_perm;
   void release() {
-    rowptr.release(); colidx.release(); blk_row.release(); rowptr64.release(); val.release();
+    rowptr.release(); colidx.release(); blk_row.release(); rowptr64.release(); val.release(); valf.release();
     t_ptr.release(); t_perm.release();
     set = false;
     has_t = false;
@@ -34,6 +43,7 @@ struct CxMat {
 
 struct CxLevel {
   CxMat A, P, R;
+  // (a CF32 handle keeps (re, im) float pairs in the same buffers: one double slot per complex value, see cx_len)
   DevBuf<double> d;            // relaxPrecs[l], complex
   bool relax_set = false;
   long long npre = 0, npost = 0, n = 0;
@@ -43,6 +53,10 @@ struct CxLevel {
 struct CxState {
   std::vector<CxLevel> lev;
   bool finalized = false;
+  bool single = false;         // a CF32 handle (mg_create_CF32): operators, relaxPrecs and level vectors in single; the coarsest solve,
+                               // the Krylov operator K and every Krylov vector stay ComplexF64
+  bool K_auto = false;         // K is As[1] widened (the system operator of a CF32 handle's drivers when none was set)
+  DevBuf<double> cw_b, cw_x;   // CF32: the coarsest right-hand side widened, the coarsest solution before it is narrowed
   bool coarse_set = false, coarse_lu = false;
   struct CxLu* coarse_multi = nullptr;   // sparse factors of >= lu_multi_min_rows rows: the chip-wide form of the factor applier
   long long n_coarse = 0;
@@ -68,7 +82,7 @@ struct CxState {
     Ainv.release();
     for (DevBuf<int>* d : {&luLptr, &luLcol, &luUptr, &luUcol, &luP, &luQ, &luLorder, &luLlvl, &luUorder, &luUlvl}) d->release();
     luLval.release(); luUval.release(); luWork.release();
-    stage_b.release(); partial.release();
+    stage_b.release(); partial.release(); cw_b.release(); cw_x.release();
     K.release();
     kwork.release(); kpart.release(); kscal.release(); stage_x.release();
     if (h_kscal) (void)hipHostFree(h_kscal);
@@ -109,20 +123,42 @@ void cx_destroy(CxState* s) {
   delete s;
 }
 
-inline cx_t* cxp(DevBuf<double>& b) { return reinterpret_cast<cx_t*>(b.p); }
+template <typename C = cx_t>
+inline C* cxp(DevBuf<double>& b) { return reinterpret_cast<C*>(b.p); }
+template <typename C = cx_t>
+inline const C* cxc(const DevBuf<double>& b) { return reinterpret_cast<const C*>(b.p); }
 inline unsigned cx_grid(long long n) { return (unsigned)((n + mgk::BLK - 1) / mgk::BLK); }
+template <typename T> struct cx_non_deduced { typedef T type; };   // (a nullptr argument must not take part in deducing C)
+// doubles that hold n complex values of the handle's precision
+inline size_t cx_len(const CxState& S, long long n) { return (S.single ? 1 : 2) * (size_t)n; }
 
-int cx_level_ok(mg_hierarchy* h, long long level) {
+// which handles an entry point serves: the _CF64 ones CF64 handles, the _CF32 ones CF32 handles, the coarsest-solve setters and
+// the _CFP64 Krylov entry points both
+enum CxWant { CX_WANT64, CX_WANT32, CX_ANY };
+int cx_handle_ok(mg_hierarchy* h, CxWant want) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+  if (!h->cx) return fail(MG_ERR_STATE, "complex entry point called on an FP64 handle (create it with mg_create_CF64 or mg_create_CF32)");
+  if (want == CX_WANT64 && h->cx->single) return fail(MG_ERR_STATE, "CF64 entry point called on a CF32 handle (its _CF32 twin serves it)");
+  if (want == CX_WANT32 && !h->cx->single) return fail(MG_ERR_STATE, "CF32 entry point called on a CF64 handle (create it with mg_create_CF32)");
+  return MG_OK;
+}
+int cx_level_ok(mg_hierarchy* h, long long level, CxWant want = CX_WANT64) {
+  MG_TRY(cx_handle_ok(h, want));
   if (level < 1 || level > h->nlevels) return fail(MG_ERR_INVALID, "bad level %lld", level);
   return MG_OK;
 }
+// what a CF32 handle does not serve (device re-setup, reading values back)
+#define MG_CF32_UNSUPPORTED(h)                                                                                       \
+  do {                                                                                                               \
+    if ((h) && (h)->cx && (h)->cx->single) return fail(MG_ERR_UNSUPPORTED, "%s is not served for CF32 handles", __func__); \
+  } while (0)
 
 // Upload one operator from the reference's CSC-of-AT arrays (1-based Int64).  Complex values are conjugated here, once:
 // the kernels then compute y_i = sum_k val_k x[col_k] = (AT^H x)_i.
+template <typename ST>
 int cx_upload(CxMat* M, const Options& opt, long long n_rows, long long n_cols, const long long* colptr, const long long* rowval,
-              const double* nzval, bool cplx) {
+              const ST* nzval, bool cplx) {
+  constexpr bool single = sizeof(ST) == sizeof(float);
   if (n_rows < 1 || n_cols < 1 || !colptr || !rowval || !nzval) return fail(MG_ERR_INVALID, "empty operator or null array");
   if (n_rows >= (1LL << 31) - 1 || n_cols >= (1LL << 31) - 1) return fail(MG_ERR_UNSUPPORTED, "dimension exceeds int32 device indices");
   if (colptr[0] != 1) return fail(MG_ERR_INVALID, "colptr[1] must be 1 (1-based Julia arrays expected)");
@@ -150,10 +186,11 @@ int cx_upload(CxMat* M, const Options& opt, long long n_rows, long long n_cols, 
     r = e;
   }
   const size_t vw = cplx ? 2 : 1;
-  std::vector<double> v((size_t)std::max<long long>(nnz, 1) * vw, 0.0);
+  std::vector<ST> v((size_t)std::max<long long>(nnz, 1) * vw, ST(0));
   for (long long k = 0; k < (long long)nnz * (long long)vw; ++k) v[(size_t)k] = (cplx && (k & 1)) ? -nzval[k] : nzval[k];
   M->release();
   M->cplx = cplx;
+  M->single = single;
   M->wide = nnz >= (1LL << 31) - 4096 || opt.force_rowptr64;
   M->n_rows = n_rows;
   M->n_cols = n_cols;
@@ -170,10 +207,11 @@ int cx_upload(CxMat* M, const Options& opt, long long n_rows, long long n_cols, 
     HIP_TRY(hipMemcpy(M->rowptr.p, rp32.data(), rp32.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   MG_TRY(M->colidx.alloc(ci.size()));
-  MG_TRY(M->val.alloc(v.size()));
+  if (single) MG_TRY(M->valf.alloc(v.size()));
+  else MG_TRY(M->val.alloc(v.size()));
   MG_TRY(M->blk_row.alloc(blk.size()));
   HIP_TRY(hipMemcpy(M->colidx.p, ci.data(), ci.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(M->val.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(const_cast<void*>(M->vals()), v.data(), v.size() * sizeof(ST), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(M->blk_row.p, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
   M->set = true;
   return MG_OK;
@@ -182,6 +220,8 @@ int cx_upload(CxMat* M, const Options& opt, long long n_rows, long long n_cols, 
 // P or R of a CF64 handle (mg_set_operator_FP64_INT64 routes them here): real values, applied to complex vectors
 int cx_set_transfer(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols, const long long* colptr,
                     const long long* rowval, const double* nzval) {
+  if (h && h->cx && h->cx->single)
+    return fail(MG_ERR_STATE, "mg_set_operator_FP64_INT64 on a CF32 handle: Ps and Rs are Float32 (mg_set_operator_CF32_INT64)");
   MG_TRY(cx_level_ok(h, level));
   if (which == MG_OP_A)
     return fail(MG_ERR_STATE, "mg_set_operator_FP64_INT64(MG_OP_A) on a CF64 handle: As are complex (mg_set_operator_CF64_INT64)");
@@ -194,42 +234,47 @@ int cx_set_transfer(mg_hierarchy* h, long long level, long long which, long long
   return MG_OK;
 }
 
-// y = epilogue(M * x) on h's stream; the launch of one (MODE, row-pointer width, value type)
-template <int MODE, typename PTR, typename VT>
-void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::CxVecArgs& v) {
+// y = epilogue(M * x) on h's stream; the launch of one (MODE, row-pointer width, value type, pair type)
+template <int MODE, typename PTR, typename VT, typename C>
+void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::CxVecArgsT<C>& v) {
   mgk::CxCsrDev<PTR, VT> D;
   D.rowptr = rowptr;
   D.colidx = M.colidx.p;
-  D.val = reinterpret_cast<const VT*>(M.val.p);
+  D.val = static_cast<const VT*>(M.vals());
   D.blk_row = M.blk_row.p;
   D.nblocks = M.nblocks;
   D.n_rows = (int)M.n_rows;
-  hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<MODE, PTR, VT>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+  hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<MODE, PTR, VT, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
 }
 
-template <int MODE>
-int cx_spmv(mg_hierarchy* h, const CxMat& M, const cx_t* x, cx_t* y, const cx_t* b, const cx_t* d, double* sumsq,
-            cx_t alpha = cx_t{1.0, 0.0}, cx_t beta = cx_t{0.0, 0.0}) {
-  mgk::CxVecArgs v;
+// C: the pair type of the vectors (cx_t or cf_t), deduced from x; the operator holds values of the same precision
+template <int MODE, typename C>
+int cx_spmv(mg_hierarchy* h, const CxMat& M, const C* x, typename cx_non_deduced<C>::type* y, const typename cx_non_deduced<C>::type* b,
+            const typename cx_non_deduced<C>::type* d, double* sumsq, typename cx_non_deduced<C>::type alpha = C{1, 0},
+            typename cx_non_deduced<C>::type beta = C{0, 0}) {
+  typedef typename mgk::cx_scalar<C>::type T;
+  if (M.single != (sizeof(T) == sizeof(float))) return fail(MG_ERR_INVALID, "internal: operator and vectors differ in precision");
+  mgk::CxVecArgsT<C> v;
   v.x = x; v.y = y; v.b = b; v.d = d; v.sumsq = sumsq;
   v.alpha = alpha; v.beta = beta;
-  v.beta_zero = (beta.x == 0.0 && beta.y == 0.0) ? 1 : 0;
+  v.beta_zero = (beta.x == 0 && beta.y == 0) ? 1 : 0;
   if (M.cplx) {
-    if (M.wide) cx_launch<MODE, long long, cx_t>(h, M, M.rowptr64.p, v);
-    else cx_launch<MODE, int, cx_t>(h, M, M.rowptr.p, v);
+    if (M.wide) cx_launch<MODE, long long, C, C>(h, M, M.rowptr64.p, v);
+    else cx_launch<MODE, int, C, C>(h, M, M.rowptr.p, v);
   } else {
     if (MODE != mgk::AXPBY) return fail(MG_ERR_INVALID, "internal: a real transfer operator serves the AXPBY form only");
-    if (M.wide) cx_launch<mgk::AXPBY, long long, double>(h, M, M.rowptr64.p, v);
-    else cx_launch<mgk::AXPBY, int, double>(h, M, M.rowptr.p, v);
+    if (M.wide) cx_launch<mgk::AXPBY, long long, T, C>(h, M, M.rowptr64.p, v);
+    else cx_launch<mgk::AXPBY, int, T, C>(h, M, M.rowptr.p, v);
   }
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 
 // ||z||^2 = sum |z_i|^2 into the pinned host scalar: the two-pass deterministic sum
-int cx_norm2(mg_hierarchy* h, const cx_t* z, long long n, double* out) {
+template <typename C>
+int cx_norm2(mg_hierarchy* h, const C* z, long long n, double* out) {
   const int np = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n + mgk::BLK - 1) / mgk::BLK));
-  hipLaunchKernelGGL(mgk::cx_sumsq_partial, dim3((unsigned)np), dim3(mgk::BLK), 0, h->play->stream, z, n, h->play->partial.p);
+  hipLaunchKernelGGL(mgk::cx_sumsq_partial<C>, dim3((unsigned)np), dim3(mgk::BLK), 0, h->play->stream, z, n, h->play->partial.p);
   hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, np, h->play->scalar.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h->h_scalar, h->play->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->play->stream));
@@ -239,7 +284,8 @@ int cx_norm2(mg_hierarchy* h, const cx_t* z, long long n, double* out) {
 }
 
 // r = b - A x with the per-block partials of ||r||^2, then the sum into the pinned host scalar
-int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const cx_t* b, const cx_t* x, cx_t* r, double* out) {
+template <typename C>
+int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const C* b, const C* x, C* r, double* out) {
   CxState& S = *h->cx;
   MG_TRY(cx_spmv<mgk::RESID>(h, L.A, x, r, b, nullptr, S.partial.p));
   hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, S.partial.p, L.A.nblocks, h->play->scalar.p);
@@ -247,6 +293,18 @@ int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const cx_t* b, const cx
   HIP_TRY(hipMemcpyAsync(h->h_scalar, h->play->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->play->stream));
   HIP_TRY(spin_sync(h->play->stream));
   *out = h->h_scalar[0];
+  return MG_OK;
+}
+
+// the two conversion passes (mgk::cx_narrow / cx_widen) on h's stream
+int cx_narrow(mg_hierarchy* h, const cx_t* src, cf_t* dst, long long n) {
+  hipLaunchKernelGGL(mgk::cx_narrow, dim3(cx_grid(n)), dim3(mgk::BLK), 0, h->play->stream, src, dst, n);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+int cx_widen(mg_hierarchy* h, const cf_t* src, cx_t* dst, long long n) {
+  hipLaunchKernelGGL(mgk::cx_widen, dim3(cx_grid(n)), dim3(mgk::BLK), 0, h->play->stream, src, dst, n);
+  HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 
@@ -276,51 +334,61 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true) {
   return MG_OK;
 }
 
+// The coarsest solve of a CF32 handle stays ComplexF64 (Julia's lu of a ComplexF32 sparse matrix factorises in double,
+// MGsetup.jl:350; MGcycle.jl:177-178): bc is widened, solved by the kernels above, xc narrowed.
+int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool = true) {
+  CxState& S = *h->cx;
+  MG_TRY(cx_widen(h, b, cxp(S.cw_b), S.n_coarse));
+  MG_TRY(cx_coarse(h, cxc(S.cw_b), cxp(S.cw_x), true));
+  return cx_narrow(h, cxc(S.cw_x), x, S.n_coarse);
+}
+
 // relax (MGcycle.jl:122-136) entered with r = b - A x: numit-1 times {x += d.*r; r = b - A x}, then x += d.*r - i.e.
 // max(numit, 1) sweeps x' = x + d.*(b - A x); from x = 0 the first one is x = d.*b.  x ping-pongs between L.x[0] / L.x[1].
-int cx_relax(mg_hierarchy* h, CxLevel& L, const cx_t* b, int& xi, bool xzero, long long numit) {
+template <typename C>
+int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long long numit) {
   long long sweeps = std::max<long long>(numit, 1);
   if (xzero) {
-    hipLaunchKernelGGL(mgk::cx_dscale, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->play->stream, reinterpret_cast<const cx_t*>(L.d.p), b,
-                       cxp(L.x[xi]), L.n);
+    hipLaunchKernelGGL(mgk::cx_dscale<C>, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, cxp<C>(L.x[xi]), L.n);
     HIP_TRY(hipGetLastError());
     --sweeps;
   }
   for (long long s = 0; s < sweeps; ++s) {
-    MG_TRY(cx_spmv<mgk::SMOOTH>(h, L.A, cxp(L.x[xi]), cxp(L.x[1 - xi]), b, reinterpret_cast<const cx_t*>(L.d.p), nullptr));
+    MG_TRY(cx_spmv<mgk::SMOOTH>(h, L.A, cxc<C>(L.x[xi]), cxp<C>(L.x[1 - xi]), b, cxc<C>(L.d), nullptr));
     xi = 1 - xi;
   }
   return MG_OK;
 }
 
-// recursiveCycle (MGcycle.jl:1-118) from level l (0-based) on b; the iterate is lev[l].x[xi] (zero on entry when xzero)
-int cx_cycle(mg_hierarchy* h, int l, const cx_t* b, int& xi, bool xzero, char ctype) {
+// recursiveCycle (MGcycle.jl:1-118) from level l (0-based) on b; the iterate is lev[l].x[xi] (zero on entry when xzero).
+// C = cx_t on a CF64 handle, cf_t on a CF32 one: the same recursion on the same buffers.
+template <typename C>
+int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype) {
   CxState& S = *h->cx;
   const int nl = (int)h->nlevels;
   CxLevel& L = S.lev[(size_t)l];
-  if (l == nl - 1) return cx_coarse(h, b, cxp(L.x[xi]), xzero);                               // l.13-18
-  MG_TRY(cx_relax(h, L, b, xi, xzero, L.npre));                                         // l.26-31, 54
-  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxp(L.x[xi]), cxp(L.r), b, nullptr, nullptr));     // l.58-60
-  CxLevel& C = S.lev[(size_t)l + 1];
-  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.R, cxp(L.r), cxp(C.b), nullptr, nullptr, nullptr));   // bc = R r   (l.66)
+  if (l == nl - 1) return cx_coarse(h, b, cxp<C>(L.x[xi]), xzero);                            // l.13-18
+  MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre));                                       // l.26-31, 54
+  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxc<C>(L.x[xi]), cxp<C>(L.r), b, nullptr, nullptr));  // l.58-60
+  CxLevel& C1 = S.lev[(size_t)l + 1];
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.R, cxc<C>(L.r), cxp<C>(C1.b), nullptr, nullptr, nullptr));   // bc = R r   (l.66)
   int ci = 0;
   if (l + 1 == nl - 1) {
-    MG_TRY(cx_coarse(h, cxp(C.b), cxp(C.x[ci])));                                       // l.67-69
+    MG_TRY(cx_coarse(h, cxc<C>(C1.b), cxp<C>(C1.x[ci])));                                 // l.67-69
   } else {
-    MG_TRY(cx_cycle(h, l + 1, cxp(C.b), ci, true, ctype));                              // xc = 0 (l.63-64), l.78
-    if (ctype == 'W') MG_TRY(cx_cycle(h, l + 1, cxp(C.b), ci, false, 'W'));            // l.79-80
-    else if (ctype == 'F') MG_TRY(cx_cycle(h, l + 1, cxp(C.b), ci, false, 'V'));       // l.81-84
+    MG_TRY(cx_cycle<C>(h, l + 1, cxc<C>(C1.b), ci, true, ctype));                         // xc = 0 (l.63-64), l.78
+    if (ctype == 'W') MG_TRY(cx_cycle<C>(h, l + 1, cxc<C>(C1.b), ci, false, 'W'));        // l.79-80
+    else if (ctype == 'F') MG_TRY(cx_cycle<C>(h, l + 1, cxc<C>(C1.b), ci, false, 'V'));   // l.81-84
   }
   // x += P xc (l.90): in place, the gather reads xc only
-  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxp(C.x[ci]), cxp(L.x[xi]), nullptr, nullptr, nullptr, cx_t{1.0, 0.0}, cx_t{1.0, 0.0}));
-  return cx_relax(h, L, b, xi, false, L.npost);                                        // r = b - A x, relax (l.92-102)
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(C1.x[ci]), cxp<C>(L.x[xi]), nullptr, nullptr, nullptr, C{1, 0}, C{1, 0}));
+  return cx_relax<C>(h, L, b, xi, false, L.npost);                                      // r = b - A x, relax (l.92-102)
 }
 
-int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs) {
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want = CX_WANT64) {
+  MG_TRY(cx_handle_ok(h, want));
   if (!h->cx->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
-  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
+  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "complex handles serve one right-hand side (nrhs=%lld)", nrhs);
   if (n != h->cx->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->cx->lev[0].n);
   return MG_OK;
 }
@@ -330,19 +398,27 @@ int cx_finalize(mg_hierarchy* h) {
   CxState& S = *h->cx;
   S.finalized = false;
   const int nl = (int)h->nlevels;
-  if (h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF64 handles");
+  if (S.single && h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve is not served for CF32 handles");
+  if (S.K_auto) {   // As[1] may have changed since it was widened: the next driver call widens it again
+    S.K.release();
+    S.K_auto = false;
+  }
+  if (h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF64 / CF32 handles");
   if (h->relax_type != 0) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF64 handles");
   size_t maxblocks = 1;
   for (int l = 0; l < nl; ++l) {
     CxLevel& L = S.lev[(size_t)l];
     if (!L.A.set) return fail(MG_ERR_STATE, "As[%d] was not set", l + 1);
     if (L.A.n_rows != L.A.n_cols) return fail(MG_ERR_INVALID, "As[%d] is not square", l + 1);
+    if (L.A.single != S.single) return fail(MG_ERR_STATE, "As[%d] was set in another precision than the handle's", l + 1);
     L.n = L.A.n_rows;
     maxblocks = std::max(maxblocks, (size_t)L.A.nblocks);
     if (l < nl - 1) {
       if (!L.P.set || !L.R.set) return fail(MG_ERR_STATE, "Ps[%d]/Rs[%d] were not set", l + 1, l + 1);
       if (!L.relax_set) return fail(MG_ERR_STATE, "relaxPrecs[%d] was not set", l + 1);
-      if ((long long)L.d.n != 2 * L.n) return fail(MG_ERR_INVALID, "relaxPrecs[%d] has length %zu, expected %lld", l + 1, L.d.n / 2, L.n);
+      if (L.d.n != cx_len(S, L.n)) return fail(MG_ERR_INVALID, "relaxPrecs[%d] has length %zu, expected %lld", l + 1, L.d.n / (S.single ? 1 : 2), L.n);
+      if (L.P.single != S.single || L.R.single != S.single)
+        return fail(MG_ERR_STATE, "Ps[%d]/Rs[%d] were set in another precision than the handle's", l + 1, l + 1);
     }
   }
   for (int l = 0; l < nl - 1; ++l) {
@@ -360,7 +436,7 @@ int cx_finalize(mg_hierarchy* h) {
     return fail(MG_ERR_INVALID, "coarse solve order %lld != coarsest level size %lld", S.n_coarse, S.lev[(size_t)nl - 1].n);
   (void)hipSetDevice(h->device);
   for (auto& L : S.lev) {
-    const size_t len = 2 * (size_t)L.n;
+    const size_t len = cx_len(S, L.n);
     if (L.b.n != len) MG_TRY(L.b.alloc(len));
     if (L.r.n != len) MG_TRY(L.r.alloc(len));
     if (L.x[0].n != len) MG_TRY(L.x[0].alloc(len));
@@ -369,6 +445,11 @@ int cx_finalize(mg_hierarchy* h) {
   const size_t n0 = 2 * (size_t)S.lev[0].n;
   if (S.stage_b.n != n0) MG_TRY(S.stage_b.alloc(n0));
   if (S.partial.n < maxblocks) MG_TRY(S.partial.alloc(maxblocks));
+  if (S.single) {
+    const size_t nc = 2 * (size_t)S.n_coarse;
+    if (S.cw_b.n != nc) MG_TRY(S.cw_b.alloc(nc));
+    if (S.cw_x.n != nc) MG_TRY(S.cw_x.alloc(nc));
+  }
   if (S.coarse_lu && !S.coarse_multi && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
   S.finalized = true;
   return MG_OK;
@@ -686,6 +767,149 @@ int cx_find_op(mg_hierarchy* h, long long level, long long which, CxMat** out) {
   return MG_OK;
 }
 
+// ---- the host-pointer forms of cycle / solve / spmv, once for both precisions (ST: the host scalar, C: the device pair) ----
+inline bool host_all_zero(const float* x, long long len) {
+  for (long long i = 0; i < len; ++i)
+    if (x[i] != 0.0f) return false;
+  return true;
+}
+
+template <typename C, typename ST>
+int cx_cycle_host(mg_hierarchy* h, const ST* b, ST* x, long long n, long long nrhs, long long x_is_zero, CxWant want) {
+  MG_TRY(cx_check_ready(h, n, nrhs, want));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  CxLevel& L0 = S.lev[0];
+  bool xz = (x_is_zero == 1);
+  if (x_is_zero < 0) xz = host_all_zero(x, 2 * n);   // norm(x) > 0.0 decides (MGcycle.jl:29)
+  const size_t bytes = sizeof(C) * (size_t)n;
+  int xi = 0;
+  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
+  if (!xz) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
+  MG_TRY(cx_cycle<C>(h, 0, cxc<C>(S.stage_b), xi, xz, h->cycle));
+  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
+  return MG_OK;
+}
+
+template <typename C, typename ST>
+int cx_solve_host(mg_hierarchy* h, const ST* b, ST* x, long long n, long long nrhs, double tol, long long maxIter, long long* iters,
+                  double* resvec, CxWant want) {
+  MG_TRY(cx_check_ready(h, n, nrhs, want));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  CxLevel& L0 = S.lev[0];
+  const size_t bytes = sizeof(C) * (size_t)n;
+  const C* bd = cxc<C>(S.stage_b);
+  int xi = 0;
+  bool xz = host_all_zero(x, 2 * n);
+  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
+  double res2 = 0.0;
+  if (xz) {   // SolveFuncs.jl:14-21
+    MG_TRY(cx_norm2<C>(h, bd, n, &res2));
+  } else {
+    HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
+    MG_TRY(cx_residual_norm2<C>(h, L0, bd, cxc<C>(L0.x[xi]), cxp<C>(L0.r), &res2));
+  }
+  const double res0 = std::sqrt(res2);
+  if (resvec) resvec[0] = res0;
+  long long it = 0;
+  for (long long count = 1; count <= maxIter; ++count) {   // l.23-37
+    MG_TRY(cx_cycle<C>(h, 0, bd, xi, xz, h->cycle));
+    xz = false;
+    MG_TRY(cx_residual_norm2<C>(h, L0, bd, cxc<C>(L0.x[xi]), cxp<C>(L0.r), &res2));
+    ++it;
+    const double res = std::sqrt(res2);
+    if (resvec) resvec[count] = res;
+    if (res / res0 < tol) break;
+  }
+  if (xz) HIP_TRY(hipMemsetAsync(L0.x[xi].p, 0, bytes, h->play->stream));   // maxIter = 0 from x = 0
+  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
+  if (iters) *iters = it;
+  return MG_OK;
+}
+
+template <typename C, typename ST>
+int cx_spmv_host(mg_hierarchy* h, long long level, long long which, const ST* alpha, const ST* x, const ST* beta, ST* y, long long nrhs,
+                 CxWant want) {
+  MG_TRY(cx_level_ok(h, level, want));
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
+  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "complex handles serve one right-hand side (nrhs=%lld)", nrhs);
+  if (!alpha || !beta || !x || !y) return fail(MG_ERR_INVALID, "null argument");
+  if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
+  CxLevel& L = S.lev[(size_t)level - 1];
+  if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
+  const CxMat& M = which == MG_OP_A ? L.A : which == MG_OP_P ? L.P : L.R;
+  (void)hipSetDevice(h->device);
+  const long long nr = M.n_rows, nc = M.n_cols;
+  const C a = C{alpha[0], alpha[1]}, bt = C{beta[0], beta[1]};
+  const bool bz = bt.x == 0 && bt.y == 0;
+  DevBuf<double> dx, dy;   // (released below on every path; sized in bytes of C)
+  int rc = dx.alloc(cx_len(S, nc));
+  if (rc == MG_OK) rc = dy.alloc(cx_len(S, nr));
+  if (rc == MG_OK && hipMemcpyAsync(dx.p, x, sizeof(C) * (size_t)nc, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "upload of x failed");
+  if (rc == MG_OK && !bz && hipMemcpyAsync(dy.p, y, sizeof(C) * (size_t)nr, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "upload of y failed");
+  if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxc<C>(dx), cxp<C>(dy), nullptr, nullptr, nullptr, a, bt);
+  if (rc == MG_OK && hipMemcpyAsync(y, dy.p, sizeof(C) * (size_t)nr, hipMemcpyDeviceToHost, h->play->stream) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "download of the product failed");
+  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_spmv: stream failed");
+  dx.release();
+  dy.release();
+  return rc;
+}
+
+// As[1] of a CF32 handle widened into the Krylov operator K: the system operator of the _CFP64 drivers when none was set (the
+// Krylov product is never single).  Same pattern and row blocks (one chunk size for both precisions), values through cx_widen.
+int cx_widen_K(mg_hierarchy* h) {
+  CxState& S = *h->cx;
+  const CxMat& A = S.lev[0].A;
+  CxMat& K = S.K;
+  const hipStream_t st = h->play->stream;
+  K.release();
+  K.cplx = true;
+  K.single = false;
+  K.wide = A.wide;
+  K.n_rows = A.n_rows; K.n_cols = A.n_cols; K.nnz = A.nnz; K.nblocks = A.nblocks; K.max_row = A.max_row;
+  if (A.wide) {
+    MG_TRY(K.rowptr64.alloc(A.rowptr64.n));
+    HIP_TRY(hipMemcpyAsync(K.rowptr64.p, A.rowptr64.p, A.rowptr64.bytes(), hipMemcpyDeviceToDevice, st));
+  } else {
+    MG_TRY(K.rowptr.alloc(A.rowptr.n));
+    HIP_TRY(hipMemcpyAsync(K.rowptr.p, A.rowptr.p, A.rowptr.bytes(), hipMemcpyDeviceToDevice, st));
+  }
+  MG_TRY(K.colidx.alloc(A.colidx.n));
+  MG_TRY(K.blk_row.alloc(A.blk_row.n));
+  MG_TRY(K.val.alloc(2 * (size_t)std::max<long long>(A.nnz, 1)));
+  HIP_TRY(hipMemcpyAsync(K.colidx.p, A.colidx.p, A.colidx.bytes(), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(K.blk_row.p, A.blk_row.p, A.blk_row.bytes(), hipMemcpyDeviceToDevice, st));
+  if (A.nnz > 0) MG_TRY(cx_widen(h, reinterpret_cast<const cf_t*>(A.valf.p), cxp(K.val), A.nnz));
+  HIP_TRY(spin_sync(st));
+  K.set = true;
+  S.K_auto = true;
+  return MG_OK;
+}
+
+// mg_create_CF64 / mg_create_CF32
+int cx_create(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out, bool single) {
+  if (!out) return fail(MG_ERR_INVALID, "out is null");
+  *out = nullptr;
+  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "complex handles serve one right-hand side (nrhs=%lld)", nrhs);
+  mg_hierarchy* h = nullptr;
+  MG_TRY(mg_create(nlevels, 1, device_id, &h));
+  h->cx = new CxState();
+  h->cx->single = single;
+  h->cx->lev.resize((size_t)nlevels);
+  *out = h;
+  return MG_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -694,15 +918,10 @@ int cx_find_op(mg_hierarchy* h, long long level, long long which, CxMat** out) {
 extern "C" {
 
 int mg_create_CF64(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out) {
-  if (!out) return fail(MG_ERR_INVALID, "out is null");
-  *out = nullptr;
-  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
-  mg_hierarchy* h = nullptr;
-  MG_TRY(mg_create(nlevels, 1, device_id, &h));
-  h->cx = new CxState();
-  h->cx->lev.resize((size_t)nlevels);
-  *out = h;
-  return MG_OK;
+  return cx_create(nlevels, nrhs, device_id, out, false);
+}
+int mg_create_CF32(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out) {
+  return cx_create(nlevels, nrhs, device_id, out, true);
 }
 
 int mg_set_operator_CF64_INT64(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols,
@@ -733,9 +952,39 @@ int mg_set_relax_CF64(mg_hierarchy* h, long long level, const double* d, long lo
   return MG_OK;
 }
 
+// A of a CF32 handle from interleaved (re, im) float pairs (the reference's AT values, conjugated here once), P and R from floats
+int mg_set_operator_CF32_INT64(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols,
+                               const long long* colptr, const long long* rowval, const float* nzval) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, level, CX_WANT32));
+  if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
+  if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
+  (void)hipSetDevice(h->device);
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  MG_TRY(cx_upload(which == MG_OP_A ? &L.A : which == MG_OP_P ? &L.P : &L.R, h->opt, n_rows, n_cols, colptr, rowval, nzval, which == MG_OP_A));
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
+int mg_set_relax_CF32(mg_hierarchy* h, long long level, const float* d, long long n, long long relaxPre, long long relaxPost) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, level, CX_WANT32));
+  if (!d || n < 1) return fail(MG_ERR_INVALID, "empty relaxPrec");
+  if (relaxPre < 0 || relaxPost < 0) return fail(MG_ERR_INVALID, "negative sweep count");
+  (void)hipSetDevice(h->device);
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  MG_TRY(L.d.alloc((size_t)n));   // n float pairs
+  HIP_TRY(hipMemcpy(L.d.p, d, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  L.relax_set = true;
+  L.npre = relaxPre;
+  L.npost = relaxPost;
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
 int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double* Ainv) {
   UploadFence upload_fence;
-  MG_TRY(cx_level_ok(h, 1));
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));   // (a CF32 handle's coarsest solve stays ComplexF64)
   if (n < 1 || !Ainv) return fail(MG_ERR_INVALID, "empty coarse inverse");
   if (n > 32000) return fail(MG_ERR_UNSUPPORTED, "dense coarse inverse of order %lld is too large", n);
   (void)hipSetDevice(h->device);
@@ -761,7 +1010,7 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
                                 const long long* Uptr, const long long* Ucol, const double* Uval, const long long* p,
                                 const long long* q) {
   UploadFence upload_fence;
-  MG_TRY(cx_level_ok(h, 1));
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));
   if (n < 1 || !Lptr || !Lcol || !Lval || !Uptr || !Ucol || !Uval || !p || !q) return fail(MG_ERR_INVALID, "null or empty factor");
   if (n >= (1LL << 31) - 1 || Lptr[n] - 1 >= (1LL << 31) || Uptr[n] - 1 >= (1LL << 31))
     return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
@@ -825,91 +1074,28 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
 }
 
 int mg_cycle_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long x_is_zero) {
-  MG_TRY(cx_check_ready(h, n, nrhs));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
-  (void)hipSetDevice(h->device);
-  CxState& S = *h->cx;
-  CxLevel& L0 = S.lev[0];
-  bool xz = (x_is_zero == 1);
-  if (x_is_zero < 0) xz = host_all_zero(x, 2 * n);   // norm(x) > 0.0 decides (MGcycle.jl:29)
-  const size_t bytes = 2 * sizeof(double) * (size_t)n;
-  int xi = 0;
-  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
-  if (!xz) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
-  MG_TRY(cx_cycle(h, 0, cxp(S.stage_b), xi, xz, h->cycle));
-  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
-  HIP_TRY(spin_sync(h->play->stream));
-  return MG_OK;
+  return cx_cycle_host<cx_t>(h, b, x, n, nrhs, x_is_zero, CX_WANT64);
+}
+int mg_cycle_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long long nrhs, long long x_is_zero) {
+  return cx_cycle_host<cf_t>(h, b, x, n, nrhs, x_is_zero, CX_WANT32);
 }
 
 int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
                   long long* iters, double* resvec) {
-  MG_TRY(cx_check_ready(h, n, nrhs));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
-  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
-  (void)hipSetDevice(h->device);
-  CxState& S = *h->cx;
-  CxLevel& L0 = S.lev[0];
-  const size_t bytes = 2 * sizeof(double) * (size_t)n;
-  const cx_t* bd = cxp(S.stage_b);
-  int xi = 0;
-  bool xz = host_all_zero(x, 2 * n);
-  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
-  double res2 = 0.0;
-  if (xz) {   // SolveFuncs.jl:14-21
-    MG_TRY(cx_norm2(h, bd, n, &res2));
-  } else {
-    HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
-    MG_TRY(cx_residual_norm2(h, L0, bd, cxp(L0.x[xi]), cxp(L0.r), &res2));
-  }
-  const double res0 = std::sqrt(res2);
-  if (resvec) resvec[0] = res0;
-  long long it = 0;
-  for (long long count = 1; count <= maxIter; ++count) {   // l.23-37
-    MG_TRY(cx_cycle(h, 0, bd, xi, xz, h->cycle));
-    xz = false;
-    MG_TRY(cx_residual_norm2(h, L0, bd, cxp(L0.x[xi]), cxp(L0.r), &res2));
-    ++it;
-    const double res = std::sqrt(res2);
-    if (resvec) resvec[count] = res;
-    if (res / res0 < tol) break;
-  }
-  if (xz) HIP_TRY(hipMemsetAsync(L0.x[xi].p, 0, bytes, h->play->stream));   // maxIter = 0 from x = 0
-  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
-  HIP_TRY(spin_sync(h->play->stream));
-  if (iters) *iters = it;
-  return MG_OK;
+  return cx_solve_host<cx_t>(h, b, x, n, nrhs, tol, maxIter, iters, resvec, CX_WANT64);
+}
+int mg_solve_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long long nrhs, double tol, long long maxIter,
+                  long long* iters, double* resvec) {
+  return cx_solve_host<cf_t>(h, b, x, n, nrhs, tol, maxIter, iters, resvec, CX_WANT32);
 }
 
 int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* x, const double* beta,
                  double* y, long long nrhs) {
-  MG_TRY(cx_level_ok(h, level));
-  CxState& S = *h->cx;
-  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
-  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "CF64 handles serve one right-hand side (nrhs=%lld)", nrhs);
-  if (!alpha || !beta || !x || !y) return fail(MG_ERR_INVALID, "null argument");
-  if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
-  CxLevel& L = S.lev[(size_t)level - 1];
-  if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
-  const CxMat& M = which == MG_OP_A ? L.A : which == MG_OP_P ? L.P : L.R;
-  (void)hipSetDevice(h->device);
-  const long long nr = M.n_rows, nc = M.n_cols;
-  const cx_t a = cx_t{alpha[0], alpha[1]}, bt = cx_t{beta[0], beta[1]};
-  const bool bz = bt.x == 0.0 && bt.y == 0.0;
-  DevBuf<double> dx, dy;   // (released below on every path)
-  int rc = dx.alloc(2 * (size_t)nc);
-  if (rc == MG_OK) rc = dy.alloc(2 * (size_t)nr);
-  if (rc == MG_OK && hipMemcpyAsync(dx.p, x, 2 * sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
-    rc = fail(MG_ERR_HIP, "upload of x failed");
-  if (rc == MG_OK && !bz && hipMemcpyAsync(dy.p, y, 2 * sizeof(double) * (size_t)nr, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
-    rc = fail(MG_ERR_HIP, "upload of y failed");
-  if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxp(dx), cxp(dy), nullptr, nullptr, nullptr, a, bt);
-  if (rc == MG_OK && hipMemcpyAsync(y, dy.p, 2 * sizeof(double) * (size_t)nr, hipMemcpyDeviceToHost, h->play->stream) != hipSuccess)
-    rc = fail(MG_ERR_HIP, "download of the product failed");
-  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_spmv_CF64: stream failed");
-  dx.release();
-  dy.release();
-  return rc;
+  return cx_spmv_host<cx_t>(h, level, which, alpha, x, beta, y, nrhs, CX_WANT64);
+}
+int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float* alpha, const float* x, const float* beta, float* y,
+                 long long nrhs) {
+  return cx_spmv_host<cf_t>(h, level, which, alpha, x, beta, y, nrhs, CX_WANT32);
 }
 
 // replaceMatrixInHierarchy on the device (MGsetup.jl:226-270) for VAL = ComplexF64: new fine values on the stored pattern, then per
@@ -921,6 +1107,7 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!fine_nzval || !omega) return fail(MG_ERR_INVALID, "null argument");
   if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+  MG_CF32_UNSUPPORTED(h);   // (a CF32 hierarchy is set up again on the host and uploaded)
   CxState& S = *h->cx;
   if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
   if (nnz != S.lev[0].A.nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored fine pattern (%lld)", nnz, S.lev[0].A.nnz);
@@ -974,6 +1161,7 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
 
 // Device time of the last mg_rap_CF64, level by level (relaxPrecs[l] and As[l+1] together), in milliseconds: out[0 .. nlevels-1).
 int mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n) {
+  MG_CF32_UNSUPPORTED(h);
   MG_TRY(cx_level_ok(h, 1));
   CxState& S = *h->cx;
   if (!out || n != h->nlevels - 1) return fail(MG_ERR_INVALID, "out must hold nlevels - 1 = %lld values", h->nlevels - 1);
@@ -989,6 +1177,7 @@ int mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n) {
 int mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!out) return fail(MG_ERR_INVALID, "null argument");
+  MG_CF32_UNSUPPORTED(h);
   CxMat* M;
   MG_TRY(cx_find_op(h, level, which, &M));
   if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
@@ -1004,6 +1193,7 @@ int mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double
 int mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!out) return fail(MG_ERR_INVALID, "null argument");
+  MG_CF32_UNSUPPORTED(h);
   MG_TRY(cx_level_ok(h, level));
   CxLevel& L = h->cx->lev[(size_t)level - 1];
   if (!L.relax_set || 2 * n != (long long)L.d.n) return fail(MG_ERR_INVALID, "relaxPrecs[%lld] not set or wrong length", level);
@@ -1016,6 +1206,7 @@ int mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n
 int mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!nzval) return fail(MG_ERR_INVALID, "null argument");
+  MG_CF32_UNSUPPORTED(h);
   CxMat* M;
   MG_TRY(cx_find_op(h, level, which, &M));
   if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
@@ -1026,9 +1217,9 @@ int mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, co
 int mg_replace_krylov_values_CFP64(mg_hierarchy* h, const double* nzval, long long nnz) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!nzval) return fail(MG_ERR_INVALID, "null argument");
-  MG_TRY(cx_level_ok(h, 1));
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));
   CxState& S = *h->cx;
-  if (!S.K.set) return fail(MG_ERR_STATE, "no Krylov operator set (mg_set_krylov_operator_CFP64_INT64)");
+  if (!S.K.set || S.K_auto) return fail(MG_ERR_STATE, "no Krylov operator set (mg_set_krylov_operator_CFP64_INT64)");
   if (nnz != S.K.nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the Krylov operator's pattern (%lld)", nnz, S.K.nnz);
   (void)hipSetDevice(h->device);
   return cx_write_values(h, S.K, nzval);

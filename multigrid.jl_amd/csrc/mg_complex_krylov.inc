@@ -12,6 +12,11 @@
 //     stopping tests and the layout of resvec are theirs.  Every vector update and every scalar is one fused pass of mg_cxvec.hpp.
 //   * Host synchronisations per iteration: BiCGSTAB 4 (dot(rtld, v) ; ||s|| ; (dot(t, s), dot(t, t)) ; (||r||, the next rho)), FGMRES 1 per
 //     inner step (the chained Gram-Schmidt leaves the i + 2 scalars of a step in HBM; one readback).
+//   * On a CF32 handle the drivers are the reference's mixed branch (VAL != eltype(B), SolveFuncs.jl:52-58): the system operator, every
+//     Krylov vector, dot and scalar stay ComplexF64; only CxKry::prec changes - v is narrowed into the fine level's b, the single cycle
+//     runs from zero, and the result is widened straight into phat / Z_i (the copy-out above, so no extra pass there) or into one more
+//     work vector for BiCGSTAB's shat.  Without a Krylov operator, As[1] is widened once into K (cx_widen_K): the Krylov product is
+//     never single.
 // Also here: the stand-alone entry points of the passes (mg_cvec_*_dev_CFP64) and mg_cycle_dev_CFP64.
 namespace {
 
@@ -110,11 +115,28 @@ struct CxKry {
     return MG_OK;
   }
   // *z = M(v): one cycle from x = 0; *z is the level buffer the cycle left its result in (valid until the next cycle)
-  int prec(const cx_t* v, const cx_t** z) {
+  // On a CF32 handle (the reference's mixed closure, SolveFuncs.jl:52-58): v is narrowed into the fine level's b, the single cycle
+  // runs from zero and its result is widened into `wide`, which *z then names.
+  int prec(const cx_t* v, const cx_t** z, cx_t* wide = nullptr) {
     int xi = 0;
-    MG_TRY(cx_cycle(h, 0, v, xi, true, h->cycle));
-    *z = cxp(S.lev[0].x[xi]);
+    CxLevel& L0 = S.lev[0];
+    if (!S.single) {
+      MG_TRY(cx_cycle<cx_t>(h, 0, v, xi, true, h->cycle));
+      *z = cxp(L0.x[xi]);
+      return MG_OK;
+    }
+    if (!wide) return fail(MG_ERR_INVALID, "internal: the mixed preconditioner needs a ComplexF64 vector for its result");
+    MG_TRY(cx_narrow(h, v, cxp<cf_t>(L0.b), n));
+    MG_TRY(cx_cycle<cf_t>(h, 0, cxc<cf_t>(L0.b), xi, true, h->cycle));
+    MG_TRY(cx_widen(h, cxc<cf_t>(L0.x[xi]), wide, n));
+    *z = wide;
     return MG_OK;
+  }
+  // dst = M(v), kept: the copy-out of the double cycle's result; the widening pass itself on a CF32 handle
+  int prec_keep(const cx_t* v, cx_t* dst) {
+    const cx_t* z = nullptr;
+    MG_TRY(prec(v, &z, dst));
+    return S.single ? MG_OK : copy(dst, z);
   }
   int product(const cx_t* x, cx_t* y) { return cx_spmv<mgk::AXPBY>(h, A, x, y, nullptr, nullptr, nullptr); }
   int residual(const cx_t* b, const cx_t* x, cx_t* r) { return cx_spmv<mgk::RESID>(h, A, x, r, b, nullptr, nullptr); }
@@ -130,8 +152,9 @@ struct CxKry {
 int cx_bicgstab_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, double tol, long long maxIter, long long* iters, long long* flag_out,
                     double* resvec, long long* nres) {
   CxKry K(h);
-  MG_TRY(K.ensure(6));
+  MG_TRY(K.ensure(K.S.single ? 7 : 6));
   cx_t *r = K.vec(0), *p = K.vec(1), *v = K.vec(2), *rtld = K.vec(3), *t = K.vec(4), *phat = K.vec(5);
+  cx_t* shat = K.S.single ? K.vec(6) : nullptr;   // (CF32: the widened s_hat; CF64: read where the cycle left it)
   const double* sc = nullptr;
   long long it = 0, flag = -1;
   KrylovReport rep(iters, flag_out, resvec, nres);
@@ -161,8 +184,7 @@ int cx_bicgstab_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, double tol, long lo
       MG_TRY(K.copy(p, r));
     }
     const cx_t* z = nullptr;
-    MG_TRY(K.prec(p, &z));                                                              // p_hat = M1(p)
-    MG_TRY(K.copy(phat, z));
+    MG_TRY(K.prec_keep(p, phat));                                                       // p_hat = M1(p)
     MG_TRY(K.product(phat, v));
     MG_TRY(K.dot1(rtld, v));
     MG_TRY(K.read(2, &sc));                                                             // synchronisation 1
@@ -178,7 +200,7 @@ int cx_bicgstab_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, double tol, long lo
       flag = -3;
       break;
     }
-    MG_TRY(K.prec(r, &z));                                                              // s_hat = M1(s), read where the cycle left it
+    MG_TRY(K.prec(r, &z, shat));                                                            // s_hat = M1(s), read where the cycle left it
     MG_TRY(K.product(z, t));
     MG_TRY(K.pass(mgcv::OpCBicgTS{t, r}, {t, r}));
     MG_TRY(K.read(3, &sc));                                                             // synchronisation 3
@@ -236,9 +258,7 @@ struct CxFgmres {
     cx_t* vi = V + (size_t)i * n;
     cx_t* zi = Z + (size_t)i * n;
     cx_t* w = V + (size_t)(i + 1) * n;
-    const cx_t* z = nullptr;
-    MG_TRY(K.prec(vi, &z));                                                         // z = M(V[:,i])
-    MG_TRY(K.copy(zi, z));
+    MG_TRY(K.prec_keep(vi, zi));                                                    // z = M(V[:,i])
     MG_TRY(K.product(zi, w));                                                       // w = A z
     // modified Gram-Schmidt as one chain on the device: h_k = dot(V_k, w) stays in HBM, the update w -= h_k V_k reads it there and
     // leaves the partials of the next dot (or of ||w||^2) in the same pass; the i + 2 scalars come back in ONE readback
@@ -277,11 +297,12 @@ int cx_fgmres_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, long long inner, doub
 // the checks every driver entry point shares; host form: b, x staged through the handle's device buffers
 template <class F>
 int cx_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long maxIter, bool device_form, F&& run) {
-  MG_TRY(cx_check_ready(h, n, 1));
+  MG_TRY(cx_check_ready(h, n, 1, CX_ANY));
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
   (void)hipSetDevice(h->device);
   CxState& S = *h->cx;
+  if (S.single && !S.K.set) MG_TRY(cx_widen_K(h));   // the Krylov product is never single
   if (device_form) {
     MG_TRY(cxv_aligned({b, x}));
     return run(ccx(b), mcx(x));
@@ -306,10 +327,11 @@ extern "C" {
 int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long long* colptr, const long long* rowval,
                                        const double* nzval) {
   UploadFence upload_fence;
-  MG_TRY(cx_level_ok(h, 1));
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));
   CxState& S = *h->cx;
   (void)hipSetDevice(h->device);
   HIP_TRY(spin_sync(h->play->stream));
+  S.K_auto = false;   // (a widened As[1] is replaced or dropped below)
   if (!colptr) {   // back to As[1]; also on a handle that is not finalized (the way out when mg_finalize refuses a stale operator)
     S.K.release();
     return MG_OK;
@@ -320,7 +342,7 @@ int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long 
 }
 
 int mg_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long x_is_zero) {
-  MG_TRY(cx_check_ready(h, n, 1));
+  MG_TRY(cx_check_ready(h, n, 1, CX_ANY));
   if (!b_dev || !x_dev) return fail(MG_ERR_INVALID, "null vector");
   if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for device vectors");
   MG_TRY(cxv_aligned({b_dev, x_dev}));
@@ -328,8 +350,14 @@ int mg_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long
   CxLevel& L0 = h->cx->lev[0];
   const size_t bytes = 2 * sizeof(double) * (size_t)n;
   int xi = 0;
+  if (h->cx->single) {   // the reference's mixed closure: bl .= b; recursiveCycle from z = 0; z2 .= z (SolveFuncs.jl:52-58)
+    if (!x_is_zero) return fail(MG_ERR_UNSUPPORTED, "mg_cycle_dev_CFP64 on a CF32 handle starts from zero (x_is_zero = 1): the mixed closure always zeroes z");
+    MG_TRY(cx_narrow(h, ccx(b_dev), cxp<cf_t>(L0.b), n));
+    MG_TRY(cx_cycle<cf_t>(h, 0, cxc<cf_t>(L0.b), xi, true, h->cycle));
+    return cx_widen(h, cxc<cf_t>(L0.x[xi]), mcx(x_dev), n);
+  }
   if (!x_is_zero) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x_dev, bytes, hipMemcpyDeviceToDevice, h->play->stream));
-  MG_TRY(cx_cycle(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle));
+  MG_TRY(cx_cycle<cx_t>(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle));
   HIP_TRY(hipMemcpyAsync(x_dev, L0.x[xi].p, bytes, hipMemcpyDeviceToDevice, h->play->stream));
   return MG_OK;
 }

@@ -575,6 +575,7 @@ int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* d) {
   if (d->cx != (h->cx != nullptr))
     return fail(MG_ERR_STATE, "mg_set_coarse_dd: a sweep handle of %s values on a hierarchy of %s values", d->cx ? "ComplexF64" : "Float64",
                 h->cx ? "ComplexF64" : "Float64");
+  if (h->cx && h->cx->single) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve is not served for CF32 handles");
   if (!d->finalized) return fail(MG_ERR_STATE, "mg_set_coarse_dd before mg_dd_finalize");
   if (d->owner && d->owner != h) return fail(MG_ERR_STATE, "the sweep handle is the coarsest solve of another hierarchy");
   if (d->device != h->device) return fail(MG_ERR_INVALID, "the sweep handle lives on device %d, the hierarchy on device %d", d->device, h->device);

@@ -30,6 +30,7 @@ KERNEL_NAMES = ["spmv", "residual", "smooth", "restrict", "prolong", "dscale", "
 
 _ll = C.c_longlong
 _dp = C.POINTER(C.c_double)
+_fp = C.POINTER(C.c_float)
 _lp = C.POINTER(C.c_longlong)
 _vp = C.c_void_p
 
@@ -217,6 +218,12 @@ SIGNATURES = {
     "mg_fgmres_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_fgmres_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_cycle_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_create_CF32": (C.c_int, [_ll, _ll, _ll, C.POINTER(_vp)]),
+    "mg_set_operator_CF32_INT64": (C.c_int, [_vp, _ll, _ll, _ll, _ll, _lp, _lp, _fp]),
+    "mg_set_relax_CF32": (C.c_int, [_vp, _ll, _fp, _ll, _ll, _ll]),
+    "mg_cycle_CF32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, _ll]),
+    "mg_solve_CF32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
+    "mg_spmv_CF32": (C.c_int, [_vp, _ll, _ll, _fp, _fp, _fp, _fp, _ll]),
     "mg_cvec_dots_dev_CFP64": (C.c_int, [_ll, C.POINTER(_vp), C.POINTER(_vp), _ll, _vp, _vp, _vp]),
     "mg_cvec_scale_dev_CFP64": (C.c_int, [_dp, _vp, _vp, _ll, _vp]),
     "mg_cvec_bicg_p_dev_CFP64": (C.c_int, [_dp, _dp, _vp, _vp, _vp, _ll, _vp]),
@@ -330,11 +337,15 @@ def _vanka_guard(param, nrhs: int):
 class DeviceHierarchy:
     """Owns one ``mg_hierarchy`` handle (HBM copy of As/Ps/Rs/relaxPrecs + coarse inverse).
 
-    Dtype-aware: a param with VAL = ComplexF64 gets a ComplexDeviceHierarchy (the _CF64 entry points)."""
+    Dtype-aware: a param with VAL = ComplexF64 gets a ComplexDeviceHierarchy (the _CF64 entry points), one with VAL = ComplexF32
+    (singlePrecision=True) a ComplexSingleDeviceHierarchy (the _CF32 entry points)."""
 
     def __new__(cls, param=None, *args, **kwargs):
-        if cls is DeviceHierarchy and param is not None and np.dtype(getattr(param, "VAL", np.float64)) == np.complex128:
+        val = np.dtype(getattr(param, "VAL", np.float64)) if param is not None else None
+        if cls is DeviceHierarchy and val == np.complex128:
             cls = ComplexDeviceHierarchy
+        elif cls is DeviceHierarchy and val == np.complex64:
+            cls = ComplexSingleDeviceHierarchy
         return super().__new__(cls)
 
     def __init__(self, param, device_id: int = 0, nrhs: Optional[int] = None, options: Optional[dict] = None):
@@ -477,6 +488,8 @@ class DeviceHierarchy:
             if self.nrhs != 1:
                 raise NotImplementedError("a DomainDecompositionParam as coarsest solver serves one right-hand side "
                                           "(the reference's sweep indexes b[Idxs])")
+            if np.dtype(param.VAL) == np.complex64:
+                raise NotImplementedError("a Schwarz coarsest solve is not served for ComplexF32 hierarchies")
             if np.dtype(LU.VAL) != np.dtype(param.VAL):
                 raise TypeError("param.LU holds %s values, the hierarchy %s" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
             h = DD._device_handle(LU, param.As[-1])
@@ -488,9 +501,10 @@ class DeviceHierarchy:
         if isinstance(LU, PJS.parallelJuliaSolver):
             if LU.L is None:
                 raise MGDeviceError("param.LU is a parallelJuliaSolver without factors: run MGsetup / SA_AMGsetup first")
-            if np.dtype(LU.VAL) != np.dtype(param.VAL):
+            from .mgdef import factor_val
+            if np.dtype(LU.VAL) != factor_val(param):
                 raise TypeError("param.LU holds %s factors, the hierarchy %s values" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
-            VAL = np.dtype(param.VAL)
+            VAL = factor_val(param)                # (ComplexF32 hierarchies keep ComplexF64 factors)
             a64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
             L, U = LU.L, LU.U
             Lp, Lc, Lv = a64(L.indptr) + 1, a64(L.indices) + 1, np.ascontiguousarray(L.data, dtype=VAL)
@@ -902,6 +916,13 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
     conjugates back.  P and R are real."""
 
+    _cdtype = np.complex128       # what As, relaxPrecs and the vectors of cycle / solve / spmv hold
+    _rdtype = np.float64          # what Ps / Rs hold
+    _sfx = "CF64"                 # the entry points of create / set_operator / set_relax / cycle / solve / spmv
+
+    def _fn(self, stem):
+        return getattr(self.lib, f"mg_{stem}_{self._sfx}")
+
     def __init__(self, param, device_id: int = 0, nrhs: Optional[int] = None, options: Optional[dict] = None):
         self.lib = load_library()
         self.handle = _vp()
@@ -912,7 +933,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             raise NotImplementedError("ComplexF64 hierarchies serve one right-hand side on the device")
         self._op_nnz = {}
         lib = self.lib
-        _check(lib, lib.mg_create_CF64(self.nlevels, 1, int(device_id), C.byref(self.handle)), "mg_create_CF64")
+        _check(lib, self._fn("create")(self.nlevels, 1, int(device_id), C.byref(self.handle)), f"mg_create_{self._sfx}")
         try:
             for key, val in (options or {}).items():
                 _check(lib, lib.mg_set_option(self.handle, key.encode(), float(val)), f"mg_set_option({key})")
@@ -999,9 +1020,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         _check(self.lib, self.lib.mg_set_nrhs(self.handle, 1), "mg_set_nrhs")
 
     @staticmethod
-    def _host_block(a, writable=False):
-        if not isinstance(a, np.ndarray) or a.dtype != np.complex128:
-            raise TypeError("expected a complex128 numpy array for a ComplexF64 hierarchy")
+    def _host_block(a, writable=False, dtype=np.complex128):
+        if not isinstance(a, np.ndarray) or a.dtype != dtype:
+            raise TypeError(f"expected a {np.dtype(dtype)} numpy array here")
         if a.ndim == 2 and a.shape[1] != 1:
             raise NotImplementedError("ComplexF64 hierarchies serve one right-hand side on the device")
         if not a.flags.c_contiguous and not a.flags.f_contiguous:
@@ -1010,28 +1031,33 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             raise ValueError("x must be writable (it is updated in place)")
         return a
 
+    def _vp_of(self, a):
+        """The vector's address in the handle's own precision (complex128 -> double*, complex64 -> float*)."""
+        return a.ctypes.data_as(_dp if self._cdtype == np.complex128 else _fp)
+
     def cycle(self, b, x, x_is_zero: int = -1):
-        b = self._host_block(b)
-        x = self._host_block(x, True)
-        _check(self.lib, self.lib.mg_cycle_CF64(self.handle, _c128(b), _c128(x), b.shape[0], 1, int(x_is_zero)), "mg_cycle_CF64")
+        b = self._host_block(b, dtype=self._cdtype)
+        x = self._host_block(x, True, dtype=self._cdtype)
+        _check(self.lib, self._fn("cycle")(self.handle, self._vp_of(b), self._vp_of(x), b.shape[0], 1, int(x_is_zero)),
+               f"mg_cycle_{self._sfx}")
         return x
 
     def solve(self, b, x, tol: float, maxIter: int):
-        b = self._host_block(b)
-        x = self._host_block(x, True)
+        b = self._host_block(b, dtype=self._cdtype)
+        x = self._host_block(x, True, dtype=self._cdtype)
         iters = C.c_longlong(0)
         resvec = np.zeros(int(maxIter) + 1)
-        _check(self.lib, self.lib.mg_solve_CF64(self.handle, _c128(b), _c128(x), b.shape[0], 1, float(tol), int(maxIter),
-                                                C.byref(iters), _f64(resvec)), "mg_solve_CF64")
+        _check(self.lib, self._fn("solve")(self.handle, self._vp_of(b), self._vp_of(x), b.shape[0], 1, float(tol), int(maxIter),
+                                           C.byref(iters), _f64(resvec)), f"mg_solve_{self._sfx}")
         return x, int(iters.value), resvec[: iters.value + 1]
 
     def spmv(self, level: int, which: int, alpha, x, beta, y):
-        x = self._host_block(x)
-        y = self._host_block(y, True)
-        a = np.array([complex(alpha).real, complex(alpha).imag])
-        bt = np.array([complex(beta).real, complex(beta).imag])
-        _check(self.lib, self.lib.mg_spmv_CF64(self.handle, int(level), int(which), _f64(a), _c128(x), _f64(bt), _c128(y), 1),
-               "mg_spmv_CF64")
+        x = self._host_block(x, dtype=self._cdtype)
+        y = self._host_block(y, True, dtype=self._cdtype)
+        a = np.array([complex(alpha).real, complex(alpha).imag], dtype=self._rdtype)
+        bt = np.array([complex(beta).real, complex(beta).imag], dtype=self._rdtype)
+        _check(self.lib, self._fn("spmv")(self.handle, int(level), int(which), self._vp_of(a), self._vp_of(x), self._vp_of(bt),
+                                          self._vp_of(y), 1), f"mg_spmv_{self._sfx}")
         return y
 
     # -- the ComplexF64 Krylov drivers (mg_*_CFP64): BiCGSTAB / FGMRES on a system operator of their own ------------------------
@@ -1105,7 +1131,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             if hasattr(t, "dtype") and hasattr(t, "data_ptr"):
                 import torch
                 if t.dtype != torch.complex128:
-                    raise TypeError("expected torch.complex128 tensors for a ComplexF64 hierarchy")
+                    raise TypeError("expected torch.complex128 tensors (the Krylov vectors of a ComplexF32 hierarchy are ComplexF64 too)")
         _sync_torch(b, x)
         return _ptr(b), _ptr(x)
 
@@ -1202,6 +1228,47 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     pcg = cycle_mixed_f32 = pcg_dev = block_pcg_dev = block_bicgstab_dev = block_fgmres_dev = _refuse
     solve_dev = spmv_dev = fused_dev = sweep_residual_dev = four_stage_dev = _refuse
     transpose_hierarchy = cycle_async_dev = _refuse
+
+
+class ComplexSingleDeviceHierarchy(ComplexDeviceHierarchy):
+    """A ComplexF32 hierarchy on the device (mg_create_CF32; ``getMGparam(np.complex128, ..., singlePrecision=True)``): As and
+    relaxPrecs complex64, Ps / Rs float32, the cycle in single precision by the same kernels; the coarsest solve stays
+    ComplexF64.  ``cycle``, ``solve``, ``spmv`` take complex64 arrays.  ``bicgstab``, ``fgmres``, their ``_dev`` forms,
+    ``cycle_dev``, ``set_krylov_operator`` and ``update_krylov_operator`` take complex128 arrays and tensors: the Krylov method
+    runs in ComplexF64 and is preconditioned by the single cycle (narrowed in, widened out; SolveFuncs.jl:52-58)."""
+
+    _cdtype = np.complex64
+    _rdtype = np.float32
+    _sfx = "CF32"
+
+    def _set_op(self, level, which, M):
+        self._op_nnz[(int(level), int(which))] = int(M.nnz)
+        colptr = np.ascontiguousarray(M.indptr, dtype=np.int64) + 1
+        rowval = np.ascontiguousarray(M.indices, dtype=np.int64) + 1
+        if which == MG_OP_A:
+            if M.dtype != np.complex64:
+                raise TypeError("As of a ComplexF32 hierarchy are complex64")
+            nzval = np.ascontiguousarray(np.conj(M.data), dtype=np.complex64)     # the reference's AT values
+        else:
+            if M.dtype != np.float32:
+                raise TypeError("Ps and Rs of a ComplexF32 hierarchy are float32")
+            nzval = np.ascontiguousarray(M.data, dtype=np.float32)
+        rc = self.lib.mg_set_operator_CF32_INT64(self.handle, level, which, M.shape[0], M.shape[1], _i64(colptr), _i64(rowval),
+                                                 nzval.ctypes.data_as(_fp))
+        _check(self.lib, rc, f"mg_set_operator_CF32(level={level}, which={which})")
+
+    def _set_relax(self, level, d, pre, post):
+        if np.asarray(d).dtype != np.complex64:
+            raise TypeError("relaxPrecs of a ComplexF32 hierarchy are complex64")
+        d = np.ascontiguousarray(d, dtype=np.complex64)
+        _check(self.lib, self.lib.mg_set_relax_CF32(self.handle, level, d.ctypes.data_as(_fp), d.size, int(pre), int(post)),
+               f"mg_set_relax_CF32(level={level})")
+
+    def _refuse_single(self, *args, **kwargs):
+        raise NotImplementedError("ComplexF32 hierarchies: replace_matrix, replace_values, get_values and rap_level_ms on the device are "
+                                  "out of scope (replaceMatrixInHierarchy recomputes on the host and uploads again)")
+
+    replace_matrix = replace_values = get_values = rap_level_ms = _refuse_single
 
 
 def complex_lu_arrays(lu):

@@ -57,15 +57,23 @@ class MGparam:
 def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, relativeTol=1e-6,
                relaxType="SPAI", relaxParam=1.0, relaxPre=2, relaxPost=2, cycleType="V",
                coarseSolveType="NoMUMPS", strongConnParam=0.4, FilteringParam=0.0,
-               transferOperatorType="FullWeighting") -> MGparam:
+               transferOperatorType="FullWeighting", *, singlePrecision: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
     ``VAL`` is ``Float64`` or ``ComplexF64`` (np.complex128: the _CF64 entry points, single GPU, V/W/F cycles, Jac/SPAI);
-    every other value type is refused.
+    every other value type is refused.  ``singlePrecision=True`` (keyword only) with ``np.complex128`` gives the reference's
+    VAL = ComplexF32 hierarchy (``param.VAL = np.complex64``, ``param.singlePrecision = True``, MGdef.jl:151): operators,
+    relaxPrecs and cycle in single precision (the _CF32 entry points), coarsest factorisation in double, and the ComplexF64
+    Krylov drivers preconditioned by the single cycle (the mixed branch of getMultigridPreconditioner).
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
-        raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path")
+        raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
+                        "hierarchy is getMGparam(np.complex128, ..., singlePrecision=True)")
+    if singlePrecision and np.dtype(VAL) != np.complex128:
+        raise NotImplementedError("singlePrecision=True serves VAL=ComplexF64 (Float32 real hierarchies are out of scope)")
+    if singlePrecision:
+        VAL = np.complex64
     if np.dtype(IND) != np.int64:
         raise TypeError("only IND=Int64 is supported")
     pre = relaxPre if callable(relaxPre) else (lambda level, _k=int(relaxPre): _k)
@@ -76,12 +84,23 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    relativeTol=float(relativeTol), relaxType=str(relaxType), relaxParam=relaxParam,
                    relaxPre=pre, relaxPost=post, cycleType=cycleType, coarseSolveType=str(coarseSolveType),
                    strongConnParam=float(strongConnParam), FilteringParam=float(FilteringParam),
-                   transferOperatorType=str(transferOperatorType), VAL=np.dtype(VAL).type, IND=np.int64)
+                   transferOperatorType=str(transferOperatorType), singlePrecision=bool(singlePrecision),
+                   VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
-    """VAL = ComplexF64: the hierarchy is served by the _CF64 entry points."""
-    return np.dtype(param.VAL) == np.complex128
+    """VAL = ComplexF64 or ComplexF32: the hierarchy is served by the _CF64 / _CF32 entry points."""
+    return np.dtype(param.VAL) in (np.dtype(np.complex128), np.dtype(np.complex64))
+
+
+def is_single(param: MGparam) -> bool:
+    """VAL = ComplexF32 (getMGparam(np.complex128, ..., singlePrecision=True)): the _CF32 entry points."""
+    return np.dtype(param.VAL) == np.complex64
+
+
+def factor_val(param: MGparam):
+    """The value type of the coarsest factorisation: Julia's lu of a ComplexF32 matrix factorises in double (MGsetup.jl:350)."""
+    return np.dtype(np.complex128) if is_single(param) else np.dtype(param.VAL)
 
 
 def hierarchyExists(param: MGparam) -> bool:
@@ -134,9 +153,10 @@ def clear_(param: MGparam) -> None:
 def copySolver(MG: MGparam) -> MGparam:
     """Copies the solver parameters without the setup and allocated memory (MGdef.jl:138-145); a solver-object ``LU`` is
     copied by its own ``copySolver`` (l.141-143), a plain factorisation is not."""
-    new = getMGparam(MG.VAL, MG.IND, MG.levels, MG.numCores, MG.maxOuterIter, MG.relativeTol, MG.relaxType,
-                     MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
-                     MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType)
+    single = is_single(MG)
+    new = getMGparam(np.complex128 if single else MG.VAL, MG.IND, MG.levels, MG.numCores, MG.maxOuterIter, MG.relativeTol,
+                     MG.relaxType, MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
+                     MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single)
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

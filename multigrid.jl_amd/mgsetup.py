@@ -15,7 +15,7 @@ import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-from .mgdef import MGparam, destroyCoarsestLU, _release_device, is_complex
+from .mgdef import MGparam, destroyCoarsestLU, _release_device, factor_val, is_complex, is_single
 from .transfer_operators import getFWInterp
 
 
@@ -36,7 +36,10 @@ def getMultilevelOperatorConstructor(param, getOperator, restrictParams):
 
 
 def _as_csr(A):
-    A = sp.csr_matrix(A, dtype=np.complex128 if np.iscomplexobj(A.data if sp.issparse(A) else A) else np.float64)
+    dt = np.dtype(A.dtype)
+    if dt != np.complex64:                                           # (a ComplexF32 hierarchy keeps its single operators)
+        dt = np.complex128 if np.iscomplexobj(A.data if sp.issparse(A) else A) else np.float64
+    A = sp.csr_matrix(A, dtype=dt)
     A.sort_indices()
     return A
 
@@ -78,10 +81,15 @@ def getRelaxPrec(A, relaxType: str, relaxParam=1.0, Mesh_l=None, withCellsBlock:
         raise NotImplementedError("RelaxHybridVanka / getHybridVankaFaces are out of scope (the cycle's call is commented out in the reference)")
     if np.iscomplexobj(A.data if sp.issparse(A) else A):
         A = _as_csr(A)
+        # A complex64 operator (a ComplexF32 hierarchy, whose As are converted first: MGsetup.jl:31-33) gives complex64 relaxPrecs:
+        # the formulas are evaluated in double on the single values and the result is converted once, as the reference's
+        # convert(Array{VAL}, conj(relaxParam ./ diag(AT))) does with its Float64 relaxParam (MGsetup.jl:145-149).
+        cdt = np.complex64 if A.dtype == np.complex64 else np.complex128
+        A = A.astype(np.complex128)
         if relaxType in ("Jac", "Jac-GMRES"):
-            return np.ascontiguousarray(float(relaxParam) / A.diagonal(), dtype=np.complex128)
+            return np.ascontiguousarray(float(relaxParam) / A.diagonal(), dtype=cdt)
         if relaxType == "SPAI":
-            return np.ascontiguousarray(float(relaxParam) * getSPAIprec(A), dtype=np.complex128)
+            return np.ascontiguousarray(float(relaxParam) * getSPAIprec(A), dtype=cdt)
         raise ValueError("Unknown relaxation type !!!!")
     if relaxType in ("Jac", "Jac-GMRES"):
         return np.ascontiguousarray(float(relaxParam) / _as_csr(A).diagonal(), dtype=np.float64)
@@ -110,7 +118,7 @@ def galerkin(R, A, P):
     The reference's serial Julia SpGEMM is the bulk of its setup time; here it is row-parallel on the host
     (csrc/mg_host.cpp) - still CPU, still before the device ever sees the hierarchy."""
     if np.iscomplexobj(A.data):    # complex VAL: scipy's SpGEMM (real P, R; host setup speed is not a goal here)
-        Ac = (R @ (A @ P)).tocsr()
+        Ac = (R @ (A @ P)).tocsr()   # (complex64 A with float32 P, R: the product is formed and kept in single, MGsetup.jl:108-110)
         Ac.sort_indices()
         return Ac
     from .hostlib import galerkin_dense_gpu, galerkin_dense_gpu_ok, galerkin_sparse_gpu, galerkin_sparse_gpu_ok, spgemm
@@ -136,6 +144,8 @@ def defineCoarsestAinv(param: MGparam, Ac) -> None:
         LU = param.LU
         if not param.Meshes:
             raise ValueError("a DomainDecompositionParam as coarsest solver needs the coarsest mesh: the hierarchy has none (SA-AMG)")
+        if is_single(param):
+            raise NotImplementedError("a Schwarz coarsest solve is not served for ComplexF32 hierarchies (singlePrecision=True)")
         if np.dtype(LU.VAL) != np.dtype(param.VAL):
             raise TypeError("param.LU is a DomainDecompositionParam of %s, the hierarchy of %s" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
         LU.Mesh = param.Meshes[-1]
@@ -143,9 +153,9 @@ def defineCoarsestAinv(param: MGparam, Ac) -> None:
         return
     if kind == "pjs":                             # setupSolver(sparse(AT'), LU)
         from .parallel_julia_solver import setupLUFactor
-        if np.dtype(param.LU.VAL) != np.dtype(param.VAL):
+        if np.dtype(param.LU.VAL) != factor_val(param):
             raise TypeError("param.LU is a parallelJuliaSolver of %s, the hierarchy of %s" % (np.dtype(param.LU.VAL), np.dtype(param.VAL)))
-        setupLUFactor(_as_csr(Ac), param.LU, upload=False)
+        setupLUFactor(_as_csr(Ac).astype(factor_val(param)), param.LU, upload=False)
         return
     if param.coarseSolveType == "MUMPS":
         raise NotImplementedError("MUMPS coarse solve is dead code in the reference (Multigrid.jl:29-40)")
@@ -157,7 +167,8 @@ def defineCoarsestAinv(param: MGparam, Ac) -> None:
         Acs = _as_csr(Ac)
         param.LU = np.ascontiguousarray(float(param.relaxParam) / Acs.diagonal(), dtype=Acs.dtype)
         return
-    param.LU = coarse_lu(Ac)
+    # (a ComplexF32 hierarchy factorises its single coarsest operator in double: UMFPACK has no single form, MGsetup.jl:350)
+    param.LU = coarse_lu(sp.csr_matrix(Ac).astype(np.complex128) if is_single(param) else Ac)
 
 
 def coarse_lu(Ac):
@@ -171,8 +182,10 @@ def _of_val(param: MGparam, A):
     """The operator in param.VAL: a complex hierarchy holds every A as complex128 (a real fine operator included); a complex
     operator needs VAL = ComplexF64."""
     A = _as_csr(A)
+    if is_single(param):               # MGsetup.jl:31-33: As converted to VAL
+        return A.astype(np.complex64)
     if is_complex(param):
-        return A.astype(np.complex128) if not np.iscomplexobj(A.data) else A
+        return A.astype(np.complex128)
     if np.iscomplexobj(A.data):
         raise TypeError("complex operator with VAL=Float64: use getMGparam(VAL=np.complex128)")
     return A
@@ -226,6 +239,8 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
             nc = nc_nodes - 1
             R = (P.T * (0.5 ** Meshes[l - 1].dim)).tocsr()      # RT = P*0.5^dim always (MGsetup.jl:56-60)
         R.sort_indices()
+        if is_single(param):                                    # Ps / Rs in real(VAL) (MGsetup.jl:79-82)
+            P, R = P.astype(np.float32), R.astype(np.float32)
         relaxPrecs.append(getRelaxPrec(A, param.relaxType, relaxParamArr[l - 1], Meshes[l - 1], withCellsBlock))
         if P.shape[0] == P.shape[1]:
             if verbose:
@@ -280,7 +295,8 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
     """New fine matrix, same P/R: recompute relaxPrecs, Galerkin products and the coarse LU (MGsetup.jl:226-270)."""
     relaxParamArr = _relax_param_arr(param)
     A = _of_val(param, A)
-    on_device = param.device is not None and param.relaxType in ("Jac", "Jac-GMRES", "SPAI")
+    # (a ComplexF32 hierarchy is recomputed on the host and uploaded again: its device re-setup is out of scope)
+    on_device = param.device is not None and param.relaxType in ("Jac", "Jac-GMRES", "SPAI") and not is_single(param)
     if on_device and is_complex(param):
         # (mg_rap_CF64.  A Schwarz coarsest solver borrows a device handle of its own, set up on the coarsest matrix: host path)
         from .mgdef import _solver_object
@@ -312,7 +328,7 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
 def transposeHierarchy(param: MGparam, verbose: bool = False) -> None:
     """Transpose every operator, swap P<->R roles (MGsetup.jl:274-318).  Real VAL: conj is a no-op."""
     if is_complex(param):
-        raise NotImplementedError("transposeHierarchy of a ComplexF64 hierarchy (the device transpose serves FP64 handles)")
+        raise NotImplementedError("transposeHierarchy of a ComplexF64 / ComplexF32 hierarchy (the device transpose serves FP64 handles)")
     if _is_vanka(param):
         raise NotImplementedError("transposeHierarchy of a Vanka hierarchy (the reference refuses it too: MGsetup.jl:288-292)")
     if param.relaxType not in ("Jac", "Jac-GMRES", "SPAI"):

@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from .device import DeviceHierarchy, MG_OP_A, MG_OP_P, MG_OP_R
-from .mgdef import MGparam, hierarchyExists, is_complex
+from .mgdef import MGparam, hierarchyExists, is_complex, is_single
 from .mgsetup import adjustMemoryForNumRHS
 
 
@@ -73,6 +73,24 @@ def getMultigridPreconditioner(param: MGparam, B: np.ndarray, verbose: bool = Fa
             return z2
 
         return MMG32
+    if is_single(param):
+        # ComplexF32 hierarchy.  complex128 B: the mixed branch VAL != eltype(B) (SolveFuncs.jl:52-58) - bl .= b; the single cycle
+        # from zero; z2 .= z - so the closure preconditions a ComplexF64 Krylov method.  complex64 B: the plain closure below.
+        if B.dtype == np.complex128:
+            bl = np.zeros(B.shape, dtype=np.complex64, order="F")
+            zl = np.zeros_like(bl)
+            z2 = np.zeros_like(B, order="F")
+
+            def MMGmixed(b):
+                bl[...] = b
+                zl[...] = 0.0
+                dev.cycle(bl, zl, 1)
+                z2[...] = zl
+                return z2
+
+            return MMGmixed
+        if B.dtype != np.complex64:
+            raise TypeError("getMultigridPreconditioner of a ComplexF32 hierarchy takes a complex128 (mixed) or complex64 B")
     z = np.zeros_like(B, order="F")
 
     def MMG(b):

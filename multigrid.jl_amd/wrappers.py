@@ -86,7 +86,8 @@ def solveLinearSystem_(A, B: np.ndarray, X: np.ndarray, param: MGsolver, doTrans
         param.timeSetup += time.perf_counter() - t0
     t0 = time.perf_counter()
     Bf = np.asfortranarray(B)
-    cplx = is_complex(param.MG)          # ComplexF64: the device drivers of their own, on the hierarchy's fine level
+    cplx = is_complex(param.MG)          # ComplexF64 / ComplexF32: the device drivers of their own, on the hierarchy's fine level
+    #                                      (ComplexF32: the Krylov method in double on As[1] widened, the single cycle as M)
     if param.Krylov == "BiCGSTAB" and cplx:
         _, _, num_iter, _ = solveBiCGSTAB_MG_CFP64(param.MG.As[0], param.MG, Bf, Xv, verbose)
     elif param.Krylov == "GMRES" and cplx and param.kind != "SA":
