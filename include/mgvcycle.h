@@ -799,8 +799,10 @@ int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count);
  *   called with a CF64 handle fails with MG_ERR_STATE, and every CF64 entry point called with an FP64 handle fails with
  *   MG_ERR_STATE too; nothing is changed.
  * Refused with MG_ERR_UNSUPPORTED (and a mg_last_error message): cycle 'K', relaxType 1 (Jac-GMRES), the GMRES coarse solve
- *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries), the _FP64 Krylov drivers
- *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64 (mg_rap_CF64 serves them), mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
+ *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries: a complex handle's own
+ *   nrhs stays 1, and blocks of right-hand sides go through the mg_block_*_CF64 / _CFP64 entry points at the end of this header, which
+ *   take nrhs with each call), the _FP64 Krylov drivers
+ *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*_FP64; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64 (mg_rap_CF64 serves them), mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
  *   mg_ghost_* call and mg_dist_set_tail_INT64 with a CF64 tail (the mg_dist_* handles are FP64 by construction).
  * Formats.  Generic CSR only, one streaming kernel (int32 row pointers; 64-bit beyond 2^31 - 4096 non-zeros or with the option
  *   "force_rowptr64"); the row-class, band, tile, march and small-level formats are real-valued and not used.  No HIP graphs. */
@@ -880,7 +882,8 @@ mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long whi
  * for FGMRES, 6 for BiCGSTAB) is allocated at the first call and released with the handle.  Host synchronisations per
  * iteration: BiCGSTAB 4, FGMRES 1 per inner step.  Refused: an FP64 handle or a handle not finalized (MG_ERR_STATE); a null
  * vector, maxIter < 0, a wrong n, inner outside [1,64], a device vector off a 16-byte boundary (MG_ERR_INVALID).  Not served
- * for complex values: PCG (the operators in question are not Hermitian positive definite), blocks of right-hand sides. */
+ * for complex values: PCG (the operators in question are not Hermitian positive definite).  These entry points take one right-hand
+ * side; a block of them goes to mg_block_bicgstab[_dev]_CFP64 (at the end of this header; block FGMRES is not served). */
 int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long long* colptr, const long long* rowval,
                                        const double* nzval);
 /* New values (nnz complex, the AT convention) on the pattern of the Krylov operator set last: a copy and one conjugation in HBM,
@@ -948,7 +951,8 @@ int mg_cvec_gs_update_dev_CFP64(long long m, const double* h_host, const double*
  * mg_solve_CF64 / mg_spmv_CF64 / mg_set_operator_FP64_INT64 on a CF32 handle: MG_ERR_STATE.  Not served for a CF32 handle
  * (MG_ERR_UNSUPPORTED): mg_rap_CF64, mg_rap_level_ms_CF64, mg_get_values_CF64, mg_get_relax_CF64, mg_replace_values_CF64 (the
  * hierarchy is set up again on the host and uploaded), mg_set_coarse_dd (a Schwarz coarsest solve), the K-cycle, Jac-GMRES,
- * nrhs > 1, and whatever a CF64 handle does not serve. */
+ * nrhs > 1 in the entry points of this section (blocks: mg_block_cycle_dev_CFP64 and mg_block_bicgstab[_dev]_CFP64 below), and
+ * whatever a CF64 handle does not serve. */
 int mg_create_CF32(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out);
 int mg_set_operator_CF32_INT64(mg_hierarchy* h, long long level, long long which, long long n_rows, long long n_cols,
                                const long long* colptr, const long long* rowval, const float* nzval);
@@ -958,6 +962,51 @@ int mg_solve_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long l
                   long long* iters, double* resvec);
 int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float* alpha, const float* x, const float* beta,
                  float* y, long long nrhs);
+
+/* ---- blocks of right-hand sides on complex handles: SpMM cycle, block solveMG, block BiCGSTAB -----------------------------------
+ * What the reference does with size(b,2) > 1 for VAL = ComplexF64: one cycle on the whole block (getMultigridPreconditioner,
+ * SolveFuncs.jl:43-63), solveMG with Frobenius norms (l.14-36), KrylovMethods.blockBiCGSTB (l.94-96).  k sources then share one pass
+ * over every operator instead of streaming it k times.
+ *
+ * nrhs arrives WITH EACH CALL, 1 <= nrhs <= 16; the handle's own nrhs stays 1 and every entry point above keeps refusing nrhs > 1.
+ * The block entry points keep a work set of their own with the handle (level vectors of n_l x nrhs, the widened coarsest pair of a
+ * CF32 handle, staging and Krylov blocks), allocated at the first block call, grown when a larger nrhs arrives and released with the
+ * handle; the single-vector state is not touched: a single-vector call after a block call gives the bits it gave before.
+ *
+ * Layout.  Host blocks (B, X, Y of the _CF64 forms and of mg_block_bicgstab_CFP64) are Julia's column-major n x nrhs, interleaved
+ * (re, im) doubles; device blocks (the _dev forms) are ROW-MAJOR [n][nrhs] ComplexF64 on a 16-byte boundary - the layout of the
+ * real block path.  Products run in csrc/mg_complex.hpp, cx_csr_stream_spmm: the matrix stream of a row block is staged in LDS
+ * once and walked by pow2 >= nrhs lanes per row, every (row, column) one lane's sum in stored order - deterministic, and a column's
+ * result does not depend on what the other columns hold.
+ *
+ * mg_block_spmv_CF64: Y = beta*Y + alpha*Op*X on one level (X: n_cols x nrhs, Y: n_rows x nrhs).
+ * mg_block_cycle_CF64: one cycle on the block; x_is_zero as for mg_cycle_CF64, a property of the WHOLE block (norm(x) of the
+ *   reference).  mg_block_cycle_dev_CFP64: the same on device blocks (x_is_zero 0 or 1), enqueued without a synchronisation; on
+ *   a CF32 handle the mixed closure on the whole block (narrow, the single cycle from zero, widen; x_is_zero = 0: MG_ERR_UNSUPPORTED).
+ * mg_block_solve_CF64: solveMG with ||.||_F over the block; resvec as for mg_solve_CF64.
+ * mg_block_bicgstab[_dev]_CFP64: blockBiCGSTB on the handle's Krylov operator (or As[1]) with one block cycle from zero as M1;
+ *   Gram matrices R0^H V, R0^H R (deterministic two-pass sums), k x k complex solves on the host, omega = tr(T^H S)/tr(T^H T).
+ *   flag 0 converged, -1 maxIter, -2 breakdown (singular R0^H V, T = 0 or omega = 0), -3 converged on the half step, -9 B = 0 (X = 0);
+ *   resvec (up to 2*maxIter + 1 entries, nres of them written): max_j ||r_j|| / ||b_j|| at the start, after every half and full step.
+ *   On a CF32 handle every Krylov block stays ComplexF64.
+ * Coarsest solve: the dense inverse, the one-workgroup triangular sweeps or the chip-wide factor applier, each on the whole block.
+ * Refused: nrhs < 1 (MG_ERR_INVALID), nrhs > 16 (MG_ERR_UNSUPPORTED), a Schwarz sweep as coarsest solve with nrhs > 1
+ * (MG_ERR_UNSUPPORTED), an FP64 handle or a handle that is not finalized (MG_ERR_STATE), a CF32 handle in the _CF64 forms
+ * (MG_ERR_STATE), a null block, a wrong n, maxIter < 0, a device block off a 16-byte boundary (MG_ERR_INVALID).  A refusal leaves the
+ * handle usable.  Not served for complex blocks: FGMRES, PCG, the K-cycle and Jac-GMRES, the sharded forms, HIP graphs.
+ * (The _CF64 forms spell their status mg_status, as the re-setup entry points above do.) */
+mg_status mg_block_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* X,
+                             const double* beta, double* Y, long long nrhs);
+mg_status mg_block_cycle_CF64(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, long long x_is_zero);
+mg_status mg_block_solve_CF64(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, double tol,
+                              long long maxIter, long long* iters, double* resvec);
+int mg_block_cycle_dev_CFP64(mg_hierarchy* h, const double* B_dev, double* X_dev, long long n, long long nrhs,
+                             long long x_is_zero);
+int mg_block_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol,
+                            long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
+int mg_block_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs,
+                                double tol, long long maxIter, long long* iters, long long* flag, double* resvec,
+                                long long* nres);
 
 const char* mg_last_error(void);
 const char* mg_version(void);

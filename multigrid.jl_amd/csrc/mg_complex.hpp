@@ -13,6 +13,8 @@
 // per lane per complex value, coalesced), stages the products in LDS, and ONE lane per row sums its row's products
 // in stored order, then applies the fused epilogue.  Workgroups are banded per XCD (xcd_band).  A row longer than a
 // chunk has a block of its own and the whole workgroup strides over it.
+// Blocks of right-hand sides (row-major [n][nrhs]) run on the same row blocks: cx_csr_stream_spmm stages the matrix stream itself in
+// LDS and lets pow2 >= nrhs lanes per row walk it (below, behind the vector kernel).
 #pragma once
 #include "mg_kernels.hpp"
 
@@ -170,6 +172,217 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
       for (int w = 0; w < BLK / 64; ++w) t += red[w];
       v.sumsq[bid] = t;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Blocks of right-hand sides: Y = epilogue(A * X) for row-major blocks [n][nrhs] (1 <= nrhs <= BLK_KMAX), on the SAME row blocks
+// as cx_csr_stream_spmv.  The matrix stream - values AND column indices - is staged in LDS once per workgroup (coalesced loads,
+// all issued up front: 16 + 4 KiB for complex A, 8 + 4 KiB for real P / R, half the value bytes in single) and is then walked
+// by nrhs columns, so the operator is read from HBM once per block instead of once per column.
+// Lane mapping: work item t = row * G + column, G = pow2 >= nrhs; a workgroup takes its items BLK at a time, so G consecutive
+// lanes own one row (lanes with column >= nrhs idle) and consecutive lane groups own consecutive rows.  Every lane walks its
+// row from LDS in STORED order and sums in its own register: each (row, column) is one lane's sum in a fixed order - the same
+// bits on every run, whatever the other columns hold.  The LDS reads of one row's entry are the same address in its G lanes
+// (a broadcast); the 64 / G rows of a wavefront read addresses one row length apart.  For rows of equal odd length (7- and
+// 27-point operators: 7 or 27 slots of 16 B for ds_read_b128, banks (a/4) mod 64; 7 or 27 dwords for the indices, mod 32) the
+// rows of a lane group fall on distinct banks; rows of even length cost up to gcd(length, 16)-way conflicts, as they do for
+// the one-lane-per-row sum of the vector kernel.  The gather of X for one entry is one contiguous 16 * nrhs-byte segment
+// across the G lanes (8 * nrhs in single).  d[row] of SMOOTH is shared by the columns.  sumsq: the per-row-block partial of
+// sum |out|^2 over ALL columns (solveMG's Frobenius norm).  A row longer than a chunk: BLK / G lane groups stride over it,
+// and the per-column partial sums are added in lane-group order by one lane per column.
+// ------------------------------------------------------------------------------------------------
+template <int MODE, typename C>
+__device__ __forceinline__ void cx_operands_blk(const CxVecArgsT<C>& v, int row, size_t e, C& pb, C& pd, C& px) {
+  if (MODE == AXPBY) {
+    if (!v.beta_zero) pb = cmul(v.beta, v.y[e]);
+  } else {
+    pb = v.b[e];
+  }
+  if (MODE == SMOOTH) {
+    pd = v.d[row];
+    px = v.x[e];
+  }
+}
+
+template <int MODE, typename PTR, typename VT, typename C>
+__global__ __launch_bounds__(BLK) void cx_csr_stream_spmm(CxCsrDev<PTR, VT> A, CxVecArgsT<C> v, int nrhs, int lg) {
+  __shared__ VT sval[CX_CHUNK];
+  __shared__ int scol[CX_CHUNK];
+  __shared__ int srow[MAXROWS + 1];
+  __shared__ C lred[BLK];
+  __shared__ double red[BLK / 64];
+
+  const int tid = threadIdx.x;
+  const int G = 1 << lg;
+  const int bid = xcd_band(blockIdx.x, A.nblocks);
+  const int r0 = A.blk_row[bid];
+  const int r1 = A.blk_row[bid + 1];
+  const int nrows = r1 - r0;
+  const PTR k0 = A.rowptr[r0];
+  const PTR k1 = A.rowptr[r1];
+  const int c = tid & (G - 1);
+
+  if (nrows == 1 && (k1 - k0) > CX_CHUNK) {
+    // one row longer than a chunk: lane group g takes the entries g, g + BLK / G, ...
+    C acc = C{};
+    if (c < nrhs)
+      for (PTR k = k0 + (tid >> lg); k < k1; k += BLK >> lg) acc += cmul(A.val[k], v.x[(size_t)A.colidx[k] * nrhs + c]);
+    lred[tid] = acc;
+    __syncthreads();
+    double sq = 0.0;
+    if (tid < nrhs) {   // (tid == c: one lane per column, lane-group order)
+      C s = C{};
+      for (int g = 0; g < (BLK >> lg); ++g) s += lred[(g << lg) + tid];
+      const size_t e = (size_t)r0 * nrhs + tid;
+      C pb = C{}, pd = pb, px = pb;
+      cx_operands_blk<MODE>(v, r0, e, pb, pd, px);
+      const C o = cx_epilogue<MODE>(v, s, pb, pd, px);
+      v.y[e] = o;
+      sq = cabs2(o);
+    }
+    if (v.sumsq && tid < 64) {   // nrhs <= 16: the columns sit in the first wavefront
+      for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+      if (tid == 0) v.sumsq[bid] = sq;
+    }
+    return;
+  }
+
+  // ---- every global load of the matrix stream up front, staged in LDS ----------------------------
+  VT va[CX_ITEMS];
+  int ca[CX_ITEMS];
+#pragma unroll
+  for (int it = 0; it < CX_ITEMS; ++it) {
+    const PTR idx = k0 + it * BLK + tid;
+    if (idx < k1) {
+      va[it] = A.val[idx];
+      ca[it] = A.colidx[idx];
+    } else {
+      va[it] = VT{};
+      ca[it] = 0;
+    }
+  }
+  if (tid <= nrows) srow[tid] = (int)(A.rowptr[r0 + tid] - k0);
+  if (tid == 0 && nrows == MAXROWS) srow[MAXROWS] = (int)(k1 - k0);
+#pragma unroll
+  for (int it = 0; it < CX_ITEMS; ++it) {
+    sval[it * BLK + tid] = va[it];
+    scol[it * BLK + tid] = ca[it];
+  }
+  __syncthreads();
+  // ---- one lane per (row, column): the row from LDS in stored order, fused epilogue ---------------
+  double sq = 0.0;
+  const int nitems = nrows << lg;
+  for (int t = tid; t < nitems; t += BLK) {
+    const int lrow = t >> lg;
+    if (c >= nrhs) continue;
+    const int row = r0 + lrow;
+    const size_t e = (size_t)row * nrhs + c;
+    C pb = C{}, pd = pb, px = pb;
+    cx_operands_blk<MODE>(v, row, e, pb, pd, px);
+    C acc = C{};
+    const int s = srow[lrow], en = srow[lrow + 1];
+    for (int k = s; k < en; ++k) acc += cmul(sval[k], v.x[(size_t)scol[k] * nrhs + c]);
+    const C o = cx_epilogue<MODE>(v, acc, pb, pd, px);
+    v.y[e] = o;
+    sq += cabs2(o);
+  }
+  if (v.sumsq) {   // a deterministic per-block partial of sum |out|^2 over all columns, summed by sum_final
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+    if ((tid & 63) == 0) red[tid >> 6] = sq;
+    __syncthreads();
+    if (tid == 0) {
+      double t = 0.0;
+      for (int w = 0; w < BLK / 64; ++w) t += red[w];
+      v.sumsq[bid] = t;
+    }
+  }
+}
+
+// x[i][:] = d[i] * b[i][:] on a row-major block (the first sweep of relax from X = 0); m = n * nrhs
+template <typename C>
+__global__ __launch_bounds__(BLK) void cx_dscale_blk(const C* __restrict__ d, const C* __restrict__ b, C* __restrict__ x, long long m,
+                                                     int nrhs) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i < m) x[i] = cmul(d[i / nrhs], b[i]);
+}
+
+// coarsest solve from the explicit inverse on a block: X = Ainv * B, B and X row-major [n][nrhs]; one wavefront per (row, column)
+__global__ __launch_bounds__(BLK) void cx_dense_matblk(const d2_t* __restrict__ Ainv, const d2_t* __restrict__ b, d2_t* __restrict__ x,
+                                                       int n, int nrhs) {
+  const long long wave = ((long long)blockIdx.x * BLK + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wave >= (long long)n * nrhs) return;   // wave-uniform
+  const int row = (int)(wave / nrhs), c = (int)(wave - (long long)row * nrhs);
+  const d2_t* a = Ainv + (size_t)row * n;
+  d2_t acc = d2_t{0.0, 0.0};
+  for (int j = lane; j < n; j += 64) acc += cmul(a[j], b[(size_t)j * nrhs + c]);
+  for (int o = 32; o > 0; o >>= 1) acc += shfl_xor_v(acc, o);
+  if (lane == 0) x[wave] = acc;
+}
+
+// The block helpers of the complex block Krylov driver (the complex forms of blk_gram_partial / blk_gram_final / blk_comb,
+// mg_kernels.hpp): blocks row-major [n][k], k <= BLK_KMAX.
+//   cx_blk_gram_partial / _final:  G = X^H Y (k x k), G[a][b] = sum_i conj(X[i][a]) Y[i][b]: deterministic two-stage reduction
+//   cx_blk_comb:                   out[i,:] = s * add[i,:] + in[i,:] * Cm   (Cm k x k complex, row-major; out may alias in / add)
+__global__ __launch_bounds__(BLK) void cx_blk_gram_partial(const d2_t* __restrict__ X, const d2_t* __restrict__ Y, long long n, int k,
+                                                           d2_t* __restrict__ partial) {
+  __shared__ d2_t red[BLK / 64][BLK_KMAX];
+  const int a = blockIdx.y;
+  d2_t acc[BLK_KMAX];
+#pragma unroll
+  for (int b = 0; b < BLK_KMAX; ++b) acc[b] = d2_t{0.0, 0.0};
+  const long long stride = (long long)gridDim.x * BLK;
+  for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) {
+    const d2_t xa = X[i * k + a];
+    const d2_t xc = d2_t{xa.x, -xa.y};
+#pragma unroll
+    for (int b = 0; b < BLK_KMAX; ++b)
+      if (b < k) acc[b] += cmul(xc, Y[i * k + b]);
+  }
+#pragma unroll
+  for (int b = 0; b < BLK_KMAX; ++b) {
+    d2_t t = acc[b];
+    for (int o = 32; o > 0; o >>= 1) t += shfl_xor_v(t, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][b] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < k) {
+    d2_t t = d2_t{0.0, 0.0};
+    for (int w = 0; w < BLK / 64; ++w) t += red[w][threadIdx.x];
+    partial[((size_t)blockIdx.x * k + a) * k + threadIdx.x] = t;
+  }
+}
+__global__ __launch_bounds__(BLK) void cx_blk_gram_final(const d2_t* __restrict__ partial, int nb, int k, d2_t* __restrict__ out) {
+  const int e = threadIdx.x;   // entry a*k + b
+  if (e >= k * k) return;
+  d2_t t = d2_t{0.0, 0.0};
+  for (int p = 0; p < nb; ++p) t += partial[(size_t)p * k * k + e];
+  out[e] = t;
+}
+__global__ __launch_bounds__(BLK) void cx_blk_comb(d2_t* out, const d2_t* add, d2_t s, const d2_t* in, const d2_t* __restrict__ Cm,
+                                                   long long n, int k) {
+  __shared__ d2_t sc[BLK_KMAX * BLK_KMAX];
+  for (int t = threadIdx.x; t < k * k; t += BLK) sc[t] = Cm[t];
+  __syncthreads();
+  // one lane per row, as blk_comb: the whole row of `in` is in registers before the row of `out` is written (out may alias in)
+  const long long stride = (long long)gridDim.x * BLK;
+  for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) {
+    d2_t row[BLK_KMAX], o[BLK_KMAX];
+#pragma unroll
+    for (int a = 0; a < BLK_KMAX; ++a) row[a] = a < k ? in[i * k + a] : d2_t{0.0, 0.0};
+#pragma unroll
+    for (int b = 0; b < BLK_KMAX; ++b) o[b] = (b < k && add) ? cmul(s, add[i * k + b]) : d2_t{0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < BLK_KMAX; ++a)
+      if (a < k) {
+#pragma unroll
+        for (int b = 0; b < BLK_KMAX; ++b)
+          if (b < k) o[b] += cmul(row[a], sc[a * k + b]);
+      }
+#pragma unroll
+    for (int b = 0; b < BLK_KMAX; ++b)
+      if (b < k) out[i * k + b] = o[b];
   }
 }
 

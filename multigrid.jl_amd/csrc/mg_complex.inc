@@ -8,6 +8,9 @@
 // cycle / solve / spmv written once over the pair type (cx_t or cf_t).  Their coarsest solve stays ComplexF64 (widen bc, the CF64
 // kernels, narrow xc), and the _CFP64 Krylov drivers take them with the single cycle as preconditioner (the mixed branch of
 // getMultigridPreconditioner, SolveFuncs.jl:52-58).
+// Blocks of right-hand sides (mg_block_*_CF64 here, mg_block_*_CFP64 in mg_complex_krylov.inc) take nrhs with each call: cx_spmv,
+// cx_relax, cx_coarse and cx_cycle carry a column count nr (0: the single-vector path, untouched; >= 1: row-major blocks [n][nr] on
+// the block work set of CxState, cx_block_ensure).
 // Also here: the stand-alone ComplexF64 factor applier behind mg_lu_*_CFP64 (CxLu; its extern "C" entry points sit beside the
 // real applier's in mg_cabi.inc).
 //
@@ -48,6 +51,7 @@ struct CxLevel {
   bool relax_set = false;
   long long npre = 0, npost = 0, n = 0;
   DevBuf<double> b, r, x[2];   // complex scratch (CYCLEmem, MGdef.jl:56-60); x ping-pongs between the sweeps
+  DevBuf<double> Bb, Br, Bx[2];   // the same for the block entry points (mg_block_*): row-major [n][blk_cap], see CxState::blk_cap
 };
 
 struct CxState {
@@ -71,6 +75,15 @@ struct CxState {
   CxMat K;
   DevBuf<double> kwork, kpart, kscal, stage_x;
   double* h_kscal = nullptr;
+  // The block work set of the mg_block_* entry points: sized lazily for blk_cap columns (cx_block_ensure), grown when a larger nrhs
+  // arrives, dropped by mg_finalize.  The handle's own nrhs stays 1 and its single-vector state above is never touched by a block call.
+  //   lev[l].Bb / Br / Bx[2]; the widened coarsest pair of a CF32 handle; the triangular sweeps' work vector; the staging blocks of the
+  //   host forms (row-major b and x, and one column-major block); the Krylov blocks, Gram partials and coefficient slots of block BiCGSTAB
+  int blk_cap = 0;
+  DevBuf<double> Bcw_b, Bcw_x, BluWork, Bstage_b, Bstage_x, Bstage_t, Bkwork, Bgpart, Bcoef;
+  double* h_bgram = nullptr;        // pinned: one k x k complex Gram matrix
+  double* h_bcoef = nullptr;        // pinned ring of coefficient matrices
+  unsigned bcoef_next = 0;
   std::vector<hipEvent_t> rap_ev;   // mg_rap_CF64: one event ahead of every level's kernels and one behind the last (mg_rap_level_ms_CF64)
   bool rap_timed = false;
   ~CxState() {
@@ -78,7 +91,11 @@ struct CxState {
     for (auto& L : lev) {
       L.A.release(); L.P.release(); L.R.release();
       L.d.release(); L.b.release(); L.r.release(); L.x[0].release(); L.x[1].release();
+      L.Bb.release(); L.Br.release(); L.Bx[0].release(); L.Bx[1].release();
     }
+    for (DevBuf<double>* d : {&Bcw_b, &Bcw_x, &BluWork, &Bstage_b, &Bstage_x, &Bstage_t, &Bkwork, &Bgpart, &Bcoef}) d->release();
+    if (h_bgram) (void)hipHostFree(h_bgram);
+    if (h_bcoef) (void)hipHostFree(h_bcoef);
     Ainv.release();
     for (DevBuf<int>* d : {&luLptr, &luLcol, &luUptr, &luUcol, &luP, &luQ, &luLorder, &luLlvl, &luUorder, &luUlvl}) d->release();
     luLval.release(); luUval.release(); luWork.release();
@@ -234,9 +251,10 @@ int cx_set_transfer(mg_hierarchy* h, long long level, long long which, long long
   return MG_OK;
 }
 
-// y = epilogue(M * x) on h's stream; the launch of one (MODE, row-pointer width, value type, pair type)
+// y = epilogue(M * x) on h's stream; the launch of one (MODE, row-pointer width, value type, pair type).  nr == 0: vectors, the
+// one-lane-per-row kernel; nr >= 1: row-major blocks [n][nr], the block kernel on the same row blocks (G = pow2 >= nr lanes per row)
 template <int MODE, typename PTR, typename VT, typename C>
-void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::CxVecArgsT<C>& v) {
+void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::CxVecArgsT<C>& v, int nr) {
   mgk::CxCsrDev<PTR, VT> D;
   D.rowptr = rowptr;
   D.colidx = M.colidx.p;
@@ -244,27 +262,34 @@ void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::Cx
   D.blk_row = M.blk_row.p;
   D.nblocks = M.nblocks;
   D.n_rows = (int)M.n_rows;
-  hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<MODE, PTR, VT, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+  if (nr == 0) {
+    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<MODE, PTR, VT, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+    return;
+  }
+  int lg = 0;
+  while ((1 << lg) < nr) ++lg;
+  hipLaunchKernelGGL((mgk::cx_csr_stream_spmm<MODE, PTR, VT, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v, nr, lg);
 }
 
-// C: the pair type of the vectors (cx_t or cf_t), deduced from x; the operator holds values of the same precision
+// C: the pair type of the vectors (cx_t or cf_t), deduced from x; the operator holds values of the same precision; nr as for cx_launch
 template <int MODE, typename C>
 int cx_spmv(mg_hierarchy* h, const CxMat& M, const C* x, typename cx_non_deduced<C>::type* y, const typename cx_non_deduced<C>::type* b,
             const typename cx_non_deduced<C>::type* d, double* sumsq, typename cx_non_deduced<C>::type alpha = C{1, 0},
-            typename cx_non_deduced<C>::type beta = C{0, 0}) {
+            typename cx_non_deduced<C>::type beta = C{0, 0}, int nr = 0) {
   typedef typename mgk::cx_scalar<C>::type T;
   if (M.single != (sizeof(T) == sizeof(float))) return fail(MG_ERR_INVALID, "internal: operator and vectors differ in precision");
+  if (nr < 0 || nr > mgk::BLK_KMAX) return fail(MG_ERR_INVALID, "internal: a block of %d columns", nr);
   mgk::CxVecArgsT<C> v;
   v.x = x; v.y = y; v.b = b; v.d = d; v.sumsq = sumsq;
   v.alpha = alpha; v.beta = beta;
   v.beta_zero = (beta.x == 0 && beta.y == 0) ? 1 : 0;
   if (M.cplx) {
-    if (M.wide) cx_launch<MODE, long long, C, C>(h, M, M.rowptr64.p, v);
-    else cx_launch<MODE, int, C, C>(h, M, M.rowptr.p, v);
+    if (M.wide) cx_launch<MODE, long long, C, C>(h, M, M.rowptr64.p, v, nr);
+    else cx_launch<MODE, int, C, C>(h, M, M.rowptr.p, v, nr);
   } else {
     if (MODE != mgk::AXPBY) return fail(MG_ERR_INVALID, "internal: a real transfer operator serves the AXPBY form only");
-    if (M.wide) cx_launch<mgk::AXPBY, long long, T, C>(h, M, M.rowptr64.p, v);
-    else cx_launch<mgk::AXPBY, int, T, C>(h, M, M.rowptr.p, v);
+    if (M.wide) cx_launch<mgk::AXPBY, long long, T, C>(h, M, M.rowptr64.p, v, nr);
+    else cx_launch<mgk::AXPBY, int, T, C>(h, M, M.rowptr.p, v, nr);
   }
   HIP_TRY(hipGetLastError());
   return MG_OK;
@@ -284,10 +309,11 @@ int cx_norm2(mg_hierarchy* h, const C* z, long long n, double* out) {
 }
 
 // r = b - A x with the per-block partials of ||r||^2, then the sum into the pinned host scalar
+// (nr >= 1: blocks [n][nr], the sum over all columns - the Frobenius norm of the block solveMG)
 template <typename C>
-int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const C* b, const C* x, C* r, double* out) {
+int cx_residual_norm2(mg_hierarchy* h, const CxLevel& L, const C* b, const C* x, C* r, double* out, int nr = 0) {
   CxState& S = *h->cx;
-  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, x, r, b, nullptr, S.partial.p));
+  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, x, r, b, nullptr, S.partial.p, C{1, 0}, C{0, 0}, nr));
   hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, S.partial.p, L.A.nblocks, h->play->scalar.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h->h_scalar, h->play->scalar.p, sizeof(double), hipMemcpyDeviceToHost, h->play->stream));
@@ -312,11 +338,16 @@ int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr, const hi
 
 // z = param.LU \ b (MGcycle.jl:177): explicit inverse, or x[q] = U \ (L \ b[p]) by the level-scheduled sptrsv_lu (one workgroup;
 // chip-wide for factors of >= lu_multi_min_rows rows), or one Schwarz sweep (MGcycle.jl:140-143; xzero: x need not be read)
-int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true) {
+// nr >= 1: b and x are row-major blocks [n][nr] (the factor applier's own layout; the Schwarz sweep serves one column)
+int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr = 0) {
   CxState& S = *h->cx;
   const long long n = S.n_coarse;
-  if (h->coarse_dd) return dd_coarse(h, reinterpret_cast<const double*>(b), reinterpret_cast<double*>(x), xzero);
-  if (S.coarse_multi) return cxlu_solve_dev(S.coarse_multi, *S.coarse_multi->fwd, b, x, 1, &h->play->stream);
+  const int k = std::max(nr, 1);
+  if (h->coarse_dd) {
+    if (k > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%d)", k);
+    return dd_coarse(h, reinterpret_cast<const double*>(b), reinterpret_cast<double*>(x), xzero);
+  }
+  if (S.coarse_multi) return cxlu_solve_dev(S.coarse_multi, *S.coarse_multi->fwd, b, x, k, &h->play->stream);
   if (S.coarse_lu) {
     mgk::LuDevT<cx_t> F;
     F.n = (int)n;
@@ -325,10 +356,13 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true) {
     F.p = S.luP.p; F.q = S.luQ.p;
     F.Lorder = S.luLorder.p; F.Llvl = S.luLlvl.p; F.nLlvl = S.nLlvl;
     F.Uorder = S.luUorder.p; F.Ulvl = S.luUlvl.p; F.nUlvl = S.nUlvl;
-    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, h->play->stream, F, b, x, cxp(S.luWork), 1);
-  } else {
+    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, h->play->stream, F, b, x, cxp(nr ? S.BluWork : S.luWork), k);
+  } else if (nr == 0) {
     hipLaunchKernelGGL(mgk::cx_dense_matvec, dim3(cx_grid(n * 64)), dim3(mgk::BLK), 0, h->play->stream,
                        reinterpret_cast<const cx_t*>(S.Ainv.p), b, x, (int)n);
+  } else {
+    hipLaunchKernelGGL(mgk::cx_dense_matblk, dim3(cx_grid(n * k * 64)), dim3(mgk::BLK), 0, h->play->stream,
+                       reinterpret_cast<const cx_t*>(S.Ainv.p), b, x, (int)n, k);
   }
   HIP_TRY(hipGetLastError());
   return MG_OK;
@@ -336,25 +370,37 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true) {
 
 // The coarsest solve of a CF32 handle stays ComplexF64 (Julia's lu of a ComplexF32 sparse matrix factorises in double,
 // MGsetup.jl:350; MGcycle.jl:177-178): bc is widened, solved by the kernels above, xc narrowed.
-int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool = true) {
+int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool = true, int nr = 0) {
   CxState& S = *h->cx;
-  MG_TRY(cx_widen(h, b, cxp(S.cw_b), S.n_coarse));
-  MG_TRY(cx_coarse(h, cxc(S.cw_b), cxp(S.cw_x), true));
-  return cx_narrow(h, cxc(S.cw_x), x, S.n_coarse);
+  DevBuf<double>&wb = nr ? S.Bcw_b : S.cw_b, &wx = nr ? S.Bcw_x : S.cw_x;
+  const long long len = S.n_coarse * std::max(nr, 1);
+  MG_TRY(cx_widen(h, b, cxp(wb), len));
+  MG_TRY(cx_coarse(h, cxc(wb), cxp(wx), true, nr));
+  return cx_narrow(h, cxc(wx), x, len);
 }
+
+// the level vectors a cycle works on: the handle's own (nr == 0: one right-hand side) or the block work set (nr >= 1 columns)
+inline DevBuf<double>& cx_lb(CxLevel& L, int nr) { return nr ? L.Bb : L.b; }
+inline DevBuf<double>& cx_lr(CxLevel& L, int nr) { return nr ? L.Br : L.r; }
+inline DevBuf<double>& cx_lx(CxLevel& L, int nr, int i) { return nr ? L.Bx[i] : L.x[i]; }
 
 // relax (MGcycle.jl:122-136) entered with r = b - A x: numit-1 times {x += d.*r; r = b - A x}, then x += d.*r - i.e.
 // max(numit, 1) sweeps x' = x + d.*(b - A x); from x = 0 the first one is x = d.*b.  x ping-pongs between L.x[0] / L.x[1].
+// nr columns (0: a vector): d[row] is shared by the columns of a block.
 template <typename C>
-int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long long numit) {
+int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long long numit, int nr = 0) {
   long long sweeps = std::max<long long>(numit, 1);
   if (xzero) {
-    hipLaunchKernelGGL(mgk::cx_dscale<C>, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, cxp<C>(L.x[xi]), L.n);
+    if (nr == 0)
+      hipLaunchKernelGGL(mgk::cx_dscale<C>, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, cxp<C>(L.x[xi]), L.n);
+    else
+      hipLaunchKernelGGL(mgk::cx_dscale_blk<C>, dim3(cx_grid(L.n * nr)), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b,
+                         cxp<C>(L.Bx[xi]), L.n * nr, nr);
     HIP_TRY(hipGetLastError());
     --sweeps;
   }
   for (long long s = 0; s < sweeps; ++s) {
-    MG_TRY(cx_spmv<mgk::SMOOTH>(h, L.A, cxc<C>(L.x[xi]), cxp<C>(L.x[1 - xi]), b, cxc<C>(L.d), nullptr));
+    MG_TRY(cx_spmv<mgk::SMOOTH>(h, L.A, cxc<C>(cx_lx(L, nr, xi)), cxp<C>(cx_lx(L, nr, 1 - xi)), b, cxc<C>(L.d), nullptr, C{1, 0}, C{0, 0}, nr));
     xi = 1 - xi;
   }
   return MG_OK;
@@ -362,27 +408,31 @@ int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long 
 
 // recursiveCycle (MGcycle.jl:1-118) from level l (0-based) on b; the iterate is lev[l].x[xi] (zero on entry when xzero).
 // C = cx_t on a CF64 handle, cf_t on a CF32 one: the same recursion on the same buffers.
+// nr columns (0: a vector on the handle's own level vectors; >= 1: row-major blocks on the block work set, xzero a property of the
+// whole block as norm(x) is in the reference).
 template <typename C>
-int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype) {
+int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype, int nr = 0) {
   CxState& S = *h->cx;
   const int nl = (int)h->nlevels;
   CxLevel& L = S.lev[(size_t)l];
-  if (l == nl - 1) return cx_coarse(h, b, cxp<C>(L.x[xi]), xzero);                            // l.13-18
-  MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre));                                       // l.26-31, 54
-  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxc<C>(L.x[xi]), cxp<C>(L.r), b, nullptr, nullptr));  // l.58-60
+  const C one = C{1, 0}, zero = C{0, 0};
+  if (l == nl - 1) return cx_coarse(h, b, cxp<C>(cx_lx(L, nr, xi)), xzero, nr);                 // l.13-18
+  MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre, nr));                                    // l.26-31, 54
+  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxc<C>(cx_lx(L, nr, xi)), cxp<C>(cx_lr(L, nr)), b, nullptr, nullptr, one, zero, nr));  // l.58-60
   CxLevel& C1 = S.lev[(size_t)l + 1];
-  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.R, cxc<C>(L.r), cxp<C>(C1.b), nullptr, nullptr, nullptr));   // bc = R r   (l.66)
+  const C* bc = cxc<C>(cx_lb(C1, nr));
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.R, cxc<C>(cx_lr(L, nr)), cxp<C>(cx_lb(C1, nr)), nullptr, nullptr, nullptr, one, zero, nr));   // bc = R r   (l.66)
   int ci = 0;
   if (l + 1 == nl - 1) {
-    MG_TRY(cx_coarse(h, cxc<C>(C1.b), cxp<C>(C1.x[ci])));                                 // l.67-69
+    MG_TRY(cx_coarse(h, bc, cxp<C>(cx_lx(C1, nr, ci)), true, nr));                         // l.67-69
   } else {
-    MG_TRY(cx_cycle<C>(h, l + 1, cxc<C>(C1.b), ci, true, ctype));                         // xc = 0 (l.63-64), l.78
-    if (ctype == 'W') MG_TRY(cx_cycle<C>(h, l + 1, cxc<C>(C1.b), ci, false, 'W'));        // l.79-80
-    else if (ctype == 'F') MG_TRY(cx_cycle<C>(h, l + 1, cxc<C>(C1.b), ci, false, 'V'));   // l.81-84
+    MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, true, ctype, nr));                                // xc = 0 (l.63-64), l.78
+    if (ctype == 'W') MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, false, 'W', nr));               // l.79-80
+    else if (ctype == 'F') MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, false, 'V', nr));          // l.81-84
   }
   // x += P xc (l.90): in place, the gather reads xc only
-  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(C1.x[ci]), cxp<C>(L.x[xi]), nullptr, nullptr, nullptr, C{1, 0}, C{1, 0}));
-  return cx_relax<C>(h, L, b, xi, false, L.npost);                                      // r = b - A x, relax (l.92-102)
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(cx_lx(C1, nr, ci)), cxp<C>(cx_lx(L, nr, xi)), nullptr, nullptr, nullptr, one, one, nr));
+  return cx_relax<C>(h, L, b, xi, false, L.npost, nr);                                   // r = b - A x, relax (l.92-102)
 }
 
 int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want = CX_WANT64) {
@@ -393,10 +443,57 @@ int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want = C
   return MG_OK;
 }
 
+int cx_block_nrhs_ok(long long nrhs) {
+  if (nrhs < 1) return fail(MG_ERR_INVALID, "nrhs=%lld: a block holds at least one right-hand side", nrhs);
+  if (nrhs > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "complex blocks hold at most %d right-hand sides (nrhs=%lld)", mgk::BLK_KMAX, nrhs);
+  return MG_OK;
+}
+// The checks of the mg_block_* entry points (the block forms take nrhs with each call; the handle's own nrhs stays 1)
+int cx_block_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want) {
+  MG_TRY(cx_handle_ok(h, want));
+  if (!h->cx->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  MG_TRY(cx_block_nrhs_ok(nrhs));
+  if (n != h->cx->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->cx->lev[0].n);
+  if (h->coarse_dd && nrhs > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%lld)", nrhs);
+  return MG_OK;
+}
+
+// The block work set for nr columns: allocated at the first block call, grown when a larger nr arrives (like CxKry::ensure), kept with
+// the handle.  Nothing of the single-vector state is touched.
+int cx_block_ensure(mg_hierarchy* h, int nr) {
+  CxState& S = *h->cx;
+  if (nr <= S.blk_cap) return MG_OK;
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));   // (an earlier block call may still read the buffers replaced below)
+  S.blk_cap = 0;
+  const size_t k = (size_t)nr;
+  for (auto& L : S.lev) {
+    const size_t len = cx_len(S, L.n) * k;
+    for (DevBuf<double>* d : {&L.Bb, &L.Br, &L.Bx[0], &L.Bx[1]}) MG_TRY(d->alloc(len));
+  }
+  const size_t n0 = 2 * (size_t)S.lev[0].n * k, nc = 2 * (size_t)S.n_coarse * k;
+  for (DevBuf<double>* d : {&S.Bstage_b, &S.Bstage_x, &S.Bstage_t}) MG_TRY(d->alloc(n0));
+  if (S.single) {
+    MG_TRY(S.Bcw_b.alloc(nc));
+    MG_TRY(S.Bcw_x.alloc(nc));
+  }
+  if (S.coarse_multi) {   // (no allocation inside the cycle: the factor applier's work vectors for nr columns)
+    CxLu* F = S.coarse_multi;
+    const size_t tlen = 2 * (size_t)std::max(F->fwd->M, 1) * k;
+    if (F->work.n < nc) MG_TRY(F->work.alloc(nc));
+    if (F->tail.n < tlen) MG_TRY(F->tail.alloc(tlen));
+  } else if (S.coarse_lu) {
+    MG_TRY(S.BluWork.alloc(nc));
+  }
+  S.blk_cap = nr;
+  return MG_OK;
+}
+
 // mg_finalize of a CF64 handle: shapes chain, every level complete, scratch allocated
 int cx_finalize(mg_hierarchy* h) {
   CxState& S = *h->cx;
   S.finalized = false;
+  S.blk_cap = 0;   // (levels may have changed size: the block work set is sized again by the next block call)
   const int nl = (int)h->nlevels;
   if (S.single && h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve is not served for CF32 handles");
   if (S.K_auto) {   // As[1] may have changed since it was widened: the next driver call widens it again
@@ -865,6 +962,110 @@ int cx_spmv_host(mg_hierarchy* h, long long level, long long which, const ST* al
   return rc;
 }
 
+// ---- the host-pointer block forms (mg_block_*_CF64): Julia's column-major n x nrhs blocks, relaid at the boundary ----
+// host column-major block -> device row-major block dst (through the column-major staging block `cm`), and back
+int cx_block_upload(mg_hierarchy* h, const double* src, DevBuf<double>& cm, cx_t* dst, long long n, int nr) {
+  const hipStream_t st = h->play->stream;
+  HIP_TRY(hipMemcpyAsync(cm.p, src, sizeof(cx_t) * (size_t)n * (size_t)nr, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(mgk::cx_relayout<true>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, st, cxc(cm), dst, n, nr);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+int cx_block_download(mg_hierarchy* h, const cx_t* src, DevBuf<double>& cm, double* dst, long long n, int nr) {
+  const hipStream_t st = h->play->stream;
+  hipLaunchKernelGGL(mgk::cx_relayout<false>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, st, src, cxp(cm), n, nr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(dst, cm.p, sizeof(cx_t) * (size_t)n * (size_t)nr, hipMemcpyDeviceToHost, st));
+  HIP_TRY(spin_sync(st));
+  return MG_OK;
+}
+int cx_block_cycle_host(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, long long x_is_zero) {
+  MG_TRY(cx_block_ready(h, n, nrhs, CX_WANT64));
+  if (!B || !X) return fail(MG_ERR_INVALID, "null block");
+  const int nr = (int)nrhs;
+  MG_TRY(cx_block_ensure(h, nr));
+  CxState& S = *h->cx;
+  CxLevel& L0 = S.lev[0];
+  bool xz = (x_is_zero == 1);
+  if (x_is_zero < 0) xz = host_all_zero(X, 2 * n * nrhs);   // norm(x) > 0.0 over the whole block decides (MGcycle.jl:29)
+  int xi = 0;
+  MG_TRY(cx_block_upload(h, B, S.Bstage_t, cxp(S.Bstage_b), n, nr));
+  if (!xz) MG_TRY(cx_block_upload(h, X, S.Bstage_t, cxp(L0.Bx[xi]), n, nr));
+  MG_TRY(cx_cycle<cx_t>(h, 0, cxc(S.Bstage_b), xi, xz, h->cycle, nr));
+  return cx_block_download(h, cxc(L0.Bx[xi]), S.Bstage_t, X, n, nr);
+}
+
+// solveMG on a block (SolveFuncs.jl:14-36): the norms are Frobenius norms of the whole block
+int cx_block_solve_host(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, double tol, long long maxIter,
+                        long long* iters, double* resvec) {
+  MG_TRY(cx_block_ready(h, n, nrhs, CX_WANT64));
+  if (!B || !X) return fail(MG_ERR_INVALID, "null block");
+  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
+  const int nr = (int)nrhs;
+  MG_TRY(cx_block_ensure(h, nr));
+  CxState& S = *h->cx;
+  CxLevel& L0 = S.lev[0];
+  const cx_t* bd = cxc(S.Bstage_b);
+  int xi = 0;
+  bool xz = host_all_zero(X, 2 * n * nrhs);
+  MG_TRY(cx_block_upload(h, B, S.Bstage_t, cxp(S.Bstage_b), n, nr));
+  double res2 = 0.0;
+  if (xz) {
+    MG_TRY(cx_norm2<cx_t>(h, bd, n * nr, &res2));
+  } else {
+    MG_TRY(cx_block_upload(h, X, S.Bstage_t, cxp(L0.Bx[xi]), n, nr));
+    MG_TRY(cx_residual_norm2<cx_t>(h, L0, bd, cxc(L0.Bx[xi]), cxp(L0.Br), &res2, nr));
+  }
+  const double res0 = std::sqrt(res2);
+  if (resvec) resvec[0] = res0;
+  long long it = 0;
+  for (long long count = 1; count <= maxIter; ++count) {
+    MG_TRY(cx_cycle<cx_t>(h, 0, bd, xi, xz, h->cycle, nr));
+    xz = false;
+    MG_TRY(cx_residual_norm2<cx_t>(h, L0, bd, cxc(L0.Bx[xi]), cxp(L0.Br), &res2, nr));
+    ++it;
+    const double res = std::sqrt(res2);
+    if (resvec) resvec[count] = res;
+    if (res / res0 < tol) break;
+  }
+  if (xz) HIP_TRY(hipMemsetAsync(L0.Bx[xi].p, 0, sizeof(cx_t) * (size_t)n * (size_t)nr, h->play->stream));   // maxIter = 0 from X = 0
+  MG_TRY(cx_block_download(h, cxc(L0.Bx[xi]), S.Bstage_t, X, n, nr));
+  if (iters) *iters = it;
+  return MG_OK;
+}
+
+// Y = beta*Y + alpha*Op*X on one level, X n_cols x nrhs and Y n_rows x nrhs column-major on the host
+int cx_block_spmv_host(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* X, const double* beta,
+                       double* Y, long long nrhs) {
+  MG_TRY(cx_level_ok(h, level, CX_WANT64));
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
+  MG_TRY(cx_block_nrhs_ok(nrhs));
+  if (!alpha || !beta || !X || !Y) return fail(MG_ERR_INVALID, "null argument");
+  if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
+  CxLevel& L = S.lev[(size_t)level - 1];
+  if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
+  const CxMat& M = which == MG_OP_A ? L.A : which == MG_OP_P ? L.P : L.R;
+  (void)hipSetDevice(h->device);
+  const int nr = (int)nrhs;
+  const long long mr = M.n_rows, mc = M.n_cols;
+  const cx_t a = cx_t{alpha[0], alpha[1]}, bt = cx_t{beta[0], beta[1]};
+  const bool bz = bt.x == 0 && bt.y == 0;
+  DevBuf<double> cm, dx, dy;   // (released below on every path)
+  int rc = cm.alloc(2 * (size_t)std::max(mr, mc) * (size_t)nr);
+  if (rc == MG_OK) rc = dx.alloc(2 * (size_t)mc * (size_t)nr);
+  if (rc == MG_OK) rc = dy.alloc(2 * (size_t)mr * (size_t)nr);
+  if (rc == MG_OK) rc = cx_block_upload(h, X, cm, cxp(dx), mc, nr);
+  if (rc == MG_OK && !bz) rc = cx_block_upload(h, Y, cm, cxp(dy), mr, nr);
+  if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxc(dx), cxp(dy), nullptr, nullptr, nullptr, a, bt, nr);
+  if (rc == MG_OK) rc = cx_block_download(h, cxc(dy), cm, Y, mr, nr);
+  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_block_spmv: stream failed");
+  cm.release();
+  dx.release();
+  dy.release();
+  return rc;
+}
+
 // As[1] of a CF32 handle widened into the Krylov operator K: the system operator of the _CFP64 drivers when none was set (the
 // Krylov product is never single).  Same pattern and row blocks (one chunk size for both precisions), values through cx_widen.
 int cx_widen_K(mg_hierarchy* h) {
@@ -1096,6 +1297,20 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
 int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float* alpha, const float* x, const float* beta, float* y,
                  long long nrhs) {
   return cx_spmv_host<cf_t>(h, level, which, alpha, x, beta, y, nrhs, CX_WANT32);
+}
+
+// blocks of right-hand sides on a CF64 handle: nrhs arrives with each call (the device-pointer forms and the block driver, which
+// also serve CF32 handles, are in mg_complex_krylov.inc)
+int mg_block_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* X, const double* beta,
+                       double* Y, long long nrhs) {
+  return cx_block_spmv_host(h, level, which, alpha, X, beta, Y, nrhs);
+}
+int mg_block_cycle_CF64(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, long long x_is_zero) {
+  return cx_block_cycle_host(h, B, X, n, nrhs, x_is_zero);
+}
+int mg_block_solve_CF64(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, double tol, long long maxIter,
+                        long long* iters, double* resvec) {
+  return cx_block_solve_host(h, B, X, n, nrhs, tol, maxIter, iters, resvec);
 }
 
 // replaceMatrixInHierarchy on the device (MGsetup.jl:226-270) for VAL = ComplexF64: new fine values on the stored pattern, then per

@@ -317,6 +317,187 @@ int cx_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long lon
   return MG_OK;
 }
 
+// ---- blocks of right-hand sides: blockBiCGSTB (SolveFuncs.jl:94-96) for VAL = ComplexF64 ---------------------------------------------
+// block_bicgstab_dev of mg_krylov.inc on complex blocks, row-major [n][k] ComplexF64 resident in HBM: products with the system operator
+// are cx_csr_stream_spmm launches, the preconditioner is one block cycle from zero (on a CF32 handle the mixed closure on the whole
+// block: narrow, the single cycle, widen), Gram matrices are X^H Y (one 16*k*k-byte readback each), the k x k solves run on the
+// host (SmallMatT<zc>, mg_krylov_host.hpp), omega = tr(T^H S) / tr(T^H T).  Flags, resvec and the stopping tests are the real driver's.
+typedef SmallMatT<zc> CMat;
+struct CxBlkKry {
+  mg_hierarchy* h;
+  CxState& S;
+  const long long n;
+  const int k;
+  const CxMat& A;      // the system operator
+  hipStream_t st;
+  static constexpr size_t SLOT = (size_t)mgk::BLK_KMAX * mgk::BLK_KMAX;   // complex entries of one coefficient matrix
+  CxBlkKry(mg_hierarchy* h_, int k_) : h(h_), S(*h_->cx), n(h_->cx->lev[0].n), k(k_), A(h_->cx->K.set ? h_->cx->K : h_->cx->lev[0].A), st(h_->play->stream) {}
+  size_t len() const { return (size_t)n * (size_t)k; }
+  int nblocks() const { return (int)std::min<long long>(256, std::max<long long>(1, (n + mgk::BLK - 1) / mgk::BLK)); }
+  int ensure(size_t blocks) {
+    const size_t need = blocks * 2 * len(), gneed = 2 * ((size_t)nblocks() + 1) * SLOT;
+    if (S.Bkwork.n < need) MG_TRY(S.Bkwork.alloc(need));
+    if (S.Bgpart.n < gneed) MG_TRY(S.Bgpart.alloc(gneed));
+    if (S.Bcoef.n == 0) MG_TRY(S.Bcoef.alloc(2 * SLOT * 8));
+    if (!S.h_bgram) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_bgram), sizeof(double) * 2 * SLOT));
+    if (!S.h_bcoef) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_bcoef), sizeof(double) * 2 * SLOT * 8));
+    return MG_OK;
+  }
+  cx_t* blk(size_t i) { return cxp(S.Bkwork) + i * len(); }
+  // G = X^H Y to the host; synchronises the stream
+  int gram(const cx_t* X, const cx_t* Y, CMat& G) {
+    const int nb = nblocks();
+    cx_t* part = cxp(S.Bgpart);
+    cx_t* out = part + (size_t)nb * k * k;
+    hipLaunchKernelGGL(mgk::cx_blk_gram_partial, dim3(nb, k), dim3(mgk::BLK), 0, st, X, Y, n, k, part);
+    hipLaunchKernelGGL(mgk::cx_blk_gram_final, dim3(1), dim3(mgk::BLK), 0, st, part, nb, k, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(S.h_bgram, out, sizeof(cx_t) * k * k, hipMemcpyDeviceToHost, st));
+    HIP_TRY(spin_sync(st));
+    G = CMat(k, k);
+    for (int e = 0; e < k * k; ++e) G.a[(size_t)e] = zc(S.h_bgram[2 * e], S.h_bgram[2 * e + 1]);
+    return MG_OK;
+  }
+  // out = s*add + in*Cm (add may be null; out may alias in or add): a ring of 8 coefficient slots, drained once per lap (blk_comb)
+  int comb(cx_t* out, const cx_t* add, zc s, const cx_t* in, const CMat& Cm) {
+    const unsigned si = S.bcoef_next++ % 8;
+    if (si == 0 && S.bcoef_next > 1) HIP_TRY(spin_sync(st));
+    double* hs = S.h_bcoef + 2 * SLOT * si;
+    cx_t* slot = cxp(S.Bcoef) + SLOT * si;
+    for (int e = 0; e < k * k; ++e) {
+      hs[2 * e] = Cm.a[(size_t)e].real();
+      hs[2 * e + 1] = Cm.a[(size_t)e].imag();
+    }
+    HIP_TRY(hipMemcpyAsync(slot, hs, sizeof(cx_t) * k * k, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(mgk::cx_blk_comb, dim3(cx_grid(n)), dim3(mgk::BLK), 0, st, out, add, cxv(s), in, slot, n, k);
+    HIP_TRY(hipGetLastError());
+    return MG_OK;
+  }
+  int colnorms(const cx_t* X, std::vector<double>& out) {
+    CMat G;
+    MG_TRY(gram(X, X, G));
+    out.assign((size_t)k, 0.0);
+    for (int j = 0; j < k; ++j) out[(size_t)j] = std::sqrt(std::max(0.0, G(j, j).real()));
+    return MG_OK;
+  }
+  int copy(cx_t* dst, const cx_t* src) {
+    HIP_TRY(hipMemcpyAsync(dst, src, sizeof(cx_t) * len(), hipMemcpyDeviceToDevice, st));
+    return MG_OK;
+  }
+  // Z = M(V): one block cycle from zero, copied (CF64) or widened (CF32) out of the level buffer into Z
+  int prec(const cx_t* V, cx_t* Z) {
+    int xi = 0;
+    CxLevel& L0 = S.lev[0];
+    if (!S.single) {
+      MG_TRY(cx_cycle<cx_t>(h, 0, V, xi, true, h->cycle, k));
+      return copy(Z, cxc(L0.Bx[xi]));
+    }
+    MG_TRY(cx_narrow(h, V, cxp<cf_t>(L0.Bb), (long long)len()));
+    MG_TRY(cx_cycle<cf_t>(h, 0, cxc<cf_t>(L0.Bb), xi, true, h->cycle, k));
+    return cx_widen(h, cxc<cf_t>(L0.Bx[xi]), Z, (long long)len());
+  }
+  int product(const cx_t* X, cx_t* Y) { return cx_spmv<mgk::AXPBY>(h, A, X, Y, nullptr, nullptr, nullptr, cx_t{1, 0}, cx_t{0, 0}, k); }
+  int residual(const cx_t* B, const cx_t* X, cx_t* R) { return cx_spmv<mgk::RESID>(h, A, X, R, B, nullptr, nullptr, cx_t{1, 0}, cx_t{0, 0}, k); }
+};
+
+int cx_block_bicgstab_dev(mg_hierarchy* h, const cx_t* B, cx_t* X, int k, double tol, long long maxIter, long long* iters,
+                          long long* flag_out, double* resvec, long long* nres) {
+  CxBlkKry K(h, k);
+  MG_TRY(K.ensure(7));
+  cx_t *R = K.blk(0), *R0 = K.blk(1), *P = K.blk(2), *Ph = K.blk(3), *V = K.blk(4), *Sh = K.blk(5), *T = K.blk(6);
+  std::vector<double> nb, rn;
+  MG_TRY(K.colnorms(B, nb));
+  long long it = 0, flag = -1;
+  KrylovReport rep(iters, flag_out, resvec, nres);
+  bool any = false;
+  for (double v : nb) any = any || v > 0.0;
+  if (!any) {
+    HIP_TRY(hipMemsetAsync(X, 0, sizeof(cx_t) * K.len(), K.st));
+    HIP_TRY(spin_sync(K.st));
+    return rep.finish(0, -9);
+  }
+  for (double& v : nb) if (!(v > 0.0)) v = 1.0;
+  auto worst_rel = [&](const cx_t* blk, double* out) -> int {
+    MG_TRY(K.colnorms(blk, rn));
+    double wv = 0.0;
+    for (int j = 0; j < k; ++j) wv = std::max(wv, rn[(size_t)j] / nb[(size_t)j]);
+    *out = wv;
+    return MG_OK;
+  };
+  const zc one(1.0, 0.0);
+  MG_TRY(K.residual(B, X, R));
+  double err = 0.0;
+  MG_TRY(worst_rel(R, &err));
+  rep.record(err);
+  if (err < tol) return rep.finish(0, 0);
+  MG_TRY(K.copy(R0, R));
+  MG_TRY(K.copy(P, R));
+  for (long long iter = 1; iter <= maxIter; ++iter) {
+    it = iter;
+    MG_TRY(K.prec(P, Ph));                                        // Phat = M(P)
+    MG_TRY(K.product(Ph, V));                                     // V = A Phat
+    CMat RtV, RtR, alpha;
+    MG_TRY(K.gram(R0, V, RtV));
+    MG_TRY(K.gram(R0, R, RtR));
+    if (!sm_solve(RtV, RtR, alpha)) { flag = -2; break; }
+    CMat nalpha = alpha;
+    for (zc& v : nalpha.a) v = -v;
+    MG_TRY(K.comb(R, R, one, V, nalpha));                         // S = R - V alpha   (in R)
+    double sn = 0.0;
+    MG_TRY(worst_rel(R, &sn));
+    rep.record(sn);
+    if (sn < tol) {
+      MG_TRY(K.comb(X, X, one, Ph, alpha));
+      flag = -3;
+      break;
+    }
+    MG_TRY(K.prec(R, Sh));                                        // Shat = M(S)
+    MG_TRY(K.product(Sh, T));                                     // T = A Shat
+    CMat TS, TT;
+    MG_TRY(K.gram(T, R, TS));
+    MG_TRY(K.gram(T, T, TT));
+    zc ts(0.0, 0.0);
+    double tt = 0.0;
+    for (int j = 0; j < k; ++j) { ts += TS(j, j); tt += TT(j, j).real(); }
+    if (tt == 0.0) { flag = -2; break; }
+    const zc omega = ts / tt;                                     // tr(T^H S) / tr(T^H T)
+    MG_TRY(K.comb(X, X, one, Ph, alpha));                         // X += Phat alpha + omega Shat
+    MG_TRY(K.comb(X, X, one, Sh, sm_scaled_identity(k, omega)));
+    MG_TRY(K.comb(R, R, one, T, sm_scaled_identity(k, -omega)));  // R = S - omega T
+    MG_TRY(worst_rel(R, &err));
+    rep.record(err);
+    if (err <= tol) { flag = 0; break; }
+    if (omega == zc(0.0, 0.0)) { flag = -2; break; }
+    CMat RtT, beta;
+    MG_TRY(K.gram(R0, T, RtT));
+    if (!sm_solve(RtV, RtT, beta)) { flag = -2; break; }
+    for (zc& v : beta.a) v = -v;
+    MG_TRY(K.comb(P, P, one, V, sm_scaled_identity(k, -omega)));  // P - omega V
+    MG_TRY(K.comb(P, R, one, P, beta));                           // P = R + (P - omega V) beta
+  }
+  HIP_TRY(spin_sync(K.st));
+  return rep.finish(it, flag);
+}
+
+// the checks the block driver's entry points share; host form: column-major blocks relaid through the block work set's staging blocks
+int cx_block_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
+                    long long* iters, long long* flag, double* resvec, long long* nres, bool device_form) {
+  MG_TRY(cx_block_ready(h, n, nrhs, CX_ANY));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null block");
+  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
+  if (device_form) MG_TRY(cxv_aligned({b, x}));
+  (void)hipSetDevice(h->device);
+  const int nr = (int)nrhs;
+  MG_TRY(cx_block_ensure(h, nr));
+  CxState& S = *h->cx;
+  if (S.single && !S.K.set) MG_TRY(cx_widen_K(h));   // the Krylov product is never single
+  if (device_form) return cx_block_bicgstab_dev(h, ccx(b), mcx(x), nr, tol, maxIter, iters, flag, resvec, nres);
+  MG_TRY(cx_block_upload(h, b, S.Bstage_t, cxp(S.Bstage_b), n, nr));
+  MG_TRY(cx_block_upload(h, x, S.Bstage_t, cxp(S.Bstage_x), n, nr));
+  MG_TRY(cx_block_bicgstab_dev(h, cxc(S.Bstage_b), cxp(S.Bstage_x), nr, tol, maxIter, iters, flag, resvec, nres));
+  return cx_block_download(h, cxc(S.Bstage_x), S.Bstage_t, x, n, nr);
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -360,6 +541,45 @@ int mg_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long
   MG_TRY(cx_cycle<cx_t>(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle));
   HIP_TRY(hipMemcpyAsync(x_dev, L0.x[xi].p, bytes, hipMemcpyDeviceToDevice, h->play->stream));
   return MG_OK;
+}
+
+// One cycle on device blocks (row-major [n][nrhs] ComplexF64, 16-byte aligned), enqueued on the handle's stream without a
+// synchronisation.  A CF32 handle runs the mixed closure on the whole block, from zero.
+int mg_block_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs, long long x_is_zero) {
+  MG_TRY(cx_block_ready(h, n, nrhs, CX_ANY));
+  if (!b_dev || !x_dev) return fail(MG_ERR_INVALID, "null block");
+  if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for device blocks");
+  MG_TRY(cxv_aligned({b_dev, x_dev}));
+  if (h->cx->single && !x_is_zero)
+    return fail(MG_ERR_UNSUPPORTED, "mg_block_cycle_dev_CFP64 on a CF32 handle starts from zero (x_is_zero = 1): the mixed closure always zeroes z");
+  (void)hipSetDevice(h->device);
+  const int nr = (int)nrhs;
+  MG_TRY(cx_block_ensure(h, nr));
+  CxLevel& L0 = h->cx->lev[0];
+  const long long len = n * nr;
+  const size_t bytes = sizeof(cx_t) * (size_t)len;
+  int xi = 0;
+  if (h->cx->single) {
+    MG_TRY(cx_narrow(h, ccx(b_dev), cxp<cf_t>(L0.Bb), len));
+    MG_TRY(cx_cycle<cf_t>(h, 0, cxc<cf_t>(L0.Bb), xi, true, h->cycle, nr));
+    return cx_widen(h, cxc<cf_t>(L0.Bx[xi]), mcx(x_dev), len);
+  }
+  if (!x_is_zero) HIP_TRY(hipMemcpyAsync(L0.Bx[xi].p, x_dev, bytes, hipMemcpyDeviceToDevice, h->play->stream));
+  MG_TRY(cx_cycle<cx_t>(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle, nr));
+  HIP_TRY(hipMemcpyAsync(x_dev, L0.Bx[xi].p, bytes, hipMemcpyDeviceToDevice, h->play->stream));
+  return MG_OK;
+}
+
+// blockBiCGSTB on the whole block: b, x column-major n x nrhs on the host (mg_block_bicgstab_CFP64) or row-major [n][nrhs] device
+// blocks (_dev); x goes in and out; resvec holds up to 2*maxIter + 1 entries: max_j ||r_j|| / ||b_j|| at the start, after every
+// half step and after every full step.
+int mg_block_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
+                            long long* iters, long long* flag, double* resvec, long long* nres) {
+  return cx_block_krylov(h, b, x, n, nrhs, tol, maxIter, iters, flag, resvec, nres, false);
+}
+int mg_block_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs, double tol,
+                                long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  return cx_block_krylov(h, b_dev, x_dev, n, nrhs, tol, maxIter, iters, flag, resvec, nres, true);
 }
 
 int mg_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, double tol, long long maxIter,

@@ -4,7 +4,7 @@
 //   KrylovReport        where a driver writes iters / flag / resvec / nres, and its epilogue
 //   HessenbergLsq<S>    the Givens least squares of FGMRES(m), S = double or std::complex<double>
 //   pinv_sym, RelaxLsq  the normal-equations step of FGMRES_relaxation (Jac-GMRES smoother, K-cycle)
-//   SmallMat, sm_*      row-major dense helpers of the block drivers
+//   SmallMatT<S>, sm_*  row-major dense helpers of the block drivers, S = double (SmallMat) or std::complex<double>
 #pragma once
 
 #include <algorithm>
@@ -165,19 +165,24 @@ struct RelaxLsq {
 };
 
 // ---- dense helpers of the block drivers ---------------------------------------------------------------------------------------------
-struct SmallMat {   // row-major dense helper, host
+// (S = double: the real block drivers; S = std::complex<double>: the complex block BiCGSTAB of mg_complex_krylov.inc, which uses
+// sm_mul, sm_solve and sm_scaled_identity)
+template <class S>
+struct SmallMatT {   // row-major dense helper, host
   int r = 0, c = 0;
-  std::vector<double> a;
-  SmallMat() {}
-  SmallMat(int r_, int c_) : r(r_), c(c_), a((size_t)r_ * c_, 0.0) {}
-  double& operator()(int i, int j) { return a[(size_t)i * c + j]; }
-  double operator()(int i, int j) const { return a[(size_t)i * c + j]; }
+  std::vector<S> a;
+  SmallMatT() {}
+  SmallMatT(int r_, int c_) : r(r_), c(c_), a((size_t)r_ * c_, S(0.0)) {}
+  S& operator()(int i, int j) { return a[(size_t)i * c + j]; }
+  S operator()(int i, int j) const { return a[(size_t)i * c + j]; }
 };
-inline SmallMat sm_mul(const SmallMat& A, const SmallMat& B) {
-  SmallMat C(A.r, B.c);
+typedef SmallMatT<double> SmallMat;
+template <class S>
+inline SmallMatT<S> sm_mul(const SmallMatT<S>& A, const SmallMatT<S>& B) {
+  SmallMatT<S> C(A.r, B.c);
   for (int i = 0; i < A.r; ++i)
     for (int k = 0; k < A.c; ++k) {
-      const double v = A(i, k);
+      const S v = A(i, k);
       for (int j = 0; j < B.c; ++j) C(i, j) += v * B(k, j);
     }
   return C;
@@ -188,29 +193,30 @@ inline SmallMat sm_T(const SmallMat& A) {
     for (int j = 0; j < A.c; ++j) C(j, i) = A(i, j);
   return C;
 }
-// X = A \ B by Gaussian elimination with partial pivoting (A k x k); false if singular
-inline bool sm_solve(SmallMat A, SmallMat B, SmallMat& X) {
+// X = A \ B by Gaussian elimination with partial pivoting (A k x k; pivots by modulus); false if singular
+template <class S>
+inline bool sm_solve(SmallMatT<S> A, SmallMatT<S> B, SmallMatT<S>& X) {
   const int k = A.r;
   for (int p = 0; p < k; ++p) {
     int piv = p;
     for (int i = p + 1; i < k; ++i)
-      if (std::fabs(A(i, p)) > std::fabs(A(piv, p))) piv = i;
-    if (A(piv, p) == 0.0) return false;
+      if (krylov_abs(A(i, p)) > krylov_abs(A(piv, p))) piv = i;
+    if (A(piv, p) == S(0.0)) return false;
     if (piv != p) {
       for (int j = 0; j < k; ++j) std::swap(A(p, j), A(piv, j));
       for (int j = 0; j < B.c; ++j) std::swap(B(p, j), B(piv, j));
     }
     for (int i = p + 1; i < k; ++i) {
-      const double f = A(i, p) / A(p, p);
-      if (f == 0.0) continue;
+      const S f = A(i, p) / A(p, p);
+      if (f == S(0.0)) continue;
       for (int j = p; j < k; ++j) A(i, j) -= f * A(p, j);
       for (int j = 0; j < B.c; ++j) B(i, j) -= f * B(p, j);
     }
   }
-  X = SmallMat(k, B.c);
+  X = SmallMatT<S>(k, B.c);
   for (int j = 0; j < B.c; ++j)
     for (int i = k - 1; i >= 0; --i) {
-      double acc = B(i, j);
+      S acc = B(i, j);
       for (int t = i + 1; t < k; ++t) acc -= A(i, t) * X(t, j);
       X(i, j) = acc / A(i, i);
     }
@@ -287,8 +293,9 @@ inline double sm_lstsq(SmallMat H, SmallMat xi, SmallMat& Y) {
     for (int c = 0; c < k; ++c) res += xi(i, c) * xi(i, c);
   return std::sqrt(res);
 }
-inline SmallMat sm_scaled_identity(int k, double v) {
-  SmallMat I(k, k);
+template <class S>
+inline SmallMatT<S> sm_scaled_identity(int k, S v) {
+  SmallMatT<S> I(k, k);
   for (int i = 0; i < k; ++i) I(i, i) = v;
   return I;
 }

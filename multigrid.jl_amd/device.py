@@ -218,6 +218,12 @@ SIGNATURES = {
     "mg_fgmres_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_fgmres_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_cycle_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_block_spmv_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _dp, _dp, _dp, _ll]),
+    "mg_block_cycle_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_block_solve_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
+    "mg_block_cycle_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_block_bicgstab_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_block_bicgstab_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_create_CF32": (C.c_int, [_ll, _ll, _ll, C.POINTER(_vp)]),
     "mg_set_operator_CF32_INT64": (C.c_int, [_vp, _ll, _ll, _ll, _ll, _lp, _lp, _fp]),
     "mg_set_relax_CF32": (C.c_int, [_vp, _ll, _fp, _ll, _ll, _ll]),
@@ -912,7 +918,8 @@ def _c128(a):
 
 class ComplexDeviceHierarchy(DeviceHierarchy):
     """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F cycles, Jac / SPAI relaxation, dense-inverse or
-    sparse-LU coarsest solve, one right-hand side.  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
+    sparse-LU coarsest solve.  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*`` methods, which
+    take the column count with each call.  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
     conjugates back.  P and R are real."""
 
@@ -1162,6 +1169,104 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         pb, px = self._dev_pair(b, x)
         _check(self.lib, self.lib.mg_cycle_dev_CFP64(self.handle, pb, px, self.n, int(x_is_zero)), "mg_cycle_dev_CFP64")
 
+    # -- blocks of right-hand sides (mg_block_*): the column count travels with each call, the handle's own nrhs stays 1 --------
+    @staticmethod
+    def _blk(a, writable=False):
+        """A complex128 block (n x k; a vector counts as n x 1) as the Fortran-ordered array the host entry points take.
+        Returns (f, k): f is `a` itself when it is Fortran-contiguous, else a copy (written back by ``_blk_back``)."""
+        if not isinstance(a, np.ndarray) or a.dtype != np.complex128:
+            raise TypeError("expected a complex128 numpy array here (blocks of a ComplexF32 hierarchy are ComplexF64 too)")
+        a2 = a.reshape(-1, 1) if a.ndim == 1 else a
+        if a2.ndim != 2:
+            raise ValueError("a block is an n x k array")
+        if writable and not a.flags.writeable:
+            raise ValueError("X must be writable (it is updated in place)")
+        return np.asfortranarray(a2), int(a2.shape[1])
+
+    @staticmethod
+    def _blk_back(a, f):
+        if not np.shares_memory(a, f):
+            a[...] = f.reshape(a.shape)
+        return a
+
+    def block_spmv(self, level: int, which: int, alpha, X, beta, Y):
+        """``Y = beta*Y + alpha*Op*X`` on one level for n x k complex128 blocks (mg_block_spmv_CF64); Y in place."""
+        Xf, k = self._blk(X)
+        Yf, ky = self._blk(Y, True)
+        if ky != k:
+            raise ValueError("X and Y must hold the same number of columns")
+        a = np.array([complex(alpha).real, complex(alpha).imag])
+        bt = np.array([complex(beta).real, complex(beta).imag])
+        _check(self.lib, self.lib.mg_block_spmv_CF64(self.handle, int(level), int(which), _f64(a), _c128(Xf), _f64(bt), _c128(Yf), k),
+               "mg_block_spmv_CF64")
+        return self._blk_back(Y, Yf)
+
+    def block_cycle(self, B, X, x_is_zero: int = -1):
+        """One cycle on the whole n x k block (mg_block_cycle_CF64); X in place.  x_is_zero is a property of the whole block."""
+        Bf, k = self._blk(B)
+        Xf, kx = self._blk(X, True)
+        if kx != k:
+            raise ValueError("B and X must hold the same number of columns")
+        _check(self.lib, self.lib.mg_block_cycle_CF64(self.handle, _c128(Bf), _c128(Xf), Bf.shape[0], k, int(x_is_zero)), "mg_block_cycle_CF64")
+        return self._blk_back(X, Xf)
+
+    def block_solve(self, B, X, tol: float, maxIter: int):
+        """solveMG on the block with Frobenius norms (mg_block_solve_CF64); returns (X, iters, resvec)."""
+        Bf, k = self._blk(B)
+        Xf, kx = self._blk(X, True)
+        if kx != k:
+            raise ValueError("B and X must hold the same number of columns")
+        iters = C.c_longlong(0)
+        resvec = np.zeros(int(maxIter) + 1)
+        _check(self.lib, self.lib.mg_block_solve_CF64(self.handle, _c128(Bf), _c128(Xf), Bf.shape[0], k, float(tol), int(maxIter),
+                                                      C.byref(iters), _f64(resvec)), "mg_block_solve_CF64")
+        return self._blk_back(X, Xf), int(iters.value), resvec[: iters.value + 1]
+
+    def _dev_block(self, B, X):
+        """Addresses and column count of two torch.complex128 device blocks [n][k], row-major (contiguous)."""
+        for t in (B, X):
+            if not (hasattr(t, "dtype") and hasattr(t, "data_ptr")):
+                raise TypeError("expected torch.complex128 device tensors of shape [n, k]")
+            import torch
+            if t.dtype != torch.complex128:
+                raise TypeError("expected torch.complex128 tensors (the blocks of a ComplexF32 hierarchy are ComplexF64 too)")
+            if t.dim() != 2 or not t.is_contiguous() or t.shape[0] != self.n:
+                raise ValueError(f"device blocks are contiguous [n, k] tensors with n = {self.n} (row-major)")
+        if tuple(B.shape) != tuple(X.shape):
+            raise ValueError("B and X must have the same shape")
+        _sync_torch(B, X)
+        return _ptr(B), _ptr(X), int(B.shape[1])
+
+    def block_cycle_dev(self, B, X, x_is_zero: int):
+        """One cycle on torch.complex128 device blocks [n, k] (mg_block_cycle_dev_CFP64), enqueued on the library's stream without
+        a synchronisation.  On a ComplexF32 hierarchy: the mixed closure on the whole block, from zero."""
+        pb, px, k = self._dev_block(B, X)
+        _check(self.lib, self.lib.mg_block_cycle_dev_CFP64(self.handle, pb, px, self.n, k, int(x_is_zero)), "mg_block_cycle_dev_CFP64")
+
+    def _block_krylov_c(self, name, b, x, k, tol, maxIter):
+        res = np.zeros(2 * max(int(maxIter), 0) + 1)
+        iters, flag, count = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        fn = getattr(self.lib, f"mg_{name}_CFP64")
+        _check(self.lib, fn(self.handle, b, x, self.n, k, float(tol), int(maxIter), C.byref(iters), C.byref(flag), _f64(res), C.byref(count)),
+               f"mg_{name}_CFP64")
+        return int(flag.value), int(iters.value), res[: count.value]
+
+    def block_bicgstab(self, B, X, tol: float, maxIter: int):
+        """KrylovMethods.blockBiCGSTB on the Krylov operator with the block cycle as M1 (mg_block_bicgstab_CFP64); X in place;
+        returns (X, flag, iters, resvec)."""
+        Bf, k = self._blk(B)
+        Xf, kx = self._blk(X, True)
+        if kx != k or Bf.shape[0] != self.n or Xf.shape[0] != self.n:
+            raise ValueError(f"blocks of {self.n} x k complex values expected, the same k for B and X")
+        out = self._block_krylov_c("block_bicgstab", _c128(Bf), _c128(Xf), k, tol, maxIter)
+        return (self._blk_back(X, Xf),) + out
+
+    def block_bicgstab_dev_CFP64(self, B, X, tol: float, maxIter: int):
+        """The same on torch.complex128 device blocks [n, k]; returns (flag, iters, resvec).  (Named after its entry point:
+        ``block_bicgstab_dev`` is the FP64 hierarchies' method and stays refused here, as tests/test_complex_krylov_host.py pins.)"""
+        pb, px, k = self._dev_block(B, X)
+        return self._block_krylov_c("block_bicgstab_dev", pb, px, k, tol, maxIter)
+
     # -- replaceMatrixInHierarchy on the device (mg_rap_CF64 and the value replacements) ---------------------------------------
     def replace_values(self, level: int, which: int, M):
         """New values of one operator on its unchanged pattern: M.data complex (the applied A) for MG_OP_A, real for P and R."""
@@ -1221,8 +1326,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         return out
 
     def _refuse(self, *args, **kwargs):
-        raise NotImplementedError("PCG, the block Krylov drivers, transposeHierarchy and the other device-pointer entry points serve "
-                                  "FP64 hierarchies only (ComplexF64: bicgstab, fgmres, cycle_dev and their _dev forms; replace_matrix, "
+        raise NotImplementedError("PCG, block PCG / FGMRES, transposeHierarchy and the other device-pointer entry points serve "
+                                  "FP64 hierarchies only (ComplexF64: bicgstab, fgmres, cycle_dev and their _dev forms; block_spmv, "
+                                  "block_cycle, block_solve, block_cycle_dev, block_bicgstab, block_bicgstab_dev_CFP64; replace_matrix, "
                                   "replace_values, get_values)")
 
     pcg = cycle_mixed_f32 = pcg_dev = block_pcg_dev = block_bicgstab_dev = block_fgmres_dev = _refuse

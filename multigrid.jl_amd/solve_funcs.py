@@ -23,6 +23,17 @@ def _ncols(b):
     return 1 if b.ndim == 1 else int(b.shape[1])
 
 
+def _complex_block(param: MGparam, b) -> bool:
+    """A complex hierarchy given more than one column: the device's block entry points take the column count with each call and
+    the handle's own nrhs stays 1 (``adjustMemoryForNumRHS(param, 1)``)."""
+    return is_complex(param) and _ncols(b) > 1
+
+
+def _width(param: MGparam, b) -> int:
+    """The nrhs the handle is sized for: the block's columns, or 1 for a complex hierarchy (see ``_complex_block``)."""
+    return 1 if is_complex(param) else _ncols(b)
+
+
 def to_device(param: MGparam, device_id: int = 0) -> DeviceHierarchy:
     """Upload the hierarchy (lifecycle hook at the end of MGsetup/SA_AMGsetup, MGsetup.jl:135-137)."""
     if not hierarchyExists(param):
@@ -40,9 +51,12 @@ def to_device(param: MGparam, device_id: int = 0) -> DeviceHierarchy:
 
 def solveMG(param: MGparam, b: np.ndarray, x: np.ndarray, verbose: bool = False):
     """``(x, param, iter) = solveMG(param,b,x,verbose)``: x is updated IN PLACE (testGMG.jl:54-55)."""
-    adjustMemoryForNumRHS(param, _ncols(b))
+    adjustMemoryForNumRHS(param, _width(param, b))
     dev = to_device(param)
-    _, iters, resvec = dev.solve(b, x, param.relativeTol, param.maxOuterIter)
+    if _complex_block(param, b):                  # the residual norms are Frobenius norms of the block (SolveFuncs.jl:14-36)
+        _, iters, resvec = dev.block_solve(b, x, param.relativeTol, param.maxOuterIter)
+    else:
+        _, iters, resvec = dev.solve(b, x, param.relativeTol, param.maxOuterIter)
     param.resvec = resvec
     if verbose:
         for c in range(1, iters + 1):
@@ -54,8 +68,11 @@ def recursiveCycle(param: MGparam, b: np.ndarray, x: np.ndarray, level: int = 1)
     """One cycle from the finest level.  Only ``level == 1`` is an entry point of the device library."""
     if level != 1:
         raise ValueError("the device library owns the recursion: only level=1 can be entered from the host")
-    adjustMemoryForNumRHS(param, _ncols(b))
-    to_device(param).cycle(b, x, -1)
+    adjustMemoryForNumRHS(param, _width(param, b))
+    if _complex_block(param, b):
+        to_device(param).block_cycle(b, x, -1)
+    else:
+        to_device(param).cycle(b, x, -1)
     return x
 
 
@@ -63,8 +80,10 @@ def getMultigridPreconditioner(param: MGparam, B: np.ndarray, verbose: bool = Fa
     """``M(b) = (z .= 0; recursiveCycle(param,b,z,1); z)`` (SolveFuncs.jl:59): x = 0 on entry."""
     if not hierarchyExists(param):
         print("You have to do a setup first.")
-    adjustMemoryForNumRHS(param, _ncols(B))
+    adjustMemoryForNumRHS(param, _width(param, B))
     dev = to_device(param)
+    if _complex_block(param, B):
+        return _complex_block_preconditioner(param, dev, B)
     if B.dtype == np.float32:            # mixed precision (SolveFuncs.jl:52-58): bl .= b; cycle in Float64; z2 .= z
         z2 = np.zeros_like(B, order="F")
 
@@ -99,6 +118,34 @@ def getMultigridPreconditioner(param: MGparam, B: np.ndarray, verbose: bool = Fa
         return z
 
     return MMG
+
+
+def _complex_block_preconditioner(param: MGparam, dev, B: np.ndarray):
+    """getMultigridPreconditioner for a complex hierarchy and a block of more than one column: one cycle on the whole block from
+    zero.  A ComplexF32 hierarchy takes a complex128 block - the mixed closure (SolveFuncs.jl:52-58) on the whole block, run on
+    device blocks (narrowed, cycled and widened in HBM)."""
+    if B.dtype != np.complex128:
+        raise TypeError("getMultigridPreconditioner: blocks of a complex hierarchy are complex128 (ComplexF32 hierarchies: the mixed closure)")
+    z = np.zeros(B.shape, dtype=np.complex128, order="F")
+    if not is_single(param):
+
+        def MMGblock(b):
+            z[...] = 0.0
+            dev.block_cycle(np.asfortranarray(b, dtype=np.complex128), z, 1)
+            return z
+
+        return MMGblock
+    import torch
+
+    def MMGblockMixed(b):
+        bd = torch.from_numpy(np.ascontiguousarray(b, dtype=np.complex128)).to(f"cuda:{torch.cuda.current_device()}")   # row-major [n][k]
+        zd = torch.zeros_like(bd)
+        dev.block_cycle_dev(bd, zd, 1)
+        torch.cuda.synchronize()
+        z[...] = zd.cpu().numpy()
+        return z
+
+    return MMGblockMixed
 
 
 def solveCG_MG(A, param: MGparam, b: np.ndarray, x0: np.ndarray, verbose: bool = False):
@@ -191,12 +238,41 @@ def solveGMRES_MG_CFP64(A, param: MGparam, b: np.ndarray, x0: np.ndarray, flexib
     return x0, param, it, resvec
 
 
+def solveBlockBiCGSTAB_MG_CFP64(A, param: MGparam, B: np.ndarray, X0: np.ndarray, verbose: bool = False):
+    """``(X, param, iter, nprec) = solveBiCGSTAB_MG(Afun,param,B,X0,verbose)`` with ``size(B,2) > 1`` (SolveFuncs.jl:94-99) for
+    VAL = ComplexF64 / ComplexF32 on the device: KrylovMethods.blockBiCGSTB on the whole n x k block (k <= 16; one column is legal),
+    system operator ``A`` as for solveBiCGSTAB_MG_CFP64, one block cycle as M1.  X0 is updated in place;
+    ``nprec = 2*iter*k + (flag == -3)*k``."""
+    if not is_complex(param):
+        raise TypeError("solveBlockBiCGSTAB_MG_CFP64 serves VAL=ComplexF64 hierarchies; a Float64 hierarchy goes to solveBiCGSTAB_MG")
+    if _ncols(B) != _ncols(X0):
+        raise ValueError("B and X0 must hold the same number of columns")
+    adjustMemoryForNumRHS(param, 1)               # the block entry points take the column count with each call
+    dev = to_device(param)
+    if A is not None and param.As and A is param.As[0]:
+        A = None
+    if A is not dev.krylov_operator:
+        dev.update_krylov_operator(A)
+    k = _ncols(B)
+    _, flag, it, resvec = dev.block_bicgstab(B, X0, param.relativeTol, param.maxOuterIter)
+    param.resvec = resvec
+    param.flag = flag
+    if verbose:
+        for j, r in enumerate(resvec):
+            print(f"{j:3d}\t{r:1.2e}")
+    nprec = 2 * it * k + (flag == -3) * k                           # SolveFuncs.jl:97 as written
+    return X0, param, it, nprec
+
+
 _WHICH = {"A": MG_OP_A, "P": MG_OP_P, "R": MG_OP_R}
 
 
 def SpMatMul(param: MGparam, level: int, which: str, x: np.ndarray, target: np.ndarray,
              alpha: float = 1.0, beta: float = 0.0):
     """``target = beta*target + alpha*Op*x`` (SpMatMul.jl:4-13) with Op = As/Ps/Rs[level] resident on device."""
-    adjustMemoryForNumRHS(param, _ncols(x))
-    to_device(param).spmv(level, _WHICH[which], alpha, x, beta, target)
+    adjustMemoryForNumRHS(param, _width(param, x))
+    if _complex_block(param, x):
+        to_device(param).block_spmv(level, _WHICH[which], alpha, x, beta, target)
+    else:
+        to_device(param).spmv(level, _WHICH[which], alpha, x, beta, target)
     return target

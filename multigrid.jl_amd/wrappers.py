@@ -18,7 +18,7 @@ import scipy.sparse as sp
 from .mgdef import MGparam, clear_, copySolver as _copy_param, hierarchyExists, is_complex
 from .mgsetup import MGsetup, transposeHierarchy
 from .sa_amg import SA_AMGsetup
-from .solve_funcs import solveBiCGSTAB_MG, solveBiCGSTAB_MG_CFP64, solveCG_MG, solveGMRES_MG, solveGMRES_MG_CFP64, solveMG
+from .solve_funcs import solveBiCGSTAB_MG, solveBiCGSTAB_MG_CFP64, solveBlockBiCGSTAB_MG_CFP64, solveCG_MG, solveGMRES_MG, solveGMRES_MG_CFP64, solveMG
 
 
 @dataclass
@@ -88,7 +88,9 @@ def solveLinearSystem_(A, B: np.ndarray, X: np.ndarray, param: MGsolver, doTrans
     Bf = np.asfortranarray(B)
     cplx = is_complex(param.MG)          # ComplexF64 / ComplexF32: the device drivers of their own, on the hierarchy's fine level
     #                                      (ComplexF32: the Krylov method in double on As[1] widened, the single cycle as M)
-    if param.Krylov == "BiCGSTAB" and cplx:
+    if param.Krylov == "BiCGSTAB" and cplx and nrhs > 1:            # size(b,2) > 1: blockBiCGSTB (MGWrapper.jl:67-69)
+        _, _, num_iter, _ = solveBlockBiCGSTAB_MG_CFP64(param.MG.As[0], param.MG, Bf, Xv, verbose)
+    elif param.Krylov == "BiCGSTAB" and cplx:
         _, _, num_iter, _ = solveBiCGSTAB_MG_CFP64(param.MG.As[0], param.MG, Bf, Xv, verbose)
     elif param.Krylov == "GMRES" and cplx and param.kind != "SA":
         _, _, num_iter, _ = solveGMRES_MG_CFP64(param.MG.As[0], param.MG, Bf, Xv, True, 5, verbose)   # MGWrapper.jl:69-71
