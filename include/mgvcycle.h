@@ -798,7 +798,8 @@ int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count);
  *   no-op hint here), mg_profile_enable / _reset / _get (nothing is recorded), mg_last_error.  Every other FP64 entry point
  *   called with a CF64 handle fails with MG_ERR_STATE, and every CF64 entry point called with an FP64 handle fails with
  *   MG_ERR_STATE too; nothing is changed.
- * Refused with MG_ERR_UNSUPPORTED (and a mg_last_error message): cycle 'K', relaxType 1 (Jac-GMRES), the GMRES coarse solve
+ * Refused with MG_ERR_UNSUPPORTED (and a mg_last_error message): cycle 'K' and relaxType 1 (Jac-GMRES) through the shared setters
+ *   mg_set_cycle_type / mg_set_relax_type (a CF64 handle takes them through mg_set_schedule_CF64, below), the GMRES coarse solve
  *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries: a complex handle's own
  *   nrhs stays 1, and blocks of right-hand sides go through the mg_block_*_CF64 / _CFP64 entry points at the end of this header, which
  *   take nrhs with each call), the _FP64 Krylov drivers
@@ -862,6 +863,27 @@ mg_status mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n);
 mg_status mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
 mg_status mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n);
 mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz);
+
+/* ---- Jac-GMRES smoothing and the K-cycle on a CF64 handle (MGcycle.jl:35-50,72-76,96-98; FGMRES.jl:48-126) ------------------------
+ * mg_set_schedule_CF64 sets cycleType ('V', 'W', 'F' or 'K') and relaxType (0: Jac / SPAI, 1: Jac-GMRES) of a CF64 handle in one
+ * call and drops `finalized` (mg_finalize allocates Z / AZ of the relaxations the schedule needs).  Other letters or types:
+ * MG_ERR_INVALID; a CF32 handle: MG_ERR_UNSUPPORTED; an FP64 handle: MG_ERR_STATE.  The shared setters keep refusing 'K' and type 1.
+ * A relaxation is FGMRES_relaxation with the Jacobi preconditioner d: one kernel launch per direction (the product w = A z_j, the
+ * next direction d.*w and the partial sums of column j of H = (AZ)'(AZ) and of xi[j] = dot(w, r0) in one walk over the rows), one
+ * launch that sums all partials, ONE host synchronisation per relaxation; the host then replays the reference's loop on the leading
+ * blocks of H (break at the first residual estimate below 1e-5) and x += Z t is one more launch.  The K-cycle runs its two FGMRES
+ * steps with one synchronisation each.  Sums are deterministic (no atomics).  relaxPre / relaxPost above 8 with Jac-GMRES:
+ * mg_finalize fails with MG_ERR_UNSUPPORTED.  On such a handle mg_cycle_CF64, mg_solve_CF64 and the _CFP64 drivers work unchanged; the
+ * block entry points (mg_block_*_CF64 / _CFP64) return MG_ERR_UNSUPPORTED, and mg_rap_CF64 serves every schedule (it recomputes
+ * operators and relaxPrecs only).
+ * mg_fgmres_relax_CF64: one such relaxation on As[level] and relaxPrecs[level] with host vectors - the reference's exported
+ * FGMRES_relaxation with the diagonal preconditioner: x += Z t for the residual r0 (n complex values each; 1 <= level < nlevels,
+ * 1 <= inner <= 8, a finalized CF64 handle of any schedule).  H_out (inner x inner complex, row-major), xi_out (inner complex),
+ * rnorms_out (inner doubles; zero behind `used`) and used_out may be NULL; H and xi hold the summed Gram scalars of ALL inner
+ * directions, also those behind a break. */
+mg_status mg_set_schedule_CF64(mg_hierarchy* h, long long cycleType, long long relaxType);
+mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r0, double* x, long long n, long long inner,
+                               double tol, double* H_out, double* xi_out, double* rnorms_out, long long* used_out);
 
 /* ---- ComplexF64 Krylov drivers on a CF64 handle (suffix CFP64, the reference's own) ---------------------------------------
  * solveBiCGSTAB_MG / solveGMRES_MG (SolveFuncs.jl:85-133) for VAL = ComplexF64: KrylovMethods.bicgstb / fgmres with one cycle

@@ -13,6 +13,9 @@
 // per lane per complex value, coalesced), stages the products in LDS, and ONE lane per row sums its row's products
 // in stored order, then applies the fused epilogue.  Workgroups are banded per XCD (xcd_band).  A row longer than a
 // chunk has a block of its own and the whole workgroup strides over it.
+// Epilogues: AXPBY, RESID (optionally also z1 = d.*r), SMOOTH, and GRAM - one step of the FGMRES relaxation (Jac-GMRES smoothing,
+// K-cycle; ComplexF64 only): w = A z_j stored as column j of AZ, the next direction d.*w, and the per-row-block partial sums of
+// column j of H = (AZ)'(AZ) and of xi[j] = dot(w, r0), see CxVecArgsT.
 // Blocks of right-hand sides (row-major [n][nrhs]) run on the same row blocks: cx_csr_stream_spmm stages the matrix stream itself in
 // LDS and lets pow2 >= nrhs lanes per row walk it (below, behind the vector kernel).
 #pragma once
@@ -56,16 +59,34 @@ struct CxCsrDev {
   int n_rows;
 };
 
+// GRAM (cx_csr_stream_spmv only, ComplexF64): step j of FGMRES_relaxation (FGMRES.jl:82-104) in the walk that computes w = A z_j.
+// The mode follows mgk::Mode (AXPBY, RESID, SMOOTH) and is served by no other kernel.
+constexpr int GRAM = 3;
+constexpr int GRAM_MAXV = 8;                       // directions of one relaxation at most (mgcv::MAXV, the width of the combination pass)
+constexpr int GRAM_NS = 2 * GRAM_MAXV + 1;         // real scalars of a step at most: 2 j + 3 for j <= 7
+
 template <typename C>
 struct CxVecArgsT {
   const C* x;      // gathered vector  [n_cols]
-  C* y;            // output           [n_rows]
+  C* y;            // output           [n_rows]   (GRAM: w, column j of AZ)
   const C* b;      // RESID / SMOOTH   [n_rows]
-  const C* d;      // SMOOTH: relaxPrec [n_rows]
+  const C* d;      // SMOOTH: relaxPrec [n_rows]  (RESID with z1, GRAM with znext: the Jacobi preconditioner MM, MGcycle.jl:36-38)
   double* sumsq;   // optional: per-row-block sum of |out|^2 (summed by sum_final)
   C alpha;         // AXPBY
   C beta;          // AXPBY (beta == 0: y is not read)
   int beta_zero;
+  C* z1;           // RESID, optional: also d.*r, the first direction of the relaxation that follows
+  // GRAM: w = A z_j is stored (y), the next direction d.*w is stored (znext, optional), and every row block leaves the partial sums of
+  //   |w[row]|^2                      (H[j][j], real:    scalar 0)
+  //   conj(w[row]) r0[row]            (xi[j], complex:   scalars 1, 2)
+  //   conj(AZ_i[row]) w[row], i < j   (H[i][j], complex: scalars 3 + 2 i, 4 + 2 i)
+  // at gpart[c * nblocks + bid], c < 2 j + 3
+  const C* az;     // AZ, column-major: column i at az + i * ldz
+  const C* r0;
+  C* znext;
+  double* gpart;
+  long long ldz;
+  int gj;
 };
 typedef CxVecArgsT<d2_t> CxVecArgs;
 
@@ -74,6 +95,7 @@ template <int MODE, typename C>
 __device__ __forceinline__ C cx_epilogue(const CxVecArgsT<C>& v, C acc, C pb, C pd, C px) {
   if (MODE == AXPBY) return cmul(v.alpha, acc) + pb;
   if (MODE == RESID) return pb - acc;
+  if (MODE == GRAM) return acc;
   return px + cmul(pd, pb - acc);   // SMOOTH: x + d.*(b - A x)   (MGcycle.jl:129-131)
 }
 
@@ -81,6 +103,9 @@ template <int MODE, typename C>
 __device__ __forceinline__ void cx_operands(const CxVecArgsT<C>& v, int row, C& pb, C& pd, C& px) {
   if (MODE == AXPBY) {
     if (!v.beta_zero) pb = cmul(v.beta, v.y[row]);
+  } else if (MODE == GRAM) {
+    pb = v.r0[row];
+    if (v.znext) pd = v.d[row];
   } else {
     pb = v.b[row];
   }
@@ -88,6 +113,21 @@ __device__ __forceinline__ void cx_operands(const CxVecArgsT<C>& v, int row, C& 
     pd = v.d[row];
     px = v.x[row];
   }
+  if (MODE == RESID && v.z1) pd = v.d[row];
+}
+
+// the Gram scalars of one row: s[0 .. 2 j + 3) for w = (A z_j)[row], azv[i] = AZ_i[row], r0v = r0[row]
+template <typename C>
+__device__ __forceinline__ void cx_gram_row(double* s, int j, const C* azv, C w, C r0v) {
+  s[0] = cabs2(w);
+  s[1] = w.x * r0v.x + w.y * r0v.y;
+  s[2] = w.x * r0v.y - w.y * r0v.x;
+#pragma unroll
+  for (int i = 0; i < GRAM_MAXV - 1; ++i)
+    if (i < j) {
+      s[3 + 2 * i] = azv[i].x * w.x + azv[i].y * w.y;
+      s[4 + 2 * i] = azv[i].x * w.y - azv[i].y * w.x;
+    }
 }
 
 template <int MODE, typename PTR, typename VT, typename C>
@@ -95,7 +135,7 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
   typedef typename cx_scalar<C>::type T;
   __shared__ C prod[CX_CHUNK];
   __shared__ int srow[MAXROWS + 1];
-  __shared__ double red[2 * (BLK / 64)];
+  __shared__ double red[(MODE == GRAM ? GRAM_NS : 2) * (BLK / 64)];
 
   const int tid = threadIdx.x;
   const int bid = xcd_band(blockIdx.x, A.nblocks);
@@ -123,6 +163,21 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
       const C o = cx_epilogue<MODE>(v, s, pb, pd, px);
       v.y[r0] = o;
       if (v.sumsq) v.sumsq[bid] = cabs2(o);
+      if (MODE == RESID && v.z1) v.z1[r0] = cmul(pd, o);
+      if constexpr (MODE == GRAM) {   // the block's only row: its scalars are the block's partials
+        if (v.znext) v.znext[r0] = cmul(pd, o);
+        const int j = v.gj;
+        C azv[GRAM_MAXV - 1];
+#pragma unroll
+        for (int i = 0; i < GRAM_MAXV - 1; ++i) azv[i] = i < j ? v.az[(size_t)i * v.ldz + r0] : C{};
+        double gs[GRAM_NS];
+#pragma unroll
+        for (int c = 0; c < GRAM_NS; ++c) gs[c] = 0.0;
+        cx_gram_row(gs, j, azv, o, pb);
+#pragma unroll
+        for (int c = 0; c < GRAM_NS; ++c)
+          if (c < 2 * j + 3) v.gpart[(size_t)c * A.nblocks + bid] = gs[c];
+      }
     }
     return;
   }
@@ -146,6 +201,11 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
   const bool owner = tid < nrows;
   C pb = C{}, pd = pb, px = pb;
   if (owner) cx_operands<MODE>(v, r0 + tid, pb, pd, px);
+  C azv[MODE == GRAM ? GRAM_MAXV - 1 : 1];
+  if constexpr (MODE == GRAM) {   // the row's entries of the columns of AZ before j
+#pragma unroll
+    for (int i = 0; i < GRAM_MAXV - 1; ++i) azv[i] = (owner && i < v.gj) ? v.az[(size_t)i * v.ldz + r0 + tid] : C{};
+  }
   // ---- gather x and stage the products -----------------------------------------------------------
 #pragma unroll
   for (int it = 0; it < CX_ITEMS; ++it) {
@@ -161,6 +221,31 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
     for (int k = s; k < e; ++k) acc += prod[k];
     outv = cx_epilogue<MODE>(v, acc, pb, pd, px);
     v.y[r0 + tid] = outv;
+    if (MODE == RESID && v.z1) v.z1[r0 + tid] = cmul(pd, outv);
+    if (MODE == GRAM && v.znext) v.znext[r0 + tid] = cmul(pd, outv);
+  }
+  if constexpr (MODE == GRAM) {
+    // 2 j + 3 scalars: lane registers (a lane owns one row; the others add zeros), wavefront shuffles, the workgroup's LDS, one
+    // partial per scalar and row block - no atomics, the same bits on every run
+    const int j = v.gj, ns = 2 * j + 3;
+    double gs[GRAM_NS];
+#pragma unroll
+    for (int c = 0; c < GRAM_NS; ++c) gs[c] = 0.0;
+    cx_gram_row(gs, j, azv, outv, pb);   // (outv, pb and azv are zero in a lane without a row)
+#pragma unroll
+    for (int c = 0; c < GRAM_NS; ++c)
+      if (c < ns) {   // (uniform)
+        double t = gs[c];
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+        if ((tid & 63) == 0) red[c * (BLK / 64) + (tid >> 6)] = t;
+      }
+    __syncthreads();
+    if (tid < ns) {
+      double t = 0.0;
+      for (int w = 0; w < BLK / 64; ++w) t += red[tid * (BLK / 64) + w];
+      v.gpart[(size_t)tid * A.nblocks + bid] = t;
+    }
+    return;
   }
   if (v.sumsq) {   // ||r||^2 = sum |r_i|^2 (SolveFuncs.jl:30): a deterministic per-block partial, summed by sum_final
     double sq = cabs2(outv);
@@ -400,6 +485,23 @@ __global__ __launch_bounds__(BLK) void cx_sumsq_partial(const C* __restrict__ z,
   const long long stride = (long long)gridDim.x * BLK;
   double acc = 0.0;
   for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) acc += cabs2(z[i]);
+  const double s = block_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// z = d.*b with the partials of sum |b_i|^2, one per workgroup: the front of an FGMRES relaxation from x = 0 (r0 = b; z_1 = MM(r0),
+// rnorm0 = norm(r0), FGMRES.jl:65,84).  Grid-stride, so any grid covers n; the host launches one workgroup per row block of the
+// level's operator, which is the stride of the relaxation's partial sums.
+__global__ __launch_bounds__(BLK) void cx_dscale_sumsq(const d2_t* __restrict__ d, const d2_t* __restrict__ b, d2_t* __restrict__ z, long long n,
+                                                       double* __restrict__ partial) {
+  __shared__ double red[BLK / 64];
+  const long long stride = (long long)gridDim.x * BLK;
+  double acc = 0.0;
+  for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) {
+    const d2_t bv = b[i];
+    z[i] = cmul(d[i], bv);
+    acc += cabs2(bv);
+  }
   const double s = block_sum(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }

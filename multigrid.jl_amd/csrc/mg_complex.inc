@@ -1,6 +1,6 @@
 // mg_complex.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
-// ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F cycles,
-// pointwise relaxation, dense-inverse or sparse-LU coarsest solve.  The state lives apart from the real levels (CxState);
+// ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F / K cycles,
+// pointwise or Jac-GMRES relaxation (K and Jac-GMRES: CF64 handles, one right-hand side), dense-inverse or sparse-LU coarsest solve.  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
 // The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
 // ComplexF32 / Int64 hierarchies (the _CF32 entry points; the reference's VAL = ComplexF32, singlePrecision) share all of it: the
@@ -52,6 +52,9 @@ struct CxLevel {
   long long npre = 0, npost = 0, n = 0;
   DevBuf<double> b, r, x[2];   // complex scratch (CYCLEmem, MGdef.jl:56-60); x ping-pongs between the sweeps
   DevBuf<double> Bb, Br, Bx[2];   // the same for the block entry points (mg_block_*): row-major [n][blk_cap], see CxState::blk_cap
+  // FGMRES_relaxation's Z and AZ (FGMRESmem, FGMRES.jl:1-30), column-major, allocated by mg_finalize only when the schedule needs them:
+  DevBuf<double> relaxZ, relaxAZ;   // Jac-GMRES smoothing on this level: max(npre, npost) columns (memRelax)
+  DevBuf<double> kZ, kAZ;           // the K-cycle's two FGMRES steps ON this level (levels 2 .. nl-1): 2 columns (memKcycle of the level above)
 };
 
 struct CxState {
@@ -69,6 +72,12 @@ struct CxState {
   DevBuf<double> luLval, luUval, luWork;
   int nLlvl = 0, nUlvl = 0;
   DevBuf<double> stage_b, partial;   // the fine right-hand side; per-row-block partials of ||r||^2
+  // The FGMRES relaxation's own partials and scalars (Jac-GMRES smoothing, K-cycle; cx_fgmres_relax): it runs inside the Krylov drivers,
+  // whose kpart / kscal must survive a cycle.  Scalar 0: ||r0||^2; step j: the 2 j + 3 scalars of its GRAM launch from 1 + j^2 + 2 j on,
+  // so `inner` steps fill (inner + 1)^2 scalars; gpart holds one partial per scalar and row block (gpart[c * nblocks + block]).
+  static constexpr int GSCAL = (mgk::GRAM_MAXV + 1) * (mgk::GRAM_MAXV + 1);
+  DevBuf<double> gpart, gscal;
+  double* h_gscal = nullptr;         // pinned
   // the Krylov drivers (mg_complex_krylov.inc): their system operator (unset: As[1]), work vectors, the partials and scalars of
   // the fused passes with the scalars' pinned readback, the iterate of the host-pointer forms
   static constexpr size_t KSCAL = 136;   // 2 * (64 + 2) doubles of an FGMRES(64) inner step, rounded up
@@ -92,7 +101,10 @@ struct CxState {
       L.A.release(); L.P.release(); L.R.release();
       L.d.release(); L.b.release(); L.r.release(); L.x[0].release(); L.x[1].release();
       L.Bb.release(); L.Br.release(); L.Bx[0].release(); L.Bx[1].release();
+      L.relaxZ.release(); L.relaxAZ.release(); L.kZ.release(); L.kAZ.release();
     }
+    gpart.release(); gscal.release();
+    if (h_gscal) (void)hipHostFree(h_gscal);
     for (DevBuf<double>* d : {&Bcw_b, &Bcw_x, &BluWork, &Bstage_b, &Bstage_x, &Bstage_t, &Bkwork, &Bgpart, &Bcoef}) d->release();
     if (h_bgram) (void)hipHostFree(h_bgram);
     if (h_bcoef) (void)hipHostFree(h_bcoef);
@@ -275,14 +287,16 @@ void cx_launch(mg_hierarchy* h, const CxMat& M, const PTR* rowptr, const mgk::Cx
 template <int MODE, typename C>
 int cx_spmv(mg_hierarchy* h, const CxMat& M, const C* x, typename cx_non_deduced<C>::type* y, const typename cx_non_deduced<C>::type* b,
             const typename cx_non_deduced<C>::type* d, double* sumsq, typename cx_non_deduced<C>::type alpha = C{1, 0},
-            typename cx_non_deduced<C>::type beta = C{0, 0}, int nr = 0) {
+            typename cx_non_deduced<C>::type beta = C{0, 0}, int nr = 0, typename cx_non_deduced<C>::type* z1 = nullptr) {
   typedef typename mgk::cx_scalar<C>::type T;
   if (M.single != (sizeof(T) == sizeof(float))) return fail(MG_ERR_INVALID, "internal: operator and vectors differ in precision");
   if (nr < 0 || nr > mgk::BLK_KMAX) return fail(MG_ERR_INVALID, "internal: a block of %d columns", nr);
-  mgk::CxVecArgsT<C> v;
+  mgk::CxVecArgsT<C> v = {};
   v.x = x; v.y = y; v.b = b; v.d = d; v.sumsq = sumsq;
   v.alpha = alpha; v.beta = beta;
   v.beta_zero = (beta.x == 0 && beta.y == 0) ? 1 : 0;
+  if (z1 && (MODE != mgk::RESID || nr != 0 || !d)) return fail(MG_ERR_INVALID, "internal: z1 = d.*r comes out of the vector residual only");
+  v.z1 = z1;
   if (M.cplx) {
     if (M.wide) cx_launch<MODE, long long, C, C>(h, M, M.rowptr64.p, v, nr);
     else cx_launch<MODE, int, C, C>(h, M, M.rowptr.p, v, nr);
@@ -406,6 +420,137 @@ int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long 
   return MG_OK;
 }
 
+// ---- FGMRES_relaxation (FGMRES.jl:48-126) for VAL = ComplexF64: Jac-GMRES smoothing and the K-cycle -----------------------------------
+// One launch per direction (the GRAM epilogue of cx_csr_stream_spmv: w = A z_j, z_{j+1} = d.*w, the partials of column j of H and of
+// xi[j]), one final sum over all scalars of the steps enqueued so far, one readback, ONE host synchronisation; the small least squares
+// is host algebra (RelaxLsqC, mg_krylov_host.hpp).
+static_assert(mgk::GRAM_MAXV == mgcv::MAXV, "the combination pass x += Z t takes all directions of a relaxation at once");
+inline int cx_gram_slot(int j) { return 1 + j * j + 2 * j; }
+
+// the relaxation's partials, scalars and pinned readback, for operators of up to `nblocks` row blocks
+int cx_gram_ensure(mg_hierarchy* h, size_t nblocks) {
+  CxState& S = *h->cx;
+  const size_t need = std::max((size_t)CxState::GSCAL * nblocks, (size_t)mgcv::MAXS * mgcv::MAXB);
+  if (S.gpart.n < need) {
+    if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+    MG_TRY(S.gpart.alloc(need));
+  }
+  if (S.gscal.n == 0) MG_TRY(S.gscal.alloc((size_t)CxState::GSCAL));
+  if (!S.h_gscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_gscal), sizeof(double) * CxState::GSCAL));
+  return MG_OK;
+}
+
+// step j: w = A z into column j of AZ, znext = d.*w (null: the last direction, or a preconditioner that is a cycle)
+int cx_gram_step(mg_hierarchy* h, const CxLevel& L, const cx_t* z, cx_t* AZ, int j, const cx_t* r0, cx_t* znext) {
+  CxState& S = *h->cx;
+  const CxMat& M = L.A;
+  if (j < 0 || j >= mgk::GRAM_MAXV) return fail(MG_ERR_INVALID, "internal: direction %d of an FGMRES relaxation", j);
+  if (S.gpart.n < (size_t)CxState::GSCAL * (size_t)M.nblocks) return fail(MG_ERR_STATE, "internal: the relaxation's partial sums are not sized");
+  mgk::CxVecArgsT<cx_t> v = {};
+  v.x = z;
+  v.y = AZ + (size_t)j * (size_t)L.n;
+  v.d = cxc(L.d);
+  v.beta_zero = 1;
+  v.az = AZ;
+  v.ldz = L.n;
+  v.gj = j;
+  v.r0 = r0;
+  v.znext = znext;
+  v.gpart = S.gpart.p + (size_t)cx_gram_slot(j) * (size_t)M.nblocks;
+  if (M.wide) {
+    mgk::CxCsrDev<long long, cx_t> D;
+    D.rowptr = M.rowptr64.p; D.colidx = M.colidx.p; D.val = static_cast<const cx_t*>(M.vals()); D.blk_row = M.blk_row.p;
+    D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
+    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, long long, cx_t, cx_t>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+  } else {
+    mgk::CxCsrDev<int, cx_t> D;
+    D.rowptr = M.rowptr.p; D.colidx = M.colidx.p; D.val = static_cast<const cx_t*>(M.vals()); D.blk_row = M.blk_row.p;
+    D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
+    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, int, cx_t, cx_t>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+  }
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// the sums of the scalars [first, first + count) on the host: one final launch (a workgroup per scalar), one copy, one synchronisation
+int cx_gram_read(mg_hierarchy* h, int first, int count, int nblocks, const double** out) {
+  CxState& S = *h->cx;
+  const hipStream_t st = h->play->stream;
+  hipLaunchKernelGGL(mgkv::krv_final, dim3((unsigned)count), dim3(mgkv::KB), 0, st, S.gpart.p + (size_t)first * (size_t)nblocks, nblocks,
+                     S.gscal.p + first);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(S.h_gscal + first, S.gscal.p + first, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
+  HIP_TRY(spin_sync(st));
+  *out = S.h_gscal;
+  return MG_OK;
+}
+
+// column j of H and xi[j] from the summed scalars of step j
+inline void cx_gram_fill(RelaxLsqC& Q, int j, const double* s) {
+  const double* g = s + cx_gram_slot(j);
+  Q.set(j, j, std::complex<double>(g[0], 0.0));
+  Q.xi[(size_t)j] = std::complex<double>(g[1], g[2]);
+  for (int i = 0; i < j; ++i) Q.set(i, j, std::complex<double>(g[3 + 2 * i], g[4 + 2 * i]));
+}
+
+// x += sum_{j < used} t_j Z_j in one pass (mgcv::OpCGsUpdate with h = -t; its ||x||^2 partial lands in the relaxation's own buffer, unread)
+int cx_relax_combine(mg_hierarchy* h, const RelaxLsqC& Q, int used, const cx_t* Z, cx_t* x, long long n) {
+  mgcv::OpCGsUpdate op;
+  op.m = used;
+  op.w = x;
+  for (int j = 0; j < mgcv::MAXV; ++j) {
+    const int jj = j < used ? j : 0;
+    op.h[j] = j < used ? cx_t{-Q.t()[(size_t)j].real(), -Q.t()[(size_t)j].imag()} : cx_t{0.0, 0.0};
+    op.v[j] = Z + (size_t)jj * (size_t)n;
+  }
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(mgcv::cxv_pass<mgcv::OpCGsUpdate>), dim3((unsigned)mgcv::cxv_grid(n)), dim3(mgcv::KB), 0, h->play->stream, op, n,
+                     h->cx->gpart.p);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// what a caller may ask back of one relaxation (mg_fgmres_relax_CF64)
+struct CxRelaxReport {
+  RelaxLsqC* Q = nullptr;
+  double* rnorms = nullptr;   // `inner` entries; those behind `used` stay untouched
+  int used = 0;
+};
+
+// FGMRES_relaxation with the diagonal preconditioner on L.A: x += Z t.  On entry column 0 of Z holds z_1 = d.*r0 and the partials of
+// ||r0||^2 sit in scalar 0 (both left by the residual in front, or by cx_relax_front_zero when r0 = b).  All `inner` GRAM steps are
+// enqueued back to back - step j + 1 needs w_j only, never t - and the host replays the reference's loop on the leading blocks of H:
+// at step j the (j+1) x (j+1) solve, break at the first rn < tol (FGMRES.jl:114-117), used = j + 1.  Directions beyond `used` are
+// not read (the reference's zero-padded H gives the same t).
+int cx_fgmres_relax(mg_hierarchy* h, const CxLevel& L, const cx_t* r0, cx_t* x, int inner, double tol, cx_t* Z, cx_t* AZ,
+                    CxRelaxReport* report = nullptr) {
+  if (inner <= 0) return MG_OK;   // w = Z*t with no columns: x unchanged (FGMRES.jl:119-123)
+  if (inner > mgk::GRAM_MAXV) return fail(MG_ERR_UNSUPPORTED, "an FGMRES relaxation of %d directions (at most %d)", inner, mgk::GRAM_MAXV);
+  const size_t n = (size_t)L.n;
+  for (int j = 0; j < inner; ++j) MG_TRY(cx_gram_step(h, L, Z + (size_t)j * n, AZ, j, r0, j + 1 < inner ? Z + (size_t)(j + 1) * n : nullptr));
+  const double* s = nullptr;
+  MG_TRY(cx_gram_read(h, 0, (inner + 1) * (inner + 1), L.A.nblocks, &s));
+  const double rnorm0 = std::sqrt(s[0]);
+  RelaxLsqC local(inner);
+  RelaxLsqC& Q = (report && report->Q) ? *report->Q : local;
+  int used = 0;
+  for (int j = 0; j < inner; ++j) {
+    cx_gram_fill(Q, j, s);
+    const double rn = Q.step(j + 1, rnorm0);
+    used = j + 1;
+    if (report && report->rnorms) report->rnorms[j] = rn;
+    if (rn < tol) break;
+  }
+  if (report) report->used = used;
+  return cx_relax_combine(h, Q, used, Z, x, L.n);
+}
+
+// z_1 = d.*b with the partials of ||b||^2 (scalar 0): the front of a relaxation from x = 0, where r0 = b
+int cx_relax_front_zero(mg_hierarchy* h, const CxLevel& L, const cx_t* b, cx_t* Z) {
+  hipLaunchKernelGGL(mgk::cx_dscale_sumsq, dim3((unsigned)L.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, cxc(L.d), b, Z, L.n, h->cx->gpart.p);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
 // recursiveCycle (MGcycle.jl:1-118) from level l (0-based) on b; the iterate is lev[l].x[xi] (zero on entry when xzero).
 // C = cx_t on a CF64 handle, cf_t on a CF32 one: the same recursion on the same buffers.
 // nr columns (0: a vector on the handle's own level vectors; >= 1: row-major blocks on the block work set, xzero a property of the
@@ -417,7 +562,25 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   CxLevel& L = S.lev[(size_t)l];
   const C one = C{1, 0}, zero = C{0, 0};
   if (l == nl - 1) return cx_coarse(h, b, cxp<C>(cx_lx(L, nr, xi)), xzero, nr);                 // l.13-18
-  MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre, nr));                                    // l.26-31, 54
+  constexpr bool is64 = sizeof(typename mgk::cx_scalar<C>::type) == sizeof(double);
+  const bool gmres_relax = h->relax_type == 1;   // Jac-GMRES (MGcycle.jl:35-38, 48-50, 96-98)
+  const double gmresTol = 1e-5;                  // l.5
+  if ((gmres_relax || ctype == 'K') && (!is64 || nr != 0))
+    return fail(MG_ERR_UNSUPPORTED, "Jac-GMRES smoothing and the K-cycle serve CF64 handles and one right-hand side");
+  if (gmres_relax) {
+    if constexpr (is64) {
+      // r = b - A x (l.28-31) with ||r||^2 and z_1 = d.*r from the same pass; from x = 0, r0 = b
+      cx_t* x = cxp(L.x[xi]);
+      if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(cx_t) * (size_t)L.n, h->play->stream));
+      if (L.npre > 0) {
+        if (xzero) MG_TRY(cx_relax_front_zero(h, L, b, cxp(L.relaxZ)));
+        else MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const cx_t*)x, cxp(L.r), b, cxc(L.d), S.gpart.p, one, zero, 0, cxp(L.relaxZ)));
+        MG_TRY(cx_fgmres_relax(h, L, xzero ? b : cxc(L.r), x, (int)L.npre, gmresTol, cxp(L.relaxZ), cxp(L.relaxAZ)));
+      }
+    }
+  } else {
+    MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre, nr));                                  // l.26-31, 54
+  }
   MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxc<C>(cx_lx(L, nr, xi)), cxp<C>(cx_lr(L, nr)), b, nullptr, nullptr, one, zero, nr));  // l.58-60
   CxLevel& C1 = S.lev[(size_t)l + 1];
   const C* bc = cxc<C>(cx_lb(C1, nr));
@@ -425,6 +588,37 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   int ci = 0;
   if (l + 1 == nl - 1) {
     MG_TRY(cx_coarse(h, bc, cxp<C>(cx_lx(C1, nr, ci)), true, nr));                         // l.67-69
+  } else if (ctype == 'K') {
+    // K-cycle (l.72-76): two FGMRES steps on A_{l+1} xc = bc from xc = 0, preconditioned by the K-cycle of level l+1 from zero.  Each
+    // step: one inner cycle, its result copied into Z, one GRAM launch (no znext: the preconditioner is a cycle), one synchronisation -
+    // so the break after step 1 costs no speculative sub-cycle.
+    if constexpr (is64) {
+      const size_t n1 = (size_t)C1.n;
+      cx_t *Z = cxp(C1.kZ), *AZ = cxp(C1.kAZ);
+      RelaxLsqC Q(2);
+      double rnorm0 = 0.0;
+      int used = 0;
+      for (int j = 0; j < 2; ++j) {
+        int cj = 0;
+        MG_TRY(cx_cycle<C>(h, l + 1, j == 0 ? bc : (const cx_t*)AZ, cj, true, 'K', 0));      // z = MMG(r0) / MMG(w)  (FGMRES.jl:83-87)
+        HIP_TRY(hipMemcpyAsync(Z + (size_t)j * n1, C1.x[cj].p, sizeof(cx_t) * n1, hipMemcpyDeviceToDevice, h->play->stream));
+        if (j == 0) {                                                                         // rnorm0 = norm(r0)  (l.65)
+          hipLaunchKernelGGL(mgk::cx_sumsq_partial<cx_t>, dim3((unsigned)C1.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, bc, C1.n, S.gpart.p);
+          HIP_TRY(hipGetLastError());
+        }
+        MG_TRY(cx_gram_step(h, C1, Z + (size_t)j * n1, AZ, j, bc, nullptr));
+        const double* s = nullptr;
+        MG_TRY(cx_gram_read(h, j == 0 ? 0 : cx_gram_slot(1), j == 0 ? cx_gram_slot(1) : 5, C1.A.nblocks, &s));
+        if (j == 0) rnorm0 = std::sqrt(s[0]);
+        cx_gram_fill(Q, j, s);
+        const double rn = Q.step(j + 1, rnorm0);
+        used = j + 1;
+        if (rn < gmresTol) break;                                                             // l.114-117
+      }
+      ci = 0;                                                                                 // xc = 0 + Z t  (l.121-123)
+      HIP_TRY(hipMemsetAsync(C1.x[ci].p, 0, sizeof(cx_t) * n1, h->play->stream));
+      MG_TRY(cx_relax_combine(h, Q, used, Z, cxp(C1.x[ci]), C1.n));
+    }
   } else {
     MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, true, ctype, nr));                                // xc = 0 (l.63-64), l.78
     if (ctype == 'W') MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, false, 'W', nr));               // l.79-80
@@ -432,6 +626,16 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   }
   // x += P xc (l.90): in place, the gather reads xc only
   MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(cx_lx(C1, nr, ci)), cxp<C>(cx_lx(L, nr, xi)), nullptr, nullptr, nullptr, one, one, nr));
+  if (gmres_relax) {                                                                      // r = b - A x, FGMRES_relaxation (l.92-98)
+    if constexpr (is64) {
+      if (L.npost > 0) {
+        cx_t* x = cxp(L.x[xi]);
+        MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const cx_t*)x, cxp(L.r), b, cxc(L.d), S.gpart.p, one, zero, 0, cxp(L.relaxZ)));
+        MG_TRY(cx_fgmres_relax(h, L, cxc(L.r), x, (int)L.npost, gmresTol, cxp(L.relaxZ), cxp(L.relaxAZ)));
+      }
+    }
+    return MG_OK;
+  }
   return cx_relax<C>(h, L, b, xi, false, L.npost, nr);                                   // r = b - A x, relax (l.92-102)
 }
 
@@ -443,6 +647,12 @@ int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want = C
   return MG_OK;
 }
 
+// The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51); that form is not built here.
+int cx_block_schedule_ok(mg_hierarchy* h) {
+  if (h->cycle == 'K' || h->relax_type == 1)
+    return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy");
+  return MG_OK;
+}
 int cx_block_nrhs_ok(long long nrhs) {
   if (nrhs < 1) return fail(MG_ERR_INVALID, "nrhs=%lld: a block holds at least one right-hand side", nrhs);
   if (nrhs > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "complex blocks hold at most %d right-hand sides (nrhs=%lld)", mgk::BLK_KMAX, nrhs);
@@ -453,6 +663,7 @@ int cx_block_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want) {
   MG_TRY(cx_handle_ok(h, want));
   if (!h->cx->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
   MG_TRY(cx_block_nrhs_ok(nrhs));
+  MG_TRY(cx_block_schedule_ok(h));
   if (n != h->cx->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->cx->lev[0].n);
   if (h->coarse_dd && nrhs > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%lld)", nrhs);
   return MG_OK;
@@ -500,8 +711,9 @@ int cx_finalize(mg_hierarchy* h) {
     S.K.release();
     S.K_auto = false;
   }
-  if (h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF64 / CF32 handles");
-  if (h->relax_type != 0) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF64 handles");
+  if (S.single && h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF32 handles");
+  if (S.single && h->relax_type != 0) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF32 handles");
+  if (h->relax_type != 0 && h->relax_type != 1) return fail(MG_ERR_UNSUPPORTED, "relaxation type %d is not served for complex handles", h->relax_type);
   size_t maxblocks = 1;
   for (int l = 0; l < nl; ++l) {
     CxLevel& L = S.lev[(size_t)l];
@@ -548,6 +760,25 @@ int cx_finalize(mg_hierarchy* h) {
     if (S.cw_x.n != nc) MG_TRY(S.cw_x.alloc(nc));
   }
   if (S.coarse_lu && !S.coarse_multi && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
+  // FGMRESmem of the schedule (MGsetup.jl:186-214): memRelax for Jac-GMRES, memKcycle for the K-cycle; dropped when the schedule left them
+  const bool gmres_relax = h->relax_type == 1, kcycle = h->cycle == 'K';
+  for (int l = 0; l < nl; ++l) {
+    CxLevel& L = S.lev[(size_t)l];
+    const long long m = (gmres_relax && l < nl - 1) ? std::max(L.npre, L.npost) : 0;
+    if (m > mgk::GRAM_MAXV)
+      return fail(MG_ERR_UNSUPPORTED, "relaxPre / relaxPost = %lld on level %d: a complex Jac-GMRES relaxation takes at most %d directions", m, l + 1,
+                  mgk::GRAM_MAXV);
+    const size_t zlen = 2 * (size_t)m * (size_t)L.n, klen = (kcycle && l >= 1 && l < nl - 1) ? 4 * (size_t)L.n : 0;
+    for (DevBuf<double>* d : {&L.relaxZ, &L.relaxAZ}) {
+      if (zlen == 0) d->release();
+      else if (d->n != zlen) MG_TRY(d->alloc(zlen));
+    }
+    for (DevBuf<double>* d : {&L.kZ, &L.kAZ}) {
+      if (klen == 0) d->release();
+      else if (d->n != klen) MG_TRY(d->alloc(klen));
+    }
+  }
+  if (gmres_relax || kcycle) MG_TRY(cx_gram_ensure(h, maxblocks));
   S.finalized = true;
   return MG_OK;
 }
@@ -1041,6 +1272,7 @@ int cx_block_spmv_host(mg_hierarchy* h, long long level, long long which, const 
   CxState& S = *h->cx;
   if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   MG_TRY(cx_block_nrhs_ok(nrhs));
+  MG_TRY(cx_block_schedule_ok(h));
   if (!alpha || !beta || !X || !Y) return fail(MG_ERR_INVALID, "null argument");
   if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
   CxLevel& L = S.lev[(size_t)level - 1];
@@ -1150,6 +1382,73 @@ int mg_set_relax_CF64(mg_hierarchy* h, long long level, const double* d, long lo
   L.npre = relaxPre;
   L.npost = relaxPost;
   h->cx->finalized = false;
+  return MG_OK;
+}
+
+// cycleType and relaxType of a CF64 handle in one call: the K-cycle and Jac-GMRES smoothing arrive here (the shared setters
+// mg_set_cycle_type / mg_set_relax_type keep refusing them on complex handles)
+int mg_set_schedule_CF64(mg_hierarchy* h, long long cycleType, long long relaxType) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+  MG_CF32_UNSUPPORTED(h);
+  if (cycleType != 'V' && cycleType != 'W' && cycleType != 'F' && cycleType != 'K')
+    return fail(MG_ERR_INVALID, "cycleType must be 'V', 'W', 'F' or 'K'");
+  if (relaxType != 0 && relaxType != 1) return fail(MG_ERR_INVALID, "relaxType must be 0 (Jac / SPAI) or 1 (Jac-GMRES) on a CF64 handle");
+  h->cycle = (char)cycleType;
+  h->relax_type = (int)relaxType;
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
+// FGMRES_relaxation with the diagonal preconditioner on one level, host vectors: x += Z t
+int mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r0, double* x, long long n, long long inner, double tol,
+                         double* H_out, double* xi_out, double* rnorms_out, long long* used_out) {
+  MG_TRY(cx_level_ok(h, level));
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  if (level >= h->nlevels) return fail(MG_ERR_INVALID, "level %lld holds no relaxPrecs (the coarsest level is solved, not relaxed)", level);
+  if (inner < 1 || inner > mgk::GRAM_MAXV) return fail(MG_ERR_INVALID, "inner=%lld outside 1..%d", inner, mgk::GRAM_MAXV);
+  if (!r0 || !x) return fail(MG_ERR_INVALID, "null vector");
+  CxLevel& L = S.lev[(size_t)level - 1];
+  if (n != L.n) return fail(MG_ERR_INVALID, "n=%lld does not match level %lld (%lld rows)", n, level, L.n);
+  (void)hipSetDevice(h->device);
+  MG_TRY(cx_gram_ensure(h, (size_t)L.A.nblocks));
+  const hipStream_t st = h->play->stream;
+  const int k = (int)inner;
+  const size_t bytes = sizeof(cx_t) * (size_t)n;
+  DevBuf<double> dr, dx, dZ, dAZ;   // (released below on every path)
+  RelaxLsqC Q(k);
+  std::vector<double> rn((size_t)k, 0.0);
+  CxRelaxReport report;
+  report.Q = &Q;
+  report.rnorms = rn.data();
+  int rc = dr.alloc(2 * (size_t)n);
+  if (rc == MG_OK) rc = dx.alloc(2 * (size_t)n);
+  if (rc == MG_OK) rc = dZ.alloc(2 * (size_t)n * (size_t)k);
+  if (rc == MG_OK) rc = dAZ.alloc(2 * (size_t)n * (size_t)k);
+  if (rc == MG_OK && (hipMemcpyAsync(dr.p, r0, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+                      hipMemcpyAsync(dx.p, x, bytes, hipMemcpyHostToDevice, st) != hipSuccess))
+    rc = fail(MG_ERR_HIP, "upload of r0 / x failed");
+  if (rc == MG_OK) rc = cx_relax_front_zero(h, L, cxc(dr), cxp(dZ));
+  if (rc == MG_OK) rc = cx_fgmres_relax(h, L, cxc(dr), cxp(dx), k, tol, cxp(dZ), cxp(dAZ), &report);
+  if (rc == MG_OK && hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MG_ERR_HIP, "download of x failed");
+  if (spin_sync(st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_fgmres_relax_CF64: stream failed");
+  dr.release(); dx.release(); dZ.release(); dAZ.release();
+  if (rc != MG_OK) return rc;
+  for (int j = report.used; j < k; ++j) cx_gram_fill(Q, j, S.h_gscal);   // (the directions behind a break: summed, not used)
+  if (H_out)
+    for (int a = 0; a < k * k; ++a) {
+      H_out[2 * a] = Q.H[(size_t)a].real();
+      H_out[2 * a + 1] = Q.H[(size_t)a].imag();
+    }
+  if (xi_out)
+    for (int a = 0; a < k; ++a) {
+      xi_out[2 * a] = Q.xi[(size_t)a].real();
+      xi_out[2 * a + 1] = Q.xi[(size_t)a].imag();
+    }
+  if (rnorms_out)
+    for (int a = 0; a < k; ++a) rnorms_out[a] = a < report.used ? rn[(size_t)a] : 0.0;
+  if (used_out) *used_out = report.used;
   return MG_OK;
 }
 

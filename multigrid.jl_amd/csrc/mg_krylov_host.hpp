@@ -4,6 +4,7 @@
 //   KrylovReport        where a driver writes iters / flag / resvec / nres, and its epilogue
 //   HessenbergLsq<S>    the Givens least squares of FGMRES(m), S = double or std::complex<double>
 //   pinv_sym, RelaxLsq  the normal-equations step of FGMRES_relaxation (Jac-GMRES smoother, K-cycle)
+//   RelaxLsqC           the same for ComplexF64 hierarchies: Hermitian H, solved on its leading blocks
 //   SmallMatT<S>, sm_*  row-major dense helpers of the block drivers, S = double (SmallMat) or std::complex<double>
 #pragma once
 
@@ -91,7 +92,8 @@ struct HessenbergLsq {
 // ---- FGMRES_relaxation (FGMRES.jl:48-126): the normal equations of min || r0 - A Z t || ---------------------------------------------
 // Moore-Penrose inverse of a small symmetric matrix (H = (AZ)'(AZ), k <= 16) by cyclic Jacobi rotations;
 // cut-off as Julia's pinv: rtol = eps * k relative to the largest singular value.
-inline void pinv_sym(const std::vector<double>& H, int k, std::vector<double>& Pinv) {
+// kcut: the order that enters the cut-off where H is a leading block (or an embedding) of a larger zero-padded matrix; 0: k itself.
+inline void pinv_sym(const std::vector<double>& H, int k, std::vector<double>& Pinv, int kcut = 0) {
   std::vector<double> A(H), V((size_t)k * k, 0.0);
   for (int i = 0; i < k; ++i) V[(size_t)i * k + i] = 1.0;
   for (int sweep = 0; sweep < 100; ++sweep) {
@@ -125,7 +127,7 @@ inline void pinv_sym(const std::vector<double>& H, int k, std::vector<double>& P
   }
   double smax = 0.0;
   for (int i = 0; i < k; ++i) smax = std::max(smax, std::fabs(A[(size_t)i * k + i]));
-  const double tol = 2.220446049250313e-16 * k * smax;
+  const double tol = 2.220446049250313e-16 * (kcut > 0 ? kcut : k) * smax;
   Pinv.assign((size_t)k * k, 0.0);
   for (int e = 0; e < k; ++e) {
     const double lam = A[(size_t)e * k + e];
@@ -161,6 +163,59 @@ struct RelaxLsq {
       txi += tv[(size_t)a] * xi[(size_t)a];
     }
     return std::sqrt(std::fabs(tHt - 2.0 * txi + rnorm0 * rnorm0));       // l.104
+  }
+};
+
+// The same for VAL = ComplexF64 (mg_complex.inc: cx_fgmres_relax, the K-cycle of cx_cycle): H = (AZ)'(AZ) is Hermitian and xi complex
+// (Julia's dot conjugates its first argument).  The device hands over ALL Gram scalars of a relaxation at once, so step(m, .) solves on
+// the leading m x m block - the reference's pinv of its zero-padded k x k H gives the same t with zeros behind it, cut-off
+// eps * k * sigma_max included.  The Moore-Penrose inverse comes from pinv_sym on the real symmetric embedding [Re H, -Im H; Im H, Re H]
+// (every eigenvalue of H twice, the inverse of the embedding is the embedding of the inverse).
+struct RelaxLsqC {
+  typedef std::complex<double> zc;
+  const int k;
+  std::vector<zc> H, xi, tv;
+  explicit RelaxLsqC(int k_) : k(k_), H((size_t)k_ * k_, zc(0.0)), xi((size_t)k_, zc(0.0)), tv((size_t)k_, zc(0.0)) {}
+  // column j of t = AZ' w, entry i <= j:  H[:,j] = t; H[j,:] = t'; H = (H + H')/2  (l.99-101: the diagonal comes out real)
+  void set(int i, int j, zc d) {
+    if (i == j) {
+      H[(size_t)j * k + j] = zc(d.real(), 0.0);
+    } else {
+      H[(size_t)i * k + j] = d;
+      H[(size_t)j * k + i] = std::conj(d);
+    }
+  }
+  const std::vector<zc>& t() const { return tv; }
+  // t = pinv(H[:m,:m]) xi[:m] (zero behind m); returns rn = sqrt(|Re(t'Ht - 2 t'xi + ||r0||^2)|)   (l.102-104)
+  double step(int m, double rnorm0) {
+    const int e = 2 * m;
+    std::vector<double> E((size_t)e * e, 0.0), Pinv;
+    for (int a = 0; a < m; ++a)
+      for (int b = 0; b < m; ++b) {
+        const zc h = H[(size_t)a * k + b];
+        E[(size_t)a * e + b] = h.real();
+        E[(size_t)(a + m) * e + b + m] = h.real();
+        E[(size_t)a * e + b + m] = -h.imag();
+        E[(size_t)(a + m) * e + b] = h.imag();
+      }
+    pinv_sym(E, e, Pinv, k);
+    std::fill(tv.begin(), tv.end(), zc(0.0));
+    for (int a = 0; a < m; ++a) {
+      double re = 0.0, im = 0.0;
+      for (int b = 0; b < m; ++b) {
+        re += Pinv[(size_t)a * e + b] * xi[(size_t)b].real() + Pinv[(size_t)a * e + b + m] * xi[(size_t)b].imag();
+        im += Pinv[(size_t)(a + m) * e + b] * xi[(size_t)b].real() + Pinv[(size_t)(a + m) * e + b + m] * xi[(size_t)b].imag();
+      }
+      tv[(size_t)a] = zc(re, im);
+    }
+    zc tHt(0.0), txi(0.0);
+    for (int a = 0; a < m; ++a) {
+      zc s(0.0);
+      for (int b = 0; b < m; ++b) s += H[(size_t)a * k + b] * tv[(size_t)b];
+      tHt += std::conj(tv[(size_t)a]) * s;
+      txi += std::conj(tv[(size_t)a]) * xi[(size_t)a];
+    }
+    return std::sqrt(std::fabs((tHt - 2.0 * txi).real() + rnorm0 * rnorm0));
   }
 };
 

@@ -201,6 +201,8 @@ SIGNATURES = {
     "mg_create_CF64": (C.c_int, [_ll, _ll, _ll, C.POINTER(_vp)]),
     "mg_set_operator_CF64_INT64": (C.c_int, [_vp, _ll, _ll, _ll, _ll, _lp, _lp, _dp]),
     "mg_set_relax_CF64": (C.c_int, [_vp, _ll, _dp, _ll, _ll, _ll]),
+    "mg_set_schedule_CF64": (C.c_int, [_vp, _ll, _ll]),
+    "mg_fgmres_relax_CF64": (C.c_int, [_vp, _ll, _dp, _dp, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp]),
     "mg_set_coarse_dense_inverse_CF64": (C.c_int, [_vp, _ll, _dp]),
     "mg_set_coarse_lu_CF64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
     "mg_cycle_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
@@ -917,9 +919,9 @@ def _c128(a):
 
 
 class ComplexDeviceHierarchy(DeviceHierarchy):
-    """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F cycles, Jac / SPAI relaxation, dense-inverse or
-    sparse-LU coarsest solve.  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*`` methods, which
-    take the column count with each call.  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
+    """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F / K cycles, Jac / SPAI / Jac-GMRES relaxation,
+    dense-inverse or sparse-LU coarsest solve.  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
+    methods, which take the column count with each call (not on a K-cycle / Jac-GMRES hierarchy).  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
     conjugates back.  P and R are real."""
 
@@ -973,35 +975,68 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         if _relax_type_code(param) == 2:
             raise NotImplementedError("ComplexF64 hierarchies: the Vanka smoothers serve VAL=Float64 hierarchies (complex operators: "
                                       "the stand-alone RelaxVankaFacesColor)")
-        if param.cycleType == "K" or param.relaxType == "Jac-GMRES":
-            raise NotImplementedError("ComplexF64 hierarchies: cycles V, W, F with the Jac / SPAI smoothers")
+        self._refuse_schedule(param)
         for l in range(1, nl + 1):
             self._set_op(l, MG_OP_A, param.As[l - 1])
             if l < nl:
                 self._set_op(l, MG_OP_P, param.Ps[l - 1])
                 self._set_op(l, MG_OP_R, param.Rs[l - 1])
                 self._set_relax(l, param.relaxPrecs[l - 1], param.relaxPre(l), param.relaxPost(l))
-        _check(lib, lib.mg_set_relax_type(self.handle, 0), "mg_set_relax_type")
-        _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
+        self._set_schedule(param)
         if param.LU is None:
             raise MGDeviceError("param.LU is empty: run MGsetup first")
         self._set_coarse(param)
         _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
         self._schedule = self._schedule_of(param)
 
+    def _refuse_schedule(self, param):
+        """The K-cycle and Jac-GMRES smoothing are served for ComplexF64 values only."""
+        if self._sfx != "CF64" and (param.cycleType == "K" or param.relaxType == "Jac-GMRES"):
+            raise NotImplementedError("ComplexF32 hierarchies: cycles V, W, F with the Jac / SPAI smoothers")
+
+    def _set_schedule(self, param):
+        lib = self.lib
+        if self._sfx == "CF64":
+            _check(lib, lib.mg_set_schedule_CF64(self.handle, ord(param.cycleType), _relax_type_code(param)), "mg_set_schedule_CF64")
+        else:
+            _check(lib, lib.mg_set_relax_type(self.handle, 0), "mg_set_relax_type")
+            _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
+
+    def _block_guard(self):
+        """The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51); that form is not built."""
+        sched = getattr(self, "_schedule", None)
+        if sched is not None and (sched[0] == "K" or sched[1] == "Jac-GMRES"):
+            raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle / Jac-GMRES ComplexF64 hierarchy "
+                                      "(solve the columns one after the other)")
+
     def sync_schedule(self, param):
         sig = self._schedule_of(param)
         if sig == getattr(self, "_schedule", sig):
             self._schedule = sig
             return
-        if param.cycleType == "K" or param.relaxType == "Jac-GMRES":
-            raise NotImplementedError("ComplexF64 hierarchies: cycles V, W, F with the Jac / SPAI smoothers")
+        self._refuse_schedule(param)
         lib = self.lib
         for l in range(1, self.nlevels):
             self._set_relax(l, param.relaxPrecs[l - 1], sig[2][l - 1], sig[3][l - 1])
-        _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
+        self._set_schedule(param)
         _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
         self._schedule = sig
+
+    def fgmres_relax(self, level: int, r0, x, inner: int, tol: float = 1e-5):
+        """One FGMRES_relaxation (FGMRES.jl:48-126) with the diagonal preconditioner on As[level] and relaxPrecs[level]
+        (mg_fgmres_relax_CF64): ``x += Z t`` in place for the residual ``r0``.  Returns (rnorms, H, xi): the residual estimates of
+        the directions used (``len(rnorms)`` is the reference's ``used``), and the summed Gram scalars H = (AZ)'(AZ)
+        (inner x inner) and xi = (AZ)'r0 of all ``inner`` directions."""
+        r0 = self._host_block(r0)
+        x = self._host_block(x, True)
+        k = int(inner)
+        H = np.zeros((max(k, 1), max(k, 1)), dtype=np.complex128)
+        xi = np.zeros(max(k, 1), dtype=np.complex128)
+        rn = np.zeros(max(k, 1))
+        used = C.c_longlong(0)
+        _check(self.lib, self.lib.mg_fgmres_relax_CF64(self.handle, int(level), _c128(r0), _c128(x), r0.shape[0], k, float(tol), _c128(H),
+                                                       _c128(xi), _f64(rn), C.byref(used)), "mg_fgmres_relax_CF64")
+        return rn[: used.value], H, xi
 
     def _set_coarse(self, param, force_sparse: bool = False):
         """`z = param.LU\\b` (MGcycle.jl:177) from the complex splu: the explicit inverse up to DENSE_COARSE_MAX rows, else the
@@ -1191,6 +1226,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def block_spmv(self, level: int, which: int, alpha, X, beta, Y):
         """``Y = beta*Y + alpha*Op*X`` on one level for n x k complex128 blocks (mg_block_spmv_CF64); Y in place."""
+        self._block_guard()
         Xf, k = self._blk(X)
         Yf, ky = self._blk(Y, True)
         if ky != k:
@@ -1203,6 +1239,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def block_cycle(self, B, X, x_is_zero: int = -1):
         """One cycle on the whole n x k block (mg_block_cycle_CF64); X in place.  x_is_zero is a property of the whole block."""
+        self._block_guard()
         Bf, k = self._blk(B)
         Xf, kx = self._blk(X, True)
         if kx != k:
@@ -1212,6 +1249,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def block_solve(self, B, X, tol: float, maxIter: int):
         """solveMG on the block with Frobenius norms (mg_block_solve_CF64); returns (X, iters, resvec)."""
+        self._block_guard()
         Bf, k = self._blk(B)
         Xf, kx = self._blk(X, True)
         if kx != k:
@@ -1224,6 +1262,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def _dev_block(self, B, X):
         """Addresses and column count of two torch.complex128 device blocks [n][k], row-major (contiguous)."""
+        self._block_guard()
         for t in (B, X):
             if not (hasattr(t, "dtype") and hasattr(t, "data_ptr")):
                 raise TypeError("expected torch.complex128 device tensors of shape [n, k]")
@@ -1254,6 +1293,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     def block_bicgstab(self, B, X, tol: float, maxIter: int):
         """KrylovMethods.blockBiCGSTB on the Krylov operator with the block cycle as M1 (mg_block_bicgstab_CFP64); X in place;
         returns (X, flag, iters, resvec)."""
+        self._block_guard()
         Bf, k = self._blk(B)
         Xf, kx = self._blk(X, True)
         if kx != k or Bf.shape[0] != self.n or Xf.shape[0] != self.n:
