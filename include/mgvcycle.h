@@ -584,7 +584,9 @@ int mg_dd0_apply_dev_CFP64(mg_dd* dd, const double* b_dev, double* x_dev, long l
 int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* dd);
 /* Which coarsest solve a hierarchy of either value type runs.  info[0]: 0 dense inverse, 1 sparse LU in one workgroup, 2 sparse
  * LU chip-wide (per-level launches and a dense trailing inverse), 3 GMRES, 4 Schwarz sweep; info[1]: its order; info[2]:
- * kernel launches per solve (GMRES: 0 - it depends on the right-hand side).  MG_ERR_STATE when none is set. */
+ * kernel launches per solve (GMRES on a real handle: 0 - it depends on the right-hand side; GMRES on a complex handle: the launches
+ * of its speculative solve, which do not - front, 10 steps, combination, on the path the handle takes now, see
+ * mg_set_coarse_gmres_CF64).  MG_ERR_STATE when none is set. */
 int mg_coarse_form(mg_hierarchy* h, long long* info);
 /* info[0..6): value type (0 Float64, 1 ComplexF64); sub-domains; colours present; colours run batched; colours run in
  * sequence; kernel launches of one sweep (doTranspose = 0; a chip-wide member counts one launch per level it launches). */
@@ -792,15 +794,15 @@ int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count);
  * Norms.  ||r|| = sqrt(sum |r_i|^2), Julia's norm of a complex vector: solveMG's stopping test and resvec (which stays double).
  * Coarsest solve.  The dense inverse (column-major complex n x n) or sparse factors in the layout of
  *   mg_set_coarse_lu_FP64_INT64 / the reference's applyLUsolve_CFP64_INT64 (deps/src/parLU.cpp:69-72) with complex values,
- *   applied by the same level-scheduled triangular sweeps.
+ *   applied by the same level-scheduled triangular sweeps; or coarseSolveType "GMRES" (mg_set_coarse_gmres_CF64, below).
  * The handle.  The value type is fixed by the constructor.  Shared by both types: mg_set_cycle_type ('V', 'W', 'F'),
  *   mg_set_relax_type (0), mg_set_option, mg_set_nrhs (1), mg_finalize, mg_destroy, mg_graph_launches, mg_set_grid_hint (a
  *   no-op hint here), mg_profile_enable / _reset / _get (nothing is recorded), mg_last_error.  Every other FP64 entry point
  *   called with a CF64 handle fails with MG_ERR_STATE, and every CF64 entry point called with an FP64 handle fails with
  *   MG_ERR_STATE too; nothing is changed.
  * Refused with MG_ERR_UNSUPPORTED (and a mg_last_error message): cycle 'K' and relaxType 1 (Jac-GMRES) through the shared setters
- *   mg_set_cycle_type / mg_set_relax_type (a CF64 handle takes them through mg_set_schedule_CF64, below), the GMRES coarse solve
- *   (mg_set_coarse_gmres_FP64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries: a complex handle's own
+ *   mg_set_cycle_type / mg_set_relax_type (a CF64 handle takes them through mg_set_schedule_CF64, below), the real GMRES coarse solve
+ *   (mg_set_coarse_gmres_FP64: a complex handle takes mg_set_coarse_gmres_CF64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries: a complex handle's own
  *   nrhs stays 1, and blocks of right-hand sides go through the mg_block_*_CF64 / _CFP64 entry points at the end of this header, which
  *   take nrhs with each call), the _FP64 Krylov drivers
  *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*_FP64; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64 (mg_rap_CF64 serves them), mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
@@ -842,7 +844,8 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
  * cx_rap_numeric: deterministic, no atomics; rows of any length, at most the option rap_chunk target columns at a time; the
  * option rap_groups sets how many rows of A a wavefront walks side by side, 1 being the order of mg_rap_FP64's kernel).  The
  * coarsest factorisation stays with the host, as for FP64: mg_get_values_CF64 of the coarsest level, factor, hand the solve
- * back (mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64), mg_finalize.  Also refused: a handle that is not
+ * back (mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64), mg_finalize - except with the GMRES coarsest solve, whose
+ * vector d is recomputed here from omega[nlevels - 1] (see mg_set_coarse_gmres_CF64): nothing is left to the host.  Also refused: a handle that is not
  * finalized (MG_ERR_STATE), relaxKind other than 0 or 1 (MG_ERR_INVALID), any operator with 64-bit row pointers
  * (MG_ERR_UNSUPPORTED).  These checks of arguments and state precede the first write: after such a refusal the handle cycles
  * with its old values.  (A HIP error in the middle of the re-setup, MG_ERR_HIP, may leave some levels refreshed, as for FP64.)
@@ -863,6 +866,39 @@ mg_status mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n);
 mg_status mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
 mg_status mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n);
 mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz);
+
+/* ---- The GMRES coarsest solve on a complex handle ----------------------------------------------------------------------------
+ * coarseSolveType "GMRES" for complex handles (MGsetup.jl:335-336, MGcycle.jl:152-164): d = param.LU = relaxParam ./ diag(A_c), n
+ * complex128 values for CF64 AND CF32 handles (as the other complex coarse setters); the coarsest solve is x .= 0 and ONE restart of
+ * KrylovMethods.fgmres(A_c, b, 10, tol = 0.01, maxIter = 1) preconditioned by v -> d .* v, in the reference's operation order
+ * (modified Gram-Schmidt, h_k = dot(v_k, w) conjugating v_k, w -= h_k v_k, k ascending).  No factorisation, nothing to redo on the
+ * host when the matrix changes.  The setter replaces whatever coarsest solve was set and detaches a borrowed Schwarz handle; an FP64
+ * handle: MG_ERR_STATE; n other than the coarsest order: mg_finalize fails with MG_ERR_INVALID.  mg_finalize allocates the work set
+ * (11 basis vectors, 10 preconditioned vectors, a table of 121 scalars with a pinned readback); no cycle allocates.
+ * The solve is enqueued speculatively and whole: all 10 Arnoldi steps, ONE readback of the table (||b||^2 and, per step, h_0 .. h_i
+ * and ||w||^2), ONE host synchronisation; the host replays the columns, breaks at the first err / ||b|| <= 0.01, and x = Z[:, :used] y
+ * is one more launch.  Steps behind the break are computed and not read.  b = 0: x = 0.  EVERY COARSEST SOLVE THEREFORE ADDS ONE HOST
+ * SYNCHRONISATION TO THE CYCLE: one per V-cycle, 2^(levels - 2) per W- or K-cycle - also for mg_cycle_dev_CFP64, which otherwise
+ * returns without one, and per preconditioner application of the _CFP64 drivers.  Launches: a step is the product w = A_c z_i (which also
+ * leaves the partials of dot(v_0, w)) and either a chain of i + 1 Gram-Schmidt passes and one normalising pass (i + 3 launches; every
+ * pass sums the partials of the pass before it, no final-sum launch in between) or, on coarsest levels of at most 8192 rows, ONE
+ * one-workgroup launch that holds w in registers (2 launches per step).  The option coarse_gmres_tail_rows (read at every solve) moves
+ * that threshold: -1 the default, 0 the chain everywhere.  mg_coarse_form reports kind 3 and the launch count of the path in use (78
+ * for the chain, 22 for the one-workgroup form).  Sums are deterministic (no atomics): a rerun gives the same bits.
+ * Served: V / W / F / K cycles with Jac / SPAI / Jac-GMRES smoothing on CF64 handles, V / W / F with Jac / SPAI on CF32 handles, a
+ * hierarchy of one level (the solve alone), mg_solve_*, the _CFP64 drivers, mg_rap_CF64 (it recomputes d = omega[nlevels - 1] / diag(A_c)
+ * on the device after the last Galerkin product: omega then holds nlevels entries, and the host has nothing to factor).
+ * A CF32 handle runs this solve in ComplexF64 like its other coarsest solves: bc widened, the solve on a ComplexF64 copy of the
+ * coarsest operator kept for it, xc narrowed.  The reference would run this fgmres in ComplexF32: a deliberate deviation of the order
+ * of the single unit roundoff (more accurate).
+ * Refused with MG_ERR_UNSUPPORTED: every mg_block_*_CF64 / _CFP64 entry point with nrhs > 1 (the reference calls blockFGMRES there,
+ * MGcycle.jl:166-167: not built).
+ * mg_coarse_gmres_CF64: the coarsest solve alone on host vectors of n = coarsest order complex values; steps (the columns used), flag
+ * (0: the estimate met 0.01; -1: it did not within 10 steps; -9: b = 0) and resvec10 (err_i / ||b|| of the steps used; room for 10) may
+ * be NULL.  MG_ERR_STATE on a handle that is not finalized or whose coarsest solve is not GMRES; MG_ERR_INVALID for another n. */
+mg_status mg_set_coarse_gmres_CF64(mg_hierarchy* h, long long n, const double* d);
+mg_status mg_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long* steps, long long* flag,
+                               double* resvec10);
 
 /* ---- Jac-GMRES smoothing and the K-cycle on a CF64 handle (MGcycle.jl:35-50,72-76,96-98; FGMRES.jl:48-126) ------------------------
  * mg_set_schedule_CF64 sets cycleType ('V', 'W', 'F' or 'K') and relaxType (0: Jac / SPAI, 1: Jac-GMRES) of a CF64 handle in one
@@ -919,7 +955,10 @@ int mg_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, lo
                     long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
 int mg_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long inner, double tol,
                         long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
-/* One cycle on device vectors (x_is_zero: 0 or 1), enqueued on the handle's stream: no host copy, no synchronisation. */
+/* One cycle on device vectors (x_is_zero: 0 or 1), enqueued on the handle's stream: no host copy, no synchronisation - except the ones
+ * the schedule itself needs: one per Jac-GMRES relaxation and K-cycle step, and one per coarsest solve with the GMRES coarsest solve
+ * (mg_set_coarse_gmres_CF64).  The drivers above pay the same per preconditioner application: BiCGSTAB two cycles per iteration, FGMRES
+ * one per inner step. */
 int mg_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long x_is_zero);
 /* The fused complex vector passes of those drivers on their own (csrc/mg_cxvec.hpp): device vectors of n complex values on a
  * 16-byte boundary (MG_ERR_INVALID otherwise), asynchronous on `stream`, deterministic two-pass sums (no atomics) into out_dev

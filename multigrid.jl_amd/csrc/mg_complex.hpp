@@ -16,6 +16,9 @@
 // Epilogues: AXPBY, RESID (optionally also z1 = d.*r), SMOOTH, and GRAM - one step of the FGMRES relaxation (Jac-GMRES smoothing,
 // K-cycle; ComplexF64 only): w = A z_j stored as column j of AZ, the next direction d.*w, and the per-row-block partial sums of
 // column j of H = (AZ)'(AZ) and of xi[j] = dot(w, r0), see CxVecArgsT.
+// CGDOT - one Arnoldi step of the GMRES coarsest solve (coarseSolveType "GMRES"; ComplexF64 only): w = A z_i stored as the next
+// basis vector, and the per-row-block partial sums of dot(v_0, w), the first coefficient of the Gram-Schmidt chain that follows
+// (mg_cxvec.hpp).
 // Blocks of right-hand sides (row-major [n][nrhs]) run on the same row blocks: cx_csr_stream_spmm stages the matrix stream itself in
 // LDS and lets pow2 >= nrhs lanes per row walk it (below, behind the vector kernel).
 #pragma once
@@ -64,6 +67,10 @@ struct CxCsrDev {
 constexpr int GRAM = 3;
 constexpr int GRAM_MAXV = 8;                       // directions of one relaxation at most (mgcv::MAXV, the width of the combination pass)
 constexpr int GRAM_NS = 2 * GRAM_MAXV + 1;         // real scalars of a step at most: 2 j + 3 for j <= 7
+// CGDOT (cx_csr_stream_spmv only, ComplexF64): w = A z stored (y) with the partials of dot(v_0, w) = sum conj(v_0[row]) w[row]
+// (v_0 in r0) at gpart[bid] (re) and gpart[nblocks + bid] (im) - GRAM's reduction on two scalars: lane registers, wavefront
+// shuffles, the workgroup's LDS, one partial per row block, no atomics, the same bits on every run.
+constexpr int CGDOT = 4;
 
 template <typename C>
 struct CxVecArgsT {
@@ -95,7 +102,7 @@ template <int MODE, typename C>
 __device__ __forceinline__ C cx_epilogue(const CxVecArgsT<C>& v, C acc, C pb, C pd, C px) {
   if (MODE == AXPBY) return cmul(v.alpha, acc) + pb;
   if (MODE == RESID) return pb - acc;
-  if (MODE == GRAM) return acc;
+  if (MODE == GRAM || MODE == CGDOT) return acc;
   return px + cmul(pd, pb - acc);   // SMOOTH: x + d.*(b - A x)   (MGcycle.jl:129-131)
 }
 
@@ -106,6 +113,8 @@ __device__ __forceinline__ void cx_operands(const CxVecArgsT<C>& v, int row, C& 
   } else if (MODE == GRAM) {
     pb = v.r0[row];
     if (v.znext) pd = v.d[row];
+  } else if (MODE == CGDOT) {
+    pb = v.r0[row];
   } else {
     pb = v.b[row];
   }
@@ -178,6 +187,10 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
         for (int c = 0; c < GRAM_NS; ++c)
           if (c < 2 * j + 3) v.gpart[(size_t)c * A.nblocks + bid] = gs[c];
       }
+      if constexpr (MODE == CGDOT) {
+        v.gpart[bid] = pb.x * o.x + pb.y * o.y;
+        v.gpart[(size_t)A.nblocks + bid] = pb.x * o.y - pb.y * o.x;
+      }
     }
     return;
   }
@@ -241,6 +254,24 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
       }
     __syncthreads();
     if (tid < ns) {
+      double t = 0.0;
+      for (int w = 0; w < BLK / 64; ++w) t += red[tid * (BLK / 64) + w];
+      v.gpart[(size_t)tid * A.nblocks + bid] = t;
+    }
+    return;
+  }
+  if constexpr (MODE == CGDOT) {   // (outv and pb are zero in a lane without a row)
+    double t0 = pb.x * outv.x + pb.y * outv.y, t1 = pb.x * outv.y - pb.y * outv.x;
+    for (int o = 32; o > 0; o >>= 1) {
+      t0 += __shfl_xor(t0, o);
+      t1 += __shfl_xor(t1, o);
+    }
+    if ((tid & 63) == 0) {
+      red[tid >> 6] = t0;
+      red[(BLK / 64) + (tid >> 6)] = t1;
+    }
+    __syncthreads();
+    if (tid < 2) {
       double t = 0.0;
       for (int w = 0; w < BLK / 64; ++w) t += red[tid * (BLK / 64) + w];
       v.gpart[(size_t)tid * A.nblocks + bid] = t;

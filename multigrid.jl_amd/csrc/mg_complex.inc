@@ -1,6 +1,7 @@
 // mg_complex.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F / K cycles,
-// pointwise or Jac-GMRES relaxation (K and Jac-GMRES: CF64 handles, one right-hand side), dense-inverse or sparse-LU coarsest solve.  The state lives apart from the real levels (CxState);
+// pointwise or Jac-GMRES relaxation (K and Jac-GMRES: CF64 handles, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
+// (the last: one right-hand side, one host synchronisation per solve).  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
 // The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
 // ComplexF32 / Int64 hierarchies (the _CF32 entry points; the reference's VAL = ComplexF32, singlePrecision) share all of it: the
@@ -71,6 +72,13 @@ struct CxState {
   DevBuf<int> luLptr, luLcol, luUptr, luUcol, luP, luQ, luLorder, luLlvl, luUorder, luUlvl;
   DevBuf<double> luLval, luUval, luWork;
   int nLlvl = 0, nUlvl = 0;
+  // coarseSolveType "GMRES" (mg_set_coarse_gmres_CF64; cx_coarse_gmres): the coarsest Jacobi vector d_c, the 11 basis vectors V and 10
+  // preconditioned vectors Z (column-major, n_c apart), the scalar table with its pinned readback, two sets of partial sums (a pass reads
+  // one and writes the other), and on a CF32 handle the coarsest operator widened to ComplexF64.  Sized by mg_finalize.
+  bool coarse_gmres = false;
+  DevBuf<double> cgD, cgV, cgZ, cgTab, cgPart;
+  double* h_cgtab = nullptr;         // pinned
+  CxMat cgA;
   DevBuf<double> stage_b, partial;   // the fine right-hand side; per-row-block partials of ||r||^2
   // The FGMRES relaxation's own partials and scalars (Jac-GMRES smoothing, K-cycle; cx_fgmres_relax): it runs inside the Krylov drivers,
   // whose kpart / kscal must survive a cycle.  Scalar 0: ||r0||^2; step j: the 2 j + 3 scalars of its GRAM launch from 1 + j^2 + 2 j on,
@@ -109,6 +117,9 @@ struct CxState {
     if (h_bgram) (void)hipHostFree(h_bgram);
     if (h_bcoef) (void)hipHostFree(h_bcoef);
     Ainv.release();
+    for (DevBuf<double>* d : {&cgD, &cgV, &cgZ, &cgTab, &cgPart}) d->release();
+    if (h_cgtab) (void)hipHostFree(h_cgtab);
+    cgA.release();
     for (DevBuf<int>* d : {&luLptr, &luLcol, &luUptr, &luUcol, &luP, &luQ, &luLorder, &luLlvl, &luUorder, &luUlvl}) d->release();
     luLval.release(); luUval.release(); luWork.release();
     stage_b.release(); partial.release(); cw_b.release(); cw_x.release();
@@ -350,8 +361,135 @@ int cx_widen(mg_hierarchy* h, const cf_t* src, cx_t* dst, long long n) {
 
 int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr, const hipStream_t* on);
 
+// ---- coarseSolveType "GMRES" (MGsetup.jl:335-336, MGcycle.jl:152-164) for complex hierarchies -------------------------------------------
+// x .= 0, then ONE restart of KrylovMethods.fgmres(A_c, b, 10, tol = 0.01, maxIter = 1, M = v -> d_c .* v).  The restart is enqueued
+// speculatively and whole, as cx_fgmres_relax enqueues a relaxation: the front, all 10 Arnoldi steps (kernels and table: mg_cxvec.hpp),
+// ONE readback of the 121 scalars, ONE host synchronisation; the host then replays the columns (coarse_gmres_replay,
+// mg_krylov_host.hpp), which fixes `used`, and x = Z[:, :used] y is one more pass.  Columns behind the break were computed and are not
+// read.  b = 0: x = 0 and flag -9, as the reference returns.  (The reference's fgmres also looks at the true residual behind a restart
+// that did not meet tol; in exact arithmetic that residual is the last estimate, and nothing in the cycle reads the flag.)
+constexpr double CX_CG_TOL = 0.01;
+// levels of at most this many rows take the one-workgroup tail (cg_tail) behind every product, larger ones the chain of passes
+// (measured: profiles/complex_coarse_gmres.md); the option coarse_gmres_tail_rows moves the threshold (0: the chain everywhere)
+constexpr long long CX_CG_TAIL_DEFAULT_ROWS = mgcv::CG_TAIL_ROWS;
+static_assert(mgcv::CG_TAIL_ROWS >= 4913, "the one-workgroup tail serves every geometric coarsest level up to 17^3 rows");
+
+inline bool cx_cg_use_tail(const mg_hierarchy* h) {
+  const long long opt = h->opt.coarse_gmres_tail_rows;
+  const long long lim = std::min<long long>(opt < 0 ? CX_CG_TAIL_DEFAULT_ROWS : opt, mgcv::CG_TAIL_ROWS);
+  return h->cx->n_coarse <= lim;
+}
+// kernel launches of one solve on the path in use: the front, the 10 steps, the combination (b = 0 skips the last)
+inline long long cx_cg_launches(const mg_hierarchy* h) {
+  if (cx_cg_use_tail(h)) return 1 + 2 * mgcv::CG_M + 1;
+  long long c = 2 + 1;
+  for (int i = 0; i < mgcv::CG_M; ++i) c += i + 3;
+  return c;
+}
+// the coarsest operator the solve applies: the level's own on a CF64 handle, its widened copy on a CF32 one
+inline const CxMat& cx_cg_operator(const CxState& S) { return S.single ? S.cgA : S.lev.back().A; }
+
+// w = A z with the partials of dot(v0, w) at part (re: [0, nblocks), im: [nblocks, 2 nblocks))
+int cx_cg_product(mg_hierarchy* h, const CxMat& M, const cx_t* z, cx_t* w, const cx_t* v0, double* part) {
+  mgk::CxVecArgsT<cx_t> v = {};
+  v.x = z;
+  v.y = w;
+  v.beta_zero = 1;
+  v.r0 = v0;
+  v.gpart = part;
+  if (M.wide) {
+    mgk::CxCsrDev<long long, cx_t> D;
+    D.rowptr = M.rowptr64.p; D.colidx = M.colidx.p; D.val = static_cast<const cx_t*>(M.vals()); D.blk_row = M.blk_row.p;
+    D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
+    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::CGDOT, long long, cx_t, cx_t>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+  } else {
+    mgk::CxCsrDev<int, cx_t> D;
+    D.rowptr = M.rowptr.p; D.colidx = M.colidx.p; D.val = static_cast<const cx_t*>(M.vals()); D.blk_row = M.blk_row.p;
+    D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
+    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::CGDOT, int, cx_t, cx_t>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+  }
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// what a caller may ask back of one coarsest solve (mg_coarse_gmres_CF64)
+struct CxCoarseReport {
+  int used = 0;
+  long long flag = 0;
+  double resvec[mgcv::CG_M] = {};
+};
+
+int cx_coarse_gmres(mg_hierarchy* h, const cx_t* b, cx_t* x, CxCoarseReport* report = nullptr) {
+  CxState& S = *h->cx;
+  const CxMat& A = cx_cg_operator(S);
+  const long long n = S.n_coarse;
+  const size_t ld = (size_t)n;
+  const hipStream_t st = h->play->stream;
+  constexpr int m = mgcv::CG_M;
+  if (!A.set || S.cgV.n != 2 * ld * (m + 1) || !S.h_cgtab) return fail(MG_ERR_STATE, "internal: the GMRES coarsest solve's work set is not sized");
+  cx_t *V = cxp(S.cgV), *Z = cxp(S.cgZ);
+  const cx_t* d = cxc(S.cgD);
+  double* tab = S.cgTab.p;
+  const size_t P = S.cgPart.n / 4;
+  double* part[2] = {S.cgPart.p, S.cgPart.p + 2 * P};
+  const bool tail = cx_cg_use_tail(h);
+  const int G = mgcv::cxv_grid(n);
+  const unsigned T = (unsigned)std::min<long long>(mgcv::CG_TAIL_T, (n + 63) / 64 * 64);
+  // front: r = b (x = 0); ||b||^2, v_0 = b / ||b||, z_0 = d.*v_0
+  if (tail) {
+    hipLaunchKernelGGL(mgcv::cg_tail, dim3(1), dim3(T), 0, st, (const double*)nullptr, 0, 0, tab, (const cx_t*)V, (long long)ld, b, V, d, Z, (int)n);
+  } else {
+    hipLaunchKernelGGL(mgk::cx_sumsq_partial<cx_t>, dim3((unsigned)G), dim3(mgk::BLK), 0, st, b, n, part[0]);
+    hipLaunchKernelGGL(mgcv::cg_norm_pass, dim3((unsigned)G), dim3(mgcv::KB), 0, st, (const double*)part[0], G, tab, b, V, d, Z, n);
+  }
+  HIP_TRY(hipGetLastError());
+  for (int i = 0; i < m; ++i) {
+    cx_t* w = V + (size_t)(i + 1) * ld;
+    cx_t* znext = i + 1 < m ? Z + (size_t)(i + 1) * ld : nullptr;
+    double* slot = tab + mgcv::cg_slot(i);
+    MG_TRY(cx_cg_product(h, A, Z + (size_t)i * ld, w, V, part[0]));
+    if (tail) {
+      hipLaunchKernelGGL(mgcv::cg_tail, dim3(1), dim3(T), 0, st, (const double*)part[0], A.nblocks, i + 1, slot, (const cx_t*)V, (long long)ld,
+                         (const cx_t*)w, w, d, znext, (int)n);
+    } else {
+      int cur = 0, np = A.nblocks;
+      for (int k = 0; k <= i; ++k) {
+        hipLaunchKernelGGL(mgcv::cg_mgs_pass, dim3((unsigned)G), dim3(mgcv::KB), 0, st, (const double*)part[cur], np, slot + 2 * k,
+                           (const cx_t*)(V + (size_t)k * ld), k < i ? (const cx_t*)(V + (size_t)(k + 1) * ld) : (const cx_t*)nullptr, w, n, part[1 - cur]);
+        cur = 1 - cur;
+        np = G;
+      }
+      hipLaunchKernelGGL(mgcv::cg_norm_pass, dim3((unsigned)G), dim3(mgcv::KB), 0, st, (const double*)part[cur], np, slot + 2 * (i + 1), (const cx_t*)w, w, d,
+                         znext, n);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(S.h_cgtab, tab, sizeof(double) * mgcv::CG_TAB, hipMemcpyDeviceToHost, st));
+  HIP_TRY(spin_sync(st));
+  HessenbergLsq<std::complex<double>> Q(m);
+  CxCoarseReport local;
+  CxCoarseReport& R = report ? *report : local;
+  coarse_gmres_replay(S.h_cgtab, CX_CG_TOL, Q, R.used, R.flag, R.resvec);
+  if (R.used == 0) {   // b = 0
+    HIP_TRY(hipMemsetAsync(x, 0, sizeof(cx_t) * ld, st));
+    return MG_OK;
+  }
+  mgcv::OpCCombine op;
+  op.m = R.used;
+  op.x = x;
+  for (int j = 0; j < m; ++j) {
+    const int jj = j < R.used ? j : 0;
+    op.y[j] = j < R.used ? cx_t{Q.y[(size_t)j].real(), Q.y[(size_t)j].imag()} : cx_t{0.0, 0.0};
+    op.z[j] = Z + (size_t)jj * ld;
+  }
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(mgcv::cxv_pass<mgcv::OpCCombine>), dim3((unsigned)G), dim3(mgcv::KB), 0, st, op, n, part[0]);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
 // z = param.LU \ b (MGcycle.jl:177): explicit inverse, or x[q] = U \ (L \ b[p]) by the level-scheduled sptrsv_lu (one workgroup;
-// chip-wide for factors of >= lu_multi_min_rows rows), or one Schwarz sweep (MGcycle.jl:140-143; xzero: x need not be read)
+// chip-wide for factors of >= lu_multi_min_rows rows), or one Schwarz sweep (MGcycle.jl:140-143; xzero: x need not be read), or one
+// restart of Jacobi-preconditioned FGMRES(10) from zero (cx_coarse_gmres: the only one that synchronises with the host, once)
 // nr >= 1: b and x are row-major blocks [n][nr] (the factor applier's own layout; the Schwarz sweep serves one column)
 int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr = 0) {
   CxState& S = *h->cx;
@@ -360,6 +498,10 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr
   if (h->coarse_dd) {
     if (k > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%d)", k);
     return dd_coarse(h, reinterpret_cast<const double*>(b), reinterpret_cast<double*>(x), xzero);
+  }
+  if (S.coarse_gmres) {   // (the reference calls blockFGMRES on a block, MGcycle.jl:166-167: not built)
+    if (k > 1) return fail(MG_ERR_UNSUPPORTED, "the GMRES coarsest solve serves one right-hand side (nrhs=%d)", k);
+    return cx_coarse_gmres(h, b, x);
   }
   if (S.coarse_multi) return cxlu_solve_dev(S.coarse_multi, *S.coarse_multi->fwd, b, x, k, &h->play->stream);
   if (S.coarse_lu) {
@@ -383,7 +525,9 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr
 }
 
 // The coarsest solve of a CF32 handle stays ComplexF64 (Julia's lu of a ComplexF32 sparse matrix factorises in double,
-// MGsetup.jl:350; MGcycle.jl:177-178): bc is widened, solved by the kernels above, xc narrowed.
+// MGsetup.jl:350; MGcycle.jl:177-178): bc is widened, solved by the kernels above, xc narrowed.  The GMRES coarsest solve too: it runs
+// in ComplexF64 on the widened copy of the coarsest operator (CxState::cgA).  The reference would run that fgmres in ComplexF32 - a
+// deliberate deviation of the order of the single unit roundoff: more accurate, and no float instantiation of the vector passes.
 int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool = true, int nr = 0) {
   CxState& S = *h->cx;
   DevBuf<double>&wb = nr ? S.Bcw_b : S.cw_b, &wx = nr ? S.Bcw_x : S.cw_x;
@@ -653,6 +797,12 @@ int cx_block_schedule_ok(mg_hierarchy* h) {
     return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy");
   return MG_OK;
 }
+// The reference calls blockFGMRES for a block on a GMRES coarsest solve (MGcycle.jl:166-167); that form is not built here.
+int cx_block_coarse_ok(mg_hierarchy* h, long long nrhs) {
+  if (h->cx->coarse_gmres && nrhs > 1)
+    return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a complex hierarchy with the GMRES coarsest solve (nrhs=%lld)", nrhs);
+  return MG_OK;
+}
 int cx_block_nrhs_ok(long long nrhs) {
   if (nrhs < 1) return fail(MG_ERR_INVALID, "nrhs=%lld: a block holds at least one right-hand side", nrhs);
   if (nrhs > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "complex blocks hold at most %d right-hand sides (nrhs=%lld)", mgk::BLK_KMAX, nrhs);
@@ -666,6 +816,7 @@ int cx_block_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want) {
   MG_TRY(cx_block_schedule_ok(h));
   if (n != h->cx->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->cx->lev[0].n);
   if (h->coarse_dd && nrhs > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%lld)", nrhs);
+  MG_TRY(cx_block_coarse_ok(h, nrhs));
   return MG_OK;
 }
 
@@ -697,6 +848,57 @@ int cx_block_ensure(mg_hierarchy* h, int nr) {
     MG_TRY(S.BluWork.alloc(nc));
   }
   S.blk_cap = nr;
+  return MG_OK;
+}
+
+// A single (ComplexF32) operator A widened into K: the same pattern and row blocks (one chunk size for both precisions), the values
+// through cx_widen.  Waited for.
+int cx_widen_mat(mg_hierarchy* h, const CxMat& A, CxMat& K) {
+  const hipStream_t st = h->play->stream;
+  K.release();
+  K.cplx = true;
+  K.single = false;
+  K.wide = A.wide;
+  K.n_rows = A.n_rows; K.n_cols = A.n_cols; K.nnz = A.nnz; K.nblocks = A.nblocks; K.max_row = A.max_row;
+  if (A.wide) {
+    MG_TRY(K.rowptr64.alloc(A.rowptr64.n));
+    HIP_TRY(hipMemcpyAsync(K.rowptr64.p, A.rowptr64.p, A.rowptr64.bytes(), hipMemcpyDeviceToDevice, st));
+  } else {
+    MG_TRY(K.rowptr.alloc(A.rowptr.n));
+    HIP_TRY(hipMemcpyAsync(K.rowptr.p, A.rowptr.p, A.rowptr.bytes(), hipMemcpyDeviceToDevice, st));
+  }
+  MG_TRY(K.colidx.alloc(A.colidx.n));
+  MG_TRY(K.blk_row.alloc(A.blk_row.n));
+  MG_TRY(K.val.alloc(2 * (size_t)std::max<long long>(A.nnz, 1)));
+  HIP_TRY(hipMemcpyAsync(K.colidx.p, A.colidx.p, A.colidx.bytes(), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(K.blk_row.p, A.blk_row.p, A.blk_row.bytes(), hipMemcpyDeviceToDevice, st));
+  if (A.nnz > 0) MG_TRY(cx_widen(h, reinterpret_cast<const cf_t*>(A.valf.p), cxp(K.val), A.nnz));
+  HIP_TRY(spin_sync(st));
+  K.set = true;
+  return MG_OK;
+}
+
+// the work set of the GMRES coarsest solve (no allocation inside a cycle), or nothing of it where another coarsest solve is set
+int cx_cg_ensure(mg_hierarchy* h) {
+  CxState& S = *h->cx;
+  if (!S.coarse_gmres) {
+    for (DevBuf<double>* d : {&S.cgD, &S.cgV, &S.cgZ, &S.cgTab, &S.cgPart}) d->release();
+    S.cgA.release();
+    return MG_OK;
+  }
+  const CxMat& Ac = S.lev.back().A;
+  const size_t nc = (size_t)S.n_coarse;
+  if (S.cgD.n != 2 * nc) return fail(MG_ERR_INVALID, "the coarsest Jacobi vector holds %zu values, the coarsest level %zu rows", S.cgD.n / 2, nc);
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  const size_t vlen = 2 * nc * (mgcv::CG_M + 1), zlen = 2 * nc * mgcv::CG_M;
+  const size_t plen = 4 * std::max<size_t>((size_t)Ac.nblocks, (size_t)mgcv::MAXB);
+  if (S.cgV.n != vlen) MG_TRY(S.cgV.alloc(vlen));
+  if (S.cgZ.n != zlen) MG_TRY(S.cgZ.alloc(zlen));
+  if (S.cgTab.n != (size_t)mgcv::CG_TAB) MG_TRY(S.cgTab.alloc((size_t)mgcv::CG_TAB));
+  if (S.cgPart.n != plen) MG_TRY(S.cgPart.alloc(plen));
+  if (!S.h_cgtab) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_cgtab), sizeof(double) * mgcv::CG_TAB));
+  if (S.single) MG_TRY(cx_widen_mat(h, Ac, S.cgA));   // (the level's values may have changed since the last finalize)
+  else S.cgA.release();
   return MG_OK;
 }
 
@@ -779,6 +981,7 @@ int cx_finalize(mg_hierarchy* h) {
     }
   }
   if (gmres_relax || kcycle) MG_TRY(cx_gram_ensure(h, maxblocks));
+  MG_TRY(cx_cg_ensure(h));
   S.finalized = true;
   return MG_OK;
 }
@@ -1273,6 +1476,7 @@ int cx_block_spmv_host(mg_hierarchy* h, long long level, long long which, const 
   if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
   MG_TRY(cx_block_nrhs_ok(nrhs));
   MG_TRY(cx_block_schedule_ok(h));
+  MG_TRY(cx_block_coarse_ok(h, nrhs));
   if (!alpha || !beta || !X || !Y) return fail(MG_ERR_INVALID, "null argument");
   if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
   CxLevel& L = S.lev[(size_t)level - 1];
@@ -1302,29 +1506,7 @@ int cx_block_spmv_host(mg_hierarchy* h, long long level, long long which, const 
 // Krylov product is never single).  Same pattern and row blocks (one chunk size for both precisions), values through cx_widen.
 int cx_widen_K(mg_hierarchy* h) {
   CxState& S = *h->cx;
-  const CxMat& A = S.lev[0].A;
-  CxMat& K = S.K;
-  const hipStream_t st = h->play->stream;
-  K.release();
-  K.cplx = true;
-  K.single = false;
-  K.wide = A.wide;
-  K.n_rows = A.n_rows; K.n_cols = A.n_cols; K.nnz = A.nnz; K.nblocks = A.nblocks; K.max_row = A.max_row;
-  if (A.wide) {
-    MG_TRY(K.rowptr64.alloc(A.rowptr64.n));
-    HIP_TRY(hipMemcpyAsync(K.rowptr64.p, A.rowptr64.p, A.rowptr64.bytes(), hipMemcpyDeviceToDevice, st));
-  } else {
-    MG_TRY(K.rowptr.alloc(A.rowptr.n));
-    HIP_TRY(hipMemcpyAsync(K.rowptr.p, A.rowptr.p, A.rowptr.bytes(), hipMemcpyDeviceToDevice, st));
-  }
-  MG_TRY(K.colidx.alloc(A.colidx.n));
-  MG_TRY(K.blk_row.alloc(A.blk_row.n));
-  MG_TRY(K.val.alloc(2 * (size_t)std::max<long long>(A.nnz, 1)));
-  HIP_TRY(hipMemcpyAsync(K.colidx.p, A.colidx.p, A.colidx.bytes(), hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipMemcpyAsync(K.blk_row.p, A.blk_row.p, A.blk_row.bytes(), hipMemcpyDeviceToDevice, st));
-  if (A.nnz > 0) MG_TRY(cx_widen(h, reinterpret_cast<const cf_t*>(A.valf.p), cxp(K.val), A.nnz));
-  HIP_TRY(spin_sync(st));
-  K.set = true;
+  MG_TRY(cx_widen_mat(h, S.lev[0].A, S.K));
   S.K_auto = true;
   return MG_OK;
 }
@@ -1502,6 +1684,7 @@ int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double*
   S.n_coarse = n;
   S.coarse_set = true;
   S.coarse_lu = false;
+  S.coarse_gmres = false;
   S.finalized = false;
   return MG_OK;
 }
@@ -1536,6 +1719,7 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
     S.n_coarse = n;
     S.coarse_set = true;
     S.coarse_lu = true;
+    S.coarse_gmres = false;
     S.Ainv.release();
     S.finalized = false;
     return MG_OK;
@@ -1568,8 +1752,63 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
   S.n_coarse = n;
   S.coarse_set = true;
   S.coarse_lu = true;
+  S.coarse_gmres = false;
   S.Ainv.release();
   S.finalized = false;
+  return MG_OK;
+}
+
+// coarseSolveType "GMRES": d = param.LU = relaxParam ./ diag(A_c), n complex128 values (a CF32 handle's too)
+int mg_set_coarse_gmres_CF64(mg_hierarchy* h, long long n, const double* d) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));
+  if (n < 1 || !d) return fail(MG_ERR_INVALID, "empty coarsest Jacobi vector");
+  if (n >= (1LL << 31) - 1) return fail(MG_ERR_UNSUPPORTED, "dimension exceeds int32 device indices");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  MG_TRY(S.cgD.alloc(2 * (size_t)n));
+  HIP_TRY(hipMemcpy(S.cgD.p, d, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  dd_detach(h);
+  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+  for (DevBuf<int>* q : {&S.luLptr, &S.luLcol, &S.luUptr, &S.luUcol, &S.luP, &S.luQ, &S.luLorder, &S.luLlvl, &S.luUorder, &S.luUlvl}) q->release();
+  S.luLval.release(); S.luUval.release(); S.luWork.release();
+  S.Ainv.release();
+  S.n_coarse = n;
+  S.coarse_set = true;
+  S.coarse_lu = false;
+  S.coarse_gmres = true;
+  S.finalized = false;
+  return MG_OK;
+}
+
+// the coarsest solve alone on host vectors: x = the GMRES coarsest solve of b; steps = the columns used, flag 0 / -1 / -9,
+// resvec[i] = err_i / ||b|| for i < steps (10 entries at most)
+int mg_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long* steps, long long* flag, double* resvec) {
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  if (!S.coarse_gmres) return fail(MG_ERR_STATE, "the coarsest solve of this handle is not GMRES (mg_set_coarse_gmres_CF64)");
+  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+  if (n != S.n_coarse) return fail(MG_ERR_INVALID, "n=%lld does not match the coarsest level (%lld rows)", n, S.n_coarse);
+  (void)hipSetDevice(h->device);
+  const hipStream_t st = h->play->stream;
+  const size_t bytes = sizeof(cx_t) * (size_t)n;
+  DevBuf<double> db, dx;   // (released below on every path)
+  CxCoarseReport report;
+  int rc = db.alloc(2 * (size_t)n);
+  if (rc == MG_OK) rc = dx.alloc(2 * (size_t)n);
+  if (rc == MG_OK && hipMemcpyAsync(db.p, b, bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(MG_ERR_HIP, "upload of b failed");
+  if (rc == MG_OK) rc = cx_coarse_gmres(h, cxc(db), cxp(dx), &report);
+  if (rc == MG_OK && hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MG_ERR_HIP, "download of x failed");
+  if (spin_sync(st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_coarse_gmres_CF64: stream failed");
+  db.release();
+  dx.release();
+  if (rc != MG_OK) return rc;
+  if (steps) *steps = report.used;
+  if (flag) *flag = report.flag;
+  if (resvec)
+    for (int i = 0; i < report.used; ++i) resvec[i] = report.resvec[i];
   return MG_OK;
 }
 
@@ -1664,6 +1903,11 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     while (groups > 1 && (size_t)chunk * ((size_t)groups * sizeof(cx_t) + sizeof(int)) > 32768) groups /= 2;
     hipLaunchKernelGGL(mgk::cx_rap_numeric, dim3((unsigned)Cm.n_rows), dim3(64), (size_t)chunk * ((size_t)groups * sizeof(cx_t) + sizeof(int)), st,
                        cx_csr32<double>(L.R), Ad, cx_csr32<double>(L.P), Cm.rowptr.p, Cm.colidx.p, cxp(Cm.val), chunk, groups);
+    HIP_TRY(hipGetLastError());
+  }
+  if (S.coarse_gmres) {   // param.LU = relaxParam ./ diag(A_c) on the new coarsest operator (MGsetup.jl:335-336): omega[nlevels - 1]
+    const CxLevel& Lc = S.lev[(size_t)nl - 1];
+    hipLaunchKernelGGL(mgk::cx_relax_jacobi, dim3(cx_grid(Lc.n)), dim3(mgk::BLK), 0, st, cx_csr32<cx_t>(Lc.A), (int)Lc.n, omega[nl - 1], cxp(S.cgD));
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(S.rap_ev[(size_t)nl - 1], st));

@@ -590,6 +590,7 @@ int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* d) {
     S.n_coarse = d->n;
     S.coarse_set = true;
     S.coarse_lu = false;
+    S.coarse_gmres = false;
     S.Ainv.release();
     S.finalized = false;
   } else {
@@ -604,7 +605,8 @@ int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* d) {
 }
 
 // info[0]: the coarsest solve in use - 0 dense inverse, 1 sparse LU in one workgroup, 2 sparse LU chip-wide, 3 GMRES, 4 Schwarz
-// sweep; info[1]: its order; info[2]: kernel launches per solve (GMRES: 0, it depends on the right-hand side)
+// sweep; info[1]: its order; info[2]: kernel launches per solve (GMRES on a real handle: 0, it depends on the right-hand side; on a
+// complex handle the whole speculative solve, which does not: front, 10 steps, combination - on the path the handle takes now)
 int mg_coarse_form(mg_hierarchy* h, long long* info) {
   if (!h || !info) return fail(MG_ERR_INVALID, "null argument");
   const bool set = h->cx ? h->cx->coarse_set : h->coarse_set;
@@ -617,8 +619,8 @@ int mg_coarse_form(mg_hierarchy* h, long long* info) {
     info[2] = f[5];
   } else if (h->cx) {
     const CxState& S = *h->cx;
-    info[0] = S.coarse_multi ? 2 : S.coarse_lu ? 1 : 0;
-    info[2] = 1;
+    info[0] = S.coarse_gmres ? 3 : S.coarse_multi ? 2 : S.coarse_lu ? 1 : 0;
+    info[2] = S.coarse_gmres ? cx_cg_launches(h) : 1;
     if (S.coarse_multi) {
       const CxLuSet& G = *S.coarse_multi->fwd;
       info[2] = G.multi ? (long long)(G.Llvl_h.size() - 1) + (long long)(G.Ulvl_h.size() - 1) + (G.M > 0 ? 3 : 0) + 1 : 1;

@@ -3,6 +3,7 @@
 // tests/native/krylov_host_algebra.cpp builds it on its own.  Nothing here touches a device vector.
 //   KrylovReport        where a driver writes iters / flag / resvec / nres, and its epilogue
 //   HessenbergLsq<S>    the Givens least squares of FGMRES(m), S = double or std::complex<double>
+//   coarse_gmres_replay the replay of a complex hierarchy's GMRES coarsest solve from its table of scalars
 //   pinv_sym, RelaxLsq  the normal-equations step of FGMRES_relaxation (Jac-GMRES smoother, K-cycle)
 //   RelaxLsqC           the same for ComplexF64 hierarchies: Hermitian H, solved on its leading blocks
 //   SmallMatT<S>, sm_*  row-major dense helpers of the block drivers, S = double (SmallMat) or std::complex<double>
@@ -88,6 +89,38 @@ struct HessenbergLsq {
     return y;
   }
 };
+
+// ---- the GMRES coarsest solve of a complex hierarchy (mg_complex.inc: cx_coarse_gmres): the host's replay of ONE restart of
+// FGMRES(m) from x = 0 that the device has run to its end.  tab: tab[0] = ||b||^2; column i from slot(i) = 1 + i^2 + 2 i on:
+// h_0 .. h_i (re, im each), then ||w||^2 - (m + 1)^2 doubles for m columns.  The columns are closed one after the other and the
+// loop breaks at the first err / ||b|| <= tol (KrylovMethods.fgmres); columns behind the break are not read.  used: the columns that
+// enter x = Z[:, :used] y (Q.solve(used) has run; y = Q.y); flag 0 (the estimate met tol), -1 (it did not), -9 (b = 0: x = 0, used = 0);
+// resvec[i] = err_i / ||b|| for i < used.
+inline int coarse_gmres_slot(int i) { return 1 + i * i + 2 * i; }
+inline void coarse_gmres_replay(const double* tab, double tol, HessenbergLsq<std::complex<double>>& Q, int& used, long long& flag,
+                                double* resvec) {
+  used = 0;
+  flag = -1;
+  if (!(tab[0] > 0.0)) {
+    flag = -9;
+    return;
+  }
+  const double bn = std::sqrt(tab[0]);
+  Q.begin(bn);
+  for (int i = 0; i < Q.m; ++i) {
+    const double* c = tab + coarse_gmres_slot(i);
+    for (int k = 0; k <= i; ++k) Q.h(k, i) = std::complex<double>(c[2 * k], c[2 * k + 1]);
+    Q.hsub(i) = std::sqrt(c[2 * (i + 1)]);
+    const double err = Q.close_column(i) / bn;
+    if (resvec) resvec[i] = err;
+    used = i + 1;
+    if (err <= tol) {
+      flag = 0;
+      break;
+    }
+  }
+  Q.solve(used);
+}
 
 // ---- FGMRES_relaxation (FGMRES.jl:48-126): the normal equations of min || r0 - A Z t || ---------------------------------------------
 // Moore-Penrose inverse of a small symmetric matrix (H = (AZ)'(AZ), k <= 16) by cyclic Jacobi rotations;

@@ -145,6 +145,8 @@ bool host_all_zero(const double* x, long long len) {
   X(bool, no_lane_pairs, false) \
   X(long long, graph_max_rows, 300000)     /* sub-cycles from the first level of at most this many rows*nrhs replay as one HIP graph */ \
   X(long long, lu_multi_min_rows, 4096)    /* sparse coarse factors of this many rows: per-level launches + dense trailing inverse */ \
+  X(long long, coarse_gmres_tail_rows, -1) /* complex GMRES coarsest solve: largest level whose steps run the one-workgroup tail (-1: the measured \
+                                              default; 0: the chain of passes everywhere; capped by the tail's row limit; read at every solve) */ \
   X(long long, lu_dense_tail_min, 64) \
   X(long long, lu_dense_tail_max, 16384)   /* largest trailing block kept as an explicit inverse (8*M^2 bytes each for L and U: 2 x 2.1 GB) */ \
   X(double, rowclass_min_cover, 0.9) \

@@ -205,6 +205,8 @@ SIGNATURES = {
     "mg_fgmres_relax_CF64": (C.c_int, [_vp, _ll, _dp, _dp, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp]),
     "mg_set_coarse_dense_inverse_CF64": (C.c_int, [_vp, _ll, _dp]),
     "mg_set_coarse_lu_CF64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
+    "mg_set_coarse_gmres_CF64": (C.c_int, [_vp, _ll, _dp]),
+    "mg_coarse_gmres_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _lp, _lp, _dp]),
     "mg_cycle_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_solve_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
     "mg_spmv_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _dp, _dp, _dp, _ll]),
@@ -920,7 +922,7 @@ def _c128(a):
 
 class ComplexDeviceHierarchy(DeviceHierarchy):
     """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F / K cycles, Jac / SPAI / Jac-GMRES relaxation,
-    dense-inverse or sparse-LU coarsest solve.  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
+    dense-inverse, sparse-LU or GMRES coarsest solve (the last adds one host synchronisation per coarsest solve and serves no blocks).  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
     methods, which take the column count with each call (not on a K-cycle / Jac-GMRES hierarchy).  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
     conjugates back.  P and R are real."""
@@ -1009,6 +1011,12 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle / Jac-GMRES ComplexF64 hierarchy "
                                       "(solve the columns one after the other)")
 
+    def _block_coarse_guard(self, k: int):
+        """The reference calls blockFGMRES for a block on the GMRES coarsest solve (MGcycle.jl:166-167); that form is not built."""
+        if getattr(self, "_coarse_gmres", False) and int(k) > 1:
+            raise NotImplementedError("blocks of right-hand sides are not served on a complex hierarchy with coarseSolveType='GMRES' "
+                                      "(solve the columns one after the other)")
+
     def sync_schedule(self, param):
         sig = self._schedule_of(param)
         if sig == getattr(self, "_schedule", sig):
@@ -1044,10 +1052,17 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         import scipy.sparse as sp
         lib = self.lib
         nc = int(param.As[-1].shape[0])
+        self._coarse_gmres = False
         if self._set_coarse_solver(param):
             return
-        if param.coarseSolveType == "GMRES":
-            raise NotImplementedError("coarseSolveType='GMRES' is not served for ComplexF64 hierarchies")
+        if param.coarseSolveType == "GMRES":                            # param.LU = relaxParam ./ diag(A_c)  (MGsetup.jl:335-336)
+            d = param.LU
+            if not isinstance(d, np.ndarray) or d.shape != (nc,):
+                raise MGDeviceError(f"param.LU is not the coarsest Jacobi vector of {nc} values: run MGsetup first")
+            d = np.ascontiguousarray(d, dtype=np.complex128)            # (complex128 for ComplexF32 hierarchies too)
+            _check(lib, lib.mg_set_coarse_gmres_CF64(self.handle, nc, _c128(d)), "mg_set_coarse_gmres_CF64")
+            self._coarse_gmres = True
+            return
         if nc <= DENSE_COARSE_MAX and not force_sparse:
             Ainv = np.asfortranarray(param.LU.solve(np.eye(nc, dtype=np.complex128)), dtype=np.complex128)
             _check(lib, lib.mg_set_coarse_dense_inverse_CF64(self.handle, nc, _c128(Ainv)), "mg_set_coarse_dense_inverse_CF64")
@@ -1055,6 +1070,18 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         Lp, Lc, Lv, Up, Uc, Uv, p, q = complex_lu_arrays(param.LU)
         _check(lib, lib.mg_set_coarse_lu_CF64_INT64(self.handle, nc, _i64(Lp), _i64(Lc), _c128(Lv), _i64(Up), _i64(Uc), _c128(Uv),
                                                     _i64(p), _i64(q)), "mg_set_coarse_lu_CF64")
+
+    def coarse_gmres(self, b):
+        """The GMRES coarsest solve alone (mg_coarse_gmres_CF64): one restart of Jacobi-preconditioned FGMRES(10) from zero on the
+        coarsest operator for the complex128 right-hand side ``b``.  Returns (x, flag, resvec): flag 0 (the estimate met 0.01), -1
+        (it did not) or -9 (b = 0, x = 0); ``resvec`` holds err_i / ||b|| of the steps used."""
+        b = self._host_block(b)
+        x = np.zeros(b.shape[0], dtype=np.complex128)
+        steps, flag = C.c_longlong(0), C.c_longlong(0)
+        res = np.zeros(10)
+        _check(self.lib, self.lib.mg_coarse_gmres_CF64(self.handle, _c128(b), _c128(x), b.shape[0], C.byref(steps), C.byref(flag),
+                                                       _f64(res)), "mg_coarse_gmres_CF64")
+        return x, int(flag.value), res[: steps.value]
 
     def set_nrhs(self, nrhs: int):
         if int(nrhs) != 1:
@@ -1231,6 +1258,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         Yf, ky = self._blk(Y, True)
         if ky != k:
             raise ValueError("X and Y must hold the same number of columns")
+        self._block_coarse_guard(k)
         a = np.array([complex(alpha).real, complex(alpha).imag])
         bt = np.array([complex(beta).real, complex(beta).imag])
         _check(self.lib, self.lib.mg_block_spmv_CF64(self.handle, int(level), int(which), _f64(a), _c128(Xf), _f64(bt), _c128(Yf), k),
@@ -1244,6 +1272,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         Xf, kx = self._blk(X, True)
         if kx != k:
             raise ValueError("B and X must hold the same number of columns")
+        self._block_coarse_guard(k)
         _check(self.lib, self.lib.mg_block_cycle_CF64(self.handle, _c128(Bf), _c128(Xf), Bf.shape[0], k, int(x_is_zero)), "mg_block_cycle_CF64")
         return self._blk_back(X, Xf)
 
@@ -1254,6 +1283,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         Xf, kx = self._blk(X, True)
         if kx != k:
             raise ValueError("B and X must hold the same number of columns")
+        self._block_coarse_guard(k)
         iters = C.c_longlong(0)
         resvec = np.zeros(int(maxIter) + 1)
         _check(self.lib, self.lib.mg_block_solve_CF64(self.handle, _c128(Bf), _c128(Xf), Bf.shape[0], k, float(tol), int(maxIter),
@@ -1273,6 +1303,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
                 raise ValueError(f"device blocks are contiguous [n, k] tensors with n = {self.n} (row-major)")
         if tuple(B.shape) != tuple(X.shape):
             raise ValueError("B and X must have the same shape")
+        self._block_coarse_guard(int(B.shape[1]))
         _sync_torch(B, X)
         return _ptr(B), _ptr(X), int(B.shape[1])
 
@@ -1298,6 +1329,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         Xf, kx = self._blk(X, True)
         if kx != k or Bf.shape[0] != self.n or Xf.shape[0] != self.n:
             raise ValueError(f"blocks of {self.n} x k complex values expected, the same k for B and X")
+        self._block_coarse_guard(k)
         out = self._block_krylov_c("block_bicgstab", _c128(Bf), _c128(Xf), k, tol, maxIter)
         return (self._blk_back(X, Xf),) + out
 
@@ -1329,7 +1361,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     def replace_matrix(self, param, A_new, timings: Optional[dict] = None) -> None:
         """replaceMatrixInHierarchy on the device, the complex twin of DeviceHierarchy.replace_matrix: numeric Galerkin products
         and relaxPrecs on the fixed patterns (mg_rap_CF64), host copies of the hierarchy refreshed from HBM, coarsest level
-        re-factored on the host.  ``timings`` (a dict) receives the seconds of the three parts."""
+        re-factored on the host (with coarseSolveType='GMRES' there is nothing to factor: its Jacobi vector is recomputed in HBM).  ``timings`` (a dict) receives the seconds of the three parts."""
         import time
         lib = self.lib
         t0 = time.perf_counter()
@@ -1354,8 +1386,11 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         t2 = time.perf_counter()
         from .mgsetup import defineCoarsestAinv
         defineCoarsestAinv(param, param.As[-1])                      # (MGsetup.jl:323-355)
-        self._set_coarse(param)
-        _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        if not getattr(self, "_coarse_gmres", False):
+            self._set_coarse(param)
+            _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        # (GMRES coarsest solve: param.LU = relaxParam ./ diag(As[-1]) above is the host's copy; mg_rap_CF64 has recomputed the device's
+        #  in HBM - no inverse, no factorisation, nothing uploaded)
         if timings is not None:
             timings.update(rap=t1 - t0, readback=t2 - t1, coarsest=time.perf_counter() - t2)
 

@@ -29,6 +29,15 @@ def _complex_block(param: MGparam, b) -> bool:
     return is_complex(param) and _ncols(b) > 1
 
 
+def _coarse_gmres_guard(param: MGparam, b) -> None:
+    """A complex hierarchy with coarseSolveType='GMRES' given a block: the reference calls blockFGMRES in its coarsest solve
+    (MGcycle.jl:166-167), which is not built - refused before the device is touched, as the device layer refuses it."""
+    from .mgdef import _solver_object
+    if _complex_block(param, b) and param.coarseSolveType == "GMRES" and _solver_object(param.LU) is None:
+        raise NotImplementedError("blocks of right-hand sides are not served on a complex hierarchy with coarseSolveType='GMRES' "
+                                  "(solve the columns one after the other)")
+
+
 def _width(param: MGparam, b) -> int:
     """The nrhs the handle is sized for: the block's columns, or 1 for a complex hierarchy (see ``_complex_block``)."""
     return 1 if is_complex(param) else _ncols(b)
@@ -51,6 +60,7 @@ def to_device(param: MGparam, device_id: int = 0) -> DeviceHierarchy:
 
 def solveMG(param: MGparam, b: np.ndarray, x: np.ndarray, verbose: bool = False):
     """``(x, param, iter) = solveMG(param,b,x,verbose)``: x is updated IN PLACE (testGMG.jl:54-55)."""
+    _coarse_gmres_guard(param, b)
     adjustMemoryForNumRHS(param, _width(param, b))
     dev = to_device(param)
     if _complex_block(param, b):                  # the residual norms are Frobenius norms of the block (SolveFuncs.jl:14-36)
@@ -68,6 +78,7 @@ def recursiveCycle(param: MGparam, b: np.ndarray, x: np.ndarray, level: int = 1)
     """One cycle from the finest level.  Only ``level == 1`` is an entry point of the device library."""
     if level != 1:
         raise ValueError("the device library owns the recursion: only level=1 can be entered from the host")
+    _coarse_gmres_guard(param, b)
     adjustMemoryForNumRHS(param, _width(param, b))
     if _complex_block(param, b):
         to_device(param).block_cycle(b, x, -1)
@@ -80,6 +91,7 @@ def getMultigridPreconditioner(param: MGparam, B: np.ndarray, verbose: bool = Fa
     """``M(b) = (z .= 0; recursiveCycle(param,b,z,1); z)`` (SolveFuncs.jl:59): x = 0 on entry."""
     if not hierarchyExists(param):
         print("You have to do a setup first.")
+    _coarse_gmres_guard(param, B)
     adjustMemoryForNumRHS(param, _width(param, B))
     dev = to_device(param)
     if _complex_block(param, B):
@@ -247,6 +259,7 @@ def solveBlockBiCGSTAB_MG_CFP64(A, param: MGparam, B: np.ndarray, X0: np.ndarray
         raise TypeError("solveBlockBiCGSTAB_MG_CFP64 serves VAL=ComplexF64 hierarchies; a Float64 hierarchy goes to solveBiCGSTAB_MG")
     if _ncols(B) != _ncols(X0):
         raise ValueError("B and X0 must hold the same number of columns")
+    _coarse_gmres_guard(param, B)
     adjustMemoryForNumRHS(param, 1)               # the block entry points take the column count with each call
     dev = to_device(param)
     if A is not None and param.As and A is param.As[0]:
@@ -270,6 +283,7 @@ _WHICH = {"A": MG_OP_A, "P": MG_OP_P, "R": MG_OP_R}
 def SpMatMul(param: MGparam, level: int, which: str, x: np.ndarray, target: np.ndarray,
              alpha: float = 1.0, beta: float = 0.0):
     """``target = beta*target + alpha*Op*x`` (SpMatMul.jl:4-13) with Op = As/Ps/Rs[level] resident on device."""
+    _coarse_gmres_guard(param, x)
     adjustMemoryForNumRHS(param, _width(param, x))
     if _complex_block(param, x):
         to_device(param).block_spmv(level, _WHICH[which], alpha, x, beta, target)
