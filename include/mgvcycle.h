@@ -805,7 +805,8 @@ int mg_ghost_allreduce_count(mg_hierarchy* h, long long* count);
  *   (mg_set_coarse_gmres_FP64: a complex handle takes mg_set_coarse_gmres_CF64), nrhs > 1 (mg_create_CF64, mg_set_nrhs, the cycle / solve / spmv entries: a complex handle's own
  *   nrhs stays 1, and blocks of right-hand sides go through the mg_block_*_CF64 / _CFP64 entry points at the end of this header, which
  *   take nrhs with each call), the _FP64 Krylov drivers
- *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*_FP64; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64 (mg_rap_CF64 serves them), mg_transpose_hierarchy, mg_kcycle_step_async_dev_FP64, every
+ *   (mg_pcg*, mg_bicgstab*, mg_fgmres*, mg_block_*_FP64; BiCGSTAB and FGMRES have _CFP64 forms below), mg_rap_FP64 (mg_rap_CF64 serves them), mg_transpose_hierarchy (a complex handle is flipped by
+ *   mg_adjoint_hierarchy_CF64 / _CF32, below), mg_kcycle_step_async_dev_FP64, every
  *   mg_ghost_* call and mg_dist_set_tail_INT64 with a CF64 tail (the mg_dist_* handles are FP64 by construction).
  * Formats.  Generic CSR only, one streaming kernel (int32 row pointers; 64-bit beyond 2^31 - 4096 non-zeros or with the option
  *   "force_rowptr64"); the row-class, band, tile, march and small-level formats are real-valued and not used.  No HIP graphs. */
@@ -866,6 +867,33 @@ mg_status mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n);
 mg_status mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
 mg_status mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n);
 mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz);
+
+/* ---- adjointHierarchy on a complex handle (transposeHierarchy for complex VAL, MGsetup.jl:274-318) ----------------------------
+ * The flip between the forward system A x = b and the adjoint system A' x = b (A' = conj(A)^T, Julia's `'`) that an inversion
+ * makes in every outer iteration, on the resident hierarchy: As[l] <- As[l]' on every level, relaxPrecs[l] <- conj(relaxPrecs[l]),
+ * Ps[l] <- Rs[l]' (Rs[l] keeps its values: the reference's second assignment reads the new Ps[l]), and the coarsest solve for the
+ * adjoint operator: the dense inverse replaced by its conjugate transpose in place ((A')^-1 = (A^-1)'; ComplexF64 on CF32 handles
+ * too), the GMRES coarsest solve's vector d conjugated (MGsetup.jl:304-305).  mg_adjoint_hierarchy_CF64 serves CF64 handles (V / W /
+ * F / K cycles, Jac / SPAI / Jac-GMRES relaxation), mg_adjoint_hierarchy_CF32 CF32 handles (V / W / F, Jac / SPAI); hierarchies of
+ * one level included.  mg_transpose_hierarchy keeps refusing complex handles.
+ * Values and column indices never leave HBM (csrc/mg_complex.hpp, cx_adj_*): per operator the entries of every column are counted
+ * (integer atomics), the n_cols counts are read back (4 bytes per column), scanned on the host into the new row pointers and cut
+ * into row blocks by the upload's rule (pointers and block table go back), every entry's row index is scattered into its column's
+ * segment, and every entry is then written - conjugated; the real values of R copied - to its place in the segment: the number
+ * of entries of that column with a smaller row index.  The result is the stored-order CSR of the adjoint, bit for bit what a host
+ * conjugate transpose with sorted indices gives, the same bits on every run; no floating-point atomics.  The transposed pattern
+ * cached for SPAI re-setups is dropped (the next mg_rap_CF64 rebuilds it), a CF32 handle's widened coarsest operator is rebuilt
+ * from the new As[end] and its widened Krylov operator from the new As[1] (at the next driver call); a Krylov operator the caller
+ * set (mg_set_krylov_operator_CFP64_INT64) is the caller's to flip and is left alone.  The call ends with the finalization path.
+ * Refused, every check before the first write, so that the handle cycles with its old bits afterwards: a null handle
+ * MG_ERR_INVALID; a handle that is not finalized, an FP64 handle, the _CF64 entry on a CF32 handle or the reverse MG_ERR_STATE;
+ * any operator with 64-bit row pointers, a column of more than 4096 entries in any A or R (the ranking reads a column once per
+ * entry of it), a coarsest solve held as sparse factors (single-workgroup or chip-wide) or a Schwarz coarsest solve
+ * MG_ERR_UNSUPPORTED - hand the adjoint hierarchy over with the set_* calls then.  A HIP error in the middle (MG_ERR_HIP) leaves a
+ * partly flipped handle that is NOT finalized: every entry point refuses it until it has been uploaded again, as for
+ * mg_transpose_hierarchy. */
+mg_status mg_adjoint_hierarchy_CF64(mg_hierarchy* h);
+mg_status mg_adjoint_hierarchy_CF32(mg_hierarchy* h);
 
 /* ---- The GMRES coarsest solve on a complex handle ----------------------------------------------------------------------------
  * coarseSolveType "GMRES" for complex handles (MGsetup.jl:335-336, MGcycle.jl:152-164): d = param.LU = relaxParam ./ diag(A_c), n

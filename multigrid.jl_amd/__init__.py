@@ -6,7 +6,7 @@ name carries a dot).
 """
 from .mgdef import (MGparam, getMGparam, hierarchyExists, destroyCoarsestLU, copySolver, clear_)
 from .mgsetup import (MGsetup, getRelaxPrec, getSPAIprec, adjustMemoryForNumRHS, replaceMatrixInHierarchy,
-                      transposeHierarchy, defineCoarsestAinv, multilevelOperatorConstructor,
+                      transposeHierarchy, adjointHierarchy, defineCoarsestAinv, multilevelOperatorConstructor,
                       getMultilevelOperatorConstructor, galerkin)
 from .transfer_operators import (getFWInterp, get1DFWInterp, restrictCellCenteredVariables, restrictNodalVariables,
                                  getRestrictionCellCentered)

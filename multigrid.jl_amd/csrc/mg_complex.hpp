@@ -1,6 +1,6 @@
 // mg_complex.hpp - gfx950 kernels of the ComplexF64 (CF64) cycle and of its single-precision form (CF32: the same kernels on
-// float pairs, see f2_t below): generic CSR only; complex hybrid Kaczmarz; the chip-wide complex triangular solve of the factor
-// applier (cx_sptrsv_*, cx_tri_*, at the end).
+// float pairs, see f2_t below): generic CSR only; the conjugate transpose of an operator in HBM (cx_adj_*: adjointHierarchy); complex
+// hybrid Kaczmarz; the chip-wide complex triangular solve of the factor applier (cx_sptrsv_*, cx_tri_*, at the end).
 //
 // Complex values are interleaved (re, im) doubles - Julia ComplexF64, numpy complex128, hipDoubleComplex - and are
 // loaded as one 16-byte d2_t.  The operator A of a CF64 handle is stored conjugated at upload (nzval of the
@@ -689,6 +689,84 @@ __global__ __launch_bounds__(BLK) void cx_relax_spai(CxCsr32<d2_t> A, int n, dou
   const d2_t diag = cx_diag(A, i);
   const double si = s[i];
   d[i] = d2_t{omega * (diag.x / si), omega * (-diag.y / si)};
+}
+
+// ------------------------------------------------------------------------------------------------
+// adjointHierarchy on a complex hierarchy (mg_adjoint_hierarchy_CF64 / _CF32; MGsetup.jl:274-318 for complex VAL): the stored-order
+// CSR of M' = conj(M)^T built in HBM from M's CSR; neither the values nor the column indices travel to the host.
+//   cx_adj_count    one lane per entry: cnt[col] += 1 (integer atomics: exact, any order)
+//   (host)          the n_cols counts come back (4 B per column), are scanned into the new row pointers and cut into row blocks
+//   cx_adj_scatter  one lane per entry (row i, column c): its row index into a free slot of column c's segment (an atomic cursor
+//                   per column hands out the slots: any order)
+//   cx_adj_order    one lane per entry again: the entry's place in its segment is the number of entries of that segment with a
+//                   smaller row index (the rows of one column are distinct), so lane k writes (i, conj(val_k)) to tptr[c] + rank -
+//                   the same place whatever order the scatter left, the same bits on every run, what a host transpose gives.
+// The row of entry k is found by bisection in rowptr (rows may be empty).  The ranking reads a segment once per entry of it: the
+// work is the sum of the squared column lengths (27^2 per column on a GMG level), the host refuses columns beyond 4096 entries.
+// Values: complex pairs are conjugated on the way (A), real ones copied (R -> P).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ d2_t cx_adj_val(d2_t a) { return d2_t{a.x, -a.y}; }
+__device__ __forceinline__ f2_t cx_adj_val(f2_t a) { return f2_t{a.x, -a.y}; }
+__device__ __forceinline__ double cx_adj_val(double a) { return a; }
+__device__ __forceinline__ float cx_adj_val(float a) { return a; }
+
+// the row that holds entry k: the last i with rowptr[i] <= k (0 <= k < rowptr[n_rows])
+__device__ __forceinline__ int cx_row_of(const int* __restrict__ rowptr, int n_rows, int k) {
+  int lo = 0, hi = n_rows;   // the first index whose pointer exceeds k lies in (0, n_rows]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (rowptr[mid] <= k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;
+}
+
+__global__ __launch_bounds__(BLK) void cx_adj_count(const int* __restrict__ col, int nnz, int* __restrict__ cnt) {
+  const long long k = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (k < nnz) atomicAdd(cnt + col[k], 1);
+}
+
+__global__ __launch_bounds__(BLK) void cx_adj_scatter(const int* __restrict__ rowptr, const int* __restrict__ col, int n_rows, int nnz,
+                                                      const int* __restrict__ tptr, int* __restrict__ cursor, int* __restrict__ trow) {
+  const long long k = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (k >= nnz) return;
+  const int c = col[k];
+  trow[tptr[c] + atomicAdd(cursor + c, 1)] = cx_row_of(rowptr, n_rows, (int)k);
+}
+
+template <typename VT>
+__global__ __launch_bounds__(BLK) void cx_adj_order(const int* __restrict__ rowptr, const int* __restrict__ col, const VT* __restrict__ val,
+                                                    int n_rows, int nnz, const int* __restrict__ tptr, const int* __restrict__ trow,
+                                                    int* __restrict__ ocol, VT* __restrict__ oval) {
+  const long long k = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (k >= nnz) return;
+  const int i = cx_row_of(rowptr, n_rows, (int)k);
+  const int c = col[k];
+  const int k0 = tptr[c], k1 = tptr[c + 1];
+  int rank = 0;
+  for (int q = k0; q < k1; ++q) rank += trow[q] < i ? 1 : 0;
+  ocol[k0 + rank] = i;
+  oval[k0 + rank] = cx_adj_val(val[k]);
+}
+
+// Ainv <- Ainv' in place (row-major n x n complex): (A')^-1 = (A^-1)', the complex twin of dense_transpose_inplace
+__global__ __launch_bounds__(BLK) void cx_dense_adjoint_inplace(d2_t* __restrict__ a, int n) {
+  const long long idx = (long long)blockIdx.x * BLK + threadIdx.x;
+  const long long i = idx / n, j = idx - i * n;
+  if (i >= n || j > i) return;
+  const d2_t lo = a[i * n + j];
+  if (j == i) {
+    a[i * n + i] = cx_adj_val(lo);
+  } else {
+    a[i * n + j] = cx_adj_val(a[j * n + i]);
+    a[j * n + i] = cx_adj_val(lo);
+  }
+}
+
+// z_k = conj(z_k) in place on float pairs (relaxPrecs of a CF32 handle)
+__global__ __launch_bounds__(BLK) void cx_conj32(f2_t* __restrict__ z, long long n) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i < n) z[i].y = -z[i].y;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -12,6 +12,8 @@
 // Blocks of right-hand sides (mg_block_*_CF64 here, mg_block_*_CFP64 in mg_complex_krylov.inc) take nrhs with each call: cx_spmv,
 // cx_relax, cx_coarse and cx_cycle carry a column count nr (0: the single-vector path, untouched; >= 1: row-major blocks [n][nr] on
 // the block work set of CxState, cx_block_ensure).
+// adjointHierarchy on the resident hierarchy (mg_adjoint_hierarchy_CF64 / _CF32; cx_adjoint_hierarchy): every operator replaced by its
+// conjugate transpose in HBM, for both precisions.
 // Also here: the stand-alone ComplexF64 factor applier behind mg_lu_*_CFP64 (CxLu; its extern "C" entry points sit beside the
 // real applier's in mg_cabi.inc).
 //
@@ -1511,6 +1513,156 @@ int cx_widen_K(mg_hierarchy* h) {
   return MG_OK;
 }
 
+// ---- adjointHierarchy on the device (mg_adjoint_hierarchy_CF64 / _CF32; MGsetup.jl:274-318 for complex VAL) -----------------
+// the per-column ranking of cx_adj_order reads a column once per entry of it: longer columns are refused up front
+constexpr int CX_ADJ_MAXCOL = 4096;
+
+// what the host works out for one operator M before anything is written: the row pointers and row blocks of M'
+struct CxAdjPlan {
+  std::vector<int> tp, blk;
+  long long max_row = 0;
+};
+
+// entries per column of M (cx_adj_count), read back and scanned; the row blocks by the rule of cx_upload.  Writes nothing of the handle.
+int cx_adj_plan(mg_hierarchy* h, const CxMat& M, const char* what, int level, CxAdjPlan& plan) {
+  const hipStream_t st = h->play->stream;
+  const size_t m = (size_t)M.n_cols;
+  DevBuf<int> cnt;
+  plan.tp.assign(m + 1, 0);
+  int rc = cnt.alloc(m);
+  if (rc == MG_OK && hipMemsetAsync(cnt.p, 0, cnt.bytes(), st) != hipSuccess) rc = fail(MG_ERR_HIP, "hipMemsetAsync failed");
+  if (rc == MG_OK && M.nnz > 0) {
+    hipLaunchKernelGGL(mgk::cx_adj_count, dim3(cx_grid(M.nnz)), dim3(mgk::BLK), 0, st, M.colidx.p, (int)M.nnz, cnt.p);
+    if (hipGetLastError() != hipSuccess) rc = fail(MG_ERR_HIP, "cx_adj_count failed to launch");
+  }
+  if (rc == MG_OK && (hipMemcpyAsync(plan.tp.data() + 1, cnt.p, m * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                      spin_sync(st) != hipSuccess))
+    rc = fail(MG_ERR_HIP, "readback of the column counts failed");
+  cnt.release();
+  MG_TRY(rc);
+  plan.max_row = 0;
+  for (size_t j = 0; j < m; ++j) {
+    plan.max_row = std::max<long long>(plan.max_row, plan.tp[j + 1]);
+    plan.tp[j + 1] += plan.tp[j];
+  }
+  if (plan.tp[m] != M.nnz) return fail(MG_ERR_HIP, "internal: the column counts of %s[%d] sum to %d, not %lld", what, level, plan.tp[m], M.nnz);
+  if (plan.max_row > CX_ADJ_MAXCOL)
+    return fail(MG_ERR_UNSUPPORTED, "%s[%d] holds a column of %lld entries: the per-column ordering of the device adjoint is quadratic (at most %d)", what,
+                level, plan.max_row, CX_ADJ_MAXCOL);
+  // row blocks: consecutive rows, <= MAXROWS rows and <= CX_CHUNK non-zeros (a longer row has a block of its own)
+  const long long nr = M.n_cols;
+  plan.blk.assign(1, 0);
+  for (long long r = 0; r < nr;) {
+    long long e = r + 1;
+    while (e < nr && (e - r) < mgk::MAXROWS && plan.tp[(size_t)e + 1] - plan.tp[(size_t)r] <= mgk::CX_CHUNK) ++e;
+    plan.blk.push_back((int)e);
+    r = e;
+  }
+  return MG_OK;
+}
+
+// Out <- M' by the plan (Out may be M itself): new arrays are filled in HBM, then take the old ones' place.  VT: M's stored values.
+template <typename VT>
+int cx_adj_apply(mg_hierarchy* h, const CxMat& M, const CxAdjPlan& plan, CxMat& Out) {
+  const hipStream_t st = h->play->stream;
+  const size_t nnz1 = (size_t)std::max<long long>(M.nnz, 1);
+  CxMat N;
+  N.cplx = M.cplx;
+  N.single = M.single;
+  N.wide = false;
+  N.n_rows = M.n_cols;
+  N.n_cols = M.n_rows;
+  N.nnz = M.nnz;
+  N.nblocks = (int)plan.blk.size() - 1;
+  N.max_row = plan.max_row;
+  DevBuf<int> cursor, trow;
+  const size_t scalars = nnz1 * (M.cplx ? 2 : 1);   // of M's precision
+  int rc = N.rowptr.alloc(plan.tp.size());
+  if (rc == MG_OK) rc = N.colidx.alloc(nnz1);
+  if (rc == MG_OK) rc = N.blk_row.alloc(plan.blk.size());
+  if (rc == MG_OK) rc = M.single ? N.valf.alloc(scalars) : N.val.alloc(scalars);
+  if (rc == MG_OK) rc = cursor.alloc((size_t)M.n_cols);
+  if (rc == MG_OK) rc = trow.alloc(nnz1);
+  if (rc == MG_OK && (hipMemcpyAsync(N.rowptr.p, plan.tp.data(), plan.tp.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+                      hipMemcpyAsync(N.blk_row.p, plan.blk.data(), plan.blk.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+                      hipMemsetAsync(cursor.p, 0, cursor.bytes(), st) != hipSuccess))
+    rc = fail(MG_ERR_HIP, "upload of the adjoint's row pointers failed");
+  if (rc == MG_OK && M.nnz > 0) {
+    const dim3 g(cx_grid(M.nnz)), b(mgk::BLK);
+    hipLaunchKernelGGL(mgk::cx_adj_scatter, g, b, 0, st, M.rowptr.p, M.colidx.p, (int)M.n_rows, (int)M.nnz, N.rowptr.p, cursor.p, trow.p);
+    hipLaunchKernelGGL(mgk::cx_adj_order<VT>, g, b, 0, st, M.rowptr.p, M.colidx.p, static_cast<const VT*>(M.vals()), (int)M.n_rows, (int)M.nnz,
+                       N.rowptr.p, trow.p, N.colidx.p, static_cast<VT*>(const_cast<void*>(N.vals())));
+    if (hipGetLastError() != hipSuccess) rc = fail(MG_ERR_HIP, "the adjoint kernels failed to launch");
+  }
+  if (spin_sync(st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "the adjoint of an operator failed on the device");   // (plan's arrays were read)
+  cursor.release();
+  trow.release();
+  if (rc != MG_OK) {
+    N.release();
+    return rc;
+  }
+  N.set = true;
+  Out.release();   // (with it the transposed pattern cached for SPAI re-setups: has_t / t_ptr / t_perm)
+  Out = N;
+  return MG_OK;
+}
+
+int cx_adj_apply(mg_hierarchy* h, const CxMat& M, const CxAdjPlan& plan, CxMat& Out) {
+  if (M.cplx) return M.single ? cx_adj_apply<cf_t>(h, M, plan, Out) : cx_adj_apply<cx_t>(h, M, plan, Out);
+  return M.single ? cx_adj_apply<float>(h, M, plan, Out) : cx_adj_apply<double>(h, M, plan, Out);
+}
+
+// As[l] <- As[l]', relaxPrecs[l] <- conj, Ps[l] <- Rs[l]' (Rs[l] keeps its values: the reference's literal pair of assignments), the
+// coarsest solve for the adjoint operator, then the finalization path.  Every refusal precedes the first write.
+int cx_adjoint_hierarchy(mg_hierarchy* h, CxWant want) {
+  MG_TRY(cx_handle_ok(h, want));
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  const int nl = (int)h->nlevels;
+  for (int l = 0; l < nl; ++l) {
+    const CxLevel& L = S.lev[(size_t)l];
+    if (L.A.wide || (l + 1 < nl && (L.P.wide || L.R.wide)))
+      return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers: the device adjoint serves int32 operators (upload the adjoint hierarchy)", l + 1);
+  }
+  if (S.coarse_lu) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is held as sparse factors: upload the adjoint hierarchy");
+  if (h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is a Schwarz sweep (mg_set_coarse_dd): set the adjoint hierarchy up again");
+  (void)hipSetDevice(h->device);
+  const hipStream_t st = h->play->stream;
+  HIP_TRY(spin_sync(st));
+  std::vector<CxAdjPlan> planA((size_t)nl), planR((size_t)std::max(nl - 1, 0));
+  for (int l = 0; l < nl; ++l) {
+    MG_TRY(cx_adj_plan(h, S.lev[(size_t)l].A, "As", l + 1, planA[(size_t)l]));
+    if (l + 1 < nl) MG_TRY(cx_adj_plan(h, S.lev[(size_t)l].R, "Rs", l + 1, planR[(size_t)l]));
+  }
+  // from here on a failure (allocation, HIP) leaves a partly flipped hierarchy: the handle is unfinalized first, so that every entry
+  // point refuses it until the caller has uploaded again (the header says so)
+  S.finalized = false;
+  for (int l = 0; l < nl; ++l) {
+    CxLevel& L = S.lev[(size_t)l];
+    const auto t0 = std::chrono::steady_clock::now();
+    MG_TRY(cx_adj_apply(h, L.A, planA[(size_t)l], L.A));   // (waited for: the host clock around it is the level's device time)
+    if (h->opt.debug_format)
+      std::fprintf(stderr, "[mgvcycle] adjoint As[%d]: %lld x %lld, %lld non-zeros, %d row blocks, %.3f ms\n", l + 1, L.A.n_rows, L.A.n_cols, L.A.nnz,
+                   L.A.nblocks, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (l + 1 == nl) break;
+    MG_TRY(cx_adj_apply(h, L.R, planR[(size_t)l], L.P));
+    if (S.single) hipLaunchKernelGGL(mgk::cx_conj32, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, st, cxp<cf_t>(L.d), L.n);
+    else hipLaunchKernelGGL(mgk::cx_conj, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, st, cxp(L.d), L.n);
+    HIP_TRY(hipGetLastError());
+  }
+  const long long nc = S.n_coarse;
+  if (S.coarse_gmres) {   // param.LU <- conj(param.LU)  (MGsetup.jl:304-305)
+    hipLaunchKernelGGL(mgk::cx_conj, dim3(cx_grid(nc)), dim3(mgk::BLK), 0, st, cxp(S.cgD), nc);
+  } else {                // (A')^-1 = (A^-1)'
+    hipLaunchKernelGGL(mgk::cx_dense_adjoint_inplace, dim3(cx_grid(nc * nc)), dim3(mgk::BLK), 0, st, cxp(S.Ainv), (int)nc);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(spin_sync(st));
+  // scratch sizes and shape checks again; a CF32 handle's widened coarsest operator (cgA) is rebuilt from the new As[end] and its
+  // widened Krylov operator (K_auto) dropped, to be widened from the new As[1] by the next driver call
+  return cx_finalize(h);
+}
+
 // mg_create_CF64 / mg_create_CF32
 int cx_create(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out, bool single) {
   if (!out) return fail(MG_ERR_INVALID, "out is null");
@@ -1930,6 +2082,18 @@ int mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n) {
     out[l] = (double)ms;
   }
   return MG_OK;
+}
+
+// adjointHierarchy (MGsetup.jl:274-318 for complex VAL) on the resident hierarchy, in HBM: see include/mgvcycle.h
+int mg_adjoint_hierarchy_CF64(mg_hierarchy* h) {
+  MG_TRY(cx_handle_ok(h, CX_WANT64));   // (a null handle is answered without touching the device)
+  UploadFence upload_fence;
+  return cx_adjoint_hierarchy(h, CX_WANT64);
+}
+int mg_adjoint_hierarchy_CF32(mg_hierarchy* h) {
+  MG_TRY(cx_handle_ok(h, CX_WANT32));
+  UploadFence upload_fence;
+  return cx_adjoint_hierarchy(h, CX_WANT32);
 }
 
 int mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz) {

@@ -217,6 +217,8 @@ SIGNATURES = {
     "mg_get_values_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
     "mg_get_relax_CF64": (C.c_int, [_vp, _ll, _dp, _ll]),
     "mg_replace_values_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
+    "mg_adjoint_hierarchy_CF64": (C.c_int, [_vp]),
+    "mg_adjoint_hierarchy_CF32": (C.c_int, [_vp]),
     "mg_bicgstab_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_bicgstab_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_fgmres_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
@@ -954,7 +956,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             raise
 
     def _set_op(self, level, which, M):
-        self._op_nnz[(int(level), int(which))] = int(M.nnz)     # (get_values sizes its array by it; patterns never change)
+        self._op_nnz[(int(level), int(which))] = int(M.nnz)     # (get_values sizes its array by it; adjoint_hierarchy updates P's)
         if which != MG_OP_A:
             if np.iscomplexobj(M.data):
                 raise TypeError("P and R of a ComplexF64 hierarchy are real")
@@ -1394,6 +1396,16 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         if timings is not None:
             timings.update(rap=t1 - t0, readback=t2 - t1, coarsest=time.perf_counter() - t2)
 
+    def adjoint_hierarchy(self, param) -> None:
+        """adjointHierarchy on the resident hierarchy (mg_adjoint_hierarchy_CF64 / _CF32): every operator replaced by its conjugate
+        transpose in HBM, relaxPrecs conjugated, Ps[l] <- Rs[l]', the dense coarsest inverse or the GMRES coarsest vector flipped
+        in place.  ``param`` is the host mirror ALREADY flipped (mgsetup.adjointHierarchy calls this last): its Ps give the sizes
+        ``get_values`` needs.  Raises MGDeviceError where the library refuses (sparse coarsest factors, a Schwarz coarsest solve,
+        64-bit row pointers, a column of more than 4096 entries); the handle then cycles with its old bits."""
+        _check(self.lib, self._fn("adjoint_hierarchy")(self.handle), f"mg_adjoint_hierarchy_{self._sfx}")
+        for l in range(1, self.nlevels):
+            self._op_nnz[(l, MG_OP_P)] = int(param.Ps[l - 1].nnz)
+
     def rap_level_ms(self) -> np.ndarray:
         """Device milliseconds of the last replace_matrix per level (relaxPrecs[l] and As[l+1] together; mg_rap_level_ms_CF64)."""
         out = np.zeros(self.nlevels - 1)
@@ -1402,7 +1414,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def _refuse(self, *args, **kwargs):
         raise NotImplementedError("PCG, block PCG / FGMRES, transposeHierarchy and the other device-pointer entry points serve "
-                                  "FP64 hierarchies only (ComplexF64: bicgstab, fgmres, cycle_dev and their _dev forms; block_spmv, "
+                                  "FP64 hierarchies only (ComplexF64: adjoint_hierarchy; bicgstab, fgmres, cycle_dev and their _dev forms; block_spmv, "
                                   "block_cycle, block_solve, block_cycle_dev, block_bicgstab, block_bicgstab_dev_CFP64; replace_matrix, "
                                   "replace_values, get_values)")
 

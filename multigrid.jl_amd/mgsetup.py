@@ -2,7 +2,7 @@
 
 Mirrors reference src/Multigrid/MGsetup.jl: ``MGsetup`` (l.7-138), ``getRelaxPrec`` (l.142-160),
 ``adjustMemoryForNumRHS`` (l.166-223), ``replaceMatrixInHierarchy`` (l.226-270),
-``transposeHierarchy`` (l.274-318), ``defineCoarsestAinv`` (l.323-355), ``getSPAIprec`` (l.359-362).
+``transposeHierarchy`` (l.274-318; ``adjointHierarchy``: the same lines for complex VAL), ``defineCoarsestAinv`` (l.323-355), ``getSPAIprec`` (l.359-362).
 
 The hierarchy is built on the CPU "exactly as the reference does" (BASELINE.json north_star); the
 cycle itself never runs here - it is owned by the HIP library (``device.py``).
@@ -352,5 +352,53 @@ def transposeHierarchy(param: MGparam, verbose: bool = False) -> None:
         from .device import MGDeviceError
         try:
             param.device.transpose_hierarchy()
+        except MGDeviceError:
+            _release_device(param)
+
+
+def _adjoint_csr(M):
+    """``sparse(M')`` as this package holds operators: CSR of conj(M)^T with sorted indices, M's dtype kept."""
+    T = sp.csr_matrix(M.conj().T, dtype=M.dtype)
+    T.sort_indices()
+    return T
+
+
+def adjointHierarchy(param: MGparam, verbose: bool = False) -> None:
+    """``transposeHierarchy`` (MGsetup.jl:274-318) for complex VAL, where ``'`` is the adjoint: As[l] <- As[l]' (the conjugate
+    transpose) on every level, relaxPrecs[l] <- conj(relaxPrecs[l]), Ps[l] <- Rs[l]', Rs[l] <- (new Ps[l])' (Rs keeps its values: the
+    reference's literal pair of assignments), doTranspose flipped.  Coarsest solve: ``param.LU <- conj(param.LU)`` for
+    coarseSolveType "GMRES" (l.304-305), else the factorisation of the new As[end] (a preset solver object is replaced, as
+    ``transposeHierarchy`` does it).  Serves ComplexF64 params and ``singlePrecision`` ones (dtypes kept); a real param is
+    ``transposeHierarchy``'s.  A resident hierarchy is flipped in HBM (mg_adjoint_hierarchy_CF64 / _CF32); what the library refuses
+    there (sparse coarsest factors, a Schwarz coarsest solve) falls back to the lazy re-upload."""
+    if not is_complex(param):
+        raise TypeError("adjointHierarchy serves complex params (VAL=ComplexF64, singlePrecision or not): a real hierarchy is "
+                        "flipped by transposeHierarchy")
+    if _is_vanka(param):
+        raise NotImplementedError("adjointHierarchy of a Vanka hierarchy (the reference refuses it too: MGsetup.jl:288-292)")
+    if param.relaxType not in ("Jac", "Jac-GMRES", "SPAI"):
+        raise RuntimeError("Not supported")
+    if len(param.As) == 0:
+        raise RuntimeError("The Hierarchy is empty - run a setup first.")
+    param.As[0] = _adjoint_csr(param.As[0])
+    param.doTranspose = (param.doTranspose + 1) % 2
+    for l in range(1, param.levels):
+        if verbose:
+            print("MG transpose level: ", l)
+        param.relaxPrecs[l - 1] = np.conj(param.relaxPrecs[l - 1])
+        newP = _adjoint_csr(param.Rs[l - 1])              # (real: the transpose, float32 kept for a single hierarchy)
+        param.Ps[l - 1] = newP
+        param.Rs[l - 1] = _adjoint_csr(newP)
+        param.As[l] = _adjoint_csr(param.As[l])
+    if param.coarseSolveType == "GMRES" and isinstance(param.LU, np.ndarray):
+        param.LU = np.conj(param.LU)                      # MGsetup.jl:304-305
+    else:
+        destroyCoarsestLU(param)
+        param.LU = None        # MGsetup.jl:310-311 factors the adjoint coarsest matrix itself: a solver object is replaced
+        defineCoarsestAinv(param, param.As[-1])
+    if param.device is not None:
+        from .device import MGDeviceError
+        try:
+            param.device.adjoint_hierarchy(param)
         except MGDeviceError:
             _release_device(param)

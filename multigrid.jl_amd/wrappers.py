@@ -16,7 +16,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .mgdef import MGparam, clear_, copySolver as _copy_param, hierarchyExists, is_complex
-from .mgsetup import MGsetup, transposeHierarchy
+from .mgsetup import MGsetup, adjointHierarchy, transposeHierarchy
 from .sa_amg import SA_AMGsetup
 from .solve_funcs import solveBiCGSTAB_MG, solveBiCGSTAB_MG_CFP64, solveBlockBiCGSTAB_MG_CFP64, solveCG_MG, solveGMRES_MG, solveGMRES_MG_CFP64, solveMG
 
@@ -50,7 +50,12 @@ def getSA_AMGsolver(MG: MGparam, Krylov: str = "BiCGSTAB", sym: int = 1, out: in
 
 
 def solveLinearSystem_(A, B: np.ndarray, X: np.ndarray, param: MGsolver, doTranspose: int = 0):
-    """``solveLinearSystem!(A,B,X,param,doTranspose)`` (MGWrapper.jl:27-86 / SAAMGWrapper.jl:26-78): X in place."""
+    """``solveLinearSystem!(A,B,X,param,doTranspose)`` (MGWrapper.jl:27-86 / SAAMGWrapper.jl:26-78): X in place.
+
+    ``doTranspose = 1`` solves with ``A'``: the transpose for a real solver, the ADJOINT ``conj(A)^T`` for a complex one (Julia's
+    ``'``).  A complex solver with ``sym != 1`` whose hierarchy stands the other way round is flipped by ``adjointHierarchy`` (a
+    resident hierarchy in HBM), a real one by ``transposeHierarchy``.  The drivers apply the hierarchy's own fine level; a system
+    operator the caller set separately with ``device.set_krylov_operator`` is the caller's to transpose."""
     if sp.issparse(B):
         B = np.asarray(B.todense())
     if B.ndim == 2 and B.shape[1] == 1:
@@ -72,7 +77,7 @@ def solveLinearSystem_(A, B: np.ndarray, X: np.ndarray, param: MGsolver, doTrans
         # of the operator, tests/test_host_api.py: As[1] == R*A*P), so the operator to hand over is A for
         # doTransposeIterative == 0 and A' for 1: the condition is the other way round.
         if param.sym != 1 and doTi == 1:
-            A = sp.csr_matrix(A.T)
+            A = sp.csr_matrix(A.conj().T) if is_complex(param.MG) else sp.csr_matrix(A.T)
         t0 = time.perf_counter()
         if param.kind == "SA":
             SA_AMGsetup(A, param.MG, param.sym == 1, nrhs, verbose)
@@ -82,7 +87,10 @@ def solveLinearSystem_(A, B: np.ndarray, X: np.ndarray, param: MGsolver, doTrans
         param.MG.doTranspose = doTranspose
     if param.sym != 1 and doTranspose != param.MG.doTranspose:
         t0 = time.perf_counter()
-        transposeHierarchy(param.MG)
+        if is_complex(param.MG):
+            adjointHierarchy(param.MG)
+        else:
+            transposeHierarchy(param.MG)
         param.timeSetup += time.perf_counter() - t0
     t0 = time.perf_counter()
     Bf = np.asfortranarray(B)
