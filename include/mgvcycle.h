@@ -969,7 +969,7 @@ mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r
  * iteration: BiCGSTAB 4, FGMRES 1 per inner step.  Refused: an FP64 handle or a handle not finalized (MG_ERR_STATE); a null
  * vector, maxIter < 0, a wrong n, inner outside [1,64], a device vector off a 16-byte boundary (MG_ERR_INVALID).  Not served
  * for complex values: PCG (the operators in question are not Hermitian positive definite).  These entry points take one right-hand
- * side; a block of them goes to mg_block_bicgstab[_dev]_CFP64 (at the end of this header; block FGMRES is not served). */
+ * side; a block of them goes to mg_block_bicgstab[_dev]_CFP64 / mg_block_fgmres[_dev]_CFP64 (at the end of this header). */
 int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long long* colptr, const long long* rowval,
                                        const double* nzval);
 /* New values (nnz complex, the AT convention) on the pattern of the Krylov operator set last: a copy and one conjugation in HBM,
@@ -1011,6 +1011,11 @@ int mg_cvec_bicg_xr_dev_CFP64(const double* alpha, const double* omega, const do
                               double* workspace_dev, double* out_dev, void* stream);
 int mg_cvec_gs_update_dev_CFP64(long long m, const double* h_host, const double* const* vs_dev, double* w, long long n,
                                 double* workspace_dev, double* out_dev, void* stream);
+/* The one-pass Gram kernel of mg_block_fgmres_CFP64 on its own: out_dev (k x k complex, row-major) = X^H Y for two row-major device
+ * blocks [n][k] on a 16-byte boundary, 1 <= k <= 16 (k < 1, n < 1: MG_ERR_INVALID; k > 16: MG_ERR_UNSUPPORTED); x_dev == y_dev is
+ * served and reads the block once.  Asynchronous on `stream`; a deterministic two-stage sum.  workspace_dev: 2048 * k * k doubles. */
+int mg_cblk_gram_dev_CFP64(const double* x_dev, const double* y_dev, long long n, long long k, double* workspace_dev,
+                           double* out_dev, void* stream);
 
 /* ---- ComplexF32 hierarchies (CF32): the single-precision cycle inside the ComplexF64 Krylov drivers ------------------------
  * The reference's VAL = ComplexF32 (getMGparam: singlePrecision, MGdef.jl:151; MGsetup.jl:31-33, 79-82, 108-110): As and relaxPrecs
@@ -1052,9 +1057,9 @@ int mg_solve_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long l
 int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float* alpha, const float* x, const float* beta,
                  float* y, long long nrhs);
 
-/* ---- blocks of right-hand sides on complex handles: SpMM cycle, block solveMG, block BiCGSTAB -----------------------------------
+/* ---- blocks of right-hand sides on complex handles: SpMM cycle, block solveMG, block BiCGSTAB, block FGMRES ---------------------
  * What the reference does with size(b,2) > 1 for VAL = ComplexF64: one cycle on the whole block (getMultigridPreconditioner,
- * SolveFuncs.jl:43-63), solveMG with Frobenius norms (l.14-36), KrylovMethods.blockBiCGSTB (l.94-96).  k sources then share one pass
+ * SolveFuncs.jl:43-63), solveMG with Frobenius norms (l.14-36), KrylovMethods.blockBiCGSTB (l.94-96), KrylovMethods.blockFGMRES (l.130).  k sources then share one pass
  * over every operator instead of streaming it k times.
  *
  * nrhs arrives WITH EACH CALL, 1 <= nrhs <= 16; the handle's own nrhs stays 1 and every entry point above keeps refusing nrhs > 1.
@@ -1078,11 +1083,18 @@ int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float*
  *   flag 0 converged, -1 maxIter, -2 breakdown (singular R0^H V, T = 0 or omega = 0), -3 converged on the half step, -9 B = 0 (X = 0);
  *   resvec (up to 2*maxIter + 1 entries, nres of them written): max_j ||r_j|| / ||b_j|| at the start, after every half and full step.
  *   On a CF32 handle every Krylov block stays ComplexF64.
+ * mg_block_fgmres[_dev]_CFP64: blockFGMRES(inner) with the arguments of mg_block_fgmres[_dev]_FP64 on the same operator and M: block
+ *   modified Gram-Schmidt with H_ij = V_i^H W, Cholesky QR applied twice (pivots at or below 1e-14 G[c][c] dropped), the exact block
+ *   least squares on the host after every inner step.  Every Gram operand is read from HBM once, and every Gram matrix but the first
+ *   of an inner step is left by the update before it (csrc/mg_complex.hpp: cx_blk_gram_onepass, cx_blk_comb_gram; above 8
+ *   columns, where the fused kernel measured slower, the update and the one-pass kernel are two launches); inner step j
+ *   synchronises the host j + 3 times.  inner in [1,64] (MG_ERR_INVALID otherwise); work set 2*inner + 2 blocks.  flag 0 converged,
+ *   -1 maxIter, -9 B = 0 (X = 0); iters: inner steps in all; resvec (up to maxIter*inner entries): ||xi - H Y||_F / ||B||_F per inner step.
  * Coarsest solve: the dense inverse, the one-workgroup triangular sweeps or the chip-wide factor applier, each on the whole block.
  * Refused: nrhs < 1 (MG_ERR_INVALID), nrhs > 16 (MG_ERR_UNSUPPORTED), a Schwarz sweep as coarsest solve with nrhs > 1
  * (MG_ERR_UNSUPPORTED), an FP64 handle or a handle that is not finalized (MG_ERR_STATE), a CF32 handle in the _CF64 forms
  * (MG_ERR_STATE), a null block, a wrong n, maxIter < 0, a device block off a 16-byte boundary (MG_ERR_INVALID).  A refusal leaves the
- * handle usable.  Not served for complex blocks: FGMRES, PCG, the K-cycle and Jac-GMRES, the sharded forms, HIP graphs.
+ * handle usable.  Not served for complex blocks: PCG, the K-cycle and Jac-GMRES, the sharded forms, HIP graphs.
  * (The _CF64 forms spell their status mg_status, as the re-setup entry points above do.) */
 mg_status mg_block_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* X,
                              const double* beta, double* Y, long long nrhs);
@@ -1096,6 +1108,11 @@ int mg_block_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long lo
 int mg_block_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs,
                                 double tol, long long maxIter, long long* iters, long long* flag, double* resvec,
                                 long long* nres);
+int mg_block_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long inner,
+                          double tol, long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres);
+int mg_block_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs,
+                              long long inner, double tol, long long maxIter, long long* iters, long long* flag,
+                              double* resvec, long long* nres);
 
 const char* mg_last_error(void);
 const char* mg_version(void);

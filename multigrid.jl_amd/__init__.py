@@ -12,7 +12,7 @@ from .transfer_operators import (getFWInterp, get1DFWInterp, restrictCellCentere
                                  getRestrictionCellCentered)
 from .sa_amg import (SA_AMGsetup, getAggregation, getStrengthMatrix, neighborhoodAggregationNew, aggrArray2P)
 from .solve_funcs import (solveMG, solveCG_MG, solveBiCGSTAB_MG, solveGMRES_MG, solveBiCGSTAB_MG_CFP64, solveGMRES_MG_CFP64, solveBlockBiCGSTAB_MG_CFP64,
-                          recursiveCycle, SpMatMul, getMultigridPreconditioner, to_device)
+                          solveBlockGMRES_MG_CFP64, recursiveCycle, SpMatMul, getMultigridPreconditioner, to_device)
 from .operators import (getRegularMesh, getNodalGradientMatrix, getNodalLaplacianMatrix,
                         getNodalDivSigGradMatrix, poisson_shifted, anisotropic_divsiggrad, seeded_rhs)
 from .wrappers import (MGsolver, getMGsolver, getSA_AMGsolver, solveLinearSystem_, setupSolver, copySolverWrapper,

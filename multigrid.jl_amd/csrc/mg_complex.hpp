@@ -502,6 +502,154 @@ __global__ __launch_bounds__(BLK) void cx_blk_comb(d2_t* out, const d2_t* add, d
   }
 }
 
+// The Gram kernels of the complex block FGMRES driver (mg_complex_krylov.inc: cx_block_fgmres_dev), which needs j + 3 Gram matrices
+// per inner step j.  cx_blk_gram_partial above runs k workgroup rows that each stream the whole of Y again; these read every
+// element of X and of Y from HBM ONCE (X == Y: once in all).
+//   cx_blk_gram_onepass:  G = X^H Y.  A workgroup stages a tile of GRAM_TILE / kk rows of X and of Y in LDS (kk = pow2 >= k; a tile is
+//     one contiguous run of at most GRAM_TILE entries, 16 KiB per operand, loaded coalesced and prefetched into registers one tile
+//     ahead).  The BLK lanes form BLK / kk^2 groups of kk^2 lanes; lane e of a group owns entry (a, b) = (e / kk, e % kk) and sums
+//     it over the tile rows r = group, group + groups, ... in ONE register: a lane holds one accumulator, never k^2.  The reads of
+//     sx[r][a] are a broadcast over kk lanes, those of sy[r][b] kk consecutive 16-byte words.  At the end the groups are added in
+//     group order through LDS and the workgroup writes one k x k partial; cx_blk_gram_final_wave adds the partials, one wavefront
+//     per entry.  Every entry is a sum in a fixed order: rows of a lane in order, groups in order, workgroups in the final kernel's
+//     fixed order - no atomics.
+//   cx_blk_comb_gram:  cx_blk_comb (the same operations in the same order, so the same bits in `out`) with an epilogue that leaves
+//     the partials of G = Q^H out, Q == out or a block that overlaps none of the others: every lane puts the row of `out` it has just
+//     written (from its registers) and its row of Q into the staged tile, GRAM_TILE / kk rows per round, and the workgroup sums the
+//     tile as above.  `out` is not read again from HBM.
+constexpr int GRAM_TILE = 1024;
+struct GramLane {
+  int a, b, g, groups;
+  bool on;
+  __device__ __forceinline__ GramLane(int k, int lgk) {
+    const int e = threadIdx.x & ((1 << (2 * lgk)) - 1);
+    a = e >> lgk;
+    b = e & ((1 << lgk) - 1);
+    g = threadIdx.x >> (2 * lgk);
+    groups = BLK >> (2 * lgk);
+    on = a < k && b < k;
+  }
+};
+__device__ __forceinline__ void cx_gram_tile(const d2_t* sx, const d2_t* sy, int rows, int k, const GramLane& L, d2_t& acc) {
+  if (!L.on) return;
+  for (int r = L.g; r < rows; r += L.groups) {
+    const d2_t xa = sx[r * k + L.a];
+    acc += cmul(d2_t{xa.x, -xa.y}, sy[r * k + L.b]);
+  }
+}
+__device__ __forceinline__ void cx_gram_store(d2_t* red, d2_t acc, int k, const GramLane& L, d2_t* __restrict__ partial) {
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  if (L.g == 0 && L.on) {
+    const int kk2 = BLK / L.groups;
+    d2_t t = d2_t{0.0, 0.0};
+    for (int g = 0; g < L.groups; ++g) t += red[g * kk2 + threadIdx.x];
+    partial[(size_t)blockIdx.x * k * k + L.a * k + L.b] = t;
+  }
+}
+// the partials of nb workgroups added per entry by ONE WAVEFRONT (grid: k * k workgroups of 64 lanes): lane l adds the partials
+// l, l + 64, ... in that order, the 64 lane sums are added by a fixed butterfly - a fixed order again, and a few microseconds where
+// the one lane per entry of cx_blk_gram_final walks the partials one load latency at a time
+__global__ __launch_bounds__(64) void cx_blk_gram_final_wave(const d2_t* __restrict__ partial, int nb, int k, d2_t* __restrict__ out) {
+  const int e = blockIdx.x;   // entry a*k + b
+  d2_t t = d2_t{0.0, 0.0};
+  for (int p = threadIdx.x; p < nb; p += 64) t += partial[(size_t)p * k * k + e];
+  for (int o = 32; o > 0; o >>= 1) t += shfl_xor_v(t, o);
+  if (threadIdx.x == 0) out[e] = t;
+}
+__global__ __launch_bounds__(BLK) void cx_blk_gram_onepass(const d2_t* X, const d2_t* Y, long long n, int k, int lgk, d2_t* __restrict__ partial) {
+  __shared__ d2_t sx[GRAM_TILE], sy[GRAM_TILE], red[BLK];
+  constexpr int PER = GRAM_TILE / BLK;
+  const int tid = threadIdx.x;
+  const GramLane L(k, lgk);
+  const bool same = X == Y;
+  const int tr = GRAM_TILE >> lgk;                 // rows of a tile
+  const int tlen = tr * k;                         // its entries (<= GRAM_TILE)
+  const long long ntiles = (n + tr - 1) / tr, total = n * k;
+  d2_t px[PER], py[PER];
+  long long tile = blockIdx.x;
+#pragma unroll
+  for (int it = 0; it < PER; ++it) {
+    const int l = it * BLK + tid;
+    const long long idx = tile * tlen + l;
+    const bool ok = tile < ntiles && l < tlen && idx < total;
+    px[it] = ok ? X[idx] : d2_t{0.0, 0.0};
+    py[it] = (ok && !same) ? Y[idx] : d2_t{0.0, 0.0};
+  }
+  d2_t acc = d2_t{0.0, 0.0};
+  for (; tile < ntiles; tile += gridDim.x) {
+#pragma unroll
+    for (int it = 0; it < PER; ++it) {
+      sx[it * BLK + tid] = px[it];
+      if (!same) sy[it * BLK + tid] = py[it];
+    }
+    __syncthreads();
+    const long long next = tile + gridDim.x;       // the next tile's loads are in flight while this one is summed
+#pragma unroll
+    for (int it = 0; it < PER; ++it) {
+      const int l = it * BLK + tid;
+      const long long idx = next * tlen + l;
+      const bool ok = next < ntiles && l < tlen && idx < total;
+      px[it] = ok ? X[idx] : d2_t{0.0, 0.0};
+      py[it] = (ok && !same) ? Y[idx] : d2_t{0.0, 0.0};
+    }
+    const int rows = (int)((n - tile * tr) < (long long)tr ? (n - tile * tr) : (long long)tr);
+    cx_gram_tile(sx, same ? sx : sy, rows, k, L, acc);
+    __syncthreads();
+  }
+  cx_gram_store(red, acc, k, L, partial);
+}
+__global__ __launch_bounds__(BLK) void cx_blk_comb_gram(d2_t* out, const d2_t* add, d2_t s, const d2_t* in, const d2_t* __restrict__ Cm,
+                                                        const d2_t* Q, long long n, int k, int lgk, d2_t* __restrict__ partial) {
+  __shared__ d2_t sc[BLK_KMAX * BLK_KMAX];
+  __shared__ d2_t sx[GRAM_TILE], sy[GRAM_TILE], red[BLK];
+  const int tid = threadIdx.x;
+  for (int t = tid; t < k * k; t += BLK) sc[t] = Cm[t];
+  __syncthreads();
+  const GramLane L(k, lgk);
+  const bool self = Q == out;
+  const int rpr = (GRAM_TILE >> lgk) < BLK ? (GRAM_TILE >> lgk) : BLK;   // rows of a round
+  d2_t acc = d2_t{0.0, 0.0};
+  const long long stride = (long long)gridDim.x * BLK;
+  for (long long base = (long long)blockIdx.x * BLK; base < n; base += stride) {   // (uniform over the workgroup)
+    const long long i = base + tid;
+    const bool live = i < n;
+    d2_t row[BLK_KMAX], o[BLK_KMAX];
+    if (live) {
+#pragma unroll
+      for (int a = 0; a < BLK_KMAX; ++a) row[a] = a < k ? in[i * k + a] : d2_t{0.0, 0.0};
+#pragma unroll
+      for (int b = 0; b < BLK_KMAX; ++b) o[b] = (b < k && add) ? cmul(s, add[i * k + b]) : d2_t{0.0, 0.0};
+#pragma unroll
+      for (int a = 0; a < BLK_KMAX; ++a)
+        if (a < k) {
+#pragma unroll
+          for (int b = 0; b < BLK_KMAX; ++b)
+            if (b < k) o[b] += cmul(row[a], sc[a * k + b]);
+        }
+#pragma unroll
+      for (int b = 0; b < BLK_KMAX; ++b)
+        if (b < k) out[i * k + b] = o[b];
+    }
+    const int here = (int)((n - base) < (long long)BLK ? (n - base) : (long long)BLK);   // rows of this trip
+    for (int r0 = 0; r0 < here; r0 += rpr) {
+      if (live && tid >= r0 && tid < r0 + rpr) {
+        const int lr = tid - r0;
+#pragma unroll
+        for (int b = 0; b < BLK_KMAX; ++b)
+          if (b < k) {
+            sy[lr * k + b] = o[b];
+            if (!self) sx[lr * k + b] = Q[i * k + b];
+          }
+      }
+      __syncthreads();
+      cx_gram_tile(self ? sy : sx, sy, (here - r0) < rpr ? (here - r0) : rpr, k, L, acc);
+      __syncthreads();
+    }
+  }
+  cx_gram_store(red, acc, k, L, partial);
+}
+
 // x = d.*b: relax's only update when the sweep starts from x = 0 (MGcycle.jl:134 with r = b)
 template <typename C>
 __global__ __launch_bounds__(BLK) void cx_dscale(const C* __restrict__ d, const C* __restrict__ b, C* __restrict__ x, long long n) {

@@ -344,13 +344,13 @@ struct CxBlkKry {
     return MG_OK;
   }
   cx_t* blk(size_t i) { return cxp(S.Bkwork) + i * len(); }
-  // G = X^H Y to the host; synchronises the stream
-  int gram(const cx_t* X, const cx_t* Y, CMat& G) {
-    const int nb = nblocks();
+  // the k x k matrix the partials of nb workgroups add up to (cx_blk_gram_final: workgroup order), on the host; synchronises the stream
+  // (wave: block FGMRES's final kernel, one wavefront per entry - another fixed order, so block BiCGSTAB keeps the one it had)
+  int gram_read(int nb, CMat& G, bool wave = false) {
     cx_t* part = cxp(S.Bgpart);
     cx_t* out = part + (size_t)nb * k * k;
-    hipLaunchKernelGGL(mgk::cx_blk_gram_partial, dim3(nb, k), dim3(mgk::BLK), 0, st, X, Y, n, k, part);
-    hipLaunchKernelGGL(mgk::cx_blk_gram_final, dim3(1), dim3(mgk::BLK), 0, st, part, nb, k, out);
+    if (wave) hipLaunchKernelGGL(mgk::cx_blk_gram_final_wave, dim3(k * k), dim3(64), 0, st, part, nb, k, out);
+    else hipLaunchKernelGGL(mgk::cx_blk_gram_final, dim3(1), dim3(mgk::BLK), 0, st, part, nb, k, out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(S.h_bgram, out, sizeof(cx_t) * k * k, hipMemcpyDeviceToHost, st));
     HIP_TRY(spin_sync(st));
@@ -358,8 +358,14 @@ struct CxBlkKry {
     for (int e = 0; e < k * k; ++e) G.a[(size_t)e] = zc(S.h_bgram[2 * e], S.h_bgram[2 * e + 1]);
     return MG_OK;
   }
-  // out = s*add + in*Cm (add may be null; out may alias in or add): a ring of 8 coefficient slots, drained once per lap (blk_comb)
-  int comb(cx_t* out, const cx_t* add, zc s, const cx_t* in, const CMat& Cm) {
+  // G = X^H Y to the host; synchronises the stream
+  int gram(const cx_t* X, const cx_t* Y, CMat& G) {
+    const int nb = nblocks();
+    hipLaunchKernelGGL(mgk::cx_blk_gram_partial, dim3(nb, k), dim3(mgk::BLK), 0, st, X, Y, n, k, cxp(S.Bgpart));
+    return gram_read(nb, G);
+  }
+  // the next of the ring of 8 coefficient slots, Cm on its way into it; the ring is drained once per lap (blk_comb)
+  int coef(const CMat& Cm, cx_t** slot_out) {
     const unsigned si = S.bcoef_next++ % 8;
     if (si == 0 && S.bcoef_next > 1) HIP_TRY(spin_sync(st));
     double* hs = S.h_bcoef + 2 * SLOT * si;
@@ -369,8 +375,62 @@ struct CxBlkKry {
       hs[2 * e + 1] = Cm.a[(size_t)e].imag();
     }
     HIP_TRY(hipMemcpyAsync(slot, hs, sizeof(cx_t) * k * k, hipMemcpyHostToDevice, st));
+    *slot_out = slot;
+    return MG_OK;
+  }
+  // out = s*add + in*Cm (add may be null; out may alias in or add)
+  int comb(cx_t* out, const cx_t* add, zc s, const cx_t* in, const CMat& Cm) {
+    cx_t* slot = nullptr;
+    MG_TRY(coef(Cm, &slot));
     hipLaunchKernelGGL(mgk::cx_blk_comb, dim3(cx_grid(n)), dim3(mgk::BLK), 0, st, out, add, cxv(s), in, slot, n, k);
     HIP_TRY(hipGetLastError());
+    return MG_OK;
+  }
+  // ---- block FGMRES: every element of a Gram operand read once (cx_blk_gram_onepass), and the combination whose epilogue leaves
+  //      the next Gram matrix (cx_blk_comb_gram); up to GRAM_WGS workgroups, several per CU, whose partials need a larger Bgpart
+  //      than gram()'s (ensure_gram) ----
+  static constexpr int GRAM_WGS = 1024;
+  int ensure_gram() {
+    const size_t gneed = 2 * ((size_t)GRAM_WGS + 1) * SLOT;
+    if (S.Bgpart.n < gneed) MG_TRY(S.Bgpart.alloc(gneed));
+    return MG_OK;
+  }
+  int lgk() const {
+    int l = 0;
+    while ((1 << l) < k) ++l;
+    return l;
+  }
+  int gram_onepass(const cx_t* X, const cx_t* Y, CMat& G) {
+    const long long tr = mgk::GRAM_TILE >> lgk();
+    const int nb = (int)std::min<long long>(GRAM_WGS, (n + tr - 1) / tr);
+    hipLaunchKernelGGL(mgk::cx_blk_gram_onepass, dim3(nb), dim3(mgk::BLK), 0, st, X, Y, n, k, lgk(), cxp(S.Bgpart));
+    return gram_read(nb, G, true);
+  }
+  // out = s*add + in*Cm as comb, and G = Q^H out to the host (Q == out, or a block apart from the others); synchronises the stream
+  // Above 8 columns the fused kernel measured slower than the two launches (profiles/complex_block_fgmres.md: 0.99 ms against
+  // 0.57 + 0.26 ms at 16 columns; level at 8, ahead at 4 and 2), so there the update and the one-pass Gram matrix stay apart.
+  int comb_gram(cx_t* out, const cx_t* add, zc s, const cx_t* in, const CMat& Cm, const cx_t* Q, CMat& G) {
+    if (k > 8) {
+      MG_TRY(comb(out, add, s, in, Cm));
+      return gram_onepass(Q, out, G);
+    }
+    cx_t* slot = nullptr;
+    MG_TRY(coef(Cm, &slot));
+    const int nb = (int)std::min<long long>(GRAM_WGS, (n + mgk::BLK - 1) / mgk::BLK);
+    hipLaunchKernelGGL(mgk::cx_blk_comb_gram, dim3(nb), dim3(mgk::BLK), 0, st, out, add, cxv(s), in, slot, Q, n, k, lgk(), cxp(S.Bgpart));
+    return gram_read(nb, G, true);
+  }
+  // W -> an orthonormal block in place by Cholesky QR applied twice, Rf with W_in = Q Rf (blk_cholqr); G1: W^H W where the caller
+  // has it already.  The second Gram matrix is the epilogue of the first scaling.
+  int cholqr(cx_t* W, const CMat* G1, CMat& Rf) {
+    CMat G;
+    if (G1) G = *G1;
+    else MG_TRY(gram_onepass(W, W, G));
+    const CMat R1 = sm_chol_semidefinite(G);
+    MG_TRY(comb_gram(W, nullptr, zc(0.0, 0.0), W, sm_tri_pinv(R1), W, G));
+    const CMat R2 = sm_chol_semidefinite(G);
+    MG_TRY(comb(W, nullptr, zc(0.0, 0.0), W, sm_tri_pinv(R2)));
+    Rf = sm_mul(R2, R1);
     return MG_OK;
   }
   int colnorms(const cx_t* X, std::vector<double>& out) {
@@ -479,9 +539,105 @@ int cx_block_bicgstab_dev(mg_hierarchy* h, const cx_t* B, cx_t* X, int k, double
   return rep.finish(it, flag);
 }
 
-// the checks the block driver's entry points share; host form: column-major blocks relaid through the block work set's staging blocks
-int cx_block_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
-                    long long* iters, long long* flag, double* resvec, long long* nres, bool device_form) {
+// blockFGMRES (SolveFuncs.jl:130) for VAL = ComplexF64: block_fgmres_core of mg_krylov.inc line by line on complex blocks.
+// V_0 = cholqr2(R), xi[:k] = Rf; per inner step Z_j = M(V_j), W = A Z_j, block modified Gram-Schmidt against V_0 .. V_j with
+// H_ij = V_i^H W, cholqr2(W), the exact block least squares on the host (sm_lstsq on SmallMatT<zc>) and the estimate
+// ||xi - H Y||_F / ||B||_F; X += sum Z_j Y_j; the true residual at a restart.  Work set: 2*inner + 2 blocks (V: inner + 1, Z: inner, R).
+// Gram matrices: H_0j free-standing (cx_blk_gram_onepass); H_{i+1,j} is the epilogue of W -= V_i H_ij, W^H W that of the last update,
+// and the second Gram matrix of cholqr2 that of its first scaling (cx_blk_comb_gram) - j + 3 per inner step, one host
+// synchronisation each (above 8 columns the epilogues are launches of cx_blk_gram_onepass behind cx_blk_comb, see comb_gram).  At a
+// restart R^H R serves both ||R||_F and the first factor of cholqr2(R).
+int cx_block_fgmres_dev(mg_hierarchy* h, const cx_t* B, cx_t* X, int k, long long inner, double tol, long long maxIter, long long* iters,
+                        long long* flag_out, double* resvec, long long* nres) {
+  CxBlkKry K(h, k);
+  const int m = (int)inner;
+  MG_TRY(K.ensure((size_t)(2 * m + 2)));
+  MG_TRY(K.ensure_gram());
+  const size_t len = K.len();
+  cx_t* Vb = K.blk(0);                       // m+1 blocks
+  cx_t* Zb = K.blk((size_t)m + 1);           // m blocks
+  cx_t* R = K.blk((size_t)2 * m + 1);        // residual
+  long long flag = -1, total = 0;
+  KrylovReport rep(iters, flag_out, resvec, nres);
+  CMat GR;
+  auto fro = [&](const cx_t* blk, double* out) -> int {   // ||blk||_F from the diagonal of blk^H blk, which stays in GR
+    MG_TRY(K.gram_onepass(blk, blk, GR));
+    double s2 = 0.0;
+    for (int j = 0; j < k; ++j) {
+      const double cn = std::sqrt(std::max(0.0, GR(j, j).real()));
+      s2 += cn * cn;
+    }
+    *out = std::sqrt(s2);
+    return MG_OK;
+  };
+  const zc one(1.0, 0.0);
+  double bn = 0.0, rn = 0.0;
+  MG_TRY(fro(B, &bn));
+  if (bn == 0.0) {
+    HIP_TRY(hipMemsetAsync(X, 0, sizeof(cx_t) * len, K.st));
+    HIP_TRY(spin_sync(K.st));
+    return rep.finish(0, -9);
+  }
+  MG_TRY(K.residual(B, X, R));
+  MG_TRY(fro(R, &rn));
+  if (rn / bn < tol) return rep.finish(0, 0);
+  for (long long it = 1; it <= maxIter && flag != 0; ++it) {
+    CMat H((m + 1) * k, m * k), xi((m + 1) * k, k), Rf, Y;
+    MG_TRY(K.copy(Vb, R));
+    MG_TRY(K.cholqr(Vb, &GR, Rf));                                 // (GR = R^H R, left by fro(R))
+    for (int i = 0; i < k; ++i)
+      for (int j = 0; j < k; ++j) xi(i, j) = Rf(i, j);
+    int used = 0;
+    for (int j = 0; j < m; ++j) {
+      cx_t* Vj = Vb + (size_t)j * len;
+      cx_t* Zj = Zb + (size_t)j * len;
+      cx_t* W = Vb + (size_t)(j + 1) * len;
+      MG_TRY(K.prec(Vj, Zj));                                      // Z_j = M(V_j)
+      MG_TRY(K.product(Zj, W));                                    // W = A Z_j
+      CMat Hij, Gn;
+      MG_TRY(K.gram_onepass(Vb, W, Hij));                          // H_0j = V_0^H W
+      for (int i = 0; i <= j; ++i) {                               // block modified Gram-Schmidt
+        for (int a = 0; a < k; ++a)
+          for (int b = 0; b < k; ++b) H(i * k + a, j * k + b) = Hij(a, b);
+        for (zc& v : Hij.a) v = -v;
+        const cx_t* Vi = Vb + (size_t)i * len;
+        MG_TRY(K.comb_gram(W, W, one, Vi, Hij, i < j ? Vi + len : W, Gn));   // W -= V_i H_ij ; V_{i+1}^H W, at the end W^H W
+        Hij = Gn;
+      }
+      CMat Hn;
+      MG_TRY(K.cholqr(W, &Hij, Hn));
+      for (int a = 0; a < k; ++a)
+        for (int b = 0; b < k; ++b) H((j + 1) * k + a, j * k + b) = Hn(a, b);
+      CMat Hb((j + 2) * k, (j + 1) * k), xb((j + 2) * k, k);
+      for (int a = 0; a < Hb.r; ++a) {
+        for (int b = 0; b < Hb.c; ++b) Hb(a, b) = H(a, b);
+        for (int b = 0; b < k; ++b) xb(a, b) = xi(a, b);
+      }
+      const double err = sm_lstsq(Hb, xb, Y) / bn;
+      rep.record(err);
+      ++total;
+      used = j + 1;
+      if (err <= tol) { flag = 0; break; }
+    }
+    for (int j = 0; j < used; ++j) {                               // X += Z_j Y_j
+      CMat Yj(k, k);
+      for (int a = 0; a < k; ++a)
+        for (int b = 0; b < k; ++b) Yj(a, b) = Y(j * k + a, b);
+      MG_TRY(K.comb(X, X, one, Zb + (size_t)j * len, Yj));
+    }
+    if (flag == 0) break;
+    MG_TRY(K.residual(B, X, R));
+    MG_TRY(fro(R, &rn));
+    if (rn / bn <= tol) { flag = 0; break; }
+  }
+  HIP_TRY(spin_sync(K.st));
+  return rep.finish(total, flag);
+}
+
+// the checks the block drivers' entry points share; host form: column-major blocks relaid through the block work set's staging blocks
+// run(B, X, nrhs): the driver on row-major device blocks
+template <class F>
+int cx_block_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long maxIter, bool device_form, F&& run) {
   MG_TRY(cx_block_ready(h, n, nrhs, CX_ANY));
   if (!b || !x) return fail(MG_ERR_INVALID, "null block");
   if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
@@ -491,11 +647,27 @@ int cx_block_krylov(mg_hierarchy* h, const double* b, double* x, long long n, lo
   MG_TRY(cx_block_ensure(h, nr));
   CxState& S = *h->cx;
   if (S.single && !S.K.set) MG_TRY(cx_widen_K(h));   // the Krylov product is never single
-  if (device_form) return cx_block_bicgstab_dev(h, ccx(b), mcx(x), nr, tol, maxIter, iters, flag, resvec, nres);
+  if (device_form) return run(ccx(b), mcx(x), nr);
   MG_TRY(cx_block_upload(h, b, S.Bstage_t, cxp(S.Bstage_b), n, nr));
   MG_TRY(cx_block_upload(h, x, S.Bstage_t, cxp(S.Bstage_x), n, nr));
-  MG_TRY(cx_block_bicgstab_dev(h, cxc(S.Bstage_b), cxp(S.Bstage_x), nr, tol, maxIter, iters, flag, resvec, nres));
+  MG_TRY(run(cxc(S.Bstage_b), cxp(S.Bstage_x), nr));
   return cx_block_download(h, cxc(S.Bstage_x), S.Bstage_t, x, n, nr);
+}
+
+// G = X^H Y by the one-pass kernel on its own (mg_cblk_gram_dev_CFP64): partials in `work`, the k x k result in `out`
+int cx_gram_alone(const cx_t* X, const cx_t* Y, long long n, long long k, cx_t* work, cx_t* out, hipStream_t s) {
+  if (n < 1) return fail(MG_ERR_INVALID, "a complex Gram matrix needs n >= 1");
+  if (k < 1) return fail(MG_ERR_INVALID, "a complex Gram matrix needs k >= 1");
+  if (k > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "complex blocks hold at most %d columns (k=%lld)", mgk::BLK_KMAX, k);
+  MG_TRY(cxv_aligned({X, Y, work, out}));
+  int lg = 0;
+  while ((1 << lg) < k) ++lg;
+  const long long tr = mgk::GRAM_TILE >> lg;
+  const int nb = (int)std::min<long long>(CxBlkKry::GRAM_WGS, (n + tr - 1) / tr);
+  hipLaunchKernelGGL(mgk::cx_blk_gram_onepass, dim3(nb), dim3(mgk::BLK), 0, s, X, Y, n, (int)k, lg, work);
+  hipLaunchKernelGGL(mgk::cx_blk_gram_final_wave, dim3((int)(k * k)), dim3(64), 0, s, work, nb, (int)k, out);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
 }
 
 }  // namespace
@@ -575,11 +747,31 @@ int mg_block_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev
 // half step and after every full step.
 int mg_block_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
                             long long* iters, long long* flag, double* resvec, long long* nres) {
-  return cx_block_krylov(h, b, x, n, nrhs, tol, maxIter, iters, flag, resvec, nres, false);
+  return cx_block_krylov(h, b, x, n, nrhs, maxIter, false, [&](const cx_t* B, cx_t* X, int k) {
+    return cx_block_bicgstab_dev(h, B, X, k, tol, maxIter, iters, flag, resvec, nres);
+  });
 }
 int mg_block_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs, double tol,
                                 long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
-  return cx_block_krylov(h, b_dev, x_dev, n, nrhs, tol, maxIter, iters, flag, resvec, nres, true);
+  return cx_block_krylov(h, b_dev, x_dev, n, nrhs, maxIter, true, [&](const cx_t* B, cx_t* X, int k) {
+    return cx_block_bicgstab_dev(h, B, X, k, tol, maxIter, iters, flag, resvec, nres);
+  });
+}
+// blockFGMRES(inner) on the whole block, arguments as mg_block_fgmres[_dev]_FP64, layout as mg_block_bicgstab[_dev]_CFP64; resvec holds
+// up to maxIter * inner entries, ||xi - H Y||_F / ||B||_F after every inner step; iters is the total number of inner steps.
+int mg_block_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long inner, double tol,
+                          long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
+  return cx_block_krylov(h, b, x, n, nrhs, maxIter, false, [&](const cx_t* B, cx_t* X, int k) {
+    return cx_block_fgmres_dev(h, B, X, k, inner, tol, maxIter, iters, flag, resvec, nres);
+  });
+}
+int mg_block_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs, long long inner,
+                              double tol, long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
+  if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
+  return cx_block_krylov(h, b_dev, x_dev, n, nrhs, maxIter, true, [&](const cx_t* B, cx_t* X, int k) {
+    return cx_block_fgmres_dev(h, B, X, k, inner, tol, maxIter, iters, flag, resvec, nres);
+  });
 }
 
 int mg_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, double tol, long long maxIter,
@@ -642,6 +834,12 @@ int mg_cvec_gs_update_dev_CFP64(long long m, const double* h_host, const double*
   if (m < 1 || m > 64 || !h_host || !vs_dev || !w || n < 1 || !workspace_dev)
     return fail(MG_ERR_INVALID, "gs_update: 1 to 64 vectors, non-null arguments");
   return cxv_gs_update((int)m, h_host, vs_dev, w, n, workspace_dev, out_dev, CXV_STREAM);
+}
+// G = X^H Y of two row-major blocks [n][k] by the one-pass Gram kernel of block FGMRES; workspace_dev: 2048 * k * k doubles,
+// out_dev: the k x k complex result, row-major
+int mg_cblk_gram_dev_CFP64(const double* x_dev, const double* y_dev, long long n, long long k, double* workspace_dev, double* out_dev,
+                           void* stream) {
+  return cx_gram_alone(ccx(x_dev), ccx(y_dev), n, k, mcx(workspace_dev), mcx(out_dev), CXV_STREAM);
 }
 #undef CXV_C
 #undef CXV_STREAM

@@ -253,8 +253,8 @@ struct RelaxLsqC {
 };
 
 // ---- dense helpers of the block drivers ---------------------------------------------------------------------------------------------
-// (S = double: the real block drivers; S = std::complex<double>: the complex block BiCGSTAB of mg_complex_krylov.inc, which uses
-// sm_mul, sm_solve and sm_scaled_identity)
+// (S = double: the real block drivers; S = std::complex<double>: the complex block drivers of mg_complex_krylov.inc - block BiCGSTAB
+// uses sm_mul, sm_solve and sm_scaled_identity, block FGMRES sm_mul and the complex sm_chol_semidefinite, sm_tri_pinv, sm_lstsq)
 template <class S>
 struct SmallMatT {   // row-major dense helper, host
   int r = 0, c = 0;
@@ -379,6 +379,84 @@ inline double sm_lstsq(SmallMat H, SmallMat xi, SmallMat& Y) {
   double res = 0.0;
   for (int i = n; i < m; ++i)
     for (int c = 0; c < k; ++c) res += xi(i, c) * xi(i, c);
+  return std::sqrt(res);
+}
+// The same three for S = std::complex<double> (the complex block FGMRES of mg_complex_krylov.inc).  G is Hermitian with a real
+// diagonal and G = Rf^H Rf; the pivot rule is the real form's on that real diagonal, d <= rtol * G[c][c].  sm_lstsq reflects with
+// I - 2 v v^H / (v^H v), v = x + phase(x_0) ||x|| e_0, which leaves a complex diagonal in the triangular factor.
+typedef SmallMatT<std::complex<double>> SmallMatC;
+inline SmallMatC sm_chol_semidefinite(const SmallMatC& G, double rtol = 1e-14) {
+  typedef std::complex<double> zc;
+  const int k = G.r;
+  SmallMatC R(k, k);
+  for (int c = 0; c < k; ++c) {
+    const double g = G(c, c).real();
+    double d = g;
+    for (int a = 0; a < c; ++a) d -= std::norm(R(a, c));
+    if (g <= 0.0 || d <= rtol * g) continue;
+    const double rc = std::sqrt(d);
+    R(c, c) = zc(rc, 0.0);
+    for (int j = c + 1; j < k; ++j) {
+      zc t = G(c, j);
+      for (int a = 0; a < c; ++a) t -= std::conj(R(a, c)) * R(a, j);
+      R(c, j) = t / rc;
+    }
+  }
+  return R;
+}
+inline SmallMatC sm_tri_pinv(const SmallMatC& R) {
+  typedef std::complex<double> zc;
+  const int k = R.r;
+  SmallMatC T(k, k);
+  for (int c = 0; c < k; ++c) {
+    if (R(c, c) == zc(0.0)) continue;
+    for (int i = 0; i < k; ++i) {
+      zc t = (i == c) ? zc(1.0) : zc(0.0);
+      for (int a = 0; a < c; ++a) t -= T(i, a) * R(a, c);
+      T(i, c) = t / R(c, c);
+    }
+  }
+  return T;
+}
+inline double sm_lstsq(SmallMatC H, SmallMatC xi, SmallMatC& Y) {
+  typedef std::complex<double> zc;
+  const int m = H.r, n = H.c, k = xi.c;
+  std::vector<zc> v((size_t)m, zc(0.0));
+  for (int j = 0; j < n; ++j) {
+    double nrm = 0.0;
+    for (int i = j; i < m; ++i) nrm += std::norm(H(i, j));
+    nrm = std::sqrt(nrm);
+    if (nrm == 0.0) continue;
+    const double a0 = std::abs(H(j, j));
+    const zc alpha = (a0 > 0.0) ? -(H(j, j) / a0) * nrm : zc(-nrm, 0.0);
+    for (int i = j; i < m; ++i) v[(size_t)i] = H(i, j);
+    v[(size_t)j] -= alpha;
+    double vn = 0.0;
+    for (int i = j; i < m; ++i) vn += std::norm(v[(size_t)i]);
+    if (vn == 0.0) continue;
+    for (int c = j; c < n; ++c) {
+      zc d(0.0);
+      for (int i = j; i < m; ++i) d += std::conj(v[(size_t)i]) * H(i, c);
+      d *= 2.0 / vn;
+      for (int i = j; i < m; ++i) H(i, c) -= d * v[(size_t)i];
+    }
+    for (int c = 0; c < k; ++c) {
+      zc d(0.0);
+      for (int i = j; i < m; ++i) d += std::conj(v[(size_t)i]) * xi(i, c);
+      d *= 2.0 / vn;
+      for (int i = j; i < m; ++i) xi(i, c) -= d * v[(size_t)i];
+    }
+  }
+  Y = SmallMatC(n, k);
+  for (int c = 0; c < k; ++c)
+    for (int i = n - 1; i >= 0; --i) {
+      zc acc = xi(i, c);
+      for (int t = i + 1; t < n; ++t) acc -= H(i, t) * Y(t, c);
+      Y(i, c) = (H(i, i) != zc(0.0)) ? acc / H(i, i) : zc(0.0);
+    }
+  double res = 0.0;
+  for (int i = n; i < m; ++i)
+    for (int c = 0; c < k; ++c) res += std::norm(xi(i, c));
   return std::sqrt(res);
 }
 template <class S>

@@ -230,6 +230,9 @@ SIGNATURES = {
     "mg_block_cycle_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
     "mg_block_bicgstab_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_block_bicgstab_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_block_fgmres_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_block_fgmres_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_cblk_gram_dev_CFP64": (C.c_int, [_vp, _vp, _ll, _ll, _vp, _vp, _vp]),
     "mg_create_CF32": (C.c_int, [_ll, _ll, _ll, C.POINTER(_vp)]),
     "mg_set_operator_CF32_INT64": (C.c_int, [_vp, _ll, _ll, _ll, _ll, _lp, _lp, _fp]),
     "mg_set_relax_CF32": (C.c_int, [_vp, _ll, _fp, _ll, _ll, _ll]),
@@ -1341,6 +1344,52 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         pb, px, k = self._dev_block(B, X)
         return self._block_krylov_c("block_bicgstab_dev", pb, px, k, tol, maxIter)
 
+    def _block_fgmres_c(self, name, b, x, k, inner, tol, maxIter):
+        res = np.zeros(max(int(maxIter), 0) * max(int(inner), 1) + 1)
+        iters, flag, count = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        fn = getattr(self.lib, f"mg_{name}_CFP64")
+        _check(self.lib, fn(self.handle, b, x, self.n, k, int(inner), float(tol), int(maxIter), C.byref(iters), C.byref(flag), _f64(res),
+                            C.byref(count)), f"mg_{name}_CFP64")
+        return int(flag.value), int(iters.value), res[: count.value]
+
+    def block_fgmres(self, B, X, inner: int, tol: float, maxIter: int):
+        """KrylovMethods.blockFGMRES(inner) on the Krylov operator with the block cycle as preconditioner (mg_block_fgmres_CFP64);
+        X in place; returns (X, flag, inner steps in all, resvec with one entry per inner step)."""
+        self._block_guard()
+        Bf, k = self._blk(B)
+        Xf, kx = self._blk(X, True)
+        if kx != k or Bf.shape[0] != self.n or Xf.shape[0] != self.n:
+            raise ValueError(f"blocks of {self.n} x k complex values expected, the same k for B and X")
+        self._block_coarse_guard(k)
+        out = self._block_fgmres_c("block_fgmres", _c128(Bf), _c128(Xf), k, inner, tol, maxIter)
+        return (self._blk_back(X, Xf),) + out
+
+    def block_fgmres_dev_CFP64(self, B, X, inner: int, tol: float, maxIter: int):
+        """The same on torch.complex128 device blocks [n, k]; returns (flag, inner steps, resvec).  (``block_fgmres_dev`` is the FP64
+        hierarchies' method and stays refused here.)"""
+        pb, px, k = self._dev_block(B, X)
+        return self._block_fgmres_c("block_fgmres_dev", pb, px, k, inner, tol, maxIter)
+
+    def cblk_gram(self, X, Y):
+        """``X^H Y`` (k x k complex128 numpy array) of two torch.complex128 device blocks [n, k] by the one-pass Gram kernel of block
+        FGMRES on its own (mg_cblk_gram_dev_CFP64); ``Y is X`` reads the block once.  Synchronises."""
+        import torch
+        for t in (X, Y):
+            if not (hasattr(t, "dtype") and hasattr(t, "data_ptr")) or t.dtype != torch.complex128:
+                raise TypeError("expected torch.complex128 device tensors of shape [n, k]")
+            if t.dim() != 2 or not t.is_contiguous():
+                raise ValueError("device blocks are contiguous [n, k] tensors (row-major)")
+        if tuple(X.shape) != tuple(Y.shape):
+            raise ValueError("X and Y must have the same shape")
+        n, k = int(X.shape[0]), int(X.shape[1])
+        work = torch.zeros(2048 * max(k, 1) * max(k, 1), dtype=torch.float64, device=X.device)
+        out = torch.zeros((max(k, 1), max(k, 1)), dtype=torch.complex128, device=X.device)
+        _sync_torch(X, Y)
+        torch.cuda.synchronize()
+        _check(self.lib, self.lib.mg_cblk_gram_dev_CFP64(_ptr(X), _ptr(Y), n, k, _ptr(work), _ptr(out), _vp(0)), "mg_cblk_gram_dev_CFP64")
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
     # -- replaceMatrixInHierarchy on the device (mg_rap_CF64 and the value replacements) ---------------------------------------
     def replace_values(self, level: int, which: int, M):
         """New values of one operator on its unchanged pattern: M.data complex (the applied A) for MG_OP_A, real for P and R."""
@@ -1415,7 +1464,8 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     def _refuse(self, *args, **kwargs):
         raise NotImplementedError("PCG, block PCG / FGMRES, transposeHierarchy and the other device-pointer entry points serve "
                                   "FP64 hierarchies only (ComplexF64: adjoint_hierarchy; bicgstab, fgmres, cycle_dev and their _dev forms; block_spmv, "
-                                  "block_cycle, block_solve, block_cycle_dev, block_bicgstab, block_bicgstab_dev_CFP64; replace_matrix, "
+                                  "block_cycle, block_solve, block_cycle_dev, block_bicgstab, block_bicgstab_dev_CFP64, block_fgmres, "
+                                  "block_fgmres_dev_CFP64; replace_matrix, "
                                   "replace_values, get_values)")
 
     pcg = cycle_mixed_f32 = pcg_dev = block_pcg_dev = block_bicgstab_dev = block_fgmres_dev = _refuse

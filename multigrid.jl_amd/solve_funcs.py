@@ -277,6 +277,31 @@ def solveBlockBiCGSTAB_MG_CFP64(A, param: MGparam, B: np.ndarray, X0: np.ndarray
     return X0, param, it, nprec
 
 
+def solveBlockGMRES_MG_CFP64(A, param: MGparam, B: np.ndarray, X0: np.ndarray, flexible: bool, inner: int, verbose: bool = False):
+    """``(X, param, iter, resvec) = solveGMRES_MG(Afun,param,B,X0,flexible,inner,verbose)`` with ``size(B,2) > 1`` (SolveFuncs.jl:130)
+    for VAL = ComplexF64 / ComplexF32 on the device: KrylovMethods.blockFGMRES(inner) on the whole n x k block (k <= 16; one column is
+    legal), system operator ``A`` as for solveBiCGSTAB_MG_CFP64, one block cycle as preconditioner; always the flexible variant.  X0 is
+    updated in place; ``iter`` counts the inner steps and ``resvec`` holds ``||xi - H Y||_F / ||B||_F`` of each."""
+    if not is_complex(param):
+        raise TypeError("solveBlockGMRES_MG_CFP64 serves VAL=ComplexF64 hierarchies; a Float64 hierarchy goes to solveGMRES_MG")
+    if _ncols(B) != _ncols(X0):
+        raise ValueError("B and X0 must hold the same number of columns")
+    _coarse_gmres_guard(param, B)
+    adjustMemoryForNumRHS(param, 1)               # the block entry points take the column count with each call
+    dev = to_device(param)
+    if A is not None and param.As and A is param.As[0]:
+        A = None
+    if A is not dev.krylov_operator:
+        dev.update_krylov_operator(A)
+    _, flag, it, resvec = dev.block_fgmres(B, X0, inner, param.relativeTol, param.maxOuterIter)
+    param.resvec = resvec
+    param.flag = flag
+    if verbose:
+        for j, r in enumerate(resvec):
+            print(f"{j + 1:3d}\t{r:1.2e}")
+    return X0, param, it, resvec
+
+
 _WHICH = {"A": MG_OP_A, "P": MG_OP_P, "R": MG_OP_R}
 
 
