@@ -919,14 +919,49 @@ mg_status mg_adjoint_hierarchy_CF32(mg_hierarchy* h);
  * A CF32 handle runs this solve in ComplexF64 like its other coarsest solves: bc widened, the solve on a ComplexF64 copy of the
  * coarsest operator kept for it, xc narrowed.  The reference would run this fgmres in ComplexF32: a deliberate deviation of the order
  * of the single unit roundoff (more accurate).
- * Refused with MG_ERR_UNSUPPORTED: every mg_block_*_CF64 / _CFP64 entry point with nrhs > 1 (the reference calls blockFGMRES there,
- * MGcycle.jl:166-167: not built).
+ * Refused with MG_ERR_UNSUPPORTED unless the handle's option coarse_gmres_blocks is set (below): every mg_block_*_CF64 / _CFP64 entry
+ * point with nrhs > 1.
  * mg_coarse_gmres_CF64: the coarsest solve alone on host vectors of n = coarsest order complex values; steps (the columns used), flag
  * (0: the estimate met 0.01; -1: it did not within 10 steps; -9: b = 0) and resvec10 (err_i / ||b|| of the steps used; room for 10) may
  * be NULL.  MG_ERR_STATE on a handle that is not finalized or whose coarsest solve is not GMRES; MG_ERR_INVALID for another n. */
 mg_status mg_set_coarse_gmres_CF64(mg_hierarchy* h, long long n, const double* d);
 mg_status mg_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long* steps, long long* flag,
                                double* resvec10);
+
+/* ---- the block GMRES coarsest solve (MGcycle.jl:165-167): blocks of right-hand sides on a GMRES-coarse complex handle -------------
+ * OPT-IN: mg_set_option(h, "coarse_gmres_blocks", 1) (default 0; read at every call).  With 0 a block of nrhs > 1 on a complex handle
+ * whose coarsest solve is GMRES is refused with MG_ERR_UNSUPPORTED, word for word as before this solve existed.  With 1 these entry
+ * points serve such a handle for 1 <= nrhs <= 16: mg_block_cycle_CF64, mg_block_solve_CF64, mg_block_spmv_CF64,
+ * mg_block_cycle_dev_CFP64, mg_block_bicgstab[_dev]_CFP64, mg_block_fgmres[_dev]_CFP64 (CF64 and CF32 handles as each of them serves
+ * them; a CF32 handle runs the solve in ComplexF64 on the widened coarsest operator).
+ * The coarsest solve of a block is X .= 0 and ONE restart of blockFGMRES(A_c, B, 10, tol = 0.01, maxIter = 1, M = V -> d .* V) with the
+ * same Jacobi vector d as the single-vector solve: V_0, xi_0 = cholqr2(B); per step Z_j = d.*V_j, W = A_c Z_j, block modified
+ * Gram-Schmidt in ascending order (H_ij = V_i^H W, W -= V_i H_ij), V_{j+1}, H_{j+1,j} = cholqr2(W) - Cholesky QR applied twice with the
+ * semidefinite factor (real pivots; a column with g <= 0 or d <= 1e-14 g is dropped: a zero row of R, a zero column of Q).  THE COLUMNS
+ * OF A BLOCK ARE COUPLED: the result is not that of nrhs single-vector solves, and the stopping test is on the whole block,
+ * ||xi - H Y||_F / ||B||_F <= 0.01.
+ * The restart is enqueued whole - front 3 launches, step j: j + 5 (the product, V_0^H W, j + 1 Gram-Schmidt passes, two Cholesky
+ * passes; every pass sums the k x k partials of the pass before it and does the small algebra itself, no launch only sums) - then ONE
+ * copy of the table (||B||_F^2, xi_0, every H_ij: 270 KB at nrhs = 16) and ONE HOST SYNCHRONISATION PER COARSEST SOLVE, as for the
+ * single-vector form; the host replays the block least squares, breaks at the first estimate <= 0.01, and X = sum_j Z_j Y_j is one
+ * copy and one more launch: 99 launches in all (mg_block_coarse_form).  No atomics: a rerun gives the same bits.  B = 0: X = 0.
+ * The work set (11 + 10 blocks of n_c x nrhs, partials, table) belongs to the block work set: allocated at the first block call,
+ * grown when a larger nrhs arrives, never inside a cycle.  nrhs = 1 through the block entry points is the single-vector solve.
+ * Still refused (MG_ERR_UNSUPPORTED): blocks on K-cycle / Jac-GMRES hierarchies, with a Schwarz coarsest solve, nrhs > 16, the
+ * sharded forms and FP64 handles (the real GMRES coarsest solve is column by column there already).
+ * mg_block_coarse_gmres_CF64: the block solve alone on host blocks, column-major n x nrhs (n = the coarsest order) like the other host
+ * block entry points; steps, flag (0 / -1 / -9) and resvec10 (the estimates of the steps used) of the whole block may be NULL.
+ * MG_ERR_STATE on a handle that is not finalized or whose coarsest solve is not GMRES; MG_ERR_UNSUPPORTED for nrhs > 1 without the
+ * option; MG_ERR_INVALID for another n.
+ * Blocks of few values (n_c * nrhs <= 1024 by default) take a one-workgroup form of everything behind the product instead of the
+ * chain: the same passes one after the other in ONE launch, 1 launch for the front and 2 per step, 22 in all.  The option
+ * coarse_gmres_tail_rows moves that threshold too (compared with n_c * nrhs for a block; 0: the chain everywhere; at most 8192).
+ * mg_block_coarse_form: info[0] = 1 where blocks are served on this handle's GMRES coarsest solve (0 otherwise), info[1] = kernel
+ * launches of one block solve of nrhs columns, info[2] = the path in use for them (0: the chain of grid-wide passes, 1: the
+ * one-workgroup form). */
+mg_status mg_block_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long* steps,
+                                     long long* flag, double* resvec10);
+mg_status mg_block_coarse_form(mg_hierarchy* h, long long nrhs, long long* info);
 
 /* ---- Jac-GMRES smoothing and the K-cycle on a CF64 handle (MGcycle.jl:35-50,72-76,96-98; FGMRES.jl:48-126) ------------------------
  * mg_set_schedule_CF64 sets cycleType ('V', 'W', 'F' or 'K') and relaxType (0: Jac / SPAI, 1: Jac-GMRES) of a CF64 handle in one

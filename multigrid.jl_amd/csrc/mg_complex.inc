@@ -1,7 +1,7 @@
 // mg_complex.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F / K cycles,
 // pointwise or Jac-GMRES relaxation (K and Jac-GMRES: CF64 handles, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
-// (the last: one right-hand side, one host synchronisation per solve).  The state lives apart from the real levels (CxState);
+// (the last: one host synchronisation per solve; blocks of right-hand sides by its block form where the option coarse_gmres_blocks asks for it).  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
 // The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
 // ComplexF32 / Int64 hierarchies (the _CF32 entry points; the reference's VAL = ComplexF32, singlePrecision) share all of it: the
@@ -81,6 +81,14 @@ struct CxState {
   DevBuf<double> cgD, cgV, cgZ, cgTab, cgPart;
   double* h_cgtab = nullptr;         // pinned
   CxMat cgA;
+  // The same solve on a block of right-hand sides (option coarse_gmres_blocks; cx_coarse_block_gmres, kernels: mg_cxblk_coarse.hpp): 11
+  // blocks V and 10 blocks Z (row-major [n_c][cb_cap]), two sets of k x k partials, the table of xi_0 and every H_ij with its pinned
+  // readback, R1 of the Cholesky QR under way, and the solution Y of the block least squares on its way back.  Part of the block
+  // work set: sized by cx_block_ensure for cb_cap columns, grown with nrhs, nothing allocated inside a cycle.
+  int cb_cap = 0;
+  DevBuf<double> cbV, cbZ, cbTab, cbPart, cbR1, cbY;
+  double* h_cbtab = nullptr;         // pinned
+  double* h_cbY = nullptr;           // pinned
   DevBuf<double> stage_b, partial;   // the fine right-hand side; per-row-block partials of ||r||^2
   // The FGMRES relaxation's own partials and scalars (Jac-GMRES smoothing, K-cycle; cx_fgmres_relax): it runs inside the Krylov drivers,
   // whose kpart / kscal must survive a cycle.  Scalar 0: ||r0||^2; step j: the 2 j + 3 scalars of its GRAM launch from 1 + j^2 + 2 j on,
@@ -122,6 +130,9 @@ struct CxState {
     for (DevBuf<double>* d : {&cgD, &cgV, &cgZ, &cgTab, &cgPart}) d->release();
     if (h_cgtab) (void)hipHostFree(h_cgtab);
     cgA.release();
+    for (DevBuf<double>* d : {&cbV, &cbZ, &cbTab, &cbPart, &cbR1, &cbY}) d->release();
+    if (h_cbtab) (void)hipHostFree(h_cbtab);
+    if (h_cbY) (void)hipHostFree(h_cbY);
     for (DevBuf<int>* d : {&luLptr, &luLcol, &luUptr, &luUcol, &luP, &luQ, &luLorder, &luLlvl, &luUorder, &luUlvl}) d->release();
     luLval.release(); luUval.release(); luWork.release();
     stage_b.release(); partial.release(); cw_b.release(); cw_x.release();
@@ -489,6 +500,145 @@ int cx_coarse_gmres(mg_hierarchy* h, const cx_t* b, cx_t* x, CxCoarseReport* rep
   return MG_OK;
 }
 
+// ---- the same for a block of right-hand sides (MGcycle.jl:165-167; option coarse_gmres_blocks) ------------------------------------------
+// X .= 0, then ONE restart of KrylovMethods.blockFGMRES(A_c, B, 10, tol = 0.01, maxIter = 1, M = V -> d_c .* V) on row-major blocks
+// [n_c][k], 2 <= k <= BLK_KMAX.  Enqueued speculatively and whole, as cx_coarse_gmres does it for a vector (kernels: mg_cxblk_coarse.hpp):
+//   front    B^H B (cx_blk_gram_onepass), the two passes of cholqr2(B): V_0, xi_0, ||B||_F^2, Z_0 = d.*V_0           3 launches
+//   step j   W = A_c Z_j (cx_csr_stream_spmm), V_0^H W (cx_blk_gram_onepass), j + 1 Gram-Schmidt passes, the two
+//            passes of cholqr2(W) with Z_{j+1} = d.*V_{j+1}                                                              j + 5 launches
+// then ONE copy of the table (||B||_F^2, xi_0, every H_ij and H_{j+1,j}) and ONE host synchronisation; the host replays the block
+// least squares (coarse_block_gmres_replay, mg_krylov_host.hpp), which fixes `used`, and X = sum_{j < used} Z_j Y_j is the copy of Y
+// and one more launch.  B = 0: X = 0 and flag -9.  The columns of a block are coupled: this is NOT k single-vector solves.
+// The first Gram matrix of a step is a launch of the existing one-pass kernel, not an epilogue of the product (see
+// profiles/complex_block_coarse_gmres.md).  Blocks of few values take the one-workgroup form of everything behind the product instead
+// (cb_tail: 1 launch for the front, 2 per step; cx_cb_use_tail).
+inline int cb_lg(int k) {
+  int l = 0;
+  while ((1 << l) < k) ++l;
+  return l;
+}
+// Blocks of at most this many values (n_c * k) take the one-workgroup form (cb_tail) behind every product, larger ones the chain of
+// passes (measured: profiles/complex_block_coarse_gmres.md).  The option coarse_gmres_tail_rows moves the threshold for blocks too: it
+// is then compared with n_c * k (0: the chain everywhere; capped by the form's limit).
+constexpr long long CX_CB_TAIL_DEFAULT_ENTRIES = 1024;   // (a single tile at every k: it lost at 125 x 16 = 2000 values, two tiles)
+inline bool cx_cb_use_tail(const mg_hierarchy* h, int k) {
+  const long long opt = h->opt.coarse_gmres_tail_rows;
+  const long long lim = std::min<long long>(opt < 0 ? CX_CB_TAIL_DEFAULT_ENTRIES : opt, mgcb::CB_TAIL_ENTRIES);
+  return h->cx->n_coarse * k <= lim;
+}
+// kernel launches of one block solve of k columns on the path in use: the front, the 10 steps, the combination (B = 0 skips the last)
+inline long long cx_cb_launches(const mg_hierarchy* h, int k) {
+  if (cx_cb_use_tail(h, k)) return 1 + 2 * mgcb::CB_M + 1;
+  long long c = 3 + 1;
+  for (int j = 0; j < mgcb::CB_M; ++j) c += j + 5;
+  return c;
+}
+int cx_cb_ensure(mg_hierarchy* h, int nr) {
+  CxState& S = *h->cx;
+  if (!S.coarse_gmres || !h->opt.coarse_gmres_blocks || nr <= 1 || nr <= S.cb_cap) return MG_OK;
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));   // (an earlier block call may still read the buffers replaced below)
+  S.cb_cap = 0;
+  constexpr int m = mgcb::CB_M;
+  const size_t len = 2 * (size_t)S.n_coarse * (size_t)nr, kk = 2 * (size_t)nr * nr;
+  const size_t tlen = coarse_block_table_len(nr, m);
+  MG_TRY(S.cbV.alloc(len * (m + 1)));
+  MG_TRY(S.cbZ.alloc(len * m));
+  MG_TRY(S.cbTab.alloc(tlen));
+  MG_TRY(S.cbPart.alloc(2 * (size_t)mgcb::CB_MAXWG * kk));
+  MG_TRY(S.cbR1.alloc(kk));
+  MG_TRY(S.cbY.alloc(kk * m));
+  if (S.h_cbtab) (void)hipHostFree(S.h_cbtab);
+  if (S.h_cbY) (void)hipHostFree(S.h_cbY);
+  S.h_cbtab = S.h_cbY = nullptr;
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_cbtab), sizeof(double) * tlen));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_cbY), sizeof(double) * kk * m));
+  S.cb_cap = nr;
+  return MG_OK;
+}
+
+int cx_coarse_block_gmres(mg_hierarchy* h, const cx_t* b, cx_t* x, int k, CxCoarseReport* report = nullptr) {
+  CxState& S = *h->cx;
+  const CxMat& A = cx_cg_operator(S);
+  const long long n = S.n_coarse;
+  const size_t len = (size_t)n * (size_t)k, kk = (size_t)k * k;
+  const hipStream_t st = h->play->stream;
+  constexpr int m = mgcb::CB_M;
+  if (k < 2 || k > mgk::BLK_KMAX) return fail(MG_ERR_INVALID, "internal: a block GMRES coarsest solve of %d columns", k);
+  if (!A.set || S.cb_cap < k || !S.h_cbtab || S.cgD.n != 2 * (size_t)n) return fail(MG_ERR_STATE, "internal: the block GMRES coarsest solve's work set is not sized");
+  cx_t *V = cxp(S.cbV), *Z = cxp(S.cbZ);
+  const cx_t* d = cxc(S.cgD);
+  cx_t* tab = cxp(S.cbTab) + 1;                      // (entry 0 of the table: ||B||_F^2 and a pad)
+  cx_t* part[2] = {cxp(S.cbPart), cxp(S.cbPart) + (size_t)mgcb::CB_MAXWG * kk};
+  const int lg = cb_lg(k), G = mgcb::cb_grid(n, lg);
+  const dim3 grid((unsigned)G), blk(mgk::BLK);
+  mgcb::CbPass p = {};
+  p.np = G; p.k = k; p.lgk = lg; p.n = n; p.d = d;
+  auto chol2 = [&](const cx_t* src, cx_t* W, int cur, cx_t* out, double* trace, cx_t* znext) {   // cholqr2(src) -> W; the Gram partials at part[cur]
+    mgcb::CbPass c = p;
+    c.pprev = part[cur]; c.src = src; c.W = W; c.out = cxp(S.cbR1); c.trace = trace; c.pout = part[1 - cur];
+    hipLaunchKernelGGL(mgcb::cb_pass<mgcb::CB_CHOL>, grid, blk, 0, st, c);
+    c.pprev = part[1 - cur]; c.src = W; c.out = out; c.r1 = cxc(S.cbR1); c.trace = nullptr; c.pout = nullptr; c.Z = znext;
+    hipLaunchKernelGGL(mgcb::cb_pass<mgcb::CB_CHOL>, grid, blk, 0, st, c);
+  };
+  const bool tail = cx_cb_use_tail(h, k);
+  mgcb::CbTail t = {};
+  t.k = k; t.lgk = lg; t.n = n; t.ld = (long long)len; t.V = V; t.d = d; t.r1 = cxp(S.cbR1); t.part = part[0];
+  // front: R = B (X = 0); V_0, xi_0 = cholqr2(B), Z_0 = d.*V_0
+  if (tail) {
+    mgcb::CbTail f = t;
+    f.nk = 0; f.src = b; f.W = V; f.Z = Z; f.slot = tab; f.trace = S.cbTab.p;
+    hipLaunchKernelGGL(mgcb::cb_tail, dim3(1), blk, 0, st, f);
+  } else {
+    hipLaunchKernelGGL(mgk::cx_blk_gram_onepass, grid, blk, 0, st, b, b, n, k, lg, part[0]);
+    chol2(b, V, 0, tab, S.cbTab.p, Z);
+  }
+  HIP_TRY(hipGetLastError());
+  for (int j = 0; j < m; ++j) {
+    cx_t* W = V + (size_t)(j + 1) * len;
+    cx_t* slot = tab + coarse_block_slot(j) * kk;
+    MG_TRY(cx_spmv<mgk::AXPBY>(h, A, Z + (size_t)j * len, W, nullptr, nullptr, nullptr, cx_t{1, 0}, cx_t{0, 0}, k));   // W = A_c Z_j
+    if (tail) {
+      mgcb::CbTail f = t;
+      f.nk = j + 1; f.src = W; f.W = W; f.Z = j + 1 < m ? Z + (size_t)(j + 1) * len : nullptr; f.slot = slot;
+      hipLaunchKernelGGL(mgcb::cb_tail, dim3(1), blk, 0, st, f);
+      HIP_TRY(hipGetLastError());
+      continue;
+    }
+    hipLaunchKernelGGL(mgk::cx_blk_gram_onepass, grid, blk, 0, st, (const cx_t*)V, (const cx_t*)W, n, k, lg, part[0]);   // V_0^H W
+    int cur = 0;
+    for (int i = 0; i <= j; ++i) {   // W -= V_i H_ij ; the partials of V_{i+1}^H W, at the end of W^H W
+      mgcb::CbPass c = p;
+      c.pprev = part[cur]; c.W = W; c.V = V + (size_t)i * len; c.U = i < j ? V + (size_t)(i + 1) * len : nullptr;
+      c.out = slot + (size_t)i * kk; c.pout = part[1 - cur];
+      hipLaunchKernelGGL(mgcb::cb_pass<mgcb::CB_MGS>, grid, blk, 0, st, c);
+      cur = 1 - cur;
+    }
+    chol2(W, W, cur, slot + (size_t)(j + 1) * kk, nullptr, j + 1 < m ? Z + (size_t)(j + 1) * len : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(S.h_cbtab, S.cbTab.p, sizeof(double) * coarse_block_table_len(k, m), hipMemcpyDeviceToHost, st));
+  HIP_TRY(spin_sync(st));
+  BlockHessenbergLsq Q(k, m);
+  SmallMatC Y;
+  CxCoarseReport local;
+  CxCoarseReport& R = report ? *report : local;
+  coarse_block_gmres_replay(S.h_cbtab, k, CX_CG_TOL, Q, R.used, R.flag, R.resvec, Y);
+  if (R.used == 0) {   // B = 0
+    HIP_TRY(hipMemsetAsync(x, 0, sizeof(cx_t) * len, st));
+    return MG_OK;
+  }
+  const size_t ny = (size_t)R.used * kk;
+  for (size_t e = 0; e < ny; ++e) {
+    S.h_cbY[2 * e] = Y.a[e].real();
+    S.h_cbY[2 * e + 1] = Y.a[e].imag();
+  }
+  HIP_TRY(hipMemcpyAsync(S.cbY.p, S.h_cbY, sizeof(cx_t) * ny, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(mgcb::cb_combine, dim3(std::min(cx_grid((long long)len), 4096u)), blk, 0, st, (const cx_t*)Z, (long long)len, R.used, cxc(S.cbY), x, n, k);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
 // z = param.LU \ b (MGcycle.jl:177): explicit inverse, or x[q] = U \ (L \ b[p]) by the level-scheduled sptrsv_lu (one workgroup;
 // chip-wide for factors of >= lu_multi_min_rows rows), or one Schwarz sweep (MGcycle.jl:140-143; xzero: x need not be read), or one
 // restart of Jacobi-preconditioned FGMRES(10) from zero (cx_coarse_gmres: the only one that synchronises with the host, once)
@@ -501,9 +651,10 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr
     if (k > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%d)", k);
     return dd_coarse(h, reinterpret_cast<const double*>(b), reinterpret_cast<double*>(x), xzero);
   }
-  if (S.coarse_gmres) {   // (the reference calls blockFGMRES on a block, MGcycle.jl:166-167: not built)
-    if (k > 1) return fail(MG_ERR_UNSUPPORTED, "the GMRES coarsest solve serves one right-hand side (nrhs=%d)", k);
-    return cx_coarse_gmres(h, b, x);
+  if (S.coarse_gmres) {   // (the reference calls blockFGMRES on a block, MGcycle.jl:166-167: served with the option coarse_gmres_blocks)
+    if (k > 1 && !h->opt.coarse_gmres_blocks) return fail(MG_ERR_UNSUPPORTED, "the GMRES coarsest solve serves one right-hand side (nrhs=%d)", k);
+    if (k > 1) return cx_coarse_block_gmres(h, b, x, k);
+    return cx_coarse_gmres(h, b, x);   // (a block of one column is a vector)
   }
   if (S.coarse_multi) return cxlu_solve_dev(S.coarse_multi, *S.coarse_multi->fwd, b, x, k, &h->play->stream);
   if (S.coarse_lu) {
@@ -799,9 +950,10 @@ int cx_block_schedule_ok(mg_hierarchy* h) {
     return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy");
   return MG_OK;
 }
-// The reference calls blockFGMRES for a block on a GMRES coarsest solve (MGcycle.jl:166-167); that form is not built here.
+// The reference calls blockFGMRES for a block on a GMRES coarsest solve (MGcycle.jl:166-167): cx_coarse_block_gmres, served where the
+// handle's option coarse_gmres_blocks is set (default 0: refused, as before that solve existed).
 int cx_block_coarse_ok(mg_hierarchy* h, long long nrhs) {
-  if (h->cx->coarse_gmres && nrhs > 1)
+  if (h->cx->coarse_gmres && nrhs > 1 && !h->opt.coarse_gmres_blocks)
     return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a complex hierarchy with the GMRES coarsest solve (nrhs=%lld)", nrhs);
   return MG_OK;
 }
@@ -826,6 +978,7 @@ int cx_block_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want) {
 // the handle.  Nothing of the single-vector state is touched.
 int cx_block_ensure(mg_hierarchy* h, int nr) {
   CxState& S = *h->cx;
+  MG_TRY(cx_cb_ensure(h, nr));
   if (nr <= S.blk_cap) return MG_OK;
   (void)hipSetDevice(h->device);
   HIP_TRY(spin_sync(h->play->stream));   // (an earlier block call may still read the buffers replaced below)
@@ -909,6 +1062,7 @@ int cx_finalize(mg_hierarchy* h) {
   CxState& S = *h->cx;
   S.finalized = false;
   S.blk_cap = 0;   // (levels may have changed size: the block work set is sized again by the next block call)
+  S.cb_cap = 0;
   const int nl = (int)h->nlevels;
   if (S.single && h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve is not served for CF32 handles");
   if (S.K_auto) {   // As[1] may have changed since it was widened: the next driver call widens it again
@@ -1961,6 +2115,58 @@ int mg_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long 
   if (flag) *flag = report.flag;
   if (resvec)
     for (int i = 0; i < report.used; ++i) resvec[i] = report.resvec[i];
+  return MG_OK;
+}
+
+// The block form of the solve alone on host blocks (option coarse_gmres_blocks): b, x column-major n x nrhs, n = the coarsest order;
+// steps, flag and resvec (10 entries at most: ||xi - H Y||_F / ||B||_F per step) are those of the whole block.  nrhs = 1 is the
+// single-vector solve.
+int mg_block_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long* steps, long long* flag,
+                               double* resvec) {
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));
+  CxState& S = *h->cx;
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  if (!S.coarse_gmres) return fail(MG_ERR_STATE, "the coarsest solve of this handle is not GMRES (mg_set_coarse_gmres_CF64)");
+  MG_TRY(cx_block_nrhs_ok(nrhs));
+  MG_TRY(cx_block_coarse_ok(h, nrhs));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null block");
+  if (n != S.n_coarse) return fail(MG_ERR_INVALID, "n=%lld does not match the coarsest level (%lld rows)", n, S.n_coarse);
+  if (nrhs == 1) return mg_coarse_gmres_CF64(h, b, x, n, steps, flag, resvec);
+  (void)hipSetDevice(h->device);
+  const int nr = (int)nrhs;
+  MG_TRY(cx_block_ensure(h, nr));
+  CxCoarseReport report;
+  const size_t len = 2 * (size_t)n * (size_t)nr;
+  DevBuf<double> cm, db, dx;   // (the staging blocks of the block work set are sized by the FINE level; released below on every path)
+  int rc = cm.alloc(len);
+  if (rc == MG_OK) rc = db.alloc(len);
+  if (rc == MG_OK) rc = dx.alloc(len);
+  if (rc == MG_OK) rc = cx_block_upload(h, b, cm, cxp(db), n, nr);
+  if (rc == MG_OK) rc = cx_coarse_block_gmres(h, cxc(db), cxp(dx), nr, &report);
+  if (rc == MG_OK) rc = cx_block_download(h, cxc(dx), cm, x, n, nr);
+  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_block_coarse_gmres_CF64: stream failed");
+  cm.release();
+  db.release();
+  dx.release();
+  if (rc != MG_OK) return rc;
+  if (steps) *steps = report.used;
+  if (flag) *flag = report.flag;
+  if (resvec)
+    for (int i = 0; i < report.used; ++i) resvec[i] = report.resvec[i];
+  return MG_OK;
+}
+
+// info[0]: 1 where blocks are served on this handle's GMRES coarsest solve (option coarse_gmres_blocks), 0 otherwise; info[1]: kernel
+// launches of one block solve of nrhs columns on the path in use (the chain: front 3, step j: j + 5, the combination; the one-workgroup
+// form: front 1, 2 per step, the combination); info[2]: that path (0: the chain of grid-wide passes, 1: the one-workgroup form)
+int mg_block_coarse_form(mg_hierarchy* h, long long nrhs, long long* info) {
+  if (!h || !info) return fail(MG_ERR_INVALID, "null argument");
+  if (!h->cx || !h->cx->coarse_set) return fail(MG_ERR_STATE, "the coarsest solve of a complex handle was not set");
+  MG_TRY(cx_block_nrhs_ok(nrhs));
+  const bool on = h->cx->coarse_gmres && h->opt.coarse_gmres_blocks && !h->coarse_dd;
+  info[0] = on ? 1 : 0;
+  info[1] = !on ? 0 : nrhs == 1 ? cx_cg_launches(h) : cx_cb_launches(h, (int)nrhs);
+  info[2] = !on ? 0 : nrhs == 1 ? (cx_cg_use_tail(h) ? 1 : 0) : (cx_cb_use_tail(h, (int)nrhs) ? 1 : 0);
   return MG_OK;
 }
 

@@ -4,6 +4,7 @@
 //   KrylovReport        where a driver writes iters / flag / resvec / nres, and its epilogue
 //   HessenbergLsq<S>    the Givens least squares of FGMRES(m), S = double or std::complex<double>
 //   coarse_gmres_replay the replay of a complex hierarchy's GMRES coarsest solve from its table of scalars
+//   coarse_block_gmres_replay, BlockHessenbergLsq   the same for a block of right-hand sides (at the end)
 //   pinv_sym, RelaxLsq  the normal-equations step of FGMRES_relaxation (Jac-GMRES smoother, K-cycle)
 //   RelaxLsqC           the same for ComplexF64 hierarchies: Hermitian H, solved on its leading blocks
 //   SmallMatT<S>, sm_*  row-major dense helpers of the block drivers, S = double (SmallMat) or std::complex<double>
@@ -464,4 +465,128 @@ inline SmallMatT<S> sm_scaled_identity(int k, S v) {
   SmallMatT<S> I(k, k);
   for (int i = 0; i < k; ++i) I(i, i) = v;
   return I;
+}
+
+// ---- the block GMRES coarsest solve of a complex hierarchy (mg_complex.inc: cx_coarse_block_gmres): the host's replay of ONE restart
+// of blockFGMRES(m) from X = 0 that the device has run to its end.  The table (doubles): tab[0] = ||B||_F^2, tab[1] unused, then k x k
+// complex blocks, row-major, (re, im) interleaved: block 0 = xi_0, and step j from block coarse_block_slot(j) on: H_0j .. H_jj, H_{j+1,j}.
+// BlockHessenbergLsq solves the exact block least squares min ||xi - H Y||_F step by step: the Householder reflections of sm_lstsq
+// (the same reflectors: I - 2 v v^H / (v^H v), v = x + phase(x_0) ||x|| e_0), kept between the steps and cut to the k + 1 rows a column
+// of a block upper Hessenberg matrix with triangular sub-diagonal blocks reaches - sm_lstsq on the leading blocks adds exact zeros to
+// the same sums.  The replay breaks at the first err = ||xi - H Y||_F / ||B||_F <= tol; blocks behind the break are not read.
+// used: the steps that enter X = sum_{j < used} Z_j Y_j (Y: (used k) x k); flag 0 / -1, and -9 with used = 0 for B = 0.
+inline size_t coarse_block_slot(int j) { return 1 + (size_t)j * ((size_t)j + 3) / 2; }
+inline size_t coarse_block_table_len(int k, int m) { return 2 + 2 * (size_t)k * k * coarse_block_slot(m); }   // doubles
+struct BlockHessenbergLsq {
+  typedef std::complex<double> zc;
+  const int k, m, rows;
+  // H ((m + 1) k x m k, triangularised column by column) and xi ((m + 1) k x k), both stored COLUMN by column: a reflection works
+  // on k + 1 consecutive values of a column (row-major, every step of it would be a cache line of its own)
+  std::vector<zc> Hc, xc;
+  std::vector<std::vector<zc>> v;      // the reflector of column c: rows c .. c + v[c].size() - 1
+  std::vector<double> vn;              // v^H v (0: no reflection)
+  BlockHessenbergLsq(int k_, int m_)
+      : k(k_), m(m_), rows((m_ + 1) * k_), Hc((size_t)(m_ + 1) * k_ * m_ * k_, zc(0.0)), xc((size_t)(m_ + 1) * k_ * k_, zc(0.0)), v((size_t)m_ * k_),
+        vn((size_t)m_ * k_, 0.0) {}
+  zc& H(int i, int j) { return Hc[(size_t)j * rows + i]; }
+  zc H(int i, int j) const { return Hc[(size_t)j * rows + i]; }
+  zc& xi(int i, int j) { return xc[(size_t)j * rows + i]; }
+  zc xi(int i, int j) const { return xc[(size_t)j * rows + i]; }
+  void begin(const SmallMatC& xi0) {
+    std::fill(Hc.begin(), Hc.end(), zc(0.0));
+    std::fill(xc.begin(), xc.end(), zc(0.0));
+    for (int a = 0; a < k; ++a)
+      for (int b = 0; b < k; ++b) xi(a, b) = xi0(a, b);
+  }
+  // (products written out in real arithmetic: std::complex's operator* goes through the library's NaN-recovering multiply, several
+  //  times the cost of the four multiplications, and this runs once per cycle on the critical path)
+  static zc mul(const zc& a, const zc& b) { return zc(a.real() * b.real() - a.imag() * b.imag(), a.real() * b.imag() + a.imag() * b.real()); }
+  static zc mulc(const zc& a, const zc& b) { return zc(a.real() * b.real() + a.imag() * b.imag(), a.real() * b.imag() - a.imag() * b.real()); }   // conj(a) b
+  void reflect(int c, zc* column) const {   // on one column of H or xi
+    const std::vector<zc>& w = v[(size_t)c];
+    if (vn[(size_t)c] == 0.0) return;
+    zc* x = column + c;
+    zc d(0.0);
+    for (size_t i = 0; i < w.size(); ++i) d += mulc(w[i], x[i]);
+    d *= 2.0 / vn[(size_t)c];
+    for (size_t i = 0; i < w.size(); ++i) x[i] -= mul(d, w[i]);
+  }
+  // block column j of H is in place (rows 0 .. (j + 2) k - 1); returns ||xi - H Y||_F over the block columns 0 .. j
+  double close_block(int j) {
+    const int c0 = j * k, c1 = c0 + k, rlim = (j + 2) * k;
+    for (int col = c0; col < c1; ++col)
+      for (int c = 0; c < c0; ++c) reflect(c, &Hc[(size_t)col * rows]);
+    for (int c = c0; c < c1; ++c) {
+      const int hi = std::min(c + k + 1, rlim);
+      std::vector<zc>& w = v[(size_t)c];
+      w.assign((size_t)(hi - c), zc(0.0));
+      vn[(size_t)c] = 0.0;
+      double nrm = 0.0;
+      for (int i = c; i < hi; ++i) nrm += std::norm(H(i, c));
+      nrm = std::sqrt(nrm);
+      if (nrm == 0.0) continue;
+      const double a0 = std::abs(H(c, c));
+      const zc alpha = (a0 > 0.0) ? -(H(c, c) / a0) * nrm : zc(-nrm, 0.0);
+      for (int i = c; i < hi; ++i) w[(size_t)(i - c)] = H(i, c);
+      w[0] -= alpha;
+      double s = 0.0;
+      for (const zc& e : w) s += std::norm(e);
+      if (s == 0.0) continue;
+      vn[(size_t)c] = s;
+      for (int col = c; col < c1; ++col) reflect(c, &Hc[(size_t)col * rows]);
+      for (int col = 0; col < k; ++col) reflect(c, &xc[(size_t)col * rows]);
+    }
+    double res = 0.0;
+    for (int i = c1; i < rlim; ++i)
+      for (int col = 0; col < k; ++col) res += std::norm(xi(i, col));
+    return std::sqrt(res);
+  }
+  // Y = H[:n, :n] \ xi[:n], n = used k, by column-oriented back substitution (row-major (used k) x k, as cb_combine reads it)
+  SmallMatC solve(int used) const {
+    const int n = used * k;
+    SmallMatC Y(n, k);
+    std::vector<zc> x((size_t)n);
+    for (int c = 0; c < k; ++c) {
+      for (int i = 0; i < n; ++i) x[(size_t)i] = xi(i, c);
+      for (int i = n - 1; i >= 0; --i) {
+        const zc y = (H(i, i) != zc(0.0)) ? x[(size_t)i] / H(i, i) : zc(0.0);
+        Y(i, c) = y;
+        const zc* hcol = &Hc[(size_t)i * rows];
+        for (int r = 0; r < i; ++r) x[(size_t)r] -= mul(hcol[r], y);
+      }
+    }
+    return Y;
+  }
+};
+inline void coarse_block_gmres_replay(const double* tab, int k, double tol, BlockHessenbergLsq& Q, int& used, long long& flag, double* resvec,
+                                      SmallMatC& Y) {
+  typedef std::complex<double> zc;
+  used = 0;
+  flag = -1;
+  Y = SmallMatC(0, k);
+  if (!(tab[0] > 0.0)) {
+    flag = -9;
+    return;
+  }
+  const double bn = std::sqrt(tab[0]);
+  const size_t kk = (size_t)k * k;
+  auto blockat = [&](size_t s, int a, int b) { const double* e = tab + 2 + 2 * (s * kk + (size_t)a * k + b); return zc(e[0], e[1]); };
+  SmallMatC xi0(k, k);
+  for (int a = 0; a < k; ++a)
+    for (int b = 0; b < k; ++b) xi0(a, b) = blockat(0, a, b);
+  Q.begin(xi0);
+  for (int j = 0; j < Q.m; ++j) {
+    const size_t s0 = coarse_block_slot(j);
+    for (int i = 0; i <= j + 1; ++i)
+      for (int a = 0; a < k; ++a)
+        for (int b = 0; b < k; ++b) Q.H(i * k + a, j * k + b) = blockat(s0 + (size_t)i, a, b);
+    const double err = Q.close_block(j) / bn;
+    if (resvec) resvec[j] = err;
+    used = j + 1;
+    if (err <= tol) {
+      flag = 0;
+      break;
+    }
+  }
+  Y = Q.solve(used);
 }

@@ -146,7 +146,11 @@ bool host_all_zero(const double* x, long long len) {
   X(long long, graph_max_rows, 300000)     /* sub-cycles from the first level of at most this many rows*nrhs replay as one HIP graph */ \
   X(long long, lu_multi_min_rows, 4096)    /* sparse coarse factors of this many rows: per-level launches + dense trailing inverse */ \
   X(long long, coarse_gmres_tail_rows, -1) /* complex GMRES coarsest solve: largest level whose steps run the one-workgroup tail (-1: the measured \
-                                              default; 0: the chain of passes everywhere; capped by the tail's row limit; read at every solve) */ \
+                                              default; 0: the chain of passes everywhere; capped by the tail's row limit; read at every solve). \
+                                              TWO UNITS: the single-vector solve compares it with the coarsest ROWS n_c, the block solve \
+                                              (coarse_gmres_blocks) with the block's VALUES n_c * nrhs - one number moves both thresholds */ \
+  X(bool, coarse_gmres_blocks, false)      /* complex GMRES coarsest solve: serve blocks of right-hand sides by the block form of the solve \
+                                              (blockFGMRES, cx_coarse_block_gmres); 0: a block on such a hierarchy is refused; read at every call */ \
   X(long long, lu_dense_tail_min, 64) \
   X(long long, lu_dense_tail_max, 16384)   /* largest trailing block kept as an explicit inverse (8*M^2 bytes each for L and U: 2 x 2.1 GB) */ \
   X(double, rowclass_min_cover, 0.9) \

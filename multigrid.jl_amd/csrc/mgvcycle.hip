@@ -36,6 +36,7 @@
 #include "mg_complex.hpp"
 #include "mg_krvec.hpp"
 #include "mg_cxvec.hpp"
+#include "mg_cxblk_coarse.hpp"
 #include "mg_dd.hpp"
 #include "mg_vanka.hpp"
 #include "mg_krylov_host.hpp"   // host only: KrylovReport, HessenbergLsq, RelaxLsq / pinv_sym, SmallMat / sm_*

@@ -207,6 +207,8 @@ SIGNATURES = {
     "mg_set_coarse_lu_CF64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
     "mg_set_coarse_gmres_CF64": (C.c_int, [_vp, _ll, _dp]),
     "mg_coarse_gmres_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _lp, _lp, _dp]),
+    "mg_block_coarse_gmres_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _lp, _lp, _dp]),
+    "mg_block_coarse_form": (C.c_int, [_vp, _ll, _lp]),
     "mg_cycle_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_solve_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
     "mg_spmv_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _dp, _dp, _dp, _ll]),
@@ -927,7 +929,7 @@ def _c128(a):
 
 class ComplexDeviceHierarchy(DeviceHierarchy):
     """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F / K cycles, Jac / SPAI / Jac-GMRES relaxation,
-    dense-inverse, sparse-LU or GMRES coarsest solve (the last adds one host synchronisation per coarsest solve and serves no blocks).  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
+    dense-inverse, sparse-LU or GMRES coarsest solve (the last adds one host synchronisation per coarsest solve and serves blocks only for a param with ``blockCoarseGMRES=True``: ``block_coarse_gmres``).  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
     methods, which take the column count with each call (not on a K-cycle / Jac-GMRES hierarchy).  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
     conjugates back.  P and R are real."""
@@ -992,6 +994,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         self._set_schedule(param)
         if param.LU is None:
             raise MGDeviceError("param.LU is empty: run MGsetup first")
+        self._block_coarse_gmres = bool(getattr(param, "blockCoarseGMRES", False))
+        if self._block_coarse_gmres:      # blocks on the GMRES coarsest solve: the block form of that solve (opt-in, read at every call)
+            _check(lib, lib.mg_set_option(self.handle, b"coarse_gmres_blocks", 1.0), "mg_set_option(coarse_gmres_blocks)")
         self._set_coarse(param)
         _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
         self._schedule = self._schedule_of(param)
@@ -1017,8 +1022,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
                                       "(solve the columns one after the other)")
 
     def _block_coarse_guard(self, k: int):
-        """The reference calls blockFGMRES for a block on the GMRES coarsest solve (MGcycle.jl:166-167); that form is not built."""
-        if getattr(self, "_coarse_gmres", False) and int(k) > 1:
+        """The reference calls blockFGMRES for a block on the GMRES coarsest solve (MGcycle.jl:166-167); that form runs where the
+        param asked for it (``blockCoarseGMRES=True``: the handle's option coarse_gmres_blocks) and is refused otherwise."""
+        if getattr(self, "_coarse_gmres", False) and int(k) > 1 and not getattr(self, "_block_coarse_gmres", False):
             raise NotImplementedError("blocks of right-hand sides are not served on a complex hierarchy with coarseSolveType='GMRES' "
                                       "(solve the columns one after the other)")
 
@@ -1087,6 +1093,26 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         _check(self.lib, self.lib.mg_coarse_gmres_CF64(self.handle, _c128(b), _c128(x), b.shape[0], C.byref(steps), C.byref(flag),
                                                        _f64(res)), "mg_coarse_gmres_CF64")
         return x, int(flag.value), res[: steps.value]
+
+    def block_coarse_gmres(self, B):
+        """The block GMRES coarsest solve alone (mg_block_coarse_gmres_CF64; a param with ``blockCoarseGMRES=True``): one restart of
+        Jacobi-preconditioned blockFGMRES(10) from zero on the coarsest operator for the complex128 block ``B`` (n_c x k, k <= 16).
+        Returns (X, flag, resvec): flag 0 / -1 / -9 and the estimates ||xi - H Y||_F / ||B||_F of the steps used, of the whole block."""
+        Bf, k = self._blk(B)
+        self._block_coarse_guard(k)
+        X = np.zeros(Bf.shape, dtype=np.complex128, order="F")
+        steps, flag = C.c_longlong(0), C.c_longlong(0)
+        res = np.zeros(10)
+        _check(self.lib, self.lib.mg_block_coarse_gmres_CF64(self.handle, _c128(Bf), _c128(X), Bf.shape[0], k, C.byref(steps), C.byref(flag),
+                                                             _f64(res)), "mg_block_coarse_gmres_CF64")
+        return X, int(flag.value), res[: steps.value]
+
+    def block_coarse_form(self, k: int = 2) -> dict:
+        """What ``mg_block_coarse_form`` reports for blocks of ``k`` columns: served (blocks run on this handle's GMRES coarsest
+        solve), the kernel launches of one block solve, the path in use (0: the chain of grid-wide passes, 1: the one-workgroup form)."""
+        info = (C.c_longlong * 3)()
+        _check(self.lib, self.lib.mg_block_coarse_form(self.handle, int(k), info), "mg_block_coarse_form")
+        return dict(served=bool(info[0]), launches=int(info[1]), path=int(info[2]))
 
     def set_nrhs(self, nrhs: int):
         if int(nrhs) != 1:

@@ -46,6 +46,7 @@ class MGparam:
     Meshes: List[Any] = field(default_factory=list)
     transferOperatorType: str = "FullWeighting"
     singlePrecision: bool = False
+    blockCoarseGMRES: bool = False     # coarseSolveType "GMRES" on a complex hierarchy: serve blocks by the block GMRES coarsest solve
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -57,7 +58,8 @@ class MGparam:
 def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, relativeTol=1e-6,
                relaxType="SPAI", relaxParam=1.0, relaxPre=2, relaxPost=2, cycleType="V",
                coarseSolveType="NoMUMPS", strongConnParam=0.4, FilteringParam=0.0,
-               transferOperatorType="FullWeighting", *, singlePrecision: bool = False) -> MGparam:
+               transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
+               blockCoarseGMRES: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -66,12 +68,17 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     VAL = ComplexF32 hierarchy (``param.VAL = np.complex64``, ``param.singlePrecision = True``, MGdef.jl:151): operators,
     relaxPrecs and cycle in single precision (the _CF32 entry points), coarsest factorisation in double, and the ComplexF64
     Krylov drivers preconditioned by the single cycle (the mixed branch of getMultigridPreconditioner).
+    ``blockCoarseGMRES=True`` (keyword only) with a complex ``VAL`` and ``coarseSolveType="GMRES"`` switches on the block form of
+    that coarsest solve (the reference's blockFGMRES branch, MGcycle.jl:165-167): blocks of 2 to 16 right-hand sides are then
+    served on the hierarchy; without it they are refused.  The columns of a block are coupled by that solve.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
                         "hierarchy is getMGparam(np.complex128, ..., singlePrecision=True)")
     if singlePrecision and np.dtype(VAL) != np.complex128:
         raise NotImplementedError("singlePrecision=True serves VAL=ComplexF64 (Float32 real hierarchies are out of scope)")
+    if blockCoarseGMRES and (np.dtype(VAL) != np.complex128 or str(coarseSolveType) != "GMRES"):
+        raise NotImplementedError("blockCoarseGMRES=True serves VAL=ComplexF64 (singlePrecision or not) with coarseSolveType='GMRES'")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -85,7 +92,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    relaxPre=pre, relaxPost=post, cycleType=cycleType, coarseSolveType=str(coarseSolveType),
                    strongConnParam=float(strongConnParam), FilteringParam=float(FilteringParam),
                    transferOperatorType=str(transferOperatorType), singlePrecision=bool(singlePrecision),
-                   VAL=np.dtype(VAL).type, IND=np.int64)
+                   blockCoarseGMRES=bool(blockCoarseGMRES), VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -156,7 +163,8 @@ def copySolver(MG: MGparam) -> MGparam:
     single = is_single(MG)
     new = getMGparam(np.complex128 if single else MG.VAL, MG.IND, MG.levels, MG.numCores, MG.maxOuterIter, MG.relativeTol,
                      MG.relaxType, MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
-                     MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single)
+                     MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single,
+                     blockCoarseGMRES=bool(MG.blockCoarseGMRES))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

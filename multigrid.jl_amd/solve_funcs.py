@@ -31,8 +31,11 @@ def _complex_block(param: MGparam, b) -> bool:
 
 def _coarse_gmres_guard(param: MGparam, b) -> None:
     """A complex hierarchy with coarseSolveType='GMRES' given a block: the reference calls blockFGMRES in its coarsest solve
-    (MGcycle.jl:166-167), which is not built - refused before the device is touched, as the device layer refuses it."""
+    (MGcycle.jl:166-167).  That form runs only where the param asked for it (``getMGparam(..., blockCoarseGMRES=True)``); without
+    it the block is refused before the device is touched, as the device layer refuses it."""
     from .mgdef import _solver_object
+    if param.blockCoarseGMRES:
+        return
     if _complex_block(param, b) and param.coarseSolveType == "GMRES" and _solver_object(param.LU) is None:
         raise NotImplementedError("blocks of right-hand sides are not served on a complex hierarchy with coarseSolveType='GMRES' "
                                   "(solve the columns one after the other)")
