@@ -984,6 +984,31 @@ mg_status mg_set_schedule_CF64(mg_hierarchy* h, long long cycleType, long long r
 mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r0, double* x, long long n, long long inner,
                                double tol, double* H_out, double* xi_out, double* rnorms_out, long long* used_out);
 
+/* ---- The Vanka cell-block smoother in the complex cycle (relaxation type 2; MGcycle.jl:46-52,99-100, Vanka.jl:372-434) -------------
+ * mg_set_vanka_CF64 / mg_set_vanka_CF32 bind the cells' blocks of one level of a CF64 / CF32 handle, as mg_set_vanka_FP64 does for a
+ * real level and with its checks: As[level] uploaded first (MG_ERR_STATE), no 64-bit row pointers (MG_ERR_UNSUPPORTED), (dim, n,
+ * includePressure) against the operator's rows (MG_ERR_INVALID), VankaType FULL_VANKA_RB (1), ECON_VANKA_RB (3) or FULL_VANKA_ADD (5)
+ * (others MG_ERR_UNSUPPORTED).  D_blocks: LocalBlocks of setupVankaFacesPreconditioner, (bs*bs) x prod(n) column-major ComplexF32 -
+ * bs*bs*cells interleaved (re, im) float pairs, for both precisions.  A CF64 level promotes them to double; a CF32 level applies them
+ * as stored, every product and sum in single.  The blocks are copied and released with the handle.  An FP64 handle, or the other
+ * precision's entry: MG_ERR_STATE.
+ * mg_set_vanka_relax_CF64 / _CF32 put the handle into relaxation type 2 together with its cycleType ('V', 'W', 'F', 'K'; other
+ * letters MG_ERR_INVALID) and drop `finalized`.  mg_set_schedule_CF64(h, c, 2) stays MG_ERR_INVALID and mg_set_relax_type(h, 2) on a
+ * complex handle MG_ERR_UNSUPPORTED; mg_set_schedule_CF64(h, c, 0 | 1) or mg_set_relax_type(h, 0) afterwards leave Vanka mode.
+ * mg_finalize then asks of every non-coarsest level blocks that serve exactly its rows (none: MG_ERR_STATE; another size:
+ * MG_ERR_INVALID) and the pointwise slot of mg_set_relax_CF64 / _CF32, which carries relaxPre / relaxPost and whose values nothing
+ * reads; 'K' on a CF32 handle is MG_ERR_UNSUPPORTED.  The cycle runs relaxPre / relaxPost Vanka iterations of x in place from the
+ * level's own CSR (a count of 0: none).  A level entered with x = 0 is zero-filled and its first pass reads b and the blocks only (no
+ * matrix walk; the one pass of FULL_VANKA_ADD altogether) - bit-identical to the general pass on a zero x, which x_is_zero = 0 runs.
+ * Served: mg_cycle_*, mg_solve_*, the _CFP64 drivers and their _dev forms.  MG_ERR_UNSUPPORTED: every block entry point
+ * (mg_block_*), mg_rap_CF64 (it knows Jac and SPAI only: set the hierarchy up on the host and upload again), mg_adjoint_hierarchy_*. */
+mg_status mg_set_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
+                            long long VankaType, const float* D_blocks);
+mg_status mg_set_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
+                            long long VankaType, const float* D_blocks);
+mg_status mg_set_vanka_relax_CF64(mg_hierarchy* h, long long cycleType);
+mg_status mg_set_vanka_relax_CF32(mg_hierarchy* h, long long cycleType);
+
 /* ---- ComplexF64 Krylov drivers on a CF64 handle (suffix CFP64, the reference's own) ---------------------------------------
  * solveBiCGSTAB_MG / solveGMRES_MG (SolveFuncs.jl:85-133) for VAL = ComplexF64: KrylovMethods.bicgstb / fgmres with one cycle
  * of the handle's hierarchy from x = 0 as preconditioner, every vector resident in HBM across iterations.  The way Helmholtz

@@ -1,6 +1,6 @@
 // mg_complex.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F / K cycles,
-// pointwise or Jac-GMRES relaxation (K and Jac-GMRES: CF64 handles, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
+// pointwise, Jac-GMRES or Vanka relaxation (K and Jac-GMRES: CF64 handles, one right-hand side; Vanka: both precisions, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
 // (the last: one host synchronisation per solve; blocks of right-hand sides by its block form where the option coarse_gmres_blocks asks for it).  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
 // The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
@@ -58,6 +58,11 @@ struct CxLevel {
   // FGMRES_relaxation's Z and AZ (FGMRESmem, FGMRES.jl:1-30), column-major, allocated by mg_finalize only when the schedule needs them:
   DevBuf<double> relaxZ, relaxAZ;   // Jac-GMRES smoothing on this level: max(npre, npost) columns (memRelax)
   DevBuf<double> kZ, kAZ;           // the K-cycle's two FGMRES steps ON this level (levels 2 .. nl-1): 2 columns (memKcycle of the level above)
+  VankaCore* vanka = nullptr;       // relaxation type 2: the cells' blocks (mg_set_vanka_CF64 / _CF32), released with the handle
+  int vanka_type = 0;
+  void release_vanka() {
+    if (vanka) { vanka->release(); delete vanka; vanka = nullptr; }
+  }
 };
 
 struct CxState {
@@ -120,6 +125,7 @@ struct CxState {
       L.d.release(); L.b.release(); L.r.release(); L.x[0].release(); L.x[1].release();
       L.Bb.release(); L.Br.release(); L.Bx[0].release(); L.Bx[1].release();
       L.relaxZ.release(); L.relaxAZ.release(); L.kZ.release(); L.kAZ.release();
+      L.release_vanka();
     }
     gpart.release(); gscal.release();
     if (h_gscal) (void)hipHostFree(h_gscal);
@@ -717,6 +723,15 @@ int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long 
   return MG_OK;
 }
 
+// relaxation type 2 (RelaxVankaFacesColor, MGcycle.jl:51-52, 99-100): numit Vanka iterations of x in place from the level's own CSR, none
+// for a count of 0.  xzero: x was zero-filled by the caller, the from-zero pass opens the relaxation (mg_vanka.hpp).
+template <typename C>
+int cx_vanka_relax(mg_hierarchy* h, CxLevel& L, const C* b, C* x, long long numit, bool xzero) {
+  if (!L.vanka) return fail(MG_ERR_STATE, "a level has no Vanka blocks (mg_set_vanka_CF64 / _CF32)");
+  return vanka_run_cx<C>(L.vanka, L.A.rowptr.p, L.A.colidx.p, static_cast<const C*>(L.A.vals()), b, x, numit, L.vanka_type, xzero,
+                         h->play->stream);
+}
+
 // ---- FGMRES_relaxation (FGMRES.jl:48-126) for VAL = ComplexF64: Jac-GMRES smoothing and the K-cycle -----------------------------------
 // One launch per direction (the GRAM epilogue of cx_csr_stream_spmv: w = A z_j, z_{j+1} = d.*w, the partials of column j of H and of
 // xi[j]), one final sum over all scalars of the steps enqueued so far, one readback, ONE host synchronisation; the small least squares
@@ -864,7 +879,13 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   const double gmresTol = 1e-5;                  // l.5
   if ((gmres_relax || ctype == 'K') && (!is64 || nr != 0))
     return fail(MG_ERR_UNSUPPORTED, "Jac-GMRES smoothing and the K-cycle serve CF64 handles and one right-hand side");
-  if (gmres_relax) {
+  const bool vanka_relax = h->relax_type == 2;   // Vanka (l.51-52, 99-100): x relaxed in place, no ping-pong
+  if (vanka_relax && nr != 0) return fail(MG_ERR_UNSUPPORTED, "Vanka relaxation (type 2) serves one right-hand side");
+  if (vanka_relax) {
+    C* x = cxp<C>(L.x[xi]);
+    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * (size_t)L.n, h->play->stream));
+    MG_TRY(cx_vanka_relax<C>(h, L, b, x, L.npre, xzero));
+  } else if (gmres_relax) {
     if constexpr (is64) {
       // r = b - A x (l.28-31) with ||r||^2 and z_1 = d.*r from the same pass; from x = 0, r0 = b
       cx_t* x = cxp(L.x[xi]);
@@ -923,6 +944,7 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   }
   // x += P xc (l.90): in place, the gather reads xc only
   MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(cx_lx(C1, nr, ci)), cxp<C>(cx_lx(L, nr, xi)), nullptr, nullptr, nullptr, one, one, nr));
+  if (vanka_relax) return cx_vanka_relax<C>(h, L, b, cxp<C>(L.x[xi]), L.npost, false);   // l.99-100
   if (gmres_relax) {                                                                      // r = b - A x, FGMRES_relaxation (l.92-98)
     if constexpr (is64) {
       if (L.npost > 0) {
@@ -948,6 +970,7 @@ int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want = C
 int cx_block_schedule_ok(mg_hierarchy* h) {
   if (h->cycle == 'K' || h->relax_type == 1)
     return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy");
+  if (h->relax_type == 2) return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a complex Vanka hierarchy");
   return MG_OK;
 }
 // The reference calls blockFGMRES for a block on a GMRES coarsest solve (MGcycle.jl:166-167): cx_coarse_block_gmres, served where the
@@ -1070,8 +1093,9 @@ int cx_finalize(mg_hierarchy* h) {
     S.K_auto = false;
   }
   if (S.single && h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF32 handles");
-  if (S.single && h->relax_type != 0) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF32 handles");
-  if (h->relax_type != 0 && h->relax_type != 1) return fail(MG_ERR_UNSUPPORTED, "relaxation type %d is not served for complex handles", h->relax_type);
+  if (S.single && h->relax_type == 1) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF32 handles");
+  if (h->relax_type != 0 && h->relax_type != 1 && h->relax_type != 2)
+    return fail(MG_ERR_UNSUPPORTED, "relaxation type %d is not served for complex handles", h->relax_type);
   size_t maxblocks = 1;
   for (int l = 0; l < nl; ++l) {
     CxLevel& L = S.lev[(size_t)l];
@@ -1096,6 +1120,16 @@ int cx_finalize(mg_hierarchy* h) {
     if (L.R.n_rows != nc || L.R.n_cols != L.n)
       return fail(MG_ERR_INVALID, "Rs[%d] is %lldx%lld, expected %lldx%lld", l + 1, L.R.n_rows, L.R.n_cols, nc, L.n);
   }
+  if (h->relax_type == 2)   // Vanka: every relaxed level has blocks, built for its operator (the pointwise slot carries the sweep counts)
+    for (int l = 0; l < nl - 1; ++l) {
+      const CxLevel& L = S.lev[(size_t)l];
+      if (!L.vanka)
+        return fail(MG_ERR_STATE, "relaxation type 2 (Vanka) is set, but level %d has no blocks (mg_set_vanka_%s)", l + 1, S.single ? "CF32" : "CF64");
+      if (L.vanka->G.N != L.n)
+        return fail(MG_ERR_INVALID, "the Vanka blocks of level %d serve %d unknowns, As[%d] has %lld rows", l + 1, L.vanka->G.N, l + 1, L.n);
+      if (L.A.wide) return fail(MG_ERR_UNSUPPORTED, "As[%d] holds 64-bit row pointers: not served by the Vanka smoother", l + 1);
+      if (L.vanka->single != S.single) return fail(MG_ERR_STATE, "the Vanka blocks of level %d were bound in another precision than the handle's", l + 1);
+    }
   if (S.K.set && S.K.n_rows != S.lev[0].n)
     return fail(MG_ERR_INVALID, "the Krylov operator has order %lld, As[1] %lld rows (clear it with mg_set_krylov_operator_CFP64_INT64(h, n, NULL, ...), finalize, then set a matching one)", S.K.n_rows, S.lev[0].n);
   if (!S.coarse_set) return fail(MG_ERR_STATE, "the coarsest solve was not set");
@@ -1778,6 +1812,7 @@ int cx_adjoint_hierarchy(mg_hierarchy* h, CxWant want) {
     if (L.A.wide || (l + 1 < nl && (L.P.wide || L.R.wide)))
       return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers: the device adjoint serves int32 operators (upload the adjoint hierarchy)", l + 1);
   }
+  if (h->relax_type == 2) return fail(MG_ERR_UNSUPPORTED, "adjointHierarchy of a Vanka hierarchy is refused (MGsetup.jl:288-292)");
   if (S.coarse_lu) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is held as sparse factors: upload the adjoint hierarchy");
   if (h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "the coarsest solve is a Schwarz sweep (mg_set_coarse_dd): set the adjoint hierarchy up again");
   (void)hipSetDevice(h->device);
@@ -1815,6 +1850,45 @@ int cx_adjoint_hierarchy(mg_hierarchy* h, CxWant want) {
   // scratch sizes and shape checks again; a CF32 handle's widened coarsest operator (cgA) is rebuilt from the new As[end] and its
   // widened Krylov operator (K_auto) dropped, to be widened from the new As[1] by the next driver call
   return cx_finalize(h);
+}
+
+// mg_set_vanka_CF64 / _CF32: a VankaCore bound to a complex level, with the checks of mg_set_vanka_FP64
+int cx_set_vanka(mg_hierarchy* h, long long level, CxWant want, long long dim, const long long* n, long long includePressure,
+                 long long VankaType, const float* D_blocks) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, level, want));
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  if (!L.A.set) return fail(MG_ERR_STATE, "As[%lld] was not set: upload the operator before its Vanka blocks", level);
+  if (L.A.wide) return fail(MG_ERR_UNSUPPORTED, "operators with 64-bit row pointers are not served by the Vanka smoother");
+  if (L.A.n_rows != L.A.n_cols) return fail(MG_ERR_INVALID, "As[%lld] is not square", level);
+  MG_TRY(vanka_type_served(VankaType));
+  mgk::VankaGeo G;
+  MG_TRY(vanka_geometry(dim, n, includePressure, L.A.n_rows, &G));
+  (void)hipSetDevice(h->device);
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  L.release_vanka();
+  VankaCore* V = new VankaCore();
+  const int rc = vanka_core_init(V, true, G, D_blocks, h->cx->single);
+  if (rc != MG_OK) {
+    V->release();
+    delete V;
+    return rc;
+  }
+  L.vanka = V;
+  L.vanka_type = (int)VankaType;
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
+// mg_set_vanka_relax_CF64 / _CF32
+int cx_set_vanka_relax(mg_hierarchy* h, CxWant want, long long cycleType) {
+  MG_TRY(cx_handle_ok(h, want));
+  if (cycleType != 'V' && cycleType != 'W' && cycleType != 'F' && cycleType != 'K')
+    return fail(MG_ERR_INVALID, "cycleType must be 'V', 'W', 'F' or 'K'");
+  h->cycle = (char)cycleType;   // ('K' on a CF32 handle: refused by mg_finalize, as everywhere)
+  h->relax_type = 2;
+  h->cx->finalized = false;
+  return MG_OK;
 }
 
 // mg_create_CF64 / mg_create_CF32
@@ -1887,6 +1961,20 @@ int mg_set_schedule_CF64(mg_hierarchy* h, long long cycleType, long long relaxTy
   h->cx->finalized = false;
   return MG_OK;
 }
+
+// The Vanka blocks of one level of a complex handle (relaxation type 2): see include/mgvcycle.h
+int mg_set_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure, long long VankaType,
+                      const float* D_blocks) {
+  return cx_set_vanka(h, level, CX_WANT64, dim, n, includePressure, VankaType, D_blocks);
+}
+int mg_set_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure, long long VankaType,
+                      const float* D_blocks) {
+  return cx_set_vanka(h, level, CX_WANT32, dim, n, includePressure, VankaType, D_blocks);
+}
+
+// Relaxation type 2 with its cycle type, on a complex handle (the shared setters and mg_set_schedule_CF64 keep refusing type 2)
+int mg_set_vanka_relax_CF64(mg_hierarchy* h, long long cycleType) { return cx_set_vanka_relax(h, CX_WANT64, cycleType); }
+int mg_set_vanka_relax_CF32(mg_hierarchy* h, long long cycleType) { return cx_set_vanka_relax(h, CX_WANT32, cycleType); }
 
 // FGMRES_relaxation with the diagonal preconditioner on one level, host vectors: x += Z t
 int mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r0, double* x, long long n, long long inner, double tol,
@@ -2223,6 +2311,8 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
   if (nnz != S.lev[0].A.nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored fine pattern (%lld)", nnz, S.lev[0].A.nnz);
   if (relaxKind != 0 && relaxKind != 1) return fail(MG_ERR_INVALID, "relaxKind must be 0 (Jac) or 1 (SPAI)");
+  if (h->relax_type == 2)
+    return fail(MG_ERR_UNSUPPORTED, "mg_rap_CF64 recomputes Jac and SPAI relaxPrecs: the blocks of a Vanka handle are set up on the host");
   const int nl = (int)h->nlevels;
   for (int l = 0; l < nl; ++l) {
     const CxLevel& L = S.lev[(size_t)l];

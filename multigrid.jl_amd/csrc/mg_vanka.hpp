@@ -18,9 +18,16 @@
 // lower cell first - the order the reference's linear walk adds them in.  No atomics; identical bits on every run.
 //
 // Cell and unknown indices are arithmetic on (dim, n, nf): nothing is uploaded but the operator and the blocks.
-// T = double or the interleaved complex d2_t (blocks: float or float2, applied conjugated - the stored block is the adjoint).
+// T = double, the interleaved complex d2_t or its single twin f2_t (blocks: float or float2, applied conjugated - the stored block
+// is the adjoint).  d2_t promotes the block to double; f2_t (a ComplexF32 level: vectors and operator values in float pairs) applies
+// it as stored, and every product and sum is single.
+//
+// From zero (vanka_delta<T, true>): a level entered with x = 0 has r = (b - A 0)[I] = b[I] for the first snapshot, so that pass reads
+// b and the block only - no matrix walk.  The general pass on a zero x sums products that are all zeros onto a +0 accumulator, which
+// stays +0, and b - (+0) = b bit for bit: both passes write the same deltas.
 #pragma once
 #include "mg_kernels.hpp"
+#include "mg_complex.hpp"
 
 namespace mgk {
 
@@ -34,13 +41,18 @@ struct VankaGeo {
 template <typename T> struct VankaBlk;
 template <> struct VankaBlk<double> { typedef float type; };
 template <> struct VankaBlk<d2_t> { typedef float2 type; };
+template <> struct VankaBlk<f2_t> { typedef float2 type; };
 
 __device__ __forceinline__ double vk_mul(double a, double b) { return a * b; }
 __device__ __forceinline__ d2_t vk_mul(d2_t a, d2_t b) { return d2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ double vk_adj(float a) { return (double)a; }                       // promoted, nothing rounded
-__device__ __forceinline__ d2_t vk_adj(float2 a) { return d2_t{(double)a.x, -(double)a.y}; }  // reshape(D)' conjugates
+__device__ __forceinline__ f2_t vk_mul(f2_t a, f2_t b) { return f2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+template <typename T> __device__ __forceinline__ T vk_adj(typename VankaBlk<T>::type a);
+template <> __device__ __forceinline__ double vk_adj<double>(float a) { return (double)a; }                       // promoted, nothing rounded
+template <> __device__ __forceinline__ d2_t vk_adj<d2_t>(float2 a) { return d2_t{(double)a.x, -(double)a.y}; }   // reshape(D)' conjugates
+template <> __device__ __forceinline__ f2_t vk_adj<f2_t>(float2 a) { return f2_t{a.x, -a.y}; }                    // as stored: no promotion
 __device__ __forceinline__ double vk_shfl8(double a, int j) { return __shfl(a, j, 8); }
 __device__ __forceinline__ d2_t vk_shfl8(d2_t a, int j) { return d2_t{__shfl(a.x, j, 8), __shfl(a.y, j, 8)}; }
+__device__ __forceinline__ f2_t vk_shfl8(f2_t a, int j) { return f2_t{__shfl(a.x, j, 8), __shfl(a.y, j, 8)}; }
 
 // unknown t of cell (c1, c2, c3), 0-based (getVankaVariablesOfCell, Vanka.jl:45-95)
 __device__ __forceinline__ int vanka_unknown(const VankaGeo& G, int c1, int c2, int c3, int t) {
@@ -53,8 +65,9 @@ __device__ __forceinline__ int vanka_unknown(const VankaGeo& G, int c1, int c2, 
 }
 
 // delta[cell][t] = (M_cell (b - A x)[I])_t for the `count` cells of one colour (parity p[d] in dimension d, m[d] cells
-// of that parity per dimension), or for all cells (all != 0: m = n, p ignored).
-template <typename T>
+// of that parity per dimension), or for all cells (all != 0: m = n, p ignored).  ZERO: x is known to be zero and is not read
+// (r = b[I]); the caller has zero-filled it for the apply pass that follows.
+template <typename T, bool ZERO = false>
 __global__ __launch_bounds__(BLK) void vanka_delta(VankaGeo G, const int* __restrict__ rowptr, const int* __restrict__ col,
                                                    const T* __restrict__ val, const typename VankaBlk<T>::type* __restrict__ D,
                                                    const T* __restrict__ b, const T* __restrict__ x, T* __restrict__ delta,
@@ -74,15 +87,19 @@ __global__ __launch_bounds__(BLK) void vanka_delta(VankaGeo G, const int* __rest
   T r = T{};
   if (live && t < G.bs) {
     const int row = vanka_unknown(G, c1, c2, c3, t);
-    T acc = T{};
-    for (int k = rowptr[row], e = rowptr[row + 1]; k < e; ++k) acc += vk_mul(val[k], x[col[k]]);   // stored order, one lane
-    r = b[row] - acc;
+    if constexpr (ZERO) {
+      r = b[row];
+    } else {
+      T acc = T{};
+      for (int k = rowptr[row], e = rowptr[row + 1]; k < e; ++k) acc += vk_mul(val[k], x[col[k]]);   // stored order, one lane
+      r = b[row] - acc;
+    }
   }
   T out = T{};
   const typename VankaBlk<T>::type* Mrow = D + (size_t)cell * (size_t)(G.bs * G.bs) + (size_t)(t < G.bs ? t : 0) * (size_t)G.bs;
   for (int j = 0; j < G.bs; ++j) {
     const T rj = vk_shfl8(r, j);
-    if (live && t < G.bs) out += vk_mul(vk_adj(Mrow[j]), rj);
+    if (live && t < G.bs) out += vk_mul(vk_adj<T>(Mrow[j]), rj);
   }
   if (live && t < G.bs) delta[(size_t)cell * (size_t)G.bs + (size_t)t] = out;
 }

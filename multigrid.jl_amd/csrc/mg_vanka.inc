@@ -1,6 +1,7 @@
 // mg_vanka.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip; not compiled on its own).
 // The Vanka cell-block smoother of src/Multigrid/Vanka.jl on the device: the stand-alone handle (mg_vanka_*, extern "C"
-// below) and the per-level form the cycle runs as relaxation type 2 (VankaCore, bound by mg_set_vanka_FP64, mg_cabi.inc).
+// below) and the per-level form the cycle runs as relaxation type 2 (VankaCore, bound by mg_set_vanka_FP64, mg_cabi.inc, to a real
+// level and by mg_set_vanka_CF64 / _CF32, mg_complex.inc, to a complex one).
 // Kernels and the lane mapping: mg_vanka.hpp.
 namespace {
 
@@ -10,8 +11,9 @@ constexpr int VANKA_FULL_RB = 1, VANKA_KACMARZ = 2, VANKA_ECON_RB = 3, VANKA_FUL
 struct VankaCore {
   mgk::VankaGeo G{};
   bool cx = false;
+  bool single = false;     // cx only: the operator and the vectors hold float pairs (a level of a CF32 handle)
   DevBuf<float> D;         // LocalBlocks: bs*bs single-precision values per cell (complex: interleaved pairs)
-  DevBuf<double> delta;    // cells x bs values of the operator's type
+  DevBuf<double> delta;    // cells x bs values of the operator's type (single: two of them per double slot)
   long long launches = 0;  // kernels enqueued so far
   int colours_live = 0;    // colours that hold a cell (n[d] = 1 leaves the even parity of d empty)
   void release() { D.release(); delta.release(); }
@@ -47,22 +49,25 @@ int vanka_type_served(long long type) {
 }
 
 // D_blocks: (bs*bs) x cells column-major, Float32 (cx: ComplexF32) - the caller's LocalBlocks as they are
-int vanka_core_init(VankaCore* V, bool cx, const mgk::VankaGeo& G, const void* D_blocks) {
+int vanka_core_init(VankaCore* V, bool cx, const mgk::VankaGeo& G, const void* D_blocks, bool single = false) {
   if (!D_blocks) return fail(MG_ERR_INVALID, "D_blocks is null");
   const size_t vw = cx ? 2 : 1;
   V->G = G;
   V->cx = cx;
+  V->single = cx && single;
   V->colours_live = 1;
   for (int d = 0; d < G.dim; ++d) V->colours_live *= G.n[d] >= 2 ? 2 : 1;
   const size_t nD = vw * (size_t)G.bs * (size_t)G.bs * (size_t)G.cells;
   MG_TRY(V->D.alloc(nD));
-  MG_TRY(V->delta.alloc(vw * (size_t)G.bs * (size_t)G.cells));
+  MG_TRY(V->delta.alloc((V->single ? 1 : vw) * (size_t)G.bs * (size_t)G.cells));
   HIP_TRY(hipMemcpy(V->D.p, D_blocks, nD * sizeof(float), hipMemcpyHostToDevice));
   return MG_OK;
 }
 
 // numit relaxations of x (in place) on `stream`, no synchronisation.  The caller has checked the type (vanka_type_served).
-template <typename T>
+// ZERO: x holds zeros on entry (the caller zero-filled it), so the first snapshot's residual is b[I] and its pass walks no matrix row
+// (vanka_delta<T, true>): the first colour of the first iteration, or the one pass of FULL_VANKA_ADD.
+template <typename T, bool ZERO = false>
 int vanka_sweeps(VankaCore* V, const int* rowptr, const int* col, const T* val, const T* b, T* x, long long numit, int type,
                  hipStream_t stream) {
   typedef typename mgk::VankaBlk<T>::type B;
@@ -73,7 +78,7 @@ int vanka_sweeps(VankaCore* V, const int* rowptr, const int* col, const T* val, 
   auto blocks = [](long long groups) { return dim3((unsigned)((groups * 8 + mgk::BLK - 1) / mgk::BLK)); };
   if (type == VANKA_FULL_ADD) {
     // y = copy(x) once per call (Vanka.jl:396): every iteration adds the same corrections
-    hipLaunchKernelGGL(mgk::vanka_delta<T>, blocks(G.cells), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, G.cells,
+    hipLaunchKernelGGL((mgk::vanka_delta<T, ZERO>), blocks(G.cells), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, G.cells,
                        G.n[0], G.n[1], 0, 0, 0, 1);
     ++V->launches;
     for (long long it = 0; it < numit; ++it) {
@@ -85,6 +90,7 @@ int vanka_sweeps(VankaCore* V, const int* rowptr, const int* col, const T* val, 
     return MG_OK;
   }
   const int ncol = 1 << G.dim;
+  bool from_zero = ZERO;   // until the first colour has been applied
   for (long long it = 0; it < numit; ++it)
     for (int c = 0; c < ncol; ++c) {
       // cellColor (Vanka.jl:105-127): the first dimension's parity is the most significant bit; odd 1-based = even 0-based first
@@ -95,8 +101,13 @@ int vanka_sweeps(VankaCore* V, const int* rowptr, const int* col, const T* val, 
       }
       const long long count = (long long)m[0] * m[1] * m[2];
       if (count == 0) continue;
-      hipLaunchKernelGGL(mgk::vanka_delta<T>, blocks(count), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, (int)count,
-                         m[0], m[1], p[0], p[1], p[2], 0);
+      if (ZERO && from_zero)
+        hipLaunchKernelGGL((mgk::vanka_delta<T, ZERO>), blocks(count), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, (int)count,
+                           m[0], m[1], p[0], p[1], p[2], 0);
+      else
+        hipLaunchKernelGGL((mgk::vanka_delta<T, false>), blocks(count), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, (int)count,
+                           m[0], m[1], p[0], p[1], p[2], 0);
+      from_zero = false;
       hipLaunchKernelGGL(mgk::vanka_apply_colour<T>, blocks(count), dim3(mgk::BLK), 0, stream, G, delta, x, (int)count, m[0], m[1], p[0],
                          p[1], p[2]);
       V->launches += 2;
@@ -111,6 +122,16 @@ int vanka_run(VankaCore* V, const int* rowptr, const int* col, const double* val
     return vanka_sweeps<mgk::d2_t>(V, rowptr, col, reinterpret_cast<const mgk::d2_t*>(val), reinterpret_cast<const mgk::d2_t*>(b),
                                    reinterpret_cast<mgk::d2_t*>(x), numit, type, stream);
   return vanka_sweeps<double>(V, rowptr, col, val, b, x, numit, type, stream);
+}
+
+// The same on a level of a complex hierarchy: C = mgk::d2_t (a CF64 handle) or mgk::f2_t (a CF32 handle, V->single).  xzero: the caller
+// has zero-filled x (a level entered from zero): the from-zero pass opens the call.
+template <typename C>
+int vanka_run_cx(VankaCore* V, const int* rowptr, const int* col, const C* val, const C* b, C* x, long long numit, int type, bool xzero,
+                 hipStream_t stream) {
+  if (!V->cx || V->single != (sizeof(C) == sizeof(mgk::f2_t))) return fail(MG_ERR_INVALID, "internal: Vanka blocks and vectors differ in type");
+  if (xzero) return vanka_sweeps<C, true>(V, rowptr, col, val, b, x, numit, type, stream);
+  return vanka_sweeps<C, false>(V, rowptr, col, val, b, x, numit, type, stream);
 }
 
 }  // namespace

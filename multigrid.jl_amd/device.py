@@ -202,6 +202,10 @@ SIGNATURES = {
     "mg_set_operator_CF64_INT64": (C.c_int, [_vp, _ll, _ll, _ll, _ll, _lp, _lp, _dp]),
     "mg_set_relax_CF64": (C.c_int, [_vp, _ll, _dp, _ll, _ll, _ll]),
     "mg_set_schedule_CF64": (C.c_int, [_vp, _ll, _ll]),
+    "mg_set_vanka_CF64": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, C.POINTER(C.c_float)]),
+    "mg_set_vanka_CF32": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, C.POINTER(C.c_float)]),
+    "mg_set_vanka_relax_CF64": (C.c_int, [_vp, _ll]),
+    "mg_set_vanka_relax_CF32": (C.c_int, [_vp, _ll]),
     "mg_fgmres_relax_CF64": (C.c_int, [_vp, _ll, _dp, _dp, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp]),
     "mg_set_coarse_dense_inverse_CF64": (C.c_int, [_vp, _ll, _dp]),
     "mg_set_coarse_lu_CF64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
@@ -345,8 +349,15 @@ def _vanka_guard(param, nrhs: int):
         raise NotImplementedError("FULL_VANKA_LEX is a sequential sweep over the cells; the package keeps no CPU fallback")
     if int(nrhs) != 1:
         raise NotImplementedError("Vanka hierarchies serve one right-hand side (blocks of right-hand sides are out of scope)")
-    if param.cycleType == "K":
-        raise NotImplementedError("Vanka hierarchies serve the V, W and F cycles (cycleType='K' is out of scope)")
+    val = np.dtype(getattr(param, "VAL", np.float64))
+    if val.kind == "c":
+        if not getattr(param, "complexVanka", False):
+            raise NotImplementedError("complex Vanka hierarchies are asked for with getMGparam(np.complex128, ..., complexVanka=True)")
+        from .mgdef import _solver_object
+        if _solver_object(param.LU) == "dd":
+            raise NotImplementedError("complex Vanka hierarchies: a Schwarz coarsest solve is out of scope")
+    if param.cycleType == "K" and val != np.complex128:
+        raise NotImplementedError("Vanka hierarchies serve the V, W and F cycles (cycleType='K': ComplexF64 hierarchies only)")
     if param.transferOperatorType not in ("SystemsFacesLinear", "SystemsFacesMixedLinear") or not param.Meshes:
         raise NotImplementedError("Vanka hierarchies need the staggered meshes of MGsetup with a Systems transfer operator")
 
@@ -928,7 +939,8 @@ def _c128(a):
 
 
 class ComplexDeviceHierarchy(DeviceHierarchy):
-    """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F / K cycles, Jac / SPAI / Jac-GMRES relaxation,
+    """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F / K cycles, Jac / SPAI / Jac-GMRES relaxation
+    or (a param with ``complexVanka=True``) the Vanka cell-block smoothers, one right-hand side only,
     dense-inverse, sparse-LU or GMRES coarsest solve (the last adds one host synchronisation per coarsest solve and serves blocks only for a param with ``blockCoarseGMRES=True``: ``block_coarse_gmres``).  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
     methods, which take the column count with each call (not on a K-cycle / Jac-GMRES hierarchy).  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
@@ -978,19 +990,37 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         _check(self.lib, self.lib.mg_set_relax_CF64(self.handle, level, _c128(d), d.size, int(pre), int(post)),
                f"mg_set_relax_CF64(level={level})")
 
+    def _set_relax_level(self, param, l, pre, post, blocks=True):
+        """relaxPrecs[l]: the pointwise vector, or (a complex Vanka hierarchy) the cells' complex64 blocks - then the pointwise
+        slot holds zeros, which nothing reads, and carries the sweep counts (blocks=False: new sweep counts only)."""
+        if not self._vanka:
+            return self._set_relax(l, param.relaxPrecs[l - 1], pre, post)
+        if not blocks:
+            return self._set_relax(l, np.zeros(param.As[l - 1].shape[0], dtype=self._cdtype), pre, post)
+        from .vanka import getVankaRelaxType
+        blk = param.relaxPrecs[l - 1]
+        if not isinstance(blk, np.ndarray) or blk.dtype != np.complex64 or blk.ndim != 2:
+            raise TypeError("relaxPrecs of a complex Vanka hierarchy are the complex64 blocks of setupVankaFacesPreconditioner")
+        blk = np.asfortranarray(blk)
+        nn = np.ascontiguousarray(param.Meshes[l - 1].n, dtype=np.int64)
+        mixed = param.transferOperatorType == "SystemsFacesMixedLinear"
+        _check(self.lib, self._fn("set_vanka")(self.handle, l, nn.size, _i64(nn), 1 if mixed else 0,
+                                               getVankaRelaxType(param.relaxType)[1], blk.ctypes.data_as(_fp)),
+               f"mg_set_vanka_{self._sfx}(level={l})")
+        self._set_relax(l, np.zeros(param.As[l - 1].shape[0], dtype=self._cdtype), pre, post)
+
     def _upload(self, param):
         lib = self.lib
         nl = self.nlevels
-        if _relax_type_code(param) == 2:
-            raise NotImplementedError("ComplexF64 hierarchies: the Vanka smoothers serve VAL=Float64 hierarchies (complex operators: "
-                                      "the stand-alone RelaxVankaFacesColor)")
+        _vanka_guard(param, self.nrhs)
+        self._vanka = _relax_type_code(param) == 2
         self._refuse_schedule(param)
         for l in range(1, nl + 1):
             self._set_op(l, MG_OP_A, param.As[l - 1])
             if l < nl:
                 self._set_op(l, MG_OP_P, param.Ps[l - 1])
                 self._set_op(l, MG_OP_R, param.Rs[l - 1])
-                self._set_relax(l, param.relaxPrecs[l - 1], param.relaxPre(l), param.relaxPost(l))
+                self._set_relax_level(param, l, param.relaxPre(l), param.relaxPost(l))
         self._set_schedule(param)
         if param.LU is None:
             raise MGDeviceError("param.LU is empty: run MGsetup first")
@@ -1008,7 +1038,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def _set_schedule(self, param):
         lib = self.lib
-        if self._sfx == "CF64":
+        if self._vanka:       # relaxation type 2 with its cycle type: a setter of its own (the shared ones refuse type 2 on complex handles)
+            _check(lib, self._fn("set_vanka_relax")(self.handle, ord(param.cycleType)), f"mg_set_vanka_relax_{self._sfx}")
+        elif self._sfx == "CF64":
             _check(lib, lib.mg_set_schedule_CF64(self.handle, ord(param.cycleType), _relax_type_code(param)), "mg_set_schedule_CF64")
         else:
             _check(lib, lib.mg_set_relax_type(self.handle, 0), "mg_set_relax_type")
@@ -1016,10 +1048,15 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def _block_guard(self):
         """The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51); that form is not built."""
+        self._vanka_block_guard()
         sched = getattr(self, "_schedule", None)
         if sched is not None and (sched[0] == "K" or sched[1] == "Jac-GMRES"):
             raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle / Jac-GMRES ComplexF64 hierarchy "
                                       "(solve the columns one after the other)")
+
+    def _vanka_block_guard(self):
+        if getattr(self, "_vanka", False):
+            raise NotImplementedError("blocks of right-hand sides are not served on a complex Vanka hierarchy (out of scope)")
 
     def _block_coarse_guard(self, k: int):
         """The reference calls blockFGMRES for a block on the GMRES coarsest solve (MGcycle.jl:166-167); that form runs where the
@@ -1034,9 +1071,14 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             self._schedule = sig
             return
         self._refuse_schedule(param)
+        _vanka_guard(param, self.nrhs)
+        old = self._schedule
+        if (_relax_type_code(param) == 2) != self._vanka or (self._vanka and sig[1] != old[1]):
+            raise NotImplementedError("relaxType changed to or from a Vanka smoother after the setup: relaxPrecs hold the other "
+                                      "smoother's data - run MGsetup again")
         lib = self.lib
         for l in range(1, self.nlevels):
-            self._set_relax(l, param.relaxPrecs[l - 1], sig[2][l - 1], sig[3][l - 1])
+            self._set_relax_level(param, l, sig[2][l - 1], sig[3][l - 1], blocks=False)
         self._set_schedule(param)
         _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
         self._schedule = sig
@@ -1099,6 +1141,8 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         Jacobi-preconditioned blockFGMRES(10) from zero on the coarsest operator for the complex128 block ``B`` (n_c x k, k <= 16).
         Returns (X, flag, resvec): flag 0 / -1 / -9 and the estimates ||xi - H Y||_F / ||B||_F of the steps used, of the whole block."""
         Bf, k = self._blk(B)
+        if k > 1:
+            self._vanka_block_guard()
         self._block_coarse_guard(k)
         X = np.zeros(Bf.shape, dtype=np.complex128, order="F")
         steps, flag = C.c_longlong(0), C.c_longlong(0)

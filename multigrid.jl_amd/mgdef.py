@@ -47,6 +47,7 @@ class MGparam:
     transferOperatorType: str = "FullWeighting"
     singlePrecision: bool = False
     blockCoarseGMRES: bool = False     # coarseSolveType "GMRES" on a complex hierarchy: serve blocks by the block GMRES coarsest solve
+    complexVanka: bool = False         # a Vanka relaxType on a complex hierarchy: the cell-block smoother in the complex cycle
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -59,7 +60,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                relaxType="SPAI", relaxParam=1.0, relaxPre=2, relaxPost=2, cycleType="V",
                coarseSolveType="NoMUMPS", strongConnParam=0.4, FilteringParam=0.0,
                transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
-               blockCoarseGMRES: bool = False) -> MGparam:
+               blockCoarseGMRES: bool = False, complexVanka: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -71,6 +72,10 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     ``blockCoarseGMRES=True`` (keyword only) with a complex ``VAL`` and ``coarseSolveType="GMRES"`` switches on the block form of
     that coarsest solve (the reference's blockFGMRES branch, MGcycle.jl:165-167): blocks of 2 to 16 right-hand sides are then
     served on the hierarchy; without it they are refused.  The columns of a block are coupled by that solve.
+    ``complexVanka=True`` (keyword only) with a complex ``VAL`` and a Vanka ``relaxType`` (VankaFaces, EconVankaFaces, VankaFacesAdd)
+    lets ``MGsetup`` build the complex Vanka hierarchy of the reference (Systems transfers, complex64 blocks per level) and the
+    device run it: ComplexF64 with cycles V / W / F / K, ``singlePrecision`` with V / W / F, one right-hand side.  Without it a
+    complex Vanka param is refused by ``MGsetup``, as before.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
@@ -79,6 +84,10 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
         raise NotImplementedError("singlePrecision=True serves VAL=ComplexF64 (Float32 real hierarchies are out of scope)")
     if blockCoarseGMRES and (np.dtype(VAL) != np.complex128 or str(coarseSolveType) != "GMRES"):
         raise NotImplementedError("blockCoarseGMRES=True serves VAL=ComplexF64 (singlePrecision or not) with coarseSolveType='GMRES'")
+    if complexVanka:
+        from .vanka import getVankaRelaxType
+        if np.dtype(VAL) != np.complex128 or not getVankaRelaxType(str(relaxType))[0]:
+            raise NotImplementedError("complexVanka=True serves VAL=ComplexF64 (singlePrecision or not) with a Vanka relaxType")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -92,7 +101,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    relaxPre=pre, relaxPost=post, cycleType=cycleType, coarseSolveType=str(coarseSolveType),
                    strongConnParam=float(strongConnParam), FilteringParam=float(FilteringParam),
                    transferOperatorType=str(transferOperatorType), singlePrecision=bool(singlePrecision),
-                   blockCoarseGMRES=bool(blockCoarseGMRES), VAL=np.dtype(VAL).type, IND=np.int64)
+                   blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka), VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -164,7 +173,7 @@ def copySolver(MG: MGparam) -> MGparam:
     new = getMGparam(np.complex128 if single else MG.VAL, MG.IND, MG.levels, MG.numCores, MG.maxOuterIter, MG.relativeTol,
                      MG.relaxType, MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
                      MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single,
-                     blockCoarseGMRES=bool(MG.blockCoarseGMRES))
+                     blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

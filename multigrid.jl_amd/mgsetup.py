@@ -204,7 +204,11 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
     if param.coarseSolveType == "VankaFaces":
         raise NotImplementedError("coarseSolveType='VankaFaces' calls functions that are commented out in the reference")
     if _is_vanka(param) and is_complex(param):
-        raise NotImplementedError("Vanka hierarchies serve VAL=Float64 (the stand-alone RelaxVankaFacesColor takes complex operators)")
+        if not param.complexVanka:
+            raise NotImplementedError("Vanka hierarchies serve VAL=Float64 (the stand-alone RelaxVankaFacesColor takes complex operators); "
+                                      "a complex one is asked for with getMGparam(np.complex128, ..., complexVanka=True)")
+        if not systems:
+            raise NotImplementedError("a complex Vanka hierarchy needs transferOperatorType 'SystemsFacesLinear' or 'SystemsFacesMixedLinear'")
     _release_device(param)
     levels = param.levels
     relaxParamArr = _relax_param_arr(param)

@@ -41,6 +41,15 @@ def _coarse_gmres_guard(param: MGparam, b) -> None:
                                   "(solve the columns one after the other)")
 
 
+def _vanka_block_guard(param: MGparam, b) -> None:
+    """A complex Vanka hierarchy given more than one column: blocks of right-hand sides with Vanka are out of scope, refused before
+    the device is touched (a real one is refused by ``_vanka_guard`` through the handle's nrhs)."""
+    from .mgsetup import _is_vanka
+    if _complex_block(param, b) and _is_vanka(param):
+        raise NotImplementedError("blocks of right-hand sides are not served on a complex Vanka hierarchy (solve the columns one "
+                                  "after the other)")
+
+
 def _width(param: MGparam, b) -> int:
     """The nrhs the handle is sized for: the block's columns, or 1 for a complex hierarchy (see ``_complex_block``)."""
     return 1 if is_complex(param) else _ncols(b)
@@ -63,6 +72,7 @@ def to_device(param: MGparam, device_id: int = 0) -> DeviceHierarchy:
 
 def solveMG(param: MGparam, b: np.ndarray, x: np.ndarray, verbose: bool = False):
     """``(x, param, iter) = solveMG(param,b,x,verbose)``: x is updated IN PLACE (testGMG.jl:54-55)."""
+    _vanka_block_guard(param, b)
     _coarse_gmres_guard(param, b)
     adjustMemoryForNumRHS(param, _width(param, b))
     dev = to_device(param)
@@ -81,6 +91,7 @@ def recursiveCycle(param: MGparam, b: np.ndarray, x: np.ndarray, level: int = 1)
     """One cycle from the finest level.  Only ``level == 1`` is an entry point of the device library."""
     if level != 1:
         raise ValueError("the device library owns the recursion: only level=1 can be entered from the host")
+    _vanka_block_guard(param, b)
     _coarse_gmres_guard(param, b)
     adjustMemoryForNumRHS(param, _width(param, b))
     if _complex_block(param, b):
@@ -94,6 +105,7 @@ def getMultigridPreconditioner(param: MGparam, B: np.ndarray, verbose: bool = Fa
     """``M(b) = (z .= 0; recursiveCycle(param,b,z,1); z)`` (SolveFuncs.jl:59): x = 0 on entry."""
     if not hierarchyExists(param):
         print("You have to do a setup first.")
+    _vanka_block_guard(param, B)
     _coarse_gmres_guard(param, B)
     adjustMemoryForNumRHS(param, _width(param, B))
     dev = to_device(param)
@@ -262,6 +274,7 @@ def solveBlockBiCGSTAB_MG_CFP64(A, param: MGparam, B: np.ndarray, X0: np.ndarray
         raise TypeError("solveBlockBiCGSTAB_MG_CFP64 serves VAL=ComplexF64 hierarchies; a Float64 hierarchy goes to solveBiCGSTAB_MG")
     if _ncols(B) != _ncols(X0):
         raise ValueError("B and X0 must hold the same number of columns")
+    _vanka_block_guard(param, B)
     _coarse_gmres_guard(param, B)
     adjustMemoryForNumRHS(param, 1)               # the block entry points take the column count with each call
     dev = to_device(param)
@@ -289,6 +302,7 @@ def solveBlockGMRES_MG_CFP64(A, param: MGparam, B: np.ndarray, X0: np.ndarray, f
         raise TypeError("solveBlockGMRES_MG_CFP64 serves VAL=ComplexF64 hierarchies; a Float64 hierarchy goes to solveGMRES_MG")
     if _ncols(B) != _ncols(X0):
         raise ValueError("B and X0 must hold the same number of columns")
+    _vanka_block_guard(param, B)
     _coarse_gmres_guard(param, B)
     adjustMemoryForNumRHS(param, 1)               # the block entry points take the column count with each call
     dev = to_device(param)
@@ -311,6 +325,7 @@ _WHICH = {"A": MG_OP_A, "P": MG_OP_P, "R": MG_OP_R}
 def SpMatMul(param: MGparam, level: int, which: str, x: np.ndarray, target: np.ndarray,
              alpha: float = 1.0, beta: float = 0.0):
     """``target = beta*target + alpha*Op*x`` (SpMatMul.jl:4-13) with Op = As/Ps/Rs[level] resident on device."""
+    _vanka_block_guard(param, x)
     _coarse_gmres_guard(param, x)
     adjustMemoryForNumRHS(param, _width(param, x))
     if _complex_block(param, x):
