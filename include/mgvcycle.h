@@ -618,6 +618,13 @@ int mg_vanka_apply_FP64(mg_vanka* v, double* x, const double* b, long long numit
 int mg_vanka_apply_dev_FP64(mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long VankaType);
 int mg_vanka_apply_CFP64(mg_vanka* v, double* x, const double* b, long long numit, long long VankaType);
 int mg_vanka_apply_dev_CFP64(mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long VankaType);
+/* The same on a block of nrhs right-hand sides, 1 <= nrhs <= 16 (nrhs < 1: MG_ERR_INVALID; nrhs > 16: MG_ERR_UNSUPPORTED; both
+ * before the first write).  Host forms: x, b column-major N x nrhs; _dev forms: row-major [N][nrhs] device blocks.  One pass over
+ * the operator and the cells' blocks serves all columns; column c holds the bits mg_vanka_apply_* gives on column c alone. */
+int mg_vanka_apply_block_FP64(mg_vanka* v, double* x, const double* b, long long nrhs, long long numit, long long VankaType);
+int mg_vanka_apply_block_dev_FP64(mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long numit, long long VankaType);
+int mg_vanka_apply_block_CFP64(mg_vanka* v, double* x, const double* b, long long nrhs, long long numit, long long VankaType);
+int mg_vanka_apply_block_dev_CFP64(mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long numit, long long VankaType);
 /* info[0..8): value type (0 Float64, 1 ComplexF64); blockSize; cells; colours (2^dim); kernel launches of one RB / ECON
  * iteration (two per colour that holds a cell); of one ADD iteration (one, plus one per call); unknowns; kernels the handle
  * has enqueued so far. */
@@ -626,6 +633,8 @@ int mg_vanka_info(mg_vanka* v, long long* info);
  * the handle's stream; ms[0..reps) in milliseconds.  x_dev is relaxed in place. */
 int mg_vanka_time_dev(mg_vanka* v, double* x_dev, const double* b_dev, long long VankaType, long long warmup, long long reps,
                       double* ms);
+int mg_vanka_time_block_dev(mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long VankaType, long long warmup,
+                            long long reps, double* ms);   /* the same on a row-major device block of nrhs columns */
 int mg_vanka_destroy(mg_vanka* v);
 
 /* ---- native multi-GPU sequencer (one process per GPU) ---------------------------------------------------------
@@ -1001,7 +1010,14 @@ mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r
  * level's own CSR (a count of 0: none).  A level entered with x = 0 is zero-filled and its first pass reads b and the blocks only (no
  * matrix walk; the one pass of FULL_VANKA_ADD altogether) - bit-identical to the general pass on a zero x, which x_is_zero = 0 runs.
  * Served: mg_cycle_*, mg_solve_*, the _CFP64 drivers and their _dev forms.  MG_ERR_UNSUPPORTED: every block entry point
- * (mg_block_*), mg_rap_CF64 (it knows Jac and SPAI only: set the hierarchy up on the host and upload again), mg_adjoint_hierarchy_*. */
+ * (mg_block_*), mg_rap_CF64 (it knows Jac and SPAI only: set the hierarchy up on the host and upload again), mg_adjoint_hierarchy_*.
+ * BLOCKS, OPT-IN: mg_set_option(h, "vanka_blocks", 1) (default 0; read at every call).  With 1 the mg_block_* entry points serve a
+ * handle in relaxation type 2 for 1 <= nrhs <= 16 and the cycles V / W / F: mg_block_cycle_CF64, mg_block_solve_CF64,
+ * mg_block_spmv_CF64, mg_block_cycle_dev_CFP64, mg_block_bicgstab[_dev]_CFP64, mg_block_fgmres[_dev]_CFP64 (CF64 and CF32 handles as
+ * each of them serves them today).  The smoother runs on the row-major block in place (the _blk kernels of mg_vanka.hpp); column c
+ * holds the bits of the one-vector smoother on column c, the from-zero pass is decided for the whole block, and the delta buffer
+ * (cells x bs x nrhs) grows with the block work set.  The K-cycle, nrhs > 16 and a Schwarz coarsest solve stay MG_ERR_UNSUPPORTED,
+ * X untouched.  With 0 every return code and message is what it was before the option existed. */
 mg_status mg_set_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
                             long long VankaType, const float* D_blocks);
 mg_status mg_set_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,

@@ -725,9 +725,13 @@ int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long 
 
 // relaxation type 2 (RelaxVankaFacesColor, MGcycle.jl:51-52, 99-100): numit Vanka iterations of x in place from the level's own CSR, none
 // for a count of 0.  xzero: x was zero-filled by the caller, the from-zero pass opens the relaxation (mg_vanka.hpp).
+// nr >= 1: b and x are row-major blocks of nr columns (option vanka_blocks), relaxed by the block form of the smoother.
 template <typename C>
-int cx_vanka_relax(mg_hierarchy* h, CxLevel& L, const C* b, C* x, long long numit, bool xzero) {
+int cx_vanka_relax(mg_hierarchy* h, CxLevel& L, const C* b, C* x, long long numit, bool xzero, int nr = 0) {
   if (!L.vanka) return fail(MG_ERR_STATE, "a level has no Vanka blocks (mg_set_vanka_CF64 / _CF32)");
+  if (nr != 0)
+    return vanka_run_cx_blk<C>(L.vanka, L.A.rowptr.p, L.A.colidx.p, static_cast<const C*>(L.A.vals()), b, x, nr, numit, L.vanka_type, xzero,
+                               h->play->stream);
   return vanka_run_cx<C>(L.vanka, L.A.rowptr.p, L.A.colidx.p, static_cast<const C*>(L.A.vals()), b, x, numit, L.vanka_type, xzero,
                          h->play->stream);
 }
@@ -880,11 +884,11 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   if ((gmres_relax || ctype == 'K') && (!is64 || nr != 0))
     return fail(MG_ERR_UNSUPPORTED, "Jac-GMRES smoothing and the K-cycle serve CF64 handles and one right-hand side");
   const bool vanka_relax = h->relax_type == 2;   // Vanka (l.51-52, 99-100): x relaxed in place, no ping-pong
-  if (vanka_relax && nr != 0) return fail(MG_ERR_UNSUPPORTED, "Vanka relaxation (type 2) serves one right-hand side");
-  if (vanka_relax) {
-    C* x = cxp<C>(L.x[xi]);
-    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * (size_t)L.n, h->play->stream));
-    MG_TRY(cx_vanka_relax<C>(h, L, b, x, L.npre, xzero));
+  if (vanka_relax && nr != 0 && !h->opt.vanka_blocks) return fail(MG_ERR_UNSUPPORTED, "Vanka relaxation (type 2) serves one right-hand side");
+  if (vanka_relax) {   // (a block, option vanka_blocks: the block form of the smoother on Bx, in place as well)
+    C* x = cxp<C>(cx_lx(L, nr, xi));
+    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * (size_t)L.n * (size_t)std::max(nr, 1), h->play->stream));
+    MG_TRY(cx_vanka_relax<C>(h, L, b, x, L.npre, xzero, nr));
   } else if (gmres_relax) {
     if constexpr (is64) {
       // r = b - A x (l.28-31) with ||r||^2 and z_1 = d.*r from the same pass; from x = 0, r0 = b
@@ -944,7 +948,7 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   }
   // x += P xc (l.90): in place, the gather reads xc only
   MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(cx_lx(C1, nr, ci)), cxp<C>(cx_lx(L, nr, xi)), nullptr, nullptr, nullptr, one, one, nr));
-  if (vanka_relax) return cx_vanka_relax<C>(h, L, b, cxp<C>(L.x[xi]), L.npost, false);   // l.99-100
+  if (vanka_relax) return cx_vanka_relax<C>(h, L, b, cxp<C>(cx_lx(L, nr, xi)), L.npost, false, nr);   // l.99-100
   if (gmres_relax) {                                                                      // r = b - A x, FGMRES_relaxation (l.92-98)
     if constexpr (is64) {
       if (L.npost > 0) {
@@ -970,7 +974,8 @@ int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want = C
 int cx_block_schedule_ok(mg_hierarchy* h) {
   if (h->cycle == 'K' || h->relax_type == 1)
     return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy");
-  if (h->relax_type == 2) return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a complex Vanka hierarchy");
+  // (served by the block form of the smoother where the handle's option vanka_blocks is set; default 0: refused, as before it existed)
+  if (h->relax_type == 2 && !h->opt.vanka_blocks) return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a complex Vanka hierarchy");
   return MG_OK;
 }
 // The reference calls blockFGMRES for a block on a GMRES coarsest solve (MGcycle.jl:166-167): cx_coarse_block_gmres, served where the
@@ -1002,6 +1007,18 @@ int cx_block_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want) {
 int cx_block_ensure(mg_hierarchy* h, int nr) {
   CxState& S = *h->cx;
   MG_TRY(cx_cb_ensure(h, nr));
+  if (h->relax_type == 2) {   // Vanka levels (option vanka_blocks): the delta buffers of the block smoother, cells x bs x nr
+    bool waited = false;
+    for (auto& L : S.lev)
+      if (L.vanka && L.vanka->bk < nr) {   // (also blocks bound again since the last block call)
+        if (!waited) {
+          (void)hipSetDevice(h->device);
+          HIP_TRY(spin_sync(h->play->stream));
+          waited = true;
+        }
+        MG_TRY(vanka_block_ensure(L.vanka, nr));
+      }
+  }
   if (nr <= S.blk_cap) return MG_OK;
   (void)hipSetDevice(h->device);
   HIP_TRY(spin_sync(h->play->stream));   // (an earlier block call may still read the buffers replaced below)

@@ -151,6 +151,9 @@ bool host_all_zero(const double* x, long long len) {
                                               (coarse_gmres_blocks) with the block's VALUES n_c * nrhs - one number moves both thresholds */ \
   X(bool, coarse_gmres_blocks, false)      /* complex GMRES coarsest solve: serve blocks of right-hand sides by the block form of the solve \
                                               (blockFGMRES, cx_coarse_block_gmres); 0: a block on such a hierarchy is refused; read at every call */ \
+  X(bool, vanka_blocks, false)             /* complex Vanka hierarchies (relaxation type 2): serve blocks of right-hand sides by the block \
+                                              form of the smoother (the _blk kernels of mg_vanka.hpp); 0: a block on such a hierarchy is \
+                                              refused; read at every call */ \
   X(long long, lu_dense_tail_min, 64) \
   X(long long, lu_dense_tail_max, 16384)   /* largest trailing block kept as an explicit inverse (8*M^2 bytes each for L and U: 2 x 2.1 GB) */ \
   X(double, rowclass_min_cover, 0.9) \

@@ -25,6 +25,13 @@
 // From zero (vanka_delta<T, true>): a level entered with x = 0 has r = (b - A 0)[I] = b[I] for the first snapshot, so that pass reads
 // b and the block only - no matrix walk.  The general pass on a zero x sums products that are all zeros onto a +0 accumulator, which
 // stays +0, and b - (+0) = b bit for bit: both passes write the same deltas.
+//
+// Blocks of right-hand sides (the _blk kernels at the end; row-major [N][k], 1 <= k <= BLK_KMAX): the group of eight owns one
+// (cell, column) pair - group q of a launch serves cell q / k, column q % k - so every rule above holds per column: one lane per
+// (row, column) sum, stored order, the dense product j = 0..bs-1 inside the group, delta launch then apply launch, no atomics.  The
+// expressions are the ones above, so column c of a block pass has the bits of the one-vector pass on column c.  The k groups of a
+// cell are neighbours: the loads of rowptr / col / val and of the dense block hit the same addresses, x[col*k + c] and b[row*k + c]
+// are consecutive in c.  delta is [cells][bs][k]; from zero is a property of the whole block.
 #pragma once
 #include "mg_kernels.hpp"
 #include "mg_complex.hpp"
@@ -148,6 +155,100 @@ __global__ __launch_bounds__(BLK) void vanka_apply_add(VankaGeo G, const T* __re
   if (lo >= 0) v = v + delta[(size_t)lo * (size_t)G.bs + (size_t)tlo];
   if (hi >= 0) v = v + delta[(size_t)hi * (size_t)G.bs + (size_t)thi];
   x[u] = v;
+}
+
+// ---- blocks of right-hand sides: row-major [N][k], 1 <= k <= BLK_KMAX ------------------------------------------------------------
+// The eight-lane group stays and owns one (cell, column) pair: group q serves the cell q / k of the launch and the column q % k, so a
+// lane still owns one (row, column) sum, walks the row's products in stored order and takes the dense product j = 0..bs-1 inside its
+// group.  Neighbouring groups (the k columns of a cell) read the same rowptr / col / val / block addresses - one fetch serves them -
+// and x[col*k + c], b[row*k + c] are consecutive in c.  The expressions are those of the one-vector kernels, so column c of a block
+// pass holds the bits the one-vector kernels give on column c alone; k = 1 is the one-vector pass.  delta is [cells][bs][k].
+// cells * 8 * k and N * k are formed in 64 bits and compared before anything is narrowed.
+template <typename T, bool ZERO = false>
+__global__ __launch_bounds__(BLK) void vanka_delta_blk(VankaGeo G, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                       const T* __restrict__ val, const typename VankaBlk<T>::type* __restrict__ D,
+                                                       const T* __restrict__ b, const T* __restrict__ x, T* __restrict__ delta, int k,
+                                                       int count, int m1, int m2, int p1, int p2, int p3, int all) {
+  const long long gid = (long long)blockIdx.x * BLK + threadIdx.x;
+  const int t = (int)(gid & 7);
+  const long long grp = gid >> 3;
+  const bool live = grp < (long long)count * k;   // (whole groups of eight: the shuffles below run with every lane of a live group)
+  int c1 = 0, c2 = 0, c3 = 0, c = 0;
+  if (live) {
+    const int g = (int)(grp / k);         // < count
+    c = (int)(grp % k);
+    const int k1 = g % m1, q = g / m1, k2 = q % m2, k3 = q / m2;
+    c1 = all ? k1 : 2 * k1 + p1;
+    c2 = all ? k2 : 2 * k2 + p2;
+    c3 = all ? k3 : 2 * k3 + p3;
+  }
+  const int cell = c1 + G.n[0] * (c2 + G.n[1] * c3);
+  T r = T{};
+  if (live && t < G.bs) {
+    const int row = vanka_unknown(G, c1, c2, c3, t);
+    if constexpr (ZERO) {
+      r = b[(size_t)row * (size_t)k + (size_t)c];
+    } else {
+      T acc = T{};
+      for (int e = rowptr[row], end = rowptr[row + 1]; e < end; ++e)
+        acc += vk_mul(val[e], x[(size_t)col[e] * (size_t)k + (size_t)c]);   // stored order, one lane
+      r = b[(size_t)row * (size_t)k + (size_t)c] - acc;
+    }
+  }
+  T out = T{};
+  const typename VankaBlk<T>::type* Mrow = D + (size_t)cell * (size_t)(G.bs * G.bs) + (size_t)(t < G.bs ? t : 0) * (size_t)G.bs;
+  for (int j = 0; j < G.bs; ++j) {
+    const T rj = vk_shfl8(r, j);
+    if (live && t < G.bs) out += vk_mul(vk_adj<T>(Mrow[j]), rj);
+  }
+  if (live && t < G.bs) delta[((size_t)cell * (size_t)G.bs + (size_t)t) * (size_t)k + (size_t)c] = out;
+}
+
+// x[I][c] += delta[cell][.][c] for the cells of one colour
+template <typename T>
+__global__ __launch_bounds__(BLK) void vanka_apply_colour_blk(VankaGeo G, const T* __restrict__ delta, T* __restrict__ x, int k, int count,
+                                                              int m1, int m2, int p1, int p2, int p3) {
+  const long long gid = (long long)blockIdx.x * BLK + threadIdx.x;
+  const int t = (int)(gid & 7);
+  const long long grp = gid >> 3;
+  if (grp >= (long long)count * k || t >= G.bs) return;
+  const int g = (int)(grp / k), c = (int)(grp % k), q = g / m1;
+  const int c1 = 2 * (g % m1) + p1, c2 = 2 * (q % m2) + p2, c3 = 2 * (q / m2) + p3;
+  const int cell = c1 + G.n[0] * (c2 + G.n[1] * c3);
+  const size_t u = (size_t)vanka_unknown(G, c1, c2, c3, t) * (size_t)k + (size_t)c;
+  x[u] = x[u] + delta[((size_t)cell * (size_t)G.bs + (size_t)t) * (size_t)k + (size_t)c];
+}
+
+// FULL_VANKA_ADD on a block: one lane per (unknown, column), the lower cell's delta first
+template <typename T>
+__global__ __launch_bounds__(BLK) void vanka_apply_add_blk(VankaGeo G, const T* __restrict__ delta, T* __restrict__ x, int k) {
+  const long long gid = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (gid >= (long long)G.N * k) return;   // (compared before narrowing)
+  const int u = (int)(gid / k), c = (int)(gid % k);
+  const int n1 = G.n[0], n2 = G.n[1], n3 = G.n[2];
+  int lo = -1, hi = -1, tlo = 0, thi = 0;   // cells and the unknown's slot in each
+  if (u < G.nf[0]) {
+    const int f = u % (n1 + 1), rest = u / (n1 + 1);   // rest = c2 + n2 * c3
+    if (f >= 1) { lo = (f - 1) + n1 * rest; tlo = 1; }
+    if (f < n1) { hi = f + n1 * rest; thi = 0; }
+  } else if (u < G.nf[0] + G.nf[1]) {
+    const int v = u - G.nf[0];
+    const int c1 = v % n1, f = (v / n1) % (n2 + 1), c3 = v / (n1 * (n2 + 1));
+    if (f >= 1) { lo = c1 + n1 * ((f - 1) + n2 * c3); tlo = 3; }
+    if (f < n2) { hi = c1 + n1 * (f + n2 * c3); thi = 2; }
+  } else if (u < G.nf[0] + G.nf[1] + G.nf[2]) {
+    const int v = u - G.nf[0] - G.nf[1];
+    const int inplane = v % (n1 * n2), f = v / (n1 * n2);
+    if (f >= 1) { lo = inplane + n1 * n2 * (f - 1); tlo = 5; }
+    if (f < n3) { hi = inplane + n1 * n2 * f; thi = 4; }
+  } else {
+    lo = u - G.nf[0] - G.nf[1] - G.nf[2];
+    tlo = G.bs - 1;
+  }
+  T v = x[(size_t)gid];
+  if (lo >= 0) v = v + delta[((size_t)lo * (size_t)G.bs + (size_t)tlo) * (size_t)k + (size_t)c];
+  if (hi >= 0) v = v + delta[((size_t)hi * (size_t)G.bs + (size_t)thi) * (size_t)k + (size_t)c];
+  x[(size_t)gid] = v;
 }
 
 }  // namespace mgk

@@ -14,9 +14,11 @@ struct VankaCore {
   bool single = false;     // cx only: the operator and the vectors hold float pairs (a level of a CF32 handle)
   DevBuf<float> D;         // LocalBlocks: bs*bs single-precision values per cell (complex: interleaved pairs)
   DevBuf<double> delta;    // cells x bs values of the operator's type (single: two of them per double slot)
+  DevBuf<double> bdelta;   // the same for a block of bk columns: cells x bs x bk (vanka_block_ensure; empty until a block arrives)
+  int bk = 0;
   long long launches = 0;  // kernels enqueued so far
   int colours_live = 0;    // colours that hold a cell (n[d] = 1 leaves the even parity of d empty)
-  void release() { D.release(); delta.release(); }
+  void release() { D.release(); delta.release(); bdelta.release(); bk = 0; }
 };
 
 // (dim, n, includePressure) -> geometry; nrows must be sum(nf) [+ prod(n)] (getVankaBlockSize, Vanka.jl:211-222)
@@ -124,6 +126,78 @@ int vanka_run(VankaCore* V, const int* rowptr, const int* col, const double* val
   return vanka_sweeps<double>(V, rowptr, col, val, b, x, numit, type, stream);
 }
 
+// The delta buffer of the block passes for k columns: grown when a larger k arrives (the caller has waited for the stream that may
+// still read the old one), kept with the core.  A complex level's grows with the handle's block work set (cx_block_ensure).
+int vanka_block_ensure(VankaCore* V, int k) {
+  if (k <= V->bk) return MG_OK;
+  V->bk = 0;
+  MG_TRY(V->bdelta.alloc((V->single || !V->cx ? 1 : 2) * (size_t)V->G.bs * (size_t)V->G.cells * (size_t)k));
+  V->bk = k;
+  return MG_OK;
+}
+
+// vanka_sweeps on a row-major block [N][k] (kernels: the _blk forms of mg_vanka.hpp): the same launches in the same order, each serving
+// all k columns.  ZERO is a property of the whole block.
+template <typename T, bool ZERO = false>
+int vanka_sweeps_blk(VankaCore* V, const int* rowptr, const int* col, const T* val, const T* b, T* x, int k, long long numit, int type,
+                     hipStream_t stream) {
+  typedef typename mgk::VankaBlk<T>::type B;
+  const mgk::VankaGeo& G = V->G;
+  if (k < 1 || k > mgk::BLK_KMAX) return fail(MG_ERR_INVALID, "internal: a Vanka block of %d columns", k);
+  if (V->bk < k) return fail(MG_ERR_STATE, "internal: the Vanka delta buffer holds %d columns, the block %d", V->bk, k);
+  const B* D = reinterpret_cast<const B*>(V->D.p);
+  T* delta = reinterpret_cast<T*>(V->bdelta.p);
+  if (numit <= 0) return MG_OK;
+  // lanes of the largest launch, in 64 bits: all cells (or all unknowns) times k
+  const long long most = std::max((long long)G.cells * 8, (long long)G.N) * k;
+  if ((most + mgk::BLK - 1) / mgk::BLK >= (1LL << 31)) return fail(MG_ERR_UNSUPPORTED, "the mesh times %d columns exceeds the launch grid", k);
+  auto blocks = [k](long long groups) { return dim3((unsigned)((groups * 8 * k + mgk::BLK - 1) / mgk::BLK)); };
+  if (type == VANKA_FULL_ADD) {
+    hipLaunchKernelGGL((mgk::vanka_delta_blk<T, ZERO>), blocks(G.cells), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, k,
+                       G.cells, G.n[0], G.n[1], 0, 0, 0, 1);
+    ++V->launches;
+    for (long long it = 0; it < numit; ++it) {
+      hipLaunchKernelGGL(mgk::vanka_apply_add_blk<T>, dim3((unsigned)(((long long)G.N * k + mgk::BLK - 1) / mgk::BLK)), dim3(mgk::BLK), 0, stream,
+                         G, delta, x, k);
+      ++V->launches;
+    }
+    HIP_TRY(hipGetLastError());
+    return MG_OK;
+  }
+  const int ncol = 1 << G.dim;
+  bool from_zero = ZERO;   // until the first colour has been applied
+  for (long long it = 0; it < numit; ++it)
+    for (int c = 0; c < ncol; ++c) {
+      int p[3] = {0, 0, 0}, m[3] = {1, 1, 1};   // cellColor, as vanka_sweeps
+      for (int d = 0; d < G.dim; ++d) {
+        p[d] = (c >> (G.dim - 1 - d)) & 1;
+        m[d] = (G.n[d] + 1 - p[d]) / 2;
+      }
+      const long long count = (long long)m[0] * m[1] * m[2];
+      if (count == 0) continue;
+      if (ZERO && from_zero)
+        hipLaunchKernelGGL((mgk::vanka_delta_blk<T, ZERO>), blocks(count), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, k,
+                           (int)count, m[0], m[1], p[0], p[1], p[2], 0);
+      else
+        hipLaunchKernelGGL((mgk::vanka_delta_blk<T, false>), blocks(count), dim3(mgk::BLK), 0, stream, G, rowptr, col, val, D, b, x, delta, k,
+                           (int)count, m[0], m[1], p[0], p[1], p[2], 0);
+      from_zero = false;
+      hipLaunchKernelGGL(mgk::vanka_apply_colour_blk<T>, blocks(count), dim3(mgk::BLK), 0, stream, G, delta, x, k, (int)count, m[0], m[1],
+                         p[0], p[1], p[2]);
+      V->launches += 2;
+    }
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+int vanka_run_blk(VankaCore* V, const int* rowptr, const int* col, const double* val, const double* b, double* x, int k, long long numit,
+                  int type, hipStream_t stream) {
+  if (V->cx)
+    return vanka_sweeps_blk<mgk::d2_t>(V, rowptr, col, reinterpret_cast<const mgk::d2_t*>(val), reinterpret_cast<const mgk::d2_t*>(b),
+                                       reinterpret_cast<mgk::d2_t*>(x), k, numit, type, stream);
+  return vanka_sweeps_blk<double>(V, rowptr, col, val, b, x, k, numit, type, stream);
+}
+
 // The same on a level of a complex hierarchy: C = mgk::d2_t (a CF64 handle) or mgk::f2_t (a CF32 handle, V->single).  xzero: the caller
 // has zero-filled x (a level entered from zero): the from-zero pass opens the call.
 template <typename C>
@@ -134,6 +208,15 @@ int vanka_run_cx(VankaCore* V, const int* rowptr, const int* col, const C* val, 
   return vanka_sweeps<C, false>(V, rowptr, col, val, b, x, numit, type, stream);
 }
 
+// vanka_run_cx on a row-major block of k columns (the block cycle of a complex handle, option vanka_blocks)
+template <typename C>
+int vanka_run_cx_blk(VankaCore* V, const int* rowptr, const int* col, const C* val, const C* b, C* x, int k, long long numit, int type,
+                     bool xzero, hipStream_t stream) {
+  if (!V->cx || V->single != (sizeof(C) == sizeof(mgk::f2_t))) return fail(MG_ERR_INVALID, "internal: Vanka blocks and vectors differ in type");
+  if (xzero) return vanka_sweeps_blk<C, true>(V, rowptr, col, val, b, x, k, numit, type, stream);
+  return vanka_sweeps_blk<C, false>(V, rowptr, col, val, b, x, k, numit, type, stream);
+}
+
 }  // namespace
 
 struct mg_vanka {
@@ -142,6 +225,7 @@ struct mg_vanka {
   VankaCore core;
   DevBuf<int> rowptr, col;
   DevBuf<double> val, stage_x, stage_b;
+  DevBuf<double> bstage_x, bstage_b;   // the block entries' row-major blocks (host forms)
   hipStream_t stream = nullptr;
 };
 
@@ -234,6 +318,56 @@ int vanka_apply_host(bool cx, mg_vanka* v, double* x, const double* b, long long
   return MG_OK;
 }
 
+// ---- blocks of right-hand sides on the stand-alone handle (mg_vanka_apply_block_*) -------------------------------------------------
+int vanka_block_args(bool cx, mg_vanka* v, const double* x, const double* b, long long nrhs, long long numit, long long type, const char* name) {
+  if (!v) return fail(MG_ERR_INVALID, "null handle");
+  if (nrhs < 1) return fail(MG_ERR_INVALID, "nrhs=%lld: a block holds at least one right-hand side", nrhs);
+  if (nrhs > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "Vanka blocks hold at most %d right-hand sides (nrhs=%lld)", mgk::BLK_KMAX, nrhs);
+  MG_TRY(vanka_args(cx, v, x, b, numit, type, name));
+  if (v->core.bk < (int)nrhs) {
+    HIP_TRY(spin_sync(v->stream));   // (an earlier block call may still read the buffer replaced below)
+    MG_TRY(vanka_block_ensure(&v->core, (int)nrhs));
+  }
+  return MG_OK;
+}
+
+int vanka_apply_block_dev(bool cx, mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long numit, long long type,
+                          const char* name) {
+  MG_TRY(vanka_block_args(cx, v, x_dev, b_dev, nrhs, numit, type, name));
+  MG_TRY(vanka_run_blk(&v->core, v->rowptr.p, v->col.p, v->val.p, b_dev, x_dev, (int)nrhs, numit, (int)type, v->stream));
+  HIP_TRY(spin_sync(v->stream));
+  return MG_OK;
+}
+
+// x, b: column-major N x nrhs on the host; relaid to row-major on the host (a stand-alone entry: nothing of it is on a hot path)
+int vanka_apply_block_host(bool cx, mg_vanka* v, double* x, const double* b, long long nrhs, long long numit, long long type,
+                           const char* name) {
+  MG_TRY(vanka_block_args(cx, v, x, b, nrhs, numit, type, name));
+  if (numit == 0) return MG_OK;
+  const size_t vw = cx ? 2 : 1, n = (size_t)v->n, k = (size_t)nrhs, len = vw * n * k;   // doubles
+  if (v->bstage_x.n < len) {
+    HIP_TRY(spin_sync(v->stream));
+    MG_TRY(v->bstage_x.alloc(len));
+    MG_TRY(v->bstage_b.alloc(len));
+  }
+  std::vector<double> rx(len), rb(len);
+  for (size_t c = 0; c < k; ++c)
+    for (size_t i = 0; i < n; ++i)
+      for (size_t w = 0; w < vw; ++w) {
+        rx[(i * k + c) * vw + w] = x[(c * n + i) * vw + w];
+        rb[(i * k + c) * vw + w] = b[(c * n + i) * vw + w];
+      }
+  HIP_TRY(hipMemcpyAsync(v->bstage_x.p, rx.data(), len * sizeof(double), hipMemcpyHostToDevice, v->stream));
+  HIP_TRY(hipMemcpyAsync(v->bstage_b.p, rb.data(), len * sizeof(double), hipMemcpyHostToDevice, v->stream));
+  MG_TRY(vanka_run_blk(&v->core, v->rowptr.p, v->col.p, v->val.p, v->bstage_b.p, v->bstage_x.p, (int)nrhs, numit, (int)type, v->stream));
+  HIP_TRY(hipMemcpyAsync(rx.data(), v->bstage_x.p, len * sizeof(double), hipMemcpyDeviceToHost, v->stream));
+  HIP_TRY(spin_sync(v->stream));
+  for (size_t c = 0; c < k; ++c)
+    for (size_t i = 0; i < n; ++i)
+      for (size_t w = 0; w < vw; ++w) x[(c * n + i) * vw + w] = rx[(i * k + c) * vw + w];
+  return MG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -261,6 +395,44 @@ int mg_vanka_apply_dev_FP64(mg_vanka* v, double* x_dev, const double* b_dev, lon
 }
 int mg_vanka_apply_dev_CFP64(mg_vanka* v, double* x_dev, const double* b_dev, long long numit, long long VankaType) {
   return vanka_apply_dev(true, v, x_dev, b_dev, numit, VankaType, "mg_vanka_apply_dev_CFP64");
+}
+
+// The same on a block of nrhs right-hand sides (1..16; kernels: the _blk forms of mg_vanka.hpp).  Host forms: x, b column-major
+// N x nrhs; _dev forms: row-major [N][nrhs] device blocks.  Column c holds the bits mg_vanka_apply_* gives on column c alone.
+int mg_vanka_apply_block_FP64(mg_vanka* v, double* x, const double* b, long long nrhs, long long numit, long long VankaType) {
+  return vanka_apply_block_host(false, v, x, b, nrhs, numit, VankaType, "mg_vanka_apply_block_FP64");
+}
+int mg_vanka_apply_block_CFP64(mg_vanka* v, double* x, const double* b, long long nrhs, long long numit, long long VankaType) {
+  return vanka_apply_block_host(true, v, x, b, nrhs, numit, VankaType, "mg_vanka_apply_block_CFP64");
+}
+int mg_vanka_apply_block_dev_FP64(mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long numit, long long VankaType) {
+  return vanka_apply_block_dev(false, v, x_dev, b_dev, nrhs, numit, VankaType, "mg_vanka_apply_block_dev_FP64");
+}
+int mg_vanka_apply_block_dev_CFP64(mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long numit, long long VankaType) {
+  return vanka_apply_block_dev(true, v, x_dev, b_dev, nrhs, numit, VankaType, "mg_vanka_apply_block_dev_CFP64");
+}
+
+// Measurement: mg_vanka_time_dev on a row-major device block of nrhs columns
+int mg_vanka_time_block_dev(mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long VankaType, long long warmup,
+                            long long reps, double* ms) {
+  if (!v || !ms || reps < 1 || warmup < 0) return fail(MG_ERR_INVALID, "bad argument");
+  MG_TRY(vanka_block_args(v->core.cx, v, x_dev, b_dev, nrhs, 1, VankaType, "mg_vanka_time_block_dev"));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = MG_OK;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventCreate failed");
+  for (long long it = 0; it < warmup + reps && rc == MG_OK; ++it) {
+    if (hipEventRecord(e0, v->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
+    if (rc == MG_OK) rc = vanka_run_blk(&v->core, v->rowptr.p, v->col.p, v->val.p, b_dev, x_dev, (int)nrhs, 1, (int)VankaType, v->stream);
+    if (rc == MG_OK) {
+      float t = 0.f;
+      if (hipEventRecord(e1, v->stream) != hipSuccess || spin_sync(v->stream) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)
+        rc = fail(MG_ERR_HIP, "event timing failed");
+      if (it >= warmup) ms[it - warmup] = (double)t;
+    }
+  }
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
 }
 
 // info[0..8): value type (0 Float64, 1 ComplexF64); blockSize; cells; colours (2^dim); kernel launches of one
@@ -312,7 +484,7 @@ int mg_vanka_destroy(mg_vanka* v) {
   v->core.release();
   v->rowptr.release();
   v->col.release();
-  for (DevBuf<double>* b : {&v->val, &v->stage_x, &v->stage_b}) b->release();
+  for (DevBuf<double>* b : {&v->val, &v->stage_x, &v->stage_b, &v->bstage_x, &v->bstage_b}) b->release();
   delete v;
   return MG_OK;
 }

@@ -159,6 +159,11 @@ SIGNATURES = {
     "mg_vanka_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
     "mg_vanka_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll]),
     "mg_vanka_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_vanka_apply_block_FP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_vanka_apply_block_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_vanka_apply_block_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_vanka_apply_block_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_vanka_time_block_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _dp]),
     "mg_vanka_info": (C.c_int, [_vp, _lp]),
     "mg_vanka_time_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _dp]),
     "mg_vanka_destroy": (C.c_int, [_vp]),
@@ -329,6 +334,7 @@ def _sync_torch(*tensors):
 
 
 DENSE_COARSE_MAX = 16384
+BLOCK_KMAX = 16                  # columns of a complex block of right-hand sides (mgk::BLK_KMAX)
 
 
 def _relax_type_code(param) -> int:
@@ -940,7 +946,7 @@ def _c128(a):
 
 class ComplexDeviceHierarchy(DeviceHierarchy):
     """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F / K cycles, Jac / SPAI / Jac-GMRES relaxation
-    or (a param with ``complexVanka=True``) the Vanka cell-block smoothers, one right-hand side only,
+    or (a param with ``complexVanka=True``) the Vanka cell-block smoothers (blocks only for a param with ``vankaBlocks=True``),
     dense-inverse, sparse-LU or GMRES coarsest solve (the last adds one host synchronisation per coarsest solve and serves blocks only for a param with ``blockCoarseGMRES=True``: ``block_coarse_gmres``).  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
     methods, which take the column count with each call (not on a K-cycle / Jac-GMRES hierarchy).  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
@@ -1027,6 +1033,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         self._block_coarse_gmres = bool(getattr(param, "blockCoarseGMRES", False))
         if self._block_coarse_gmres:      # blocks on the GMRES coarsest solve: the block form of that solve (opt-in, read at every call)
             _check(lib, lib.mg_set_option(self.handle, b"coarse_gmres_blocks", 1.0), "mg_set_option(coarse_gmres_blocks)")
+        self._vanka_blocks = self._vanka and bool(getattr(param, "vankaBlocks", False))
+        if self._vanka_blocks:            # blocks on a Vanka hierarchy: the block form of the smoother (opt-in, read at every call)
+            _check(lib, lib.mg_set_option(self.handle, b"vanka_blocks", 1.0), "mg_set_option(vanka_blocks)")
         self._set_coarse(param)
         _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
         self._schedule = self._schedule_of(param)
@@ -1055,7 +1064,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
                                       "(solve the columns one after the other)")
 
     def _vanka_block_guard(self):
-        if getattr(self, "_vanka", False):
+        """Blocks on a complex Vanka hierarchy run where the param asked for them (``vankaBlocks=True``: the handle's option
+        vanka_blocks) and are refused otherwise."""
+        if getattr(self, "_vanka", False) and not getattr(self, "_vanka_blocks", False):
             raise NotImplementedError("blocks of right-hand sides are not served on a complex Vanka hierarchy (out of scope)")
 
     def _block_coarse_guard(self, k: int):

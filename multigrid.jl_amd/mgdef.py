@@ -48,6 +48,7 @@ class MGparam:
     singlePrecision: bool = False
     blockCoarseGMRES: bool = False     # coarseSolveType "GMRES" on a complex hierarchy: serve blocks by the block GMRES coarsest solve
     complexVanka: bool = False         # a Vanka relaxType on a complex hierarchy: the cell-block smoother in the complex cycle
+    vankaBlocks: bool = False          # complexVanka only: serve blocks of right-hand sides by the block form of the smoother
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -60,7 +61,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                relaxType="SPAI", relaxParam=1.0, relaxPre=2, relaxPost=2, cycleType="V",
                coarseSolveType="NoMUMPS", strongConnParam=0.4, FilteringParam=0.0,
                transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
-               blockCoarseGMRES: bool = False, complexVanka: bool = False) -> MGparam:
+               blockCoarseGMRES: bool = False, complexVanka: bool = False, vankaBlocks: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -76,6 +77,9 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     lets ``MGsetup`` build the complex Vanka hierarchy of the reference (Systems transfers, complex64 blocks per level) and the
     device run it: ComplexF64 with cycles V / W / F / K, ``singlePrecision`` with V / W / F, one right-hand side.  Without it a
     complex Vanka param is refused by ``MGsetup``, as before.
+    ``vankaBlocks=True`` (keyword only, with ``complexVanka=True``) switches on the block form of that smoother: blocks of up to 16
+    right-hand sides are then served on the hierarchy for the cycles V / W / F (solveMG, recursiveCycle, getMultigridPreconditioner,
+    the block _CFP64 drivers, the device's ``block_*`` methods); without it they are refused, as before.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
@@ -88,6 +92,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
         from .vanka import getVankaRelaxType
         if np.dtype(VAL) != np.complex128 or not getVankaRelaxType(str(relaxType))[0]:
             raise NotImplementedError("complexVanka=True serves VAL=ComplexF64 (singlePrecision or not) with a Vanka relaxType")
+    if vankaBlocks and not complexVanka:
+        raise NotImplementedError("vankaBlocks=True serves a complex Vanka hierarchy (complexVanka=True)")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -101,7 +107,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    relaxPre=pre, relaxPost=post, cycleType=cycleType, coarseSolveType=str(coarseSolveType),
                    strongConnParam=float(strongConnParam), FilteringParam=float(FilteringParam),
                    transferOperatorType=str(transferOperatorType), singlePrecision=bool(singlePrecision),
-                   blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka), VAL=np.dtype(VAL).type, IND=np.int64)
+                   blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka),
+                   vankaBlocks=bool(vankaBlocks), VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -173,7 +180,8 @@ def copySolver(MG: MGparam) -> MGparam:
     new = getMGparam(np.complex128 if single else MG.VAL, MG.IND, MG.levels, MG.numCores, MG.maxOuterIter, MG.relativeTol,
                      MG.relaxType, MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
                      MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single,
-                     blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka))
+                     blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka),
+                     vankaBlocks=bool(MG.vankaBlocks))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

@@ -42,12 +42,26 @@ def _coarse_gmres_guard(param: MGparam, b) -> None:
 
 
 def _vanka_block_guard(param: MGparam, b) -> None:
-    """A complex Vanka hierarchy given more than one column: blocks of right-hand sides with Vanka are out of scope, refused before
-    the device is touched (a real one is refused by ``_vanka_guard`` through the handle's nrhs)."""
+    """A complex Vanka hierarchy given more than one column: refused before the device is touched (a real one is refused by
+    ``_vanka_guard`` through the handle's nrhs) unless the param asked for the block form of the smoother
+    (``getMGparam(..., complexVanka=True, vankaBlocks=True)``)."""
     from .mgsetup import _is_vanka
-    if _complex_block(param, b) and _is_vanka(param):
+    if not (_complex_block(param, b) and _is_vanka(param)):
+        return
+    if not getattr(param, "vankaBlocks", False):
         raise NotImplementedError("blocks of right-hand sides are not served on a complex Vanka hierarchy (solve the columns one "
                                   "after the other)")
+    # vankaBlocks=True: the block form of the smoother serves the block; what it does not serve is refused here, before the device
+    from .device import BLOCK_KMAX
+    from .mgdef import _solver_object
+    if _ncols(b) > BLOCK_KMAX:
+        raise NotImplementedError(f"complex Vanka hierarchies serve blocks of at most {BLOCK_KMAX} right-hand sides ({_ncols(b)} given)")
+    if np.asarray(b).dtype.kind != "c":
+        raise NotImplementedError("a real block on a complex Vanka hierarchy is not served (blocks of a complex hierarchy are complex128)")
+    if param.cycleType == "K":
+        raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle complex Vanka hierarchy")
+    if _solver_object(param.LU) == "dd":
+        raise NotImplementedError("complex Vanka hierarchies: a Schwarz coarsest solve is out of scope")
 
 
 def _width(param: MGparam, b) -> int:

@@ -227,6 +227,31 @@ class VankaHandle:
     def info(self):
         return vanka_info(self.h)
 
+    def apply_dev(self, x, b, numit: int, VankaType: int = FULL_VANKA_RB):
+        """``numit`` iterations on torch device tensors, x in place, waited for: 1-D vectors (mg_vanka_apply_dev_*) or contiguous
+        row-major blocks [N, k], 1 <= k <= 16 (mg_vanka_apply_block_dev_*); float64 for a real handle, complex128 for a complex one."""
+        import torch
+        want = torch.complex128 if self.cx else torch.float64
+        for t in (x, b):
+            if not (hasattr(t, "dtype") and hasattr(t, "data_ptr")) or t.dtype != want:
+                raise TypeError(f"expected {want} device tensors")
+            if t.dim() not in (1, 2) or not t.is_contiguous() or t.shape[0] != self.N:
+                raise ValueError(f"device vectors hold {self.N} values, device blocks are contiguous [{self.N}, k] tensors")
+        if tuple(x.shape) != tuple(b.shape):
+            raise ValueError("x and b must have the same shape")
+        lib = D.load_library()
+        D._sync_torch(x, b)
+        sfx = "CFP64" if self.cx else "FP64"
+        if x.dim() == 1:
+            D._check(lib, getattr(lib, f"mg_vanka_apply_dev_{sfx}")(self.h, D._ptr(x), D._ptr(b), int(numit), int(VankaType)),
+                     "mg_vanka_apply_dev")
+        else:
+            if not 1 <= int(x.shape[1]) <= D.BLOCK_KMAX:
+                raise NotImplementedError(f"a Vanka block holds 1 to {D.BLOCK_KMAX} right-hand sides ({int(x.shape[1])} given)")
+            D._check(lib, getattr(lib, f"mg_vanka_apply_block_dev_{sfx}")(self.h, D._ptr(x), D._ptr(b), int(x.shape[1]), int(numit),
+                                                                         int(VankaType)), "mg_vanka_apply_block_dev")
+        return x
+
     def close(self):
         if getattr(self, "h", None):
             D.load_library().mg_vanka_destroy(self.h)
@@ -272,7 +297,10 @@ def RelaxVankaFacesColor(AT, x, b, Dblk, numit: int, numCores: int, M, includePr
     these blocks and this mesh - then nothing is uploaded.
 
     FULL_VANKA_RB / ECON_VANKA_RB: per iteration 2^dim coloured passes, each from a snapshot of x.  FULL_VANKA_ADD: the
-    corrections are formed once per call from the incoming x and added numit times (l.396-405).  numit = 0 does nothing."""
+    corrections are formed once per call from the incoming x and added numit times (l.396-405).  numit = 0 does nothing.
+
+    A 2-D ``x`` and ``b`` (N x k, 1 <= k <= 16, not in the reference) are relaxed as a block by one pass over the operator and the
+    blocks (mg_vanka_apply_block_*): column c gets the bits of the call on column c alone."""
     x_arr = np.asarray(x)
     b_arr = np.asarray(b)
     cx = np.iscomplexobj(AT.data if sp.issparse(AT) else AT)
@@ -292,13 +320,19 @@ def RelaxVankaFacesColor(AT, x, b, Dblk, numit: int, numCores: int, M, includePr
     n = _mesh_n(M)
     blockSize, nf = getVankaBlockSize(n, includePressure)
     N = int(nf.sum()) + (int(np.prod(n)) if includePressure else 0)
-    if x_arr.ndim != 1 or b_arr.ndim != 1 or x_arr.shape[0] != N or b_arr.shape[0] != N:
+    block = x_arr.ndim == 2 and b_arr.ndim == 2
+    if block:
+        if x_arr.shape != b_arr.shape or x_arr.shape[0] != N:
+            raise ValueError(f"blocks x and b must both be {N} x k for a mesh of {n.tolist()} cells")
+        if not 1 <= x_arr.shape[1] <= D.BLOCK_KMAX:
+            raise NotImplementedError(f"a Vanka block holds 1 to {D.BLOCK_KMAX} right-hand sides ({x_arr.shape[1]} given)")
+    elif x_arr.ndim != 1 or b_arr.ndim != 1 or x_arr.shape[0] != N or b_arr.shape[0] != N:
         raise ValueError(f"x and b must be vectors of sum(nf) [+ prod(n)] = {N} values for a mesh of {n.tolist()} cells")
     if Dblk.shape != (blockSize * blockSize, int(np.prod(n))):
         raise ValueError(f"D must be {(blockSize * blockSize, int(np.prod(n)))}, got {Dblk.shape}")
     if AT.shape != (N, N):
         raise ValueError(f"the operator is {AT.shape}, expected {(N, N)}")
-    if not (isinstance(x, np.ndarray) and x.flags.c_contiguous and x.flags.writeable):
+    if not (isinstance(x, np.ndarray) and (x.flags.c_contiguous or (block and x.flags.f_contiguous)) and x.flags.writeable):
         raise ValueError("x must be a contiguous writable array (it is relaxed in place)")
     if int(numit) < 0:
         raise ValueError("numit must be >= 0")
@@ -308,9 +342,17 @@ def RelaxVankaFacesColor(AT, x, b, Dblk, numit: int, numCores: int, M, includePr
     H = VankaHandle(AT, Dblk, n, includePressure) if own else handle
     try:
         lib = D.load_library()
-        bb = np.ascontiguousarray(b_arr)
-        apply = lib.mg_vanka_apply_CFP64 if cx else lib.mg_vanka_apply_FP64
-        D._check(lib, apply(H.h, D._f64(x), D._f64(bb), int(numit), int(VankaType)), "mg_vanka_apply")
+        if block:                       # the host entry takes column-major N x k
+            xf = np.asfortranarray(x)
+            bf = np.asfortranarray(b_arr)
+            apply = lib.mg_vanka_apply_block_CFP64 if cx else lib.mg_vanka_apply_block_FP64
+            D._check(lib, apply(H.h, D._f64(xf), D._f64(bf), int(x.shape[1]), int(numit), int(VankaType)), "mg_vanka_apply_block")
+            if not np.shares_memory(xf, x):
+                x[...] = xf
+        else:
+            bb = np.ascontiguousarray(b_arr)
+            apply = lib.mg_vanka_apply_CFP64 if cx else lib.mg_vanka_apply_FP64
+            D._check(lib, apply(H.h, D._f64(x), D._f64(bb), int(numit), int(VankaType)), "mg_vanka_apply")
     finally:
         if own:
             H.close()
