@@ -635,6 +635,32 @@ int mg_vanka_time_dev(mg_vanka* v, double* x_dev, const double* b_dev, long long
                       double* ms);
 int mg_vanka_time_block_dev(mg_vanka* v, double* x_dev, const double* b_dev, long long nrhs, long long VankaType, long long warmup,
                             long long reps, double* ms);   /* the same on a row-major device block of nrhs columns */
+/* THE BLOCKS BUILT ON THE DEVICE (setupVankaFacesPreconditioner, Vanka.jl:294-370, from the handle's resident operator; kernel
+ * vanka_build_blocks, csrc/mg_vanka.hpp: one launch, eight lanes per cell, Gauss-Jordan with partial pivoting in double, the result in
+ * single in the LocalBlocks layout; the same bits on every run).  w[nw]: nw = 1 a scalar w, nw = 2 the pair (w0, w1) - w1 damps the
+ * pressure row.  VankaType 1 with a scalar replaces the leading (bs-1)x(bs-1) part of each block by its diagonal and scales the inverse
+ * by w; 1 with a pair scales the rows of the full inverse; 3 (scalar only: nw = 2 is MG_ERR_INVALID) divides that diagonal by w; 5
+ * scales row t by t_t * W_t, t_t = 1/2 on a face shared with a neighbouring cell.  Types 2 and 4 and unknown ones: MG_ERR_UNSUPPORTED.
+ * All of these are answered before the first write.  A cell whose elimination meets a pivot of squared modulus zero or not finite makes
+ * the call return MG_ERR_INVALID after the launch has been waited for; the message names the first such cell (1-based) and the handle
+ * keeps the blocks it had (the build writes a second buffer that replaces the first only on success).
+ *   mg_vanka_create_built_*   mg_vanka_create_* with (VankaType, w, nw) in the place of D_blocks; a singular cell: no handle.
+ *   mg_vanka_build_blocks_*   the handle's blocks again from its resident operator.
+ *   mg_vanka_replace_values_* new operator values (valA's convention, nnz of them) on the stored pattern; the blocks stay as they are.
+ *   mg_vanka_get_blocks       the blocks as mg_vanka_create_* takes them: count = bs*bs*prod(n) values (CFP64: pairs of floats).
+ *   mg_vanka_time_build       measurement: device time of `reps` builds after `warmup` untimed ones (the handle's blocks stay). */
+int mg_vanka_create_built_FP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure,
+                                     long long nrows, const long long* rowptr, const long long* colA, const double* valA,
+                                     long long VankaType, const double* w, long long nw, mg_vanka** out);
+int mg_vanka_create_built_CFP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure,
+                                      long long nrows, const long long* rowptr, const long long* colA, const double* valA,
+                                      long long VankaType, const double* w, long long nw, mg_vanka** out);
+int mg_vanka_build_blocks_FP64(mg_vanka* v, long long VankaType, const double* w, long long nw);
+int mg_vanka_build_blocks_CFP64(mg_vanka* v, long long VankaType, const double* w, long long nw);
+int mg_vanka_replace_values_FP64(mg_vanka* v, const double* nzval, long long nnz);
+int mg_vanka_replace_values_CFP64(mg_vanka* v, const double* nzval, long long nnz);
+int mg_vanka_get_blocks(mg_vanka* v, float* out, long long count);
+int mg_vanka_time_build(mg_vanka* v, long long VankaType, const double* w, long long nw, long long warmup, long long reps, double* ms);
 int mg_vanka_destroy(mg_vanka* v);
 
 /* ---- native multi-GPU sequencer (one process per GPU) ---------------------------------------------------------
@@ -1017,7 +1043,24 @@ mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r
  * each of them serves them today).  The smoother runs on the row-major block in place (the _blk kernels of mg_vanka.hpp); column c
  * holds the bits of the one-vector smoother on column c, the from-zero pass is decided for the whole block, and the delta buffer
  * (cells x bs x nrhs) grows with the block work set.  The K-cycle, nrhs > 16 and a Schwarz coarsest solve stay MG_ERR_UNSUPPORTED,
- * X untouched.  With 0 every return code and message is what it was before the option existed. */
+ * X untouched.  With 0 every return code and message is what it was before the option existed.
+ * DEVICE SET-UP OF THE BLOCKS, OPT-IN.  mg_build_vanka_CF64 / _CF32 are mg_set_vanka_* with (VankaType, w, nw) in the place of
+ * D_blocks: the checks are the same, the blocks are built in HBM from the level's resident operator (as mg_vanka_build_blocks_*
+ * above; a CF32 level's float pairs are widened, the elimination runs in double for both precisions; nw = 2 with type 3:
+ * MG_ERR_INVALID) and the level remembers (VankaType, w).  A singular cell: MG_ERR_INVALID, the level keeps what it had.
+ * mg_get_vanka_blocks_CF64 / _CF32 read a level's blocks back (count = bs*bs*prod(n) ComplexF32 values; no blocks: MG_ERR_STATE).
+ * mg_set_option(h, "vanka_device_setup", 1) (default 0; read at every call): mg_rap_CF64 then serves a CF64 handle in relaxation
+ * type 2 - new fine values, the numeric Galerkin products, and every relaxed level's blocks built again with that level's
+ * remembered (VankaType, w), each behind the product that feeds it; relaxKind and omega are validated and not used.  A level
+ * whose blocks came from mg_set_vanka_CF64 has nothing remembered: MG_ERR_STATE before the first write.  A singular cell on any
+ * level: MG_ERR_INVALID after the products (the operators hold the new values, every level keeps its previous blocks).  With 0
+ * mg_rap_CF64 refuses a Vanka handle with the code and message it always had; CF32 handles stay MG_ERR_UNSUPPORTED there. */
+mg_status mg_build_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
+                              long long VankaType, const double* w, long long nw);
+mg_status mg_build_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
+                              long long VankaType, const double* w, long long nw);
+mg_status mg_get_vanka_blocks_CF64(mg_hierarchy* h, long long level, float* out, long long count);
+mg_status mg_get_vanka_blocks_CF32(mg_hierarchy* h, long long level, float* out, long long count);
 mg_status mg_set_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
                             long long VankaType, const float* D_blocks);
 mg_status mg_set_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,

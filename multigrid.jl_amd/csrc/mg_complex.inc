@@ -1897,6 +1897,57 @@ int cx_set_vanka(mg_hierarchy* h, long long level, CxWant want, long long dim, c
   return MG_OK;
 }
 
+// mg_build_vanka_CF64 / _CF32: cx_set_vanka with the blocks built in HBM from the level's resident operator (vanka_build_blocks,
+// mg_vanka.hpp) for (VankaType, w[nw]), which the level remembers (mg_rap_CF64 with the option vanka_device_setup rebuilds from them).
+// A singular cell: MG_ERR_INVALID, and the level keeps what it had.
+int cx_build_vanka(mg_hierarchy* h, long long level, CxWant want, long long dim, const long long* n, long long includePressure,
+                   long long VankaType, const double* w, long long nw) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, level, want));
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  if (!L.A.set) return fail(MG_ERR_STATE, "As[%lld] was not set: upload the operator before its Vanka blocks", level);
+  if (L.A.wide) return fail(MG_ERR_UNSUPPORTED, "operators with 64-bit row pointers are not served by the Vanka smoother");
+  if (L.A.n_rows != L.A.n_cols) return fail(MG_ERR_INVALID, "As[%lld] is not square", level);
+  mgk::VankaBuild P;
+  MG_TRY(vanka_build_args(VankaType, w, nw, &P));
+  mgk::VankaGeo G;
+  MG_TRY(vanka_geometry(dim, n, includePressure, L.A.n_rows, &G));
+  (void)hipSetDevice(h->device);
+  const hipStream_t st = h->play->stream;
+  HIP_TRY(hipDeviceSynchronize());   // (the operator's upload ran on the NULL stream)
+  VankaCore* V = new VankaCore();
+  int bad = 0, first = 0;
+  int rc = vanka_core_alloc(V, true, G, h->cx->single);
+  if (rc == MG_OK) rc = vanka_build_launch(V, L.A.rowptr.p, L.A.colidx.p, L.A.vals(), P, st);
+  if (rc == MG_OK && spin_sync(st) != hipSuccess) rc = fail(MG_ERR_HIP, "mg_build_vanka: the build failed on the device");
+  if (rc == MG_OK) rc = vanka_build_finish(V, P, &bad, &first);
+  if (rc == MG_OK && bad) rc = vanka_singular(bad, first, "mg_build_vanka");
+  if (rc != MG_OK) {
+    V->release();
+    delete V;
+    return rc;
+  }
+  L.release_vanka();
+  L.vanka = V;
+  L.vanka_type = (int)VankaType;
+  h->cx->finalized = false;
+  return MG_OK;
+}
+
+// mg_get_vanka_blocks_CF64 / _CF32: the level's blocks as mg_set_vanka_* takes them, count = bs*bs*cells ComplexF32 values
+int cx_get_vanka_blocks(mg_hierarchy* h, long long level, CxWant want, float* out, long long count) {
+  MG_TRY(cx_level_ok(h, level, want));
+  if (!out) return fail(MG_ERR_INVALID, "null argument");
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  if (!L.vanka) return fail(MG_ERR_STATE, "level %lld has no Vanka blocks", level);
+  const long long have = (long long)L.vanka->G.bs * L.vanka->G.bs * L.vanka->G.cells;
+  if (count != have) return fail(MG_ERR_INVALID, "count=%lld: level %lld holds %lld block values", count, level, have);
+  (void)hipSetDevice(h->device);
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  HIP_TRY(hipMemcpy(out, L.vanka->D.p, vanka_block_floats(L.vanka) * sizeof(float), hipMemcpyDeviceToHost));
+  return MG_OK;
+}
+
 // mg_set_vanka_relax_CF64 / _CF32
 int cx_set_vanka_relax(mg_hierarchy* h, CxWant want, long long cycleType) {
   MG_TRY(cx_handle_ok(h, want));
@@ -1987,6 +2038,22 @@ int mg_set_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const lon
 int mg_set_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure, long long VankaType,
                       const float* D_blocks) {
   return cx_set_vanka(h, level, CX_WANT32, dim, n, includePressure, VankaType, D_blocks);
+}
+
+// The same with the blocks built on the device from the level's resident operator, and their readback: see include/mgvcycle.h
+int mg_build_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure, long long VankaType,
+                        const double* w, long long nw) {
+  return cx_build_vanka(h, level, CX_WANT64, dim, n, includePressure, VankaType, w, nw);
+}
+int mg_build_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure, long long VankaType,
+                        const double* w, long long nw) {
+  return cx_build_vanka(h, level, CX_WANT32, dim, n, includePressure, VankaType, w, nw);
+}
+int mg_get_vanka_blocks_CF64(mg_hierarchy* h, long long level, float* out, long long count) {
+  return cx_get_vanka_blocks(h, level, CX_WANT64, out, count);
+}
+int mg_get_vanka_blocks_CF32(mg_hierarchy* h, long long level, float* out, long long count) {
+  return cx_get_vanka_blocks(h, level, CX_WANT32, out, count);
 }
 
 // Relaxation type 2 with its cycle type, on a complex handle (the shared setters and mg_set_schedule_CF64 keep refusing type 2)
@@ -2328,9 +2395,16 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
   if (nnz != S.lev[0].A.nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored fine pattern (%lld)", nnz, S.lev[0].A.nnz);
   if (relaxKind != 0 && relaxKind != 1) return fail(MG_ERR_INVALID, "relaxKind must be 0 (Jac) or 1 (SPAI)");
-  if (h->relax_type == 2)
+  const bool vanka = h->relax_type == 2;
+  if (vanka && !h->opt.vanka_device_setup)
     return fail(MG_ERR_UNSUPPORTED, "mg_rap_CF64 recomputes Jac and SPAI relaxPrecs: the blocks of a Vanka handle are set up on the host");
   const int nl = (int)h->nlevels;
+  if (vanka)   // option vanka_device_setup: every relaxed level's blocks are built again with what mg_build_vanka_CF64 was given
+    for (int l = 0; l + 1 < nl; ++l) {
+      const CxLevel& L = S.lev[(size_t)l];
+      if (!L.vanka || !L.vanka->has_w)
+        return fail(MG_ERR_STATE, "level %d's Vanka blocks were bound by mg_set_vanka_CF64: no (VankaType, w) to build them again with (mg_build_vanka_CF64)", l + 1);
+    }
   for (int l = 0; l < nl; ++l) {
     const CxLevel& L = S.lev[(size_t)l];
     if (L.A.wide || (l + 1 < nl && (L.P.wide || L.R.wide)))
@@ -2353,7 +2427,9 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     const unsigned nb = cx_grid(L.n);
     const mgk::CxCsr32<cx_t> Ad = cx_csr32<cx_t>(L.A);
     HIP_TRY(hipEventRecord(S.rap_ev[(size_t)l], st));
-    if (relaxKind == 0) {
+    if (vanka) {   // the level's blocks from its new values, into the spare buffer (exchanged below, once nothing was found singular)
+      MG_TRY(vanka_build_launch(L.vanka, L.A.rowptr.p, L.A.colidx.p, L.A.vals(), L.vanka->built, st));
+    } else if (relaxKind == 0) {
       hipLaunchKernelGGL(mgk::cx_relax_jacobi, dim3(nb), dim3(mgk::BLK), 0, st, Ad, (int)L.n, omega[l], cxp(L.d));
     } else {   // the level's r as scratch for the column sums
       hipLaunchKernelGGL(mgk::cx_colsumsq, dim3(nb), dim3(mgk::BLK), 0, st, reinterpret_cast<const cx_t*>(L.A.val.p), L.A.t_ptr.p,
@@ -2378,6 +2454,21 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   HIP_TRY(hipEventRecord(S.rap_ev[(size_t)nl - 1], st));
   HIP_TRY(spin_sync(st));
   S.rap_timed = true;
+  if (vanka) {   // a singular cell anywhere: no level's blocks are exchanged (the operators hold the new values; the blocks the old ones)
+    int bad = 0, first = 0;
+    for (int l = 0; l + 1 < nl; ++l) {
+      VankaCore* V = S.lev[(size_t)l].vanka;
+      int flag[2] = {0, 0};
+      HIP_TRY(hipMemcpy(flag, V->flag.p, sizeof(flag), hipMemcpyDeviceToHost));
+      if (flag[0] != 0)
+        return fail(MG_ERR_INVALID, "mg_rap_CF64: level %d: cell %d of %d with a singular block: every level keeps its previous blocks", l + 1,
+                    INT_MAX - flag[1] + 1, flag[0]);
+    }
+    for (int l = 0; l + 1 < nl; ++l) {
+      VankaCore* V = S.lev[(size_t)l].vanka;
+      MG_TRY(vanka_build_finish(V, V->built, &bad, &first));
+    }
+  }
   if (levels_done) *levels_done = nl - 1;
   return MG_OK;
 }

@@ -154,6 +154,9 @@ bool host_all_zero(const double* x, long long len) {
   X(bool, vanka_blocks, false)             /* complex Vanka hierarchies (relaxation type 2): serve blocks of right-hand sides by the block \
                                               form of the smoother (the _blk kernels of mg_vanka.hpp); 0: a block on such a hierarchy is \
                                               refused; read at every call */ \
+  X(bool, vanka_device_setup, false)       /* complex Vanka hierarchies whose blocks were built on the device (mg_build_vanka_CF64): \
+                                              mg_rap_CF64 recomputes the operators and rebuilds the blocks in HBM; 0: it refuses a \
+                                              Vanka handle, as before the device build existed; read at every call */ \
   X(long long, lu_dense_tail_min, 64) \
   X(long long, lu_dense_tail_max, 16384)   /* largest trailing block kept as an explicit inverse (8*M^2 bytes each for L and U: 2 x 2.1 GB) */ \
   X(double, rowclass_min_cover, 0.9) \

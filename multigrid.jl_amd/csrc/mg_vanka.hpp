@@ -251,4 +251,151 @@ __global__ __launch_bounds__(BLK) void vanka_apply_add_blk(VankaGeo G, const T* 
   x[(size_t)gid] = v;
 }
 
+// ---- the cells' blocks built on the device: setupVankaFacesPreconditioner (Vanka.jl:294-370) from the resident operator -------------
+// vanka_build_blocks<T>: one launch per level, the eight-lane group of the apply kernels per cell.  Lane t owns row t of [Acc | I]:
+// it gathers Acc[t, :] = A[I_t, I] from its own CSR row (one compare of every stored column with the cell's bs unknowns; an absent
+// entry stays zero, of a repeated one the first counts), applies the variant's edit, and the group inverts by Gauss-Jordan with
+// partial pivoting: per column the largest squared modulus among the rows not yet used (three exchange steps inside the group, the
+// lowest row on ties), the rows exchanged, the pivot row scaled by the pivot's reciprocal and taken out of every other row.  Rows
+// travel between lanes by shuffles of registers that every loop below indexes with compile-time constants (the loops are unrolled to
+// VK_MAXBS and cut by the group-uniform bs): nothing is indexed dynamically, nothing goes to scratch or LDS.  All arithmetic is in
+// double (a float-pair operator is widened on load); the resident values are A's own (conjugated once at upload), i.e. what the host
+// function reads.  Lane t then scales its row of the inverse (scale_t below) and writes conj(Minv[t, j]) in single precision to entry
+// j + t*bs of the cell's column - the LocalBlocks layout, the cell's bs*bs values one contiguous run of the group's stores.
+// A pivot whose squared modulus is zero or not finite marks the cell: flag[0] counts such cells, flag[1] keeps INT_MAX - the lowest one (integer
+// atomics on a zero-filled pair), and the cell's block is not written.  No floating-point atomics: the same bits on every run.
+constexpr int VK_MAXBS = 7;
+
+struct VankaBuild {
+  int type;          // 1 FULL_VANKA_RB, 3 ECON_VANKA_RB, 5 FULL_VANKA_ADD
+  int scalar;        // w is one number (nw = 1): types 1 and 3 replace the leading (bs-1)x(bs-1) part of Acc by its diagonal
+  double w0, w1;     // W = w0 everywhere, w1 on the pressure row of a pair (scalar: w1 = w0)
+};
+
+template <typename T> struct VankaWide;   // the type the elimination runs in
+template <> struct VankaWide<double> { typedef double type; };
+template <> struct VankaWide<d2_t> { typedef d2_t type; };
+template <> struct VankaWide<f2_t> { typedef d2_t type; };
+__device__ __forceinline__ double vb_widen(double a) { return a; }
+__device__ __forceinline__ d2_t vb_widen(d2_t a) { return a; }
+__device__ __forceinline__ d2_t vb_widen(f2_t a) { return d2_t{(double)a.x, (double)a.y}; }
+__device__ __forceinline__ double vb_abs2(double a) { return a * a; }
+__device__ __forceinline__ double vb_abs2(d2_t a) { return a.x * a.x + a.y * a.y; }
+__device__ __forceinline__ double vb_recip(double p, double) { return 1.0 / p; }
+__device__ __forceinline__ d2_t vb_recip(d2_t p, double m2) { return d2_t{p.x / m2, -p.y / m2}; }
+__device__ __forceinline__ double vb_scale(double s, double a) { return s * a; }
+__device__ __forceinline__ d2_t vb_scale(double s, d2_t a) { return d2_t{s * a.x, s * a.y}; }
+__device__ __forceinline__ double vb_one(double) { return 1.0; }
+__device__ __forceinline__ d2_t vb_one(d2_t) { return d2_t{1.0, 0.0}; }
+__device__ __forceinline__ float vb_store(double a) { return (float)a; }
+__device__ __forceinline__ float2 vb_store(d2_t a) { return make_float2((float)a.x, -(float)a.y); }   // the stored block is the adjoint
+
+template <typename T>
+__global__ __launch_bounds__(BLK) void vanka_build_blocks(VankaGeo G, VankaBuild P, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                          const T* __restrict__ val, typename VankaBlk<T>::type* __restrict__ D,
+                                                          int* __restrict__ flag) {
+  typedef typename VankaWide<T>::type W;
+  const long long gid = (long long)blockIdx.x * BLK + threadIdx.x;
+  const int t = (int)(gid & 7);
+  const bool live = (gid >> 3) < G.cells;   // (whole groups of eight: every lane of a live group runs the shuffles below)
+  const int bs = G.bs;
+  const int cell = live ? (int)(gid >> 3) : 0;
+  const int c1 = cell % G.n[0], q = cell / G.n[0], c2 = q % G.n[1], c3 = q / G.n[1];
+  const bool mine = live && t < bs;
+  // row t of [Acc | I]; the lanes past bs hold rows of the identity, which no pivot search considers
+  W a[VK_MAXBS], v[VK_MAXBS];
+#pragma unroll
+  for (int j = 0; j < VK_MAXBS; ++j) {
+    a[j] = W{};
+    v[j] = j == t ? vb_one(W{}) : W{};
+  }
+  if (mine) {
+    int I[VK_MAXBS];
+#pragma unroll
+    for (int j = 0; j < VK_MAXBS; ++j) I[j] = j < bs ? vanka_unknown(G, c1, c2, c3, j) : -1;
+    const int row = vanka_unknown(G, c1, c2, c3, t);
+    for (int e = rowptr[row + 1] - 1, e0 = rowptr[row]; e >= e0; --e) {   // backwards: of a repeated column the first entry stays
+      const int c = col[e];
+      const W x = vb_widen(val[e]);
+#pragma unroll
+      for (int j = 0; j < VK_MAXBS; ++j)
+        if (c == I[j]) a[j] = x;
+    }
+    // the variant's edit of Acc (Vanka.jl:327-362)
+    if (P.scalar && (P.type == 1 || P.type == 3) && t < bs - 1) {
+#pragma unroll
+      for (int j = 0; j < VK_MAXBS; ++j) {
+        if (j < bs - 1 && j != t) a[j] = W{};
+        if (j == t && P.type == 3) a[j] = a[j] / P.w0;
+      }
+    }
+  }
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < VK_MAXBS; ++k) {
+    if (k >= bs) break;   // (uniform)
+    // the pivot: largest squared modulus of column k among rows k .. bs-1, the lowest row on ties
+    double best = (t >= k && t < bs) ? vb_abs2(a[k]) : -1.0;
+    if (best != best) best = __builtin_inf();   // (a NaN entry is chosen and then refused below)
+    int at = t;
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+      const double ob = __shfl_xor(best, o, 8);
+      const int oa = __shfl_xor(at, o, 8);
+      if (ob > best || (ob == best && oa < at)) { best = ob; at = oa; }
+    }
+    if (!(best > 0.0) || best == __builtin_inf()) bad = true;
+    // rows k and `at` change places; the pivot row is scaled and taken out of the others
+    W pa[VK_MAXBS], pv[VK_MAXBS];
+#pragma unroll
+    for (int j = 0; j < VK_MAXBS; ++j) {
+      const W ka = vk_shfl8(a[j], k), kv = vk_shfl8(v[j], k);
+      pa[j] = vk_shfl8(a[j], at);
+      pv[j] = vk_shfl8(v[j], at);
+      if (t == at) { a[j] = ka; v[j] = kv; }
+    }
+    const W rp = vb_recip(pa[k], best);
+#pragma unroll
+    for (int j = 0; j < VK_MAXBS; ++j) {
+      pa[j] = vk_mul(rp, pa[j]);
+      pv[j] = vk_mul(rp, pv[j]);
+    }
+    if (t == k) {
+#pragma unroll
+      for (int j = 0; j < VK_MAXBS; ++j) { a[j] = pa[j]; v[j] = pv[j]; }
+    } else {
+      const W f = a[k];
+#pragma unroll
+      for (int j = 0; j < VK_MAXBS; ++j) {
+        a[j] = a[j] - vk_mul(f, pa[j]);
+        v[j] = v[j] - vk_mul(f, pv[j]);
+      }
+    }
+  }
+  if (!live) return;
+  if (bad) {
+    if (t == 0) {
+      atomicAdd(&flag[0], 1);
+      atomicMax(&flag[1], INT_MAX - cell);
+    }
+    return;
+  }
+  if (t >= bs) return;
+  // the damping of row t: W_t (type 1), nothing (type 3), t_t * W_t with t_t = 1/2 on a face shared with a neighbour (type 5)
+  double s = 1.0;
+  if (P.type != 3) {
+    const bool pressure = G.ip && t == bs - 1;
+    s = pressure ? P.w1 : P.w0;
+    if (P.type == 5 && !pressure) {
+      const int d = t >> 1, c = d == 0 ? c1 : d == 1 ? c2 : c3, nd = d == 0 ? G.n[0] : d == 1 ? G.n[1] : G.n[2];
+      const bool boundary = (t & 1) ? c == nd - 1 : c == 0;
+      s = (boundary ? 1.0 : 0.5) * s;
+    }
+  }
+  typename VankaBlk<T>::type* out = D + (size_t)cell * (size_t)(bs * bs) + (size_t)t * (size_t)bs;
+#pragma unroll
+  for (int j = 0; j < VK_MAXBS; ++j)
+    if (j < bs) out[j] = vb_store(vb_scale(s, v[j]));   // (s = 1 is exact)
+}
+
 }  // namespace mgk

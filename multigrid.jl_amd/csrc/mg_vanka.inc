@@ -18,7 +18,13 @@ struct VankaCore {
   int bk = 0;
   long long launches = 0;  // kernels enqueued so far
   int colours_live = 0;    // colours that hold a cell (n[d] = 1 leaves the even parity of d empty)
-  void release() { D.release(); delta.release(); bdelta.release(); bk = 0; }
+  // the device build (vanka_build_launch / _finish): the blocks under construction, exchanged with D once a build has marked no cell;
+  // {marked cells, the lowest of them}; and what the last successful build was asked for (has_w: D came from a build, not from the host)
+  DevBuf<float> Dnew;
+  DevBuf<int> flag;
+  bool has_w = false;
+  mgk::VankaBuild built{};
+  void release() { D.release(); delta.release(); bdelta.release(); Dnew.release(); flag.release(); bk = 0; has_w = false; }
 };
 
 // (dim, n, includePressure) -> geometry; nrows must be sum(nf) [+ prod(n)] (getVankaBlockSize, Vanka.jl:211-222)
@@ -50,20 +56,88 @@ int vanka_type_served(long long type) {
   return fail(MG_ERR_UNSUPPORTED, "unknown Vanka type %lld", type);
 }
 
-// D_blocks: (bs*bs) x cells column-major, Float32 (cx: ComplexF32) - the caller's LocalBlocks as they are
-int vanka_core_init(VankaCore* V, bool cx, const mgk::VankaGeo& G, const void* D_blocks, bool single = false) {
-  if (!D_blocks) return fail(MG_ERR_INVALID, "D_blocks is null");
+// floats of the cells' blocks
+inline size_t vanka_block_floats(const VankaCore* V) {
+  return (V->cx ? 2 : 1) * (size_t)V->G.bs * (size_t)V->G.bs * (size_t)V->G.cells;
+}
+
+// geometry and buffers of a core; the blocks arrive from the host (vanka_core_init) or from a build (vanka_build_launch)
+int vanka_core_alloc(VankaCore* V, bool cx, const mgk::VankaGeo& G, bool single = false) {
   const size_t vw = cx ? 2 : 1;
   V->G = G;
   V->cx = cx;
   V->single = cx && single;
   V->colours_live = 1;
   for (int d = 0; d < G.dim; ++d) V->colours_live *= G.n[d] >= 2 ? 2 : 1;
-  const size_t nD = vw * (size_t)G.bs * (size_t)G.bs * (size_t)G.cells;
-  MG_TRY(V->D.alloc(nD));
+  MG_TRY(V->D.alloc(vanka_block_floats(V)));
   MG_TRY(V->delta.alloc((V->single ? 1 : vw) * (size_t)G.bs * (size_t)G.cells));
-  HIP_TRY(hipMemcpy(V->D.p, D_blocks, nD * sizeof(float), hipMemcpyHostToDevice));
   return MG_OK;
+}
+
+// D_blocks: (bs*bs) x cells column-major, Float32 (cx: ComplexF32) - the caller's LocalBlocks as they are
+int vanka_core_init(VankaCore* V, bool cx, const mgk::VankaGeo& G, const void* D_blocks, bool single = false) {
+  if (!D_blocks) return fail(MG_ERR_INVALID, "D_blocks is null");
+  MG_TRY(vanka_core_alloc(V, cx, G, single));
+  HIP_TRY(hipMemcpy(V->D.p, D_blocks, vanka_block_floats(V) * sizeof(float), hipMemcpyHostToDevice));
+  return MG_OK;
+}
+
+// ---- the blocks built on the device (kernel: vanka_build_blocks, mg_vanka.hpp) ------------------------------------------------------
+// (VankaType, w[nw]) of a build: types as vanka_type_served; nw = 1 (a scalar w) or 2 (the pair (w0, w1)); ECON_VANKA_RB divides the
+// diagonal by its one w (Vanka.jl:361), so a pair is refused, as setupVankaFacesPreconditioner refuses it
+int vanka_build_args(long long type, const double* w, long long nw, mgk::VankaBuild* P) {
+  MG_TRY(vanka_type_served(type));
+  if (!w) return fail(MG_ERR_INVALID, "w is null");
+  if (nw != 1 && nw != 2) return fail(MG_ERR_INVALID, "nw=%lld: w is one number or a pair", nw);
+  if (type == VANKA_ECON_RB && nw == 2) return fail(MG_ERR_INVALID, "ECON_VANKA_RB takes a scalar w (nw = 1)");
+  P->type = (int)type;
+  P->scalar = nw == 1 ? 1 : 0;
+  P->w0 = w[0];
+  P->w1 = nw == 2 ? w[1] : w[0];
+  return MG_OK;
+}
+
+// Enqueue one build of the core's blocks from the CSR of its operator (val: double, or interleaved pairs of doubles, or of floats where
+// V->single) into V->Dnew; V->D and whatever relaxes with it are not touched.  vanka_build_finish, after the caller has waited for the
+// stream, makes them the core's blocks.
+int vanka_build_launch(VankaCore* V, const int* rowptr, const int* col, const void* val, const mgk::VankaBuild& P, hipStream_t stream) {
+  const mgk::VankaGeo& G = V->G;
+  const size_t nD = vanka_block_floats(V);
+  if (V->Dnew.n != nD) MG_TRY(V->Dnew.alloc(nD));
+  if (V->flag.n != 2) MG_TRY(V->flag.alloc(2));
+  HIP_TRY(hipMemsetAsync(V->flag.p, 0, 2 * sizeof(int), stream));
+  const dim3 grid((unsigned)(((long long)G.cells * 8 + mgk::BLK - 1) / mgk::BLK)), block(mgk::BLK);
+  if (!V->cx)
+    hipLaunchKernelGGL(mgk::vanka_build_blocks<double>, grid, block, 0, stream, G, P, rowptr, col, static_cast<const double*>(val), V->Dnew.p,
+                       V->flag.p);
+  else if (V->single)
+    hipLaunchKernelGGL(mgk::vanka_build_blocks<mgk::f2_t>, grid, block, 0, stream, G, P, rowptr, col, static_cast<const mgk::f2_t*>(val),
+                       reinterpret_cast<float2*>(V->Dnew.p), V->flag.p);
+  else
+    hipLaunchKernelGGL(mgk::vanka_build_blocks<mgk::d2_t>, grid, block, 0, stream, G, P, rowptr, col, static_cast<const mgk::d2_t*>(val),
+                       reinterpret_cast<float2*>(V->Dnew.p), V->flag.p);
+  ++V->launches;
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// The stream of the build has been waited for.  No cell marked: the new blocks become the core's and (type, w) are remembered.
+// Otherwise the core keeps its blocks; *bad_cells and *first_cell (0-based) say what was found.
+int vanka_build_finish(VankaCore* V, const mgk::VankaBuild& P, int* bad_cells, int* first_cell) {
+  int flag[2] = {0, 0};
+  HIP_TRY(hipMemcpy(flag, V->flag.p, sizeof(flag), hipMemcpyDeviceToHost));
+  *bad_cells = flag[0];
+  *first_cell = INT_MAX - flag[1];   // (the kernel keeps the maximum of INT_MAX - cell: a zero-filled flag needs no other start value)
+  if (flag[0] != 0) return MG_OK;
+  std::swap(V->D.p, V->Dnew.p);   // (both hold vanka_block_floats values)
+  V->has_w = true;
+  V->built = P;
+  return MG_OK;
+}
+
+int vanka_singular(int bad_cells, int first_cell, const char* where) {
+  return fail(MG_ERR_INVALID, "%s: the block of cell %d is singular (a zero or non-finite pivot; %d such cell%s): the previous blocks are kept",
+              where, first_cell + 1, bad_cells, bad_cells == 1 ? "" : "s");
 }
 
 // numit relaxations of x (in place) on `stream`, no synchronisation.  The caller has checked the type (vanka_type_served).
@@ -231,12 +305,16 @@ struct mg_vanka {
 
 namespace {
 
+int vanka_build_handle(mg_vanka* v, const mgk::VankaBuild& P, const char* name);
+
+// D_blocks: the caller's blocks, or null with `build`: the blocks are built on the device from the operator just uploaded
 int vanka_create(bool cx, long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
-                 const long long* rowptr, const long long* colA, const double* valA, const void* D_blocks, mg_vanka** out) {
+                 const long long* rowptr, const long long* colA, const double* valA, const void* D_blocks, mg_vanka** out,
+                 const mgk::VankaBuild* build = nullptr) {
   const size_t vw = cx ? 2 : 1;
   if (!out) return fail(MG_ERR_INVALID, "out is null");
   *out = nullptr;
-  if (nrows < 1 || !rowptr || !colA || !valA || !D_blocks) return fail(MG_ERR_INVALID, "null or empty argument");
+  if (nrows < 1 || !rowptr || !colA || !valA || (!D_blocks && !build)) return fail(MG_ERR_INVALID, "null or empty argument");
   mgk::VankaGeo G;
   MG_TRY(vanka_geometry(dim, n, includePressure, nrows, &G));
   if (rowptr[0] != 1) return fail(MG_ERR_INVALID, "rowptr[1] must be 1 (1-based Julia arrays expected)");
@@ -269,12 +347,14 @@ int vanka_create(bool cx, long long device_id, long long dim, const long long* n
     HIP_TRY(hipMemcpy(v->rowptr.p, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v->col.p, ci.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v->val.p, valA, vw * (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-    MG_TRY(vanka_core_init(&v->core, cx, G, D_blocks));
+    if (build) MG_TRY(vanka_core_alloc(&v->core, cx, G));
+    else MG_TRY(vanka_core_init(&v->core, cx, G, D_blocks));
     HIP_TRY(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
     return MG_OK;
   };
-  const int rc = up();
+  int rc = up();
   (void)hipDeviceSynchronize();   // the blocking copies above ran on the NULL stream; the kernels run on the handle's own
+  if (rc == MG_OK && build) rc = vanka_build_handle(v, *build, "mg_vanka_create_built");
   if (rc != MG_OK) {
     mg_vanka_destroy(v);
     return rc;
@@ -368,6 +448,50 @@ int vanka_apply_block_host(bool cx, mg_vanka* v, double* x, const double* b, lon
   return MG_OK;
 }
 
+// ---- the blocks of the stand-alone handle built from its resident operator ----------------------------------------------------------
+int vanka_build_handle(mg_vanka* v, const mgk::VankaBuild& P, const char* name) {
+  (void)hipSetDevice(v->device);
+  HIP_TRY(spin_sync(v->stream));   // (an earlier build's buffer may still be read)
+  MG_TRY(vanka_build_launch(&v->core, v->rowptr.p, v->col.p, v->val.p, P, v->stream));
+  HIP_TRY(spin_sync(v->stream));
+  int bad = 0, first = 0;
+  MG_TRY(vanka_build_finish(&v->core, P, &bad, &first));
+  return bad ? vanka_singular(bad, first, name) : MG_OK;
+}
+
+int vanka_handle_type(bool cx, mg_vanka* v, const char* name) {
+  if (!v) return fail(MG_ERR_INVALID, "null handle");
+  if (v->core.cx != cx)
+    return fail(MG_ERR_STATE, "%s on a handle of %s values (%s)", name, v->core.cx ? "ComplexF64" : "Float64", v->core.cx ? "the _CFP64 form" : "the _FP64 form");
+  return MG_OK;
+}
+
+int vanka_build_entry(bool cx, mg_vanka* v, long long type, const double* w, long long nw, const char* name) {
+  MG_TRY(vanka_handle_type(cx, v, name));
+  mgk::VankaBuild P;
+  MG_TRY(vanka_build_args(type, w, nw, &P));
+  return vanka_build_handle(v, P, name);
+}
+
+int vanka_replace_values(bool cx, mg_vanka* v, const double* nzval, long long nnz, const char* name) {
+  MG_TRY(vanka_handle_type(cx, v, name));
+  if (!nzval) return fail(MG_ERR_INVALID, "nzval is null");
+  if (nnz != v->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, v->nnz);
+  (void)hipSetDevice(v->device);
+  HIP_TRY(spin_sync(v->stream));
+  if (nnz > 0) HIP_TRY(hipMemcpy(v->val.p, nzval, (cx ? 2 : 1) * (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+  return MG_OK;
+}
+
+int vanka_create_built(bool cx, long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
+                       const long long* rowptr, const long long* colA, const double* valA, long long type, const double* w, long long nw,
+                       mg_vanka** out) {
+  if (out) *out = nullptr;
+  mgk::VankaBuild P;
+  MG_TRY(vanka_build_args(type, w, nw, &P));
+  return vanka_create(cx, device_id, dim, n, includePressure, nrows, rowptr, colA, valA, nullptr, out, &P);
+}
+
 }  // namespace
 
 extern "C" {
@@ -382,6 +506,67 @@ int mg_vanka_create_FP64_INT64(long long device_id, long long dim, const long lo
 int mg_vanka_create_CFP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
                                 const long long* rowptr, const long long* colA, const double* valA, const float* D_blocks, mg_vanka** out) {
   return vanka_create(true, device_id, dim, n, includePressure, nrows, rowptr, colA, valA, D_blocks, out);
+}
+
+// The blocks built on the device (kernel: vanka_build_blocks, mg_vanka.hpp) instead of handed over: see include/mgvcycle.h.
+// mg_vanka_create_built_*: the create call with (VankaType, w[nw]) in the place of D_blocks.
+int mg_vanka_create_built_FP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
+                                     const long long* rowptr, const long long* colA, const double* valA, long long VankaType, const double* w,
+                                     long long nw, mg_vanka** out) {
+  return vanka_create_built(false, device_id, dim, n, includePressure, nrows, rowptr, colA, valA, VankaType, w, nw, out);
+}
+int mg_vanka_create_built_CFP64_INT64(long long device_id, long long dim, const long long* n, long long includePressure, long long nrows,
+                                      const long long* rowptr, const long long* colA, const double* valA, long long VankaType, const double* w,
+                                      long long nw, mg_vanka** out) {
+  return vanka_create_built(true, device_id, dim, n, includePressure, nrows, rowptr, colA, valA, VankaType, w, nw, out);
+}
+// mg_vanka_build_blocks_*: the handle's blocks again from its resident operator; a singular cell leaves the previous blocks in place
+int mg_vanka_build_blocks_FP64(mg_vanka* v, long long VankaType, const double* w, long long nw) {
+  return vanka_build_entry(false, v, VankaType, w, nw, "mg_vanka_build_blocks_FP64");
+}
+int mg_vanka_build_blocks_CFP64(mg_vanka* v, long long VankaType, const double* w, long long nw) {
+  return vanka_build_entry(true, v, VankaType, w, nw, "mg_vanka_build_blocks_CFP64");
+}
+// mg_vanka_replace_values_*: new values of the operator (valA's convention) on the stored pattern; the blocks are not touched
+int mg_vanka_replace_values_FP64(mg_vanka* v, const double* nzval, long long nnz) {
+  return vanka_replace_values(false, v, nzval, nnz, "mg_vanka_replace_values_FP64");
+}
+int mg_vanka_replace_values_CFP64(mg_vanka* v, const double* nzval, long long nnz) {
+  return vanka_replace_values(true, v, nzval, nnz, "mg_vanka_replace_values_CFP64");
+}
+// mg_vanka_get_blocks: the handle's blocks as mg_vanka_create_* takes them; count = bs*bs*cells values (Float32, or ComplexF32 pairs)
+int mg_vanka_get_blocks(mg_vanka* v, float* out, long long count) {
+  if (!v || !out) return fail(MG_ERR_INVALID, "null argument");
+  const long long want = (long long)v->core.G.bs * v->core.G.bs * v->core.G.cells;
+  if (count != want) return fail(MG_ERR_INVALID, "count=%lld: the handle holds %lld block values", count, want);
+  (void)hipSetDevice(v->device);
+  HIP_TRY(spin_sync(v->stream));
+  HIP_TRY(hipMemcpy(out, v->core.D.p, vanka_block_floats(&v->core) * sizeof(float), hipMemcpyDeviceToHost));
+  return MG_OK;
+}
+
+// Measurement: device time of one build (into the spare buffer; the handle's blocks are not replaced), as mg_vanka_time_dev
+int mg_vanka_time_build(mg_vanka* v, long long VankaType, const double* w, long long nw, long long warmup, long long reps, double* ms) {
+  if (!v || !ms || reps < 1 || warmup < 0) return fail(MG_ERR_INVALID, "bad argument");
+  mgk::VankaBuild P;
+  MG_TRY(vanka_build_args(VankaType, w, nw, &P));
+  (void)hipSetDevice(v->device);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = MG_OK;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventCreate failed");
+  for (long long it = 0; it < warmup + reps && rc == MG_OK; ++it) {
+    if (hipEventRecord(e0, v->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
+    if (rc == MG_OK) rc = vanka_build_launch(&v->core, v->rowptr.p, v->col.p, v->val.p, P, v->stream);
+    if (rc == MG_OK) {
+      float t = 0.f;
+      if (hipEventRecord(e1, v->stream) != hipSuccess || spin_sync(v->stream) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)
+        rc = fail(MG_ERR_HIP, "event timing failed");
+      if (it >= warmup) ms[it - warmup] = (double)t;
+    }
+  }
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
 }
 
 int mg_vanka_apply_FP64(mg_vanka* v, double* x, const double* b, long long numit, long long VankaType) {

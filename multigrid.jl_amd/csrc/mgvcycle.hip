@@ -20,6 +20,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <chrono>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <map>

@@ -166,6 +166,14 @@ SIGNATURES = {
     "mg_vanka_time_block_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _dp]),
     "mg_vanka_info": (C.c_int, [_vp, _lp]),
     "mg_vanka_time_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _dp]),
+    "mg_vanka_create_built_FP64_INT64": (C.c_int, [_ll, _ll, _lp, _ll, _ll, _lp, _lp, _dp, _ll, _dp, _ll, C.POINTER(_vp)]),
+    "mg_vanka_create_built_CFP64_INT64": (C.c_int, [_ll, _ll, _lp, _ll, _ll, _lp, _lp, _dp, _ll, _dp, _ll, C.POINTER(_vp)]),
+    "mg_vanka_build_blocks_FP64": (C.c_int, [_vp, _ll, _dp, _ll]),
+    "mg_vanka_build_blocks_CFP64": (C.c_int, [_vp, _ll, _dp, _ll]),
+    "mg_vanka_replace_values_FP64": (C.c_int, [_vp, _dp, _ll]),
+    "mg_vanka_replace_values_CFP64": (C.c_int, [_vp, _dp, _ll]),
+    "mg_vanka_get_blocks": (C.c_int, [_vp, C.POINTER(C.c_float), _ll]),
+    "mg_vanka_time_build": (C.c_int, [_vp, _ll, _dp, _ll, _ll, _ll, _dp]),
     "mg_vanka_destroy": (C.c_int, [_vp]),
     "mg_dist_unique_id": (C.c_int, [C.c_char_p]),
     "mg_dist_create": (C.c_int, [_ll, _ll, _ll, C.c_char_p, _ll, _ll, _ll, C.POINTER(_vp)]),
@@ -209,6 +217,10 @@ SIGNATURES = {
     "mg_set_schedule_CF64": (C.c_int, [_vp, _ll, _ll]),
     "mg_set_vanka_CF64": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, C.POINTER(C.c_float)]),
     "mg_set_vanka_CF32": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, C.POINTER(C.c_float)]),
+    "mg_build_vanka_CF64": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, _dp, _ll]),
+    "mg_build_vanka_CF32": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, _dp, _ll]),
+    "mg_get_vanka_blocks_CF64": (C.c_int, [_vp, _ll, C.POINTER(C.c_float), _ll]),
+    "mg_get_vanka_blocks_CF32": (C.c_int, [_vp, _ll, C.POINTER(C.c_float), _ll]),
     "mg_set_vanka_relax_CF64": (C.c_int, [_vp, _ll]),
     "mg_set_vanka_relax_CF32": (C.c_int, [_vp, _ll]),
     "mg_fgmres_relax_CF64": (C.c_int, [_vp, _ll, _dp, _dp, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp]),
@@ -1007,13 +1019,32 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         blk = param.relaxPrecs[l - 1]
         if not isinstance(blk, np.ndarray) or blk.dtype != np.complex64 or blk.ndim != 2:
             raise TypeError("relaxPrecs of a complex Vanka hierarchy are the complex64 blocks of setupVankaFacesPreconditioner")
-        blk = np.asfortranarray(blk)
         nn = np.ascontiguousarray(param.Meshes[l - 1].n, dtype=np.int64)
         mixed = param.transferOperatorType == "SystemsFacesMixedLinear"
-        _check(self.lib, self._fn("set_vanka")(self.handle, l, nn.size, _i64(nn), 1 if mixed else 0,
-                                               getVankaRelaxType(param.relaxType)[1], blk.ctypes.data_as(_fp)),
-               f"mg_set_vanka_{self._sfx}(level={l})")
+        self.__dict__.setdefault("_vanka_shape", {})[int(l)] = tuple(blk.shape)     # (vanka_blocks sizes its array by it)
+        if getattr(param, "vankaDeviceSetup", False):
+            # the level's blocks built in HBM from the operator just uploaded (mg_build_vanka_*): nothing of relaxPrecs[l] is sent
+            from .mgsetup import _relax_param_arr
+            from .vanka import _w_pair, _check_build
+            wv, nw = _w_pair(_relax_param_arr(param)[l - 1])
+            _check_build(self.lib, self._fn("build_vanka")(self.handle, l, nn.size, _i64(nn), 1 if mixed else 0,
+                                                           getVankaRelaxType(param.relaxType)[1], _f64(wv), nw),
+                         f"mg_build_vanka_{self._sfx}(level={l})")
+        else:
+            blk = np.asfortranarray(blk)
+            _check(self.lib, self._fn("set_vanka")(self.handle, l, nn.size, _i64(nn), 1 if mixed else 0,
+                                                   getVankaRelaxType(param.relaxType)[1], blk.ctypes.data_as(_fp)),
+                   f"mg_set_vanka_{self._sfx}(level={l})")
         self._set_relax(l, np.zeros(param.As[l - 1].shape[0], dtype=self._cdtype), pre, post)
+
+    def vanka_blocks(self, level: int) -> np.ndarray:
+        """The Vanka blocks of ``level`` as the handle holds them (mg_get_vanka_blocks_*): (bs^2, cells) complex64, column-major."""
+        if int(level) not in getattr(self, "_vanka_shape", {}):
+            raise MGDeviceError(f"vanka_blocks: level {level} holds no Vanka blocks")
+        out = np.zeros(self._vanka_shape[int(level)], dtype=np.complex64, order="F")
+        _check(self.lib, self._fn("get_vanka_blocks")(self.handle, int(level), out.ctypes.data_as(_fp), out.size),
+               f"mg_get_vanka_blocks_{self._sfx}(level={level})")
+        return out
 
     def _upload(self, param):
         lib = self.lib
@@ -1036,6 +1067,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         self._vanka_blocks = self._vanka and bool(getattr(param, "vankaBlocks", False))
         if self._vanka_blocks:            # blocks on a Vanka hierarchy: the block form of the smoother (opt-in, read at every call)
             _check(lib, lib.mg_set_option(self.handle, b"vanka_blocks", 1.0), "mg_set_option(vanka_blocks)")
+        self._vanka_device_setup = self._vanka and bool(getattr(param, "vankaDeviceSetup", False))
+        if self._vanka_device_setup:      # mg_rap_CF64 serves the Vanka handle: operators and blocks refreshed in HBM (opt-in, read at every call)
+            _check(lib, lib.mg_set_option(self.handle, b"vanka_device_setup", 1.0), "mg_set_option(vanka_device_setup)")
         self._set_coarse(param)
         _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
         self._schedule = self._schedule_of(param)
@@ -1499,8 +1533,15 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         t0 = time.perf_counter()
         nz = np.ascontiguousarray(np.conj(A_new.data), dtype=np.complex128)     # the reference's AT values
         rp = param.relaxParam
-        omega = np.ascontiguousarray([float(rp[l]) if isinstance(rp, (list, tuple, np.ndarray)) else float(rp)
-                                      for l in range(self.nlevels)], dtype=np.float64)
+        vanka = getattr(self, "_vanka", False)
+        if vanka and not getattr(self, "_vanka_device_setup", False):
+            raise MGDeviceError("replace_matrix of a complex Vanka hierarchy needs the device set-up of its blocks "
+                                "(getMGparam(..., complexVanka=True, vankaDeviceSetup=True))")
+        if vanka:     # (the levels remember their own (VankaType, w): omega is validated and not used)
+            omega = np.ones(self.nlevels, dtype=np.float64)
+        else:
+            omega = np.ascontiguousarray([float(rp[l]) if isinstance(rp, (list, tuple, np.ndarray)) else float(rp)
+                                          for l in range(self.nlevels)], dtype=np.float64)
         kind = 1 if param.relaxType == "SPAI" else 0
         done = C.c_longlong(0)
         _check(lib, lib.mg_rap_CF64(self.handle, _c128(nz), nz.size, kind, _f64(omega), C.byref(done)), "mg_rap_CF64")
@@ -1511,7 +1552,11 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             vals = np.empty(M.nnz, dtype=np.complex128)
             _check(lib, lib.mg_get_values_CF64(self.handle, l, MG_OP_A, _c128(vals), vals.size), "mg_get_values_CF64")
             np.conjugate(vals, out=M.data)
+        tb = time.perf_counter()
         for l in range(1, self.nlevels):
+            if vanka:                                              # the cells' blocks, rebuilt in HBM (mg_get_vanka_blocks_CF64)
+                param.relaxPrecs[l - 1] = self.vanka_blocks(l)
+                continue
             d = np.empty(param.As[l - 1].shape[0], dtype=np.complex128)
             _check(lib, lib.mg_get_relax_CF64(self.handle, l, _c128(d), d.size), "mg_get_relax_CF64")
             param.relaxPrecs[l - 1] = d
@@ -1525,6 +1570,8 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         #  in HBM - no inverse, no factorisation, nothing uploaded)
         if timings is not None:
             timings.update(rap=t1 - t0, readback=t2 - t1, coarsest=time.perf_counter() - t2)
+            if vanka:     # (the part of `readback` spent on the blocks)
+                timings.update(blocks_readback=t2 - tb)
 
     def adjoint_hierarchy(self, param) -> None:
         """adjointHierarchy on the resident hierarchy (mg_adjoint_hierarchy_CF64 / _CF32): every operator replaced by its conjugate

@@ -49,6 +49,7 @@ class MGparam:
     blockCoarseGMRES: bool = False     # coarseSolveType "GMRES" on a complex hierarchy: serve blocks by the block GMRES coarsest solve
     complexVanka: bool = False         # a Vanka relaxType on a complex hierarchy: the cell-block smoother in the complex cycle
     vankaBlocks: bool = False          # complexVanka only: serve blocks of right-hand sides by the block form of the smoother
+    vankaDeviceSetup: bool = False     # complexVanka only: the cells' blocks are built (and, ComplexF64, refreshed) on the device
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -61,7 +62,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                relaxType="SPAI", relaxParam=1.0, relaxPre=2, relaxPost=2, cycleType="V",
                coarseSolveType="NoMUMPS", strongConnParam=0.4, FilteringParam=0.0,
                transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
-               blockCoarseGMRES: bool = False, complexVanka: bool = False, vankaBlocks: bool = False) -> MGparam:
+               blockCoarseGMRES: bool = False, complexVanka: bool = False, vankaBlocks: bool = False,
+               vankaDeviceSetup: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -80,6 +82,11 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     ``vankaBlocks=True`` (keyword only, with ``complexVanka=True``) switches on the block form of that smoother: blocks of up to 16
     right-hand sides are then served on the hierarchy for the cycles V / W / F (solveMG, recursiveCycle, getMultigridPreconditioner,
     the block _CFP64 drivers, the device's ``block_*`` methods); without it they are refused, as before.
+    ``vankaDeviceSetup=True`` (keyword only, with ``complexVanka=True``; with or without ``singlePrecision`` and ``vankaBlocks``)
+    builds the cells' blocks on the device: ``MGsetup`` and the host path of ``replaceMatrixInHierarchy`` take ``relaxPrecs[l]`` from
+    ``setupVankaFacesPreconditioner(..., device=True)`` (ordinary host arrays, as before), the upload builds every level's blocks in
+    HBM from the resident operator instead of sending them, and ``replaceMatrixInHierarchy`` of a resident ComplexF64 param with
+    an unchanged pattern recomputes operators and blocks in HBM and keeps the handle.  Without it nothing changes.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
@@ -94,6 +101,9 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
             raise NotImplementedError("complexVanka=True serves VAL=ComplexF64 (singlePrecision or not) with a Vanka relaxType")
     if vankaBlocks and not complexVanka:
         raise NotImplementedError("vankaBlocks=True serves a complex Vanka hierarchy (complexVanka=True)")
+    if vankaDeviceSetup and not complexVanka:
+        raise NotImplementedError("vankaDeviceSetup=True serves a complex Vanka hierarchy (complexVanka=True); FP64 Vanka hierarchies "
+                                  "set their blocks up on the host")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -108,7 +118,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    strongConnParam=float(strongConnParam), FilteringParam=float(FilteringParam),
                    transferOperatorType=str(transferOperatorType), singlePrecision=bool(singlePrecision),
                    blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka),
-                   vankaBlocks=bool(vankaBlocks), VAL=np.dtype(VAL).type, IND=np.int64)
+                   vankaBlocks=bool(vankaBlocks), vankaDeviceSetup=bool(vankaDeviceSetup), VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -181,7 +191,7 @@ def copySolver(MG: MGparam) -> MGparam:
                      MG.relaxType, MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
                      MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single,
                      blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka),
-                     vankaBlocks=bool(MG.vankaBlocks))
+                     vankaBlocks=bool(MG.vankaBlocks), vankaDeviceSetup=bool(MG.vankaDeviceSetup))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

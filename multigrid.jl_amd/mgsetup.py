@@ -64,18 +64,23 @@ def getSPAIprec(A):
     return A.diagonal() / s
 
 
-def getRelaxPrec(A, relaxType: str, relaxParam=1.0, Mesh_l=None, withCellsBlock: bool = False):
+def getRelaxPrec(A, relaxType: str, relaxParam=1.0, Mesh_l=None, withCellsBlock: bool = False, device: bool = False):
     """Jac: d = omega/diag (MGsetup.jl:145-147).  SPAI: d = omega*diag/colnorm^2 (l.148-149).  The Vanka types: the cells'
     blocks of setupVankaFacesPreconditioner on the level's mesh (l.153-154; relaxParam a float or a tuple of two).
 
     Complex A (the applied operator, = the reference's AT^H): the reference's d = conj(relaxParam ./ diag(AT)) and
     conj(relaxParam*getSPAIprec(AT)) become d = omega/diag(A) and d = omega*conj(diag(A))/colsumsq|A| - for a real A both
-    are the formulas above."""
+    are the formulas above.
+
+    ``device=True`` (the Vanka types only; a param with ``vankaDeviceSetup=True``): the blocks are built on the device
+    (``setupVankaFacesPreconditioner(..., device=True)``) and returned as the same host array."""
     from .vanka import getVankaRelaxType, setupVankaFacesPreconditioner
     isVanka, VankaType = getVankaRelaxType(relaxType)
     if isVanka:
         if Mesh_l is None:
             raise ValueError(f"relaxType={relaxType!r} needs the level's mesh (getRelaxPrec(A, relaxType, relaxParam, Mesh_l, withCellsBlock))")
+        if device:
+            return setupVankaFacesPreconditioner(A, Mesh_l, relaxParam, withCellsBlock, VankaType, device=True)
         return setupVankaFacesPreconditioner(A, Mesh_l, relaxParam, withCellsBlock, VankaType)
     if relaxType == "hybridVankaFacesKaczmarz":
         raise NotImplementedError("RelaxHybridVanka / getHybridVankaFaces are out of scope (the cycle's call is commented out in the reference)")
@@ -101,6 +106,11 @@ def getRelaxPrec(A, relaxType: str, relaxParam=1.0, Mesh_l=None, withCellsBlock:
 def _is_vanka(param: MGparam) -> bool:
     from .vanka import getVankaRelaxType
     return getVankaRelaxType(param.relaxType)[0]
+
+
+def _vanka_device_kw(param: MGparam) -> dict:
+    """getRelaxPrec's ``device=True`` for a param that asked for the device set-up of its Vanka blocks (``vankaDeviceSetup``)."""
+    return {"device": True} if getattr(param, "vankaDeviceSetup", False) and _is_vanka(param) else {}
 
 
 def _relax_param_arr(param: MGparam):
@@ -245,7 +255,8 @@ def MGsetup(ATf, Mesh, param: MGparam, nrhs: int = 1, verbose: bool = False) -> 
         R.sort_indices()
         if is_single(param):                                    # Ps / Rs in real(VAL) (MGsetup.jl:79-82)
             P, R = P.astype(np.float32), R.astype(np.float32)
-        relaxPrecs.append(getRelaxPrec(A, param.relaxType, relaxParamArr[l - 1], Meshes[l - 1], withCellsBlock))
+        relaxPrecs.append(getRelaxPrec(A, param.relaxType, relaxParamArr[l - 1], Meshes[l - 1], withCellsBlock,
+                                       **_vanka_device_kw(param)))
         if P.shape[0] == P.shape[1]:
             if verbose:
                 print(f"Stopped Coarsening at level {l}")
@@ -301,6 +312,8 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
     A = _of_val(param, A)
     # (a ComplexF32 hierarchy is recomputed on the host and uploaded again: its device re-setup is out of scope)
     on_device = param.device is not None and param.relaxType in ("Jac", "Jac-GMRES", "SPAI") and not is_single(param)
+    if param.device is not None and not is_single(param) and is_complex(param) and _is_vanka(param) and getattr(param, "vankaDeviceSetup", False):
+        on_device = True       # (mg_rap_CF64 with the option vanka_device_setup: operators and blocks recomputed in HBM)
     if on_device and is_complex(param):
         # (mg_rap_CF64.  A Schwarz coarsest solver borrows a device handle of its own, set up on the coarsest matrix: host path)
         from .mgdef import _solver_object
@@ -322,7 +335,7 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
         Al = param.As[l - 1]
         Mesh_l = param.Meshes[l - 1] if param.Meshes else None      # MGsetup.jl:247-252
         param.relaxPrecs[l - 1] = getRelaxPrec(Al, param.relaxType, relaxParamArr[l - 1], Mesh_l,
-                                               param.transferOperatorType == "SystemsFacesMixedLinear")
+                                               param.transferOperatorType == "SystemsFacesMixedLinear", **_vanka_device_kw(param))
         param.As[l] = galerkin(param.Rs[l - 1], Al, param.Ps[l - 1])
     defineCoarsestAinv(param, param.As[-1])
     param.doTranspose = 0

@@ -1,6 +1,7 @@
 """The Vanka cell-block smoother behind the reference's interface (src/Multigrid/Vanka.jl): ``getVankaRelaxType``,
 ``getVankaBlockSize``, ``getVankaVariablesOfCell``, ``cellColor``, ``cellRBColor``, ``setupVankaFacesPreconditioner`` on the
-host, ``RelaxVankaFacesColor`` on the device (csrc/mg_vanka.hpp through ``mg_vanka_*``); there is no CPU fallback.
+host (``device=True``: built on the device by vanka_build_blocks), ``RelaxVankaFacesColor`` on the device (csrc/mg_vanka.hpp
+through ``mg_vanka_*``); there is no CPU fallback.
 
 The reference sets ``const parallel = false`` (Vanka.jl:10): what runs there is the Julia serial path of RelaxVankaFacesColor
 (l.383-425), and that is what is mirrored - not the red-black C path of deps/src/Vanka.c.
@@ -104,13 +105,59 @@ def _weights(w, blockSize, includePressure):
     return np.full(blockSize, float(w)), True
 
 
-def setupVankaFacesPreconditioner(AT, M, w, includePressure: bool, VankaType: int = FULL_VANKA_RB):
+def _w_pair(w):
+    """w as the C ABI takes it: (float64 array of 1 or 2 values, nw)."""
+    if isinstance(w, (tuple, list, np.ndarray)):
+        if len(w) != 2:
+            raise ValueError("w is a Float64 or a tuple of two")
+        return np.array([float(w[0]), float(w[1])], dtype=np.float64), 2
+    return np.array([float(w)], dtype=np.float64), 1
+
+
+def _check_build(lib, rc, what):
+    """_check of a device build: a singular cell (MG_ERR_INVALID naming it) is numpy's LinAlgError, as np.linalg.inv raises it."""
+    if rc == 1:
+        msg = lib.mg_last_error()
+        msg = msg.decode() if msg else ""
+        if "singular" in msg:
+            raise np.linalg.LinAlgError(f"{what}: {msg}")
+    D._check(lib, rc, what)
+
+
+def _setup_blocks_device(AT, M, w, includePressure, VankaType):
+    """setupVankaFacesPreconditioner on the device: upload the operator, build (vanka_build_blocks), read back, close."""
+    A = sp.csr_matrix(AT)
+    if VankaType == KACMARZ_VANKA:
+        raise NotImplementedError("KACMARZ_VANKA belongs to the hybrid cell-wise path (RelaxHybridVanka), which is out of scope")
+    if VankaType not in (FULL_VANKA_RB, FULL_VANKA_LEX, ECON_VANKA_RB, FULL_VANKA_ADD):
+        raise ValueError("unknown Vanka Type.")
+    if VankaType == FULL_VANKA_LEX:
+        raise NotImplementedError("FULL_VANKA_LEX is not served on the device (device=False sets its blocks up on the host)")
+    if VankaType == ECON_VANKA_RB and isinstance(w, (tuple, list, np.ndarray)):
+        raise TypeError("ECON_VANKA_RB takes a scalar w (Vanka.jl:361 divides the diagonal by it)")
+    n = _mesh_n(M)
+    blockSize, nf = getVankaBlockSize(n, includePressure)
+    N = int(nf.sum()) + (int(np.prod(n)) if includePressure else 0)
+    if A.shape != (N, N):
+        raise ValueError(f"the operator is {A.shape}, a mesh of {n.tolist()} cells has {N} unknowns")
+    with VankaHandle(A, None, n, includePressure, w=w, VankaType=VankaType) as H:
+        return H.blocks()
+
+
+def setupVankaFacesPreconditioner(AT, M, w, includePressure: bool, VankaType: int = FULL_VANKA_RB, device: bool = False):
     """LocalBlocks (Vanka.jl:294-370): per cell the adjoint of the damped inverse of Acc = A[I, I], in single precision,
     flattened column-major into column ``cell`` of a (bs^2, prod(n)) array.
 
     FULL_VANKA_RB / _LEX with a scalar w replace the leading (bs-1)x(bs-1) part of Acc by its diagonal (l.333: the line the
     reference runs IS the economic variant), a tuple w leaves Acc alone and scales the rows of its inverse; ECON_VANKA_RB
-    divides that diagonal by w and does not damp further; FULL_VANKA_ADD halves the rows of faces shared with a neighbour."""
+    divides that diagonal by w and does not damp further; FULL_VANKA_ADD halves the rows of faces shared with a neighbour.
+
+    ``device=True`` (not in the reference's signature; default False: the host path below, untouched): the blocks are built on the
+    device from the uploaded operator (mg_vanka_create_built_*) and read back - the same shape, dtype and memory order, the
+    values those of the host path to the rounding of two double-precision eliminations; a singular cell raises
+    ``np.linalg.LinAlgError``.  A complex64 operator is widened first, as the host path reads it."""
+    if device:
+        return _setup_blocks_device(AT, M, w, includePressure, VankaType)
     A = sp.csr_matrix(AT)
     n = _mesh_n(M)
     cx = np.iscomplexobj(A.data)
@@ -207,25 +254,64 @@ class VankaHandle:
     relaxes with the same operator many times builds it once (``vanka_handle``) and passes it to ``RelaxVankaFacesColor``;
     after changing the operator's or the blocks' values it closes it and builds another - nothing is cached behind its back."""
 
-    def __init__(self, A, Dblk, n, includePressure):
+    def __init__(self, A, Dblk, n, includePressure, w=None, VankaType: int = FULL_VANKA_RB):
+        """``Dblk``: the cells' blocks, or None with ``w`` (a float or a pair): the blocks are built on the device from the
+        uploaded operator for (w, VankaType) (mg_vanka_create_built_*)."""
         A = A if sp.isspmatrix_csr(A) and A.has_sorted_indices else _sorted_csr(A)
         lib = D.load_library()
         self.cx = bool(np.iscomplexobj(A.data))
         self.N = int(A.shape[0])
         self.n = tuple(int(k) for k in n)
         self.includePressure = bool(includePressure)
+        self.nnz = int(A.nnz)
         cp = np.ascontiguousarray(A.indptr, dtype=np.int64) + 1
         rv = np.ascontiguousarray(A.indices, dtype=np.int64) + 1
         nz = np.ascontiguousarray(A.data, dtype=np.complex128 if self.cx else np.float64)
-        blk = np.asfortranarray(Dblk, dtype=np.complex64 if self.cx else np.float32)
         nn = np.ascontiguousarray(n, dtype=np.int64)
         self.h = C.c_void_p()
-        create = lib.mg_vanka_create_CFP64_INT64 if self.cx else lib.mg_vanka_create_FP64_INT64
-        D._check(lib, create(0, nn.size, D._i64(nn), 1 if includePressure else 0, A.shape[0], D._i64(cp), D._i64(rv), D._f64(nz),
-                             blk.ctypes.data_as(_fp), C.byref(self.h)), "mg_vanka_create")
+        sfx = "CFP64_INT64" if self.cx else "FP64_INT64"
+        if Dblk is None:
+            if w is None:
+                raise ValueError("a Vanka handle takes the cells' blocks, or w (and VankaType) to build them on the device")
+            wv, nw = _w_pair(w)
+            _check_build(lib, getattr(lib, f"mg_vanka_create_built_{sfx}")(0, nn.size, D._i64(nn), 1 if includePressure else 0, A.shape[0],
+                                                                            D._i64(cp), D._i64(rv), D._f64(nz), int(VankaType), D._f64(wv), nw,
+                                                                            C.byref(self.h)), "mg_vanka_create_built")
+            return
+        blk = np.asfortranarray(Dblk, dtype=np.complex64 if self.cx else np.float32)
+        D._check(lib, getattr(lib, f"mg_vanka_create_{sfx}")(0, nn.size, D._i64(nn), 1 if includePressure else 0, A.shape[0], D._i64(cp),
+                                                             D._i64(rv), D._f64(nz), blk.ctypes.data_as(_fp), C.byref(self.h)), "mg_vanka_create")
 
     def info(self):
         return vanka_info(self.h)
+
+    def build_blocks(self, w, VankaType: int = FULL_VANKA_RB):
+        """The handle's blocks again from its resident operator (mg_vanka_build_blocks_*): ``w`` a float or a pair.  A singular
+        cell raises ``np.linalg.LinAlgError`` and the handle keeps the blocks it had."""
+        lib = D.load_library()
+        wv, nw = _w_pair(w)
+        fn = lib.mg_vanka_build_blocks_CFP64 if self.cx else lib.mg_vanka_build_blocks_FP64
+        _check_build(lib, fn(self.h, int(VankaType), D._f64(wv), nw), "mg_vanka_build_blocks")
+
+    def replace_values(self, A):
+        """New values of the operator on the uploaded pattern (mg_vanka_replace_values_*); the blocks stay until ``build_blocks``."""
+        A = A if sp.isspmatrix_csr(A) and A.has_sorted_indices else _sorted_csr(A)
+        if A.shape != (self.N, self.N) or A.nnz != self.nnz:
+            raise ValueError("replace_values takes an operator of the uploaded pattern")
+        if np.iscomplexobj(A.data) and not self.cx:
+            raise TypeError("complex values for a handle of a real operator")
+        lib = D.load_library()
+        nz = np.ascontiguousarray(A.data, dtype=np.complex128 if self.cx else np.float64)
+        fn = lib.mg_vanka_replace_values_CFP64 if self.cx else lib.mg_vanka_replace_values_FP64
+        D._check(lib, fn(self.h, D._f64(nz), nz.size), "mg_vanka_replace_values")
+
+    def blocks(self):
+        """The handle's blocks as setupVankaFacesPreconditioner returns them: (bs^2, cells), float32 / complex64, column-major."""
+        lib = D.load_library()
+        bs = getVankaBlockSize(np.asarray(self.n), self.includePressure)[0]
+        out = np.zeros((bs * bs, int(np.prod(self.n))), dtype=np.complex64 if self.cx else np.float32, order="F")
+        D._check(lib, lib.mg_vanka_get_blocks(self.h, out.ctypes.data_as(_fp), out.size), "mg_vanka_get_blocks")
+        return out
 
     def apply_dev(self, x, b, numit: int, VankaType: int = FULL_VANKA_RB):
         """``numit`` iterations on torch device tensors, x in place, waited for: 1-D vectors (mg_vanka_apply_dev_*) or contiguous
@@ -270,9 +356,10 @@ class VankaHandle:
             pass
 
 
-def vanka_handle(A, Dblk, n, includePressure) -> VankaHandle:
-    """Upload operator and blocks once; the caller holds the handle and closes it."""
-    return VankaHandle(A, Dblk, _mesh_n(n), includePressure)
+def vanka_handle(A, Dblk, n, includePressure, w=None, VankaType: int = FULL_VANKA_RB) -> VankaHandle:
+    """Upload operator and blocks once; the caller holds the handle and closes it.  ``Dblk=None`` with ``w`` (and ``VankaType``):
+    the blocks are built on the device from the uploaded operator."""
+    return VankaHandle(A, Dblk, _mesh_n(n), includePressure, w=w, VankaType=VankaType)
 
 
 def _sorted_csr(A):
