@@ -152,7 +152,8 @@ int mg_replace_values_FP64(mg_hierarchy* h, long long level, long long which,
  * per level relaxPrecs[l] (relaxKind 0: Jac omega/diag, 1: SPAI omega*diag/colnorm^2; omega[l] per level) and the
  * Galerkin product As[l+1] = Ps[l]*As[l]*Rs[l] on the fixed patterns (rows of As[l+1] of any length: 2048 target columns
  * at a time; deterministic - the same sums in the same order on every run).  The coarsest factorisation stays on the host: fetch the
- * coarsest values (mg_get_values_FP64), factor, mg_set_coarse_dense_inverse_FP64, mg_finalize. */
+ * coarsest values (mg_get_values_FP64), factor, mg_set_coarse_dense_inverse_FP64, mg_finalize - unless the option
+ * "coarse_device_inverse" is set and a dense inverse installed: then it is rebuilt here, in HBM (mg_build_coarse_dense_inverse_FP64). */
 int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind,
                 const double* omega, long long* levels_done);
 int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
@@ -881,7 +882,8 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
  * option rap_groups sets how many rows of A a wavefront walks side by side, 1 being the order of mg_rap_FP64's kernel).  The
  * coarsest factorisation stays with the host, as for FP64: mg_get_values_CF64 of the coarsest level, factor, hand the solve
  * back (mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64), mg_finalize - except with the GMRES coarsest solve, whose
- * vector d is recomputed here from omega[nlevels - 1] (see mg_set_coarse_gmres_CF64): nothing is left to the host.  Also refused: a handle that is not
+ * vector d is recomputed here from omega[nlevels - 1] (see mg_set_coarse_gmres_CF64), and with the option "coarse_device_inverse" and a
+ * dense inverse installed, which is rebuilt here in HBM (mg_build_coarse_dense_inverse_CF64): nothing is left to the host.  Also refused: a handle that is not
  * finalized (MG_ERR_STATE), relaxKind other than 0 or 1 (MG_ERR_INVALID), any operator with 64-bit row pointers
  * (MG_ERR_UNSUPPORTED).  These checks of arguments and state precede the first write: after such a refusal the handle cycles
  * with its old values.  (A HIP error in the middle of the re-setup, MG_ERR_HIP, may leave some levels refreshed, as for FP64.)
@@ -902,6 +904,38 @@ mg_status mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n);
 mg_status mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
 mg_status mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n);
 mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz);
+
+/* ---- the explicit inverse of the coarsest operator built on the device (csrc/mg_dense_inv.hpp) ---------------------------------------------------------------
+ * A dense inverse with partial pivoting in HBM: blocked in-place Gauss-Jordan with row interchanges, panels of 64 columns, the
+ * trailing update an LDS-tiled FP64 GEMM.  Pivot of a column: the largest |re| + |im| (|a| for real values) among the eligible
+ * rows, ties to the lowest row, found by a two-stage reduction in a fixed order.  No atomics: a rerun gives the same bits.  Every
+ * stage is a launch of its own on one stream; the pivots and the singular flag stay in device memory and the host synchronises
+ * ONCE per inverse, when it reads the flag.  A zero or non-finite pivot: MG_ERR_INVALID, naming the column.
+ *
+ * mg_dense_inverse_FP64 / _CF64: stand-alone, on device `device`.  A: n x n column-major on the host (CF64: interleaved (re, im));
+ *   out receives inv(A) in the same layout (out may be A).  Checked ahead of the first device call: a null pointer or n < 1
+ *   MG_ERR_INVALID, n > 8192 MG_ERR_UNSUPPORTED.
+ * mg_build_coarse_dense_inverse_FP64 / _CF64: inv(As[nlevels]) from the coarsest operator resident on the handle, installed as
+ *   the coarsest solve - the state mg_set_coarse_dense_inverse_* leaves (a borrowed Schwarz handle detached, sparse factors
+ *   dropped, mg_finalize due).  The _CF64 form also takes CF32 handles, whose coarsest operator is widened to ComplexF64.  The
+ *   result is built into a spare buffer and exchanged with the installed inverse only when no pivot was flagged: a singular
+ *   operator (MG_ERR_INVALID) leaves the previous coarsest solve in place.  Refused ahead of the first write: a null handle
+ *   MG_ERR_INVALID, a handle of the other value type MG_ERR_STATE, a coarsest operator that was not uploaded MG_ERR_STATE, one
+ *   with 64-bit row pointers, a sharded handle, or more rows than the option "coarse_device_inverse_max" (default and at most
+ *   8192) MG_ERR_UNSUPPORTED.
+ * mg_get_coarse_dense_inverse_FP64 / _CF64: the installed inverse, column-major n x n, whoever installed it; MG_ERR_STATE when
+ *   the coarsest solve is not a dense inverse, MG_ERR_INVALID when n is not its order.
+ * With the option "coarse_device_inverse" set on the handle, mg_rap_FP64 / mg_rap_CF64 rebuild the inverse behind their last
+ *   Galerkin product, on the same stream and inside their one synchronisation, while the coarsest solve is a dense inverse:
+ *   nothing of the coarsest solve is left to the host, and no mg_finalize is due.  A singular new operator is their
+ *   MG_ERR_INVALID: the operators then hold the new values and the coarsest solve the previous inverse.
+ *   mg_coarse_form keeps reporting kind 0. */
+mg_status mg_dense_inverse_FP64(long long device, long long n, const double* A, double* out);
+mg_status mg_dense_inverse_CF64(long long device, long long n, const double* A, double* out);
+mg_status mg_build_coarse_dense_inverse_FP64(mg_hierarchy* h);
+mg_status mg_build_coarse_dense_inverse_CF64(mg_hierarchy* h);
+mg_status mg_get_coarse_dense_inverse_FP64(mg_hierarchy* h, long long n, double* out);
+mg_status mg_get_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, double* out);
 
 /* ---- adjointHierarchy on a complex handle (transposeHierarchy for complex VAL, MGsetup.jl:274-318) ----------------------------
  * The flip between the forward system A x = b and the adjoint system A' x = b (A' = conj(A)^T, Julia's `'`) that an inversion

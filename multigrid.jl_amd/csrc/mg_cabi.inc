@@ -76,6 +76,34 @@ int use_device(long long device_id) {
   HIP_TRY(hipSetDevice((int)device_id));
   return MG_OK;
 }
+// The explicit inverse of the resident coarsest operator, built in HBM (mg_dense_inv.hpp) (mg_build_coarse_dense_inverse_FP64, mg_rap_FP64).
+// coarse_inverse_check: what is refused before the first write; coarse_inverse_finish (behind the caller's synchronisation): the
+// flag read, the spare buffer exchanged with Ainv when it is clean.
+int coarse_inverse_check(mg_hierarchy* h) {
+  if (h->ghost) return fail(MG_ERR_UNSUPPORTED, "the device inverse is not served for a sharded hierarchy");
+  const Csr& A = h->lev[(size_t)h->nlevels - 1].A;
+  if (!A.set) return fail(MG_ERR_STATE, "the coarsest operator was not uploaded");
+  if (A.wide) return fail(MG_ERR_UNSUPPORTED, "the coarsest operator holds 64-bit row pointers: the device inverse serves int32 operators");
+  if (A.n_rows != A.n_cols) return fail(MG_ERR_INVALID, "the coarsest operator is %lld x %lld", A.n_rows, A.n_cols);
+  if (A.n_rows > dense_inv_max(h->opt))
+    return fail(MG_ERR_UNSUPPORTED, "the coarsest operator has %lld rows: the device inverse serves up to %lld (option coarse_device_inverse_max)",
+                A.n_rows, dense_inv_max(h->opt));
+  return MG_OK;
+}
+int coarse_inverse_finish(mg_hierarchy* h, DenseInv<double>& K, DevBuf<double>& spare, const char* who) {
+  int col = 0;
+  const int rc = K.singular_column(&col);
+  if (rc != MG_OK || col != 0) {
+    spare.release();
+    return rc != MG_OK ? rc
+                       : fail(MG_ERR_INVALID, "%s: the coarsest operator is singular to working precision (zero or non-finite pivot in column %d): the previous inverse stays",
+                              who, col);
+  }
+  std::swap(h->Ainv, spare);
+  spare.release();
+  return MG_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -114,9 +142,11 @@ int mg_create(long long nlevels, long long nrhs, long long device_id, mg_hierarc
 }
 
 // replaceMatrixInHierarchy on the device (MGsetup.jl:226-270): new fine values (same sparsity), then per level
-// relaxPrecs[l] = getRelaxPrec(As[l]) and As[l+1] = Ps[l]*As[l]*Rs[l] on the fixed patterns.  The coarsest
-// factorisation stays with the host: fetch the coarsest values with mg_get_values_FP64, factor, hand the
-// inverse back with mg_set_coarse_dense_inverse_FP64 and call mg_finalize.
+// relaxPrecs[l] = getRelaxPrec(As[l]) and As[l+1] = Ps[l]*As[l]*Rs[l] on the fixed patterns.  With the option
+// coarse_device_inverse and a dense inverse installed, the new coarsest operator's inverse is built in HBM behind the
+// last Galerkin product, inside the same synchronisation (mg_dense_inv.hpp; a singular operator is an error return
+// and the previous inverse stays).  Otherwise the coarsest factorisation stays with the host: fetch the coarsest
+// values with mg_get_values_FP64, factor, hand the inverse back with mg_set_coarse_dense_inverse_FP64 and call mg_finalize.
 int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind,
                 const double* omega, long long* levels_done) {
   MG_CF64_UNSUPPORTED(h);
@@ -133,6 +163,8 @@ int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   for (int l = 0; l < nl; ++l)
     if (h->lev[(size_t)l].A.wide || h->lev[(size_t)l].P.wide || h->lev[(size_t)l].R.wide)
       return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers (>= 2^31 non-zeros): the numeric Galerkin product on the device serves int32 operators", l + 1);
+  const bool dev_inverse = h->opt.coarse_device_inverse && h->coarse_set && !h->coarse_lu && !h->coarse_gmres && !h->coarse_dd && h->Ainv.p;
+  if (dev_inverse) MG_TRY(coarse_inverse_check(h));
   HIP_TRY(spin_sync(h->play->stream));
   HIP_TRY(hipMemcpyAsync(L0.A.val.p, fine_nzval, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, h->play->stream));
   for (int l = 0; l + 1 < nl; ++l) {
@@ -151,7 +183,20 @@ int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
                        C.A.rowptr.p, C.A.colidx.p, C.A.val.p, (int)std::max<long long>(1, std::min<long long>(h->opt.rap_chunk, mgk::RAP_CAP)));
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(spin_sync(h->play->stream));
+  DenseInv<double> inv;      // option coarse_device_inverse: the new coarsest operator's inverse, into a spare buffer (exchanged below)
+  DevBuf<double> inv_spare;
+  int inv_rc = MG_OK;
+  if (dev_inverse) {
+    const Csr& Ac = h->lev[(size_t)nl - 1].A;
+    inv_rc = coarse_inverse_enqueue<double, double>(inv, inv_spare, Ac.n_rows, Ac.rowptr.p, Ac.colidx.p, Ac.val.p, h->play->stream);
+  }
+  const hipError_t synced = spin_sync(h->play->stream);
+  if (synced != hipSuccess || inv_rc != MG_OK) {
+    inv_spare.release();
+    if (inv_rc != MG_OK) return inv_rc;
+    HIP_TRY(synced);
+  }
+  if (dev_inverse) inv_rc = coarse_inverse_finish(h, inv, inv_spare, "mg_rap_FP64");
   // row-class dictionaries follow the new values (coarse values come back from HBM; rap_numeric adds every entry in a
   // fixed order, so rows that were bit-identical before a constant-coefficient update still are afterwards)
   MG_TRY(refresh_rowclasses(&L0.A, fine_nzval));
@@ -169,7 +214,7 @@ int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     MG_TRY(build_band27(h->lev[(size_t)l].A, h->lev[(size_t)l].grid));   // (the planar values follow the new ones: one fill kernel)
   }
   if (levels_done) *levels_done = nl - 1;
-  return MG_OK;
+  return inv_rc;   // (a singular coarsest operator: the operators hold the new values, the coarsest solve the previous inverse)
 }
 
 int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz) {
@@ -401,6 +446,49 @@ int mg_set_coarse_dense_inverse_FP64(mg_hierarchy* h, long long n, const double*
   h->coarse_gmres = false;
   h->finalized = false;
   return MG_OK;
+}
+
+int mg_build_coarse_dense_inverse_FP64(mg_hierarchy* h) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  MG_REAL_ONLY(h);
+  MG_TRY(coarse_inverse_check(h));
+  graphs_clear(h);
+  (void)hipSetDevice(h->device);
+  const Csr& A = h->lev[(size_t)h->nlevels - 1].A;
+  DenseInv<double> K;
+  DevBuf<double> spare;
+  int rc = coarse_inverse_enqueue<double, double>(K, spare, A.n_rows, A.rowptr.p, A.colidx.p, A.val.p, h->play->stream);
+  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_build_coarse_dense_inverse_FP64: stream failed");
+  if (rc != MG_OK) {
+    spare.release();
+    return rc;
+  }
+  MG_TRY(coarse_inverse_finish(h, K, spare, "mg_build_coarse_dense_inverse_FP64"));
+  dd_detach(h);
+  h->n_coarse = A.n_rows;
+  h->coarse_set = true;
+  h->coarse_lu = false;
+  h->coarse_gmres = false;
+  h->finalized = false;
+  return MG_OK;
+}
+
+int mg_get_coarse_dense_inverse_FP64(mg_hierarchy* h, long long n, double* out) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  MG_REAL_ONLY(h);
+  if (!out) return fail(MG_ERR_INVALID, "null argument");
+  if (!h->coarse_set || h->coarse_lu || h->coarse_gmres || h->coarse_dd || !h->Ainv.p)
+    return fail(MG_ERR_STATE, "the coarsest solve of this handle is not a dense inverse");
+  if (n != h->n_coarse) return fail(MG_ERR_INVALID, "n=%lld differs from the coarsest order %lld", n, h->n_coarse);
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));
+  return dense_inverse_readback<1>(h->Ainv, n, out);
+}
+
+int mg_dense_inverse_FP64(long long device, long long n, const double* A, double* out) {
+  MG_TRY(dense_inverse_args(n, A, out, "mg_dense_inverse_FP64"));
+  MG_TRY(use_device(device));
+  return dense_inverse_host<double>(n, A, out, "mg_dense_inverse_FP64");
 }
 
 // Coarsest solve from sparse LU factors in the layout of the reference's native applier (deps/src/parLU.cpp:120-190;

@@ -2167,6 +2167,88 @@ int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double*
   return MG_OK;
 }
 
+// The explicit inverse of the resident coarsest operator, built in HBM (mg_dense_inv.hpp) - the device twin of the setter above.
+// cx_coarse_inverse_check: what is refused before the first write; cx_coarse_inverse_enqueue: the launches on the handle's stream
+// into `spare`; cx_coarse_inverse_finish (behind the caller's synchronisation): the flag read, `spare` exchanged with Ainv when clean.
+static int cx_coarse_inverse_check(mg_hierarchy* h) {
+  CxState& S = *h->cx;
+  const CxMat& A = S.lev[(size_t)h->nlevels - 1].A;
+  if (!A.set) return fail(MG_ERR_STATE, "the coarsest operator was not uploaded");
+  if (A.wide) return fail(MG_ERR_UNSUPPORTED, "the coarsest operator holds 64-bit row pointers: the device inverse serves int32 operators");
+  if (A.n_rows != A.n_cols) return fail(MG_ERR_INVALID, "the coarsest operator is %lld x %lld", A.n_rows, A.n_cols);
+  if (A.n_rows > dense_inv_max(h->opt))
+    return fail(MG_ERR_UNSUPPORTED, "the coarsest operator has %lld rows: the device inverse serves up to %lld (option coarse_device_inverse_max)",
+                A.n_rows, dense_inv_max(h->opt));
+  return MG_OK;
+}
+static int cx_coarse_inverse_enqueue(mg_hierarchy* h, DenseInv<cx_t>& K, DevBuf<double>& spare) {
+  const CxMat& A = h->cx->lev[(size_t)h->nlevels - 1].A;
+  const hipStream_t st = h->play->stream;
+  if (A.single)   // (a CF32 handle's coarsest operator, widened as the host does with astype(complex128))
+    return coarse_inverse_enqueue<cx_t, cf_t>(K, spare, A.n_rows, A.rowptr.p, A.colidx.p, reinterpret_cast<const cf_t*>(A.valf.p), st);
+  return coarse_inverse_enqueue<cx_t, cx_t>(K, spare, A.n_rows, A.rowptr.p, A.colidx.p, reinterpret_cast<const cx_t*>(A.val.p), st);
+}
+static int cx_coarse_inverse_finish(mg_hierarchy* h, DenseInv<cx_t>& K, DevBuf<double>& spare, const char* who) {
+  int col = 0;
+  const int rc = K.singular_column(&col);
+  if (rc != MG_OK || col != 0) {
+    spare.release();
+    return rc != MG_OK ? rc
+                       : fail(MG_ERR_INVALID, "%s: the coarsest operator is singular to working precision (zero or non-finite pivot in column %d): the previous inverse stays",
+                              who, col);
+  }
+  std::swap(h->cx->Ainv, spare);
+  spare.release();
+  return MG_OK;
+}
+
+int mg_build_coarse_dense_inverse_CF64(mg_hierarchy* h) {
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));   // (a CF32 handle's coarsest solve stays ComplexF64)
+  MG_TRY(cx_coarse_inverse_check(h));
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  DenseInv<cx_t> K;
+  DevBuf<double> spare;
+  int rc = cx_coarse_inverse_enqueue(h, K, spare);
+  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_build_coarse_dense_inverse_CF64: stream failed");
+  if (rc != MG_OK) {
+    spare.release();
+    return rc;
+  }
+  MG_TRY(cx_coarse_inverse_finish(h, K, spare, "mg_build_coarse_dense_inverse_CF64"));
+  dd_detach(h);
+  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+  for (DevBuf<int>* q : {&S.luLptr, &S.luLcol, &S.luUptr, &S.luUcol, &S.luP, &S.luQ, &S.luLorder, &S.luLlvl, &S.luUorder, &S.luUlvl}) q->release();
+  S.luLval.release(); S.luUval.release(); S.luWork.release();
+  S.n_coarse = S.lev[(size_t)h->nlevels - 1].A.n_rows;
+  S.coarse_set = true;
+  S.coarse_lu = false;
+  S.coarse_gmres = false;
+  S.finalized = false;
+  return MG_OK;
+}
+
+int mg_get_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, double* out) {
+  MG_TRY(cx_level_ok(h, 1, CX_ANY));
+  if (!out) return fail(MG_ERR_INVALID, "null argument");
+  CxState& S = *h->cx;
+  if (!S.coarse_set || S.coarse_lu || S.coarse_gmres || h->coarse_dd || !S.Ainv.p)
+    return fail(MG_ERR_STATE, "the coarsest solve of this handle is not a dense inverse");
+  if (n != S.n_coarse) return fail(MG_ERR_INVALID, "n=%lld differs from the coarsest order %lld", n, S.n_coarse);
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));
+  return dense_inverse_readback<2>(S.Ainv, n, out);
+}
+
+int mg_dense_inverse_CF64(long long device, long long n, const double* A, double* out) {
+  MG_TRY(dense_inverse_args(n, A, out, "mg_dense_inverse_CF64"));
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(MG_ERR_INVALID, "device=%lld but %d devices visible", device, ndev);
+  HIP_TRY(hipSetDevice((int)device));
+  return dense_inverse_host<cx_t>(n, A, out, "mg_dense_inverse_CF64");
+}
+
 int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* Lptr, const long long* Lcol, const double* Lval,
                                 const long long* Uptr, const long long* Ucol, const double* Uval, const long long* p,
                                 const long long* q) {
@@ -2383,7 +2465,10 @@ int mg_block_solve_CF64(mg_hierarchy* h, const double* B, double* X, long long n
 
 // replaceMatrixInHierarchy on the device (MGsetup.jl:226-270) for VAL = ComplexF64: new fine values on the stored pattern, then per
 // level relaxPrecs[l] = getRelaxPrec(As[l]) and As[l+1] = Rs[l]*(As[l]*Ps[l]) on the fixed patterns.  Generic CSR has no derived
-// formats to rebuild.  The coarsest factorisation stays with the host: mg_get_values_CF64 of the coarsest level, factor,
+// formats to rebuild.  The coarsest solve: with the option coarse_device_inverse and a dense inverse installed, the inverse of the new
+// coarsest operator is built in HBM behind the last Galerkin product (mg_dense_inv.hpp), on the same stream and inside the call's one
+// synchronisation - a singular operator is an error return and the previous inverse stays; the GMRES coarsest solve recomputes its
+// Jacobi vector there.  Otherwise the factorisation stays with the host: mg_get_values_CF64 of the coarsest level, factor,
 // mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64, mg_finalize.  The checks of arguments and state precede the first write.
 int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind, const double* omega,
                 long long* levels_done) {
@@ -2410,6 +2495,8 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     if (L.A.wide || (l + 1 < nl && (L.P.wide || L.R.wide)))
       return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers: the numeric Galerkin product on the device serves int32 operators", l + 1);
   }
+  const bool dev_inverse = h->opt.coarse_device_inverse && S.coarse_set && !S.coarse_lu && !S.coarse_gmres && !h->coarse_dd && S.Ainv.p;
+  if (dev_inverse) MG_TRY(cx_coarse_inverse_check(h));
   (void)hipSetDevice(h->device);
   const hipStream_t st = h->play->stream;
   if (relaxKind == 1)
@@ -2452,8 +2539,17 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(S.rap_ev[(size_t)nl - 1], st));
-  HIP_TRY(spin_sync(st));
+  DenseInv<cx_t> inv;        // option coarse_device_inverse: the new coarsest operator's inverse, into a spare buffer (exchanged below)
+  DevBuf<double> inv_spare;
+  int inv_rc = dev_inverse ? cx_coarse_inverse_enqueue(h, inv, inv_spare) : MG_OK;
+  const hipError_t synced = spin_sync(st);
+  if (synced != hipSuccess || inv_rc != MG_OK) {
+    inv_spare.release();
+    if (inv_rc != MG_OK) return inv_rc;
+    HIP_TRY(synced);
+  }
   S.rap_timed = true;
+  if (dev_inverse) inv_rc = cx_coarse_inverse_finish(h, inv, inv_spare, "mg_rap_CF64");
   if (vanka) {   // a singular cell anywhere: no level's blocks are exchanged (the operators hold the new values; the blocks the old ones)
     int bad = 0, first = 0;
     for (int l = 0; l + 1 < nl; ++l) {
@@ -2470,7 +2566,7 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     }
   }
   if (levels_done) *levels_done = nl - 1;
-  return MG_OK;
+  return inv_rc;   // (a singular coarsest operator: the operators hold the new values, the coarsest solve the previous inverse)
 }
 
 // Device time of the last mg_rap_CF64, level by level (relaxPrecs[l] and As[l+1] together), in milliseconds: out[0 .. nlevels-1).

@@ -157,6 +157,10 @@ bool host_all_zero(const double* x, long long len) {
   X(bool, vanka_device_setup, false)       /* complex Vanka hierarchies whose blocks were built on the device (mg_build_vanka_CF64): \
                                               mg_rap_CF64 recomputes the operators and rebuilds the blocks in HBM; 0: it refuses a \
                                               Vanka handle, as before the device build existed; read at every call */ \
+  X(bool, coarse_device_inverse, false)     /* the explicit inverse of the coarsest operator is built in HBM (mg_build_coarse_dense_inverse_*): \
+                                              mg_rap_FP64 / mg_rap_CF64 rebuild it behind the last Galerkin product while the coarsest solve is \
+                                              a dense inverse; 0: they leave it to the host, as before the device build existed; read at every call */ \
+  X(long long, coarse_device_inverse_max, 8192)   /* largest order the device build serves (at most 8192: work matrix plus result 2 x 1.07 GB complex) */ \
   X(long long, lu_dense_tail_min, 64) \
   X(long long, lu_dense_tail_max, 16384)   /* largest trailing block kept as an explicit inverse (8*M^2 bytes each for L and U: 2 x 2.1 GB) */ \
   X(double, rowclass_min_cover, 0.9) \

@@ -40,6 +40,7 @@
 #include "mg_cxblk_coarse.hpp"
 #include "mg_dd.hpp"
 #include "mg_vanka.hpp"
+#include "mg_dense_inv.hpp"
 #include "mg_krylov_host.hpp"   // host only: KrylovReport, HessenbergLsq, RelaxLsq / pinv_sym, SmallMat / sm_*
 
 
@@ -52,6 +53,7 @@
 #include "mg_schedule.inc"   // FGMRES relaxation, cycle_level, HIP graphs, solve loop
 #include "mg_krylov.inc"     // PCG / BiCGSTAB / FGMRES and block variants
 #include "mg_formats.inc"    // upload, format builders, scratch
+#include "mg_dense_inv.inc"  // the dense inverse with partial pivoting on the device: work set, chain of launches
 #include "mg_complex.inc"    // ComplexF64 hierarchies: generic-CSR kernels' launchers, cycle, solve, and their extern "C" entry points
 #include "mg_complex_krylov.inc"   // extern "C": ComplexF64 BiCGSTAB / FGMRES on a system operator of their own, their fused vector passes
 #include "mg_cabi.inc"       // extern "C": the single-GPU API and its ghost-layer form (mg_ghost_*)

@@ -44,6 +44,12 @@ SIGNATURES = {
     "mg_set_grid_hint": (C.c_int, [_vp, _ll, _ll, _ll, _ll]),
     "mg_set_option": (C.c_int, [_vp, C.c_char_p, C.c_double]),
     "mg_set_coarse_dense_inverse_FP64": (C.c_int, [_vp, _ll, _dp]),
+    "mg_build_coarse_dense_inverse_FP64": (C.c_int, [_vp]),
+    "mg_build_coarse_dense_inverse_CF64": (C.c_int, [_vp]),
+    "mg_get_coarse_dense_inverse_FP64": (C.c_int, [_vp, _ll, _dp]),
+    "mg_get_coarse_dense_inverse_CF64": (C.c_int, [_vp, _ll, _dp]),
+    "mg_dense_inverse_FP64": (C.c_int, [_ll, _ll, _dp, _dp]),
+    "mg_dense_inverse_CF64": (C.c_int, [_ll, _ll, _dp, _dp]),
     "mg_graph_launches": (C.c_int, [_vp, _lp, _lp]),
     "mg_set_coarse_lu_FP64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
     "mg_set_coarse_gmres_FP64": (C.c_int, [_vp, _ll, _dp]),
@@ -346,6 +352,28 @@ def _sync_torch(*tensors):
 
 
 DENSE_COARSE_MAX = 16384
+MG_ERR_INVALID = 1
+MG_ERR_UNSUPPORTED = 4
+
+
+def dense_inverse(A, device: int = 0) -> np.ndarray:
+    """inv(A) of a dense float64 or complex128 matrix of order <= 8192 on the device (mg_dense_inverse_FP64 / _CF64): partial
+    pivoting, one host synchronisation, the same bits on every run.  A singular matrix (a zero or non-finite pivot) raises
+    ``np.linalg.LinAlgError``, as ``np.linalg.inv`` does; every other refusal is an MGDeviceError."""
+    A = np.asarray(A)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("dense_inverse takes a square matrix")
+    cx = np.iscomplexobj(A)
+    Af = np.asfortranarray(A, dtype=np.complex128 if cx else np.float64)
+    out = np.zeros_like(Af, order="F")
+    lib = load_library()
+    what = "mg_dense_inverse_CF64" if cx else "mg_dense_inverse_FP64"
+    rc = getattr(lib, what)(int(device), Af.shape[0], Af.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
+    if rc == MG_ERR_INVALID and Af.shape[0] >= 1:
+        msg = lib.mg_last_error()
+        raise np.linalg.LinAlgError(f"{what}: {msg.decode() if msg else 'singular matrix'}")
+    _check(lib, rc, what)
+    return out
 BLOCK_KMAX = 16                  # columns of a complex block of right-hand sides (mgk::BLK_KMAX)
 
 
@@ -498,6 +526,7 @@ class DeviceHierarchy:
         import scipy.sparse as sp
         lib = self.lib
         nc = int(param.As[-1].shape[0])
+        self._coarse_device_inverse = False
         if self._set_coarse_solver(param):
             return
         if param.coarseSolveType == "GMRES":                            # param.LU = relaxParam ./ diag(A_c)
@@ -505,6 +534,8 @@ class DeviceHierarchy:
             _check(lib, lib.mg_set_coarse_gmres_FP64(self.handle, nc, _f64(d)), "mg_set_coarse_gmres")
             return
         if nc <= DENSE_COARSE_MAX and not force_sparse:
+            if self._build_coarse_inverse(param):                       # coarseDeviceInverse: inv(As[end]) built in HBM
+                return
             Ainv = np.asfortranarray(param.LU.solve(np.eye(nc)))        # LU \ I, column-major
             _check(lib, lib.mg_set_coarse_dense_inverse_FP64(self.handle, nc, _f64(Ainv)), "mg_set_coarse_dense_inverse")
             return
@@ -522,6 +553,38 @@ class DeviceHierarchy:
                                                     _f64(Uv), _i64(p), _i64(q)), "mg_set_coarse_lu")
 
     _coarse_dd = None        # the DomainDecompositionParam whose device handle this hierarchy borrows as its coarsest solve
+    _coarse_device_inverse = False     # the installed dense inverse was built on the device (a param with coarseDeviceInverse=True)
+    _inverse_sfx = "FP64"
+
+    def _build_coarse_inverse(self, param) -> bool:
+        """A param with ``coarseDeviceInverse=True`` whose coarsest solve is a dense inverse: set the handle's option
+        coarse_device_inverse (mg_rap_* then rebuild the inverse in HBM) and build inv(As[end]) from the resident operator
+        (mg_build_coarse_dense_inverse_*).  False - and the option cleared - where the param did not ask or the library does not
+        serve the operator (MG_ERR_UNSUPPORTED: more than coarse_device_inverse_max rows, 64-bit row pointers): the caller takes
+        the host route.  ``_coarse_device_inverse`` records which route ran."""
+        lib = self.lib
+        self._coarse_device_inverse = False
+        if not getattr(param, "coarseDeviceInverse", False):
+            return False
+        _check(lib, lib.mg_set_option(self.handle, b"coarse_device_inverse", 1.0), "mg_set_option(coarse_device_inverse)")
+        what = f"mg_build_coarse_dense_inverse_{self._inverse_sfx}"
+        rc = getattr(lib, what)(self.handle)
+        if rc == MG_ERR_UNSUPPORTED:
+            _check(lib, lib.mg_set_option(self.handle, b"coarse_device_inverse", 0.0), "mg_set_option(coarse_device_inverse)")
+            return False
+        _check(lib, rc, what)
+        self._coarse_device_inverse = True
+        return True
+
+    def coarse_dense_inverse(self) -> np.ndarray:
+        """The installed explicit inverse of the coarsest operator (mg_get_coarse_dense_inverse_*), n_c x n_c, whichever route
+        installed it; MGDeviceError when the coarsest solve is not a dense inverse."""
+        cx = self._inverse_sfx == "CF64"
+        nc = int(self.coarse_form()["order"])
+        out = np.zeros((nc, nc), dtype=np.complex128 if cx else np.float64, order="F")
+        what = f"mg_get_coarse_dense_inverse_{self._inverse_sfx}"
+        _check(self.lib, getattr(self.lib, what)(self.handle, nc, out.ctypes.data_as(_dp)), what)
+        return out
 
     def _set_coarse_solver(self, param) -> bool:
         """param.LU a solver object (MGsetup.jl:323-331, MGcycle.jl:138-148): a DomainDecompositionParam is attached as one
@@ -596,7 +659,8 @@ class DeviceHierarchy:
 
     def replace_matrix(self, param, A_new) -> None:
         """replaceMatrixInHierarchy on the device: numeric Galerkin products + relaxPrecs on the fixed patterns
-        (mg_rap_FP64), host copies of the hierarchy refreshed from HBM, coarsest level re-factored on the host."""
+        (mg_rap_FP64), host copies of the hierarchy refreshed from HBM, coarsest level re-factored on the host (a param with
+        ``coarseDeviceInverse=True``: its explicit inverse is rebuilt in HBM by mg_rap_FP64; the host keeps its splu)."""
         import scipy.sparse as sp
         import scipy.sparse.linalg as spla
         lib = self.lib
@@ -618,9 +682,11 @@ class DeviceHierarchy:
             _check(lib, lib.mg_get_relax_FP64(self.handle, l, _f64(d), d.size), "mg_get_relax")
             param.relaxPrecs[l - 1] = d
         from .mgsetup import defineCoarsestAinv
-        defineCoarsestAinv(param, param.As[-1])                      # (MGsetup.jl:323-355)
-        self._set_coarse(param)
-        _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        defineCoarsestAinv(param, param.As[-1])                      # (MGsetup.jl:323-355; param.LU stays the host's factorisation)
+        if not self._coarse_device_inverse:
+            self._set_coarse(param)
+            _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        # (coarseDeviceInverse: mg_rap_FP64 has rebuilt the inverse in HBM behind its last Galerkin product - nothing uploaded)
 
     def close(self):
         if self.handle:
@@ -1151,6 +1217,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         lib = self.lib
         nc = int(param.As[-1].shape[0])
         self._coarse_gmres = False
+        self._coarse_device_inverse = False
         if self._set_coarse_solver(param):
             return
         if param.coarseSolveType == "GMRES":                            # param.LU = relaxParam ./ diag(A_c)  (MGsetup.jl:335-336)
@@ -1162,6 +1229,8 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             self._coarse_gmres = True
             return
         if nc <= DENSE_COARSE_MAX and not force_sparse:
+            if self._build_coarse_inverse(param):                       # coarseDeviceInverse: inv(As[end]) built in HBM
+                return
             Ainv = np.asfortranarray(param.LU.solve(np.eye(nc, dtype=np.complex128)), dtype=np.complex128)
             _check(lib, lib.mg_set_coarse_dense_inverse_CF64(self.handle, nc, _c128(Ainv)), "mg_set_coarse_dense_inverse_CF64")
             return
@@ -1295,6 +1364,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     _krylov_operator = None
     _krylov_pattern = None                      # (shape, indptr, indices) of the operator uploaded last
+    _inverse_sfx = "CF64"                       # (mg_build / mg_get_coarse_dense_inverse_CF64 serve CF32 handles too)
 
     @property
     def krylov_operator(self):
@@ -1527,7 +1597,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     def replace_matrix(self, param, A_new, timings: Optional[dict] = None) -> None:
         """replaceMatrixInHierarchy on the device, the complex twin of DeviceHierarchy.replace_matrix: numeric Galerkin products
         and relaxPrecs on the fixed patterns (mg_rap_CF64), host copies of the hierarchy refreshed from HBM, coarsest level
-        re-factored on the host (with coarseSolveType='GMRES' there is nothing to factor: its Jacobi vector is recomputed in HBM).  ``timings`` (a dict) receives the seconds of the three parts."""
+        re-factored on the host (with coarseSolveType='GMRES' there is nothing to factor: its Jacobi vector is recomputed in HBM;
+        a param with ``coarseDeviceInverse=True``: the explicit inverse is rebuilt in HBM by mg_rap_CF64 and ``coarsest`` is the
+        host's splu alone).  ``timings`` (a dict) receives the seconds of the three parts."""
         import time
         lib = self.lib
         t0 = time.perf_counter()
@@ -1563,9 +1635,11 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         t2 = time.perf_counter()
         from .mgsetup import defineCoarsestAinv
         defineCoarsestAinv(param, param.As[-1])                      # (MGsetup.jl:323-355)
-        if not getattr(self, "_coarse_gmres", False):
+        if not getattr(self, "_coarse_gmres", False) and not self._coarse_device_inverse:
             self._set_coarse(param)
             _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
+        # (coarseDeviceInverse: mg_rap_CF64 has rebuilt the explicit inverse in HBM behind its last Galerkin product; param.LU above
+        #  stays the host's splu - nothing uploaded)
         # (GMRES coarsest solve: param.LU = relaxParam ./ diag(As[-1]) above is the host's copy; mg_rap_CF64 has recomputed the device's
         #  in HBM - no inverse, no factorisation, nothing uploaded)
         if timings is not None:

@@ -50,6 +50,7 @@ class MGparam:
     complexVanka: bool = False         # a Vanka relaxType on a complex hierarchy: the cell-block smoother in the complex cycle
     vankaBlocks: bool = False          # complexVanka only: serve blocks of right-hand sides by the block form of the smoother
     vankaDeviceSetup: bool = False     # complexVanka only: the cells' blocks are built (and, ComplexF64, refreshed) on the device
+    coarseDeviceInverse: bool = False  # the coarsest operator's explicit inverse is built (and refreshed) on the device
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -63,7 +64,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                coarseSolveType="NoMUMPS", strongConnParam=0.4, FilteringParam=0.0,
                transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
                blockCoarseGMRES: bool = False, complexVanka: bool = False, vankaBlocks: bool = False,
-               vankaDeviceSetup: bool = False) -> MGparam:
+               vankaDeviceSetup: bool = False, coarseDeviceInverse: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -87,6 +88,13 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     ``setupVankaFacesPreconditioner(..., device=True)`` (ordinary host arrays, as before), the upload builds every level's blocks in
     HBM from the resident operator instead of sending them, and ``replaceMatrixInHierarchy`` of a resident ComplexF64 param with
     an unchanged pattern recomputes operators and blocks in HBM and keeps the handle.  Without it nothing changes.
+    ``coarseDeviceInverse=True`` (keyword only; Float64 and ComplexF64, with or without ``singlePrecision``) builds the explicit
+    inverse of the coarsest operator on the device, from the operator resident there (a dense inverse with partial pivoting,
+    ``mg_build_coarse_dense_inverse_*``), instead of ``LU.solve(eye)`` on the host plus an upload; ``replaceMatrixInHierarchy`` of a
+    resident param then rebuilds it in HBM behind the Galerkin products.  ``param.LU`` stays the host's factorisation.  The flag
+    is a no-op where the coarsest solve is not a dense inverse of at most ``coarse_device_inverse_max`` (8192) rows: a solver
+    object in ``param.LU`` (Schwarz, parallelJuliaSolver) or a larger coarsest level take today's route.  With
+    ``coarseSolveType="GMRES"`` it is refused (there is no inverse to build).  Without it nothing changes.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
@@ -104,6 +112,9 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     if vankaDeviceSetup and not complexVanka:
         raise NotImplementedError("vankaDeviceSetup=True serves a complex Vanka hierarchy (complexVanka=True); FP64 Vanka hierarchies "
                                   "set their blocks up on the host")
+    if coarseDeviceInverse and str(coarseSolveType) == "GMRES":
+        raise NotImplementedError("coarseDeviceInverse=True builds the coarsest operator's explicit inverse: coarseSolveType='GMRES' "
+                                  "has none")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -118,7 +129,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    strongConnParam=float(strongConnParam), FilteringParam=float(FilteringParam),
                    transferOperatorType=str(transferOperatorType), singlePrecision=bool(singlePrecision),
                    blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka),
-                   vankaBlocks=bool(vankaBlocks), vankaDeviceSetup=bool(vankaDeviceSetup), VAL=np.dtype(VAL).type, IND=np.int64)
+                   vankaBlocks=bool(vankaBlocks), vankaDeviceSetup=bool(vankaDeviceSetup),
+                   coarseDeviceInverse=bool(coarseDeviceInverse), VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -191,7 +203,8 @@ def copySolver(MG: MGparam) -> MGparam:
                      MG.relaxType, MG.relaxParam, MG.relaxPre, MG.relaxPost, MG.cycleType, MG.coarseSolveType,
                      MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single,
                      blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka),
-                     vankaBlocks=bool(MG.vankaBlocks), vankaDeviceSetup=bool(MG.vankaDeviceSetup))
+                     vankaBlocks=bool(MG.vankaBlocks), vankaDeviceSetup=bool(MG.vankaDeviceSetup),
+                     coarseDeviceInverse=bool(MG.coarseDeviceInverse))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

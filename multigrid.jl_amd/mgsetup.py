@@ -307,7 +307,9 @@ def adjustMemoryForNumRHS(param: MGparam, nrhs: int = 1, verbose: bool = False) 
 
 
 def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
-    """New fine matrix, same P/R: recompute relaxPrecs, Galerkin products and the coarse LU (MGsetup.jl:226-270)."""
+    """New fine matrix, same P/R: recompute relaxPrecs, Galerkin products and the coarse LU (MGsetup.jl:226-270).  On a resident
+    param with ``coarseDeviceInverse=True`` the explicit inverse of the new coarsest operator is rebuilt in HBM (mg_rap_*); the
+    host still factors it (``param.LU``) and uploads nothing."""
     relaxParamArr = _relax_param_arr(param)
     A = _of_val(param, A)
     # (a ComplexF32 hierarchy is recomputed on the host and uploaded again: its device re-setup is out of scope)
