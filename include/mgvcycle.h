@@ -225,6 +225,35 @@ int mg_block_fgmres_dev_FP64(mg_hierarchy* h, const double* b_dev, double* x_dev
                              long long inner, double tol, long long maxIter, long long* iters, long long* flag,
                              double* resvec, long long* nres);
 
+/* ---- the real drivers' passes on their own (tests, callers with loops of their own) ------------------------------------------
+ * Each entry runs ONE vector or block pass of the drivers above through the helper the driver itself calls: the same kernel, grid,
+ * partial buffers and stream.  h: a finalized real FP64 handle whose drivers are not sharded (MG_ERR_STATE otherwise); n: the length
+ * of the caller's vectors, n >= 1 - it need not be the hierarchy's.  Null pointers, n < 1, k outside 1..16, i outside 0..63:
+ * MG_ERR_INVALID.  A refusal launches nothing and leaves the handle usable.  Vectors and blocks (row-major [n][k]) are device
+ * pointers; *_host arguments are host pointers, and an entry that fills one has drained the handle's stream when it returns.  The
+ * others enqueue on the handle's stream and return.
+ *   dot       *out_host = x'y                                norm      *out_host = ||x||_2
+ *   axpby     y = a x + b y ; y is not read when b == 0      cg_p      p = z + beta p
+ *   cg_update x += alpha p ; r -= alpha Ap ; with rnorm_host != NULL also *rnorm_host = ||r|| of the new r, from the same pass
+ *   mgs_step  w -= (*hk_dev) v ; *out_dev = w'u of the new w (u == NULL: w'w)
+ *   mgs_chain V: i + 2 vectors n apart, w = the last: h_k = w'V_k, w -= h_k V_k for k = 0..i in turn, then w /= ||w|| unless
+ *             ||w|| == 0; h_host receives h_0 .. h_i and ||w||^2 (i + 2 doubles) - the orthogonalisation of one FGMRES inner step
+ *   blk_gram  G_host (k x k row-major) = X'Y                 blk_comb  out = s add + in C_host (k x k row-major); add may be
+ *             NULL (then s is ignored); out may be in or add */
+int mg_kry_dot_dev_FP64(mg_hierarchy* h, const double* x_dev, const double* y_dev, long long n, double* out_host);
+int mg_kry_norm_dev_FP64(mg_hierarchy* h, const double* x_dev, long long n, double* out_host);
+int mg_kry_axpby_dev_FP64(mg_hierarchy* h, double a, const double* x_dev, double b, double* y_dev, long long n);
+int mg_kry_cg_update_dev_FP64(mg_hierarchy* h, double alpha, const double* p_dev, const double* Ap_dev, double* x_dev,
+                              double* r_dev, long long n, double* rnorm_host);
+int mg_kry_cg_p_dev_FP64(mg_hierarchy* h, double beta, const double* z_dev, double* p_dev, long long n);
+int mg_kry_mgs_step_dev_FP64(mg_hierarchy* h, const double* hk_dev, const double* v_dev, double* w_dev, const double* u_dev,
+                             long long n, double* out_dev);
+int mg_kry_mgs_chain_dev_FP64(mg_hierarchy* h, double* V_dev, long long n, long long i, double* h_host);
+int mg_kry_blk_gram_dev_FP64(mg_hierarchy* h, const double* X_dev, const double* Y_dev, long long n, long long k,
+                             double* G_host);
+int mg_kry_blk_comb_dev_FP64(mg_hierarchy* h, double* out_dev, const double* add_dev, double s, const double* in_dev,
+                             const double* C_host, long long n, long long k);
+
 /* Mixed-precision preconditioner hook of getMultigridPreconditioner (SolveFuncs.jl:52-58): a Float32 block against the
  * Float64 hierarchy - bl .= b; z .= 0; recursiveCycle(param,bl,z,1); z2 .= z.  Column-major n x nrhs host blocks. */
 int mg_cycle_mixed_FP32(mg_hierarchy* h, const float* b32, float* z32, long long n, long long nrhs);

@@ -67,6 +67,18 @@ int krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long n
   return MG_OK;
 }
 
+// One pass of the real drivers on the caller's vectors (mg_kry_*_dev_FP64): a finalized real FP64 handle whose drivers are not sharded
+// (MG_ERR_STATE otherwise), n >= 1 of the caller's choosing.  A refusal launches nothing.
+int kry_pass_ready(mg_hierarchy* h, long long n, const char* who) {
+  if (!h) return fail(MG_ERR_INVALID, "%s: null hierarchy handle", who);
+  if (h->cx) return fail(MG_ERR_STATE, "%s: FP64 entry point called on a complex handle", who);
+  if (!h->finalized) return fail(MG_ERR_STATE, "%s: hierarchy not finalized", who);
+  if (h->ghost) return fail(MG_ERR_STATE, "%s: this handle is one rank's part of a sharded hierarchy, its drivers' sums span all ranks", who);
+  if (n < 1) return fail(MG_ERR_INVALID, "%s: n=%lld", who, n);
+  (void)hipSetDevice(h->device);
+  return MG_OK;
+}
+
 // device_id a visible device, made current (the create entry points)
 int use_device(long long device_id) {
   int ndev = 0;
@@ -1064,6 +1076,68 @@ int mg_block_fgmres_FP64(mg_hierarchy* h, const double* b, double* x, long long 
   MG_CF64_UNSUPPORTED(h);
   return krylov(h, b, x, n, nrhs, maxIter, /*device_form=*/false,
                 [&](const double* bv, double* xv) { return block_fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
+}
+
+// ---- the real drivers' passes on their own: each entry runs ONE helper of the drivers above (mg_krylov.inc, mg_schedule.inc, mg_launch.inc)
+// on the caller's device vectors - the drivers' grids, partial buffers and stream, n of the caller's choosing ----------------------------
+int mg_kry_dot_dev_FP64(mg_hierarchy* h, const double* x, const double* y, long long n, double* out) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!x || !y || !out) return fail(MG_ERR_INVALID, "%s: null vector", __func__);
+  return dot_sync(h, x, y, n, out);
+}
+int mg_kry_norm_dev_FP64(mg_hierarchy* h, const double* x, long long n, double* out) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!x || !out) return fail(MG_ERR_INVALID, "%s: null vector", __func__);
+  return norm_sync(h, x, n, out);
+}
+int mg_kry_axpby_dev_FP64(mg_hierarchy* h, double a, const double* x, double b, double* y, long long n) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!x || !y) return fail(MG_ERR_INVALID, "%s: null vector", __func__);
+  return k_axpby(h, a, x, b, y, n);
+}
+int mg_kry_cg_update_dev_FP64(mg_hierarchy* h, double alpha, const double* p, const double* Ap, double* x, double* r, long long n,
+                              double* rnorm) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!p || !Ap || !x || !r) return fail(MG_ERR_INVALID, "%s: null vector", __func__);
+  return rnorm ? cg_update_norm(h, alpha, p, Ap, x, r, n, rnorm) : cg_update(h, alpha, p, Ap, x, r, n);
+}
+int mg_kry_cg_p_dev_FP64(mg_hierarchy* h, double beta, const double* z, double* p, long long n) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!z || !p) return fail(MG_ERR_INVALID, "%s: null vector", __func__);
+  return cg_direction(h, beta, z, p, n);
+}
+int mg_kry_mgs_step_dev_FP64(mg_hierarchy* h, const double* hk, const double* v, double* w, const double* u, long long n, double* out) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!hk || !v || !w || !out) return fail(MG_ERR_INVALID, "%s: null vector", __func__);
+  mgs_update(h, hk, v, w, u, n, out);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+int mg_kry_mgs_chain_dev_FP64(mg_hierarchy* h, double* V, long long n, long long i, double* h_host) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!V || !h_host) return fail(MG_ERR_INVALID, "%s: null vector", __func__);
+  if (i < 0 || i > 63) return fail(MG_ERR_INVALID, "%s: i=%lld outside 0..63", __func__, i);
+  MG_TRY(mgs_chain(h, V, n, (int)i, (size_t)i + 2));
+  std::memcpy(h_host, h->h_kscal, sizeof(double) * (size_t)(i + 2));
+  return MG_OK;
+}
+int mg_kry_blk_gram_dev_FP64(mg_hierarchy* h, const double* X, const double* Y, long long n, long long k, double* G_host) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!X || !Y || !G_host) return fail(MG_ERR_INVALID, "%s: null block", __func__);
+  if (k < 1 || k > mgk::BLK_KMAX) return fail(MG_ERR_INVALID, "%s: k=%lld outside 1..%d", __func__, k, mgk::BLK_KMAX);
+  SmallMat G;
+  MG_TRY(blk_gram(h, X, Y, n, (int)k, G));
+  std::memcpy(G_host, G.a.data(), sizeof(double) * (size_t)(k * k));
+  return MG_OK;
+}
+int mg_kry_blk_comb_dev_FP64(mg_hierarchy* h, double* out, const double* add, double s, const double* in, const double* C_host,
+                             long long n, long long k) {
+  MG_TRY(kry_pass_ready(h, n, __func__));
+  if (!out || !in || !C_host) return fail(MG_ERR_INVALID, "%s: null block", __func__);
+  if (k < 1 || k > mgk::BLK_KMAX) return fail(MG_ERR_INVALID, "%s: k=%lld outside 1..%d", __func__, k, mgk::BLK_KMAX);
+  SmallMat Cm((int)k, (int)k);
+  std::memcpy(Cm.a.data(), C_host, sizeof(double) * (size_t)(k * k));
+  return blk_comb(h, out, add, s, in, Cm, n, (int)k);
 }
 
 // Mixed-precision preconditioner hook (getMultigridPreconditioner, SolveFuncs.jl:52-58): the caller's block is Float32,

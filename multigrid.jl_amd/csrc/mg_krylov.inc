@@ -48,6 +48,61 @@ struct KrylovSpace {
   int done() { return ghs ? gh_check_depths(h) : (int)MG_OK; }
 };
 
+// ---- the drivers' own launches by name: pcg_dev and FgmresCore::arnoldi below and the entry points mg_kry_*_dev_FP64 (mg_cabi.inc) run
+// these, so the grid, the partial buffer and the stream of a pass are chosen in one place ------------------------------------------------
+// x += alpha p ; r -= alpha Ap
+int cg_update(mg_hierarchy* h, double alpha, const double* p, const double* Ap, double* x, double* r, long long n) {
+  hipLaunchKernelGGL(mgk::cg_update_xr, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, alpha, p, Ap, x, r, n);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+// the same with *rn = ||r|| of the new r out of the pass; synchronises the stream
+int cg_update_norm(mg_hierarchy* h, double alpha, const double* p, const double* Ap, double* x, double* r, long long n, double* rn) {
+  const int nb = (int)std::min<long long>(grid_for(n), (long long)h->play->partial.n);
+  hipLaunchKernelGGL(mgk::cg_update_xr_norm, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, alpha, p, Ap, x, r, n, h->play->partial.p);
+  launch_sum_final(h, h->play->partial.p, nb);
+  HIP_TRY(hipGetLastError());
+  return scalar_sync(h, rn);
+}
+// p = z + beta p
+int cg_direction(mg_hierarchy* h, double beta, const double* z, double* p, long long n) {
+  hipLaunchKernelGGL(mgk::cg_update_p, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, beta, z, p, n);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+// The chain dot -> update -> dot of modified Gram-Schmidt, every scalar in HBM.  mgs_blocks: the workgroups of each of its reductions;
+// mgs_dot: *out = x.y ; mgs_update: w -= (*hk) v, then *out = w.u (u == nullptr: w.w) from the same pass.  hk, out: device; no synchronisation.
+int mgs_blocks(mg_hierarchy* h, long long n) {
+  return (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n / 2 + mgk::BLK - 1) / mgk::BLK));
+}
+void mgs_dot(mg_hierarchy* h, const double* x, const double* y, long long n, double* out) {
+  const int nb = mgs_blocks(h, n);
+  hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, x, y, n, h->play->partial.p);
+  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, out);
+}
+void mgs_update(mg_hierarchy* h, const double* hk, const double* v, double* w, const double* u, long long n, double* out) {
+  const int nb = mgs_blocks(h, n);
+  hipLaunchKernelGGL(mgk::mgs_step, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, hk, v, w, u, n, h->play->partial.p);
+  hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, out);
+}
+// One inner step's orthogonalisation: V holds i + 2 vectors n apart, w = the last against V_0 .. V_i, then w /= ||w|| unless it vanished.
+// The i + 2 scalars (h_0 .. h_i, ||w||^2) come back in ONE readback: h->h_kscal, valid on return (the stream is drained).  slots: the
+// scalars the device column is sized for (the caller's m + 2 >= i + 2).
+int mgs_chain(mg_hierarchy* h, double* V, long long n, int i, size_t slots) {
+  if (h->kscal.n < slots) MG_TRY(h->kscal.alloc(slots));
+  if (!h->h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_kscal), sizeof(double) * 66));
+  double* w = V + (size_t)(i + 1) * n;
+  double* hd = h->kscal.p;
+  mgs_dot(h, w, V, n, hd);
+  for (int k = 0; k <= i; ++k)
+    mgs_update(h, hd + k, V + (size_t)k * n, w, k < i ? V + (size_t)(k + 1) * n : (const double*)nullptr, n, hd + k + 1);
+  hipLaunchKernelGGL(mgk::scale_rsqrt, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, hd + i + 1, w, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_kscal, hd, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, h->play->stream));
+  HIP_TRY(spin_sync(h->play->stream));
+  return MG_OK;
+}
+
 // Preconditioned CG with one multigrid cycle (x = 0 on entry) as M: solveCG_MG (SolveFuncs.jl:104-116) ->
 // KrylovMethods.cg (v0.6.0, un-vendored: Manifest.toml:35-41), restated from its published algorithm:
 //   r = b - A x0 ; z = M r ; p = z ; nr0 = ||b||
@@ -87,7 +142,6 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
   // out of the product kernel where the marching kernel serves A (partials of p[row]*Ap[row]); ||r||^2 out of the update.
   double gamma = 0.0;
   MG_TRY(K.dot(r, z, &gamma));
-  const int nb_upd = (int)std::min<long long>(grid_for(n), (long long)h->play->partial.n);
   for (long long k = 1; k <= maxIter; ++k) {
     it = k;
     double pAp = 0.0, rn = 0.0;
@@ -100,14 +154,10 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
     const double alpha = gamma / pAp;
     if (std::isinf(alpha) || alpha < 0.0) { flag = -2; break; }
     if (K.ghs) {
-      hipLaunchKernelGGL(mgk::cg_update_xr, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, alpha, p, Ap, x, r, n);
-      HIP_TRY(hipGetLastError());
+      MG_TRY(cg_update(h, alpha, p, Ap, x, r, n));
       MG_TRY(K.norm(r, &rn));
     } else {
-      hipLaunchKernelGGL(mgk::cg_update_xr_norm, dim3(nb_upd), dim3(mgk::BLK), 0, h->play->stream, alpha, p, Ap, x, r, n, h->play->partial.p);
-      launch_sum_final(h, h->play->partial.p, nb_upd);
-      HIP_TRY(hipGetLastError());
-      MG_TRY(scalar_sync(h, &rn));
+      MG_TRY(cg_update_norm(h, alpha, p, Ap, x, r, n, &rn));
     }
     rep.set(k - 1, rn / nr0);
     if (rn / nr0 <= tol) { flag = 0; break; }
@@ -116,8 +166,7 @@ int pcg_dev(mg_hierarchy* h, const double* b, double* x, double tol, long long m
     MG_TRY(K.dot(z, r, &zr));
     const double beta = zr / gamma;
     gamma = zr;                                                        // = r'z at the top of the next iteration
-    hipLaunchKernelGGL(mgk::cg_update_p, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, beta, z, p, n);
-    HIP_TRY(hipGetLastError());
+    MG_TRY(cg_direction(h, beta, z, p, n));
   }
   HIP_TRY(spin_sync(h->play->stream));
   rep.finish(it, flag);
@@ -314,21 +363,7 @@ struct FgmresCore {
       G.hsub(i) = wn;
       if (wn != 0.0) MG_TRY(k_axpby(h, 1.0 / wn, w, 0.0, w, n));
     } else {
-      if (h->kscal.n < (size_t)m + 2) MG_TRY(h->kscal.alloc((size_t)m + 2));
-      if (!h->h_kscal) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_kscal), sizeof(double) * 66));
-      const int nb = (int)std::min<long long>(h->nred_blocks, std::max<long long>(1, (n / 2 + mgk::BLK - 1) / mgk::BLK));
-      double* hd = h->kscal.p;
-      hipLaunchKernelGGL(mgk::dot_partial, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, w, V, n, h->play->partial.p);
-      hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd);
-      for (int k = 0; k <= i; ++k) {
-        hipLaunchKernelGGL(mgk::mgs_step, dim3(nb), dim3(mgk::BLK), 0, h->play->stream, hd + k, V + (size_t)k * n, w,
-                           k < i ? V + (size_t)(k + 1) * n : (const double*)nullptr, n, h->play->partial.p);
-        hipLaunchKernelGGL(mgk::sum_final, dim3(1), dim3(mgk::BLK), 0, h->play->stream, h->play->partial.p, nb, hd + k + 1);
-      }
-      hipLaunchKernelGGL(mgk::scale_rsqrt, dim3(grid_for(n)), dim3(mgk::BLK), 0, h->play->stream, hd + i + 1, w, n);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(h->h_kscal, hd, sizeof(double) * (size_t)(i + 2), hipMemcpyDeviceToHost, h->play->stream));
-      HIP_TRY(spin_sync(h->play->stream));
+      MG_TRY(mgs_chain(h, V, n, i, (size_t)m + 2));
       for (int k = 0; k <= i; ++k) G.h(k, i) = h->h_kscal[k];
       G.hsub(i) = std::sqrt(h->h_kscal[i + 1]);
     }

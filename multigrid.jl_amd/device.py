@@ -76,6 +76,15 @@ SIGNATURES = {
     "mg_block_bicgstab_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_block_fgmres_FP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
     "mg_block_fgmres_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
+    "mg_kry_dot_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _dp]),
+    "mg_kry_norm_dev_FP64": (C.c_int, [_vp, _vp, _ll, _dp]),
+    "mg_kry_axpby_dev_FP64": (C.c_int, [_vp, C.c_double, _vp, C.c_double, _vp, _ll]),
+    "mg_kry_cg_update_dev_FP64": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _ll, _dp]),
+    "mg_kry_cg_p_dev_FP64": (C.c_int, [_vp, C.c_double, _vp, _vp, _ll]),
+    "mg_kry_mgs_step_dev_FP64": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _ll, _vp]),
+    "mg_kry_mgs_chain_dev_FP64": (C.c_int, [_vp, _vp, _ll, _ll, _dp]),
+    "mg_kry_blk_gram_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _dp]),
+    "mg_kry_blk_comb_dev_FP64": (C.c_int, [_vp, _vp, _vp, C.c_double, _vp, _dp, _ll, _ll]),
     "mg_cycle_mixed_FP32": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _ll, _ll]),
     "mg_host_register": (C.c_int, [_vp, _ll]),
     "mg_host_unregister": (C.c_int, [_vp]),
@@ -353,6 +362,7 @@ def _sync_torch(*tensors):
 
 DENSE_COARSE_MAX = 16384
 MG_ERR_INVALID = 1
+MG_ERR_STATE = 3
 MG_ERR_UNSUPPORTED = 4
 
 
@@ -823,6 +833,67 @@ class DeviceHierarchy:
         _sync_torch(b, x)
         return self._krylov("fgmres_dev", np.zeros(max(int(inner) * int(maxIter), 1)), _ptr(b), _ptr(x), self.n, int(inner),
                             float(tol), int(maxIter))
+
+    # -- the real drivers' passes on their own (mg_kry_*_dev_FP64): float64 device tensors of the caller's length n; the ones that
+    #    return a host value have drained the library's stream, the others only enqueue on it (``sync()`` before reading) -----------
+    def _kry(self, name, *args):
+        _check(self.lib, getattr(self.lib, f"mg_kry_{name}_dev_FP64")(self.handle, *args), f"mg_kry_{name}_dev")
+
+    def kry_dot(self, x, y, n: int) -> float:
+        _sync_torch(x, y)
+        out = C.c_double(0.0)
+        self._kry("dot", _ptr(x), _ptr(y), int(n), C.byref(out))
+        return out.value
+
+    def kry_norm(self, x, n: int) -> float:
+        _sync_torch(x)
+        out = C.c_double(0.0)
+        self._kry("norm", _ptr(x), int(n), C.byref(out))
+        return out.value
+
+    def kry_axpby(self, a: float, x, b: float, y, n: int):
+        """y = a x + b y (b == 0: y is not read)."""
+        _sync_torch(x, y)
+        self._kry("axpby", float(a), _ptr(x), float(b), _ptr(y), int(n))
+
+    def kry_cg_update(self, alpha: float, p, Ap, x, r, n: int, norm: bool = False):
+        """x += alpha p ; r -= alpha Ap ; with ``norm`` returns ||r|| of the new r from the same pass."""
+        _sync_torch(p, Ap, x, r)
+        out = C.c_double(0.0)
+        self._kry("cg_update", float(alpha), _ptr(p), _ptr(Ap), _ptr(x), _ptr(r), int(n), C.byref(out) if norm else None)
+        return out.value if norm else None
+
+    def kry_cg_p(self, beta: float, z, p, n: int):
+        """p = z + beta p."""
+        _sync_torch(z, p)
+        self._kry("cg_p", float(beta), _ptr(z), _ptr(p), int(n))
+
+    def kry_mgs_step(self, hk, v, w, u, n: int, out):
+        """w -= hk[0] v ; out[0] = w'u of the new w (u None: w'w); hk and out are device scalars."""
+        _sync_torch(hk, v, w, u, out)
+        self._kry("mgs_step", _ptr(hk), _ptr(v), _ptr(w), _ptr(u) if u is not None else None, int(n), _ptr(out))
+
+    def kry_mgs_chain(self, V, n: int, i: int):
+        """V: i + 2 vectors n apart, the last one orthogonalised against the others and normalised; returns (h_0 .. h_i, ||w||^2)."""
+        _sync_torch(V)
+        hh = np.zeros(int(i) + 2)
+        self._kry("mgs_chain", _ptr(V), int(n), int(i), _f64(hh))
+        return hh
+
+    def kry_blk_gram(self, X, Y, n: int, k: int):
+        """X'Y (k x k) of two row-major [n][k] device blocks."""
+        _sync_torch(X, Y)
+        G = np.zeros((int(k), int(k)))
+        self._kry("blk_gram", _ptr(X), _ptr(Y), int(n), int(k), _f64(G))
+        return G
+
+    def kry_blk_comb(self, out, add, s: float, inp, Cm, n: int, k: int):
+        """out = s add + inp Cm (row-major [n][k] device blocks, Cm a k x k numpy array); add may be None, out may be inp or add."""
+        _sync_torch(out, add, inp)
+        Cc = np.ascontiguousarray(Cm, dtype=np.float64)
+        if Cc.shape != (int(k), int(k)):
+            raise ValueError("Cm must be k x k")
+        self._kry("blk_comb", _ptr(out), _ptr(add) if add is not None else None, float(s), _ptr(inp), _f64(Cc), int(n), int(k))
 
     def spmv(self, level: int, which: int, alpha: float, x, beta: float, y):
         x = self._host_block(x)

@@ -63,12 +63,7 @@ def test_halo_form_krylov_hip_vs_oracle(built, world, kind, cyc, method, mode, b
 
 
 # ---- GPU: the fused passes alone ----------------------------------------------------------------------------------------------
-LD = np.longdouble
-U = 2.0 ** -53
-
-
-def _ld(t):
-    return t.detach().cpu().numpy().astype(LD)
+from krylov_bounds import LD, _close_sum, _close_vec, _ld  # noqa: E402  (shared with the real drivers' kernel-level test)
 
 
 def _vectors(n, count, layout, seed):
@@ -84,27 +79,6 @@ def _vectors(n, count, layout, seed):
         assert v.data_ptr() % 16 == 8 * off
         out.append(v)
     return out
-
-
-def _close_vec(name, got, ref_ld, *terms):
-    """|got - ref| <= 2 ulp of the largest magnitude among the expression's terms, partial results and result (every rounding of the
-    unfused fp64 evaluation is at most half an ulp of one of them; no pass below has more than four)."""
-    mag = np.abs(ref_ld)
-    for t in terms:
-        mag = np.maximum(mag, np.abs(t))
-    err = np.abs(_ld(got) - ref_ld)
-    bound = 2.0 * np.spacing(mag.astype(np.float64)).astype(LD)
-    worst = float((err / bound).max())
-    print(f"    {name}: worst error {2 * worst:.3f} ulp (bound 2)")
-    assert worst <= 1.0, (name, worst)
-
-
-def _close_sum(name, got, terms_ld):
-    """|got - sum| <= n * 2^-53 * sum|terms| (any order of summation of fp64 products)."""
-    ref, bound = terms_ld.sum(), terms_ld.size * LD(U) * np.abs(terms_ld).sum()
-    err = abs(LD(got) - ref)
-    print(f"    {name}: |sum - reference| = {float(err):.3e} (bound {float(bound):.3e})")
-    assert err <= bound, (name, float(err), float(bound))
 
 
 def _passes(D, n, layout):
