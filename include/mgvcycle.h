@@ -925,6 +925,22 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
  * Determinism is per configuration: the order of the sums depends on the number of lane groups, which follows rap_groups and is
  * halved while the accumulator copies of a level's longest row exceed 32 KB of LDS - the same handle gives the same bits on
  * every run; handles with other options or other row lengths may differ in the last bits.
+ *
+ * The _CF32 forms (mg_rap_CF32, mg_rap_level_ms_CF32, mg_get_values_CF32, mg_get_relax_CF32, mg_replace_values_CF32) are the same
+ * five for a CF32 handle (mg_create_CF32), with the conventions of mg_set_operator_CF32_INT64 / mg_set_relax_CF32: (re, im) float
+ * pairs for A and relaxPrecs, floats for P and R; omega stays double.  The kernels are the same templates (csrc/mg_complex.hpp): a
+ * single value is widened as it is loaded, every product and sum is the ComplexF64 one of mg_rap_CF64 - the same walk, lane
+ * groups, LDS accumulator and order - and As[l+1] and relaxPrecs[l] are rounded to single once, where they are stored: each part
+ * of each entry of As[l+1] is the correctly rounded double sum of the widened operators to within that sum's own rounding.
+ * mg_rap_CF32 refuses what mg_rap_CF64 refuses, with the same codes, before the first write; a CF64 or FP64 handle is
+ * MG_ERR_STATE in all five, and the _CF64 forms keep refusing a CF32 handle (MG_ERR_UNSUPPORTED).  Behind its last product and
+ * inside its one synchronisation mg_rap_CF32 also refreshes what a CF32 handle derives from its operators: the coarsest operator
+ * widened for the GMRES coarsest solve, then that solve's Jacobi vector from it; the explicit inverse with the option
+ * "coarse_device_inverse" (singular: MG_ERR_INVALID, the previous inverse stays); on a Vanka handle with the option
+ * "vanka_device_setup" every level's blocks (mg_build_vanka_CF32's kernel; a singular cell: no level's blocks are exchanged); and
+ * As[1] widened for the Krylov drivers is dropped, so that the next driver call widens the new values (a Krylov operator set by
+ * the caller is the caller's to refresh: mg_replace_krylov_values_CFP64).  mg_replace_values_CF32 of As[1] drops that copy too, and
+ * of the coarsest operator refreshes the GMRES coarsest solve's widened copy (its Jacobi vector stays the caller's).
  * These return mg_status (below): MG_OK or an MG_ERR_* code, as every entry point of this header does. */
 typedef int mg_status;   /* the status every entry point returns (MG_OK, MG_ERR_*); the older prototypes spell it int */
 mg_status mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind, const double* omega,
@@ -933,6 +949,12 @@ mg_status mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n);
 mg_status mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
 mg_status mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n);
 mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz);
+mg_status mg_rap_CF32(mg_hierarchy* h, const float* fine_nzval, long long nnz, long long relaxKind, const double* omega,
+                      long long* levels_done);
+mg_status mg_rap_level_ms_CF32(mg_hierarchy* h, double* out, long long n);
+mg_status mg_get_values_CF32(mg_hierarchy* h, long long level, long long which, float* out, long long nnz);
+mg_status mg_get_relax_CF32(mg_hierarchy* h, long long level, float* out, long long n);
+mg_status mg_replace_values_CF32(mg_hierarchy* h, long long level, long long which, const float* nzval, long long nnz);
 
 /* ---- the explicit inverse of the coarsest operator built on the device (csrc/mg_dense_inv.hpp) ---------------------------------------------------------------
  * A dense inverse with partial pivoting in HBM: blocked in-place Gauss-Jordan with row interchanges, panels of 64 columns, the
@@ -1117,7 +1139,8 @@ mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r
  * remembered (VankaType, w), each behind the product that feeds it; relaxKind and omega are validated and not used.  A level
  * whose blocks came from mg_set_vanka_CF64 has nothing remembered: MG_ERR_STATE before the first write.  A singular cell on any
  * level: MG_ERR_INVALID after the products (the operators hold the new values, every level keeps its previous blocks).  With 0
- * mg_rap_CF64 refuses a Vanka handle with the code and message it always had; CF32 handles stay MG_ERR_UNSUPPORTED there. */
+ * mg_rap_CF64 refuses a Vanka handle with the code and message it always had; CF32 handles stay MG_ERR_UNSUPPORTED there
+ * (mg_rap_CF32 serves a CF32 Vanka handle under the same option, with mg_build_vanka_CF32's kernel). */
 mg_status mg_build_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
                               long long VankaType, const double* w, long long nw);
 mg_status mg_build_vanka_CF32(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure,
@@ -1225,8 +1248,8 @@ int mg_cblk_gram_dev_CFP64(const double* x_dev, const double* y_dev, long long n
  *
  * Refusals.  A _CF32 entry point on a CF64 or FP64 handle, and mg_set_operator_CF64_INT64 / mg_set_relax_CF64 / mg_cycle_CF64 /
  * mg_solve_CF64 / mg_spmv_CF64 / mg_set_operator_FP64_INT64 on a CF32 handle: MG_ERR_STATE.  Not served for a CF32 handle
- * (MG_ERR_UNSUPPORTED): mg_rap_CF64, mg_rap_level_ms_CF64, mg_get_values_CF64, mg_get_relax_CF64, mg_replace_values_CF64 (the
- * hierarchy is set up again on the host and uploaded), mg_set_coarse_dd (a Schwarz coarsest solve), the K-cycle, Jac-GMRES,
+ * (MG_ERR_UNSUPPORTED): mg_rap_CF64, mg_rap_level_ms_CF64, mg_get_values_CF64, mg_get_relax_CF64, mg_replace_values_CF64 (their
+ * _CF32 forms above serve it), mg_set_coarse_dd (a Schwarz coarsest solve), the K-cycle, Jac-GMRES,
  * nrhs > 1 in the entry points of this section (blocks: mg_block_cycle_dev_CFP64 and mg_block_bicgstab[_dev]_CFP64 below), and
  * whatever a CF64 handle does not serve. */
 int mg_create_CF32(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out);

@@ -741,9 +741,19 @@ struct CxCsr32 {
   const VT* val;
 };
 
-__global__ __launch_bounds__(64) void cx_rap_numeric(CxCsr32<double> R, CxCsr32<d2_t> A, CxCsr32<double> P,
+// The stored value types are template arguments: AV the pairs of A and C (d2_t, or f2_t on a CF32 handle), TV the scalars of R and P
+// (double or float).  A single value is widened as it is loaded (cx_wide: exact), every product and sum is the ComplexF64 one - the
+// same walk, lane groups, LDS accumulator of d2_t and summation order for both - and the result is rounded once, where it is stored
+// (cx_store_as).  For d2_t / double both helpers are the identity: the ComplexF64 instantiation is the code it was.
+__device__ __forceinline__ d2_t cx_wide(d2_t a) { return a; }
+__device__ __forceinline__ d2_t cx_wide(f2_t a) { return d2_t{(double)a.x, (double)a.y}; }
+__device__ __forceinline__ void cx_store_as(d2_t* p, d2_t a) { *p = a; }
+__device__ __forceinline__ void cx_store_as(f2_t* p, d2_t a) { *p = f2_t{(float)a.x, (float)a.y}; }
+
+template <typename AV, typename TV>
+__global__ __launch_bounds__(64) void cx_rap_numeric(CxCsr32<TV> R, CxCsr32<AV> A, CxCsr32<TV> P,
                                                      const int* __restrict__ Crowptr, const int* __restrict__ Ccol,
-                                                     d2_t* __restrict__ Cval, int chunk, int groups) {
+                                                     AV* __restrict__ Cval, int chunk, int groups) {
   extern __shared__ d2_t cx_rap_lds[];   // groups copies of chunk sums, then chunk column indices
   d2_t* sacc = cx_rap_lds;
   int* scol = reinterpret_cast<int*>(cx_rap_lds + (size_t)groups * chunk);
@@ -763,13 +773,13 @@ __global__ __launch_bounds__(64) void cx_rap_numeric(CxCsr32<double> R, CxCsr32<
     const int cmin = scol[0], cmax = scol[clen - 1];
     for (int kk = R.rowptr[i]; kk < R.rowptr[i + 1]; ++kk) {        // wave-uniform, stored order
       const int k = R.colidx[kk];
-      const double rv = R.val[kk];
+      const double rv = (double)R.val[kk];
       const int a1 = A.rowptr[k + 1];
       for (int jj0 = A.rowptr[k]; jj0 < a1; jj0 += groups) {        // wave-uniform; group g: entry jj0 + g
         const int jj = jj0 + g;
         if (jj < a1) {
           const int j = A.colidx[jj];
-          const d2_t ra = cmul(rv, A.val[jj]);
+          const d2_t ra = cmul(rv, cx_wide(A.val[jj]));
           for (int pp = P.rowptr[j] + sub; pp < P.rowptr[j + 1]; pp += W) {   // distinct columns: one lane each
             const int c = P.colidx[pp];
             if (c < cmin || c > cmax) continue;                     // (another chunk's column)
@@ -779,7 +789,7 @@ __global__ __launch_bounds__(64) void cx_rap_numeric(CxCsr32<double> R, CxCsr32<
               if (scol[mid] < c) lo = mid + 1;
               else hi = mid;
             }
-            if (scol[lo] == c) mine[lo] += cmul(P.val[pp], ra);
+            if (scol[lo] == c) mine[lo] += cmul((double)P.val[pp], ra);
           }
         }
         __builtin_amdgcn_wave_barrier();   // one wavefront: LDS accesses of the next rows of P follow in program order
@@ -789,7 +799,7 @@ __global__ __launch_bounds__(64) void cx_rap_numeric(CxCsr32<double> R, CxCsr32<
     for (int t = lane; t < clen; t += 64) {
       d2_t s = sacc[t];
       for (int q = 1; q < groups; ++q) s += sacc[(size_t)q * chunk + t];   // group order
-      Cval[c0 + t0 + t] = s;
+      cx_store_as(Cval + c0 + t0 + t, s);
     }
   }
 }
@@ -800,28 +810,32 @@ __global__ __launch_bounds__(BLK) void cx_conj(d2_t* __restrict__ z, long long n
   if (i < n) z[i].y = -z[i].y;
 }
 
-__device__ __forceinline__ d2_t cx_diag(const CxCsr32<d2_t>& A, int i) {
+template <typename AV>
+__device__ __forceinline__ d2_t cx_diag(const CxCsr32<AV>& A, int i) {
   d2_t diag = d2_t{0.0, 0.0};
   for (int k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k)
-    if (A.colidx[k] == i) diag = A.val[k];
+    if (A.colidx[k] == i) diag = cx_wide(A.val[k]);
   return diag;
 }
 // d_i = omega / a_ii  (getRelaxPrec "Jac" for complex values: conj(relaxParam ./ diag(AT)), MGsetup.jl:145-147)
-__global__ __launch_bounds__(BLK) void cx_relax_jacobi(CxCsr32<d2_t> A, int n, double omega, d2_t* __restrict__ d) {
+// (AV: A's stored pairs, DV: d's - the GMRES coarsest vector of a CF32 handle is ComplexF64 from the widened operator)
+template <typename AV, typename DV>
+__global__ __launch_bounds__(BLK) void cx_relax_jacobi(CxCsr32<AV> A, int n, double omega, DV* __restrict__ d) {
   const int i = blockIdx.x * BLK + threadIdx.x;
   if (i >= n) return;
-  d[i] = cdiv(d2_t{omega, 0.0}, cx_diag(A, i));
+  cx_store_as(d + i, cdiv(d2_t{omega, 0.0}, cx_diag(A, i)));
 }
 // s_j = sum over the entries of COLUMN j of re^2 + im^2 in ascending row order (getSPAIprec, MGsetup.jl:359-362: row j of AT):
 // squares rounded, then summed, as colsumsq_kernel does - no atomics, the same bits on every run and as the host's bincount.
-__global__ __launch_bounds__(BLK) void cx_colsumsq(const d2_t* __restrict__ val, const int* __restrict__ tptr,
+template <typename AV>
+__global__ __launch_bounds__(BLK) void cx_colsumsq(const AV* __restrict__ val, const int* __restrict__ tptr,
                                                    const int* __restrict__ tperm, int n_cols, double* __restrict__ s) {
 #pragma clang fp contract(off)
   const int j = blockIdx.x * BLK + threadIdx.x;
   if (j >= n_cols) return;
   double acc = 0.0;
   for (int k = tptr[j]; k < tptr[j + 1]; ++k) {
-    const d2_t a = val[tperm[k]];
+    const d2_t a = cx_wide(val[tperm[k]]);
     const double re2 = a.x * a.x;
     const double im2 = a.y * a.y;
     const double sq = re2 + im2;
@@ -830,13 +844,14 @@ __global__ __launch_bounds__(BLK) void cx_colsumsq(const d2_t* __restrict__ val,
   s[j] = acc;
 }
 // d_i = omega * conj(a_ii) / s_i  (conj(relaxParam * getSPAIprec(AT)), MGsetup.jl:148-149): the quotient first
-__global__ __launch_bounds__(BLK) void cx_relax_spai(CxCsr32<d2_t> A, int n, double omega, const double* __restrict__ s,
-                                                     d2_t* __restrict__ d) {
+template <typename AV>
+__global__ __launch_bounds__(BLK) void cx_relax_spai(CxCsr32<AV> A, int n, double omega, const double* __restrict__ s,
+                                                     AV* __restrict__ d) {
   const int i = blockIdx.x * BLK + threadIdx.x;
   if (i >= n) return;
   const d2_t diag = cx_diag(A, i);
   const double si = s[i];
-  d[i] = d2_t{omega * (diag.x / si), omega * (-diag.y / si)};
+  cx_store_as(d + i, d2_t{omega * (diag.x / si), omega * (-diag.y / si)});
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1476,26 +1476,42 @@ int cx_build_transposed_pattern(CxMat& A) {
 
 template <typename VT>
 mgk::CxCsr32<VT> cx_csr32(const CxMat& M) {
-  return mgk::CxCsr32<VT>{M.rowptr.p, M.colidx.p, reinterpret_cast<const VT*>(M.val.p)};
+  return mgk::CxCsr32<VT>{M.rowptr.p, M.colidx.p, static_cast<const VT*>(M.vals())};   // (val, or valf of a CF32 handle's operator)
 }
 
 // New values on M's unchanged pattern from host memory, on h's stream and waited for: complex values arrive in the reference's
 // AT convention and are conjugated in HBM (cx_conj), real ones are copied.
-int cx_write_values(mg_hierarchy* h, CxMat& M, const double* nzval) {
+// ST: the host scalar, that of M's stored values (double, or float for the operators of a CF32 handle).
+template <typename ST>
+int cx_write_values(mg_hierarchy* h, CxMat& M, const ST* nzval) {
+  constexpr bool single = sizeof(ST) == sizeof(float);
+  if (M.single != single) return fail(MG_ERR_INVALID, "internal: values and operator differ in precision");
   const hipStream_t st = h->play->stream;
   HIP_TRY(spin_sync(st));
   if (M.nnz > 0) {
-    HIP_TRY(hipMemcpyAsync(M.val.p, nzval, (size_t)M.nnz * (M.cplx ? 2 : 1) * sizeof(double), hipMemcpyHostToDevice, st));
-    if (M.cplx) hipLaunchKernelGGL(mgk::cx_conj, dim3(cx_grid(M.nnz)), dim3(mgk::BLK), 0, st, cxp(M.val), M.nnz);
+    HIP_TRY(hipMemcpyAsync(const_cast<void*>(M.vals()), nzval, (size_t)M.nnz * (M.cplx ? 2 : 1) * sizeof(ST), hipMemcpyHostToDevice, st));
+    if (M.cplx) {
+      if (single) hipLaunchKernelGGL(mgk::cx_conj32, dim3(cx_grid(M.nnz)), dim3(mgk::BLK), 0, st, reinterpret_cast<cf_t*>(M.valf.p), M.nnz);
+      else hipLaunchKernelGGL(mgk::cx_conj, dim3(cx_grid(M.nnz)), dim3(mgk::BLK), 0, st, cxp(M.val), M.nnz);
+    }
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(spin_sync(st));
   return MG_OK;
 }
 
-// the operator `which` of `level` of a CF64 handle, set
-int cx_find_op(mg_hierarchy* h, long long level, long long which, CxMat** out) {
-  MG_TRY(cx_level_ok(h, level));
+// The values of K, a widened copy of the single operator A made by cx_widen_mat on the pattern both still hold, widened again from
+// A's present values: enqueued on h's stream, not waited for.
+int cx_widen_values(mg_hierarchy* h, const CxMat& A, CxMat& K) {
+  if (!K.set || K.single || !A.single || K.nnz != A.nnz || K.n_rows != A.n_rows)
+    return fail(MG_ERR_STATE, "internal: the widened copy does not hold the operator's pattern");
+  if (A.nnz > 0) MG_TRY(cx_widen(h, reinterpret_cast<const cf_t*>(A.valf.p), cxp(K.val), A.nnz));
+  return MG_OK;
+}
+
+// the operator `which` of `level` of a CF64 handle (want: or of a CF32 one), set
+int cx_find_op(mg_hierarchy* h, long long level, long long which, CxMat** out, CxWant want = CX_WANT64) {
+  MG_TRY(cx_level_ok(h, level, want));
   if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
   if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
   CxLevel& L = h->cx->lev[(size_t)level - 1];
@@ -2463,32 +2479,38 @@ int mg_block_solve_CF64(mg_hierarchy* h, const double* B, double* X, long long n
   return cx_block_solve_host(h, B, X, n, nrhs, tol, maxIter, iters, resvec);
 }
 
-// replaceMatrixInHierarchy on the device (MGsetup.jl:226-270) for VAL = ComplexF64: new fine values on the stored pattern, then per
-// level relaxPrecs[l] = getRelaxPrec(As[l]) and As[l+1] = Rs[l]*(As[l]*Ps[l]) on the fixed patterns.  Generic CSR has no derived
-// formats to rebuild.  The coarsest solve: with the option coarse_device_inverse and a dense inverse installed, the inverse of the new
-// coarsest operator is built in HBM behind the last Galerkin product (mg_dense_inv.hpp), on the same stream and inside the call's one
-// synchronisation - a singular operator is an error return and the previous inverse stays; the GMRES coarsest solve recomputes its
-// Jacobi vector there.  Otherwise the factorisation stays with the host: mg_get_values_CF64 of the coarsest level, factor,
-// mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64, mg_finalize.  The checks of arguments and state precede the first write.
-int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind, const double* omega,
-                long long* levels_done) {
-  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
-  if (!fine_nzval || !omega) return fail(MG_ERR_INVALID, "null argument");
-  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
-  MG_CF32_UNSUPPORTED(h);   // (a CF32 hierarchy is set up again on the host and uploaded)
+}  // extern "C"
+
+namespace {
+
+// replaceMatrixInHierarchy on the device (MGsetup.jl:226-270) for VAL = ComplexF64 or ComplexF32 (C: the handle's pair type, cx_t or
+// cf_t): new fine values on the stored pattern, then per level relaxPrecs[l] = getRelaxPrec(As[l]) and As[l+1] = Rs[l]*(As[l]*Ps[l]) on
+// the fixed patterns.  Generic CSR has no derived formats to rebuild.  A CF32 handle's kernels read the single values, compute in
+// ComplexF64 and round once on the store (mg_complex.hpp).  The coarsest solve: with the option coarse_device_inverse and a dense
+// inverse installed, the inverse of the new coarsest operator is built in HBM behind the last Galerkin product (mg_dense_inv.hpp), on
+// the same stream and inside the call's one synchronisation - a singular operator is an error return and the previous inverse stays;
+// the GMRES coarsest solve recomputes its Jacobi vector there (a CF32 handle: from the coarsest operator widened again into cgA, ahead
+// of it).  Otherwise the factorisation stays with the host: mg_get_values_* of the coarsest level, factor,
+// mg_set_coarse_dense_inverse_CF64 / mg_set_coarse_lu_CF64_INT64, mg_finalize.  A CF32 handle's auto-widened Krylov operator is
+// dropped: the next driver call widens the new As[1].  The checks of arguments and state precede the first write.
+template <typename C>
+int cx_rap(mg_hierarchy* h, const typename mgk::cx_scalar<C>::type* fine_nzval, long long nnz, long long relaxKind, const double* omega,
+           long long* levels_done, const char* who, const char* sfx) {
+  typedef typename mgk::cx_scalar<C>::type ST;
   CxState& S = *h->cx;
   if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
   if (nnz != S.lev[0].A.nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored fine pattern (%lld)", nnz, S.lev[0].A.nnz);
   if (relaxKind != 0 && relaxKind != 1) return fail(MG_ERR_INVALID, "relaxKind must be 0 (Jac) or 1 (SPAI)");
   const bool vanka = h->relax_type == 2;
   if (vanka && !h->opt.vanka_device_setup)
-    return fail(MG_ERR_UNSUPPORTED, "mg_rap_CF64 recomputes Jac and SPAI relaxPrecs: the blocks of a Vanka handle are set up on the host");
+    return fail(MG_ERR_UNSUPPORTED, "%s recomputes Jac and SPAI relaxPrecs: the blocks of a Vanka handle are set up on the host", who);
   const int nl = (int)h->nlevels;
-  if (vanka)   // option vanka_device_setup: every relaxed level's blocks are built again with what mg_build_vanka_CF64 was given
+  if (vanka)   // option vanka_device_setup: every relaxed level's blocks are built again with what mg_build_vanka_* was given
     for (int l = 0; l + 1 < nl; ++l) {
       const CxLevel& L = S.lev[(size_t)l];
       if (!L.vanka || !L.vanka->has_w)
-        return fail(MG_ERR_STATE, "level %d's Vanka blocks were bound by mg_set_vanka_CF64: no (VankaType, w) to build them again with (mg_build_vanka_CF64)", l + 1);
+        return fail(MG_ERR_STATE, "level %d's Vanka blocks were bound by mg_set_vanka_%s: no (VankaType, w) to build them again with (mg_build_vanka_%s)", l + 1,
+                    sfx, sfx);
     }
   for (int l = 0; l < nl; ++l) {
     const CxLevel& L = S.lev[(size_t)l];
@@ -2497,6 +2519,8 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   }
   const bool dev_inverse = h->opt.coarse_device_inverse && S.coarse_set && !S.coarse_lu && !S.coarse_gmres && !h->coarse_dd && S.Ainv.p;
   if (dev_inverse) MG_TRY(cx_coarse_inverse_check(h));
+  if (S.single && S.coarse_gmres && (!S.cgA.set || S.cgA.nnz != S.lev[(size_t)nl - 1].A.nnz))
+    return fail(MG_ERR_STATE, "the widened coarsest operator of the GMRES coarsest solve is missing: call mg_finalize first");
   (void)hipSetDevice(h->device);
   const hipStream_t st = h->play->stream;
   if (relaxKind == 1)
@@ -2507,35 +2531,38 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     S.rap_ev.push_back(e);
   }
   S.rap_timed = false;
-  MG_TRY(cx_write_values(h, S.lev[0].A, fine_nzval));
+  MG_TRY(cx_write_values<ST>(h, S.lev[0].A, fine_nzval));
   for (int l = 0; l + 1 < nl; ++l) {
     CxLevel& L = S.lev[(size_t)l];
     CxMat& Cm = S.lev[(size_t)l + 1].A;
     const unsigned nb = cx_grid(L.n);
-    const mgk::CxCsr32<cx_t> Ad = cx_csr32<cx_t>(L.A);
+    const mgk::CxCsr32<C> Ad = cx_csr32<C>(L.A);
     HIP_TRY(hipEventRecord(S.rap_ev[(size_t)l], st));
     if (vanka) {   // the level's blocks from its new values, into the spare buffer (exchanged below, once nothing was found singular)
       MG_TRY(vanka_build_launch(L.vanka, L.A.rowptr.p, L.A.colidx.p, L.A.vals(), L.vanka->built, st));
     } else if (relaxKind == 0) {
-      hipLaunchKernelGGL(mgk::cx_relax_jacobi, dim3(nb), dim3(mgk::BLK), 0, st, Ad, (int)L.n, omega[l], cxp(L.d));
-    } else {   // the level's r as scratch for the column sums
-      hipLaunchKernelGGL(mgk::cx_colsumsq, dim3(nb), dim3(mgk::BLK), 0, st, reinterpret_cast<const cx_t*>(L.A.val.p), L.A.t_ptr.p,
+      hipLaunchKernelGGL((mgk::cx_relax_jacobi<C, C>), dim3(nb), dim3(mgk::BLK), 0, st, Ad, (int)L.n, omega[l], cxp<C>(L.d));
+    } else {   // the level's r as scratch for the column sums (one double per row in either precision)
+      hipLaunchKernelGGL((mgk::cx_colsumsq<C>), dim3(nb), dim3(mgk::BLK), 0, st, static_cast<const C*>(L.A.vals()), L.A.t_ptr.p,
                          L.A.t_perm.p, (int)L.A.n_cols, L.r.p);
-      hipLaunchKernelGGL(mgk::cx_relax_spai, dim3(nb), dim3(mgk::BLK), 0, st, Ad, (int)L.n, omega[l], L.r.p, cxp(L.d));
+      hipLaunchKernelGGL((mgk::cx_relax_spai<C>), dim3(nb), dim3(mgk::BLK), 0, st, Ad, (int)L.n, omega[l], L.r.p, cxp<C>(L.d));
     }
     const long long cap = std::max<long long>(1, std::min<long long>(h->opt.rap_chunk, mgk::RAP_CAP));
     const int chunk = (int)std::max<long long>(1, std::min<long long>(cap, Cm.max_row));
     // lane groups: the default (option rap_groups: 1, 2, 4, 8, 16), halved while the accumulator copies exceed 32 KB of LDS
+    // (the accumulator holds ComplexF64 sums in either precision)
     int groups = 1;
     while (groups * 2 <= std::min<long long>(h->opt.rap_groups > 0 ? h->opt.rap_groups : mgk::CX_RAP_GROUPS, 16)) groups *= 2;
     while (groups > 1 && (size_t)chunk * ((size_t)groups * sizeof(cx_t) + sizeof(int)) > 32768) groups /= 2;
-    hipLaunchKernelGGL(mgk::cx_rap_numeric, dim3((unsigned)Cm.n_rows), dim3(64), (size_t)chunk * ((size_t)groups * sizeof(cx_t) + sizeof(int)), st,
-                       cx_csr32<double>(L.R), Ad, cx_csr32<double>(L.P), Cm.rowptr.p, Cm.colidx.p, cxp(Cm.val), chunk, groups);
+    hipLaunchKernelGGL((mgk::cx_rap_numeric<C, ST>), dim3((unsigned)Cm.n_rows), dim3(64), (size_t)chunk * ((size_t)groups * sizeof(cx_t) + sizeof(int)), st,
+                       cx_csr32<ST>(L.R), Ad, cx_csr32<ST>(L.P), Cm.rowptr.p, Cm.colidx.p, static_cast<C*>(const_cast<void*>(Cm.vals())), chunk, groups);
     HIP_TRY(hipGetLastError());
   }
   if (S.coarse_gmres) {   // param.LU = relaxParam ./ diag(A_c) on the new coarsest operator (MGsetup.jl:335-336): omega[nlevels - 1]
     const CxLevel& Lc = S.lev[(size_t)nl - 1];
-    hipLaunchKernelGGL(mgk::cx_relax_jacobi, dim3(cx_grid(Lc.n)), dim3(mgk::BLK), 0, st, cx_csr32<cx_t>(Lc.A), (int)Lc.n, omega[nl - 1], cxp(S.cgD));
+    if (S.single) MG_TRY(cx_widen_values(h, Lc.A, S.cgA));   // (the operator the coarsest solve applies: ahead of everything that reads it)
+    hipLaunchKernelGGL((mgk::cx_relax_jacobi<cx_t, cx_t>), dim3(cx_grid(Lc.n)), dim3(mgk::BLK), 0, st, cx_csr32<cx_t>(cx_cg_operator(S)), (int)Lc.n,
+                       omega[nl - 1], cxp(S.cgD));
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(S.rap_ev[(size_t)nl - 1], st));
@@ -2549,7 +2576,11 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
     HIP_TRY(synced);
   }
   S.rap_timed = true;
-  if (dev_inverse) inv_rc = cx_coarse_inverse_finish(h, inv, inv_spare, "mg_rap_CF64");
+  if (S.single && S.K_auto) {   // As[1] widened for the Krylov drivers holds the old values: the next driver call widens the new ones
+    S.K.release();
+    S.K_auto = false;
+  }
+  if (dev_inverse) inv_rc = cx_coarse_inverse_finish(h, inv, inv_spare, who);
   if (vanka) {   // a singular cell anywhere: no level's blocks are exchanged (the operators hold the new values; the blocks the old ones)
     int bad = 0, first = 0;
     for (int l = 0; l + 1 < nl; ++l) {
@@ -2557,7 +2588,7 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
       int flag[2] = {0, 0};
       HIP_TRY(hipMemcpy(flag, V->flag.p, sizeof(flag), hipMemcpyDeviceToHost));
       if (flag[0] != 0)
-        return fail(MG_ERR_INVALID, "mg_rap_CF64: level %d: cell %d of %d with a singular block: every level keeps its previous blocks", l + 1,
+        return fail(MG_ERR_INVALID, "%s: level %d: cell %d of %d with a singular block: every level keeps its previous blocks", who, l + 1,
                     INT_MAX - flag[1] + 1, flag[0]);
     }
     for (int l = 0; l + 1 < nl; ++l) {
@@ -2569,19 +2600,86 @@ int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   return inv_rc;   // (a singular coarsest operator: the operators hold the new values, the coarsest solve the previous inverse)
 }
 
-// Device time of the last mg_rap_CF64, level by level (relaxPrecs[l] and As[l+1] together), in milliseconds: out[0 .. nlevels-1).
-int mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n) {
-  MG_CF32_UNSUPPORTED(h);
-  MG_TRY(cx_level_ok(h, 1));
+// Device time of the last mg_rap_* of the handle, level by level (relaxPrecs[l] and As[l+1] together), in milliseconds
+int cx_rap_level_ms(mg_hierarchy* h, double* out, long long n, const char* rap) {
   CxState& S = *h->cx;
   if (!out || n != h->nlevels - 1) return fail(MG_ERR_INVALID, "out must hold nlevels - 1 = %lld values", h->nlevels - 1);
-  if (!S.rap_timed) return fail(MG_ERR_STATE, "no completed mg_rap_CF64 on this handle");
+  if (!S.rap_timed) return fail(MG_ERR_STATE, "no completed %s on this handle", rap);
   for (long long l = 0; l < n; ++l) {
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, S.rap_ev[(size_t)l], S.rap_ev[(size_t)l + 1]));
     out[l] = (double)ms;
   }
   return MG_OK;
+}
+
+// mg_get_values_* / mg_get_relax_* / mg_replace_values_* behind the handle checks of their entry points; ST: the host scalar of the
+// handle's precision.  Complex values leave and arrive in the reference's AT convention.
+template <typename ST>
+int cx_get_values(mg_hierarchy* h, long long level, long long which, ST* out, long long nnz, CxWant want) {
+  CxMat* M;
+  MG_TRY(cx_find_op(h, level, which, &M, want));
+  if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));
+  const size_t len = (size_t)nnz * (M->cplx ? 2 : 1);
+  if (len > 0) HIP_TRY(hipMemcpy(out, M->vals(), len * sizeof(ST), hipMemcpyDeviceToHost));
+  if (M->cplx)   // back to the reference's AT convention
+    for (size_t k = 1; k < len; k += 2) out[k] = -out[k];
+  return MG_OK;
+}
+
+template <typename ST>
+int cx_get_relax(mg_hierarchy* h, long long level, ST* out, long long n, CxWant want) {
+  MG_TRY(cx_level_ok(h, level, want));
+  CxLevel& L = h->cx->lev[(size_t)level - 1];
+  if (!L.relax_set || (long long)cx_len(*h->cx, n) != (long long)L.d.n) return fail(MG_ERR_INVALID, "relaxPrecs[%lld] not set or wrong length", level);
+  (void)hipSetDevice(h->device);
+  HIP_TRY(spin_sync(h->play->stream));
+  HIP_TRY(hipMemcpy(out, L.d.p, 2 * (size_t)n * sizeof(ST), hipMemcpyDeviceToHost));
+  return MG_OK;
+}
+
+template <typename ST>
+int cx_replace_values(mg_hierarchy* h, long long level, long long which, const ST* nzval, long long nnz, CxWant want) {
+  CxMat* M;
+  MG_TRY(cx_find_op(h, level, which, &M, want));
+  if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
+  (void)hipSetDevice(h->device);
+  return cx_write_values<ST>(h, *M, nzval);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mg_rap_CF64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind, const double* omega,
+                long long* levels_done) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!fine_nzval || !omega) return fail(MG_ERR_INVALID, "null argument");
+  if (!h->cx) return fail(MG_ERR_STATE, "CF64 entry point called on an FP64 handle (create it with mg_create_CF64)");
+  MG_CF32_UNSUPPORTED(h);   // (its _CF32 twin serves a CF32 hierarchy)
+  return cx_rap<cx_t>(h, fine_nzval, nnz, relaxKind, omega, levels_done, "mg_rap_CF64", "CF64");
+}
+
+// The same for a CF32 handle: fine values, As and relaxPrecs in single, every sum in ComplexF64, one rounding on the store.
+int mg_rap_CF32(mg_hierarchy* h, const float* fine_nzval, long long nnz, long long relaxKind, const double* omega,
+                long long* levels_done) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!fine_nzval || !omega) return fail(MG_ERR_INVALID, "null argument");
+  MG_TRY(cx_handle_ok(h, CX_WANT32));
+  return cx_rap<cf_t>(h, fine_nzval, nnz, relaxKind, omega, levels_done, "mg_rap_CF32", "CF32");
+}
+
+// Device time of the last mg_rap_CF64, level by level (relaxPrecs[l] and As[l+1] together), in milliseconds: out[0 .. nlevels-1).
+int mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n) {
+  MG_CF32_UNSUPPORTED(h);
+  MG_TRY(cx_level_ok(h, 1));
+  return cx_rap_level_ms(h, out, n, "mg_rap_CF64");
+}
+int mg_rap_level_ms_CF32(mg_hierarchy* h, double* out, long long n) {
+  MG_TRY(cx_level_ok(h, 1, CX_WANT32));
+  return cx_rap_level_ms(h, out, n, "mg_rap_CF32");
 }
 
 // adjointHierarchy (MGsetup.jl:274-318 for complex VAL) on the resident hierarchy, in HBM: see include/mgvcycle.h
@@ -2600,40 +2698,49 @@ int mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!out) return fail(MG_ERR_INVALID, "null argument");
   MG_CF32_UNSUPPORTED(h);
-  CxMat* M;
-  MG_TRY(cx_find_op(h, level, which, &M));
-  if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
-  (void)hipSetDevice(h->device);
-  HIP_TRY(spin_sync(h->play->stream));
-  const size_t len = (size_t)nnz * (M->cplx ? 2 : 1);
-  if (len > 0) HIP_TRY(hipMemcpy(out, M->val.p, len * sizeof(double), hipMemcpyDeviceToHost));
-  if (M->cplx)   // back to the reference's AT convention
-    for (size_t k = 1; k < len; k += 2) out[k] = -out[k];
-  return MG_OK;
+  return cx_get_values<double>(h, level, which, out, nnz, CX_WANT64);
+}
+int mg_get_values_CF32(mg_hierarchy* h, long long level, long long which, float* out, long long nnz) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!out) return fail(MG_ERR_INVALID, "null argument");
+  return cx_get_values<float>(h, level, which, out, nnz, CX_WANT32);
 }
 
 int mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!out) return fail(MG_ERR_INVALID, "null argument");
   MG_CF32_UNSUPPORTED(h);
-  MG_TRY(cx_level_ok(h, level));
-  CxLevel& L = h->cx->lev[(size_t)level - 1];
-  if (!L.relax_set || 2 * n != (long long)L.d.n) return fail(MG_ERR_INVALID, "relaxPrecs[%lld] not set or wrong length", level);
-  (void)hipSetDevice(h->device);
-  HIP_TRY(spin_sync(h->play->stream));
-  HIP_TRY(hipMemcpy(out, L.d.p, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  return MG_OK;
+  return cx_get_relax<double>(h, level, out, n, CX_WANT64);
+}
+int mg_get_relax_CF32(mg_hierarchy* h, long long level, float* out, long long n) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!out) return fail(MG_ERR_INVALID, "null argument");
+  return cx_get_relax<float>(h, level, out, n, CX_WANT32);
 }
 
 int mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz) {
   if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
   if (!nzval) return fail(MG_ERR_INVALID, "null argument");
   MG_CF32_UNSUPPORTED(h);
-  CxMat* M;
-  MG_TRY(cx_find_op(h, level, which, &M));
-  if (nnz != M->nnz) return fail(MG_ERR_INVALID, "nnz=%lld differs from the stored pattern (%lld)", nnz, M->nnz);
-  (void)hipSetDevice(h->device);
-  return cx_write_values(h, *M, nzval);
+  return cx_replace_values<double>(h, level, which, nzval, nnz, CX_WANT64);
+}
+// (a CF32 handle keeps widened copies of two operators: that of the coarsest one for the GMRES coarsest solve follows the new values
+// here, that of As[1] for the Krylov drivers is dropped and widened again by the next driver call)
+int mg_replace_values_CF32(mg_hierarchy* h, long long level, long long which, const float* nzval, long long nnz) {
+  if (!h) return fail(MG_ERR_INVALID, "null hierarchy handle");
+  if (!nzval) return fail(MG_ERR_INVALID, "null argument");
+  MG_TRY(cx_replace_values<float>(h, level, which, nzval, nnz, CX_WANT32));
+  CxState& S = *h->cx;
+  if (which != MG_OP_A) return MG_OK;
+  if (level == 1 && S.K_auto) {
+    S.K.release();
+    S.K_auto = false;
+  }
+  if (level == h->nlevels && S.coarse_gmres && S.cgA.set) {
+    MG_TRY(cx_widen_values(h, S.lev[(size_t)level - 1].A, S.cgA));
+    HIP_TRY(spin_sync(h->play->stream));
+  }
+  return MG_OK;
 }
 
 int mg_replace_krylov_values_CFP64(mg_hierarchy* h, const double* nzval, long long nnz) {

@@ -255,6 +255,11 @@ SIGNATURES = {
     "mg_get_values_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
     "mg_get_relax_CF64": (C.c_int, [_vp, _ll, _dp, _ll]),
     "mg_replace_values_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _ll]),
+    "mg_rap_CF32": (C.c_int, [_vp, _fp, _ll, _ll, _dp, _lp]),
+    "mg_rap_level_ms_CF32": (C.c_int, [_vp, _dp, _ll]),
+    "mg_get_values_CF32": (C.c_int, [_vp, _ll, _ll, _fp, _ll]),
+    "mg_get_relax_CF32": (C.c_int, [_vp, _ll, _fp, _ll]),
+    "mg_replace_values_CF32": (C.c_int, [_vp, _ll, _ll, _fp, _ll]),
     "mg_adjoint_hierarchy_CF64": (C.c_int, [_vp]),
     "mg_adjoint_hierarchy_CF32": (C.c_int, [_vp]),
     "mg_bicgstab_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
@@ -1650,19 +1655,22 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     def replace_values(self, level: int, which: int, M):
         """New values of one operator on its unchanged pattern: M.data complex (the applied A) for MG_OP_A, real for P and R."""
         if which == MG_OP_A:
-            nz = np.ascontiguousarray(np.conj(M.data), dtype=np.complex128)     # the reference's AT values
+            nz = np.ascontiguousarray(np.conj(M.data), dtype=self._cdtype)      # the reference's AT values
         else:
             if np.iscomplexobj(M.data):
-                raise TypeError("P and R of a ComplexF64 hierarchy are real")
-            nz = np.ascontiguousarray(M.data, dtype=np.float64)
-        _check(self.lib, self.lib.mg_replace_values_CF64(self.handle, int(level), int(which), _f64(nz), M.data.size), "mg_replace_values_CF64")
+                raise TypeError("P and R of a complex hierarchy are real")
+            nz = np.ascontiguousarray(M.data, dtype=self._rdtype)
+        _check(self.lib, self._fn("replace_values")(self.handle, int(level), int(which), self._vp_of(nz), M.data.size),
+               f"mg_replace_values_{self._sfx}")
 
     def get_values(self, level: int, which: int) -> np.ndarray:
-        """Values of operator `which` of `level` as applied (stored CSR order): complex128 for A, float64 for P and R."""
+        """Values of operator `which` of `level` as applied (stored CSR order): complex128 for A, float64 for P and R (a ComplexF32
+        hierarchy: complex64 and float32)."""
         if (int(level), int(which)) not in self._op_nnz:
             raise MGDeviceError(f"get_values: level {level} holds no operator {which}")
-        vals = np.zeros(self._op_nnz[(int(level), int(which))], dtype=np.complex128 if which == MG_OP_A else np.float64)
-        _check(self.lib, self.lib.mg_get_values_CF64(self.handle, int(level), int(which), _f64(vals), vals.size), "mg_get_values_CF64")
+        vals = np.zeros(self._op_nnz[(int(level), int(which))], dtype=self._cdtype if which == MG_OP_A else self._rdtype)
+        _check(self.lib, self._fn("get_values")(self.handle, int(level), int(which), self._vp_of(vals), vals.size),
+               f"mg_get_values_{self._sfx}")
         return np.conjugate(vals, out=vals) if which == MG_OP_A else vals
 
     def replace_matrix(self, param, A_new, timings: Optional[dict] = None) -> None:
@@ -1670,11 +1678,12 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         and relaxPrecs on the fixed patterns (mg_rap_CF64), host copies of the hierarchy refreshed from HBM, coarsest level
         re-factored on the host (with coarseSolveType='GMRES' there is nothing to factor: its Jacobi vector is recomputed in HBM;
         a param with ``coarseDeviceInverse=True``: the explicit inverse is rebuilt in HBM by mg_rap_CF64 and ``coarsest`` is the
-        host's splu alone).  ``timings`` (a dict) receives the seconds of the three parts."""
+        host's splu alone).  ``timings`` (a dict) receives the seconds of the three parts.  A ComplexF32 hierarchy whose param
+        carries ``singleDeviceSetup`` runs the same steps through the _CF32 entry points, its values complex64."""
         import time
         lib = self.lib
         t0 = time.perf_counter()
-        nz = np.ascontiguousarray(np.conj(A_new.data), dtype=np.complex128)     # the reference's AT values
+        nz = np.ascontiguousarray(np.conj(A_new.data), dtype=self._cdtype)      # the reference's AT values
         rp = param.relaxParam
         vanka = getattr(self, "_vanka", False)
         if vanka and not getattr(self, "_vanka_device_setup", False):
@@ -1687,21 +1696,21 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
                                           for l in range(self.nlevels)], dtype=np.float64)
         kind = 1 if param.relaxType == "SPAI" else 0
         done = C.c_longlong(0)
-        _check(lib, lib.mg_rap_CF64(self.handle, _c128(nz), nz.size, kind, _f64(omega), C.byref(done)), "mg_rap_CF64")
+        _check(lib, self._fn("rap")(self.handle, self._vp_of(nz), nz.size, kind, _f64(omega), C.byref(done)), f"mg_rap_{self._sfx}")
         t1 = time.perf_counter()
         param.As[0] = A_new
         for l in range(2, self.nlevels + 1):                       # refresh the host copies (same patterns)
             M = param.As[l - 1]
-            vals = np.empty(M.nnz, dtype=np.complex128)
-            _check(lib, lib.mg_get_values_CF64(self.handle, l, MG_OP_A, _c128(vals), vals.size), "mg_get_values_CF64")
+            vals = np.empty(M.nnz, dtype=self._cdtype)
+            _check(lib, self._fn("get_values")(self.handle, l, MG_OP_A, self._vp_of(vals), vals.size), f"mg_get_values_{self._sfx}")
             np.conjugate(vals, out=M.data)
         tb = time.perf_counter()
         for l in range(1, self.nlevels):
             if vanka:                                              # the cells' blocks, rebuilt in HBM (mg_get_vanka_blocks_CF64)
                 param.relaxPrecs[l - 1] = self.vanka_blocks(l)
                 continue
-            d = np.empty(param.As[l - 1].shape[0], dtype=np.complex128)
-            _check(lib, lib.mg_get_relax_CF64(self.handle, l, _c128(d), d.size), "mg_get_relax_CF64")
+            d = np.empty(param.As[l - 1].shape[0], dtype=self._cdtype)
+            _check(lib, self._fn("get_relax")(self.handle, l, self._vp_of(d), d.size), f"mg_get_relax_{self._sfx}")
             param.relaxPrecs[l - 1] = d
         t2 = time.perf_counter()
         from .mgsetup import defineCoarsestAinv
@@ -1729,9 +1738,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             self._op_nnz[(l, MG_OP_P)] = int(param.Ps[l - 1].nnz)
 
     def rap_level_ms(self) -> np.ndarray:
-        """Device milliseconds of the last replace_matrix per level (relaxPrecs[l] and As[l+1] together; mg_rap_level_ms_CF64)."""
+        """Device milliseconds of the last replace_matrix per level (relaxPrecs[l] and As[l+1] together; mg_rap_level_ms_*)."""
         out = np.zeros(self.nlevels - 1)
-        _check(self.lib, self.lib.mg_rap_level_ms_CF64(self.handle, _f64(out), out.size), "mg_rap_level_ms_CF64")
+        _check(self.lib, self._fn("rap_level_ms")(self.handle, _f64(out), out.size), f"mg_rap_level_ms_{self._sfx}")
         return out
 
     def _refuse(self, *args, **kwargs):
@@ -1780,11 +1789,32 @@ class ComplexSingleDeviceHierarchy(ComplexDeviceHierarchy):
         _check(self.lib, self.lib.mg_set_relax_CF32(self.handle, level, d.ctypes.data_as(_fp), d.size, int(pre), int(post)),
                f"mg_set_relax_CF32(level={level})")
 
+    _single_device_setup = False      # the param uploaded last carried singleDeviceSetup: the four methods below are served
+
+    def _upload(self, param):
+        self._single_device_setup = bool(getattr(param, "singleDeviceSetup", False))
+        super()._upload(param)
+
     def _refuse_single(self, *args, **kwargs):
         raise NotImplementedError("ComplexF32 hierarchies: replace_matrix, replace_values, get_values and rap_level_ms on the device are "
-                                  "out of scope (replaceMatrixInHierarchy recomputes on the host and uploads again)")
+                                  "served for a param with singleDeviceSetup=True (without it replaceMatrixInHierarchy recomputes on "
+                                  "the host and uploads again)")
 
-    replace_matrix = replace_values = get_values = rap_level_ms = _refuse_single
+    def _served_single(name):
+        """The ComplexF64 method of that name, by the _CF32 entry points, where the param asked for it; the refusal otherwise."""
+        def method(self, *args, **kwargs):
+            if not self._single_device_setup:
+                return self._refuse_single()
+            return getattr(ComplexDeviceHierarchy, name)(self, *args, **kwargs)
+        method.__name__ = name
+        method.__doc__ = getattr(ComplexDeviceHierarchy, name).__doc__
+        return method
+
+    replace_matrix = _served_single("replace_matrix")
+    replace_values = _served_single("replace_values")
+    get_values = _served_single("get_values")
+    rap_level_ms = _served_single("rap_level_ms")
+    del _served_single
 
 
 def complex_lu_arrays(lu):

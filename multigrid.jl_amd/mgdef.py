@@ -49,8 +49,9 @@ class MGparam:
     blockCoarseGMRES: bool = False     # coarseSolveType "GMRES" on a complex hierarchy: serve blocks by the block GMRES coarsest solve
     complexVanka: bool = False         # a Vanka relaxType on a complex hierarchy: the cell-block smoother in the complex cycle
     vankaBlocks: bool = False          # complexVanka only: serve blocks of right-hand sides by the block form of the smoother
-    vankaDeviceSetup: bool = False     # complexVanka only: the cells' blocks are built (and, ComplexF64, refreshed) on the device
+    vankaDeviceSetup: bool = False     # complexVanka only: the cells' blocks are built (and, ComplexF64 or singleDeviceSetup, refreshed) on the device
     coarseDeviceInverse: bool = False  # the coarsest operator's explicit inverse is built (and refreshed) on the device
+    singleDeviceSetup: bool = False    # singlePrecision only: replaceMatrixInHierarchy refreshes the resident hierarchy in HBM
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -64,7 +65,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                coarseSolveType="NoMUMPS", strongConnParam=0.4, FilteringParam=0.0,
                transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
                blockCoarseGMRES: bool = False, complexVanka: bool = False, vankaBlocks: bool = False,
-               vankaDeviceSetup: bool = False, coarseDeviceInverse: bool = False) -> MGparam:
+               vankaDeviceSetup: bool = False, coarseDeviceInverse: bool = False,
+               singleDeviceSetup: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -95,6 +97,12 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     is a no-op where the coarsest solve is not a dense inverse of at most ``coarse_device_inverse_max`` (8192) rows: a solver
     object in ``param.LU`` (Schwarz, parallelJuliaSolver) or a larger coarsest level take today's route.  With
     ``coarseSolveType="GMRES"`` it is refused (there is no inverse to build).  Without it nothing changes.
+    ``singleDeviceSetup=True`` (keyword only, with ``singlePrecision=True``) lets ``replaceMatrixInHierarchy`` of a resident
+    ComplexF32 param with an unchanged pattern recompute the Galerkin products and relaxPrecs in HBM (``mg_rap_CF32``: single
+    values widened on load, ComplexF64 sums, one rounding on the store) and keep the handle, under the conditions of the
+    ComplexF64 path: Jac or SPAI, or a Vanka hierarchy with ``vankaDeviceSetup=True``; the GMRES coarsest solve and
+    ``coarseDeviceInverse`` are refreshed there too.  Without it a ComplexF32 param is recomputed on the host and uploaded again,
+    as before.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
@@ -115,6 +123,9 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     if coarseDeviceInverse and str(coarseSolveType) == "GMRES":
         raise NotImplementedError("coarseDeviceInverse=True builds the coarsest operator's explicit inverse: coarseSolveType='GMRES' "
                                   "has none")
+    if singleDeviceSetup and not singlePrecision:
+        raise NotImplementedError("singleDeviceSetup=True serves a ComplexF32 hierarchy (singlePrecision=True); Float64 and "
+                                  "ComplexF64 hierarchies are refreshed on the device without it")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -130,7 +141,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    transferOperatorType=str(transferOperatorType), singlePrecision=bool(singlePrecision),
                    blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka),
                    vankaBlocks=bool(vankaBlocks), vankaDeviceSetup=bool(vankaDeviceSetup),
-                   coarseDeviceInverse=bool(coarseDeviceInverse), VAL=np.dtype(VAL).type, IND=np.int64)
+                   coarseDeviceInverse=bool(coarseDeviceInverse), singleDeviceSetup=bool(singleDeviceSetup),
+                   VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -204,7 +216,7 @@ def copySolver(MG: MGparam) -> MGparam:
                      MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single,
                      blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka),
                      vankaBlocks=bool(MG.vankaBlocks), vankaDeviceSetup=bool(MG.vankaDeviceSetup),
-                     coarseDeviceInverse=bool(MG.coarseDeviceInverse))
+                     coarseDeviceInverse=bool(MG.coarseDeviceInverse), singleDeviceSetup=bool(MG.singleDeviceSetup))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

@@ -309,13 +309,16 @@ def adjustMemoryForNumRHS(param: MGparam, nrhs: int = 1, verbose: bool = False) 
 def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
     """New fine matrix, same P/R: recompute relaxPrecs, Galerkin products and the coarse LU (MGsetup.jl:226-270).  On a resident
     param with ``coarseDeviceInverse=True`` the explicit inverse of the new coarsest operator is rebuilt in HBM (mg_rap_*); the
-    host still factors it (``param.LU``) and uploads nothing."""
+    host still factors it (``param.LU``) and uploads nothing.  A resident ComplexF32 param takes the device path where it carries
+    ``singleDeviceSetup=True`` (mg_rap_CF32) and the host path with a fresh upload otherwise."""
     relaxParamArr = _relax_param_arr(param)
     A = _of_val(param, A)
-    # (a ComplexF32 hierarchy is recomputed on the host and uploaded again: its device re-setup is out of scope)
-    on_device = param.device is not None and param.relaxType in ("Jac", "Jac-GMRES", "SPAI") and not is_single(param)
-    if param.device is not None and not is_single(param) and is_complex(param) and _is_vanka(param) and getattr(param, "vankaDeviceSetup", False):
-        on_device = True       # (mg_rap_CF64 with the option vanka_device_setup: operators and blocks recomputed in HBM)
+    # (a ComplexF32 hierarchy is recomputed on the host and uploaded again, unless its param asked for the device re-setup:
+    #  singleDeviceSetup, mg_rap_CF32)
+    served = not is_single(param) or bool(getattr(param, "singleDeviceSetup", False))
+    on_device = param.device is not None and param.relaxType in ("Jac", "Jac-GMRES", "SPAI") and served
+    if param.device is not None and served and is_complex(param) and _is_vanka(param) and getattr(param, "vankaDeviceSetup", False):
+        on_device = True       # (mg_rap_CF64 / _CF32 with the option vanka_device_setup: operators and blocks recomputed in HBM)
     if on_device and is_complex(param):
         # (mg_rap_CF64.  A Schwarz coarsest solver borrows a device handle of its own, set up on the coarsest matrix: host path)
         from .mgdef import _solver_object
