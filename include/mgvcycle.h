@@ -1086,7 +1086,7 @@ mg_status mg_block_coarse_form(mg_hierarchy* h, long long nrhs, long long* info)
 /* ---- Jac-GMRES smoothing and the K-cycle on a CF64 handle (MGcycle.jl:35-50,72-76,96-98; FGMRES.jl:48-126) ------------------------
  * mg_set_schedule_CF64 sets cycleType ('V', 'W', 'F' or 'K') and relaxType (0: Jac / SPAI, 1: Jac-GMRES) of a CF64 handle in one
  * call and drops `finalized` (mg_finalize allocates Z / AZ of the relaxations the schedule needs).  Other letters or types:
- * MG_ERR_INVALID; a CF32 handle: MG_ERR_UNSUPPORTED; an FP64 handle: MG_ERR_STATE.  The shared setters keep refusing 'K' and type 1.
+ * MG_ERR_INVALID; a CF32 handle: MG_ERR_UNSUPPORTED (its own form: mg_set_schedule_CF32, below); an FP64 handle: MG_ERR_STATE.  The shared setters keep refusing 'K' and type 1.
  * A relaxation is FGMRES_relaxation with the Jacobi preconditioner d: one kernel launch per direction (the product w = A z_j, the
  * next direction d.*w and the partial sums of column j of H = (AZ)'(AZ) and of xi[j] = dot(w, r0) in one walk over the rows), one
  * launch that sums all partials, ONE host synchronisation per relaxation; the host then replays the reference's loop on the leading
@@ -1104,6 +1104,29 @@ mg_status mg_set_schedule_CF64(mg_hierarchy* h, long long cycleType, long long r
 mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r0, double* x, long long n, long long inner,
                                double tol, double* H_out, double* xi_out, double* rnorms_out, long long* used_out);
 
+/* ---- The same on a CF32 handle, OPT-IN: mg_set_option(h, "single_kcycle", 1) (default 0; read by mg_finalize and at every call) ------
+ * The reference's configuration for Helmholtz - the K-cycle (or Jac-GMRES smoothing) on a ComplexF32 hierarchy, singlePrecision=True.
+ * Without the option a CF32 handle refuses both as before: mg_set_schedule_CF32 and mg_fgmres_relax_CF32 return MG_ERR_UNSUPPORTED, and
+ * so does mg_finalize behind mg_set_vanka_relax_CF32(h, 'K').  With it mg_set_schedule_CF32 takes what mg_set_schedule_CF64 takes, and
+ * mg_finalize accepts 'K' and relaxation type 1 (Z / AZ of the relaxations in complex64: half the bytes; relaxPre / relaxPost above 8
+ * with Jac-GMRES stay MG_ERR_UNSUPPORTED).  Served then, one right-hand side: V / W / F / K with Jac / SPAI / Jac-GMRES, K with the
+ * Vanka smoothers, every coarsest solve a CF32 handle serves, through mg_cycle_CF32, mg_solve_CF32, mg_cycle_dev_CFP64 and the mixed
+ * closure of mg_bicgstab[_dev]_CFP64 / mg_fgmres[_dev]_CFP64; the synchronisations per cycle are those of a CF64 handle.  Still
+ * MG_ERR_UNSUPPORTED: every block entry point on such a schedule, a Schwarz coarsest solve, 'K' / type 1 through the shared setters
+ * mg_set_cycle_type / mg_set_relax_type.
+ * ARITHMETIC.  Z and AZ are complex64; w = A z_j, its products and row sums, and the next direction d.*w are formed in single, in
+ * stored order (the arithmetic of the CF32 sweep and residual kernels).  DEVIATION from the reference, which forms H, xi and the small
+ * least squares in ComplexF32: here the Gram scalars are formed in DOUBLE - w, r0 and AZ_i are widened before they are multiplied, so
+ * every product of two singles is exact and only the fixed-order sums round - and the least squares, the residual estimates and the
+ * break at 1e-5 are the ComplexF64 host algebra.  (In single the estimate cancels down to about sqrt(2^-24) ||r0||: the break would be
+ * noise.)  x += Z t: t in double, the sum of an element formed in double in direction order, rounded once on the store.
+ * mg_fgmres_relax_CF32: as mg_fgmres_relax_CF64 with complex64 r0 and x (n (re, im) float pairs each); H_out, xi_out, rnorms_out stay
+ * double.  Z_out / AZ_out (may be NULL) receive the n x inner column-major complex64 Z and AZ of the relaxation (all inner
+ * directions).  A CF64 or FP64 handle: MG_ERR_STATE. */
+mg_status mg_set_schedule_CF32(mg_hierarchy* h, long long cycleType, long long relaxType);
+mg_status mg_fgmres_relax_CF32(mg_hierarchy* h, long long level, const float* r0, float* x, long long n, long long inner, double tol,
+                               double* H_out, double* xi_out, double* rnorms_out, long long* used_out, float* Z_out, float* AZ_out);
+
 /* ---- The Vanka cell-block smoother in the complex cycle (relaxation type 2; MGcycle.jl:46-52,99-100, Vanka.jl:372-434) -------------
  * mg_set_vanka_CF64 / mg_set_vanka_CF32 bind the cells' blocks of one level of a CF64 / CF32 handle, as mg_set_vanka_FP64 does for a
  * real level and with its checks: As[level] uploaded first (MG_ERR_STATE), no 64-bit row pointers (MG_ERR_UNSUPPORTED), (dim, n,
@@ -1117,7 +1140,7 @@ mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r
  * complex handle MG_ERR_UNSUPPORTED; mg_set_schedule_CF64(h, c, 0 | 1) or mg_set_relax_type(h, 0) afterwards leave Vanka mode.
  * mg_finalize then asks of every non-coarsest level blocks that serve exactly its rows (none: MG_ERR_STATE; another size:
  * MG_ERR_INVALID) and the pointwise slot of mg_set_relax_CF64 / _CF32, which carries relaxPre / relaxPost and whose values nothing
- * reads; 'K' on a CF32 handle is MG_ERR_UNSUPPORTED.  The cycle runs relaxPre / relaxPost Vanka iterations of x in place from the
+ * reads; 'K' on a CF32 handle is MG_ERR_UNSUPPORTED unless its option single_kcycle is set.  The cycle runs relaxPre / relaxPost Vanka iterations of x in place from the
  * level's own CSR (a count of 0: none).  A level entered with x = 0 is zero-filled and its first pass reads b and the blocks only (no
  * matrix walk; the one pass of FULL_VANKA_ADD altogether) - bit-identical to the general pass on a zero x, which x_is_zero = 0 runs.
  * Served: mg_cycle_*, mg_solve_*, the _CFP64 drivers and their _dev forms.  MG_ERR_UNSUPPORTED: every block entry point
@@ -1249,7 +1272,7 @@ int mg_cblk_gram_dev_CFP64(const double* x_dev, const double* y_dev, long long n
  * Refusals.  A _CF32 entry point on a CF64 or FP64 handle, and mg_set_operator_CF64_INT64 / mg_set_relax_CF64 / mg_cycle_CF64 /
  * mg_solve_CF64 / mg_spmv_CF64 / mg_set_operator_FP64_INT64 on a CF32 handle: MG_ERR_STATE.  Not served for a CF32 handle
  * (MG_ERR_UNSUPPORTED): mg_rap_CF64, mg_rap_level_ms_CF64, mg_get_values_CF64, mg_get_relax_CF64, mg_replace_values_CF64 (their
- * _CF32 forms above serve it), mg_set_coarse_dd (a Schwarz coarsest solve), the K-cycle, Jac-GMRES,
+ * _CF32 forms above serve it), mg_set_coarse_dd (a Schwarz coarsest solve), the K-cycle and Jac-GMRES (served with the option single_kcycle, see mg_set_schedule_CF32),
  * nrhs > 1 in the entry points of this section (blocks: mg_block_cycle_dev_CFP64 and mg_block_bicgstab[_dev]_CFP64 below), and
  * whatever a CF64 handle does not serve. */
 int mg_create_CF32(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out);

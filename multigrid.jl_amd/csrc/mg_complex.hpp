@@ -14,7 +14,7 @@
 // in stored order, then applies the fused epilogue.  Workgroups are banded per XCD (xcd_band).  A row longer than a
 // chunk has a block of its own and the whole workgroup strides over it.
 // Epilogues: AXPBY, RESID (optionally also z1 = d.*r), SMOOTH, and GRAM - one step of the FGMRES relaxation (Jac-GMRES smoothing,
-// K-cycle; ComplexF64 only): w = A z_j stored as column j of AZ, the next direction d.*w, and the per-row-block partial sums of
+// K-cycle; ComplexF64, and ComplexF32 where the handle's option single_kcycle is set): w = A z_j stored as column j of AZ, the next direction d.*w, and the per-row-block partial sums of
 // column j of H = (AZ)'(AZ) and of xi[j] = dot(w, r0), see CxVecArgsT.
 // CGDOT - one Arnoldi step of the GMRES coarsest solve (coarseSolveType "GMRES"; ComplexF64 only): w = A z_i stored as the next
 // basis vector, and the per-row-block partial sums of dot(v_0, w), the first coefficient of the Gram-Schmidt chain that follows
@@ -48,6 +48,9 @@ __device__ __forceinline__ d2_t cdiv(d2_t a, d2_t b) {
 }
 __device__ __forceinline__ double cabs2(d2_t a) { return a.x * a.x + a.y * a.y; }
 __device__ __forceinline__ double cabs2(f2_t a) { return (double)a.x * (double)a.x + (double)a.y * (double)a.y; }   // exact products
+// a value widened to double: every product of two widened singles is exact
+__device__ __forceinline__ d2_t cwide(d2_t a) { return a; }
+__device__ __forceinline__ d2_t cwide(f2_t a) { return d2_t{(double)a.x, (double)a.y}; }
 __device__ __forceinline__ d2_t shfl_xor_v(d2_t a, int o) { return d2_t{__shfl_xor(a.x, o), __shfl_xor(a.y, o)}; }
 __device__ __forceinline__ f2_t shfl_xor_v(f2_t a, int o) { return f2_t{__shfl_xor(a.x, o), __shfl_xor(a.y, o)}; }
 
@@ -62,7 +65,7 @@ struct CxCsrDev {
   int n_rows;
 };
 
-// GRAM (cx_csr_stream_spmv only, ComplexF64): step j of FGMRES_relaxation (FGMRES.jl:82-104) in the walk that computes w = A z_j.
+// GRAM (cx_csr_stream_spmv only; both pair types): step j of FGMRES_relaxation (FGMRES.jl:82-104) in the walk that computes w = A z_j.
 // The mode follows mgk::Mode (AXPBY, RESID, SMOOTH) and is served by no other kernel.
 constexpr int GRAM = 3;
 constexpr int GRAM_MAXV = 8;                       // directions of one relaxation at most (mgcv::MAXV, the width of the combination pass)
@@ -125,17 +128,22 @@ __device__ __forceinline__ void cx_operands(const CxVecArgsT<C>& v, int row, C& 
   if (MODE == RESID && v.z1) pd = v.d[row];
 }
 
-// the Gram scalars of one row: s[0 .. 2 j + 3) for w = (A z_j)[row], azv[i] = AZ_i[row], r0v = r0[row]
+// the Gram scalars of one row: s[0 .. 2 j + 3) for w = (A z_j)[row], azv[i] = AZ_i[row], r0v = r0[row].
+// The operands are widened to double BEFORE they are multiplied (cwide), so on a ComplexF32 hierarchy every product is exact and only
+// the sums round - in double.  (The reference forms H in ComplexF32, where the estimate rn = sqrt|t'Ht - 2t'xi + ||r0||^2| cancels
+// down to about sqrt(2^-24) ||r0|| and the break at rn < 1e-5 is noise; see the README.)
 template <typename C>
-__device__ __forceinline__ void cx_gram_row(double* s, int j, const C* azv, C w, C r0v) {
-  s[0] = cabs2(w);
-  s[1] = w.x * r0v.x + w.y * r0v.y;
-  s[2] = w.x * r0v.y - w.y * r0v.x;
+__device__ __forceinline__ void cx_gram_row(double* s, int j, const C* azv, C wv, C r0v) {
+  const d2_t w = cwide(wv), r = cwide(r0v);
+  s[0] = cabs2(wv);
+  s[1] = w.x * r.x + w.y * r.y;
+  s[2] = w.x * r.y - w.y * r.x;
 #pragma unroll
   for (int i = 0; i < GRAM_MAXV - 1; ++i)
     if (i < j) {
-      s[3 + 2 * i] = azv[i].x * w.x + azv[i].y * w.y;
-      s[4 + 2 * i] = azv[i].x * w.y - azv[i].y * w.x;
+      const d2_t a = cwide(azv[i]);
+      s[3 + 2 * i] = a.x * w.x + a.y * w.y;
+      s[4 + 2 * i] = a.x * w.y - a.y * w.x;
     }
 }
 
@@ -671,13 +679,15 @@ __global__ __launch_bounds__(BLK) void cx_sumsq_partial(const C* __restrict__ z,
 // z = d.*b with the partials of sum |b_i|^2, one per workgroup: the front of an FGMRES relaxation from x = 0 (r0 = b; z_1 = MM(r0),
 // rnorm0 = norm(r0), FGMRES.jl:65,84).  Grid-stride, so any grid covers n; the host launches one workgroup per row block of the
 // level's operator, which is the stride of the relaxation's partial sums.
-__global__ __launch_bounds__(BLK) void cx_dscale_sumsq(const d2_t* __restrict__ d, const d2_t* __restrict__ b, d2_t* __restrict__ z, long long n,
+// (C = f2_t: the product in single, the partials in double all the same.)
+template <typename C>
+__global__ __launch_bounds__(BLK) void cx_dscale_sumsq(const C* __restrict__ d, const C* __restrict__ b, C* __restrict__ z, long long n,
                                                        double* __restrict__ partial) {
   __shared__ double red[BLK / 64];
   const long long stride = (long long)gridDim.x * BLK;
   double acc = 0.0;
   for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) {
-    const d2_t bv = b[i];
+    const C bv = b[i];
     z[i] = cmul(d[i], bv);
     acc += cabs2(bv);
   }

@@ -1,6 +1,6 @@
 // mg_complex.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F / K cycles,
-// pointwise, Jac-GMRES or Vanka relaxation (K and Jac-GMRES: CF64 handles, one right-hand side; Vanka: both precisions, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
+// pointwise, Jac-GMRES or Vanka relaxation (K and Jac-GMRES: one right-hand side, CF64 handles and - option single_kcycle - CF32 ones; Vanka: both precisions, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
 // (the last: one host synchronisation per solve; blocks of right-hand sides by its block form where the option coarse_gmres_blocks asks for it).  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
 // The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
@@ -736,7 +736,8 @@ int cx_vanka_relax(mg_hierarchy* h, CxLevel& L, const C* b, C* x, long long numi
                          h->play->stream);
 }
 
-// ---- FGMRES_relaxation (FGMRES.jl:48-126) for VAL = ComplexF64: Jac-GMRES smoothing and the K-cycle -----------------------------------
+// ---- FGMRES_relaxation (FGMRES.jl:48-126): Jac-GMRES smoothing and the K-cycle, written once over the pair type C --------------------
+// (C = cf_t, option single_kcycle: Z, AZ, the product and d.*w in single; the Gram scalars, the least squares and t in double.)
 // One launch per direction (the GRAM epilogue of cx_csr_stream_spmv: w = A z_j, z_{j+1} = d.*w, the partials of column j of H and of
 // xi[j]), one final sum over all scalars of the steps enqueued so far, one readback, ONE host synchronisation; the small least squares
 // is host algebra (RelaxLsqC, mg_krylov_host.hpp).
@@ -757,15 +758,19 @@ int cx_gram_ensure(mg_hierarchy* h, size_t nblocks) {
 }
 
 // step j: w = A z into column j of AZ, znext = d.*w (null: the last direction, or a preconditioner that is a cycle)
-int cx_gram_step(mg_hierarchy* h, const CxLevel& L, const cx_t* z, cx_t* AZ, int j, const cx_t* r0, cx_t* znext) {
+// C: the pair type of the level (cx_t or cf_t), deduced from z
+template <typename C>
+int cx_gram_step(mg_hierarchy* h, const CxLevel& L, const C* z, typename cx_non_deduced<C>::type* AZ, int j,
+                 const typename cx_non_deduced<C>::type* r0, typename cx_non_deduced<C>::type* znext) {
   CxState& S = *h->cx;
   const CxMat& M = L.A;
   if (j < 0 || j >= mgk::GRAM_MAXV) return fail(MG_ERR_INVALID, "internal: direction %d of an FGMRES relaxation", j);
   if (S.gpart.n < (size_t)CxState::GSCAL * (size_t)M.nblocks) return fail(MG_ERR_STATE, "internal: the relaxation's partial sums are not sized");
-  mgk::CxVecArgsT<cx_t> v = {};
+  if (M.single != (sizeof(C) == sizeof(cf_t))) return fail(MG_ERR_INVALID, "internal: operator and vectors differ in precision");
+  mgk::CxVecArgsT<C> v = {};
   v.x = z;
   v.y = AZ + (size_t)j * (size_t)L.n;
-  v.d = cxc(L.d);
+  v.d = cxc<C>(L.d);
   v.beta_zero = 1;
   v.az = AZ;
   v.ldz = L.n;
@@ -774,15 +779,15 @@ int cx_gram_step(mg_hierarchy* h, const CxLevel& L, const cx_t* z, cx_t* AZ, int
   v.znext = znext;
   v.gpart = S.gpart.p + (size_t)cx_gram_slot(j) * (size_t)M.nblocks;
   if (M.wide) {
-    mgk::CxCsrDev<long long, cx_t> D;
-    D.rowptr = M.rowptr64.p; D.colidx = M.colidx.p; D.val = static_cast<const cx_t*>(M.vals()); D.blk_row = M.blk_row.p;
+    mgk::CxCsrDev<long long, C> D;
+    D.rowptr = M.rowptr64.p; D.colidx = M.colidx.p; D.val = static_cast<const C*>(M.vals()); D.blk_row = M.blk_row.p;
     D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
-    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, long long, cx_t, cx_t>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, long long, C, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
   } else {
-    mgk::CxCsrDev<int, cx_t> D;
-    D.rowptr = M.rowptr.p; D.colidx = M.colidx.p; D.val = static_cast<const cx_t*>(M.vals()); D.blk_row = M.blk_row.p;
+    mgk::CxCsrDev<int, C> D;
+    D.rowptr = M.rowptr.p; D.colidx = M.colidx.p; D.val = static_cast<const C*>(M.vals()); D.blk_row = M.blk_row.p;
     D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
-    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, int, cx_t, cx_t>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
+    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, int, C, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
   }
   HIP_TRY(hipGetLastError());
   return MG_OK;
@@ -810,6 +815,21 @@ inline void cx_gram_fill(RelaxLsqC& Q, int j, const double* s) {
 }
 
 // x += sum_{j < used} t_j Z_j in one pass (mgcv::OpCGsUpdate with h = -t; its ||x||^2 partial lands in the relaxation's own buffer, unread)
+// (cf_t: mgcv::OpCRelaxCombineF - complex64 x and Z, the sum of an element in double, rounded once on the store)
+int cx_relax_combine(mg_hierarchy* h, const RelaxLsqC& Q, int used, const cf_t* Z, cf_t* x, long long n) {
+  mgcv::OpCRelaxCombineF op;
+  op.m = used;
+  op.x = x;
+  for (int j = 0; j < mgcv::MAXV; ++j) {
+    const int jj = j < used ? j : 0;
+    op.t[j] = j < used ? cx_t{Q.t()[(size_t)j].real(), Q.t()[(size_t)j].imag()} : cx_t{0.0, 0.0};
+    op.z[j] = Z + (size_t)jj * (size_t)n;
+  }
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(mgcv::cxv_pass<mgcv::OpCRelaxCombineF>), dim3((unsigned)mgcv::cxv_grid(n)), dim3(mgcv::KB), 0, h->play->stream, op,
+                     n, h->cx->gpart.p);
+  HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
 int cx_relax_combine(mg_hierarchy* h, const RelaxLsqC& Q, int used, const cx_t* Z, cx_t* x, long long n) {
   mgcv::OpCGsUpdate op;
   op.m = used;
@@ -837,8 +857,9 @@ struct CxRelaxReport {
 // enqueued back to back - step j + 1 needs w_j only, never t - and the host replays the reference's loop on the leading blocks of H:
 // at step j the (j+1) x (j+1) solve, break at the first rn < tol (FGMRES.jl:114-117), used = j + 1.  Directions beyond `used` are
 // not read (the reference's zero-padded H gives the same t).
-int cx_fgmres_relax(mg_hierarchy* h, const CxLevel& L, const cx_t* r0, cx_t* x, int inner, double tol, cx_t* Z, cx_t* AZ,
-                    CxRelaxReport* report = nullptr) {
+template <typename C>
+int cx_fgmres_relax(mg_hierarchy* h, const CxLevel& L, const C* r0, typename cx_non_deduced<C>::type* x, int inner, double tol,
+                    typename cx_non_deduced<C>::type* Z, typename cx_non_deduced<C>::type* AZ, CxRelaxReport* report = nullptr) {
   if (inner <= 0) return MG_OK;   // w = Z*t with no columns: x unchanged (FGMRES.jl:119-123)
   if (inner > mgk::GRAM_MAXV) return fail(MG_ERR_UNSUPPORTED, "an FGMRES relaxation of %d directions (at most %d)", inner, mgk::GRAM_MAXV);
   const size_t n = (size_t)L.n;
@@ -861,8 +882,9 @@ int cx_fgmres_relax(mg_hierarchy* h, const CxLevel& L, const cx_t* r0, cx_t* x, 
 }
 
 // z_1 = d.*b with the partials of ||b||^2 (scalar 0): the front of a relaxation from x = 0, where r0 = b
-int cx_relax_front_zero(mg_hierarchy* h, const CxLevel& L, const cx_t* b, cx_t* Z) {
-  hipLaunchKernelGGL(mgk::cx_dscale_sumsq, dim3((unsigned)L.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, cxc(L.d), b, Z, L.n, h->cx->gpart.p);
+template <typename C>
+int cx_relax_front_zero(mg_hierarchy* h, const CxLevel& L, const C* b, typename cx_non_deduced<C>::type* Z) {
+  hipLaunchKernelGGL(mgk::cx_dscale_sumsq<C>, dim3((unsigned)L.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, Z, L.n, h->cx->gpart.p);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -881,8 +903,8 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   constexpr bool is64 = sizeof(typename mgk::cx_scalar<C>::type) == sizeof(double);
   const bool gmres_relax = h->relax_type == 1;   // Jac-GMRES (MGcycle.jl:35-38, 48-50, 96-98)
   const double gmresTol = 1e-5;                  // l.5
-  if ((gmres_relax || ctype == 'K') && (!is64 || nr != 0))
-    return fail(MG_ERR_UNSUPPORTED, "Jac-GMRES smoothing and the K-cycle serve CF64 handles and one right-hand side");
+  if ((gmres_relax || ctype == 'K') && ((!is64 && !h->opt.single_kcycle) || nr != 0))
+    return fail(MG_ERR_UNSUPPORTED, "Jac-GMRES smoothing and the K-cycle serve CF64 handles (CF32 ones with the option single_kcycle) and one right-hand side");
   const bool vanka_relax = h->relax_type == 2;   // Vanka (l.51-52, 99-100): x relaxed in place, no ping-pong
   if (vanka_relax && nr != 0 && !h->opt.vanka_blocks) return fail(MG_ERR_UNSUPPORTED, "Vanka relaxation (type 2) serves one right-hand side");
   if (vanka_relax) {   // (a block, option vanka_blocks: the block form of the smoother on Bx, in place as well)
@@ -890,15 +912,13 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
     if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * (size_t)L.n * (size_t)std::max(nr, 1), h->play->stream));
     MG_TRY(cx_vanka_relax<C>(h, L, b, x, L.npre, xzero, nr));
   } else if (gmres_relax) {
-    if constexpr (is64) {
-      // r = b - A x (l.28-31) with ||r||^2 and z_1 = d.*r from the same pass; from x = 0, r0 = b
-      cx_t* x = cxp(L.x[xi]);
-      if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(cx_t) * (size_t)L.n, h->play->stream));
-      if (L.npre > 0) {
-        if (xzero) MG_TRY(cx_relax_front_zero(h, L, b, cxp(L.relaxZ)));
-        else MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const cx_t*)x, cxp(L.r), b, cxc(L.d), S.gpart.p, one, zero, 0, cxp(L.relaxZ)));
-        MG_TRY(cx_fgmres_relax(h, L, xzero ? b : cxc(L.r), x, (int)L.npre, gmresTol, cxp(L.relaxZ), cxp(L.relaxAZ)));
-      }
+    // r = b - A x (l.28-31) with ||r||^2 and z_1 = d.*r from the same pass; from x = 0, r0 = b
+    C* x = cxp<C>(L.x[xi]);
+    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * (size_t)L.n, h->play->stream));
+    if (L.npre > 0) {
+      if (xzero) MG_TRY(cx_relax_front_zero<C>(h, L, b, cxp<C>(L.relaxZ)));
+      else MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const C*)x, cxp<C>(L.r), b, cxc<C>(L.d), S.gpart.p, one, zero, 0, cxp<C>(L.relaxZ)));
+      MG_TRY(cx_fgmres_relax<C>(h, L, xzero ? b : cxc<C>(L.r), x, (int)L.npre, gmresTol, cxp<C>(L.relaxZ), cxp<C>(L.relaxAZ)));
     }
   } else {
     MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre, nr));                                  // l.26-31, 54
@@ -914,33 +934,31 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
     // K-cycle (l.72-76): two FGMRES steps on A_{l+1} xc = bc from xc = 0, preconditioned by the K-cycle of level l+1 from zero.  Each
     // step: one inner cycle, its result copied into Z, one GRAM launch (no znext: the preconditioner is a cycle), one synchronisation -
     // so the break after step 1 costs no speculative sub-cycle.
-    if constexpr (is64) {
-      const size_t n1 = (size_t)C1.n;
-      cx_t *Z = cxp(C1.kZ), *AZ = cxp(C1.kAZ);
-      RelaxLsqC Q(2);
-      double rnorm0 = 0.0;
-      int used = 0;
-      for (int j = 0; j < 2; ++j) {
-        int cj = 0;
-        MG_TRY(cx_cycle<C>(h, l + 1, j == 0 ? bc : (const cx_t*)AZ, cj, true, 'K', 0));      // z = MMG(r0) / MMG(w)  (FGMRES.jl:83-87)
-        HIP_TRY(hipMemcpyAsync(Z + (size_t)j * n1, C1.x[cj].p, sizeof(cx_t) * n1, hipMemcpyDeviceToDevice, h->play->stream));
-        if (j == 0) {                                                                         // rnorm0 = norm(r0)  (l.65)
-          hipLaunchKernelGGL(mgk::cx_sumsq_partial<cx_t>, dim3((unsigned)C1.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, bc, C1.n, S.gpart.p);
-          HIP_TRY(hipGetLastError());
-        }
-        MG_TRY(cx_gram_step(h, C1, Z + (size_t)j * n1, AZ, j, bc, nullptr));
-        const double* s = nullptr;
-        MG_TRY(cx_gram_read(h, j == 0 ? 0 : cx_gram_slot(1), j == 0 ? cx_gram_slot(1) : 5, C1.A.nblocks, &s));
-        if (j == 0) rnorm0 = std::sqrt(s[0]);
-        cx_gram_fill(Q, j, s);
-        const double rn = Q.step(j + 1, rnorm0);
-        used = j + 1;
-        if (rn < gmresTol) break;                                                             // l.114-117
+    const size_t n1 = (size_t)C1.n;
+    C *Z = cxp<C>(C1.kZ), *AZ = cxp<C>(C1.kAZ);
+    RelaxLsqC Q(2);
+    double rnorm0 = 0.0;
+    int used = 0;
+    for (int j = 0; j < 2; ++j) {
+      int cj = 0;
+      MG_TRY(cx_cycle<C>(h, l + 1, j == 0 ? bc : (const C*)AZ, cj, true, 'K', 0));          // z = MMG(r0) / MMG(w)  (FGMRES.jl:83-87)
+      HIP_TRY(hipMemcpyAsync(Z + (size_t)j * n1, C1.x[cj].p, sizeof(C) * n1, hipMemcpyDeviceToDevice, h->play->stream));
+      if (j == 0) {                                                                         // rnorm0 = norm(r0)  (l.65)
+        hipLaunchKernelGGL(mgk::cx_sumsq_partial<C>, dim3((unsigned)C1.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, bc, C1.n, S.gpart.p);
+        HIP_TRY(hipGetLastError());
       }
-      ci = 0;                                                                                 // xc = 0 + Z t  (l.121-123)
-      HIP_TRY(hipMemsetAsync(C1.x[ci].p, 0, sizeof(cx_t) * n1, h->play->stream));
-      MG_TRY(cx_relax_combine(h, Q, used, Z, cxp(C1.x[ci]), C1.n));
+      MG_TRY(cx_gram_step<C>(h, C1, Z + (size_t)j * n1, AZ, j, bc, nullptr));
+      const double* s = nullptr;
+      MG_TRY(cx_gram_read(h, j == 0 ? 0 : cx_gram_slot(1), j == 0 ? cx_gram_slot(1) : 5, C1.A.nblocks, &s));
+      if (j == 0) rnorm0 = std::sqrt(s[0]);
+      cx_gram_fill(Q, j, s);
+      const double rn = Q.step(j + 1, rnorm0);
+      used = j + 1;
+      if (rn < gmresTol) break;                                                             // l.114-117
     }
+    ci = 0;                                                                                 // xc = 0 + Z t  (l.121-123)
+    HIP_TRY(hipMemsetAsync(C1.x[ci].p, 0, sizeof(C) * n1, h->play->stream));
+    MG_TRY(cx_relax_combine(h, Q, used, Z, cxp<C>(C1.x[ci]), C1.n));
   } else {
     MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, true, ctype, nr));                                // xc = 0 (l.63-64), l.78
     if (ctype == 'W') MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, false, 'W', nr));               // l.79-80
@@ -950,12 +968,10 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(cx_lx(C1, nr, ci)), cxp<C>(cx_lx(L, nr, xi)), nullptr, nullptr, nullptr, one, one, nr));
   if (vanka_relax) return cx_vanka_relax<C>(h, L, b, cxp<C>(cx_lx(L, nr, xi)), L.npost, false, nr);   // l.99-100
   if (gmres_relax) {                                                                      // r = b - A x, FGMRES_relaxation (l.92-98)
-    if constexpr (is64) {
-      if (L.npost > 0) {
-        cx_t* x = cxp(L.x[xi]);
-        MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const cx_t*)x, cxp(L.r), b, cxc(L.d), S.gpart.p, one, zero, 0, cxp(L.relaxZ)));
-        MG_TRY(cx_fgmres_relax(h, L, cxc(L.r), x, (int)L.npost, gmresTol, cxp(L.relaxZ), cxp(L.relaxAZ)));
-      }
+    if (L.npost > 0) {
+      C* x = cxp<C>(L.x[xi]);
+      MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const C*)x, cxp<C>(L.r), b, cxc<C>(L.d), S.gpart.p, one, zero, 0, cxp<C>(L.relaxZ)));
+      MG_TRY(cx_fgmres_relax<C>(h, L, cxc<C>(L.r), x, (int)L.npost, gmresTol, cxp<C>(L.relaxZ), cxp<C>(L.relaxAZ)));
     }
     return MG_OK;
   }
@@ -1109,8 +1125,10 @@ int cx_finalize(mg_hierarchy* h) {
     S.K.release();
     S.K_auto = false;
   }
-  if (S.single && h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF32 handles");
-  if (S.single && h->relax_type == 1) return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF32 handles");
+  // (the option single_kcycle lifts both refusals: the GRAM step, its front and its combination pass in single)
+  if (S.single && !h->opt.single_kcycle && h->cycle == 'K') return fail(MG_ERR_UNSUPPORTED, "cycle 'K' is not served for CF32 handles");
+  if (S.single && !h->opt.single_kcycle && h->relax_type == 1)
+    return fail(MG_ERR_UNSUPPORTED, "relaxation type 1 (Jac-GMRES) is not served for CF32 handles");
   if (h->relax_type != 0 && h->relax_type != 1 && h->relax_type != 2)
     return fail(MG_ERR_UNSUPPORTED, "relaxation type %d is not served for complex handles", h->relax_type);
   size_t maxblocks = 1;
@@ -1177,7 +1195,7 @@ int cx_finalize(mg_hierarchy* h) {
     if (m > mgk::GRAM_MAXV)
       return fail(MG_ERR_UNSUPPORTED, "relaxPre / relaxPost = %lld on level %d: a complex Jac-GMRES relaxation takes at most %d directions", m, l + 1,
                   mgk::GRAM_MAXV);
-    const size_t zlen = 2 * (size_t)m * (size_t)L.n, klen = (kcycle && l >= 1 && l < nl - 1) ? 4 * (size_t)L.n : 0;
+    const size_t zlen = (size_t)m * cx_len(S, L.n), klen = (kcycle && l >= 1 && l < nl - 1) ? 2 * cx_len(S, L.n) : 0;
     for (DevBuf<double>* d : {&L.relaxZ, &L.relaxAZ}) {
       if (zlen == 0) d->release();
       else if (d->n != zlen) MG_TRY(d->alloc(zlen));
@@ -1969,7 +1987,7 @@ int cx_set_vanka_relax(mg_hierarchy* h, CxWant want, long long cycleType) {
   MG_TRY(cx_handle_ok(h, want));
   if (cycleType != 'V' && cycleType != 'W' && cycleType != 'F' && cycleType != 'K')
     return fail(MG_ERR_INVALID, "cycleType must be 'V', 'W', 'F' or 'K'");
-  h->cycle = (char)cycleType;   // ('K' on a CF32 handle: refused by mg_finalize, as everywhere)
+  h->cycle = (char)cycleType;   // ('K' on a CF32 handle: refused by mg_finalize unless the option single_kcycle is set)
   h->relax_type = 2;
   h->cx->finalized = false;
   return MG_OK;
@@ -1986,6 +2004,65 @@ int cx_create(long long nlevels, long long nrhs, long long device_id, mg_hierarc
   h->cx->single = single;
   h->cx->lev.resize((size_t)nlevels);
   *out = h;
+  return MG_OK;
+}
+
+// FGMRES_relaxation with the diagonal preconditioner on one level, host vectors of the handle's precision (T: double or float, (re, im)
+// interleaved): x += Z t.  Z_out / AZ_out (optional): the n x inner column-major bases of the relaxation.
+template <typename C, typename T>
+int cx_fgmres_relax_host(mg_hierarchy* h, long long level, const T* r0, T* x, long long n, long long inner, double tol, double* H_out,
+                         double* xi_out, double* rnorms_out, long long* used_out, T* Z_out, T* AZ_out) {
+  MG_TRY(cx_level_ok(h, level, sizeof(C) == sizeof(cf_t) ? CX_WANT32 : CX_WANT64));
+  CxState& S = *h->cx;
+  if (S.single && !h->opt.single_kcycle) return fail(MG_ERR_UNSUPPORTED, "mg_fgmres_relax_CF32 is not served for CF32 handles without the option single_kcycle");
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  if (level >= h->nlevels) return fail(MG_ERR_INVALID, "level %lld holds no relaxPrecs (the coarsest level is solved, not relaxed)", level);
+  if (inner < 1 || inner > mgk::GRAM_MAXV) return fail(MG_ERR_INVALID, "inner=%lld outside 1..%d", inner, mgk::GRAM_MAXV);
+  if (!r0 || !x) return fail(MG_ERR_INVALID, "null vector");
+  CxLevel& L = S.lev[(size_t)level - 1];
+  if (n != L.n) return fail(MG_ERR_INVALID, "n=%lld does not match level %lld (%lld rows)", n, level, L.n);
+  (void)hipSetDevice(h->device);
+  MG_TRY(cx_gram_ensure(h, (size_t)L.A.nblocks));
+  const hipStream_t st = h->play->stream;
+  const int k = (int)inner;
+  const size_t bytes = sizeof(C) * (size_t)n;
+  DevBuf<double> dr, dx, dZ, dAZ;   // (released below on every path)
+  RelaxLsqC Q(k);
+  std::vector<double> rn((size_t)k, 0.0);
+  CxRelaxReport report;
+  report.Q = &Q;
+  report.rnorms = rn.data();
+  int rc = dr.alloc(cx_len(S, n));
+  if (rc == MG_OK) rc = dx.alloc(cx_len(S, n));
+  if (rc == MG_OK) rc = dZ.alloc(cx_len(S, n) * (size_t)k);
+  if (rc == MG_OK) rc = dAZ.alloc(cx_len(S, n) * (size_t)k);
+  if (rc == MG_OK && (hipMemcpyAsync(dr.p, r0, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+                      hipMemcpyAsync(dx.p, x, bytes, hipMemcpyHostToDevice, st) != hipSuccess))
+    rc = fail(MG_ERR_HIP, "upload of r0 / x failed");
+  if (rc == MG_OK) rc = cx_relax_front_zero<C>(h, L, cxc<C>(dr), cxp<C>(dZ));
+  if (rc == MG_OK) rc = cx_fgmres_relax<C>(h, L, cxc<C>(dr), cxp<C>(dx), k, tol, cxp<C>(dZ), cxp<C>(dAZ), &report);
+  if (rc == MG_OK && hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MG_ERR_HIP, "download of x failed");
+  if (rc == MG_OK && Z_out && hipMemcpyAsync(Z_out, dZ.p, bytes * (size_t)k, hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "download of Z failed");
+  if (rc == MG_OK && AZ_out && hipMemcpyAsync(AZ_out, dAZ.p, bytes * (size_t)k, hipMemcpyDeviceToHost, st) != hipSuccess)
+    rc = fail(MG_ERR_HIP, "download of AZ failed");
+  if (spin_sync(st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_fgmres_relax_%s: stream failed", sizeof(C) == sizeof(cf_t) ? "CF32" : "CF64");
+  dr.release(); dx.release(); dZ.release(); dAZ.release();
+  if (rc != MG_OK) return rc;
+  for (int j = report.used; j < k; ++j) cx_gram_fill(Q, j, S.h_gscal);   // (the directions behind a break: summed, not used)
+  if (H_out)
+    for (int a = 0; a < k * k; ++a) {
+      H_out[2 * a] = Q.H[(size_t)a].real();
+      H_out[2 * a + 1] = Q.H[(size_t)a].imag();
+    }
+  if (xi_out)
+    for (int a = 0; a < k; ++a) {
+      xi_out[2 * a] = Q.xi[(size_t)a].real();
+      xi_out[2 * a + 1] = Q.xi[(size_t)a].imag();
+    }
+  if (rnorms_out)
+    for (int a = 0; a < k; ++a) rnorms_out[a] = a < report.used ? rn[(size_t)a] : 0.0;
+  if (used_out) *used_out = report.used;
   return MG_OK;
 }
 
@@ -2045,6 +2122,18 @@ int mg_set_schedule_CF64(mg_hierarchy* h, long long cycleType, long long relaxTy
   h->cx->finalized = false;
   return MG_OK;
 }
+// The same for a CF32 handle whose option single_kcycle is set (MG_ERR_UNSUPPORTED without it)
+int mg_set_schedule_CF32(mg_hierarchy* h, long long cycleType, long long relaxType) {
+  MG_TRY(cx_handle_ok(h, CX_WANT32));
+  if (!h->opt.single_kcycle) return fail(MG_ERR_UNSUPPORTED, "mg_set_schedule_CF32 is not served for CF32 handles without the option single_kcycle");
+  if (cycleType != 'V' && cycleType != 'W' && cycleType != 'F' && cycleType != 'K')
+    return fail(MG_ERR_INVALID, "cycleType must be 'V', 'W', 'F' or 'K'");
+  if (relaxType != 0 && relaxType != 1) return fail(MG_ERR_INVALID, "relaxType must be 0 (Jac / SPAI) or 1 (Jac-GMRES) on a CF32 handle");
+  h->cycle = (char)cycleType;
+  h->relax_type = (int)relaxType;
+  h->cx->finalized = false;
+  return MG_OK;
+}
 
 // The Vanka blocks of one level of a complex handle (relaxation type 2): see include/mgvcycle.h
 int mg_set_vanka_CF64(mg_hierarchy* h, long long level, long long dim, const long long* n, long long includePressure, long long VankaType,
@@ -2079,53 +2168,13 @@ int mg_set_vanka_relax_CF32(mg_hierarchy* h, long long cycleType) { return cx_se
 // FGMRES_relaxation with the diagonal preconditioner on one level, host vectors: x += Z t
 int mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r0, double* x, long long n, long long inner, double tol,
                          double* H_out, double* xi_out, double* rnorms_out, long long* used_out) {
-  MG_TRY(cx_level_ok(h, level));
-  CxState& S = *h->cx;
-  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
-  if (level >= h->nlevels) return fail(MG_ERR_INVALID, "level %lld holds no relaxPrecs (the coarsest level is solved, not relaxed)", level);
-  if (inner < 1 || inner > mgk::GRAM_MAXV) return fail(MG_ERR_INVALID, "inner=%lld outside 1..%d", inner, mgk::GRAM_MAXV);
-  if (!r0 || !x) return fail(MG_ERR_INVALID, "null vector");
-  CxLevel& L = S.lev[(size_t)level - 1];
-  if (n != L.n) return fail(MG_ERR_INVALID, "n=%lld does not match level %lld (%lld rows)", n, level, L.n);
-  (void)hipSetDevice(h->device);
-  MG_TRY(cx_gram_ensure(h, (size_t)L.A.nblocks));
-  const hipStream_t st = h->play->stream;
-  const int k = (int)inner;
-  const size_t bytes = sizeof(cx_t) * (size_t)n;
-  DevBuf<double> dr, dx, dZ, dAZ;   // (released below on every path)
-  RelaxLsqC Q(k);
-  std::vector<double> rn((size_t)k, 0.0);
-  CxRelaxReport report;
-  report.Q = &Q;
-  report.rnorms = rn.data();
-  int rc = dr.alloc(2 * (size_t)n);
-  if (rc == MG_OK) rc = dx.alloc(2 * (size_t)n);
-  if (rc == MG_OK) rc = dZ.alloc(2 * (size_t)n * (size_t)k);
-  if (rc == MG_OK) rc = dAZ.alloc(2 * (size_t)n * (size_t)k);
-  if (rc == MG_OK && (hipMemcpyAsync(dr.p, r0, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-                      hipMemcpyAsync(dx.p, x, bytes, hipMemcpyHostToDevice, st) != hipSuccess))
-    rc = fail(MG_ERR_HIP, "upload of r0 / x failed");
-  if (rc == MG_OK) rc = cx_relax_front_zero(h, L, cxc(dr), cxp(dZ));
-  if (rc == MG_OK) rc = cx_fgmres_relax(h, L, cxc(dr), cxp(dx), k, tol, cxp(dZ), cxp(dAZ), &report);
-  if (rc == MG_OK && hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MG_ERR_HIP, "download of x failed");
-  if (spin_sync(st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_fgmres_relax_CF64: stream failed");
-  dr.release(); dx.release(); dZ.release(); dAZ.release();
-  if (rc != MG_OK) return rc;
-  for (int j = report.used; j < k; ++j) cx_gram_fill(Q, j, S.h_gscal);   // (the directions behind a break: summed, not used)
-  if (H_out)
-    for (int a = 0; a < k * k; ++a) {
-      H_out[2 * a] = Q.H[(size_t)a].real();
-      H_out[2 * a + 1] = Q.H[(size_t)a].imag();
-    }
-  if (xi_out)
-    for (int a = 0; a < k; ++a) {
-      xi_out[2 * a] = Q.xi[(size_t)a].real();
-      xi_out[2 * a + 1] = Q.xi[(size_t)a].imag();
-    }
-  if (rnorms_out)
-    for (int a = 0; a < k; ++a) rnorms_out[a] = a < report.used ? rn[(size_t)a] : 0.0;
-  if (used_out) *used_out = report.used;
-  return MG_OK;
+  return cx_fgmres_relax_host<cx_t, double>(h, level, r0, x, n, inner, tol, H_out, xi_out, rnorms_out, used_out, nullptr, nullptr);
+}
+// The same on a CF32 handle (option single_kcycle): complex64 vectors, the product in single, H / xi / rnorms in double; Z_out / AZ_out
+// (optional) receive the n x inner column-major complex64 bases
+int mg_fgmres_relax_CF32(mg_hierarchy* h, long long level, const float* r0, float* x, long long n, long long inner, double tol,
+                         double* H_out, double* xi_out, double* rnorms_out, long long* used_out, float* Z_out, float* AZ_out) {
+  return cx_fgmres_relax_host<cf_t, float>(h, level, r0, x, n, inner, tol, H_out, xi_out, rnorms_out, used_out, Z_out, AZ_out);
 }
 
 // A of a CF32 handle from interleaved (re, im) float pairs (the reference's AT values, conjugated here once), P and R from floats

@@ -146,6 +146,23 @@ struct OpCGsUpdate {
     cabs2_acc(acc[0], wv);
   }
 };
+// The combination pass of an FGMRES relaxation on a ComplexF32 hierarchy: x += sum_{j<m} t_j z_j, m <= 8, for complex64 x and z_j
+// and double coefficients.  Every element is widened on load, its sum is formed in double in direction order and rounded once on
+// the store (the convention of mg_rap_CF32): 8 (m + 2) bytes.
+struct OpCRelaxCombineF {
+  static constexpr int NS = 0;
+  int m;
+  d2_t t[MAXV];
+  const mgk::f2_t* z[MAXV];
+  mgk::f2_t* x;
+  __device__ __forceinline__ void at(long long i, double*) const {
+    d2_t xv = mgk::cwide(x[i]);
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j)
+      if (j < m) xv = xv + cmul(t[j], mgk::cwide(z[j][i]));
+    x[i] = mgk::f2_t{(float)xv.x, (float)xv.y};
+  }
+};
 // FGMRES, the chained form of modified Gram-Schmidt: the coefficient h_k = *hk is read from HBM (the sum the pass before left
 // there), w -= h_k v, and the partials of the NEXT scalar come out of the same pass - dot(u, w) (u = the next basis vector) or,
 // with u == nullptr, ||w||^2 in scalar 0 and zero in scalar 1.  48 bytes (64 with u).

@@ -239,6 +239,8 @@ SIGNATURES = {
     "mg_set_vanka_relax_CF64": (C.c_int, [_vp, _ll]),
     "mg_set_vanka_relax_CF32": (C.c_int, [_vp, _ll]),
     "mg_fgmres_relax_CF64": (C.c_int, [_vp, _ll, _dp, _dp, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp]),
+    "mg_set_schedule_CF32": (C.c_int, [_vp, _ll, _ll]),
+    "mg_fgmres_relax_CF32": (C.c_int, [_vp, _ll, _fp, _fp, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp, _fp, _fp]),
     "mg_set_coarse_dense_inverse_CF64": (C.c_int, [_vp, _ll, _dp]),
     "mg_set_coarse_lu_CF64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
     "mg_set_coarse_gmres_CF64": (C.c_int, [_vp, _ll, _dp]),
@@ -417,7 +419,7 @@ def _vanka_guard(param, nrhs: int):
         from .mgdef import _solver_object
         if _solver_object(param.LU) == "dd":
             raise NotImplementedError("complex Vanka hierarchies: a Schwarz coarsest solve is out of scope")
-    if param.cycleType == "K" and val != np.complex128:
+    if param.cycleType == "K" and val != np.complex128 and not (val == np.complex64 and getattr(param, "singleKcycle", False)):
         raise NotImplementedError("Vanka hierarchies serve the V, W and F cycles (cycleType='K': ComplexF64 hierarchies only)")
     if param.transferOperatorType not in ("SystemsFacesLinear", "SystemsFacesMixedLinear") or not param.Meshes:
         raise NotImplementedError("Vanka hierarchies need the staggered meshes of MGsetup with a Systems transfer operator")
@@ -1217,8 +1219,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         self._schedule = self._schedule_of(param)
 
     def _refuse_schedule(self, param):
-        """The K-cycle and Jac-GMRES smoothing are served for ComplexF64 values only."""
-        if self._sfx != "CF64" and (param.cycleType == "K" or param.relaxType == "Jac-GMRES"):
+        """The K-cycle and Jac-GMRES smoothing are served for ComplexF64 values, and for ComplexF32 ones where the param uploaded
+        carried ``singleKcycle=True`` (the handle's option single_kcycle)."""
+        if self._sfx != "CF64" and not getattr(self, "_single_kcycle", False) and (param.cycleType == "K" or param.relaxType == "Jac-GMRES"):
             raise NotImplementedError("ComplexF32 hierarchies: cycles V, W, F with the Jac / SPAI smoothers")
 
     def _set_schedule(self, param):
@@ -1227,6 +1230,8 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             _check(lib, self._fn("set_vanka_relax")(self.handle, ord(param.cycleType)), f"mg_set_vanka_relax_{self._sfx}")
         elif self._sfx == "CF64":
             _check(lib, lib.mg_set_schedule_CF64(self.handle, ord(param.cycleType), _relax_type_code(param)), "mg_set_schedule_CF64")
+        elif getattr(self, "_single_kcycle", False):
+            _check(lib, lib.mg_set_schedule_CF32(self.handle, ord(param.cycleType), _relax_type_code(param)), "mg_set_schedule_CF32")
         else:
             _check(lib, lib.mg_set_relax_type(self.handle, 0), "mg_set_relax_type")
             _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
@@ -1236,7 +1241,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         self._vanka_block_guard()
         sched = getattr(self, "_schedule", None)
         if sched is not None and (sched[0] == "K" or sched[1] == "Jac-GMRES"):
-            raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle / Jac-GMRES ComplexF64 hierarchy "
+            raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy "
                                       "(solve the columns one after the other)")
 
     def _vanka_block_guard(self):
@@ -1760,7 +1765,9 @@ class ComplexSingleDeviceHierarchy(ComplexDeviceHierarchy):
     relaxPrecs complex64, Ps / Rs float32, the cycle in single precision by the same kernels; the coarsest solve stays
     ComplexF64.  ``cycle``, ``solve``, ``spmv`` take complex64 arrays.  ``bicgstab``, ``fgmres``, their ``_dev`` forms,
     ``cycle_dev``, ``set_krylov_operator`` and ``update_krylov_operator`` take complex128 arrays and tensors: the Krylov method
-    runs in ComplexF64 and is preconditioned by the single cycle (narrowed in, widened out; SolveFuncs.jl:52-58)."""
+    runs in ComplexF64 and is preconditioned by the single cycle (narrowed in, widened out; SolveFuncs.jl:52-58).  A param with
+    ``singleKcycle=True`` adds the K-cycle and Jac-GMRES smoothing (option single_kcycle, mg_set_schedule_CF32; Gram sums and least
+    squares in double) and ``fgmres_relax`` on complex64 vectors; without it both are refused."""
 
     _cdtype = np.complex64
     _rdtype = np.float32
@@ -1791,9 +1798,38 @@ class ComplexSingleDeviceHierarchy(ComplexDeviceHierarchy):
 
     _single_device_setup = False      # the param uploaded last carried singleDeviceSetup: the four methods below are served
 
+    _single_kcycle = False            # the param uploaded last carried singleKcycle: 'K' and Jac-GMRES are served (option single_kcycle)
+
     def _upload(self, param):
         self._single_device_setup = bool(getattr(param, "singleDeviceSetup", False))
+        self._single_kcycle = bool(getattr(param, "singleKcycle", False))
+        if self._single_kcycle:           # (ahead of the schedule: mg_set_schedule_CF32 and mg_finalize read it)
+            _check(self.lib, self.lib.mg_set_option(self.handle, b"single_kcycle", 1.0), "mg_set_option(single_kcycle)")
         super()._upload(param)
+
+    def fgmres_relax(self, level: int, r0, x, inner: int, tol: float = 1e-5, want_bases: bool = False):
+        """One FGMRES_relaxation on As[level] and relaxPrecs[level] of a ``singleKcycle`` hierarchy (mg_fgmres_relax_CF32): ``x += Z t``
+        in place for the residual ``r0``, both complex64.  Z and AZ are complex64 and the product is formed in single; H, xi and the
+        residual estimates are formed in double.  Returns (rnorms, H, xi) as the ComplexF64 method does, and with ``want_bases`` also
+        (Z, AZ): the n x inner complex64 bases of all ``inner`` directions."""
+        r0 = self._host_block(r0, dtype=np.complex64)
+        x = self._host_block(x, True, dtype=np.complex64)
+        k = int(inner)
+        H = np.zeros((max(k, 1), max(k, 1)), dtype=np.complex128)
+        xi = np.zeros(max(k, 1), dtype=np.complex128)
+        rn = np.zeros(max(k, 1))
+        used = C.c_longlong(0)
+        Z = AZ = None
+        if want_bases:
+            Z = np.zeros((r0.shape[0], max(k, 1)), dtype=np.complex64, order="F")
+            AZ = np.zeros_like(Z)
+        _check(self.lib, self.lib.mg_fgmres_relax_CF32(self.handle, int(level), r0.ctypes.data_as(_fp), x.ctypes.data_as(_fp), r0.shape[0], k,
+                                                       float(tol), _c128(H), _c128(xi), _f64(rn), C.byref(used),
+                                                       Z.ctypes.data_as(_fp) if want_bases else None,
+                                                       AZ.ctypes.data_as(_fp) if want_bases else None), "mg_fgmres_relax_CF32")
+        if want_bases:
+            return rn[: used.value], H, xi, Z, AZ
+        return rn[: used.value], H, xi
 
     def _refuse_single(self, *args, **kwargs):
         raise NotImplementedError("ComplexF32 hierarchies: replace_matrix, replace_values, get_values and rap_level_ms on the device are "

@@ -52,6 +52,7 @@ class MGparam:
     vankaDeviceSetup: bool = False     # complexVanka only: the cells' blocks are built (and, ComplexF64 or singleDeviceSetup, refreshed) on the device
     coarseDeviceInverse: bool = False  # the coarsest operator's explicit inverse is built (and refreshed) on the device
     singleDeviceSetup: bool = False    # singlePrecision only: replaceMatrixInHierarchy refreshes the resident hierarchy in HBM
+    singleKcycle: bool = False         # singlePrecision only: the K-cycle and Jac-GMRES smoothing on the ComplexF32 hierarchy
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -66,7 +67,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
                blockCoarseGMRES: bool = False, complexVanka: bool = False, vankaBlocks: bool = False,
                vankaDeviceSetup: bool = False, coarseDeviceInverse: bool = False,
-               singleDeviceSetup: bool = False) -> MGparam:
+               singleDeviceSetup: bool = False, singleKcycle: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -80,7 +81,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     served on the hierarchy; without it they are refused.  The columns of a block are coupled by that solve.
     ``complexVanka=True`` (keyword only) with a complex ``VAL`` and a Vanka ``relaxType`` (VankaFaces, EconVankaFaces, VankaFacesAdd)
     lets ``MGsetup`` build the complex Vanka hierarchy of the reference (Systems transfers, complex64 blocks per level) and the
-    device run it: ComplexF64 with cycles V / W / F / K, ``singlePrecision`` with V / W / F, one right-hand side.  Without it a
+    device run it: ComplexF64 with cycles V / W / F / K, ``singlePrecision`` with V / W / F (K with ``singleKcycle=True``), one
+    right-hand side.  Without it a
     complex Vanka param is refused by ``MGsetup``, as before.
     ``vankaBlocks=True`` (keyword only, with ``complexVanka=True``) switches on the block form of that smoother: blocks of up to 16
     right-hand sides are then served on the hierarchy for the cycles V / W / F (solveMG, recursiveCycle, getMultigridPreconditioner,
@@ -103,6 +105,12 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     ComplexF64 path: Jac or SPAI, or a Vanka hierarchy with ``vankaDeviceSetup=True``; the GMRES coarsest solve and
     ``coarseDeviceInverse`` are refreshed there too.  Without it a ComplexF32 param is recomputed on the host and uploaded again,
     as before.
+    ``singleKcycle=True`` (keyword only, with ``singlePrecision=True``) serves ``cycleType="K"`` and ``relaxType="Jac-GMRES"`` on the
+    ComplexF32 hierarchy (the handle's option ``single_kcycle``, ``mg_set_schedule_CF32``): V / W / F / K with Jac / SPAI /
+    Jac-GMRES, and K with the Vanka smoothers, one right-hand side.  The directions Z and A Z are complex64 and the product is formed
+    in single; the Gram sums, the small least squares and the break test are formed in double (a deviation from the reference, which
+    forms them in ComplexF32 where the residual estimate is noise at the 1e-5 break).  Blocks of right-hand sides stay refused on
+    such a schedule.  Without it a ComplexF32 param with ``"K"`` or ``"Jac-GMRES"`` is refused, as before.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
@@ -126,6 +134,9 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     if singleDeviceSetup and not singlePrecision:
         raise NotImplementedError("singleDeviceSetup=True serves a ComplexF32 hierarchy (singlePrecision=True); Float64 and "
                                   "ComplexF64 hierarchies are refreshed on the device without it")
+    if singleKcycle and not singlePrecision:
+        raise NotImplementedError("singleKcycle=True serves a ComplexF32 hierarchy (singlePrecision=True); ComplexF64 hierarchies "
+                                  "run the K-cycle and Jac-GMRES without it")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -142,7 +153,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka),
                    vankaBlocks=bool(vankaBlocks), vankaDeviceSetup=bool(vankaDeviceSetup),
                    coarseDeviceInverse=bool(coarseDeviceInverse), singleDeviceSetup=bool(singleDeviceSetup),
-                   VAL=np.dtype(VAL).type, IND=np.int64)
+                   singleKcycle=bool(singleKcycle), VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -216,7 +227,8 @@ def copySolver(MG: MGparam) -> MGparam:
                      MG.strongConnParam, MG.FilteringParam, MG.transferOperatorType, singlePrecision=single,
                      blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka),
                      vankaBlocks=bool(MG.vankaBlocks), vankaDeviceSetup=bool(MG.vankaDeviceSetup),
-                     coarseDeviceInverse=bool(MG.coarseDeviceInverse), singleDeviceSetup=bool(MG.singleDeviceSetup))
+                     coarseDeviceInverse=bool(MG.coarseDeviceInverse), singleDeviceSetup=bool(MG.singleDeviceSetup),
+                     singleKcycle=bool(MG.singleKcycle))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd

@@ -310,7 +310,8 @@ def replaceMatrixInHierarchy(param: MGparam, A, verbose: bool = False) -> None:
     """New fine matrix, same P/R: recompute relaxPrecs, Galerkin products and the coarse LU (MGsetup.jl:226-270).  On a resident
     param with ``coarseDeviceInverse=True`` the explicit inverse of the new coarsest operator is rebuilt in HBM (mg_rap_*); the
     host still factors it (``param.LU``) and uploads nothing.  A resident ComplexF32 param takes the device path where it carries
-    ``singleDeviceSetup=True`` (mg_rap_CF32) and the host path with a fresh upload otherwise."""
+    ``singleDeviceSetup=True`` (mg_rap_CF32) and the host path with a fresh upload otherwise; with ``singleKcycle=True`` the ComplexF64
+    rule holds: K with Jac / SPAI keeps the handle, Jac-GMRES takes the host path."""
     relaxParamArr = _relax_param_arr(param)
     A = _of_val(param, A)
     # (a ComplexF32 hierarchy is recomputed on the host and uploaded again, unless its param asked for the device re-setup:
@@ -392,7 +393,8 @@ def adjointHierarchy(param: MGparam, verbose: bool = False) -> None:
     coarseSolveType "GMRES" (l.304-305), else the factorisation of the new As[end] (a preset solver object is replaced, as
     ``transposeHierarchy`` does it).  Serves ComplexF64 params and ``singlePrecision`` ones (dtypes kept); a real param is
     ``transposeHierarchy``'s.  A resident hierarchy is flipped in HBM (mg_adjoint_hierarchy_CF64 / _CF32); what the library refuses
-    there (sparse coarsest factors, a Schwarz coarsest solve) falls back to the lazy re-upload."""
+    there (sparse coarsest factors, a Schwarz coarsest solve) falls back to the lazy re-upload, and so does a ``singleKcycle`` param
+    (flipping its resident hierarchy in HBM is not built)."""
     if not is_complex(param):
         raise TypeError("adjointHierarchy serves complex params (VAL=ComplexF64, singlePrecision or not): a real hierarchy is "
                         "flipped by transposeHierarchy")
@@ -418,6 +420,8 @@ def adjointHierarchy(param: MGparam, verbose: bool = False) -> None:
         destroyCoarsestLU(param)
         param.LU = None        # MGsetup.jl:310-311 factors the adjoint coarsest matrix itself: a solver object is replaced
         defineCoarsestAinv(param, param.As[-1])
+    if param.device is not None and is_single(param) and getattr(param, "singleKcycle", False):
+        _release_device(param)     # (a singleKcycle hierarchy is not flipped in HBM: uploaded again by the next cycle)
     if param.device is not None:
         from .device import MGDeviceError
         try:
