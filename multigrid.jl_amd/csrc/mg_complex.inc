@@ -11,7 +11,10 @@
 // getMultigridPreconditioner, SolveFuncs.jl:52-58).
 // Blocks of right-hand sides (mg_block_*_CF64 here, mg_block_*_CFP64 in mg_complex_krylov.inc) take nrhs with each call: cx_spmv,
 // cx_relax, cx_coarse and cx_cycle carry a column count nr (0: the single-vector path, untouched; >= 1: row-major blocks [n][nr] on
-// the block work set of CxState, cx_block_ensure).
+// the block work set of CxState, cx_block_ensure).  Everything a vector entry point and its block twin differ in - the checks, the
+// buffers, the lengths, how a host array is staged - is answered by the selector CxCols, so each form between the C ABI and that
+// core is written once: cx_cycle_host / cx_solve_host / cx_spmv_host (both precisions, vectors and blocks), cx_coarse_gmres_host,
+// and in mg_complex_krylov.inc cx_krylov and cx_cycle_dev.
 // adjointHierarchy on the resident hierarchy (mg_adjoint_hierarchy_CF64 / _CF32; cx_adjoint_hierarchy): every operator replaced by its
 // conjugate transpose in HBM, for both precisions.
 // Also here: the stand-alone ComplexF64 factor applier behind mg_lu_*_CFP64 (CxLu; its extern "C" entry points sit beside the
@@ -645,6 +648,64 @@ int cx_coarse_block_gmres(mg_hierarchy* h, const cx_t* b, cx_t* x, int k, CxCoar
   return MG_OK;
 }
 
+// ---- the work set of a call: everything a vector entry point and its block twin differ in -------------------------------------------
+// nr == 0: one right-hand side on the handle's own buffers (the one-lane-per-row kernels); nr >= 1: a row-major block [n][nr] on the
+// block work set (the block kernels, also for nr == 1).  `asked` is the nrhs the caller passed, checked by served().  The host forms of
+// blocks (column-major on the host, relaid through a staging block) exist in ComplexF64 only.
+int cx_block_ensure(mg_hierarchy* h, int nr);
+struct CxCols {
+  int nr;
+  long long asked;
+  static CxCols vec(long long nrhs = 1) { return {0, nrhs}; }
+  static CxCols blk(long long nrhs) { return {(int)std::min<long long>(std::max<long long>(nrhs, 1), mgk::BLK_KMAX), nrhs}; }
+  static CxCols of(int nr) { return {nr, std::max(nr, 1)}; }   // (inside the core: a count that was checked on the way in)
+  const char* noun() const { return nr ? "block" : "vector"; }
+  size_t len(long long n) const { return (size_t)n * (size_t)std::max(nr, 1); }
+  DevBuf<double>& b(CxLevel& L) const { return nr ? L.Bb : L.b; }
+  DevBuf<double>& r(CxLevel& L) const { return nr ? L.Br : L.r; }
+  DevBuf<double>& x(CxLevel& L, int i) const { return nr ? L.Bx[i] : L.x[i]; }
+  DevBuf<double>& stage_b(CxState& S) const { return nr ? S.Bstage_b : S.stage_b; }
+  DevBuf<double>& stage_x(CxState& S) const { return nr ? S.Bstage_x : S.stage_x; }
+  DevBuf<double>& cw_b(CxState& S) const { return nr ? S.Bcw_b : S.cw_b; }   // the widened coarsest pair of a CF32 handle
+  DevBuf<double>& cw_x(CxState& S) const { return nr ? S.Bcw_x : S.cw_x; }
+  DevBuf<double>& lu_work(CxState& S) const { return nr ? S.BluWork : S.luWork; }   // the triangular sweeps' work vector
+  int served(mg_hierarchy* h) const;                                 // the column count, the schedule and the coarsest solve take it
+  int ready(mg_hierarchy* h, long long n, CxWant want) const;        // + the handle, finalized, n = the fine level's rows
+  int ensure(mg_hierarchy* h) const { return nr ? cx_block_ensure(h, nr) : MG_OK; }
+  // host array -> dst (n values per column), enqueued on h's stream: one copy, for a block through `cm` and cx_relayout
+  template <typename C>
+  int upload(mg_hierarchy* h, const void* host, DevBuf<double>& cm, C* dst, long long n) const {
+    const hipStream_t st = h->play->stream;
+    if (nr == 0) {
+      HIP_TRY(hipMemcpyAsync(dst, host, sizeof(C) * (size_t)n, hipMemcpyHostToDevice, st));
+      return MG_OK;
+    }
+    if constexpr (std::is_same<C, cx_t>::value) {
+      HIP_TRY(hipMemcpyAsync(cm.p, host, sizeof(cx_t) * len(n), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(mgk::cx_relayout<true>, dim3(cx_grid((long long)len(n))), dim3(mgk::BLK), 0, st, cxc(cm), dst, n, nr);
+      HIP_TRY(hipGetLastError());
+      return MG_OK;
+    }
+    return fail(MG_ERR_INVALID, "internal: host blocks are ComplexF64");
+  }
+  // src -> host array, enqueued the same way; the caller waits for the stream
+  template <typename C>
+  int download(mg_hierarchy* h, const C* src, DevBuf<double>& cm, void* host, long long n) const {
+    const hipStream_t st = h->play->stream;
+    if (nr == 0) {
+      HIP_TRY(hipMemcpyAsync(host, src, sizeof(C) * (size_t)n, hipMemcpyDeviceToHost, st));
+      return MG_OK;
+    }
+    if constexpr (std::is_same<C, cx_t>::value) {
+      hipLaunchKernelGGL(mgk::cx_relayout<false>, dim3(cx_grid((long long)len(n))), dim3(mgk::BLK), 0, st, src, cxp(cm), n, nr);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(host, cm.p, sizeof(cx_t) * len(n), hipMemcpyDeviceToHost, st));
+      return MG_OK;
+    }
+    return fail(MG_ERR_INVALID, "internal: host blocks are ComplexF64");
+  }
+};
+
 // z = param.LU \ b (MGcycle.jl:177): explicit inverse, or x[q] = U \ (L \ b[p]) by the level-scheduled sptrsv_lu (one workgroup;
 // chip-wide for factors of >= lu_multi_min_rows rows), or one Schwarz sweep (MGcycle.jl:140-143; xzero: x need not be read), or one
 // restart of Jacobi-preconditioned FGMRES(10) from zero (cx_coarse_gmres: the only one that synchronises with the host, once)
@@ -671,7 +732,7 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr
     F.p = S.luP.p; F.q = S.luQ.p;
     F.Lorder = S.luLorder.p; F.Llvl = S.luLlvl.p; F.nLlvl = S.nLlvl;
     F.Uorder = S.luUorder.p; F.Ulvl = S.luUlvl.p; F.nUlvl = S.nUlvl;
-    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, h->play->stream, F, b, x, cxp(nr ? S.BluWork : S.luWork), k);
+    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, h->play->stream, F, b, x, cxp(CxCols::of(nr).lu_work(S)), k);
   } else if (nr == 0) {
     hipLaunchKernelGGL(mgk::cx_dense_matvec, dim3(cx_grid(n * 64)), dim3(mgk::BLK), 0, h->play->stream,
                        reinterpret_cast<const cx_t*>(S.Ainv.p), b, x, (int)n);
@@ -689,35 +750,32 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr
 // deliberate deviation of the order of the single unit roundoff: more accurate, and no float instantiation of the vector passes.
 int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool = true, int nr = 0) {
   CxState& S = *h->cx;
-  DevBuf<double>&wb = nr ? S.Bcw_b : S.cw_b, &wx = nr ? S.Bcw_x : S.cw_x;
-  const long long len = S.n_coarse * std::max(nr, 1);
+  const CxCols W = CxCols::of(nr);
+  DevBuf<double>&wb = W.cw_b(S), &wx = W.cw_x(S);
+  const long long len = (long long)W.len(S.n_coarse);
   MG_TRY(cx_widen(h, b, cxp(wb), len));
   MG_TRY(cx_coarse(h, cxc(wb), cxp(wx), true, nr));
   return cx_narrow(h, cxc(wx), x, len);
 }
-
-// the level vectors a cycle works on: the handle's own (nr == 0: one right-hand side) or the block work set (nr >= 1 columns)
-inline DevBuf<double>& cx_lb(CxLevel& L, int nr) { return nr ? L.Bb : L.b; }
-inline DevBuf<double>& cx_lr(CxLevel& L, int nr) { return nr ? L.Br : L.r; }
-inline DevBuf<double>& cx_lx(CxLevel& L, int nr, int i) { return nr ? L.Bx[i] : L.x[i]; }
 
 // relax (MGcycle.jl:122-136) entered with r = b - A x: numit-1 times {x += d.*r; r = b - A x}, then x += d.*r - i.e.
 // max(numit, 1) sweeps x' = x + d.*(b - A x); from x = 0 the first one is x = d.*b.  x ping-pongs between L.x[0] / L.x[1].
 // nr columns (0: a vector): d[row] is shared by the columns of a block.
 template <typename C>
 int cx_relax(mg_hierarchy* h, CxLevel& L, const C* b, int& xi, bool xzero, long long numit, int nr = 0) {
+  const CxCols W = CxCols::of(nr);
   long long sweeps = std::max<long long>(numit, 1);
   if (xzero) {
     if (nr == 0)
-      hipLaunchKernelGGL(mgk::cx_dscale<C>, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, cxp<C>(L.x[xi]), L.n);
+      hipLaunchKernelGGL(mgk::cx_dscale<C>, dim3(cx_grid(L.n)), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, cxp<C>(W.x(L, xi)), L.n);
     else
       hipLaunchKernelGGL(mgk::cx_dscale_blk<C>, dim3(cx_grid(L.n * nr)), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b,
-                         cxp<C>(L.Bx[xi]), L.n * nr, nr);
+                         cxp<C>(W.x(L, xi)), L.n * nr, nr);
     HIP_TRY(hipGetLastError());
     --sweeps;
   }
   for (long long s = 0; s < sweeps; ++s) {
-    MG_TRY(cx_spmv<mgk::SMOOTH>(h, L.A, cxc<C>(cx_lx(L, nr, xi)), cxp<C>(cx_lx(L, nr, 1 - xi)), b, cxc<C>(L.d), nullptr, C{1, 0}, C{0, 0}, nr));
+    MG_TRY(cx_spmv<mgk::SMOOTH>(h, L.A, cxc<C>(W.x(L, xi)), cxp<C>(W.x(L, 1 - xi)), b, cxc<C>(L.d), nullptr, C{1, 0}, C{0, 0}, nr));
     xi = 1 - xi;
   }
   return MG_OK;
@@ -898,8 +956,9 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   CxState& S = *h->cx;
   const int nl = (int)h->nlevels;
   CxLevel& L = S.lev[(size_t)l];
+  const CxCols W = CxCols::of(nr);
   const C one = C{1, 0}, zero = C{0, 0};
-  if (l == nl - 1) return cx_coarse(h, b, cxp<C>(cx_lx(L, nr, xi)), xzero, nr);                 // l.13-18
+  if (l == nl - 1) return cx_coarse(h, b, cxp<C>(W.x(L, xi)), xzero, nr);                 // l.13-18
   constexpr bool is64 = sizeof(typename mgk::cx_scalar<C>::type) == sizeof(double);
   const bool gmres_relax = h->relax_type == 1;   // Jac-GMRES (MGcycle.jl:35-38, 48-50, 96-98)
   const double gmresTol = 1e-5;                  // l.5
@@ -908,8 +967,8 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   const bool vanka_relax = h->relax_type == 2;   // Vanka (l.51-52, 99-100): x relaxed in place, no ping-pong
   if (vanka_relax && nr != 0 && !h->opt.vanka_blocks) return fail(MG_ERR_UNSUPPORTED, "Vanka relaxation (type 2) serves one right-hand side");
   if (vanka_relax) {   // (a block, option vanka_blocks: the block form of the smoother on Bx, in place as well)
-    C* x = cxp<C>(cx_lx(L, nr, xi));
-    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * (size_t)L.n * (size_t)std::max(nr, 1), h->play->stream));
+    C* x = cxp<C>(W.x(L, xi));
+    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * W.len(L.n), h->play->stream));
     MG_TRY(cx_vanka_relax<C>(h, L, b, x, L.npre, xzero, nr));
   } else if (gmres_relax) {
     // r = b - A x (l.28-31) with ||r||^2 and z_1 = d.*r from the same pass; from x = 0, r0 = b
@@ -923,13 +982,13 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   } else {
     MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre, nr));                                  // l.26-31, 54
   }
-  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxc<C>(cx_lx(L, nr, xi)), cxp<C>(cx_lr(L, nr)), b, nullptr, nullptr, one, zero, nr));  // l.58-60
+  MG_TRY(cx_spmv<mgk::RESID>(h, L.A, cxc<C>(W.x(L, xi)), cxp<C>(W.r(L)), b, nullptr, nullptr, one, zero, nr));  // l.58-60
   CxLevel& C1 = S.lev[(size_t)l + 1];
-  const C* bc = cxc<C>(cx_lb(C1, nr));
-  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.R, cxc<C>(cx_lr(L, nr)), cxp<C>(cx_lb(C1, nr)), nullptr, nullptr, nullptr, one, zero, nr));   // bc = R r   (l.66)
+  const C* bc = cxc<C>(W.b(C1));
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.R, cxc<C>(W.r(L)), cxp<C>(W.b(C1)), nullptr, nullptr, nullptr, one, zero, nr));   // bc = R r   (l.66)
   int ci = 0;
   if (l + 1 == nl - 1) {
-    MG_TRY(cx_coarse(h, bc, cxp<C>(cx_lx(C1, nr, ci)), true, nr));                         // l.67-69
+    MG_TRY(cx_coarse(h, bc, cxp<C>(W.x(C1, ci)), true, nr));                         // l.67-69
   } else if (ctype == 'K') {
     // K-cycle (l.72-76): two FGMRES steps on A_{l+1} xc = bc from xc = 0, preconditioned by the K-cycle of level l+1 from zero.  Each
     // step: one inner cycle, its result copied into Z, one GRAM launch (no znext: the preconditioner is a cycle), one synchronisation -
@@ -965,8 +1024,8 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
     else if (ctype == 'F') MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, false, 'V', nr));          // l.81-84
   }
   // x += P xc (l.90): in place, the gather reads xc only
-  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(cx_lx(C1, nr, ci)), cxp<C>(cx_lx(L, nr, xi)), nullptr, nullptr, nullptr, one, one, nr));
-  if (vanka_relax) return cx_vanka_relax<C>(h, L, b, cxp<C>(cx_lx(L, nr, xi)), L.npost, false, nr);   // l.99-100
+  MG_TRY(cx_spmv<mgk::AXPBY>(h, L.P, cxc<C>(W.x(C1, ci)), cxp<C>(W.x(L, xi)), nullptr, nullptr, nullptr, one, one, nr));
+  if (vanka_relax) return cx_vanka_relax<C>(h, L, b, cxp<C>(W.x(L, xi)), L.npost, false, nr);   // l.99-100
   if (gmres_relax) {                                                                      // r = b - A x, FGMRES_relaxation (l.92-98)
     if (L.npost > 0) {
       C* x = cxp<C>(L.x[xi]);
@@ -976,14 +1035,6 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
     return MG_OK;
   }
   return cx_relax<C>(h, L, b, xi, false, L.npost, nr);                                   // r = b - A x, relax (l.92-102)
-}
-
-int cx_check_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want = CX_WANT64) {
-  MG_TRY(cx_handle_ok(h, want));
-  if (!h->cx->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
-  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "complex handles serve one right-hand side (nrhs=%lld)", nrhs);
-  if (n != h->cx->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->cx->lev[0].n);
-  return MG_OK;
 }
 
 // The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51); that form is not built here.
@@ -1006,15 +1057,22 @@ int cx_block_nrhs_ok(long long nrhs) {
   if (nrhs > mgk::BLK_KMAX) return fail(MG_ERR_UNSUPPORTED, "complex blocks hold at most %d right-hand sides (nrhs=%lld)", mgk::BLK_KMAX, nrhs);
   return MG_OK;
 }
-// The checks of the mg_block_* entry points (the block forms take nrhs with each call; the handle's own nrhs stays 1)
-int cx_block_ready(mg_hierarchy* h, long long n, long long nrhs, CxWant want) {
+// The checks of every entry point: a vector form takes nrhs = 1, a block form takes nrhs with each call (the handle's own nrhs stays 1)
+int CxCols::served(mg_hierarchy* h) const {
+  if (nr == 0) {
+    if (asked != 1) return fail(MG_ERR_UNSUPPORTED, "complex handles serve one right-hand side (nrhs=%lld)", asked);
+    return MG_OK;
+  }
+  MG_TRY(cx_block_nrhs_ok(asked));
+  MG_TRY(cx_block_schedule_ok(h));
+  return cx_block_coarse_ok(h, asked);
+}
+int CxCols::ready(mg_hierarchy* h, long long n, CxWant want) const {
   MG_TRY(cx_handle_ok(h, want));
   if (!h->cx->finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
-  MG_TRY(cx_block_nrhs_ok(nrhs));
-  MG_TRY(cx_block_schedule_ok(h));
+  MG_TRY(served(h));
   if (n != h->cx->lev[0].n) return fail(MG_ERR_INVALID, "n=%lld does not match the fine level (%lld rows)", n, h->cx->lev[0].n);
-  if (h->coarse_dd && nrhs > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%lld)", nrhs);
-  MG_TRY(cx_block_coarse_ok(h, nrhs));
+  if (h->coarse_dd && nr > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%lld)", asked);
   return MG_OK;
 }
 
@@ -1539,204 +1597,101 @@ int cx_find_op(mg_hierarchy* h, long long level, long long which, CxMat** out, C
   return MG_OK;
 }
 
-// ---- the host-pointer forms of cycle / solve / spmv, once for both precisions (ST: the host scalar, C: the device pair) ----
+// ---- the host-pointer forms of cycle / solve / spmv, once for both precisions (ST: the host scalar, C: the device pair) and for
+//      vectors and blocks (CxCols; mg_block_*_CF64: Julia's column-major n x nrhs blocks, relaid at the boundary) ----
 inline bool host_all_zero(const float* x, long long len) {
   for (long long i = 0; i < len; ++i)
     if (x[i] != 0.0f) return false;
   return true;
 }
 
+// b, x: n values per column on the host (a block: column-major n x nrhs, relaid at the boundary); W: the work set they run on
 template <typename C, typename ST>
-int cx_cycle_host(mg_hierarchy* h, const ST* b, ST* x, long long n, long long nrhs, long long x_is_zero, CxWant want) {
-  MG_TRY(cx_check_ready(h, n, nrhs, want));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+int cx_cycle_host(mg_hierarchy* h, const ST* b, ST* x, long long n, long long x_is_zero, CxWant want, CxCols W) {
+  MG_TRY(W.ready(h, n, want));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null %s", W.noun());
   (void)hipSetDevice(h->device);
+  MG_TRY(W.ensure(h));
   CxState& S = *h->cx;
   CxLevel& L0 = S.lev[0];
   bool xz = (x_is_zero == 1);
-  if (x_is_zero < 0) xz = host_all_zero(x, 2 * n);   // norm(x) > 0.0 decides (MGcycle.jl:29)
-  const size_t bytes = sizeof(C) * (size_t)n;
+  if (x_is_zero < 0) xz = host_all_zero(x, 2 * (long long)W.len(n));   // norm(x) > 0.0 over the whole block decides (MGcycle.jl:29)
   int xi = 0;
-  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
-  if (!xz) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
-  MG_TRY(cx_cycle<C>(h, 0, cxc<C>(S.stage_b), xi, xz, h->cycle));
-  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
+  MG_TRY(W.upload(h, b, S.Bstage_t, cxp<C>(W.stage_b(S)), n));
+  if (!xz) MG_TRY(W.upload(h, x, S.Bstage_t, cxp<C>(W.x(L0, xi)), n));
+  MG_TRY(cx_cycle<C>(h, 0, cxc<C>(W.stage_b(S)), xi, xz, h->cycle, W.nr));
+  MG_TRY(W.download(h, cxc<C>(W.x(L0, xi)), S.Bstage_t, x, n));
   HIP_TRY(spin_sync(h->play->stream));
   return MG_OK;
 }
 
+// solveMG (SolveFuncs.jl:14-36); on a block the norms are Frobenius norms of the whole block
 template <typename C, typename ST>
-int cx_solve_host(mg_hierarchy* h, const ST* b, ST* x, long long n, long long nrhs, double tol, long long maxIter, long long* iters,
-                  double* resvec, CxWant want) {
-  MG_TRY(cx_check_ready(h, n, nrhs, want));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
+int cx_solve_host(mg_hierarchy* h, const ST* b, ST* x, long long n, double tol, long long maxIter, long long* iters, double* resvec,
+                  CxWant want, CxCols W) {
+  MG_TRY(W.ready(h, n, want));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null %s", W.noun());
   if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
   (void)hipSetDevice(h->device);
+  MG_TRY(W.ensure(h));
   CxState& S = *h->cx;
   CxLevel& L0 = S.lev[0];
-  const size_t bytes = sizeof(C) * (size_t)n;
-  const C* bd = cxc<C>(S.stage_b);
+  const C* bd = cxc<C>(W.stage_b(S));
   int xi = 0;
-  bool xz = host_all_zero(x, 2 * n);
-  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
+  bool xz = host_all_zero(x, 2 * (long long)W.len(n));
+  MG_TRY(W.upload(h, b, S.Bstage_t, cxp<C>(W.stage_b(S)), n));
   double res2 = 0.0;
-  if (xz) {   // SolveFuncs.jl:14-21
-    MG_TRY(cx_norm2<C>(h, bd, n, &res2));
+  if (xz) {   // l.14-21
+    MG_TRY(cx_norm2<C>(h, bd, (long long)W.len(n), &res2));
   } else {
-    HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
-    MG_TRY(cx_residual_norm2<C>(h, L0, bd, cxc<C>(L0.x[xi]), cxp<C>(L0.r), &res2));
+    MG_TRY(W.upload(h, x, S.Bstage_t, cxp<C>(W.x(L0, xi)), n));
+    MG_TRY(cx_residual_norm2<C>(h, L0, bd, cxc<C>(W.x(L0, xi)), cxp<C>(W.r(L0)), &res2, W.nr));
   }
   const double res0 = std::sqrt(res2);
   if (resvec) resvec[0] = res0;
   long long it = 0;
   for (long long count = 1; count <= maxIter; ++count) {   // l.23-37
-    MG_TRY(cx_cycle<C>(h, 0, bd, xi, xz, h->cycle));
+    MG_TRY(cx_cycle<C>(h, 0, bd, xi, xz, h->cycle, W.nr));
     xz = false;
-    MG_TRY(cx_residual_norm2<C>(h, L0, bd, cxc<C>(L0.x[xi]), cxp<C>(L0.r), &res2));
+    MG_TRY(cx_residual_norm2<C>(h, L0, bd, cxc<C>(W.x(L0, xi)), cxp<C>(W.r(L0)), &res2, W.nr));
     ++it;
     const double res = std::sqrt(res2);
     if (resvec) resvec[count] = res;
     if (res / res0 < tol) break;
   }
-  if (xz) HIP_TRY(hipMemsetAsync(L0.x[xi].p, 0, bytes, h->play->stream));   // maxIter = 0 from x = 0
-  HIP_TRY(hipMemcpyAsync(x, L0.x[xi].p, bytes, hipMemcpyDeviceToHost, h->play->stream));
+  if (xz) HIP_TRY(hipMemsetAsync(W.x(L0, xi).p, 0, sizeof(C) * W.len(n), h->play->stream));   // maxIter = 0 from x = 0
+  MG_TRY(W.download(h, cxc<C>(W.x(L0, xi)), S.Bstage_t, x, n));
   HIP_TRY(spin_sync(h->play->stream));
   if (iters) *iters = it;
   return MG_OK;
 }
 
+// y = beta*y + alpha*Op*x on one level; x holds n_cols and y n_rows values per column
 template <typename C, typename ST>
-int cx_spmv_host(mg_hierarchy* h, long long level, long long which, const ST* alpha, const ST* x, const ST* beta, ST* y, long long nrhs,
-                 CxWant want) {
+int cx_spmv_host(mg_hierarchy* h, long long level, long long which, const ST* alpha, const ST* x, const ST* beta, ST* y, CxWant want,
+                 CxCols W) {
   MG_TRY(cx_level_ok(h, level, want));
   CxState& S = *h->cx;
   if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
-  if (nrhs != 1) return fail(MG_ERR_UNSUPPORTED, "complex handles serve one right-hand side (nrhs=%lld)", nrhs);
+  MG_TRY(W.served(h));
   if (!alpha || !beta || !x || !y) return fail(MG_ERR_INVALID, "null argument");
   if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
   CxLevel& L = S.lev[(size_t)level - 1];
   if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
   const CxMat& M = which == MG_OP_A ? L.A : which == MG_OP_P ? L.P : L.R;
   (void)hipSetDevice(h->device);
-  const long long nr = M.n_rows, nc = M.n_cols;
+  const long long mr = M.n_rows, mc = M.n_cols;
   const C a = C{alpha[0], alpha[1]}, bt = C{beta[0], beta[1]};
   const bool bz = bt.x == 0 && bt.y == 0;
-  DevBuf<double> dx, dy;   // (released below on every path; sized in bytes of C)
-  int rc = dx.alloc(cx_len(S, nc));
-  if (rc == MG_OK) rc = dy.alloc(cx_len(S, nr));
-  if (rc == MG_OK && hipMemcpyAsync(dx.p, x, sizeof(C) * (size_t)nc, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
-    rc = fail(MG_ERR_HIP, "upload of x failed");
-  if (rc == MG_OK && !bz && hipMemcpyAsync(dy.p, y, sizeof(C) * (size_t)nr, hipMemcpyHostToDevice, h->play->stream) != hipSuccess)
-    rc = fail(MG_ERR_HIP, "upload of y failed");
-  if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxc<C>(dx), cxp<C>(dy), nullptr, nullptr, nullptr, a, bt);
-  if (rc == MG_OK && hipMemcpyAsync(y, dy.p, sizeof(C) * (size_t)nr, hipMemcpyDeviceToHost, h->play->stream) != hipSuccess)
-    rc = fail(MG_ERR_HIP, "download of the product failed");
+  DevBuf<double> cm, dx, dy;   // (released below on every path; cm: the column-major staging block of a block call)
+  int rc = W.nr ? cm.alloc(2 * W.len(std::max(mr, mc))) : MG_OK;
+  if (rc == MG_OK) rc = dx.alloc(cx_len(S, (long long)W.len(mc)));
+  if (rc == MG_OK) rc = dy.alloc(cx_len(S, (long long)W.len(mr)));
+  if (rc == MG_OK) rc = W.upload(h, x, cm, cxp<C>(dx), mc);
+  if (rc == MG_OK && !bz) rc = W.upload(h, y, cm, cxp<C>(dy), mr);
+  if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxc<C>(dx), cxp<C>(dy), nullptr, nullptr, nullptr, a, bt, W.nr);
+  if (rc == MG_OK) rc = W.download(h, cxc<C>(dy), cm, y, mr);
   if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_spmv: stream failed");
-  dx.release();
-  dy.release();
-  return rc;
-}
-
-// ---- the host-pointer block forms (mg_block_*_CF64): Julia's column-major n x nrhs blocks, relaid at the boundary ----
-// host column-major block -> device row-major block dst (through the column-major staging block `cm`), and back
-int cx_block_upload(mg_hierarchy* h, const double* src, DevBuf<double>& cm, cx_t* dst, long long n, int nr) {
-  const hipStream_t st = h->play->stream;
-  HIP_TRY(hipMemcpyAsync(cm.p, src, sizeof(cx_t) * (size_t)n * (size_t)nr, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(mgk::cx_relayout<true>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, st, cxc(cm), dst, n, nr);
-  HIP_TRY(hipGetLastError());
-  return MG_OK;
-}
-int cx_block_download(mg_hierarchy* h, const cx_t* src, DevBuf<double>& cm, double* dst, long long n, int nr) {
-  const hipStream_t st = h->play->stream;
-  hipLaunchKernelGGL(mgk::cx_relayout<false>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, st, src, cxp(cm), n, nr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(dst, cm.p, sizeof(cx_t) * (size_t)n * (size_t)nr, hipMemcpyDeviceToHost, st));
-  HIP_TRY(spin_sync(st));
-  return MG_OK;
-}
-int cx_block_cycle_host(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, long long x_is_zero) {
-  MG_TRY(cx_block_ready(h, n, nrhs, CX_WANT64));
-  if (!B || !X) return fail(MG_ERR_INVALID, "null block");
-  const int nr = (int)nrhs;
-  MG_TRY(cx_block_ensure(h, nr));
-  CxState& S = *h->cx;
-  CxLevel& L0 = S.lev[0];
-  bool xz = (x_is_zero == 1);
-  if (x_is_zero < 0) xz = host_all_zero(X, 2 * n * nrhs);   // norm(x) > 0.0 over the whole block decides (MGcycle.jl:29)
-  int xi = 0;
-  MG_TRY(cx_block_upload(h, B, S.Bstage_t, cxp(S.Bstage_b), n, nr));
-  if (!xz) MG_TRY(cx_block_upload(h, X, S.Bstage_t, cxp(L0.Bx[xi]), n, nr));
-  MG_TRY(cx_cycle<cx_t>(h, 0, cxc(S.Bstage_b), xi, xz, h->cycle, nr));
-  return cx_block_download(h, cxc(L0.Bx[xi]), S.Bstage_t, X, n, nr);
-}
-
-// solveMG on a block (SolveFuncs.jl:14-36): the norms are Frobenius norms of the whole block
-int cx_block_solve_host(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, double tol, long long maxIter,
-                        long long* iters, double* resvec) {
-  MG_TRY(cx_block_ready(h, n, nrhs, CX_WANT64));
-  if (!B || !X) return fail(MG_ERR_INVALID, "null block");
-  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
-  const int nr = (int)nrhs;
-  MG_TRY(cx_block_ensure(h, nr));
-  CxState& S = *h->cx;
-  CxLevel& L0 = S.lev[0];
-  const cx_t* bd = cxc(S.Bstage_b);
-  int xi = 0;
-  bool xz = host_all_zero(X, 2 * n * nrhs);
-  MG_TRY(cx_block_upload(h, B, S.Bstage_t, cxp(S.Bstage_b), n, nr));
-  double res2 = 0.0;
-  if (xz) {
-    MG_TRY(cx_norm2<cx_t>(h, bd, n * nr, &res2));
-  } else {
-    MG_TRY(cx_block_upload(h, X, S.Bstage_t, cxp(L0.Bx[xi]), n, nr));
-    MG_TRY(cx_residual_norm2<cx_t>(h, L0, bd, cxc(L0.Bx[xi]), cxp(L0.Br), &res2, nr));
-  }
-  const double res0 = std::sqrt(res2);
-  if (resvec) resvec[0] = res0;
-  long long it = 0;
-  for (long long count = 1; count <= maxIter; ++count) {
-    MG_TRY(cx_cycle<cx_t>(h, 0, bd, xi, xz, h->cycle, nr));
-    xz = false;
-    MG_TRY(cx_residual_norm2<cx_t>(h, L0, bd, cxc(L0.Bx[xi]), cxp(L0.Br), &res2, nr));
-    ++it;
-    const double res = std::sqrt(res2);
-    if (resvec) resvec[count] = res;
-    if (res / res0 < tol) break;
-  }
-  if (xz) HIP_TRY(hipMemsetAsync(L0.Bx[xi].p, 0, sizeof(cx_t) * (size_t)n * (size_t)nr, h->play->stream));   // maxIter = 0 from X = 0
-  MG_TRY(cx_block_download(h, cxc(L0.Bx[xi]), S.Bstage_t, X, n, nr));
-  if (iters) *iters = it;
-  return MG_OK;
-}
-
-// Y = beta*Y + alpha*Op*X on one level, X n_cols x nrhs and Y n_rows x nrhs column-major on the host
-int cx_block_spmv_host(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* X, const double* beta,
-                       double* Y, long long nrhs) {
-  MG_TRY(cx_level_ok(h, level, CX_WANT64));
-  CxState& S = *h->cx;
-  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized");
-  MG_TRY(cx_block_nrhs_ok(nrhs));
-  MG_TRY(cx_block_schedule_ok(h));
-  MG_TRY(cx_block_coarse_ok(h, nrhs));
-  if (!alpha || !beta || !X || !Y) return fail(MG_ERR_INVALID, "null argument");
-  if (which != MG_OP_A && which != MG_OP_P && which != MG_OP_R) return fail(MG_ERR_INVALID, "bad operator selector %lld", which);
-  CxLevel& L = S.lev[(size_t)level - 1];
-  if (which != MG_OP_A && level == h->nlevels) return fail(MG_ERR_INVALID, "the coarsest level %lld has no transfer operators", level);
-  const CxMat& M = which == MG_OP_A ? L.A : which == MG_OP_P ? L.P : L.R;
-  (void)hipSetDevice(h->device);
-  const int nr = (int)nrhs;
-  const long long mr = M.n_rows, mc = M.n_cols;
-  const cx_t a = cx_t{alpha[0], alpha[1]}, bt = cx_t{beta[0], beta[1]};
-  const bool bz = bt.x == 0 && bt.y == 0;
-  DevBuf<double> cm, dx, dy;   // (released below on every path)
-  int rc = cm.alloc(2 * (size_t)std::max(mr, mc) * (size_t)nr);
-  if (rc == MG_OK) rc = dx.alloc(2 * (size_t)mc * (size_t)nr);
-  if (rc == MG_OK) rc = dy.alloc(2 * (size_t)mr * (size_t)nr);
-  if (rc == MG_OK) rc = cx_block_upload(h, X, cm, cxp(dx), mc, nr);
-  if (rc == MG_OK && !bz) rc = cx_block_upload(h, Y, cm, cxp(dy), mr, nr);
-  if (rc == MG_OK) rc = cx_spmv<mgk::AXPBY>(h, M, cxc(dx), cxp(dy), nullptr, nullptr, nullptr, a, bt, nr);
-  if (rc == MG_OK) rc = cx_block_download(h, cxc(dy), cm, Y, mr, nr);
-  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_block_spmv: stream failed");
   cm.release();
   dx.release();
   dy.release();
@@ -2407,6 +2362,32 @@ int mg_set_coarse_gmres_CF64(mg_hierarchy* h, long long n, const double* d) {
   return MG_OK;
 }
 
+// The GMRES coarsest solve alone on host arrays, behind the entry points' checks: b staged (W: a vector, or a column-major block relaid),
+// the vector or the block solve, x back, the report copied out.  (The staging blocks of the block work set are sized by the FINE level.)
+static int cx_coarse_gmres_host(mg_hierarchy* h, const double* b, double* x, long long n, CxCols W, long long* steps, long long* flag,
+                                double* resvec) {
+  (void)hipSetDevice(h->device);
+  MG_TRY(W.ensure(h));
+  CxCoarseReport report;
+  DevBuf<double> cm, db, dx;   // (released below on every path)
+  int rc = W.nr ? cm.alloc(2 * W.len(n)) : MG_OK;
+  if (rc == MG_OK) rc = db.alloc(2 * W.len(n));
+  if (rc == MG_OK) rc = dx.alloc(2 * W.len(n));
+  if (rc == MG_OK) rc = W.upload(h, b, cm, cxp(db), n);
+  if (rc == MG_OK) rc = W.nr ? cx_coarse_block_gmres(h, cxc(db), cxp(dx), W.nr, &report) : cx_coarse_gmres(h, cxc(db), cxp(dx), &report);
+  if (rc == MG_OK) rc = W.download(h, cxc(dx), cm, x, n);
+  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_coarse_gmres_CF64: stream failed");
+  cm.release();
+  db.release();
+  dx.release();
+  if (rc != MG_OK) return rc;
+  if (steps) *steps = report.used;
+  if (flag) *flag = report.flag;
+  if (resvec)
+    for (int i = 0; i < report.used; ++i) resvec[i] = report.resvec[i];
+  return MG_OK;
+}
+
 // the coarsest solve alone on host vectors: x = the GMRES coarsest solve of b; steps = the columns used, flag 0 / -1 / -9,
 // resvec[i] = err_i / ||b|| for i < steps (10 entries at most)
 int mg_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long* steps, long long* flag, double* resvec) {
@@ -2416,25 +2397,7 @@ int mg_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long long 
   if (!S.coarse_gmres) return fail(MG_ERR_STATE, "the coarsest solve of this handle is not GMRES (mg_set_coarse_gmres_CF64)");
   if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
   if (n != S.n_coarse) return fail(MG_ERR_INVALID, "n=%lld does not match the coarsest level (%lld rows)", n, S.n_coarse);
-  (void)hipSetDevice(h->device);
-  const hipStream_t st = h->play->stream;
-  const size_t bytes = sizeof(cx_t) * (size_t)n;
-  DevBuf<double> db, dx;   // (released below on every path)
-  CxCoarseReport report;
-  int rc = db.alloc(2 * (size_t)n);
-  if (rc == MG_OK) rc = dx.alloc(2 * (size_t)n);
-  if (rc == MG_OK && hipMemcpyAsync(db.p, b, bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(MG_ERR_HIP, "upload of b failed");
-  if (rc == MG_OK) rc = cx_coarse_gmres(h, cxc(db), cxp(dx), &report);
-  if (rc == MG_OK && hipMemcpyAsync(x, dx.p, bytes, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(MG_ERR_HIP, "download of x failed");
-  if (spin_sync(st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_coarse_gmres_CF64: stream failed");
-  db.release();
-  dx.release();
-  if (rc != MG_OK) return rc;
-  if (steps) *steps = report.used;
-  if (flag) *flag = report.flag;
-  if (resvec)
-    for (int i = 0; i < report.used; ++i) resvec[i] = report.resvec[i];
-  return MG_OK;
+  return cx_coarse_gmres_host(h, b, x, n, CxCols::vec(), steps, flag, resvec);
 }
 
 // The block form of the solve alone on host blocks (option coarse_gmres_blocks): b, x column-major n x nrhs, n = the coarsest order;
@@ -2450,29 +2413,7 @@ int mg_block_coarse_gmres_CF64(mg_hierarchy* h, const double* b, double* x, long
   MG_TRY(cx_block_coarse_ok(h, nrhs));
   if (!b || !x) return fail(MG_ERR_INVALID, "null block");
   if (n != S.n_coarse) return fail(MG_ERR_INVALID, "n=%lld does not match the coarsest level (%lld rows)", n, S.n_coarse);
-  if (nrhs == 1) return mg_coarse_gmres_CF64(h, b, x, n, steps, flag, resvec);
-  (void)hipSetDevice(h->device);
-  const int nr = (int)nrhs;
-  MG_TRY(cx_block_ensure(h, nr));
-  CxCoarseReport report;
-  const size_t len = 2 * (size_t)n * (size_t)nr;
-  DevBuf<double> cm, db, dx;   // (the staging blocks of the block work set are sized by the FINE level; released below on every path)
-  int rc = cm.alloc(len);
-  if (rc == MG_OK) rc = db.alloc(len);
-  if (rc == MG_OK) rc = dx.alloc(len);
-  if (rc == MG_OK) rc = cx_block_upload(h, b, cm, cxp(db), n, nr);
-  if (rc == MG_OK) rc = cx_coarse_block_gmres(h, cxc(db), cxp(dx), nr, &report);
-  if (rc == MG_OK) rc = cx_block_download(h, cxc(dx), cm, x, n, nr);
-  if (spin_sync(h->play->stream) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "mg_block_coarse_gmres_CF64: stream failed");
-  cm.release();
-  db.release();
-  dx.release();
-  if (rc != MG_OK) return rc;
-  if (steps) *steps = report.used;
-  if (flag) *flag = report.flag;
-  if (resvec)
-    for (int i = 0; i < report.used; ++i) resvec[i] = report.resvec[i];
-  return MG_OK;
+  return cx_coarse_gmres_host(h, b, x, n, nrhs == 1 ? CxCols::vec() : CxCols::blk(nrhs), steps, flag, resvec);
 }
 
 // info[0]: 1 where blocks are served on this handle's GMRES coarsest solve (option coarse_gmres_blocks), 0 otherwise; info[1]: kernel
@@ -2490,42 +2431,42 @@ int mg_block_coarse_form(mg_hierarchy* h, long long nrhs, long long* info) {
 }
 
 int mg_cycle_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long x_is_zero) {
-  return cx_cycle_host<cx_t>(h, b, x, n, nrhs, x_is_zero, CX_WANT64);
+  return cx_cycle_host<cx_t>(h, b, x, n, x_is_zero, CX_WANT64, CxCols::vec(nrhs));
 }
 int mg_cycle_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long long nrhs, long long x_is_zero) {
-  return cx_cycle_host<cf_t>(h, b, x, n, nrhs, x_is_zero, CX_WANT32);
+  return cx_cycle_host<cf_t>(h, b, x, n, x_is_zero, CX_WANT32, CxCols::vec(nrhs));
 }
 
 int mg_solve_CF64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
                   long long* iters, double* resvec) {
-  return cx_solve_host<cx_t>(h, b, x, n, nrhs, tol, maxIter, iters, resvec, CX_WANT64);
+  return cx_solve_host<cx_t>(h, b, x, n, tol, maxIter, iters, resvec, CX_WANT64, CxCols::vec(nrhs));
 }
 int mg_solve_CF32(mg_hierarchy* h, const float* b, float* x, long long n, long long nrhs, double tol, long long maxIter,
                   long long* iters, double* resvec) {
-  return cx_solve_host<cf_t>(h, b, x, n, nrhs, tol, maxIter, iters, resvec, CX_WANT32);
+  return cx_solve_host<cf_t>(h, b, x, n, tol, maxIter, iters, resvec, CX_WANT32, CxCols::vec(nrhs));
 }
 
 int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* x, const double* beta,
                  double* y, long long nrhs) {
-  return cx_spmv_host<cx_t>(h, level, which, alpha, x, beta, y, nrhs, CX_WANT64);
+  return cx_spmv_host<cx_t>(h, level, which, alpha, x, beta, y, CX_WANT64, CxCols::vec(nrhs));
 }
 int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float* alpha, const float* x, const float* beta, float* y,
                  long long nrhs) {
-  return cx_spmv_host<cf_t>(h, level, which, alpha, x, beta, y, nrhs, CX_WANT32);
+  return cx_spmv_host<cf_t>(h, level, which, alpha, x, beta, y, CX_WANT32, CxCols::vec(nrhs));
 }
 
 // blocks of right-hand sides on a CF64 handle: nrhs arrives with each call (the device-pointer forms and the block driver, which
 // also serve CF32 handles, are in mg_complex_krylov.inc)
 int mg_block_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* X, const double* beta,
                        double* Y, long long nrhs) {
-  return cx_block_spmv_host(h, level, which, alpha, X, beta, Y, nrhs);
+  return cx_spmv_host<cx_t>(h, level, which, alpha, X, beta, Y, CX_WANT64, CxCols::blk(nrhs));
 }
 int mg_block_cycle_CF64(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, long long x_is_zero) {
-  return cx_block_cycle_host(h, B, X, n, nrhs, x_is_zero);
+  return cx_cycle_host<cx_t>(h, B, X, n, x_is_zero, CX_WANT64, CxCols::blk(nrhs));
 }
 int mg_block_solve_CF64(mg_hierarchy* h, const double* B, double* X, long long n, long long nrhs, double tol, long long maxIter,
                         long long* iters, double* resvec) {
-  return cx_block_solve_host(h, B, X, n, nrhs, tol, maxIter, iters, resvec);
+  return cx_solve_host<cx_t>(h, B, X, n, tol, maxIter, iters, resvec, CX_WANT64, CxCols::blk(nrhs));
 }
 
 }  // extern "C"

@@ -294,29 +294,6 @@ int cx_fgmres_dev(mg_hierarchy* h, const cx_t* b, cx_t* x, long long inner, doub
   return fgmres_loop<zc>(sp, m, tol, maxIter, rep);
 }
 
-// the checks every driver entry point shares; host form: b, x staged through the handle's device buffers
-template <class F>
-int cx_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long maxIter, bool device_form, F&& run) {
-  MG_TRY(cx_check_ready(h, n, 1, CX_ANY));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null vector");
-  if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
-  (void)hipSetDevice(h->device);
-  CxState& S = *h->cx;
-  if (S.single && !S.K.set) MG_TRY(cx_widen_K(h));   // the Krylov product is never single
-  if (device_form) {
-    MG_TRY(cxv_aligned({b, x}));
-    return run(ccx(b), mcx(x));
-  }
-  const size_t len = 2 * (size_t)n, bytes = len * sizeof(double);
-  if (S.stage_x.n != len) MG_TRY(S.stage_x.alloc(len));
-  HIP_TRY(hipMemcpyAsync(S.stage_b.p, b, bytes, hipMemcpyHostToDevice, h->play->stream));
-  HIP_TRY(hipMemcpyAsync(S.stage_x.p, x, bytes, hipMemcpyHostToDevice, h->play->stream));
-  MG_TRY(run(cxp(S.stage_b), cxp(S.stage_x)));
-  HIP_TRY(hipMemcpyAsync(x, S.stage_x.p, bytes, hipMemcpyDeviceToHost, h->play->stream));
-  HIP_TRY(spin_sync(h->play->stream));
-  return MG_OK;
-}
-
 // ---- blocks of right-hand sides: blockBiCGSTB (SolveFuncs.jl:94-96) for VAL = ComplexF64 ---------------------------------------------
 // block_bicgstab_dev of mg_krylov.inc on complex blocks, row-major [n][k] ComplexF64 resident in HBM: products with the system operator
 // are cx_csr_stream_spmm launches, the preconditioner is one block cycle from zero (on a CF32 handle the mixed closure on the whole
@@ -634,24 +611,27 @@ int cx_block_fgmres_dev(mg_hierarchy* h, const cx_t* B, cx_t* X, int k, long lon
   return rep.finish(total, flag);
 }
 
-// the checks the block drivers' entry points share; host form: column-major blocks relaid through the block work set's staging blocks
-// run(B, X, nrhs): the driver on row-major device blocks
+// The checks every driver entry point shares, vector (W.nr == 0) or block.  device_form: b, x resident (a block: row-major [n][nrhs]);
+// host form: staged through the work set's staging buffers (a block: column-major on the host, relaid).  run(b, x): the driver.
 template <class F>
-int cx_block_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long maxIter, bool device_form, F&& run) {
-  MG_TRY(cx_block_ready(h, n, nrhs, CX_ANY));
-  if (!b || !x) return fail(MG_ERR_INVALID, "null block");
+int cx_krylov(mg_hierarchy* h, const double* b, double* x, long long n, long long maxIter, CxCols W, bool device_form, F&& run) {
+  MG_TRY(W.ready(h, n, CX_ANY));
+  if (!b || !x) return fail(MG_ERR_INVALID, "null %s", W.noun());
   if (maxIter < 0) return fail(MG_ERR_INVALID, "maxIter < 0");
   if (device_form) MG_TRY(cxv_aligned({b, x}));
   (void)hipSetDevice(h->device);
-  const int nr = (int)nrhs;
-  MG_TRY(cx_block_ensure(h, nr));
+  MG_TRY(W.ensure(h));
   CxState& S = *h->cx;
   if (S.single && !S.K.set) MG_TRY(cx_widen_K(h));   // the Krylov product is never single
-  if (device_form) return run(ccx(b), mcx(x), nr);
-  MG_TRY(cx_block_upload(h, b, S.Bstage_t, cxp(S.Bstage_b), n, nr));
-  MG_TRY(cx_block_upload(h, x, S.Bstage_t, cxp(S.Bstage_x), n, nr));
-  MG_TRY(run(cxc(S.Bstage_b), cxp(S.Bstage_x), nr));
-  return cx_block_download(h, cxc(S.Bstage_x), S.Bstage_t, x, n, nr);
+  if (device_form) return run(ccx(b), mcx(x));
+  DevBuf<double>&sb = W.stage_b(S), &sx = W.stage_x(S);
+  if (W.nr == 0 && sx.n != 2 * (size_t)n) MG_TRY(sx.alloc(2 * (size_t)n));   // (the vector iterate's staging buffer: sized on first use)
+  MG_TRY(W.upload(h, b, S.Bstage_t, cxp(sb), n));
+  MG_TRY(W.upload(h, x, S.Bstage_t, cxp(sx), n));
+  MG_TRY(run(cxc(sb), cxp(sx)));
+  MG_TRY(W.download(h, cxc(sx), S.Bstage_t, x, n));
+  HIP_TRY(spin_sync(h->play->stream));
+  return MG_OK;
 }
 
 // G = X^H Y by the one-pass kernel on its own (mg_cblk_gram_dev_CFP64): partials in `work`, the k x k result in `out`
@@ -667,6 +647,33 @@ int cx_gram_alone(const cx_t* X, const cx_t* Y, long long n, long long k, cx_t* 
   hipLaunchKernelGGL(mgk::cx_blk_gram_onepass, dim3(nb), dim3(mgk::BLK), 0, s, X, Y, n, (int)k, lg, work);
   hipLaunchKernelGGL(mgk::cx_blk_gram_final_wave, dim3((int)(k * k)), dim3(64), 0, s, work, nb, (int)k, out);
   HIP_TRY(hipGetLastError());
+  return MG_OK;
+}
+
+// One cycle on device vectors or blocks (row-major [n][nrhs]), ComplexF64, 16-byte aligned, enqueued on the handle's stream without a
+// synchronisation.  A CF32 handle runs the reference's mixed closure on the whole vector or block, from zero: bl .= b; recursiveCycle
+// from z = 0; z2 .= z (SolveFuncs.jl:52-58).
+int cx_cycle_dev(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long x_is_zero, CxCols W, const char* who) {
+  MG_TRY(W.ready(h, n, CX_ANY));
+  if (!b_dev || !x_dev) return fail(MG_ERR_INVALID, "null %s", W.noun());
+  if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for device %ss", W.noun());
+  MG_TRY(cxv_aligned({b_dev, x_dev}));
+  if (h->cx->single && !x_is_zero)
+    return fail(MG_ERR_UNSUPPORTED, "%s on a CF32 handle starts from zero (x_is_zero = 1): the mixed closure always zeroes z", who);
+  (void)hipSetDevice(h->device);
+  MG_TRY(W.ensure(h));
+  CxLevel& L0 = h->cx->lev[0];
+  const long long len = (long long)W.len(n);
+  const size_t bytes = sizeof(cx_t) * (size_t)len;
+  int xi = 0;
+  if (h->cx->single) {
+    MG_TRY(cx_narrow(h, ccx(b_dev), cxp<cf_t>(W.b(L0)), len));
+    MG_TRY(cx_cycle<cf_t>(h, 0, cxc<cf_t>(W.b(L0)), xi, true, h->cycle, W.nr));
+    return cx_widen(h, cxc<cf_t>(W.x(L0, xi)), mcx(x_dev), len);
+  }
+  if (!x_is_zero) HIP_TRY(hipMemcpyAsync(W.x(L0, xi).p, x_dev, bytes, hipMemcpyDeviceToDevice, h->play->stream));
+  MG_TRY(cx_cycle<cx_t>(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle, W.nr));
+  HIP_TRY(hipMemcpyAsync(x_dev, W.x(L0, xi).p, bytes, hipMemcpyDeviceToDevice, h->play->stream));
   return MG_OK;
 }
 
@@ -695,51 +702,10 @@ int mg_set_krylov_operator_CFP64_INT64(mg_hierarchy* h, long long n, const long 
 }
 
 int mg_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long x_is_zero) {
-  MG_TRY(cx_check_ready(h, n, 1, CX_ANY));
-  if (!b_dev || !x_dev) return fail(MG_ERR_INVALID, "null vector");
-  if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for device vectors");
-  MG_TRY(cxv_aligned({b_dev, x_dev}));
-  (void)hipSetDevice(h->device);
-  CxLevel& L0 = h->cx->lev[0];
-  const size_t bytes = 2 * sizeof(double) * (size_t)n;
-  int xi = 0;
-  if (h->cx->single) {   // the reference's mixed closure: bl .= b; recursiveCycle from z = 0; z2 .= z (SolveFuncs.jl:52-58)
-    if (!x_is_zero) return fail(MG_ERR_UNSUPPORTED, "mg_cycle_dev_CFP64 on a CF32 handle starts from zero (x_is_zero = 1): the mixed closure always zeroes z");
-    MG_TRY(cx_narrow(h, ccx(b_dev), cxp<cf_t>(L0.b), n));
-    MG_TRY(cx_cycle<cf_t>(h, 0, cxc<cf_t>(L0.b), xi, true, h->cycle));
-    return cx_widen(h, cxc<cf_t>(L0.x[xi]), mcx(x_dev), n);
-  }
-  if (!x_is_zero) HIP_TRY(hipMemcpyAsync(L0.x[xi].p, x_dev, bytes, hipMemcpyDeviceToDevice, h->play->stream));
-  MG_TRY(cx_cycle<cx_t>(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle));
-  HIP_TRY(hipMemcpyAsync(x_dev, L0.x[xi].p, bytes, hipMemcpyDeviceToDevice, h->play->stream));
-  return MG_OK;
+  return cx_cycle_dev(h, b_dev, x_dev, n, x_is_zero, CxCols::vec(), __func__);
 }
-
-// One cycle on device blocks (row-major [n][nrhs] ComplexF64, 16-byte aligned), enqueued on the handle's stream without a
-// synchronisation.  A CF32 handle runs the mixed closure on the whole block, from zero.
 int mg_block_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs, long long x_is_zero) {
-  MG_TRY(cx_block_ready(h, n, nrhs, CX_ANY));
-  if (!b_dev || !x_dev) return fail(MG_ERR_INVALID, "null block");
-  if (x_is_zero != 0 && x_is_zero != 1) return fail(MG_ERR_INVALID, "x_is_zero must be 0 or 1 for device blocks");
-  MG_TRY(cxv_aligned({b_dev, x_dev}));
-  if (h->cx->single && !x_is_zero)
-    return fail(MG_ERR_UNSUPPORTED, "mg_block_cycle_dev_CFP64 on a CF32 handle starts from zero (x_is_zero = 1): the mixed closure always zeroes z");
-  (void)hipSetDevice(h->device);
-  const int nr = (int)nrhs;
-  MG_TRY(cx_block_ensure(h, nr));
-  CxLevel& L0 = h->cx->lev[0];
-  const long long len = n * nr;
-  const size_t bytes = sizeof(cx_t) * (size_t)len;
-  int xi = 0;
-  if (h->cx->single) {
-    MG_TRY(cx_narrow(h, ccx(b_dev), cxp<cf_t>(L0.Bb), len));
-    MG_TRY(cx_cycle<cf_t>(h, 0, cxc<cf_t>(L0.Bb), xi, true, h->cycle, nr));
-    return cx_widen(h, cxc<cf_t>(L0.Bx[xi]), mcx(x_dev), len);
-  }
-  if (!x_is_zero) HIP_TRY(hipMemcpyAsync(L0.Bx[xi].p, x_dev, bytes, hipMemcpyDeviceToDevice, h->play->stream));
-  MG_TRY(cx_cycle<cx_t>(h, 0, ccx(b_dev), xi, x_is_zero == 1, h->cycle, nr));
-  HIP_TRY(hipMemcpyAsync(x_dev, L0.Bx[xi].p, bytes, hipMemcpyDeviceToDevice, h->play->stream));
-  return MG_OK;
+  return cx_cycle_dev(h, b_dev, x_dev, n, x_is_zero, CxCols::blk(nrhs), __func__);
 }
 
 // blockBiCGSTB on the whole block: b, x column-major n x nrhs on the host (mg_block_bicgstab_CFP64) or row-major [n][nrhs] device
@@ -747,14 +713,14 @@ int mg_block_cycle_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev
 // half step and after every full step.
 int mg_block_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, double tol, long long maxIter,
                             long long* iters, long long* flag, double* resvec, long long* nres) {
-  return cx_block_krylov(h, b, x, n, nrhs, maxIter, false, [&](const cx_t* B, cx_t* X, int k) {
-    return cx_block_bicgstab_dev(h, B, X, k, tol, maxIter, iters, flag, resvec, nres);
+  return cx_krylov(h, b, x, n, maxIter, CxCols::blk(nrhs), false, [&](const cx_t* B, cx_t* X) {
+    return cx_block_bicgstab_dev(h, B, X, (int)nrhs, tol, maxIter, iters, flag, resvec, nres);
   });
 }
 int mg_block_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs, double tol,
                                 long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
-  return cx_block_krylov(h, b_dev, x_dev, n, nrhs, maxIter, true, [&](const cx_t* B, cx_t* X, int k) {
-    return cx_block_bicgstab_dev(h, B, X, k, tol, maxIter, iters, flag, resvec, nres);
+  return cx_krylov(h, b_dev, x_dev, n, maxIter, CxCols::blk(nrhs), true, [&](const cx_t* B, cx_t* X) {
+    return cx_block_bicgstab_dev(h, B, X, (int)nrhs, tol, maxIter, iters, flag, resvec, nres);
   });
 }
 // blockFGMRES(inner) on the whole block, arguments as mg_block_fgmres[_dev]_FP64, layout as mg_block_bicgstab[_dev]_CFP64; resvec holds
@@ -762,38 +728,38 @@ int mg_block_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_
 int mg_block_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long nrhs, long long inner, double tol,
                           long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
-  return cx_block_krylov(h, b, x, n, nrhs, maxIter, false, [&](const cx_t* B, cx_t* X, int k) {
-    return cx_block_fgmres_dev(h, B, X, k, inner, tol, maxIter, iters, flag, resvec, nres);
+  return cx_krylov(h, b, x, n, maxIter, CxCols::blk(nrhs), false, [&](const cx_t* B, cx_t* X) {
+    return cx_block_fgmres_dev(h, B, X, (int)nrhs, inner, tol, maxIter, iters, flag, resvec, nres);
   });
 }
 int mg_block_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs, long long inner,
                               double tol, long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
-  return cx_block_krylov(h, b_dev, x_dev, n, nrhs, maxIter, true, [&](const cx_t* B, cx_t* X, int k) {
-    return cx_block_fgmres_dev(h, B, X, k, inner, tol, maxIter, iters, flag, resvec, nres);
+  return cx_krylov(h, b_dev, x_dev, n, maxIter, CxCols::blk(nrhs), true, [&](const cx_t* B, cx_t* X) {
+    return cx_block_fgmres_dev(h, B, X, (int)nrhs, inner, tol, maxIter, iters, flag, resvec, nres);
   });
 }
 
 int mg_bicgstab_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, double tol, long long maxIter,
                           long long* iters, long long* flag, double* resvec, long long* nres) {
-  return cx_krylov(h, b_dev, x_dev, n, maxIter, true,
+  return cx_krylov(h, b_dev, x_dev, n, maxIter, CxCols::vec(), true,
                    [&](const cx_t* bv, cx_t* xv) { return cx_bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
 }
 int mg_bicgstab_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, double tol, long long maxIter, long long* iters,
                       long long* flag, double* resvec, long long* nres) {
-  return cx_krylov(h, b, x, n, maxIter, false,
+  return cx_krylov(h, b, x, n, maxIter, CxCols::vec(), false,
                    [&](const cx_t* bv, cx_t* xv) { return cx_bicgstab_dev(h, bv, xv, tol, maxIter, iters, flag, resvec, nres); });
 }
 int mg_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long inner, double tol,
                         long long maxIter, long long* iters, long long* flag, double* resvec, long long* nres) {
   if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
-  return cx_krylov(h, b_dev, x_dev, n, maxIter, true,
+  return cx_krylov(h, b_dev, x_dev, n, maxIter, CxCols::vec(), true,
                    [&](const cx_t* bv, cx_t* xv) { return cx_fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
 }
 int mg_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long n, long long inner, double tol, long long maxIter,
                     long long* iters, long long* flag, double* resvec, long long* nres) {
   if (inner < 1 || inner > 64) return fail(MG_ERR_INVALID, "inner must be in [1,64]");
-  return cx_krylov(h, b, x, n, maxIter, false,
+  return cx_krylov(h, b, x, n, maxIter, CxCols::vec(), false,
                    [&](const cx_t* bv, cx_t* xv) { return cx_fgmres_dev(h, bv, xv, inner, tol, maxIter, iters, flag, resvec, nres); });
 }
 

@@ -1275,21 +1275,31 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         _check(lib, lib.mg_finalize(self.handle), "mg_finalize")
         self._schedule = sig
 
-    def fgmres_relax(self, level: int, r0, x, inner: int, tol: float = 1e-5):
+    def fgmres_relax(self, level: int, r0, x, inner: int, tol: float = 1e-5, want_bases: bool = False):
         """One FGMRES_relaxation (FGMRES.jl:48-126) with the diagonal preconditioner on As[level] and relaxPrecs[level]
-        (mg_fgmres_relax_CF64): ``x += Z t`` in place for the residual ``r0``.  Returns (rnorms, H, xi): the residual estimates of
-        the directions used (``len(rnorms)`` is the reference's ``used``), and the summed Gram scalars H = (AZ)'(AZ)
-        (inner x inner) and xi = (AZ)'r0 of all ``inner`` directions."""
-        r0 = self._host_block(r0)
-        x = self._host_block(x, True)
+        (mg_fgmres_relax_CF64 / _CF32): ``x += Z t`` in place for the residual ``r0``, both in the hierarchy's own precision.  Returns
+        (rnorms, H, xi): the residual estimates of the directions used (``len(rnorms)`` is the reference's ``used``), and the summed
+        Gram scalars H = (AZ)'(AZ) (inner x inner) and xi = (AZ)'r0 of all ``inner`` directions, formed in double.  On a
+        ``singleKcycle`` ComplexF32 hierarchy Z and AZ are complex64 and the product is formed in single; there ``want_bases`` adds
+        (Z, AZ), the n x inner complex64 bases of all ``inner`` directions."""
+        single = self._sfx == "CF32"
+        if want_bases and not single:
+            raise TypeError("want_bases is served on ComplexF32 hierarchies (mg_fgmres_relax_CF32 takes the two arrays)")
+        r0 = self._host_block(r0, dtype=self._cdtype)
+        x = self._host_block(x, True, dtype=self._cdtype)
         k = int(inner)
         H = np.zeros((max(k, 1), max(k, 1)), dtype=np.complex128)
         xi = np.zeros(max(k, 1), dtype=np.complex128)
         rn = np.zeros(max(k, 1))
         used = C.c_longlong(0)
-        _check(self.lib, self.lib.mg_fgmres_relax_CF64(self.handle, int(level), _c128(r0), _c128(x), r0.shape[0], k, float(tol), _c128(H),
-                                                       _c128(xi), _f64(rn), C.byref(used)), "mg_fgmres_relax_CF64")
-        return rn[: used.value], H, xi
+        Z = AZ = None
+        if want_bases:
+            Z = np.zeros((r0.shape[0], max(k, 1)), dtype=np.complex64, order="F")
+            AZ = np.zeros_like(Z)
+        bases = (Z.ctypes.data_as(_fp) if want_bases else None, AZ.ctypes.data_as(_fp) if want_bases else None) if single else ()
+        _check(self.lib, self._fn("fgmres_relax")(self.handle, int(level), self._vp_of(r0), self._vp_of(x), r0.shape[0], k, float(tol),
+                                                  _c128(H), _c128(xi), _f64(rn), C.byref(used), *bases), f"mg_fgmres_relax_{self._sfx}")
+        return (rn[: used.value], H, xi) + ((Z, AZ) if want_bases else ())
 
     def _set_coarse(self, param, force_sparse: bool = False):
         """`z = param.LU\\b` (MGcycle.jl:177) from the complex splu: the explicit inverse up to DENSE_COARSE_MAX rows, else the
@@ -1452,7 +1462,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         """The object handed to ``set_krylov_operator`` last (None: the drivers apply the hierarchy's fine level)."""
         return self._krylov_operator
 
-    def _krylov_c(self, name, res, b, x, *args):
+    def _cfp64_driver(self, name, res, b, x, *args):
+        """mg_<name>_CFP64(handle, b, x, n, *args, iters, flag, res, count) -> (flag, iters, res[:count]); the caller sizes ``res`` for
+        the longest history its driver may write."""
         iters, flag, count = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
         fn = getattr(self.lib, f"mg_{name}_CFP64")
         _check(self.lib, fn(self.handle, b, x, self.n, *args, C.byref(iters), C.byref(flag), _f64(res), C.byref(count)), f"mg_{name}_CFP64")
@@ -1478,23 +1490,23 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     def bicgstab(self, b, x, tol: float, maxIter: int):
         """KrylovMethods.bicgstb on the Krylov operator with the cycle as M1; returns (x, flag, iters, resvec)."""
         b, x = self._host_pair(b, x)
-        return (x,) + self._krylov_c("bicgstab", np.zeros(2 * max(int(maxIter), 0) + 1), _c128(b), _c128(x), float(tol), int(maxIter))
+        return (x,) + self._cfp64_driver("bicgstab", np.zeros(2 * max(int(maxIter), 0) + 1), _c128(b), _c128(x), float(tol), int(maxIter))
 
     def fgmres(self, b, x, inner: int, tol: float, maxIter: int):
         """KrylovMethods.fgmres (flexible, restarted) on the Krylov operator with the cycle as preconditioner; returns
         (x, flag, inner steps, resvec)."""
         b, x = self._host_pair(b, x)
-        return (x,) + self._krylov_c("fgmres", np.zeros(max(1, int(inner) * int(maxIter))), _c128(b), _c128(x), int(inner), float(tol),
-                                     int(maxIter))
+        return (x,) + self._cfp64_driver("fgmres", np.zeros(max(1, int(inner) * int(maxIter))), _c128(b), _c128(x), int(inner), float(tol),
+                                         int(maxIter))
 
     def bicgstab_dev(self, b, x, tol: float, maxIter: int):
         """The same on torch.complex128 device tensors; returns (flag, iters, resvec)."""
         pb, px = self._dev_pair(b, x)
-        return self._krylov_c("bicgstab_dev", np.zeros(2 * max(int(maxIter), 0) + 1), pb, px, float(tol), int(maxIter))
+        return self._cfp64_driver("bicgstab_dev", np.zeros(2 * max(int(maxIter), 0) + 1), pb, px, float(tol), int(maxIter))
 
     def fgmres_dev(self, b, x, inner: int, tol: float, maxIter: int):
         pb, px = self._dev_pair(b, x)
-        return self._krylov_c("fgmres_dev", np.zeros(max(1, int(inner) * int(maxIter))), pb, px, int(inner), float(tol), int(maxIter))
+        return self._cfp64_driver("fgmres_dev", np.zeros(max(1, int(inner) * int(maxIter))), pb, px, int(inner), float(tol), int(maxIter))
 
     def cycle_dev(self, b, x, x_is_zero: int):
         """One cycle on torch.complex128 device tensors (x_is_zero 0 or 1), enqueued on the library's stream without a
@@ -1522,14 +1534,20 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             a[...] = f.reshape(a.shape)
         return a
 
+    def _block_pair(self, B, X, mismatch: str, need_n: bool = False):
+        """What every host block method opens with: the guards, both blocks Fortran-ordered (X writable), the same column count - and,
+        with ``need_n``, the fine level's rows - or ValueError(mismatch).  Returns (Bf, Xf, k)."""
+        self._block_guard()
+        Bf, k = self._blk(B)
+        Xf, kx = self._blk(X, True)
+        if kx != k or (need_n and (Bf.shape[0] != self.n or Xf.shape[0] != self.n)):
+            raise ValueError(mismatch)
+        self._block_coarse_guard(k)
+        return Bf, Xf, k
+
     def block_spmv(self, level: int, which: int, alpha, X, beta, Y):
         """``Y = beta*Y + alpha*Op*X`` on one level for n x k complex128 blocks (mg_block_spmv_CF64); Y in place."""
-        self._block_guard()
-        Xf, k = self._blk(X)
-        Yf, ky = self._blk(Y, True)
-        if ky != k:
-            raise ValueError("X and Y must hold the same number of columns")
-        self._block_coarse_guard(k)
+        Xf, Yf, k = self._block_pair(X, Y, "X and Y must hold the same number of columns")
         a = np.array([complex(alpha).real, complex(alpha).imag])
         bt = np.array([complex(beta).real, complex(beta).imag])
         _check(self.lib, self.lib.mg_block_spmv_CF64(self.handle, int(level), int(which), _f64(a), _c128(Xf), _f64(bt), _c128(Yf), k),
@@ -1538,23 +1556,13 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
 
     def block_cycle(self, B, X, x_is_zero: int = -1):
         """One cycle on the whole n x k block (mg_block_cycle_CF64); X in place.  x_is_zero is a property of the whole block."""
-        self._block_guard()
-        Bf, k = self._blk(B)
-        Xf, kx = self._blk(X, True)
-        if kx != k:
-            raise ValueError("B and X must hold the same number of columns")
-        self._block_coarse_guard(k)
+        Bf, Xf, k = self._block_pair(B, X, "B and X must hold the same number of columns")
         _check(self.lib, self.lib.mg_block_cycle_CF64(self.handle, _c128(Bf), _c128(Xf), Bf.shape[0], k, int(x_is_zero)), "mg_block_cycle_CF64")
         return self._blk_back(X, Xf)
 
     def block_solve(self, B, X, tol: float, maxIter: int):
         """solveMG on the block with Frobenius norms (mg_block_solve_CF64); returns (X, iters, resvec)."""
-        self._block_guard()
-        Bf, k = self._blk(B)
-        Xf, kx = self._blk(X, True)
-        if kx != k:
-            raise ValueError("B and X must hold the same number of columns")
-        self._block_coarse_guard(k)
+        Bf, Xf, k = self._block_pair(B, X, "B and X must hold the same number of columns")
         iters = C.c_longlong(0)
         resvec = np.zeros(int(maxIter) + 1)
         _check(self.lib, self.lib.mg_block_solve_CF64(self.handle, _c128(Bf), _c128(Xf), Bf.shape[0], k, float(tol), int(maxIter),
@@ -1584,57 +1592,33 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         pb, px, k = self._dev_block(B, X)
         _check(self.lib, self.lib.mg_block_cycle_dev_CFP64(self.handle, pb, px, self.n, k, int(x_is_zero)), "mg_block_cycle_dev_CFP64")
 
-    def _block_krylov_c(self, name, b, x, k, tol, maxIter):
-        res = np.zeros(2 * max(int(maxIter), 0) + 1)
-        iters, flag, count = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        fn = getattr(self.lib, f"mg_{name}_CFP64")
-        _check(self.lib, fn(self.handle, b, x, self.n, k, float(tol), int(maxIter), C.byref(iters), C.byref(flag), _f64(res), C.byref(count)),
-               f"mg_{name}_CFP64")
-        return int(flag.value), int(iters.value), res[: count.value]
-
     def block_bicgstab(self, B, X, tol: float, maxIter: int):
         """KrylovMethods.blockBiCGSTB on the Krylov operator with the block cycle as M1 (mg_block_bicgstab_CFP64); X in place;
         returns (X, flag, iters, resvec)."""
-        self._block_guard()
-        Bf, k = self._blk(B)
-        Xf, kx = self._blk(X, True)
-        if kx != k or Bf.shape[0] != self.n or Xf.shape[0] != self.n:
-            raise ValueError(f"blocks of {self.n} x k complex values expected, the same k for B and X")
-        self._block_coarse_guard(k)
-        out = self._block_krylov_c("block_bicgstab", _c128(Bf), _c128(Xf), k, tol, maxIter)
+        Bf, Xf, k = self._block_pair(B, X, f"blocks of {self.n} x k complex values expected, the same k for B and X", need_n=True)
+        out = self._cfp64_driver("block_bicgstab", np.zeros(2 * max(int(maxIter), 0) + 1), _c128(Bf), _c128(Xf), k, float(tol), int(maxIter))
         return (self._blk_back(X, Xf),) + out
 
     def block_bicgstab_dev_CFP64(self, B, X, tol: float, maxIter: int):
         """The same on torch.complex128 device blocks [n, k]; returns (flag, iters, resvec).  (Named after its entry point:
         ``block_bicgstab_dev`` is the FP64 hierarchies' method and stays refused here, as tests/test_complex_krylov_host.py pins.)"""
         pb, px, k = self._dev_block(B, X)
-        return self._block_krylov_c("block_bicgstab_dev", pb, px, k, tol, maxIter)
-
-    def _block_fgmres_c(self, name, b, x, k, inner, tol, maxIter):
-        res = np.zeros(max(int(maxIter), 0) * max(int(inner), 1) + 1)
-        iters, flag, count = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        fn = getattr(self.lib, f"mg_{name}_CFP64")
-        _check(self.lib, fn(self.handle, b, x, self.n, k, int(inner), float(tol), int(maxIter), C.byref(iters), C.byref(flag), _f64(res),
-                            C.byref(count)), f"mg_{name}_CFP64")
-        return int(flag.value), int(iters.value), res[: count.value]
+        return self._cfp64_driver("block_bicgstab_dev", np.zeros(2 * max(int(maxIter), 0) + 1), pb, px, k, float(tol), int(maxIter))
 
     def block_fgmres(self, B, X, inner: int, tol: float, maxIter: int):
         """KrylovMethods.blockFGMRES(inner) on the Krylov operator with the block cycle as preconditioner (mg_block_fgmres_CFP64);
         X in place; returns (X, flag, inner steps in all, resvec with one entry per inner step)."""
-        self._block_guard()
-        Bf, k = self._blk(B)
-        Xf, kx = self._blk(X, True)
-        if kx != k or Bf.shape[0] != self.n or Xf.shape[0] != self.n:
-            raise ValueError(f"blocks of {self.n} x k complex values expected, the same k for B and X")
-        self._block_coarse_guard(k)
-        out = self._block_fgmres_c("block_fgmres", _c128(Bf), _c128(Xf), k, inner, tol, maxIter)
+        Bf, Xf, k = self._block_pair(B, X, f"blocks of {self.n} x k complex values expected, the same k for B and X", need_n=True)
+        out = self._cfp64_driver("block_fgmres", np.zeros(max(int(maxIter), 0) * max(int(inner), 1) + 1), _c128(Bf), _c128(Xf), k, int(inner),
+                                 float(tol), int(maxIter))
         return (self._blk_back(X, Xf),) + out
 
     def block_fgmres_dev_CFP64(self, B, X, inner: int, tol: float, maxIter: int):
         """The same on torch.complex128 device blocks [n, k]; returns (flag, inner steps, resvec).  (``block_fgmres_dev`` is the FP64
         hierarchies' method and stays refused here.)"""
         pb, px, k = self._dev_block(B, X)
-        return self._block_fgmres_c("block_fgmres_dev", pb, px, k, inner, tol, maxIter)
+        return self._cfp64_driver("block_fgmres_dev", np.zeros(max(int(maxIter), 0) * max(int(inner), 1) + 1), pb, px, k, int(inner), float(tol),
+                                  int(maxIter))
 
     def cblk_gram(self, X, Y):
         """``X^H Y`` (k x k complex128 numpy array) of two torch.complex128 device blocks [n, k] by the one-pass Gram kernel of block
@@ -1806,30 +1790,6 @@ class ComplexSingleDeviceHierarchy(ComplexDeviceHierarchy):
         if self._single_kcycle:           # (ahead of the schedule: mg_set_schedule_CF32 and mg_finalize read it)
             _check(self.lib, self.lib.mg_set_option(self.handle, b"single_kcycle", 1.0), "mg_set_option(single_kcycle)")
         super()._upload(param)
-
-    def fgmres_relax(self, level: int, r0, x, inner: int, tol: float = 1e-5, want_bases: bool = False):
-        """One FGMRES_relaxation on As[level] and relaxPrecs[level] of a ``singleKcycle`` hierarchy (mg_fgmres_relax_CF32): ``x += Z t``
-        in place for the residual ``r0``, both complex64.  Z and AZ are complex64 and the product is formed in single; H, xi and the
-        residual estimates are formed in double.  Returns (rnorms, H, xi) as the ComplexF64 method does, and with ``want_bases`` also
-        (Z, AZ): the n x inner complex64 bases of all ``inner`` directions."""
-        r0 = self._host_block(r0, dtype=np.complex64)
-        x = self._host_block(x, True, dtype=np.complex64)
-        k = int(inner)
-        H = np.zeros((max(k, 1), max(k, 1)), dtype=np.complex128)
-        xi = np.zeros(max(k, 1), dtype=np.complex128)
-        rn = np.zeros(max(k, 1))
-        used = C.c_longlong(0)
-        Z = AZ = None
-        if want_bases:
-            Z = np.zeros((r0.shape[0], max(k, 1)), dtype=np.complex64, order="F")
-            AZ = np.zeros_like(Z)
-        _check(self.lib, self.lib.mg_fgmres_relax_CF32(self.handle, int(level), r0.ctypes.data_as(_fp), x.ctypes.data_as(_fp), r0.shape[0], k,
-                                                       float(tol), _c128(H), _c128(xi), _f64(rn), C.byref(used),
-                                                       Z.ctypes.data_as(_fp) if want_bases else None,
-                                                       AZ.ctypes.data_as(_fp) if want_bases else None), "mg_fgmres_relax_CF32")
-        if want_bases:
-            return rn[: used.value], H, xi, Z, AZ
-        return rn[: used.value], H, xi
 
     def _refuse_single(self, *args, **kwargs):
         raise NotImplementedError("ComplexF32 hierarchies: replace_matrix, replace_values, get_values and rap_level_ms on the device are "
