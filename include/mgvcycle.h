@@ -1093,7 +1093,8 @@ mg_status mg_block_coarse_form(mg_hierarchy* h, long long nrhs, long long* info)
  * blocks of H (break at the first residual estimate below 1e-5) and x += Z t is one more launch.  The K-cycle runs its two FGMRES
  * steps with one synchronisation each.  Sums are deterministic (no atomics).  relaxPre / relaxPost above 8 with Jac-GMRES:
  * mg_finalize fails with MG_ERR_UNSUPPORTED.  On such a handle mg_cycle_CF64, mg_solve_CF64 and the _CFP64 drivers work unchanged; the
- * block entry points (mg_block_*_CF64 / _CFP64) return MG_ERR_UNSUPPORTED, and mg_rap_CF64 serves every schedule (it recomputes
+ * block entry points (mg_block_*_CF64 / _CFP64) return MG_ERR_UNSUPPORTED unless the option kcycle_blocks is set (the section on
+ * blocks at the end), and mg_rap_CF64 serves every schedule (it recomputes
  * operators and relaxPrecs only).
  * mg_fgmres_relax_CF64: one such relaxation on As[level] and relaxPrecs[level] with host vectors - the reference's exported
  * FGMRES_relaxation with the diagonal preconditioner: x += Z t for the residual r0 (n complex values each; 1 <= level < nlevels,
@@ -1112,7 +1113,7 @@ mg_status mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r
  * with Jac-GMRES stay MG_ERR_UNSUPPORTED).  Served then, one right-hand side: V / W / F / K with Jac / SPAI / Jac-GMRES, K with the
  * Vanka smoothers, every coarsest solve a CF32 handle serves, through mg_cycle_CF32, mg_solve_CF32, mg_cycle_dev_CFP64 and the mixed
  * closure of mg_bicgstab[_dev]_CFP64 / mg_fgmres[_dev]_CFP64; the synchronisations per cycle are those of a CF64 handle.  Still
- * MG_ERR_UNSUPPORTED: every block entry point on such a schedule, a Schwarz coarsest solve, 'K' / type 1 through the shared setters
+ * MG_ERR_UNSUPPORTED: every block entry point on such a schedule (unless the option kcycle_blocks is set as well), a Schwarz coarsest solve, 'K' / type 1 through the shared setters
  * mg_set_cycle_type / mg_set_relax_type.
  * ARITHMETIC.  Z and AZ are complex64; w = A z_j, its products and row sums, and the next direction d.*w are formed in single, in
  * stored order (the arithmetic of the CF32 sweep and residual kernels).  DEVIATION from the reference, which forms H, xi and the small
@@ -1322,7 +1323,7 @@ int mg_spmv_CF32(mg_hierarchy* h, long long level, long long which, const float*
  * Refused: nrhs < 1 (MG_ERR_INVALID), nrhs > 16 (MG_ERR_UNSUPPORTED), a Schwarz sweep as coarsest solve with nrhs > 1
  * (MG_ERR_UNSUPPORTED), an FP64 handle or a handle that is not finalized (MG_ERR_STATE), a CF32 handle in the _CF64 forms
  * (MG_ERR_STATE), a null block, a wrong n, maxIter < 0, a device block off a 16-byte boundary (MG_ERR_INVALID).  A refusal leaves the
- * handle usable.  Not served for complex blocks: PCG, the K-cycle and Jac-GMRES, the sharded forms, HIP graphs.
+ * handle usable.  Not served for complex blocks: PCG, the K-cycle and Jac-GMRES (opt-in: the next section), the sharded forms, HIP graphs.
  * (The _CF64 forms spell their status mg_status, as the re-setup entry points above do.) */
 mg_status mg_block_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double* alpha, const double* X,
                              const double* beta, double* Y, long long nrhs);
@@ -1341,6 +1342,32 @@ int mg_block_fgmres_CFP64(mg_hierarchy* h, const double* b, double* x, long long
 int mg_block_fgmres_dev_CFP64(mg_hierarchy* h, const double* b_dev, double* x_dev, long long n, long long nrhs,
                               long long inner, double tol, long long maxIter, long long* iters, long long* flag,
                               double* resvec, long long* nres);
+
+/* ---- blocks on K-cycle / Jac-GMRES complex hierarchies, OPT-IN: mg_set_option(h, "kcycle_blocks", 1) before mg_finalize (default 0) -
+ * The reference runs FGMRES_relaxation on a block as ONE long vector of length n*nrhs (FGMRES.jl:51-53, 89-97; MGcycle.jl:48-50,
+ * 72-76, 96-98): one H, one xi, one t and one break test for the whole block.  With the option every block entry point above serves
+ * a handle whose cycle is 'K' and / or whose relaxation type is 1 in that form, 1 <= nrhs <= 16; without it they return
+ * MG_ERR_UNSUPPORTED with the messages they had before the option existed.  THE COLUMNS ARE COUPLED: a column's result depends on its
+ * neighbours and on their scaling (one t for all), and it is not what the vector entry points give column by column.  A Jac-GMRES
+ * cycle is non-linear in its right-hand side: as a preconditioner it belongs under mg_block_fgmres_CFP64, not mg_block_bicgstab_CFP64.
+ * Kernels: the GRAM mode of cx_csr_stream_spmm (W = A Z_j as block j of AZ, the next direction d.*W, and per row block the partial
+ * sums over all its rows and columns of the vector form's 2 j + 3 scalars: lane registers, wavefront shuffles, LDS, no atomics, the
+ * same bits on every run).  One host synchronisation per relaxation and one per K step for the WHOLE block - the vector form's counts.
+ * Work set (with the block work set, grown with nrhs): per Jac-GMRES level 2*max(relaxPre, relaxPost) blocks of n_l x nrhs, per
+ * level from 2 on with 'K' four blocks.  A CF32 handle is served when its option single_kcycle is set as well (the mixed complex128
+ * closure of the block entry points); a GMRES coarsest solve when coarse_gmres_blocks is set as well.  Still MG_ERR_UNSUPPORTED: Vanka
+ * with 'K' on a block, a Schwarz coarsest solve on a block, nrhs > 16, more than 8 directions, FP64 handles, the sharded forms.
+ * mg_block_fgmres_relax_CF64 / _CF32: one such relaxation on As[level] and relaxPrecs[level] from host blocks, X += sum_j t_j Z_j for
+ * the residual block R0.  Both take ComplexF64 column-major n x nrhs host blocks; the CF32 form narrows on the device and returns X,
+ * Z_out and AZ_out widened, which is exact.  1 <= level < nlevels, 1 <= inner <= 8.  H_out, xi_out, rnorms_out, used_out as for
+ * mg_fgmres_relax_CF64; Z_out / AZ_out (may be NULL) receive the bases as n x nrhs x inner (block j a column-major n x nrhs block;
+ * the leading `used` blocks enter X).  Without the option: MG_ERR_UNSUPPORTED. */
+mg_status mg_block_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* R0, double* X, long long n, long long nrhs,
+                                     long long inner, double tol, double* H_out, double* xi_out, double* rnorms_out,
+                                     long long* used_out, double* Z_out, double* AZ_out);
+mg_status mg_block_fgmres_relax_CF32(mg_hierarchy* h, long long level, const double* R0, double* X, long long n, long long nrhs,
+                                     long long inner, double tol, double* H_out, double* xi_out, double* rnorms_out,
+                                     long long* used_out, double* Z_out, double* AZ_out);
 
 const char* mg_last_error(void);
 const char* mg_version(void);

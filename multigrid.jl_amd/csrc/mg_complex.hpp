@@ -15,7 +15,8 @@
 // chunk has a block of its own and the whole workgroup strides over it.
 // Epilogues: AXPBY, RESID (optionally also z1 = d.*r), SMOOTH, and GRAM - one step of the FGMRES relaxation (Jac-GMRES smoothing,
 // K-cycle; ComplexF64, and ComplexF32 where the handle's option single_kcycle is set): w = A z_j stored as column j of AZ, the next direction d.*w, and the per-row-block partial sums of
-// column j of H = (AZ)'(AZ) and of xi[j] = dot(w, r0), see CxVecArgsT.
+// column j of H = (AZ)'(AZ) and of xi[j] = dot(w, r0), see CxVecArgsT.  cx_csr_stream_spmm has the same mode for a block of right-hand
+// sides taken as ONE long vector (the handle's option kcycle_blocks): one H, one xi for the whole block.
 // CGDOT - one Arnoldi step of the GMRES coarsest solve (coarseSolveType "GMRES"; ComplexF64 only): w = A z_i stored as the next
 // basis vector, and the per-row-block partial sums of dot(v_0, w), the first coefficient of the Gram-Schmidt chain that follows
 // (mg_cxvec.hpp).
@@ -65,7 +66,7 @@ struct CxCsrDev {
   int n_rows;
 };
 
-// GRAM (cx_csr_stream_spmv only; both pair types): step j of FGMRES_relaxation (FGMRES.jl:82-104) in the walk that computes w = A z_j.
+// GRAM (both pair types; cx_csr_stream_spmm: the same step on a block taken as one long vector, option kcycle_blocks): step j of FGMRES_relaxation (FGMRES.jl:82-104) in the walk that computes w = A z_j.
 // The mode follows mgk::Mode (AXPBY, RESID, SMOOTH) and is served by no other kernel.
 constexpr int GRAM = 3;
 constexpr int GRAM_MAXV = 8;                       // directions of one relaxation at most (mgcv::MAXV, the width of the combination pass)
@@ -315,18 +316,39 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmv(CxCsrDev<PTR, VT> A, C
 // across the G lanes (8 * nrhs in single).  d[row] of SMOOTH is shared by the columns.  sumsq: the per-row-block partial of
 // sum |out|^2 over ALL columns (solveMG's Frobenius norm).  A row longer than a chunk: BLK / G lane groups stride over it,
 // and the per-column partial sums are added in lane-group order by one lane per column.
+// RESID optionally stores z1 = d[row] * r as well (the first direction of the FGMRES relaxation that follows).  GRAM: step j of that
+// relaxation on the block as ONE long vector of length n * nrhs (FGMRES.jl:51-53): W = A Z_j is stored (y: block j of AZ, blocks
+// ldz = n * nrhs apart), znext = d[row] * W optionally, and every row block leaves the 2 j + 3 partial sums of CxVecArgsT over all its
+// rows and columns in the vector form's slots.
 // ------------------------------------------------------------------------------------------------
 template <int MODE, typename C>
 __device__ __forceinline__ void cx_operands_blk(const CxVecArgsT<C>& v, int row, size_t e, C& pb, C& pd, C& px) {
   if (MODE == AXPBY) {
     if (!v.beta_zero) pb = cmul(v.beta, v.y[e]);
   } else {
-    pb = v.b[e];
+    pb = MODE == GRAM ? v.r0[e] : v.b[e];
   }
   if (MODE == SMOOTH) {
     pd = v.d[row];
     px = v.x[e];
   }
+  if ((MODE == RESID && v.z1) || (MODE == GRAM && v.znext)) pd = v.d[row];   // (shared by the columns, as SMOOTH shares it)
+}
+
+// the Gram scalars of one (row, column) of a block added to the lane's own sums gs[0 .. 2 j + 3): w = W[row][c], the entries of the
+// earlier blocks AZ_i at the same flat index e, r0v = R0[row][c] - cx_gram_row on the long vector of length n * nrhs
+template <typename C>
+__device__ __forceinline__ void cx_gram_item(double* gs, const CxVecArgsT<C>& v, size_t e, C wv, C r0v) {
+  const int j = v.gj;
+  C azv[GRAM_MAXV - 1];
+#pragma unroll
+  for (int i = 0; i < GRAM_MAXV - 1; ++i) azv[i] = i < j ? v.az[(size_t)i * v.ldz + e] : C{};
+  double s[GRAM_NS];
+#pragma unroll
+  for (int q = 0; q < GRAM_NS; ++q) s[q] = 0.0;
+  cx_gram_row(s, j, azv, wv, r0v);
+#pragma unroll
+  for (int q = 0; q < GRAM_NS; ++q) gs[q] += s[q];
 }
 
 template <int MODE, typename PTR, typename VT, typename C>
@@ -335,7 +357,7 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmm(CxCsrDev<PTR, VT> A, C
   __shared__ int scol[CX_CHUNK];
   __shared__ int srow[MAXROWS + 1];
   __shared__ C lred[BLK];
-  __shared__ double red[BLK / 64];
+  __shared__ double red[(MODE == GRAM ? GRAM_NS : 1) * (BLK / 64)];
 
   const int tid = threadIdx.x;
   const int G = 1 << lg;
@@ -355,6 +377,9 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmm(CxCsrDev<PTR, VT> A, C
     lred[tid] = acc;
     __syncthreads();
     double sq = 0.0;
+    double gs[MODE == GRAM ? GRAM_NS : 1];
+#pragma unroll
+    for (int q = 0; q < (MODE == GRAM ? GRAM_NS : 1); ++q) gs[q] = 0.0;
     if (tid < nrhs) {   // (tid == c: one lane per column, lane-group order)
       C s = C{};
       for (int g = 0; g < (BLK >> lg); ++g) s += lred[(g << lg) + tid];
@@ -364,6 +389,24 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmm(CxCsrDev<PTR, VT> A, C
       const C o = cx_epilogue<MODE>(v, s, pb, pd, px);
       v.y[e] = o;
       sq = cabs2(o);
+      if (MODE == RESID && v.z1) v.z1[e] = cmul(pd, o);
+      if constexpr (MODE == GRAM) {
+        if (v.znext) v.znext[e] = cmul(pd, o);
+        cx_gram_item(gs, v, e, o, pb);
+      }
+    }
+    if constexpr (MODE == GRAM) {   // the block's only row: the scalars of its nrhs result lanes, summed in the first wavefront
+      if (tid < 64) {
+        const int ns = 2 * v.gj + 3;
+#pragma unroll
+        for (int q = 0; q < GRAM_NS; ++q)
+          if (q < ns) {   // (uniform)
+            double t = gs[q];
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+            if (tid == 0) v.gpart[(size_t)q * A.nblocks + bid] = t;
+          }
+      }
+      return;
     }
     if (v.sumsq && tid < 64) {   // nrhs <= 16: the columns sit in the first wavefront
       for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
@@ -396,6 +439,9 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmm(CxCsrDev<PTR, VT> A, C
   __syncthreads();
   // ---- one lane per (row, column): the row from LDS in stored order, fused epilogue ---------------
   double sq = 0.0;
+  double gs[MODE == GRAM ? GRAM_NS : 1];
+#pragma unroll
+  for (int q = 0; q < (MODE == GRAM ? GRAM_NS : 1); ++q) gs[q] = 0.0;
   const int nitems = nrows << lg;
   for (int t = tid; t < nitems; t += BLK) {
     const int lrow = t >> lg;
@@ -409,7 +455,32 @@ __global__ __launch_bounds__(BLK) void cx_csr_stream_spmm(CxCsrDev<PTR, VT> A, C
     for (int k = s; k < en; ++k) acc += cmul(sval[k], v.x[(size_t)scol[k] * nrhs + c]);
     const C o = cx_epilogue<MODE>(v, acc, pb, pd, px);
     v.y[e] = o;
-    sq += cabs2(o);
+    if (MODE == RESID && v.z1) v.z1[e] = cmul(pd, o);
+    if constexpr (MODE == GRAM) {
+      if (v.znext) v.znext[e] = cmul(pd, o);
+      cx_gram_item(gs, v, e, o, pb);
+    } else {
+      sq += cabs2(o);
+    }
+  }
+  if constexpr (MODE == GRAM) {
+    // 2 j + 3 scalars over all rows AND columns of the row block: a lane's registers over the items it owns, wavefront shuffles, the
+    // workgroup's LDS, one partial per scalar and row block - the vector form's slots, no atomics, the same bits on every run
+    const int ns = 2 * v.gj + 3;
+#pragma unroll
+    for (int q = 0; q < GRAM_NS; ++q)
+      if (q < ns) {   // (uniform)
+        double t = gs[q];
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+        if ((tid & 63) == 0) red[q * (BLK / 64) + (tid >> 6)] = t;
+      }
+    __syncthreads();
+    if (tid < ns) {
+      double t = 0.0;
+      for (int w = 0; w < BLK / 64; ++w) t += red[tid * (BLK / 64) + w];
+      v.gpart[(size_t)tid * A.nblocks + bid] = t;
+    }
+    return;
   }
   if (v.sumsq) {   // a deterministic per-block partial of sum |out|^2 over all columns, summed by sum_final
     for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
@@ -689,6 +760,23 @@ __global__ __launch_bounds__(BLK) void cx_dscale_sumsq(const C* __restrict__ d, 
   for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += stride) {
     const C bv = b[i];
     z[i] = cmul(d[i], bv);
+    acc += cabs2(bv);
+  }
+  const double s = block_sum(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// The same front for a row-major block [n][nrhs] (m = n * nrhs): Z_1 = d.*B with d[row] shared by the columns, and the partials of
+// ||B||_F^2 - the long vector's rnorm0 (FGMRES.jl:51-53, 65)
+template <typename C>
+__global__ __launch_bounds__(BLK) void cx_dscale_sumsq_blk(const C* __restrict__ d, const C* __restrict__ b, C* __restrict__ z, long long m,
+                                                           int nrhs, double* __restrict__ partial) {
+  __shared__ double red[BLK / 64];
+  const long long stride = (long long)gridDim.x * BLK;
+  double acc = 0.0;
+  for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < m; i += stride) {
+    const C bv = b[i];
+    z[i] = cmul(d[i / nrhs], bv);
     acc += cabs2(bv);
   }
   const double s = block_sum(acc, red);

@@ -1,6 +1,6 @@
 // mg_complex.inc - part of libmgvcycle.so's single translation unit (included by mgvcycle.hip in this order; not compiled on its own).
 // ComplexF64 / Int64 hierarchies (the _CF64 entry points of include/mgvcycle.h): generic CSR on one GPU, V / W / F / K cycles,
-// pointwise, Jac-GMRES or Vanka relaxation (K and Jac-GMRES: one right-hand side, CF64 handles and - option single_kcycle - CF32 ones; Vanka: both precisions, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
+// pointwise, Jac-GMRES or Vanka relaxation (K and Jac-GMRES: CF64 handles and - option single_kcycle - CF32 ones, one right-hand side or - option kcycle_blocks - a block taken as one long vector; Vanka: both precisions, one right-hand side), dense-inverse, sparse-LU or GMRES coarsest solve
 // (the last: one host synchronisation per solve; blocks of right-hand sides by its block form where the option coarse_gmres_blocks asks for it).  The state lives apart from the real levels (CxState);
 // the handle's real side is never finalized, so every FP64 entry point refuses a CF64 handle.
 // The ComplexF64 Krylov drivers on these hierarchies (mg_*_CFP64) follow in mg_complex_krylov.inc; their state is part of CxState.
@@ -61,6 +61,9 @@ struct CxLevel {
   // FGMRES_relaxation's Z and AZ (FGMRESmem, FGMRES.jl:1-30), column-major, allocated by mg_finalize only when the schedule needs them:
   DevBuf<double> relaxZ, relaxAZ;   // Jac-GMRES smoothing on this level: max(npre, npost) columns (memRelax)
   DevBuf<double> kZ, kAZ;           // the K-cycle's two FGMRES steps ON this level (levels 2 .. nl-1): 2 columns (memKcycle of the level above)
+  // The same directions for a block of right-hand sides taken as one long vector (option kcycle_blocks): direction j is a row-major
+  // block [n][blk_cap] at j * n * nr.  Part of the block work set (cx_block_ensure), allocated only where the schedule needs them.
+  DevBuf<double> BrelaxZ, BrelaxAZ, BkZ, BkAZ;
   VankaCore* vanka = nullptr;       // relaxation type 2: the cells' blocks (mg_set_vanka_CF64 / _CF32), released with the handle
   int vanka_type = 0;
   void release_vanka() {
@@ -128,6 +131,7 @@ struct CxState {
       L.d.release(); L.b.release(); L.r.release(); L.x[0].release(); L.x[1].release();
       L.Bb.release(); L.Br.release(); L.Bx[0].release(); L.Bx[1].release();
       L.relaxZ.release(); L.relaxAZ.release(); L.kZ.release(); L.kAZ.release();
+      L.BrelaxZ.release(); L.BrelaxAZ.release(); L.BkZ.release(); L.BkAZ.release();
       L.release_vanka();
     }
     gpart.release(); gscal.release();
@@ -328,7 +332,7 @@ int cx_spmv(mg_hierarchy* h, const CxMat& M, const C* x, typename cx_non_deduced
   v.x = x; v.y = y; v.b = b; v.d = d; v.sumsq = sumsq;
   v.alpha = alpha; v.beta = beta;
   v.beta_zero = (beta.x == 0 && beta.y == 0) ? 1 : 0;
-  if (z1 && (MODE != mgk::RESID || nr != 0 || !d)) return fail(MG_ERR_INVALID, "internal: z1 = d.*r comes out of the vector residual only");
+  if (z1 && (MODE != mgk::RESID || !d)) return fail(MG_ERR_INVALID, "internal: z1 = d.*r comes out of the residual only");
   v.z1 = z1;
   if (M.cplx) {
     if (M.wide) cx_launch<MODE, long long, C, C>(h, M, M.rowptr64.p, v, nr);
@@ -669,6 +673,10 @@ struct CxCols {
   DevBuf<double>& cw_b(CxState& S) const { return nr ? S.Bcw_b : S.cw_b; }   // the widened coarsest pair of a CF32 handle
   DevBuf<double>& cw_x(CxState& S) const { return nr ? S.Bcw_x : S.cw_x; }
   DevBuf<double>& lu_work(CxState& S) const { return nr ? S.BluWork : S.luWork; }   // the triangular sweeps' work vector
+  DevBuf<double>& relaxZ(CxLevel& L) const { return nr ? L.BrelaxZ : L.relaxZ; }    // the directions of the FGMRES relaxation
+  DevBuf<double>& relaxAZ(CxLevel& L) const { return nr ? L.BrelaxAZ : L.relaxAZ; }
+  DevBuf<double>& kZ(CxLevel& L) const { return nr ? L.BkZ : L.kZ; }
+  DevBuf<double>& kAZ(CxLevel& L) const { return nr ? L.BkAZ : L.kAZ; }
   int served(mg_hierarchy* h) const;                                 // the column count, the schedule and the coarsest solve take it
   int ready(mg_hierarchy* h, long long n, CxWant want) const;        // + the handle, finalized, n = the fine level's rows
   int ensure(mg_hierarchy* h) const { return nr ? cx_block_ensure(h, nr) : MG_OK; }
@@ -817,36 +825,30 @@ int cx_gram_ensure(mg_hierarchy* h, size_t nblocks) {
 
 // step j: w = A z into column j of AZ, znext = d.*w (null: the last direction, or a preconditioner that is a cycle)
 // C: the pair type of the level (cx_t or cf_t), deduced from z
+// nr >= 1: z, r0, znext and the columns of AZ are row-major blocks [n][nr] taken as long vectors (the block kernel; the same scalars)
 template <typename C>
 int cx_gram_step(mg_hierarchy* h, const CxLevel& L, const C* z, typename cx_non_deduced<C>::type* AZ, int j,
-                 const typename cx_non_deduced<C>::type* r0, typename cx_non_deduced<C>::type* znext) {
+                 const typename cx_non_deduced<C>::type* r0, typename cx_non_deduced<C>::type* znext, int nr = 0) {
   CxState& S = *h->cx;
+  const size_t ld = CxCols::of(nr).len(L.n);
   const CxMat& M = L.A;
   if (j < 0 || j >= mgk::GRAM_MAXV) return fail(MG_ERR_INVALID, "internal: direction %d of an FGMRES relaxation", j);
   if (S.gpart.n < (size_t)CxState::GSCAL * (size_t)M.nblocks) return fail(MG_ERR_STATE, "internal: the relaxation's partial sums are not sized");
   if (M.single != (sizeof(C) == sizeof(cf_t))) return fail(MG_ERR_INVALID, "internal: operator and vectors differ in precision");
   mgk::CxVecArgsT<C> v = {};
   v.x = z;
-  v.y = AZ + (size_t)j * (size_t)L.n;
+  v.y = AZ + (size_t)j * ld;
   v.d = cxc<C>(L.d);
   v.beta_zero = 1;
   v.az = AZ;
-  v.ldz = L.n;
+  v.ldz = (long long)ld;
   v.gj = j;
   v.r0 = r0;
   v.znext = znext;
   v.gpart = S.gpart.p + (size_t)cx_gram_slot(j) * (size_t)M.nblocks;
-  if (M.wide) {
-    mgk::CxCsrDev<long long, C> D;
-    D.rowptr = M.rowptr64.p; D.colidx = M.colidx.p; D.val = static_cast<const C*>(M.vals()); D.blk_row = M.blk_row.p;
-    D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
-    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, long long, C, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
-  } else {
-    mgk::CxCsrDev<int, C> D;
-    D.rowptr = M.rowptr.p; D.colidx = M.colidx.p; D.val = static_cast<const C*>(M.vals()); D.blk_row = M.blk_row.p;
-    D.nblocks = M.nblocks; D.n_rows = (int)M.n_rows;
-    hipLaunchKernelGGL((mgk::cx_csr_stream_spmv<mgk::GRAM, int, C, C>), dim3((unsigned)M.nblocks), dim3(mgk::BLK), 0, h->play->stream, D, v);
-  }
+  if (nr < 0 || nr > mgk::BLK_KMAX) return fail(MG_ERR_INVALID, "internal: a block of %d columns", nr);
+  if (M.wide) cx_launch<mgk::GRAM, long long, C, C>(h, M, M.rowptr64.p, v, nr);
+  else cx_launch<mgk::GRAM, int, C, C>(h, M, M.rowptr.p, v, nr);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -915,13 +917,15 @@ struct CxRelaxReport {
 // enqueued back to back - step j + 1 needs w_j only, never t - and the host replays the reference's loop on the leading blocks of H:
 // at step j the (j+1) x (j+1) solve, break at the first rn < tol (FGMRES.jl:114-117), used = j + 1.  Directions beyond `used` are
 // not read (the reference's zero-padded H gives the same t).
+// nr >= 1: r0, x and every direction are row-major blocks [n][nr], and the relaxation is the reference's long-vector form
+// (FGMRES.jl:51-53, 89-97): ONE H, xi, t and break test for the whole block, so its columns are coupled.
 template <typename C>
 int cx_fgmres_relax(mg_hierarchy* h, const CxLevel& L, const C* r0, typename cx_non_deduced<C>::type* x, int inner, double tol,
-                    typename cx_non_deduced<C>::type* Z, typename cx_non_deduced<C>::type* AZ, CxRelaxReport* report = nullptr) {
+                    typename cx_non_deduced<C>::type* Z, typename cx_non_deduced<C>::type* AZ, CxRelaxReport* report = nullptr, int nr = 0) {
   if (inner <= 0) return MG_OK;   // w = Z*t with no columns: x unchanged (FGMRES.jl:119-123)
   if (inner > mgk::GRAM_MAXV) return fail(MG_ERR_UNSUPPORTED, "an FGMRES relaxation of %d directions (at most %d)", inner, mgk::GRAM_MAXV);
-  const size_t n = (size_t)L.n;
-  for (int j = 0; j < inner; ++j) MG_TRY(cx_gram_step(h, L, Z + (size_t)j * n, AZ, j, r0, j + 1 < inner ? Z + (size_t)(j + 1) * n : nullptr));
+  const size_t n = CxCols::of(nr).len(L.n);
+  for (int j = 0; j < inner; ++j) MG_TRY(cx_gram_step(h, L, Z + (size_t)j * n, AZ, j, r0, j + 1 < inner ? Z + (size_t)(j + 1) * n : nullptr, nr));
   const double* s = nullptr;
   MG_TRY(cx_gram_read(h, 0, (inner + 1) * (inner + 1), L.A.nblocks, &s));
   const double rnorm0 = std::sqrt(s[0]);
@@ -936,13 +940,18 @@ int cx_fgmres_relax(mg_hierarchy* h, const CxLevel& L, const C* r0, typename cx_
     if (rn < tol) break;
   }
   if (report) report->used = used;
-  return cx_relax_combine(h, Q, used, Z, x, L.n);
+  return cx_relax_combine(h, Q, used, Z, x, (long long)n);
 }
 
 // z_1 = d.*b with the partials of ||b||^2 (scalar 0): the front of a relaxation from x = 0, where r0 = b
+// (nr >= 1: Z_1 = d.*B on a row-major block, the partials of ||B||_F^2)
 template <typename C>
-int cx_relax_front_zero(mg_hierarchy* h, const CxLevel& L, const C* b, typename cx_non_deduced<C>::type* Z) {
-  hipLaunchKernelGGL(mgk::cx_dscale_sumsq<C>, dim3((unsigned)L.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, Z, L.n, h->cx->gpart.p);
+int cx_relax_front_zero(mg_hierarchy* h, const CxLevel& L, const C* b, typename cx_non_deduced<C>::type* Z, int nr = 0) {
+  if (nr == 0)
+    hipLaunchKernelGGL(mgk::cx_dscale_sumsq<C>, dim3((unsigned)L.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, Z, L.n, h->cx->gpart.p);
+  else
+    hipLaunchKernelGGL(mgk::cx_dscale_sumsq_blk<C>, dim3((unsigned)L.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, cxc<C>(L.d), b, Z, L.n * nr, nr,
+                       h->cx->gpart.p);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
@@ -962,8 +971,8 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   constexpr bool is64 = sizeof(typename mgk::cx_scalar<C>::type) == sizeof(double);
   const bool gmres_relax = h->relax_type == 1;   // Jac-GMRES (MGcycle.jl:35-38, 48-50, 96-98)
   const double gmresTol = 1e-5;                  // l.5
-  if ((gmres_relax || ctype == 'K') && ((!is64 && !h->opt.single_kcycle) || nr != 0))
-    return fail(MG_ERR_UNSUPPORTED, "Jac-GMRES smoothing and the K-cycle serve CF64 handles (CF32 ones with the option single_kcycle) and one right-hand side");
+  if ((gmres_relax || ctype == 'K') && ((!is64 && !h->opt.single_kcycle) || (nr != 0 && !h->opt.kcycle_blocks)))
+    return fail(MG_ERR_UNSUPPORTED, "Jac-GMRES smoothing and the K-cycle serve CF64 handles (CF32 ones with the option single_kcycle) and one right-hand side");   // (blocks: the option kcycle_blocks)
   const bool vanka_relax = h->relax_type == 2;   // Vanka (l.51-52, 99-100): x relaxed in place, no ping-pong
   if (vanka_relax && nr != 0 && !h->opt.vanka_blocks) return fail(MG_ERR_UNSUPPORTED, "Vanka relaxation (type 2) serves one right-hand side");
   if (vanka_relax) {   // (a block, option vanka_blocks: the block form of the smoother on Bx, in place as well)
@@ -972,12 +981,13 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
     MG_TRY(cx_vanka_relax<C>(h, L, b, x, L.npre, xzero, nr));
   } else if (gmres_relax) {
     // r = b - A x (l.28-31) with ||r||^2 and z_1 = d.*r from the same pass; from x = 0, r0 = b
-    C* x = cxp<C>(L.x[xi]);
-    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * (size_t)L.n, h->play->stream));
+    // (a block, option kcycle_blocks: the same on the block work set, the block one long vector)
+    C* x = cxp<C>(W.x(L, xi));
+    if (xzero) HIP_TRY(hipMemsetAsync(x, 0, sizeof(C) * W.len(L.n), h->play->stream));
     if (L.npre > 0) {
-      if (xzero) MG_TRY(cx_relax_front_zero<C>(h, L, b, cxp<C>(L.relaxZ)));
-      else MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const C*)x, cxp<C>(L.r), b, cxc<C>(L.d), S.gpart.p, one, zero, 0, cxp<C>(L.relaxZ)));
-      MG_TRY(cx_fgmres_relax<C>(h, L, xzero ? b : cxc<C>(L.r), x, (int)L.npre, gmresTol, cxp<C>(L.relaxZ), cxp<C>(L.relaxAZ)));
+      if (xzero) MG_TRY(cx_relax_front_zero<C>(h, L, b, cxp<C>(W.relaxZ(L)), nr));
+      else MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const C*)x, cxp<C>(W.r(L)), b, cxc<C>(L.d), S.gpart.p, one, zero, nr, cxp<C>(W.relaxZ(L))));
+      MG_TRY(cx_fgmres_relax<C>(h, L, xzero ? b : cxc<C>(W.r(L)), x, (int)L.npre, gmresTol, cxp<C>(W.relaxZ(L)), cxp<C>(W.relaxAZ(L)), nullptr, nr));
     }
   } else {
     MG_TRY(cx_relax<C>(h, L, b, xi, xzero, L.npre, nr));                                  // l.26-31, 54
@@ -993,20 +1003,21 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
     // K-cycle (l.72-76): two FGMRES steps on A_{l+1} xc = bc from xc = 0, preconditioned by the K-cycle of level l+1 from zero.  Each
     // step: one inner cycle, its result copied into Z, one GRAM launch (no znext: the preconditioner is a cycle), one synchronisation -
     // so the break after step 1 costs no speculative sub-cycle.
-    const size_t n1 = (size_t)C1.n;
-    C *Z = cxp<C>(C1.kZ), *AZ = cxp<C>(C1.kAZ);
+    // (a block: the two steps on the long vector of length n1 * nr, the inner cycles on the whole block)
+    const size_t n1 = W.len(C1.n);
+    C *Z = cxp<C>(W.kZ(C1)), *AZ = cxp<C>(W.kAZ(C1));
     RelaxLsqC Q(2);
     double rnorm0 = 0.0;
     int used = 0;
     for (int j = 0; j < 2; ++j) {
       int cj = 0;
-      MG_TRY(cx_cycle<C>(h, l + 1, j == 0 ? bc : (const C*)AZ, cj, true, 'K', 0));          // z = MMG(r0) / MMG(w)  (FGMRES.jl:83-87)
-      HIP_TRY(hipMemcpyAsync(Z + (size_t)j * n1, C1.x[cj].p, sizeof(C) * n1, hipMemcpyDeviceToDevice, h->play->stream));
+      MG_TRY(cx_cycle<C>(h, l + 1, j == 0 ? bc : (const C*)AZ, cj, true, 'K', nr));         // z = MMG(r0) / MMG(w)  (FGMRES.jl:83-87)
+      HIP_TRY(hipMemcpyAsync(Z + (size_t)j * n1, W.x(C1, cj).p, sizeof(C) * n1, hipMemcpyDeviceToDevice, h->play->stream));
       if (j == 0) {                                                                         // rnorm0 = norm(r0)  (l.65)
-        hipLaunchKernelGGL(mgk::cx_sumsq_partial<C>, dim3((unsigned)C1.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, bc, C1.n, S.gpart.p);
+        hipLaunchKernelGGL(mgk::cx_sumsq_partial<C>, dim3((unsigned)C1.A.nblocks), dim3(mgk::BLK), 0, h->play->stream, bc, (long long)n1, S.gpart.p);
         HIP_TRY(hipGetLastError());
       }
-      MG_TRY(cx_gram_step<C>(h, C1, Z + (size_t)j * n1, AZ, j, bc, nullptr));
+      MG_TRY(cx_gram_step<C>(h, C1, Z + (size_t)j * n1, AZ, j, bc, nullptr, nr));
       const double* s = nullptr;
       MG_TRY(cx_gram_read(h, j == 0 ? 0 : cx_gram_slot(1), j == 0 ? cx_gram_slot(1) : 5, C1.A.nblocks, &s));
       if (j == 0) rnorm0 = std::sqrt(s[0]);
@@ -1016,8 +1027,8 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
       if (rn < gmresTol) break;                                                             // l.114-117
     }
     ci = 0;                                                                                 // xc = 0 + Z t  (l.121-123)
-    HIP_TRY(hipMemsetAsync(C1.x[ci].p, 0, sizeof(C) * n1, h->play->stream));
-    MG_TRY(cx_relax_combine(h, Q, used, Z, cxp<C>(C1.x[ci]), C1.n));
+    HIP_TRY(hipMemsetAsync(W.x(C1, ci).p, 0, sizeof(C) * n1, h->play->stream));
+    MG_TRY(cx_relax_combine(h, Q, used, Z, cxp<C>(W.x(C1, ci)), (long long)n1));
   } else {
     MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, true, ctype, nr));                                // xc = 0 (l.63-64), l.78
     if (ctype == 'W') MG_TRY(cx_cycle<C>(h, l + 1, bc, ci, false, 'W', nr));               // l.79-80
@@ -1028,18 +1039,19 @@ int cx_cycle(mg_hierarchy* h, int l, const C* b, int& xi, bool xzero, char ctype
   if (vanka_relax) return cx_vanka_relax<C>(h, L, b, cxp<C>(W.x(L, xi)), L.npost, false, nr);   // l.99-100
   if (gmres_relax) {                                                                      // r = b - A x, FGMRES_relaxation (l.92-98)
     if (L.npost > 0) {
-      C* x = cxp<C>(L.x[xi]);
-      MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const C*)x, cxp<C>(L.r), b, cxc<C>(L.d), S.gpart.p, one, zero, 0, cxp<C>(L.relaxZ)));
-      MG_TRY(cx_fgmres_relax<C>(h, L, cxc<C>(L.r), x, (int)L.npost, gmresTol, cxp<C>(L.relaxZ), cxp<C>(L.relaxAZ)));
+      C* x = cxp<C>(W.x(L, xi));
+      MG_TRY(cx_spmv<mgk::RESID>(h, L.A, (const C*)x, cxp<C>(W.r(L)), b, cxc<C>(L.d), S.gpart.p, one, zero, nr, cxp<C>(W.relaxZ(L))));
+      MG_TRY(cx_fgmres_relax<C>(h, L, cxc<C>(W.r(L)), x, (int)L.npost, gmresTol, cxp<C>(W.relaxZ(L)), cxp<C>(W.relaxAZ(L)), nullptr, nr));
     }
     return MG_OK;
   }
   return cx_relax<C>(h, L, b, xi, false, L.npost, nr);                                   // r = b - A x, relax (l.92-102)
 }
 
-// The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51); that form is not built here.
+// The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51): served where the handle's option
+// kcycle_blocks is set (default 0: refused, as before that form existed; Vanka with 'K' stays refused either way).
 int cx_block_schedule_ok(mg_hierarchy* h) {
-  if (h->cycle == 'K' || h->relax_type == 1)
+  if ((h->cycle == 'K' || h->relax_type == 1) && (!h->opt.kcycle_blocks || h->relax_type == 2))
     return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy");
   // (served by the block form of the smoother where the handle's option vanka_blocks is set; default 0: refused, as before it existed)
   if (h->relax_type == 2 && !h->opt.vanka_blocks) return fail(MG_ERR_UNSUPPORTED, "blocks of right-hand sides are not served on a complex Vanka hierarchy");
@@ -1093,7 +1105,24 @@ int cx_block_ensure(mg_hierarchy* h, int nr) {
         MG_TRY(vanka_block_ensure(L.vanka, nr));
       }
   }
-  if (nr <= S.blk_cap) return MG_OK;
+  // the direction blocks of the long-vector FGMRES relaxation (option kcycle_blocks), where the schedule needs them: per level with
+  // Jac-GMRES max(npre, npost) blocks each of Z and AZ, per level with 'K' from level 2 on two blocks each (cx_finalize's counts)
+  const int nl = (int)h->nlevels;
+  const bool dirs = h->opt.kcycle_blocks;
+  auto zlen = [&](int l, size_t kk) {
+    const CxLevel& L = S.lev[(size_t)l];
+    return (dirs && h->relax_type == 1 && l < nl - 1) ? (size_t)std::max(L.npre, L.npost) * cx_len(S, L.n) * kk : (size_t)0;
+  };
+  auto klen = [&](int l, size_t kk) {
+    return (dirs && h->cycle == 'K' && l >= 1 && l < nl - 1) ? 2 * cx_len(S, S.lev[(size_t)l].n) * kk : (size_t)0;
+  };
+  if (nr <= S.blk_cap) {   // (the option may have been set since the work set was sized: then it is sized again, with the directions)
+    bool sized = true;
+    for (int l = 0; l < nl; ++l)
+      sized = sized && S.lev[(size_t)l].BrelaxZ.n >= zlen(l, (size_t)S.blk_cap) && S.lev[(size_t)l].BkZ.n >= klen(l, (size_t)S.blk_cap);
+    if (sized) return MG_OK;
+    nr = S.blk_cap;
+  }
   (void)hipSetDevice(h->device);
   HIP_TRY(spin_sync(h->play->stream));   // (an earlier block call may still read the buffers replaced below)
   S.blk_cap = 0;
@@ -1107,6 +1136,17 @@ int cx_block_ensure(mg_hierarchy* h, int nr) {
   if (S.single) {
     MG_TRY(S.Bcw_b.alloc(nc));
     MG_TRY(S.Bcw_x.alloc(nc));
+  }
+  for (int l = 0; l < nl; ++l) {
+    CxLevel& L = S.lev[(size_t)l];
+    for (DevBuf<double>* d : {&L.BrelaxZ, &L.BrelaxAZ}) {
+      if (zlen(l, k) == 0) d->release();
+      else MG_TRY(d->alloc(zlen(l, k)));
+    }
+    for (DevBuf<double>* d : {&L.BkZ, &L.BkAZ}) {
+      if (klen(l, k) == 0) d->release();
+      else MG_TRY(d->alloc(klen(l, k)));
+    }
   }
   if (S.coarse_multi) {   // (no allocation inside the cycle: the factor applier's work vectors for nr columns)
     CxLu* F = S.coarse_multi;
@@ -2021,6 +2061,87 @@ int cx_fgmres_relax_host(mg_hierarchy* h, long long level, const T* r0, T* x, lo
   return MG_OK;
 }
 
+// The same relaxation on a block of right-hand sides taken as one long vector (option kcycle_blocks; FGMRES.jl:51-53): R0, X and the
+// bases are ComplexF64 column-major n x nrhs host blocks for both precisions (relaid to the device's row-major layout at the boundary;
+// a CF32 handle narrows on the device and returns X, Z and AZ widened, which is exact).  Z_out / AZ_out (optional): n x nrhs x inner,
+// of which the leading `used` blocks enter X.
+template <typename C>
+int cx_block_fgmres_relax_host(mg_hierarchy* h, long long level, const double* R0, double* X, long long n, long long nrhs, long long inner,
+                               double tol, double* H_out, double* xi_out, double* rnorms_out, long long* used_out, double* Z_out,
+                               double* AZ_out) {
+  constexpr bool single = sizeof(C) == sizeof(cf_t);
+  const char* name = single ? "mg_block_fgmres_relax_CF32" : "mg_block_fgmres_relax_CF64";
+  MG_TRY(cx_level_ok(h, level, single ? CX_WANT32 : CX_WANT64));
+  CxState& S = *h->cx;
+  if (!h->opt.kcycle_blocks) return fail(MG_ERR_UNSUPPORTED, "%s is not served without the option kcycle_blocks", name);
+  if (S.single && !h->opt.single_kcycle) return fail(MG_ERR_UNSUPPORTED, "%s is not served for CF32 handles without the option single_kcycle", name);
+  if (!S.finalized) return fail(MG_ERR_STATE, "hierarchy not finalized: call mg_finalize first");
+  if (level >= h->nlevels) return fail(MG_ERR_INVALID, "level %lld holds no relaxPrecs (the coarsest level is solved, not relaxed)", level);
+  MG_TRY(cx_block_nrhs_ok(nrhs));
+  if (inner > mgk::GRAM_MAXV) return fail(MG_ERR_UNSUPPORTED, "an FGMRES relaxation of %lld directions (at most %d)", inner, mgk::GRAM_MAXV);
+  if (inner < 1) return fail(MG_ERR_INVALID, "inner=%lld outside 1..%d", inner, mgk::GRAM_MAXV);
+  if (!R0 || !X) return fail(MG_ERR_INVALID, "null block");
+  CxLevel& L = S.lev[(size_t)level - 1];
+  if (n != L.n) return fail(MG_ERR_INVALID, "n=%lld does not match level %lld (%lld rows)", n, level, L.n);
+  (void)hipSetDevice(h->device);
+  MG_TRY(cx_gram_ensure(h, (size_t)L.A.nblocks));
+  const hipStream_t st = h->play->stream;
+  const int k = (int)inner, nr = (int)nrhs;
+  const CxCols W = CxCols::of(nr);
+  const size_t len = W.len(n), dlen = cx_len(S, n) * (size_t)nr;
+  DevBuf<double> dr, dx, dZ, dAZ, cm, rm;   // (released below on every path; cm / rm: one column-major and one row-major ComplexF64 block)
+  RelaxLsqC Q(k);
+  std::vector<double> rn((size_t)k, 0.0);
+  CxRelaxReport report;
+  report.Q = &Q;
+  report.rnorms = rn.data();
+  // host block -> dst (the handle's precision, row-major), and back
+  auto up = [&](const double* host, DevBuf<double>& dst) -> int {
+    MG_TRY(W.upload<cx_t>(h, host, cm, single ? cxp(rm) : cxp(dst), n));
+    if (single) MG_TRY(cx_narrow(h, cxc(rm), cxp<cf_t>(dst), (long long)len));
+    return MG_OK;
+  };
+  auto down = [&](const C* src, double* host) -> int {
+    if constexpr (single) {
+      MG_TRY(cx_widen(h, src, cxp(rm), (long long)len));
+      return W.download<cx_t>(h, cxc(rm), cm, host, n);
+    } else {
+      return W.download<cx_t>(h, src, cm, host, n);
+    }
+  };
+  int rc = dr.alloc(dlen);
+  if (rc == MG_OK) rc = dx.alloc(dlen);
+  if (rc == MG_OK) rc = dZ.alloc(dlen * (size_t)k);
+  if (rc == MG_OK) rc = dAZ.alloc(dlen * (size_t)k);
+  if (rc == MG_OK) rc = cm.alloc(2 * len);
+  if (rc == MG_OK) rc = rm.alloc(2 * len);
+  if (rc == MG_OK) rc = up(R0, dr);
+  if (rc == MG_OK) rc = up(X, dx);
+  if (rc == MG_OK) rc = cx_relax_front_zero<C>(h, L, cxc<C>(dr), cxp<C>(dZ), nr);
+  if (rc == MG_OK) rc = cx_fgmres_relax<C>(h, L, cxc<C>(dr), cxp<C>(dx), k, tol, cxp<C>(dZ), cxp<C>(dAZ), &report, nr);
+  if (rc == MG_OK) rc = down(cxc<C>(dx), X);
+  for (int j = 0; j < k && rc == MG_OK && Z_out; ++j) rc = down(cxc<C>(dZ) + (size_t)j * len, Z_out + 2 * (size_t)j * len);
+  for (int j = 0; j < k && rc == MG_OK && AZ_out; ++j) rc = down(cxc<C>(dAZ) + (size_t)j * len, AZ_out + 2 * (size_t)j * len);
+  if (spin_sync(st) != hipSuccess && rc == MG_OK) rc = fail(MG_ERR_HIP, "%s: stream failed", name);
+  for (DevBuf<double>* d : {&dr, &dx, &dZ, &dAZ, &cm, &rm}) d->release();
+  if (rc != MG_OK) return rc;
+  for (int j = report.used; j < k; ++j) cx_gram_fill(Q, j, S.h_gscal);   // (the directions behind a break: summed, not used)
+  if (H_out)
+    for (int a = 0; a < k * k; ++a) {
+      H_out[2 * a] = Q.H[(size_t)a].real();
+      H_out[2 * a + 1] = Q.H[(size_t)a].imag();
+    }
+  if (xi_out)
+    for (int a = 0; a < k; ++a) {
+      xi_out[2 * a] = Q.xi[(size_t)a].real();
+      xi_out[2 * a + 1] = Q.xi[(size_t)a].imag();
+    }
+  if (rnorms_out)
+    for (int a = 0; a < k; ++a) rnorms_out[a] = a < report.used ? rn[(size_t)a] : 0.0;
+  if (used_out) *used_out = report.used;
+  return MG_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -2130,6 +2251,18 @@ int mg_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* r0, dou
 int mg_fgmres_relax_CF32(mg_hierarchy* h, long long level, const float* r0, float* x, long long n, long long inner, double tol,
                          double* H_out, double* xi_out, double* rnorms_out, long long* used_out, float* Z_out, float* AZ_out) {
   return cx_fgmres_relax_host<cf_t, float>(h, level, r0, x, n, inner, tol, H_out, xi_out, rnorms_out, used_out, Z_out, AZ_out);
+}
+
+// The same relaxation on a block of right-hand sides as ONE long vector (option kcycle_blocks): see include/mgvcycle.h
+int mg_block_fgmres_relax_CF64(mg_hierarchy* h, long long level, const double* R0, double* X, long long n, long long nrhs, long long inner,
+                               double tol, double* H_out, double* xi_out, double* rnorms_out, long long* used_out, double* Z_out,
+                               double* AZ_out) {
+  return cx_block_fgmres_relax_host<cx_t>(h, level, R0, X, n, nrhs, inner, tol, H_out, xi_out, rnorms_out, used_out, Z_out, AZ_out);
+}
+int mg_block_fgmres_relax_CF32(mg_hierarchy* h, long long level, const double* R0, double* X, long long n, long long nrhs, long long inner,
+                               double tol, double* H_out, double* xi_out, double* rnorms_out, long long* used_out, double* Z_out,
+                               double* AZ_out) {
+  return cx_block_fgmres_relax_host<cf_t>(h, level, R0, X, n, nrhs, inner, tol, H_out, xi_out, rnorms_out, used_out, Z_out, AZ_out);
 }
 
 // A of a CF32 handle from interleaved (re, im) float pairs (the reference's AT values, conjugated here once), P and R from floats

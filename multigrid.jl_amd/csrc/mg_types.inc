@@ -157,6 +157,11 @@ bool host_all_zero(const double* x, long long len) {
   X(bool, single_kcycle, false)            /* ComplexF32 hierarchies: serve the K-cycle and Jac-GMRES smoothing (mg_set_schedule_CF32, \
                                               mg_fgmres_relax_CF32; Gram sums and least squares in double); 0: refused on a CF32 \
                                               handle, as before the single form existed; read at mg_finalize and at every call */ \
+  X(bool, kcycle_blocks, false)            /* complex hierarchies with cycle 'K' and / or Jac-GMRES smoothing: serve blocks of right-hand \
+                                              sides by the reference's long-vector form (one H, xi, t and break test per relaxation for \
+                                              the whole block: the columns are coupled; the GRAM mode of cx_csr_stream_spmm); 0: a \
+                                              block on such a hierarchy is refused, as before that form existed; set before \
+                                              mg_finalize, read at every call */ \
   X(bool, vanka_device_setup, false)       /* complex Vanka hierarchies whose blocks were built on the device (mg_build_vanka_CF64): \
                                               mg_rap_CF64 recomputes the operators and rebuilds the blocks in HBM; 0: it refuses a \
                                               Vanka handle, as before the device build existed; read at every call */ \

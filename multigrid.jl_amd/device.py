@@ -271,6 +271,8 @@ SIGNATURES = {
     "mg_cycle_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
     "mg_block_spmv_CF64": (C.c_int, [_vp, _ll, _ll, _dp, _dp, _dp, _dp, _ll]),
     "mg_block_cycle_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
+    "mg_block_fgmres_relax_CF64": (C.c_int, [_vp, _ll, _dp, _dp, _ll, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp, _dp, _dp]),
+    "mg_block_fgmres_relax_CF32": (C.c_int, [_vp, _ll, _dp, _dp, _ll, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp, _dp, _dp]),
     "mg_block_solve_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _dp]),
     "mg_block_cycle_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
     "mg_block_bicgstab_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, C.c_double, _ll, _lp, _lp, _dp, _lp]),
@@ -1104,7 +1106,7 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
     """A ComplexF64 hierarchy on the device (mg_create_CF64): generic CSR, V / W / F / K cycles, Jac / SPAI / Jac-GMRES relaxation
     or (a param with ``complexVanka=True``) the Vanka cell-block smoothers (blocks only for a param with ``vankaBlocks=True``),
     dense-inverse, sparse-LU or GMRES coarsest solve (the last adds one host synchronisation per coarsest solve and serves blocks only for a param with ``blockCoarseGMRES=True``: ``block_coarse_gmres``).  The handle serves one right-hand side; blocks of up to 16 go through the ``block_*``
-    methods, which take the column count with each call (not on a K-cycle / Jac-GMRES hierarchy).  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
+    methods, which take the column count with each call (on a K-cycle / Jac-GMRES hierarchy only for a param with ``blockKcycle=True``: the block is then one long vector, its columns coupled).  ``param.As[l]`` is the applied operator A (= the reference's AT^H): it is
     uploaded as the reference's AT arrays, colptr = indptr+1, rowval = indices+1, nzval = conj(A.data), which the library
     conjugates back.  P and R are real."""
 
@@ -1211,6 +1213,9 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         self._vanka_blocks = self._vanka and bool(getattr(param, "vankaBlocks", False))
         if self._vanka_blocks:            # blocks on a Vanka hierarchy: the block form of the smoother (opt-in, read at every call)
             _check(lib, lib.mg_set_option(self.handle, b"vanka_blocks", 1.0), "mg_set_option(vanka_blocks)")
+        self._kcycle_blocks = bool(getattr(param, "blockKcycle", False))
+        if self._kcycle_blocks:           # blocks on a K-cycle / Jac-GMRES hierarchy: the long-vector form (opt-in, ahead of mg_finalize)
+            _check(lib, lib.mg_set_option(self.handle, b"kcycle_blocks", 1.0), "mg_set_option(kcycle_blocks)")
         self._vanka_device_setup = self._vanka and bool(getattr(param, "vankaDeviceSetup", False))
         if self._vanka_device_setup:      # mg_rap_CF64 serves the Vanka handle: operators and blocks refreshed in HBM (opt-in, read at every call)
             _check(lib, lib.mg_set_option(self.handle, b"vanka_device_setup", 1.0), "mg_set_option(vanka_device_setup)")
@@ -1237,10 +1242,12 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
             _check(lib, lib.mg_set_cycle_type(self.handle, ord(param.cycleType)), "mg_set_cycle_type")
 
     def _block_guard(self):
-        """The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51); that form is not built."""
+        """The reference runs its FGMRES relaxation on a block as one long vector (FGMRES.jl:51); that form runs where the param asked
+        for it (``blockKcycle=True``: the handle's option kcycle_blocks; never for Vanka with 'K') and is refused otherwise."""
         self._vanka_block_guard()
         sched = getattr(self, "_schedule", None)
-        if sched is not None and (sched[0] == "K" or sched[1] == "Jac-GMRES"):
+        if sched is not None and (sched[0] == "K" or sched[1] == "Jac-GMRES") and (
+                not getattr(self, "_kcycle_blocks", False) or getattr(self, "_vanka", False)):
             raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy "
                                       "(solve the columns one after the other)")
 
@@ -1299,6 +1306,35 @@ class ComplexDeviceHierarchy(DeviceHierarchy):
         bases = (Z.ctypes.data_as(_fp) if want_bases else None, AZ.ctypes.data_as(_fp) if want_bases else None) if single else ()
         _check(self.lib, self._fn("fgmres_relax")(self.handle, int(level), self._vp_of(r0), self._vp_of(x), r0.shape[0], k, float(tol),
                                                   _c128(H), _c128(xi), _f64(rn), C.byref(used), *bases), f"mg_fgmres_relax_{self._sfx}")
+        return (rn[: used.value], H, xi) + ((Z, AZ) if want_bases else ())
+
+    def block_fgmres_relax(self, level: int, R0, X, inner: int, tol: float = 1e-5, want_bases: bool = False):
+        """One FGMRES_relaxation on the n x k complex128 block ``R0`` taken as ONE long vector of length n*k (FGMRES.jl:51-53;
+        mg_block_fgmres_relax_CF64 / _CF32; a param with ``blockKcycle=True``): ``X += sum_j t_j Z_j`` in place, one H, xi, t and break
+        test for the whole block - its columns are coupled.  Returns (rnorms, H, xi) as ``fgmres_relax`` does; ``want_bases`` adds
+        (Z, AZ), complex128 arrays of shape (n, k, inner) holding all ``inner`` direction blocks (on a ComplexF32 hierarchy the
+        device's complex64 values widened, which is exact)."""
+        if not getattr(self, "_kcycle_blocks", False):
+            raise NotImplementedError("blocks of right-hand sides are not served on a K-cycle / Jac-GMRES complex hierarchy "
+                                      "(solve the columns one after the other)")
+        Bf, k = self._blk(R0)
+        Xf, kx = self._blk(X, True)
+        if kx != k or Xf.shape[0] != Bf.shape[0]:
+            raise ValueError("R0 and X must hold the same number of rows and columns")
+        m = max(int(inner), 1)
+        H = np.zeros((m, m), dtype=np.complex128)
+        xi = np.zeros(m, dtype=np.complex128)
+        rn = np.zeros(m)
+        used = C.c_longlong(0)
+        Z = AZ = None
+        if want_bases:
+            Z = np.zeros((Bf.shape[0], k, m), dtype=np.complex128, order="F")
+            AZ = np.zeros_like(Z)
+        _check(self.lib, self._fn("block_fgmres_relax")(self.handle, int(level), _c128(Bf), _c128(Xf), Bf.shape[0], k, int(inner), float(tol),
+                                                        _c128(H), _c128(xi), _f64(rn), C.byref(used),
+                                                        _c128(Z) if want_bases else None, _c128(AZ) if want_bases else None),
+               f"mg_block_fgmres_relax_{self._sfx}")
+        self._blk_back(X, Xf)
         return (rn[: used.value], H, xi) + ((Z, AZ) if want_bases else ())
 
     def _set_coarse(self, param, force_sparse: bool = False):

@@ -53,6 +53,7 @@ class MGparam:
     coarseDeviceInverse: bool = False  # the coarsest operator's explicit inverse is built (and refreshed) on the device
     singleDeviceSetup: bool = False    # singlePrecision only: replaceMatrixInHierarchy refreshes the resident hierarchy in HBM
     singleKcycle: bool = False         # singlePrecision only: the K-cycle and Jac-GMRES smoothing on the ComplexF32 hierarchy
+    blockKcycle: bool = False          # complex only: blocks on a K-cycle / Jac-GMRES hierarchy, the block one long vector (columns coupled)
     VAL: Any = np.float64
     IND: Any = np.int64
     # device side (no reference counterpart): handle of the HIP cycle library + last residual history
@@ -67,7 +68,8 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                transferOperatorType="FullWeighting", *, singlePrecision: bool = False,
                blockCoarseGMRES: bool = False, complexVanka: bool = False, vankaBlocks: bool = False,
                vankaDeviceSetup: bool = False, coarseDeviceInverse: bool = False,
-               singleDeviceSetup: bool = False, singleKcycle: bool = False) -> MGparam:
+               singleDeviceSetup: bool = False, singleKcycle: bool = False,
+               blockKcycle: bool = False) -> MGparam:
     """Positional constructor with the reference's defaults (MGdef.jl:149-161).
 
     ``relaxPre``/``relaxPost`` may be ints or functions of the (1-based) level, as in MGdef.jl:98-99,158-159.
@@ -110,7 +112,16 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     Jac-GMRES, and K with the Vanka smoothers, one right-hand side.  The directions Z and A Z are complex64 and the product is formed
     in single; the Gram sums, the small least squares and the break test are formed in double (a deviation from the reference, which
     forms them in ComplexF32 where the residual estimate is noise at the 1e-5 break).  Blocks of right-hand sides stay refused on
-    such a schedule.  Without it a ComplexF32 param with ``"K"`` or ``"Jac-GMRES"`` is refused, as before.
+    such a schedule (unless ``blockKcycle=True`` is set as well).  Without it a ComplexF32 param with ``"K"`` or ``"Jac-GMRES"`` is
+    refused, as before.
+    ``blockKcycle=True`` (keyword only, with a complex ``VAL``; the handle's option ``kcycle_blocks``) serves blocks of 1 to 16
+    right-hand sides on a hierarchy with ``cycleType="K"`` and / or ``relaxType="Jac-GMRES"`` in the reference's form: every FGMRES
+    relaxation and every K step takes the block as ONE long vector of length n*k (FGMRES.jl:51-53), with one H, one t and one break
+    test for the whole block.  The columns of a block are therefore coupled - a column's result depends on its neighbours and on
+    their scaling, and differs from what the same column gives alone.  A Jac-GMRES cycle is non-linear in its right-hand side:
+    as a preconditioner it belongs under block FGMRES (``solveBlockGMRES_MG_CFP64``), not block BiCGSTAB.  With ``singlePrecision``
+    it needs ``singleKcycle=True`` as well, with ``coarseSolveType="GMRES"`` ``blockCoarseGMRES=True``.  Vanka with ``"K"`` and a
+    Schwarz coarsest solve stay refused on a block.  Without it such blocks are refused, as before; a real ``VAL`` refuses it.
     """
     if np.dtype(VAL) not in (np.dtype(np.float64), np.dtype(np.complex128)):
         raise TypeError("only VAL=Float64 or VAL=ComplexF64 (np.complex128) is supported on the device path; a ComplexF32 "
@@ -137,6 +148,9 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
     if singleKcycle and not singlePrecision:
         raise NotImplementedError("singleKcycle=True serves a ComplexF32 hierarchy (singlePrecision=True); ComplexF64 hierarchies "
                                   "run the K-cycle and Jac-GMRES without it")
+    if blockKcycle and np.dtype(VAL) != np.complex128:
+        raise NotImplementedError("blockKcycle=True serves VAL=ComplexF64 (singlePrecision or not): blocks on a K-cycle / Jac-GMRES "
+                                  "hierarchy are a feature of the complex path")
     if singlePrecision:
         VAL = np.complex64
     if np.dtype(IND) != np.int64:
@@ -153,7 +167,7 @@ def getMGparam(VAL=np.float64, IND=np.int64, levels=3, numCores=8, maxIter=20, r
                    blockCoarseGMRES=bool(blockCoarseGMRES), complexVanka=bool(complexVanka),
                    vankaBlocks=bool(vankaBlocks), vankaDeviceSetup=bool(vankaDeviceSetup),
                    coarseDeviceInverse=bool(coarseDeviceInverse), singleDeviceSetup=bool(singleDeviceSetup),
-                   singleKcycle=bool(singleKcycle), VAL=np.dtype(VAL).type, IND=np.int64)
+                   singleKcycle=bool(singleKcycle), blockKcycle=bool(blockKcycle), VAL=np.dtype(VAL).type, IND=np.int64)
 
 
 def is_complex(param: MGparam) -> bool:
@@ -228,7 +242,7 @@ def copySolver(MG: MGparam) -> MGparam:
                      blockCoarseGMRES=bool(MG.blockCoarseGMRES), complexVanka=bool(MG.complexVanka),
                      vankaBlocks=bool(MG.vankaBlocks), vankaDeviceSetup=bool(MG.vankaDeviceSetup),
                      coarseDeviceInverse=bool(MG.coarseDeviceInverse), singleDeviceSetup=bool(MG.singleDeviceSetup),
-                     singleKcycle=bool(MG.singleKcycle))
+                     singleKcycle=bool(MG.singleKcycle), blockKcycle=bool(MG.blockKcycle))
     kind = _solver_object(MG.LU)
     if kind == "dd":
         from .domain_decomposition import copySolver as copy_dd
