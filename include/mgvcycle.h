@@ -537,12 +537,34 @@ int mg_lu_create_CFP64_INT64(long long device_id, long long n, const long long* 
 int mg_lu_solve_CFP64(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose);
 int mg_lu_solve_dev_CFP64(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs,
                           long long doTranspose);
-/* The form a handle's factors are applied in, either value type; doTranspose selects the transposed (adjoint) set and builds
- * it if needed.  info[0..7): value type (0 Float64, 1 ComplexF64); 1 for the chip-wide form; order of the dense trailing
+/* Single factors (applyLUsolve_FP32_UINT32, applyLUsolve_CFP32_UINT32, applyLUsolve_CFP32_INT64; the forms a Helmholtz inversion
+ * builds, because the factors are what fills memory): the layout, limits, validation and adjoint convention of
+ * mg_lu_create_CFP64_INT64 with Lval, Uval, b and x in float (interleaved for ComplexF32), row pointers 1-based Int64 as in every
+ * form, and column indices and p, q in the index type of the name (1-based).  Arithmetic: factor values, b, y, x and the work
+ * vectors are STORED in single - 12 / 8 bytes per factor entry with its column index, against 20 - and every row is EVALUATED in
+ * double: a value and the gathered y are widened on load, products, partial sums, the subtraction from the right-hand side and
+ * the division by the diagonal are double, the result is rounded once on its store.  The dense trailing block is gathered and
+ * inverted in double and its inverse stored in single.  A rerun gives the same bits.  A solve entry point of another value type
+ * fails with MG_ERR_STATE and leaves the handle usable; n, nnz or n*nrhs beyond int32 return MG_ERR_UNSUPPORTED. */
+int mg_lu_create_FP32_UINT32(long long device_id, long long n, const long long* Lptr, const unsigned int* Lcol,
+                             const float* Lval, const long long* Uptr, const unsigned int* Ucol, const float* Uval,
+                             const unsigned int* p, const unsigned int* q, mg_lu** out);
+int mg_lu_create_CFP32_UINT32(long long device_id, long long n, const long long* Lptr, const unsigned int* Lcol,
+                              const float* Lval, const long long* Uptr, const unsigned int* Ucol, const float* Uval,
+                              const unsigned int* p, const unsigned int* q, mg_lu** out);
+int mg_lu_create_CFP32_INT64(long long device_id, long long n, const long long* Lptr, const long long* Lcol,
+                             const float* Lval, const long long* Uptr, const long long* Ucol, const float* Uval,
+                             const long long* p, const long long* q, mg_lu** out);
+int mg_lu_solve_FP32(mg_lu* f, const float* b, float* x, long long n, long long nrhs, long long doTranspose);
+int mg_lu_solve_dev_FP32(mg_lu* f, const float* b_dev, float* x_dev, long long n, long long nrhs, long long doTranspose);
+int mg_lu_solve_CFP32(mg_lu* f, const float* b, float* x, long long n, long long nrhs, long long doTranspose);
+int mg_lu_solve_dev_CFP32(mg_lu* f, const float* b_dev, float* x_dev, long long n, long long nrhs, long long doTranspose);
+/* The form a handle's factors are applied in, any value type; doTranspose selects the transposed (adjoint) set and builds
+ * it if needed.  info[0..7): value type (0 Float64, 1 ComplexF64, 2 Float32, 3 ComplexF32); 1 for the chip-wide form; order of the dense trailing
  * block; launched levels of L ahead of it and of U behind it; all dependency levels of L and of U. */
 int mg_lu_form(mg_lu* f, long long doTranspose, long long* info);
 /* Measurement: `warmup` untimed solves on device vectors (row-major [n][nrhs], as the _dev solve of the handle's value
- * type), then `reps` solves, each enqueued between two events on the handle's stream - the second recorded before the host
+ * type - for a single handle b_dev and x_dev point to float data), then `reps` solves, each enqueued between two events on the handle's stream - the second recorded before the host
  * waits, so a sample is stream time without the host's wake-up; ms[0..reps) in milliseconds.  The factor set of the direction
  * is built before the first sample. */
 int mg_lu_time_dev(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose,
@@ -1014,6 +1036,14 @@ mg_status mg_get_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, double*
  * mg_transpose_hierarchy. */
 mg_status mg_adjoint_hierarchy_CF64(mg_hierarchy* h);
 mg_status mg_adjoint_hierarchy_CF32(mg_hierarchy* h);
+
+/* ComplexF32 factors on a CF32 handle (a parallelJuliaSolver(ComplexF32, Int64) as param.LU): Lval, Uval interleaved floats.  The
+ * coarsest solve applies them to the cycle's own single bc - no widening and narrowing passes around it - with the arithmetic of
+ * mg_lu_*_CFP32, in one workgroup below lu_multi_min_rows rows and chip-wide from there on, for a vector and for blocks.  A CF64
+ * or FP64 handle refuses it (MG_ERR_STATE); mg_set_coarse_lu_CF64_INT64 on a CF32 handle keeps the widened ComplexF64 route. */
+mg_status mg_set_coarse_lu_CF32_INT64(mg_hierarchy* h, long long n, const long long* Lptr, const long long* Lcol,
+                                      const float* Lval, const long long* Uptr, const long long* Ucol,
+                                      const float* Uval, const long long* p, const long long* q);
 
 /* ---- The GMRES coarsest solve on a complex handle ----------------------------------------------------------------------------
  * coarseSolveType "GMRES" for complex handles (MGsetup.jl:335-336, MGcycle.jl:152-164): d = param.LU = relaxParam ./ diag(A_c), n

@@ -550,7 +550,7 @@ int mg_set_coarse_lu_FP64_INT64(mg_hierarchy* h, long long n, const long long* L
   h->luML = h->luMU = 0;
   h->luInvL.release(); h->luInvU.release(); h->luTail.release();
   if (h->lu_multi) {
-    // (the complex applier's cxlu_upload, mg_complex.inc, carries the same estimate with 16-byte values: keep the two in step)
+    // (the templated applier's cxlu_upload, mg_complex.inc, carries the same estimate with sizeof(value) bytes: keep the two in step)
     // Size M of the trailing block: a level costs ~8 us of dependent latency whatever its width, the dense product
     // 8*M^2/2 bytes of traffic per factor - take the candidate with the smallest estimate.  (33^3 Poisson level under
     // a minimum-degree ordering: 3284 levels per factor at M = 0, 639 at M = 4096, 132 at M = 8192.)
@@ -1186,8 +1186,22 @@ struct mg_lu {
   std::vector<double> Lval, Uval;
   mg_hierarchy* fwd = nullptr;
   mg_hierarchy* trans = nullptr;
-  CxLu* cx = nullptr;   // a ComplexF64 handle (mg_lu_create_CFP64_INT64): the applier of mg_complex.inc, nothing above is used
+  // value type of the factors: 0 Float64 (the hierarchies above), 1 ComplexF64, 2 Float32, 3 ComplexF32 - the last three are held by
+  // the applier of mg_complex.inc in its instantiation for that type, and nothing above is used
+  int kind = 0;
+  CxLu* cx = nullptr;
+  CxLuT<cf_t>* cf = nullptr;
+  CxLuT<float>* sf = nullptr;
 };
+extern "C++" {   // (templates: this file sits inside the extern "C" block of the entry points)
+namespace {
+const char* lu_kind_name(int kind) { return kind == 0 ? "Float64" : kind == 1 ? "ComplexF64" : kind == 2 ? "Float32" : "ComplexF32"; }
+template <typename V> CxLuT<V>*& mg_lu_slot(mg_lu* f);
+template <> CxLuT<cx_t>*& mg_lu_slot<cx_t>(mg_lu* f) { return f->cx; }
+template <> CxLuT<cf_t>*& mg_lu_slot<cf_t>(mg_lu* f) { return f->cf; }
+template <> CxLuT<float>*& mg_lu_slot<float>(mg_lu* f) { return f->sf; }
+}  // namespace
+}  // extern "C++"
 namespace {
 // CSR (1-based) of the transpose of an n x n CSR (1-based) matrix; columns of every row come out ascending
 void transpose_csr1(long long n, const std::vector<long long>& ptr, const std::vector<long long>& col, const std::vector<double>& val,
@@ -1274,7 +1288,7 @@ int mg_lu_create_FP64_INT64(long long device_id, long long n, const long long* L
 // overwrites it, parLU.cpp:176)
 int mg_lu_solve_FP64(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose) {
   if (!f) return fail(MG_ERR_INVALID, "null factor handle");
-  if (f->cx) return fail(MG_ERR_STATE, "mg_lu_solve_FP64 on a handle of ComplexF64 factors (mg_lu_solve_CFP64)");
+  if (f->kind != 0) return fail(MG_ERR_STATE, "mg_lu_solve_FP64 on a handle of %s factors (its own solve entry points serve it)", lu_kind_name(f->kind));
   if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
   if (nrhs < 1 || !b || !x) return fail(MG_ERR_INVALID, "bad argument");
   mg_hierarchy* h = nullptr;
@@ -1286,7 +1300,7 @@ int mg_lu_solve_FP64(mg_lu* f, const double* b, double* x, long long n, long lon
 // device-resident form: b_dev, x_dev row-major [n][nrhs] in HBM
 int mg_lu_solve_dev_FP64(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose) {
   if (!f) return fail(MG_ERR_INVALID, "null factor handle");
-  if (f->cx) return fail(MG_ERR_STATE, "mg_lu_solve_dev_FP64 on a handle of ComplexF64 factors (mg_lu_solve_dev_CFP64)");
+  if (f->kind != 0) return fail(MG_ERR_STATE, "mg_lu_solve_dev_FP64 on a handle of %s factors (its own solve entry points serve it)", lu_kind_name(f->kind));
   if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
   if (nrhs < 1 || !b_dev || !x_dev) return fail(MG_ERR_INVALID, "bad argument");
   mg_hierarchy* h = nullptr;
@@ -1297,66 +1311,164 @@ int mg_lu_solve_dev_FP64(mg_lu* f, const double* b_dev, double* x_dev, long long
 
 // ComplexF64 factors (applyLUsolve_CFP64_INT64, parLU.cpp:69-72): values, b and x interleaved (re, im).  doTranspose solves
 // with the ADJOINT, x[p] = L^H \ (U^H \ b[q]) (Julia's A'), from conjugate-transposed factors built on first use.
-int mg_lu_create_CFP64_INT64(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const double* Lval,
-                             const long long* Uptr, const long long* Ucol, const double* Uval, const long long* p,
-                             const long long* q, mg_lu** out) {
+// Single factors (applyLUsolve_FP32_UINT32, _CFP32_UINT32, _CFP32_INT64; parLU.cpp): values, b and x in float (complex: interleaved),
+// column indices and permutations in the index type of the name, row pointers Int64 as in every form.  The factors are stored in
+// single and every row is evaluated in double (mg_complex.hpp).  doTranspose: the transposed (complex: adjoint) factors, as above.
+extern "C++" {
+namespace {
+template <typename V, typename IDX>
+int cxlu_create_entry(long long device_id, long long n, const long long* Lptr, const IDX* Lcol, const typename lu_store<V>::scalar* Lval,
+                      const long long* Uptr, const IDX* Ucol, const typename lu_store<V>::scalar* Uval, const IDX* p, const IDX* q, mg_lu** out) {
   if (!out) return fail(MG_ERR_INVALID, "out is null");
   *out = nullptr;
   if (n < 1 || !Lptr || !Lcol || !Lval || !Uptr || !Ucol || !Uval || !p || !q) return fail(MG_ERR_INVALID, "null or empty factor");
   if (Lptr[0] != 1 || Uptr[0] != 1 || Lptr[n] < 1 || Uptr[n] < 1) return fail(MG_ERR_INVALID, "row pointers must be 1-based");
-  CxLu* S = nullptr;
-  MG_TRY(cxlu_create(device_id, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, &S));
+  if (n >= (1LL << 31) - 1 || Lptr[n] - 1 >= (1LL << 31) || Uptr[n] - 1 >= (1LL << 31))   // (ahead of the copies below)
+    return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
+  // the applier takes Int64 indices: UInt32 ones are widened here, once
+  std::vector<long long> lc, uc, pp, qq;
+  const long long *Lc, *Uc, *P, *Q;
+  if constexpr (std::is_same<IDX, long long>::value) {
+    Lc = Lcol; Uc = Ucol; P = p; Q = q;
+  } else {
+    lc.assign(Lcol, Lcol + (Lptr[n] - 1)); uc.assign(Ucol, Ucol + (Uptr[n] - 1));
+    pp.assign(p, p + n); qq.assign(q, q + n);
+    Lc = lc.data(); Uc = uc.data(); P = pp.data(); Q = qq.data();
+  }
+  CxLuT<V>* S = nullptr;
+  MG_TRY(cxlu_create<V>(device_id, n, Lptr, Lc, Lval, Uptr, Uc, Uval, P, Q, &S));
   mg_lu* f = new mg_lu();
   f->device = (int)device_id;
   f->n = n;
-  f->cx = S;
+  f->kind = lu_store<V>::kind;
+  mg_lu_slot<V>(f) = S;
   *out = f;
   return MG_OK;
 }
+}  // namespace
+}  // extern "C++"
 
+int mg_lu_create_CFP64_INT64(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const double* Lval,
+                             const long long* Uptr, const long long* Ucol, const double* Uval, const long long* p,
+                             const long long* q, mg_lu** out) {
+  return cxlu_create_entry<cx_t, long long>(device_id, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, out);
+}
+int mg_lu_create_FP32_UINT32(long long device_id, long long n, const long long* Lptr, const unsigned int* Lcol, const float* Lval,
+                             const long long* Uptr, const unsigned int* Ucol, const float* Uval, const unsigned int* p,
+                             const unsigned int* q, mg_lu** out) {
+  return cxlu_create_entry<float, unsigned int>(device_id, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, out);
+}
+int mg_lu_create_CFP32_UINT32(long long device_id, long long n, const long long* Lptr, const unsigned int* Lcol, const float* Lval,
+                              const long long* Uptr, const unsigned int* Ucol, const float* Uval, const unsigned int* p,
+                              const unsigned int* q, mg_lu** out) {
+  return cxlu_create_entry<cf_t, unsigned int>(device_id, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, out);
+}
+int mg_lu_create_CFP32_INT64(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const float* Lval,
+                             const long long* Uptr, const long long* Ucol, const float* Uval, const long long* p,
+                             const long long* q, mg_lu** out) {
+  return cxlu_create_entry<cf_t, long long>(device_id, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, out);
+}
+
+extern "C++" {
 namespace {
-int cxlu_entry(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose, bool host, const char* name) {
+const char* lu_kind_create(int kind) {
+  return kind == 1 ? "mg_lu_create_CFP64_INT64" : kind == 2 ? "mg_lu_create_FP32_UINT32" : "mg_lu_create_CFP32_UINT32 / _INT64";
+}
+template <typename V>
+int cxlu_entry(mg_lu* f, const typename lu_store<V>::scalar* b, typename lu_store<V>::scalar* x, long long n, long long nrhs,
+               long long doTranspose, bool host, const char* name) {
   if (!f) return fail(MG_ERR_INVALID, "null factor handle");
-  if (!f->cx) return fail(MG_ERR_STATE, "%s on a handle of Float64 factors (create it with mg_lu_create_CFP64_INT64)", name);
+  if (f->kind != lu_store<V>::kind)
+    return fail(MG_ERR_STATE, "%s on a handle of %s factors (create it with %s)", name, lu_kind_name(f->kind), lu_kind_create(lu_store<V>::kind));
   if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
   if (nrhs < 1 || !b || !x) return fail(MG_ERR_INVALID, "bad argument");
   if (n * nrhs >= (1LL << 31)) return fail(MG_ERR_UNSUPPORTED, "n*nrhs=%lld exceeds int32 device indices", n * nrhs);
-  CxLu* S = f->cx;
+  CxLuT<V>* S = mg_lu_slot<V>(f);
   (void)hipSetDevice(S->device);
-  CxLuSet* G = nullptr;
+  CxLuSetT<V>* G = nullptr;
   MG_TRY(cxlu_set(S, doTranspose != 0, &G));
   if (host) return cxlu_solve_host(S, *G, b, x, (int)nrhs);
-  MG_TRY(cxlu_solve_dev(S, *G, reinterpret_cast<const cx_t*>(b), reinterpret_cast<cx_t*>(x), (int)nrhs));
+  MG_TRY(cxlu_solve_dev<V>(S, *G, reinterpret_cast<const V*>(b), reinterpret_cast<V*>(x), (int)nrhs));
   HIP_TRY(spin_sync(S->stream));
   return MG_OK;
 }
 }  // namespace
+}  // extern "C++"
 
 // b, x: host, n x nrhs column-major ComplexF64; b is NOT used as work space
 int mg_lu_solve_CFP64(mg_lu* f, const double* b, double* x, long long n, long long nrhs, long long doTranspose) {
-  return cxlu_entry(f, b, x, n, nrhs, doTranspose, true, "mg_lu_solve_CFP64");
+  return cxlu_entry<cx_t>(f, b, x, n, nrhs, doTranspose, true, "mg_lu_solve_CFP64");
 }
 
 // device-resident form: b_dev, x_dev row-major [n][nrhs] ComplexF64 in HBM
 int mg_lu_solve_dev_CFP64(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose) {
-  return cxlu_entry(f, b_dev, x_dev, n, nrhs, doTranspose, false, "mg_lu_solve_dev_CFP64");
+  return cxlu_entry<cx_t>(f, b_dev, x_dev, n, nrhs, doTranspose, false, "mg_lu_solve_dev_CFP64");
 }
 
-// The form a handle's factors are applied in (either value type): info[0] value type (0 Float64, 1 ComplexF64), [1] 1 for
-// the chip-wide form, [2] order of the dense trailing block, [3] / [4] launched levels of L / U around it, [5] / [6] all
-// dependency levels of L / U.  doTranspose selects the transposed (adjoint) set, which is built if it was not yet.
+// the same pairs for Float32 and ComplexF32 handles
+int mg_lu_solve_FP32(mg_lu* f, const float* b, float* x, long long n, long long nrhs, long long doTranspose) {
+  return cxlu_entry<float>(f, b, x, n, nrhs, doTranspose, true, "mg_lu_solve_FP32");
+}
+int mg_lu_solve_dev_FP32(mg_lu* f, const float* b_dev, float* x_dev, long long n, long long nrhs, long long doTranspose) {
+  return cxlu_entry<float>(f, b_dev, x_dev, n, nrhs, doTranspose, false, "mg_lu_solve_dev_FP32");
+}
+int mg_lu_solve_CFP32(mg_lu* f, const float* b, float* x, long long n, long long nrhs, long long doTranspose) {
+  return cxlu_entry<cf_t>(f, b, x, n, nrhs, doTranspose, true, "mg_lu_solve_CFP32");
+}
+int mg_lu_solve_dev_CFP32(mg_lu* f, const float* b_dev, float* x_dev, long long n, long long nrhs, long long doTranspose) {
+  return cxlu_entry<cf_t>(f, b_dev, x_dev, n, nrhs, doTranspose, false, "mg_lu_solve_dev_CFP32");
+}
+
+extern "C++" {
+namespace {
+// the three applier kinds behind one call: fn(S) with S the handle's CxLuT<V>*
+template <typename FN>
+int lu_with_applier(mg_lu* f, FN&& fn) {
+  return f->kind == 1 ? fn(f->cx) : f->kind == 2 ? fn(f->sf) : fn(f->cf);
+}
+template <typename V>
+int cxlu_form(CxLuT<V>* S, long long doTranspose, long long* info) {
+  (void)hipSetDevice(S->device);
+  CxLuSetT<V>* G = nullptr;
+  MG_TRY(cxlu_set(S, doTranspose != 0, &G));
+  info[0] = lu_store<V>::kind; info[1] = G->multi ? 1 : 0; info[2] = G->M;
+  info[3] = G->multi ? (long long)G->Llvl_h.size() - 1 : G->nLlvl;
+  info[4] = G->multi ? (long long)G->Ulvl_h.size() - 1 : G->nUlvl;
+  info[5] = G->nLlvl; info[6] = G->nUlvl;
+  return MG_OK;
+}
+// mg_lu_time_dev on an applier handle: the samples of `warmup + reps` solves on its own stream
+template <typename V>
+int cxlu_time_dev(CxLuT<V>* S, const void* b_dev, void* x_dev, long long nrhs, long long doTranspose, long long warmup, long long reps,
+                  double* ms) {
+  CxLuSetT<V>* G = nullptr;
+  MG_TRY(cxlu_set(S, doTranspose != 0, &G));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int rc = MG_OK;
+  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventCreate failed");
+  for (long long it = 0; it < warmup + reps && rc == MG_OK; ++it) {
+    if (hipEventRecord(e0, S->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
+    if (rc == MG_OK) rc = cxlu_solve_dev<V>(S, *G, static_cast<const V*>(b_dev), static_cast<V*>(x_dev), (int)nrhs);
+    if (rc == MG_OK) {
+      float t = 0.f;
+      if (hipEventRecord(e1, S->stream) != hipSuccess || spin_sync(S->stream) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)
+        rc = fail(MG_ERR_HIP, "event timing failed");
+      if (it >= warmup) ms[it - warmup] = (double)t;
+    }
+  }
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+// The form a handle's factors are applied in (any value type): info[0] value type (0 Float64, 1 ComplexF64, 2 Float32,
+// 3 ComplexF32), [1] 1 for the chip-wide form, [2] order of the dense trailing block, [3] / [4] launched levels of L / U around it,
+// [5] / [6] all dependency levels of L / U.  doTranspose selects the transposed (adjoint) set, which is built if it was not yet.
 int mg_lu_form(mg_lu* f, long long doTranspose, long long* info) {
   if (!f || !info) return fail(MG_ERR_INVALID, "null argument");
-  if (f->cx) {
-    (void)hipSetDevice(f->cx->device);
-    CxLuSet* G = nullptr;
-    MG_TRY(cxlu_set(f->cx, doTranspose != 0, &G));
-    info[0] = 1; info[1] = G->multi ? 1 : 0; info[2] = G->M;
-    info[3] = G->multi ? (long long)G->Llvl_h.size() - 1 : G->nLlvl;
-    info[4] = G->multi ? (long long)G->Ulvl_h.size() - 1 : G->nUlvl;
-    info[5] = G->nLlvl; info[6] = G->nUlvl;
-    return MG_OK;
-  }
+  if (f->kind != 0) return lu_with_applier(f, [&](auto* S) { return cxlu_form(S, doTranspose, info); });
   mg_hierarchy* h = nullptr;
   MG_TRY(lu_hierarchy(f, doTranspose != 0, &h));
   info[0] = 0; info[1] = h->lu_multi ? 1 : 0; info[2] = h->luML;
@@ -1366,36 +1478,30 @@ int mg_lu_form(mg_lu* f, long long doTranspose, long long* info) {
   return MG_OK;
 }
 
-// Device time of one solve on device vectors (either value type; row-major [n][nrhs]): `warmup` untimed solves, then `reps`
-// solves, each enqueued between two events on the handle's stream (the second is recorded BEFORE the host waits, so a sample
-// is stream time - kernels and the gaps between their launches - without the host's wake-up); ms[0..reps) in milliseconds.
+// Device time of one solve on device vectors (any value type - b_dev, x_dev hold the handle's; row-major [n][nrhs]): `warmup` untimed
+// solves, then `reps` solves, each enqueued between two events on the handle's stream (the second is recorded BEFORE the host waits, so
+// a sample is stream time - kernels and the gaps between their launches - without the host's wake-up); ms[0..reps) in milliseconds.
 // The factor set of the direction is built before the first sample, whatever `warmup` is.
 int mg_lu_time_dev(mg_lu* f, const double* b_dev, double* x_dev, long long n, long long nrhs, long long doTranspose,
                    long long warmup, long long reps, double* ms) {
   if (!f || !ms || !b_dev || !x_dev || reps < 1 || warmup < 0 || nrhs < 1) return fail(MG_ERR_INVALID, "bad argument");
   if (n != f->n) return fail(MG_ERR_INVALID, "n=%lld but the factors have order %lld", n, f->n);
   (void)hipSetDevice(f->device);
-  hipStream_t stream;
-  mg_hierarchy* h = nullptr;
-  CxLuSet* G = nullptr;
-  if (f->cx) {
+  if (f->kind != 0) {
     if (n * nrhs >= (1LL << 31)) return fail(MG_ERR_UNSUPPORTED, "n*nrhs=%lld exceeds int32 device indices", n * nrhs);
-    MG_TRY(cxlu_set(f->cx, doTranspose != 0, &G));
-    stream = f->cx->stream;
-  } else {
-    MG_TRY(lu_hierarchy(f, doTranspose != 0, &h));
-    MG_TRY(mg_set_nrhs(h, nrhs));
-    MG_TRY(check_ready(h, n, nrhs));
-    stream = h->play->stream;
+    return lu_with_applier(f, [&](auto* S) { return cxlu_time_dev(S, b_dev, x_dev, nrhs, doTranspose, warmup, reps, ms); });
   }
+  mg_hierarchy* h = nullptr;
+  MG_TRY(lu_hierarchy(f, doTranspose != 0, &h));
+  MG_TRY(mg_set_nrhs(h, nrhs));
+  MG_TRY(check_ready(h, n, nrhs));
+  const hipStream_t stream = h->play->stream;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = MG_OK;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventCreate failed");
   for (long long it = 0; it < warmup + reps && rc == MG_OK; ++it) {
     if (hipEventRecord(e0, stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipEventRecord failed");
-    if (rc == MG_OK)
-      rc = f->cx ? cxlu_solve_dev(f->cx, *G, reinterpret_cast<const cx_t*>(b_dev), reinterpret_cast<cx_t*>(x_dev), (int)nrhs)
-                 : cycle_dev(h, b_dev, x_dev, true);
+    if (rc == MG_OK) rc = cycle_dev(h, b_dev, x_dev, true);
     if (rc == MG_OK) {
       float t = 0.f;
       if (hipEventRecord(e1, stream) != hipSuccess || spin_sync(stream) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)
@@ -1405,13 +1511,15 @@ int mg_lu_time_dev(mg_lu* f, const double* b_dev, double* x_dev, long long n, lo
   }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (h) prof_collect(h);
+  prof_collect(h);
   return rc;
 }
 
 int mg_lu_destroy(mg_lu* f) {
   if (!f) return MG_OK;
   if (f->cx) cxlu_destroy(f->cx);
+  if (f->cf) cxlu_destroy(f->cf);
+  if (f->sf) cxlu_destroy(f->sf);
   if (f->fwd) mg_destroy(f->fwd);
   if (f->trans) mg_destroy(f->trans);
   delete f;

@@ -34,7 +34,7 @@ constexpr int CX_CHUNK = BLK * CX_ITEMS;    // 1024 products: 16 KiB of LDS per 
 // A ComplexF32 (CF32) hierarchy runs the same kernels on (re, im) float pairs: every kernel of the cycle below is written once
 // over the pair type C (d2_t or f2_t) with its scalar cx_scalar<C>.  Products and row sums are formed in C's precision, in stored
 // order (the reference's arithmetic for VAL = ComplexF32); the partials of ||r||^2 are double for both.
-typedef float f2_t __attribute__((ext_vector_type(2)));
+// (f2_t: mg_kernels.hpp, beside d2_t)
 template <typename C> struct cx_scalar;
 template <> struct cx_scalar<d2_t> { typedef double type; };
 template <> struct cx_scalar<f2_t> { typedef float type; };
@@ -1102,51 +1102,57 @@ __global__ __launch_bounds__(64) void hybrid_kaczmarz_c(const int* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Chip-wide sparse triangular solve on complex factors (mg_lu_*_CFP64): the complex form of sptrsv_level /
+// Chip-wide sparse triangular solve of the factor applier (mg_lu_*_CFP64 / _CFP32 / _FP32): the form of sptrsv_level /
 // sptrsv_tail_rhs / sptrsv_scatter / tri_gather_block / tri_inverse / tri_apply (mg_kernels.hpp), same layout and
 // scheduling - one wavefront per row, one launch per wide level, up to 4 right-hand-side columns travelling together,
 // the trailing chain of single-row levels replaced by the explicit inverse of its dense block, vectors row-major
-// [n][nrhs], no inter-workgroup waiting.  A row moves 20 bytes per entry (16 value + 4 index) against 12 for real
-// factors; a lane's gather of y is 16*nc contiguous bytes.  The adjoint solve needs no kernel of its own: the host
-// uploads the conjugate-transposed factors as a second resident set.
+// [n][nrhs], no inter-workgroup waiting.  Written once over the STORED value type S: d2_t (ComplexF64), f2_t (ComplexF32)
+// or float, with the accumulation type lu_acc<S> of the single-workgroup sweep (mg_kernels.hpp): a single factor value and
+// the gathered y are widened on load, the lane sums, the shuffles, the subtraction and the division are double, the result is
+// rounded once on its store.  A row moves 20 / 12 / 8 bytes per entry (value + 4-byte index); a lane's gather of y is
+// sizeof(S)*nc contiguous bytes.  The adjoint solve needs no kernel of its own: the host uploads the conjugate-transposed
+// factors as a second resident set.
 // ------------------------------------------------------------------------------------------------
 typedef LuDevT<d2_t> CxLuDev;
 
-template <bool LOWER>
-__global__ __launch_bounds__(BLK) void cx_sptrsv_level(CxLuDev F, const int4* __restrict__ slots, int t0, int t1,
-                                                       const d2_t* __restrict__ b, d2_t* y, int nrhs) {
+template <bool LOWER, typename S>
+__global__ __launch_bounds__(BLK) void cx_sptrsv_level(LuDevT<S> F, const int4* __restrict__ slots, int t0, int t1,
+                                                       const S* __restrict__ b, S* y, int nrhs) {
+  typedef typename lu_acc<S>::type A;
   const int t = t0 + (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
   const int lane = threadIdx.x & 63;
   if (t >= t1) return;  // wave-uniform
   const int* __restrict__ col = LOWER ? F.Lcol : F.Ucol;
-  const d2_t* __restrict__ val = LOWER ? F.Lval : F.Uval;
+  const S* __restrict__ val = LOWER ? F.Lval : F.Uval;
   const int4 sl = slots[t];                       // (row, first and end of the off-diagonal entries, the diagonal entry)
   const int row = sl.x, s = sl.y, e = sl.z;
-  const d2_t dg = val[sl.w];
+  const A dg = lu_wide(val[sl.w]);
   for (int c0 = 0; c0 < nrhs; c0 += 4) {
     const int nc = min(4, nrhs - c0);
-    d2_t acc[4] = {d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}};
+    A acc[4] = {A{}, A{}, A{}, A{}};
     for (int k = s + lane; k < e; k += 64) {
-      const d2_t v = val[k];
-      const d2_t* yy = y + (size_t)col[k] * nrhs + c0;
+      const A v = lu_wide(val[k]);
+      const S* yy = y + (size_t)col[k] * nrhs + c0;
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        if (u < nc) acc[u] += cmul(v, yy[u]);
+        if (u < nc) acc[u] += lu_mul(v, lu_wide(yy[u]));
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
-      for (int o = 32; o > 0; o >>= 1) acc[u] += shfl_xor_v(acc[u], o);
+      for (int o = 32; o > 0; o >>= 1) acc[u] += lu_shfl_xor(acc[u], o);
     if (lane < nc) {
-      const d2_t rhs = LOWER ? b[(size_t)F.p[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
-      const d2_t a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-      y[(size_t)row * nrhs + c0 + lane] = cdiv(rhs - a, dg);
+      const A rhs = lu_wide(LOWER ? b[(size_t)F.p[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane]);
+      const A a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+      y[(size_t)row * nrhs + c0 + lane] = lu_round<S>(lu_div(rhs - a, dg));
     }
   }
 }
 
 // t = b[p] - L21*y1 for the rows n0.. of the trailing block of L
-__global__ __launch_bounds__(BLK) void cx_sptrsv_tail_rhs(CxLuDev F, int n0, const d2_t* __restrict__ b,
-                                                          const d2_t* __restrict__ y, d2_t* __restrict__ t, int nrhs) {
+template <typename S>
+__global__ __launch_bounds__(BLK) void cx_sptrsv_tail_rhs(LuDevT<S> F, int n0, const S* __restrict__ b,
+                                                          const S* __restrict__ y, S* __restrict__ t, int nrhs) {
+  typedef typename lu_acc<S>::type A;
   const int i = (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
   const int lane = threadIdx.x & 63;
   const int row = n0 + i;
@@ -1154,29 +1160,30 @@ __global__ __launch_bounds__(BLK) void cx_sptrsv_tail_rhs(CxLuDev F, int n0, con
   const int s = F.Lptr[row], e = F.Lptr[row + 1] - 1;
   for (int c0 = 0; c0 < nrhs; c0 += 4) {
     const int nc = min(4, nrhs - c0);
-    d2_t acc[4] = {d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}, d2_t{0.0, 0.0}};
+    A acc[4] = {A{}, A{}, A{}, A{}};
     for (int k = s + lane; k < e; k += 64) {
       const int c = F.Lcol[k];
       if (c >= n0) continue;                       // the trailing block itself is applied through its inverse
-      const d2_t v = F.Lval[k];
-      const d2_t* yy = y + (size_t)c * nrhs + c0;
+      const A v = lu_wide(F.Lval[k]);
+      const S* yy = y + (size_t)c * nrhs + c0;
 #pragma unroll
       for (int u = 0; u < 4; ++u)
-        if (u < nc) acc[u] += cmul(v, yy[u]);
+        if (u < nc) acc[u] += lu_mul(v, lu_wide(yy[u]));
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
-      for (int o = 32; o > 0; o >>= 1) acc[u] += shfl_xor_v(acc[u], o);
+      for (int o = 32; o > 0; o >>= 1) acc[u] += lu_shfl_xor(acc[u], o);
     if (lane < nc) {
-      const d2_t a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-      t[(size_t)i * nrhs + c0 + lane] = b[(size_t)F.p[row] * nrhs + c0 + lane] - a;
+      const A a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+      t[(size_t)i * nrhs + c0 + lane] = lu_round<S>(lu_wide(b[(size_t)F.p[row] * nrhs + c0 + lane]) - a);
     }
   }
 }
 
 // x[q[r]] = y[r]
-__global__ __launch_bounds__(BLK) void cx_sptrsv_scatter(const int* __restrict__ q, const d2_t* __restrict__ y,
-                                                         d2_t* __restrict__ x, int n, int nrhs) {
+template <typename S>
+__global__ __launch_bounds__(BLK) void cx_sptrsv_scatter(const int* __restrict__ q, const S* __restrict__ y,
+                                                         S* __restrict__ x, int n, int nrhs) {
   const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
   if (i >= (long long)n * nrhs) return;
   const int r = (int)(i / nrhs), u = (int)(i - (long long)r * nrhs);
@@ -1184,9 +1191,14 @@ __global__ __launch_bounds__(BLK) void cx_sptrsv_scatter(const int* __restrict__
 }
 
 // Dense block (row-major, leading dimension ld = M rounded up to 64, zero outside the triangle, unit diagonal in the
-// padding) of the rows/columns n0.. of a complex factor in CSR; D was zeroed by the host.
+// padding) of the rows/columns n0.. of a factor in CSR, widened to ComplexF64 whatever S is (a real value gets a zero
+// imaginary part: the block is inverted by the one complex kernel below); D was zeroed by the host.
+__device__ __forceinline__ d2_t tri_wide(d2_t a) { return a; }
+__device__ __forceinline__ d2_t tri_wide(f2_t a) { return d2_t{(double)a.x, (double)a.y}; }
+__device__ __forceinline__ d2_t tri_wide(float a) { return d2_t{(double)a, 0.0}; }
+template <typename S>
 __global__ __launch_bounds__(BLK) void cx_tri_gather_block(const int* __restrict__ ptr, const int* __restrict__ col,
-                                                           const d2_t* __restrict__ val, int n0, int M, int ld,
+                                                           const S* __restrict__ val, int n0, int M, int ld,
                                                            d2_t* __restrict__ D) {
   const int i = (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
   const int lane = threadIdx.x & 63;
@@ -1197,8 +1209,17 @@ __global__ __launch_bounds__(BLK) void cx_tri_gather_block(const int* __restrict
   }
   for (int k = ptr[n0 + i] + lane; k < ptr[n0 + i + 1]; k += 64) {
     const int c = col[k] - n0;
-    if (c >= 0) D[(size_t)i * ld + c] = val[k];
+    if (c >= 0) D[(size_t)i * ld + c] = tri_wide(val[k]);
   }
+}
+
+// the ComplexF64 inverse of a single factor's trailing block rounded into its stored type (once, at setup)
+__device__ __forceinline__ void tri_narrow(d2_t a, f2_t* o) { *o = f2_t{(float)a.x, (float)a.y}; }
+__device__ __forceinline__ void tri_narrow(d2_t a, float* o) { *o = (float)a.x; }
+template <typename S>
+__global__ __launch_bounds__(BLK) void cx_tri_store(const d2_t* __restrict__ X, S* __restrict__ T, long long len) {
+  const long long i = (long long)blockIdx.x * BLK + threadIdx.x;
+  if (i < len) tri_narrow(X[i], T + i);
 }
 
 // X = inv(D) for a dense complex triangular block (ld x ld, ld a multiple of 64): tri_inverse with 32 x 32 blocks
@@ -1285,25 +1306,27 @@ __global__ __launch_bounds__(256) void cx_tri_inverse(const d2_t* __restrict__ D
   }
 }
 
-// x = T * b for a dense complex TRIANGULAR M x M block (row-major, leading dimension ld): one wavefront per (row, column)
-template <bool LOWER>
-__global__ __launch_bounds__(BLK) void cx_tri_apply(const d2_t* __restrict__ T, int ld, const d2_t* __restrict__ b,
-                                                    d2_t* __restrict__ x, int M, int nrhs) {
+// x = T * b for a dense TRIANGULAR M x M block stored in S (row-major, leading dimension ld): one wavefront per (row, column),
+// the sum in lu_acc<S>, rounded once
+template <bool LOWER, typename S>
+__global__ __launch_bounds__(BLK) void cx_tri_apply(const S* __restrict__ T, int ld, const S* __restrict__ b,
+                                                    S* __restrict__ x, int M, int nrhs) {
+  typedef typename lu_acc<S>::type A;
   const int wave = (int)(((long long)blockIdx.x * BLK + threadIdx.x) >> 6);
   const int lane = threadIdx.x & 63;
   if (wave >= M * nrhs) return;  // wave-uniform
   const int row = wave / nrhs, c = wave - row * nrhs;
-  const d2_t* __restrict__ a = T + (size_t)row * ld;
+  const S* __restrict__ a = T + (size_t)row * ld;
   const int j0 = LOWER ? 0 : (row & ~63), j1 = LOWER ? row + 1 : M;
-  d2_t acc = d2_t{0.0, 0.0};
-  for (int j = j0 + lane; j < j1; j += 64) acc += cmul(a[j], b[(size_t)j * nrhs + c]);
-  for (int o = 32; o > 0; o >>= 1) acc += shfl_xor_v(acc, o);
-  if (lane == 0) x[(size_t)row * nrhs + c] = acc;
+  A acc = A{};
+  for (int j = j0 + lane; j < j1; j += 64) acc += lu_mul(lu_wide(a[j]), lu_wide(b[(size_t)j * nrhs + c]));
+  for (int o = 32; o > 0; o >>= 1) acc += lu_shfl_xor(acc, o);
+  if (lane == 0) x[(size_t)row * nrhs + c] = lu_round<S>(acc);
 }
 
-// column-major n x nrhs (the host's layout) <-> row-major [n][nrhs] (the device's), complex entries
-template <bool TO_ROWMAJOR>
-__global__ __launch_bounds__(BLK) void cx_relayout(const d2_t* __restrict__ src, d2_t* __restrict__ dst, long long n, int nrhs) {
+// column-major n x nrhs (the host's layout) <-> row-major [n][nrhs] (the device's), entries of any value type
+template <bool TO_ROWMAJOR, typename S>
+__global__ __launch_bounds__(BLK) void cx_relayout(const S* __restrict__ src, S* __restrict__ dst, long long n, int nrhs) {
   const long long i = (long long)blockIdx.x * BLK + threadIdx.x;   // index into the row-major array
   if (i >= n * nrhs) return;
   const long long r = i / nrhs, c = i - r * nrhs;

@@ -17,8 +17,8 @@
 // and in mg_complex_krylov.inc cx_krylov and cx_cycle_dev.
 // adjointHierarchy on the resident hierarchy (mg_adjoint_hierarchy_CF64 / _CF32; cx_adjoint_hierarchy): every operator replaced by its
 // conjugate transpose in HBM, for both precisions.
-// Also here: the stand-alone ComplexF64 factor applier behind mg_lu_*_CFP64 (CxLu; its extern "C" entry points sit beside the
-// real applier's in mg_cabi.inc).
+// Also here: the stand-alone factor applier behind mg_lu_*_CFP64 / _CFP32 / _FP32 (CxLuT<S>, written once over the stored value
+// type; its extern "C" entry points sit beside the real applier's in mg_cabi.inc).
 //
 // Reference behaviour reproduced for VAL = ComplexF64:
 //   recursiveCycle  src/Multigrid/MGcycle.jl:1-118, relax l.122-136, solveCoarsest l.177
@@ -29,6 +29,42 @@ typedef mgk::f2_t cf_t;   // the pair type of a ComplexF32 (CF32) handle: the sa
 
 // (the state types live beside mg_hierarchy, outside the anonymous namespace: the handle holds a CxState*)
 // one operator of a CF64 hierarchy, generic CSR: complex values (A = AT^H) or real values (P, R)
+// ---- stand-alone factor applier (mg_lu_*_CFP64 / _CFP32 / _FP32): state of its own, apart from the CF64 hierarchies ----
+// Written once over the stored value type S of the kernels (mg_complex.hpp): cx_t (ComplexF64), cf_t (ComplexF32) or float.
+// lu_store<S>: the host scalar the caller's values come in and how many of them make one value.
+template <typename S> struct lu_store;
+template <> struct lu_store<cx_t> { typedef double scalar; static constexpr int comps = 2; static constexpr int kind = 1; };
+template <> struct lu_store<float> { typedef float scalar; static constexpr int comps = 1; static constexpr int kind = 2; };
+template <> struct lu_store<cf_t> { typedef float scalar; static constexpr int comps = 2; static constexpr int kind = 3; };
+// one resident set of factors: the plain ones (x[q] = U \ (L \ b[p])) or the conjugate-transposed ones of the adjoint solve
+template <typename S>
+struct CxLuSetT {
+  DevBuf<int> Lptr, Lcol, Uptr, Ucol, P, Q, Lorder, Llvl, Uorder, Ulvl, Lslot, Uslot;
+  DevBuf<S> Lval, Uval, invL, invU;
+  int nLlvl = 0, nUlvl = 0;                // dependency levels of the whole factors (single-workgroup form)
+  bool multi = false;                      // chip-wide form: per-level launches + dense trailing inverse
+  int M = 0;                               // order of the trailing block held as an explicit inverse
+  std::vector<int> Llvl_h, Ulvl_h;         // host copies of the level pointers ahead of / behind the trailing block
+  ~CxLuSetT() {
+    for (DevBuf<int>* d : {&Lptr, &Lcol, &Uptr, &Ucol, &P, &Q, &Lorder, &Llvl, &Uorder, &Ulvl, &Lslot, &Uslot}) d->release();
+    for (DevBuf<S>* d : {&Lval, &Uval, &invL, &invU}) d->release();
+  }
+};
+template <typename S>
+struct CxLuT {
+  int device = 0;
+  long long n = 0;
+  Options opt;
+  hipStream_t stream = nullptr;
+  std::vector<long long> Lptr, Lcol, Uptr, Ucol, p, q;   // the caller's factors (1-based): the adjoint set is derived from them
+  std::vector<typename lu_store<S>::scalar> Lval, Uval;
+  CxLuSetT<S>* fwd = nullptr;
+  CxLuSetT<S>* adj = nullptr;
+  DevBuf<S> work, tail, stage_b, stage_x, stage_t;
+};
+typedef CxLuSetT<cx_t> CxLuSet;
+typedef CxLuT<cx_t> CxLu;
+
 struct CxMat {
   bool set = false, cplx = false, wide = false;
   bool single = false;          // values in valf (a CF32 handle's operators); val otherwise
@@ -79,7 +115,8 @@ struct CxState {
   bool K_auto = false;         // K is As[1] widened (the system operator of a CF32 handle's drivers when none was set)
   DevBuf<double> cw_b, cw_x;   // CF32: the coarsest right-hand side widened, the coarsest solution before it is narrowed
   bool coarse_set = false, coarse_lu = false;
-  struct CxLu* coarse_multi = nullptr;   // sparse factors of >= lu_multi_min_rows rows: the chip-wide form of the factor applier
+  CxLu* coarse_multi = nullptr;   // sparse factors of >= lu_multi_min_rows rows: the chip-wide form of the factor applier
+  CxLuT<cf_t>* coarse_single = nullptr;   // CF32: ComplexF32 factors applied to the cycle's own bc (mg_set_coarse_lu_CF32_INT64), either form
   long long n_coarse = 0;
   DevBuf<double> Ainv;         // row-major n_c x n_c complex
   DevBuf<int> luLptr, luLcol, luUptr, luUcol, luP, luQ, luLorder, luLlvl, luUorder, luUlvl;
@@ -155,37 +192,16 @@ struct CxState {
   }
 };
 
-// ---- stand-alone complex factor applier (mg_lu_*_CFP64): state of its own, apart from the CF64 hierarchies --------------
-// one resident set of factors: the plain ones (x[q] = U \ (L \ b[p])) or the conjugate-transposed ones of the adjoint solve
-struct CxLuSet {
-  DevBuf<int> Lptr, Lcol, Uptr, Ucol, P, Q, Lorder, Llvl, Uorder, Ulvl, Lslot, Uslot;
-  DevBuf<double> Lval, Uval, invL, invU;   // interleaved (re, im)
-  int nLlvl = 0, nUlvl = 0;                // dependency levels of the whole factors (single-workgroup form)
-  bool multi = false;                      // chip-wide form: per-level launches + dense trailing inverse
-  int M = 0;                               // order of the trailing block held as an explicit inverse
-  std::vector<int> Llvl_h, Ulvl_h;         // host copies of the level pointers ahead of / behind the trailing block
-  ~CxLuSet() {
-    for (DevBuf<int>* d : {&Lptr, &Lcol, &Uptr, &Ucol, &P, &Q, &Lorder, &Llvl, &Uorder, &Ulvl, &Lslot, &Uslot}) d->release();
-    for (DevBuf<double>* d : {&Lval, &Uval, &invL, &invU}) d->release();
-  }
-};
-struct CxLu {
-  int device = 0;
-  long long n = 0;
-  Options opt;
-  hipStream_t stream = nullptr;
-  std::vector<long long> Lptr, Lcol, Uptr, Ucol, p, q;   // the caller's factors (1-based): the adjoint set is derived from them
-  std::vector<double> Lval, Uval;
-  CxLuSet* fwd = nullptr;
-  CxLuSet* adj = nullptr;
-  DevBuf<double> work, tail, stage_b, stage_x, stage_t;
-};
-
 namespace {
 
-void cxlu_destroy(CxLu* S);
+template <typename S> void cxlu_destroy(CxLuT<S>* S_);
+// the factor appliers a hierarchy holds for its coarsest solve, released (another coarsest solve is being set, or the handle goes)
+void cx_drop_coarse_appliers(CxState& S) {
+  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+  if (S.coarse_single) { cxlu_destroy(S.coarse_single); S.coarse_single = nullptr; }
+}
 void cx_destroy(CxState* s) {
-  if (s->coarse_multi) cxlu_destroy(s->coarse_multi);
+  cx_drop_coarse_appliers(*s);
   delete s;
 }
 
@@ -385,7 +401,8 @@ int cx_widen(mg_hierarchy* h, const cf_t* src, cx_t* dst, long long n) {
   return MG_OK;
 }
 
-int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr, const hipStream_t* on);
+template <typename S>
+int cxlu_solve_dev(CxLuT<S>* S_, CxLuSetT<S>& G, const S* b, S* x, int nr, const hipStream_t* on = nullptr);
 
 // ---- coarseSolveType "GMRES" (MGsetup.jl:335-336, MGcycle.jl:152-164) for complex hierarchies -------------------------------------------
 // x .= 0, then ONE restart of KrylovMethods.fgmres(A_c, b, 10, tol = 0.01, maxIter = 1, M = v -> d_c .* v).  The restart is enqueued
@@ -758,6 +775,8 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr
 // deliberate deviation of the order of the single unit roundoff: more accurate, and no float instantiation of the vector passes.
 int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool = true, int nr = 0) {
   CxState& S = *h->cx;
+  // ComplexF32 factors (mg_set_coarse_lu_CF32_INT64): applied to the cycle's own bc, no widened pair
+  if (S.coarse_single) return cxlu_solve_dev(S.coarse_single, *S.coarse_single->fwd, b, x, std::max(nr, 1), &h->play->stream);
   const CxCols W = CxCols::of(nr);
   DevBuf<double>&wb = W.cw_b(S), &wx = W.cw_x(S);
   const long long len = (long long)W.len(S.n_coarse);
@@ -1133,9 +1152,12 @@ int cx_block_ensure(mg_hierarchy* h, int nr) {
   }
   const size_t n0 = 2 * (size_t)S.lev[0].n * k, nc = 2 * (size_t)S.n_coarse * k;
   for (DevBuf<double>* d : {&S.Bstage_b, &S.Bstage_x, &S.Bstage_t}) MG_TRY(d->alloc(n0));
-  if (S.single) {
+  if (S.single && !S.coarse_single) {   // (ComplexF32 factors are applied to the cycle's own block: no widened pair)
     MG_TRY(S.Bcw_b.alloc(nc));
     MG_TRY(S.Bcw_x.alloc(nc));
+  } else {
+    S.Bcw_b.release();
+    S.Bcw_x.release();
   }
   for (int l = 0; l < nl; ++l) {
     CxLevel& L = S.lev[(size_t)l];
@@ -1150,8 +1172,13 @@ int cx_block_ensure(mg_hierarchy* h, int nr) {
   }
   if (S.coarse_multi) {   // (no allocation inside the cycle: the factor applier's work vectors for nr columns)
     CxLu* F = S.coarse_multi;
-    const size_t tlen = 2 * (size_t)std::max(F->fwd->M, 1) * k;
-    if (F->work.n < nc) MG_TRY(F->work.alloc(nc));
+    const size_t wlen = (size_t)S.n_coarse * k, tlen = (size_t)std::max(F->fwd->M, 1) * k;
+    if (F->work.n < wlen) MG_TRY(F->work.alloc(wlen));
+    if (F->tail.n < tlen) MG_TRY(F->tail.alloc(tlen));
+  } else if (S.coarse_single) {
+    CxLuT<cf_t>* F = S.coarse_single;
+    const size_t wlen = (size_t)S.n_coarse * k, tlen = (size_t)std::max(F->fwd->M, 1) * k;
+    if (F->work.n < wlen) MG_TRY(F->work.alloc(wlen));
     if (F->tail.n < tlen) MG_TRY(F->tail.alloc(tlen));
   } else if (S.coarse_lu) {
     MG_TRY(S.BluWork.alloc(nc));
@@ -1279,12 +1306,15 @@ int cx_finalize(mg_hierarchy* h) {
   const size_t n0 = 2 * (size_t)S.lev[0].n;
   if (S.stage_b.n != n0) MG_TRY(S.stage_b.alloc(n0));
   if (S.partial.n < maxblocks) MG_TRY(S.partial.alloc(maxblocks));
-  if (S.single) {
+  if (S.single && !S.coarse_single) {
     const size_t nc = 2 * (size_t)S.n_coarse;
     if (S.cw_b.n != nc) MG_TRY(S.cw_b.alloc(nc));
     if (S.cw_x.n != nc) MG_TRY(S.cw_x.alloc(nc));
+  } else {   // (a CF64 handle, or ComplexF32 factors applied to the cycle's own bc: no widened pair)
+    S.cw_b.release();
+    S.cw_x.release();
   }
-  if (S.coarse_lu && !S.coarse_multi && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
+  if (S.coarse_lu && !S.coarse_multi && !S.coarse_single && S.luWork.n != 2 * (size_t)S.n_coarse) MG_TRY(S.luWork.alloc(2 * (size_t)S.n_coarse));
   // FGMRESmem of the schedule (MGsetup.jl:186-214): memRelax for Jac-GMRES, memKcycle for the K-cycle; dropped when the schedule left them
   const bool gmres_relax = h->relax_type == 1, kcycle = h->cycle == 'K';
   for (int l = 0; l < nl; ++l) {
@@ -1309,22 +1339,25 @@ int cx_finalize(mg_hierarchy* h) {
   return MG_OK;
 }
 
-// ---- the complex factor applier ------------------------------------------------------------------------------------------
-void cxlu_destroy(CxLu* S) {
+// ---- the factor applier, written once over the stored value type V (cx_t, cf_t, float) -------------------------------------
+template <typename V>
+void cxlu_destroy(CxLuT<V>* S) {
   if (!S) return;
   (void)hipSetDevice(S->device);
   if (S->stream) (void)spin_sync(S->stream);
   delete S->fwd;
   delete S->adj;
-  for (DevBuf<double>* d : {&S->work, &S->tail, &S->stage_b, &S->stage_x, &S->stage_t}) d->release();
+  for (DevBuf<V>* d : {&S->work, &S->tail, &S->stage_b, &S->stage_x, &S->stage_t}) d->release();
   if (S->stream) (void)hipStreamDestroy(S->stream);
   delete S;
 }
 
 // Validate and upload one set of factors in parLU's layout (the checks and the form selection of
-// mg_set_coarse_lu_FP64_INT64, 16 bytes per value in the traffic term of the trailing block's estimate).
-int cxlu_upload(CxLu* S, CxLuSet* F, const long long* Lptr, const long long* Lcol, const double* Lval, const long long* Uptr,
-                const long long* Ucol, const double* Uval, const long long* p, const long long* q, const char* what) {
+// mg_set_coarse_lu_FP64_INT64, sizeof(V) bytes per value in the traffic term of the trailing block's estimate).
+template <typename V>
+int cxlu_upload(CxLuT<V>* S, CxLuSetT<V>* F, const long long* Lptr, const long long* Lcol, const typename lu_store<V>::scalar* Lval,
+                const long long* Uptr, const long long* Ucol, const typename lu_store<V>::scalar* Uval, const long long* p,
+                const long long* q, const char* what) {
   const long long n = S->n;
   const size_t N = (size_t)n;
   std::vector<int> LP, LC, LO, LL, UP, UC, UO, UL, pp(N), qq(N);
@@ -1343,17 +1376,17 @@ int cxlu_upload(CxLu* S, CxLuSet* F, const long long* Lptr, const long long* Lco
   MG_TRY(up_i(F->Lptr, LP)); MG_TRY(up_i(F->Lcol, LC)); MG_TRY(up_i(F->Lorder, LO)); MG_TRY(up_i(F->Llvl, LL));
   MG_TRY(up_i(F->Uptr, UP)); MG_TRY(up_i(F->Ucol, UC)); MG_TRY(up_i(F->Uorder, UO)); MG_TRY(up_i(F->Ulvl, UL));
   MG_TRY(up_i(F->P, pp)); MG_TRY(up_i(F->Q, qq));
-  MG_TRY(F->Lval.alloc(2 * LC.size()));
-  MG_TRY(F->Uval.alloc(2 * UC.size()));
-  HIP_TRY(hipMemcpy(F->Lval.p, Lval, 2 * LC.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(F->Uval.p, Uval, 2 * UC.size() * sizeof(double), hipMemcpyHostToDevice));
+  MG_TRY(F->Lval.alloc(LC.size()));
+  MG_TRY(F->Uval.alloc(UC.size()));
+  HIP_TRY(hipMemcpy(F->Lval.p, Lval, LC.size() * sizeof(V), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(F->Uval.p, Uval, UC.size() * sizeof(V), hipMemcpyHostToDevice));
   F->nLlvl = (int)LL.size() - 1;
   F->nUlvl = (int)UL.size() - 1;
   F->multi = n >= S->opt.lu_multi_min_rows;
   F->M = 0;
   if (!F->multi) return MG_OK;
   // Size M of the trailing block: a level costs ~8 us of dependent latency whatever its width, the dense product
-  // 16*M^2/2 bytes of traffic per factor - the candidate with the smallest estimate
+  // sizeof(V)*M^2/2 bytes of traffic per factor - the candidate with the smallest estimate
   // (the estimate, the slots and the inversion sequence of mg_set_coarse_lu_FP64_INT64, mg_cabi.inc: keep the two in step)
   const int cap = (int)std::min<long long>(S->opt.lu_dense_tail_max, n);
   int M = 0;
@@ -1363,7 +1396,7 @@ int cxlu_upload(CxLu* S, CxLuSet* F, const long long* Lptr, const long long* Lco
     lu_levels(n, LP, LC, true, cand, o, lp);
     double est = 8e-6 * (double)(lp.size() - 1);
     lu_levels(n, UP, UC, false, cand, o, lp);
-    est += 8e-6 * (double)(lp.size() - 1) + 2.0 * 8.0 * (double)cand * (double)cand / 4e12;
+    est += 8e-6 * (double)(lp.size() - 1) + 2.0 * (0.5 * (double)sizeof(V)) * (double)cand * (double)cand / 4e12;
     if (cand == 0 || est < best) { best = est; M = cand; }
   }
   auto slots = [&](const std::vector<int>& P, bool lower, const std::vector<int>& order, DevBuf<int>& d) -> int {
@@ -1381,22 +1414,29 @@ int cxlu_upload(CxLu* S, CxLuSet* F, const long long* Lptr, const long long* Lco
   MG_TRY(slots(LP, true, o, F->Lslot));
   lu_levels(n, UP, UC, false, M, o, F->Ulvl_h);
   MG_TRY(slots(UP, false, o, F->Uslot));
-  auto invert = [&](bool lower, const DevBuf<int>& ptr, const DevBuf<int>& col, const DevBuf<double>& val, DevBuf<double>& inv) -> int {
+  // the block is gathered and inverted in ComplexF64 whatever V is; a single factor's inverse is then rounded into V (X: its double form)
+  auto invert = [&](bool lower, const DevBuf<int>& ptr, const DevBuf<int>& col, const DevBuf<V>& val, DevBuf<V>& inv) -> int {
+    constexpr bool direct = std::is_same<V, cx_t>::value;
     const int ld = (M + 63) / 64 * 64;
-    const size_t len = 2 * (size_t)ld * (size_t)ld;
-    DevBuf<double> D;
+    const size_t len = (size_t)ld * (size_t)ld;
+    DevBuf<cx_t> D, X;
     int rc = D.alloc(len);
     if (rc == MG_OK) rc = inv.alloc(len);
-    if (rc == MG_OK && hipMemsetAsync(D.p, 0, len * sizeof(double), S->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipMemsetAsync failed");
+    if (rc == MG_OK && !direct) rc = X.alloc(len);
+    if (rc == MG_OK && hipMemsetAsync(D.p, 0, len * sizeof(cx_t), S->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "hipMemsetAsync failed");
     if (rc == MG_OK) {
-      hipLaunchKernelGGL(mgk::cx_tri_gather_block, dim3(cx_grid((long long)ld * 64)), dim3(mgk::BLK), 0, S->stream, ptr.p, col.p,
-                         reinterpret_cast<const cx_t*>(val.p), (int)n - M, M, ld, cxp(D));
+      cx_t* out = direct ? reinterpret_cast<cx_t*>(inv.p) : X.p;
+      hipLaunchKernelGGL(mgk::cx_tri_gather_block<V>, dim3(cx_grid((long long)ld * 64)), dim3(mgk::BLK), 0, S->stream, ptr.p, col.p,
+                         (const V*)val.p, (int)n - M, M, ld, D.p);
       const dim3 g((unsigned)(ld / mgk::CX_TRI_NB));
-      if (lower) hipLaunchKernelGGL(mgk::cx_tri_inverse<true>, g, dim3(256), 0, S->stream, reinterpret_cast<const cx_t*>(D.p), cxp(inv), ld);
-      else hipLaunchKernelGGL(mgk::cx_tri_inverse<false>, g, dim3(256), 0, S->stream, reinterpret_cast<const cx_t*>(D.p), cxp(inv), ld);
+      if (lower) hipLaunchKernelGGL(mgk::cx_tri_inverse<true>, g, dim3(256), 0, S->stream, (const cx_t*)D.p, out, ld);
+      else hipLaunchKernelGGL(mgk::cx_tri_inverse<false>, g, dim3(256), 0, S->stream, (const cx_t*)D.p, out, ld);
+      if constexpr (!direct)
+        hipLaunchKernelGGL(mgk::cx_tri_store<V>, dim3(cx_grid((long long)len)), dim3(mgk::BLK), 0, S->stream, (const cx_t*)X.p, inv.p, (long long)len);
       if (hipGetLastError() != hipSuccess || hipStreamSynchronize(S->stream) != hipSuccess) rc = fail(MG_ERR_HIP, "inversion of the trailing block failed");
     }
     D.release();
+    X.release();
     return rc;
   };
   if (M > 0) {
@@ -1405,18 +1445,20 @@ int cxlu_upload(CxLu* S, CxLuSet* F, const long long* Lptr, const long long* Lco
   }
   F->M = M;
   if (S->opt.debug_format)
-    std::fprintf(stderr, "[mgvcycle] complex LU (%s) n=%lld: dense trailing block %d, L %zu levels ahead of it (%d in all), U %zu behind it (%d)\n",
+    std::fprintf(stderr, "[mgvcycle] %s LU (%s) n=%lld: dense trailing block %d, L %zu levels ahead of it (%d in all), U %zu behind it (%d)\n",
+                 lu_store<V>::kind == 1 ? "complex" : lu_store<V>::kind == 3 ? "single complex" : "single real",
                  what, n, M, F->Llvl_h.size() - 1, F->nLlvl, F->Ulvl_h.size() - 1, F->nUlvl);
   return MG_OK;
 }
 
-// CSR (1-based) of the conjugate transpose of an n x n complex CSR (1-based) matrix; columns of every row come out ascending,
-// so U^H is lower triangular with its diagonal last and L^H upper triangular with its diagonal first
-void cx_adjoint_csr1(long long n, const std::vector<long long>& ptr, const std::vector<long long>& col, const std::vector<double>& val,
-                     std::vector<long long>& tp, std::vector<long long>& tc, std::vector<double>& tv) {
+// CSR (1-based) of the conjugate transpose (comps = 1: the transpose) of an n x n CSR (1-based) matrix; columns of every row come out
+// ascending, so U^H is lower triangular with its diagonal last and L^H upper triangular with its diagonal first
+template <typename T, int comps = 2>
+void cx_adjoint_csr1(long long n, const std::vector<long long>& ptr, const std::vector<long long>& col, const std::vector<T>& val,
+                     std::vector<long long>& tp, std::vector<long long>& tc, std::vector<T>& tv) {
   const size_t nnz = col.size();
   tc.resize(nnz);
-  tv.resize(2 * nnz);
+  tv.resize(comps * nnz);
   std::vector<long long> cnt((size_t)n, 0);
   for (size_t k = 0; k < nnz; ++k) cnt[(size_t)col[k] - 1]++;
   tp.assign((size_t)n + 1, 1);
@@ -1427,25 +1469,27 @@ void cx_adjoint_csr1(long long n, const std::vector<long long>& ptr, const std::
       const long long c = col[(size_t)k] - 1;
       const long long w = pos[(size_t)c]++ - 1;
       tc[(size_t)w] = r + 1;
-      tv[2 * (size_t)w] = val[2 * (size_t)k];
-      tv[2 * (size_t)w + 1] = -val[2 * (size_t)k + 1];
+      tv[comps * (size_t)w] = val[comps * (size_t)k];
+      if (comps == 2) tv[2 * (size_t)w + 1] = -val[2 * (size_t)k + 1];
     }
 }
 
 // the resident set of one solve direction; the adjoint set is built on its first use and kept beside the plain one
-int cxlu_set(CxLu* S, bool adjoint, CxLuSet** out) {
-  CxLuSet*& F = adjoint ? S->adj : S->fwd;
+template <typename V>
+int cxlu_set(CxLuT<V>* S, bool adjoint, CxLuSetT<V>** out) {
+  CxLuSetT<V>*& F = adjoint ? S->adj : S->fwd;
   if (!F) {
-    CxLuSet* G = new CxLuSet();
+    CxLuSetT<V>* G = new CxLuSetT<V>();
     int rc;
     if (!adjoint) {
       rc = cxlu_upload(S, G, S->Lptr.data(), S->Lcol.data(), S->Lval.data(), S->Uptr.data(), S->Ucol.data(), S->Uval.data(), S->p.data(),
                        S->q.data(), "plain");
     } else {   // A^H = Q U^H L^H P with A[p,q] = L U: x[p] = L^H \ (U^H \ b[q])
+      typedef typename lu_store<V>::scalar T;
       std::vector<long long> lp, lc, up, uc;
-      std::vector<double> lv, uv;
-      cx_adjoint_csr1(S->n, S->Uptr, S->Ucol, S->Uval, lp, lc, lv);
-      cx_adjoint_csr1(S->n, S->Lptr, S->Lcol, S->Lval, up, uc, uv);
+      std::vector<T> lv, uv;
+      cx_adjoint_csr1<T, lu_store<V>::comps>(S->n, S->Uptr, S->Ucol, S->Uval, lp, lc, lv);
+      cx_adjoint_csr1<T, lu_store<V>::comps>(S->n, S->Lptr, S->Lcol, S->Lval, up, uc, uv);
       rc = cxlu_upload(S, G, lp.data(), lc.data(), lv.data(), up.data(), uc.data(), uv.data(), S->q.data(), S->p.data(), "adjoint");
     }
     if (rc != MG_OK) {
@@ -1460,70 +1504,72 @@ int cxlu_set(CxLu* S, bool adjoint, CxLuSet** out) {
 
 // x = A \ b (or A^H \ b) on device vectors, row-major [n][nrhs]; enqueued on S->stream (on: on *on, a borrower's stream), no
 // synchronisation
-int cxlu_solve_dev(CxLu* S, CxLuSet& G, const cx_t* b, cx_t* x, int nr, const hipStream_t* on = nullptr) {
+template <typename V>
+int cxlu_solve_dev(CxLuT<V>* S, CxLuSetT<V>& G, const V* b, V* x, int nr, const hipStream_t* on) {
   const hipStream_t st = on ? *on : S->stream;
   const long long n = S->n;
-  const size_t wlen = 2 * (size_t)n * (size_t)nr, tlen = 2 * (size_t)std::max(G.M, 1) * (size_t)nr;
+  const size_t wlen = (size_t)n * (size_t)nr, tlen = (size_t)std::max(G.M, 1) * (size_t)nr;
   if (S->work.n < wlen) MG_TRY(S->work.alloc(wlen));
   if (S->tail.n < tlen) MG_TRY(S->tail.alloc(tlen));
-  mgk::CxLuDev F;
+  mgk::LuDevT<V> F;
   F.n = (int)n;
-  F.Lptr = G.Lptr.p; F.Lcol = G.Lcol.p; F.Lval = reinterpret_cast<const cx_t*>(G.Lval.p);
-  F.Uptr = G.Uptr.p; F.Ucol = G.Ucol.p; F.Uval = reinterpret_cast<const cx_t*>(G.Uval.p);
+  F.Lptr = G.Lptr.p; F.Lcol = G.Lcol.p; F.Lval = G.Lval.p;
+  F.Uptr = G.Uptr.p; F.Ucol = G.Ucol.p; F.Uval = G.Uval.p;
   F.p = G.P.p; F.q = G.Q.p;
   F.Lorder = G.Lorder.p; F.Llvl = G.Llvl.p; F.nLlvl = G.nLlvl;
   F.Uorder = G.Uorder.p; F.Ulvl = G.Ulvl.p; F.nUlvl = G.nUlvl;
-  cx_t* y = cxp(S->work);
+  V* y = S->work.p;
   if (!G.multi) {
-    hipLaunchKernelGGL(mgk::sptrsv_lu<cx_t>, dim3(1), dim3(1024), 0, st, F, b, x, y, nr);
+    hipLaunchKernelGGL(mgk::sptrsv_lu<V>, dim3(1), dim3(1024), 0, st, F, b, x, y, nr);
     HIP_TRY(hipGetLastError());
     return MG_OK;
   }
   auto wave_blocks = [](long long waves) { return dim3(cx_grid(waves * 64)); };
-  cx_t* t = cxp(S->tail);
+  V* t = S->tail.p;
   const int M = G.M, n0 = (int)n - M, ld = (M + 63) / 64 * 64;
   // y = L \ b[p]: the levels ahead of the trailing block one launch each, the block through its inverse
   const int nLl = (int)G.Llvl_h.size() - 1, nUl = (int)G.Ulvl_h.size() - 1;
   for (int l = 0; l < nLl; ++l) {
     const int t0 = G.Llvl_h[(size_t)l], t1 = G.Llvl_h[(size_t)l + 1];
-    hipLaunchKernelGGL(mgk::cx_sptrsv_level<true>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, st, F,
+    hipLaunchKernelGGL((mgk::cx_sptrsv_level<true, V>), wave_blocks(t1 - t0), dim3(mgk::BLK), 0, st, F,
                        reinterpret_cast<const int4*>(G.Lslot.p), t0, t1, b, y, nr);
   }
   if (M > 0) {
-    hipLaunchKernelGGL(mgk::cx_sptrsv_tail_rhs, wave_blocks(M), dim3(mgk::BLK), 0, st, F, n0, b, y, t, nr);
-    hipLaunchKernelGGL(mgk::cx_tri_apply<true>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, st,
-                       reinterpret_cast<const cx_t*>(G.invL.p), ld, t, y + (size_t)n0 * (size_t)nr, M, nr);
+    hipLaunchKernelGGL(mgk::cx_sptrsv_tail_rhs<V>, wave_blocks(M), dim3(mgk::BLK), 0, st, F, n0, b, (const V*)y, t, nr);
+    hipLaunchKernelGGL((mgk::cx_tri_apply<true, V>), wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, st,
+                       (const V*)G.invL.p, ld, (const V*)t, y + (size_t)n0 * (size_t)nr, M, nr);
     // y = U \ y: the trailing block first, then the levels behind it
-    HIP_TRY(hipMemcpyAsync(t, y + (size_t)n0 * (size_t)nr, (size_t)M * (size_t)nr * sizeof(cx_t), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(mgk::cx_tri_apply<false>, wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, st,
-                       reinterpret_cast<const cx_t*>(G.invU.p), ld, t, y + (size_t)n0 * (size_t)nr, M, nr);
+    HIP_TRY(hipMemcpyAsync(t, y + (size_t)n0 * (size_t)nr, (size_t)M * (size_t)nr * sizeof(V), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL((mgk::cx_tri_apply<false, V>), wave_blocks((long long)M * nr), dim3(mgk::BLK), 0, st,
+                       (const V*)G.invU.p, ld, (const V*)t, y + (size_t)n0 * (size_t)nr, M, nr);
   }
   for (int l = 0; l < nUl; ++l) {
     const int t0 = G.Ulvl_h[(size_t)l], t1 = G.Ulvl_h[(size_t)l + 1];
-    hipLaunchKernelGGL(mgk::cx_sptrsv_level<false>, wave_blocks(t1 - t0), dim3(mgk::BLK), 0, st, F,
+    hipLaunchKernelGGL((mgk::cx_sptrsv_level<false, V>), wave_blocks(t1 - t0), dim3(mgk::BLK), 0, st, F,
                        reinterpret_cast<const int4*>(G.Uslot.p), t0, t1, b, y, nr);
   }
-  hipLaunchKernelGGL(mgk::cx_sptrsv_scatter, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, st, G.Q.p, y, x, (int)n, nr);
+  hipLaunchKernelGGL(mgk::cx_sptrsv_scatter<V>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, st, (const int*)G.Q.p, (const V*)y, x, (int)n, nr);
   HIP_TRY(hipGetLastError());
   return MG_OK;
 }
 
-// host form: b, x column-major n x nrhs interleaved complex; b is only read
-int cxlu_solve_host(CxLu* S, CxLuSet& G, const double* b, double* x, int nr) {
+// host form: b, x column-major n x nrhs in the handle's value type (complex: interleaved); b is only read
+template <typename V>
+int cxlu_solve_host(CxLuT<V>* S, CxLuSetT<V>& G, const typename lu_store<V>::scalar* b, typename lu_store<V>::scalar* x, int nr) {
   const long long n = S->n;
-  const size_t len = 2 * (size_t)n * (size_t)nr, bytes = len * sizeof(double);
+  const size_t len = (size_t)n * (size_t)nr, bytes = len * sizeof(V);
   if (S->stage_b.n < len) MG_TRY(S->stage_b.alloc(len));
   if (S->stage_x.n < len) MG_TRY(S->stage_x.alloc(len));
   if (nr > 1 && S->stage_t.n < len) MG_TRY(S->stage_t.alloc(len));
   if (nr == 1) {
     HIP_TRY(hipMemcpyAsync(S->stage_b.p, b, bytes, hipMemcpyHostToDevice, S->stream));
-    MG_TRY(cxlu_solve_dev(S, G, cxp(S->stage_b), cxp(S->stage_x), 1));
+    MG_TRY(cxlu_solve_dev<V>(S, G, S->stage_b.p, S->stage_x.p, 1));
     HIP_TRY(hipMemcpyAsync(x, S->stage_x.p, bytes, hipMemcpyDeviceToHost, S->stream));
   } else {
     HIP_TRY(hipMemcpyAsync(S->stage_t.p, b, bytes, hipMemcpyHostToDevice, S->stream));
-    hipLaunchKernelGGL(mgk::cx_relayout<true>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, cxp(S->stage_t), cxp(S->stage_b), n, nr);
-    MG_TRY(cxlu_solve_dev(S, G, cxp(S->stage_b), cxp(S->stage_x), nr));
-    hipLaunchKernelGGL(mgk::cx_relayout<false>, dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, cxp(S->stage_x), cxp(S->stage_t), n, nr);
+    hipLaunchKernelGGL((mgk::cx_relayout<true, V>), dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, (const V*)S->stage_t.p, S->stage_b.p, n, nr);
+    MG_TRY(cxlu_solve_dev<V>(S, G, S->stage_b.p, S->stage_x.p, nr));
+    hipLaunchKernelGGL((mgk::cx_relayout<false, V>), dim3(cx_grid(n * nr)), dim3(mgk::BLK), 0, S->stream, (const V*)S->stage_x.p, S->stage_t.p, n, nr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(x, S->stage_t.p, bytes, hipMemcpyDeviceToHost, S->stream));
   }
@@ -1531,10 +1577,12 @@ int cxlu_solve_host(CxLu* S, CxLuSet& G, const double* b, double* x, int nr) {
   return MG_OK;
 }
 
-// the create step behind mg_lu_create_CFP64_INT64: arguments already checked for null / 1-based pointers
-int cxlu_create(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const double* Lval, const long long* Uptr,
-                const long long* Ucol, const double* Uval, const long long* p, const long long* q, CxLu** out,
-                const Options* opt = nullptr) {
+// the create step behind mg_lu_create_*: arguments already checked for null / 1-based pointers
+template <typename V>
+int cxlu_create(long long device_id, long long n, const long long* Lptr, const long long* Lcol, const typename lu_store<V>::scalar* Lval,
+                const long long* Uptr, const long long* Ucol, const typename lu_store<V>::scalar* Uval, const long long* p,
+                const long long* q, CxLuT<V>** out, const Options* opt = nullptr) {
+  constexpr int comps = lu_store<V>::comps;
   if (n >= (1LL << 31) - 1 || Lptr[n] - 1 >= (1LL << 31) || Uptr[n] - 1 >= (1LL << 31))
     return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
   int ndev = 0;
@@ -1542,21 +1590,21 @@ int cxlu_create(long long device_id, long long n, const long long* Lptr, const l
   if (ndev <= 0) return fail(MG_ERR_HIP, "no HIP device visible: the factor applier has no CPU fallback");
   if (device_id < 0 || device_id >= ndev) return fail(MG_ERR_INVALID, "device_id=%lld but %d devices visible", device_id, ndev);
   HIP_TRY(hipSetDevice((int)device_id));
-  CxLu* S = new CxLu();
+  CxLuT<V>* S = new CxLuT<V>();
   S->opt = opt ? *opt : Options::from_env();   // the only place the environment is read for this handle (opt: a hierarchy's own)
   S->device = (int)device_id;
   S->n = n;
   S->Lptr.assign(Lptr, Lptr + n + 1);
   S->Uptr.assign(Uptr, Uptr + n + 1);
   S->Lcol.assign(Lcol, Lcol + (Lptr[n] - 1));
-  S->Lval.assign(Lval, Lval + 2 * (Lptr[n] - 1));
+  S->Lval.assign(Lval, Lval + comps * (Lptr[n] - 1));
   S->Ucol.assign(Ucol, Ucol + (Uptr[n] - 1));
-  S->Uval.assign(Uval, Uval + 2 * (Uptr[n] - 1));
+  S->Uval.assign(Uval, Uval + comps * (Uptr[n] - 1));
   S->p.assign(p, p + n);
   S->q.assign(q, q + n);
   int rc = MG_OK;
   if (hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(MG_ERR_HIP, "hipStreamCreate failed");
-  CxLuSet* F = nullptr;
+  CxLuSetT<V>* F = nullptr;
   if (rc == MG_OK) rc = cxlu_set(S, false, &F);   // validates and uploads the factors
   if (rc != MG_OK) {
     cxlu_destroy(S);
@@ -2311,7 +2359,7 @@ int mg_set_coarse_dense_inverse_CF64(mg_hierarchy* h, long long n, const double*
   MG_TRY(S.Ainv.alloc(rm.size()));
   HIP_TRY(hipMemcpy(S.Ainv.p, rm.data(), rm.size() * sizeof(double), hipMemcpyHostToDevice));
   dd_detach(h);
-  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+  cx_drop_coarse_appliers(S);
   S.n_coarse = n;
   S.coarse_set = true;
   S.coarse_lu = false;
@@ -2370,7 +2418,7 @@ int mg_build_coarse_dense_inverse_CF64(mg_hierarchy* h) {
   }
   MG_TRY(cx_coarse_inverse_finish(h, K, spare, "mg_build_coarse_dense_inverse_CF64"));
   dd_detach(h);
-  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+  cx_drop_coarse_appliers(S);
   for (DevBuf<int>* q : {&S.luLptr, &S.luLcol, &S.luUptr, &S.luUcol, &S.luP, &S.luQ, &S.luLorder, &S.luLlvl, &S.luUorder, &S.luUlvl}) q->release();
   S.luLval.release(); S.luUval.release(); S.luWork.release();
   S.n_coarse = S.lev[(size_t)h->nlevels - 1].A.n_rows;
@@ -2419,12 +2467,12 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
     // inverse, held by a factor applier of the hierarchy's own and enqueued on the hierarchy's stream (cx_coarse)
     CxLu* F = nullptr;
     MG_TRY(cxlu_create(h->device, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, &F, &h->opt));
-    const size_t wlen = 2 * (size_t)n, tlen = 2 * (size_t)std::max(F->fwd->M, 1);   // (no allocation inside the cycle)
+    const size_t wlen = (size_t)n, tlen = (size_t)std::max(F->fwd->M, 1);   // (no allocation inside the cycle)
     if (F->work.alloc(wlen) != MG_OK || F->tail.alloc(tlen) != MG_OK) {
       cxlu_destroy(F);
       return fail(MG_ERR_HIP, "allocation of the coarsest solve's work vectors failed");
     }
-    if (S.coarse_multi) cxlu_destroy(S.coarse_multi);
+    cx_drop_coarse_appliers(S);
     S.coarse_multi = F;
     for (DevBuf<int>* d : {&S.luLptr, &S.luLcol, &S.luUptr, &S.luUcol, &S.luP, &S.luQ, &S.luLorder, &S.luLlvl, &S.luUorder, &S.luUlvl}) d->release();
     S.luLval.release(); S.luUval.release(); S.luWork.release();
@@ -2437,7 +2485,7 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
     S.finalized = false;
     return MG_OK;
   }
-  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+  cx_drop_coarse_appliers(S);
   const size_t N = (size_t)n;
   std::vector<int> LP, LC, LO, LL, UP, UC, UO, UL, pp(N), qq(N);
   MG_TRY(lu_convert(n, Lptr, Lcol, true, LP, LC, LO, LL));
@@ -2471,6 +2519,42 @@ int mg_set_coarse_lu_CF64_INT64(mg_hierarchy* h, long long n, const long long* L
   return MG_OK;
 }
 
+// ComplexF32 factors on a CF32 handle (the reference's parallelJuliaSolver(ComplexF32, Int64) as param.LU): the coarsest solve applies
+// them to the cycle's own float2 bc - no widened pair - in the single-workgroup form below lu_multi_min_rows rows and the chip-wide
+// form from there on, both held by a factor applier of the hierarchy's own and enqueued on the hierarchy's stream (cx_coarse).
+int mg_set_coarse_lu_CF32_INT64(mg_hierarchy* h, long long n, const long long* Lptr, const long long* Lcol, const float* Lval,
+                                const long long* Uptr, const long long* Ucol, const float* Uval, const long long* p,
+                                const long long* q) {
+  UploadFence upload_fence;
+  MG_TRY(cx_level_ok(h, 1, CX_WANT32));
+  if (n < 1 || !Lptr || !Lcol || !Lval || !Uptr || !Ucol || !Uval || !p || !q) return fail(MG_ERR_INVALID, "null or empty factor");
+  if (n >= (1LL << 31) - 1 || Lptr[n] - 1 >= (1LL << 31) || Uptr[n] - 1 >= (1LL << 31))
+    return fail(MG_ERR_UNSUPPORTED, "factors exceed int32 device indices");
+  if (Lptr[0] != 1 || Uptr[0] != 1) return fail(MG_ERR_INVALID, "row pointers must be 1-based");
+  (void)hipSetDevice(h->device);
+  CxState& S = *h->cx;
+  if (h->play->stream) HIP_TRY(spin_sync(h->play->stream));
+  CxLuT<cf_t>* F = nullptr;
+  MG_TRY(cxlu_create<cf_t>(h->device, n, Lptr, Lcol, Lval, Uptr, Ucol, Uval, p, q, &F, &h->opt));
+  const size_t wlen = (size_t)n, tlen = (size_t)std::max(F->fwd->M, 1);   // (no allocation inside the cycle)
+  if (F->work.alloc(wlen) != MG_OK || F->tail.alloc(tlen) != MG_OK) {
+    cxlu_destroy(F);
+    return fail(MG_ERR_HIP, "allocation of the coarsest solve's work vectors failed");
+  }
+  cx_drop_coarse_appliers(S);
+  S.coarse_single = F;
+  for (DevBuf<int>* d : {&S.luLptr, &S.luLcol, &S.luUptr, &S.luUcol, &S.luP, &S.luQ, &S.luLorder, &S.luLlvl, &S.luUorder, &S.luUlvl}) d->release();
+  S.luLval.release(); S.luUval.release(); S.luWork.release();
+  dd_detach(h);
+  S.n_coarse = n;
+  S.coarse_set = true;
+  S.coarse_lu = true;
+  S.coarse_gmres = false;
+  S.Ainv.release();
+  S.finalized = false;
+  return MG_OK;
+}
+
 // coarseSolveType "GMRES": d = param.LU = relaxParam ./ diag(A_c), n complex128 values (a CF32 handle's too)
 int mg_set_coarse_gmres_CF64(mg_hierarchy* h, long long n, const double* d) {
   UploadFence upload_fence;
@@ -2483,7 +2567,7 @@ int mg_set_coarse_gmres_CF64(mg_hierarchy* h, long long n, const double* d) {
   MG_TRY(S.cgD.alloc(2 * (size_t)n));
   HIP_TRY(hipMemcpy(S.cgD.p, d, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   dd_detach(h);
-  if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+  cx_drop_coarse_appliers(S);
   for (DevBuf<int>* q : {&S.luLptr, &S.luLcol, &S.luUptr, &S.luUcol, &S.luP, &S.luQ, &S.luLorder, &S.luLlvl, &S.luUorder, &S.luUlvl}) q->release();
   S.luLval.release(); S.luUval.release(); S.luWork.release();
   S.Ainv.release();

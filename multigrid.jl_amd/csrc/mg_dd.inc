@@ -586,7 +586,7 @@ int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* d) {
   d->owner = h;
   if (h->cx) {
     CxState& S = *h->cx;
-    if (S.coarse_multi) { cxlu_destroy(S.coarse_multi); S.coarse_multi = nullptr; }
+    cx_drop_coarse_appliers(S);
     S.n_coarse = d->n;
     S.coarse_set = true;
     S.coarse_lu = false;
@@ -624,6 +624,12 @@ int mg_coarse_form(mg_hierarchy* h, long long* info) {
     if (S.coarse_multi) {
       const CxLuSet& G = *S.coarse_multi->fwd;
       info[2] = G.multi ? (long long)(G.Llvl_h.size() - 1) + (long long)(G.Ulvl_h.size() - 1) + (G.M > 0 ? 3 : 0) + 1 : 1;
+    } else if (S.coarse_single) {   // ComplexF32 factors: one applier holds either form
+      const CxLuSetT<cf_t>& G = *S.coarse_single->fwd;
+      if (G.multi) {
+        info[0] = 2;
+        info[2] = (long long)(G.Llvl_h.size() - 1) + (long long)(G.Ulvl_h.size() - 1) + (G.M > 0 ? 3 : 0) + 1;
+      }
     }
   } else if (h->coarse_gmres) {
     info[0] = 3;

@@ -44,6 +44,7 @@ constexpr int MM_PAIRS = MM_ITEMS / 2;
 enum Mode { AXPBY = 0, RESID = 1, SMOOTH = 2 };
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
+typedef float f2_t __attribute__((ext_vector_type(2)));   // a ComplexF32 value (mg_complex.hpp; the single factor sweeps below)
 typedef int i2_t __attribute__((ext_vector_type(2)));
 // The matrix stream (values, column indices) is read exactly once per launch.  NT = non-temporal loads:
 // the stream then does not evict the gather window of the source vector from the XCD's L2.  Measured on
@@ -3762,6 +3763,20 @@ __device__ __forceinline__ d2_t lu_div(d2_t a, d2_t b) {
   return d2_t{(a.x * b.x + a.y * b.y) / s, (a.y * b.x - a.x * b.y) / s};
 }
 __device__ __forceinline__ d2_t lu_shfl_xor(d2_t a, int o) { return d2_t{__shfl_xor(a.x, o), __shfl_xor(a.y, o)}; }
+// Single factors (T = float, f2_t): values and vectors are STORED in T, every row is evaluated in its accumulation type
+// lu_acc<T> - a factor value and the gathered y widened on load (the product of two widened singles is exact in double), the
+// partial sums, the subtraction from the right-hand side and the division in double, one rounding on the store of y[row].
+// For T = double / d2_t the accumulation type is T itself and widening and rounding are the identity.
+template <typename T> struct lu_acc { typedef T type; };
+template <> struct lu_acc<float> { typedef double type; };
+template <> struct lu_acc<f2_t> { typedef d2_t type; };
+__device__ __forceinline__ double lu_wide(double a) { return a; }
+__device__ __forceinline__ d2_t lu_wide(d2_t a) { return a; }
+__device__ __forceinline__ double lu_wide(float a) { return (double)a; }
+__device__ __forceinline__ d2_t lu_wide(f2_t a) { return d2_t{(double)a.x, (double)a.y}; }
+template <typename T> __device__ __forceinline__ T lu_round(typename lu_acc<T>::type a) { return a; }
+template <> __device__ __forceinline__ float lu_round<float>(double a) { return (float)a; }
+template <> __device__ __forceinline__ f2_t lu_round<f2_t>(d2_t a) { return f2_t{(float)a.x, (float)a.y}; }
 
 // One triangular sweep over the dependency levels.  A level with >= 16 rows gives every wavefront its own rows; a
 // level with fewer rows (the dense trailing supernodes of a factor are chains of single-row levels) splits each row
@@ -3772,7 +3787,8 @@ __device__ __forceinline__ void sptrsv_sweep(const int* __restrict__ ptr, const 
                                              const T* __restrict__ val, const int* __restrict__ order,
                                              const int* __restrict__ lvl, int nlvl, const int* __restrict__ perm,
                                              const T* __restrict__ b, T* y, int nrhs, int c0, int nc,
-                                             T (*sred)[4]) {
+                                             typename lu_acc<T>::type (*sred)[4]) {
+  typedef typename lu_acc<T>::type A;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   for (int l = 0; l < nlvl; ++l) {
     const int t0 = lvl[l], t1 = lvl[l + 1], cnt = t1 - t0;
@@ -3783,23 +3799,23 @@ __device__ __forceinline__ void sptrsv_sweep(const int* __restrict__ ptr, const 
       const int row = order[t];
       const int s = LOWER ? ptr[row] : ptr[row] + 1;
       const int e = LOWER ? ptr[row + 1] - 1 : ptr[row + 1];
-      T acc[4] = {T{}, T{}, T{}, T{}};
+      A acc[4] = {A{}, A{}, A{}, A{}};
       for (int k = s + part * 64 + lane; k < e; k += 64 * g) {
-        const T v = val[k];
+        const A v = lu_wide(val[k]);
         const T* yy = y + (size_t)col[k] * nrhs + c0;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-          if (u < nc) acc[u] += lu_mul(v, yy[u]);
+          if (u < nc) acc[u] += lu_mul(v, lu_wide(yy[u]));
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         for (int o = 32; o > 0; o >>= 1) acc[u] += lu_shfl_xor(acc[u], o);
       if (g == 1) {
         if (lane < nc) {
-          const T dg = val[LOWER ? e : s - 1];
-          const T rhs = LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
-          const T a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-          y[(size_t)row * nrhs + c0 + lane] = lu_div(rhs - a, dg);
+          const A dg = lu_wide(val[LOWER ? e : s - 1]);
+          const A rhs = lu_wide(LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane]);
+          const A a = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+          y[(size_t)row * nrhs + c0 + lane] = lu_round<T>(lu_div(rhs - a, dg));
         }
       } else if (lane < 4) {
         sred[wave][lane] = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
@@ -3810,11 +3826,11 @@ __device__ __forceinline__ void sptrsv_sweep(const int* __restrict__ ptr, const 
       const int t = t0 + wave / g;
       if (part == 0 && t < t1 && lane < nc) {
         const int row = order[t];
-        T a = T{};
+        A a = A{};
         for (int w = 0; w < g; ++w) a += sred[wave + w][lane];
-        const T dg = val[LOWER ? ptr[row + 1] - 1 : ptr[row]];
-        const T rhs = LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane];
-        y[(size_t)row * nrhs + c0 + lane] = lu_div(rhs - a, dg);
+        const A dg = lu_wide(val[LOWER ? ptr[row + 1] - 1 : ptr[row]]);
+        const A rhs = lu_wide(LOWER ? b[(size_t)perm[row] * nrhs + c0 + lane] : y[(size_t)row * nrhs + c0 + lane]);
+        y[(size_t)row * nrhs + c0 + lane] = lu_round<T>(lu_div(rhs - a, dg));
       }
     }
     __syncthreads();
@@ -3824,7 +3840,7 @@ __device__ __forceinline__ void sptrsv_sweep(const int* __restrict__ ptr, const 
 template <typename T>
 __global__ __launch_bounds__(1024) void sptrsv_lu(LuDevT<T> F, const T* __restrict__ b, T* __restrict__ x,
                                                   T* work, int nrhs) {
-  __shared__ T sred[16][4];
+  __shared__ typename lu_acc<T>::type sred[16][4];
   for (int c0 = 0; c0 < nrhs; c0 += 4) {
     const int nc = min(4, nrhs - c0);
     sptrsv_sweep<true>(F.Lptr, F.Lcol, F.Lval, F.Lorder, F.Llvl, F.nLlvl, F.p, b, work, nrhs, c0, nc, sred);   // y = L \\ b[p]

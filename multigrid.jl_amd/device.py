@@ -32,6 +32,7 @@ _ll = C.c_longlong
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _lp = C.POINTER(C.c_longlong)
+_up = C.POINTER(C.c_uint)
 _vp = C.c_void_p
 
 # name -> (restype, argtypes); exactly the symbols include/mgvcycle.h declares
@@ -139,6 +140,13 @@ SIGNATURES = {
     "mg_lu_create_CFP64_INT64": (C.c_int, [_ll, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp, C.POINTER(_vp)]),
     "mg_lu_solve_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_lu_solve_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_lu_create_FP32_UINT32": (C.c_int, [_ll, _ll, _lp, _up, _fp, _lp, _up, _fp, _up, _up, C.POINTER(_vp)]),
+    "mg_lu_create_CFP32_UINT32": (C.c_int, [_ll, _ll, _lp, _up, _fp, _lp, _up, _fp, _up, _up, C.POINTER(_vp)]),
+    "mg_lu_create_CFP32_INT64": (C.c_int, [_ll, _ll, _lp, _lp, _fp, _lp, _lp, _fp, _lp, _lp, C.POINTER(_vp)]),
+    "mg_lu_solve_FP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, _ll]),
+    "mg_lu_solve_dev_FP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_lu_solve_CFP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, _ll]),
+    "mg_lu_solve_dev_CFP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
     "mg_lu_form": (C.c_int, [_vp, _ll, _lp]),
     "mg_lu_time_dev": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _ll, _dp]),
     "mg_lu_destroy": (C.c_int, [_vp]),
@@ -243,6 +251,7 @@ SIGNATURES = {
     "mg_fgmres_relax_CF32": (C.c_int, [_vp, _ll, _fp, _fp, _ll, _ll, C.c_double, _dp, _dp, _dp, _lp, _fp, _fp]),
     "mg_set_coarse_dense_inverse_CF64": (C.c_int, [_vp, _ll, _dp]),
     "mg_set_coarse_lu_CF64_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _dp, _lp, _lp, _dp, _lp, _lp]),
+    "mg_set_coarse_lu_CF32_INT64": (C.c_int, [_vp, _ll, _lp, _lp, _fp, _lp, _lp, _fp, _lp, _lp]),
     "mg_set_coarse_gmres_CF64": (C.c_int, [_vp, _ll, _dp]),
     "mg_coarse_gmres_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _lp, _lp, _dp]),
     "mg_block_coarse_gmres_CF64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _lp, _lp, _dp]),
@@ -336,6 +345,14 @@ def _f64(a):
 
 def _i64(a):
     return a.ctypes.data_as(_lp)
+
+
+def _f32(a):
+    return a.ctypes.data_as(_fp)
+
+
+def _u32(a):
+    return a.ctypes.data_as(_up)
 
 
 def _julia_arrays(M):
@@ -629,18 +646,20 @@ class DeviceHierarchy:
         if isinstance(LU, PJS.parallelJuliaSolver):
             if LU.L is None:
                 raise MGDeviceError("param.LU is a parallelJuliaSolver without factors: run MGsetup / SA_AMGsetup first")
-            from .mgdef import factor_val
-            if np.dtype(LU.VAL) != factor_val(param):
+            from .mgdef import factor_vals
+            if np.dtype(LU.VAL) not in factor_vals(param):
                 raise TypeError("param.LU holds %s factors, the hierarchy %s values" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
-            VAL = factor_val(param)                # (ComplexF32 hierarchies keep ComplexF64 factors)
+            # (a ComplexF32 hierarchy keeps ComplexF64 factors, or applies the ComplexF32 ones of a single solver object to its own bc)
+            VAL = np.dtype(LU.VAL)
             a64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
             L, U = LU.L, LU.U
             Lp, Lc, Lv = a64(L.indptr) + 1, a64(L.indices) + 1, np.ascontiguousarray(L.data, dtype=VAL)
             Up, Uc, Uv = a64(U.indptr) + 1, a64(U.indices) + 1, np.ascontiguousarray(U.data, dtype=VAL)
-            cx = VAL == np.complex128
-            fn, what = (lib.mg_set_coarse_lu_CF64_INT64, "mg_set_coarse_lu_CF64") if cx else (lib.mg_set_coarse_lu_FP64_INT64, "mg_set_coarse_lu")
+            fn, what, val = {np.dtype(np.complex64): (lib.mg_set_coarse_lu_CF32_INT64, "mg_set_coarse_lu_CF32", _f32),
+                             np.dtype(np.complex128): (lib.mg_set_coarse_lu_CF64_INT64, "mg_set_coarse_lu_CF64", _f64),
+                             np.dtype(np.float64): (lib.mg_set_coarse_lu_FP64_INT64, "mg_set_coarse_lu", _f64)}[VAL]
             self._detach_dd()
-            _check(lib, fn(self.handle, L.shape[0], _i64(Lp), _i64(Lc), _f64(Lv), _i64(Up), _i64(Uc), _f64(Uv), _i64(a64(LU.p)), _i64(a64(LU.q))), what)
+            _check(lib, fn(self.handle, L.shape[0], _i64(Lp), _i64(Lc), val(Lv), _i64(Up), _i64(Uc), val(Uv), _i64(a64(LU.p)), _i64(a64(LU.q))), what)
             return True
         self._detach_dd()
         return False

@@ -185,6 +185,13 @@ def factor_val(param: MGparam):
     return np.dtype(np.complex128) if is_single(param) else np.dtype(param.VAL)
 
 
+def factor_vals(param: MGparam):
+    """The value types a ``parallelJuliaSolver`` preset as ``param.LU`` may hold: ``factor_val``, and on a ComplexF32 hierarchy
+    ComplexF32 too - a single solver object (``getParallelJuliaSolver(np.complex64, ..., singleFactors=True)``), whose factors the
+    coarsest solve applies to the cycle's own single vectors (mg_set_coarse_lu_CF32_INT64)."""
+    return (factor_val(param), np.dtype(np.complex64)) if is_single(param) else (factor_val(param),)
+
+
 def hierarchyExists(param: MGparam) -> bool:
     return len(param.As) > 0
 

@@ -15,7 +15,7 @@ import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-from .mgdef import MGparam, destroyCoarsestLU, _release_device, factor_val, is_complex, is_single
+from .mgdef import MGparam, destroyCoarsestLU, _release_device, factor_val, factor_vals, is_complex, is_single
 from .transfer_operators import getFWInterp
 
 
@@ -163,8 +163,9 @@ def defineCoarsestAinv(param: MGparam, Ac) -> None:
         return
     if kind == "pjs":                             # setupSolver(sparse(AT'), LU)
         from .parallel_julia_solver import setupLUFactor
-        if np.dtype(param.LU.VAL) != factor_val(param):
+        if np.dtype(param.LU.VAL) not in factor_vals(param):
             raise TypeError("param.LU is a parallelJuliaSolver of %s, the hierarchy of %s" % (np.dtype(param.LU.VAL), np.dtype(param.VAL)))
+        # (a single solver object factorises the widened matrix in double itself and keeps single factors)
         setupLUFactor(_as_csr(Ac).astype(factor_val(param)), param.LU, upload=False)
         return
     if param.coarseSolveType == "MUMPS":
