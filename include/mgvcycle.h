@@ -153,7 +153,9 @@ int mg_replace_values_FP64(mg_hierarchy* h, long long level, long long which,
  * Galerkin product As[l+1] = Ps[l]*As[l]*Rs[l] on the fixed patterns (rows of As[l+1] of any length: 2048 target columns
  * at a time; deterministic - the same sums in the same order on every run).  The coarsest factorisation stays on the host: fetch the
  * coarsest values (mg_get_values_FP64), factor, mg_set_coarse_dense_inverse_FP64, mg_finalize - unless the option
- * "coarse_device_inverse" is set and a dense inverse installed: then it is rebuilt here, in HBM (mg_build_coarse_dense_inverse_FP64). */
+ * "coarse_device_inverse" is set and a dense inverse installed: then it is rebuilt here, in HBM (mg_build_coarse_dense_inverse_FP64).
+ * A coarse operator As[l+1] with a row whose stored columns descend anywhere is refused (MG_ERR_UNSUPPORTED, found at upload,
+ * before anything is written): the kernel finds its target columns by binary search in that row. */
 int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long long relaxKind,
                 const double* omega, long long* levels_done);
 int mg_get_values_FP64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
@@ -927,7 +929,7 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
  * pattern's (MG_ERR_INVALID otherwise).  Common refusals: a null handle or array MG_ERR_INVALID, an FP64 handle MG_ERR_STATE.
  *
  * mg_rap_CF64 is mg_rap_FP64 for complex values: it writes the new fine values, then per level recomputes relaxPrecs[l]
- * (relaxKind 0: Jac, d = omega/a_ii; 1: SPAI, d = omega*conj(a_ii)/s_i with s_i the sum of re^2 + im^2 over COLUMN i in ascending
+ * (relaxKind 0: Jac, d = omega/a_ii, contraction off: s = fl(fl(x x) + fl(y y)), d = (fl(omega x)/s, fl(-omega y)/s); 1: SPAI, d = omega*conj(a_ii)/s_i with s_i the sum of re^2 + im^2 over COLUMN i in ascending
  * row order; omega[l] real, one per level) and As[l+1] = Rs[l]*(As[l]*Ps[l]) on its fixed pattern (csrc/mg_complex.hpp,
  * cx_rap_numeric: deterministic, no atomics; rows of any length, at most the option rap_chunk target columns at a time; the
  * option rap_groups sets how many rows of A a wavefront walks side by side, 1 being the order of mg_rap_FP64's kernel).  The
@@ -942,7 +944,9 @@ int mg_spmv_CF64(mg_hierarchy* h, long long level, long long which, const double
  * n must be nlevels - 1 (MG_ERR_INVALID), and a mg_rap_CF64 must have completed on the handle (MG_ERR_STATE).
  * mg_get_values_CF64 / mg_replace_values_CF64: one operator's values in stored CSR order (A: nnz complex; P, R: nnz real).
  * mg_get_relax_CF64: relaxPrecs[level], n complex values, as mg_set_relax_CF64 takes them.
- * Assumed, as by mg_rap_FP64, and not validated at upload for hand-built hierarchies: the rows of every As[l+1] are sorted, hold
+ * A coarse operator As[l+1] with a row whose stored columns descend anywhere is refused (MG_ERR_UNSUPPORTED, found at upload,
+ * before the first write: the kernel finds its target columns by binary search).
+ * Assumed, as by mg_rap_FP64, and not validated at upload for hand-built hierarchies: the rows of every As[l+1] hold
  * no column twice and contain every column the product reaches; no row of P holds a column twice.
  * Determinism is per configuration: the order of the sums depends on the number of lane groups, which follows rap_groups and is
  * halved while the accumulator copies of a level's longest row exceed 32 KB of LDS - the same handle gives the same bits on
@@ -971,6 +975,8 @@ mg_status mg_rap_level_ms_CF64(mg_hierarchy* h, double* out, long long n);
 mg_status mg_get_values_CF64(mg_hierarchy* h, long long level, long long which, double* out, long long nnz);
 mg_status mg_get_relax_CF64(mg_hierarchy* h, long long level, double* out, long long n);
 mg_status mg_replace_values_CF64(mg_hierarchy* h, long long level, long long which, const double* nzval, long long nnz);
+/* mg_rap_CF32 refuses a coarse operator As[l+1] with a row whose stored columns descend anywhere (MG_ERR_UNSUPPORTED, found at upload,
+ * before anything is written), as mg_rap_FP64 and mg_rap_CF64 do. */
 mg_status mg_rap_CF32(mg_hierarchy* h, const float* fine_nzval, long long nnz, long long relaxKind, const double* omega,
                       long long* levels_done);
 mg_status mg_rap_level_ms_CF32(mg_hierarchy* h, double* out, long long n);

@@ -175,6 +175,9 @@ int mg_rap_FP64(mg_hierarchy* h, const double* fine_nzval, long long nnz, long l
   for (int l = 0; l < nl; ++l)
     if (h->lev[(size_t)l].A.wide || h->lev[(size_t)l].P.wide || h->lev[(size_t)l].R.wide)
       return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers (>= 2^31 non-zeros): the numeric Galerkin product on the device serves int32 operators", l + 1);
+  for (int l = 1; l < nl; ++l)
+    if (!h->lev[(size_t)l].A.rows_sorted)
+      return fail(MG_ERR_UNSUPPORTED, "As[%d] holds a row whose stored columns do not ascend: the numeric Galerkin product on the device finds its target columns by binary search (sort the rows, or take the host path)", l + 1);
   const bool dev_inverse = h->opt.coarse_device_inverse && h->coarse_set && !h->coarse_lu && !h->coarse_gmres && !h->coarse_dd && h->Ainv.p;
   if (dev_inverse) MG_TRY(coarse_inverse_check(h));
   HIP_TRY(spin_sync(h->play->stream));

@@ -917,11 +917,26 @@ __device__ __forceinline__ d2_t cx_diag(const CxCsr32<AV>& A, int i) {
 }
 // d_i = omega / a_ii  (getRelaxPrec "Jac" for complex values: conj(relaxParam ./ diag(AT)), MGsetup.jl:145-147)
 // (AV: A's stored pairs, DV: d's - the GMRES coarsest vector of a CF32 handle is ComplexF64 from the widened operator)
+// cdiv((omega, 0), a) with contraction off, so that the vector is one fixed sequence of roundings (as cx_colsumsq's sums are):
+// s = fl(fl(x x) + fl(y y)), d = (fl(fl(omega x) + fl(0 y)) / s, fl(fl(0 x) - fl(omega y)) / s).
+__device__ __forceinline__ d2_t cx_jac_div(double omega, d2_t a) {
+#pragma clang fp contract(off)
+  const double xx = a.x * a.x;
+  const double yy = a.y * a.y;
+  const double s = xx + yy;
+  const double ox = omega * a.x;
+  const double zy = 0.0 * a.y;
+  const double zx = 0.0 * a.x;
+  const double oy = omega * a.y;
+  const double nr = ox + zy;
+  const double ni = zx - oy;
+  return d2_t{nr / s, ni / s};
+}
 template <typename AV, typename DV>
 __global__ __launch_bounds__(BLK) void cx_relax_jacobi(CxCsr32<AV> A, int n, double omega, DV* __restrict__ d) {
   const int i = blockIdx.x * BLK + threadIdx.x;
   if (i >= n) return;
-  cx_store_as(d + i, cdiv(d2_t{omega, 0.0}, cx_diag(A, i)));
+  cx_store_as(d + i, cx_jac_div(omega, cx_diag(A, i)));
 }
 // s_j = sum over the entries of COLUMN j of re^2 + im^2 in ascending row order (getSPAIprec, MGsetup.jl:359-362: row j of AT):
 // squares rounded, then summed, as colsumsq_kernel does - no atomics, the same bits on every run and as the host's bincount.

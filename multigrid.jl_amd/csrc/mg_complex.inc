@@ -71,6 +71,7 @@ struct CxMat {
   long long n_rows = 0, n_cols = 0, nnz = 0;
   int nblocks = 0;
   long long max_row = 0;        // the longest row (sizes the accumulator of cx_rap_numeric)
+  bool rows_sorted = true;      // every row's stored columns ascend (cx_upload): what cx_rap_numeric needs of a coarse operator's pattern
   DevBuf<int> rowptr, colidx, blk_row;
   DevBuf<long long> rowptr64;   // wide: >= 2^31 - 4096 non-zeros (or the option force_rowptr64)
   DevBuf<double> val;           // nnz real values, or 2*nnz interleaved (re, im)
@@ -279,7 +280,12 @@ int cx_upload(CxMat* M, const Options& opt, long long n_rows, long long n_cols, 
   M->nnz = nnz;
   M->nblocks = (int)blk.size() - 1;
   M->max_row = 0;
-  for (long long i = 0; i < n_rows; ++i) M->max_row = std::max(M->max_row, rp[(size_t)i + 1] - rp[(size_t)i]);
+  M->rows_sorted = true;
+  for (long long i = 0; i < n_rows; ++i) {
+    M->max_row = std::max(M->max_row, rp[(size_t)i + 1] - rp[(size_t)i]);
+    for (long long k = rp[(size_t)i] + 1; k < rp[(size_t)i + 1] && M->rows_sorted; ++k)
+      if (ci[(size_t)k] < ci[(size_t)k - 1]) M->rows_sorted = false;
+  }
   if (M->wide) {
     MG_TRY(M->rowptr64.alloc(rp.size()));
     HIP_TRY(hipMemcpy(M->rowptr64.p, rp.data(), rp.size() * sizeof(long long), hipMemcpyHostToDevice));
@@ -2724,6 +2730,9 @@ int cx_rap(mg_hierarchy* h, const typename mgk::cx_scalar<C>::type* fine_nzval, 
     if (L.A.wide || (l + 1 < nl && (L.P.wide || L.R.wide)))
       return fail(MG_ERR_UNSUPPORTED, "level %d holds an operator with 64-bit row pointers: the numeric Galerkin product on the device serves int32 operators", l + 1);
   }
+  for (int l = 1; l < nl; ++l)
+    if (!S.lev[(size_t)l].A.rows_sorted)
+      return fail(MG_ERR_UNSUPPORTED, "As[%d] holds a row whose stored columns do not ascend: the numeric Galerkin product on the device finds its target columns by binary search (sort the rows, or take the host path)", l + 1);
   const bool dev_inverse = h->opt.coarse_device_inverse && S.coarse_set && !S.coarse_lu && !S.coarse_gmres && !h->coarse_dd && S.Ainv.p;
   if (dev_inverse) MG_TRY(cx_coarse_inverse_check(h));
   if (S.single && S.coarse_gmres && (!S.cgA.set || S.cgA.nnz != S.lev[(size_t)nl - 1].A.nnz))

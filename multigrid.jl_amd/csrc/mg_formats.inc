@@ -1941,6 +1941,10 @@ int upload_csr_wide(Csr* M, const Options& opt, long long n_rows, long long n_co
     r = e;
   }
   for (long long i = 0; i < n_rows; ++i) M->max_row_nnz = (int)std::min<long long>(0x7fffffff, std::max<long long>(M->max_row_nnz, rp[(size_t)i + 1] - rp[(size_t)i]));
+  M->rows_sorted = true;
+  for (long long i = 0; i < n_rows && M->rows_sorted; ++i)
+    for (long long k = rp[(size_t)i] + 1; k < rp[(size_t)i + 1] && M->rows_sorted; ++k)
+      if (rowval[k] < rowval[k - 1]) M->rows_sorted = false;
   M->nblocks = (int)blk.size() - 1;
   M->nblocks_mm = 0;
   MG_TRY(M->rowptr64.alloc(rp.size()));
@@ -2022,7 +2026,12 @@ int upload_csr(Csr* M, const Options& opt, long long n_rows, long long n_cols, c
   HIP_TRY(hipMemcpy(M->blk_row.p, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice));
   M->h_blk_row = blk;
   M->max_row_nnz = 0;
-  for (long long i = 0; i < n_rows; ++i) M->max_row_nnz = std::max(M->max_row_nnz, rp[(size_t)i + 1] - rp[(size_t)i]);
+  M->rows_sorted = true;
+  for (long long i = 0; i < n_rows; ++i) {
+    M->max_row_nnz = std::max(M->max_row_nnz, rp[(size_t)i + 1] - rp[(size_t)i]);
+    for (int k = rp[(size_t)i] + 1; k < rp[(size_t)i + 1] && M->rows_sorted; ++k)
+      if (ci[(size_t)k] < ci[(size_t)k - 1]) M->rows_sorted = false;
+  }
   M->nblocks_mm = (int)blk_mm.size() - 1;
   MG_TRY(M->blk_row_mm.alloc(blk_mm.size()));
   HIP_TRY(hipMemcpy(M->blk_row_mm.p, blk_mm.data(), blk_mm.size() * sizeof(int), hipMemcpyHostToDevice));

@@ -392,6 +392,7 @@ struct Csr {
   std::vector<int> h_rp, h_ci;  // host pattern, kept only while has_rc (to re-derive the classes for new values)
   std::vector<int> h_blk_row;  // host copy of the row-block boundaries (for building schedules)
   int max_row_nnz = 0;
+  bool rows_sorted = true;   // every row's stored columns ascend (upload_csr): what rap_numeric needs of a coarse operator's pattern
   bool has_sched = false;
   int nblocks = 0;
   bool nt = false;  // non-temporal loads of the matrix stream (mg_kernels.hpp load_stream)
