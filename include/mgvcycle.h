@@ -505,6 +505,28 @@ int mg_kaczmarz_apply_CFP64(mg_kaczmarz* k, double* x, const double* b, long lon
                             long long sequential);
 int mg_kaczmarz_apply_dev_CFP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
                                 long long sequential);
+/* Float32 / ComplexF32 values (applyHybridKaczmarz_FP32_INT64 / _CFP32_INT64; the ccalls of parRelax.jl:61-79 for a single
+ * VAL), the same arguments with valA, invD, x and b in float (interleaved (re, im) for CFP32); valA = AT.nzval.  The
+ * arithmetic mixes precisions as the reference's single builds do (parRelax.h:27 calls the double-complex conj()): per
+ * listed row, inner -= conj(valA_k) x_k widens both operands to double, forms the product and the difference in double
+ * and rounds inner back to single after every term; inner *= invD_i and x_k += inner * valA_k are single arithmetic, every
+ * product and sum rounded to float (C99's plain complex product).  sequential = 1 is bit-identical to the reference binary
+ * with numCores = 1.  x moves through L2 one value per access (4 bytes, or one 8-byte access for a CFP32 pair, which
+ * therefore cannot tear between racing sub-domains); the _dev forms return MG_ERR_INVALID for an x_dev or b_dev that is not
+ * aligned to one value.  Any apply entry called on a handle of another value type fails with MG_ERR_STATE and leaves the
+ * handle usable.  Validation, limits and the no-GPU error are those of mg_kaczmarz_create_FP64_INT64. */
+int mg_kaczmarz_create_FP32_INT64(long long device_id, long long n, const long long* rowptr, const float* valA,
+                                  const long long* colA, long long numDomains, long long domainLength,
+                                  const unsigned int* ArrIdxs, const float* invD, mg_kaczmarz** out);
+int mg_kaczmarz_apply_FP32(mg_kaczmarz* k, float* x, const float* b, long long nrhs, long long numit, long long sequential);
+int mg_kaczmarz_apply_dev_FP32(mg_kaczmarz* k, float* x_dev, const float* b_dev, long long nrhs, long long numit,
+                               long long sequential);
+int mg_kaczmarz_create_CFP32_INT64(long long device_id, long long n, const long long* rowptr, const float* valA,
+                                   const long long* colA, long long numDomains, long long domainLength,
+                                   const unsigned int* ArrIdxs, const float* invD, mg_kaczmarz** out);
+int mg_kaczmarz_apply_CFP32(mg_kaczmarz* k, float* x, const float* b, long long nrhs, long long numit, long long sequential);
+int mg_kaczmarz_apply_dev_CFP32(mg_kaczmarz* k, float* x_dev, const float* b_dev, long long nrhs, long long numit,
+                                long long sequential);
 int mg_kaczmarz_destroy(mg_kaczmarz* k);
 
 /* ---- stand-alone sparse-factor applier -----------------------------------------------------------------------------

@@ -2178,21 +2178,26 @@ int mg_vec_sumsq_dev_FP64(const double* x, long long len, double* workspace, dou
 }
 
 // ---- hybrid Kaczmarz relaxation (deps/src/parRelax.h:7-43) -------------------------------------------------------------
+// The four value types of the reference's parRelax.c; a value is kz_bytes[vt] bytes (complex: interleaved re, im).
+enum KzType { KZ_FP64 = 0, KZ_CFP64 = 1, KZ_FP32 = 2, KZ_CFP32 = 3 };
+static const size_t kz_bytes[4] = {sizeof(double), 2 * sizeof(double), sizeof(float), 2 * sizeof(float)};
+static const char* const kz_name[4] = {"FP64", "CFP64", "FP32", "CFP32"};
+
 struct mg_kaczmarz {
   int device = 0;
-  bool cx = false;   // value type: false = FP64, true = CFP64 (val, invD, x, b hold interleaved complex doubles)
+  KzType vt = KZ_FP64;   // value type of val, invD, x and b, fixed at creation
   long long n = 0, nnz = 0, num_domains = 0, domain_length = 0;
   DevBuf<int> rowptr, col;
-  DevBuf<double> val, invD, x, b;
+  DevBuf<unsigned char> val, invD, x, b;   // sized in bytes: kz_bytes[vt] per value
   DevBuf<unsigned int> arr;
   hipStream_t stream = nullptr;
 };
 
-// Both value types: vw = doubles per value (1 FP64, 2 CFP64); valA and invD hold nnz and n values of vw doubles.
-static int kaczmarz_create(bool cx, long long device_id, long long n, const long long* rowptr, const double* valA,
+// Every value type: valA and invD hold nnz and n values of kz_bytes[vt] bytes.
+static int kaczmarz_create(KzType vt, long long device_id, long long n, const long long* rowptr, const void* valA,
                            const long long* colA, long long numDomains, long long domainLength,
-                           const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out) {
-  const size_t vw = cx ? 2 : 1;
+                           const unsigned int* ArrIdxs, const void* invD, mg_kaczmarz** out) {
+  const size_t vb = kz_bytes[vt];
   UploadFence upload_fence;
   if (!out) return fail(MG_ERR_INVALID, "out is null");
   *out = nullptr;
@@ -2222,7 +2227,7 @@ static int kaczmarz_create(bool cx, long long device_id, long long n, const long
   HIP_TRY(hipSetDevice((int)device_id));
   mg_kaczmarz* k = new mg_kaczmarz();
   k->device = (int)device_id;
-  k->cx = cx;
+  k->vt = vt;
   k->n = n;
   k->nnz = nnz;
   k->num_domains = numDomains;
@@ -2231,13 +2236,13 @@ static int kaczmarz_create(bool cx, long long device_id, long long n, const long
   auto up = [&]() -> int {
     MG_TRY(k->rowptr.alloc(rp.size()));
     MG_TRY(k->col.alloc(ci.size()));
-    MG_TRY(k->val.alloc(vw * (size_t)std::max<long long>(nnz, 1)));
-    MG_TRY(k->invD.alloc(vw * (size_t)n));
+    MG_TRY(k->val.alloc(vb * (size_t)std::max<long long>(nnz, 1)));
+    MG_TRY(k->invD.alloc(vb * (size_t)n));
     MG_TRY(k->arr.alloc((size_t)(numDomains * domainLength)));
     HIP_TRY(hipMemcpy(k->rowptr.p, rp.data(), rp.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k->col.p, ci.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(k->val.p, valA, vw * (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(k->invD.p, invD, vw * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k->val.p, valA, vb * (size_t)nnz, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(k->invD.p, invD, vb * (size_t)n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k->arr.p, ArrIdxs, (size_t)(numDomains * domainLength) * sizeof(unsigned int), hipMemcpyHostToDevice));
     HIP_TRY(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking));
     return MG_OK;
@@ -2254,14 +2259,26 @@ static int kaczmarz_create(bool cx, long long device_id, long long n, const long
 int mg_kaczmarz_create_FP64_INT64(long long device_id, long long n, const long long* rowptr, const double* valA,
                                   const long long* colA, long long numDomains, long long domainLength,
                                   const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out) {
-  return kaczmarz_create(false, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
+  return kaczmarz_create(KZ_FP64, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
 }
 
 // valA = nzval of the CSC of the reference's AT = A^H (conj of A's CSR values), invD complex: interleaved (re, im) doubles
 int mg_kaczmarz_create_CFP64_INT64(long long device_id, long long n, const long long* rowptr, const double* valA,
                                    const long long* colA, long long numDomains, long long domainLength,
                                    const unsigned int* ArrIdxs, const double* invD, mg_kaczmarz** out) {
-  return kaczmarz_create(true, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
+  return kaczmarz_create(KZ_CFP64, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
+}
+
+// The single forms (applyHybridKaczmarz_FP32_INT64 / _CFP32_INT64): valA = AT.nzval and invD in float, interleaved for CFP32
+int mg_kaczmarz_create_FP32_INT64(long long device_id, long long n, const long long* rowptr, const float* valA,
+                                  const long long* colA, long long numDomains, long long domainLength,
+                                  const unsigned int* ArrIdxs, const float* invD, mg_kaczmarz** out) {
+  return kaczmarz_create(KZ_FP32, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
+}
+int mg_kaczmarz_create_CFP32_INT64(long long device_id, long long n, const long long* rowptr, const float* valA,
+                                   const long long* colA, long long numDomains, long long domainLength,
+                                   const unsigned int* ArrIdxs, const float* invD, mg_kaczmarz** out) {
+  return kaczmarz_create(KZ_CFP32, device_id, n, rowptr, valA, colA, numDomains, domainLength, ArrIdxs, invD, out);
 }
 
 int mg_kaczmarz_destroy(mg_kaczmarz* k) {
@@ -2282,68 +2299,107 @@ int mg_kaczmarz_destroy(mg_kaczmarz* k) {
   return MG_OK;
 }
 
-// The arguments of an apply and the handle's value type (cx: the entry point's)
-static int kaczmarz_args(bool cx, mg_kaczmarz* k, const double* x, const double* b, long long nrhs, long long numit) {
+// The arguments of an apply and the handle's value type (vt: the entry point's)
+static int kaczmarz_args(KzType vt, mg_kaczmarz* k, const void* x, const void* b, long long nrhs, long long numit) {
   if (!k || !x || !b || nrhs < 1 || numit < 0) return fail(MG_ERR_INVALID, "bad argument");
-  if (k->cx != cx)
-    return fail(MG_ERR_STATE, "%s", cx ? "CFP64 Kaczmarz entry point called on an FP64 handle (mg_kaczmarz_create_CFP64_INT64)"
-                                       : "FP64 Kaczmarz entry point called on a CFP64 handle (mg_kaczmarz_apply*_CFP64)");
+  if (k->vt != vt) {
+    if (vt == KZ_CFP64 && k->vt == KZ_FP64)
+      return fail(MG_ERR_STATE, "CFP64 Kaczmarz entry point called on an FP64 handle (mg_kaczmarz_create_CFP64_INT64)");
+    if (vt == KZ_FP64 && k->vt == KZ_CFP64)
+      return fail(MG_ERR_STATE, "FP64 Kaczmarz entry point called on a CFP64 handle (mg_kaczmarz_apply*_CFP64)");
+    return fail(MG_ERR_STATE, "%s Kaczmarz entry point called on a %s handle (mg_kaczmarz_apply*_%s)", kz_name[vt], kz_name[k->vt],
+                kz_name[k->vt]);
+  }
   (void)hipSetDevice(k->device);
   return MG_OK;
 }
 
-// numit sweeps on device-resident x (in/out) and b, column-major n x nrhs (cx: complex, interleaved); one launch per sweep
+// one sweep of a single handle: S = float or mgk::f2_t
+#define KACZMARZ_LAUNCH_SINGLE(S)                                                                                              \
+  hipLaunchKernelGGL(mgk::hybrid_kaczmarz_s<S>, grid, dim3(64), 0, k->stream, k->rowptr.p, k->col.p,                           \
+                     reinterpret_cast<const S*>(k->val.p), k->arr.p, (int)k->num_domains, (int)k->domain_length,               \
+                     static_cast<S*>(x_dev), static_cast<const S*>(b_dev), (int)nrhs, k->n,                                    \
+                     reinterpret_cast<const S*>(k->invD.p), sequential ? 1 : 0)
+
+// numit sweeps on device-resident x (in/out) and b, column-major n x nrhs (complex: interleaved); one launch per sweep
 // (the barrier the reference's `omp for` has between sweeps).  sequential != 0: one wavefront walks all sub-domains in
-// order (the reference with one thread); otherwise one wavefront per sub-domain.
-static int kaczmarz_apply_dev(bool cx, mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
+// order (the reference with one thread); otherwise one wavefront per sub-domain.  The single kernels move a value in one
+// access: x and b must be aligned to it.
+static int kaczmarz_apply_dev(KzType vt, mg_kaczmarz* k, void* x_dev, const void* b_dev, long long nrhs, long long numit,
                               long long sequential) {
-  MG_TRY(kaczmarz_args(cx, k, x_dev, b_dev, nrhs, numit));
+  MG_TRY(kaczmarz_args(vt, k, x_dev, b_dev, nrhs, numit));
+  if ((vt == KZ_FP32 || vt == KZ_CFP32) &&
+      (reinterpret_cast<uintptr_t>(x_dev) % kz_bytes[vt] != 0 || reinterpret_cast<uintptr_t>(b_dev) % kz_bytes[vt] != 0))
+    return fail(MG_ERR_INVALID, "x_dev and b_dev must be aligned to %zu bytes (one %s value)", kz_bytes[vt], kz_name[vt]);
   const dim3 grid(sequential ? 1u : (unsigned)k->num_domains);
   for (long long it = 0; it < numit; ++it) {
-    if (cx)
+    if (vt == KZ_CFP64)
       hipLaunchKernelGGL(mgk::hybrid_kaczmarz_c, grid, dim3(64), 0, k->stream, k->rowptr.p, k->col.p,
-                         reinterpret_cast<const mgk::d2_t*>(k->val.p), k->arr.p, (int)k->num_domains, (int)k->domain_length, x_dev,
-                         b_dev, (int)nrhs, k->n, reinterpret_cast<const mgk::d2_t*>(k->invD.p), sequential ? 1 : 0);
+                         reinterpret_cast<const mgk::d2_t*>(k->val.p), k->arr.p, (int)k->num_domains, (int)k->domain_length,
+                         static_cast<double*>(x_dev), static_cast<const double*>(b_dev), (int)nrhs, k->n,
+                         reinterpret_cast<const mgk::d2_t*>(k->invD.p), sequential ? 1 : 0);
+    else if (vt == KZ_FP64)
+      hipLaunchKernelGGL(mgk::hybrid_kaczmarz, grid, dim3(64), 0, k->stream, k->rowptr.p, k->col.p,
+                         reinterpret_cast<const double*>(k->val.p), k->arr.p, (int)k->num_domains, (int)k->domain_length,
+                         static_cast<double*>(x_dev), static_cast<const double*>(b_dev), (int)nrhs, k->n,
+                         reinterpret_cast<const double*>(k->invD.p), sequential ? 1 : 0);
+    else if (vt == KZ_CFP32)
+      KACZMARZ_LAUNCH_SINGLE(mgk::f2_t);
     else
-      hipLaunchKernelGGL(mgk::hybrid_kaczmarz, grid, dim3(64), 0, k->stream, k->rowptr.p, k->col.p, k->val.p, k->arr.p,
-                         (int)k->num_domains, (int)k->domain_length, x_dev, b_dev, (int)nrhs, k->n, k->invD.p, sequential ? 1 : 0);
+      KACZMARZ_LAUNCH_SINGLE(float);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(spin_sync(k->stream));
   return MG_OK;
 }
+#undef KACZMARZ_LAUNCH_SINGLE
 
 // Host buffers, exactly the reference's call (parRelax.jl:61-64 / 71-74): x (in/out) and b are n x nrhs column-major.
-static int kaczmarz_apply_host(bool cx, mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit,
+static int kaczmarz_apply_host(KzType vt, mg_kaczmarz* k, void* x, const void* b, long long nrhs, long long numit,
                                long long sequential) {
-  MG_TRY(kaczmarz_args(cx, k, x, b, nrhs, numit));
-  const size_t len = (cx ? 2 : 1) * (size_t)k->n * (size_t)nrhs;   // doubles
+  MG_TRY(kaczmarz_args(vt, k, x, b, nrhs, numit));
+  const size_t len = kz_bytes[vt] * (size_t)k->n * (size_t)nrhs;   // bytes
   if (k->x.n != len) {
     MG_TRY(k->x.alloc(len));
     MG_TRY(k->b.alloc(len));
   }
-  HIP_TRY(hipMemcpyAsync(k->x.p, x, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
-  HIP_TRY(hipMemcpyAsync(k->b.p, b, len * sizeof(double), hipMemcpyHostToDevice, k->stream));
-  MG_TRY(kaczmarz_apply_dev(cx, k, k->x.p, k->b.p, nrhs, numit, sequential));
-  HIP_TRY(hipMemcpyAsync(x, k->x.p, len * sizeof(double), hipMemcpyDeviceToHost, k->stream));
+  HIP_TRY(hipMemcpyAsync(k->x.p, x, len, hipMemcpyHostToDevice, k->stream));
+  HIP_TRY(hipMemcpyAsync(k->b.p, b, len, hipMemcpyHostToDevice, k->stream));
+  MG_TRY(kaczmarz_apply_dev(vt, k, k->x.p, k->b.p, nrhs, numit, sequential));
+  HIP_TRY(hipMemcpyAsync(x, k->x.p, len, hipMemcpyDeviceToHost, k->stream));
   HIP_TRY(spin_sync(k->stream));
   return MG_OK;
 }
 
 int mg_kaczmarz_apply_dev_FP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
                                long long sequential) {
-  return kaczmarz_apply_dev(false, k, x_dev, b_dev, nrhs, numit, sequential);
+  return kaczmarz_apply_dev(KZ_FP64, k, x_dev, b_dev, nrhs, numit, sequential);
 }
 int mg_kaczmarz_apply_FP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit, long long sequential) {
-  return kaczmarz_apply_host(false, k, x, b, nrhs, numit, sequential);
+  return kaczmarz_apply_host(KZ_FP64, k, x, b, nrhs, numit, sequential);
 }
 // The complex sweeps (applyHybridKaczmarz_CFP64_INT64): x and b interleaved complex
 int mg_kaczmarz_apply_dev_CFP64(mg_kaczmarz* k, double* x_dev, const double* b_dev, long long nrhs, long long numit,
                                 long long sequential) {
-  return kaczmarz_apply_dev(true, k, x_dev, b_dev, nrhs, numit, sequential);
+  return kaczmarz_apply_dev(KZ_CFP64, k, x_dev, b_dev, nrhs, numit, sequential);
 }
 int mg_kaczmarz_apply_CFP64(mg_kaczmarz* k, double* x, const double* b, long long nrhs, long long numit, long long sequential) {
-  return kaczmarz_apply_host(true, k, x, b, nrhs, numit, sequential);
+  return kaczmarz_apply_host(KZ_CFP64, k, x, b, nrhs, numit, sequential);
+}
+// The single sweeps (applyHybridKaczmarz_FP32_INT64 / _CFP32_INT64): x and b in float, interleaved for CFP32
+int mg_kaczmarz_apply_dev_FP32(mg_kaczmarz* k, float* x_dev, const float* b_dev, long long nrhs, long long numit,
+                               long long sequential) {
+  return kaczmarz_apply_dev(KZ_FP32, k, x_dev, b_dev, nrhs, numit, sequential);
+}
+int mg_kaczmarz_apply_FP32(mg_kaczmarz* k, float* x, const float* b, long long nrhs, long long numit, long long sequential) {
+  return kaczmarz_apply_host(KZ_FP32, k, x, b, nrhs, numit, sequential);
+}
+int mg_kaczmarz_apply_dev_CFP32(mg_kaczmarz* k, float* x_dev, const float* b_dev, long long nrhs, long long numit,
+                                long long sequential) {
+  return kaczmarz_apply_dev(KZ_CFP32, k, x_dev, b_dev, nrhs, numit, sequential);
+}
+int mg_kaczmarz_apply_CFP32(mg_kaczmarz* k, float* x, const float* b, long long nrhs, long long numit, long long sequential) {
+  return kaczmarz_apply_host(KZ_CFP32, k, x, b, nrhs, numit, sequential);
 }
 
 // Run the hierarchy's kernels on the caller's stream (e.g. torch's current stream) instead of its own.

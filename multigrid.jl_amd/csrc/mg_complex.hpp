@@ -1,6 +1,6 @@
 // mg_complex.hpp - gfx950 kernels of the ComplexF64 (CF64) cycle and of its single-precision form (CF32: the same kernels on
 // float pairs, see f2_t below): generic CSR only; the conjugate transpose of an operator in HBM (cx_adj_*: adjointHierarchy); complex
-// hybrid Kaczmarz; the chip-wide complex triangular solve of the factor applier (cx_sptrsv_*, cx_tri_*, at the end).
+// hybrid Kaczmarz and the Float32 / ComplexF32 one (hybrid_kaczmarz_s); the chip-wide complex triangular solve of the factor applier (cx_sptrsv_*, cx_tri_*, at the end).
 //
 // Complex values are interleaved (re, im) doubles - Julia ComplexF64, numpy complex128, hipDoubleComplex - and are
 // loaded as one 16-byte d2_t.  The operator A of a CF64 handle is stored conjugated at upload (nzval of the
@@ -1108,6 +1108,95 @@ __global__ __launch_bounds__(64) void hybrid_kaczmarz_c(const int* __restrict__ 
           const d2_t upd = kz_cmul(inner.x, inner.y, v.x, v.y);
           kz_store(xp, oldr + upd.x);
           kz_store(xp + 1, oldi + upd.y);
+        }
+        // the next row of this wavefront must see these stores: wait until L2 has acknowledged them
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Single hybrid Kaczmarz relaxation (applyHybridKaczmarz_FP32_INT64 / _CFP32_INT64: deps/src/parRelax.h:7-43 built with
+// spValType = float / float complex), written once over the STORED type S = float or f2_t.  The schedule is that of
+// hybrid_kaczmarz_c above.  The arithmetic mixes precisions per statement, because the reference's does: parRelax.h:27
+// calls conj(), the DOUBLE complex function of <complex.h>, so in the single builds
+//   inner -= conj(val_k) * x_k   widens val_k and x_k to double, forms the product in double (real: exact; complex: the plain
+//                                formula, each part's sum rounded once to double), subtracts it from the widened inner in
+//                                double and rounds inner back to single AFTER EVERY TERM (per part for complex);
+//   inner *= invD_i ;  x_k += inner * val_k   stay in single: the plain complex formula, every product and sum rounded to float.
+// The lanes form the double products in parallel; the subtraction chain runs over the shuffled products in stored order with
+// the rounding to single after each term, so the sequential schedule equals the reference binary run with one thread bit for
+// bit.  x is read and written through L2 with relaxed agent-scope atomics (L1 bypassed), one access per value: 4 bytes for
+// float and ONE 8-byte access for a ComplexF32 pair, so - unlike the ComplexF64 kernel's two 8-byte halves - a pair read by a
+// racing sub-domain always comes whole from one update (it cannot tear).  x must be aligned to sizeof(S).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float kzs_load(float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ f2_t kzs_load(f2_t* p) {
+  const unsigned long long u = __hip_atomic_load(reinterpret_cast<unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return __builtin_bit_cast(f2_t, u);
+}
+__device__ __forceinline__ void kzs_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void kzs_store(f2_t* p, f2_t v) {
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+// conj(val) * x in double on the widened operands
+__device__ __forceinline__ double kzs_prod(float v, float x) {
+#pragma clang fp contract(off)
+  return (double)v * (double)x;
+}
+__device__ __forceinline__ d2_t kzs_prod(f2_t v, f2_t x) { return kz_cmul((double)v.x, -(double)v.y, (double)x.x, (double)x.y); }
+// inner = (S)((double)inner - lane t's product)
+__device__ __forceinline__ float kzs_sub(float inner, double prod, int t) {
+#pragma clang fp contract(off)
+  return (float)((double)inner - __shfl(prod, t));
+}
+__device__ __forceinline__ f2_t kzs_sub(f2_t inner, d2_t prod, int t) {
+#pragma clang fp contract(off)
+  return f2_t{(float)((double)inner.x - __shfl(prod.x, t)), (float)((double)inner.y - __shfl(prod.y, t))};
+}
+// the single product: every operation rounded to float
+__device__ __forceinline__ float kzs_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ f2_t kzs_mul(f2_t a, f2_t b) {
+#pragma clang fp contract(off)
+  return f2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
+}
+
+template <typename S>
+__global__ __launch_bounds__(64) void hybrid_kaczmarz_s(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                        const S* __restrict__ val, const unsigned int* __restrict__ arr,
+                                                        int num_domains, int domain_length, S* x, const S* __restrict__ b,
+                                                        int nrhs, long long n, const S* __restrict__ invD, int sequential) {
+#pragma clang fp contract(off)   // every product and sum rounded separately, as in the reference's plain C (no FMA)
+  const int lane = threadIdx.x;
+  const int d0 = sequential ? 0 : blockIdx.x, d1 = sequential ? num_domains : blockIdx.x + 1;
+  for (int dom = d0; dom < d1; ++dom) {
+    for (int i = 0; i < domain_length; ++i) {
+      const unsigned int row1 = arr[(size_t)dom * domain_length + i];
+      if (row1 == 0) continue;   // zero padding (wave-uniform)
+      const int row = (int)row1 - 1;
+      const int s = rowptr[row], e = rowptr[row + 1];
+      const S di = invD[row];
+      for (int c = 0; c < nrhs; ++c) {
+        S* xc = x + (size_t)c * n;
+        S inner = b[(size_t)c * n + row];
+        for (int k0 = s; k0 < e; k0 += 64) {
+          const int k = k0 + lane;
+          decltype(kzs_prod(S{}, S{})) prod{};
+          if (k < e) prod = kzs_prod(val[k], kzs_load(xc + col[k]));
+          const int cnt = min(64, e - k0);
+          for (int t = 0; t < cnt; ++t) inner = kzs_sub(inner, prod, t);   // stored order, rounded to single after every term
+        }
+        inner = kzs_mul(inner, di);
+        for (int k = s + lane; k < e; k += 64) {
+          S* xp = xc + col[k];
+          const S old = kzs_load(xp);
+          const S upd = kzs_mul(inner, val[k]);
+          kzs_store(xp, old + upd);
         }
         // the next row of this wavefront must see these stores: wait until L2 has acknowledged them
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

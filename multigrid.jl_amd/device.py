@@ -174,6 +174,12 @@ SIGNATURES = {
     "mg_kaczmarz_create_CFP64_INT64": (C.c_int, [_ll, _ll, _lp, _dp, _lp, _ll, _ll, C.POINTER(C.c_uint), _dp, C.POINTER(_vp)]),
     "mg_kaczmarz_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll, _ll]),
     "mg_kaczmarz_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_kaczmarz_create_FP32_INT64": (C.c_int, [_ll, _ll, _lp, _fp, _lp, _ll, _ll, C.POINTER(C.c_uint), _fp, C.POINTER(_vp)]),
+    "mg_kaczmarz_apply_FP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, _ll]),
+    "mg_kaczmarz_apply_dev_FP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_kaczmarz_create_CFP32_INT64": (C.c_int, [_ll, _ll, _lp, _fp, _lp, _ll, _ll, C.POINTER(C.c_uint), _fp, C.POINTER(_vp)]),
+    "mg_kaczmarz_apply_CFP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, _ll]),
+    "mg_kaczmarz_apply_dev_CFP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
     "mg_kaczmarz_destroy": (C.c_int, [_vp]),
     "mg_set_vanka_FP64": (C.c_int, [_vp, _ll, _ll, _lp, _ll, _ll, C.POINTER(C.c_float)]),
     "mg_vanka_create_FP64_INT64": (C.c_int, [_ll, _ll, _lp, _ll, _ll, _lp, _lp, _dp, C.POINTER(C.c_float), C.POINTER(_vp)]),
