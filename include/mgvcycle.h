@@ -664,7 +664,7 @@ int mg_set_coarse_dd(mg_hierarchy* h, mg_dd* dd);
  * of its speculative solve, which do not - front, 10 steps, combination, on the path the handle takes now, see
  * mg_set_coarse_gmres_CF64).  MG_ERR_STATE when none is set. */
 int mg_coarse_form(mg_hierarchy* h, long long* info);
-/* info[0..6): value type (0 Float64, 1 ComplexF64); sub-domains; colours present; colours run batched; colours run in
+/* info[0..6): value type (0 Float64, 1 ComplexF64, 2 Float32, 3 ComplexF32 - the single kinds: see below); sub-domains; colours present; colours run batched; colours run in
  * sequence; kernel launches of one sweep (doTranspose = 0; a chip-wide member counts one launch per level it launches). */
 int mg_dd_info(mg_dd* dd, long long* info);
 /* Measurement, as mg_lu_time_dev: `warmup` untimed sweeps on device vectors of the handle's value type, then `reps` sweeps,
@@ -1073,6 +1073,52 @@ mg_status mg_set_coarse_lu_CF32_INT64(mg_hierarchy* h, long long n, const long l
                                       const float* Lval, const long long* Uptr, const long long* Ucol,
                                       const float* Uval, const long long* p, const long long* q);
 
+/* ---- Float32 / ComplexF32 Schwarz sweeps --------------------------------------------------------------------------------------
+ * The multiplicative Schwarz preconditioner (mg_dd_*, above) with VAL = Float32 / ComplexF32: DomainDecompositionParam{VAL,IND} is
+ * generic in VAL, computeResidualAtIdx and solveSubDomain run in VAL (DDSerial.jl:4-20, 183-187) and parallelJuliaSolver has the three
+ * single forms.  A handle records its value type with the factor applier's codes - 0 Float64, 1 ComplexF64, 2 Float32, 3 ComplexF32
+ * (mg_dd_info[0]) - and keeps the operator, the caller's factors, the packed arenas and the work vectors in float: half the HBM of a
+ * double handle, no double copy beside it.
+ * create: valA in float (interleaved (re, im) for CFP32), the CSR indices Int64 - the reference's AT is Int64-indexed whatever VAL is.
+ * set_factor: the three forms parLU has - (Float32, UInt32), (ComplexF32, UInt32), (ComplexF32, Int64): column indices and
+ * permutations in the index type of the name, row pointers Int64; there is no (Float32, Int64) form.  apply / dd0_apply: b and x in
+ * float, host pointers or HBM (_dev); mg_dd_finalize, mg_dd_info, mg_dd_time_dev (b_dev / x_dev then point to float data) and
+ * mg_dd_destroy serve every kind.  doTranspose: the transposed (CFP32: conjugate-transposed) single factors - moving a value or
+ * flipping a sign bit is exact.  A member of at least lu_multi_min_rows rows gets a single applier of its own (mg_lu_*_FP32 /
+ * _CFP32) and its colour runs in sequence, as for double handles.
+ * Arithmetic: the single factor applier's contract.  Values, factors, b, x, r and y are STORED in single; every residual row and every
+ * triangular row is EVALUATED in double - operands widened before each product, the sum in the order of the double kernels, one
+ * rounding to single on the store; x[I] += t is one single add.  A deliberate deviation from the reference, which sums in VAL.
+ * Every mg_dd_* entry point called on a handle of another kind fails with MG_ERR_STATE, names the entry points that serve the handle
+ * and leaves it usable.
+ * mg_set_coarse_dd accepts a ComplexF32 handle on a CF32 hierarchy (mg_create_CF32): the sweep runs from zero on the cycle's own
+ * complex64 coarsest vectors - no widened pair is allocated; mg_coarse_form reports 4.  Every other pairing of kinds is MG_ERR_STATE
+ * with both named; a ComplexF64 handle on a CF32 hierarchy stays MG_ERR_UNSUPPORTED.  Unchanged refusals for such a hierarchy: blocks
+ * (nrhs > 1), sharded forms, mg_adjoint_hierarchy_CF32, HIP graphs of its sub-cycles. */
+mg_status mg_dd_create_FP32_INT64(long long device_id, long long n, const long long* rowptr, const long long* colA,
+                                  const float* valA, long long numSub, const long long* idxptr, const unsigned int* idx,
+                                  const long long* color, mg_dd** out);
+mg_status mg_dd_create_CFP32_INT64(long long device_id, long long n, const long long* rowptr, const long long* colA,
+                                   const float* valA, long long numSub, const long long* idxptr, const unsigned int* idx,
+                                   const long long* color, mg_dd** out);
+mg_status mg_dd_set_factor_FP32_UINT32(mg_dd* dd, long long ic, long long n_i, const long long* Lptr, const unsigned int* Lcol,
+                                       const float* Lval, const long long* Uptr, const unsigned int* Ucol, const float* Uval,
+                                       const unsigned int* p, const unsigned int* q);
+mg_status mg_dd_set_factor_CFP32_UINT32(mg_dd* dd, long long ic, long long n_i, const long long* Lptr, const unsigned int* Lcol,
+                                        const float* Lval, const long long* Uptr, const unsigned int* Ucol, const float* Uval,
+                                        const unsigned int* p, const unsigned int* q);
+mg_status mg_dd_set_factor_CFP32_INT64(mg_dd* dd, long long ic, long long n_i, const long long* Lptr, const long long* Lcol,
+                                       const float* Lval, const long long* Uptr, const long long* Ucol, const float* Uval,
+                                       const long long* p, const long long* q);
+mg_status mg_dd_apply_FP32(mg_dd* dd, const float* b, float* x, long long n, long long niter, long long doTranspose);
+mg_status mg_dd_apply_dev_FP32(mg_dd* dd, const float* b_dev, float* x_dev, long long n, long long niter, long long doTranspose);
+mg_status mg_dd_apply_CFP32(mg_dd* dd, const float* b, float* x, long long n, long long niter, long long doTranspose);
+mg_status mg_dd_apply_dev_CFP32(mg_dd* dd, const float* b_dev, float* x_dev, long long n, long long niter, long long doTranspose);
+mg_status mg_dd0_apply_FP32(mg_dd* dd, const float* b, float* x, long long n, long long doTranspose);
+mg_status mg_dd0_apply_dev_FP32(mg_dd* dd, const float* b_dev, float* x_dev, long long n, long long doTranspose);
+mg_status mg_dd0_apply_CFP32(mg_dd* dd, const float* b, float* x, long long n, long long doTranspose);
+mg_status mg_dd0_apply_dev_CFP32(mg_dd* dd, const float* b_dev, float* x_dev, long long n, long long doTranspose);
+
 /* ---- The GMRES coarsest solve on a complex handle ----------------------------------------------------------------------------
  * coarseSolveType "GMRES" for complex handles (MGsetup.jl:335-336, MGcycle.jl:152-164): d = param.LU = relaxParam ./ diag(A_c), n
  * complex128 values for CF64 AND CF32 handles (as the other complex coarse setters); the coarsest solve is x .= 0 and ONE restart of
@@ -1331,7 +1377,7 @@ int mg_cblk_gram_dev_CFP64(const double* x_dev, const double* y_dev, long long n
  * Refusals.  A _CF32 entry point on a CF64 or FP64 handle, and mg_set_operator_CF64_INT64 / mg_set_relax_CF64 / mg_cycle_CF64 /
  * mg_solve_CF64 / mg_spmv_CF64 / mg_set_operator_FP64_INT64 on a CF32 handle: MG_ERR_STATE.  Not served for a CF32 handle
  * (MG_ERR_UNSUPPORTED): mg_rap_CF64, mg_rap_level_ms_CF64, mg_get_values_CF64, mg_get_relax_CF64, mg_replace_values_CF64 (their
- * _CF32 forms above serve it), mg_set_coarse_dd (a Schwarz coarsest solve), the K-cycle and Jac-GMRES (served with the option single_kcycle, see mg_set_schedule_CF32),
+ * _CF32 forms above serve it), mg_set_coarse_dd with a ComplexF64 sweep handle (a ComplexF32 one is served: "Float32 / ComplexF32 Schwarz sweeps"), the K-cycle and Jac-GMRES (served with the option single_kcycle, see mg_set_schedule_CF32),
  * nrhs > 1 in the entry points of this section (blocks: mg_block_cycle_dev_CFP64 and mg_block_bicgstab[_dev]_CFP64 below), and
  * whatever a CF64 handle does not serve. */
 int mg_create_CF32(long long nlevels, long long nrhs, long long device_id, mg_hierarchy** out);

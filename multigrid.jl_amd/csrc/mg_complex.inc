@@ -741,6 +741,7 @@ struct CxCols {
 // chip-wide for factors of >= lu_multi_min_rows rows), or one Schwarz sweep (MGcycle.jl:140-143; xzero: x need not be read), or one
 // restart of Jacobi-preconditioned FGMRES(10) from zero (cx_coarse_gmres: the only one that synchronises with the host, once)
 // nr >= 1: b and x are row-major blocks [n][nr] (the factor applier's own layout; the Schwarz sweep serves one column)
+int dd_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool x_zero);   // (mg_dd.inc: the sweep on a CF32 hierarchy's own coarsest vectors)
 int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr = 0) {
   CxState& S = *h->cx;
   const long long n = S.n_coarse;
@@ -779,8 +780,13 @@ int cx_coarse(mg_hierarchy* h, const cx_t* b, cx_t* x, bool xzero = true, int nr
 // MGsetup.jl:350; MGcycle.jl:177-178): bc is widened, solved by the kernels above, xc narrowed.  The GMRES coarsest solve too: it runs
 // in ComplexF64 on the widened copy of the coarsest operator (CxState::cgA).  The reference would run that fgmres in ComplexF32 - a
 // deliberate deviation of the order of the single unit roundoff: more accurate, and no float instantiation of the vector passes.
-int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool = true, int nr = 0) {
+int cx_coarse(mg_hierarchy* h, const cf_t* b, cf_t* x, bool xzero = true, int nr = 0) {
   CxState& S = *h->cx;
+  // a ComplexF32 Schwarz sweep (mg_set_coarse_dd admits no other kind here): on the cycle's own bc and xc, no widened pair
+  if (h->coarse_dd) {
+    if (nr > 1) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve serves one right-hand side (nrhs=%d)", nr);
+    return dd_coarse(h, b, x, xzero);
+  }
   // ComplexF32 factors (mg_set_coarse_lu_CF32_INT64): applied to the cycle's own bc, no widened pair
   if (S.coarse_single) return cxlu_solve_dev(S.coarse_single, *S.coarse_single->fwd, b, x, std::max(nr, 1), &h->play->stream);
   const CxCols W = CxCols::of(nr);
@@ -1158,7 +1164,7 @@ int cx_block_ensure(mg_hierarchy* h, int nr) {
   }
   const size_t n0 = 2 * (size_t)S.lev[0].n * k, nc = 2 * (size_t)S.n_coarse * k;
   for (DevBuf<double>* d : {&S.Bstage_b, &S.Bstage_x, &S.Bstage_t}) MG_TRY(d->alloc(n0));
-  if (S.single && !S.coarse_single) {   // (ComplexF32 factors are applied to the cycle's own block: no widened pair)
+  if (S.single && !S.coarse_single && !h->coarse_dd) {   // (ComplexF32 factors are applied to the cycle's own block: no widened pair)
     MG_TRY(S.Bcw_b.alloc(nc));
     MG_TRY(S.Bcw_x.alloc(nc));
   } else {
@@ -1251,7 +1257,6 @@ int cx_finalize(mg_hierarchy* h) {
   S.blk_cap = 0;   // (levels may have changed size: the block work set is sized again by the next block call)
   S.cb_cap = 0;
   const int nl = (int)h->nlevels;
-  if (S.single && h->coarse_dd) return fail(MG_ERR_UNSUPPORTED, "a Schwarz sweep as coarsest solve is not served for CF32 handles");
   if (S.K_auto) {   // As[1] may have changed since it was widened: the next driver call widens it again
     S.K.release();
     S.K_auto = false;
@@ -1312,11 +1317,11 @@ int cx_finalize(mg_hierarchy* h) {
   const size_t n0 = 2 * (size_t)S.lev[0].n;
   if (S.stage_b.n != n0) MG_TRY(S.stage_b.alloc(n0));
   if (S.partial.n < maxblocks) MG_TRY(S.partial.alloc(maxblocks));
-  if (S.single && !S.coarse_single) {
+  if (S.single && !S.coarse_single && !h->coarse_dd) {
     const size_t nc = 2 * (size_t)S.n_coarse;
     if (S.cw_b.n != nc) MG_TRY(S.cw_b.alloc(nc));
     if (S.cw_x.n != nc) MG_TRY(S.cw_x.alloc(nc));
-  } else {   // (a CF64 handle, or ComplexF32 factors applied to the cycle's own bc: no widened pair)
+  } else {   // (a CF64 handle, or ComplexF32 factors / a ComplexF32 Schwarz sweep applied to the cycle's own bc: no widened pair)
     S.cw_b.release();
     S.cw_x.release();
   }

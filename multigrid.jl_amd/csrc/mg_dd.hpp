@@ -4,7 +4,11 @@
 //   parallelJuliaSolver's x[q] = U \ (L \ r[p]), parLU.cpp:120-190),   x[I_i] += t   (l.129).
 // Sub-domains of one colour that touch no common entry of x are one launch (dd_color_sweep: one 1024-thread workgroup
 // per sub-domain, the three stages separated by workgroup barriers); otherwise the members run one after another
-// (dd_gather_residual, the factor applier's solve, dd_scatter_add).  T = double or the interleaved complex d2_t.
+// (dd_gather_residual, the factor applier's solve, dd_scatter_add).  T = double, the interleaved complex d2_t, or their
+// single twins float / f2_t.  A single handle STORES the operator, the factors, b, x, r and y in T and evaluates every
+// residual row and every triangular row in lu_acc<T> (double / d2_t), as the single factor applier does (mg_kernels.hpp,
+// sptrsv_sweep): operands widened on load - an f2_t moves as one 8-byte access -, the sum in the order of the double
+// forms, one rounding on the store; x[I] += t is one add in T.  For double / d2_t widening and rounding are the identity.
 #pragma once
 
 namespace mgk {
@@ -41,17 +45,17 @@ __device__ __forceinline__ void dd_residual_rows(const int* __restrict__ rowptr,
   const int part = threadIdx.x & 7;
   for (int t0 = first; t0 < n_i; t0 += step) {       // t0 is uniform over the eight lanes of a row
     const int row = I[t0];
-    T acc = T{};
-    for (int k = rowptr[row] + part, e = rowptr[row + 1]; k < e; k += 8) acc += lu_mul(val[k], x[col[k]]);
+    typename lu_acc<T>::type acc{};
+    for (int k = rowptr[row] + part, e = rowptr[row + 1]; k < e; k += 8) acc += lu_mul(lu_wide(val[k]), lu_wide(x[col[k]]));
     for (int o = 4; o > 0; o >>= 1) acc += lu_shfl_xor(acc, o);
-    if (part == 0) r[t0] = b[row] - acc;
+    if (part == 0) r[t0] = lu_round<T>(lu_wide(b[row]) - acc);
   }
 }
 
 // One launch per independent colour: workgroup g serves sub-domain members[m0 + g].
 template <typename T>
 __global__ __launch_bounds__(1024) void dd_color_sweep(DdDevT<T> D, int m0, const T* __restrict__ b, T* x) {
-  __shared__ T sred[16][4];
+  __shared__ typename lu_acc<T>::type sred[16][4];   // what sptrsv_sweep combines split rows through
   const DdSub S = D.sub[D.members[m0 + blockIdx.x]];
   const int* I = D.idx + S.vec0;
   T* r = D.r + S.vec0;

@@ -163,6 +163,19 @@ SIGNATURES = {
     "mg_dd0_apply_dev_FP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
     "mg_dd0_apply_CFP64": (C.c_int, [_vp, _dp, _dp, _ll, _ll]),
     "mg_dd0_apply_dev_CFP64": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_dd_create_FP32_INT64": (C.c_int, [_ll, _ll, _lp, _lp, _fp, _ll, _lp, C.POINTER(C.c_uint), _lp, C.POINTER(_vp)]),
+    "mg_dd_create_CFP32_INT64": (C.c_int, [_ll, _ll, _lp, _lp, _fp, _ll, _lp, C.POINTER(C.c_uint), _lp, C.POINTER(_vp)]),
+    "mg_dd_set_factor_FP32_UINT32": (C.c_int, [_vp, _ll, _ll, _lp, _up, _fp, _lp, _up, _fp, _up, _up]),
+    "mg_dd_set_factor_CFP32_UINT32": (C.c_int, [_vp, _ll, _ll, _lp, _up, _fp, _lp, _up, _fp, _up, _up]),
+    "mg_dd_set_factor_CFP32_INT64": (C.c_int, [_vp, _ll, _ll, _lp, _lp, _fp, _lp, _lp, _fp, _lp, _lp]),
+    "mg_dd_apply_FP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, _ll]),
+    "mg_dd_apply_dev_FP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_dd_apply_CFP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll, _ll]),
+    "mg_dd_apply_dev_CFP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll, _ll]),
+    "mg_dd0_apply_FP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll]),
+    "mg_dd0_apply_dev_FP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
+    "mg_dd0_apply_CFP32": (C.c_int, [_vp, _fp, _fp, _ll, _ll]),
+    "mg_dd0_apply_dev_CFP32": (C.c_int, [_vp, _vp, _vp, _ll, _ll]),
     "mg_set_coarse_dd": (C.c_int, [_vp, _vp]),
     "mg_coarse_form": (C.c_int, [_vp, _lp]),
     "mg_dd_info": (C.c_int, [_vp, _lp]),
@@ -639,8 +652,9 @@ class DeviceHierarchy:
             if self.nrhs != 1:
                 raise NotImplementedError("a DomainDecompositionParam as coarsest solver serves one right-hand side "
                                           "(the reference's sweep indexes b[Idxs])")
-            if np.dtype(param.VAL) == np.complex64:
-                raise NotImplementedError("a Schwarz coarsest solve is not served for ComplexF32 hierarchies")
+            if np.dtype(param.VAL) == np.complex64 and np.dtype(LU.VAL) != np.complex64:
+                raise NotImplementedError("a Schwarz coarsest solve is not served for ComplexF32 hierarchies "
+                                          "(a DomainDecompositionParam of ComplexF32, singleValues=True, is)")
             if np.dtype(LU.VAL) != np.dtype(param.VAL):
                 raise TypeError("param.LU holds %s values, the hierarchy %s" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
             h = DD._device_handle(LU, param.As[-1])

@@ -154,7 +154,9 @@ def defineCoarsestAinv(param: MGparam, Ac) -> None:
         LU = param.LU
         if not param.Meshes:
             raise ValueError("a DomainDecompositionParam as coarsest solver needs the coarsest mesh: the hierarchy has none (SA-AMG)")
-        if is_single(param):
+        # (a ComplexF32 hierarchy takes a ComplexF32 sweep - getDomainDecompositionParam(np.complex64, ..., singleValues=True) - set up
+        # on its complex64 coarsest operator; a ComplexF64 one stays unserved there)
+        if is_single(param) and np.dtype(LU.VAL) != np.complex64:
             raise NotImplementedError("a Schwarz coarsest solve is not served for ComplexF32 hierarchies (singlePrecision=True)")
         if np.dtype(LU.VAL) != np.dtype(param.VAL):
             raise TypeError("param.LU is a DomainDecompositionParam of %s, the hierarchy of %s" % (np.dtype(LU.VAL), np.dtype(param.VAL)))
